@@ -12,8 +12,15 @@ A u = b with Jacobi-preconditioned CG to rtol 1e-8 (the reference run
 216x206x222, 10 016 937 dofs, src/mesh.cpp:78-151).  Inputs (mesh, dofmap, Dirichlet set, nodal
 coefficients) are resident in HBM before the timed region.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times K steps and prints the JSON line (value, ms_per_step, the product's
+roofline from the timed steps).  --full adds what is measured beside the headline, after its timed region:
+the CPU baseline (the oracle on the host cores), one Chebyshev-Jacobi solve of the same system, and for the
+default 10 M-dof run the one-shot driver runs, the product on the full pattern and the other BASELINE
+configurations (other_configs).  --dump-outputs DIR writes what the last timed step computed as .npy files
+(dump_outputs below).
 
 For N > 1 the cube is cut into N z-slabs, one per GPU (strong scaling: the total problem is
 fixed); inside libzzz_hip the halo exchange runs on RCCL and the CG scalars are reduced through
@@ -516,11 +523,53 @@ def full_pattern_product(a, nx, ny, nz):
             "reference_format_over_peak": spmv_algorithmic_bytes(nrows, nnz) / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS}
 
 
+DUMP_SAMPLE = 1 << 20  # entries of a sampled array in --dump-outputs: 8 MB in float64
+
+
+def dump_outputs(ctx, outdir, iters, rel, unorm):
+    """--dump-outputs: what a caller of the timed path receives from its last step -- the solution u, the right-hand side b,
+    the assembled matrix A (caller's numbering) and the solve's scalars -- as float64 .npy files, so that two builds can be
+    compared output for output.  A vector or matrix longer than DUMP_SAMPLE entries is written as a sample: the same seeded
+    positions for the same arguments in every run, stored beside it (u_index, A_rows / A_cols).  48 MB in all at most."""
+    os.makedirs(outdir, exist_ok=True)
+
+    def positions(n, seed):
+        if n <= DUMP_SAMPLE:
+            return np.arange(n, dtype=np.int64)
+        return np.unique(np.random.default_rng(seed).integers(0, n, size=DUMP_SAMPLE, dtype=np.int64))
+
+    def save(name, arr):
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
+
+    save("solve", [iters, rel, unorm])  # Krylov iterations, relative residual, |u|
+    u, b = ctx.vec_download(zzz.VEC_U), ctx.vec_download(zzz.VEC_B)
+    iu = positions(u.size, 1)
+    save("u", u[iu])
+    save("b", b[iu])
+    save("u_index", iu)
+    del u, b
+    nrows, _, nnz = ctx.csr_sizes()
+    if nnz > 2**31 - 1:
+        # csr_download's row pointers are 32-bit (and the whole matrix would be tens of GB of host memory): u and b only
+        sys.stderr.write(f"bench.py: --dump-outputs: A ({nnz} nonzeros) not written\n")
+        return
+    rowptr, cols, vals = ctx.csr_download()
+    ia = positions(nnz, 2)
+    save("A_values", vals[ia])
+    save("A_rows", np.searchsorted(rowptr, ia, side="right") - 1)
+    save("A_cols", cols[ia])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what lies beside the headline (CPU baseline, Chebyshev-Jacobi solve, one-shot driver runs, "
+                         "full-pattern product, other BASELINE configurations); off: the headline alone")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (u, b, A, solve scalars; sampled when large) as DIR/<name>.npy")
     ap.add_argument("--config", default=None, choices=sorted(CONFIGS),
                     help="a BASELINE.json configuration as a one-GPU workload (default: c2 = the headline); sets "
                          "--problem_type/--order/--scaling_type/--ndofs")
@@ -545,10 +594,12 @@ def main():
                          "`ZZZ Solve` should not depend on this; ZZZ_RENUMBER=0 shows what the caller's order would cost")
     ap.add_argument("--only", default=None, help="run only this record of other_configs (c1, c4_total, c5_rank, c5_whole, "
                     "unstructured_p1, cgpoisson_p1_c2, cgpoisson_p3_c5rank) and print it")
-    ap.add_argument("--no_cpu_baseline", action="store_true")
-    ap.add_argument("--no_alt_pc", action="store_true", help="skip the Chebyshev-Jacobi solve beside the measurement")
+    ap.add_argument("--no_cpu_baseline", action="store_true",
+                    help="--full: skip the CPU baseline; every run: the feed is generated on the device instead of uploaded from "
+                         "host arrays (identical problem)")
+    ap.add_argument("--no_alt_pc", action="store_true", help="--full: skip the Chebyshev-Jacobi solve beside the measurement")
     ap.add_argument("--no_other_configs", action="store_true",
-                    help="default run only: skip the compact records beside the headline (c1, c4_total, c5_rank, c5 whole, "
+                    help="--full, default workload only: skip the compact records beside the headline (c1, c4_total, c5_rank, c5 whole, "
                          "cgpoisson P1 / P3, the product on the full pattern; after and outside the headline's timed region)")
     ap.add_argument("--force_dist", action="store_true",
                     help="N=1 only: take the whole N > 1 code path (gloo process group, unique-id broadcast, 1-rank RCCL "
@@ -559,6 +610,8 @@ def main():
                     help="KSPCG form: classical (PETSc default, two reductions per iteration) or "
                          "-ksp_cg_single_reduction (one); auto = classical on one GPU, single_reduction on N > 1")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if a.only:
         zzz.hip()
         rec = {"unstructured_p1": lambda: run_other_config(None, steps=2, unstructured=5000000),
@@ -595,7 +648,7 @@ def main():
     # driver's clearing of that memory inside whatever phase allocates first: 0.7 s under `ZZZ Assemble matrix`, measured) and
     # outside every timed region.
     one_shot = {}
-    if world == 1 and not multi and not a.force_comm and a.config is None and not a.no_other_configs \
+    if a.full and world == 1 and not multi and not a.force_comm and a.config is None and not a.no_other_configs \
             and (a.problem_type, a.order, a.ndofs) == ("poisson", 1, 10000000):
         for key, dargs in (("driver_one_shot", ["--problem_type", "poisson", "--order", "1", "--scaling_type", "strong", "--ndofs", "10000000",
                                                 "-ksp_type", "cg", "-pc_type", "jacobi", "-ksp_rtol", "1e-8"]),
@@ -642,8 +695,9 @@ def main():
     nx, ny, nz, r = zzz.mesh_size(a.ndofs, strong, a.mesh_nproc or world, bs, a.order)
     nx, ny, nz = nx << r, ny << r, nz << r
     form = zzz.FORM_ELASTICITY if a.problem_type == "elasticity" else zzz.FORM_POISSON
-    # host feed (C++ generator + upload) only when the CPU baseline needs the host arrays; otherwise the
-    # feed is generated on the device (zzz_cube_generate) -- identical problem, no PCIe traffic
+    # host feed (C++ generator + upload) unless --no_cpu_baseline, whether or not --full runs the CPU baseline that needs the
+    # host arrays (a plain run times the inputs a --full one does); otherwise the feed is generated on the device
+    # (zzz_cube_generate) -- identical problem, no PCIe traffic
     if a.numbering != "native":
         if multi:
             raise SystemExit("--numbering applies to single-GPU runs (the multi-GPU feed is generated on the device)")
@@ -858,6 +912,9 @@ def main():
                 dist.all_gather_object(rank_info, mine)
     ms_per_step = elapsed / a.steps * 1e3
     iters = phases[-1]["iters"]
+    if a.dump_outputs and rank == 0:
+        # before anything else touches u (--full's Chebyshev-Jacobi solve overwrites it); N > 1: rank 0's slab
+        dump_outputs(ctx, a.dump_outputs, iters, phases[-1]["rel"], unorm)
 
     out = None
     if rank == 0:
@@ -987,7 +1044,7 @@ def main():
                                         "chosen_by": ("--cg " + a.cg) if a.cg != "auto" else
                                                      ("warm-up tuning (fastest of %d combinations)" % len(tuning) if tuning else "default")}
         out["config"]["feed"] = "host arrays uploaded (zzz_*_upload)" if P is not None else "generated on the device (zzz_cube_generate)"
-        if not multi and not a.no_cpu_baseline:
+        if a.full and not multi and not a.no_cpu_baseline:
             if nnz > 2**31 - 1:
                 # the oracle's assembly takes the 32-bit row pointers of DOLFINx; a matrix beyond them (c5 whole: 2.4 G
                 # nonzeros, ~60 GB of host working copies) is not timed on the CPU -- said here rather than failing
@@ -1001,7 +1058,7 @@ def main():
     # beside the measurement (after it, untimed): the same assembled system solved once with the library's polynomial
     # preconditioner -- fewer iterations and all-reduces for more products, i.e. what the N > 1 runs are bound by
     alt_pc = None
-    if pc == zzz.PC_JACOBI and not a.no_alt_pc:
+    if a.full and pc == zzz.PC_JACOBI and not a.no_alt_pc:
         try:
             def line_without_it():
                 if rank == 0:
@@ -1033,7 +1090,7 @@ def main():
         if rank == 0:
             out["alt_preconditioner"] = alt_pc
     ctx.close()
-    if rank == 0 and not multi and not a.force_comm and a.config is None and not a.no_other_configs \
+    if a.full and rank == 0 and not multi and not a.force_comm and a.config is None and not a.no_other_configs \
             and (a.problem_type, a.order, a.ndofs) == ("poisson", 1, 10000000):
         # the other BASELINE configs, compactly, so that the driver's record (not only builder-run profiles) has them
         try:

@@ -166,7 +166,7 @@ def test_bench_contract_line():
     import sys
 
     root = os.path.dirname(zzz.PKG)
-    for extra in ([], ["--no_cpu_baseline", "--force_comm"]):
+    for extra in (["--full"], ["--no_cpu_baseline", "--force_comm"]):
         out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--ndofs", "40000", "--steps", "1",
                               "--warmup", "0"] + extra, capture_output=True, text=True, timeout=600)
         assert out.returncode == 0, out.stderr[-2000:]
@@ -185,14 +185,14 @@ def test_bench_contract_line():
         # the scalar copies the driver's parser keeps (round 5): the same numbers as the nested records
         assert r["iteration_frac"] == it["frac"] and r["iteration_us"] > 0
         assert ("full_pattern" in r) == ("full_pattern_frac" in r)
-        if not extra:
+        if extra == ["--full"]:
             c = d["cpu_baseline"]
             assert c["kind"] == "port" and c["cores"] >= 1 and c["value"] > 0 and "sample" in c
             # the CPU leg solves the whole problem (nothing extrapolated) and reports its own iteration count
             assert abs(c["krylov_iterations"] - d["config"]["krylov_iterations"]) <= 2 and c["solve_s"] > 0
             # BASELINE configs[0] on one host thread, and what one rank of the multi-GPU configurations does per iteration
             assert c["c1_1_thread_dofs_per_s"] > 0 and c["c1_1_thread"]["threads"] == 1
-            # (other_configs.rank_sizes exists for the default 10 M-dof run only: its record is checked below at a small size)
+            # (other_configs.rank_sizes exists for the --full 10 M-dof run only: its record is checked below at a small size)
     # one record of other_configs.rank_sizes (a rank's share as a problem of its own, communication path attached), in a child
     # process as bench.py runs it
     code = ("import sys, json; sys.path.insert(0, %r); sys.path.insert(0, %r); import bench; "
@@ -214,6 +214,48 @@ def test_bench_contract_line():
     assert cfg["scalar_allreduce"] in ("ncclAllReduce", "peer-memory mailboxes over xGMI (one kernel: reduce + exchange)")
     assert ("-ksp_cg_single_reduction" in cfg["workload"]) == min(
         cfg["cg_form_tuning_s"], key=cfg["cg_form_tuning_s"].get).startswith("single_reduction")
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain bench.py run (no --full) is the headline alone: exactly --steps timed steps, nothing measured beside them.
+    --dump-outputs writes the last timed step's u, b, A and solve scalars as float64 .npy files, the same bits in every run
+    of the same arguments (no atomics on the data path), and they are that step's results: |u| and the iteration count of
+    the line, A's sampled entries consistent with the CSR the line describes."""
+    import json
+    import subprocess
+    import sys
+
+    root = os.path.dirname(zzz.PKG)
+    runs = []
+    for k in range(2):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--ndofs", "40000", "--steps", "3", "--warmup", "1",
+                              "--dump-outputs", str(tmp_path / f"run{k}")], capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.lstrip().startswith("{")]
+        assert len(lines) == 1, out.stdout[-2000:]
+        runs.append(json.loads(lines[0]))
+    d = runs[0]
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    assert abs(d["value"] - d["config"]["dofs"] / (d["ms_per_step"] * 1e-3)) <= 1e-9 * d["value"]
+    for k in ("cpu_baseline", "alt_preconditioner", "other_configs"):
+        assert k not in d, k
+    assert "full_pattern" not in d["roofline"]
+    names = {"solve", "u", "b", "u_index", "A_values", "A_rows", "A_cols"}
+    total = 0
+    for name in names:
+        a0, a1 = np.load(tmp_path / "run0" / f"{name}.npy"), np.load(tmp_path / "run1" / f"{name}.npy")
+        assert a0.dtype == np.float64 and a0.shape == a1.shape
+        np.testing.assert_array_equal(a0, a1)
+        total += os.path.getsize(tmp_path / "run0" / f"{name}.npy")
+    assert sorted(os.listdir(tmp_path / "run0")) == sorted(n + ".npy" for n in names) and total <= 64 << 20
+    dump = {n: np.load(tmp_path / "run0" / f"{n}.npy") for n in names}
+    cfg = d["config"]
+    n = cfg["rows_rank0"]
+    assert dump["u"].size == n and np.array_equal(dump["u_index"], np.arange(n))  # 40 k dofs: not sampled
+    assert dump["solve"][0] == cfg["krylov_iterations"] and dump["solve"][1] == cfg["relative_residual"]
+    assert abs(np.linalg.norm(dump["u"]) - cfg["solution_norm"]) <= 1e-12 * cfg["solution_norm"]
+    assert dump["A_values"].size == cfg["nnz_rank0"] and np.all(np.diff(dump["A_rows"]) >= 0)
+    assert dump["A_rows"].max() == n - 1 and 0 <= dump["A_cols"].min() and dump["A_cols"].max() < n
 
 
 def test_bench_multi_gpu_process_layout_on_one_gpu():
