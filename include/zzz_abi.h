@@ -243,8 +243,8 @@ int zzz_spmv(zzz_ctx* ctx, const double* x, double* y);
 
 /* Measurement aid: HIP-event time of `reps` back-to-back launches of the CG SpMV kernel
  * (w = A p with the <p,w> partials) on the context's stream; variant < 0 keeps the configured
- * kernel variant; otherwise a bit set for A/B runs: bit 0 non-temporal loads, bit 1 pipelined CSR
- * tiles, bit 3 the operator stream of zzz_sellp.hip when one was built (default 9 = stream + non-temporal),
+ * kernel variant; otherwise a bit set for A/B runs: bit 0 non-temporal loads, bit 1 unused (ignored),
+ * bit 3 the operator stream of zzz_sellp.hip when one was built (default 9 = stream + non-temporal),
  * bit 4 int32 instead of packed 16-bit columns in the tile kernel. */
 int zzz_spmv_time(zzz_ctx* ctx, int reps, int variant, double* avg_ms);
 
@@ -330,8 +330,7 @@ int zzz_cg_solve(zzz_ctx* ctx, const zzz_solver_opts* opts, int* iters, double* 
 /* Residual-norm history of the last solve (KSPGetResidualHistory): copies min(n, iters+1). */
 int zzz_cg_history(zzz_ctx* ctx, int n, double* out);
 
-/* About the last zzz_cg_solve: info[0] = 1 when the iteration ran as two kernels (product fused with the
- * direction update p = z + b p, x += a p: the A/B variant ZZZ_CG_FUSED=2), 0 for the three-kernel form; bit 1 (value 2)
+/* About the last zzz_cg_solve: info[0] bit 0 is reserved and always 0; bit 1 (value 2)
  * when Jacobi's inverse diagonal was read as 16-bit codes into a table of its distinct values and z = D^-1 r recomputed
  * instead of stored (68 instead of 80 B per row and iteration in the two vector kernels; the same bits), info[0] >> 8 = those
  * distinct values;

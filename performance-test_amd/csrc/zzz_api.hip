@@ -150,10 +150,6 @@ int zzz_ctx_create(int device, zzz_ctx** out)
     }
   }
   // tuning knobs for A/B measurements (defaults are the measured best)
-#ifdef ZZZ_EXPERIMENTS
-  if (const char* e = getenv("ZZZ_SPMV_TILE")) // (tools build only: the 4096-nonzero tiles lost)
-    ctx->spmv_tile = atoi(e) == 4096 ? 4096 : 2048;
-#endif
   if (const char* e = getenv("ZZZ_SPMV_VARIANT"))
   {
     ctx->spmv_variant = atoi(e) & 27;
@@ -163,10 +159,6 @@ int zzz_ctx_create(int device, zzz_ctx** out)
   {
     const int v = atoi(e);
     ctx->sellp_mode = v >= 0 && v <= 4 ? v : 1; // (4: natural row order through the long-row packer whatever the row lengths: tests)
-#ifdef ZZZ_EXPERIMENTS
-    if (v == 5) // experiment: component-major slices for block size 3 (zzz_sellp_pack.hip: k_sp_cm)
-      ctx->sellp_mode = 5;
-#endif
     ctx->sellp_long_rows = v == 4;
     if (v == 4)
       ctx->sellp_mode = 2;
@@ -819,7 +811,7 @@ int zzz_spmv_time(zzz_ctx* ctx, int reps, int variant, double* avg_ms)
   const bool saved_auto = ctx->spmv_auto;
   if (variant >= 0)
   {
-    ctx->spmv_variant = variant & 27; // bit 0 nt, bit 1 pipelined tiles, bit 3 SELL, bit 4 int32 columns
+    ctx->spmv_variant = variant & 27; // bit 0 nt, bit 1 unused, bit 3 SELL, bit 4 int32 columns
     ctx->spmv_auto = false;
   }
   hipEvent_t e0, e1;
@@ -827,12 +819,6 @@ int zzz_spmv_time(zzz_ctx* ctx, int reps, int variant, double* avg_ms)
   ZZZ_HIP(ctx, hipEventCreate(&e1));
   ZZZ_HIP(ctx, hipMemsetAsync(ctx->state.p, 0, sizeof(zzz::CgState), ctx->stream));
   int np = 0;
-  struct TimingOnly // the products below are timed, their results discarded (zzz_sellp.hip: the ZZZ_EXP_WIN probe)
-  {
-    zzz_ctx* c;
-    explicit TimingOnly(zzz_ctx* cc) : c(cc) { c->timing_only = true; }
-    ~TimingOnly() { c->timing_only = false; }
-  } timing_only(ctx);
   int rc = launch_spmv(ctx, ctx->p.p, ctx->w.p, ctx->part_a.p, &np); // warm-up
   ZZZ_HIP(ctx, hipEventRecord(e0, ctx->stream));
   for (int i = 0; i < reps && !rc; ++i)
@@ -1063,7 +1049,7 @@ int zzz_cg_info(zzz_ctx* ctx, int64_t info[4])
 {
   if (!ctx || !info)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_cg_info: bad arguments");
-  info[0] = (ctx->last_solve_fused ? 1 : 0) | (ctx->last_solve_dinv_codes > 0 ? 2 : 0) | ((int64_t)ctx->last_solve_dinv_codes << 8);
+  info[0] = (ctx->last_solve_dinv_codes > 0 ? 2 : 0) | ((int64_t)ctx->last_solve_dinv_codes << 8);
   info[1] = ctx->last_iters;
   info[2] = ctx->last_reason;
   info[3] = (int64_t)(ctx->last_pc_bound * 1.0e6); // Chebyshev-Jacobi: spectrum bound x 1e6

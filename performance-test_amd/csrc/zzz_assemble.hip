@@ -245,7 +245,7 @@ struct AdjIter
 };
 
 // ---- matrix, P1, BS = 1 (Poisson a1, src/Poisson.py:31) or 3 (Elasticity a1, src/Elasticity.py:39)
-template <int BS, int NNZ, int BLK, int PROBE = 0> // PROBE: timing ablations of the tools build (wrong results)
+template <int BS, int NNZ, int BLK>
 __global__ __launch_bounds__(BLK) void asm_matrix_p1(const double* __restrict__ xq,
                                                            const int32_t* __restrict__ cell_dofs,
                                                            const int32_t* __restrict__ adjT_off,
@@ -291,7 +291,7 @@ __global__ __launch_bounds__(BLK) void asm_matrix_p1(const double* __restrict__ 
     // per SIMD: occupancy alone does not hide the chain).
     // (profiles/r05_pmc_asm_c2.json, 10 M dofs: 296 VALU + 44 SALU + 26 LDS + 17 VMEM instructions per (row, cell) pair,
     // VALU busy 78 % of the kernel's cycles, L2 hit rate 80 %: the kernel is bound by the instructions it issues -- with
-    // every gather, the search and the geometry removed (ZZZ_ASM_PROBE=15 of the tools build) it still takes 1.55 of its
+    // every gather, the search and the geometry removed (a timing probe, since removed from the code) it still takes 1.55 of its
     // 2.65 ms: three wavefronts per SIMD, 24 dependent round trips per row.)
     // The walk has no branches: every lane runs the slice's `alen` iterations (the transposed adjacency pads shorter
     // rows with -1), a padding entry loads and evaluates cell 0 and only its update of the row is masked; the
@@ -319,26 +319,8 @@ __global__ __launch_bounds__(BLK) void asm_matrix_p1(const double* __restrict__ 
       K.dd = *reinterpret_cast<const int4*>(cell_dofs + 4 * (int64_t)max(cell, 0));
     };
     auto data_at = [&](const Conn& K, Data& D) {
-      if (PROBE & 2) // no coordinate gathers
-      {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-        {
-          D.p[k][0] = (double)(K.dd.x + k * k);
-          D.p[k][1] = (double)(K.dd.y - k);
-          D.p[k][2] = (double)(K.dd.z + 3 * k);
-        }
-      }
-      else
-        load_cell_q(xq, K.dd, D.p); // (skipping the row's own vertex, as asm_vector_p1 does, made this kernel 3 % slower)
+      load_cell_q(xq, K.dd, D.p); // (skipping the row's own vertex, as asm_vector_p1 does, made this kernel 3 % slower)
       const int dj[4] = {K.dd.x, K.dd.y, K.dd.z, K.dd.w};
-      if (PROBE & 4) // no flag gathers
-      {
-#pragma unroll
-        for (int j = 0; j < 4 * BS; ++j)
-          D.bcj[j] = 0;
-        return;
-      }
 #pragma unroll
       for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -358,15 +340,7 @@ __global__ __launch_bounds__(BLK) void asm_matrix_p1(const double* __restrict__ 
       const int dofs[4] = {K0.dd.x, K0.dd.y, K0.dd.z, K0.dd.w};
       double g[4][3];
       Geom G;
-      if (PROBE & 8) // no geometry
-      {
-        G.adet = D0.p[0][0];
-#pragma unroll
-        for (int k = 0; k < 9; ++k)
-          G.K[k / 3][k % 3] = D0.p[1 + k / 4][k % 3];
-      }
-      else
-        geometry(D0.p, G);
+      geometry(D0.p, G);
       p1_grads(G, g);
       const double w = G.adet / 6.0; // reference volume
 
@@ -382,14 +356,7 @@ __global__ __launch_bounds__(BLK) void asm_matrix_p1(const double* __restrict__ 
       int pos4[4];
       {
         const int col4[4] = {dofs[0] * BS, dofs[1] * BS, dofs[2] * BS, dofs[3] * BS};
-        if (PROBE & 1) // no column search
-        {
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            pos4[j] = (col4[j] + j) & 7;
-        }
-        else
-          find_pos4(cols_s + a0, len, col4, pos4);
+        find_pos4(cols_s + a0, len, col4, pos4);
       }
       double val[4][BS];
 #pragma unroll
@@ -1223,11 +1190,6 @@ int asm_tile_nnz(const zzz_ctx* ctx)
     return ASM_NNZ_P1;
   if (ctx->bs == 3 && ctx->order == 1 && ctx->asm_node3)
     return ASM_NNZ_NODE3; // (one thread per node: asm_matrix_p1_node3)
-#ifdef ZZZ_EXPERIMENTS
-  if (const char* e = getenv("ZZZ_ASM_CAP")) // measurement knob, tools build only
-    if (atoi(e) >= 1024 && atoi(e) <= 8192)
-      return atoi(e);
-#endif
   if (ctx->have_asm_pos)
   {
     // position-based kernel (asm_matrix_pk_pos: no columns in LDS, persistent workgroups): smaller tiles = more
@@ -1567,12 +1529,7 @@ static int launch_matrix_pk_pos(zzz_ctx* ctx)
   (void)hipGetLastError();
   // long rows (the packer's synchronous path): the compacted copy of the kept entries is written from here as well
   const int64_t* crow = nullptr;
-#ifdef ZZZ_EXPERIMENTS
-  const bool compact_here = !getenv("ZZZ_ASM_NO_COMPACT"); // A/B knob (tools build)
-#else
-  const bool compact_here = true;
-#endif
-  if (rownnz && ctx->nnz >= 16 * ctx->nrows && ctx->nnz + 8 * ctx->nrows < ((int64_t)1 << 40) && compact_here)
+  if (rownnz && ctx->nnz >= 16 * ctx->nrows && ctx->nnz + 8 * ctx->nrows < ((int64_t)1 << 40))
   {
     if (int rc = sellp_capacity_rows(ctx))
       return rc;
@@ -1630,19 +1587,6 @@ int launch_assemble_matrix(zzz_ctx* ctx, int form)
   {
     if (bs == 1)
     {
-#ifdef ZZZ_EXPERIMENTS
-      const int probe = getenv("ZZZ_ASM_PROBE") ? atoi(getenv("ZZZ_ASM_PROBE")) & 15 : 0; // timing ablations (wrong results)
-#define ZZZ_P1_PROBE(P)                                                                                                        \
-  if (probe == P)                                                                                                              \
-  {                                                                                                                            \
-    hipLaunchKernelGGL((asm_matrix_p1<1, ASM_NNZ_P1, 128, P>), grid, dim3(128), 0, ctx->stream, ctx->xq, ctx->cell_dofs.p,     \
-                       ctx->adjT_off.p, ctx->adjT_cells.p, ctx->adj_li.p, ctx->bc.p, ctx->rowptr.p, ctx->cols.p, ctx->vals.p,  \
-                       ctx->asm_tile.p, ctx->n_asm_tiles);                                                                     \
-    return ZZZ_OK;                                                                                                             \
-  }
-      ZZZ_P1_PROBE(1) ZZZ_P1_PROBE(6) ZZZ_P1_PROBE(8) ZZZ_P1_PROBE(15)
-#undef ZZZ_P1_PROBE
-#endif
       // one thread per row: a 1920-nonzero tile holds ~126 rows of 15, so 128 threads leave no lane idle
       hipLaunchKernelGGL((asm_matrix_p1<1, ASM_NNZ_P1, 128>), grid, dim3(128), 0, ctx->stream, ctx->xq, ctx->cell_dofs.p,
                          ctx->adjT_off.p, ctx->adjT_cells.p, ctx->adj_li.p, ctx->bc.p, ctx->rowptr.p, ctx->cols.p, ctx->vals.p,
@@ -1664,23 +1608,11 @@ int launch_assemble_matrix(zzz_ctx* ctx, int form)
       return rc;
     if (ctx->have_asm_pos) // positions from the pattern build: no column search (asm_matrix_pk_pos)
     {
-#ifdef ZZZ_EXPERIMENTS
-      const char* e = getenv("ZZZ_ASM_LPR"); // measurement knob (lanes per row), tools build only
-      const int lpr = e ? atoi(e) : 0;
-      if (ctx->order == 2)
-        rc = bs == 1 ? (lpr == 2 ? launch_matrix_pk_pos<10, 1, 2>(ctx) : launch_matrix_pk_pos<10, 1, 4>(ctx))
-                     : launch_matrix_pk_pos<10, 3, 4>(ctx);
-      else
-        rc = bs == 1 ? (lpr == 8 ? launch_matrix_pk_pos<20, 1, 8>(ctx) : lpr == 2 ? launch_matrix_pk_pos<20, 1, 2>(ctx)
-                                                                        : launch_matrix_pk_pos<20, 1, 4>(ctx))
-                     : (lpr == 4 ? launch_matrix_pk_pos<20, 3, 4>(ctx) : launch_matrix_pk_pos<20, 3, 8>(ctx));
-#else
       // lanes per row: Poisson four (P3: five columns each, no idle lane: 2.80 against 2.92 ms), elasticity P3 eight
       if (ctx->order == 2)
         rc = bs == 1 ? launch_matrix_pk_pos<10, 1, 4>(ctx) : launch_matrix_pk_pos<10, 3, 4>(ctx);
       else
         rc = bs == 1 ? launch_matrix_pk_pos<20, 1, 4>(ctx) : launch_matrix_pk_pos<20, 3, 8>(ctx);
-#endif
     }
     else if (ctx->order == 2)
       rc = bs == 1 ? launch_matrix_pk<10, 1, 4>(ctx) : launch_matrix_pk<10, 3, 4>(ctx);

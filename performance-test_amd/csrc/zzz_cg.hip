@@ -20,7 +20,6 @@
 // HBM traffic per iteration beyond the SpMV: 40 B/row (x and p update) + 40 B/row (r, z update).
 #include "zzz_device.h"
 #include "zzz_internal.h"
-#include "zzz_cg_device.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -28,6 +27,143 @@
 namespace zzz
 {
 typedef double dbl2 __attribute__((ext_vector_type(2)));
+
+// one workgroup-wide sum of parts[0..np) (fixed order); result in every thread
+__device__ inline double reduce_parts_bcast(const double* __restrict__ parts, int np, double* sh)
+{
+  double s = 0;
+  for (int i = threadIdx.x; i < np; i += blockDim.x)
+    s += parts[i];
+  const double t = block_reduce_sum(s, sh);
+  __shared__ double bc;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    bc = t;
+  __syncthreads();
+  return bc;
+}
+
+
+// The same for up to three partial arrays in ONE pass and one barrier pair (same tree per array as reduce_parts_bcast:
+// strided per-thread sums, shuffles inside a wavefront, the per-wavefront sums added in order -- here by every thread
+// from LDS instead of by thread 0 plus a broadcast).  pc may be null.
+__device__ inline void reduce_parts3_bcast(const double* __restrict__ pa, const double* __restrict__ pb,
+                                           const double* __restrict__ pc, int np, double& ra, double& rb, double& rc)
+{
+  __shared__ double sh[3 * 16];
+  double s0 = 0, s1 = 0, s2 = 0;
+  for (int i = threadIdx.x; i < np; i += blockDim.x)
+  {
+    s0 += pa[i];
+    s1 += pb[i];
+    if (pc)
+      s2 += pc[i];
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1)
+  {
+    s0 += __shfl_down(s0, o, 64);
+    s1 += __shfl_down(s1, o, 64);
+    s2 += __shfl_down(s2, o, 64);
+  }
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  __syncthreads();
+  if (lane == 0)
+  {
+    sh[wv] = s0;
+    sh[nw + wv] = s1;
+    sh[2 * nw + wv] = s2;
+  }
+  __syncthreads();
+  ra = rb = rc = 0.0;
+  for (int i = 0; i < nw; ++i)
+  {
+    ra += sh[i];
+    rb += sh[nw + i];
+    rc += sh[2 * nw + i];
+  }
+}
+
+// The scalar logic at the head of iteration `it` (convergence test of the completed iterations and the new
+// direction's coefficient), identical in every workgroup; workgroup 0 records it.  pa/pb: partials (or the single
+// all-reduced values) of <r,z> and of the test norm.  Returns false when an EARLIER launch has stopped the solve
+// (this one must do nothing).  sh: >= blockDim.x/64 doubles of LDS.
+struct DirScalars
+{
+  double rz, bprev;
+  int conv;
+};
+__device__ inline bool cg_direction_scalars(CgState* __restrict__ st, double* __restrict__ beta_hist,
+                                            double* __restrict__ dp_hist, int it, const CgParams& P,
+                                            const double* __restrict__ pa, const double* __restrict__ pb, int np, double* sh,
+                                            DirScalars& S)
+{
+  // every input of the scalar logic is requested up-front (uniform loads, one round trip): the stop word, the state,
+  // last iteration's <r,z>, and -- communicator attached, np == 1 -- the two all-reduced sums themselves
+  const int c = __atomic_load_n(&st->conv_it1, __ATOMIC_RELAXED);
+  const double dp0_st = st->dp0, ttol_st = st->ttol;
+  const double bprev_h = (it == 0) ? 1.0 : beta_hist[it - 1];
+  double rz = pa[0], nn = pb[0], unused;
+  // stopped by an EARLIER launch (c - 1 < it): that word was written before this launch began, so every wavefront
+  // reads the same value and the branch is uniform without a broadcast
+  if (c != 0 && c - 1 < it)
+    return false;
+  if (np != 1)
+    reduce_parts3_bcast(pa, pb, nullptr, np, rz, nn, unused);
+  // scalar logic, identical in every workgroup; workgroup 0 records it
+  double dp, dp0 = dp0_st, ttol = ttol_st;
+  int conv = 0;
+  if (P.variant == ZZZ_CG_CGH)
+  {
+    // src/cg.h:53-55,74-79: rnorm = <r,r>; break when rnorm/rnorm0 < rtol^2 (strict), no test at k = 0
+    dp = rz;
+    if (it == 0)
+    {
+      dp0 = rz;
+      ttol = P.rtol * P.rtol;
+    }
+    else if (rz / dp0 < P.rtol * P.rtol)
+      conv = 1;
+  }
+  else
+  {
+    dp = (P.norm == ZZZ_NORM_NATURAL) ? sqrt(fabs(rz)) : sqrt(nn);
+    if (it == 0)
+    {
+      dp0 = dp;
+      ttol = fmax(P.rtol * dp, P.atol);
+    }
+    if (!isfinite(dp))
+      conv = 2;
+    else if (dp <= ttol) // KSPConvergedDefault
+      conv = 1;
+    else if (dp >= P.dtol * dp0) // ... KSP_DIVERGED_DTOL
+      conv = 3;
+  }
+  const double bprev = bprev_h;
+  if (blockIdx.x == 0 && threadIdx.x == 0)
+  {
+    beta_hist[it] = rz;
+    dp_hist[it] = dp;
+    st->dp = dp;
+    if (it == 0)
+    {
+      st->dp0 = dp0;
+      st->ttol = ttol;
+    }
+    if (conv)
+    {
+      st->iters = it;
+      st->converged = conv; // the other workgroups reach the same verdict from the same partials
+      __atomic_store_n(&st->conv_it1, it + 1, __ATOMIC_RELAXED);
+    }
+  }
+  S.rz = rz;
+  S.bprev = bprev;
+  S.conv = conv;
+  return true;
+}
+
 constexpr int VB = 256;        // threads per workgroup of the vector kernels
 constexpr int VGRID_MAX = 2048; // 8 workgroups per CU
 // Product launches timed with HIP events when zzz_solver_opts.profile is set: every PROF_STRIDE-th iteration.  An event
@@ -371,7 +507,7 @@ __global__ __launch_bounds__(VB) void k_update_xr(CgState* __restrict__ st, cons
                                                   const double* __restrict__ w, const double* __restrict__ dinv,
                                                   double* __restrict__ r, double* __restrict__ z, int64_t n, int norm,
                                                   double* __restrict__ pa, double* __restrict__ pb, int variant,
-                                                  TailArgs tail, DinvCodes dz = DinvCodes())
+                                                  DinvCodes dz = DinvCodes())
 {
   __shared__ double dtab[DZ ? DZ_MAX : 1];
   if (DZ)
@@ -482,11 +618,6 @@ __global__ __launch_bounds__(VB) void k_update_xr(CgState* __restrict__ st, cons
   }
   const double ta = block_reduce_sum(sa, sh);
   const double tb = block_reduce_sum(sb, sh);
-  if (tail.parts) // multi-GPU: <r,z> and the norm are all-reduced in the tail of this launch (zzz_tail.h)
-  {
-    tail_arrive(tail, ta, tb, 0.0);
-    return;
-  }
   if (threadIdx.x == 0)
   {
     pa[blockIdx.x] = ta;
@@ -778,15 +909,7 @@ static int vgrid(int64_t n)
   // at least 8 entries per thread: every workgroup starts by summing the producer's per-workgroup partials, so for
   // small vectors fewer, longer workgroups are faster (1.25 M rows: 57.8 -> 52.9 us per iteration with 610 instead of
   // 2048 workgroups, 0.5 M rows 40.8 -> 37.0 us; 16 per thread the same, 32 slower); large vectors keep 8 per CU
-#ifdef ZZZ_EXPERIMENTS
-  static const int per = [] {
-    const char* e = getenv("ZZZ_VGRID_PER"); // measurement knob (entries per thread), tools build only
-    const int v = e ? atoi(e) : 0;
-    return v >= 1 && v <= 64 ? v : 8;
-  }();
-#else
   constexpr int per = 8;
-#endif
   int64_t g = (n + VB * per - 1) / (VB * per);
   if (g > VGRID_MAX)
     g = VGRID_MAX;
@@ -866,23 +989,6 @@ int cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
   // (kernels by load policy and by whether z is recomputed from the coded inverse diagonal: chosen where dz is known)
   auto pick_update_p = [&](bool dzf) { return dzf ? (nt ? k_update_p<true, true> : k_update_p<false, true>) : (nt ? k_update_p<true, false> : k_update_p<false, false>); };
   auto pick_update_xr = [&](bool dzf) { return dzf ? (nt ? k_update_xr<true, true> : k_update_xr<false, true>) : (nt ? k_update_xr<true, false> : k_update_xr<false, false>); };
-  // A/B knob ZZZ_CG_FUSED=2: two kernels per iteration (product fused with the direction update, zzz_sellp.hip).
-  // Bit-identical, but MEASURED slower wherever it was tried: at the 8-GPU per-rank size (1.25 M rows, loop resident
-  // in the Infinity Cache) the fused kernel takes 39-41 us against 14.7 + 19.6 us for k_update_p + product (the
-  // second gather and the row updates lengthen every wavefront's dependent chain, and at that size the product is
-  // latency-bound: ~2.4 slices per wavefront); for HBM-sized loops it saves 4 % of the bytes at best.  Off by default.
-  int fused_mode = 0;
-#ifdef ZZZ_EXPERIMENTS
-  if (const char* e = getenv("ZZZ_CG_FUSED"))
-    fused_mode = atoi(e);
-#endif
-  const bool fused = o->op == ZZZ_OP_CSR && fused_mode == 2 && sellp_active(ctx) && ctx->sp_win_max == 0; // (its kernel gathers from memory)
-  ctx->last_solve_fused = fused;
-  // multi-GPU: the scalar all-reduce rides in the tail of the product launch when that launch is the operator stream's
-  const bool fold_product = multi && !fused && o->op == ZZZ_OP_CSR && sellp_active(ctx);
-  if (fused)
-    ZZZ_HIP(ctx, ctx->p_alt.alloc((size_t)ctx->nloc()));
-  double* pbuf[2] = {ctx->p.p, fused ? ctx->p_alt.p : ctx->p.p};
 
   ZZZ_HIP(ctx, ctx->beta_hist.reserve((size_t)max_it + 2));
   ZZZ_HIP(ctx, ctx->dp_hist.reserve((size_t)max_it + 2));
@@ -909,7 +1015,7 @@ int cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
   // the Infinity Cache (where bytes are what the vector kernels wait for: the criterion of their load policy;
   // ZZZ_CG_DINV_CODES: 0 never, 2 at any size), at most 2 048 values
   DinvCodes dzc{nullptr, nullptr, nullptr, 0};
-  if (o->variant == ZZZ_CG_PETSC && o->pc == ZZZ_PC_JACOBI && !fused && ctx->cg_dinv_codes != 0 && (ctx->cg_dinv_codes == 2 || nt))
+  if (o->variant == ZZZ_CG_PETSC && o->pc == ZZZ_PC_JACOBI && ctx->cg_dinv_codes != 0 && (ctx->cg_dinv_codes == 2 || nt))
     if (int rc = dinv_codes_build(ctx, n, dzc))
       return rc;
   ctx->last_solve_dinv_codes = dzc.codes ? dzc.ndict : 0;
@@ -994,30 +1100,15 @@ int cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
   for (; it < max_it && !stop; ++it)
   {
     // convergence test of iteration `it` and the new search direction
-    if (!fused)
-      hipLaunchKernelGGL(kern_update_p, dim3(g), dim3(VB), 0, s, ctx->state.p, ctx->beta_hist.p, ctx->dp_hist.p,
-                         ctx->alpha_hist.p, it, P, rz_src, nn_src, n_rz, ctx->z.p, ctx->p.p, ctx->u.p, n, 1, dzc);
+    hipLaunchKernelGGL(kern_update_p, dim3(g), dim3(VB), 0, s, ctx->state.p, ctx->beta_hist.p, ctx->dp_hist.p,
+                       ctx->alpha_hist.p, it, P, rz_src, nn_src, n_rz, ctx->z.p, ctx->p.p, ctx->u.p, n, 1, dzc);
     int np = 0;
     const bool timed = nprof < max_prof && it % PROF_STRIDE == 0;
     ctx->prof_now = timed;
     if (timed)
       (void)hipEventRecord(ctx->ev[2 * nprof], s);
-    bool folded = false;
-    if (fold_product && comm_tail_args(ctx, ctx->tail, 1, ctx->red.p + 2))
     {
-      ctx->tail_armed = true; // <p,w> is all-reduced in the tail of the product launch
-      ctx->tail_used = false;
-    }
-    {
-#ifdef ZZZ_EXPERIMENTS
-      int rc = fused ? launch_sellp_dir(ctx, ctx->z.p, pbuf[it & 1], pbuf[(it + 1) & 1], ctx->u.p, ctx->w.p, ctx->part_a.p, &np,
-                                        it, P, rz_src, nn_src, n_rz, multi && ctx->overlap)
-                     : apply(ctx->p.p, ctx->w.p, ctx->part_a.p, &np);
-#else
       int rc = apply(ctx->p.p, ctx->w.p, ctx->part_a.p, &np);
-#endif
-      folded = ctx->tail_used;
-      ctx->tail_armed = ctx->tail_used = false;
       if (rc)
         return rc;
     }
@@ -1029,29 +1120,15 @@ int cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
     }
     if (multi)
     {
-      if (!folded)
-      {
-        int rc = comm_reduce_allreduce(ctx, stop_flag, ctx->part_a.p, nullptr, nullptr, np, 1, ctx->red.p + 2);
-        if (rc)
-          return rc;
-      }
-      np = 1;
-    }
-    TailArgs Txr;
-    const bool folded_xr = multi && comm_tail_args(ctx, Txr, 2, ctx->red.p);
-    if (folded_xr)
-    {
-      Txr.expected = g;
-      Txr.base = 0;
-    }
-    hipLaunchKernelGGL(kern_update_xr, dim3(g), dim3(VB), 0, s, ctx->state.p, ctx->beta_hist.p, ctx->alpha_hist.p, it, pw_src,
-                       np, ctx->w.p, ctx->dinv.p, ctx->r.p, ctx->z.p, n, P.norm, pa, pb, P.variant, Txr, dzc);
-    if (!folded_xr)
-    {
-      int rc = allreduce_beta();
+      int rc = comm_reduce_allreduce(ctx, stop_flag, ctx->part_a.p, nullptr, nullptr, np, 1, ctx->red.p + 2);
       if (rc)
         return rc;
+      np = 1;
     }
+    hipLaunchKernelGGL(kern_update_xr, dim3(g), dim3(VB), 0, s, ctx->state.p, ctx->beta_hist.p, ctx->alpha_hist.p, it, pw_src,
+                       np, ctx->w.p, ctx->dinv.p, ctx->r.p, ctx->z.p, n, P.norm, pa, pb, P.variant, dzc);
+    if (int rc = allreduce_beta())
+      return rc;
     if ((it + 1) % CHECK == 0)
     {
       const int slot = nchk % NSLOT;
@@ -1070,7 +1147,7 @@ int cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
   // the test of the last completed iteration (it == max_it when the loop ran out) and its pending
   // solution update; no new direction
   hipLaunchKernelGGL(kern_update_p, dim3(g), dim3(VB), 0, s, ctx->state.p, ctx->beta_hist.p, ctx->dp_hist.p,
-                     ctx->alpha_hist.p, it, P, rz_src, nn_src, n_rz, ctx->z.p, pbuf[it & 1], ctx->u.p, n, 0, dzc);
+                     ctx->alpha_hist.p, it, P, rz_src, nn_src, n_rz, ctx->z.p, ctx->p.p, ctx->u.p, n, 0, dzc);
   ZZZ_HIP(ctx, hipGetLastError());
   CgState fin;
   ZZZ_HIP(ctx, hipMemcpyAsync(&fin, ctx->state.p, sizeof(CgState), hipMemcpyDeviceToHost, s));
@@ -1550,7 +1627,6 @@ static int cg_solve_chebyshev(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters
   const double hi = C.hi, theta = C.theta;
   const bool fused = C.fused;
   double *chd = C.d, *chg = C.g;
-  ctx->last_solve_fused = false;
   ZZZ_HIP(ctx, ctx->beta_hist.reserve((size_t)max_it + 2));
   ZZZ_HIP(ctx, ctx->dp_hist.reserve((size_t)max_it + 2));
   ZZZ_HIP(ctx, ctx->alpha_hist.reserve((size_t)max_it + 2));
@@ -1725,7 +1801,6 @@ static int cg_solve_single_reduction(zzz_ctx* ctx, const zzz_solver_opts* o, int
     if (int rc = chebyshev_setup(ctx, o, C))
       return rc;
   const bool ntv = loop_exceeds_cache(ctx, 8);
-  ctx->last_solve_fused = false;
 
   ZZZ_HIP(ctx, ctx->beta_hist.reserve((size_t)max_it + 2));
   ZZZ_HIP(ctx, ctx->dp_hist.reserve((size_t)max_it + 2));
@@ -1774,15 +1849,8 @@ static int cg_solve_single_reduction(zzz_ctx* ctx, const zzz_solver_opts* o, int
   }
   int np = 0;
   // s = A z with the three partial dot products; then (multi) one all-reduce of three doubles
-  const bool fold_product = multi && sellp_active(ctx);
   auto apply = [&]() -> int {
     int rc;
-    bool folded = false;
-    if (fold_product && comm_tail_args(ctx, ctx->tail, 3, ctx->red.p))
-    {
-      ctx->tail_armed = true; // (<r,z>, norm, <z,s>) all-reduced in the tail of the product launch
-      ctx->tail_used = false;
-    }
     if (multi && ctx->overlap && ctx->have_tile_split)
       rc = launch_spmv_overlapped(ctx, ctx->z.p, ctx->sr_s.p, parts, &np, ctx->r.p, nn_is_rr);
     else
@@ -1795,19 +1863,14 @@ static int cg_solve_single_reduction(zzz_ctx* ctx, const zzz_solver_opts* o, int
       }
       rc = launch_spmv(ctx, ctx->z.p, ctx->sr_s.p, parts, &np, ctx->r.p, nn_is_rr);
     }
-    folded = ctx->tail_used;
-    ctx->tail_armed = ctx->tail_used = false;
     if (rc)
       return rc;
     if (multi)
     {
-      if (!folded)
-      {
-        rc = comm_reduce_allreduce(ctx, reinterpret_cast<const int*>(ctx->state.p), parts + SPMV_PSTRIDE,
-                                   parts + 2 * SPMV_PSTRIDE, parts, np, 3, ctx->red.p);
-        if (rc)
-          return rc;
-      }
+      rc = comm_reduce_allreduce(ctx, reinterpret_cast<const int*>(ctx->state.p), parts + SPMV_PSTRIDE,
+                                 parts + 2 * SPMV_PSTRIDE, parts, np, 3, ctx->red.p);
+      if (rc)
+        return rc;
       np = 1;
     }
     return ZZZ_OK;

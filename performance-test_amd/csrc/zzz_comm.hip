@@ -234,8 +234,6 @@ struct P2P
   std::vector<bool> ipc_opened;         // peer[r] came from hipIpcOpenMemHandle
   zzz::DevBuf<double*> peer_dev;        // the same pointers for the kernel
   zzz::DevBuf<int32_t> fail;            // device flag: a poll timed out
-  double* tail_mem = nullptr;           // partial arrays + tickets of the folded all-reduce (zzz_tail.h)
-  bool tail_on = false;                 // ZZZ_TAIL=1 when the mailbox was created (A/B variant, off by default)
   int64_t seq = 0;                      // round counter = tag; identical call sequence on every rank
   // halo window (behind the mailbox in the same allocation, so the same IPC handle maps it): the forward scatter of
   // the product's input vector as plain device stores into the NEIGHBOUR's memory over xGMI instead of ncclSend /
@@ -464,34 +462,6 @@ int comm_reduce_allreduce(zzz_ctx* ctx, const int* stop, const double* pa, const
   return comm_allreduce_sum(ctx, out, nv);
 }
 
-bool comm_tail_args(zzz_ctx* ctx, TailArgs& T, int nv, double* out)
-{
-#ifndef ZZZ_EXPERIMENTS
-  (void)ctx, (void)T, (void)nv, (void)out;
-  return false; // the folded all-reduce (zzz_tail.h) exists in the tools build only: measured 1 us slower per reduction point
-#else
-  // A/B knob ZZZ_TAIL=1 (read when the mailbox is created): fold the all-reduce into the producer's tail.  Measured
-  // slower than the kernel of its own (zzz_tail.h has the numbers), so off unless asked for.
-  const bool off = !(ctx->comm && ctx->comm->p2p && ctx->comm->p2p->tail_on);
-  if (off || !comm_p2p_enabled(ctx) || !ctx->comm->p2p->tail_mem)
-    return false;
-  P2P* P = ctx->comm->p2p;
-  T = TailArgs();
-  T.parts = P->tail_mem;
-  T.ticket = reinterpret_cast<int*>(P->tail_mem + (size_t)TAIL_PART_DOUBLES);
-  T.nv = nv;
-  T.out = out;
-  T.peers = P->peer_dev.p;
-  T.box = P->box;
-  T.nranks = P->nranks;
-  T.rank = P->rank;
-  T.seq = ++P->seq;
-  T.fail = P->fail.p;
-  T.timeout = P2P_TIMEOUT_TICKS;
-  return true;
-#endif
-}
-
 // did a peer all-reduce time out since the last call?  (checked at the end of a solve)
 int comm_p2p_check(zzz_ctx* ctx)
 {
@@ -518,8 +488,6 @@ static void p2p_destroy(P2P* P)
       (void)hipIpcCloseMemHandle(P->peer[r]);
   if (P->box)
     (void)hipFree(P->box);
-  if (P->tail_mem)
-    (void)hipFree(P->tail_mem);
   delete P;
 }
 
@@ -1136,10 +1104,6 @@ int zzz_comm_p2p_export(zzz_ctx* ctx, void* handle)
   P2P* P = new P2P();
   P->nranks = ctx->comm->nranks;
   P->rank = ctx->comm->rank;
-#ifdef ZZZ_EXPERIMENTS
-  if (const char* e = getenv("ZZZ_TAIL"))
-    P->tail_on = atoi(e) == 1;
-#endif
   size_t bytes = sizeof(double) * 2 * (size_t)P->nranks * P2P_SLOT;
   bytes = (bytes + 4095) / 4096 * 4096;
   // the halo window behind the mailbox (ZZZ_P2P_HALO_MB, default 64; 0 = none: halo through the communicator)
@@ -1178,23 +1142,6 @@ int zzz_comm_p2p_export(zzz_ctx* ctx, void* handle)
   P->halo_on = P->halo_off != 0;
   if (const char* hk = getenv("ZZZ_P2P_HALO")) // A/B knob: 0 keeps the halo on the communicator
     P->halo_on = P->halo_on && atoi(hk) != 0;
-#ifdef ZZZ_EXPERIMENTS
-  if (e == hipSuccess)
-  {
-    // partial arrays + tickets of the folded all-reduce (producers on all eight XCDs, one reader)
-    const size_t tb = sizeof(double) * (size_t)TAIL_PART_DOUBLES + sizeof(int) * (size_t)TAIL_TICKET_INTS;
-    // ordinary device memory: the producers store write-through (sc1), the reader acquires at agent scope (zzz_tail.h).
-    // (Uncached memory was tried first: its stores alone stretched a 20-us product of 2048 workgroups to 40 us.)
-    hipError_t e2 = hipMalloc(reinterpret_cast<void**>(&P->tail_mem), tb);
-    if (e2 == hipSuccess)
-      e2 = hipMemset(P->tail_mem, 0, tb);
-    if (e2 != hipSuccess)
-    {
-      (void)hipGetLastError();
-      P->tail_mem = nullptr; // the separate all-reduce kernel stays in use
-    }
-  }
-#endif
   if (e == hipSuccess)
   {
     h.ok = 1;

@@ -10,7 +10,6 @@
 #include <vector>
 
 #include "../../include/zzz_abi.h"
-#include "zzz_tail.h"
 
 // One term of the Chebyshev-Jacobi polynomial (cg_solve_chebyshev) as the epilogue of the product of d: with
 // w_i = (A d)_i in the lane that owns row i,  g_i -= D^-1_ii w_i;  d'_i = c1 d_i + c2 g_i (written to the product's
@@ -63,7 +62,7 @@ struct DevBuf
   // Scratch that may be asked for while ANOTHER context's kernel is waiting for this one (two ranks on one GPU: the other rank
   // polls its all-reduce mailbox inside a kernel while this one still builds its product form): grows only, and a buffer that
   // is too small is RETIRED -- handed to `retired`, freed with the context -- not freed: hipFree waits for every kernel on the
-  // device, i.e. for the poll's time-out (tools/r06/soak_new_forms.sh, elasticity P2 on two ranks: found in round 5 at the
+  // device, i.e. for the poll's time-out (a soak run of elasticity P2 on two ranks: found in round 5 at the
   // dictionaries' buffers, again in round 6 at the scans' scratch behind a pattern build's larger one).
   hipError_t grow_keep(size_t count, std::vector<void*>& retired)
   {
@@ -105,6 +104,7 @@ struct Comm; // zzz_comm.cpp
 typedef int64_t rp_t; // row pointers of the CSR matrix of record
 
 constexpr int SPMV_PSTRIDE = 4096; // distance between the three partial arrays of the single-reduction SpMV
+constexpr int SPMV_TILE_NNZ = 2048; // most nonzeros in one tile of the CSR SpMV (zzz_spmv.hip)
 
 // CG scalars kept on the device so the iteration loop never waits for the host.
 struct CgState
@@ -250,10 +250,9 @@ struct zzz_ctx
   zzz::DevBuf<int32_t> tiles_interior, tiles_boundary;
   int64_t n_tiles_interior = 0, n_tiles_boundary = 0;
   bool have_tile_split = false;
-  int spmv_tile = 2048;  // nonzeros per tile (2048 | 4096), fixed at pattern build
   int spmv_lpr_shift = 0, spmv_lpr_forced = -1; // log2(lanes per row) of the SpMV row phase
   bool spmv_auto = true; // choose bit 0 from the matrix size (off when ZZZ_SPMV_VARIANT / zzz_spmv_time force one)
-  int spmv_variant = 1;  // bit 0: non-temporal matrix loads, bit 1: pipelined CSR tiles,
+  int spmv_variant = 1;  // bit 0: non-temporal matrix loads, bit 1: unused,
                          // bit 3: the sliced-ELL operator stream (zzz_sellp.hip) instead of the CSR tile kernel
   // Operator stream of the CG SpMV (zzz_sellp.hip): sliced-ELL copy in chunks of 8 entries per row, exact zeros
   // dropped, 16-bit slot-relative column codes; rebuilt from the CSR values after every assembly
@@ -369,7 +368,6 @@ struct zzz_ctx
 
   // vectors, (n_owned+n_ghost)*bs each
   zzz::DevBuf<double> b, u, r, z, p, w, dinv;
-  zzz::DevBuf<double> p_alt; // second direction buffer of the fused product + direction kernel (zzz_sellp.hip)
   // reductions
   zzz::DevBuf<double> part_a, part_b, red; // block partials; reduced scalars
   zzz::DevBuf<double> beta_hist, dp_hist, dpi_hist;
@@ -388,7 +386,6 @@ struct zzz_ctx
   zzz::DevBuf<int32_t> sp_win_seg;  // [group][SP_WIN_NSEG] = {first column, length}
   int sp_win_max = 0;               // doubles of LDS per workgroup the product launches with (0: no windowed group)
   int64_t sp_win_bytes = 0;         // window bytes a product loads (all windowed groups)
-  bool timing_only = false;  // inside zzz_spmv_time: the products' results are discarded (the ZZZ_EXP_WIN probe may run)
   bool halo_pending = false; // comm_halo_begin put an exchange on the comm stream: comm_halo_end waits for it
   zzz::MfPlan mf; // matrix-free action
   zzz::DevBuf<double> near_null; // the six orthonormalised rigid-body modes (zzz_nullspace.hip), [6][near_null_ld]
@@ -399,7 +396,6 @@ struct zzz_ctx
   int cheb_est_its = 0;
   double cheb_hi = 0.0;
   double last_pc_bound = 0.0; // ZZZ_PC_CHEBYSHEV_JACOBI: the spectrum bound the last solve used
-  bool last_solve_fused = false; // the last solve ran the fused product + direction kernel
 
   // profiling
   std::vector<hipEvent_t> ev;
@@ -412,10 +408,6 @@ struct zzz_ctx
   int prof_halo_n = 0;
   double prof_halo_wait_ms = 0.0;
 
-  // the scalar all-reduce folded into the tail of the producing kernel (zzz_tail.h): armed by the CG loop before a
-  // product whose partials it wants all-reduced, consumed by the operator-stream launcher (tail_used tells the loop)
-  zzz::TailArgs tail;
-  bool tail_armed = false, tail_used = false;
   // multi-GPU
   zzz::Comm* comm = nullptr;
   int nneigh = 0;
@@ -507,8 +499,6 @@ int launch_sellp(zzz_ctx* ctx, const double* x, double* y, double* partials, int
                  const ChebEpi* epi = nullptr);
 int launch_sellp_overlapped(zzz_ctx* ctx, double* x, double* y, double* partials, int* npartials, const double* rvec,
                             int nn_is_rr, const ChebEpi* epi = nullptr);
-int launch_sellp_dir(zzz_ctx* ctx, double* z, const double* p_old, double* p_new, double* xsol, double* y, double* partials,
-                     int* npartials, int it, const zzz::CgParams& P, const double* pa, const double* pb, int np, bool overlap);
 
 // kernels_assemble
 int launch_assemble_matrix(zzz_ctx* ctx, int form);
@@ -532,9 +522,6 @@ int comm_allreduce_sum(zzz_ctx* ctx, double* dev, int n);
 int comm_reduce_allreduce(zzz_ctx* ctx, const int* stop, const double* pa, const double* pb, const double* pc, int np, int nv,
                           double* out);
 bool comm_p2p_enabled(const zzz_ctx* ctx);
-// fills T for one folded all-reduce of nv values into out (takes the next mailbox round number); false when the
-// mailboxes are not in use or ZZZ_TAIL=0: the caller then launches the separate reduce / all-reduce kernel
-bool comm_tail_args(zzz_ctx* ctx, zzz::TailArgs& T, int nv, double* out);
 int comm_p2p_check(zzz_ctx* ctx);
 int comm_halo_forward(zzz_ctx* ctx, double* vec);
 int comm_halo_begin(zzz_ctx* ctx, double* vec); // on the comm stream, after the work enqueued so far

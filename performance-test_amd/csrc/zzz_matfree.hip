@@ -569,13 +569,7 @@ struct MfArgs
   const int* stop;
   int64_t nblocks;
   int nc, nsb, nloc_cap;
-  int dbg; // ZZZ_EXPERIMENTS builds only (ZZZ_MF_DEBUG): phases switched off for timing, results wrong
 };
-#ifdef ZZZ_EXPERIMENTS
-#define MF_DBG(bit) (A.dbg & (bit))
-#else
-#define MF_DBG(bit) 0
-#endif
 
 // The factorised tables: constexpr copies decide at compile time which entries are zero; the values are staged in LDS
 // by every (persistent) workgroup and reach the multiply-adds as broadcast reads.  (As literals they occupied ~200
@@ -705,8 +699,8 @@ __global__ __launch_bounds__(T, (ND == 20 ? 3 : 1)) void k_mf_action(const MfArg
     // stage the block's u (and coordinates), clear its y
     for (int d = tid; d < nloc; d += T)
     {
-      const int32_t g = (GU || DIAG || MF_DBG(4)) ? 0 : A.dof_ids[dof_off + d];
-      const double uv = (GU || DIAG || MF_DBG(4)) ? 1.0 : A.u[g];
+      const int32_t g = (GU || DIAG) ? 0 : A.dof_ids[dof_off + d];
+      const double uv = (GU || DIAG) ? 1.0 : A.u[g];
       if (ND == 4)
       {
         const double* __restrict__ q = A.xyz + 3ll * (dof_off + d);
@@ -792,15 +786,7 @@ __global__ __launch_bounds__(T, (ND == 20 ? 3 : 1)) void k_mf_action(const MfArg
           for (int j = 0; j < ND; ++j)
             ue[j] = rec[(iw[j >> 1] >> (16 * (j & 1))) & 0xffff];
         }
-        if constexpr (DIAG)
-          ;
-        else if (MF_DBG(1))
-        {
-#pragma unroll
-          for (int j = 0; j < ND; ++j)
-            ye[j] = ue[j] * G[j % 6];
-        }
-        else
+        if constexpr (!DIAG)
           mf_element_pk<ND>(tab_s, tabT_s, ue, G, ye);
       }
       // rounds: the incidences of rank r of this step are added in round r (distinct addresses inside a round).  The
@@ -823,18 +809,7 @@ __global__ __launch_bounds__(T, (ND == 20 ? 3 : 1)) void k_mf_action(const MfArg
             Rc[c] = max(Rc[c], (int)((m >> (8 * k)) & 255u));
           }
       }
-      const int R2 = Rc[2], R1 = max(R2, Rc[1]), R0 = MF_DBG(2) ? 1 : (MF_DBG(32) ? 0 : max(R1, Rc[0]));
-      if (MF_DBG(32)) // timing probe: one unconditional addition per local dof, a barrier before each (wrong results)
-      {
-#pragma unroll
-        for (int j = 0; j < ND; ++j)
-        {
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          __syncthreads();
-          const int i = (iw[j >> 1] >> (16 * (j & 1))) & 0xffff;
-          __hip_atomic_fetch_add(&ys[i], ye[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
-      }
+      const int R2 = Rc[2], R1 = max(R2, Rc[1]), R0 = max(R1, Rc[0]);
       for (int r = 0; r < R0; ++r)
       {
         // hipcc (ROCm 7.2) emitted this loop's s_barrier WITHOUT a wait for the LDS store of the round before (seen in
@@ -857,7 +832,7 @@ __global__ __launch_bounds__(T, (ND == 20 ? 3 : 1)) void k_mf_action(const MfArg
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __syncthreads();
     // dofs interior to the block: final values; shared ones: this block's partial sum
-    for (int d = tid; d < (MF_DBG(8) ? 0 : n_int); d += T)
+    for (int d = tid; d < n_int; d += T)
     {
       const int32_t g = A.dof_ids[dof_off + d];
       // bc->set(y.array(), std::nullopt, 0.0), src/cgpoisson_problem.cpp:207; the diagonal: 1.0 there
@@ -1027,11 +1002,7 @@ int plan_attempt(zzz_ctx* ctx, int nc, int T, int nloc_limit, bool* retry)
     if (lds > 48 * 1024)
       ZZZ_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_mf_assign), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     const int per_cu = std::max(1, std::min(16, (160 * 1024) / (lds + 256)));
-    int W = 64;
-#ifdef ZZZ_EXPERIMENTS
-    if (const char* e = getenv("ZZZ_MF_ASSIGN_W"))
-      W = std::max(1, std::min(64, atoi(e)));
-#endif
+    const int W = 64;
     hipLaunchKernelGGL(k_mf_assign, dim3((unsigned)std::min<int64_t>(nb, 256ll * per_cu)), dim3(64), lds, s, sorted_cells.p,
                        ctx->cell_dofs.p, nd, ncells, nc, T, nsb, cw, H, W, nb, M.mf_cell.p);
     ZZZ_HIP(ctx, hipGetLastError());
@@ -1150,26 +1121,6 @@ int plan_attempt(zzz_ctx* ctx, int nc, int T, int nloc_limit, bool* retry)
   int32_t h_err = 0;
   ZZZ_HIP(ctx, hipMemcpyAsync(&h_err, nlmax.p + 1, sizeof(int32_t), hipMemcpyDeviceToHost, s));
   ZZZ_HIP(ctx, hipStreamSynchronize(s));
-#ifdef ZZZ_EXPERIMENTS
-  if (getenv("ZZZ_MF_PLAN_STATS"))
-  {
-    // quality of the step assignment: rounds per (block, step) = the most cells of the step at one dof
-    std::vector<uint8_t> hr((size_t)(nb * nsb * M.nrw * 4));
-    ZZZ_HIP(ctx, hipMemcpy(hr.data(), M.rmax.p, hr.size(), hipMemcpyDeviceToHost));
-    double sum = 0;
-    int worst = 0;
-    for (int64_t bs_ = 0; bs_ < nb * nsb; ++bs_)
-    {
-      int m = 0;
-      for (int j = 0; j < nd; ++j)
-        m = std::max(m, (int)hr[(size_t)bs_ * M.nrw * 4 + j]);
-      sum += m;
-      worst = std::max(worst, m);
-    }
-    fprintf(stderr, "[zzz] matrix-free plan: %lld blocks x %d steps, rounds per step: mean %.3f, worst %d\n", (long long)nb, nsb,
-            sum / (double)(nb * nsb), worst);
-  }
-#endif
   if (h_err)
     return fail(ctx, ZZZ_ERR_LIMIT, "matrix-free plan: a dof meets more than 254 cells of one step");
 
@@ -1257,12 +1208,8 @@ int mf_plan_build(zzz_ctx* ctx)
   // (the plan's own kernels put a block's index and rank words together in LDS: 4 (nd / 2 + (nd + 3) / 4) bytes per cell)
   while (nc / 2 >= T && (nc / 2) % T == 0 && (nd / 2 + (nd + 3) / 4) * 4 * nc > 150 * 1024)
     nc /= 2;
-  // LDS budget per workgroup: 64 KiB unless ZZZ_MF_LDS_KB says otherwise (160 KiB per CU)
-  int lds_kb = nd == 4 ? 40 : 64;
-#ifdef ZZZ_EXPERIMENTS
-  if (const char* e = getenv("ZZZ_MF_LDS_KB")) // measurement knob, tools build only
-    lds_kb = std::min(160, std::max(8, atoi(e)));
-#endif
+  // LDS budget per workgroup (160 KiB per CU)
+  const int lds_kb = nd == 4 ? 40 : 64;
   const int nloc_limit = std::min(65535, lds_kb * 1024 / (nd == 4 ? 40 : (nd == 20 ? 8 : 16)));
   for (;;)
   {
@@ -1335,11 +1282,6 @@ static int mf_run(zzz_ctx* ctx, bool diag, const double* u, double* y, double* p
   A.nc = M.nc;
   A.nsb = M.nsb;
   A.nloc_cap = M.nloc_max;
-  A.dbg = 0;
-#ifdef ZZZ_EXPERIMENTS
-  if (const char* e = getenv("ZZZ_MF_DEBUG"))
-    A.dbg = atoi(e);
-#endif
   int rc = ZZZ_OK;
 #define ZZZ_MF_T(ND_, DG_)                                                                                              \
   (M.threads == 128 ? mf_launch<ND_, 128, DG_>(ctx, A, grid, lds)                                                         \
@@ -1355,7 +1297,7 @@ static int mf_run(zzz_ctx* ctx, bool diag, const double* u, double* y, double* p
 #undef ZZZ_MF_T
   if (rc)
     return rc;
-  if (M.nshared > 0 && !(A.dbg & 16))
+  if (M.nshared > 0)
     hipLaunchKernelGGL(k_mf_finish, dim3(gf), dim3(256), 0, ctx->stream, M.sh_dof.p, M.sh_off.p, M.sh_flag.p, M.nshared, M.ypart.p, u,
                        y, partials ? partials + grid : nullptr, A.stop, diag ? 1.0 : 0.0);
   if (npartials)

@@ -607,13 +607,12 @@ __global__ void k_spmv_tiles(const rp_t* __restrict__ rowptr, int nrows, int64_t
 // their numbering need a handful of narrow bands per 2048-nonzero tile, so the column stream shrinks from
 // 4 to 2 bytes per nonzero (12 -> 10 B per nonzero of SpMV traffic).  A tile that does not fit keeps its
 // int32 columns: its descriptor gets .y = ~r1 and `nfallback` counts it.  One workgroup per tile.
-template <int TILE>
 __global__ __launch_bounds__(256) void k_tile_encode_cols(int4* __restrict__ tiles, int64_t ntiles,
                                                           const int32_t* __restrict__ cols, int offb,
                                                           uint16_t* __restrict__ cols16, int32_t* __restrict__ tile_base,
                                                           int32_t* __restrict__ nfallback)
 {
-  constexpr int PER = TILE / 256;
+  constexpr int PER = SPMV_TILE_NNZ / 256;
   const int NB = 1 << (16 - offb), W = 1 << offb;
   __shared__ int sbase[64];
   __shared__ int red[4];
@@ -733,12 +732,8 @@ int ensure_cols16(zzz_ctx* ctx)
   auto run = [&](int offb, int32_t* nfb) -> int {
     ZZZ_HIP(ctx, hipMemsetAsync(ctx->scr_c16.p, 0, sizeof(int32_t), s));
     const int g = grid_for(ctx->ntiles, 1, 256 * 8);
-    if (ctx->spmv_tile == 4096)
-      hipLaunchKernelGGL(k_tile_encode_cols<4096>, dim3(g), dim3(256), 0, s, reinterpret_cast<int4*>(ctx->tile_row.p),
-                         ctx->ntiles, ctx->cols.p, offb, ctx->cols16.p, ctx->tile_base.p, ctx->scr_c16.p);
-    else
-      hipLaunchKernelGGL(k_tile_encode_cols<2048>, dim3(g), dim3(256), 0, s, reinterpret_cast<int4*>(ctx->tile_row.p),
-                         ctx->ntiles, ctx->cols.p, offb, ctx->cols16.p, ctx->tile_base.p, ctx->scr_c16.p);
+    hipLaunchKernelGGL(k_tile_encode_cols, dim3(g), dim3(256), 0, s, reinterpret_cast<int4*>(ctx->tile_row.p), ctx->ntiles,
+                       ctx->cols.p, offb, ctx->cols16.p, ctx->tile_base.p, ctx->scr_c16.p);
     ZZZ_HIP(ctx, hipGetLastError());
     ZZZ_HIP(ctx, hipMemcpyAsync(nfb, ctx->scr_c16.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     ZZZ_HIP(ctx, hipStreamSynchronize(s));
@@ -788,7 +783,7 @@ int build_tiles_device(zzz_ctx* ctx, int max_block_cols)
     const double avg = ctx->nrows > 0 ? (double)ctx->nnz / (double)ctx->nrows : 0.0;
     ctx->spmv_lpr_shift = ctx->spmv_lpr_forced >= 0 ? ctx->spmv_lpr_forced : (avg >= 128.0 ? 3 : 0);
   }
-  const int64_t Ws = (int64_t)ctx->spmv_tile - maxrow - 2;
+  const int64_t Ws = (int64_t)SPMV_TILE_NNZ - maxrow - 2;
   const int64_t Wa = (int64_t)asm_tile_nnz(ctx) - maxblock;
   if (Ws < maxrow || Wa < maxblock || Wa < 1)
     return fail(ctx, ZZZ_ERR_LIMIT, "matrix rows too long for the kernel tiles (%d nonzeros per row)", maxrow);
@@ -1039,10 +1034,6 @@ __global__ __launch_bounds__(ADJ_W) void k_adj_window(const int32_t* __restrict_
 static void adjacency_find_runs(zzz_ctx* ctx)
 {
   ctx->adj_runs_n = 0;
-#ifdef ZZZ_EXPERIMENTS
-  if (getenv("ZZZ_ADJ_SORT")) // A/B knob (tools build): always the radix sort
-    return;
-#endif
   const int nd = ctx->nd;
   const int64_t nc = ctx->ncells;
   if (nc >= INT32_MAX)
@@ -1096,16 +1087,6 @@ static void adjacency_find_runs(zzz_ctx* ctx)
   ctx->adj_runs_n = nruns;
 }
 
-#define ZZZ_DBG(name)                                                                                                  \
-  do                                                                                                                   \
-  {                                                                                                                    \
-    if (getenv("ZZZ_DEBUG_SYNC"))                                                                                      \
-    {                                                                                                                  \
-      hipError_t e_ = hipStreamSynchronize(ctx->stream);                                                               \
-      fprintf(stderr, "[zzz dbg] %s: %s\n", name, hipGetErrorString(e_));                                              \
-      fflush(stderr);                                                                                                  \
-    }                                                                                                                  \
-  } while (0)
 // adjacency through the runs, enqueued without a host wait: whether every window fitted arrives in
 // ctx->adj_flag_host behind these kernels and is looked at the next time the build waits for the device anyway
 static int adjacency_by_runs(zzz_ctx* ctx)
@@ -1120,13 +1101,8 @@ static int adjacency_by_runs(zzz_ctx* ctx)
   ZZZ_HIP(ctx, hipMemsetAsync(flag, 0, sizeof(int32_t), s));
   hipLaunchKernelGGL(k_run_window_bounds, dim3(grid_for((int64_t)nruns * (nwin + 1), 256, 16384)), dim3(256), 0, s,
                      ctx->cell_dofs.p, nd, ctx->adj_runs.p, nruns, nwin, ctx->adj_run_lo.p);
-  if (getenv("ZZZ_DEBUG_SYNC"))
-    fprintf(stderr, "[zzz dbg] nruns %d nwin %d nb %d\n", nruns, nwin, nb);
-  ZZZ_DBG("k_run_window_bounds");
   hipLaunchKernelGGL(k_window_tot, dim3(grid_for(nwin)), dim3(256), 0, s, ctx->adj_run_lo.p, nruns, nwin, ctx->adj_win_base.p);
-  ZZZ_DBG("k_window_tot");
   hipLaunchKernelGGL(k_window_base, dim3(1), dim3(1024), 0, s, nwin, ctx->adj_win_base.p, flag);
-  ZZZ_DBG("k_window_base");
   hipLaunchKernelGGL(k_adj_window, dim3(nwin), dim3(ADJ_W), 0, s, ctx->cell_dofs.p, nd, ctx->adj_runs.p, nruns, ctx->adj_run_lo.p,
                      nwin, ctx->adj_win_base.p, nb, ctx->adj_off.p, ctx->adj_cells.p);
   ZZZ_HIP(ctx, hipMemcpyAsync(ctx->adj_flag_host, flag, sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -1246,14 +1222,12 @@ int pattern_build_device(zzz_ctx* ctx, bool* fallback)
   {
     if (int rc = adjacency_by_runs(ctx))
       return rc;
-    ZZZ_DBG("adjacency_by_runs");
   }
   else
   {
     ZZZ_HIP(ctx, rocprim::radix_sort_pairs<AdjSortConfig>(tmp.p, tb, ctx->cell_dofs.p, keys_out.p, cell_of.p, ctx->adj_cells.p, (size_t)N,
                                            0, (unsigned)end_bit, s));
     hipLaunchKernelGGL(k_adj_bounds, dim3(grid_for((N + 4) / 4)), dim3(256), 0, s, keys_out.p, N, nb, ctx->adj_off.p);
-    ZZZ_DBG("radix sort + k_adj_bounds");
   }
 
   // 2. pattern: count, scan, fill
@@ -1268,18 +1242,12 @@ int pattern_build_device(zzz_ctx* ctx, bool* fallback)
   bool counted = false;
   // (called after a device wait) a window of the sort-free adjacency did not fit: build again, sorting
   auto adjacency_overflowed = [&]() { return by_runs && ctx->adj_flag_host && *ctx->adj_flag_host != 0; };
-#ifdef ZZZ_EXPERIMENTS
-  const bool p1_thread_rows = !getenv("ZZZ_PATTERN_WAVE"); // A/B knob (tools build): P1 rows by wavefronts like P2 / P3
-#else
-  const bool p1_thread_rows = true;
-#endif
-  if (nd == 4 && stage && p1_thread_rows)
+  if (nd == 4 && stage)
   {
     // P1: one thread per row; scal[2] = "a row has more than ROW_T_CAP unique columns"
     int rc = build_adjT_offsets(ctx);
     if (rc)
       return rc;
-    ZZZ_DBG("build_adjT_offsets");
     // 8 workgroups per CU = 4 wavefronts per SIMD, what the kernel's 108 registers allow (a cap of 4 left half of that
     // occupancy unused: 2.98 -> ~2.0 ms)
     const dim3 tg((grid_for((int64_t)nb, ROW_T_BLOCK, 256 * 8) + 7) / 8 * 8);
@@ -1292,7 +1260,6 @@ int pattern_build_device(zzz_ctx* ctx, bool* fallback)
       else
         hipLaunchKernelGGL((k_row_pattern_thread4<32, 4096>), tg, dim3(ROW_T_BLOCK), 0, s, ctx->cell_dofs.p, ctx->adj_off.p,
                            ctx->adj_cells.p, nb, cnt.p, scal.p, scal.p + 2, stage, ctx->adjT_off.p, ctx->adjT_cells.p, ctx->adj_li.p);
-      ZZZ_DBG("k_row_pattern_thread4");
       ZZZ_HIP(ctx, hipMemcpyAsync(h, scal.p, sizeof(h), hipMemcpyDeviceToHost, s));
       ZZZ_HIP(ctx, hipStreamSynchronize(s));
       if (adjacency_overflowed())
@@ -1359,12 +1326,10 @@ int pattern_build_device(zzz_ctx* ctx, bool* fallback)
                        ctx->adj_cells.p, nb, cnt.p, scal.p, bptr.p, ctx->cols.p, scal.p + 1, (int32_t*)nullptr, (uint16_t*)nullptr,
                        (int32_t*)nullptr);
   ZZZ_HIP(ctx, hipGetLastError());
-  ZZZ_DBG("k_row_copy");
   // 3. tiles
   int rc = build_tiles_device(ctx, h[0]);
   if (rc)
     return rc;
-  ZZZ_DBG("build_tiles_device");
   ZZZ_HIP(ctx, hipStreamSynchronize(s));
   return ZZZ_OK;
 }

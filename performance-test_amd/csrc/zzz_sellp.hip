@@ -7,7 +7,6 @@
 #include <vector>
 
 #include "zzz_sellp.h"
-#include "zzz_cg_device.h"
 
 namespace zzz
 {
@@ -182,7 +181,7 @@ __global__ __launch_bounds__(SP_BLOCK, 8) void spmv_sellp_kernel(const int2* __r
                                                               const int* __restrict__ stop_flag,
                                                               const int32_t* __restrict__ group_list, int64_t nlist,
                                                               const double* __restrict__ rvec, int pstride, int nn_is_rr,
-                                                              TailArgs tail, ChebEpi epi, const int2* __restrict__ win_info,
+                                                              ChebEpi epi, const int2* __restrict__ win_info,
                                                               const int2* __restrict__ win_seg, const uint16_t* __restrict__ vcode,
                                                               const double* __restrict__ dict_g, int dict_n,
                                                               const int32_t* __restrict__ sd_info,
@@ -413,16 +412,6 @@ __global__ __launch_bounds__(SP_BLOCK, 8) void spmv_sellp_kernel(const int2* __r
       s1 = block_reduce_sum(dot_rx, red);
       s2 = block_reduce_sum(dot_nn, red);
     }
-    if (!CHEB && tail.parts)
-    {
-      // multi-GPU: the all-reduce of these sums happens in the tail of this launch (zzz_tail.h); output order
-      // (<r,x>, norm, <x,y>) for the single-reduction form, <x,y> alone otherwise
-      if (rvec)
-        tail_arrive(tail, s1, s2, sres);
-      else
-        tail_arrive(tail, sres, 0.0, 0.0);
-      return;
-    }
     if (threadIdx.x == 0)
     {
       if (!CHEB)
@@ -436,165 +425,6 @@ __global__ __launch_bounds__(SP_BLOCK, 8) void spmv_sellp_kernel(const int2* __r
   }
 }
 
-#ifdef ZZZ_EXPERIMENTS // measurement-only kernels: the tools build (libzzz_hip_exp.so), never the product library
-// ---- TIMING PROBE (ZZZ_EXP_WIN=<doubles>): what would an x window in LDS buy? ------------------------------------
-// The cost structure of a windowed product without its packer: per group of four slices the workgroup loads <doubles>
-// consecutive entries of x into LDS (coalesced 16-B loads), and every gather of the chunk loop reads LDS at a
-// pseudo-random index instead of global memory.  The RESULT IS WRONG by construction; only zzz_spmv_time may run it.
-template <bool NT>
-__global__ __launch_bounds__(SP_BLOCK) void spmv_sellp_win_probe_kernel(const int2* __restrict__ desc,
-                                                                    const double* __restrict__ svals,
-                                                                    const uint16_t* __restrict__ c16,
-                                                                    const int32_t* __restrict__ c32,
-                                                                    const int32_t* __restrict__ meta,
-                                                                    const double* __restrict__ x, double* __restrict__ y,
-                                                                    int nrows, int64_t nslices, double* __restrict__ partials,
-                                                                    int wlen, int lds_slots)
-{
-  extern __shared__ __attribute__((aligned(16))) double win[];
-  __shared__ double red[SP_BLOCK / 64];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int64_t ngroups = (nslices + 3) / 4;
-  double dot = 0.0;
-  for (int i = 0;; ++i)
-  {
-    const int64_t g = sp_xcd_item(ngroups, blockIdx.x, gridDim.x, i);
-    if (g < 0)
-      break;
-    __syncthreads();
-    {
-      int64_t base = g * 256 - wlen / 2;
-      if (base < 0)
-        base = 0;
-      if (base + wlen > nrows)
-        base = nrows > wlen ? nrows - wlen : 0;
-      base &= ~(int64_t)1;
-      const dbl2* __restrict__ src = reinterpret_cast<const dbl2*>(x + base);
-      dbl2* dst = reinterpret_cast<dbl2*>(win);
-      for (int k = threadIdx.x; k < wlen / 2; k += SP_BLOCK)
-        dst[k] = src[k];
-    }
-    __syncthreads();
-    const int s = __builtin_amdgcn_readfirstlane((int)(4 * g + wv));
-    if (s >= nslices)
-      continue;
-    const int2 ds = desc[s];
-    const int c0 = ds.x, nch = ds.y & 0xffffff, wl = ds.y >> 24;
-    const int r = s * 64 + lane < nrows ? s * 64 + lane : -1;
-    double sum = 0.0;
-    for (int j = 0; j < nch; ++j)
-    {
-      dbl2 v[4];
-      int cl[8];
-      if (j + 1 < nch || wl == 8)
-        read_chunk<NT, true>(c0 + j, 8, lane, svals, c16, c32, meta, v, cl);
-      else
-        read_chunk<NT, false>(c0 + j, wl, lane, svals, c16, c32, meta, v, cl);
-#pragma unroll
-      for (int e = 0; e < 8; ++e)
-      {
-        // the first lds_slots slots of every chunk gather from the window, the others from memory (a PARTIAL window)
-        const unsigned idx = (unsigned)cl[e] % (unsigned)wlen;
-        const double xv = e < lds_slots ? win[idx] : gather(x, min(cl[e], nrows - 1));
-        sum += ((e & 1) ? v[e >> 1].y : v[e >> 1].x) * xv;
-      }
-    }
-    if (r >= 0)
-    {
-      y[r] = sum;
-      dot += sum;
-    }
-  }
-  const double sres = block_reduce_sum(dot, red);
-  if (threadIdx.x == 0 && partials)
-    partials[blockIdx.x] = sres;
-}
-
-// ---- product fused with the direction update -------------------------------------------------------------
-// One CG iteration as TWO kernels instead of three: the head of iteration `it` (convergence test, k_update_p of
-// zzz_cg.hip) and the product w = A p, with p = z + b p_old formed on the fly where the product gathers it
-// (the same two roundings as k_update_p, so p, w and every scalar keep their bits), written once per owned row
-// into the OTHER p buffer (the gathers of other workgroups still read p_old), together with the pending
-// solution update x += alpha_{it-1} p_old (src/cg.h:68,82).  Ghost entries of p follow the same recurrence from the
-// ghost values of z, so the halo exchange of an iteration moves z instead of p.  An A/B variant (ZZZ_CG_FUSED=2):
-// measured slower than the three-kernel form at every size tried (cg_solve has the numbers), kept because it
-// pins the iteration's arithmetic from a second side -- tests demand identical bits from both forms.
-template <bool NT, bool PERM>
-__global__ __launch_bounds__(SP_BLOCK, 4) void spmv_sellp_dir_kernel(
-    const int2* __restrict__ desc, const double* __restrict__ svals, const uint16_t* __restrict__ c16,
-    const int32_t* __restrict__ c32, const int32_t* __restrict__ meta, const int32_t* __restrict__ perm,
-    const double* __restrict__ z, const double* __restrict__ p_old, double* __restrict__ p_new, double* __restrict__ xsol,
-    double* __restrict__ y, int nrows, int ncols, int64_t nslices, double* __restrict__ partials,
-    const int32_t* __restrict__ group_list, int64_t nlist, int ghost_update, CgState* __restrict__ st,
-    double* __restrict__ beta_hist, double* __restrict__ dp_hist, const double* __restrict__ alpha_hist, int it, CgParams P,
-    const double* __restrict__ pa, const double* __restrict__ pb, int np)
-{
-  __shared__ double red[SP_BLOCK / 64];
-  DirScalars S;
-  if (!cg_direction_scalars(st, beta_hist, dp_hist, it, P, pa, pb, np, red, S))
-    return;
-  const double bcoef = S.rz / S.bprev;
-  const double alpha = it > 0 ? alpha_hist[it - 1] : 0.0;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int64_t ngroups = group_list ? nlist : (nslices + 3) / 4;
-  double dot = 0.0;
-  for (int i = 0;; ++i)
-  {
-    const int64_t gi = sp_xcd_item(ngroups, blockIdx.x, gridDim.x, i);
-    if (gi < 0)
-      break;
-    const int64_t g = group_list ? group_list[gi] : gi;
-    const int s = __builtin_amdgcn_readfirstlane((int)(4 * g + wv));
-    if (s >= nslices)
-      continue;
-    int r = PERM ? perm[(int64_t)s * 64 + lane] : s * 64 + lane;
-    if (!PERM && r >= nrows)
-      r = -1;
-    const double po = r >= 0 ? p_old[r] : 0.0;
-    if (r >= 0 && it > 0)
-      xsol[r] = alpha * po + xsol[r]; // the previous iteration's solution update, also by the launch that stops
-    if (S.conv)
-      continue;
-    const double pn = r >= 0 ? bcoef * po + z[r] : 0.0;
-    const int2 ds = desc[s];
-    const int c0 = ds.x, nch = ds.y & 0xffffff, wl = ds.y >> 24;
-    double sum = 0.0;
-    for (int j = 0; j < nch; ++j)
-    {
-      const int w = j + 1 < nch ? 8 : wl;
-      dbl2 v[4];
-      int cl[8];
-      read_chunk<NT, false>(c0 + j, w, lane, svals, c16, c32, meta, v, cl);
-      double zv[8], pv[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e)
-      {
-        zv[e] = e < w ? gather(z, cl[e]) : 0.0;
-        pv[e] = e < w ? gather(p_old, cl[e]) : 0.0;
-      }
-#pragma unroll
-      for (int e = 0; e < 8; ++e)
-        if (e < w)
-          sum += ((e & 1) ? v[e >> 1].y : v[e >> 1].x) * (bcoef * pv[e] + zv[e]);
-    }
-    if (r >= 0)
-    {
-      p_new[r] = pn;
-      y[r] = sum;
-      dot += sum * pn;
-    }
-  }
-  if (S.conv)
-    return;
-  if (ghost_update) // ghost entries of the new direction (the launch that runs behind the halo of z)
-    for (int64_t k = nrows + blockIdx.x * (int64_t)SP_BLOCK + threadIdx.x; k < ncols; k += (int64_t)gridDim.x * SP_BLOCK)
-      p_new[k] = bcoef * p_old[k] + z[k];
-  const double sres = block_reduce_sum(dot, red);
-  if (threadIdx.x == 0)
-    partials[blockIdx.x] = sres;
-}
-
-#endif // ZZZ_EXPERIMENTS
 
 // ---- host side ------------------------------------------------------------------------------------------
 // A failed build leaves its form off (and the stream, where there is one, as it is).
@@ -602,15 +432,11 @@ bool sellp_special_build(zzz_ctx* ctx)
 {
   if (sellp_blk_build(ctx) != ZZZ_OK)
   {
-    if (getenv("ZZZ_DEBUG_SYNC"))
-      fprintf(stderr, "[zzz dbg] sellp_blk_build: %s\n", ctx->err.c_str());
     ctx->bk_on = false;
     (void)hipGetLastError();
   }
   if (sellp_win_build(ctx) != ZZZ_OK)
   {
-    if (getenv("ZZZ_DEBUG_SYNC"))
-      fprintf(stderr, "[zzz dbg] sellp_win_build: %s\n", ctx->err.c_str());
     ctx->bw_on = false;
     (void)hipGetLastError();
   }
@@ -635,8 +461,8 @@ bool sellp_active(zzz_ctx* ctx)
     // was a dead wait until the poll's time-out (round 5, found by tools/soak_driver.sh: elasticity P2, two ranks).
     // The special forms first (block rows for block size 3, zzz_sellp_blk.hip; block windows for long scalar rows,
     // zzz_sellp_win.hip): where one of them serves the product, the stream's value dictionaries are not built -- the launches
-    // that still take the generic kernel (a folded all-reduce: tools build only) read its values as doubles.  7.6 ms per
-    // assembly at 6.2 M rows of P3, 3 ms at C4.  A failed build leaves the stream as it is.
+    // that still take the generic kernel read its values as doubles.  7.6 ms per assembly at 6.2 M rows of P3, 3 ms at C4.
+    // A failed build leaves the stream as it is.
     ctx->sp_dict_done = true;
     ctx->sp_dict_on = ctx->sp_sd_on = ctx->sp_sd_all = false;
     ctx->sp_dict_n = 0;
@@ -692,17 +518,13 @@ static bool sp_stream_nt(const zzz_ctx* ctx)
   return (double)sellp_stream_bytes(ctx) + 48.0 * (double)(ctx->n_owned + ctx->n_ghost) * ctx->bs > 200.0e6;
 }
 
-// plain: the launch carries no Chebyshev epilogue and no folded all-reduce, so the specialised kernels (one-chunk slices,
-// block rows) may serve it; otherwise the generic kernel runs and keeps its eight workgroups per CU
+// plain: the launch carries no Chebyshev epilogue, so the specialised kernels (one-chunk slices, block rows) may serve it;
+// otherwise the generic kernel runs and keeps its eight workgroups per CU
 static int sp_grid(const zzz_ctx* ctx, int64_t ngroups, bool sr, bool plain)
 {
   // persistent workgroups: as many as are resident at once (a second round of a grid that is not would run on part of the chip)
   const int pw = plain ? sellp_pipe_wgs(ctx, sr) : 0;
   int64_t gs = 256 * (pw ? pw : 8); // (1024 or 1536 workgroups at the per-rank size: no faster)
-#ifdef ZZZ_EXPERIMENTS
-  if (const char* e = getenv("ZZZ_SP_WGS_PER_CU")) // how the product's time depends on the wavefronts in flight
-    gs = 256 * std::max(1, std::min(8, atoi(e)));
-#endif
   const int64_t need = (ngroups + 7) / 8 * 8;
   if (gs > need)
     gs = need;
@@ -714,7 +536,7 @@ static int sp_grid(const zzz_ctx* ctx, int64_t ngroups, bool sr, bool plain)
 template <bool DOT>
 static void launch_one(zzz_ctx* ctx, int grid, const double* x, double* y, double* partials, const int* stop,
                        const int32_t* group_list, int64_t nlist, const double* rvec, int nn_is_rr,
-                       const TailArgs& tail = TailArgs(), const ChebEpi* epi = nullptr, int special = 0)
+                       const ChebEpi* epi = nullptr, int special = 0)
 {
   // load policy by stream size, as for the tile kernel: a stream that stays in the 256 MiB Infinity Cache from
   // one CG iteration to the next is read with plain loads, a larger one with non-temporal loads
@@ -727,7 +549,7 @@ static void launch_one(zzz_ctx* ctx, int grid, const double* x, double* y, doubl
     return;
   if (special == 2 && launch_sellp_win(ctx, DOT, nt, grid, x, y, partials, stop, group_list, nlist, rvec, nn_is_rr, epi))
     return;
-  if (!epi && !tail.parts && launch_sellp_pipe(ctx, DOT, nt, grid, x, y, partials, stop, group_list, nlist, rvec, nn_is_rr))
+  if (!epi && launch_sellp_pipe(ctx, DOT, nt, grid, x, y, partials, stop, group_list, nlist, rvec, nn_is_rr))
     return;
   const int2* off = reinterpret_cast<const int2*>(ctx->sp_desc.p);
   const int2* winfo = reinterpret_cast<const int2*>(ctx->sp_win_info.p);
@@ -741,13 +563,13 @@ static void launch_one(zzz_ctx* ctx, int grid, const double* x, double* y, doubl
       hipLaunchKernelGGL((spmv_sellp_kernel<DOT, NT, PERM, true, WIN, DICT>), dim3(grid), dim3(SP_BLOCK), LDSB,         \
                          ctx->stream, off, ctx->sp_vals.p, ctx->sp_codes16.p, ctx->sp_codes32.p, ctx->sp_meta.p,           \
                          ctx->sp_perm.p, x, y, (int)ctx->nrows, ctx->nslices, partials, stop, group_list, nlist, rvec,     \
-                         SPMV_PSTRIDE, nn_is_rr, TailArgs(), *epi, winfo, wseg, VC_, DG_, ctx->sp_dict_n,                  \
+                         SPMV_PSTRIDE, nn_is_rr, *epi, winfo, wseg, VC_, DG_, ctx->sp_dict_n,                              \
                          ctx->sp_sd_info.p, ctx->sp_sd_off.p);                                                         \
     else                                                                                                               \
       hipLaunchKernelGGL((spmv_sellp_kernel<DOT, NT, PERM, false, WIN, DICT>), dim3(grid), dim3(SP_BLOCK), LDSB,        \
                          ctx->stream, off, ctx->sp_vals.p, ctx->sp_codes16.p, ctx->sp_codes32.p, ctx->sp_meta.p,           \
                          ctx->sp_perm.p, x, y, (int)ctx->nrows, ctx->nslices, partials, stop, group_list, nlist, rvec,     \
-                         SPMV_PSTRIDE, nn_is_rr, tail, ChebEpi(), winfo, wseg, VC_, DG_, ctx->sp_dict_n,                   \
+                         SPMV_PSTRIDE, nn_is_rr, ChebEpi(), winfo, wseg, VC_, DG_, ctx->sp_dict_n,                         \
                          ctx->sp_sd_info.p, ctx->sp_sd_off.p);                                                         \
   } while (0)
 #define ZZZ_SP_GO5(NT, PERM, WIN, LDSB)                                                                                \
@@ -795,58 +617,20 @@ int launch_sellp(zzz_ctx* ctx, const double* x, double* y, double* partials, int
                  const ChebEpi* epi)
 {
   const int* stop = partials ? reinterpret_cast<const int*>(ctx->state.p) : nullptr; // CgState::converged
-  const bool plain = !epi && !(partials && ctx->tail_armed);
-  const bool no_tail = !(partials && ctx->tail_armed); // (the special forms carry the Chebyshev epilogue, not the folded all-reduce)
-  const int blk = no_tail ? (sellp_blk_serves(ctx) ? 1 : (sellp_win_serves(ctx) ? 2 : 0)) : 0;
+  const int blk = sellp_blk_serves(ctx) ? 1 : (sellp_win_serves(ctx) ? 2 : 0); // (the special forms carry the Chebyshev epilogue)
   if (!blk)
     if (int rc = sellp_need_generic(ctx))
       return rc;
   const int gs = blk == 1 ? sellp_blk_grid(ctx, ctx->bk_slices) : blk == 2 ? sellp_win_grid(ctx, ctx->bw_nblk)
-                          : sp_grid(ctx, (ctx->nslices + 3) / 4, (partials && rvec), plain);
-#ifdef ZZZ_EXPERIMENTS
-  const char* e = ctx->timing_only ? getenv("ZZZ_EXP_WIN") : nullptr; // timing probe, wrong results by construction (see
-  if (e)                                                               // the kernel): inside zzz_spmv_time only
-  {
-    const int wlen = atoi(e) & ~1;
-    if (wlen >= 256 && wlen <= 8192 && !ctx->sp_sorted && !epi && wlen < ctx->nrows && ctx->sp_win_max == 0 && !blk)
-    {
-      const int lds_slots = getenv("ZZZ_EXP_WIN_SLOTS") ? atoi(getenv("ZZZ_EXP_WIN_SLOTS")) : 8;
-      const int per_cu = std::max(1, std::min(8, (int)(160 * 1024 / ((size_t)wlen * 8 + 512))));
-      const int grid = std::min(gs, 256 * per_cu);
-      const bool nt = sp_stream_nt(ctx);
-      const int2* off = reinterpret_cast<const int2*>(ctx->sp_desc.p);
-      if (nt)
-        hipLaunchKernelGGL(spmv_sellp_win_probe_kernel<true>, dim3(grid), dim3(SP_BLOCK), (size_t)wlen * 8, ctx->stream, off,
-                           ctx->sp_vals.p, ctx->sp_codes16.p, ctx->sp_codes32.p, ctx->sp_meta.p, x, y, (int)ctx->nrows,
-                           ctx->nslices, partials, wlen, lds_slots);
-      else
-        hipLaunchKernelGGL(spmv_sellp_win_probe_kernel<false>, dim3(grid), dim3(SP_BLOCK), (size_t)wlen * 8, ctx->stream, off,
-                           ctx->sp_vals.p, ctx->sp_codes16.p, ctx->sp_codes32.p, ctx->sp_meta.p, x, y, (int)ctx->nrows,
-                           ctx->nslices, partials, wlen, lds_slots);
-      if (npartials)
-        *npartials = grid;
-      ZZZ_HIP(ctx, hipGetLastError());
-      return ZZZ_OK;
-    }
-  }
-#endif
+                          : sp_grid(ctx, (ctx->nslices + 3) / 4, (partials && rvec), !epi);
   if (partials)
   {
-    TailArgs T;
-    if (ctx->tail_armed)
-    {
-      T = ctx->tail;
-      T.expected = gs;
-      T.base = 0;
-      ctx->tail_armed = false;
-      ctx->tail_used = true;
-    }
-    launch_one<true>(ctx, gs, x, y, partials, stop, nullptr, 0, rvec, nn_is_rr, T, epi, blk);
+    launch_one<true>(ctx, gs, x, y, partials, stop, nullptr, 0, rvec, nn_is_rr, epi, blk);
     if (npartials)
       *npartials = gs;
   }
   else
-    launch_one<false>(ctx, gs, x, y, nullptr, stop, nullptr, 0, nullptr, 0, TailArgs(), epi, blk);
+    launch_one<false>(ctx, gs, x, y, nullptr, stop, nullptr, 0, nullptr, 0, epi, blk);
   ZZZ_HIP(ctx, hipGetLastError());
   return ZZZ_OK;
 }
@@ -857,9 +641,8 @@ int launch_sellp_overlapped(zzz_ctx* ctx, double* x, double* y, double* partials
                             int nn_is_rr, const ChebEpi* epi)
 {
   const int* stop = partials ? reinterpret_cast<const int*>(ctx->state.p) : nullptr;
-  const bool plain = !epi && !(partials && ctx->tail_armed);
-  const bool no_tail = !(partials && ctx->tail_armed);
-  const int blk = !no_tail ? 0 : (sellp_blk_serves(ctx) && ctx->bk_have_split) ? 1 : (sellp_win_serves(ctx) && ctx->bw_have_split) ? 2 : 0;
+  const bool plain = !epi;
+  const int blk = (sellp_blk_serves(ctx) && ctx->bk_have_split) ? 1 : (sellp_win_serves(ctx) && ctx->bw_have_split) ? 2 : 0;
   if (!blk)
     if (int rc = sellp_need_generic(ctx))
       return rc;
@@ -876,28 +659,15 @@ int launch_sellp_overlapped(zzz_ctx* ctx, double* x, double* y, double* partials
   const int g_bd = gb ? (blk ? special_grid(gb) : sp_grid(ctx, gb, (partials && rvec), plain)) : 0;
   if (partials && (size_t)(g_in + g_bd) > (size_t)SPMV_PSTRIDE)
     return fail(ctx, ZZZ_ERR_ARG, "partials buffer too small");
-  TailArgs Ti, Tb;
-  if (partials && ctx->tail_armed)
-  {
-    // one ticket over both launches: the workgroup that arrives last (in the boundary launch, or in the interior
-    // one when no group touches a ghost column) finishes the reduction
-    Ti = ctx->tail;
-    Ti.expected = g_in + g_bd;
-    Ti.base = 0;
-    Tb = Ti;
-    Tb.base = g_in;
-    ctx->tail_armed = false;
-    ctx->tail_used = true;
-  }
   int rc = comm_halo_begin(ctx, x);
   if (rc)
     return rc;
   if (gi)
   {
     if (partials)
-      launch_one<true>(ctx, g_in, x, y, partials, stop, list_in, gi, rvec, nn_is_rr, Ti, epi, blk);
+      launch_one<true>(ctx, g_in, x, y, partials, stop, list_in, gi, rvec, nn_is_rr, epi, blk);
     else
-      launch_one<false>(ctx, g_in, x, y, nullptr, stop, list_in, gi, nullptr, 0, TailArgs(), epi, blk);
+      launch_one<false>(ctx, g_in, x, y, nullptr, stop, list_in, gi, nullptr, 0, epi, blk);
   }
   rc = comm_halo_end(ctx);
   if (rc)
@@ -905,83 +675,14 @@ int launch_sellp_overlapped(zzz_ctx* ctx, double* x, double* y, double* partials
   if (gb)
   {
     if (partials)
-      launch_one<true>(ctx, g_bd, x, y, partials + g_in, stop, list_bd, gb, rvec, nn_is_rr, Tb, epi, blk);
+      launch_one<true>(ctx, g_bd, x, y, partials + g_in, stop, list_bd, gb, rvec, nn_is_rr, epi, blk);
     else
-      launch_one<false>(ctx, g_bd, x, y, nullptr, stop, list_bd, gb, nullptr, 0, TailArgs(), epi, blk);
+      launch_one<false>(ctx, g_bd, x, y, nullptr, stop, list_bd, gb, nullptr, 0, epi, blk);
   }
   if (npartials)
     *npartials = g_in + g_bd;
   ZZZ_HIP(ctx, hipGetLastError());
   return ZZZ_OK;
 }
-#ifdef ZZZ_EXPERIMENTS
-// the fused product + direction kernel on the whole matrix, or (partitioned matrix) interior groups, halo of z,
-// boundary groups.  Partials of <p,w>: interior workgroups first.
-int launch_sellp_dir(zzz_ctx* ctx, double* z, const double* p_old, double* p_new, double* xsol, double* y, double* partials,
-                     int* npartials, int it, const CgParams& P, const double* pa, const double* pb, int np, bool overlap)
-{
-  if (int rc = sellp_need_generic(ctx))
-    return rc;
-  const bool nt = ctx->spmv_auto ? sp_stream_nt(ctx) : (ctx->spmv_variant & 1) != 0;
-  const int2* off = reinterpret_cast<const int2*>(ctx->sp_desc.p);
-  const int ncols = (int)ctx->nloc();
-  auto go = [&](int grid, const int32_t* list, int64_t nlist, double* parts, int ghost) {
-#define ZZZ_SPD_GO(NT, PERM)                                                                                           \
-  hipLaunchKernelGGL((spmv_sellp_dir_kernel<NT, PERM>), dim3(grid), dim3(SP_BLOCK), 0, ctx->stream, off, ctx->sp_vals.p,  \
-                     ctx->sp_codes16.p, ctx->sp_codes32.p, ctx->sp_meta.p, ctx->sp_perm.p, z, p_old, p_new, xsol, y,   \
-                     (int)ctx->nrows, ncols, ctx->nslices, parts, list, nlist, ghost, ctx->state.p, ctx->beta_hist.p, \
-                     ctx->dp_hist.p, ctx->alpha_hist.p, it, P, pa, pb, np)
-    if (ctx->sp_sorted)
-    {
-      if (nt)
-        ZZZ_SPD_GO(true, true);
-      else
-        ZZZ_SPD_GO(false, true);
-    }
-    else
-    {
-      if (nt)
-        ZZZ_SPD_GO(true, false);
-      else
-        ZZZ_SPD_GO(false, false);
-    }
-#undef ZZZ_SPD_GO
-  };
-  if (overlap && ctx->have_group_split)
-  {
-    const int64_t gi = ctx->n_groups_interior, gb = ctx->n_groups_boundary;
-    int g_in = gi ? sp_grid(ctx, gi, false, false) : 0;
-    if (g_in > 256 * 7 && ctx->nneigh > 0)
-      g_in = 256 * 7; // room for the exchange's kernel beside the persistent workgroups (launch_spmv_overlapped)
-    const int g_bd = gb ? sp_grid(ctx, gb, false, false) : 8;
-    if ((size_t)(g_in + g_bd) > (size_t)SPMV_PSTRIDE)
-      return fail(ctx, ZZZ_ERR_ARG, "partials buffer too small");
-    int rc = comm_halo_begin(ctx, z);
-    if (rc)
-      return rc;
-    if (gi)
-      go(g_in, ctx->groups_interior.p, gi, partials, 0);
-    rc = comm_halo_end(ctx);
-    if (rc)
-      return rc;
-    go(g_bd, ctx->groups_boundary.p, gb, partials + g_in, 1); // also with no boundary group: the ghost entries of p
-    *npartials = g_in + g_bd;
-  }
-  else
-  {
-    if (ctx->comm)
-    {
-      int rc = comm_halo_forward(ctx, z);
-      if (rc)
-        return rc;
-    }
-    const int gs = sp_grid(ctx, (ctx->nslices + 3) / 4, false, false);
-    go(gs, nullptr, 0, partials, ctx->n_ghost > 0 ? 1 : 0);
-    *npartials = gs;
-  }
-  ZZZ_HIP(ctx, hipGetLastError());
-  return ZZZ_OK;
-}
-#endif // ZZZ_EXPERIMENTS
 ZZZ_PRELOAD_TU(sellp)
 } // namespace zzz

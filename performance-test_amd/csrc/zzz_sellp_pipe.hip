@@ -497,7 +497,7 @@ int sellp_pairs_build(zzz_ctx* ctx)
 
 // ---- host side -----------------------------------------------------------------------------------------------------
 // Does the kernel serve this context's stream, and with how many workgroups per CU?  0: the generic kernel.  (What a launch
-// adds: no Chebyshev epilogue, no folded all-reduce.)
+// adds: no Chebyshev epilogue.)
 int sellp_pipe_wgs(const zzz_ctx* ctx, bool sr)
 {
   if (!ctx->sellp_pipe || !ctx->sp_pipe_ok || ctx->sp_sorted || ctx->sp_chunks <= 0)

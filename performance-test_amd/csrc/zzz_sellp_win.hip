@@ -24,7 +24,7 @@
 //
 // When it applies: scalar matrices and those of block size 3 the block-row form declined (elasticity P2 / P3: their scalar rows
 // are long rows like any), natural row order of the stream, at least BW_MIN_AVG entries per row on average, every block
-// within the LDS budget, no folded all-reduce on the launch (tools build).  Chebyshev-Jacobi terms ride on it as epilogues (CHEB).
+// within the LDS budget.  Chebyshev-Jacobi terms ride on it as epilogues (CHEB).
 // ZZZ_SELLP_BWIN: 0 never, 1 (default) by size (rows of ~48 entries from 300 000 rows on, of ~27 from 800 000: below, the generic
 // product is as fast or faster -- a few blocks for 256 CUs), 2 always.
 #include <algorithm>
@@ -291,9 +291,8 @@ __global__ __launch_bounds__(BW_THREADS) void k_bw_block(const int32_t* __restri
                                                          const int64_t* __restrict__ chunk0, int32_t* __restrict__ perm,
                                                          int2* __restrict__ desc, int32_t* __restrict__ wlist,
                                                          uint16_t* __restrict__ ccode, uint8_t* __restrict__ gflag, int* __restrict__ info,
-                                                         uint32_t* __restrict__ cpack, uint8_t* __restrict__ cflag, int phases, int32_t ncols)
+                                                         uint32_t* __restrict__ cpack, uint8_t* __restrict__ cflag, int32_t ncols)
 {
-  // (phases: 4 = everything; the tools build stops a block after the first walk (1), the compaction (2), the sort (3) to time them)
   __shared__ union
   {
     int32_t hcol[BW_WHASH]; // the set of columns (-1: empty)
@@ -406,8 +405,6 @@ __global__ __launch_bounds__(BW_THREADS) void k_bw_block(const int32_t* __restri
       __syncthreads();
       continue;
     }
-    if (phases < 2)
-      continue;
     // The window in ascending column order: every thread takes its sixteen slots of the set as (column, slot) pairs -- an empty
     // slot's key is beyond every column --, the workgroup sorts the 16 384 pairs by key (rocPRIM's block radix sort, in the set's
     // own LDS: the columns are in registers by then), and pair number i < n_win is window entry i.  (An indirect bitonic sort of
@@ -426,14 +423,7 @@ __global__ __launch_bounds__(BW_THREADS) void k_bw_block(const int32_t* __restri
         slots[k] = (uint16_t)h;
       }
       __syncthreads(); // (the set's LDS becomes the sort's)
-      if (phases < 3)
-        continue;
       bw_sort_pairs(keys, slots, u.sort, (unsigned)key_bits);
-      if (phases < 4)
-      {
-        __syncthreads();
-        continue;
-      }
       const int64_t w0 = (int64_t)b * BW_WCAP;
 #pragma unroll
       for (int k = 0; k < PER; ++k)
@@ -1008,8 +998,6 @@ static int bw_structure(zzz_ctx* ctx)
   ZZZ_HIP(ctx, hipMemcpyAsync(h, info.p, sizeof(h), hipMemcpyDeviceToHost, s));
   ZZZ_HIP(ctx, hipMemcpyAsync(&tot[0], ctx->bw_chunk0.p + nblk, sizeof(int64_t), hipMemcpyDeviceToHost, s));
   ZZZ_HIP(ctx, hipStreamSynchronize(s));
-  if (getenv("ZZZ_DEBUG_SYNC"))
-    fprintf(stderr, "[zzz dbg] bw_structure pass 1: flag %d chunks %lld nblk %d\n", h[0], (long long)tot[0], nblk);
   if (h[0] || tot[0] <= 0)
     return ZZZ_OK; // declined: a row of 2^11 entries or more
   ZZZ_HIP(ctx, ctx->bw_perm.alloc((size_t)nblk * BW_R));
@@ -1023,14 +1011,9 @@ static int bw_structure(zzz_ctx* ctx)
   ZZZ_HIP(ctx, ctx->bw_cflag.alloc((size_t)nblk));
   ZZZ_HIP(ctx, ctx->bw_vflag.alloc((size_t)nblk));
   ZZZ_HIP(ctx, hipMemsetAsync(ctx->bw_cpack.p, 0, (size_t)tot[0] * 768, s));
-  int phases = 4;
-#ifdef ZZZ_EXPERIMENTS
-  if (const char* e = getenv("ZZZ_BW_PHASES")) // timing of the builder's phases (an incomplete structure: the form then declines)
-    phases = atoi(e);
-#endif
   hipLaunchKernelGGL(k_bw_block, dim3(grid), dim3(BW_THREADS), 0, s, ctx->bw_order.p, nrows, nblk, ctx->rowptr.p, ctx->cols.p,
                      ctx->bw_skey.p, ctx->bw_blk_wn.p, ctx->bw_chunk0.p, ctx->bw_perm.p, reinterpret_cast<int2*>(ctx->bw_desc.p),
-                     ctx->bw_wlist.p, ctx->bw_ccode.p, ctx->bw_gflag.p, info.p, ctx->bw_cpack.p, ctx->bw_cflag.p, phases, (int32_t)ctx->nloc());
+                     ctx->bw_wlist.p, ctx->bw_ccode.p, ctx->bw_gflag.p, info.p, ctx->bw_cpack.p, ctx->bw_cflag.p, (int32_t)ctx->nloc());
   ZZZ_HIP(ctx, hipGetLastError());
   ZZZ_HIP(ctx, hipMemcpyAsync(h, info.p, sizeof(h), hipMemcpyDeviceToHost, s));
   ZZZ_HIP(ctx, hipStreamSynchronize(s));
@@ -1039,10 +1022,7 @@ static int bw_structure(zzz_ctx* ctx)
     memcpy(&we, h + 6, sizeof(we));
     tot[1] = (int64_t)we;
   }
-  if (getenv("ZZZ_DEBUG_SYNC"))
-    fprintf(stderr, "[zzz dbg] bw_structure pass 2: flag %d ghost blocks %d window %lld max window %d bad blocks %d\n", h[0], h[1],
-            (long long)tot[1], h[3], h[4]);
-  if (h[0] || tot[1] <= 0 || phases < 4)
+  if (h[0] || tot[1] <= 0)
     return ZZZ_OK; // declined: a block beyond the LDS budget
   // interior / boundary blocks for the halo-compute overlap of a partitioned matrix
   ctx->bw_n_interior = ctx->bw_n_boundary = 0;
@@ -1089,8 +1069,6 @@ int sellp_win_build(zzz_ctx* ctx)
   // about equal at 118 k), rows of ~27 from 0.9 M on (0.027 against 0.031; 0.022 against 0.016 at 275 k)
   if (ctx->sellp_bwin == 1 && ctx->nrows < (ctx->nnz >= 40 * ctx->nrows ? 300000 : 800000))
     return ZZZ_OK;
-  if (getenv("ZZZ_DEBUG_SYNC"))
-    fprintf(stderr, "[zzz dbg] sellp_win_build: rows %lld nnz %lld knob %d\n", (long long)ctx->nrows, (long long)ctx->nnz, ctx->sellp_bwin);
   if (ctx->nrows >= (int64_t)1 << 31 || ctx->order == 0 || ctx->ncells <= 0)
     return ZZZ_OK;
   hipStream_t s = ctx->stream;
@@ -1100,8 +1078,6 @@ int sellp_win_build(zzz_ctx* ctx)
     if (int rc = bw_structure(ctx))
       return rc;
   }
-  if (getenv("ZZZ_DEBUG_SYNC"))
-    fprintf(stderr, "[zzz dbg] bw structure ok %d\n", (int)ctx->bw_struct_ok);
   if (!ctx->bw_struct_ok)
     return ZZZ_OK;
   const int32_t nblk = ctx->bw_nblk;
@@ -1120,8 +1096,6 @@ int sellp_win_build(zzz_ctx* ctx)
   int32_t h[8];
   ZZZ_HIP(ctx, hipMemcpyAsync(h, info.p, sizeof(h), hipMemcpyDeviceToHost, s));
   ZZZ_HIP(ctx, hipStreamSynchronize(s));
-  if (getenv("ZZZ_DEBUG_SYNC"))
-    fprintf(stderr, "[zzz dbg] bw values: flag %d max dictionary %d bad blocks %d of %d\n", h[2], h[3], h[4], nblk);
   if (h[2])
     return ZZZ_OK; // a block with more distinct values than the table holds (an irregular mesh): the stream serves the product
   if (!ctx->bw_lds_attr)

@@ -3,7 +3,7 @@
 // Replaces PETSc MatMult inside KSPSolve (src/poisson_problem.cpp:177) and the `action` of
 // linalg::cg (src/cg.h:62).  HBM-bound: 12 B per nonzero streamed once, x gathered through L2.
 //
-// Layout of the work: the nonzero stream is cut into row-aligned tiles of <= TILE_NNZ entries and
+// Layout of the work: the nonzero stream is cut into row-aligned tiles of <= SPMV_TILE_NNZ entries and
 // <= BLOCK rows.  A workgroup streams one tile's values and columns with 16-B / 8-B per-lane
 // contiguous loads (every 128-B line of the matrix is fetched exactly once, fully coalesced),
 // multiplies by the gathered x and parks the products in LDS; then one thread per row adds its
@@ -34,15 +34,6 @@ __device__ inline int64_t xcd_tile(int64_t ntiles, int b, int nb, int i)
   return t < hi ? t : -1;
 }
 
-// LDS-only workgroup barrier: orders the LDS writes/reads of the tile without draining the
-// global loads already issued for the NEXT tile (a plain __syncthreads() waits for vmcnt(0)).
-__device__ inline void lds_barrier()
-{
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
 template <bool NT, typename T>
 __device__ inline T stream_load(const T* p)
 {
@@ -50,8 +41,7 @@ __device__ inline T stream_load(const T* p)
 }
 
 // One tile descriptor = {first row, end row, first nonzero, end nonzero}: one 16-B load per tile.
-// TILE = nonzeros per tile; PIPE = issue the next tile's matrix loads before reducing this one.
-template <bool DOT, bool NT, bool PIPE, int TILE>
+template <bool DOT, bool NT>
 __global__ __launch_bounds__(SPMV_BLOCK, 8) void spmv_tile_kernel(const rp_t* __restrict__ rowptr,
                                                                const int32_t* __restrict__ cols,
                                                                const double* __restrict__ vals,
@@ -78,6 +68,7 @@ __global__ __launch_bounds__(SPMV_BLOCK, 8) void spmv_tile_kernel(const rp_t* __
   // partitioned matrix); ntiles is then the length of the list
   if (stop_flag && *stop_flag) // CG already converged: the host is a few iterations ahead
     return;
+  constexpr int TILE = SPMV_TILE_NNZ;
   __shared__ __attribute__((aligned(16))) double prod[TILE + 16];
   __shared__ double red[SPMV_BLOCK / 64];
   constexpr int NPASS = TILE / (2 * SPMV_BLOCK);
@@ -153,16 +144,7 @@ __global__ __launch_bounds__(SPMV_BLOCK, 8) void spmv_tile_kernel(const rp_t* __
       }
     }
     const int64_t tn = xcd_tile(ntiles, blockIdx.x, gridDim.x, i + 1);
-    if (PIPE && tn >= 0)
-    {
-      const int64_t ti = tile_list ? tile_list[tn] : tn;
-      td = tiles[ti];
-      issue(td, ti);
-    }
-    if (PIPE)
-      lds_barrier();
-    else
-      __syncthreads();
+    __syncthreads();
     if (lpr_shift == 0)
     {
       for (int rr = r; rr < r1; rr += SPMV_BLOCK) // one row per thread unless the rows are very short
@@ -171,7 +153,7 @@ __global__ __launch_bounds__(SPMV_BLOCK, 8) void spmv_tile_kernel(const rp_t* __
         const double xr_ = (rr == r) ? xr : (DOT ? x[rr] : 0.0);
         // products are added in column order (the serial CPU order); 8 LDS reads in flight at a time
         double sum = 0.0;
-        constexpr int QB = PIPE ? 4 : 8; // the pipelined form holds the next tile's loads in registers meanwhile
+        constexpr int QB = 8;
         for (int k = ra_; k < rb_; k += QB)
         {
           double q[QB];
@@ -235,12 +217,9 @@ __global__ __launch_bounds__(SPMV_BLOCK, 8) void spmv_tile_kernel(const rp_t* __
         }
       }
     }
-    if (PIPE)
-      lds_barrier();
-    else
-      __syncthreads();
+    __syncthreads();
     t = tn;
-    if (!PIPE && t >= 0)
+    if (t >= 0)
     {
       const int64_t ti = tile_list ? tile_list[t] : t;
       td = tiles[ti];
@@ -288,45 +267,21 @@ static void launch_variant(zzz_ctx* ctx, int grid, const double* x, double* y, d
   // bit 4 of the variant: ignore the packed columns (A/B and parity of the two index streams)
   const uint16_t* c16 = (ctx->have_cols16 && !(ctx->spmv_variant & 16)) ? ctx->cols16.p : nullptr;
   const int col_max = (int)ctx->nloc() - 1; // nloc() counts scalar entries (a clamp bs times too far read past the end of x)
-#define ZZZ_SPMV_GO(NT, PIPE, TILE)                                                                                   \
-  hipLaunchKernelGGL((spmv_tile_kernel<DOT, NT, PIPE, TILE>), dim3(grid), dim3(SPMV_BLOCK), 0, ctx->stream,           \
+#define ZZZ_SPMV_GO(NT)                                                                                               \
+  hipLaunchKernelGGL((spmv_tile_kernel<DOT, NT>), dim3(grid), dim3(SPMV_BLOCK), 0, ctx->stream,                       \
                      ctx->rowptr.p, ctx->cols.p, ctx->vals.p, x, y, tiles, nt, nnz_even, partials, stop, tile_list,    \
                      rvec, SPMV_PSTRIDE, nn_is_rr, c16, ctx->tile_base.p, ctx->cols16_offb, col_max, ctx->spmv_lpr_shift)
-  // bit 0: non-temporal matrix loads, bit 1: pipelined tiles.  Unless a variant was forced, the load
+  // bit 0: non-temporal matrix loads.  Unless a variant was forced, the load
   // policy follows the matrix size: a matrix that fits the 256 MiB Infinity Cache is re-read from it
   // every CG iteration, and non-temporal loads would throw that away (measured, 1.25 M-dof P1 matrix,
   // 221 MB: 44 us plain vs 55 us nt; 2.5 M dofs and up: nt 2-8 % faster).
   int var = ctx->spmv_variant;
   if (ctx->spmv_auto)
     var = (var & ~1) | (12.0 * (double)ctx->nnz > 300.0e6 ? 1 : 0);
-#ifdef ZZZ_EXPERIMENTS
-  // the tools build keeps the variants that were measured and lost: tiles of 4096 nonzeros (they miss the register target
-  // of eight wavefronts per SIMD) and the software-pipelined tile loop (no gain: eight workgroups per CU cover the latency)
-  if (ctx->spmv_tile == 4096)
-  {
-    switch (var & 3)
-    {
-    case 0: ZZZ_SPMV_GO(false, false, 4096); break;
-    case 1: ZZZ_SPMV_GO(true, false, 4096); break;
-    case 2: ZZZ_SPMV_GO(false, true, 4096); break;
-    default: ZZZ_SPMV_GO(true, true, 4096); break;
-    }
-  }
-  else if (var & 2)
-  {
-    if (var & 1)
-      ZZZ_SPMV_GO(true, true, 2048);
-    else
-      ZZZ_SPMV_GO(false, true, 2048);
-  }
+  if (var & 1)
+    ZZZ_SPMV_GO(true);
   else
-#endif
-  {
-    if (var & 1)
-      ZZZ_SPMV_GO(true, false, 2048);
-    else
-      ZZZ_SPMV_GO(false, false, 2048);
-  }
+    ZZZ_SPMV_GO(false);
 #undef ZZZ_SPMV_GO
 }
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Times the matrix-free action (csrc/zzz_matfree.hip) and the cg.h solve on it at the cgpoisson sizes of BASELINE's
 configs: P1 10 M dofs (c2's mesh) and P3 6.2 M dofs (c5's per-GPU share).  Knobs through the environment:
-ZZZ_MF_NC / ZZZ_MF_T / ZZZ_MF_LDS_KB (plan geometry), ZZZ_MF_LEGACY=1 (the two-pass kernels of rounds 1-3).
+ZZZ_MF_NC / ZZZ_MF_T (plan geometry), ZZZ_MF_LEGACY=1 (the two-pass kernels of rounds 1-3).
 usage: mf_bench.py [p1|p2|p3|small] ..."""
 import json
 import os

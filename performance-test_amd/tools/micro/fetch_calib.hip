@@ -1,7 +1,7 @@
 // Calibration of rocprofv3's FETCH_SIZE / WRITE_SIZE on gfx950 (verdict item 6): kernels that move a KNOWN number
 // of bytes from a buffer larger than every cache, each exactly once, in the access shapes of this library's kernels.  Run under
 //   rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d out -- ./fetch_calib
-// (and once more with WRITE_SIZE); performance-test_amd/tools/r06/fetch_calib.sh turns the counter rows into bytes-per-unit factors.
+// (and once more with WRITE_SIZE); the counter rows divided by the known bytes give the bytes-per-unit factors.
 //   hipcc -O3 --offload-arch=gfx950 -o fetch_calib fetch_calib.hip
 //   k_stream16   : every lane one 16-B load, lanes contiguous (the CG vector kernels, the code streams of the products)
 //   k_stream16nt : the same with non-temporal loads

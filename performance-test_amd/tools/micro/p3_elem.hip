@@ -3,7 +3,7 @@
 // one pass is a difference -- can the table entries come through the scalar cache instead of LDS broadcast reads?
 //   A  two copies in LDS, broadcast reads (what k_mf_action does).  NOT representative here: outside the action kernel the
 //      compiler hoists the LDS reads and spills 1 500 vector registers; in k_mf_action the same code takes 168 registers and
-//      the element phase 0.085 ms at 1.36 M cells (tools/mf_phases.sh)
+//      the element phase 0.085 ms at 1.36 M cells (measured with the action's other phases switched off)
 //   B  constant memory, the mode loop ROLLED and every entry multiplied (no zero skipped: the mode is a run-time index)
 //   C  as B in sections of 20 entries with the next section requested before the current one is used
 //   D  constant memory, unrolled, zeros skipped at compile time (the compiler schedules the scalar loads)

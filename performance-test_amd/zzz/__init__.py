@@ -121,12 +121,8 @@ def hip():
         L.zzz_cg_history.argtypes = [C.c_void_p, C.c_int, _f64p]
         L.zzz_profile_get.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
         L.zzz_spmv_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
-        # (tools/ab_product.sh loads an older build of the library beside the current one: ZZZ_AB_OLD tolerates the entry
-        # points that build does not have yet; without it a missing symbol is an error, as everywhere)
-        if hasattr(L, "zzz_spmv_values_info") or not os.environ.get("ZZZ_AB_OLD"):
-            L.zzz_spmv_values_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
-        if hasattr(L, "zzz_spmv_values_info2") or not os.environ.get("ZZZ_AB_OLD"):
-            L.zzz_spmv_values_info2.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]
+        L.zzz_spmv_values_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        L.zzz_spmv_values_info2.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]
         L.zzz_internal_order_download.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
         L.zzz_comm_unique_id.argtypes = [C.c_void_p]
         L.zzz_comm_init.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
@@ -577,9 +573,6 @@ class Context:
         """how the operator stream holds its values: dict(form = 'doubles' | 'dictionary in memory' | 'dictionary in LDS',
         distinct values, bytes per product in that form, bytes per product as doubles)"""
         info = (C.c_int64 * 10)()
-        if os.environ.get("ZZZ_AB_OLD") and not hasattr(self.L, "zzz_spmv_values_info2"):
-            return dict(form="doubles", distinct_values=0, bytes_per_product=0, bytes_per_product_as_doubles=0,
-                        one_chunk_kernel=False, workgroups_per_cu=8, block_rows=False, row_windows=False, special_form="", block_table_entries=0, block_chunks=0, block_form=0)
         self._ck(self.L.zzz_spmv_values_info2(self.h, 10, info))
         return dict(form=("doubles", "dictionary in memory", "dictionary in LDS", "slice dictionaries")[int(info[0])], distinct_values=int(info[1]),
                     bytes_per_product=int(info[2]), bytes_per_product_as_doubles=int(info[3]),
@@ -597,12 +590,6 @@ class Context:
         info = (C.c_int64 * 8)()
         self._ck(self.L.zzz_spmv_info(self.h, info))
         return int(info[4])
-
-    def cg_fused(self):
-        """did the last solve run the fused product + direction kernel (two kernels per iteration)?"""
-        info = (C.c_int64 * 4)()
-        self._ck(self.L.zzz_cg_info(self.h, info))
-        return bool(info[0])
 
     def internal_order(self):
         """(perm, kind): perm[i] = caller index of the library's internal owned block dof i (identity when the caller's

@@ -11,28 +11,6 @@ CASES = sorted(glob.glob(os.path.join(GOLD, "*_p[123]_*.npz")))
 SUPPORTED_ORDERS = (1, 2, 3)
 
 
-def in_tools_build(fn):
-    """The measurement-only code paths (ZZZ_TAIL, ZZZ_CG_FUSED=2, pipelined / 4096-nonzero tiles, the measurement knobs) are
-    compiled under -DZZZ_EXPERIMENTS into libzzz_hip_exp.so (`make exp`), not into the product library: a test of them
-    re-runs itself in a child process that loads that build through ZZZ_HIP_LIB."""
-    import functools
-    import subprocess
-    import sys
-
-    @functools.wraps(fn)
-    def wrapper(*a, **k):
-        exp = os.path.join(zzz.PKG, "libzzz_hip_exp.so")
-        if os.environ.get("ZZZ_HIP_LIB") == exp:
-            return fn(*a, **k)
-        if not os.path.exists(exp):
-            pytest.skip("libzzz_hip_exp.so (make -C performance-test_amd exp) is absent")
-        out = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", "-p", "no:cacheprovider",
-                              f"{os.path.abspath(sys.modules[fn.__module__].__file__)}::{fn.__name__}"], env=dict(os.environ, ZZZ_HIP_LIB=exp),
-                             capture_output=True, text=True, timeout=1800)
-        assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-1000:]
-    return wrapper
-
-
 @pytest.fixture(scope="module")
 def ctx():
     assert zzz.device_count() >= 1, "no GPU visible: these tests must not pass on a fallback"
@@ -69,9 +47,9 @@ def _internal_system(rp, cl, v, perm, bs):
     return B.indptr.astype(np.int64), B.indices.astype(np.int32), v[(B.data - 1).astype(np.int64)], sperm
 
 
-def _spmv_variant_case(variant, tile):
-    old = {k: os.environ.get(k) for k in ("ZZZ_SPMV_VARIANT", "ZZZ_SPMV_TILE")}
-    os.environ["ZZZ_SPMV_VARIANT"], os.environ["ZZZ_SPMV_TILE"] = str(variant), str(tile)
+def _spmv_variant_case(variant):
+    old = os.environ.get("ZZZ_SPMV_VARIANT")
+    os.environ["ZZZ_SPMV_VARIANT"] = str(variant)
     try:
         zo.set_num_threads(1)
         for problem, order, dims in (("poisson", 1, (11, 9, 10)), ("elasticity", 2, (3, 3, 4)), ("poisson", 3, (3, 4, 3))):
@@ -90,11 +68,10 @@ def _spmv_variant_case(variant, tile):
                 assert abs(it - oit) <= 2
                 assert np.linalg.norm(c.vec_download(zzz.VEC_U) - ou) <= 1e-6 * np.linalg.norm(ou)
     finally:
-        for k, val in old.items():
-            if val is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = val
+        if old is None:
+            os.environ.pop("ZZZ_SPMV_VARIANT", None)
+        else:
+            os.environ["ZZZ_SPMV_VARIANT"] = old
 
 
 # (problem, order, n): cubes of n^3 cells either side of every size rule that picks a form of the product by itself
@@ -105,4 +82,4 @@ _SWEEP = [("poisson", 1, 40), ("poisson", 1, 56), ("poisson", 1, 66), ("poisson"
 
 
 
-__all__ = ['CASES', 'GOLD', 'SUPPORTED_ORDERS', '_SWEEP', '_internal_system', '_spmv_variant_case', '_upload_arrays', 'ctx', 'glob', 'in_tools_build', 'np', 'os', 'pytest', 'zo', 'zzz']
+__all__ = ['CASES', 'GOLD', 'SUPPORTED_ORDERS', '_SWEEP', '_internal_system', '_spmv_variant_case', '_upload_arrays', 'ctx', 'glob', 'np', 'os', 'pytest', 'zo', 'zzz']

@@ -266,37 +266,6 @@ def test_rccl_path_single_rank(ctx):
         assert it3 == it0 and rn3 == rn0
 
 
-@in_tools_build
-def test_allreduce_folded_into_the_producers_tail_keeps_every_bit():
-    """ZZZ_TAIL=1 (csrc/zzz_tail.h): the scalar all-reduce of a multi-GPU iteration done by the last-arriving workgroup of
-    the product / of k_update_xr instead of a kernel of its own -- same summation tree, same mailbox protocol: identical
-    iteration counts, norm histories and solutions, in both CG forms, with more partials than one pass of the tree
-    (> 512 workgroups).  An A/B variant, off by default (measured 1 us slower per iteration at the 8-GPU per-rank size)."""
-    P = zzz.Part("poisson", 1, 60, 60, 61)
-    res = {}
-    try:
-        for tail in ("0", "1"):
-            os.environ["ZZZ_TAIL"] = tail
-            with zzz.Context(0) as c:
-                c.comm_init(1, 0, zzz.comm_unique_id())
-                c.upload_part(P)
-                c.upload_halo(P)
-                assert c.comm_p2p_attach(c.comm_p2p_export())
-                c.pattern_build()
-                c.assemble_matrix(zzz.FORM_POISSON)
-                c.assemble_vector(zzz.FORM_POISSON)
-                for sr in (False, True):
-                    it, rn, r0 = c.cg_solve(pc=zzz.PC_JACOBI, rtol=1e-8, single_reduction=sr)
-                    res[(tail, sr)] = (it, rn, r0, c.cg_history(it + 1), c.vec_download(zzz.VEC_U))
-    finally:
-        os.environ.pop("ZZZ_TAIL", None)
-    for sr in (False, True):
-        a, b = res[("0", sr)], res[("1", sr)]
-        assert a[0] == b[0] and a[1] == b[1] and a[2] == b[2] and a[0] > 50
-        np.testing.assert_array_equal(a[3], b[3])
-        np.testing.assert_array_equal(a[4], b[4])
-
-
 @pytest.mark.parametrize("problem,order,dims", [("poisson", 1, (12, 10, 14)), ("poisson", 2, (6, 5, 7)),
                                                 ("poisson", 3, (4, 3, 5)), ("elasticity", 1, (6, 6, 6)),
                                                 ("elasticity", 2, (3, 3, 4))])
@@ -439,49 +408,6 @@ def test_single_reduction_cg_breakdown_and_limits(ctx):
     ctx.vec_upload(zzz.VEC_B, np.zeros(G.n_owned))
     it, rn, r0 = ctx.cg_solve(pc=zzz.PC_JACOBI, single_reduction=True)
     assert it == 0 and rn == 0.0 and np.all(ctx.vec_download(zzz.VEC_U) == 0.0)
-
-
-@in_tools_build
-def test_fused_direction_kernel_keeps_every_bit():
-    """Two kernels per iteration (the product fused with p = z + b p and the pending x update, chosen for
-    cache-resident loops) against the three-kernel form: the same operations on the same operands, so the
-    iteration count, the whole residual history and the solution are bit-identical -- for KSPCG with each norm
-    type, for src/cg.h, on natural and length-sorted streams."""
-    keys = ("ZZZ_CG_FUSED", "ZZZ_SELLP", "ZZZ_SELLP_WIN")
-    old = {k: os.environ.get(k) for k in keys}
-    try:
-        os.environ["ZZZ_SELLP_WIN"] = "0"  # the fused kernel gathers from memory: an A/B variant of window-free streams
-        for problem, order, dims, sellp in (("poisson", 1, (17, 15, 19), "1"), ("elasticity", 1, (7, 6, 8), "1"),
-                                            ("poisson", 2, (7, 6, 5), "3"), ("poisson", 3, (4, 4, 5), "2")):
-            P = zzz.Part(problem, order, *dims)
-            res = {}
-            for fused in ("0", "2"):
-                os.environ["ZZZ_CG_FUSED"], os.environ["ZZZ_SELLP"] = fused, sellp
-                with zzz.Context(0) as c:
-                    c.upload_part(P)
-                    c.pattern_build()
-                    c.assemble_matrix(P.form)
-                    c.assemble_vector(P.form)
-                    out = []
-                    for kw in (dict(pc=zzz.PC_JACOBI, rtol=1e-8), dict(pc=zzz.PC_NONE, norm=zzz.NORM_UNPRECONDITIONED, rtol=1e-7),
-                               dict(pc=zzz.PC_JACOBI, norm=zzz.NORM_NATURAL, rtol=1e-8), dict(pc=zzz.PC_JACOBI, rtol=1e-30, max_it=9),
-                               dict(variant=zzz.CG_CGH, pc=zzz.PC_NONE, rtol=1e-6, max_it=100)):
-                        if kw.get("variant") == zzz.CG_CGH:
-                            c.vec_upload(zzz.VEC_U, np.zeros(P.n_owned * P.bs))
-                        it, rn, r0 = c.cg_solve(**kw)
-                        assert c.cg_fused() == (fused == "2")
-                        out.append((it, rn, r0, c.cg_history(it + 1), c.vec_download(zzz.VEC_U)))
-                    res[fused] = out
-            for a, b in zip(res["0"], res["2"]):
-                assert a[0] == b[0] and a[1] == b[1] and a[2] == b[2]
-                np.testing.assert_array_equal(a[3], b[3])
-                np.testing.assert_array_equal(a[4], b[4])
-    finally:
-        for k, val in old.items():
-            if val is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = val
 
 
 @pytest.mark.parametrize("order,dims,nc,t", [

@@ -121,8 +121,6 @@ def test_knob_combinations_keep_results(seed):
     are in the draw), Jacobi and Chebyshev-Jacobi solves with the default's iteration count +-2 and solution to 1e-7.
     ZZZ_TEST_SEEDS=<n> draws more combinations (a soak run of 400 passes)."""
     rng = np.random.default_rng(1000 + seed)
-    # (the knobs of the PRODUCT library; the tools build's extra ones -- ZZZ_CG_FUSED, ZZZ_SPMV_TILE, pipelined tiles,
-    # ZZZ_ASM_LPR, ZZZ_VGRID_PER, ZZZ_TAIL -- have tests of their own that load that build)
     # (ZZZ_SELLP_FORMS: a mask of the code-free chunk forms, 1 affine, 2 aligned, 4 periodic; ZZZ_SELLP=4: the long-row packer)
     knobs = {"ZZZ_SPMV_VARIANT": ["1", "8", "9", "16", "17"], "ZZZ_SELLP": ["0", "2", "3", "4"], "ZZZ_SELLP_DROP": ["0"],
              "ZZZ_SELLP_FORMS": ["0", "1", "3", "4", "5", "6"], "ZZZ_SELLP_PIPE": ["0"],
@@ -224,14 +222,7 @@ def test_x_windows_of_the_operator_stream_keep_every_bit(order, dims):
 def test_spmv_kernel_variants_are_bit_exact(variant):
     """Every SpMV kernel variant of the product library (plain / non-temporal loads, the operator stream, int32 instead
     of packed 16-bit columns) adds a row's products in the same column order: bit-identical y, identical solve."""
-    _spmv_variant_case(variant, 2048)
-
-
-@in_tools_build
-def test_spmv_kernel_variants_of_the_tools_build_are_bit_exact():
-    """... and the ones the tools build keeps for re-measurement (pipelined tile loop, 4096-nonzero tiles)."""
-    for variant, tile in ((2, 2048), (3, 2048), (19, 2048), (0, 4096), (1, 4096), (3, 4096), (17, 4096)):
-        _spmv_variant_case(variant, tile)
+    _spmv_variant_case(variant)
 
 
 @pytest.mark.parametrize("cols16", ["0", "10", "11", "12", "13", "auto"])
