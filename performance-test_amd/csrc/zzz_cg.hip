@@ -228,105 +228,20 @@ __global__ void k_extract_dinv(const rp_t* __restrict__ rowptr, const int32_t* _
   }
 }
 
-// ---- the inverse diagonal as 16-bit codes (DinvCodes below): distinct values of d[0..n) into a small open-addressing set
-constexpr int DD_BITS = 14; // 16 384 slots for at most DZ_MAX = 2 048 values
-constexpr unsigned long long DD_EMPTY = ~0ull;
-__device__ inline unsigned dd_hash(unsigned long long b)
-{
-  b ^= b >> 29;
-  b *= 0x9E3779B97F4A7C15ull;
-  return (unsigned)(b >> (64 - DD_BITS));
-}
-// info[0] distinct values, info[1] too many (or a value with the bit pattern of the empty marker)
+// ---- the inverse diagonal as 16-bit codes (DinvCodes below): distinct values of d[0..n) into a set (zzz_valset.h) of
+// 16 384 slots for at most DZ_MAX = 2 048 values
+constexpr int DD_BITS = decltype(zzz_ctx::dd_set)::bits;
 __global__ __launch_bounds__(256) void k_dd_insert(const double* __restrict__ d, int64_t n, unsigned long long* __restrict__ table,
                                                    int* __restrict__ info, int limit)
 {
-  const int lane = threadIdx.x & 63;
   const int64_t span = (n + 63) & ~(int64_t)63;
   for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < span; i += gridDim.x * 256ll)
   {
-    if (__hip_atomic_load(&info[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-      return;
     const bool have = i < n;
     const unsigned long long b = have ? (unsigned long long)__double_as_longlong(d[i]) : 0ull;
-    bool need = have;
-    unsigned long long todo = __ballot(need);
-    while (todo) // one lane per distinct value of the wavefront goes to the table
-    {
-      const int src = __ffsll((long long)todo) - 1;
-      const unsigned long long bb = ((unsigned long long)(unsigned)__shfl((int)(b >> 32), src) << 32) | (unsigned)__shfl((int)(unsigned)b, src);
-      if (lane == src)
-      {
-        if (bb == DD_EMPTY)
-          info[1] = 1;
-        else
-        {
-          unsigned h = dd_hash(bb);
-          for (int probe = 0; probe < (1 << DD_BITS); ++probe)
-          {
-            const unsigned long long cur = __hip_atomic_load(&table[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (cur == bb)
-              break;
-            if (cur == DD_EMPTY)
-            {
-              const unsigned long long old = atomicCAS(&table[h], DD_EMPTY, bb);
-              if (old == DD_EMPTY)
-              {
-                if (atomicAdd(&info[0], 1) >= limit)
-                  info[1] = 1;
-                break;
-              }
-              if (old == bb)
-                break;
-            }
-            h = (h + 1) & ((1u << DD_BITS) - 1);
-          }
-        }
-      }
-      need = need && b != bb;
-      todo = __ballot(need);
-      if (__hip_atomic_load(&info[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-        return;
-    }
+    if (!valset_insert_wave<DD_BITS>(table, info, limit, b, have))
+      return;
   }
-}
-// codes in slot order (one workgroup); dict[code] = value
-__global__ __launch_bounds__(1024) void k_dd_number(const unsigned long long* __restrict__ table, int32_t* __restrict__ slot_code,
-                                                    double* __restrict__ dict, int* __restrict__ info)
-{
-  __shared__ int wsum[16];
-  if (info[1])
-    return;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  int mine = 0;
-  for (int k = threadIdx.x; k < (1 << DD_BITS); k += 1024)
-    mine += table[k] != DD_EMPTY ? 1 : 0;
-  int incl = mine;
-  for (int dd = 1; dd < 64; dd <<= 1)
-  {
-    const int t = __shfl_up(incl, dd);
-    if (lane >= dd)
-      incl += t;
-  }
-  if (lane == 63)
-    wsum[wv] = incl;
-  __syncthreads();
-  int off = 0;
-  for (int q = 0; q < wv; ++q)
-    off += wsum[q];
-  int code = off + incl - mine;
-  for (int k = threadIdx.x; k < (1 << DD_BITS); k += 1024)
-  {
-    const unsigned long long b = table[k];
-    if (b != DD_EMPTY)
-    {
-      slot_code[k] = code;
-      dict[code] = __longlong_as_double((long long)b);
-      ++code;
-    }
-  }
-  if (threadIdx.x == 1023)
-    info[2] = code;
 }
 __global__ __launch_bounds__(256) void k_dd_encode(const double* __restrict__ d, int64_t n, int64_t npad,
                                                    const unsigned long long* __restrict__ table, const int32_t* __restrict__ slot_code,
@@ -335,18 +250,7 @@ __global__ __launch_bounds__(256) void k_dd_encode(const double* __restrict__ d,
   if (info[1])
     return;
   for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < npad; i += gridDim.x * 256ll)
-  {
-    uint16_t c = 0;
-    if (i < n)
-    {
-      const unsigned long long b = (unsigned long long)__double_as_longlong(d[i]);
-      unsigned h = dd_hash(b);
-      while (table[h] != b)
-        h = (h + 1) & ((1u << DD_BITS) - 1);
-      c = (uint16_t)slot_code[h];
-    }
-    codes[i] = c;
-  }
+    codes[i] = i < n ? (uint16_t)valset_find<DD_BITS>(table, slot_code, (unsigned long long)__double_as_longlong(d[i])) : 0;
 }
 
 // r = b - w (w = A x0, or nothing when x0 == 0); z = dinv r; partials: pa = <r,z>, pb = test norm^2
@@ -876,25 +780,19 @@ struct EventRing
 static int dinv_codes_build(zzz_ctx* ctx, int64_t n, DinvCodes& dzc)
 {
   hipStream_t s = ctx->stream;
-    const int64_t npad = (n + 1) & ~(int64_t)1;
-    ZZZ_HIP(ctx, ctx->dd_table.reserve((size_t)1 << DD_BITS));
-    ZZZ_HIP(ctx, ctx->dd_slot.reserve((size_t)1 << DD_BITS));
-    ZZZ_HIP(ctx, ctx->dd_dict.reserve((size_t)DZ_MAX));
-    ZZZ_HIP(ctx, ctx->dd_codes.reserve((size_t)npad));
-    ZZZ_HIP(ctx, ctx->dd_info.reserve(8));
-    ZZZ_HIP(ctx, hipMemsetAsync(ctx->dd_info.p, 0, 8 * sizeof(int32_t), s));
-    ZZZ_HIP(ctx, hipMemsetAsync(ctx->dd_table.p, 0xff, sizeof(unsigned long long) << DD_BITS, s));
-    const unsigned gd = (unsigned)std::min<int64_t>((n + 255) / 256, 4096);
-    hipLaunchKernelGGL(k_dd_insert, dim3(gd), dim3(256), 0, s, ctx->dinv.p, n, ctx->dd_table.p, ctx->dd_info.p, DZ_MAX);
-    hipLaunchKernelGGL(k_dd_number, dim3(1), dim3(1024), 0, s, ctx->dd_table.p, ctx->dd_slot.p, ctx->dd_dict.p, ctx->dd_info.p);
-    hipLaunchKernelGGL(k_dd_encode, dim3(gd), dim3(256), 0, s, ctx->dinv.p, n, npad, ctx->dd_table.p, ctx->dd_slot.p, ctx->dd_codes.p,
-                       ctx->dd_info.p);
-    int32_t h[4] = {0, 1, 0, 0};
-    ZZZ_HIP(ctx, hipMemcpyAsync(h, ctx->dd_info.p, sizeof(h), hipMemcpyDeviceToHost, s));
-    ZZZ_HIP(ctx, hipStreamSynchronize(s));
-    if (!h[1] && h[2] > 0 && h[2] <= DZ_MAX)
-      dzc = DinvCodes{reinterpret_cast<const uint32_t*>(ctx->dd_codes.p), ctx->dd_dict.p, ctx->r.p, h[2]};
-    return ZZZ_OK;
+  const int64_t npad = (n + 1) & ~(int64_t)1;
+  ValSet<DD_BITS, 0>& vs = ctx->dd_set;
+  ZZZ_HIP(ctx, vs.begin(DZ_MAX, s, ctx->retired));
+  ZZZ_HIP(ctx, ctx->dd_codes.reserve((size_t)npad));
+  const unsigned gd = (unsigned)std::min<int64_t>((n + 255) / 256, 4096);
+  hipLaunchKernelGGL(k_dd_insert, dim3(gd), dim3(256), 0, s, ctx->dinv.p, n, vs.table.p, vs.info.p, DZ_MAX);
+  vs.number(s);
+  hipLaunchKernelGGL(k_dd_encode, dim3(gd), dim3(256), 0, s, ctx->dinv.p, n, npad, vs.table.p, vs.slot.p, ctx->dd_codes.p, vs.info.p);
+  int nd = 0;
+  ZZZ_HIP(ctx, vs.finish(s, nd));
+  if (nd)
+    dzc = DinvCodes{reinterpret_cast<const uint32_t*>(ctx->dd_codes.p), vs.dict.p, ctx->r.p, nd};
+  return ZZZ_OK;
 }
 
 // bytes one CG iteration touches (operator + `nvec` vectors) against the Infinity Cache

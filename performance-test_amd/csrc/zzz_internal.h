@@ -153,6 +153,8 @@ struct MfPlan
 };
 } // namespace zzz
 
+#include "zzz_valset.h" // (after DevBuf: a set owns four of them)
+
 struct zzz_ctx
 {
   int device = 0;
@@ -282,13 +284,11 @@ struct zzz_ctx
   zzz::DevBuf<uint8_t> sp_wlast; // per slice: entries of the longest row in its last chunk (1..8)
   // value dictionary of the stream (zzz_sellp.hip, sp_dict_build): the matrices of a regular mesh hold a few hundred to a few
   // ten thousand DISTINCT values (10 M-dof P1 Poisson: ~1 300); where there are at most 65 535 the product reads a 16-bit
-  // code per entry (sp_vcode: [chunk][lane][8]) and looks the value up (sp_dict: code 0 = +0.0) -- the same doubles in the
+  // code per entry (sp_vcode: [chunk][lane][8]) and looks the value up (sp_dset.dict: code 0 = +0.0) -- the same doubles in the
   // same order, a quarter of the bytes.  More distinct values (an unstructured mesh): sp_dict_on stays false, sp_vals is read.
   zzz::DevBuf<uint16_t> sp_vcode;
-  zzz::DevBuf<double> sp_dict;
-  zzz::DevBuf<unsigned long long> sp_dict_table; // open-addressing set of the values' bit patterns (build only)
-  zzz::DevBuf<int32_t> sp_dict_slot;             // table slot -> code (build only)
-  zzz::DevBuf<int32_t> sp_dict_info;             // counters of the build
+  zzz::ValSet<18, 1> sp_dset;        // the values' set, dictionary (dict: code 0 = +0.0) and counters (zzz_valset.h)
+  zzz::DevBuf<int32_t> sp_dict_info; // [0..1] bytes a product reads in dictionary form, [2] slices that stay doubles (sp_sd_build)
   // per-slice dictionaries (long rows: k_sp_sd_build): 16-bit codes [chunk][lane][8], tables [slice][1024], entries per slice
   zzz::DevBuf<uint16_t> sp_vcode8;
   zzz::DevBuf<double> sp_sd_vals;
@@ -304,9 +304,7 @@ struct zzz_ctx
   bool sellp_early = true;       // ZZZ_SELLP_EARLY=0: pack the generic stream at every assembly, special forms at the first product (A/B)
   int sellp_dict = 1;       // ZZZ_SELLP_DICT=0: no value dictionary
   // Jacobi's inverse diagonal as 16-bit codes (zzz_cg.hip, DinvCodes)
-  zzz::DevBuf<unsigned long long> dd_table;
-  zzz::DevBuf<int32_t> dd_slot, dd_info;
-  zzz::DevBuf<double> dd_dict;
+  zzz::ValSet<14, 0> dd_set;
   zzz::DevBuf<uint16_t> dd_codes;
   int cg_dinv_codes = 1;          // ZZZ_CG_DINV_CODES: 0 never, 1 when the CG loop exceeds the Infinity Cache, 2 always
   int last_solve_dinv_codes = 0;  // distinct values of the inverse diagonal when the last solve ran on codes, else 0
@@ -345,9 +343,7 @@ struct zzz_ctx
   // matrix's distinct 3 x 3 blocks (copied into LDS by every workgroup), 16 block slots per node and chunk
   zzz::DevBuf<int32_t> bk_desc, bk_meta, bk_flags, bk_nch, bk_c0, bk_slot_code, bk_info, bk_list_interior, bk_list_boundary;
   zzz::DevBuf<uint16_t> bk_code, bk_ccode, bk_rows16;
-  zzz::DevBuf<unsigned long long> bk_vset;
-  zzz::DevBuf<int32_t> bk_vcode;
-  zzz::DevBuf<double> bk_vdict;
+  zzz::ValSet<13, 1> bk_vset; // form 2: the table's distinct values
   int bk_form = 1, bk_ndict = 0; // 1: the table's rows (nine doubles) in LDS; 2: rows of value offsets in memory, the values in LDS
   zzz::DevBuf<double> bk_tab;
   zzz::DevBuf<unsigned long long> bk_hash_tag, bk_hash_tag2, bk_hash_owner;

@@ -23,7 +23,7 @@ constexpr int SP_WIN_WORDS = 8192; // bitmap words of k_sp_windows (32 KiB of LD
 constexpr int SP_WIN_SPAN = (SP_WIN_WORDS - 2) * 32; // columns between a group's smallest and largest at most
 
 // per-slice value dictionaries (k_sp_sd_build)
-constexpr int SD_SLOTS = 2048, SD_MAX = 1024;
+constexpr int SD_BITS = 11, SD_SLOTS = 1 << SD_BITS, SD_MAX = 1024;
 
 // Column-code class of a chunk, two bits per chunk in the slice's mode word (sp_smode: chunk j of a slice at bits 2 j, 2 j + 1;
 // written by the packers from emit_chunk's mode).  What the pipelined product has to LOAD per lane for the chunk's columns:

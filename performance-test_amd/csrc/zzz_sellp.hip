@@ -478,8 +478,6 @@ bool sellp_active(zzz_ctx* ctx)
         ctx->sp_dict_on = false;
         (void)hipGetLastError();
         ctx->sp_vcode.release();
-        ctx->sp_dict_table.release();
-        ctx->sp_dict_slot.release();
       }
       if (sp_sd_build(ctx) != ZZZ_OK)
       {
@@ -558,7 +556,7 @@ static void launch_one(zzz_ctx* ctx, int grid, const double* x, double* y, doubl
   do                                                                                                                   \
   {                                                                                                                    \
     const uint16_t* VC_ = (DICT) == 3 ? ctx->sp_vcode8.p : ctx->sp_vcode.p;         \
-    const double* DG_ = (DICT) == 3 ? ctx->sp_sd_vals.p : ctx->sp_dict.p;                                               \
+    const double* DG_ = (DICT) == 3 ? ctx->sp_sd_vals.p : ctx->sp_dset.dict.p;                                         \
     if (epi)                                                                                                           \
       hipLaunchKernelGGL((spmv_sellp_kernel<DOT, NT, PERM, true, WIN, DICT>), dim3(grid), dim3(SP_BLOCK), LDSB,         \
                          ctx->stream, off, ctx->sp_vals.p, ctx->sp_codes16.p, ctx->sp_codes32.p, ctx->sp_meta.p,           \

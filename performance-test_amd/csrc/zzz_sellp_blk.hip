@@ -42,9 +42,8 @@ constexpr int BK_HASH_BITS = 18;         // open-addressing set of the distinct 
 constexpr int BK_HASH = 1 << BK_HASH_BITS;
 constexpr int BK_TAB_MAX = 2200;         // form 1: entries of the block table incl. the zero block: 2200 x 72 B = 158 400 B of LDS
 constexpr int BK_CODE_MAX = 65536;       // form 2: entries of the block table (16-bit codes), rows of nine value offsets in memory
-constexpr int BK_VAL_BITS = 13;          // form 2: set of the table's distinct VALUES (build only)
-constexpr int BK_VAL_HASH = 1 << BK_VAL_BITS;
-constexpr int BK_VAL_MAX = 2048;         // ... at most this many (the dictionary every workgroup copies into LDS: 16 KiB)
+constexpr int BK_VAL_BITS = decltype(zzz_ctx::bk_vset)::bits; // form 2: set of the table's distinct VALUES (zzz_valset.h)
+constexpr int BK_VAL_MAX = 2048;         // ... entries of its dictionary (every workgroup copies it into LDS: 16 KiB)
 constexpr int BK_THREADS = 1024;         // one workgroup per CU (the table takes its LDS), sixteen wavefronts
 
 // the nine values of block k of node r: rows 3 r + a at rp[a], block k of a row at entries 3 k .. 3 k + 2
@@ -203,39 +202,15 @@ __global__ __launch_bounds__(256) void k_bk_insert(const rp_t* __restrict__ rowp
   }
 }
 
-// pass 3: codes in slot order (deterministic), the table's rows from the owners; entry 0 = the zero block
+// pass 3: the codes (valset_number: the zero block is entry 0), the table's rows from the owners
 __global__ __launch_bounds__(1024) void k_bk_number(const unsigned long long* __restrict__ tag, const unsigned long long* __restrict__ owner,
                                                     const rp_t* __restrict__ rowptr, const unsigned long long* __restrict__ vals,
                                                     int32_t* __restrict__ slot_code, unsigned long long* __restrict__ tab,
                                                     int* __restrict__ info)
 {
-  __shared__ int wsum[16];
   if (info[1])
     return;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  constexpr int PER = BK_HASH / 1024; // consecutive slots per thread
-  int mine = 0;
-  for (int k = 0; k < PER; ++k)
-    mine += tag[threadIdx.x * PER + k] != 0ull ? 1 : 0;
-  int incl = mine;
-  for (int d = 1; d < 64; d <<= 1)
-  {
-    const int t = __shfl_up(incl, d);
-    if (lane >= d)
-      incl += t;
-  }
-  if (lane == 63)
-    wsum[wv] = incl;
-  __syncthreads();
-  int off = 1;
-  for (int q = 0; q < wv; ++q)
-    off += wsum[q];
-  int code = off + incl - mine;
-  for (int k = 0; k < PER; ++k)
-  {
-    const int h = threadIdx.x * PER + k;
-    if (tag[h] == 0ull)
-      continue;
+  const int n = valset_number<BK_HASH_BITS, 1>(tag, 0ull, [&](int h, int code, unsigned long long) {
     slot_code[h] = code;
     if (code < BK_CODE_MAX)
     {
@@ -248,106 +223,27 @@ __global__ __launch_bounds__(1024) void k_bk_number(const unsigned long long* __
       for (int i = 0; i < 9; ++i)
         tab[(int64_t)code * 9 + i] = B.b[i];
     }
-    ++code;
-  }
+  });
   if (threadIdx.x < 9)
     tab[threadIdx.x] = 0ull;
-  if (threadIdx.x == 1023)
+  if (threadIdx.x == 0)
   {
-    info[2] = code;
-    if (code > BK_CODE_MAX)
+    info[2] = n;
+    if (n > BK_CODE_MAX)
       info[1] = 2;
   }
 }
 
-// form 2 (more distinct blocks than the LDS table holds): the DISTINCT VALUES of the table's rows into a set, numbered in
-// slot order; then every row as nine byte offsets (value code x 8, 16 bits each) into that dictionary, 32 B per row
-__device__ inline unsigned bk_val_hash(unsigned long long b)
-{
-  b ^= b >> 29;
-  b *= 0x9E3779B97F4A7C15ull;
-  return (unsigned)(b >> (64 - BK_VAL_BITS));
-}
-
+// form 2 (more distinct blocks than the LDS table holds): the DISTINCT VALUES of the table's rows into a set; then every row
+// as nine byte offsets (value code x 8, 16 bits each) into its dictionary, 32 B per row
 __global__ __launch_bounds__(256) void k_bk_val_insert(const unsigned long long* __restrict__ tab, int n9,
-                                                       unsigned long long* __restrict__ vset, int* __restrict__ info)
+                                                       unsigned long long* __restrict__ vset, int* __restrict__ info, int limit)
 {
   for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < n9; k += gridDim.x * blockDim.x)
   {
     const unsigned long long b = tab[k];
-    if (b == 0ull)
-      continue; // +0.0 is offset 0 without the set
-    if (b == ~0ull)
-    {
-      info[1] = 5; // (the empty marker: no assembled value has this NaN pattern; met all the same: no dictionary)
-      continue;
-    }
-    unsigned h = bk_val_hash(b);
-    for (int probe = 0; probe < BK_VAL_HASH; ++probe)
-    {
-      unsigned long long cur = __hip_atomic_load(&vset[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (cur == ~0ull)
-      {
-        cur = atomicCAS(&vset[h], ~0ull, b);
-        if (cur == ~0ull)
-        {
-          if (atomicAdd(&info[3], 1) >= BK_VAL_MAX - 2)
-            info[1] = 5;
-          cur = b;
-        }
-      }
-      if (cur == b)
-        break;
-      h = (h + 1) & (BK_VAL_HASH - 1);
-      if (__hip_atomic_load(&info[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-        return;
-    }
-  }
-}
-
-__global__ __launch_bounds__(1024) void k_bk_val_number(const unsigned long long* __restrict__ vset, int32_t* __restrict__ vcode,
-                                                        unsigned long long* __restrict__ dict, int* __restrict__ info)
-{
-  __shared__ int wsum[16];
-  if (info[1])
-    return;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  constexpr int PER = BK_VAL_HASH / 1024;
-  int mine = 0;
-  for (int k = 0; k < PER; ++k)
-    mine += vset[threadIdx.x * PER + k] != ~0ull ? 1 : 0;
-  int incl = mine;
-  for (int d = 1; d < 64; d <<= 1)
-  {
-    const int t = __shfl_up(incl, d);
-    if (lane >= d)
-      incl += t;
-  }
-  if (lane == 63)
-    wsum[wv] = incl;
-  __syncthreads();
-  int off = 1; // (entry 0 is +0.0)
-  for (int q = 0; q < wv; ++q)
-    off += wsum[q];
-  int code = off + incl - mine;
-  for (int k = 0; k < PER; ++k)
-  {
-    const int h = threadIdx.x * PER + k;
-    const unsigned long long b = vset[h];
-    if (b == ~0ull)
-      continue;
-    vcode[h] = code;
-    if (code < BK_VAL_MAX)
-      dict[code] = b;
-    ++code;
-  }
-  if (threadIdx.x == 0)
-    dict[0] = 0ull;
-  if (threadIdx.x == 1023)
-  {
-    info[3] = code; // entries of the dictionary, +0.0 included
-    if (code > BK_VAL_MAX)
-      info[1] = 5;
+    if (b != 0ull) // (+0.0 is offset 0 without the set)
+      valset_insert<BK_VAL_BITS>(vset, info, limit, b);
   }
 }
 
@@ -368,12 +264,7 @@ __global__ __launch_bounds__(256) void k_bk_rows16(const unsigned long long* __r
     {
       const unsigned long long b = tab[(int64_t)r * 9 + i];
       if (b != 0ull)
-      {
-        unsigned h = bk_val_hash(b);
-        while (vset[h] != b)
-          h = (h + 1) & (BK_VAL_HASH - 1);
-        off[i] = (unsigned)vcode[h] * 8u;
-      }
+        off[i] = (unsigned)valset_find<BK_VAL_BITS>(vset, vcode, b) * 8u;
     }
     uint4v q0, q1;
     q0.x = off[0] | (off[1] << 16), q0.y = off[2] | (off[3] << 16), q0.z = off[4] | (off[5] << 16), q0.w = off[6] | (off[7] << 16);
@@ -842,7 +733,7 @@ __global__ __launch_bounds__(BK_THREADS) void spmv_blk3_kernel(const int2* __res
 // Declined (bk_on stays false, nothing else changes): another block size, sorted rows, more distinct blocks than the table
 // holds, columns beyond 16-bit codes, ZZZ_SELLP_BLK=0.
 // Set-up at C4 (1.33 M nodes): k_bk_insert 1.95 ms (the one walk over the values: lane per node, 1 080 B apart), k_bk_number
-// 0.37 ms, k_bk_fill 0.50 ms.
+// 0.29 ms (0.37 when each thread read a run of consecutive slots), k_bk_fill 0.50 ms.
 int sellp_blk_build(zzz_ctx* ctx)
 {
   ctx->bk_on = false;
@@ -898,25 +789,18 @@ int sellp_blk_build(zzz_ctx* ctx)
   if (ctx->bk_form == 2)
   {
     // more blocks than the LDS table holds: their distinct VALUES into a dictionary for LDS, the rows as offsets into it
-    ZZZ_HIP(ctx, ctx->bk_vset.alloc((size_t)BK_VAL_HASH));
-    ZZZ_HIP(ctx, ctx->bk_vcode.alloc((size_t)BK_VAL_HASH));
-    ZZZ_HIP(ctx, ctx->bk_vdict.alloc((size_t)BK_VAL_MAX));
+    ValSet<BK_VAL_BITS, 1>& vs = ctx->bk_vset;
+    ZZZ_HIP(ctx, vs.begin(BK_VAL_MAX, s, ctx->retired));
     ZZZ_HIP(ctx, ctx->bk_rows16.alloc((size_t)h[2] * 16));
-    ZZZ_HIP(ctx, hipMemsetAsync(ctx->bk_vset.p, 0xff, sizeof(unsigned long long) * BK_VAL_HASH, s));
     const unsigned long long* tabb = reinterpret_cast<const unsigned long long*>(ctx->bk_tab.p);
     hipLaunchKernelGGL(k_bk_val_insert, dim3((unsigned)std::min<int64_t>(((int64_t)h[2] * 9 + 255) / 256, 2048)), dim3(256), 0, s, tabb,
-                       h[2] * 9, ctx->bk_vset.p, info.p);
-    hipLaunchKernelGGL(k_bk_val_number, dim3(1), dim3(1024), 0, s, ctx->bk_vset.p, ctx->bk_vcode.p,
-                       reinterpret_cast<unsigned long long*>(ctx->bk_vdict.p), info.p);
+                       h[2] * 9, vs.table.p, vs.info.p, BK_VAL_MAX - 2);
+    vs.number(s);
     hipLaunchKernelGGL(k_bk_rows16, dim3((unsigned)std::min<int64_t>((h[2] + 255) / 256, 2048)), dim3(256), 0, s, tabb, h[2],
-                       ctx->bk_vset.p, ctx->bk_vcode.p, ctx->bk_rows16.p, info.p);
-    ZZZ_HIP(ctx, hipGetLastError());
-    int32_t h2[8];
-    ZZZ_HIP(ctx, hipMemcpyAsync(h2, info.p, sizeof(h2), hipMemcpyDeviceToHost, s));
-    ZZZ_HIP(ctx, hipStreamSynchronize(s));
-    if (h2[1] || h2[3] <= 0 || h2[3] > BK_VAL_MAX)
+                       vs.table.p, vs.slot.p, ctx->bk_rows16.p, vs.info.p);
+    ZZZ_HIP(ctx, vs.finish(s, ctx->bk_ndict));
+    if (!ctx->bk_ndict)
       return ZZZ_OK;
-    ctx->bk_ndict = h2[3];
   }
   // (the chunk index times 1024 codes stays below 2^31 elements only as int64: the kernels index with 64 bits)
   ZZZ_HIP(ctx, ctx->bk_desc.alloc(2 * (size_t)nsl + 2));
@@ -1016,7 +900,7 @@ bool launch_sellp_blk(zzz_ctx* ctx, bool dot, bool nt, int grid, const double* x
   a.pstride = SPMV_PSTRIDE;
   a.nn_is_rr = nn_is_rr;
   const size_t lds = f1 ? (size_t)ctx->bk_entries * 72 : (size_t)ctx->bk_ndict * 8;
-  const double* tabp = f1 ? ctx->bk_tab.p : ctx->bk_vdict.p;
+  const double* tabp = f1 ? ctx->bk_tab.p : ctx->bk_vset.dict.p;
 #define ZZZ_BK_GO3(DOT, SR, NT, FORM, CHEB, EPI)                                                                                   \
   hipLaunchKernelGGL((spmv_blk3_kernel<DOT, SR, NT, FORM, CHEB>), dim3(grid), dim3(BK_THREADS), lds, ctx->stream,                  \
                      reinterpret_cast<const int2*>(ctx->bk_desc.p), ctx->bk_meta.p, ctx->bk_flags.p, ctx->bk_code.p, ctx->bk_ccode.p,  \

@@ -17,17 +17,8 @@ struct Even2
 // ---- value dictionary -----------------------------------------------------------------------------------
 // The entries of the packed stream as (slice, chunk, lane, slot) with the values the product would load: slots of a
 // slice's last chunk beyond its width and lanes without a row are never loaded (and hold anything).
-constexpr int SP_DICT_BITS = 18;                        // table of 2^18 slots for at most 65 535 values
-constexpr unsigned long long SP_DICT_EMPTY = ~0ull;     // (a NaN pattern no assembled value has; met all the same: no dictionary)
+constexpr int SP_DICT_BITS = decltype(zzz_ctx::sp_dset)::bits; // table of 2^18 slots (zzz_valset.h)
 constexpr int SP_DICT_MAX = 65535;
-constexpr int SP_DICT_LDS_MAX = SP_DICT_LDS_ENTRIES;
-
-__device__ inline unsigned sp_dict_hash(unsigned long long b)
-{
-  b ^= b >> 29;
-  b *= 0x9E3779B97F4A7C15ull;
-  return (unsigned)(b >> (64 - SP_DICT_BITS));
-}
 
 // value of entry (chunk c of width w, lane, slot e) in the value blocks: [4][64 lanes][2]; the last entry of an odd width
 // sits alone, 8 B per lane (emit_chunk)
@@ -37,10 +28,7 @@ __device__ inline unsigned long long sp_value_bits(const double* __restrict__ sv
   return reinterpret_cast<const unsigned long long*>(svals)[c * 512 + at];
 }
 
-// info[0] distinct values so far, info[1] overflow / unusable.  The lanes of a slice mostly hold the same value in a slot:
-// one lane per distinct value of the wavefront goes to the table; the table is read past the L1 cache (a line cached as
-// empty before another CU's insertion would send every later occurrence of that value to the atomic: 3.4 ms at 1.25 M rows
-// instead of 0.05).
+// the stream's distinct values into the set (zzz_valset.h); a lane skips the value it has just seen
 template <bool PERM>
 __global__ __launch_bounds__(256) void k_sp_dict_insert(const int2* __restrict__ desc, const int32_t* __restrict__ perm,
                                                          const double* __restrict__ svals, int nrows, int64_t nslices,
@@ -49,8 +37,6 @@ __global__ __launch_bounds__(256) void k_sp_dict_insert(const int2* __restrict__
   const int lane = threadIdx.x & 63;
   for (int64_t s = blockIdx.x * 4ll + (threadIdx.x >> 6); s < nslices; s += gridDim.x * 4ll)
   {
-    if (__hip_atomic_load(&info[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-      return; // more distinct values than the dictionary may hold (an unstructured mesh): nothing left to find out
     const int r = PERM ? perm[s * 64 + lane] : (int)(s * 64 + lane);
     const bool row = r >= 0 && r < nrows;
     const int2 ds = desc[s];
@@ -62,107 +48,22 @@ __global__ __launch_bounds__(256) void k_sp_dict_insert(const int2* __restrict__
       for (int e = 0; e < w; ++e)
       {
         const unsigned long long b = row ? sp_value_bits(svals, c0 + j, w, lane, e) : 0ull;
-        bool need = b != last && b != 0ull; // (a row repeats its values: the previous one is in the table already)
+        const bool need = b != last && b != 0ull; // (a row repeats its values: the previous one is in the table already)
         last = b;
-        unsigned long long todo = __ballot(need);
-        while (todo)
-        {
-          if (__hip_atomic_load(&info[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-            return; // (the waves in flight when the limit is met would fill the table up otherwise)
-          const int src = __ffsll((long long)todo) - 1;
-          const unsigned long long bb = ((unsigned long long)(unsigned)__shfl((int)(b >> 32), src) << 32)
-                                        | (unsigned)__shfl((int)(unsigned)b, src);
-          if (lane == src)
-          {
-            if (bb == SP_DICT_EMPTY)
-              info[1] = 1;
-            else
-            {
-              unsigned h = sp_dict_hash(bb);
-              for (int probe = 0; probe < (1 << SP_DICT_BITS); ++probe)
-              {
-                const unsigned long long cur = __hip_atomic_load(&table[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (cur == bb)
-                  break;
-                if (cur == SP_DICT_EMPTY)
-                {
-                  const unsigned long long old = atomicCAS(&table[h], SP_DICT_EMPTY, bb);
-                  if (old == SP_DICT_EMPTY)
-                  {
-                    if (atomicAdd(&info[0], 1) >= limit - 1)
-                      info[1] = 1;
-                    break;
-                  }
-                  if (old == bb)
-                    break;
-                }
-                h = (h + 1) & ((1u << SP_DICT_BITS) - 1);
-                if (__hip_atomic_load(&info[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-                  break; // too many distinct values: the table may be filling up, stop looking
-              }
-            }
-          }
-          need = need && b != bb;
-          todo = __ballot(need);
-        }
+        if (!valset_insert_wave<SP_DICT_BITS>(table, info, limit, b, need))
+          return; // more distinct values than the dictionary may hold (an unstructured mesh): nothing left to find out
       }
     }
   }
 }
 
-// codes: every thread numbers the occupied slots it meets (slot = k * 1024 + thread), threads in order; code 0 = +0.0
-__global__ __launch_bounds__(1024) void k_sp_dict_number(const unsigned long long* __restrict__ table, int32_t* __restrict__ slot_code,
-                                                         double* __restrict__ dict, int* __restrict__ info, int lds_max, int forced)
-{
-  __shared__ int wsum[16];
-  if (info[1])
-    return;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  int mine = 0;
-  for (int k = threadIdx.x; k < (1 << SP_DICT_BITS); k += 1024)
-    mine += table[k] != SP_DICT_EMPTY ? 1 : 0;
-  // exclusive scan of `mine` over the 1024 threads
-  int incl = mine;
-  for (int d = 1; d < 64; d <<= 1)
-  {
-    const int t = __shfl_up(incl, d);
-    if (lane >= d)
-      incl += t;
-  }
-  if (lane == 63)
-    wsum[wv] = incl;
-  __syncthreads();
-  int off = 1; // (code 0 is +0.0)
-  for (int q = 0; q < wv; ++q)
-    off += wsum[q];
-  int code = off + incl - mine;
-  for (int k = threadIdx.x; k < (1 << SP_DICT_BITS); k += 1024)
-  {
-    const unsigned long long b = table[k];
-    if (b != SP_DICT_EMPTY)
-    {
-      slot_code[k] = code;
-      if (code <= SP_DICT_MAX)
-        dict[code] = __longlong_as_double((long long)b);
-      ++code;
-    }
-  }
-  if (threadIdx.x == 1023)
-  {
-    dict[0] = 0.0;
-    info[2] = code; // entries of the dictionary, +0.0 included
-    if (code > lds_max && !forced)
-      info[1] = 2; // too large for the LDS copy: the stream stays as doubles, the encoding pass has nothing to do
-  }
-}
-
-// the stream's values as codes, [chunk][lane][8] (16 B per lane and chunk); info[4..5]: bytes the product reads in this form
+// the stream's values as codes, [chunk][lane][8] (16 B per lane and chunk); bytes_out: bytes the product reads in this form
 template <bool PERM>
 __global__ __launch_bounds__(256) void k_sp_dict_encode(const int2* __restrict__ desc, const int32_t* __restrict__ perm,
                                                          const double* __restrict__ svals, const int32_t* __restrict__ meta,
                                                          int nrows, int64_t nslices, const unsigned long long* __restrict__ table,
-                                                         const int32_t* __restrict__ slot_code, uint16_t* __restrict__ vcode,
-                                                         int* __restrict__ info)
+                                                         const int32_t* __restrict__ slot_code, const int* __restrict__ info,
+                                                         uint16_t* __restrict__ vcode, unsigned long long* __restrict__ bytes_out)
 {
   if (info[1])
     return;
@@ -191,11 +92,8 @@ __global__ __launch_bounds__(256) void k_sp_dict_encode(const int2* __restrict__
             continue;
           if (b != last)
           {
-            unsigned h = sp_dict_hash(b);
-            while (table[h] != b)
-              h = (h + 1) & ((1u << SP_DICT_BITS) - 1);
             last = b;
-            last_code = (unsigned)slot_code[h];
+            last_code = (unsigned)valset_find<SP_DICT_BITS>(table, slot_code, b);
           }
           code[e] = last_code;
         }
@@ -226,7 +124,7 @@ __global__ __launch_bounds__(256) void k_sp_dict_encode(const int2* __restrict__
     }
   }
   if (lane == 0 && bytes)
-    atomicAdd(reinterpret_cast<unsigned long long*>(info + 4), bytes);
+    atomicAdd(bytes_out, bytes);
 }
 
 // ---- per-slice value dictionaries (long rows: P3) ----------------------------------------------------------------
@@ -240,7 +138,7 @@ __global__ __launch_bounds__(256) void k_sp_dict_encode(const int2* __restrict__
 // The product copies a slice's table into its wavefront's part of LDS (8 KiB per wavefront: five workgroups per CU).
 // Tried: 8-bit codes and tables of 256 (a third of P3's slices qualify: product 0.67 -> 0.54 ms at 6.2 M dofs), tables of 512
 // (0.46 ms there, 4.19 ms at 49.8 M dofs), tables of 1 024 (0.47 / 3.68 ms: kept).
-// (SD_SLOTS = 2048, SD_MAX = 1024: zzz_sellp.h)
+// (SD_SLOTS = 2048, SD_MAX = 1024: zzz_sellp.h; the hash: zzz_valset.h)
 template <bool PERM, bool COUNT>
 __global__ __launch_bounds__(128) void k_sp_sd_build(const int2* __restrict__ desc, const int32_t* __restrict__ perm,
                                                       const double* __restrict__ svals, const int32_t* __restrict__ meta,
@@ -296,7 +194,7 @@ __global__ __launch_bounds__(128) void k_sp_sd_build(const int2* __restrict__ de
         const unsigned long long b = row ? sp_value_bits(svals, c0 + j, w, lane, e) : 0ull;
         if (b != 0ull && b != last && b != ~0ull)
         {
-          unsigned h = sp_dict_hash(b) & (SD_SLOTS - 1);
+          unsigned h = valset_hash<SD_BITS>(b);
           for (int probe = 0; probe < SD_SLOTS; ++probe)
           {
             const unsigned long long cur = keys[h];
@@ -355,7 +253,7 @@ __global__ __launch_bounds__(128) void k_sp_sd_build(const int2* __restrict__ de
               continue;
             if (b != last)
             {
-              unsigned h = sp_dict_hash(b) & (SD_SLOTS - 1);
+              unsigned h = valset_hash<SD_BITS>(b);
               while (keys[h] != b)
                 h = (h + 1) & (SD_SLOTS - 1);
               last = b;
@@ -416,47 +314,40 @@ int sp_dict_build(zzz_ctx* ctx)
     return ZZZ_OK;
   hipStream_t s = ctx->stream;
   const int64_t nsl = ctx->nslices;
-  ZZZ_HIP(ctx, ctx->sp_dict_table.alloc((size_t)1 << SP_DICT_BITS));
-  ZZZ_HIP(ctx, ctx->sp_dict_slot.alloc((size_t)1 << SP_DICT_BITS));
-  ZZZ_HIP(ctx, ctx->sp_dict.alloc((size_t)SP_DICT_MAX + 1));
+  ValSet<SP_DICT_BITS, 1>& vs = ctx->sp_dset;
+  ZZZ_HIP(ctx, vs.begin(SP_DICT_MAX + 1, s, ctx->retired));
   ZZZ_HIP(ctx, ctx->sp_vcode.alloc((size_t)ctx->sp_chunks * 512));
-  DevBuf<int32_t>& info = ctx->sp_dict_info;
-  ZZZ_HIP(ctx, info.reserve(8));
-  ZZZ_HIP(ctx, hipMemsetAsync(info.p, 0, 8 * sizeof(int32_t), s));
-  ZZZ_HIP(ctx, hipMemsetAsync(ctx->sp_dict_table.p, 0xff, sizeof(unsigned long long) << SP_DICT_BITS, s));
+  ZZZ_HIP(ctx, ctx->sp_dict_info.reserve(4));
+  ZZZ_HIP(ctx, hipMemsetAsync(ctx->sp_dict_info.p, 0, 4 * sizeof(int32_t), s));
+  unsigned long long* bytes = reinterpret_cast<unsigned long long*>(ctx->sp_dict_info.p);
   const int2* desc = reinterpret_cast<const int2*>(ctx->sp_desc.p);
   const unsigned grid = (unsigned)std::min<int64_t>((nsl + 3) / 4, 256 * 16);
-  // (the search stops at the first value beyond what will be used: the LDS copy's capacity, unless the memory form is forced)
-  const int limit = ctx->sellp_dict == 2 ? SP_DICT_MAX : SP_DICT_LDS_MAX - 1;
-  if (ctx->sp_sorted)
-    hipLaunchKernelGGL(k_sp_dict_insert<true>, dim3(grid), dim3(256), 0, s, desc, ctx->sp_perm.p, ctx->sp_vals.p, (int)ctx->nrows, nsl,
-                       ctx->sp_dict_table.p, info.p, limit);
-  else
-    hipLaunchKernelGGL(k_sp_dict_insert<false>, dim3(grid), dim3(256), 0, s, desc, (const int32_t*)nullptr, ctx->sp_vals.p,
-                       (int)ctx->nrows, nsl, ctx->sp_dict_table.p, info.p, limit);
-  hipLaunchKernelGGL(k_sp_dict_number, dim3(1), dim3(1024), 0, s, ctx->sp_dict_table.p, ctx->sp_dict_slot.p, ctx->sp_dict.p, info.p,
-                     SP_DICT_LDS_MAX, ctx->sellp_dict == 2 ? 1 : 0);
-  if (ctx->sp_sorted)
-    hipLaunchKernelGGL(k_sp_dict_encode<true>, dim3(grid), dim3(256), 0, s, desc, ctx->sp_perm.p, ctx->sp_vals.p, ctx->sp_meta.p,
-                       (int)ctx->nrows, nsl, ctx->sp_dict_table.p, ctx->sp_dict_slot.p, ctx->sp_vcode.p, info.p);
-  else
-    hipLaunchKernelGGL(k_sp_dict_encode<false>, dim3(grid), dim3(256), 0, s, desc, (const int32_t*)nullptr, ctx->sp_vals.p,
-                       ctx->sp_meta.p, (int)ctx->nrows, nsl, ctx->sp_dict_table.p, ctx->sp_dict_slot.p, ctx->sp_vcode.p, info.p);
-  ZZZ_HIP(ctx, hipGetLastError());
-  int32_t h[8];
-  ZZZ_HIP(ctx, hipMemcpyAsync(h, info.p, sizeof(h), hipMemcpyDeviceToHost, s));
-  ZZZ_HIP(ctx, hipStreamSynchronize(s));
-  if (h[1] || h[2] <= 0 || h[2] > SP_DICT_MAX + 1)
-    return ZZZ_OK;
+  // The search stops at the first value beyond what will be used: the LDS copy's capacity, unless the memory form is forced.
   // A dictionary too large for the LDS copy is gathered from memory: 2.3x fewer bytes at P3 6.2 M dofs (8 270 values) and the
   // same 0.61-0.63 ms per product -- the gathers, not the bytes, are what the kernel waits for -- so that form is not used
   // unless ZZZ_SELLP_DICT=2 asks for it (tests)
-  if (h[2] > SP_DICT_LDS_MAX && ctx->sellp_dict != 2)
+  const int limit = ctx->sellp_dict == 2 ? SP_DICT_MAX - 1 : SP_DICT_LDS_ENTRIES - 2;
+  if (ctx->sp_sorted)
+    hipLaunchKernelGGL(k_sp_dict_insert<true>, dim3(grid), dim3(256), 0, s, desc, ctx->sp_perm.p, ctx->sp_vals.p, (int)ctx->nrows, nsl,
+                       vs.table.p, vs.info.p, limit);
+  else
+    hipLaunchKernelGGL(k_sp_dict_insert<false>, dim3(grid), dim3(256), 0, s, desc, (const int32_t*)nullptr, ctx->sp_vals.p,
+                       (int)ctx->nrows, nsl, vs.table.p, vs.info.p, limit);
+  vs.number(s);
+  if (ctx->sp_sorted)
+    hipLaunchKernelGGL(k_sp_dict_encode<true>, dim3(grid), dim3(256), 0, s, desc, ctx->sp_perm.p, ctx->sp_vals.p, ctx->sp_meta.p,
+                       (int)ctx->nrows, nsl, vs.table.p, vs.slot.p, vs.info.p, ctx->sp_vcode.p, bytes);
+  else
+    hipLaunchKernelGGL(k_sp_dict_encode<false>, dim3(grid), dim3(256), 0, s, desc, (const int32_t*)nullptr, ctx->sp_vals.p,
+                       ctx->sp_meta.p, (int)ctx->nrows, nsl, vs.table.p, vs.slot.p, vs.info.p, ctx->sp_vcode.p, bytes);
+  unsigned long long hb = 0;
+  ZZZ_HIP(ctx, hipMemcpyAsync(&hb, bytes, sizeof(hb), hipMemcpyDeviceToHost, s));
+  int n = 0;
+  ZZZ_HIP(ctx, vs.finish(s, n));
+  if (!n)
     return ZZZ_OK;
-  unsigned long long bytes = 0;
-  memcpy(&bytes, h + 4, sizeof(bytes));
-  ctx->sp_dict_n = h[2];
-  ctx->sp_dict_bytes = (int64_t)bytes + (int64_t)h[2] * 8;
+  ctx->sp_dict_n = n;
+  ctx->sp_dict_bytes = (int64_t)hb + (int64_t)n * 8;
   ctx->sp_dict_on = true;
   return ZZZ_OK;
 }
@@ -475,12 +366,12 @@ int sp_sd_build(zzz_ctx* ctx)
   ZZZ_HIP(ctx, ctx->sp_vcode8.alloc((size_t)ctx->sp_chunks * 512));
   ZZZ_HIP(ctx, ctx->sp_sd_info.alloc((size_t)nsl + 1));
   ZZZ_HIP(ctx, ctx->sp_sd_off.alloc((size_t)nsl + 1));
-  ZZZ_HIP(ctx, ctx->sp_dict_info.reserve(8));
-  ZZZ_HIP(ctx, hipMemsetAsync(ctx->sp_dict_info.p, 0, 8 * sizeof(int32_t), s));
+  ZZZ_HIP(ctx, ctx->sp_dict_info.reserve(4));
+  ZZZ_HIP(ctx, hipMemsetAsync(ctx->sp_dict_info.p, 0, 4 * sizeof(int32_t), s));
   ZZZ_HIP(ctx, hipMemsetAsync(ctx->sp_sd_info.p + nsl, 0, sizeof(int32_t), s)); // closes the scan
   const int2* desc = reinterpret_cast<const int2*>(ctx->sp_desc.p);
   const unsigned grid = (unsigned)std::min<int64_t>((nsl + 1) / 2, 256 * 8);
-  unsigned long long* bytes = reinterpret_cast<unsigned long long*>(ctx->sp_dict_info.p + 4);
+  unsigned long long* bytes = reinterpret_cast<unsigned long long*>(ctx->sp_dict_info.p);
   // first pass: the tables' sizes; scan: where each starts; second pass: tables and codes
   if (ctx->sp_sorted)
     hipLaunchKernelGGL((k_sp_sd_build<true, true>), dim3(grid), dim3(128), 0, s, desc, ctx->sp_perm.p, ctx->sp_vals.p, ctx->sp_meta.p,
@@ -508,16 +399,16 @@ int sp_sd_build(zzz_ctx* ctx)
                        ctx->sp_meta.p, (int)ctx->nrows, nsl, ctx->sp_vcode8.p, ctx->sp_sd_vals.p, ctx->sp_sd_off.p, ctx->sp_sd_info.p,
                        bytes);
   ZZZ_HIP(ctx, hipGetLastError());
-  int32_t h[8];
+  int32_t h[4];
   ZZZ_HIP(ctx, hipMemcpyAsync(h, ctx->sp_dict_info.p, sizeof(h), hipMemcpyDeviceToHost, s));
   ZZZ_HIP(ctx, hipStreamSynchronize(s));
   unsigned long long b = 0;
-  memcpy(&b, h + 4, sizeof(b));
+  memcpy(&b, h, sizeof(b));
   if (ctx->sellp_dict != 3 && (double)b > 0.6 * (double)ctx->sp_bytes)
     return ZZZ_OK;
   ctx->sp_sd_bytes = (int64_t)b;
   ctx->sp_sd_on = true;
-  ctx->sp_sd_all = h[6] == 0;
+  ctx->sp_sd_all = h[2] == 0;
   return ZZZ_OK;
 }
 ZZZ_PRELOAD_TU(sellp_dict)

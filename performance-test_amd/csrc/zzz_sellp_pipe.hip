@@ -527,7 +527,7 @@ bool launch_sellp_pipe(zzz_ctx* ctx, bool dot, bool nt, int grid, const double* 
 #define ZZZ_ONE_GO(DOT, SR, NT)                                                                                                    \
   hipLaunchKernelGGL((spmv_one_kernel<DOT, SR, NT>), dim3(grid), dim3(SP_BLOCK), lds, ctx->stream,                                 \
                      reinterpret_cast<const int2*>(ctx->sp_desc.p), ctx->sp_smode.p, ctx->sp_pairs.p, ctx->sp_vals.p,               \
-                     ctx->sp_codes16.p, ctx->sp_meta.p, ctx->sp_vcode.p, ctx->sp_dict.p, x, y, rvec, group_list, a)
+                     ctx->sp_codes16.p, ctx->sp_meta.p, ctx->sp_vcode.p, ctx->sp_dset.dict.p, x, y, rvec, group_list, a)
   if (dot && rvec)
   {
     if (nt)

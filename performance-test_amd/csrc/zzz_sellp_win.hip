@@ -569,7 +569,7 @@ __global__ __launch_bounds__(BW_THREADS) void k_bw_values(const int32_t* __restr
             bad = 1;
             continue;
           }
-          unsigned h = (unsigned)(((v[e] ^ (v[e] >> 29)) * 0x9E3779B97F4A7C15ull) >> (64 - BW_DBITS));
+          unsigned h = valset_hash<BW_DBITS>(v[e]);
           for (int probe = 0; probe < BW_DHASH; ++probe)
           {
             unsigned long long cur = hval[h];
