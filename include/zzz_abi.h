@@ -95,7 +95,14 @@ enum
 enum
 {
   ZZZ_CG_PETSC = 0, /* KSPCG: zero initial guess, test dp <= max(rtol*dp0, atol) */
-  ZZZ_CG_CGH = 1    /* src/cg.h:38-86: x is the initial guess, test <r,r>/<r0,r0> < rtol^2 */
+  ZZZ_CG_CGH = 1,   /* src/cg.h:38-86: x is the initial guess, test <r,r>/<r0,r0> < rtol^2 */
+  /* [EXT] KSPPIPECG, what solver.set_from_options() selects for -ksp_type pipecg (Ghysels & Vanroose 2014, Alg. 4):
+   * the iteration of ZZZ_CG_PETSC with r, u = M^-1 r, w = A u and their directions kept by recurrence, so that the
+   * ONE fused reduction of (<r,u>, <w,u>, norm) of an iteration overlaps its product n = A M^-1 w instead of
+   * standing in front of it; two launches per iteration.  Conventions (zero initial guess, KSPConvergedDefault,
+   * norm types, history, reasons) as ZZZ_CG_PETSC.  ZZZ_OP_CSR with ZZZ_PC_NONE | ZZZ_PC_JACOBI only, and not with
+   * single_reduction.  No multi-GPU hardware run of this form exists. */
+  ZZZ_CG_PIPE = 2
 };
 enum
 {
@@ -105,7 +112,7 @@ enum
 
 typedef struct
 {
-  int32_t variant;  /* ZZZ_CG_PETSC | ZZZ_CG_CGH */
+  int32_t variant;  /* ZZZ_CG_PETSC | ZZZ_CG_CGH | ZZZ_CG_PIPE */
   int32_t pc;       /* ZZZ_PC_* (ZZZ_CG_CGH requires ZZZ_PC_NONE; with ZZZ_OP_MATFREE: none or jacobi) */
   int32_t norm;     /* ZZZ_NORM_* (ZZZ_CG_PETSC only) */
   int32_t op;       /* ZZZ_OP_* */
@@ -333,7 +340,9 @@ int zzz_cg_history(zzz_ctx* ctx, int n, double* out);
 /* About the last zzz_cg_solve: info[0] bit 0 is reserved and always 0; bit 1 (value 2)
  * when Jacobi's inverse diagonal was read as 16-bit codes into a table of its distinct values and z = D^-1 r recomputed
  * instead of stored (68 instead of 80 B per row and iteration in the two vector kernels; the same bits), info[0] >> 8 = those
- * distinct values;
+ * distinct values; bit 2 (value 4) when the solve was ZZZ_CG_PIPE with a communicator and its all-reduces ran on a stream of
+ * their own beside the halo exchange and the product (not with the host-mediated local backend, nor with mailboxes
+ * between contexts of one process);
  * info[1] = its iteration count (same iterates, bit for bit, either way); info[2] = how it ended, in
  * KSPConvergedReason's numbering: 2 KSP_CONVERGED_RTOL, 3 KSP_CONVERGED_ATOL, -3 KSP_DIVERGED_ITS (max_it / kmax
  * reached), -4 KSP_DIVERGED_DTOL, -9 KSP_DIVERGED_NANORINF; info[3] = with ZZZ_PC_CHEBYSHEV_JACOBI the upper bound of

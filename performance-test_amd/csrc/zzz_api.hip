@@ -143,6 +143,7 @@ int zzz_ctx_create(int device, zzz_ctx** out)
       zzz::preload_sellp();
       zzz::preload_spmv();
       zzz::preload_cg();
+      zzz::preload_cg_pipe();
       zzz::preload_comm();
       zzz::preload_matfree();
       zzz::preload_nullspace();
@@ -203,6 +204,8 @@ int zzz_ctx_create(int device, zzz_ctx** out)
   }
   if (const char* e = getenv("ZZZ_OVERLAP"))
     ctx->overlap = atoi(e) != 0;
+  if (const char* e = getenv("ZZZ_CG_PIPE_STREAM")) // 0: the all-reduce of the pipelined CG stays on the main stream (A/B against its own stream)
+    ctx->pipe_stream = atoi(e) != 0;
   *out = ctx;
   return ZZZ_OK;
 }
@@ -944,8 +947,11 @@ int zzz_cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rno
     return fail(ctx, ZZZ_ERR_ARG, "zzz_cg_solve: matrix not assembled");
   if (o->op != ZZZ_OP_CSR && o->op != ZZZ_OP_MATFREE)
     return fail(ctx, ZZZ_ERR_ARG, "unknown operator kind %d", o->op);
-  if (o->variant != ZZZ_CG_PETSC && o->variant != ZZZ_CG_CGH)
+  if (o->variant != ZZZ_CG_PETSC && o->variant != ZZZ_CG_CGH && o->variant != ZZZ_CG_PIPE)
     return fail(ctx, ZZZ_ERR_ARG, "unknown CG variant %d", o->variant);
+  if (o->variant == ZZZ_CG_PIPE && (o->op != ZZZ_OP_CSR || o->single_reduction || (o->pc != ZZZ_PC_NONE && o->pc != ZZZ_PC_JACOBI)))
+    return fail(ctx, ZZZ_ERR_ARG, "-ksp_type pipecg applies to the assembled operator with -pc_type jacobi or none, and not with "
+                                  "-ksp_cg_single_reduction");
   if (o->variant == ZZZ_CG_CGH && o->pc != ZZZ_PC_NONE)
     return fail(ctx, ZZZ_ERR_ARG, "src/cg.h has no preconditioner: use pc = ZZZ_PC_NONE");
   if (o->pc != ZZZ_PC_NONE && o->pc != ZZZ_PC_JACOBI && o->pc != ZZZ_PC_CHEBYSHEV_JACOBI)
@@ -1049,7 +1055,7 @@ int zzz_cg_info(zzz_ctx* ctx, int64_t info[4])
 {
   if (!ctx || !info)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_cg_info: bad arguments");
-  info[0] = (ctx->last_solve_dinv_codes > 0 ? 2 : 0) | ((int64_t)ctx->last_solve_dinv_codes << 8);
+  info[0] = (ctx->last_solve_dinv_codes > 0 ? 2 : 0) | (ctx->last_solve_red_overlapped ? 4 : 0) | ((int64_t)ctx->last_solve_dinv_codes << 8);
   info[1] = ctx->last_iters;
   info[2] = ctx->last_reason;
   info[3] = (int64_t)(ctx->last_pc_bound * 1.0e6); // Chebyshev-Jacobi: spectrum bound x 1e6

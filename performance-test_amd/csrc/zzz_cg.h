@@ -1,0 +1,134 @@
+// What the CG translation units share (zzz_cg.hip: classical, single-reduction and Chebyshev-Jacobi forms;
+// zzz_cg_pipe.hip: the pipelined form): the vector kernels' launch shape and load policy, the coded inverse diagonal,
+// the partial-sum tree and the host helpers of a solve.  Not part of the ABI.
+#pragma once
+#include "zzz_device.h"
+#include "zzz_internal.h"
+
+namespace zzz
+{
+typedef double dbl2 __attribute__((ext_vector_type(2)));
+
+// One workgroup-wide sum of up to three partial arrays in ONE pass and one barrier pair (same tree per array as
+// reduce_parts_bcast of zzz_cg.hip:
+// strided per-thread sums, shuffles inside a wavefront, the per-wavefront sums added in order -- here by every thread
+// from LDS instead of by thread 0 plus a broadcast).  pc may be null.
+__device__ inline void reduce_parts3_bcast(const double* __restrict__ pa, const double* __restrict__ pb,
+                                           const double* __restrict__ pc, int np, double& ra, double& rb, double& rc)
+{
+  __shared__ double sh[3 * 16];
+  double s0 = 0, s1 = 0, s2 = 0;
+  for (int i = threadIdx.x; i < np; i += blockDim.x)
+  {
+    s0 += pa[i];
+    s1 += pb[i];
+    if (pc)
+      s2 += pc[i];
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1)
+  {
+    s0 += __shfl_down(s0, o, 64);
+    s1 += __shfl_down(s1, o, 64);
+    s2 += __shfl_down(s2, o, 64);
+  }
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  __syncthreads();
+  if (lane == 0)
+  {
+    sh[wv] = s0;
+    sh[nw + wv] = s1;
+    sh[2 * nw + wv] = s2;
+  }
+  __syncthreads();
+  ra = rb = rc = 0.0;
+  for (int i = 0; i < nw; ++i)
+  {
+    ra += sh[i];
+    rb += sh[nw + i];
+    rc += sh[2 * nw + i];
+  }
+}
+
+constexpr int VB = 256;        // threads per workgroup of the vector kernels
+constexpr int VGRID_MAX = 2048; // 8 workgroups per CU
+
+// Product launches timed with HIP events when zzz_solver_opts.profile is set: every PROF_STRIDE-th iteration.  An event
+// record between two kernels costs ~3.5 us of idle GPU (rocprofv3 timeline at 1.25 M rows: 4.1-4.4 us gaps on both sides
+// of the product against 0.5-0.8 us elsewhere), i.e. 7 us per timed iteration -- 13 % of a 52-us iteration when every
+// launch was timed.
+constexpr int PROF_STRIDE = 8;
+
+// Non-temporal access for data touched once per iteration pays only when the working set of the loop exceeds the
+// 256 MiB Infinity Cache; a loop that fits (the 8-GPU per-rank size: ~100 MB of operator stream + 60 MB of vectors)
+// keeps everything on-die with plain accesses.
+template <bool NT, typename T>
+__device__ inline T vload(const T* p)
+{
+  return NT ? __builtin_nontemporal_load(p) : *p;
+}
+template <bool NT, typename T>
+__device__ inline void vstore(T v, T* p)
+{
+  if (NT)
+    __builtin_nontemporal_store(v, p);
+  else
+    *p = v;
+}
+
+// The convergence flag can be set by workgroup 0 of the SAME launch while other workgroups start: one value per
+// workgroup (thread 0's, loaded by the caller ahead of its other requests), so all threads of a workgroup take the same
+// branch -- the reductions behind it need every wavefront.
+__device__ inline int block_flag(int f)
+{
+  __shared__ int flag;
+  if (threadIdx.x == 0)
+    flag = f;
+  __syncthreads();
+  return flag;
+}
+
+struct DinvCodes
+{
+  const uint32_t* codes; // two 16-bit codes per word, entry pairs as the dbl2 accesses take them
+  const double* dict;
+  const double* r;
+  int ndict;
+};
+constexpr int DZ_MAX = 2048;
+
+// the polling events of one solve: destroyed on every exit path
+template <int N>
+struct EventRing
+{
+  hipEvent_t ev[N] = {};
+  int created = 0;
+  hipError_t create()
+  {
+    for (; created < N; ++created)
+    {
+      hipError_t e = hipEventCreateWithFlags(&ev[created], hipEventDisableTiming);
+      if (e != hipSuccess)
+        return e;
+    }
+    return hipSuccess;
+  }
+  ~EventRing()
+  {
+    for (int i = 0; i < created; ++i)
+      (void)hipEventDestroy(ev[i]);
+  }
+  hipEvent_t& operator[](int i) { return ev[i]; }
+};
+
+// zzz_cg.hip
+int dinv_codes_build(zzz_ctx* ctx, int64_t n, DinvCodes& dzc); // ctx->dinv as 16-bit codes (dzc.codes stays null: too many values)
+bool loop_exceeds_cache(zzz_ctx* ctx, int nvec);               // operator + nvec vectors against the Infinity Cache
+int vgrid(int64_t n);                                          // workgroups of a vector kernel over n entries
+int finish_reason(zzz_ctx* ctx, const zzz_solver_opts* o, const CgState& fin, int its);
+// the start-up kernels on the context's stream: ctx->dinv = 1 / diag(A) (jacobi) or 1; r = b, z = dinv r with the
+// partials of <r,z> and of the test norm
+int cg_solve_pipe(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm); // zzz_cg_pipe.hip
+void cg_launch_extract_dinv(zzz_ctx* ctx, int64_t n, int jacobi);
+void cg_launch_init_residual(zzz_ctx* ctx, double* z, int64_t n, int norm, double* pa, double* pb);
+} // namespace zzz

@@ -20,14 +20,13 @@
 // HBM traffic per iteration beyond the SpMV: 40 B/row (x and p update) + 40 B/row (r, z update).
 #include "zzz_device.h"
 #include "zzz_internal.h"
+#include "zzz_cg.h"
 
 #include <cmath>
 #include <cstdlib>
 
 namespace zzz
 {
-typedef double dbl2 __attribute__((ext_vector_type(2)));
-
 // one workgroup-wide sum of parts[0..np) (fixed order); result in every thread
 __device__ inline double reduce_parts_bcast(const double* __restrict__ parts, int np, double* sh)
 {
@@ -41,47 +40,6 @@ __device__ inline double reduce_parts_bcast(const double* __restrict__ parts, in
     bc = t;
   __syncthreads();
   return bc;
-}
-
-
-// The same for up to three partial arrays in ONE pass and one barrier pair (same tree per array as reduce_parts_bcast:
-// strided per-thread sums, shuffles inside a wavefront, the per-wavefront sums added in order -- here by every thread
-// from LDS instead of by thread 0 plus a broadcast).  pc may be null.
-__device__ inline void reduce_parts3_bcast(const double* __restrict__ pa, const double* __restrict__ pb,
-                                           const double* __restrict__ pc, int np, double& ra, double& rb, double& rc)
-{
-  __shared__ double sh[3 * 16];
-  double s0 = 0, s1 = 0, s2 = 0;
-  for (int i = threadIdx.x; i < np; i += blockDim.x)
-  {
-    s0 += pa[i];
-    s1 += pb[i];
-    if (pc)
-      s2 += pc[i];
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1)
-  {
-    s0 += __shfl_down(s0, o, 64);
-    s1 += __shfl_down(s1, o, 64);
-    s2 += __shfl_down(s2, o, 64);
-  }
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  __syncthreads();
-  if (lane == 0)
-  {
-    sh[wv] = s0;
-    sh[nw + wv] = s1;
-    sh[2 * nw + wv] = s2;
-  }
-  __syncthreads();
-  ra = rb = rc = 0.0;
-  for (int i = 0; i < nw; ++i)
-  {
-    ra += sh[i];
-    rb += sh[nw + i];
-    rc += sh[2 * nw + i];
-  }
 }
 
 // The scalar logic at the head of iteration `it` (convergence test of the completed iterations and the new
@@ -163,32 +121,6 @@ __device__ inline bool cg_direction_scalars(CgState* __restrict__ st, double* __
   S.conv = conv;
   return true;
 }
-
-constexpr int VB = 256;        // threads per workgroup of the vector kernels
-constexpr int VGRID_MAX = 2048; // 8 workgroups per CU
-// Product launches timed with HIP events when zzz_solver_opts.profile is set: every PROF_STRIDE-th iteration.  An event
-// record between two kernels costs ~3.5 us of idle GPU (rocprofv3 timeline at 1.25 M rows: 4.1-4.4 us gaps on both sides
-// of the product against 0.5-0.8 us elsewhere), i.e. 7 us per timed iteration -- 13 % of a 52-us iteration when every
-// launch was timed.
-constexpr int PROF_STRIDE = 8;
-
-// Non-temporal access for data touched once per iteration pays only when the working set of the loop exceeds the
-// 256 MiB Infinity Cache; a loop that fits (the 8-GPU per-rank size: ~100 MB of operator stream + 60 MB of vectors)
-// keeps everything on-die with plain accesses.
-template <bool NT, typename T>
-__device__ inline T vload(const T* p)
-{
-  return NT ? __builtin_nontemporal_load(p) : *p;
-}
-template <bool NT, typename T>
-__device__ inline void vstore(T v, T* p)
-{
-  if (NT)
-    __builtin_nontemporal_store(v, p);
-  else
-    *p = v;
-}
-
 
 __global__ void k_invert(double* __restrict__ d, int64_t n)
 {
@@ -279,18 +211,6 @@ __global__ __launch_bounds__(VB) void k_init_residual(const double* __restrict__
   }
 }
 
-// The convergence flag can be set by workgroup 0 of the SAME launch while other workgroups start: one value per
-// workgroup (thread 0's, loaded by the caller ahead of its other requests), so all threads of a workgroup take the same
-// branch -- the reductions behind it need every wavefront.
-__device__ inline int block_flag(int f)
-{
-  __shared__ int flag;
-  if (threadIdx.x == 0)
-    flag = f;
-  __syncthreads();
-  return flag;
-}
-
 // `it` = number of completed iterations.  pa/pb: partials of <r,z> and of the test norm (np each).
 // The solution update of the PREVIOUS iteration, x += alpha_{it-1} p_{it-1}, is applied here (p is read
 // anyway) instead of in k_update_xr: one vector read less per iteration, same operations on the same
@@ -300,14 +220,6 @@ __device__ inline int block_flag(int f)
 // matrix's: section 3 of DESIGN.md); as 16-bit codes into a table in LDS it costs 2 B per row instead of 8, and with it
 // z = D^-1 r is cheaper to RECOMPUTE here from r (the same product of the same two doubles: the same bits) than to
 // write in k_update_xr and read back: 80 -> 68 B per row and iteration for the two kernels.  dz.codes = nullptr: off.
-struct DinvCodes
-{
-  const uint32_t* codes; // two 16-bit codes per word, entry pairs as the dbl2 accesses take them
-  const double* dict;
-  const double* r;
-  int ndict;
-};
-constexpr int DZ_MAX = 2048;
 
 template <bool NT, bool DZ = false>
 __global__ __launch_bounds__(VB) void k_update_p(CgState* __restrict__ st, double* __restrict__ beta_hist,
@@ -751,33 +663,9 @@ __global__ __launch_bounds__(1024) void k_reduce_plain(const double* __restrict_
     out[0] = s;
 }
 
-// the polling events of one solve: destroyed on every exit path
-template <int N>
-struct EventRing
-{
-  hipEvent_t ev[N] = {};
-  int created = 0;
-  hipError_t create()
-  {
-    for (; created < N; ++created)
-    {
-      hipError_t e = hipEventCreateWithFlags(&ev[created], hipEventDisableTiming);
-      if (e != hipSuccess)
-        return e;
-    }
-    return hipSuccess;
-  }
-  ~EventRing()
-  {
-    for (int i = 0; i < created; ++i)
-      (void)hipEventDestroy(ev[i]);
-  }
-  hipEvent_t& operator[](int i) { return ev[i]; }
-};
-
 // The inverse diagonal (ctx->dinv, n entries) as 16-bit codes into a table of its distinct values, for the kernels that take
 // DinvCodes: dzc.codes stays null when there are more than DZ_MAX values.  Synchronises the stream once (the count).
-static int dinv_codes_build(zzz_ctx* ctx, int64_t n, DinvCodes& dzc)
+int dinv_codes_build(zzz_ctx* ctx, int64_t n, DinvCodes& dzc)
 {
   hipStream_t s = ctx->stream;
   const int64_t npad = (n + 1) & ~(int64_t)1;
@@ -796,13 +684,13 @@ static int dinv_codes_build(zzz_ctx* ctx, int64_t n, DinvCodes& dzc)
 }
 
 // bytes one CG iteration touches (operator + `nvec` vectors) against the Infinity Cache
-static bool loop_exceeds_cache(zzz_ctx* ctx, int nvec)
+bool loop_exceeds_cache(zzz_ctx* ctx, int nvec)
 {
   const double op = sellp_active(ctx) ? (double)sellp_stream_bytes(ctx) : 10.0 * (double)ctx->nnz;
   return op + 8.0 * nvec * (double)ctx->nloc() > 200.0e6;
 }
 
-static int vgrid(int64_t n)
+int vgrid(int64_t n)
 {
   // at least 8 entries per thread: every workgroup starts by summing the producer's per-workgroup partials, so for
   // small vectors fewer, longer workgroups are faster (1.25 M rows: 57.8 -> 52.9 us per iteration with 610 instead of
@@ -814,6 +702,17 @@ static int vgrid(int64_t n)
   if (g < 1)
     g = 1;
   return (int)g;
+}
+
+void cg_launch_extract_dinv(zzz_ctx* ctx, int64_t n, int jacobi)
+{
+  hipLaunchKernelGGL(k_extract_dinv, dim3(vgrid(n)), dim3(VB), 0, ctx->stream, ctx->rowptr.p, ctx->cols.p, ctx->vals.p, ctx->dinv.p, n,
+                     jacobi);
+}
+void cg_launch_init_residual(zzz_ctx* ctx, double* z, int64_t n, int norm, double* pa, double* pb)
+{
+  hipLaunchKernelGGL(k_init_residual, dim3(vgrid(n)), dim3(VB), 0, ctx->stream, ctx->b.p, (const double*)nullptr, ctx->dinv.p, ctx->r.p,
+                     z, n, norm, pa, pb);
 }
 
 // sum of squares over the owned entries, all-reduced over ranks when a communicator is attached
@@ -843,11 +742,11 @@ static int cg_solve_single_reduction(zzz_ctx* ctx, const zzz_solver_opts* o, int
 // solver.solve()'s iteration count whatever the reason (src/poisson_problem.cpp:172-178) and the driver prints its summary
 // and timings all the same, so a diverged solve is NOT an error here either -- unless the caller asks for PETSc's
 // -ksp_error_if_not_converged (zzz_solver_opts.error_if_not_converged).
-static int finish_reason(zzz_ctx* ctx, const zzz_solver_opts* o, const CgState& fin, int its)
+int finish_reason(zzz_ctx* ctx, const zzz_solver_opts* o, const CgState& fin, int its)
 {
   int reason;
   if (fin.converged == 1)
-    reason = (o->variant == ZZZ_CG_PETSC && fin.dp < o->atol) ? 3 /* KSP_CONVERGED_ATOL */ : 2 /* KSP_CONVERGED_RTOL */;
+    reason = (o->variant != ZZZ_CG_CGH && fin.dp < o->atol) ? 3 /* KSP_CONVERGED_ATOL */ : 2 /* KSP_CONVERGED_RTOL */;
   else if (fin.converged == 2)
     reason = -9; // KSP_DIVERGED_NANORINF
   else if (fin.converged == 3)
@@ -867,12 +766,14 @@ static int finish_reason(zzz_ctx* ctx, const zzz_solver_opts* o, const CgState& 
   return ZZZ_OK;
 }
 
-
 static int cg_solve_chebyshev(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm);
 
 int cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
 {
   ctx->last_pc_bound = 0.0;
+  ctx->last_solve_red_overlapped = false;
+  if (o->variant == ZZZ_CG_PIPE)
+    return cg_solve_pipe(ctx, o, iters, rnorm); // zzz_cg_pipe.hip
   if (o->pc == ZZZ_PC_CHEBYSHEV_JACOBI && !o->single_reduction)
     return cg_solve_chebyshev(ctx, o, iters, rnorm);
   if (o->single_reduction)

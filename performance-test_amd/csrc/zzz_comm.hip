@@ -444,10 +444,11 @@ bool comm_p2p_enabled(const zzz_ctx* ctx) { return ctx->comm && ctx->comm->p2p &
 
 // out[0..nv) = all-reduced sums of up to three partial arrays of length np (pb/pc may be null for nv < 2/3).
 // stop: device flag that turns the call into a no-op (CgState::converged) or null.
+// st: the stream to enqueue on (null: the context's main stream; the host-synchronous local backend knows no other).
 int comm_reduce_allreduce(zzz_ctx* ctx, const int* stop, const double* pa, const double* pb, const double* pc, int np,
-                          int nv, double* out)
+                          int nv, double* out, hipStream_t st)
 {
-  hipStream_t s = ctx->stream;
+  hipStream_t s = st ? st : ctx->stream;
   if (comm_p2p_enabled(ctx))
   {
     P2P* P = ctx->comm->p2p;
@@ -459,7 +460,59 @@ int comm_reduce_allreduce(zzz_ctx* ctx, const int* stop, const double* pa, const
   }
   hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(512), 0, s, stop, pa, pb, pc, np, nv, out);
   ZZZ_HIP(ctx, hipGetLastError());
+  if (s != ctx->stream)
+  {
+    // (comm_reduce_begin comes here only with a communicator of the library's: see its conditions)
+    ZZZ_NCCL(ctx, g_rccl.AllReduce(out, out, (size_t)nv, ncclFloat64, ncclSum, ctx->comm->comm, s));
+    return ZZZ_OK;
+  }
   return comm_allreduce_sum(ctx, out, nv);
+}
+
+// overlap form: the all-reduce runs on a stream of its own behind everything enqueued on the main stream so far (the
+// partials are final); the main stream goes on with work that does not need the sums -- the halo exchange and the product
+// of the same iteration (zzz_cg_pipe.hip) -- and waits for them in comm_reduce_end.  Every rank makes the same calls in
+// the same order, as with comm_reduce_allreduce.  Where a second stream cannot help or is not safe the all-reduce stays
+// on the main stream, in the same place of the sequence, with the same results:
+//   * the host-synchronous local backend (every call ends with a stream synchronisation: nothing is in flight to overlap);
+//   * mailboxes between contexts of ONE process on one GPU (validation): they share its few hardware queues, and a
+//     waiting mailbox kernel on a second stream per rank could sit in front of the very kernel it waits for
+//     (comm_halo_begin keeps the exchange on the main stream there for the same reason);
+//   * ZZZ_CG_PIPE_STREAM=0 (A/B: what the second stream and its two events cost where no link latency is there to hide).
+int comm_reduce_begin(zzz_ctx* ctx, const int* stop, const double* pa, const double* pb, const double* pc, int np, int nv,
+                      double* out)
+{
+  ctx->red_pending = false;
+  if (!ctx->comm)
+    return ZZZ_OK;
+  const bool second = comm_p2p_enabled(ctx) ? !ctx->comm->p2p->inproc : (!ctx->comm->local && ctx->comm->comm != nullptr);
+  if (!second || !ctx->pipe_stream)
+    return comm_reduce_allreduce(ctx, stop, pa, pb, pc, np, nv, out);
+  if (!ctx->red_stream)
+  {
+    // default priority: at the most urgent one (as the halo's stream has it) the mailbox kernel beside a product made the
+    // iteration erratic and several times slower on one GPU (1.3 M rows: 53 -> 54..235 us, 5 M rows: 143 -> 307..322 us)
+    ZZZ_HIP(ctx, hipStreamCreateWithFlags(&ctx->red_stream, hipStreamNonBlocking));
+    ZZZ_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_parts_ready, hipEventDisableTiming));
+    ZZZ_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_red_done, hipEventDisableTiming));
+  }
+  ZZZ_HIP(ctx, hipEventRecord(ctx->ev_parts_ready, ctx->stream));
+  ZZZ_HIP(ctx, hipStreamWaitEvent(ctx->red_stream, ctx->ev_parts_ready, 0));
+  if (int rc = comm_reduce_allreduce(ctx, stop, pa, pb, pc, np, nv, out, ctx->red_stream))
+    return rc;
+  ZZZ_HIP(ctx, hipEventRecord(ctx->ev_red_done, ctx->red_stream));
+  ctx->red_pending = true;
+  ctx->last_solve_red_overlapped = true;
+  return ZZZ_OK;
+}
+
+int comm_reduce_end(zzz_ctx* ctx)
+{
+  if (!ctx->red_pending)
+    return ZZZ_OK;
+  ctx->red_pending = false;
+  ZZZ_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_red_done, 0));
+  return ZZZ_OK;
 }
 
 // did a peer all-reduce time out since the last call?  (checked at the end of a solve)
@@ -920,6 +973,15 @@ void comm_destroy(zzz_ctx* ctx)
     (void)hipEventDestroy(ctx->ev_halo_done);
     (void)hipStreamDestroy(ctx->comm_stream);
     ctx->comm_stream = nullptr;
+  }
+  if (ctx->red_stream)
+  {
+    (void)hipStreamSynchronize(ctx->red_stream);
+    (void)hipEventDestroy(ctx->ev_parts_ready);
+    (void)hipEventDestroy(ctx->ev_red_done);
+    (void)hipStreamDestroy(ctx->red_stream);
+    ctx->red_stream = nullptr;
+    ctx->red_pending = false;
   }
   if (ctx->comm)
   {

@@ -368,6 +368,9 @@ struct zzz_ctx
   zzz::DevBuf<double> part_a, part_b, red; // block partials; reduced scalars
   zzz::DevBuf<double> beta_hist, dp_hist, dpi_hist;
   zzz::DevBuf<double> sr_s; // single-reduction CG: s = A z
+  // pipelined CG (zzz_cg_pipe.hip): m = D^-1 w with its ghost entries, n = A m, and the block partials of the three sums in
+  // two sets (an iteration's kernel reads one and leaves the next iteration's in the other)
+  zzz::DevBuf<double> pipe_m, pipe_n, pipe_parts;
   zzz::DevBuf<double> cheb_d, cheb_d2, cheb_g; // Chebyshev-Jacobi: the polynomial's direction (two buffers: fused terms
                                                // write the next one while lanes still gather the old) and residual
   zzz::DevBuf<double> cheb_noise; // ... and the right-hand side of its spectrum estimate
@@ -414,6 +417,12 @@ struct zzz_ctx
   std::vector<int64_t> send_contig; // per neighbour: first owned block dof when its list is a contiguous range, else -1
   hipStream_t comm_stream = nullptr;
   hipEvent_t ev_x_ready = nullptr, ev_halo_done = nullptr;
+  // the all-reduce that overlaps a product (comm_reduce_begin / comm_reduce_end): its own stream and events
+  hipStream_t red_stream = nullptr;
+  hipEvent_t ev_parts_ready = nullptr, ev_red_done = nullptr;
+  bool red_pending = false;
+  bool pipe_stream = true; // ZZZ_CG_PIPE_STREAM=0: the all-reduce of the pipelined CG stays on the main stream (A/B)
+  bool last_solve_red_overlapped = false; // the last solve's all-reduces went to red_stream (zzz_cg_info)
   bool overlap = true; // ZZZ_OVERLAP=0 disables the halo/compute overlap
 
   int64_t nloc() const { return (n_owned + n_ghost) * bs; }
@@ -445,6 +454,7 @@ void set_global_error(const char* msg);
   }
 void preload_assemble();
 void preload_cg();
+void preload_cg_pipe();
 void preload_comm();
 void preload_cubegen();
 void preload_matfree();
@@ -516,7 +526,12 @@ int comm_allreduce_sum(zzz_ctx* ctx, double* dev, int n);
 // out[0..nv) = all-reduced sums of up to three partial arrays (one kernel with the peer-memory backend,
 // reduce kernel + ncclAllReduce otherwise); stop: device flag that makes the call a no-op, or null
 int comm_reduce_allreduce(zzz_ctx* ctx, const int* stop, const double* pa, const double* pb, const double* pc, int np, int nv,
-                          double* out);
+                          double* out, hipStream_t st = nullptr);
+// overlap form (pipelined CG): the same all-reduce behind everything enqueued on the main stream so far, on a stream of
+// its own where the transport allows one; the main stream goes on and meets the result at comm_reduce_end
+int comm_reduce_begin(zzz_ctx* ctx, const int* stop, const double* pa, const double* pb, const double* pc, int np, int nv,
+                      double* out);
+int comm_reduce_end(zzz_ctx* ctx);
 bool comm_p2p_enabled(const zzz_ctx* ctx);
 int comm_p2p_check(zzz_ctx* ctx);
 int comm_halo_forward(zzz_ctx* ctx, double* vec);

@@ -141,7 +141,7 @@ void usage()
                "  --allreduce arg (=peer)         peer (xGMI peer-memory mailboxes, else falls back) | comm\n"
                "  --operator arg (=assembled)     poisson: assembled (the AIJ matrix) | matfree (KSPCG on the matrix-free\n"
                "                                  operator, Jacobi from the element matrices' diagonals; no matrix)\n"
-               "PETSc-style solver options honoured: -ksp_type cg -pc_type {jacobi,none,chebyshev_jacobi} -ksp_rtol -ksp_atol\n"
+               "PETSc-style solver options honoured: -ksp_type {cg,pipecg} -pc_type {jacobi,none,chebyshev_jacobi} -ksp_rtol -ksp_atol\n"
                "  -ksp_divtol -pc_chebyshev_jacobi_degree (=3) -pc_chebyshev_jacobi_ratio (=60) -pc_chebyshev_jacobi_esteig (=10)\n"
                "  -ksp_max_it -ksp_norm_type {preconditioned,unpreconditioned,natural} -ksp_view -ksp_monitor\n"
                "  -ksp_cg_single_reduction -ksp_converged_reason -ksp_error_if_not_converged\n"
@@ -470,7 +470,7 @@ void run_rank(Shared& S, std::barrier<>& bar, int rank)
   }
   else
   {
-    so.variant = ZZZ_CG_PETSC;
+    so.variant = o.ksp_type == "pipecg" ? ZZZ_CG_PIPE : ZZZ_CG_PETSC;
     so.pc = o.pc_type == "none" ? ZZZ_PC_NONE : o.pc_type == "chebyshev_jacobi" ? ZZZ_PC_CHEBYSHEV_JACOBI : ZZZ_PC_JACOBI;
     so.pc_degree = o.pc_degree;
     so.pc_ratio = o.pc_ratio;
@@ -637,8 +637,8 @@ void solve(int argc, char** argv)
   if (o.problem_type != "poisson" && o.problem_type != "cgpoisson" && o.problem_type != "elasticity")
     throw std::runtime_error("Unknown problem type: " + o.problem_type); // src/main.cpp:170
   // src/main.cpp:131-141: "cube", anything else is the unstructured (spoke) mesh
-  if (o.ksp_type != "cg")
-    throw std::runtime_error("-ksp_type " + o.ksp_type + ": only cg is built");
+  if (o.ksp_type != "cg" && o.ksp_type != "pipecg")
+    throw std::runtime_error("-ksp_type " + o.ksp_type + ": only cg and pipecg are built");
   if (o.pc_type != "jacobi" && o.pc_type != "none" && o.pc_type != "chebyshev_jacobi")
     throw std::runtime_error("-pc_type " + o.pc_type +
                              ": only jacobi, none and chebyshev_jacobi are built (hypre/gamg are out of scope)");
@@ -658,6 +658,11 @@ void solve(int argc, char** argv)
                              "matrix-free kernel holds the Poisson form only)");
   if (o.op == "matfree" && (o.pc_type == "chebyshev_jacobi" || o.ksp_cg_single_reduction))
     throw std::runtime_error("--operator matfree: -pc_type jacobi or none, classical CG");
+  if (o.ksp_type == "pipecg" && o.problem_type == "cgpoisson")
+    throw std::runtime_error("-ksp_type pipecg: cgpoisson runs linalg::cg, not a KSP");
+  if (o.ksp_type == "pipecg" && (o.op == "matfree" || o.pc_type == "chebyshev_jacobi" || o.ksp_cg_single_reduction))
+    throw std::runtime_error("-ksp_type pipecg: the assembled operator with -pc_type jacobi or none, without "
+                             "-ksp_cg_single_reduction");
   if (o.ngpus < 1 || (o.comm == "rccl" && o.ngpus > ndev))
     throw std::runtime_error("--ngpus " + std::to_string(o.ngpus) + " but " + std::to_string(ndev) + " GPU(s) visible");
 
@@ -753,7 +758,7 @@ void solve(int argc, char** argv)
       throw std::runtime_error("rank " + std::to_string(r) + ": " + S.error[r]);
 
   if (o.ksp_view)
-    std::cout << "KSP Object: type: cg\n  maximum iterations=" << o.ksp_max_it << ", initial guess is zero\n  tolerances:  relative="
+    std::cout << "KSP Object: type: " << o.ksp_type << "\n  maximum iterations=" << o.ksp_max_it << ", initial guess is zero\n  tolerances:  relative="
               << o.ksp_rtol << ", absolute=" << o.ksp_atol << "\n  using " << o.ksp_norm_type
               << " norm type for convergence test\n"
               << (o.ksp_cg_single_reduction ? "  using single-reduction variant\n" : "") << "PC Object: type: " << o.pc_type

@@ -19,7 +19,7 @@ COEFF_F, COEFF_G = 0, 1
 VEC_B, VEC_U = 0, 1
 PC_NONE, PC_JACOBI, PC_CHEBYSHEV_JACOBI = 0, 1, 2
 NORM_PRECONDITIONED, NORM_UNPRECONDITIONED, NORM_NATURAL = 0, 1, 2
-CG_PETSC, CG_CGH = 0, 1
+CG_PETSC, CG_CGH, CG_PIPE = 0, 1, 2
 OP_CSR, OP_MATFREE = 0, 1
 ERR_NO_GPU = 4
 
@@ -613,7 +613,8 @@ class Context:
     def cg_info(self):
         info = (C.c_int64 * 4)()
         self._ck(self.L.zzz_cg_info(self.h, info))
-        return {"fused": bool(info[0] & 1), "dinv_codes": int(info[0] >> 8) if info[0] & 2 else 0, "reason": int(info[2]),
+        return {"fused": bool(info[0] & 1), "dinv_codes": int(info[0] >> 8) if info[0] & 2 else 0,
+                "allreduce_overlapped": bool(info[0] & 4), "reason": int(info[2]),
                 "pc_spectrum_bound": info[3] * 1.0e-6}
 
     def profile(self):
