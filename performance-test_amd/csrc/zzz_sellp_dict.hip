@@ -406,6 +406,8 @@ int sp_sd_build(zzz_ctx* ctx)
   memcpy(&b, h, sizeof(b));
   if (ctx->sellp_dict != 3 && (double)b > 0.6 * (double)ctx->sp_bytes)
     return ZZZ_OK;
+  if ((int64_t)h[2] >= nsl)
+    return ZZZ_OK; // (no slice got a dictionary: the stream is read as doubles and says so)
   ctx->sp_sd_bytes = (int64_t)b;
   ctx->sp_sd_on = true;
   ctx->sp_sd_all = h[2] == 0;

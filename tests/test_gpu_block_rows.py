@@ -54,7 +54,7 @@ def _run(P, x, **env):
                                         (3, (5, 5, 4))])
 def test_block_row_product_is_the_serial_csr_loop(order, dims):
     """Elasticity P1-P3: the product in block-row form == zo.spmv bit for bit == the generic stream's product
-    (ZZZ_SELLP_BLK=0); CG in the classical and the single-reduction form agrees with the generic kernel's solve
+    (ZZZ_SELLP_BLK=0) -- also where the form declines (P3), which is stated per parameter and asserted; CG in the classical and the single-reduction form agrees with the generic kernel's solve
     (iterations +-1, solution 1e-9) and with the oracle (iterations +-2, 1e-6); Chebyshev-Jacobi (its products carry an
     epilogue and stay on the generic kernel) is unchanged."""
     zo.set_num_threads(4)
@@ -63,16 +63,20 @@ def test_block_row_product_is_the_serial_csr_loop(order, dims):
     a = _run(P, x, ZZZ_SELLP_BLK=2, ZZZ_SELLP=2)
     b = _run(P, x, ZZZ_SELLP_BLK=0, ZZZ_SELLP=2)
     assert not b["vi"]["block_rows"]
-    if order > 1 and dims != (4, 4, 3) and not a["vi"]["block_rows"]:
-        # (P2 / P3 elasticity on all but tiny meshes: more than 2 048 distinct values -- declined, the generic stream serves it)
-        np.testing.assert_array_equal(a["y"], b["y"])
-        return
-    assert a["vi"]["block_rows"], a["vi"]
-    assert a["vi"]["block_table_entries"] >= 2 and a["vi"]["block_chunks"] >= 1
-    # few distinct blocks (dyadic coordinates, tiny meshes): the table's rows in LDS; else rows of offsets + a value dictionary
-    assert a["vi"]["block_form"] == (1 if a["vi"]["block_table_entries"] <= 2200 else 2)
-    if dims == (44, 40, 36):
-        assert a["vi"]["block_form"] == 2
+    # P1 and P2 here: at most 13 384 distinct blocks of at most 1 676 distinct values (P2 8^3, coordinates i / 8: 772 blocks) -- the
+    # form serves.  P3: 4 183 blocks of 7 733 values at 3 x 2 x 2, 20 474 of 18 480 at 5 x 5 x 4 (counted on the oracle's matrix):
+    # too many blocks for the table in LDS, too many values for form 2's dictionary -- declined, the generic stream serves, and
+    # everything below but the form's own figures is asserted all the same
+    serves = order < 3
+    assert a["vi"]["block_rows"] == serves, a["vi"]
+    if serves:
+        assert a["vi"]["block_table_entries"] >= 2 and a["vi"]["block_chunks"] >= 1
+        # few distinct blocks (dyadic coordinates, tiny meshes): the table's rows in LDS; else rows of offsets + a value dictionary
+        assert a["vi"]["block_form"] == (1 if a["vi"]["block_table_entries"] <= 2200 else 2)
+        if dims == (44, 40, 36):
+            assert a["vi"]["block_form"] == 2
+    else:
+        assert a["vi"]["special_form"] == "", a["vi"]
     rp, cl, v = a["csr"]
     oy = zo.spmv(rp.astype(np.int64), cl, v, x)
     np.testing.assert_array_equal(a["y"], oy)
