@@ -180,6 +180,14 @@ int zzz_ctx_create(int device, zzz_ctx** out)
     ctx->sellp_pipe = atoi(e);
   if (const char* e = getenv("ZZZ_CG_DINV_CODES"))
     ctx->cg_dinv_codes = atoi(e);
+  if (const char* e = getenv("ZZZ_CG_XDEFER")) // the classical CG's solution update once per K iterations: 0 never, 1 by size, 2 always
+    ctx->cg_xdefer = atoi(e);
+  if (const char* e = getenv("ZZZ_CG_XDEFER_K"))
+  {
+    const int v = atoi(e);
+    if (v == 2 || v == 4 || v == 8)
+      ctx->cg_xdefer_k = v;
+  }
   if (const char* e = getenv("ZZZ_SELLP_FORMS")) // A/B knob, a mask of the code-free chunk forms (default 7): 1 affine chunks
   {                                              // (column = slot base + lane), 2 one-chunk slices placed by column so that
     const int v = atoi(e);                       // short boundary rows fit the affine form, 4 periodic chunks (block size 3)
@@ -1055,7 +1063,9 @@ int zzz_cg_info(zzz_ctx* ctx, int64_t info[4])
 {
   if (!ctx || !info)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_cg_info: bad arguments");
-  info[0] = (ctx->last_solve_dinv_codes > 0 ? 2 : 0) | (ctx->last_solve_red_overlapped ? 4 : 0) | ((int64_t)ctx->last_solve_dinv_codes << 8);
+  // bit 3: the solution update was deferred; bits 4-7: over how many iterations (K; 1 when it was not)
+  info[0] = (ctx->last_solve_dinv_codes > 0 ? 2 : 0) | (ctx->last_solve_red_overlapped ? 4 : 0) | (ctx->last_solve_xdefer_k > 1 ? 8 : 0) |
+            ((int64_t)(ctx->last_solve_xdefer_k & 15) << 4) | ((int64_t)ctx->last_solve_dinv_codes << 8);
   info[1] = ctx->last_iters;
   info[2] = ctx->last_reason;
   info[3] = (int64_t)(ctx->last_pc_bound * 1.0e6); // Chebyshev-Jacobi: spectrum bound x 1e6

@@ -17,7 +17,11 @@
 // Every kernel returns at once when the device-side `converged` flag is set; the host polls that
 // flag a few iterations behind the queue, so the returned iteration count is exact.
 // Reductions use fixed trees => reproducible runs.
-// HBM traffic per iteration beyond the SpMV: 40 B/row (x and p update) + 40 B/row (r, z update).
+// HBM traffic per iteration beyond the SpMV, in-place loop: 40 B/row (x and p update) + 40 B/row (r, z update); with
+// Jacobi's inverse diagonal as codes and z recomputed (DZ) 42 + 26 = 68.  Where the loop runs out of HBM the solution
+// update is deferred (ZZZ_CG_XDEFER, k_update_p_light / _flush below): p_k in a ring of K vectors, x read and written
+// once per K iterations instead of in every one -- 16 B/row become 8 + 8/K, k_update_p 26 B/row in K - 1 of K launches
+// and 34 + 8 K in the K-th: 36 + 26 = 62 B/row on average at the default K = 4.
 #include "zzz_device.h"
 #include "zzz_internal.h"
 #include "zzz_cg.h"
@@ -314,6 +318,217 @@ __global__ __launch_bounds__(VB) void k_update_p(CgState* __restrict__ st, doubl
     if (dir)
       p[i] = bcoef * pi + (DZ ? dtab[reinterpret_cast<const uint16_t*>(dz.codes)[i]] * dz.r[i] : z[i]);
   }
+}
+
+// ---- the solution update deferred (ZZZ_CG_XDEFER): a ring of K direction vectors, x touched once per K iterations ----
+// Nothing in the loop reads x, yet k_update_p above reads and writes it in every iteration: 16 of its 42 B per row.
+// Here p_k lives in slot k mod K of a ring (slot 0 is ctx->p) and k_update_p comes in two forms:
+//   light (k mod K != 0, and k == 0): test and scalars as above, p_k = z_k + beta p_{k-1} from slot (k-1) mod K into
+//          slot k mod K.  x is not touched: 26 B per row with DZ.
+//   flush (k mod K == 0, k > 0): the same, and per entry the K pending updates x = alpha_j p_j + x, j = k-K .. k-1 in
+//          ascending order -- slots 0 .. K-1 in that order, because K divides k.  p_{k-1} is in registers anyway, the
+//          older K-1 are read for the last time, and the new p_k overwrites p_{k-K} in slot 0 by the lane that has
+//          just read it.  16 + 8 (K-1) B per row more than the light form.
+// Every entry of x receives the same multiplies and adds in the same order as in the in-place kernel, only later:
+// the same bits.  The launch that detects convergence at iteration c leaves the ring alone like every launch behind
+// it (a flush form still applies its updates, as the in-place kernel does), so the flushes that ran are those with
+// k mod K == 0 and k <= c, x holds the updates j < K floor(c / K), and slots 0 .. c mod K - 1 hold the directions of
+// the rest: k_x_apply_pending, after the loop, reads c on the device and applies them.
+constexpr int XD_KMAX = 8;
+struct PRing
+{
+  double* slot[XD_KMAX];
+};
+
+template <bool NT, bool DZ, int NF> // NF: updates applied by this launch (0: the light form; K: the flush form)
+__device__ __forceinline__ void update_p_deferred(CgState* __restrict__ st, double* __restrict__ beta_hist, double* __restrict__ dp_hist,
+                                                  const double* __restrict__ alpha_hist, int it, const CgParams& P,
+                                                  const double* __restrict__ pa, const double* __restrict__ pb, int np,
+                                                  const double* __restrict__ z, const double* pprev, double* pnew, const PRing& ring,
+                                                  double* __restrict__ x, int64_t n, int update_dir, const DinvCodes& dz)
+{
+  __shared__ double sh[VB / 64];
+  __shared__ double dtab[DZ ? DZ_MAX : 1];
+  if (DZ)
+  {
+    for (int k = threadIdx.x; k < dz.ndict; k += VB)
+      dtab[k] = dz.dict[k];
+    __syncthreads();
+  }
+  // first entries requested before the scalar prologue, as in k_update_p (the older directions of a flush are not: they
+  // would be K - 1 more 16-B requests per lane for a form that runs once in K iterations)
+  const int64_t n2 = n >> 1, stride = (int64_t)gridDim.x * VB;
+  const int64_t i0 = blockIdx.x * (int64_t)VB + threadIdx.x;
+  const dbl2* pp2 = reinterpret_cast<const dbl2*>(pprev);
+  dbl2* pn2 = reinterpret_cast<dbl2*>(pnew);
+  dbl2* __restrict__ x2 = reinterpret_cast<dbl2*>(x);
+  const dbl2* __restrict__ z2 = reinterpret_cast<const dbl2*>(DZ ? dz.r : z);
+  const int64_t c0 = (i0 < n2) ? i0 : 0;
+  dbl2 pi0 = {0, 0}, xi0 = {0, 0}, zi0 = {0, 0};
+  uint32_t dc0 = 0;
+  if (n2 > 0)
+  {
+    pi0 = pp2[c0];
+    if (NF)
+      xi0 = vload<NT>(x2 + c0);
+    zi0 = vload<NT>(z2 + c0); // DZ: r
+    if (DZ)
+      dc0 = dz.codes[c0];
+  }
+  double al[NF ? NF : 1]; // alpha_{it-K} .. alpha_{it-1}, requested with the rest of the prologue's inputs
+  if (NF)
+  {
+#pragma unroll
+    for (int j = 0; j < NF; ++j)
+      al[j] = alpha_hist[it - NF + j];
+  }
+  DirScalars S;
+  if (!cg_direction_scalars(st, beta_hist, dp_hist, it, P, pa, pb, np, sh, S))
+    return;
+  const bool dir = !S.conv && update_dir;
+  if (NF == 0)
+  {
+    if (!dir)
+      return; // nothing but the test: the pending updates are k_x_apply_pending's
+    if (it == 0)
+    {
+      for (int64_t i = blockIdx.x * (int64_t)VB + threadIdx.x; i < n; i += (int64_t)gridDim.x * VB)
+        pnew[i] = DZ ? dtab[reinterpret_cast<const uint16_t*>(dz.codes)[i]] * dz.r[i] : z[i];
+      return;
+    }
+  }
+  const double bcoef = S.rz / S.bprev;
+  for (int64_t i = i0; i < n2; i += stride)
+  {
+    dbl2 pi, xi = {0, 0}, zi;
+    if (i == i0)
+    {
+      pi = pi0;
+      xi = xi0;
+      zi = zi0;
+    }
+    else
+    {
+      pi = pp2[i];
+      if (NF)
+        xi = vload<NT>(x2 + i);
+      zi = vload<NT>(z2 + i);
+    }
+    if (DZ)
+    {
+      const uint32_t dc = i == i0 ? dc0 : dz.codes[i];
+      zi.x = dtab[dc & 0xffffu] * zi.x; // z = D^-1 r, as k_update_xr formed it for its sums
+      zi.y = dtab[dc >> 16] * zi.y;
+    }
+    if (NF)
+    {
+#pragma unroll
+      for (int j = 0; j < NF - 1; ++j)
+      {
+        // K = 8: at most four older directions in flight (all seven: 74 registers, six wavefronts per SIMD instead of eight)
+        if (j == 4)
+          __builtin_amdgcn_sched_barrier(0);
+        const dbl2 pj = vload<NT>(reinterpret_cast<const dbl2*>(ring.slot[j]) + i); // last use of p_{it-K+j}
+        xi.x = al[j] * pj.x + xi.x; // src/cg.h:68, up to K kernels late
+        xi.y = al[j] * pj.y + xi.y;
+      }
+      xi.x = al[NF - 1] * pi.x + xi.x;
+      xi.y = al[NF - 1] * pi.y + xi.y;
+      vstore<NT>(xi, x2 + i);
+    }
+    if (dir)
+    {
+      dbl2 pn;
+      pn.x = bcoef * pi.x + zi.x;
+      pn.y = bcoef * pi.y + zi.y;
+      pn2[i] = pn;
+    }
+  }
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0)
+  {
+    const int64_t i = n - 1;
+    const double pi = pprev[i];
+    if (NF)
+    {
+      double xi = x[i];
+#pragma unroll
+      for (int j = 0; j < NF - 1; ++j)
+        xi = al[j] * ring.slot[j][i] + xi;
+      x[i] = al[NF - 1] * pi + xi;
+    }
+    if (dir)
+      pnew[i] = bcoef * pi + (DZ ? dtab[reinterpret_cast<const uint16_t*>(dz.codes)[i]] * dz.r[i] : z[i]);
+  }
+}
+
+// (two kernels, not one with a flag: a kernel trace tells them apart by name)
+template <bool NT, bool DZ>
+__global__ __launch_bounds__(VB) void k_update_p_light(CgState* __restrict__ st, double* __restrict__ beta_hist, double* __restrict__ dp_hist,
+                                                       const double* __restrict__ alpha_hist, int it, CgParams P,
+                                                       const double* __restrict__ pa, const double* __restrict__ pb, int np,
+                                                       const double* __restrict__ z, const double* pprev, double* pnew, PRing ring,
+                                                       double* __restrict__ x, int64_t n, int update_dir, DinvCodes dz)
+{
+  update_p_deferred<NT, DZ, 0>(st, beta_hist, dp_hist, alpha_hist, it, P, pa, pb, np, z, pprev, pnew, ring, x, n, update_dir, dz);
+}
+template <bool NT, bool DZ, int K>
+__global__ __launch_bounds__(VB) void k_update_p_flush(CgState* __restrict__ st, double* __restrict__ beta_hist, double* __restrict__ dp_hist,
+                                                       const double* __restrict__ alpha_hist, int it, CgParams P,
+                                                       const double* __restrict__ pa, const double* __restrict__ pb, int np,
+                                                       const double* __restrict__ z, const double*, double*, PRing ring,
+                                                       double* __restrict__ x, int64_t n, int update_dir, DinvCodes dz)
+{
+  update_p_deferred<NT, DZ, K>(st, beta_hist, dp_hist, alpha_hist, it, P, pa, pb, np, z, ring.slot[K - 1], ring.slot[0], ring, x, n,
+                               update_dir, dz);
+}
+
+// The updates still pending when the solve has ended: j in [K floor(c / K), c), c = the iteration the solve stopped at
+// (st->iters; it_end = max_it when nothing stopped it), p_j in slot j mod K.  The one launch of a solve that runs
+// although the stop word is set; the host enqueues it once, without knowing c.
+template <int K>
+__global__ __launch_bounds__(VB) void k_x_apply_pending(const CgState* __restrict__ st, const double* __restrict__ alpha_hist, int it_end,
+                                                        PRing ring, double* __restrict__ x, int64_t n)
+{
+  const int c = st->converged ? st->iters : it_end;
+  const int lo = (c / K) * K, m = c - lo;
+  if (m == 0)
+    return;
+  double al[K - 1];
+#pragma unroll
+  for (int j = 0; j < K - 1; ++j)
+    al[j] = j < m ? alpha_hist[lo + j] : 0.0;
+  const int64_t n2 = n >> 1;
+  dbl2* __restrict__ x2 = reinterpret_cast<dbl2*>(x);
+  for (int64_t i = blockIdx.x * (int64_t)VB + threadIdx.x; i < n2; i += (int64_t)gridDim.x * VB)
+  {
+    dbl2 xi = x2[i];
+#pragma unroll
+    for (int j = 0; j < K - 1; ++j)
+      if (j < m)
+      {
+        const dbl2 pj = reinterpret_cast<const dbl2*>(ring.slot[j])[i];
+        xi.x = al[j] * pj.x + xi.x;
+        xi.y = al[j] * pj.y + xi.y;
+      }
+    x2[i] = xi;
+  }
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0)
+  {
+    double xi = x[n - 1];
+#pragma unroll
+    for (int j = 0; j < K - 1; ++j)
+      if (j < m)
+        xi = al[j] * ring.slot[j][n - 1] + xi;
+    x[n - 1] = xi;
+  }
+}
+
+typedef void (*update_p_ring_fn)(CgState*, double*, double*, const double*, int, CgParams, const double*, const double*, int,
+                                 const double*, const double*, double*, PRing, double*, int64_t, int, DinvCodes);
+template <bool NT, bool DZ>
+static update_p_ring_fn pick_update_p_flush(int K)
+{
+  return K == 2 ? k_update_p_flush<NT, DZ, 2> : K == 4 ? k_update_p_flush<NT, DZ, 4> : k_update_p_flush<NT, DZ, 8>;
 }
 
 template <bool NT, bool DZ = false>
@@ -772,6 +987,7 @@ int cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
 {
   ctx->last_pc_bound = 0.0;
   ctx->last_solve_red_overlapped = false;
+  ctx->last_solve_xdefer_k = 1;
   if (o->variant == ZZZ_CG_PIPE)
     return cg_solve_pipe(ctx, o, iters, rnorm); // zzz_cg_pipe.hip
   if (o->pc == ZZZ_PC_CHEBYSHEV_JACOBI && !o->single_reduction)
@@ -821,6 +1037,55 @@ int cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
   const bool dz = dzc.codes != nullptr;
   auto kern_update_p = pick_update_p(dz);
   auto kern_update_xr = pick_update_xr(dz);
+
+  // The solution update deferred (k_update_p_light / _flush): where x comes from HBM, i.e. under the same rule as the
+  // load policy (ZZZ_CG_XDEFER: 0 never, 2 at any size; ZZZ_CG_XDEFER_K: the ring's length).  Slot 0 is ctx->p, the other
+  // slots are allocated at the first solve that uses them and kept.  Owned entries of a slot are written in full by the
+  // k_update_p that forms its direction before anything reads them; ghost tail and padding are cleared here, once per solve,
+  // as the memset above does for ctx->p.
+  int K = (ctx->cg_xdefer != 0 && (ctx->cg_xdefer == 2 || nt)) ? ctx->cg_xdefer_k : 1;
+  PRing ring{};
+  ring.slot[0] = ctx->p.p;
+  for (int j = 1; j < K; ++j)
+  {
+    DevBuf<double>& rb = ctx->p_ring[j - 1];
+    const double* before = rb.p;
+    if (rb.reserve(ctx->p.n) != hipSuccess)
+    {
+      (void)hipGetLastError();
+      for (DevBuf<double>& b : ctx->p_ring)
+        b.release();
+      fprintf(stderr, "zzz: no memory for %d more direction vectors of %zu entries: CG updates the solution in every iteration (K = 1)\n",
+              K - 1, ctx->p.n);
+      K = 1;
+      break;
+    }
+    if (rb.p != before)
+      ZZZ_HIP(ctx, hipMemsetAsync(rb.p, 0, sizeof(double) * rb.cap, s));
+    else if (ctx->p.n > (size_t)n)
+      ZZZ_HIP(ctx, hipMemsetAsync(rb.p + n, 0, sizeof(double) * (ctx->p.n - (size_t)n), s));
+    ring.slot[j] = rb.p;
+  }
+  ctx->last_solve_xdefer_k = K;
+  update_p_ring_fn kern_light = nullptr, kern_flush = nullptr;
+  if (K > 1)
+  {
+    kern_light = dz ? (nt ? k_update_p_light<true, true> : k_update_p_light<false, true>)
+                    : (nt ? k_update_p_light<true, false> : k_update_p_light<false, false>);
+    kern_flush = dz ? (nt ? pick_update_p_flush<true, true>(K) : pick_update_p_flush<false, true>(K))
+                    : (nt ? pick_update_p_flush<true, false>(K) : pick_update_p_flush<false, false>(K));
+  }
+  // the test of iteration k and (update_dir) the direction p_k; where p_k lives
+  auto dir_of = [&](int k) { return ring.slot[k % K]; };
+  auto launch_update_p = [&](int k, int update_dir, const double* rz_src, const double* nn_src, int n_rz) {
+    if (K == 1)
+      hipLaunchKernelGGL(kern_update_p, dim3(g), dim3(VB), 0, s, ctx->state.p, ctx->beta_hist.p, ctx->dp_hist.p, ctx->alpha_hist.p, k,
+                         P, rz_src, nn_src, n_rz, ctx->z.p, ctx->p.p, ctx->u.p, n, update_dir, dzc);
+    else
+      hipLaunchKernelGGL((k > 0 && k % K == 0) ? kern_flush : kern_light, dim3(g), dim3(VB), 0, s, ctx->state.p, ctx->beta_hist.p,
+                         ctx->dp_hist.p, ctx->alpha_hist.p, k, P, rz_src, nn_src, n_rz, ctx->z.p, (const double*)dir_of(k + K - 1),
+                         dir_of(k), ring, ctx->u.p, n, update_dir, dzc);
+  };
 
   auto apply = [&](double* x, double* y, double* parts, int* np) -> int {
     // partitioned CSR operator: halo of x overlapped with the interior tiles
@@ -899,15 +1164,14 @@ int cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
   for (; it < max_it && !stop; ++it)
   {
     // convergence test of iteration `it` and the new search direction
-    hipLaunchKernelGGL(kern_update_p, dim3(g), dim3(VB), 0, s, ctx->state.p, ctx->beta_hist.p, ctx->dp_hist.p,
-                       ctx->alpha_hist.p, it, P, rz_src, nn_src, n_rz, ctx->z.p, ctx->p.p, ctx->u.p, n, 1, dzc);
+    launch_update_p(it, 1, rz_src, nn_src, n_rz);
     int np = 0;
     const bool timed = nprof < max_prof && it % PROF_STRIDE == 0;
     ctx->prof_now = timed;
     if (timed)
       (void)hipEventRecord(ctx->ev[2 * nprof], s);
     {
-      int rc = apply(ctx->p.p, ctx->w.p, ctx->part_a.p, &np);
+      int rc = apply(dir_of(it), ctx->w.p, ctx->part_a.p, &np);
       if (rc)
         return rc;
     }
@@ -945,8 +1209,14 @@ int cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
   }
   // the test of the last completed iteration (it == max_it when the loop ran out) and its pending
   // solution update; no new direction
-  hipLaunchKernelGGL(kern_update_p, dim3(g), dim3(VB), 0, s, ctx->state.p, ctx->beta_hist.p, ctx->dp_hist.p,
-                     ctx->alpha_hist.p, it, P, rz_src, nn_src, n_rz, ctx->z.p, ctx->p.p, ctx->u.p, n, 0, dzc);
+  launch_update_p(it, 0, rz_src, nn_src, n_rz);
+  // ... and, with the update deferred, those of the iterations since the last flush that ran
+  if (K == 2)
+    hipLaunchKernelGGL(k_x_apply_pending<2>, dim3(g), dim3(VB), 0, s, ctx->state.p, ctx->alpha_hist.p, it, ring, ctx->u.p, n);
+  else if (K == 4)
+    hipLaunchKernelGGL(k_x_apply_pending<4>, dim3(g), dim3(VB), 0, s, ctx->state.p, ctx->alpha_hist.p, it, ring, ctx->u.p, n);
+  else if (K == 8)
+    hipLaunchKernelGGL(k_x_apply_pending<8>, dim3(g), dim3(VB), 0, s, ctx->state.p, ctx->alpha_hist.p, it, ring, ctx->u.p, n);
   ZZZ_HIP(ctx, hipGetLastError());
   CgState fin;
   ZZZ_HIP(ctx, hipMemcpyAsync(&fin, ctx->state.p, sizeof(CgState), hipMemcpyDeviceToHost, s));
@@ -1242,6 +1512,7 @@ static int chebyshev_esteig(zzz_ctx* ctx, const zzz_solver_opts* o, int its, dou
   double rn[2];
   const int rc = cg_solve(ctx, &o2, &ran, rn);
   swap_b();
+  ctx->last_solve_xdefer_k = 1; // (zzz_cg_info reports the solve this estimate belongs to, and that one keeps its kernels)
   if (rc)
     return rc;
   if (ran < 2)

@@ -308,6 +308,12 @@ struct zzz_ctx
   zzz::DevBuf<uint16_t> dd_codes;
   int cg_dinv_codes = 1;          // ZZZ_CG_DINV_CODES: 0 never, 1 when the CG loop exceeds the Infinity Cache, 2 always
   int last_solve_dinv_codes = 0;  // distinct values of the inverse diagonal when the last solve ran on codes, else 0
+  // the classical loop's solution update applied once per K iterations from a ring of K direction vectors (zzz_cg.hip,
+  // k_update_p_light / _flush): slot 0 of the ring is `p`, these are slots 1 .. K-1
+  zzz::DevBuf<double> p_ring[7];
+  int cg_xdefer = 1;              // ZZZ_CG_XDEFER: 0 never, 1 when the CG loop exceeds the Infinity Cache, 2 always
+  int cg_xdefer_k = 4;            // ZZZ_CG_XDEFER_K: 2, 4 or 8
+  int last_solve_xdefer_k = 1;    // the ring's length in the last solve (1: x updated in place in every iteration)
   int sp_dict_n = 0;        // distinct values (with +0.0)
   int64_t sp_dict_bytes = 0; // bytes a product reads from the stream in dictionary form
   bool sp_sorted = false;    // rows ordered by length inside windows (SELL-C-sigma)

@@ -614,7 +614,8 @@ class Context:
         info = (C.c_int64 * 4)()
         self._ck(self.L.zzz_cg_info(self.h, info))
         return {"fused": bool(info[0] & 1), "dinv_codes": int(info[0] >> 8) if info[0] & 2 else 0,
-                "allreduce_overlapped": bool(info[0] & 4), "reason": int(info[2]),
+                "allreduce_overlapped": bool(info[0] & 4), "xdefer_k": int((info[0] >> 4) & 15) if info[0] & 8 else 1,
+                "reason": int(info[2]),
                 "pc_spectrum_bound": info[3] * 1.0e-6}
 
     def profile(self):
