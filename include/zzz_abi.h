@@ -84,7 +84,25 @@ enum
    * fewer CG iterations, i.e. fewer all-reduces per solve, for more products -- for multi-GPU runs.  Spectrum
    * bounds [hi / pc_ratio, hi] with hi = min(Gershgorin's bound of D^-1 A, 1.1 x a Lanczos estimate: pc_esteig_its).
    * ZZZ_CG_PETSC + ZZZ_OP_CSR only (classical or single-reduction form). */
-  ZZZ_PC_CHEBYSHEV_JACOBI = 2
+  ZZZ_PC_CHEBYSHEV_JACOBI = 2,
+  /* geometric multigrid: one V-cycle per application (PCSetUp / PCApply of PETSc's PCMG behind
+   * solver.set_from_options(), src/poisson_problem.cpp:169; the reference's README.md:59-146 runs every recommended
+   * configuration with a multigrid preconditioner, GAMG or BoomerAMG -- this is the geometric counterpart for its own
+   * cube meshes, not an algebraic one).  Scope: P1, Poisson and elasticity, a context whose feed came from
+   * zzz_cube_generate with nparts == 1, the assembled operator, ZZZ_CG_PETSC in its classical form, all three norm
+   * types.  Declined with ZZZ_ERR_ARG and a message that names the reason (the context stays usable): order 2 or 3,
+   * an uploaded / unstructured feed, a communicator attached, ZZZ_OP_MATFREE, single_reduction, ZZZ_CG_PIPE, ZZZ_CG_CGH.
+   * Level l+1 is the same problem RE-DISCRETISED on max(2, (n+1)/2) cells per axis (not nested when n is odd), generated,
+   * patterned and assembled by the library's own kernels; the coarsest level is the first with at most
+   * pc_mg_coarse_eq_limit scalar dofs (or 2 x 2 x 2 cells, or level pc_mg_levels, 12 at most) and is solved with a dense
+   * inverse (at most 4 096 dofs).  Transfer: the coarse Kuhn-P1 function evaluated at the fine vertices, closed form, no
+   * P stored, constrained dofs zeroed on both sides.  Smoother: pc_degree steps of Chebyshev-Jacobi on
+   * [hi / pc_ratio, hi] before (from zero) and after (from the corrected iterate) -- the same polynomial, so the cycle is
+   * symmetric; for mg pc_degree == 0 selects 2 and pc_ratio <= 1 selects 10; hi is each level's own bound, taken as
+   * ZZZ_PC_CHEBYSHEV_JACOBI takes it (pc_esteig_its).  The hierarchy is built by the first solve (or zzz_mg_setup), kept
+   * across solves, rebuilt when the feed changes, its values refreshed when the matrix values change.  After
+   * zzz_csr_upload_values on the context the coarse levels STAY the re-discretised ones of the generated problem. */
+  ZZZ_PC_MG = 3
 };
 enum
 {
@@ -138,7 +156,11 @@ typedef struct
   int32_t pc_esteig_its; /* ZZZ_PC_CHEBYSHEV_JACOBI: Jacobi-PCG iterations on a noise vector whose Lanczos coefficients give
                           * the estimate of the largest eigenvalue of D^-1 A (PETSc's -ksp_chebyshev_esteig, safety factor
                           * 1.1); the bound used is min(Gershgorin's, 1.1 x estimate).  0 selects 10, < 0 Gershgorin alone */
-  double pc_ratio;   /* ZZZ_PC_CHEBYSHEV_JACOBI: upper / lower bound of the targeted spectrum (<= 1 selects 60) */
+  double pc_ratio;   /* ZZZ_PC_CHEBYSHEV_JACOBI: upper / lower bound of the targeted spectrum (<= 1 selects 60; ZZZ_PC_MG: 10) */
+  /* (added with ABI version 7 behind the fields above, whose layout is unchanged; zero selects the defaults) */
+  int32_t pc_mg_levels;          /* ZZZ_PC_MG: most levels (-pc_mg_levels); 0: as many as the coarse limit asks for, <= 12 */
+  int32_t pc_mg_coarse_eq_limit; /* ZZZ_PC_MG: the coarsest level is the first with at most this many scalar dofs; 0 selects
+                                  * 1000, what the reference's README.md passes to GAMG (-pc_gamg_coarse_eq_limit 1000) */
 } zzz_solver_opts;
 
 /* ---- library / device ------------------------------------------------------------------ */
@@ -381,8 +403,26 @@ int zzz_spmv_info(zzz_ctx* ctx, int64_t info[8]);
  * info[7] still counts the blocks); info[2] is then the bytes of THAT form. */
 int zzz_spmv_values_info(zzz_ctx* ctx, int64_t info[4]);
 int zzz_spmv_values_info2(zzz_ctx* ctx, int n, int64_t* info);
-/* Version of this header's ABI: bumped whenever an existing entry point changes what it reads or writes (6: round 6). */
-#define ZZZ_ABI_VERSION 6
+/* ---- geometric multigrid (ZZZ_PC_MG) ----------------------------------------------------------
+ * PCSetUp(PCMG) behind solver.set_from_options() (src/poisson_problem.cpp:169; README.md:59-146): builds the hierarchy
+ * for these options, or refreshes its values after an assembly.  Optional: zzz_cg_solve(pc = ZZZ_PC_MG) does it on first
+ * use, inside the solve, where PETSc's PCSetUp runs.  Overwrites the context's Krylov work vectors (not b, not u). */
+int zzz_mg_setup(zzz_ctx* ctx, const zzz_solver_opts* opts);
+/* PCView of that hierarchy.  level < 0: out = {levels, scalar dofs of the coarsest, set-ups done so far (builds and
+ * refreshes), products per V-cycle on level 0, device bytes of the coarse levels, HIP-event ms per V-cycle in the last solve
+ * with opts.profile != 0 (else 0), host ms of the last set-up that did work (it ends synchronised), 0}.  Otherwise that level's
+ * {nx, ny, nz, scalar dofs, nonzeros, hi, lo, smoother degree} (hi = lo = degree = 0 on the coarsest: a dense solve). */
+int zzz_mg_info(zzz_ctx* ctx, int level, double out[8]);
+/* PCApply: z = M r, one V-cycle on host vectors of the owned size -- zzz_spmv's counterpart, for parity checks. */
+int zzz_mg_apply(zzz_ctx* ctx, const double* r, double* z);
+/* The grid transfer between level and level + 1 alone (MatInterpolate / MatRestrict of PCMG): dir 0 gives
+ * out = P~ in (in: level + 1, out: level), dir 1 gives out = P~^T in.  P~ = F_f P F_c with F zeroing the constrained
+ * dofs.  The restriction sums in a fixed order: two calls give the same bits. */
+int zzz_mg_transfer(zzz_ctx* ctx, int level, int dir, const double* in, double* out);
+
+/* Version of this header's ABI: bumped whenever an existing entry point changes what it reads or writes (7: zzz_cg_solve
+ * reads the two pc_mg_* fields behind pc_ratio). */
+#define ZZZ_ABI_VERSION 7
 int zzz_abi_version(void);
 
 /* ---- multi-GPU (one context per GPU; RCCL over xGMI) --------------------------------------- */

@@ -146,6 +146,7 @@ int zzz_ctx_create(int device, zzz_ctx** out)
       zzz::preload_cg_pipe();
       zzz::preload_comm();
       zzz::preload_matfree();
+      zzz::preload_mg();
       zzz::preload_nullspace();
       (void)hipGetLastError();
     }
@@ -225,6 +226,7 @@ void zzz_ctx_destroy(zzz_ctx* ctx)
   (void)hipSetDevice(ctx->device);
   if (ctx->stream)
     (void)hipStreamSynchronize(ctx->stream);
+  mg_destroy(ctx);
   comm_destroy(ctx);
   for (hipEvent_t ev : ctx->ev)
     (void)hipEventDestroy(ev);
@@ -236,7 +238,7 @@ void zzz_ctx_destroy(zzz_ctx* ctx)
     (void)hipHostFree(ctx->h_state);
   if (ctx->adj_flag_host)
     (void)hipHostFree(ctx->adj_flag_host);
-  if (ctx->stream)
+  if (ctx->stream && !ctx->stream_borrowed)
     (void)hipStreamDestroy(ctx->stream);
   for (void* q : ctx->retired)
     (void)hipFree(q);
@@ -273,6 +275,8 @@ int zzz_sync(zzz_ctx* ctx)
 int zzz_mesh_upload(zzz_ctx* ctx, int64_t nverts, const double* x, int64_t ncells, const int32_t* cell_verts)
 {
   ZZZ_ENTER(ctx);
+  ctx->cube_feed = false; // (ZZZ_PC_MG needs a generated cube)
+  ++ctx->feed_version;
   if (nverts <= 0 || ncells <= 0 || !x || !cell_verts)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_mesh_upload: empty mesh or NULL array");
   if (nverts > INT32_MAX / 4 || ncells > (INT32_MAX - 8) / 20)
@@ -297,6 +301,8 @@ int zzz_mesh_upload(zzz_ctx* ctx, int64_t nverts, const double* x, int64_t ncell
 int zzz_dofmap_upload(zzz_ctx* ctx, int order, int bs, const int32_t* cell_dofs, int64_t n_owned, int64_t n_ghost)
 {
   ZZZ_ENTER(ctx);
+  ctx->cube_feed = false; // (ZZZ_PC_MG needs a generated cube)
+  ++ctx->feed_version;
   const int nd = ndofs_cell(order);
   if (nd < 0) // form_poisson_a.at(order - 1) throws std::out_of_range in the reference
     return fail(ctx, ZZZ_ERR_ARG, "order %d not supported (1..3)", order);
@@ -347,6 +353,8 @@ int zzz_dofmap_upload(zzz_ctx* ctx, int order, int bs, const int32_t* cell_dofs,
 int zzz_bc_upload(zzz_ctx* ctx, int64_t nbc, const int32_t* bc_dofs)
 {
   ZZZ_ENTER(ctx);
+  ctx->cube_feed = false; // (ZZZ_PC_MG needs a generated cube)
+  ++ctx->feed_version;
   if (ctx->order == 0)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_bc_upload before zzz_dofmap_upload");
   if (nbc < 0 || (nbc > 0 && !bc_dofs))
@@ -371,6 +379,8 @@ int zzz_bc_upload(zzz_ctx* ctx, int64_t nbc, const int32_t* bc_dofs)
 int zzz_facets_upload(zzz_ctx* ctx, int64_t nfacets, const int32_t* pairs)
 {
   ZZZ_ENTER(ctx);
+  ctx->cube_feed = false; // (ZZZ_PC_MG needs a generated cube)
+  ++ctx->feed_version;
   if (ctx->order == 0)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_facets_upload before zzz_dofmap_upload");
   if (nfacets < 0 || (nfacets > 0 && !pairs))
@@ -962,8 +972,11 @@ int zzz_cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rno
                                   "-ksp_cg_single_reduction");
   if (o->variant == ZZZ_CG_CGH && o->pc != ZZZ_PC_NONE)
     return fail(ctx, ZZZ_ERR_ARG, "src/cg.h has no preconditioner: use pc = ZZZ_PC_NONE");
-  if (o->pc != ZZZ_PC_NONE && o->pc != ZZZ_PC_JACOBI && o->pc != ZZZ_PC_CHEBYSHEV_JACOBI)
-    return fail(ctx, ZZZ_ERR_ARG, "unsupported preconditioner %d (none, jacobi, chebyshev-jacobi)", o->pc);
+  if (o->pc != ZZZ_PC_NONE && o->pc != ZZZ_PC_JACOBI && o->pc != ZZZ_PC_CHEBYSHEV_JACOBI && o->pc != ZZZ_PC_MG)
+    return fail(ctx, ZZZ_ERR_ARG, "unsupported preconditioner %d (none, jacobi, chebyshev-jacobi, mg)", o->pc);
+  if (o->pc == ZZZ_PC_MG)
+    if (int rc = mg_check(ctx, o))
+      return rc;
   if (o->pc == ZZZ_PC_CHEBYSHEV_JACOBI && o->op != ZZZ_OP_CSR)
     return fail(ctx, ZZZ_ERR_ARG, "the Chebyshev-Jacobi preconditioner needs the assembled operator");
   if (o->pc == ZZZ_PC_CHEBYSHEV_JACOBI && (o->variant != ZZZ_CG_PETSC || o->pc_degree < 0 || o->pc_degree > 64 || o->pc_esteig_its > 64))

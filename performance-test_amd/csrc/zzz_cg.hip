@@ -992,6 +992,8 @@ int cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
     return cg_solve_pipe(ctx, o, iters, rnorm); // zzz_cg_pipe.hip
   if (o->pc == ZZZ_PC_CHEBYSHEV_JACOBI && !o->single_reduction)
     return cg_solve_chebyshev(ctx, o, iters, rnorm);
+  if (o->pc == ZZZ_PC_MG)
+    return cg_solve_mg(ctx, o, iters, rnorm);
   if (o->single_reduction)
     return cg_solve_single_reduction(ctx, o, iters, rnorm);
   const int64_t n = ctx->n_owned * ctx->bs; // owned scalar rows
@@ -1851,6 +1853,128 @@ static int cg_solve_chebyshev(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters
   if (ctx->prof_spmv_n)
     ctx->prof_spmv_ms /= (double)ctx->prof_spmv_n;
   ctx->last_pc_bound = hi;
+  return finish_reason(ctx, o, fin, its);
+}
+
+int chebyshev_bound(zzz_ctx* ctx, const zzz_solver_opts* o, double* hi)
+{
+  ChebPlan C;
+  if (int rc = chebyshev_setup(ctx, o, C))
+    return rc;
+  *hi = C.hi;
+  return ZZZ_OK;
+}
+
+// ---- KSPCG with the multigrid preconditioner (ZZZ_PC_MG, zzz_mg.hip) -------------------------------------------------
+// cg_solve_chebyshev with "V-cycle, then k_dots_rz" in the polynomial's place: the scalar logic, history and reasons are
+// the classical loop's (k_update_p, k_update_xr).  An iteration is a few milliseconds of device work at the sizes that
+// matter and there are about ten of them, so the state is read back in EVERY iteration, behind k_update_p and ahead of
+// the product and the cycle the host enqueues before it waits for it: one iteration of lag, and the cycle's own
+// kernels return at once on the device's stop flag.
+int cg_solve_mg(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
+{
+  const int64_t n = ctx->n_owned * ctx->bs;
+  const int max_it = o->max_it;
+  CgParams P{o->variant, ZZZ_PC_JACOBI, o->norm, o->rtol, o->atol, o->dtol > 0.0 ? o->dtol : 1.0e4};
+  const int g = vgrid(n);
+  hipStream_t s = ctx->stream;
+  if (int rc = mg_setup(ctx, o)) // PCSetUp: runs the levels' spectrum estimates through this context's CG vectors
+    return rc;
+  ZZZ_HIP(ctx, ctx->beta_hist.reserve((size_t)max_it + 2));
+  ZZZ_HIP(ctx, ctx->dp_hist.reserve((size_t)max_it + 2));
+  ZZZ_HIP(ctx, ctx->alpha_hist.reserve((size_t)max_it + 2));
+  ZZZ_HIP(ctx, hipMemsetAsync(ctx->state.p, 0, sizeof(CgState), s));
+  ZZZ_HIP(ctx, hipMemsetAsync(ctx->p.p, 0, sizeof(double) * ctx->p.n, s));
+  ZZZ_HIP(ctx, hipMemsetAsync(ctx->u.p, 0, sizeof(double) * ctx->u.n, s)); // KSP zero initial guess
+  hipLaunchKernelGGL(k_extract_dinv, dim3(g), dim3(VB), 0, s, ctx->rowptr.p, ctx->cols.p, ctx->vals.p, ctx->dinv.p, n, 1);
+  const int* stop_flag = reinterpret_cast<const int*>(ctx->state.p);
+  double* pa = ctx->part_b.p;
+  double* pb = ctx->part_b.p + VGRID_MAX;
+  mg_profile_begin(ctx);
+  auto precondition = [&]() -> int {
+    if (int rc = mg_vcycle(ctx, ctx->r.p, ctx->z.p, o->profile != 0))
+      return rc;
+    hipLaunchKernelGGL(k_dots_rz, dim3(g), dim3(VB), 0, s, stop_flag, ctx->r.p, ctx->z.p, n, P.norm, pa, pb);
+    return ZZZ_OK;
+  };
+  hipLaunchKernelGGL(k_init_residual, dim3(g), dim3(VB), 0, s, ctx->b.p, (const double*)nullptr, ctx->dinv.p, ctx->r.p, ctx->z.p, n,
+                     P.norm, pa, pb);
+  if (int rc = precondition())
+    return rc;
+  const int max_prof = o->profile ? 512 : 0;
+  if ((int)ctx->ev.size() < 2 * max_prof)
+  {
+    size_t old = ctx->ev.size();
+    ctx->ev.resize(2 * max_prof);
+    for (size_t i = old; i < ctx->ev.size(); ++i)
+      ZZZ_HIP(ctx, hipEventCreate(&ctx->ev[i]));
+  }
+  int nprof = 0;
+  ctx->prof_halo_n = 0;
+  ctx->prof_halo_wait_ms = 0.0;
+  constexpr int NSLOT = 2;
+  EventRing<NSLOT> chk_ev;
+  ZZZ_HIP(ctx, chk_ev.create());
+  bool stop = false;
+  int it = 0;
+  for (; it < max_it && !stop; ++it)
+  {
+    hipLaunchKernelGGL(k_update_p<false>, dim3(g), dim3(VB), 0, s, ctx->state.p, ctx->beta_hist.p, ctx->dp_hist.p, ctx->alpha_hist.p,
+                       it, P, pa, pb, g, ctx->z.p, ctx->p.p, ctx->u.p, n, 1);
+    const int slot = it % NSLOT;
+    ZZZ_HIP(ctx, hipMemcpyAsync(&ctx->h_state[slot], ctx->state.p, sizeof(CgState), hipMemcpyDeviceToHost, s));
+    ZZZ_HIP(ctx, hipEventRecord(chk_ev[slot], s));
+    int np = 0;
+    const bool timed = nprof < max_prof;
+    if (timed)
+      (void)hipEventRecord(ctx->ev[2 * nprof], s);
+    if (int rc = launch_spmv(ctx, ctx->p.p, ctx->w.p, ctx->part_a.p, &np))
+      return rc;
+    if (timed)
+    {
+      (void)hipEventRecord(ctx->ev[2 * nprof + 1], s);
+      ++nprof;
+    }
+    hipLaunchKernelGGL(k_update_xr<false>, dim3(g), dim3(VB), 0, s, ctx->state.p, ctx->beta_hist.p, ctx->alpha_hist.p, it,
+                       ctx->part_a.p, np, ctx->w.p, ctx->dinv.p, ctx->r.p, ctx->z.p, n, P.norm, pa, pb, P.variant, DinvCodes());
+    if (int rc = precondition())
+      return rc;
+    ZZZ_HIP(ctx, hipEventSynchronize(chk_ev[slot]));
+    if (ctx->h_state[slot].converged)
+      stop = true;
+  }
+  hipLaunchKernelGGL(k_update_p<false>, dim3(g), dim3(VB), 0, s, ctx->state.p, ctx->beta_hist.p, ctx->dp_hist.p, ctx->alpha_hist.p, it,
+                     P, pa, pb, g, ctx->z.p, ctx->p.p, ctx->u.p, n, 0);
+  ZZZ_HIP(ctx, hipGetLastError());
+  CgState fin;
+  ZZZ_HIP(ctx, hipMemcpyAsync(&fin, ctx->state.p, sizeof(CgState), hipMemcpyDeviceToHost, s));
+  ZZZ_HIP(ctx, hipStreamSynchronize(s));
+  const int its = fin.converged ? fin.iters : max_it;
+  ctx->last_iters = its;
+  if (iters)
+    *iters = its;
+  if (rnorm)
+  {
+    rnorm[0] = fin.dp;
+    rnorm[1] = fin.dp0;
+  }
+  ctx->history.resize((size_t)its + 1);
+  ZZZ_HIP(ctx, hipMemcpy(ctx->history.data(), ctx->dp_hist.p, sizeof(double) * ((size_t)its + 1), hipMemcpyDeviceToHost));
+  ctx->prof_spmv_ms = 0.0;
+  ctx->prof_spmv_n = 0;
+  for (int i = 0; i < std::min(nprof, its); ++i)
+  {
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, ctx->ev[2 * i], ctx->ev[2 * i + 1]) == hipSuccess)
+    {
+      ctx->prof_spmv_ms += ms;
+      ctx->prof_spmv_n++;
+    }
+  }
+  if (ctx->prof_spmv_n)
+    ctx->prof_spmv_ms /= (double)ctx->prof_spmv_n;
+  mg_profile_end(ctx, o->profile ? its + 1 : 0); // (the cycle of the start-up and one per iteration that ran)
+  ctx->last_pc_bound = mg_level0_bound(ctx);
   return finish_reason(ctx, o, fin, its);
 }
 

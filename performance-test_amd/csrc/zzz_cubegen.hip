@@ -176,6 +176,14 @@ extern "C" int zzz_cube_generate(zzz_ctx* ctx, int problem, int order, int64_t n
                        send_idx.empty() ? &zero32 : send_idx.data(), recv_cnt.empty() ? &zero64 : recv_cnt.data());
   if (rc)
     return rc;
+  // what ZZZ_PC_MG coarsens (zzz_mg.hip); zzz_halo_upload above is no feed change of its own
+  ctx->cube_feed = true;
+  ctx->cube_problem = problem;
+  ctx->cube_nparts = nparts;
+  ctx->cube_n[0] = nx;
+  ctx->cube_n[1] = ny;
+  ctx->cube_n[2] = nz;
+  ++ctx->feed_version;
   if (info)
   {
     info[0] = S.L.total() * bs;      // index_map.size_global() * bs (src/main.cpp:178-180)

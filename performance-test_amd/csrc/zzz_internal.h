@@ -100,6 +100,7 @@ struct DevBuf
 };
 
 struct Comm; // zzz_comm.cpp
+struct MgHier; // zzz_mg.hip: the level hierarchy of ZZZ_PC_MG
 
 typedef int64_t rp_t; // row pointers of the CSR matrix of record
 
@@ -431,6 +432,15 @@ struct zzz_ctx
   bool last_solve_red_overlapped = false; // the last solve's all-reduces went to red_stream (zzz_cg_info)
   bool overlap = true; // ZZZ_OVERLAP=0 disables the halo/compute overlap
 
+  // ZZZ_PC_MG (zzz_mg.hip): the cube this context's feed was generated from by zzz_cube_generate (cleared by every
+  // upload of mesh, dofmap, Dirichlet set or facets; feed_version counts all of them), and the hierarchy built on it
+  bool cube_feed = false;
+  int cube_problem = 0, cube_nparts = 0;
+  int64_t cube_n[3] = {0, 0, 0};
+  uint64_t feed_version = 0;
+  zzz::MgHier* mg = nullptr;
+  bool stream_borrowed = false; // a coarse level of another context's hierarchy: `stream` is that context's
+
   int64_t nloc() const { return (n_owned + n_ghost) * bs; }
 };
 
@@ -464,6 +474,7 @@ void preload_cg_pipe();
 void preload_comm();
 void preload_cubegen();
 void preload_matfree();
+void preload_mg();
 void preload_nullspace();
 void preload_pattern();
 void preload_renumber();
@@ -526,6 +537,19 @@ int mf_diagonal(zzz_ctx* ctx, double* y);
 // kernels_cg
 int cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm);
 int vec_norm_local(zzz_ctx* ctx, const double* v, int64_t n, double* out);
+
+// multigrid preconditioner (zzz_mg.hip)
+int mg_check(zzz_ctx* ctx, const zzz_solver_opts* o);   // ZZZ_ERR_ARG with the reason when ZZZ_PC_MG does not apply
+int mg_setup(zzz_ctx* ctx, const zzz_solver_opts* o);   // builds / refreshes the hierarchy (synchronises; clobbers the CG vectors)
+int mg_vcycle(zzz_ctx* ctx, const double* r, double* z, bool timed); // z = M r enqueued on ctx->stream, skipped once ctx->state says stop
+void mg_profile_begin(zzz_ctx* ctx);           // zzz_solver_opts.profile: HIP events around the cycles of a solve ...
+void mg_profile_end(zzz_ctx* ctx, int cycles); // ... and their mean over the cycles that ran (zzz_mg_info)
+int mg_level0_products(const zzz_ctx* ctx);
+double mg_level0_bound(const zzz_ctx* ctx);
+void mg_destroy(zzz_ctx* ctx);
+// zzz_cg.hip: the spectrum bound of D^-1 A as ZZZ_PC_CHEBYSHEV_JACOBI takes it (cached per mat_version); leaves ctx->dinv = 1 / diag(A)
+int chebyshev_bound(zzz_ctx* ctx, const zzz_solver_opts* o, double* hi);
+int cg_solve_mg(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm);
 
 // comm
 int comm_allreduce_sum(zzz_ctx* ctx, double* dev, int n);

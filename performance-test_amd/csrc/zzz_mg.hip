@@ -1,0 +1,812 @@
+// ZZZ_PC_MG: geometric multigrid preconditioner for the P1 cube problems (PCSetUp / PCApply of PETSc's PCMG behind
+// solver.set_from_options(), src/poisson_problem.cpp:169; the reference's README.md:59-146 recommends a multigrid
+// preconditioner for every configuration).
+//
+// Level 0 is the caller's context.  Level l+1 is the SAME problem re-discretised on max(2, (n+1)/2) cells per axis -- a
+// child context fed by zzz_cube_generate, patterned by zzz_csr_pattern_build and assembled by zzz_assemble_matrix, on
+// the caller's stream; its product is launch_spmv in whatever stream form its matrix gets.  The levels are not nested
+// when n is odd.  What is new here: the grid transfer (closed form, no P stored), the Chebyshev-Jacobi smoother from a
+// nonzero start, the dense coarsest solve, the V-cycle.  Nothing in the cycle synchronises with the host, and every kernel
+// of it returns at once when the solve's stop flag is set.
+//
+// Transfer, for fine vertex (i_x, i_y, i_z) and axis a (nf / nc: fine / coarse cells of that axis):
+//   c_a = min(i_a nc_a / nf_a, nc_a - 1) in 64-bit integers;  f_a = double(i_a nc_a - c_a nf_a) / double(nf_a);
+//   axes sorted by descending f, ties to the lower axis: (a1, a2, a3);
+//   weights 1 - f_a1, f_a1 - f_a2, f_a2 - f_a3, f_a3 on the coarse vertices c, c + e_a1, c + e_a1 + e_a2, c + e_a1 + e_a2 + e_a3
+// -- the Kuhn simplex of the coarse cube that holds the fine vertex (host/cube_layout.h cuts every cube along the same
+// diagonal), i.e. the coarse P1 function evaluated there: exact for linear functions, the nested interpolation when
+// nf = 2 nc.  c_a and f_a depend on (a, i_a) alone: three small tables per level pair, computed on the host in the
+// integers above, so the kernels divide nothing.  P~ = F_f P F_c with F zeroing the constrained dofs.
+#include "zzz_cg.h"
+
+#include <algorithm>
+#include <array>
+#include <chrono>
+#include <cmath>
+#include <memory>
+
+namespace zzz
+{
+// one level pair: vertices per axis, table offsets of the axes (fine tables: c and f per fine index; coarse tables: the
+// range of fine indices whose simplex can touch a coarse index)
+struct MgGeom
+{
+  int32_t pf[3], pc[3]; // vertices per axis, fine / coarse
+  int32_t of[3], oc[3]; // where axis a starts in the fine / coarse tables
+  int32_t bs;
+  int64_t nfv, ncv; // vertices
+};
+
+struct MgSimplex
+{
+  int32_t j[4]; // coarse vertices
+  double w[4];
+};
+
+// (values and axes travel through the three compare-exchanges in registers: no indexed private array, no scratch)
+__device__ inline MgSimplex mg_simplex(const MgGeom& G, const int32_t* __restrict__ tc, const double* __restrict__ tf, int ix,
+                                       int iy, int iz)
+{
+  const int cx = tc[G.of[0] + ix], cy = tc[G.of[1] + iy], cz = tc[G.of[2] + iz];
+  double v0 = tf[G.of[0] + ix], v1 = tf[G.of[1] + iy], v2 = tf[G.of[2] + iz];
+  const int sx = 1, sy = G.pc[0], sz = G.pc[0] * G.pc[1];
+  int s0 = sx, s1 = sy, s2 = sz;
+  // descending, ties to the lower axis: strict comparisons of neighbours keep equal values in axis order
+  if (v1 > v0)
+  {
+    const double t = v0; v0 = v1; v1 = t;
+    const int u = s0; s0 = s1; s1 = u;
+  }
+  if (v2 > v1)
+  {
+    const double t = v1; v1 = v2; v2 = t;
+    const int u = s1; s1 = s2; s2 = u;
+  }
+  if (v1 > v0)
+  {
+    const double t = v0; v0 = v1; v1 = t;
+    const int u = s0; s0 = s1; s1 = u;
+  }
+  MgSimplex S;
+  S.j[0] = (cz * G.pc[1] + cy) * G.pc[0] + cx;
+  S.j[1] = S.j[0] + s0;
+  S.j[2] = S.j[1] + s1;
+  S.j[3] = S.j[2] + s2;
+  S.w[0] = 1.0 - v0;
+  S.w[1] = v0 - v1;
+  S.w[2] = v1 - v2;
+  S.w[3] = v2;
+  return S;
+}
+
+// x_f (+)= P~ e_c: a thread per fine vertex, four gathers per component, summed in the simplex's order
+__global__ __launch_bounds__(VB) void k_mg_prolong(const int* __restrict__ stop, MgGeom G, const int32_t* __restrict__ tc,
+                                                   const double* __restrict__ tf, const uint8_t* __restrict__ bcf,
+                                                   const uint8_t* __restrict__ bcc, const double* __restrict__ ec,
+                                                   double* __restrict__ xf, int accumulate)
+{
+  if (stop && *stop)
+    return;
+  for (int64_t v = blockIdx.x * (int64_t)VB + threadIdx.x; v < G.nfv; v += (int64_t)gridDim.x * VB)
+  {
+    const int ix = (int)(v % G.pf[0]), iy = (int)((v / G.pf[0]) % G.pf[1]), iz = (int)(v / ((int64_t)G.pf[0] * G.pf[1]));
+    const MgSimplex S = mg_simplex(G, tc, tf, ix, iy, iz);
+    for (int k = 0; k < G.bs; ++k)
+    {
+      const int64_t i = v * G.bs + k;
+      double e[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+      {
+        const int64_t j = (int64_t)S.j[q] * G.bs + k;
+        e[q] = bcc[j] ? 0.0 : ec[j];
+      }
+      double s = S.w[0] * e[0];
+      s += S.w[1] * e[1];
+      s += S.w[2] * e[2];
+      s += S.w[3] * e[3];
+      if (bcf[i])
+        s = 0.0;
+      xf[i] = accumulate ? xf[i] + s : s;
+    }
+  }
+}
+
+// r_c = P~^T r_f in gather form: a thread per coarse vertex walks the fine vertices whose simplex can hold it, in
+// ascending (i_z, i_y, i_x) -- no atomics, the same bits in every run.  sub != null: r_f = b - sub, the residual formed
+// on the way in (b - A x with sub = A x), which saves the pass that would store it.
+template <int BS>
+__global__ __launch_bounds__(VB) void k_mg_restrict(const int* __restrict__ stop, MgGeom G, const int32_t* __restrict__ tc,
+                                                    const double* __restrict__ tf, const int32_t* __restrict__ rng,
+                                                    const uint8_t* __restrict__ bcf, const uint8_t* __restrict__ bcc,
+                                                    const double* __restrict__ rf, const double* __restrict__ sub,
+                                                    double* __restrict__ rc)
+{
+  if (stop && *stop)
+    return;
+  for (int64_t c = blockIdx.x * (int64_t)VB + threadIdx.x; c < G.ncv; c += (int64_t)gridDim.x * VB)
+  {
+    const int Cx = (int)(c % G.pc[0]), Cy = (int)((c / G.pc[0]) % G.pc[1]), Cz = (int)(c / ((int64_t)G.pc[0] * G.pc[1]));
+    const int x0 = rng[2 * (G.oc[0] + Cx)], x1 = rng[2 * (G.oc[0] + Cx) + 1];
+    const int y0 = rng[2 * (G.oc[1] + Cy)], y1 = rng[2 * (G.oc[1] + Cy) + 1];
+    const int z0 = rng[2 * (G.oc[2] + Cz)], z1 = rng[2 * (G.oc[2] + Cz) + 1];
+    double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0;
+    for (int iz = z0; iz <= z1; ++iz)
+      for (int iy = y0; iy <= y1; ++iy)
+        for (int ix = x0; ix <= x1; ++ix)
+        {
+          const MgSimplex S = mg_simplex(G, tc, tf, ix, iy, iz);
+          // the four vertices of a simplex are distinct: at most one of them is this thread's
+          double w;
+          if (S.j[0] == (int32_t)c)
+            w = S.w[0];
+          else if (S.j[1] == (int32_t)c)
+            w = S.w[1];
+          else if (S.j[2] == (int32_t)c)
+            w = S.w[2];
+          else if (S.j[3] == (int32_t)c)
+            w = S.w[3];
+          else
+            continue;
+          const int64_t i = (((int64_t)iz * G.pf[1] + iy) * G.pf[0] + ix) * BS;
+          {
+            double v = sub ? rf[i] - sub[i] : rf[i];
+            if (bcf[i])
+              v = 0.0;
+            acc0 += w * v;
+          }
+          if (BS == 3)
+          {
+            double v = sub ? rf[i + 1] - sub[i + 1] : rf[i + 1];
+            if (bcf[i + 1])
+              v = 0.0;
+            acc1 += w * v;
+            v = sub ? rf[i + 2] - sub[i + 2] : rf[i + 2];
+            if (bcf[i + 2])
+              v = 0.0;
+            acc2 += w * v;
+          }
+        }
+    const int64_t o = c * BS;
+    rc[o] = bcc[o] ? 0.0 : acc0;
+    if (BS == 3)
+    {
+      rc[o + 1] = bcc[o + 1] ? 0.0 : acc1;
+      rc[o + 2] = bcc[o + 2] ? 0.0 : acc2;
+    }
+  }
+}
+
+// First term of the Chebyshev-Jacobi smoother: g = D^-1 (b - t), d = g / theta, x = (x +) d.  t == null: the start from
+// zero, whose residual is b and costs no product (k_cheb_init's form); t = A x: the start from x (the post-smoother).
+__global__ __launch_bounds__(VB) void k_mg_first(const int* __restrict__ stop, const double* __restrict__ b,
+                                                 const double* __restrict__ t, const double* __restrict__ dinv, double theta,
+                                                 double* __restrict__ gv, double* __restrict__ d, double* __restrict__ x, int64_t n)
+{
+  if (stop && *stop)
+    return;
+  for (int64_t i = blockIdx.x * (int64_t)VB + threadIdx.x; i < n; i += (int64_t)gridDim.x * VB)
+  {
+    const double gi = t ? dinv[i] * (b[i] - t[i]) : dinv[i] * b[i];
+    const double di = gi / theta;
+    gv[i] = gi;
+    d[i] = di;
+    x[i] = t ? x[i] + di : di;
+  }
+}
+// A further term, t = A d given (k_cheb_step's arithmetic): g -= D^-1 t; d = c1 d + c2 g; x += d
+__global__ __launch_bounds__(VB) void k_mg_term(const int* __restrict__ stop, const double* __restrict__ t,
+                                                const double* __restrict__ dinv, double c1, double c2, double* __restrict__ gv,
+                                                double* __restrict__ d, double* __restrict__ x, int64_t n)
+{
+  if (stop && *stop)
+    return;
+  for (int64_t i = blockIdx.x * (int64_t)VB + threadIdx.x; i < n; i += (int64_t)gridDim.x * VB)
+  {
+    const double gi = -1.0 * (dinv[i] * t[i]) + gv[i];
+    const double dn = c1 * d[i] + c2 * gi;
+    gv[i] = gi;
+    d[i] = dn;
+    x[i] = x[i] + dn;
+  }
+}
+// The coarsest level: x = A^-1 b with the dense inverse, a wavefront per row; lane l sums columns l, l + 64, ... in
+// ascending order and the 64 sums meet in the shuffle tree -- one fixed order.
+__global__ __launch_bounds__(VB) void k_mg_dense(const int* __restrict__ stop, const double* __restrict__ ainv,
+                                                 const double* __restrict__ b, double* __restrict__ x, int n)
+{
+  if (stop && *stop)
+    return;
+  const int row = blockIdx.x * (VB / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= n)
+    return;
+  const double* __restrict__ a = ainv + (size_t)row * n;
+  double s = 0.0;
+  for (int j = lane; j < n; j += 64)
+    s += a[j] * b[j];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1)
+    s += __shfl_down(s, o, 64);
+  if (lane == 0)
+    x[row] = s;
+}
+
+struct MgLevel
+{
+  zzz_ctx* ctx = nullptr; // level 0: the caller's; else owned
+  int64_t n[3] = {0, 0, 0};
+  int64_t ndof = 0;
+  double hi = 0.0, lo = 0.0;
+  // transfer between this level and the next coarser one
+  MgGeom G{};
+  DevBuf<int32_t> tc, rng;
+  DevBuf<double> tf;
+};
+
+struct MgHier
+{
+  std::vector<std::unique_ptr<MgLevel>> lv;
+  DevBuf<double> ainv, tx_in, tx_out;
+  int degree = 2, est_its = 0, opt_levels = 0, opt_limit = 0;
+  double ratio = 10.0;
+  uint64_t feed_version = 0, mat_version = ~0ull;
+  int setups = 0;
+  double coarse_bytes = 0.0;
+  double setup_ms = 0.0; // host time of the last set-up that did work (it ends synchronised)
+  double cycle_ms = 0.0; // HIP-event time per V-cycle in the last solve with zzz_solver_opts.profile set
+  std::vector<hipEvent_t> ev;
+  int nev = 0;
+  bool ready = false;
+  ~MgHier()
+  {
+    for (hipEvent_t e : ev)
+      (void)hipEventDestroy(e);
+    for (size_t l = 1; l < lv.size(); ++l)
+      if (lv[l]->ctx)
+        zzz_ctx_destroy(lv[l]->ctx);
+  }
+};
+
+constexpr int MG_MAX_LEVELS = 12;
+constexpr int64_t MG_DENSE_MAX = 4096; // dofs the dense coarsest solve takes (128 MiB of inverse)
+
+void mg_destroy(zzz_ctx* ctx)
+{
+  delete ctx->mg;
+  ctx->mg = nullptr;
+}
+int mg_level0_products(const zzz_ctx* ctx)
+{
+  if (!ctx->mg || !ctx->mg->ready)
+    return 0;
+  return ctx->mg->lv.size() > 1 ? 2 * ctx->mg->degree : 0; // degree - 1 terms, the residual, A x of the post-smoother, degree - 1 terms
+}
+double mg_level0_bound(const zzz_ctx* ctx) { return ctx->mg && ctx->mg->ready ? ctx->mg->lv[0]->hi : 0.0; }
+
+int mg_check(zzz_ctx* ctx, const zzz_solver_opts* o)
+{
+  if (o->variant == ZZZ_CG_PIPE)
+    return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg: not with -ksp_type pipecg (ZZZ_CG_PIPE takes jacobi or none)");
+  if (o->variant != ZZZ_CG_PETSC)
+    return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg: KSPCG (ZZZ_CG_PETSC) only; src/cg.h (ZZZ_CG_CGH) has no preconditioner");
+  if (o->single_reduction)
+    return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg: not with -ksp_cg_single_reduction (the classical form of KSPCG only)");
+  if (o->op != ZZZ_OP_CSR)
+    return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg: needs the assembled operator, not ZZZ_OP_MATFREE");
+  if (ctx->comm)
+    return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg: a communicator is attached; multi-rank multigrid is not built");
+  if (!ctx->cube_feed)
+    return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg: the feed was uploaded (unstructured or host-built), not generated by "
+                                  "zzz_cube_generate: the library does not know the cube to coarsen");
+  if (ctx->cube_nparts != 1 || ctx->n_ghost != 0)
+    return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg: the cube was generated as part of %d: one part only", ctx->cube_nparts);
+  if (ctx->order != 1)
+    return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg: order %d; P1 only (p-coarsening for P2 / P3 is not built)", ctx->order);
+  if (ctx->renumbered)
+    return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg: the context keeps an internal dof order; the transfer needs the lexicographic one");
+  if (!ctx->have_matrix)
+    return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg: matrix not assembled");
+  if (o->pc_degree < 0 || o->pc_degree > 64 || o->pc_esteig_its > 64)
+    return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg: smoother degree 1..64, estimate <= 64 steps");
+  if (o->pc_mg_levels < 0 || o->pc_mg_coarse_eq_limit < 0)
+    return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg: negative pc_mg_levels or pc_mg_coarse_eq_limit");
+  return ZZZ_OK;
+}
+
+// the error of a child context becomes the caller's
+static int child_fail(zzz_ctx* ctx, zzz_ctx* c, int rc, int level, const char* what)
+{
+  return fail(ctx, rc, "-pc_type mg, level %d, %s: %s", level, what, c ? c->err.c_str() : zzz_last_error(nullptr));
+}
+
+static int mg_build_tables(zzz_ctx* ctx, MgLevel& F, const MgLevel& C)
+{
+  MgGeom& G = F.G;
+  G.bs = ctx->bs;
+  int32_t nf_tot = 0, nc_tot = 0;
+  for (int a = 0; a < 3; ++a)
+  {
+    G.pf[a] = (int32_t)F.n[a] + 1;
+    G.pc[a] = (int32_t)C.n[a] + 1;
+    G.of[a] = nf_tot;
+    G.oc[a] = nc_tot;
+    nf_tot += G.pf[a];
+    nc_tot += G.pc[a];
+  }
+  G.nfv = (int64_t)G.pf[0] * G.pf[1] * G.pf[2];
+  G.ncv = (int64_t)G.pc[0] * G.pc[1] * G.pc[2];
+  std::vector<int32_t> tc((size_t)nf_tot), rng(2 * (size_t)nc_tot);
+  std::vector<double> tf((size_t)nf_tot);
+  for (int a = 0; a < 3; ++a)
+  {
+    const int64_t nf = F.n[a], nc = C.n[a];
+    for (int64_t j = 0; j <= nc; ++j)
+    {
+      rng[2 * (size_t)(G.oc[a] + j)] = INT32_MAX;
+      rng[2 * (size_t)(G.oc[a] + j) + 1] = -1;
+    }
+    for (int64_t i = 0; i <= nf; ++i)
+    {
+      const int64_t c = std::min(i * nc / nf, nc - 1);
+      tc[(size_t)(G.of[a] + i)] = (int32_t)c;
+      tf[(size_t)(G.of[a] + i)] = (double)(i * nc - c * nf) / (double)nf;
+      // fine index i can reach coarse indices c and c + 1 of this axis
+      for (int64_t j = c; j <= c + 1; ++j)
+      {
+        int32_t* r = &rng[2 * (size_t)(G.oc[a] + j)];
+        r[0] = std::min(r[0], (int32_t)i);
+        r[1] = std::max(r[1], (int32_t)i);
+      }
+    }
+  }
+  hipStream_t s = ctx->stream;
+  ZZZ_HIP(ctx, F.tc.alloc(tc.size()));
+  ZZZ_HIP(ctx, F.tf.alloc(tf.size()));
+  ZZZ_HIP(ctx, F.rng.alloc(rng.size()));
+  ZZZ_HIP(ctx, hipMemcpyAsync(F.tc.p, tc.data(), tc.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  ZZZ_HIP(ctx, hipMemcpyAsync(F.tf.p, tf.data(), tf.size() * sizeof(double), hipMemcpyHostToDevice, s));
+  ZZZ_HIP(ctx, hipMemcpyAsync(F.rng.p, rng.data(), rng.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  ZZZ_HIP(ctx, hipStreamSynchronize(s)); // (the staging vectors are locals)
+  return ZZZ_OK;
+}
+
+// The coarsest matrix, downloaded once per set-up, factorised A = L L^T inside its band and inverted column by column
+// on the host (plain C++; the columns are independent, so the threads change no bit), symmetrised, uploaded.
+static int mg_dense_inverse(zzz_ctx* ctx, MgHier& H)
+{
+  zzz_ctx* c = H.lv.back()->ctx;
+  const int64_t n = c->n_owned * c->bs, nnz = c->nnz;
+  std::vector<rp_t> rp((size_t)n + 1);
+  std::vector<int32_t> cols((size_t)nnz);
+  std::vector<double> vals((size_t)nnz);
+  ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  ZZZ_HIP(ctx, hipMemcpy(rp.data(), c->rowptr.p, rp.size() * sizeof(rp_t), hipMemcpyDeviceToHost));
+  ZZZ_HIP(ctx, hipMemcpy(cols.data(), c->cols.p, cols.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+  ZZZ_HIP(ctx, hipMemcpy(vals.data(), c->vals.p, vals.size() * sizeof(double), hipMemcpyDeviceToHost));
+  std::vector<double> L((size_t)(n * n), 0.0), LT((size_t)(n * n), 0.0), X((size_t)(n * n), 0.0);
+  int64_t bw = 0;
+  for (int64_t i = 0; i < n; ++i)
+    for (rp_t k = rp[(size_t)i]; k < rp[(size_t)i + 1]; ++k)
+    {
+      const int64_t j = cols[(size_t)k];
+      if (j <= i && vals[(size_t)k] != 0.0)
+      {
+        L[(size_t)(i * n + j)] = vals[(size_t)k];
+        bw = std::max(bw, i - j);
+      }
+    }
+  for (int64_t i = 0; i < n; ++i)
+  {
+    const int64_t j0 = std::max<int64_t>(0, i - bw);
+    for (int64_t j = j0; j <= i; ++j)
+    {
+      double sum = L[(size_t)(i * n + j)];
+      const double *li = &L[(size_t)(i * n)], *lj = &L[(size_t)(j * n)];
+      for (int64_t k = std::max(j0, std::max<int64_t>(0, j - bw)); k < j; ++k)
+        sum -= li[k] * lj[k];
+      if (j == i)
+      {
+        if (!(sum > 0.0) || !std::isfinite(sum))
+          return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg: the coarsest matrix (%lld dofs) is not positive definite: pivot %g in row %lld",
+                      (long long)n, sum, (long long)i);
+        L[(size_t)(i * n + i)] = std::sqrt(sum);
+      }
+      else
+        L[(size_t)(i * n + j)] = sum / L[(size_t)(j * n + j)];
+    }
+  }
+  for (int64_t i = 0; i < n; ++i)
+    for (int64_t j = std::max<int64_t>(0, i - bw); j <= i; ++j)
+      LT[(size_t)(j * n + i)] = L[(size_t)(i * n + j)];
+#pragma omp parallel for schedule(dynamic, 8)
+  for (int64_t col = 0; col < n; ++col)
+  {
+    double* x = &X[(size_t)(col * n)]; // column `col` of the inverse, stored as a row
+    // L y = e_col (y is zero above col), then L^T x = y
+    for (int64_t i = col; i < n; ++i)
+    {
+      double sum = i == col ? 1.0 : 0.0;
+      const double* li = &L[(size_t)(i * n)];
+      for (int64_t k = std::max(col, i - bw); k < i; ++k)
+        sum -= li[k] * x[k];
+      x[i] = sum / li[i];
+    }
+    for (int64_t i = n - 1; i >= 0; --i)
+    {
+      double sum = x[i];
+      const double* lt = &LT[(size_t)(i * n)];
+      const int64_t k1 = std::min(n - 1, i + bw);
+      for (int64_t k = i + 1; k <= k1; ++k)
+        sum -= lt[k] * x[k];
+      x[i] = sum / lt[i];
+    }
+  }
+  for (int64_t i = 0; i < n; ++i)
+    for (int64_t j = 0; j < i; ++j)
+    {
+      const double v = 0.5 * (X[(size_t)(i * n + j)] + X[(size_t)(j * n + i)]);
+      X[(size_t)(i * n + j)] = X[(size_t)(j * n + i)] = v;
+    }
+  ZZZ_HIP(ctx, H.ainv.reserve((size_t)(n * n)));
+  ZZZ_HIP(ctx, hipMemcpy(H.ainv.p, X.data(), X.size() * sizeof(double), hipMemcpyHostToDevice));
+  return ZZZ_OK;
+}
+
+int mg_setup(zzz_ctx* ctx, const zzz_solver_opts* o)
+{
+  if (int rc = mg_check(ctx, o))
+    return rc;
+  const int form = ctx->cube_problem;
+  const int limit = o->pc_mg_coarse_eq_limit > 0 ? o->pc_mg_coarse_eq_limit : 1000;
+  int max_levels = o->pc_mg_levels > 0 ? std::min<int>(o->pc_mg_levels, MG_MAX_LEVELS) : MG_MAX_LEVELS;
+  const int degree = o->pc_degree > 0 ? o->pc_degree : 2;
+  const double ratio = o->pc_ratio > 1.0 ? o->pc_ratio : 10.0;
+  const int est_its = o->pc_esteig_its == 0 ? 10 : o->pc_esteig_its;
+  MgHier* H = ctx->mg;
+  bool built = false;
+  const auto t_begin = std::chrono::steady_clock::now();
+  if (!H || !H->ready || H->feed_version != ctx->feed_version || H->opt_levels != o->pc_mg_levels || H->opt_limit != limit)
+  {
+    // ---- the levels --------------------------------------------------------------------------
+    mg_destroy(ctx);
+    std::vector<std::array<int64_t, 3>> dims;
+    dims.push_back({ctx->cube_n[0], ctx->cube_n[1], ctx->cube_n[2]});
+    for (;;)
+    {
+      const auto& d = dims.back();
+      const int64_t dofs = (d[0] + 1) * (d[1] + 1) * (d[2] + 1) * ctx->bs;
+      if (dofs <= limit || (d[0] <= 2 && d[1] <= 2 && d[2] <= 2) || (int)dims.size() >= max_levels)
+        break;
+      dims.push_back({std::max<int64_t>(2, (d[0] + 1) / 2), std::max<int64_t>(2, (d[1] + 1) / 2), std::max<int64_t>(2, (d[2] + 1) / 2)});
+    }
+    {
+      const auto& d = dims.back();
+      const int64_t dofs = (d[0] + 1) * (d[1] + 1) * (d[2] + 1) * ctx->bs;
+      if (dofs > MG_DENSE_MAX)
+        return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg: the coarsest of %d levels has %lld dofs, the dense solve takes at most %lld: "
+                                      "allow more levels (pc_mg_levels) or a lower pc_mg_coarse_eq_limit",
+                    (int)dims.size(), (long long)dofs, (long long)MG_DENSE_MAX);
+    }
+    size_t free0 = 0, free1 = 0, total = 0;
+    ZZZ_HIP(ctx, hipMemGetInfo(&free0, &total));
+    H = ctx->mg = new MgHier();
+    for (size_t l = 0; l < dims.size(); ++l)
+    {
+      H->lv.emplace_back(new MgLevel());
+      MgLevel& L = *H->lv.back();
+      for (int a = 0; a < 3; ++a)
+        L.n[a] = dims[l][(size_t)a];
+      L.ndof = (L.n[0] + 1) * (L.n[1] + 1) * (L.n[2] + 1) * ctx->bs;
+      if (l == 0)
+      {
+        L.ctx = ctx;
+        continue;
+      }
+      zzz_ctx* c = nullptr;
+      if (int rc = zzz_ctx_create(ctx->device, &c))
+        return child_fail(ctx, nullptr, rc, (int)l, "context");
+      // every level enqueues on the caller's stream: the cycle needs no event between levels
+      (void)hipStreamDestroy(c->stream);
+      c->stream = ctx->stream;
+      c->stream_borrowed = true;
+      L.ctx = c;
+      if (int rc = zzz_cube_generate(c, form, 1, L.n[0], L.n[1], L.n[2], 1, 0, nullptr))
+        return child_fail(ctx, c, rc, (int)l, "generate");
+      if (int rc = zzz_csr_pattern_build(c))
+        return child_fail(ctx, c, rc, (int)l, "pattern");
+      if (c->renumbered || c->n_owned * c->bs != L.ndof)
+        return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg, level %d: the generated level is not in lexicographic order", (int)l);
+    }
+    for (size_t l = 0; l + 1 < H->lv.size(); ++l)
+      if (int rc = mg_build_tables(ctx, *H->lv[l], *H->lv[l + 1]))
+        return rc;
+    // smoother work vectors of every level that smooths (level 0's as ZZZ_PC_CHEBYSHEV_JACOBI allocates them)
+    for (size_t l = 0; l + 1 < H->lv.size(); ++l)
+    {
+      zzz_ctx* c = H->lv[l]->ctx;
+      ZZZ_HIP(ctx, c->cheb_d.alloc((size_t)c->nloc()));
+      ZZZ_HIP(ctx, c->cheb_d2.alloc((size_t)c->nloc()));
+      ZZZ_HIP(ctx, c->cheb_g.alloc((size_t)c->nloc()));
+    }
+    ZZZ_HIP(ctx, hipMemGetInfo(&free1, &total));
+    H->coarse_bytes = free0 > free1 ? (double)(free0 - free1) : 0.0; // (set-up scratch of the levels included; level 0's smoother vectors too)
+    H->feed_version = ctx->feed_version;
+    H->opt_levels = o->pc_mg_levels;
+    H->opt_limit = limit;
+    H->mat_version = ~0ull;
+    built = true;
+  }
+  const bool values = built || H->mat_version != ctx->mat_version;
+  if (values || H->degree != degree || H->ratio != ratio || H->est_its != est_its)
+  {
+    H->ready = false;
+    // ---- the levels' values: matrices, inverse diagonals, spectrum bounds, the coarsest inverse ----
+    zzz_solver_opts os = *o;
+    os.variant = ZZZ_CG_PETSC;
+    os.op = ZZZ_OP_CSR;
+    os.single_reduction = 0;
+    os.pc_esteig_its = o->pc_esteig_its;
+    for (size_t l = 0; l < H->lv.size(); ++l)
+    {
+      MgLevel& L = *H->lv[l];
+      zzz_ctx* c = L.ctx;
+      if (l > 0 && values)
+        if (int rc = zzz_assemble_matrix(c, form))
+          return child_fail(ctx, c, rc, (int)l, "assembly");
+      L.hi = L.lo = 0.0;
+      if (l + 1 == H->lv.size())
+        break;
+      if (int rc = chebyshev_bound(c, &os, &L.hi)) // (leaves c->dinv = 1 / diag(A))
+        return l > 0 ? child_fail(ctx, c, rc, (int)l, "spectrum bound") : rc;
+      L.lo = L.hi / ratio;
+    }
+    if (values)
+      if (int rc = mg_dense_inverse(ctx, *H))
+        return rc;
+    H->degree = degree;
+    H->ratio = ratio;
+    H->est_its = est_its;
+    H->mat_version = ctx->mat_version;
+    ++H->setups;
+    H->ready = true;
+    ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    H->setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  }
+  // the estimates above ran Jacobi solves through the levels' vectors: the inverse diagonals as the cycle reads them
+  for (size_t l = 0; l + 1 < H->lv.size(); ++l)
+  {
+    zzz_ctx* c = H->lv[l]->ctx;
+    cg_launch_extract_dinv(c, c->n_owned * c->bs, 1);
+  }
+  ZZZ_HIP(ctx, hipGetLastError());
+  return ZZZ_OK;
+}
+
+static int mg_restrict(zzz_ctx* ctx, const int* stop, MgLevel& F, MgLevel& C, const double* rf, const double* sub, double* rc)
+{
+  const int g = vgrid(F.G.ncv * 8); // (a thread walks up to 64 fine vertices: one coarse vertex per thread, no striding)
+  if (ctx->bs == 3)
+    hipLaunchKernelGGL(k_mg_restrict<3>, dim3(g), dim3(VB), 0, ctx->stream, stop, F.G, F.tc.p, F.tf.p, F.rng.p, F.ctx->bc.p, C.ctx->bc.p,
+                       rf, sub, rc);
+  else
+    hipLaunchKernelGGL(k_mg_restrict<1>, dim3(g), dim3(VB), 0, ctx->stream, stop, F.G, F.tc.p, F.tf.p, F.rng.p, F.ctx->bc.p, C.ctx->bc.p,
+                       rf, sub, rc);
+  return ZZZ_OK;
+}
+static void mg_prolong(zzz_ctx* ctx, const int* stop, MgLevel& F, MgLevel& C, const double* ec, double* xf, int accumulate)
+{
+  hipLaunchKernelGGL(k_mg_prolong, dim3(vgrid(F.G.nfv * 4)), dim3(VB), 0, ctx->stream, stop, F.G, F.tc.p, F.tf.p, F.ctx->bc.p, C.ctx->bc.p,
+                     ec, xf, accumulate);
+}
+
+// terms 2 .. degree of the smoother on level L (g, d and x hold the first)
+static int mg_terms(zzz_ctx* ctx, const int* stop, const MgHier& H, MgLevel& L, double* x)
+{
+  zzz_ctx* c = L.ctx;
+  const int64_t n = c->n_owned * c->bs;
+  const double theta = 0.5 * (L.hi + L.lo), delta = 0.5 * (L.hi - L.lo), sigma = theta / delta;
+  double rho = 1.0 / sigma;
+  for (int st = 1; st < H.degree; ++st)
+  {
+    const double rhon = 1.0 / (2.0 * sigma - rho);
+    const double c1 = rhon * rho, c2 = 2.0 * rhon / delta;
+    rho = rhon;
+    if (int rc = launch_spmv(c, c->cheb_d.p, c->cheb_d2.p, nullptr, nullptr))
+      return rc;
+    hipLaunchKernelGGL(k_mg_term, dim3(vgrid(n)), dim3(VB), 0, ctx->stream, stop, c->cheb_d2.p, c->dinv.p, c1, c2, c->cheb_g.p,
+                       c->cheb_d.p, x, n);
+  }
+  return ZZZ_OK;
+}
+
+static int mg_cycle_level(zzz_ctx* ctx, const int* stop, MgHier& H, size_t l, const double* b, double* x)
+{
+  MgLevel& L = *H.lv[l];
+  zzz_ctx* c = L.ctx;
+  const int64_t n = c->n_owned * c->bs;
+  hipStream_t s = ctx->stream;
+  if (l + 1 == H.lv.size())
+  {
+    hipLaunchKernelGGL(k_mg_dense, dim3((unsigned)((n + VB / 64 - 1) / (VB / 64))), dim3(VB), 0, s, stop, H.ainv.p, b, x, (int)n);
+    return ZZZ_OK;
+  }
+  MgLevel& C = *H.lv[l + 1];
+  const double theta = 0.5 * (L.hi + L.lo);
+  const int g = vgrid(n);
+  double* t = c->cheb_d2.p;
+  // pre-smoother from zero
+  hipLaunchKernelGGL(k_mg_first, dim3(g), dim3(VB), 0, s, stop, b, (const double*)nullptr, c->dinv.p, theta, c->cheb_g.p, c->cheb_d.p, x, n);
+  if (int rc = mg_terms(ctx, stop, H, L, x))
+    return rc;
+  // coarse correction: r_c = P~^T (b - A x), e_c = M_c r_c, x += P~ e_c
+  if (int rc = launch_spmv(c, x, t, nullptr, nullptr))
+    return rc;
+  if (int rc = mg_restrict(ctx, stop, L, C, b, t, C.ctx->b.p))
+    return rc;
+  if (int rc = mg_cycle_level(ctx, stop, H, l + 1, C.ctx->b.p, C.ctx->u.p))
+    return rc;
+  mg_prolong(ctx, stop, L, C, C.ctx->u.p, x, 1);
+  // post-smoother from x: the same polynomial
+  if (int rc = launch_spmv(c, x, t, nullptr, nullptr))
+    return rc;
+  hipLaunchKernelGGL(k_mg_first, dim3(g), dim3(VB), 0, s, stop, b, (const double*)t, c->dinv.p, theta, c->cheb_g.p, c->cheb_d.p, x, n);
+  return mg_terms(ctx, stop, H, L, x);
+}
+
+int mg_vcycle(zzz_ctx* ctx, const double* r, double* z, bool timed)
+{
+  if (!ctx->mg || !ctx->mg->ready)
+    return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg: no hierarchy (zzz_mg_setup)");
+  MgHier& H = *ctx->mg;
+  timed = timed && H.nev + 2 <= 64;
+  if (timed)
+  {
+    while ((int)H.ev.size() < H.nev + 2)
+    {
+      hipEvent_t e;
+      ZZZ_HIP(ctx, hipEventCreate(&e));
+      H.ev.push_back(e);
+    }
+    (void)hipEventRecord(H.ev[(size_t)H.nev], ctx->stream);
+  }
+  if (int rc = mg_cycle_level(ctx, reinterpret_cast<const int*>(ctx->state.p), H, 0, r, z))
+    return rc;
+  if (timed)
+  {
+    (void)hipEventRecord(H.ev[(size_t)H.nev + 1], ctx->stream);
+    H.nev += 2;
+  }
+  ZZZ_HIP(ctx, hipGetLastError());
+  return ZZZ_OK;
+}
+// the cycles of a profiled solve that ran before it stopped: the first `cycles` event pairs (the stream is idle)
+void mg_profile_begin(zzz_ctx* ctx)
+{
+  if (ctx->mg)
+    ctx->mg->nev = 0;
+}
+void mg_profile_end(zzz_ctx* ctx, int cycles)
+{
+  if (!ctx->mg)
+    return;
+  MgHier& H = *ctx->mg;
+  double sum = 0.0;
+  int n = 0;
+  for (int i = 0; i < std::min(cycles, H.nev / 2); ++i)
+  {
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, H.ev[2 * (size_t)i], H.ev[2 * (size_t)i + 1]) == hipSuccess)
+    {
+      sum += ms;
+      ++n;
+    }
+  }
+  H.cycle_ms = n ? sum / n : 0.0;
+  H.nev = 0;
+}
+ZZZ_PRELOAD_TU(mg)
+} // namespace zzz
+
+using namespace zzz;
+
+extern "C" {
+
+int zzz_mg_setup(zzz_ctx* ctx, const zzz_solver_opts* opts)
+{
+  if (!ctx)
+    return fail(nullptr, ZZZ_ERR_ARG, "NULL context");
+  ZZZ_HIP(ctx, hipSetDevice(ctx->device));
+  if (!opts)
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_mg_setup: NULL options");
+  zzz_solver_opts o = *opts;
+  o.pc = ZZZ_PC_MG;
+  if (int rc = mg_setup(ctx, &o))
+    return rc;
+  ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return ZZZ_OK;
+}
+
+int zzz_mg_info(zzz_ctx* ctx, int level, double out[8])
+{
+  if (!ctx)
+    return fail(nullptr, ZZZ_ERR_ARG, "NULL context");
+  if (!out)
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_mg_info: NULL output");
+  for (int i = 0; i < 8; ++i)
+    out[i] = 0.0;
+  const MgHier* H = ctx->mg;
+  if (!H || !H->ready)
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_mg_info: no hierarchy (zzz_mg_setup, or a solve with ZZZ_PC_MG)");
+  if (level < 0)
+  {
+    out[0] = (double)H->lv.size();
+    out[1] = (double)H->lv.back()->ndof;
+    out[2] = (double)H->setups;
+    out[3] = (double)mg_level0_products(ctx);
+    out[4] = H->coarse_bytes;
+    out[5] = H->cycle_ms;
+    out[6] = H->setup_ms;
+    return ZZZ_OK;
+  }
+  if ((size_t)level >= H->lv.size())
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_mg_info: level %d of %d", level, (int)H->lv.size());
+  const MgLevel& L = *H->lv[(size_t)level];
+  out[0] = (double)L.n[0];
+  out[1] = (double)L.n[1];
+  out[2] = (double)L.n[2];
+  out[3] = (double)L.ndof;
+  out[4] = (double)L.ctx->nnz;
+  const bool smooths = (size_t)level + 1 < H->lv.size();
+  out[5] = smooths ? L.hi : 0.0;
+  out[6] = smooths ? L.lo : 0.0;
+  out[7] = smooths ? (double)H->degree : 0.0;
+  return ZZZ_OK;
+}
+
+int zzz_mg_apply(zzz_ctx* ctx, const double* r, double* z)
+{
+  if (!ctx)
+    return fail(nullptr, ZZZ_ERR_ARG, "NULL context");
+  ZZZ_HIP(ctx, hipSetDevice(ctx->device));
+  if (!r || !z)
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_mg_apply: NULL vector");
+  if (!ctx->mg || !ctx->mg->ready)
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_mg_apply: no hierarchy (zzz_mg_setup, or a solve with ZZZ_PC_MG)");
+  const size_t n = (size_t)(ctx->n_owned * ctx->bs);
+  hipStream_t s = ctx->stream;
+  ZZZ_HIP(ctx, hipMemsetAsync(ctx->state.p, 0, sizeof(CgState), s)); // (a finished solve leaves its stop flag set)
+  ZZZ_HIP(ctx, hipMemcpyAsync(ctx->r.p, r, n * sizeof(double), hipMemcpyHostToDevice, s));
+  if (int rc = mg_vcycle(ctx, ctx->r.p, ctx->z.p, false))
+    return rc;
+  ZZZ_HIP(ctx, hipMemcpyAsync(z, ctx->z.p, n * sizeof(double), hipMemcpyDeviceToHost, s));
+  ZZZ_HIP(ctx, hipStreamSynchronize(s));
+  return ZZZ_OK;
+}
+
+int zzz_mg_transfer(zzz_ctx* ctx, int level, int dir, const double* in, double* out)
+{
+  if (!ctx)
+    return fail(nullptr, ZZZ_ERR_ARG, "NULL context");
+  ZZZ_HIP(ctx, hipSetDevice(ctx->device));
+  MgHier* H = ctx->mg;
+  if (!H || !H->ready)
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_mg_transfer: no hierarchy (zzz_mg_setup, or a solve with ZZZ_PC_MG)");
+  if (level < 0 || (size_t)level + 1 >= H->lv.size() || (dir != 0 && dir != 1) || !in || !out)
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_mg_transfer: level %d of %d (the coarsest has no transfer below it), dir %d, or NULL vector",
+                level, (int)H->lv.size(), dir);
+  MgLevel &F = *H->lv[(size_t)level], &C = *H->lv[(size_t)level + 1];
+  const size_t nin = (size_t)(dir == 0 ? C.ndof : F.ndof), nout = (size_t)(dir == 0 ? F.ndof : C.ndof);
+  hipStream_t s = ctx->stream;
+  ZZZ_HIP(ctx, H->tx_in.reserve(nin));
+  ZZZ_HIP(ctx, H->tx_out.reserve(nout));
+  ZZZ_HIP(ctx, hipMemcpyAsync(H->tx_in.p, in, nin * sizeof(double), hipMemcpyHostToDevice, s));
+  if (dir == 0)
+    mg_prolong(ctx, nullptr, F, C, H->tx_in.p, H->tx_out.p, 0);
+  else if (int rc = mg_restrict(ctx, nullptr, F, C, H->tx_in.p, nullptr, H->tx_out.p))
+    return rc;
+  ZZZ_HIP(ctx, hipGetLastError());
+  ZZZ_HIP(ctx, hipMemcpyAsync(out, H->tx_out.p, nout * sizeof(double), hipMemcpyDeviceToHost, s));
+  ZZZ_HIP(ctx, hipStreamSynchronize(s));
+  return ZZZ_OK;
+}
+}

@@ -12,6 +12,7 @@
 #include "../../include/zzz_host.h"
 
 #include <algorithm>
+#include <array>
 #include <barrier>
 #include <chrono>
 #include <cmath>
@@ -117,6 +118,10 @@ struct Options
   int pc_degree = 0;      // -pc_chebyshev_jacobi_degree (0: the library's default, 3)
   double pc_ratio = 0.0;  // -pc_chebyshev_jacobi_ratio  (0: the library's default, 60)
   int pc_esteig = 0;      // -pc_chebyshev_jacobi_esteig (0: the library's default, 10 Lanczos steps; < 0: Gershgorin alone)
+  int pc_mg_levels = 0;   // -pc_mg_levels (0: as many as -pc_mg_coarse_eq_limit asks for)
+  int pc_mg_coarse_eq_limit = 0; // -pc_mg_coarse_eq_limit (0: the library's default, 1000)
+  int mg_degree = 0;      // -mg_levels_ksp_max_it: the smoother's Chebyshev degree (0: the library's default, 2)
+  double mg_ratio = 0.0;  // -mg_levels_ksp_chebyshev_ratio: upper / lower bound of the smoothed spectrum (0: 10)
   bool ksp_view = false, log_view = false, options_left = false, ksp_monitor = false, ksp_cg_single_reduction = false;
   bool ksp_error_if_not_converged = false, ksp_converged_reason = false;
   std::vector<std::string> unused;
@@ -141,10 +146,13 @@ void usage()
                "  --allreduce arg (=peer)         peer (xGMI peer-memory mailboxes, else falls back) | comm\n"
                "  --operator arg (=assembled)     poisson: assembled (the AIJ matrix) | matfree (KSPCG on the matrix-free\n"
                "                                  operator, Jacobi from the element matrices' diagonals; no matrix)\n"
-               "PETSc-style solver options honoured: -ksp_type {cg,pipecg} -pc_type {jacobi,none,chebyshev_jacobi} -ksp_rtol -ksp_atol\n"
+               "PETSc-style solver options honoured: -ksp_type {cg,pipecg} -pc_type {jacobi,none,chebyshev_jacobi,mg} -ksp_rtol -ksp_atol\n"
                "  -ksp_divtol -pc_chebyshev_jacobi_degree (=3) -pc_chebyshev_jacobi_ratio (=60) -pc_chebyshev_jacobi_esteig (=10)\n"
                "  -ksp_max_it -ksp_norm_type {preconditioned,unpreconditioned,natural} -ksp_view -ksp_monitor\n"
                "  -ksp_cg_single_reduction -ksp_converged_reason -ksp_error_if_not_converged\n"
+               "  -pc_type mg: geometric multigrid, P1 cube meshes (--order 1, --mesh_type cube, --ngpus 1, poisson or elasticity,\n"
+               "  --operator assembled, -ksp_type cg without -ksp_cg_single_reduction): -pc_mg_levels (=0: by the limit)\n"
+               "  -pc_mg_coarse_eq_limit (=1000) -mg_levels_ksp_max_it (=2, Chebyshev degree) -mg_levels_ksp_chebyshev_ratio (=10)\n"
                "  -log_view -options_left\n"
             << std::endl;
 }
@@ -210,6 +218,14 @@ Options parse(int argc, char** argv)
         o.ksp_type = next();
       else if (key == "pc_type")
         o.pc_type = next();
+      else if (key == "pc_mg_levels")
+        o.pc_mg_levels = std::stoi(next());
+      else if (key == "pc_mg_coarse_eq_limit")
+        o.pc_mg_coarse_eq_limit = std::stoi(next());
+      else if (key == "mg_levels_ksp_max_it")
+        o.mg_degree = std::stoi(next());
+      else if (key == "mg_levels_ksp_chebyshev_ratio")
+        o.mg_ratio = std::stod(next());
       else if (key == "pc_chebyshev_jacobi_degree")
         o.pc_degree = std::stoi(next());
       else if (key == "pc_chebyshev_jacobi_ratio")
@@ -290,6 +306,7 @@ struct Shared
   std::vector<double> tcg;    // cgpoisson: time of the linalg::cg call alone (the Gdof/s line)
   std::vector<double> tplan;  // cgpoisson: set-up of the matrix-free plan (inside ZZZ Solve, outside the Gdof/s timer)
   std::vector<int> iters;
+  std::vector<std::array<double, 8>> mg_view; // -pc_type mg: the summary of zzz_mg_info, then one entry per level (rank 0)
   std::vector<double> norm, rnorm0, rnorm;
   std::vector<std::string> error;
   std::int64_t num_dofs = 0, num_cells = 0;
@@ -471,10 +488,13 @@ void run_rank(Shared& S, std::barrier<>& bar, int rank)
   else
   {
     so.variant = o.ksp_type == "pipecg" ? ZZZ_CG_PIPE : ZZZ_CG_PETSC;
-    so.pc = o.pc_type == "none" ? ZZZ_PC_NONE : o.pc_type == "chebyshev_jacobi" ? ZZZ_PC_CHEBYSHEV_JACOBI : ZZZ_PC_JACOBI;
-    so.pc_degree = o.pc_degree;
-    so.pc_ratio = o.pc_ratio;
+    so.pc = o.pc_type == "none" ? ZZZ_PC_NONE : o.pc_type == "chebyshev_jacobi" ? ZZZ_PC_CHEBYSHEV_JACOBI
+            : o.pc_type == "mg" ? ZZZ_PC_MG : ZZZ_PC_JACOBI;
+    so.pc_degree = o.pc_type == "mg" ? o.mg_degree : o.pc_degree;
+    so.pc_ratio = o.pc_type == "mg" ? o.mg_ratio : o.pc_ratio;
     so.pc_esteig_its = o.pc_esteig;
+    so.pc_mg_levels = o.pc_mg_levels;
+    so.pc_mg_coarse_eq_limit = o.pc_mg_coarse_eq_limit;
     so.norm = o.ksp_norm_type == "unpreconditioned" ? ZZZ_NORM_UNPRECONDITIONED
               : o.ksp_norm_type == "natural"        ? ZZZ_NORM_NATURAL
                                                     : ZZZ_NORM_PRECONDITIONED;
@@ -510,6 +530,17 @@ void run_rank(Shared& S, std::barrier<>& bar, int rank)
         S.tcg[rank] = tcg.stop();
         S.rnorm[rank] = rn[0];
         S.rnorm0[rank] = rn[1];
+        if (root && so.pc == ZZZ_PC_MG) // PCView: the hierarchy zzz_cg_solve set up above (PCSetUp runs inside ZZZ Solve, as in PETSc)
+        {
+          std::array<double, 8> v{};
+          ZCK(ctx, zzz_mg_info(ctx, -1, v.data()));
+          S.mg_view.push_back(v);
+          for (int l = 0; l < (int)S.mg_view[0][0]; ++l)
+          {
+            ZCK(ctx, zzz_mg_info(ctx, l, v.data()));
+            S.mg_view.push_back(v);
+          }
+        }
       }
       catch (const std::exception& e)
       {
@@ -639,9 +670,10 @@ void solve(int argc, char** argv)
   // src/main.cpp:131-141: "cube", anything else is the unstructured (spoke) mesh
   if (o.ksp_type != "cg" && o.ksp_type != "pipecg")
     throw std::runtime_error("-ksp_type " + o.ksp_type + ": only cg and pipecg are built");
-  if (o.pc_type != "jacobi" && o.pc_type != "none" && o.pc_type != "chebyshev_jacobi")
+  if (o.pc_type != "jacobi" && o.pc_type != "none" && o.pc_type != "chebyshev_jacobi" && o.pc_type != "mg")
     throw std::runtime_error("-pc_type " + o.pc_type +
-                             ": only jacobi, none and chebyshev_jacobi are built (hypre/gamg are out of scope)");
+                             ": only jacobi, none, chebyshev_jacobi and mg are built (hypre/gamg are out of scope: the "
+                             "multigrid preconditioner here is the geometric one, -pc_type mg)");
   if (o.order < 1 || o.order > 3)
     throw std::out_of_range("vector::_M_range_check: order must be 1..3"); // form_*.at(order - 1)
   const int ndev = zzz_device_count();
@@ -663,6 +695,21 @@ void solve(int argc, char** argv)
   if (o.ksp_type == "pipecg" && (o.op == "matfree" || o.pc_type == "chebyshev_jacobi" || o.ksp_cg_single_reduction))
     throw std::runtime_error("-ksp_type pipecg: the assembled operator with -pc_type jacobi or none, without "
                              "-ksp_cg_single_reduction");
+  if (o.pc_type == "mg")
+  {
+    // what ZZZ_PC_MG declines (include/zzz_abi.h), said here before any GPU work
+    const char* why = o.order != 1                          ? "--order 1 only (no p-coarsening for P2 / P3)"
+                      : o.mesh_type != "cube"               ? "--mesh_type cube only (the levels are coarser cubes)"
+                      : o.ngpus != 1                        ? "--ngpus 1 only (multi-rank multigrid is not built)"
+                      : o.problem_type == "cgpoisson"       ? "poisson or elasticity (cgpoisson runs linalg::cg, which has no preconditioner)"
+                      : o.op == "matfree"                   ? "--operator assembled only"
+                      : o.ksp_type != "cg"                  ? "-ksp_type cg only"
+                      : o.ksp_cg_single_reduction           ? "not with -ksp_cg_single_reduction"
+                      : o.pc_mg_levels < 0 || o.pc_mg_coarse_eq_limit < 0 || o.mg_degree < 0 ? "negative -pc_mg_* / -mg_levels_* value"
+                                                            : nullptr;
+    if (why)
+      throw std::runtime_error(std::string("-pc_type mg: ") + why);
+  }
   if (o.ngpus < 1 || (o.comm == "rccl" && o.ngpus > ndev))
     throw std::runtime_error("--ngpus " + std::to_string(o.ngpus) + " but " + std::to_string(ndev) + " GPU(s) visible");
 
@@ -768,6 +815,22 @@ void solve(int argc, char** argv)
               << (S.nranks > 1 ? (S.p2p_enabled[0] ? "  scalar all-reduces: peer-memory mailboxes; halo: peer-memory window where the plan fits\n"
                                                     : "  scalar all-reduces and halo: communicator\n")
                                : "");
+  if (o.ksp_view && !S.mg_view.empty())
+  {
+    const auto& m = S.mg_view[0];
+    std::cout << "  levels=" << (int)m[0] << ", V-cycle, " << (int)m[3] << " products per cycle on level 0, coarse levels hold "
+              << (long long)m[4] << " bytes\n";
+    for (size_t l = 1; l < S.mg_view.size(); ++l)
+    {
+      const auto& v = S.mg_view[l];
+      std::cout << "  level " << l - 1 << ": cells " << (long long)v[0] << "x" << (long long)v[1] << "x" << (long long)v[2] << ", dofs "
+                << (long long)v[3] << ", nonzeros " << (long long)v[4];
+      if (v[7] > 0)
+        std::cout << ", smoother chebyshev-jacobi degree " << (int)v[7] << " on [" << v[6] << ", " << v[5] << "]\n";
+      else
+        std::cout << ", dense direct solve\n";
+    }
+  }
   g_timers.list(); // dolfinx::list_timings, src/main.cpp:226
   // src/main.cpp:229-234
   std::cout << "*** Number of Krylov iterations: " << S.iters[0] << std::endl;

@@ -17,7 +17,7 @@ ROOT = os.path.dirname(PKG)
 FORM_POISSON, FORM_ELASTICITY = 0, 1
 COEFF_F, COEFF_G = 0, 1
 VEC_B, VEC_U = 0, 1
-PC_NONE, PC_JACOBI, PC_CHEBYSHEV_JACOBI = 0, 1, 2
+PC_NONE, PC_JACOBI, PC_CHEBYSHEV_JACOBI, PC_MG = 0, 1, 2, 3
 NORM_PRECONDITIONED, NORM_UNPRECONDITIONED, NORM_NATURAL = 0, 1, 2
 CG_PETSC, CG_CGH, CG_PIPE = 0, 1, 2
 OP_CSR, OP_MATFREE = 0, 1
@@ -31,6 +31,7 @@ ABI_SYMBOLS = [
     "zzz_vec_download", "zzz_vec_upload", "zzz_vec_norm", "zzz_spmv", "zzz_spmv_time", "zzz_spmv_values_info", "zzz_spmv_values_info2", "zzz_abi_version", "zzz_action", "zzz_matfree_setup", "zzz_matfree_info", "zzz_matfree_diagonal", "zzz_action_time", "zzz_near_nullspace_build", "zzz_near_nullspace_download", "zzz_cg_solve", "zzz_cg_history",
     "zzz_profile_get", "zzz_cg_info", "zzz_internal_order_download", "zzz_global_ids_upload", "zzz_global_ids_download", "zzz_ghost_layer_build", "zzz_local_sizes", "zzz_spmv_info", "zzz_comm_load", "zzz_comm_library_path", "zzz_comm_info", "zzz_comm_unique_id", "zzz_comm_init", "zzz_halo_upload", "zzz_local_group_create",
     "zzz_local_group_destroy", "zzz_local_group_abort", "zzz_comm_init_local", "zzz_comm_init_peer_only", "zzz_comm_p2p_export", "zzz_comm_p2p_attach", "zzz_comm_p2p_disable", "zzz_comm_p2p_enable", "zzz_comm_p2p_halo",
+    "zzz_mg_setup", "zzz_mg_info", "zzz_mg_apply", "zzz_mg_transfer",
 ]
 HOST_SYMBOLS = [
     "zzzh_num_pdofs", "zzzh_num_entities", "zzzh_mesh_size", "zzzh_count_suffix", "zzzh_part_create", "zzzh_part_create_native", "zzzh_part_create_spoke", "zzzh_part_create_spoke_part", "zzzh_spoke_size", "zzzh_part_destroy", "zzzh_part_global_verts",
@@ -47,7 +48,8 @@ class SolverOpts(C.Structure):
     _fields_ = [("variant", C.c_int32), ("pc", C.c_int32), ("norm", C.c_int32), ("op", C.c_int32),
                 ("max_it", C.c_int32), ("profile", C.c_int32), ("single_reduction", C.c_int32), ("error_if_not_converged", C.c_int32),
                 ("rtol", C.c_double), ("atol", C.c_double), ("dtol", C.c_double),
-                ("pc_degree", C.c_int32), ("pc_esteig_its", C.c_int32), ("pc_ratio", C.c_double)]
+                ("pc_degree", C.c_int32), ("pc_esteig_its", C.c_int32), ("pc_ratio", C.c_double),
+                ("pc_mg_levels", C.c_int32), ("pc_mg_coarse_eq_limit", C.c_int32)]
 
 
 class ZzzError(RuntimeError):
@@ -119,6 +121,10 @@ def hip():
         L.zzz_near_nullspace_download.argtypes = [C.c_void_p, C.c_int, _f64p]
         L.zzz_cg_solve.argtypes = [C.c_void_p, C.POINTER(SolverOpts), C.POINTER(C.c_int), C.POINTER(C.c_double)]
         L.zzz_cg_history.argtypes = [C.c_void_p, C.c_int, _f64p]
+        L.zzz_mg_setup.argtypes = [C.c_void_p, C.POINTER(SolverOpts)]
+        L.zzz_mg_info.argtypes = [C.c_void_p, C.c_int, _f64p]
+        L.zzz_mg_apply.argtypes = [C.c_void_p, _f64p, _f64p]
+        L.zzz_mg_transfer.argtypes = [C.c_void_p, C.c_int, C.c_int, _f64p, _f64p]
         L.zzz_profile_get.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
         L.zzz_spmv_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
         L.zzz_spmv_values_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
@@ -541,13 +547,47 @@ class Context:
 
     def cg_solve(self, variant=CG_PETSC, pc=PC_JACOBI, norm=NORM_PRECONDITIONED, op=OP_CSR, rtol=1e-8, atol=1e-50,
                  max_it=10000, profile=False, single_reduction=False, dtol=0.0, error_if_not_converged=False,
-                 pc_degree=0, pc_ratio=0.0, pc_esteig_its=0):
+                 pc_degree=0, pc_ratio=0.0, pc_esteig_its=0, pc_mg_levels=0, pc_mg_coarse_eq_limit=0):
         o = SolverOpts(variant, pc, norm, op, max_it, 1 if profile else 0, 1 if single_reduction else 0,
-                       1 if error_if_not_converged else 0, rtol, atol, dtol, pc_degree, pc_esteig_its, pc_ratio)
+                       1 if error_if_not_converged else 0, rtol, atol, dtol, pc_degree, pc_esteig_its, pc_ratio,
+                       pc_mg_levels, pc_mg_coarse_eq_limit)
         it = C.c_int()
         rn = (C.c_double * 2)()
         self._ck(self.L.zzz_cg_solve(self.h, C.byref(o), C.byref(it), rn))
         return it.value, rn[0], rn[1]
+
+    def mg_setup(self, pc_degree=0, pc_ratio=0.0, pc_esteig_its=0, pc_mg_levels=0, pc_mg_coarse_eq_limit=0):
+        """PCSetUp of ZZZ_PC_MG (optional: the first solve with pc=PC_MG does it)"""
+        o = SolverOpts(CG_PETSC, PC_MG, NORM_PRECONDITIONED, OP_CSR, 10000, 0, 0, 0, 1e-8, 1e-50, 0.0, pc_degree, pc_esteig_its,
+                       pc_ratio, pc_mg_levels, pc_mg_coarse_eq_limit)
+        self._ck(self.L.zzz_mg_setup(self.h, C.byref(o)))
+
+    def mg_info(self, level=-1):
+        """level < 0: dict(levels, coarse_dofs, setups, products_per_cycle, coarse_bytes, cycle_ms, setup_ms); else that level's
+        dict(cells=(nx, ny, nz), dofs, nnz, hi, lo, degree)"""
+        out = np.zeros(8)
+        self._ck(self.L.zzz_mg_info(self.h, level, out))
+        if level < 0:
+            return dict(levels=int(out[0]), coarse_dofs=int(out[1]), setups=int(out[2]), products_per_cycle=int(out[3]),
+                        coarse_bytes=int(out[4]), cycle_ms=float(out[5]), setup_ms=float(out[6]))
+        return dict(cells=(int(out[0]), int(out[1]), int(out[2])), dofs=int(out[3]), nnz=int(out[4]), hi=float(out[5]),
+                    lo=float(out[6]), degree=int(out[7]))
+
+    def mg_apply(self, r):
+        """z = M r: one V-cycle (zzz_mg_apply)"""
+        r = np.ascontiguousarray(r, np.float64)
+        z = np.zeros_like(r)
+        self._ck(self.L.zzz_mg_apply(self.h, r, z))
+        return z
+
+    def mg_transfer(self, level, direction, v):
+        """direction 0: P~ v (level + 1 -> level); 1: P~^T v"""
+        v = np.ascontiguousarray(v, np.float64)
+        a, b = self.mg_info(level)["dofs"], self.mg_info(level + 1)["dofs"]
+        assert v.shape[0] == (b if direction == 0 else a)
+        out = np.zeros(a if direction == 0 else b)
+        self._ck(self.L.zzz_mg_transfer(self.h, level, direction, v, out))
+        return out
 
     def cg_history(self, n):
         out = np.zeros(n)
