@@ -102,7 +102,16 @@ enum
    * ZZZ_PC_CHEBYSHEV_JACOBI takes it (pc_esteig_its).  The hierarchy is built by the first solve (or zzz_mg_setup), kept
    * across solves, rebuilt when the feed changes, its values refreshed when the matrix values change.  After
    * zzz_csr_upload_values on the context the coarse levels STAY the re-discretised ones of the generated problem. */
-  ZZZ_PC_MG = 3
+  ZZZ_PC_MG = 3,
+  /* p-multigrid for orders 2 and 3 on the same cubes: ZZZ_PC_MG's scope with the order test dropped.  Level 0 is the
+   * caller's Pk matrix, smoothed like every other level; level 1 is the SAME cube re-discretised at order 1 (generated,
+   * patterned and assembled like ZZZ_PC_MG's coarse levels); levels 2.. are ZZZ_PC_MG's hierarchy of that P1 problem, to
+   * which pc_mg_coarse_eq_limit and the dense-size rule apply.  pc_mg_levels counts all levels, so at order > 1 a value
+   * of 1 is declined.  Transfer between levels 0 and 1: the P1 function evaluated at the Pk dof points of the Kuhn cube
+   * (1 term at a vertex, 2 on an edge with the weights of the Pk nodes, 3 x 1/3 at a face centroid), closed form, no P
+   * stored, fixed summation order, constrained dofs zeroed on both sides.  At order 1 it builds exactly ZZZ_PC_MG's
+   * hierarchy.  ZZZ_PC_MG itself keeps declining orders 2 and 3. */
+  ZZZ_PC_PMG = 4
 };
 enum
 {
@@ -403,14 +412,16 @@ int zzz_spmv_info(zzz_ctx* ctx, int64_t info[8]);
  * info[7] still counts the blocks); info[2] is then the bytes of THAT form. */
 int zzz_spmv_values_info(zzz_ctx* ctx, int64_t info[4]);
 int zzz_spmv_values_info2(zzz_ctx* ctx, int n, int64_t* info);
-/* ---- geometric multigrid (ZZZ_PC_MG) ----------------------------------------------------------
+/* ---- geometric multigrid (ZZZ_PC_MG, ZZZ_PC_PMG) ----------------------------------------------
  * PCSetUp(PCMG) behind solver.set_from_options() (src/poisson_problem.cpp:169; README.md:59-146): builds the hierarchy
  * for these options, or refreshes its values after an assembly.  Optional: zzz_cg_solve(pc = ZZZ_PC_MG) does it on first
- * use, inside the solve, where PETSc's PCSetUp runs.  Overwrites the context's Krylov work vectors (not b, not u). */
+ * use, inside the solve, where PETSc's PCSetUp runs.  Overwrites the context's Krylov work vectors (not b, not u).
+ * opts->pc == ZZZ_PC_PMG builds the p-multigrid hierarchy; any other value is read as ZZZ_PC_MG. */
 int zzz_mg_setup(zzz_ctx* ctx, const zzz_solver_opts* opts);
 /* PCView of that hierarchy.  level < 0: out = {levels, scalar dofs of the coarsest, set-ups done so far (builds and
  * refreshes), products per V-cycle on level 0, device bytes of the coarse levels, HIP-event ms per V-cycle in the last solve
- * with opts.profile != 0 (else 0), host ms of the last set-up that did work (it ends synchronised), 0}.  Otherwise that level's
+ * with opts.profile != 0 (else 0), host ms of the last set-up that did work (it ends synchronised), levels of order > 1
+ * (ZZZ_PC_PMG at order 2 or 3: 1, they come first; else 0)}.  Otherwise that level's
  * {nx, ny, nz, scalar dofs, nonzeros, hi, lo, smoother degree} (hi = lo = degree = 0 on the coarsest: a dense solve). */
 int zzz_mg_info(zzz_ctx* ctx, int level, double out[8]);
 /* PCApply: z = M r, one V-cycle on host vectors of the owned size -- zzz_spmv's counterpart, for parity checks. */
@@ -421,7 +432,9 @@ int zzz_mg_apply(zzz_ctx* ctx, const double* r, double* z);
 int zzz_mg_transfer(zzz_ctx* ctx, int level, int dir, const double* in, double* out);
 
 /* Version of this header's ABI: bumped whenever an existing entry point changes what it reads or writes (7: zzz_cg_solve
- * reads the two pc_mg_* fields behind pc_ratio). */
+ * reads the two pc_mg_* fields behind pc_ratio).  ZZZ_PC_PMG did not bump it: a new enumerator changes no struct, no
+ * entry point and nothing that a caller built against the earlier header passes or receives -- such a caller never
+ * sends the value 4, and a library without it answers that value with ZZZ_ERR_ARG. */
 #define ZZZ_ABI_VERSION 7
 int zzz_abi_version(void);
 

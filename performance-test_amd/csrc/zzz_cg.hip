@@ -992,7 +992,7 @@ int cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
     return cg_solve_pipe(ctx, o, iters, rnorm); // zzz_cg_pipe.hip
   if (o->pc == ZZZ_PC_CHEBYSHEV_JACOBI && !o->single_reduction)
     return cg_solve_chebyshev(ctx, o, iters, rnorm);
-  if (o->pc == ZZZ_PC_MG)
+  if (o->pc == ZZZ_PC_MG || o->pc == ZZZ_PC_PMG)
     return cg_solve_mg(ctx, o, iters, rnorm);
   if (o->single_reduction)
     return cg_solve_single_reduction(ctx, o, iters, rnorm);
@@ -1865,7 +1865,7 @@ int chebyshev_bound(zzz_ctx* ctx, const zzz_solver_opts* o, double* hi)
   return ZZZ_OK;
 }
 
-// ---- KSPCG with the multigrid preconditioner (ZZZ_PC_MG, zzz_mg.hip) -------------------------------------------------
+// ---- KSPCG with the multigrid preconditioner (ZZZ_PC_MG / ZZZ_PC_PMG, zzz_mg.hip) -------------------------------------------------
 // cg_solve_chebyshev with "V-cycle, then k_dots_rz" in the polynomial's place: the scalar logic, history and reasons are
 // the classical loop's (k_update_p, k_update_xr).  An iteration is a few milliseconds of device work at the sizes that
 // matter and there are about ten of them, so the state is read back in EVERY iteration, behind k_update_p and ahead of

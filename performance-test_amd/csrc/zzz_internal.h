@@ -100,7 +100,7 @@ struct DevBuf
 };
 
 struct Comm; // zzz_comm.cpp
-struct MgHier; // zzz_mg.hip: the level hierarchy of ZZZ_PC_MG
+struct MgHier; // zzz_mg.hip: the level hierarchy of ZZZ_PC_MG and ZZZ_PC_PMG
 
 typedef int64_t rp_t; // row pointers of the CSR matrix of record
 
@@ -476,6 +476,7 @@ void preload_cubegen();
 void preload_matfree();
 void preload_mg();
 void preload_nullspace();
+void preload_pmg();
 void preload_pattern();
 void preload_renumber();
 void preload_sellp();
@@ -547,6 +548,12 @@ void mg_profile_end(zzz_ctx* ctx, int cycles); // ... and their mean over the cy
 int mg_level0_products(const zzz_ctx* ctx);
 double mg_level0_bound(const zzz_ctx* ctx);
 void mg_destroy(zzz_ctx* ctx);
+// zzz_pmg.hip: the transfer between the Pk (order 2, 3) and the P1 dofs of one generated n[0] x n[1] x n[2] cube, enqueued on
+// ctx->stream; bcf / bcc are the Dirichlet bytes of the two contexts, sub (may be null) is subtracted from rf on the way in
+int pmg_prolong(zzz_ctx* ctx, const int* stop, int order, int bs, const int64_t n[3], const uint8_t* bcf, const uint8_t* bcc,
+                const double* ec, double* xf, int accumulate);
+int pmg_restrict(zzz_ctx* ctx, const int* stop, int order, int bs, const int64_t n[3], const uint8_t* bcf, const uint8_t* bcc,
+                 const double* rf, const double* sub, double* rc);
 // zzz_cg.hip: the spectrum bound of D^-1 A as ZZZ_PC_CHEBYSHEV_JACOBI takes it (cached per mat_version); leaves ctx->dinv = 1 / diag(A)
 int chebyshev_bound(zzz_ctx* ctx, const zzz_solver_opts* o, double* hi);
 int cg_solve_mg(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm);

@@ -17,6 +17,11 @@
 // diagonal), i.e. the coarse P1 function evaluated there: exact for linear functions, the nested interpolation when
 // nf = 2 nc.  c_a and f_a depend on (a, i_a) alone: three small tables per level pair, computed on the host in the
 // integers above, so the kernels divide nothing.  P~ = F_f P F_c with F zeroing the constrained dofs.
+//
+// ZZZ_PC_PMG at order k = 2, 3 puts ONE level in front: level 0 is the caller's Pk matrix, level 1 the same cube at order 1
+// (a child context like the others), levels 2.. the hierarchy above of that P1 problem.  The pair (0, 1) is transferred by
+// zzz_pmg.hip; smoother, cycle, set-up caching, refresh, stop flag and profiling are the ones here.  At order 1
+// ZZZ_PC_PMG is ZZZ_PC_MG.
 #include "zzz_cg.h"
 
 #include <algorithm>
@@ -236,6 +241,7 @@ struct MgLevel
   zzz_ctx* ctx = nullptr; // level 0: the caller's; else owned
   int64_t n[3] = {0, 0, 0};
   int64_t ndof = 0;
+  int order = 1; // > 1: the Pk level of ZZZ_PC_PMG; the transfer to the next level is zzz_pmg.hip's, without tables
   double hi = 0.0, lo = 0.0;
   // transfer between this level and the next coarser one
   MgGeom G{};
@@ -285,38 +291,45 @@ double mg_level0_bound(const zzz_ctx* ctx) { return ctx->mg && ctx->mg->ready ? 
 
 int mg_check(zzz_ctx* ctx, const zzz_solver_opts* o)
 {
+  const bool pmg = o->pc == ZZZ_PC_PMG;
+  const char* tag = pmg ? "-pc_type pmg" : "-pc_type mg";
   if (o->variant == ZZZ_CG_PIPE)
-    return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg: not with -ksp_type pipecg (ZZZ_CG_PIPE takes jacobi or none)");
+    return fail(ctx, ZZZ_ERR_ARG, "%s: not with -ksp_type pipecg (ZZZ_CG_PIPE takes jacobi or none)", tag);
   if (o->variant != ZZZ_CG_PETSC)
-    return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg: KSPCG (ZZZ_CG_PETSC) only; src/cg.h (ZZZ_CG_CGH) has no preconditioner");
+    return fail(ctx, ZZZ_ERR_ARG, "%s: KSPCG (ZZZ_CG_PETSC) only; src/cg.h (ZZZ_CG_CGH) has no preconditioner", tag);
   if (o->single_reduction)
-    return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg: not with -ksp_cg_single_reduction (the classical form of KSPCG only)");
+    return fail(ctx, ZZZ_ERR_ARG, "%s: not with -ksp_cg_single_reduction (the classical form of KSPCG only)", tag);
   if (o->op != ZZZ_OP_CSR)
-    return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg: needs the assembled operator, not ZZZ_OP_MATFREE");
+    return fail(ctx, ZZZ_ERR_ARG, "%s: needs the assembled operator, not ZZZ_OP_MATFREE", tag);
   if (ctx->comm)
-    return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg: a communicator is attached; multi-rank multigrid is not built");
+    return fail(ctx, ZZZ_ERR_ARG, "%s: a communicator is attached; multi-rank multigrid is not built", tag);
   if (!ctx->cube_feed)
-    return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg: the feed was uploaded (unstructured or host-built), not generated by "
-                                  "zzz_cube_generate: the library does not know the cube to coarsen");
+    return fail(ctx, ZZZ_ERR_ARG, "%s: the feed was uploaded (unstructured or host-built), not generated by "
+                                  "zzz_cube_generate: the library does not know the cube to coarsen", tag);
   if (ctx->cube_nparts != 1 || ctx->n_ghost != 0)
-    return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg: the cube was generated as part of %d: one part only", ctx->cube_nparts);
-  if (ctx->order != 1)
-    return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg: order %d; P1 only (p-coarsening for P2 / P3 is not built)", ctx->order);
+    return fail(ctx, ZZZ_ERR_ARG, "%s: the cube was generated as part of %d: one part only", tag, ctx->cube_nparts);
+  if (ctx->order != 1 && !pmg)
+    return fail(ctx, ZZZ_ERR_ARG, "%s: order %d; P1 only (p-coarsening for P2 / P3 is -pc_type pmg, ZZZ_PC_PMG)", tag, ctx->order);
+  if (ctx->order < 1 || ctx->order > 3)
+    return fail(ctx, ZZZ_ERR_ARG, "%s: order %d", tag, ctx->order);
+  if (ctx->order > 1 && o->pc_mg_levels == 1)
+    return fail(ctx, ZZZ_ERR_ARG, "%s: pc_mg_levels = 1 at order %d: the P%d level and the P1 level of the same cube make two at least",
+                tag, ctx->order, ctx->order);
   if (ctx->renumbered)
-    return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg: the context keeps an internal dof order; the transfer needs the lexicographic one");
+    return fail(ctx, ZZZ_ERR_ARG, "%s: the context keeps an internal dof order; the transfer needs the lexicographic one", tag);
   if (!ctx->have_matrix)
-    return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg: matrix not assembled");
+    return fail(ctx, ZZZ_ERR_ARG, "%s: matrix not assembled", tag);
   if (o->pc_degree < 0 || o->pc_degree > 64 || o->pc_esteig_its > 64)
-    return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg: smoother degree 1..64, estimate <= 64 steps");
+    return fail(ctx, ZZZ_ERR_ARG, "%s: smoother degree 1..64, estimate <= 64 steps", tag);
   if (o->pc_mg_levels < 0 || o->pc_mg_coarse_eq_limit < 0)
-    return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg: negative pc_mg_levels or pc_mg_coarse_eq_limit");
+    return fail(ctx, ZZZ_ERR_ARG, "%s: negative pc_mg_levels or pc_mg_coarse_eq_limit", tag);
   return ZZZ_OK;
 }
 
 // the error of a child context becomes the caller's
 static int child_fail(zzz_ctx* ctx, zzz_ctx* c, int rc, int level, const char* what)
 {
-  return fail(ctx, rc, "-pc_type mg, level %d, %s: %s", level, what, c ? c->err.c_str() : zzz_last_error(nullptr));
+  return fail(ctx, rc, "-pc_type mg / pmg, level %d, %s: %s", level, what, c ? c->err.c_str() : zzz_last_error(nullptr));
 }
 
 static int mg_build_tables(zzz_ctx* ctx, MgLevel& F, const MgLevel& C)
@@ -469,7 +482,11 @@ int mg_setup(zzz_ctx* ctx, const zzz_solver_opts* o)
   {
     // ---- the levels --------------------------------------------------------------------------
     mg_destroy(ctx);
+    // ZZZ_PC_PMG at order > 1: the Pk level first, then the P1 levels from the same cube on; pc_mg_levels counts all
+    const size_t high = ctx->order > 1 ? 1 : 0;
     std::vector<std::array<int64_t, 3>> dims;
+    if (high)
+      dims.push_back({ctx->cube_n[0], ctx->cube_n[1], ctx->cube_n[2]});
     dims.push_back({ctx->cube_n[0], ctx->cube_n[1], ctx->cube_n[2]});
     for (;;)
     {
@@ -500,6 +517,8 @@ int mg_setup(zzz_ctx* ctx, const zzz_solver_opts* o)
       if (l == 0)
       {
         L.ctx = ctx;
+        L.order = ctx->order;
+        L.ndof = ctx->n_owned * ctx->bs;
         continue;
       }
       zzz_ctx* c = nullptr;
@@ -515,9 +534,9 @@ int mg_setup(zzz_ctx* ctx, const zzz_solver_opts* o)
       if (int rc = zzz_csr_pattern_build(c))
         return child_fail(ctx, c, rc, (int)l, "pattern");
       if (c->renumbered || c->n_owned * c->bs != L.ndof)
-        return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg, level %d: the generated level is not in lexicographic order", (int)l);
+        return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg / pmg, level %d: the generated level is not in lexicographic order", (int)l);
     }
-    for (size_t l = 0; l + 1 < H->lv.size(); ++l)
+    for (size_t l = high; l + 1 < H->lv.size(); ++l)
       if (int rc = mg_build_tables(ctx, *H->lv[l], *H->lv[l + 1]))
         return rc;
     // smoother work vectors of every level that smooths (level 0's as ZZZ_PC_CHEBYSHEV_JACOBI allocates them)
@@ -584,6 +603,8 @@ int mg_setup(zzz_ctx* ctx, const zzz_solver_opts* o)
 
 static int mg_restrict(zzz_ctx* ctx, const int* stop, MgLevel& F, MgLevel& C, const double* rf, const double* sub, double* rc)
 {
+  if (F.order > 1)
+    return pmg_restrict(ctx, stop, F.order, ctx->bs, F.n, F.ctx->bc.p, C.ctx->bc.p, rf, sub, rc);
   const int g = vgrid(F.G.ncv * 8); // (a thread walks up to 64 fine vertices: one coarse vertex per thread, no striding)
   if (ctx->bs == 3)
     hipLaunchKernelGGL(k_mg_restrict<3>, dim3(g), dim3(VB), 0, ctx->stream, stop, F.G, F.tc.p, F.tf.p, F.rng.p, F.ctx->bc.p, C.ctx->bc.p,
@@ -593,10 +614,13 @@ static int mg_restrict(zzz_ctx* ctx, const int* stop, MgLevel& F, MgLevel& C, co
                        rf, sub, rc);
   return ZZZ_OK;
 }
-static void mg_prolong(zzz_ctx* ctx, const int* stop, MgLevel& F, MgLevel& C, const double* ec, double* xf, int accumulate)
+static int mg_prolong(zzz_ctx* ctx, const int* stop, MgLevel& F, MgLevel& C, const double* ec, double* xf, int accumulate)
 {
+  if (F.order > 1)
+    return pmg_prolong(ctx, stop, F.order, ctx->bs, F.n, F.ctx->bc.p, C.ctx->bc.p, ec, xf, accumulate);
   hipLaunchKernelGGL(k_mg_prolong, dim3(vgrid(F.G.nfv * 4)), dim3(VB), 0, ctx->stream, stop, F.G, F.tc.p, F.tf.p, F.ctx->bc.p, C.ctx->bc.p,
                      ec, xf, accumulate);
+  return ZZZ_OK;
 }
 
 // terms 2 .. degree of the smoother on level L (g, d and x hold the first)
@@ -645,7 +669,8 @@ static int mg_cycle_level(zzz_ctx* ctx, const int* stop, MgHier& H, size_t l, co
     return rc;
   if (int rc = mg_cycle_level(ctx, stop, H, l + 1, C.ctx->b.p, C.ctx->u.p))
     return rc;
-  mg_prolong(ctx, stop, L, C, C.ctx->u.p, x, 1);
+  if (int rc = mg_prolong(ctx, stop, L, C, C.ctx->u.p, x, 1))
+    return rc;
   // post-smoother from x: the same polynomial
   if (int rc = launch_spmv(c, x, t, nullptr, nullptr))
     return rc;
@@ -719,7 +744,7 @@ int zzz_mg_setup(zzz_ctx* ctx, const zzz_solver_opts* opts)
   if (!opts)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_mg_setup: NULL options");
   zzz_solver_opts o = *opts;
-  o.pc = ZZZ_PC_MG;
+  o.pc = opts->pc == ZZZ_PC_PMG ? ZZZ_PC_PMG : ZZZ_PC_MG;
   if (int rc = mg_setup(ctx, &o))
     return rc;
   ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -746,6 +771,7 @@ int zzz_mg_info(zzz_ctx* ctx, int level, double out[8])
     out[4] = H->coarse_bytes;
     out[5] = H->cycle_ms;
     out[6] = H->setup_ms;
+    out[7] = H->lv[0]->order > 1 ? 1.0 : 0.0;
     return ZZZ_OK;
   }
   if ((size_t)level >= H->lv.size())
@@ -801,7 +827,10 @@ int zzz_mg_transfer(zzz_ctx* ctx, int level, int dir, const double* in, double* 
   ZZZ_HIP(ctx, H->tx_out.reserve(nout));
   ZZZ_HIP(ctx, hipMemcpyAsync(H->tx_in.p, in, nin * sizeof(double), hipMemcpyHostToDevice, s));
   if (dir == 0)
-    mg_prolong(ctx, nullptr, F, C, H->tx_in.p, H->tx_out.p, 0);
+  {
+    if (int rc = mg_prolong(ctx, nullptr, F, C, H->tx_in.p, H->tx_out.p, 0))
+      return rc;
+  }
   else if (int rc = mg_restrict(ctx, nullptr, F, C, H->tx_in.p, nullptr, H->tx_out.p))
     return rc;
   ZZZ_HIP(ctx, hipGetLastError());

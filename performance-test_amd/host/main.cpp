@@ -146,13 +146,15 @@ void usage()
                "  --allreduce arg (=peer)         peer (xGMI peer-memory mailboxes, else falls back) | comm\n"
                "  --operator arg (=assembled)     poisson: assembled (the AIJ matrix) | matfree (KSPCG on the matrix-free\n"
                "                                  operator, Jacobi from the element matrices' diagonals; no matrix)\n"
-               "PETSc-style solver options honoured: -ksp_type {cg,pipecg} -pc_type {jacobi,none,chebyshev_jacobi,mg} -ksp_rtol -ksp_atol\n"
+               "PETSc-style solver options honoured: -ksp_type {cg,pipecg} -pc_type {jacobi,none,chebyshev_jacobi,mg,pmg} -ksp_rtol -ksp_atol\n"
                "  -ksp_divtol -pc_chebyshev_jacobi_degree (=3) -pc_chebyshev_jacobi_ratio (=60) -pc_chebyshev_jacobi_esteig (=10)\n"
                "  -ksp_max_it -ksp_norm_type {preconditioned,unpreconditioned,natural} -ksp_view -ksp_monitor\n"
                "  -ksp_cg_single_reduction -ksp_converged_reason -ksp_error_if_not_converged\n"
                "  -pc_type mg: geometric multigrid, P1 cube meshes (--order 1, --mesh_type cube, --ngpus 1, poisson or elasticity,\n"
                "  --operator assembled, -ksp_type cg without -ksp_cg_single_reduction): -pc_mg_levels (=0: by the limit)\n"
                "  -pc_mg_coarse_eq_limit (=1000) -mg_levels_ksp_max_it (=2, Chebyshev degree) -mg_levels_ksp_chebyshev_ratio (=10)\n"
+               "  -pc_type pmg: p-multigrid, the same with --order 1..3: the Pk matrix is level 0, the P1 problem on the same cube\n"
+               "  level 1, -pc_type mg's hierarchy below it; the same -pc_mg_* / -mg_levels_* options (-pc_mg_levels counts all levels)\n"
                "  -log_view -options_left\n"
             << std::endl;
 }
@@ -489,9 +491,10 @@ void run_rank(Shared& S, std::barrier<>& bar, int rank)
   {
     so.variant = o.ksp_type == "pipecg" ? ZZZ_CG_PIPE : ZZZ_CG_PETSC;
     so.pc = o.pc_type == "none" ? ZZZ_PC_NONE : o.pc_type == "chebyshev_jacobi" ? ZZZ_PC_CHEBYSHEV_JACOBI
-            : o.pc_type == "mg" ? ZZZ_PC_MG : ZZZ_PC_JACOBI;
-    so.pc_degree = o.pc_type == "mg" ? o.mg_degree : o.pc_degree;
-    so.pc_ratio = o.pc_type == "mg" ? o.mg_ratio : o.pc_ratio;
+            : o.pc_type == "mg" ? ZZZ_PC_MG : o.pc_type == "pmg" ? ZZZ_PC_PMG : ZZZ_PC_JACOBI;
+    const bool multigrid = o.pc_type == "mg" || o.pc_type == "pmg";
+    so.pc_degree = multigrid ? o.mg_degree : o.pc_degree;
+    so.pc_ratio = multigrid ? o.mg_ratio : o.pc_ratio;
     so.pc_esteig_its = o.pc_esteig;
     so.pc_mg_levels = o.pc_mg_levels;
     so.pc_mg_coarse_eq_limit = o.pc_mg_coarse_eq_limit;
@@ -530,7 +533,7 @@ void run_rank(Shared& S, std::barrier<>& bar, int rank)
         S.tcg[rank] = tcg.stop();
         S.rnorm[rank] = rn[0];
         S.rnorm0[rank] = rn[1];
-        if (root && so.pc == ZZZ_PC_MG) // PCView: the hierarchy zzz_cg_solve set up above (PCSetUp runs inside ZZZ Solve, as in PETSc)
+        if (root && (so.pc == ZZZ_PC_MG || so.pc == ZZZ_PC_PMG)) // PCView: the hierarchy zzz_cg_solve set up above (PCSetUp runs inside ZZZ Solve, as in PETSc)
         {
           std::array<double, 8> v{};
           ZCK(ctx, zzz_mg_info(ctx, -1, v.data()));
@@ -670,10 +673,10 @@ void solve(int argc, char** argv)
   // src/main.cpp:131-141: "cube", anything else is the unstructured (spoke) mesh
   if (o.ksp_type != "cg" && o.ksp_type != "pipecg")
     throw std::runtime_error("-ksp_type " + o.ksp_type + ": only cg and pipecg are built");
-  if (o.pc_type != "jacobi" && o.pc_type != "none" && o.pc_type != "chebyshev_jacobi" && o.pc_type != "mg")
+  if (o.pc_type != "jacobi" && o.pc_type != "none" && o.pc_type != "chebyshev_jacobi" && o.pc_type != "mg" && o.pc_type != "pmg")
     throw std::runtime_error("-pc_type " + o.pc_type +
-                             ": only jacobi, none, chebyshev_jacobi and mg are built (hypre/gamg are out of scope: the "
-                             "multigrid preconditioner here is the geometric one, -pc_type mg)");
+                             ": only jacobi, none, chebyshev_jacobi, mg and pmg are built (hypre/gamg are out of scope: the "
+                             "multigrid preconditioner here is the geometric one, -pc_type mg, or -pc_type pmg for --order 2 / 3)");
   if (o.order < 1 || o.order > 3)
     throw std::out_of_range("vector::_M_range_check: order must be 1..3"); // form_*.at(order - 1)
   const int ndev = zzz_device_count();
@@ -695,10 +698,10 @@ void solve(int argc, char** argv)
   if (o.ksp_type == "pipecg" && (o.op == "matfree" || o.pc_type == "chebyshev_jacobi" || o.ksp_cg_single_reduction))
     throw std::runtime_error("-ksp_type pipecg: the assembled operator with -pc_type jacobi or none, without "
                              "-ksp_cg_single_reduction");
-  if (o.pc_type == "mg")
+  if (o.pc_type == "mg" || o.pc_type == "pmg")
   {
-    // what ZZZ_PC_MG declines (include/zzz_abi.h), said here before any GPU work
-    const char* why = o.order != 1                          ? "--order 1 only (no p-coarsening for P2 / P3)"
+    // what ZZZ_PC_MG / ZZZ_PC_PMG decline (include/zzz_abi.h), said here before any GPU work
+    const char* why = o.order != 1 && o.pc_type == "mg"     ? "--order 1 only (p-coarsening for P2 / P3 is -pc_type pmg)"
                       : o.mesh_type != "cube"               ? "--mesh_type cube only (the levels are coarser cubes)"
                       : o.ngpus != 1                        ? "--ngpus 1 only (multi-rank multigrid is not built)"
                       : o.problem_type == "cgpoisson"       ? "poisson or elasticity (cgpoisson runs linalg::cg, which has no preconditioner)"
@@ -706,9 +709,10 @@ void solve(int argc, char** argv)
                       : o.ksp_type != "cg"                  ? "-ksp_type cg only"
                       : o.ksp_cg_single_reduction           ? "not with -ksp_cg_single_reduction"
                       : o.pc_mg_levels < 0 || o.pc_mg_coarse_eq_limit < 0 || o.mg_degree < 0 ? "negative -pc_mg_* / -mg_levels_* value"
+                      : o.order > 1 && o.pc_mg_levels == 1  ? "-pc_mg_levels 1 with --order 2 / 3 (the Pk and the P1 level make two)"
                                                             : nullptr;
     if (why)
-      throw std::runtime_error(std::string("-pc_type mg: ") + why);
+      throw std::runtime_error("-pc_type " + o.pc_type + ": " + why);
   }
   if (o.ngpus < 1 || (o.comm == "rccl" && o.ngpus > ndev))
     throw std::runtime_error("--ngpus " + std::to_string(o.ngpus) + " but " + std::to_string(ndev) + " GPU(s) visible");
@@ -823,7 +827,8 @@ void solve(int argc, char** argv)
     for (size_t l = 1; l < S.mg_view.size(); ++l)
     {
       const auto& v = S.mg_view[l];
-      std::cout << "  level " << l - 1 << ": cells " << (long long)v[0] << "x" << (long long)v[1] << "x" << (long long)v[2] << ", dofs "
+      std::cout << "  level " << l - 1 << ": cells " << (long long)v[0] << "x" << (long long)v[1] << "x" << (long long)v[2] << ", order "
+                << (l - 1 < (size_t)m[7] ? o.order : 1) << ", dofs "
                 << (long long)v[3] << ", nonzeros " << (long long)v[4];
       if (v[7] > 0)
         std::cout << ", smoother chebyshev-jacobi degree " << (int)v[7] << " on [" << v[6] << ", " << v[5] << "]\n";

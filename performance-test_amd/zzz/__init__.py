@@ -17,7 +17,7 @@ ROOT = os.path.dirname(PKG)
 FORM_POISSON, FORM_ELASTICITY = 0, 1
 COEFF_F, COEFF_G = 0, 1
 VEC_B, VEC_U = 0, 1
-PC_NONE, PC_JACOBI, PC_CHEBYSHEV_JACOBI, PC_MG = 0, 1, 2, 3
+PC_NONE, PC_JACOBI, PC_CHEBYSHEV_JACOBI, PC_MG, PC_PMG = 0, 1, 2, 3, 4
 NORM_PRECONDITIONED, NORM_UNPRECONDITIONED, NORM_NATURAL = 0, 1, 2
 CG_PETSC, CG_CGH, CG_PIPE = 0, 1, 2
 OP_CSR, OP_MATFREE = 0, 1
@@ -556,20 +556,21 @@ class Context:
         self._ck(self.L.zzz_cg_solve(self.h, C.byref(o), C.byref(it), rn))
         return it.value, rn[0], rn[1]
 
-    def mg_setup(self, pc_degree=0, pc_ratio=0.0, pc_esteig_its=0, pc_mg_levels=0, pc_mg_coarse_eq_limit=0):
-        """PCSetUp of ZZZ_PC_MG (optional: the first solve with pc=PC_MG does it)"""
-        o = SolverOpts(CG_PETSC, PC_MG, NORM_PRECONDITIONED, OP_CSR, 10000, 0, 0, 0, 1e-8, 1e-50, 0.0, pc_degree, pc_esteig_its,
+    def mg_setup(self, pc_degree=0, pc_ratio=0.0, pc_esteig_its=0, pc_mg_levels=0, pc_mg_coarse_eq_limit=0, pc=PC_MG):
+        """PCSetUp of ZZZ_PC_MG or ZZZ_PC_PMG (optional: the first solve with that pc does it)"""
+        o = SolverOpts(CG_PETSC, pc, NORM_PRECONDITIONED, OP_CSR, 10000, 0, 0, 0, 1e-8, 1e-50, 0.0, pc_degree, pc_esteig_its,
                        pc_ratio, pc_mg_levels, pc_mg_coarse_eq_limit)
         self._ck(self.L.zzz_mg_setup(self.h, C.byref(o)))
 
     def mg_info(self, level=-1):
-        """level < 0: dict(levels, coarse_dofs, setups, products_per_cycle, coarse_bytes, cycle_ms, setup_ms); else that level's
+        """level < 0: dict(levels, coarse_dofs, setups, products_per_cycle, coarse_bytes, cycle_ms, setup_ms, high_order_levels);
+        else that level's
         dict(cells=(nx, ny, nz), dofs, nnz, hi, lo, degree)"""
         out = np.zeros(8)
         self._ck(self.L.zzz_mg_info(self.h, level, out))
         if level < 0:
             return dict(levels=int(out[0]), coarse_dofs=int(out[1]), setups=int(out[2]), products_per_cycle=int(out[3]),
-                        coarse_bytes=int(out[4]), cycle_ms=float(out[5]), setup_ms=float(out[6]))
+                        coarse_bytes=int(out[4]), cycle_ms=float(out[5]), setup_ms=float(out[6]), high_order_levels=int(out[7]))
         return dict(cells=(int(out[0]), int(out[1]), int(out[2])), dofs=int(out[3]), nnz=int(out[4]), hi=float(out[5]),
                     lo=float(out[6]), degree=int(out[7]))
 
