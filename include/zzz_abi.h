@@ -203,9 +203,38 @@ int zzz_mesh_upload(zzz_ctx* ctx, int64_t nverts, const double* x, int64_t ncell
  * src/poisson_problem.cpp:117); bs 1 or 3; cell_dofs: ncells*nd block indices, nd = 4/10/20. */
 int zzz_dofmap_upload(zzz_ctx* ctx, int order, int bs, const int32_t* cell_dofs, int64_t n_owned, int64_t n_ghost);
 
-/* fem::DirichletBC(u0 == 0, bdofs) (src/poisson_problem.cpp:53-77, src/elasticity_problem.cpp:119-145).
- * bc_dofs: local SCALAR dof indices, owned and ghost, all with value 0. */
+/* fem::DirichletBC(u0, bdofs) (src/poisson_problem.cpp:53-77, src/elasticity_problem.cpp:119-145): WHERE u is prescribed.
+ * bc_dofs: local SCALAR dof indices, owned and ghost; their value is 0 (the reference's u0) until zzz_bc_values_upload
+ * says otherwise, and again after every call of this function. */
 int zzz_bc_upload(zzz_ctx* ctx, int64_t nbc, const int32_t* bc_dofs);
+
+/* The values of u0 behind that DirichletBC when u0 is not the zero function: bc->dof_values() / u0->x() of
+ * fem::DirichletBC(u0, bdofs) (src/poisson_problem.cpp:53-77, src/elasticity_problem.cpp:119-145), consumed by
+ * fem::apply_lifting(b, {a}, {{bc}}, {}, 1.0) and bc->set(b) (src/poisson_problem.cpp:152-155,
+ * src/elasticity_problem.cpp:226-229; the action form: src/cgpoisson_problem.cpp:159-168).
+ * values: (n_owned + n_ghost) * bs doubles in the caller's local numbering, owned then ghosts, exactly like
+ * zzz_coeff_upload: u0 at every dof.  Only the entries at constrained dofs are ever read; whatever the others hold
+ * (NaN and Inf included) reaches no result.  NULL clears the values: the context is back to u0 == 0.
+ * With values present zzz_assemble_vector produces DOLFINx's vector (scale 1, x0 empty):
+ *   owned unconstrained row i:  b_i = L_i - sum_cells sum_{j constrained in the cell} A_e[i][j] g_j,  A_e the
+ *                               UNCONSTRAINED element matrix of form a (the entries zzz_assemble_matrix computes before it
+ *                               zeroes rows and columns); cells in the row's adjacency order, local columns ascending,
+ *                               no atomics: the same bits in every run;
+ *   owned constrained row i:    b_i = g_i.
+ * Without values (or after NULL) zzz_assemble_vector enqueues exactly the kernels it did before this entry point existed.
+ * Owned rows are complete locally (ghost-cell layer) and g at ghost dofs comes from this upload: no communication.
+ * Solves: with ZZZ_OP_CSR nothing changes -- constrained rows are identity rows, u[bc] converges to g.  ZZZ_OP_MATFREE
+ * zeroes the constrained ROWS of its action (src/cgpoisson_problem.cpp:207), so with values present it iterates on b
+ * with the constrained entries taken as zero (what scale 0.0 leaves there, :168; the caller's b is not modified);
+ * ZZZ_CG_PETSC then writes u[bc] = g when it ends, ZZZ_CG_CGH leaves u[bc] at the caller's initial guess like src/cg.h.
+ * Call order: after zzz_dofmap_upload / zzz_cube_generate AND after a Dirichlet set exists (zzz_bc_upload /
+ * zzz_cube_generate); ZZZ_ERR_ARG with the reason otherwise.  Whatever changes the dof layout or the Dirichlet set CLEARS
+ * the values: zzz_dofmap_upload, zzz_bc_upload, zzz_cube_generate, zzz_ghost_layer_build -- after the last of these the
+ * caller uploads values again, for the sizes zzz_local_sizes then reports (the new ghosts included).
+ * The matrix does not depend on u0: an upload leaves a multigrid hierarchy, the Chebyshev bound and the product's forms
+ * valid.  Time-dependent values: upload again and call zzz_assemble_vector again.  One Dirichlet object; apply_lifting's
+ * x0 and scale arguments are not served. */
+int zzz_bc_values_upload(zzz_ctx* ctx, const double* values);
 
 /* Exterior facets integrated by the `ds` term of L (src/Poisson.py:32); what
  * create_entities(2)/create_connectivity(2,3) prepare (src/main.cpp:147-148).
@@ -254,7 +283,8 @@ int zzz_assemble_matrix(zzz_ctx* ctx, int form);
 
 /* The `ZZZ Assemble vector` block (src/poisson_problem.cpp:146-157,
  * src/elasticity_problem.cpp:220-231): cell (+ exterior-facet) integrals of L into b,
- * apply_lifting (identically zero: u0 == 0), bc->set. */
+ * apply_lifting (identically zero while u0 == 0; a pass of its own over the rows next to the Dirichlet set once
+ * zzz_bc_values_upload has given u0 values), bc->set. */
 int zzz_assemble_vector(zzz_ctx* ctx, int form);
 
 /* ---- vectors --------------------------------------------------------------------------- */
@@ -434,7 +464,8 @@ int zzz_mg_transfer(zzz_ctx* ctx, int level, int dir, const double* in, double* 
 /* Version of this header's ABI: bumped whenever an existing entry point changes what it reads or writes (7: zzz_cg_solve
  * reads the two pc_mg_* fields behind pc_ratio).  ZZZ_PC_PMG did not bump it: a new enumerator changes no struct, no
  * entry point and nothing that a caller built against the earlier header passes or receives -- such a caller never
- * sends the value 4, and a library without it answers that value with ZZZ_ERR_ARG. */
+ * sends the value 4, and a library without it answers that value with ZZZ_ERR_ARG.  Nor did zzz_bc_values_upload: a new
+ * entry point, no struct and no existing entry changed. */
 #define ZZZ_ABI_VERSION 7
 int zzz_abi_version(void);
 

@@ -64,6 +64,12 @@ int alloc_problem_vectors(zzz_ctx* ctx)
   ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return ZZZ_OK;
 }
+// A new dof layout or Dirichlet set: the values of u0 uploaded for the old one mean nothing, and the lifting rows change
+void bc_values_clear(zzz_ctx* ctx)
+{
+  ctx->have_bc_val = false;
+  ++ctx->bc_version;
+}
 } // namespace zzz
 
 using namespace zzz;
@@ -336,6 +342,7 @@ int zzz_dofmap_upload(zzz_ctx* ctx, int order, int bs, const int32_t* cell_dofs,
   if (rc)
     return rc;
   ctx->have_bc = false;
+  bc_values_clear(ctx);
   ctx->have_coeff[0] = ctx->have_coeff[1] = false;
   ctx->have_pattern = ctx->have_matrix = false;
   ctx->xq_valid = false;
@@ -356,6 +363,7 @@ int zzz_bc_upload(zzz_ctx* ctx, int64_t nbc, const int32_t* bc_dofs)
   ZZZ_ENTER(ctx);
   ctx->cube_feed = false; // (ZZZ_PC_MG needs a generated cube)
   ++ctx->feed_version;
+  bc_values_clear(ctx); // (a new Dirichlet set, or a failed attempt at one: u0 == 0 until values are uploaded for it)
   if (ctx->order == 0)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_bc_upload before zzz_dofmap_upload");
   if (nbc < 0 || (nbc > 0 && !bc_dofs))
@@ -374,6 +382,36 @@ int zzz_bc_upload(zzz_ctx* ctx, int64_t nbc, const int32_t* bc_dofs)
   ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
   ctx->have_bc = true;
   ctx->mf.valid = ctx->mf.failed = false; // the plan of the matrix-free action carries the Dirichlet markers of its dof lists
+  return ZZZ_OK;
+}
+
+int zzz_bc_values_upload(zzz_ctx* ctx, const double* values)
+{
+  ZZZ_ENTER(ctx);
+  if (!values) // u0 == 0 again: the vector assembly enqueues what it did before any upload
+  {
+    ctx->have_bc_val = false;
+    return ZZZ_OK;
+  }
+  if (ctx->order == 0)
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_bc_values_upload before zzz_dofmap_upload / zzz_cube_generate: the values are indexed by local dof");
+  if (!ctx->have_bc)
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_bc_values_upload before a Dirichlet set exists (zzz_bc_upload / zzz_cube_generate): the values "
+                                  "belong to its dofs");
+  const size_t nv = (size_t)ctx->nloc();
+  std::vector<double> tmp;
+  if (ctx->renumbered)
+  {
+    tmp.resize(nv);
+    to_internal(ctx, values, tmp.data(), false);
+    values = tmp.data();
+  }
+  ZZZ_HIP(ctx, ctx->bc_val.alloc(nv));
+  ZZZ_HIP(ctx, hipMemcpyAsync(ctx->bc_val.p, values, nv * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  // (no feed_version, cube_feed or mat_version here: the matrix does not depend on u0, so a multigrid hierarchy, the
+  // Chebyshev bound and the product's special forms stay what they are)
+  ctx->have_bc_val = true;
   return ZZZ_OK;
 }
 
@@ -727,7 +765,9 @@ int zzz_assemble_vector(zzz_ctx* ctx, int form)
     return fail(ctx, ZZZ_ERR_ARG, "unknown form %d", form);
   if (!ctx->have_coeff[ZZZ_COEFF_F] || (form == ZZZ_FORM_POISSON && !ctx->have_coeff[ZZZ_COEFF_G]))
     return fail(ctx, ZZZ_ERR_ARG, "coefficient(s) of L not uploaded");
-  return launch_assemble_vector(ctx, form);
+  if (int rc = launch_assemble_vector(ctx, form))
+    return rc;
+  return ctx->have_bc_val ? launch_lift(ctx) : ZZZ_OK; // apply_lifting and bc->set with u0 != 0: a pass of its own
 }
 
 static zzz::DevBuf<double>* pick_vec(zzz_ctx* ctx, int which)

@@ -117,6 +117,66 @@ __device__ inline void p1_grads(const Geom& G, double g[4][3])
 
 __device__ inline double sel3(double a0, double a1, double a2, int c) { return c == 0 ? a0 : (c == 1 ? a1 : a2); }
 
+// ---- entries of the element matrices of form a, shared by the matrix kernels and the lifting pass (k_lift), so that
+// the two cannot drift apart.  Every helper is the expression the matrix kernels held inline: same operations, same order.
+constexpr double EL_E = 1.0e6, EL_NU = 0.3; // src/Elasticity.py:12-15
+constexpr double EL_MU = EL_E / (2.0 * (1.0 + EL_NU));
+constexpr double EL_LAMBDA = EL_E * EL_NU / ((1.0 + EL_NU) * (1.0 - 2.0 * EL_NU));
+
+// P1 elasticity, entry (row node i, component c; column node j, component d) of a cell of reference volume weight w:
+// mu (delta_cd g_i.g_j + d_d phi_i d_c phi_j) + lambda d_c phi_i d_d phi_j, with gg = g_i.g_j, gid = d_d phi_i,
+// gjc = d_c phi_j, gic = d_c phi_i, gjd = d_d phi_j
+__device__ inline double p1_elasticity_entry(double w, double gg, bool c_is_d, double gid, double gjc, double gic, double gjd)
+{
+  return w * (EL_MU * ((c_is_d ? gg : 0.0) + gid * gjc) + EL_LAMBDA * gic * gjd);
+}
+
+// Pk Poisson: |detJ| (K K^T) (six numbers: 00 11 22 01 02 12) contracted with the symmetrised reference tensors of the
+// pair (li, j); Tlj points at piece 0 of the pair, the pieces are NN apart
+template <int NN>
+__device__ inline double pk_poisson_entry(const double* GG, const double* Tlj)
+{
+  double val = 0.0;
+#pragma unroll
+  for (int t = 0; t < 6; ++t)
+    val += GG[t] * Tlj[t * NN];
+  return val;
+}
+
+// Pk elasticity: D[cc][d] = |detJ| sum_{al,be} K[al][cc] K[be][d] S^[al][be]_{li,j} = int d_cc phi_i d_d phi_j
+// (Kf: K[al][d] at Kf[3 al + d]; Tlj points at piece (0, 0) of the pair (li, j), the nine pieces are NN apart)
+template <int NN>
+__device__ inline void pk_grad_products(double adet, const double* Kf, const double* Tlj, double (&D)[3][3])
+{
+  double tmp[3][3];
+#pragma unroll
+  for (int al = 0; al < 3; ++al)
+#pragma unroll
+    for (int d = 0; d < 3; ++d)
+      tmp[al][d] = Tlj[(al * 3 + 0) * NN] * Kf[0 + d] + Tlj[(al * 3 + 1) * NN] * Kf[3 + d] + Tlj[(al * 3 + 2) * NN] * Kf[6 + d];
+#pragma unroll
+  for (int cc = 0; cc < 3; ++cc)
+#pragma unroll
+    for (int d = 0; d < 3; ++d)
+      D[cc][d] = adet * (Kf[0 + cc] * tmp[0][d] + Kf[3 + cc] * tmp[1][d] + Kf[6 + cc] * tmp[2][d]);
+}
+// ... and the entry (component c of the row, d of the column) of the pair from D and its trace
+__device__ inline double pk_elasticity_entry(const double (&D)[3][3], double tr, int c, int d)
+{
+  const double Dcd = sel3(D[0][d], D[1][d], D[2][d], c), Ddc = sel3(D[d][0], D[d][1], D[d][2], c);
+  return EL_MU * ((c == d ? tr : 0.0) + Ddc) + EL_LAMBDA * Dcd;
+}
+// |detJ| (K K^T): 00 11 22 01 02 12
+__device__ inline void pk_poisson_geom(const Geom& G, double (&GG)[6])
+{
+  GG[0] = G.adet * (G.K[0][0] * G.K[0][0] + G.K[0][1] * G.K[0][1] + G.K[0][2] * G.K[0][2]);
+  GG[1] = G.adet * (G.K[1][0] * G.K[1][0] + G.K[1][1] * G.K[1][1] + G.K[1][2] * G.K[1][2]);
+  GG[2] = G.adet * (G.K[2][0] * G.K[2][0] + G.K[2][1] * G.K[2][1] + G.K[2][2] * G.K[2][2]);
+  GG[3] = G.adet * (G.K[0][0] * G.K[1][0] + G.K[0][1] * G.K[1][1] + G.K[0][2] * G.K[1][2]);
+  GG[4] = G.adet * (G.K[0][0] * G.K[2][0] + G.K[0][1] * G.K[2][1] + G.K[0][2] * G.K[2][2]);
+  GG[5] = G.adet * (G.K[1][0] * G.K[2][0] + G.K[1][1] * G.K[2][1] + G.K[1][2] * G.K[2][2]);
+}
+
 __device__ inline int find_pos(const int32_t* __restrict__ c, int len, int32_t col)
 {
   int lo = 0, hi = len - 1;
@@ -280,9 +340,6 @@ __global__ __launch_bounds__(BLK) void asm_matrix_p1(const double* __restrict__ 
     const int i = r / BS, c = r % BS;
     const int a0 = (int)(rowptr[r] - s), len = (int)(rowptr[r + 1] - rowptr[r]);
     const bool bcr = bc[r] != 0;
-    constexpr double Ey = 1.0e6, nu = 0.3; // src/Elasticity.py:12-15
-    constexpr double mu = Ey / (2.0 * (1.0 + nu));
-    constexpr double lmbda = Ey * nu / ((1.0 + nu) * (1.0 - 2.0 * nu));
     const AdjIter adj(adjT_off, adjT_cells, adj_li, i);
     // Three-stage software pipeline over the row's cells.  A cell needs a chain of three dependent loads (adjacency
     // -> connectivity -> coordinates and BC flags); each link is issued one iteration ahead of the next: while cell a
@@ -371,8 +428,7 @@ __global__ __launch_bounds__(BLK) void asm_matrix_p1(const double* __restrict__ 
 #pragma unroll
           for (int d = 0; d < BS; ++d)
           {
-            // mu (delta_cd g_i.g_j + d_d phi_i d_c phi_j) + lambda d_c phi_i d_d phi_j
-            const double v = w * (mu * ((c == d ? gg : 0.0) + gi[d] * gjc) + lmbda * gic * g[j][d]);
+            const double v = p1_elasticity_entry(w, gg, c == d, gi[d], gjc, gic, g[j][d]);
             val[j][d] = (bcr || D0.bcj[j * BS + d]) ? 0.0 : v;
           }
         }
@@ -462,9 +518,6 @@ __global__ __launch_bounds__(64) void asm_matrix_p1_node3(const double* __restri
       bcols_s[b0 + k] = cols[a + 3 * k] / BS;
   }
   __syncthreads();
-  constexpr double Ey = 1.0e6, nu = 0.3; // src/Elasticity.py:12-15
-  constexpr double mu = Ey / (2.0 * (1.0 + nu));
-  constexpr double lmbda = Ey * nu / ((1.0 + nu) * (1.0 - 2.0 * nu));
   for (int i = d0 + (int)threadIdx.x; i < d1; i += BLK)
   {
     const int64_t ra = rowptr[(int64_t)i * BS];
@@ -554,8 +607,7 @@ __global__ __launch_bounds__(64) void asm_matrix_p1_node3(const double* __restri
 #pragma unroll
             for (int d = 0; d < BS; ++d)
             {
-              // mu (delta_cd g_i.g_j + d_d phi_i d_c phi_j) + lambda d_c phi_i d_d phi_j
-              const double v = w * (mu * ((c == d ? gg : 0.0) + gi[d] * gjc) + lmbda * gic * g[j][d]);
+              const double v = p1_elasticity_entry(w, gg, c == d, gi[d], gjc, gic, g[j][d]);
               acc[j][c][d] += (bcr[c] || D0.bcj[j * BS + d]) ? 0.0 : v;
             }
           }
@@ -883,9 +935,6 @@ __global__ __launch_bounds__(ASM_BLOCK) void asm_matrix_pk(const double* __restr
     const int r = i * BS + c;
     const int a0 = (int)(rowptr[r] - s), len = (int)(rowptr[r + 1] - rowptr[r]);
     const bool bcr = bc[r] != 0;
-    constexpr double Ey = 1.0e6, nu = 0.3; // src/Elasticity.py:12-15
-    constexpr double mu = Ey / (2.0 * (1.0 + nu));
-    constexpr double lmbda = Ey * nu / ((1.0 + nu) * (1.0 - 2.0 * nu));
     const AdjIter adj(adjT_off, adjT_cells, adj_li, i);
     // Three-stage software pipeline over the row's cells, as in asm_matrix_p1: the chain adjacency -> connectivity
     // (vertices + this lane's columns) -> coordinates and BC flags is issued one link per iteration ahead.
@@ -953,14 +1002,8 @@ __global__ __launch_bounds__(ASM_BLOCK) void asm_matrix_pk(const double* __restr
       const double* Tl = T_s + li * ND;
       if (BS == 1)
       {
-        // |detJ| (K K^T): 00 11 22 01 02 12
         double GG[6];
-        GG[0] = G.adet * (G.K[0][0] * G.K[0][0] + G.K[0][1] * G.K[0][1] + G.K[0][2] * G.K[0][2]);
-        GG[1] = G.adet * (G.K[1][0] * G.K[1][0] + G.K[1][1] * G.K[1][1] + G.K[1][2] * G.K[1][2]);
-        GG[2] = G.adet * (G.K[2][0] * G.K[2][0] + G.K[2][1] * G.K[2][1] + G.K[2][2] * G.K[2][2]);
-        GG[3] = G.adet * (G.K[0][0] * G.K[1][0] + G.K[0][1] * G.K[1][1] + G.K[0][2] * G.K[1][2]);
-        GG[4] = G.adet * (G.K[0][0] * G.K[2][0] + G.K[0][1] * G.K[2][1] + G.K[0][2] * G.K[2][2]);
-        GG[5] = G.adet * (G.K[1][0] * G.K[2][0] + G.K[1][1] * G.K[2][1] + G.K[1][2] * G.K[2][2]);
+        pk_poisson_geom(G, GG);
 #pragma unroll
         for (int q = 0; q < JM; ++q)
         {
@@ -969,10 +1012,7 @@ __global__ __launch_bounds__(ASM_BLOCK) void asm_matrix_pk(const double* __restr
             break;
           const int dj = K0.dj[q];
           const int pos = find_pos(cols_s + a0, len, dj);
-          double val = 0.0;
-#pragma unroll
-          for (int t = 0; t < 6; ++t)
-            val += GG[t] * Tl[t * NN + j];
+          double val = pk_poisson_entry<NN>(GG, Tl + j);
           if (bcr || D0.bcj[q])
             val = 0.0;
           vals_s[a0 + pos] += val;
@@ -988,28 +1028,13 @@ __global__ __launch_bounds__(ASM_BLOCK) void asm_matrix_pk(const double* __restr
             break;
           const int dj = K0.dj[q];
           const int pos = find_pos(cols_s + a0, len, dj * 3);
-          // D[cc][d] = |detJ| sum_{al,be} K[al][cc] K[be][d] S^[al][be]_{li,j} = int d_cc phi_i d_d phi_j
           double D[3][3];
-          {
-            double tmp[3][3];
-#pragma unroll
-            for (int al = 0; al < 3; ++al)
-#pragma unroll
-              for (int d = 0; d < 3; ++d)
-                tmp[al][d] = Tl[(al * 3 + 0) * NN + j] * G.K[0][d] + Tl[(al * 3 + 1) * NN + j] * G.K[1][d]
-                             + Tl[(al * 3 + 2) * NN + j] * G.K[2][d];
-#pragma unroll
-            for (int cc = 0; cc < 3; ++cc)
-#pragma unroll
-              for (int d = 0; d < 3; ++d)
-                D[cc][d] = G.adet * (G.K[0][cc] * tmp[0][d] + G.K[1][cc] * tmp[1][d] + G.K[2][cc] * tmp[2][d]);
-          }
+          pk_grad_products<NN>(G.adet, &G.K[0][0], Tl + j, D);
           const double tr = D[0][0] + D[1][1] + D[2][2];
 #pragma unroll
           for (int d = 0; d < 3; ++d)
           {
-            const double Dcd = sel3(D[0][d], D[1][d], D[2][d], c), Ddc = sel3(D[d][0], D[d][1], D[d][2], c);
-            double val = mu * ((c == d ? tr : 0.0) + Ddc) + lmbda * Dcd;
+            double val = pk_elasticity_entry(D, tr, c, d);
             if (bcr || D0.bcj[q * BS + d])
               val = 0.0;
             vals_s[a0 + pos + d] += val;
@@ -1331,9 +1356,6 @@ __global__ __launch_bounds__(ASM_BLOCK) void asm_matrix_pk_pos(const double* __r
   __syncthreads();
   const int lane = (int)threadIdx.x % LPR;
   constexpr int JM = (ND + LPR - 1) / LPR; // columns of a cell this lane handles
-  constexpr double Ey = 1.0e6, nu = 0.3; // src/Elasticity.py:12-15
-  constexpr double mu = Ey / (2.0 * (1.0 + nu));
-  constexpr double lmbda = Ey * nu / ((1.0 + nu) * (1.0 - 2.0 * nu));
   for (int q = (int)threadIdx.x / LPR; q < nt * BS; q += ASM_BLOCK / LPR)
   {
     const int i = d0 + (sorted ? ord_s[q / BS] : q / BS), c = q % BS;
@@ -1398,10 +1420,7 @@ __global__ __launch_bounds__(ASM_BLOCK) void asm_matrix_pk_pos(const double* __r
           const int j = lane + qq * LPR;
           if (j >= ND)
             break;
-          double val = 0.0;
-#pragma unroll
-          for (int t = 0; t < 6; ++t)
-            val += K0.g[t] * Tl[t * NN + j];
+          double val = pk_poisson_entry<NN>(K0.g, Tl + j);
           if (bcr)
             val = 0.0;
           vals_s[a0 + K0.pj[qq]] += val;
@@ -1417,28 +1436,13 @@ __global__ __launch_bounds__(ASM_BLOCK) void asm_matrix_pk_pos(const double* __r
           const int j = lane + qq * LPR;
           if (j >= ND)
             break;
-          // D[cc][d] = |detJ| sum_{al,be} K[al][cc] K[be][d] S^[al][be]_{li,j} = int d_cc phi_i d_d phi_j
           double D[3][3];
-          {
-            double tmp[3][3];
-#pragma unroll
-            for (int al = 0; al < 3; ++al)
-#pragma unroll
-              for (int d = 0; d < 3; ++d)
-                tmp[al][d] = Tl[(al * 3 + 0) * NN + j] * Kf[0 + d] + Tl[(al * 3 + 1) * NN + j] * Kf[3 + d]
-                             + Tl[(al * 3 + 2) * NN + j] * Kf[6 + d];
-#pragma unroll
-            for (int cc = 0; cc < 3; ++cc)
-#pragma unroll
-              for (int d = 0; d < 3; ++d)
-                D[cc][d] = adet * (Kf[0 + cc] * tmp[0][d] + Kf[3 + cc] * tmp[1][d] + Kf[6 + cc] * tmp[2][d]);
-          }
+          pk_grad_products<NN>(adet, Kf, Tl + j, D);
           const double tr = D[0][0] + D[1][1] + D[2][2];
 #pragma unroll
           for (int d = 0; d < 3; ++d)
           {
-            const double Dcd = sel3(D[0][d], D[1][d], D[2][d], c), Ddc = sel3(D[d][0], D[d][1], D[d][2], c);
-            double val = mu * ((c == d ? tr : 0.0) + Ddc) + lmbda * Dcd;
+            double val = pk_elasticity_entry(D, tr, c, d);
             if (bcr)
               val = 0.0;
             vals_s[a0 + K0.pj[qq] * 3 + d] += val;
@@ -1671,6 +1675,274 @@ int launch_assemble_vector(zzz_ctx* ctx, int form)
     else
       bs == 1 ? launch_vector_pk<20, 1>(ctx, nrows) : launch_vector_pk<20, 3>(ctx, nrows);
   }
+  ZZZ_HIP(ctx, hipGetLastError());
+  return ZZZ_OK;
+}
+
+// ---- lifting: apply_lifting(b, {a}, {{bc}}, {}, 1.0) and bc->set(b) with u0 != 0 (src/poisson_problem.cpp:152-155,
+// src/elasticity_problem.cpp:226-229; zzz_bc_values_upload).  A pass of its own behind the vector kernels above, which
+// stay what they are: for every owned unconstrained row i,  b_i -= sum_cells sum_{j constrained in the cell} A_e[i][j] g_j
+// with A_e the UNCONSTRAINED element matrix of form a (the entries the matrix kernels compute, through the same helpers,
+// before rows and columns are zeroed); then b_i = g_i on the constrained rows.  Only rows that share a cell with a
+// constrained dof change: a surface-sized list (k_lift_flag + rocprim::select), built once per pattern and Dirichlet set.
+// Owned rows are complete locally (ghost-cell layer) and g at ghost dofs comes from the caller: no communication.
+
+// flag[r] = row r is unconstrained and its pattern row holds a constrained column; eight lanes per row
+__global__ __launch_bounds__(256) void k_lift_flag(const rp_t* __restrict__ rowptr, const int32_t* __restrict__ cols,
+                                                   const uint8_t* __restrict__ bc, int64_t nrows, uint8_t* __restrict__ flag)
+{
+  const int sub = threadIdx.x & 7;
+  for (int64_t r = (blockIdx.x * 256ll + threadIdx.x) >> 3; r < nrows; r += (int64_t)gridDim.x * 32) // (a group's lanes share r)
+  {
+    const rp_t k0 = rowptr[r], k1 = rowptr[r + 1];
+    int any = 0;
+    for (rp_t k = k0 + sub; k < k1; k += 8)
+      any |= bc[cols[k]];
+    any |= __shfl_xor(any, 1, 8);
+    any |= __shfl_xor(any, 2, 8);
+    any |= __shfl_xor(any, 4, 8);
+    if (sub == 0)
+      flag[r] = (any && !bc[r]) ? 1 : 0;
+  }
+}
+
+// One listed row per group of LPR lanes (a group sits inside one wavefront).  The row's cells are walked in adjacency
+// order; a cell without a constrained dof is skipped by the whole group; in any other cell lane l forms the row's element
+// entries against local columns l, l + LPR, ... and the products with g, and the group adds them to the row's sum in
+// ascending local column order (a column's BS components first, in ascending order): one fixed order, no atomics, the same
+// bits in every run.  Every load is unconditional at an index inside its array; what an unconstrained column loads from g
+// (which may hold anything there) is dropped by a select, never multiplied.  P1 reads coordinates by dof (xq) like the P1
+// matrix kernels, P2 / P3 the vertices of the cell and the reference tensors from LDS, geometry once per (row, cell).
+template <int ND, int BS, int LPR>
+__global__ __launch_bounds__(ASM_BLOCK) void k_lift(const double* __restrict__ x, const int32_t* __restrict__ cell_verts,
+                                                    const int32_t* __restrict__ cell_dofs, const int32_t* __restrict__ adjT_off,
+                                                    const int32_t* __restrict__ adjT_cells, const uint8_t* __restrict__ adj_li,
+                                                    const uint8_t* __restrict__ bc, const double* __restrict__ gval,
+                                                    const int32_t* __restrict__ rows, int64_t nlist,
+                                                    const double* __restrict__ tab, double* __restrict__ b)
+{
+  constexpr int NT = (BS == 1) ? 6 : 9;
+  constexpr int NN = ND * ND;
+  constexpr int JM = (ND + LPR - 1) / LPR; // local columns per lane
+  __shared__ double T_s[ND == 4 ? 1 : NT * NN];
+  if (ND != 4)
+  {
+    for (int k = threadIdx.x; k < NT * NN; k += ASM_BLOCK)
+    {
+      if (BS == 1)
+      {
+        // symmetrised pieces, as the matrix kernels stage them
+        const int t = k / NN, ij = k % NN;
+        const int a = t < 3 ? t : (t == 3 ? 0 : (t == 4 ? 0 : 1)), bb = t < 3 ? t : (t == 3 ? 1 : 2);
+        T_s[k] = (t < 3) ? tab[(a * 3 + a) * NN + ij] : tab[(a * 3 + bb) * NN + ij] + tab[(bb * 3 + a) * NN + ij];
+      }
+      else
+        T_s[k] = tab[k];
+    }
+    __syncthreads();
+  }
+  const int lane = (int)threadIdx.x % LPR;
+  const int64_t q = (blockIdx.x * (int64_t)ASM_BLOCK + threadIdx.x) / LPR;
+  const int r = rows[min(q, nlist - 1)]; // (lanes past the list walk its last row and store nothing)
+  const int i = r / BS, c = r % BS;
+  const AdjIter adj(adjT_off, adjT_cells, adj_li, i);
+  double sum = 0.0;
+  for (int a = 0; a < adj.len; ++a)
+  {
+    const int cell = adj.cell(a);
+    if (cell < 0) // the row's list is exhausted (the slice's padding)
+      break;
+    const int li = adj.li(a);
+    const int32_t* __restrict__ cd = cell_dofs + (int64_t)ND * cell;
+    int dj[JM];
+    unsigned fl = 0; // bit qq * BS + d: component d of this lane's qq-th column is constrained
+#pragma unroll
+    for (int qq = 0; qq < JM; ++qq)
+      dj[qq] = cd[min(lane + qq * LPR, ND - 1)];
+#pragma unroll
+    for (int qq = 0; qq < JM; ++qq)
+#pragma unroll
+      for (int d = 0; d < BS; ++d)
+        if (bc[(int64_t)dj[qq] * BS + d] && lane + qq * LPR < ND)
+          fl |= 1u << (qq * BS + d);
+    unsigned any = fl;
+#pragma unroll
+    for (int o = 1; o < LPR; o <<= 1)
+      any |= __shfl_xor(any, o, LPR);
+    if (!any)
+      continue;
+    double gl[JM][BS];
+#pragma unroll
+    for (int qq = 0; qq < JM; ++qq)
+#pragma unroll
+      for (int d = 0; d < BS; ++d)
+      {
+        const double v = gval[(int64_t)dj[qq] * BS + d];
+        gl[qq][d] = ((fl >> (qq * BS + d)) & 1u) ? v : 0.0;
+      }
+    double p[4][3];
+    if (ND == 4)
+      load_cell_q(x, *reinterpret_cast<const int4*>(cd), p);
+    else
+      load_cell(x, *reinterpret_cast<const int4*>(cell_verts + 4 * (int64_t)cell), p);
+    Geom G;
+    geometry(p, G);
+    double t[JM]; // sum_d A_e[(li, c)][(j, d)] g_(j, d) for this lane's columns; 0 where nothing is constrained
+    if constexpr (ND == 4)
+    {
+      double g[4][3];
+      p1_grads(G, g);
+      const double w = G.adet / 6.0; // reference volume
+      double gi[3] = {0, 0, 0};
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (k == li)
+        {
+          gi[0] = g[k][0];
+          gi[1] = g[k][1];
+          gi[2] = g[k][2];
+        }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) // (LPR == 1: qq is j)
+      {
+        const double gg = gi[0] * g[j][0] + gi[1] * g[j][1] + gi[2] * g[j][2];
+        if (BS == 1)
+          t[j] = ((fl >> j) & 1u) ? (w * gg) * gl[j][0] : 0.0;
+        else
+        {
+          const double gic = sel3(gi[0], gi[1], gi[2], c), gjc = sel3(g[j][0], g[j][1], g[j][2], c);
+          double acc = 0.0;
+#pragma unroll
+          for (int d = 0; d < BS; ++d)
+          {
+            const double v = p1_elasticity_entry(w, gg, c == d, gi[d], gjc, gic, g[j][d]);
+            acc += ((fl >> (j * BS + d)) & 1u) ? v * gl[j][d] : 0.0;
+          }
+          t[j] = acc;
+        }
+      }
+    }
+    else
+    {
+      const double* Tl = T_s + li * ND;
+      double GG[6];
+      if (BS == 1)
+        pk_poisson_geom(G, GG);
+#pragma unroll
+      for (int qq = 0; qq < JM; ++qq)
+      {
+        const int j = min(lane + qq * LPR, ND - 1);
+        if (BS == 1)
+          t[qq] = ((fl >> qq) & 1u) ? pk_poisson_entry<NN>(GG, Tl + j) * gl[qq][0] : 0.0;
+        else
+        {
+          double acc = 0.0;
+          if ((fl >> (qq * BS)) & 7u)
+          {
+            double D[3][3];
+            pk_grad_products<NN>(G.adet, &G.K[0][0], Tl + j, D);
+            const double tr = D[0][0] + D[1][1] + D[2][2];
+#pragma unroll
+            for (int d = 0; d < 3; ++d)
+              acc += ((fl >> (qq * BS + d)) & 1u) ? pk_elasticity_entry(D, tr, c, d) * gl[qq][d] : 0.0;
+          }
+          t[qq] = acc;
+        }
+      }
+    }
+    // the row's sum, local columns ascending: column j sits in lane j % LPR as its (j / LPR)-th
+#pragma unroll
+    for (int j = 0; j < ND; ++j)
+      sum += LPR == 1 ? t[j] : __shfl(t[j / LPR], j % LPR, LPR);
+  }
+  if (lane == 0 && q < nlist)
+    b[r] -= sum;
+}
+
+// b[r] = g[r] on the owned constrained rows: bc->set(b) with u0's values
+__global__ __launch_bounds__(256) void k_bc_set_values(const uint8_t* __restrict__ bc, const double* __restrict__ gval, int64_t nrows,
+                                                       double* __restrict__ b)
+{
+  for (int64_t r = blockIdx.x * 256ll + threadIdx.x; r < nrows; r += (int64_t)gridDim.x * 256)
+  {
+    const double v = gval[r];
+    if (bc[r])
+      b[r] = v;
+  }
+}
+
+static int lift_rows_build(zzz_ctx* ctx)
+{
+  const int64_t nrows = ctx->nrows;
+  const char* info = getenv("ZZZ_LIFT_INFO"); // != 0: the list's size and what its build cost, on stderr
+  const bool timed = info && atoi(info) != 0;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (timed)
+  {
+    ZZZ_HIP(ctx, hipEventCreate(&e0));
+    ZZZ_HIP(ctx, hipEventCreate(&e1));
+    ZZZ_HIP(ctx, hipEventRecord(e0, ctx->stream));
+  }
+  // (grow_keep: another rank's kernel may be waiting for this one when both share a GPU, and hipFree waits for the device)
+  ZZZ_HIP(ctx, ctx->lift_flag.grow_keep((size_t)nrows, ctx->retired));
+  ZZZ_HIP(ctx, ctx->lift_rows.grow_keep((size_t)nrows + 1, ctx->retired)); // (+ 1: the count travels in the last entry)
+  hipLaunchKernelGGL(k_lift_flag, dim3((unsigned)std::min<int64_t>((nrows + 31) / 32, 16384)), dim3(256), 0, ctx->stream,
+                     ctx->rowptr.p, ctx->cols.p, ctx->bc.p, nrows, ctx->lift_flag.p);
+  rocprim::counting_iterator<int32_t> ids(0);
+  int32_t* count = ctx->lift_rows.p + nrows;
+  size_t tb = 0;
+  ZZZ_HIP(ctx, rocprim::select(nullptr, tb, ids, ctx->lift_flag.p, ctx->lift_rows.p, count, (size_t)nrows, ctx->stream));
+  ZZZ_HIP(ctx, ctx->scr_tmp.grow_keep(tb, ctx->retired));
+  ZZZ_HIP(ctx, rocprim::select(ctx->scr_tmp.p, tb, ids, ctx->lift_flag.p, ctx->lift_rows.p, count, (size_t)nrows, ctx->stream));
+  int32_t n = 0;
+  ZZZ_HIP(ctx, hipMemcpyAsync(&n, count, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->n_lift_rows = n;
+  if (timed)
+  {
+    float ms = 0;
+    ZZZ_HIP(ctx, hipEventRecord(e1, ctx->stream));
+    ZZZ_HIP(ctx, hipEventSynchronize(e1));
+    ZZZ_HIP(ctx, hipEventElapsedTime(&ms, e0, e1));
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    fprintf(stderr, "zzz: lifting rows: %d of %lld owned rows (%.2f %%), list built in %.3f ms\n", (int)n, (long long)nrows,
+            nrows ? 100.0 * n / nrows : 0.0, ms);
+  }
+  ctx->lift_pattern_version = ctx->pattern_version;
+  ctx->lift_bc_version = ctx->bc_version;
+  return ZZZ_OK;
+}
+
+template <int ND, int BS, int LPR>
+static void launch_k_lift(zzz_ctx* ctx)
+{
+  const int64_t nthreads = ctx->n_lift_rows * LPR;
+  hipLaunchKernelGGL((k_lift<ND, BS, LPR>), dim3((unsigned)((nthreads + ASM_BLOCK - 1) / ASM_BLOCK)), dim3(ASM_BLOCK), 0, ctx->stream,
+                     ND == 4 ? ctx->xq : ctx->x.p, ctx->cell_verts.p, ctx->cell_dofs.p, ctx->adjT_off.p, ctx->adjT_cells.p, ctx->adj_li.p,
+                     ctx->bc.p, ctx->bc_val.p, ctx->lift_rows.p, ctx->n_lift_rows, ctx->tables.p, ctx->b.p);
+}
+
+// behind launch_assemble_vector (which has checked the form against the dofmap and left b with zeros on the constrained rows)
+int launch_lift(zzz_ctx* ctx)
+{
+  if (ctx->lift_pattern_version != ctx->pattern_version || ctx->lift_bc_version != ctx->bc_version)
+    if (int rc = lift_rows_build(ctx))
+      return rc;
+  if (ctx->n_lift_rows > 0)
+  {
+    // lanes per row: one at P1 (four columns); otherwise as many as leave each lane five (Poisson) or three (elasticity: nine
+    // entries each) columns of a cell -- the P3 matrix kernels' split, for the same reason: a P3 vertex row walks 24 cells of 20 dofs
+    if (ctx->order == 1)
+      ctx->bs == 1 ? launch_k_lift<4, 1, 1>(ctx) : launch_k_lift<4, 3, 1>(ctx);
+    else if (ctx->order == 2)
+      ctx->bs == 1 ? launch_k_lift<10, 1, 2>(ctx) : launch_k_lift<10, 3, 4>(ctx);
+    else
+      ctx->bs == 1 ? launch_k_lift<20, 1, 4>(ctx) : launch_k_lift<20, 3, 8>(ctx);
+  }
+  const int64_t nrows = ctx->n_owned * ctx->bs;
+  hipLaunchKernelGGL(k_bc_set_values, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((nrows + 255) / 256, 2048))), dim3(256), 0,
+                     ctx->stream, ctx->bc.p, ctx->bc_val.p, nrows, ctx->b.p);
   ZZZ_HIP(ctx, hipGetLastError());
   return ZZZ_OK;
 }

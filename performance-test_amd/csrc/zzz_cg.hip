@@ -126,6 +126,28 @@ __device__ inline bool cg_direction_scalars(CgState* __restrict__ st, double* __
   return true;
 }
 
+// Inhomogeneous Dirichlet values with the matrix-free operator (zzz_bc_values_upload): its action zeroes the constrained
+// ROWS (src/cgpoisson_problem.cpp:207), so the solve iterates on b with its constrained entries taken as zero -- what
+// apply_lifting's scale 0.0 leaves there (:168) -- in a copy: the caller's b keeps b[bc] = g ...
+__global__ void k_masked_copy(const double* __restrict__ b, const uint8_t* __restrict__ bc, double* __restrict__ out, int64_t n)
+{
+  for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < n; r += (int64_t)gridDim.x * blockDim.x)
+  {
+    const double v = b[r];
+    out[r] = bc[r] ? 0.0 : v;
+  }
+}
+// ... and KSPCG, whose iterates keep u[bc] = 0, ends with u[bc] = g (the identity rows of the assembled operator give the same)
+__global__ void k_set_bc_values(const uint8_t* __restrict__ bc, const double* __restrict__ g, double* __restrict__ u, int64_t n)
+{
+  for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < n; r += (int64_t)gridDim.x * blockDim.x)
+  {
+    const double v = g[r];
+    if (bc[r])
+      u[r] = v;
+  }
+}
+
 __global__ void k_invert(double* __restrict__ d, int64_t n)
 {
   for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < n; r += (int64_t)gridDim.x * blockDim.x)
@@ -1117,7 +1139,16 @@ int cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
     ZZZ_HIP(ctx, hipMemsetAsync(ctx->u.p, 0, sizeof(double) * ctx->u.n, s)); // KSP zero initial guess
   double* pa = ctx->part_b.p;
   double* pb = ctx->part_b.p + VGRID_MAX;
-  hipLaunchKernelGGL(k_init_residual, dim3(g), dim3(VB), 0, s, ctx->b.p, w0, ctx->dinv.p, ctx->r.p, ctx->z.p, n, P.norm,
+  // (the matrix-free operator is served by this loop alone: every other form asks for the assembled one)
+  const bool lifted_mf = o->op == ZZZ_OP_MATFREE && ctx->have_bc_val;
+  const double* rhs = ctx->b.p;
+  if (lifted_mf)
+  {
+    ZZZ_HIP(ctx, ctx->b_masked.grow_keep((size_t)n, ctx->retired));
+    hipLaunchKernelGGL(k_masked_copy, dim3(g), dim3(VB), 0, s, ctx->b.p, ctx->bc.p, ctx->b_masked.p, n);
+    rhs = ctx->b_masked.p;
+  }
+  hipLaunchKernelGGL(k_init_residual, dim3(g), dim3(VB), 0, s, rhs, w0, ctx->dinv.p, ctx->r.p, ctx->z.p, n, P.norm,
                      pa, pb);
   // where the consumer kernels find <r,z>, the test norm and <p,w>: the producers' partials, or the
   // single all-reduced value when a communicator is attached
@@ -1219,6 +1250,8 @@ int cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
     hipLaunchKernelGGL(k_x_apply_pending<4>, dim3(g), dim3(VB), 0, s, ctx->state.p, ctx->alpha_hist.p, it, ring, ctx->u.p, n);
   else if (K == 8)
     hipLaunchKernelGGL(k_x_apply_pending<8>, dim3(g), dim3(VB), 0, s, ctx->state.p, ctx->alpha_hist.p, it, ring, ctx->u.p, n);
+  if (lifted_mf && o->variant == ZZZ_CG_PETSC) // (src/cg.h leaves u[bc] at the caller's initial guess, and so does ZZZ_CG_CGH)
+    hipLaunchKernelGGL(k_set_bc_values, dim3(g), dim3(VB), 0, s, ctx->bc.p, ctx->bc_val.p, ctx->u.p, n);
   ZZZ_HIP(ctx, hipGetLastError());
   CgState fin;
   ZZZ_HIP(ctx, hipMemcpyAsync(&fin, ctx->state.p, sizeof(CgState), hipMemcpyDeviceToHost, s));

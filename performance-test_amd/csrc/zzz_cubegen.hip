@@ -140,6 +140,7 @@ extern "C" int zzz_cube_generate(zzz_ctx* ctx, int problem, int order, int64_t n
   ZZZ_HIP(ctx, hipStreamSynchronize(s));
   ctx->nfacets = -1; // not counted: the mask is what the kernels read
   ctx->have_bc = true;
+  bc_values_clear(ctx);
   ctx->have_coeff[0] = true;
   ctx->have_coeff[1] = problem == ZZZ_FORM_POISSON;
   ctx->have_pattern = ctx->have_matrix = false;

@@ -197,6 +197,18 @@ struct zzz_ctx
   // bc marker per local scalar dof (owned + ghost)
   zzz::DevBuf<uint8_t> bc;
   bool have_bc = false;
+  // values of u0 at the constrained dofs (zzz_bc_values_upload): nloc * bs doubles in the device's numbering; only the
+  // entries whose marker is set are ever read.  Cleared by everything that changes the dof layout or the Dirichlet set.
+  zzz::DevBuf<double> bc_val;
+  bool have_bc_val = false;
+  uint64_t bc_version = 0; // counts Dirichlet sets (zzz_dofmap_upload, zzz_bc_upload, zzz_cube_generate)
+  // lifting pass (zzz_assemble.hip: k_lift): the owned unconstrained scalar rows whose pattern row holds a constrained
+  // column, ascending; built by the first lifted assembly of a (pattern, Dirichlet set) pair and kept until either changes
+  zzz::DevBuf<int32_t> lift_rows;
+  zzz::DevBuf<uint8_t> lift_flag; // scratch of the build (kept: a rebuild asks for the same size)
+  int64_t n_lift_rows = 0;
+  uint64_t lift_pattern_version = ~0ull, lift_bc_version = ~0ull;
+  zzz::DevBuf<double> b_masked; // the matrix-free solve's right-hand side with its constrained entries zeroed (zzz_cg.hip)
 
   // exterior-facet mask per cell (bit f = local facet f is exterior)
   zzz::DevBuf<uint8_t> facet_mask;
@@ -527,6 +539,8 @@ int launch_sellp_overlapped(zzz_ctx* ctx, double* x, double* y, double* partials
 // kernels_assemble
 int launch_assemble_matrix(zzz_ctx* ctx, int form);
 int launch_assemble_vector(zzz_ctx* ctx, int form);
+int launch_lift(zzz_ctx* ctx); // b -= A_e g over the lifting rows, then b[bc] = g (apply_lifting + bc->set with values)
+void bc_values_clear(zzz_ctx* ctx);
 int launch_matfree_action(zzz_ctx* ctx, const double* x, double* y, double* partials, int* npartials);
 int launch_matfree_legacy(zzz_ctx* ctx, const double* x, double* y, double* partials, int* npartials);
 int launch_matfree_diagonal(zzz_ctx* ctx, double* d);

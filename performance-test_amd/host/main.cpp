@@ -111,6 +111,9 @@ struct Options
   // poisson only: "assembled" = the reference's path (AIJ matrix, MatMult); "matfree" = KSPCG + PCJACOBI on the matrix-free
   // operator of cgpoisson: no matrix, the diagonal from the element matrices (an extension; faster from P2 up)
   std::string op = "assembled";
+  // u0 == bc_value at every constrained dof (all components for elasticity); absent = 0 = the reference's u0: no upload
+  bool have_bc_value = false;
+  double bc_value = 0.0;
   // PETSc options database (README.md:66-82)
   std::string ksp_type = "cg", pc_type = "jacobi", ksp_norm_type = "preconditioned";
   double ksp_rtol = 1e-5, ksp_atol = 1e-50, ksp_divtol = 1e4; // PETSc defaults (KSPCreate)
@@ -146,6 +149,8 @@ void usage()
                "  --allreduce arg (=peer)         peer (xGMI peer-memory mailboxes, else falls back) | comm\n"
                "  --operator arg (=assembled)     poisson: assembled (the AIJ matrix) | matfree (KSPCG on the matrix-free\n"
                "                                  operator, Jacobi from the element matrices' diagonals; no matrix)\n"
+               "  --bc_value arg (=0)             value of u0 at every Dirichlet dof (the reference's u0 is 0); non-zero: the\n"
+               "                                  vector assembly lifts it (apply_lifting, bc->set)\n"
                "PETSc-style solver options honoured: -ksp_type {cg,pipecg} -pc_type {jacobi,none,chebyshev_jacobi,mg,pmg} -ksp_rtol -ksp_atol\n"
                "  -ksp_divtol -pc_chebyshev_jacobi_degree (=3) -pc_chebyshev_jacobi_ratio (=60) -pc_chebyshev_jacobi_esteig (=10)\n"
                "  -ksp_max_it -ksp_norm_type {preconditioned,unpreconditioned,natural} -ksp_view -ksp_monitor\n"
@@ -200,6 +205,11 @@ Options parse(int argc, char** argv)
         o.allreduce = value(i, arg, key);
       else if (key == "operator")
         o.op = value(i, arg, key);
+      else if (key == "bc_value")
+      {
+        o.bc_value = std::stod(value(i, arg, key));
+        o.have_bc_value = o.bc_value != 0.0; // (0 is the reference: nothing is uploaded and the run is the run without the flag)
+      }
       else if (key == "memory_profiling")
         o.mem_profile = true;
       else if (key == "subcomm_partition")
@@ -431,7 +441,15 @@ void run_rank(Shared& S, std::barrier<>& bar, int rank)
   phase("ZZZ Create facets and facet->cell connectivity", [&] {});
 
   Timer umbrella("ZZZ Assemble"); // poisson/cgpoisson only in the reference (src/poisson_problem.cpp:49)
-  phase("ZZZ Create boundary conditions", [&] {});
+  phase("ZZZ Create boundary conditions", [&] {
+    if (!o.have_bc_value)
+      return;
+    // u0 = the constant function: its value at every local dof, owned and ghost (only the constrained ones are read)
+    std::int64_t ls[6] = {0, 0, 0, 0, 0, 0};
+    ZCK(ctx, zzz_local_sizes(ctx, ls));
+    const std::vector<double> u0((size_t)((ls[2] + ls[3]) * (problem == ZZZH_ELASTICITY ? 3 : 1)), o.bc_value);
+    ZCK(ctx, zzz_bc_values_upload(ctx, u0.data()));
+  });
   phase("ZZZ Create RHS function", [&] {});
   if (problem == ZZZH_ELASTICITY)
     phase("ZZZ Create forms", [&] {});

@@ -25,7 +25,7 @@ ERR_NO_GPU = 4
 
 ABI_SYMBOLS = [
     "zzz_device_count", "zzz_device_memory", "zzz_ctx_create", "zzz_ctx_destroy", "zzz_last_error", "zzz_sync", "zzz_mesh_upload",
-    "zzz_dofmap_upload", "zzz_bc_upload", "zzz_facets_upload", "zzz_coeff_upload", "zzz_cube_generate",
+    "zzz_dofmap_upload", "zzz_bc_upload", "zzz_bc_values_upload", "zzz_facets_upload", "zzz_coeff_upload", "zzz_cube_generate",
     "zzz_csr_pattern_build",
     "zzz_csr_sizes", "zzz_csr_download", "zzz_csr_rowptr64_download", "zzz_csr_upload_values", "zzz_assemble_matrix", "zzz_assemble_vector",
     "zzz_vec_download", "zzz_vec_upload", "zzz_vec_norm", "zzz_spmv", "zzz_spmv_time", "zzz_spmv_values_info", "zzz_spmv_values_info2", "zzz_abi_version", "zzz_action", "zzz_matfree_setup", "zzz_matfree_info", "zzz_matfree_diagonal", "zzz_action_time", "zzz_near_nullspace_build", "zzz_near_nullspace_download", "zzz_cg_solve", "zzz_cg_history",
@@ -97,6 +97,8 @@ def hip():
         L.zzz_mesh_upload.argtypes = [C.c_void_p, C.c_int64, _f64p, C.c_int64, _i32p]
         L.zzz_dofmap_upload.argtypes = [C.c_void_p, C.c_int, C.c_int, _i32p, C.c_int64, C.c_int64]
         L.zzz_bc_upload.argtypes = [C.c_void_p, C.c_int64, _i32p]
+        if hasattr(L, "zzz_bc_values_upload"):  # (ZZZ_HIP_LIB may name a build from before the entry point: the A/B tools)
+            L.zzz_bc_values_upload.argtypes = [C.c_void_p, C.c_void_p]
         L.zzz_facets_upload.argtypes = [C.c_void_p, C.c_int64, _i32p]
         L.zzz_coeff_upload.argtypes = [C.c_void_p, C.c_int, _f64p]
         L.zzz_cube_generate.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int,
@@ -366,6 +368,7 @@ class Context:
         self.h = h
         self.bs = 1
         self.n_owned = 0
+        self.n_ghost = 0
 
     def close(self):
         if getattr(self, "h", None):
@@ -401,6 +404,18 @@ class Context:
     def upload_bc(self, bc_dofs):
         b = np.ascontiguousarray(bc_dofs, np.int32)
         self._ck(self.L.zzz_bc_upload(self.h, b.shape[0], b if b.size else np.zeros(1, np.int32)))
+
+    def upload_bc_values(self, values):
+        """u0 at every local dof, owned then ghosts ((n_owned + n_ghost) * bs; only constrained entries are read):
+        bc->dof_values() of a DirichletBC whose u0 is not zero.  None clears: u0 == 0 again."""
+        if values is None:
+            self._ck(self.L.zzz_bc_values_upload(self.h, None))
+            return
+        v = np.ascontiguousarray(values, np.float64)
+        # (before a dofmap the library refuses the call itself, whatever the size)
+        if self.n_owned and v.shape != ((self.n_owned + self.n_ghost) * self.bs,):
+            raise ValueError(f"upload_bc_values: {v.shape} values for {(self.n_owned + self.n_ghost) * self.bs} local dofs")
+        self._ck(self.L.zzz_bc_values_upload(self.h, v.ctypes.data_as(C.c_void_p)))
 
     def upload_facets(self, facets):
         f = np.ascontiguousarray(facets, np.int32).reshape(-1)
