@@ -341,6 +341,25 @@ int zzz_matfree_diagonal(zzz_ctx* ctx, double* diag);
  * partials (what one iteration of linalg::cg launches at src/cg.h:62,65). */
 int zzz_action_time(zzz_ctx* ctx, int reps, double* avg_ms);
 
+/* ---- single precision: the cgpoisson path with T = float ----------------------------------
+ * src/cgpoisson_problem.cpp:28 says `using T = PetscScalar` and src/cg.h:18-86 is `template <typename U>`: on a
+ * single-precision PETSc the reference runs the action, the halo and linalg::cg in float.  These entry points are that
+ * instantiation on one rank, beside the double path, which they leave untouched: the operator's plan is shared, only its
+ * value arrays (geometry factors, reference tables, P1 coordinates, partial sums) get float twins, built by the first
+ * float action and dropped with the plan.  G = |detJ| K K^T is computed in double and rounded; P1 coordinates are stored
+ * relative to an origin of their cell block (subtracted in double), so that the Jacobian's differences carry the block's
+ * extent and not the domain's.  Declined with ZZZ_ERR_ARG and a reason: block size 3, an attached communicator. */
+
+/* y = action(x) in float (src/cgpoisson_problem.cpp:193-230 with T = float): host arrays of n_owned floats, as zzz_action
+ * takes doubles.  Bit-reproducible from call to call. */
+int zzz_action_f32(zzz_ctx* ctx, const float* x, float* y);
+/* Measurement aid, as zzz_action_time: `reps` float actions with the <p,y> partials (src/cg.h:62,65 with U = float). */
+int zzz_action_time_f32(zzz_ctx* ctx, int reps, double* avg_ms);
+/* info[0] the float twins are built, [1] bytes one float action addresses (zzz_matfree_info's [7] in double), [2] bytes of
+ * LDS a workgroup of the float action uses for its block (src/cgpoisson_problem.cpp:182, the storage of `un`, in float),
+ * [3] workgroups per CU that leaves room for. */
+int zzz_matfree_info_f32(zzz_ctx* ctx, int64_t info[4]);
+
 /* `ZZZ Create near-nullspace`: build_near_nullspace of src/elasticity_problem.cpp:36-94 (called at :233-244) -- the six
  * rigid-body modes of the vector-valued space at the dof coordinates (tabulate_dof_coordinates: every dof's reference
  * node pushed through its cell's affine map), orthonormalised in basis order as la::orthonormalize does, checked as
@@ -394,6 +413,15 @@ int zzz_internal_order_download(zzz_ctx* ctx, int32_t* perm /* n_owned */, int32
  * the context; returns the Krylov iteration count like KSPGetIterationNumber / cg()'s k.
  * rnorm[0] = final norm, rnorm[1] = initial norm (variant CGH: <r,r> and <r0,r0>). */
 int zzz_cg_solve(zzz_ctx* ctx, const zzz_solver_opts* opts, int* iters, double* rnorm);
+/* linalg::cg<float> (src/cg.h:38-86 with U = float, called at src/cgpoisson_problem.cpp:233) on the float action: x, r,
+ * p, y are float device vectors, alpha and beta floats as `const U alpha`, `const U beta` are (:65,75).  DIFFERENCE: the
+ * sums behind <p,y> and <r,r> are accumulated in double and rounded once, where the reference accumulates them in U --
+ * more accurate, and deterministic.  b is read from the context's double b, x starts from its u (the initial guess, :39)
+ * and the solution is stored there as doubles: zzz_vec_download, zzz_vec_norm, zzz_cg_history and zzz_cg_info serve both
+ * precisions.  rnorm as for ZZZ_CG_CGH.  Accepted: variant ZZZ_CG_CGH, pc ZZZ_PC_NONE, op ZZZ_OP_MATFREE.  Declined with
+ * ZZZ_ERR_ARG and the reason, the context staying usable: any other variant, preconditioner or operator,
+ * single_reduction, block size 3, an attached communicator, Dirichlet values uploaded by zzz_bc_values_upload. */
+int zzz_cg_solve_f32(zzz_ctx* ctx, const zzz_solver_opts* opts, int* iters, double* rnorm);
 
 /* Residual-norm history of the last solve (KSPGetResidualHistory): copies min(n, iters+1). */
 int zzz_cg_history(zzz_ctx* ctx, int n, double* out);

@@ -150,6 +150,7 @@ int zzz_ctx_create(int device, zzz_ctx** out)
       zzz::preload_spmv();
       zzz::preload_cg();
       zzz::preload_cg_pipe();
+      zzz::preload_cg_f32();
       zzz::preload_comm();
       zzz::preload_matfree();
       zzz::preload_mg();
@@ -1029,6 +1030,115 @@ int zzz_cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rno
   if (o->max_it < 0 || o->max_it > (1 << 24))
     return fail(ctx, ZZZ_ERR_ARG, "max_it %d out of range", o->max_it);
   return cg_solve(ctx, o, iters, rnorm);
+}
+
+// ---- single precision: T = float of src/cgpoisson_problem.cpp:28 --------------------------------------------------------
+// what the float path does not serve, said once for its entry points (null: it applies)
+static const char* f32_declined(const zzz_ctx* ctx)
+{
+  if (ctx->order == 0)
+    return "no dofmap";
+  if (ctx->bs != 1)
+    return "block size 3: the float32 path exists for the Poisson form M only (src/Poisson.py:33), not for elasticity";
+  if (ctx->comm)
+    return "a communicator is attached: the float32 path has no halo exchange or all-reduce yet (one rank only)";
+  return nullptr;
+}
+
+int zzz_action_f32(zzz_ctx* ctx, const float* x, float* y)
+{
+  ZZZ_ENTER(ctx);
+  if (!x || !y)
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_action_f32: NULL vector");
+  if (const char* why = f32_declined(ctx))
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_action_f32: %s", why);
+  const size_t n = (size_t)ctx->n_owned, nl = (size_t)ctx->nloc();
+  std::vector<float> tmp;
+  if (ctx->renumbered)
+  {
+    tmp.resize(n);
+    for (size_t i = 0; i < n; ++i)
+      tmp[i] = x[ctx->h_perm[i]];
+    x = tmp.data();
+  }
+  ZZZ_HIP(ctx, ctx->f32_p.reserve(nl));
+  ZZZ_HIP(ctx, ctx->f32_y.reserve(nl));
+  ZZZ_HIP(ctx, hipMemsetAsync(ctx->f32_p.p, 0, nl * sizeof(float), ctx->stream));
+  ZZZ_HIP(ctx, hipMemcpyAsync(ctx->f32_p.p, x, n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (int rc = mf_action_f32(ctx, ctx->f32_p.p, ctx->f32_y.p, nullptr, nullptr))
+    return rc;
+  float* dst = ctx->renumbered ? tmp.data() : y;
+  ZZZ_HIP(ctx, hipMemcpyAsync(dst, ctx->f32_y.p, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (ctx->renumbered)
+    for (size_t i = 0; i < n; ++i)
+      y[ctx->h_perm[i]] = tmp[i];
+  return ZZZ_OK;
+}
+
+int zzz_action_time_f32(zzz_ctx* ctx, int reps, double* avg_ms)
+{
+  ZZZ_ENTER(ctx);
+  if (reps <= 0 || !avg_ms)
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_action_time_f32: bad arguments");
+  if (const char* why = f32_declined(ctx))
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_action_time_f32: %s", why);
+  const size_t nl = (size_t)ctx->nloc();
+  const float* before = ctx->f32_p.p;
+  ZZZ_HIP(ctx, ctx->f32_p.reserve(nl));
+  ZZZ_HIP(ctx, ctx->f32_y.reserve(nl));
+  if (ctx->f32_p.p != before) // (never written: time a defined vector)
+    ZZZ_HIP(ctx, hipMemsetAsync(ctx->f32_p.p, 0, nl * sizeof(float), ctx->stream));
+  hipEvent_t e0, e1;
+  ZZZ_HIP(ctx, hipEventCreate(&e0));
+  ZZZ_HIP(ctx, hipEventCreate(&e1));
+  ZZZ_HIP(ctx, hipMemsetAsync(ctx->state.p, 0, sizeof(zzz::CgState), ctx->stream));
+  int np = 0;
+  int rc = mf_action_f32(ctx, ctx->f32_p.p, ctx->f32_y.p, ctx->part_a.p, &np); // warm-up (and the plan and its twins, if missing)
+  ZZZ_HIP(ctx, hipEventRecord(e0, ctx->stream));
+  for (int i = 0; i < reps && !rc; ++i)
+    rc = mf_action_f32(ctx, ctx->f32_p.p, ctx->f32_y.p, ctx->part_a.p, &np);
+  ZZZ_HIP(ctx, hipEventRecord(e1, ctx->stream));
+  ZZZ_HIP(ctx, hipEventSynchronize(e1));
+  float ms = 0;
+  ZZZ_HIP(ctx, hipEventElapsedTime(&ms, e0, e1));
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  *avg_ms = ms / reps;
+  return rc;
+}
+
+int zzz_matfree_info_f32(zzz_ctx* ctx, int64_t info[4])
+{
+  if (!ctx || !info)
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_matfree_info_f32: bad arguments");
+  return mf_f32_info(ctx, info);
+}
+
+int zzz_cg_solve_f32(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
+{
+  ZZZ_ENTER(ctx);
+  if (!o)
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_cg_solve_f32: NULL options");
+  if (o->variant != ZZZ_CG_CGH)
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_cg_solve_f32: variant %d: float32 runs linalg::cg (src/cg.h, ZZZ_CG_CGH) only", o->variant);
+  if (o->pc != ZZZ_PC_NONE)
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_cg_solve_f32: preconditioner %d: src/cg.h has none, use pc = ZZZ_PC_NONE", o->pc);
+  if (o->op != ZZZ_OP_MATFREE)
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_cg_solve_f32: operator %d: float32 exists for the matrix-free operator (ZZZ_OP_MATFREE) only", o->op);
+  if (o->single_reduction)
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_cg_solve_f32: -ksp_cg_single_reduction (single_reduction) applies to KSPCG on the assembled operator only");
+  if (const char* why = f32_declined(ctx))
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_cg_solve_f32: %s", why);
+  if (ctx->have_bc_val)
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_cg_solve_f32: Dirichlet values were uploaded (zzz_bc_values_upload): the lifted right-hand side is "
+                                  "not formed in float32 yet");
+  if (o->max_it < 0 || o->max_it > (1 << 24))
+    return fail(ctx, ZZZ_ERR_ARG, "max_it %d out of range", o->max_it);
+  if (ctx->b.n < (size_t)ctx->nloc() || ctx->u.n < (size_t)ctx->nloc())
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_cg_solve_f32: no problem vectors");
+  return cg_solve_f32(ctx, o, iters, rnorm);
 }
 
 int zzz_cg_history(zzz_ctx* ctx, int n, double* out)

@@ -151,6 +151,14 @@ struct MfPlan
   DevBuf<int32_t> sh_dof, sh_off, sh_slot; // shared dofs; where their partial sums start; (block, shared entry) -> slot
   DevBuf<uint8_t> sh_flag;                 // Dirichlet marker of each shared dof
   DevBuf<int32_t> mf_cell;      // [block][cell] -> cell of the context (-1: none), kept for rebuilding the geometry
+  // single precision (zzz_action_f32, zzz_cg_solve_f32): float twins of the VALUE arrays alone -- every index array above
+  // serves both scalars.  Built by the first float action of a plan, stale as soon as the plan is rebuilt.
+  bool f32_built = false;
+  int64_t nu = 0;                   // entries of the block-local dof lists
+  int64_t bytes_per_action_f32 = 0; // what one float action addresses
+  DevBuf<float> xyz32;              // P1: coordinates relative to the block's first listed dof (subtracted in double)
+  DevBuf<float> geom32, dtab32;     // P2/P3: geom and dtab rounded
+  DevBuf<float> ypart32;            // partial sums of the shared dofs
 };
 } // namespace zzz
 
@@ -406,6 +414,8 @@ struct zzz_ctx
   int64_t sp_win_bytes = 0;         // window bytes a product loads (all windowed groups)
   bool halo_pending = false; // comm_halo_begin put an exchange on the comm stream: comm_halo_end waits for it
   zzz::MfPlan mf; // matrix-free action
+  // linalg::cg in float (zzz_cg_f32.hip): x, r, p, y of src/cg.h:38-86 with U = float; grow-only, never freed by a solve
+  zzz::DevBuf<float> f32_x, f32_r, f32_p, f32_y;
   zzz::DevBuf<double> near_null; // the six orthonormalised rigid-body modes (zzz_nullspace.hip), [6][near_null_ld]
   int64_t near_null_ld = 0;
   // ZZZ_PC_CHEBYSHEV_JACOBI: the spectrum bound of the matrix as it stands (Gershgorin and Lanczos estimate cost ~10 products
@@ -483,6 +493,7 @@ void set_global_error(const char* msg);
 void preload_assemble();
 void preload_cg();
 void preload_cg_pipe();
+void preload_cg_f32();
 void preload_comm();
 void preload_cubegen();
 void preload_matfree();
@@ -548,6 +559,11 @@ int launch_matfree_diagonal(zzz_ctx* ctx, double* d);
 int mf_plan_build(zzz_ctx* ctx);
 int mf_action(zzz_ctx* ctx, const double* x, double* y, double* partials, int* npartials);
 int mf_diagonal(zzz_ctx* ctx, double* y);
+// the same action on the plan's float twins (built on first use; the plan itself as well); x, y: nloc floats on the device
+int mf_action_f32(zzz_ctx* ctx, const float* x, float* y, double* partials, int* npartials);
+int mf_f32_info(zzz_ctx* ctx, int64_t info[4]); // zzz_matfree_info_f32
+// zzz_cg_f32.hip
+int cg_solve_f32(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm);
 
 // kernels_cg
 int cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm);

@@ -31,7 +31,9 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "element_tables.inc"
+#include <type_traits>
+
+#include "zzz_mf_elem.h"
 
 namespace zzz
 {
@@ -522,26 +524,7 @@ __global__ __launch_bounds__(256) void k_mf_geom(const double* __restrict__ x, c
       for (int k = 0; k < 4; ++k)
         for (int a = 0; a < 3; ++a)
           p[k][a] = x[3ll * vv[k] + a];
-      double J[3][3];
-      for (int a = 0; a < 3; ++a)
-        for (int al = 0; al < 3; ++al)
-          J[a][al] = p[al + 1][a] - p[0][a];
-      // K = J^-1 = C / det, K[al][a] = dX_al / dx_a
-      double C[3][3];
-      C[0][0] = J[1][1] * J[2][2] - J[1][2] * J[2][1];
-      C[0][1] = J[0][2] * J[2][1] - J[0][1] * J[2][2];
-      C[0][2] = J[0][1] * J[1][2] - J[0][2] * J[1][1];
-      C[1][0] = J[1][2] * J[2][0] - J[1][0] * J[2][2];
-      C[1][1] = J[0][0] * J[2][2] - J[0][2] * J[2][0];
-      C[1][2] = J[0][2] * J[1][0] - J[0][0] * J[1][2];
-      C[2][0] = J[1][0] * J[2][1] - J[1][1] * J[2][0];
-      C[2][1] = J[0][1] * J[2][0] - J[0][0] * J[2][1];
-      C[2][2] = J[0][0] * J[1][1] - J[0][1] * J[1][0];
-      const double det = J[0][0] * C[0][0] + J[0][1] * C[1][0] + J[0][2] * C[2][0];
-      const double sc = 1.0 / fabs(det); // |det| K K^T = C C^T / |det|
-      const int pa[6] = {0, 1, 2, 0, 0, 1}, pb[6] = {0, 1, 2, 1, 2, 2};
-      for (int t = 0; t < 6; ++t)
-        G[t] = (C[pa[t]][0] * C[pb[t]][0] + C[pa[t]][1] * C[pb[t]][1] + C[pa[t]][2] * C[pb[t]][2]) * sc;
+      mf_cell_geom(p, G);
     }
     for (int t = 0; t < 6; ++t)
       geom[(b * 6 + t) * nc + e] = G[t];
@@ -549,92 +532,30 @@ __global__ __launch_bounds__(256) void k_mf_geom(const double* __restrict__ x, c
 }
 
 // ---- the action ------------------------------------------------------------------------------------------------------
+// R: the scalar of the value arrays (double, or float: T = float of src/cgpoisson_problem.cpp:28); the plan's index arrays
+// serve both, and the partial sums of <x, y> are doubles either way
+template <typename R>
 struct MfArgs
 {
   const int32_t* hdr;
   const int32_t* dof_ids;
   const uint8_t* dof_flag;
-  const double* xyz;
+  const R* xyz;
   const uint32_t* idxw;
   const uint32_t* rnkw;
   const uint8_t* rmax;
-  const double* geom;
-  const double* dtab;
+  const R* geom;
+  const R* dtab;
   const int32_t* pslot;
   const int32_t* gid;
-  double* ypart;
-  const double* u;
-  double* y;
+  R* ypart;
+  const R* u;
+  R* y;
   double* partials;
   const int* stop;
   int64_t nblocks;
   int nc, nsb, nloc_cap;
 };
-
-// The factorised tables: constexpr copies decide at compile time which entries are zero; the values are staged in LDS
-// by every (persistent) workgroup and reach the multiply-adds as broadcast reads.  (As literals they occupied ~200
-// vector registers of every lane; as scalar loads from constant memory the compiler hoisted them all and spilled 865
-// scalar registers; with the loads chained section by section through empty asm statements -- rows of the table as
-// scalar operands, no LDS traffic for them -- the kernel still spilled 410 scalar registers into vector lanes and was
-// 3 % faster at P3 6.2 M dofs, 0.281 against 0.291 ms, 1 % at P2: measured in round 4, not kept.)
-template <int ND>
-struct MfTab;
-template <>
-struct MfTab<10>
-{
-  static constexpr int NQ = 4;
-  static constexpr bool nz(int a, int q, int j) { return ZZZ_DTAB_P2[(a * 4 + q) * 10 + j] != 0.0; }
-};
-template <>
-struct MfTab<20>
-{
-  static constexpr int NQ = 10;
-  static constexpr bool nz(int a, int q, int j) { return ZZZ_DTAB_P3[(a * 10 + q) * 20 + j] != 0.0; }
-};
-
-// y_e = sum_q sum_a D_a[q][:]^T h_a(q),  h(q) = G g(q),  g_a(q) = D_a[q][:] . u_e -- mode q by mode q, so that only u_e,
-// y_e and six scalars are live.  A table entry is READ TWICE, once for each of its uses, the second time from a second
-// copy of the table laid out for that use ([q][j][a]; the compiler cannot tell that the two are equal): kept in
-// registers between the uses, the ~39 entries of a mode cost 78 vector registers, 220 in all, two wavefronts per SIMD.  Multiply-adds are fused here (the library is otherwise built with
-// -ffp-contract=off): the action is compared with the oracle to a tolerance, not bit for bit.
-template <int ND>
-__device__ inline void mf_element_pk(const double* __restrict__ tab, const double* __restrict__ tabT, const double (&ue)[ND],
-                                     const double (&G)[6], double (&ye)[ND])
-{
-#pragma clang fp contract(fast)
-  constexpr int NQ = MfTab<ND>::NQ;
-#pragma unroll
-  for (int j = 0; j < ND; ++j)
-    ye[j] = 0.0;
-#pragma unroll
-  for (int q = 0; q < NQ; ++q)
-  {
-    double g[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-    {
-      double acc = 0.0;
-#pragma unroll
-      for (int j = 0; j < ND; ++j)
-        if (MfTab<ND>::nz(a, q, j))
-          acc += tab[(a * NQ + q) * ND + j] * ue[j];
-      g[a] = acc;
-    }
-    const double h0 = G[0] * g[0] + G[3] * g[1] + G[4] * g[2];
-    const double h1 = G[3] * g[0] + G[1] * g[1] + G[5] * g[2];
-    const double h2 = G[4] * g[0] + G[5] * g[1] + G[2] * g[2];
-#pragma unroll
-    for (int j = 0; j < ND; ++j)
-    {
-      if (MfTab<ND>::nz(0, q, j))
-        ye[j] += tabT[(q * ND + j) * 3 + 0] * h0;
-      if (MfTab<ND>::nz(1, q, j))
-        ye[j] += tabT[(q * ND + j) * 3 + 1] * h1;
-      if (MfTab<ND>::nz(2, q, j))
-        ye[j] += tabT[(q * ND + j) * 3 + 2] * h2;
-    }
-  }
-}
 
 // the element matrix's diagonal: S_jj = sum_q d(q, j)^T G d(q, j), d_a(q, j) = D_a[q][j]
 template <int ND>
@@ -661,8 +582,14 @@ __device__ inline void mf_element_diag_pk(const double* __restrict__ tabT, const
 
 // DIAG: the same pass with the element matrix's diagonal in place of the element vector: y = diag(A) in the action's own
 // summation order (1.0 on constrained rows, fem::set_diagonal) -- what Jacobi needs when the operator is never assembled
-template <int ND, int T, bool DIAG>
-__global__ __launch_bounds__(T, (ND == 20 ? 3 : 1)) void k_mf_action(const MfArgs A)
+// R = float: the same pass on the plan's single-precision value arrays.  LDS per dof: P1 ONE 16-B record {x, y, z, u}
+// (coordinates relative to the block's origin, zzz_mf_elem.h) and ys, 20 B against 40; P2 us + ys, 8 B; P3 ys, 4 B.  The
+// rounds add with ds_add_f32 under the same rule (no two lanes of a round meet on an address): reproducible as well.
+// The partial sums of <x, y> are formed per thread and reduced in double.
+// wavefronts per SIMD the compiler must leave room for: P3 in double needs the 168 registers of three, in float (half the
+// registers for u_e, y_e and the table entries in flight) it fits the 128 of four
+template <int ND, int T, bool DIAG, typename R>
+__global__ __launch_bounds__(T, (ND == 20 ? (std::is_same<R, float>::value ? 4 : 3) : 1)) void k_mf_action(const MfArgs<R> A)
 {
   if (A.stop && *A.stop)
     return;
@@ -672,18 +599,20 @@ __global__ __launch_bounds__(T, (ND == 20 ? 3 : 1)) void k_mf_action(const MfArg
   // 16 bank positions, not the 8 of 32-B records), then ys[nloc_cap]; P2: us[nloc_cap] then ys[nloc_cap]; P3 (GU): ys only,
   // the cells gather u from memory through their global dof numbers (16 B per dof of LDS less: three workgroups per CU)
   constexpr bool GU = ND == 20;
-  double* const rec = reinterpret_cast<double*>(mf_lds);
-  double* const zu = rec + 2 * (size_t)A.nloc_cap;
-  double* const ys = rec + (size_t)(ND == 4 ? 4 : (GU ? 0 : 1)) * A.nloc_cap;
+  constexpr bool F32 = std::is_same<R, float>::value;
+  static_assert(!(F32 && DIAG), "the diagonal stays double");
+  R* const rec = reinterpret_cast<R*>(mf_lds);
+  R* const zu = rec + 2 * (size_t)A.nloc_cap; // (double P1 only)
+  R* const ys = rec + (size_t)(ND == 4 ? 4 : (GU ? 0 : 1)) * A.nloc_cap;
   __shared__ double red[T / 64];
   constexpr int NTAB = ND == 4 ? 1 : 3 * ND * (ND == 10 ? 4 : 10);
-  __shared__ double tab_s[NTAB], tabT_s[NTAB];
+  __shared__ R tab_s[NTAB], tabT_s[NTAB];
   const int tid = threadIdx.x;
   if (ND != 4)
     for (int k = tid; k < NTAB; k += T) // (the first block's barrier below orders this)
     {
       constexpr int NQ = ND == 10 ? 4 : 10;
-      const double v = A.dtab[k]; // [a][q][j]
+      const R v = A.dtab[k]; // [a][q][j]
       const int a = k / (NQ * ND), q = (k / ND) % NQ, j = k % ND;
       tab_s[k] = v;
       tabT_s[(q * ND + j) * 3 + a] = v;
@@ -700,8 +629,13 @@ __global__ __launch_bounds__(T, (ND == 20 ? 3 : 1)) void k_mf_action(const MfArg
     for (int d = tid; d < nloc; d += T)
     {
       const int32_t g = (GU || DIAG) ? 0 : A.dof_ids[dof_off + d];
-      const double uv = (GU || DIAG) ? 1.0 : A.u[g];
-      if (ND == 4)
+      const R uv = (GU || DIAG) ? (R)1.0 : A.u[g];
+      if constexpr (ND == 4 && F32)
+      {
+        const float* __restrict__ q = A.xyz + 3ll * (dof_off + d);
+        *reinterpret_cast<float4*>(rec + 4 * d) = make_float4(q[0], q[1], q[2], uv);
+      }
+      else if constexpr (ND == 4)
       {
         const double* __restrict__ q = A.xyz + 3ll * (dof_off + d);
         *reinterpret_cast<double2*>(rec + 2 * d) = make_double2(q[0], q[1]);
@@ -721,7 +655,7 @@ __global__ __launch_bounds__(T, (ND == 20 ? 3 : 1)) void k_mf_action(const MfArg
 #pragma unroll
       for (int w = 0; w < NRW; ++w)
         rw[w] = A.rnkw[(b * NRW + w) * A.nc + e];
-      double ye[ND];
+      R ye[ND];
       if (s == 0)
       {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -729,46 +663,27 @@ __global__ __launch_bounds__(T, (ND == 20 ? 3 : 1)) void k_mf_action(const MfArg
       }
       if constexpr (ND == 4)
       {
-#pragma clang fp contract(fast)
         const int i0 = iw[0] & 0xffff, i1 = iw[0] >> 16, i2 = iw[1] & 0xffff, i3 = iw[1] >> 16;
-        const double2 a0 = *reinterpret_cast<const double2*>(rec + 2 * i0), b0 = *reinterpret_cast<const double2*>(zu + 2 * i0);
-        const double2 a1 = *reinterpret_cast<const double2*>(rec + 2 * i1), b1 = *reinterpret_cast<const double2*>(zu + 2 * i1);
-        const double2 a2 = *reinterpret_cast<const double2*>(rec + 2 * i2), b2 = *reinterpret_cast<const double2*>(zu + 2 * i2);
-        const double2 a3 = *reinterpret_cast<const double2*>(rec + 2 * i3), b3 = *reinterpret_cast<const double2*>(zu + 2 * i3);
-        const double4 p0 = make_double4(a0.x, a0.y, b0.x, b0.y), p1 = make_double4(a1.x, a1.y, b1.x, b1.y);
-        const double4 p2 = make_double4(a2.x, a2.y, b2.x, b2.y), p3 = make_double4(a3.x, a3.y, b3.x, b3.y);
-        // J[a][al] = p_(al+1)[a] - p_0[a]; C = cofactors: K = J^-1 = C / det, grad phi_(al+1) = C[al][:] / det
-        const double J00 = p1.x - p0.x, J01 = p2.x - p0.x, J02 = p3.x - p0.x;
-        const double J10 = p1.y - p0.y, J11 = p2.y - p0.y, J12 = p3.y - p0.y;
-        const double J20 = p1.z - p0.z, J21 = p2.z - p0.z, J22 = p3.z - p0.z;
-        const double C00 = J11 * J22 - J12 * J21, C01 = J02 * J21 - J01 * J22, C02 = J01 * J12 - J02 * J11;
-        const double C10 = J12 * J20 - J10 * J22, C11 = J00 * J22 - J02 * J20, C12 = J02 * J10 - J00 * J12;
-        const double C20 = J10 * J21 - J11 * J20, C21 = J01 * J20 - J00 * J21, C22 = J00 * J11 - J01 * J10;
-        const double det = J00 * C00 + J01 * C10 + J02 * C20;
-        const double d1 = p1.w - p0.w, d2 = p2.w - p0.w, d3 = p3.w - p0.w;
-        const double sc = 1.0 / (6.0 * fabs(det));
-        if constexpr (DIAG)
+        if constexpr (F32)
         {
-          const double s0 = C00 + C10 + C20, s1 = C01 + C11 + C21, s2 = C02 + C12 + C22;
-          ye[0] = (s0 * s0 + s1 * s1 + s2 * s2) * sc;
-          ye[1] = (C00 * C00 + C01 * C01 + C02 * C02) * sc;
-          ye[2] = (C10 * C10 + C11 * C11 + C12 * C12) * sc;
-          ye[3] = (C20 * C20 + C21 * C21 + C22 * C22) * sc;
+          const float4 q0 = *reinterpret_cast<const float4*>(rec + 4 * i0), q1 = *reinterpret_cast<const float4*>(rec + 4 * i1);
+          const float4 q2 = *reinterpret_cast<const float4*>(rec + 4 * i2), q3 = *reinterpret_cast<const float4*>(rec + 4 * i3);
+          mf_element_p1<DIAG, float>({q0.x, q0.y, q0.z, q0.w}, {q1.x, q1.y, q1.z, q1.w}, {q2.x, q2.y, q2.z, q2.w},
+                                     {q3.x, q3.y, q3.z, q3.w}, ye);
         }
         else
         {
-        const double t0 = (C00 * d1 + C10 * d2 + C20 * d3) * sc;
-        const double t1 = (C01 * d1 + C11 * d2 + C21 * d3) * sc;
-        const double t2 = (C02 * d1 + C12 * d2 + C22 * d3) * sc;
-        ye[1] = C00 * t0 + C01 * t1 + C02 * t2;
-        ye[2] = C10 * t0 + C11 * t1 + C12 * t2;
-        ye[3] = C20 * t0 + C21 * t1 + C22 * t2;
-        ye[0] = -(ye[1] + ye[2] + ye[3]);
+          const double2 a0 = *reinterpret_cast<const double2*>(rec + 2 * i0), b0 = *reinterpret_cast<const double2*>(zu + 2 * i0);
+          const double2 a1 = *reinterpret_cast<const double2*>(rec + 2 * i1), b1 = *reinterpret_cast<const double2*>(zu + 2 * i1);
+          const double2 a2 = *reinterpret_cast<const double2*>(rec + 2 * i2), b2 = *reinterpret_cast<const double2*>(zu + 2 * i2);
+          const double2 a3 = *reinterpret_cast<const double2*>(rec + 2 * i3), b3 = *reinterpret_cast<const double2*>(zu + 2 * i3);
+          mf_element_p1<DIAG, double>({a0.x, a0.y, b0.x, b0.y}, {a1.x, a1.y, b1.x, b1.y}, {a2.x, a2.y, b2.x, b2.y},
+                                      {a3.x, a3.y, b3.x, b3.y}, ye);
         }
       }
       else
       {
-        double G[6], ue[ND];
+        R G[6], ue[ND];
 #pragma unroll
         for (int t = 0; t < 6; ++t)
           G[t] = A.geom[(b * 6 + t) * A.nc + e];
@@ -787,7 +702,7 @@ __global__ __launch_bounds__(T, (ND == 20 ? 3 : 1)) void k_mf_action(const MfArg
             ue[j] = rec[(iw[j >> 1] >> (16 * (j & 1))) & 0xffff];
         }
         if constexpr (!DIAG)
-          mf_element_pk<ND>(tab_s, tabT_s, ue, G, ye);
+          mf_element_pk<ND, R>(tab_s, tabT_s, ue, G, ye);
       }
       // rounds: the incidences of rank r of this step are added in round r (distinct addresses inside a round).  The
       // additions are LDS atomics WITHOUT return (ds_add_f64: nothing to wait for inside a round; a read-add-write chain
@@ -836,10 +751,10 @@ __global__ __launch_bounds__(T, (ND == 20 ? 3 : 1)) void k_mf_action(const MfArg
     {
       const int32_t g = A.dof_ids[dof_off + d];
       // bc->set(y.array(), std::nullopt, 0.0), src/cgpoisson_problem.cpp:207; the diagonal: 1.0 there
-      const double v = A.dof_flag[dof_off + d] ? (DIAG ? 1.0 : 0.0) : ys[d];
+      const R v = A.dof_flag[dof_off + d] ? (R)(DIAG ? 1.0 : 0.0) : ys[d];
       A.y[g] = v;
       if constexpr (!DIAG)
-        dot += v * (ND == 4 ? zu[2 * d + 1] : (GU ? A.u[g] : rec[d]));
+        dot += (double)v * (double)(ND == 4 ? (F32 ? rec[4 * d + 3] : zu[2 * d + 1]) : (GU ? A.u[g] : rec[d]));
     }
     for (int d = tid; d < n_sh; d += T)
       A.ypart[A.pslot[part_off + d]] = ys[n_int + d];
@@ -855,11 +770,12 @@ __global__ __launch_bounds__(T, (ND == 20 ? 3 : 1)) void k_mf_action(const MfArg
 }
 
 // the dofs shared between blocks: their partial sums (side by side, ascending block) added in that order
+template <typename R>
 __global__ __launch_bounds__(256) void k_mf_finish(const int32_t* __restrict__ sh_dof, const int32_t* __restrict__ sh_off,
                                                    const uint8_t* __restrict__ sh_flag, int64_t nshared,
-                                                   const double* __restrict__ ypart, const double* __restrict__ u,
-                                                   double* __restrict__ y, double* __restrict__ partials,
-                                                   const int* __restrict__ stop, double fixed_value)
+                                                   const R* __restrict__ ypart, const R* __restrict__ u,
+                                                   R* __restrict__ y, double* __restrict__ partials,
+                                                   const int* __restrict__ stop, R fixed_value)
 {
   if (stop && *stop)
     return;
@@ -869,15 +785,15 @@ __global__ __launch_bounds__(256) void k_mf_finish(const int32_t* __restrict__ s
   {
     const int32_t g = sh_dof[k];
     const int p0 = sh_off[k], p1 = sh_off[k + 1];
-    const double ug = u ? u[g] : 0.0;
+    const R ug = u ? u[g] : (R)0.0;
     const bool fixed = sh_flag[k] != 0;
-    double s = ypart[p0];
+    R s = ypart[p0];
     for (int p = p0 + 1; p < p1; ++p)
       s += ypart[p];
     if (fixed)
       s = fixed_value; // bc->set(y.array(), std::nullopt, 0.0), src/cgpoisson_problem.cpp:207 (the diagonal: 1.0)
     y[g] = s;
-    dot += s * ug;
+    dot += (double)s * (double)ug;
   }
   if (partials)
   {
@@ -931,6 +847,19 @@ unsigned bits_for(uint64_t v)
 }
 
 int lds_bytes(int nd, int nloc_cap) { return (nd == 4 ? 40 : (nd == 20 ? 8 : 16)) * nloc_cap; }
+int lds_bytes_f32(int nd, int nloc_cap) { return (nd == 4 ? 20 : (nd == 20 ? 4 : 8)) * nloc_cap; }
+
+// what one action addresses with values of vb bytes: the per-cell streams, the block lists (ids, flags, coordinates), u
+// gathered and y written per list entry, the partial sums out and back, the shared dofs' finish
+int64_t action_bytes(const MfPlan& M, int64_t vb)
+{
+  const int nd = M.nd;
+  const int64_t total = M.nblocks * M.nc, nu = M.nu;
+  return total * (4ll * M.ndw + 4ll * M.nrw + (nd == 4 ? 0 : 6 * vb) + (nd == 20 ? 4 * nd + vb * nd : 0))
+         + nu * (nd == 20 ? 0 : 4 + 1 + vb + (nd == 4 ? 3 * vb : 0)) + (nd == 20 ? (nu - M.nslots) * (4 + 1 + vb) : 0)
+         + (nu - M.nslots) * vb + M.nslots * (vb + vb + 4) + M.nshared * (4 + 4 + 1 + vb + vb)
+         + M.nblocks * (MF_HDR * 4 + M.nsb * M.nrw * 4);
+}
 
 // one attempt with blocks of nc cells; *retry: some block touches more dofs than LDS holds
 int plan_attempt(zzz_ctx* ctx, int nc, int T, int nloc_limit, bool* retry)
@@ -1167,11 +1096,9 @@ int plan_attempt(zzz_ctx* ctx, int nc, int T, int nloc_limit, bool* retry)
   }
   ZZZ_HIP(ctx, hipGetLastError());
   ZZZ_HIP(ctx, hipStreamSynchronize(s));
-  // what one action addresses: the per-cell streams, the block lists (ids, flags, coordinates), u gathered and y
-  // written per list entry, the partial sums out and back, the shared dofs' finish
-  M.bytes_per_action = total * (4ll * M.ndw + 4ll * M.nrw + (nd == 4 ? 0 : 48) + (nd == 20 ? 4 * nd + 8 * nd : 0))
-                       + nu * (nd == 20 ? 0 : 4 + 1 + 8 + (nd == 4 ? 24 : 0)) + (nd == 20 ? (nu - M.nslots) * (4 + 1 + 8) : 0)
-                       + (nu - M.nslots) * 8 + M.nslots * (8 + 8 + 4) + M.nshared * (4 + 4 + 1 + 8 + 8) + nb * (MF_HDR * 4 + nsb * M.nrw * 4);
+  M.nu = nu;
+  M.bytes_per_action = action_bytes(M, 8);
+  M.bytes_per_action_f32 = action_bytes(M, 4);
   return ZZZ_OK;
 }
 } // namespace
@@ -1180,6 +1107,7 @@ int mf_plan_build(zzz_ctx* ctx)
 {
   MfPlan& M = ctx->mf;
   M.valid = M.failed = false;
+  M.f32_built = false; // (the twins follow the plan)
   if (ctx->bs != 1)
     return fail(ctx, ZZZ_ERR_ARG, "the matrix-free operator exists for the Poisson form M only (src/Poisson.py:33)");
   if (ctx->order == 0 || ctx->ncells == 0)
@@ -1226,52 +1154,145 @@ int mf_plan_build(zzz_ctx* ctx)
   return ZZZ_OK;
 }
 
-template <int ND, int T, bool DIAG>
-static int mf_launch(zzz_ctx* ctx, const MfArgs& A, int grid, int lds)
+template <int ND, int T, bool DIAG, typename R>
+static int mf_launch(zzz_ctx* ctx, const MfArgs<R>& A, int grid, int lds)
 {
   static int attr_lds[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; // per device: the limit this instantiation was given
   if (lds > 48 * 1024 && lds > attr_lds[ctx->device & 15])
   {
-    ZZZ_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_mf_action<ND, T, DIAG>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    ZZZ_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_mf_action<ND, T, DIAG, R>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     attr_lds[ctx->device & 15] = lds;
   }
-  hipLaunchKernelGGL((k_mf_action<ND, T, DIAG>), dim3(grid), dim3(T), lds, ctx->stream, A);
+  hipLaunchKernelGGL((k_mf_action<ND, T, DIAG, R>), dim3(grid), dim3(T), lds, ctx->stream, A);
   return ZZZ_OK;
 }
 
-static int mf_run(zzz_ctx* ctx, bool diag, const double* u, double* y, double* partials, int* npartials);
+// persistent workgroups: as many as fit a CU by LDS and threads
+static int mf_per_cu(const MfPlan& M, int lds)
+{
+  const int per_cu = std::min((160 * 1024) / std::max(lds + 512, 1), 2048 / M.threads);
+  return std::max(1, std::min(per_cu, 8));
+}
+
+template <typename R>
+static int mf_run(zzz_ctx* ctx, bool diag, const R* u, R* y, double* partials, int* npartials);
 
 int mf_action(zzz_ctx* ctx, const double* u, double* y, double* partials, int* npartials)
 {
-  return mf_run(ctx, false, u, y, partials, npartials);
+  return mf_run<double>(ctx, false, u, y, partials, npartials);
 }
 
 // y = diag(A) (1.0 on constrained rows), summed in the order of the action
-int mf_diagonal(zzz_ctx* ctx, double* y) { return mf_run(ctx, true, nullptr, y, nullptr, nullptr); }
+int mf_diagonal(zzz_ctx* ctx, double* y) { return mf_run<double>(ctx, true, nullptr, y, nullptr, nullptr); }
 
-static int mf_run(zzz_ctx* ctx, bool diag, const double* u, double* y, double* partials, int* npartials)
+// ---- the float twins of the plan's value arrays ---------------------------------------------------------------------------
+namespace
+{
+__global__ __launch_bounds__(256) void k_mf32_round(const double* __restrict__ in, int64_t n, float* __restrict__ out)
+{
+  for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += gridDim.x * 256ll)
+    out[i] = mf_round<float>(in[i]);
+}
+// P1 coordinates of every block's dof list, relative to the block's first listed dof
+__global__ __launch_bounds__(256) void k_mf32_xyz(const int32_t* __restrict__ hdr, int64_t nblocks, const double* __restrict__ xyz,
+                                                  float* __restrict__ out)
+{
+  for (int64_t b = blockIdx.x; b < nblocks; b += gridDim.x)
+  {
+    const int64_t off = hdr[MF_HDR * b + 0];
+    const int nloc = hdr[MF_HDR * b + 1];
+    for (int k = threadIdx.x; k < 3 * nloc; k += 256)
+      out[3 * off + k] = mf_rel_coord<float>(xyz[3 * off + k], xyz[3 * off + k % 3]);
+  }
+}
+} // namespace
+
+static int mf_f32_build(zzz_ctx* ctx)
+{
+  MfPlan& M = ctx->mf;
+  hipStream_t s = ctx->stream;
+  if (M.nd == 4)
+  {
+    ZZZ_HIP(ctx, M.xyz32.alloc((size_t)M.nu * 3));
+    hipLaunchKernelGGL(k_mf32_xyz, dim3((unsigned)std::min<int64_t>(M.nblocks, 8192)), dim3(256), 0, s, M.hdr.p, M.nblocks, M.xyz.p,
+                       M.xyz32.p);
+  }
+  else
+  {
+    const int64_t ng = M.nblocks * 6 * M.nc, nt = M.nd == 10 ? 120 : 600;
+    ZZZ_HIP(ctx, M.geom32.alloc((size_t)ng));
+    ZZZ_HIP(ctx, M.dtab32.alloc((size_t)nt));
+    hipLaunchKernelGGL(k_mf32_round, dim3(grid_for(ng)), dim3(256), 0, s, M.geom.p, ng, M.geom32.p);
+    hipLaunchKernelGGL(k_mf32_round, dim3(1), dim3(256), 0, s, M.dtab.p, nt, M.dtab32.p);
+  }
+  ZZZ_HIP(ctx, M.ypart32.alloc((size_t)std::max<int64_t>(M.nslots, 1)));
+  ZZZ_HIP(ctx, hipGetLastError());
+  ZZZ_HIP(ctx, hipStreamSynchronize(s));
+  M.f32_built = true;
+  return ZZZ_OK;
+}
+
+int mf_action_f32(zzz_ctx* ctx, const float* u, float* y, double* partials, int* npartials)
 {
   MfPlan& M = ctx->mf;
   if (!M.valid)
+  {
+    if (M.failed)
+      return fail(ctx, ZZZ_ERR_LIMIT, "the float32 action needs the cell-block plan, which this mesh does not fit");
+    if (int rc = mf_plan_build(ctx))
+      return rc;
+  }
+  if (!M.f32_built)
+    if (int rc = mf_f32_build(ctx))
+      return rc;
+  return mf_run<float>(ctx, false, u, y, partials, npartials);
+}
+
+int mf_f32_info(zzz_ctx* ctx, int64_t info[4])
+{
+  const MfPlan& M = ctx->mf;
+  const int lds = M.valid ? lds_bytes_f32(M.nd, M.nloc_max) : 0;
+  info[0] = M.valid && M.f32_built ? 1 : 0;
+  info[1] = M.valid ? M.bytes_per_action_f32 : 0;
+  info[2] = lds;
+  info[3] = M.valid ? mf_per_cu(M, lds) : 0;
+  return ZZZ_OK;
+}
+
+template <typename R>
+static int mf_run(zzz_ctx* ctx, bool diag, const R* u, R* y, double* partials, int* npartials)
+{
+  constexpr bool F32 = std::is_same<R, float>::value;
+  MfPlan& M = ctx->mf;
+  if (!M.valid)
     return fail(ctx, ZZZ_ERR_ARG, "matrix-free plan missing");
-  const int lds = lds_bytes(M.nd, M.nloc_max);
+  const int lds = F32 ? lds_bytes_f32(M.nd, M.nloc_max) : lds_bytes(M.nd, M.nloc_max);
   // persistent workgroups: as many as fit a CU by LDS and threads, XCD-aware walk over the blocks
-  int per_cu = std::min((160 * 1024) / std::max(lds + 512, 1), 2048 / M.threads);
-  per_cu = std::max(1, std::min(per_cu, 8));
+  const int per_cu = mf_per_cu(M, lds);
   int grid = (int)std::min<int64_t>(256ll * per_cu, (M.nblocks + 7) / 8 * 8);
   grid = std::max(8, grid / 8 * 8);
   const int gf = (int)std::min<int64_t>(std::max<int64_t>((M.nshared + 255) / 256, 1), 2048);
-  MfArgs A;
+  MfArgs<R> A;
   A.hdr = M.hdr.p;
   A.dof_ids = M.dof_ids.p;
   A.dof_flag = M.dof_flag.p;
-  A.xyz = M.xyz.p;
   A.idxw = M.idxw.p;
   A.rnkw = M.rnkw.p;
   A.rmax = M.rmax.p;
-  A.geom = M.geom.p;
-  A.dtab = M.dtab.p;
-  A.ypart = M.ypart.p;
+  if constexpr (F32)
+  {
+    A.xyz = M.xyz32.p;
+    A.geom = M.geom32.p;
+    A.dtab = M.dtab32.p;
+    A.ypart = M.ypart32.p;
+  }
+  else
+  {
+    A.xyz = M.xyz.p;
+    A.geom = M.geom.p;
+    A.dtab = M.dtab.p;
+    A.ypart = M.ypart.p;
+  }
   A.pslot = M.sh_slot.p;
   A.gid = M.gid.p;
   A.u = u;
@@ -1284,22 +1305,30 @@ static int mf_run(zzz_ctx* ctx, bool diag, const double* u, double* y, double* p
   A.nloc_cap = M.nloc_max;
   int rc = ZZZ_OK;
 #define ZZZ_MF_T(ND_, DG_)                                                                                              \
-  (M.threads == 128 ? mf_launch<ND_, 128, DG_>(ctx, A, grid, lds)                                                         \
-                    : M.threads == 256 ? mf_launch<ND_, 256, DG_>(ctx, A, grid, lds)                                      \
-                                       : M.threads == 512 ? mf_launch<ND_, 512, DG_>(ctx, A, grid, lds)                   \
-                                                          : mf_launch<ND_, 1024, DG_>(ctx, A, grid, lds))
-  if (M.nd == 4)
-    rc = diag ? ZZZ_MF_T(4, true) : ZZZ_MF_T(4, false);
-  else if (M.nd == 10)
-    rc = diag ? ZZZ_MF_T(10, true) : ZZZ_MF_T(10, false);
+  (M.threads == 128 ? mf_launch<ND_, 128, DG_, R>(ctx, A, grid, lds)                                                      \
+                    : M.threads == 256 ? mf_launch<ND_, 256, DG_, R>(ctx, A, grid, lds)                                   \
+                                       : M.threads == 512 ? mf_launch<ND_, 512, DG_, R>(ctx, A, grid, lds)                \
+                                                          : mf_launch<ND_, 1024, DG_, R>(ctx, A, grid, lds))
+  if constexpr (F32)
+  {
+    // (the diagonal stays double)
+    rc = M.nd == 4 ? ZZZ_MF_T(4, false) : (M.nd == 10 ? ZZZ_MF_T(10, false) : ZZZ_MF_T(20, false));
+  }
   else
-    rc = diag ? ZZZ_MF_T(20, true) : ZZZ_MF_T(20, false);
+  {
+    if (M.nd == 4)
+      rc = diag ? ZZZ_MF_T(4, true) : ZZZ_MF_T(4, false);
+    else if (M.nd == 10)
+      rc = diag ? ZZZ_MF_T(10, true) : ZZZ_MF_T(10, false);
+    else
+      rc = diag ? ZZZ_MF_T(20, true) : ZZZ_MF_T(20, false);
+  }
 #undef ZZZ_MF_T
   if (rc)
     return rc;
   if (M.nshared > 0)
-    hipLaunchKernelGGL(k_mf_finish, dim3(gf), dim3(256), 0, ctx->stream, M.sh_dof.p, M.sh_off.p, M.sh_flag.p, M.nshared, M.ypart.p, u,
-                       y, partials ? partials + grid : nullptr, A.stop, diag ? 1.0 : 0.0);
+    hipLaunchKernelGGL(k_mf_finish<R>, dim3(gf), dim3(256), 0, ctx->stream, M.sh_dof.p, M.sh_off.p, M.sh_flag.p, M.nshared, A.ypart, u,
+                       y, partials ? partials + grid : nullptr, A.stop, (R)(diag ? 1.0 : 0.0));
   if (npartials)
     *npartials = grid + (M.nshared > 0 ? gf : 0);
   ZZZ_HIP(ctx, hipGetLastError());

@@ -1,0 +1,194 @@
+// Per-cell arithmetic of the matrix-free action (zzz_matfree.hip) and the rounding rules of its single-precision value
+// arrays, generic over the scalar R as src/cgpoisson_problem.cpp:28 (`using T = PetscScalar`) makes the reference's.
+// Host-compilable (as zzz_pmg.h is): a stand-alone program runs the same code on the CPU under the sanitizers.
+//   * geometry factors, reference tables: computed in double, then rounded once (mf_round);
+//   * P1 coordinates: NOT absolute.  The Jacobian is a difference of coordinates; formed from rounded absolute values its
+//     relative error is eps32 / h and grows with the mesh.  The float copy holds every coordinate relative to an origin of
+//     its cell block, subtracted in double (mf_rel_coord): the float differences carry the block's extent, not the domain's.
+#pragma once
+#include <cmath>
+#include <cstdint>
+
+#include "element_tables.inc"
+
+#if !defined(ZZZ_HD)
+#if defined(__HIPCC__)
+#define ZZZ_HD __host__ __device__
+#else
+#define ZZZ_HD
+#endif
+#endif
+
+// Float on the device: an empty asm statement that takes the table offset together with the values just formed makes the
+// next phase's table reads depend on this phase's results, so the scheduler cannot hoist them all to the top (it filled
+// every register the launch bound allows with hoisted reads and the allocator then spilled)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define ZZZ_MF_YE4(i) "+v"(ye[i]), "+v"(ye[i + 1]), "+v"(ye[i + 2]), "+v"(ye[i + 3])
+#define ZZZ_MF_FENCE_G() asm volatile("" : "+v"(off), "+v"(g[0]), "+v"(g[1]), "+v"(g[2]))
+#define ZZZ_MF_FENCE_Y()                                                                                                \
+  do                                                                                                                    \
+  {                                                                                                                     \
+    if constexpr (ND == 20)                                                                                             \
+      asm volatile("" : "+v"(off), ZZZ_MF_YE4(0), ZZZ_MF_YE4(4), ZZZ_MF_YE4(8), ZZZ_MF_YE4(12), ZZZ_MF_YE4(16));         \
+    else                                                                                                                \
+      asm volatile("" : "+v"(off), ZZZ_MF_YE4(0), ZZZ_MF_YE4(4), "+v"(ye[ND - 2]), "+v"(ye[ND - 1]));                    \
+  } while (0)
+#else
+#define ZZZ_MF_FENCE_G() ((void)0)
+#define ZZZ_MF_FENCE_Y() ((void)0)
+#endif
+// where the statement stands: 1 after every mode, 2 (default) also between a mode's two phases -- 118 against 92 registers at
+// P3, 4 against 5 wavefronts per SIMD; a build-time switch for A/B runs (-DZZZ_MF_FENCE_MODE=1)
+#ifndef ZZZ_MF_FENCE_MODE
+#define ZZZ_MF_FENCE_MODE 2
+#endif
+
+namespace zzz
+{
+template <typename R>
+ZZZ_HD inline R mf_round(double v)
+{
+  return (R)v;
+}
+template <typename R>
+ZZZ_HD inline R mf_rel_coord(double x, double origin)
+{
+  return (R)(x - origin);
+}
+
+// The factorised tables: constexpr copies decide at compile time which entries are zero; the values are staged in LDS
+// by every (persistent) workgroup and reach the multiply-adds as broadcast reads.  (As literals they occupied ~200
+// vector registers of every lane; as scalar loads from constant memory the compiler hoisted them all and spilled 865
+// scalar registers; with the loads chained section by section through empty asm statements -- rows of the table as
+// scalar operands, no LDS traffic for them -- the kernel still spilled 410 scalar registers into vector lanes and was
+// 3 % faster at P3 6.2 M dofs, 0.281 against 0.291 ms, 1 % at P2: measured in round 4, not kept.)
+template <int ND>
+struct MfTab;
+template <>
+struct MfTab<10>
+{
+  static constexpr int NQ = 4;
+  static constexpr bool nz(int a, int q, int j) { return ZZZ_DTAB_P2[(a * 4 + q) * 10 + j] != 0.0; }
+};
+template <>
+struct MfTab<20>
+{
+  static constexpr int NQ = 10;
+  static constexpr bool nz(int a, int q, int j) { return ZZZ_DTAB_P3[(a * 10 + q) * 20 + j] != 0.0; }
+};
+
+// y_e = sum_q sum_a D_a[q][:]^T h_a(q),  h(q) = G g(q),  g_a(q) = D_a[q][:] . u_e -- mode q by mode q, so that only u_e,
+// y_e and six scalars are live.  A table entry is READ TWICE, once for each of its uses, the second time from a second
+// copy of the table laid out for that use ([q][j][a]; the compiler cannot tell that the two are equal): kept in
+// registers between the uses, the ~39 entries of a mode cost 78 vector registers, 220 in all, two wavefronts per SIMD.  Multiply-adds are fused here (the library is otherwise built with
+// -ffp-contract=off): the action is compared with the oracle to a tolerance, not bit for bit.
+template <int ND, typename R>
+ZZZ_HD inline void mf_element_pk(const R* __restrict__ tab, const R* __restrict__ tabT, const R (&ue)[ND], const R (&G)[6],
+                                 R (&ye)[ND])
+{
+#pragma clang fp contract(fast)
+  constexpr int NQ = MfTab<ND>::NQ;
+  [[maybe_unused]] int off = 0; // (always 0: see ZZZ_MF_FENCE_G / _Y above)
+#pragma unroll
+  for (int j = 0; j < ND; ++j)
+    ye[j] = 0.0;
+#pragma unroll
+  for (int q = 0; q < NQ; ++q)
+  {
+    R g[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+    {
+      R acc = 0.0;
+#pragma unroll
+      for (int j = 0; j < ND; ++j)
+        if (MfTab<ND>::nz(a, q, j))
+          acc += (sizeof(R) == 4 ? tab[off + (a * NQ + q) * ND + j] : tab[(a * NQ + q) * ND + j]) * ue[j];
+      g[a] = acc;
+    }
+    if constexpr (sizeof(R) == 4 && ZZZ_MF_FENCE_MODE >= 2)
+      ZZZ_MF_FENCE_G();
+    const R h0 = G[0] * g[0] + G[3] * g[1] + G[4] * g[2];
+    const R h1 = G[3] * g[0] + G[1] * g[1] + G[5] * g[2];
+    const R h2 = G[4] * g[0] + G[5] * g[1] + G[2] * g[2];
+#pragma unroll
+    for (int j = 0; j < ND; ++j)
+    {
+      if (MfTab<ND>::nz(0, q, j))
+        ye[j] += (sizeof(R) == 4 ? tabT[off + (q * ND + j) * 3 + 0] : tabT[(q * ND + j) * 3 + 0]) * h0;
+      if (MfTab<ND>::nz(1, q, j))
+        ye[j] += (sizeof(R) == 4 ? tabT[off + (q * ND + j) * 3 + 1] : tabT[(q * ND + j) * 3 + 1]) * h1;
+      if (MfTab<ND>::nz(2, q, j))
+        ye[j] += (sizeof(R) == 4 ? tabT[off + (q * ND + j) * 3 + 2] : tabT[(q * ND + j) * 3 + 2]) * h2;
+    }
+    if constexpr (sizeof(R) == 4 && ZZZ_MF_FENCE_MODE >= 1)
+      ZZZ_MF_FENCE_Y();
+  }
+}
+
+// P2/P3: G = |detJ| K K^T of one cell from its four vertices, in double (the float action reads it rounded: mf_round);
+// G = {G00, G11, G22, G01, G02, G12}
+ZZZ_HD inline void mf_cell_geom(const double (&p)[4][3], double (&G)[6])
+{
+  double J[3][3];
+  for (int a = 0; a < 3; ++a)
+    for (int al = 0; al < 3; ++al)
+      J[a][al] = p[al + 1][a] - p[0][a];
+  // K = J^-1 = C / det, K[al][a] = dX_al / dx_a
+  double C[3][3];
+  C[0][0] = J[1][1] * J[2][2] - J[1][2] * J[2][1];
+  C[0][1] = J[0][2] * J[2][1] - J[0][1] * J[2][2];
+  C[0][2] = J[0][1] * J[1][2] - J[0][2] * J[1][1];
+  C[1][0] = J[1][2] * J[2][0] - J[1][0] * J[2][2];
+  C[1][1] = J[0][0] * J[2][2] - J[0][2] * J[2][0];
+  C[1][2] = J[0][2] * J[1][0] - J[0][0] * J[1][2];
+  C[2][0] = J[1][0] * J[2][1] - J[1][1] * J[2][0];
+  C[2][1] = J[0][1] * J[2][0] - J[0][0] * J[2][1];
+  C[2][2] = J[0][0] * J[1][1] - J[0][1] * J[1][0];
+  const double det = J[0][0] * C[0][0] + J[0][1] * C[1][0] + J[0][2] * C[2][0];
+  const double sc = 1.0 / std::fabs(det); // |det| K K^T = C C^T / |det|
+  const int pa[6] = {0, 1, 2, 0, 0, 1}, pb[6] = {0, 1, 2, 1, 2, 2};
+  for (int t = 0; t < 6; ++t)
+    G[t] = (C[pa[t]][0] * C[pb[t]][0] + C[pa[t]][1] * C[pb[t]][1] + C[pa[t]][2] * C[pb[t]][2]) * sc;
+}
+
+// P1: p_k = {x, y, z, u} of vertex k.  J[a][al] = p_(al+1)[a] - p_0[a]; C = cofactors: K = J^-1 = C / det,
+// grad phi_(al+1) = C[al][:] / det;  y_e = c (c^T u) / (6 |det J|).  DIAG: the element matrix's diagonal instead.
+template <typename R>
+struct MfPoint
+{
+  R x, y, z, w;
+};
+template <bool DIAG, typename R>
+ZZZ_HD inline void mf_element_p1(const MfPoint<R>& p0, const MfPoint<R>& p1, const MfPoint<R>& p2, const MfPoint<R>& p3, R (&ye)[4])
+{
+#pragma clang fp contract(fast)
+  const R J00 = p1.x - p0.x, J01 = p2.x - p0.x, J02 = p3.x - p0.x;
+  const R J10 = p1.y - p0.y, J11 = p2.y - p0.y, J12 = p3.y - p0.y;
+  const R J20 = p1.z - p0.z, J21 = p2.z - p0.z, J22 = p3.z - p0.z;
+  const R C00 = J11 * J22 - J12 * J21, C01 = J02 * J21 - J01 * J22, C02 = J01 * J12 - J02 * J11;
+  const R C10 = J12 * J20 - J10 * J22, C11 = J00 * J22 - J02 * J20, C12 = J02 * J10 - J00 * J12;
+  const R C20 = J10 * J21 - J11 * J20, C21 = J01 * J20 - J00 * J21, C22 = J00 * J11 - J01 * J10;
+  const R det = J00 * C00 + J01 * C10 + J02 * C20;
+  const R d1 = p1.w - p0.w, d2 = p2.w - p0.w, d3 = p3.w - p0.w;
+  const R sc = (R)1.0 / ((R)6.0 * std::fabs(det));
+  if constexpr (DIAG)
+  {
+    const R s0 = C00 + C10 + C20, s1 = C01 + C11 + C21, s2 = C02 + C12 + C22;
+    ye[0] = (s0 * s0 + s1 * s1 + s2 * s2) * sc;
+    ye[1] = (C00 * C00 + C01 * C01 + C02 * C02) * sc;
+    ye[2] = (C10 * C10 + C11 * C11 + C12 * C12) * sc;
+    ye[3] = (C20 * C20 + C21 * C21 + C22 * C22) * sc;
+  }
+  else
+  {
+    const R t0 = (C00 * d1 + C10 * d2 + C20 * d3) * sc;
+    const R t1 = (C01 * d1 + C11 * d2 + C21 * d3) * sc;
+    const R t2 = (C02 * d1 + C12 * d2 + C22 * d3) * sc;
+    ye[1] = C00 * t0 + C01 * t1 + C02 * t2;
+    ye[2] = C10 * t0 + C11 * t1 + C12 * t2;
+    ye[3] = C20 * t0 + C21 * t1 + C22 * t2;
+    ye[0] = -(ye[1] + ye[2] + ye[3]);
+  }
+}
+} // namespace zzz

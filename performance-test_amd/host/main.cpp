@@ -111,6 +111,9 @@ struct Options
   // poisson only: "assembled" = the reference's path (AIJ matrix, MatMult); "matfree" = KSPCG + PCJACOBI on the matrix-free
   // operator of cgpoisson: no matrix, the diagonal from the element matrices (an extension; faster from P2 up)
   std::string op = "assembled";
+  // cgpoisson only: the reference's scalar is PetscScalar (src/cgpoisson_problem.cpp:28); "float32" runs the action and
+  // linalg::cg as a single-precision PETSc build would (zzz_cg_solve_f32), one GPU
+  std::string scalar_type = "float64";
   // u0 == bc_value at every constrained dof (all components for elasticity); absent = 0 = the reference's u0: no upload
   bool have_bc_value = false;
   double bc_value = 0.0;
@@ -149,6 +152,8 @@ void usage()
                "  --allreduce arg (=peer)         peer (xGMI peer-memory mailboxes, else falls back) | comm\n"
                "  --operator arg (=assembled)     poisson: assembled (the AIJ matrix) | matfree (KSPCG on the matrix-free\n"
                "                                  operator, Jacobi from the element matrices' diagonals; no matrix)\n"
+               "  --scalar_type arg (=float64)    float64 | float32 (cgpoisson on one GPU: action and linalg::cg in single\n"
+               "                                  precision, as the reference built on a single-precision PETSc)\n"
                "  --bc_value arg (=0)             value of u0 at every Dirichlet dof (the reference's u0 is 0); non-zero: the\n"
                "                                  vector assembly lifts it (apply_lifting, bc->set)\n"
                "PETSc-style solver options honoured: -ksp_type {cg,pipecg} -pc_type {jacobi,none,chebyshev_jacobi,mg,pmg} -ksp_rtol -ksp_atol\n"
@@ -205,6 +210,8 @@ Options parse(int argc, char** argv)
         o.allreduce = value(i, arg, key);
       else if (key == "operator")
         o.op = value(i, arg, key);
+      else if (key == "scalar_type")
+        o.scalar_type = value(i, arg, key);
       else if (key == "bc_value")
       {
         o.bc_value = std::stod(value(i, arg, key));
@@ -487,6 +494,8 @@ void run_rank(Shared& S, std::barrier<>& bar, int rank)
     std::cout << "  petsc version:   n/a (own CSR + CG on HIP/RCCL)" << std::endl;
     std::cout << "  Problem type:    " << o.problem_type << std::endl;
     std::cout << "  Scaling type:    " << o.scaling_type << std::endl;
+    if (o.scalar_type == "float32")
+      std::cout << "  Scalar type:     float32" << std::endl;
     std::cout << "  Num processes:   " << S.nranks << std::endl;
     std::cout << "  Num cells:       " << S.num_cells << count_suffix(S.num_cells) << std::endl;
     std::cout << "  Total degrees of freedom:               " << S.num_dofs << count_suffix(S.num_dofs) << std::endl;
@@ -546,7 +555,10 @@ void run_rank(Shared& S, std::barrier<>& bar, int rank)
           S.tplan[rank] = tplan.stop();
         }
         Timer tcg("cg");
-        ZCK(ctx, zzz_cg_solve(ctx, &so, &S.iters[rank], rn));
+        if (o.scalar_type == "float32")
+          ZCK(ctx, zzz_cg_solve_f32(ctx, &so, &S.iters[rank], rn));
+        else
+          ZCK(ctx, zzz_cg_solve(ctx, &so, &S.iters[rank], rn));
         ZCK(ctx, zzz_sync(ctx));
         S.tcg[rank] = tcg.stop();
         S.rnorm[rank] = rn[0];
@@ -688,6 +700,15 @@ void solve(int argc, char** argv)
     throw std::runtime_error("Scaling type '" + o.scaling_type + "` unknown"); // src/main.cpp:115
   if (o.problem_type != "poisson" && o.problem_type != "cgpoisson" && o.problem_type != "elasticity")
     throw std::runtime_error("Unknown problem type: " + o.problem_type); // src/main.cpp:170
+  if (o.scalar_type != "float64" && o.scalar_type != "float32")
+    throw std::runtime_error("--scalar_type " + o.scalar_type + ": float64 or float32");
+  if (o.scalar_type == "float32" && o.problem_type != "cgpoisson")
+    throw std::runtime_error("--scalar_type float32 applies to --problem_type cgpoisson only (the assembled path, KSPCG and "
+                             "elasticity run in float64)");
+  if (o.scalar_type == "float32" && o.ngpus != 1)
+    throw std::runtime_error("--scalar_type float32: --ngpus 1 only (the float32 halo exchange and all-reduce are not built)");
+  if (o.scalar_type == "float32" && o.have_bc_value)
+    throw std::runtime_error("--scalar_type float32: not with --bc_value (the lifted right-hand side is not formed in float32)");
   // src/main.cpp:131-141: "cube", anything else is the unstructured (spoke) mesh
   if (o.ksp_type != "cg" && o.ksp_type != "pipecg")
     throw std::runtime_error("-ksp_type " + o.ksp_type + ": only cg and pipecg are built");

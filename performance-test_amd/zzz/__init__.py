@@ -32,6 +32,7 @@ ABI_SYMBOLS = [
     "zzz_profile_get", "zzz_cg_info", "zzz_internal_order_download", "zzz_global_ids_upload", "zzz_global_ids_download", "zzz_ghost_layer_build", "zzz_local_sizes", "zzz_spmv_info", "zzz_comm_load", "zzz_comm_library_path", "zzz_comm_info", "zzz_comm_unique_id", "zzz_comm_init", "zzz_halo_upload", "zzz_local_group_create",
     "zzz_local_group_destroy", "zzz_local_group_abort", "zzz_comm_init_local", "zzz_comm_init_peer_only", "zzz_comm_p2p_export", "zzz_comm_p2p_attach", "zzz_comm_p2p_disable", "zzz_comm_p2p_enable", "zzz_comm_p2p_halo",
     "zzz_mg_setup", "zzz_mg_info", "zzz_mg_apply", "zzz_mg_transfer",
+    "zzz_action_f32", "zzz_action_time_f32", "zzz_matfree_info_f32", "zzz_cg_solve_f32",
 ]
 HOST_SYMBOLS = [
     "zzzh_num_pdofs", "zzzh_num_entities", "zzzh_mesh_size", "zzzh_count_suffix", "zzzh_part_create", "zzzh_part_create_native", "zzzh_part_create_spoke", "zzzh_part_create_spoke_part", "zzzh_spoke_size", "zzzh_part_destroy", "zzzh_part_global_verts",
@@ -78,6 +79,7 @@ _HOST = None
 _i32p = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
 _i64p = np.ctypeslib.ndpointer(np.int64, flags="C_CONTIGUOUS")
 _f64p = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
+_f32p = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
 
 
 def hip():
@@ -144,6 +146,11 @@ def hip():
         L.zzz_comm_p2p_disable.argtypes = [C.c_void_p]
         L.zzz_comm_p2p_enable.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         L.zzz_halo_upload.argtypes = [C.c_void_p, C.c_int, _i32p, _i64p, _i32p, _i64p]
+        if hasattr(L, "zzz_action_f32"):  # (ZZZ_HIP_LIB may name a build from before the float32 path: the A/B tools)
+            L.zzz_action_f32.argtypes = [C.c_void_p, _f32p, _f32p]
+            L.zzz_action_time_f32.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double)]
+            L.zzz_matfree_info_f32.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+            L.zzz_cg_solve_f32.argtypes = [C.c_void_p, C.POINTER(SolverOpts), C.POINTER(C.c_int), C.POINTER(C.c_double)]
         _HIP = L
     return _HIP
 
@@ -559,6 +566,33 @@ class Context:
         ms = C.c_double()
         self._ck(self.L.zzz_action_time(self.h, reps, C.byref(ms)))
         return ms.value
+
+    def action_f32(self, x):
+        """y = action(x) in float32 (zzz_action_f32): float32 in, float32 out"""
+        x = np.ascontiguousarray(x, np.float32)
+        y = np.zeros_like(x)
+        self._ck(self.L.zzz_action_f32(self.h, x, y))
+        return y
+
+    def action_time_f32(self, reps=20):
+        ms = C.c_double()
+        self._ck(self.L.zzz_action_time_f32(self.h, reps, C.byref(ms)))
+        return ms.value
+
+    def matfree_info_f32(self):
+        a = (C.c_int64 * 4)()
+        self._ck(self.L.zzz_matfree_info_f32(self.h, a))
+        return dict(zip(("built", "bytes_per_action", "lds_bytes", "workgroups_per_cu"), [int(v) for v in a]))
+
+    def cg_solve_f32(self, variant=CG_CGH, pc=PC_NONE, op=OP_MATFREE, rtol=1e-6, max_it=100, single_reduction=False,
+                     error_if_not_converged=False):
+        """linalg::cg in float32 on the float32 action (zzz_cg_solve_f32); returns (iterations, <r,r>, <r0,r0>)"""
+        o = SolverOpts(variant, pc, NORM_PRECONDITIONED, op, max_it, 0, 1 if single_reduction else 0,
+                       1 if error_if_not_converged else 0, rtol, 1e-50, 0.0, 0, 0, 0.0, 0, 0)
+        it = C.c_int()
+        rn = (C.c_double * 2)()
+        self._ck(self.L.zzz_cg_solve_f32(self.h, C.byref(o), C.byref(it), rn))
+        return it.value, rn[0], rn[1]
 
     def cg_solve(self, variant=CG_PETSC, pc=PC_JACOBI, norm=NORM_PRECONDITIONED, op=OP_CSR, rtol=1e-8, atol=1e-50,
                  max_it=10000, profile=False, single_reduction=False, dtol=0.0, error_if_not_converged=False,
