@@ -365,6 +365,8 @@ int zzz_matfree_info_f32(zzz_ctx* ctx, int64_t info[4]);
  * node pushed through its cell's affine map), orthonormalised in basis order as la::orthonormalize does, checked as
  * la::is_orthonormal does (error "Space not orthonormal" otherwise; *max_deviation = largest |<x_i,x_j> - delta_ij|).
  * Inner products over the owned entries, summed over the ranks (collective with a communicator attached).  The
+ * rotations are taken about the centre of the dofs: the same basis in exact arithmetic, and no digits lost to the
+ * projection on a mesh far from the origin.  The
  * reference passes the basis to MatSetNearNullSpace for GAMG; Jacobi-CG does not consume it. */
 int zzz_near_nullspace_build(zzz_ctx* ctx, double* max_deviation);
 /* mode k (0..5) of that basis, owned part, 3 * n_owned entries in the caller's numbering */

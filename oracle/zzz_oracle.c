@@ -400,6 +400,25 @@ static void facet_table(const basis_t* B, int deg, int lf, qtab_t* T)
         X[d] = q0[d] + s * (q1[d] - q0[d]) + t * (q2[d] - q0[d]);
       T->w[q] = (double)(wu[a] * wv[b] * (1 - xu[a]));
       basis_eval(B, X, T->phi[q], NULL);
+      /* A Lagrange function whose node is not on the facet vanishes on it identically; evaluated through the monomial
+       * coefficients it comes out as ~1e-20 instead, and g * 1e-20 * |n| is no longer small next to an entry of b whose
+       * own terms are tiny (f spans eleven decades; a facet of area 2^20 on an anisotropic mesh): tests/test_hp_ref.py.
+       * Vertex v is on facet lf unless v == lf, an edge if both its vertices are, of the face nodes only lf's own. */
+      {
+        const int npe = B->order - 1;
+        int n = 0;
+        for (int v = 0; v < 4; ++v, ++n)
+          if (v == lf)
+            T->phi[q][n] = 0.0;
+        for (int e = 0; e < 6; ++e)
+          for (int s2 = 0; s2 < npe; ++s2, ++n)
+            if (EDGE_V[e][0] == lf || EDGE_V[e][1] == lf)
+              T->phi[q][n] = 0.0;
+        if (B->order == 3)
+          for (int f = 0; f < 4; ++f, ++n)
+            if (f != lf)
+              T->phi[q][n] = 0.0;
+      }
     }
   T->nq = q;
 }
@@ -1731,14 +1750,22 @@ void zo_set_num_threads(int n)
 /* build_near_nullspace, src/elasticity_problem.cpp:36-94: basis[k] (k < 3) = 1 in component k; rotations
  * x3 = (-x1, x0, 0), x4 = (x2, 0, -x0), x5 = (0, -x2, x1) at the dof coordinates (:56-71); la::orthonormalize
  * [EXT: dolfinx/la/utils.h]: for i: for k < i: x_i -= <x_i, x_k> x_k; x_i /= |x_i| (:74-75); la::is_orthonormal (:76-81):
- * returns the largest |<x_i, x_j> - delta_ij|.  B: [6][3 n], row-major.  One rank: all entries are owned. */
+ * returns the largest |<x_i, x_j> - delta_ij|.  B: [6][3 n], row-major.  One rank: all entries are owned.
+ * [EXT] The coordinates are taken from the centre of the dofs: the span and, in exact arithmetic, the orthonormalised
+ * basis are those of the rotations about the origin (the translations are projected out of them first), but far from
+ * the origin that projection cancels -- at 65 536 it left five digits fewer (tests/test_gpu_hostile_geometry.py). */
 double zo_near_nullspace(i64 n, const double* dof_x, double* B)
 {
   const i64 ld = 3 * n;
+  double c[3] = {0.0, 0.0, 0.0};
   memset(B, 0, sizeof(double) * (size_t)(6 * ld));
+  for (i64 i = 0; i < 3 * n; ++i)
+    c[i % 3] += dof_x[i];
+  for (int a = 0; a < 3; ++a)
+    c[a] /= (double)n;
   for (i64 i = 0; i < n; ++i)
   {
-    const double x0 = dof_x[3 * i], x1 = dof_x[3 * i + 1], x2 = dof_x[3 * i + 2];
+    const double x0 = dof_x[3 * i] - c[0], x1 = dof_x[3 * i + 1] - c[1], x2 = dof_x[3 * i + 2] - c[2];
     for (int k = 0; k < 3; ++k)
       B[k * ld + 3 * i + k] = 1.0;
     B[3 * ld + 3 * i + 0] = -x1;

@@ -1,6 +1,6 @@
 // `ZZZ Create near-nullspace` (src/elasticity_problem.cpp:36-94, called at :233-244): the six rigid-body modes of the
 // vector-valued space as la::Vector basis -- translations e_0, e_1, e_2 and the rotations (-x1, x0, 0), (x2, 0, -x0),
-// (0, -x2, x1) at the dof coordinates -- orthonormalised by la::orthonormalize (modified Gram-Schmidt in basis order:
+// (0, -x2, x1) at the dof coordinates ([EXT] taken from the centre of the dofs, see below) -- orthonormalised by la::orthonormalize (modified Gram-Schmidt in basis order:
 // x_i -= <x_i, x_k> x_k for k < i, then x_i /= |x_i|; inner products over the OWNED entries, summed over the ranks) and
 // checked with la::is_orthonormal ("Space not orthonormal" otherwise).  The reference hands the result to
 // MatSetNearNullSpace for GAMG; with Jacobi-CG nothing consumes it, the phase is built for the surface and for parity.
@@ -194,6 +194,27 @@ int zzz_near_nullspace_build(zzz_ctx* ctx, double* max_deviation)
   const int gb = (int)std::min<int64_t>((nblock + 255) / 256, 4096), gv = (int)std::min<int64_t>((ld + 255) / 256, 4096);
   hipLaunchKernelGGL(k_nn_modes, dim3(gb), dim3(256), 0, s, dofx.p, nblock, B, ld);
   ZZZ_HIP(ctx, hipGetLastError());
+  // [EXT] turn about the centre c of the owned dofs (all ranks), not about the origin: x_3 += c1 e_0 - c0 e_1 and so on.  The
+  // span is the same and so, in exact arithmetic, is the orthonormalised basis, since the translations are projected out
+  // of the rotations first.  In doubles that projection cancels: on a mesh 65 536 away from the origin a rotation about
+  // the origin is a translation up to 1.5e-5 of its size, and what was left of it had lost five digits.
+  {
+    double cnt = 0.0, c[3];
+    if (int rc = nn_dot(ctx, B, B, nown, parts, &cnt))
+      return rc;
+    for (int a = 0; a < 3; ++a)
+    {
+      if (int rc = nn_dot(ctx, dofx.p, B + a * ld, nown, parts, &c[a]))
+        return rc;
+      c[a] /= cnt;
+    }
+    const int T[3][2] = {{0, 1}, {2, 0}, {1, 2}}; // x_{3+r} = -x[T[r][1]] e_{T[r][0]} + x[T[r][0]] e_{T[r][1]}
+    for (int r = 0; r < 3; ++r)
+    {
+      hipLaunchKernelGGL(k_nn_axpy, dim3(gv), dim3(256), 0, s, c[T[r][1]], B + T[r][0] * ld, B + (3 + r) * ld, ld);
+      hipLaunchKernelGGL(k_nn_axpy, dim3(gv), dim3(256), 0, s, -c[T[r][0]], B + T[r][1] * ld, B + (3 + r) * ld, ld);
+    }
+  }
   // la::orthonormalize
   for (int i = 0; i < 6; ++i)
   {

@@ -1,0 +1,183 @@
+"""Hostile geometries for the parity tests: TEST INFRASTRUCTURE ONLY.
+
+The base is the oracle's cube (zo.Problem): mesh, dofmap, Dirichlet set, coefficients, exterior facets.  Vertices, dofs
+and cells are shuffled with a fixed seed, so that the library's internal orders have something to undo; a case then maps
+the vertex coordinates and leaves everything else alone (Dirichlet set, facets and coefficients are inputs).  Every case
+is a valid mesh: the maps are injective and no cell degenerates.
+
+reference(case) is the one mp pass per (case, order) that the matrix, vector, action and diagonal tests share
+(tests/_hp_ref.py), with the oracle's values on the same input next to it.
+"""
+import numpy as np
+
+import _hp_ref as hp
+import zzz_oracle as zo
+
+BASE = {1: (6, 5, 5), 2: (4, 4, 5), 3: (3, 3, 4)}
+SEED = 20240611
+
+
+def _rotation():
+    """a fixed generic rotation: angle 0.7 about (1, 2, 3) (Rodrigues)"""
+    k = np.array([1.0, 2.0, 3.0]) / np.sqrt(14.0)
+    Kx = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    return np.eye(3) + np.sin(0.7) * Kx + (1 - np.cos(0.7)) * Kx @ Kx
+
+
+def _shear50(x, xi):
+    y = x.copy()
+    y[:, 0] += 50.0 * x[:, 1]
+    return y
+
+
+def _mirror(x, xi):
+    y = x.copy()
+    y[:, 0] = 1.0 - x[:, 0]
+    return y
+
+
+# name -> (map(x, xi) -> x', dims of the P1 base when they are not BASE[1])
+MAPS = {
+    "identity": (lambda x, xi: x.copy(), None),
+    "offset": (lambda x, xi: x + np.array([1024.0, -4096.0, 65536.0]), None),
+    "aniso": (lambda x, xi: x * np.array([2.0 ** 20, 1.0, 2.0 ** -20]), None),
+    "needle": (lambda x, xi: x * np.array([1.0, 2.0 ** -12, 2.0 ** -12]), None),
+    "needle_line": (lambda x, xi: x * np.array([1.0, 2.0 ** -12, 2.0 ** -12]), (30, 1, 1)),
+    "graded": (lambda x, xi: x ** 3, None),
+    "graded_corner": (lambda x, xi: x ** 6, (12, 10, 10)),
+    "graded_corner_16": (lambda x, xi: x ** 8, (16, 14, 14)),  # the one whose default plan has to halve its blocks
+    "mirror": (_mirror, None),
+    "mirror_axes": (lambda x, xi: np.ascontiguousarray(_mirror(x, xi)[:, [2, 0, 1]]), None),
+    "noise13": (lambda x, xi: x * (1.0 + 1e-13 * xi), None),
+    "noise10": (lambda x, xi: x + 3e-10 * xi, None),
+    "noise7": (lambda x, xi: x + 1e-7 * xi, None),
+    "rotated": (lambda x, xi: x @ _rotation().T, None),
+    "shear50_a": (_shear50, None),          # ny = 5: (nx+1)(ny+1) x (ny+1) x (nz+1) lines <= 8 nv -- passes for a lattice
+    "shear50_b": (_shear50, (6, 9, 5)),     # ny = 9: ny + 1 > 8 -- a point cloud
+}
+P1_CASES = list(MAPS)
+P2_CASES = ["aniso", "graded", "mirror", "shear50_a", "noise10"]
+P3_CASES = ["offset", "graded", "mirror", "shear50_a"]
+POISSON_CASES = [(n, 1) for n in P1_CASES] + [(n, 2) for n in P2_CASES] + [(n, 3) for n in P3_CASES]
+ELASTICITY_CASES = ["offset", "aniso", "mirror", "shear50_a", "noise10"]
+SOLVE_CASES = ("identity", "offset", "graded", "mirror", "mirror_axes", "noise13", "noise10", "noise7", "rotated")
+# the kind of internal order the code fixes for a case (1: lattice, 0: the caller's, or 2 when the bins are asked for)
+KIND_LATTICE = ("identity", "offset", "aniso", "needle", "needle_line", "graded", "graded_corner", "graded_corner_16", "noise13")
+KIND_CLOUD = ("noise7", "rotated")
+
+
+class Case:
+    pass
+
+
+_CASES = {}
+
+
+def case(name, order, problem="poisson"):
+    key = (name, order, problem)
+    if key in _CASES:
+        return _CASES[key]
+    fmap, dims = MAPS[name]
+    dims = dims if (dims is not None and order == 1) else BASE[order]
+    zo.set_num_threads(1)
+    O = zo.Problem(problem, order, *dims)
+    rng = np.random.default_rng(SEED + 97 * order)
+    nv, nb, nc = O.x.shape[0], O.nblock, O.cells.shape[0]
+    pv, pd, pc = rng.permutation(nv), rng.permutation(nb), rng.permutation(nc)
+    xi = rng.standard_normal(O.x.shape)
+    C = Case()
+    C.name, C.order, C.problem, C.dims, C.bs, C.form, C.nblock = name, order, problem, dims, O.bs, O.form, nb
+    C.n = nb * O.bs
+    x0 = np.zeros_like(O.x)
+    x0[pv] = O.x  # vertex v is now called pv[v]
+    C.x_base = x0
+    C.x = np.ascontiguousarray(fmap(x0, xi), dtype=np.float64)
+    C.cells = np.ascontiguousarray(pv[O.cells][pc].astype(np.int32))
+    C.cell_dofs = np.ascontiguousarray(pd[O.cell_dofs][pc].astype(np.int32))
+    sd = (pd[:, None] * O.bs + np.arange(O.bs)).reshape(-1)  # scalar dof d is now called sd[d]
+    C.bc = np.zeros_like(O.bc)
+    C.bc[sd] = O.bc
+    C.f = np.zeros_like(O.f)
+    C.f[sd] = O.f
+    if problem == "poisson":
+        C.g = np.zeros_like(O.g)
+        C.g[sd] = O.g
+        C.facets = zo.exterior_facets(C.cells)
+    else:
+        C.g, C.facets = None, None
+    dof_x = np.zeros_like(O.dof_x)
+    dof_x[pd] = O.dof_x
+    C.dof_x_base = dof_x
+    C.rowptr, C.cols = zo.pattern(nb, C.cell_dofs, O.bs)
+    _CASES[key] = C
+    return C
+
+
+def oracle(C):
+    """the oracle's A and b on the case's input (one thread: the serial sums)"""
+    if not hasattr(C, "ov"):
+        zo.set_num_threads(1)
+        C.ov = zo.assemble_matrix(C.form, C.order, C.x, C.cells, C.cell_dofs, C.bc, C.rowptr, C.cols)
+        C.ob = zo.assemble_vector(C.form, C.order, C.x, C.cells, C.cell_dofs, C.f, C.g, C.facets, C.bc)
+    return C.ov, C.ob
+
+
+def reference(C):
+    """dict of the mp pass of a Poisson case: R, S (unconstrained), Rc, Sc (Dirichlet rows and columns applied), r, s
+    (b, constrained entries exactly zero), the oracle's unconstrained matrix ou and its figures against the reference"""
+    key = (C.name, C.order)
+    if key in hp.CACHE:
+        return hp.CACHE[key]
+    assert C.problem == "poisson"
+    R, S = hp.matrix(C.order, C.x, C.cells, C.cell_dofs, C.rowptr, C.cols)
+    r, s = hp.vector(C.order, C.x, C.cells, C.cell_dofs, C.f, C.g, C.facets, C.n)
+    bcb = C.bc.astype(bool)
+    r[bcb] = 0.0
+    s[bcb] = 0.0
+    Rc, Sc = hp.dirichlet(R, S, C.rowptr, C.cols, C.bc)
+    zo.set_num_threads(1)
+    ou = zo.assemble_matrix(C.form, C.order, C.x, C.cells, C.cell_dofs, np.zeros_like(C.bc), C.rowptr, C.cols)
+    ov, ob = oracle(C)
+    ref = dict(R=R, S=S, Rc=Rc, Sc=Sc, r=r, s=s, ou=ou,
+               oracle_A_free=hp.metric(ou, R, S) / hp.U, oracle_A=hp.metric(ov, Rc, Sc) / hp.U,
+               oracle_b=hp.metric(ob, r, s) / hp.U)
+    hp.CACHE[key] = ref
+    return ref
+
+
+def action_reference(C, u):
+    """(y, t, the oracle's figure) of y = A_unconstrained u, y[bc] = 0 (the matrix-free operator of cgpoisson)"""
+    ref = reference(C)
+    y, t = hp.apply(ref["R"], ref["S"], C.rowptr, C.cols, u)
+    bcb = C.bc.astype(bool)
+    y[bcb] = 0.0
+    t[bcb] = 0.0
+    oy = zo.action_poisson(C.order, C.x, C.cells, C.cell_dofs, C.bc, u)
+    return y, t, hp.metric(oy, y, t) / hp.U
+
+
+def diagonal_reference(C):
+    """(d, scale, the oracle's figure): the diagonal of the constrained matrix, 1.0 exactly on constrained rows"""
+    ref = reference(C)
+    d, sd = hp.diagonal(ref["Rc"], ref["Sc"], C.rowptr, C.cols)
+    od, _ = hp.diagonal(oracle(C)[0], ref["Sc"], C.rowptr, C.cols)
+    return d, sd, hp.metric(od, d, sd) / hp.U
+
+
+def plan_blocks(C, nc):
+    """The dofs that each block of nc cells of the matrix-free plan touches (csrc/zzz_matfree.hip, plan_attempt), restated:
+    centroids in 1024 bins of ONE resolution taken from the longest extent, bit-interleaved (x lowest), stable sort of the
+    cells in the caller's order, consecutive runs of nc.  Exact when the library keeps the caller's cell order."""
+    def spread(q):
+        r = np.zeros_like(q)
+        for b in range(10):
+            r |= ((q >> b) & 1) << (3 * b)
+        return r
+    lo, hi = C.x.min(0), C.x.max(0)
+    sc = (1024.0 / (hi - lo)).min()
+    xs = C.x[C.cells]
+    m = 0.25 * (xs[:, 0] + xs[:, 1] + xs[:, 2] + xs[:, 3])
+    q = np.clip(((m - lo) * sc).astype(np.int64), 0, 1023)
+    key = spread(q[:, 0]) | (spread(q[:, 1]) << 1) | (spread(q[:, 2]) << 2)
+    o = np.argsort(key, kind="stable")
+    return [len(np.unique(C.cell_dofs[o[b:b + nc]])) for b in range(0, len(o), nc)]
