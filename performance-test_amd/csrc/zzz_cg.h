@@ -1,6 +1,12 @@
-// What the CG translation units share (zzz_cg.hip: classical, single-reduction and Chebyshev-Jacobi forms;
-// zzz_cg_pipe.hip: the pipelined form): the vector kernels' launch shape and load policy, the coded inverse diagonal,
-// the partial-sum tree and the host helpers of a solve.  Not part of the ABI.
+// What the CG translation units share (zzz_cg.hip: classical, single-reduction, Chebyshev-Jacobi and multigrid forms;
+// zzz_cg_pipe.hip: the pipelined form; zzz_cg_f32.hip: linalg::cg in float): the vector kernels' launch shape and load
+// policy, the coded inverse diagonal, the partial-sum tree, and the host side every form's driver has in common --
+//   CgSolve          the skeleton of a solve: prologue (histories, CgState, profile events), the timing of the product,
+//                    the host's poll of the device state, and the epilogue (state read-back, iteration count, norms,
+//                    history, profile averages, KSPConvergedReason)
+//   cg_apply_csr     the product on the assembled operator, halo exchange included
+//   cg_report_reset  what zzz_cg_info says about a solve, at its "nothing special" values
+// Not part of the ABI.
 #pragma once
 #include "zzz_device.h"
 #include "zzz_internal.h"
@@ -121,14 +127,44 @@ struct EventRing
   hipEvent_t& operator[](int i) { return ev[i]; }
 };
 
+// The skeleton of one solve.  A driver keeps its own loop and launches and calls, in this order: begin() AFTER its
+// preconditioner's set-up (chebyshev_setup and mg_setup run a solve of their own through the same context) and before its
+// first stream operation; per iteration product_begin() / product_end() around the product and poll() at the end;
+// finish() behind its last launch.
+struct CgSolve
+{
+  // host polling: copy the state every CHECK iterations, look at it NSLOT-1 batches later
+  static constexpr int CHECK = 8, NSLOT = 4;
+  zzz_ctx* ctx = nullptr;
+  const zzz_solver_opts* o = nullptr;
+  int stride = PROF_STRIDE; // every stride-th product is timed (zzz_solver_opts.profile)
+  int max_prof = 0, nprof = 0, nchk = 0;
+  bool timed = false;
+  bool stop = false; // set by poll(): the device had stopped in the copy looked at
+  EventRing<NSLOT> chk_ev;
+
+  // beta_hist and dp_hist reserved (a form's other buffers are its own), CgState cleared on the stream, profile events
+  // made, halo-wait samples reset, polling events made
+  int begin(zzz_ctx* c, const zzz_solver_opts* opts, int prof_stride = PROF_STRIDE);
+  void product_begin(int it); // it: the loop's counter
+  int product_end(int rc);    // rc: the product's return code, handed back (prof_now is cleared either way)
+  int poll(int done);         // done: iterations enqueued so far
+  // behind the last launch: waits for the stream; last_iters, *iters, rnorm[0..1], the history, the profile's means,
+  // last_reason.  ZZZ_ERR_DIVERGED only under error_if_not_converged.
+  int finish(int* iters, double* rnorm);
+};
+
 // zzz_cg.hip
+// y = A x on the assembled operator, ghost values of x fetched first (overlapped with the interior tiles where the
+// partition allows); parts / np: the partials of <x,y> and, with dot_r, of <dot_r,x> and the test norm behind them
+int cg_apply_csr(zzz_ctx* ctx, double* x, double* y, double* parts, int* np, const double* dot_r = nullptr, int nn_is_rr = 0);
+void cg_report_reset(zzz_ctx* ctx); // last_pc_bound, last_solve_red_overlapped, last_solve_xdefer_k, last_solve_dinv_codes
 int dinv_codes_build(zzz_ctx* ctx, int64_t n, DinvCodes& dzc); // ctx->dinv as 16-bit codes (dzc.codes stays null: too many values)
 bool loop_exceeds_cache(zzz_ctx* ctx, int nvec);               // operator + nvec vectors against the Infinity Cache
 int vgrid(int64_t n);                                          // workgroups of a vector kernel over n entries
-int finish_reason(zzz_ctx* ctx, const zzz_solver_opts* o, const CgState& fin, int its);
+int cg_solve_pipe(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm); // zzz_cg_pipe.hip
 // the start-up kernels on the context's stream: ctx->dinv = 1 / diag(A) (jacobi) or 1; r = b, z = dinv r with the
 // partials of <r,z> and of the test norm
-int cg_solve_pipe(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm); // zzz_cg_pipe.hip
 void cg_launch_extract_dinv(zzz_ctx* ctx, int64_t n, int jacobi);
 void cg_launch_init_residual(zzz_ctx* ctx, double* z, int64_t n, int norm, double* pa, double* pb);
 } // namespace zzz

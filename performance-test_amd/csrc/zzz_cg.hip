@@ -979,7 +979,7 @@ static int cg_solve_single_reduction(zzz_ctx* ctx, const zzz_solver_opts* o, int
 // solver.solve()'s iteration count whatever the reason (src/poisson_problem.cpp:172-178) and the driver prints its summary
 // and timings all the same, so a diverged solve is NOT an error here either -- unless the caller asks for PETSc's
 // -ksp_error_if_not_converged (zzz_solver_opts.error_if_not_converged).
-int finish_reason(zzz_ctx* ctx, const zzz_solver_opts* o, const CgState& fin, int its)
+static int finish_reason(zzz_ctx* ctx, const zzz_solver_opts* o, const CgState& fin, int its)
 {
   int reason;
   if (fin.converged == 1)
@@ -1003,13 +1003,151 @@ int finish_reason(zzz_ctx* ctx, const zzz_solver_opts* o, const CgState& fin, in
   return ZZZ_OK;
 }
 
-static int cg_solve_chebyshev(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm);
-
-int cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
+// What zzz_cg_info reports about a solve, at the values of a solve with nothing special about it: every solve starts
+// here (and so does the solve a spectrum estimate belongs to, after the estimate's own short solve)
+void cg_report_reset(zzz_ctx* ctx)
 {
   ctx->last_pc_bound = 0.0;
   ctx->last_solve_red_overlapped = false;
   ctx->last_solve_xdefer_k = 1;
+  ctx->last_solve_dinv_codes = 0;
+}
+
+int cg_apply_csr(zzz_ctx* ctx, double* x, double* y, double* parts, int* np, const double* dot_r, int nn_is_rr)
+{
+  if (ctx->comm)
+  {
+    // partitioned operator: halo of x overlapped with the interior tiles
+    if (ctx->overlap && ctx->have_tile_split)
+      return launch_spmv_overlapped(ctx, x, y, parts, np, dot_r, nn_is_rr);
+    if (int rc = comm_halo_forward(ctx, x))
+      return rc;
+  }
+  return launch_spmv(ctx, x, y, parts, np, dot_r, nn_is_rr);
+}
+
+int CgSolve::begin(zzz_ctx* c, const zzz_solver_opts* opts, int prof_stride)
+{
+  ctx = c;
+  o = opts;
+  stride = prof_stride;
+  ZZZ_HIP(ctx, ctx->beta_hist.reserve((size_t)o->max_it + 2));
+  ZZZ_HIP(ctx, ctx->dp_hist.reserve((size_t)o->max_it + 2));
+  ZZZ_HIP(ctx, hipMemsetAsync(ctx->state.p, 0, sizeof(CgState), ctx->stream));
+  // profiling events around the product launches
+  max_prof = o->profile ? 512 : 0;
+  if ((int)ctx->ev.size() < 2 * max_prof)
+  {
+    size_t old = ctx->ev.size();
+    ctx->ev.resize(2 * max_prof);
+    for (size_t i = old; i < ctx->ev.size(); ++i)
+      ZZZ_HIP(ctx, hipEventCreate(&ctx->ev[i]));
+  }
+  ctx->prof_halo_n = 0;
+  ctx->prof_halo_wait_ms = 0.0;
+  ZZZ_HIP(ctx, chk_ev.create());
+  return ZZZ_OK;
+}
+
+// An event record between two kernels is not free (PROF_STRIDE, zzz_cg.h): only every stride-th product is timed.
+// prof_now lets the halo exchange of a timed product sample its exposed wait (zzz_comm.hip).
+void CgSolve::product_begin(int it)
+{
+  timed = nprof < max_prof && it % stride == 0;
+  ctx->prof_now = timed;
+  if (timed)
+    (void)hipEventRecord(ctx->ev[2 * nprof], ctx->stream);
+}
+
+int CgSolve::product_end(int rc)
+{
+  ctx->prof_now = false;
+  if (rc)
+    return rc;
+  if (timed)
+  {
+    (void)hipEventRecord(ctx->ev[2 * nprof + 1], ctx->stream);
+    ++nprof;
+  }
+  return ZZZ_OK;
+}
+
+int CgSolve::poll(int done)
+{
+  if (done % CHECK != 0)
+    return ZZZ_OK;
+  const int slot = nchk % NSLOT;
+  if (nchk >= NSLOT - 1)
+  {
+    const int old = (nchk - (NSLOT - 1)) % NSLOT;
+    ZZZ_HIP(ctx, hipEventSynchronize(chk_ev[old]));
+    if (ctx->h_state[old].converged)
+      stop = true;
+  }
+  ZZZ_HIP(ctx, hipMemcpyAsync(&ctx->h_state[slot], ctx->state.p, sizeof(CgState), hipMemcpyDeviceToHost, ctx->stream));
+  ZZZ_HIP(ctx, hipEventRecord(chk_ev[slot], ctx->stream));
+  ++nchk;
+  return ZZZ_OK;
+}
+
+int CgSolve::finish(int* iters, double* rnorm)
+{
+  hipStream_t s = ctx->stream;
+  ZZZ_HIP(ctx, hipGetLastError());
+  CgState fin;
+  ZZZ_HIP(ctx, hipMemcpyAsync(&fin, ctx->state.p, sizeof(CgState), hipMemcpyDeviceToHost, s));
+  ZZZ_HIP(ctx, hipStreamSynchronize(s));
+  if (int rc = comm_p2p_check(ctx)) // (nothing without a communicator)
+    return rc;
+
+  const int its = fin.converged ? fin.iters : o->max_it;
+  ctx->last_iters = its;
+  if (iters)
+    *iters = its;
+  if (rnorm)
+  {
+    rnorm[0] = fin.dp;
+    rnorm[1] = fin.dp0;
+  }
+  ctx->history.resize((size_t)its + 1);
+  ZZZ_HIP(ctx, hipMemcpy(ctx->history.data(), ctx->dp_hist.p, sizeof(double) * ((size_t)its + 1), hipMemcpyDeviceToHost));
+
+  ctx->prof_spmv_ms = 0.0;
+  ctx->prof_spmv_n = 0;
+  const int used = std::min(nprof, (its + stride - 1) / stride); // launches past convergence return at once: not counted
+  for (int i = 0; i < used; ++i)
+  {
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, ctx->ev[2 * i], ctx->ev[2 * i + 1]) == hipSuccess)
+    {
+      ctx->prof_spmv_ms += ms;
+      ctx->prof_spmv_n++;
+    }
+  }
+  if (ctx->prof_spmv_n)
+    ctx->prof_spmv_ms /= (double)ctx->prof_spmv_n;
+  // the exposed halo wait, over the samples comm_halo_forward took while prof_now was set
+  int cnt = 0;
+  for (int i = 0; i < ctx->prof_halo_n; ++i)
+  {
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, ctx->ev_halo[(size_t)(2 * i)], ctx->ev_halo[(size_t)(2 * i + 1)]) == hipSuccess)
+    {
+      ctx->prof_halo_wait_ms += ms;
+      ++cnt;
+    }
+  }
+  if (cnt)
+    ctx->prof_halo_wait_ms /= cnt;
+  (void)hipGetLastError();
+  return finish_reason(ctx, o, fin, its);
+}
+
+static int cg_solve_chebyshev(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm);
+
+int cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
+{
+  cg_report_reset(ctx);
   if (o->variant == ZZZ_CG_PIPE)
     return cg_solve_pipe(ctx, o, iters, rnorm); // zzz_cg_pipe.hip
   if (o->pc == ZZZ_PC_CHEBYSHEV_JACOBI && !o->single_reduction)
@@ -1029,10 +1167,10 @@ int cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
   auto pick_update_p = [&](bool dzf) { return dzf ? (nt ? k_update_p<true, true> : k_update_p<false, true>) : (nt ? k_update_p<true, false> : k_update_p<false, false>); };
   auto pick_update_xr = [&](bool dzf) { return dzf ? (nt ? k_update_xr<true, true> : k_update_xr<false, true>) : (nt ? k_update_xr<true, false> : k_update_xr<false, false>); };
 
-  ZZZ_HIP(ctx, ctx->beta_hist.reserve((size_t)max_it + 2));
-  ZZZ_HIP(ctx, ctx->dp_hist.reserve((size_t)max_it + 2));
+  CgSolve S;
+  if (int rc = S.begin(ctx, o))
+    return rc;
   ZZZ_HIP(ctx, ctx->alpha_hist.reserve((size_t)max_it + 2));
-  ZZZ_HIP(ctx, hipMemsetAsync(ctx->state.p, 0, sizeof(CgState), s));
   ZZZ_HIP(ctx, hipMemsetAsync(ctx->p.p, 0, sizeof(double) * ctx->p.n, s));
 
   // PCSetUp(PCJACOBI): inverse diagonal (inside `ZZZ Solve`, as KSPSetUp is in the reference)
@@ -1112,17 +1250,11 @@ int cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
   };
 
   auto apply = [&](double* x, double* y, double* parts, int* np) -> int {
-    // partitioned CSR operator: halo of x overlapped with the interior tiles
-    if (multi && o->op == ZZZ_OP_CSR && ctx->overlap && ctx->have_tile_split)
-      return launch_spmv_overlapped(ctx, x, y, parts, np);
-    if (multi)
-    {
-      int rc = comm_halo_forward(ctx, x);
-      if (rc)
-        return rc;
-    }
     if (o->op == ZZZ_OP_CSR)
-      return launch_spmv(ctx, x, y, parts, np);
+      return cg_apply_csr(ctx, x, y, parts, np);
+    if (multi)
+      if (int rc = comm_halo_forward(ctx, x))
+        return rc;
     return launch_matfree_action(ctx, x, y, parts, np);
   };
 
@@ -1173,47 +1305,15 @@ int cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
       return rc;
   }
 
-  // profiling events around the SpMV launches
-  const int max_prof = o->profile ? 512 : 0;
-  if ((int)ctx->ev.size() < 2 * max_prof)
-  {
-    size_t old = ctx->ev.size();
-    ctx->ev.resize(2 * max_prof);
-    for (size_t i = old; i < ctx->ev.size(); ++i)
-      ZZZ_HIP(ctx, hipEventCreate(&ctx->ev[i]));
-  }
-  int nprof = 0;
-  ctx->prof_halo_n = 0;
-  ctx->prof_halo_wait_ms = 0.0;
-
-  // host polling: copy the state every CHECK iterations, look at it NSLOT-1 batches later
-  constexpr int CHECK = 8, NSLOT = 4;
-  EventRing<NSLOT> chk_ev;
-  ZZZ_HIP(ctx, chk_ev.create());
-  int nchk = 0;
-  bool stop = false;
-
   int it = 0;
-  for (; it < max_it && !stop; ++it)
+  for (; it < max_it && !S.stop; ++it)
   {
     // convergence test of iteration `it` and the new search direction
     launch_update_p(it, 1, rz_src, nn_src, n_rz);
     int np = 0;
-    const bool timed = nprof < max_prof && it % PROF_STRIDE == 0;
-    ctx->prof_now = timed;
-    if (timed)
-      (void)hipEventRecord(ctx->ev[2 * nprof], s);
-    {
-      int rc = apply(dir_of(it), ctx->w.p, ctx->part_a.p, &np);
-      if (rc)
-        return rc;
-    }
-    ctx->prof_now = false;
-    if (timed)
-    {
-      (void)hipEventRecord(ctx->ev[2 * nprof + 1], s);
-      ++nprof;
-    }
+    S.product_begin(it);
+    if (int rc = S.product_end(apply(dir_of(it), ctx->w.p, ctx->part_a.p, &np)))
+      return rc;
     if (multi)
     {
       int rc = comm_reduce_allreduce(ctx, stop_flag, ctx->part_a.p, nullptr, nullptr, np, 1, ctx->red.p + 2);
@@ -1225,20 +1325,8 @@ int cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
                        np, ctx->w.p, ctx->dinv.p, ctx->r.p, ctx->z.p, n, P.norm, pa, pb, P.variant, dzc);
     if (int rc = allreduce_beta())
       return rc;
-    if ((it + 1) % CHECK == 0)
-    {
-      const int slot = nchk % NSLOT;
-      if (nchk >= NSLOT - 1)
-      {
-        const int old = (nchk - (NSLOT - 1)) % NSLOT;
-        ZZZ_HIP(ctx, hipEventSynchronize(chk_ev[old]));
-        if (ctx->h_state[old].converged)
-          stop = true;
-      }
-      ZZZ_HIP(ctx, hipMemcpyAsync(&ctx->h_state[slot], ctx->state.p, sizeof(CgState), hipMemcpyDeviceToHost, s));
-      ZZZ_HIP(ctx, hipEventRecord(chk_ev[slot], s));
-      ++nchk;
-    }
+    if (int rc = S.poll(it + 1))
+      return rc;
   }
   // the test of the last completed iteration (it == max_it when the loop ran out) and its pending
   // solution update; no new direction
@@ -1252,55 +1340,7 @@ int cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
     hipLaunchKernelGGL(k_x_apply_pending<8>, dim3(g), dim3(VB), 0, s, ctx->state.p, ctx->alpha_hist.p, it, ring, ctx->u.p, n);
   if (lifted_mf && o->variant == ZZZ_CG_PETSC) // (src/cg.h leaves u[bc] at the caller's initial guess, and so does ZZZ_CG_CGH)
     hipLaunchKernelGGL(k_set_bc_values, dim3(g), dim3(VB), 0, s, ctx->bc.p, ctx->bc_val.p, ctx->u.p, n);
-  ZZZ_HIP(ctx, hipGetLastError());
-  CgState fin;
-  ZZZ_HIP(ctx, hipMemcpyAsync(&fin, ctx->state.p, sizeof(CgState), hipMemcpyDeviceToHost, s));
-  ZZZ_HIP(ctx, hipStreamSynchronize(s));
-  if (int rc = comm_p2p_check(ctx))
-    return rc;
-
-  const int its = fin.converged ? fin.iters : max_it;
-  ctx->last_iters = its;
-  if (iters)
-    *iters = its;
-  if (rnorm)
-  {
-    rnorm[0] = fin.dp;
-    rnorm[1] = fin.dp0;
-  }
-  ctx->history.resize((size_t)its + 1);
-  ZZZ_HIP(ctx, hipMemcpy(ctx->history.data(), ctx->dp_hist.p, sizeof(double) * ((size_t)its + 1), hipMemcpyDeviceToHost));
-
-  ctx->prof_spmv_ms = 0.0;
-  ctx->prof_spmv_n = 0;
-  const int used = std::min(nprof, (its + PROF_STRIDE - 1) / PROF_STRIDE); // launches past convergence return at once: not counted
-  for (int i = 0; i < used; ++i)
-  {
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, ctx->ev[2 * i], ctx->ev[2 * i + 1]) == hipSuccess)
-    {
-      ctx->prof_spmv_ms += ms;
-      ctx->prof_spmv_n++;
-    }
-  }
-  if (ctx->prof_spmv_n)
-    ctx->prof_spmv_ms /= (double)ctx->prof_spmv_n;
-  {
-    int cnt = 0;
-    for (int i = 0; i < ctx->prof_halo_n; ++i)
-    {
-      float ms = 0;
-      if (hipEventElapsedTime(&ms, ctx->ev_halo[(size_t)(2 * i)], ctx->ev_halo[(size_t)(2 * i + 1)]) == hipSuccess)
-      {
-        ctx->prof_halo_wait_ms += ms;
-        ++cnt;
-      }
-    }
-    if (cnt)
-      ctx->prof_halo_wait_ms /= cnt;
-    (void)hipGetLastError();
-  }
-  return finish_reason(ctx, o, fin, its);
+  return S.finish(iters, rnorm);
 }
 
 // ---- KSPCG with the Chebyshev-Jacobi polynomial preconditioner (ZZZ_PC_CHEBYSHEV_JACOBI; oracle: zo_pcg_cheb) -------
@@ -1547,7 +1587,7 @@ static int chebyshev_esteig(zzz_ctx* ctx, const zzz_solver_opts* o, int its, dou
   double rn[2];
   const int rc = cg_solve(ctx, &o2, &ran, rn);
   swap_b();
-  ctx->last_solve_xdefer_k = 1; // (zzz_cg_info reports the solve this estimate belongs to, and that one keeps its kernels)
+  cg_report_reset(ctx); // (zzz_cg_info reports the solve this estimate belongs to, and that one keeps its own kernels)
   if (rc)
     return rc;
   if (ran < 2)
@@ -1732,23 +1772,15 @@ static int cg_solve_chebyshev(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters
   const double hi = C.hi, theta = C.theta;
   const bool fused = C.fused;
   double *chd = C.d, *chg = C.g;
-  ZZZ_HIP(ctx, ctx->beta_hist.reserve((size_t)max_it + 2));
-  ZZZ_HIP(ctx, ctx->dp_hist.reserve((size_t)max_it + 2));
+  CgSolve S;
+  if (int rc = S.begin(ctx, o))
+    return rc;
   ZZZ_HIP(ctx, ctx->alpha_hist.reserve((size_t)max_it + 2));
-  ZZZ_HIP(ctx, hipMemsetAsync(ctx->state.p, 0, sizeof(CgState), s));
   ZZZ_HIP(ctx, hipMemsetAsync(ctx->p.p, 0, sizeof(double) * ctx->p.n, s));
   ZZZ_HIP(ctx, hipMemsetAsync(ctx->u.p, 0, sizeof(double) * ctx->u.n, s)); // KSP zero initial guess
   hipLaunchKernelGGL(k_extract_dinv, dim3(g), dim3(VB), 0, s, ctx->rowptr.p, ctx->cols.p, ctx->vals.p, ctx->dinv.p, n, 1);
 
   const int* stop_flag = reinterpret_cast<const int*>(ctx->state.p);
-  auto apply = [&](double* x, double* y, double* parts, int* np) -> int {
-    if (multi && ctx->overlap && ctx->have_tile_split)
-      return launch_spmv_overlapped(ctx, x, y, parts, np);
-    if (multi)
-      if (int rc = comm_halo_forward(ctx, x))
-        return rc;
-    return launch_spmv(ctx, x, y, parts, np);
-  };
   double* pa = ctx->part_b.p;
   double* pb = ctx->part_b.p + VGRID_MAX;
   int np_last = g;
@@ -1790,43 +1822,15 @@ static int cg_solve_chebyshev(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters
     pw_src = ctx->red.p + 2;
     n_rz = 1;
   }
-  const int max_prof = o->profile ? 512 : 0;
-  if ((int)ctx->ev.size() < 2 * max_prof)
-  {
-    size_t old = ctx->ev.size();
-    ctx->ev.resize(2 * max_prof);
-    for (size_t i = old; i < ctx->ev.size(); ++i)
-      ZZZ_HIP(ctx, hipEventCreate(&ctx->ev[i]));
-  }
-  int nprof = 0;
-  ctx->prof_halo_n = 0;
-  ctx->prof_halo_wait_ms = 0.0;
-  constexpr int CHECK = 8, NSLOT = 4;
-  EventRing<NSLOT> chk_ev;
-  ZZZ_HIP(ctx, chk_ev.create());
-  int nchk = 0;
-  bool stop = false;
   int it = 0;
-  for (; it < max_it && !stop; ++it)
+  for (; it < max_it && !S.stop; ++it)
   {
     hipLaunchKernelGGL(k_update_p<false>, dim3(g), dim3(VB), 0, s, ctx->state.p, ctx->beta_hist.p, ctx->dp_hist.p, ctx->alpha_hist.p,
                        it, P, rz_src, nn_src, n_rz, ctx->z.p, ctx->p.p, ctx->u.p, n, 1);
     int np = 0;
-    const bool timed = nprof < max_prof && it % PROF_STRIDE == 0;
-    ctx->prof_now = timed;
-    if (timed)
-      (void)hipEventRecord(ctx->ev[2 * nprof], s);
-    {
-      int rc = apply(ctx->p.p, ctx->w.p, ctx->part_a.p, &np);
-      ctx->prof_now = false;
-      if (rc)
-        return rc;
-    }
-    if (timed)
-    {
-      (void)hipEventRecord(ctx->ev[2 * nprof + 1], s);
-      ++nprof;
-    }
+    S.product_begin(it);
+    if (int rc = S.product_end(cg_apply_csr(ctx, ctx->p.p, ctx->w.p, ctx->part_a.p, &np)))
+      return rc;
     if (multi)
     {
       if (int rc = comm_reduce_allreduce(ctx, stop_flag, ctx->part_a.p, nullptr, nullptr, np, 1, ctx->red.p + 2))
@@ -1837,56 +1841,13 @@ static int cg_solve_chebyshev(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters
                        ctx->w.p, ctx->dinv.p, theta, ctx->r.p, chg, chd, ctx->z.p, n);
     if (int rc = polynomial())
       return rc;
-    if ((it + 1) % CHECK == 0)
-    {
-      const int slot = nchk % NSLOT;
-      if (nchk >= NSLOT - 1)
-      {
-        const int old = (nchk - (NSLOT - 1)) % NSLOT;
-        ZZZ_HIP(ctx, hipEventSynchronize(chk_ev[old]));
-        if (ctx->h_state[old].converged)
-          stop = true;
-      }
-      ZZZ_HIP(ctx, hipMemcpyAsync(&ctx->h_state[slot], ctx->state.p, sizeof(CgState), hipMemcpyDeviceToHost, s));
-      ZZZ_HIP(ctx, hipEventRecord(chk_ev[slot], s));
-      ++nchk;
-    }
+    if (int rc = S.poll(it + 1))
+      return rc;
   }
   hipLaunchKernelGGL(k_update_p<false>, dim3(g), dim3(VB), 0, s, ctx->state.p, ctx->beta_hist.p, ctx->dp_hist.p, ctx->alpha_hist.p, it,
                      P, rz_src, nn_src, n_rz, ctx->z.p, ctx->p.p, ctx->u.p, n, 0);
-  ZZZ_HIP(ctx, hipGetLastError());
-  CgState fin;
-  ZZZ_HIP(ctx, hipMemcpyAsync(&fin, ctx->state.p, sizeof(CgState), hipMemcpyDeviceToHost, s));
-  ZZZ_HIP(ctx, hipStreamSynchronize(s));
-  if (int rc = comm_p2p_check(ctx))
-    return rc;
-  const int its = fin.converged ? fin.iters : max_it;
-  ctx->last_iters = its;
-  if (iters)
-    *iters = its;
-  if (rnorm)
-  {
-    rnorm[0] = fin.dp;
-    rnorm[1] = fin.dp0;
-  }
-  ctx->history.resize((size_t)its + 1);
-  ZZZ_HIP(ctx, hipMemcpy(ctx->history.data(), ctx->dp_hist.p, sizeof(double) * ((size_t)its + 1), hipMemcpyDeviceToHost));
-  ctx->prof_spmv_ms = 0.0;
-  ctx->prof_spmv_n = 0;
-  const int used = std::min(nprof, (its + PROF_STRIDE - 1) / PROF_STRIDE);
-  for (int i = 0; i < used; ++i)
-  {
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, ctx->ev[2 * i], ctx->ev[2 * i + 1]) == hipSuccess)
-    {
-      ctx->prof_spmv_ms += ms;
-      ctx->prof_spmv_n++;
-    }
-  }
-  if (ctx->prof_spmv_n)
-    ctx->prof_spmv_ms /= (double)ctx->prof_spmv_n;
   ctx->last_pc_bound = hi;
-  return finish_reason(ctx, o, fin, its);
+  return S.finish(iters, rnorm);
 }
 
 int chebyshev_bound(zzz_ctx* ctx, const zzz_solver_opts* o, double* hi)
@@ -1913,10 +1874,10 @@ int cg_solve_mg(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnor
   hipStream_t s = ctx->stream;
   if (int rc = mg_setup(ctx, o)) // PCSetUp: runs the levels' spectrum estimates through this context's CG vectors
     return rc;
-  ZZZ_HIP(ctx, ctx->beta_hist.reserve((size_t)max_it + 2));
-  ZZZ_HIP(ctx, ctx->dp_hist.reserve((size_t)max_it + 2));
+  CgSolve S;
+  if (int rc = S.begin(ctx, o, 1)) // (every product timed: about ten iterations of a few milliseconds each)
+    return rc;
   ZZZ_HIP(ctx, ctx->alpha_hist.reserve((size_t)max_it + 2));
-  ZZZ_HIP(ctx, hipMemsetAsync(ctx->state.p, 0, sizeof(CgState), s));
   ZZZ_HIP(ctx, hipMemsetAsync(ctx->p.p, 0, sizeof(double) * ctx->p.n, s));
   ZZZ_HIP(ctx, hipMemsetAsync(ctx->u.p, 0, sizeof(double) * ctx->u.n, s)); // KSP zero initial guess
   hipLaunchKernelGGL(k_extract_dinv, dim3(g), dim3(VB), 0, s, ctx->rowptr.p, ctx->cols.p, ctx->vals.p, ctx->dinv.p, n, 1);
@@ -1934,81 +1895,34 @@ int cg_solve_mg(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnor
                      P.norm, pa, pb);
   if (int rc = precondition())
     return rc;
-  const int max_prof = o->profile ? 512 : 0;
-  if ((int)ctx->ev.size() < 2 * max_prof)
-  {
-    size_t old = ctx->ev.size();
-    ctx->ev.resize(2 * max_prof);
-    for (size_t i = old; i < ctx->ev.size(); ++i)
-      ZZZ_HIP(ctx, hipEventCreate(&ctx->ev[i]));
-  }
-  int nprof = 0;
-  ctx->prof_halo_n = 0;
-  ctx->prof_halo_wait_ms = 0.0;
-  constexpr int NSLOT = 2;
-  EventRing<NSLOT> chk_ev;
-  ZZZ_HIP(ctx, chk_ev.create());
-  bool stop = false;
   int it = 0;
-  for (; it < max_it && !stop; ++it)
+  for (; it < max_it && !S.stop; ++it)
   {
     hipLaunchKernelGGL(k_update_p<false>, dim3(g), dim3(VB), 0, s, ctx->state.p, ctx->beta_hist.p, ctx->dp_hist.p, ctx->alpha_hist.p,
                        it, P, pa, pb, g, ctx->z.p, ctx->p.p, ctx->u.p, n, 1);
-    const int slot = it % NSLOT;
+    const int slot = it % 2; // (two of the skeleton's polling events: this form waits for the copy it has just asked for)
     ZZZ_HIP(ctx, hipMemcpyAsync(&ctx->h_state[slot], ctx->state.p, sizeof(CgState), hipMemcpyDeviceToHost, s));
-    ZZZ_HIP(ctx, hipEventRecord(chk_ev[slot], s));
+    ZZZ_HIP(ctx, hipEventRecord(S.chk_ev[slot], s));
     int np = 0;
-    const bool timed = nprof < max_prof;
-    if (timed)
-      (void)hipEventRecord(ctx->ev[2 * nprof], s);
-    if (int rc = launch_spmv(ctx, ctx->p.p, ctx->w.p, ctx->part_a.p, &np))
+    S.product_begin(it);
+    if (int rc = S.product_end(launch_spmv(ctx, ctx->p.p, ctx->w.p, ctx->part_a.p, &np)))
       return rc;
-    if (timed)
-    {
-      (void)hipEventRecord(ctx->ev[2 * nprof + 1], s);
-      ++nprof;
-    }
     hipLaunchKernelGGL(k_update_xr<false>, dim3(g), dim3(VB), 0, s, ctx->state.p, ctx->beta_hist.p, ctx->alpha_hist.p, it,
                        ctx->part_a.p, np, ctx->w.p, ctx->dinv.p, ctx->r.p, ctx->z.p, n, P.norm, pa, pb, P.variant, DinvCodes());
     if (int rc = precondition())
       return rc;
-    ZZZ_HIP(ctx, hipEventSynchronize(chk_ev[slot]));
+    ZZZ_HIP(ctx, hipEventSynchronize(S.chk_ev[slot]));
     if (ctx->h_state[slot].converged)
-      stop = true;
+      S.stop = true;
   }
   hipLaunchKernelGGL(k_update_p<false>, dim3(g), dim3(VB), 0, s, ctx->state.p, ctx->beta_hist.p, ctx->dp_hist.p, ctx->alpha_hist.p, it,
                      P, pa, pb, g, ctx->z.p, ctx->p.p, ctx->u.p, n, 0);
-  ZZZ_HIP(ctx, hipGetLastError());
-  CgState fin;
-  ZZZ_HIP(ctx, hipMemcpyAsync(&fin, ctx->state.p, sizeof(CgState), hipMemcpyDeviceToHost, s));
-  ZZZ_HIP(ctx, hipStreamSynchronize(s));
-  const int its = fin.converged ? fin.iters : max_it;
-  ctx->last_iters = its;
-  if (iters)
-    *iters = its;
-  if (rnorm)
-  {
-    rnorm[0] = fin.dp;
-    rnorm[1] = fin.dp0;
-  }
-  ctx->history.resize((size_t)its + 1);
-  ZZZ_HIP(ctx, hipMemcpy(ctx->history.data(), ctx->dp_hist.p, sizeof(double) * ((size_t)its + 1), hipMemcpyDeviceToHost));
-  ctx->prof_spmv_ms = 0.0;
-  ctx->prof_spmv_n = 0;
-  for (int i = 0; i < std::min(nprof, its); ++i)
-  {
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, ctx->ev[2 * i], ctx->ev[2 * i + 1]) == hipSuccess)
-    {
-      ctx->prof_spmv_ms += ms;
-      ctx->prof_spmv_n++;
-    }
-  }
-  if (ctx->prof_spmv_n)
-    ctx->prof_spmv_ms /= (double)ctx->prof_spmv_n;
-  mg_profile_end(ctx, o->profile ? its + 1 : 0); // (the cycle of the start-up and one per iteration that ran)
   ctx->last_pc_bound = mg_level0_bound(ctx);
-  return finish_reason(ctx, o, fin, its);
+  const int rc = S.finish(iters, rnorm);
+  // the cycle of the start-up and one per iteration that ran.  Behind a finish that failed (a HIP error) last_iters is the
+  // solve's before and the mean says nothing; the call still runs, to hand the cycle's events back for the next solve.
+  mg_profile_end(ctx, o->profile ? ctx->last_iters + 1 : 0);
+  return rc;
 }
 
 // -ksp_cg_single_reduction: see k_sr_update.  Two kernels and one reduction point per iteration.
@@ -2029,11 +1943,11 @@ static int cg_solve_single_reduction(zzz_ctx* ctx, const zzz_solver_opts* o, int
       return rc;
   const bool ntv = loop_exceeds_cache(ctx, 8);
 
-  ZZZ_HIP(ctx, ctx->beta_hist.reserve((size_t)max_it + 2));
-  ZZZ_HIP(ctx, ctx->dp_hist.reserve((size_t)max_it + 2));
+  CgSolve S;
+  if (int rc = S.begin(ctx, o))
+    return rc;
   ZZZ_HIP(ctx, ctx->dpi_hist.reserve((size_t)max_it + 2));
   ZZZ_HIP(ctx, ctx->sr_s.alloc((size_t)ctx->nloc()));
-  ZZZ_HIP(ctx, hipMemsetAsync(ctx->state.p, 0, sizeof(CgState), s));
   ZZZ_HIP(ctx, hipMemsetAsync(ctx->p.p, 0, sizeof(double) * ctx->p.n, s));
   ZZZ_HIP(ctx, hipMemsetAsync(ctx->w.p, 0, sizeof(double) * ctx->w.n, s));
   ZZZ_HIP(ctx, hipMemsetAsync(ctx->z.p, 0, sizeof(double) * ctx->z.n, s)); // ghost entries of z are exchanged
@@ -2077,144 +1991,41 @@ static int cg_solve_single_reduction(zzz_ctx* ctx, const zzz_solver_opts* o, int
   int np = 0;
   // s = A z with the three partial dot products; then (multi) one all-reduce of three doubles
   auto apply = [&]() -> int {
-    int rc;
-    if (multi && ctx->overlap && ctx->have_tile_split)
-      rc = launch_spmv_overlapped(ctx, ctx->z.p, ctx->sr_s.p, parts, &np, ctx->r.p, nn_is_rr);
-    else
-    {
-      if (multi)
-      {
-        rc = comm_halo_forward(ctx, ctx->z.p);
-        if (rc)
-          return rc;
-      }
-      rc = launch_spmv(ctx, ctx->z.p, ctx->sr_s.p, parts, &np, ctx->r.p, nn_is_rr);
-    }
-    if (rc)
+    if (int rc = cg_apply_csr(ctx, ctx->z.p, ctx->sr_s.p, parts, &np, ctx->r.p, nn_is_rr))
       return rc;
     if (multi)
     {
-      rc = comm_reduce_allreduce(ctx, reinterpret_cast<const int*>(ctx->state.p), parts + SPMV_PSTRIDE,
-                                 parts + 2 * SPMV_PSTRIDE, parts, np, 3, ctx->red.p);
-      if (rc)
+      if (int rc = comm_reduce_allreduce(ctx, reinterpret_cast<const int*>(ctx->state.p), parts + SPMV_PSTRIDE,
+                                         parts + 2 * SPMV_PSTRIDE, parts, np, 3, ctx->red.p))
         return rc;
       np = 1;
     }
     return ZZZ_OK;
   };
 
-  const int max_prof = o->profile ? 512 : 0;
-  if ((int)ctx->ev.size() < 2 * max_prof)
-  {
-    size_t old = ctx->ev.size();
-    ctx->ev.resize(2 * max_prof);
-    for (size_t i = old; i < ctx->ev.size(); ++i)
-      ZZZ_HIP(ctx, hipEventCreate(&ctx->ev[i]));
-  }
-  int nprof = 0;
-  ctx->prof_halo_n = 0;
-  ctx->prof_halo_wait_ms = 0.0;
-  {
-    int rc = apply();
-    if (rc)
-      return rc;
-  }
-  constexpr int CHECK = 8, NSLOT = 4;
-  EventRing<NSLOT> chk_ev;
-  ZZZ_HIP(ctx, chk_ev.create());
-  int nchk = 0;
-  bool stop = false;
+  if (int rc = apply())
+    return rc;
   int it = 0;
-  for (; it < max_it && !stop; ++it)
+  for (; it < max_it && !S.stop; ++it)
   {
     hipLaunchKernelGGL(kern_sr_update, dim3(g), dim3(VB), 0, s, ctx->state.p, ctx->beta_hist.p, ctx->dpi_hist.p, ctx->dp_hist.p,
                        it, P, rz_src, nn_src, zs_src, np, ctx->dinv.p, ctx->sr_s.p, ctx->z.p, ctx->p.p, ctx->w.p, ctx->u.p,
                        ctx->r.p, n, 0, C.theta, C.g, C.d, dzc);
     if (int rc = polynomial(false))
       return rc;
-    const bool timed = nprof < max_prof && it % PROF_STRIDE == 0;
-    ctx->prof_now = timed;
-    if (timed)
-      (void)hipEventRecord(ctx->ev[2 * nprof], s);
-    {
-      int rc = apply();
-      if (rc)
-        return rc;
-    }
-    ctx->prof_now = false;
-    if (timed)
-    {
-      (void)hipEventRecord(ctx->ev[2 * nprof + 1], s);
-      ++nprof;
-    }
-    if ((it + 1) % CHECK == 0)
-    {
-      const int slot = nchk % NSLOT;
-      if (nchk >= NSLOT - 1)
-      {
-        const int old = (nchk - (NSLOT - 1)) % NSLOT;
-        ZZZ_HIP(ctx, hipEventSynchronize(chk_ev[old]));
-        if (ctx->h_state[old].converged)
-          stop = true;
-      }
-      ZZZ_HIP(ctx, hipMemcpyAsync(&ctx->h_state[slot], ctx->state.p, sizeof(CgState), hipMemcpyDeviceToHost, s));
-      ZZZ_HIP(ctx, hipEventRecord(chk_ev[slot], s));
-      ++nchk;
-    }
+    S.product_begin(it);
+    if (int rc = S.product_end(apply()))
+      return rc;
+    if (int rc = S.poll(it + 1))
+      return rc;
   }
   // convergence test of the last completed iteration: scalars only
   hipLaunchKernelGGL(kern_sr_update, dim3(1), dim3(VB), 0, s, ctx->state.p, ctx->beta_hist.p, ctx->dpi_hist.p, ctx->dp_hist.p, it,
                      P, rz_src, nn_src, zs_src, np, ctx->dinv.p, ctx->sr_s.p, ctx->z.p, ctx->p.p, ctx->w.p, ctx->u.p, ctx->r.p,
                      n, 1, C.theta, C.g, C.d, dzc);
-  ZZZ_HIP(ctx, hipGetLastError());
-  CgState fin;
-  ZZZ_HIP(ctx, hipMemcpyAsync(&fin, ctx->state.p, sizeof(CgState), hipMemcpyDeviceToHost, s));
-  ZZZ_HIP(ctx, hipStreamSynchronize(s));
-  if (int rc = comm_p2p_check(ctx))
-    return rc;
-  const int its = fin.converged ? fin.iters : max_it;
-  ctx->last_iters = its;
-  if (iters)
-    *iters = its;
-  if (rnorm)
-  {
-    rnorm[0] = fin.dp;
-    rnorm[1] = fin.dp0;
-  }
-  ctx->history.resize((size_t)its + 1);
-  ZZZ_HIP(ctx, hipMemcpy(ctx->history.data(), ctx->dp_hist.p, sizeof(double) * ((size_t)its + 1), hipMemcpyDeviceToHost));
-  ctx->prof_spmv_ms = 0.0;
-  ctx->prof_spmv_n = 0;
-  const int used = std::min(nprof, (its + PROF_STRIDE - 1) / PROF_STRIDE);
-  for (int i = 0; i < used; ++i)
-  {
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, ctx->ev[2 * i], ctx->ev[2 * i + 1]) == hipSuccess)
-    {
-      ctx->prof_spmv_ms += ms;
-      ctx->prof_spmv_n++;
-    }
-  }
-  if (ctx->prof_spmv_n)
-    ctx->prof_spmv_ms /= (double)ctx->prof_spmv_n;
-  {
-    int cnt = 0;
-    for (int i = 0; i < ctx->prof_halo_n; ++i)
-    {
-      float ms = 0;
-      if (hipEventElapsedTime(&ms, ctx->ev_halo[(size_t)(2 * i)], ctx->ev_halo[(size_t)(2 * i + 1)]) == hipSuccess)
-      {
-        ctx->prof_halo_wait_ms += ms;
-        ++cnt;
-      }
-    }
-    if (cnt)
-      ctx->prof_halo_wait_ms /= cnt;
-    (void)hipGetLastError();
-  }
   if (cheb)
     ctx->last_pc_bound = C.hi;
-  return finish_reason(ctx, o, fin, its);
+  return S.finish(iters, rnorm);
 }
 ZZZ_PRELOAD_TU(cg)
 } // namespace zzz

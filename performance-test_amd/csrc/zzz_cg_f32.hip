@@ -139,10 +139,7 @@ __global__ __launch_bounds__(VB) void k32_store_u(const float* __restrict__ x, d
 
 int cg_solve_f32(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
 {
-  ctx->last_pc_bound = 0.0;
-  ctx->last_solve_red_overlapped = false;
-  ctx->last_solve_xdefer_k = 1;
-  ctx->last_solve_dinv_codes = 0;
+  cg_report_reset(ctx);
   const int64_t n = ctx->n_owned; // (block size 1, one rank: no ghosts)
   const size_t nl = (size_t)ctx->nloc();
   const int max_it = o->max_it;
@@ -154,9 +151,9 @@ int cg_solve_f32(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rno
   ZZZ_HIP(ctx, ctx->f32_r.reserve(nl));
   ZZZ_HIP(ctx, ctx->f32_p.reserve(nl));
   ZZZ_HIP(ctx, ctx->f32_y.reserve(nl));
-  ZZZ_HIP(ctx, ctx->beta_hist.reserve((size_t)max_it + 2));
-  ZZZ_HIP(ctx, ctx->dp_hist.reserve((size_t)max_it + 2));
-  ZZZ_HIP(ctx, hipMemsetAsync(ctx->state.p, 0, sizeof(CgState), s));
+  CgSolve S;
+  if (int rc = S.begin(ctx, o))
+    return rc;
   CgState* const st = ctx->state.p;
   float *x = ctx->f32_x.p, *r = ctx->f32_r.p, *p = ctx->f32_p.p, *y = ctx->f32_y.p;
   double* rr_parts = ctx->part_b.p; // g <= VGRID_MAX entries
@@ -170,55 +167,19 @@ int cg_solve_f32(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rno
   hipLaunchKernelGGL(k32_init, dim3(g), dim3(VB), 0, s, 1, ctx->b.p, ctx->u.p, y, x, r, p, n, rr_parts);
   hipLaunchKernelGGL(k32_update_p, dim3(g), dim3(VB), 0, s, st, ctx->beta_hist.p, ctx->dp_hist.p, 0, rtol2, rr_parts, g, r, p, n);
 
-  // host polling: copy the state every CHECK iterations, look at it NSLOT-1 batches later
-  constexpr int CHECK = 8, NSLOT = 4;
-  EventRing<NSLOT> chk_ev;
-  ZZZ_HIP(ctx, chk_ev.create());
-  int nchk = 0;
-  bool stop = false;
-  for (int it = 1; it <= max_it && !stop; ++it)
+  for (int it = 1; it <= max_it && !S.stop; ++it)
   {
     int np = 0;
     if (int rc = mf_action_f32(ctx, p, y, pw_parts, &np))
       return rc;
     hipLaunchKernelGGL(k32_update_xr, dim3(g), dim3(VB), 0, s, st, ctx->beta_hist.p, it, pw_parts, np, p, y, x, r, n, rr_parts);
     hipLaunchKernelGGL(k32_update_p, dim3(g), dim3(VB), 0, s, st, ctx->beta_hist.p, ctx->dp_hist.p, it, rtol2, rr_parts, g, r, p, n);
-    if (it % CHECK == 0)
-    {
-      const int slot = nchk % NSLOT;
-      if (nchk >= NSLOT - 1)
-      {
-        const int old = (nchk - (NSLOT - 1)) % NSLOT;
-        ZZZ_HIP(ctx, hipEventSynchronize(chk_ev[old]));
-        if (ctx->h_state[old].converged)
-          stop = true;
-      }
-      ZZZ_HIP(ctx, hipMemcpyAsync(&ctx->h_state[slot], ctx->state.p, sizeof(CgState), hipMemcpyDeviceToHost, s));
-      ZZZ_HIP(ctx, hipEventRecord(chk_ev[slot], s));
-      ++nchk;
-    }
+    if (int rc = S.poll(it))
+      return rc;
   }
   // the solution into the context's u, as doubles: zzz_vec_download, zzz_vec_norm and the driver's --output see it there
   hipLaunchKernelGGL(k32_store_u, dim3(g), dim3(VB), 0, s, x, ctx->u.p, n);
-  ZZZ_HIP(ctx, hipGetLastError());
-  CgState fin;
-  ZZZ_HIP(ctx, hipMemcpyAsync(&fin, ctx->state.p, sizeof(CgState), hipMemcpyDeviceToHost, s));
-  ZZZ_HIP(ctx, hipStreamSynchronize(s));
-
-  const int its = fin.converged ? fin.iters : max_it;
-  ctx->last_iters = its;
-  if (iters)
-    *iters = its;
-  if (rnorm)
-  {
-    rnorm[0] = fin.dp;
-    rnorm[1] = fin.dp0;
-  }
-  ctx->history.resize((size_t)its + 1);
-  ZZZ_HIP(ctx, hipMemcpy(ctx->history.data(), ctx->dp_hist.p, sizeof(double) * ((size_t)its + 1), hipMemcpyDeviceToHost));
-  ctx->prof_spmv_ms = 0.0;
-  ctx->prof_spmv_n = 0;
-  return finish_reason(ctx, o, fin, its);
+  return S.finish(iters, rnorm);
 }
 ZZZ_PRELOAD_TU(cg_f32)
 } // namespace zzz

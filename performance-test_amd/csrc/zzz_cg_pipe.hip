@@ -283,14 +283,14 @@ int cg_solve_pipe(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rn
   hipStream_t s = ctx->stream;
   const bool ntv = loop_exceeds_cache(ctx, 10);
 
-  ZZZ_HIP(ctx, ctx->beta_hist.reserve((size_t)max_it + 2)); // gamma
-  ZZZ_HIP(ctx, ctx->dp_hist.reserve((size_t)max_it + 2));
+  CgSolve S;
+  if (int rc = S.begin(ctx, o)) // (beta_hist: gamma)
+    return rc;
   ZZZ_HIP(ctx, ctx->alpha_hist.reserve((size_t)max_it + 2));
   ZZZ_HIP(ctx, ctx->sr_s.alloc((size_t)ctx->nloc()));
   ZZZ_HIP(ctx, ctx->pipe_m.alloc((size_t)ctx->nloc()));
   ZZZ_HIP(ctx, ctx->pipe_n.alloc((size_t)ctx->nloc()));
   ZZZ_HIP(ctx, ctx->pipe_parts.reserve((size_t)(2 * 3 * VGRID_MAX)));
-  ZZZ_HIP(ctx, hipMemsetAsync(ctx->state.p, 0, sizeof(CgState), s));
   ZZZ_HIP(ctx, hipMemsetAsync(ctx->z.p, 0, sizeof(double) * ctx->z.n, s));
   ZZZ_HIP(ctx, hipMemsetAsync(ctx->sr_s.p, 0, sizeof(double) * ctx->sr_s.n, s));
   ZZZ_HIP(ctx, hipMemsetAsync(ctx->p.p, 0, sizeof(double) * ctx->p.n, s));
@@ -312,12 +312,7 @@ int cg_solve_pipe(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rn
   // them makes the launches behind a converged solve return at once, as in the other forms)
   auto apply = [&](double* v, double* y) -> int {
     int np = 0;
-    if (multi && ctx->overlap && ctx->have_tile_split)
-      return launch_spmv_overlapped(ctx, v, y, ctx->part_a.p, &np);
-    if (multi)
-      if (int rc = comm_halo_forward(ctx, v))
-        return rc;
-    return launch_spmv(ctx, v, y, ctx->part_a.p, &np);
+    return cg_apply_csr(ctx, v, y, ctx->part_a.p, &np);
   };
   // the two sets of partials, and where the kernel of iteration `it` finds its sums
   auto parts = [&](int it) { return ctx->pipe_parts.p + (size_t)(it & 1) * 3 * VGRID_MAX; };
@@ -352,110 +347,26 @@ int cg_solve_pipe(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rn
   if (int rc = reduce_begin(0))
     return rc;
 
-  const int max_prof = o->profile ? 512 : 0;
-  if ((int)ctx->ev.size() < 2 * max_prof)
-  {
-    size_t old = ctx->ev.size();
-    ctx->ev.resize(2 * max_prof);
-    for (size_t i = old; i < ctx->ev.size(); ++i)
-      ZZZ_HIP(ctx, hipEventCreate(&ctx->ev[i]));
-  }
-  int nprof = 0;
-  ctx->prof_halo_n = 0;
-  ctx->prof_halo_wait_ms = 0.0;
   // n = A m of iteration 0, beside the first all-reduce
   if (int rc = apply(m, nvec))
     return rc;
-  // host polling: copy the state every CHECK iterations, look at it NSLOT-1 batches later
-  constexpr int CHECK = 8, NSLOT = 4;
-  EventRing<NSLOT> chk_ev;
-  ZZZ_HIP(ctx, chk_ev.create());
-  int nchk = 0;
-  bool stop = false;
   int it = 0;
-  for (; it < max_it && !stop; ++it)
+  for (; it < max_it && !S.stop; ++it)
   {
     if (int rc = update(it, 0))
       return rc;
     if (int rc = reduce_begin(it + 1)) // ... beside the halo exchange and the product below
       return rc;
-    const bool timed = nprof < max_prof && it % PROF_STRIDE == 0;
-    ctx->prof_now = timed;
-    if (timed)
-      (void)hipEventRecord(ctx->ev[2 * nprof], s);
-    if (int rc = apply(m, nvec))
+    S.product_begin(it);
+    if (int rc = S.product_end(apply(m, nvec)))
       return rc;
-    ctx->prof_now = false;
-    if (timed)
-    {
-      (void)hipEventRecord(ctx->ev[2 * nprof + 1], s);
-      ++nprof;
-    }
-    if ((it + 1) % CHECK == 0)
-    {
-      const int slot = nchk % NSLOT;
-      if (nchk >= NSLOT - 1)
-      {
-        const int old = (nchk - (NSLOT - 1)) % NSLOT;
-        ZZZ_HIP(ctx, hipEventSynchronize(chk_ev[old]));
-        if (ctx->h_state[old].converged)
-          stop = true;
-      }
-      ZZZ_HIP(ctx, hipMemcpyAsync(&ctx->h_state[slot], ctx->state.p, sizeof(CgState), hipMemcpyDeviceToHost, s));
-      ZZZ_HIP(ctx, hipEventRecord(chk_ev[slot], s));
-      ++nchk;
-    }
+    if (int rc = S.poll(it + 1))
+      return rc;
   }
   // convergence test of the last completed iteration: scalars only
   if (int rc = update(it, 1))
     return rc;
-  ZZZ_HIP(ctx, hipGetLastError());
-  CgState fin;
-  ZZZ_HIP(ctx, hipMemcpyAsync(&fin, ctx->state.p, sizeof(CgState), hipMemcpyDeviceToHost, s));
-  ZZZ_HIP(ctx, hipStreamSynchronize(s));
-  if (int rc = comm_p2p_check(ctx))
-    return rc;
-  const int its = fin.converged ? fin.iters : max_it;
-  ctx->last_iters = its;
-  if (iters)
-    *iters = its;
-  if (rnorm)
-  {
-    rnorm[0] = fin.dp;
-    rnorm[1] = fin.dp0;
-  }
-  ctx->history.resize((size_t)its + 1);
-  ZZZ_HIP(ctx, hipMemcpy(ctx->history.data(), ctx->dp_hist.p, sizeof(double) * ((size_t)its + 1), hipMemcpyDeviceToHost));
-  ctx->prof_spmv_ms = 0.0;
-  ctx->prof_spmv_n = 0;
-  const int used = std::min(nprof, (its + PROF_STRIDE - 1) / PROF_STRIDE); // launches past convergence return at once
-  for (int i = 0; i < used; ++i)
-  {
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, ctx->ev[2 * i], ctx->ev[2 * i + 1]) == hipSuccess)
-    {
-      ctx->prof_spmv_ms += ms;
-      ctx->prof_spmv_n++;
-    }
-  }
-  if (ctx->prof_spmv_n)
-    ctx->prof_spmv_ms /= (double)ctx->prof_spmv_n;
-  {
-    int cnt = 0;
-    for (int i = 0; i < ctx->prof_halo_n; ++i)
-    {
-      float ms = 0;
-      if (hipEventElapsedTime(&ms, ctx->ev_halo[(size_t)(2 * i)], ctx->ev_halo[(size_t)(2 * i + 1)]) == hipSuccess)
-      {
-        ctx->prof_halo_wait_ms += ms;
-        ++cnt;
-      }
-    }
-    if (cnt)
-      ctx->prof_halo_wait_ms /= cnt;
-    (void)hipGetLastError();
-  }
-  return finish_reason(ctx, o, fin, its);
+  return S.finish(iters, rnorm);
 }
 ZZZ_PRELOAD_TU(cg_pipe)
 } // namespace zzz

@@ -395,6 +395,85 @@ def test_chebyshev_jacobi_preconditioner(ctx, problem, order, dims, degree, rati
             ctx.cg_solve(pc=zzz.PC_CHEBYSHEV_JACOBI, **bad)
 
 
+_REPORT_KNOBS = {"ZZZ_CG_DINV_CODES": "2", "ZZZ_CG_XDEFER": "2"}  # (read when a context is created)
+
+
+def _report_context():
+    """a context on the generated P1 Poisson cube of 6 x 5 x 4 cells (multigrid needs a generated cube) whose Jacobi solves
+    take the inverse diagonal as codes and defer the solution update at any size"""
+    old = {k: os.environ.get(k) for k in _REPORT_KNOBS}
+    os.environ.update(_REPORT_KNOBS)
+    try:
+        c = zzz.Context(0)
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+    c.cube_generate("poisson", 1, 6, 5, 4)
+    c.pattern_build()
+    c.assemble_matrix(zzz.FORM_POISSON)
+    c.assemble_vector(zzz.FORM_POISSON)
+    return c
+
+
+@pytest.fixture(scope="module")
+def report_ctx():
+    with _report_context() as c:
+        yield c
+
+
+def _jacobi_with_codes(c):
+    """the solve whose kernels must not show in the report of the next one: checked here, so that no test below passes
+    because the codes were never in use"""
+    it, _, _ = c.cg_solve(pc=zzz.PC_JACOBI, rtol=1e-9)
+    info = c.cg_info()
+    assert info["dinv_codes"] > 0 and info["xdefer_k"] > 1 and info["pc_spectrum_bound"] == 0.0, info
+    return it
+
+
+def test_report_after_chebyshev_jacobi_is_its_own(report_ctx):
+    """zzz_cg_info after a classical-form Chebyshev-Jacobi solve: neither the code count of the solve before it in the
+    context nor that of its own spectrum estimate's short Jacobi solve (which runs on codes under these knobs)"""
+    c = report_ctx
+    _jacobi_with_codes(c)
+    c.cg_solve(pc=zzz.PC_CHEBYSHEV_JACOBI, rtol=1e-9)
+    info = c.cg_info()
+    print("cg_info after Chebyshev-Jacobi:", info)
+    assert info["dinv_codes"] == 0
+    assert info["xdefer_k"] == 1
+    assert info["pc_spectrum_bound"] > 0
+
+
+def test_report_after_multigrid_is_its_own(report_ctx):
+    """the same after a ZZZ_PC_MG solve (two levels: 6 x 5 x 4 and 3 x 3 x 2 cells, so that level 0 has a bound)"""
+    c = report_ctx
+    _jacobi_with_codes(c)
+    c.cg_solve(pc=zzz.PC_MG, rtol=1e-9, pc_mg_coarse_eq_limit=60)
+    assert c.mg_info()["levels"] == 2
+    info = c.cg_info()
+    print("cg_info after multigrid:", info)
+    assert info["dinv_codes"] == 0
+    assert info["xdefer_k"] == 1
+    assert info["pc_spectrum_bound"] > 0
+
+
+def test_jacobi_after_chebyshev_jacobi_is_the_fresh_solve(report_ctx):
+    """a Jacobi solve behind a Chebyshev-Jacobi one reports no spectrum bound and is, bit for bit, the Jacobi solve of a
+    fresh context"""
+    c = report_ctx
+    c.cg_solve(pc=zzz.PC_CHEBYSHEV_JACOBI, rtol=1e-9)
+    assert c.cg_info()["pc_spectrum_bound"] > 0
+    it = _jacobi_with_codes(c)
+    hist, u = c.cg_history(it + 1), c.vec_download(zzz.VEC_U)
+    with _report_context() as f:
+        itf = _jacobi_with_codes(f)
+        assert it == itf
+        np.testing.assert_array_equal(hist, f.cg_history(itf + 1))
+        np.testing.assert_array_equal(u, f.vec_download(zzz.VEC_U))
+
+
 def test_single_reduction_cg_breakdown_and_limits(ctx):
     """max_it reached, zero right-hand side and immediate convergence behave as in the classical path"""
     G = zzz.Part("poisson", 1, 6, 6, 6)
