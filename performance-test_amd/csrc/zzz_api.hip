@@ -838,20 +838,7 @@ int zzz_spmv(zzz_ctx* ctx, const double* x, double* y)
   ZZZ_HIP(ctx, hipMemsetAsync(ctx->p.p, 0, ctx->p.n * sizeof(double), ctx->stream));
   ZZZ_HIP(ctx, hipMemcpyAsync(ctx->p.p, x, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  int rc;
-  if (ctx->comm && ctx->overlap && ctx->have_tile_split)
-    rc = launch_spmv_overlapped(ctx, ctx->p.p, ctx->w.p, nullptr, nullptr);
-  else
-  {
-    if (ctx->comm)
-    {
-      rc = comm_halo_forward(ctx, ctx->p.p);
-      if (rc)
-        return rc;
-    }
-    rc = launch_spmv(ctx, ctx->p.p, ctx->w.p, nullptr, nullptr);
-  }
-  if (rc)
+  if (int rc = launch_product(ctx, ctx->p.p, ctx->w.p, nullptr, nullptr))
     return rc;
   if (ctx->renumbered)
   {

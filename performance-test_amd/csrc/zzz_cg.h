@@ -4,7 +4,6 @@
 //   CgSolve          the skeleton of a solve: prologue (histories, CgState, profile events), the timing of the product,
 //                    the host's poll of the device state, and the epilogue (state read-back, iteration count, norms,
 //                    history, profile averages, KSPConvergedReason)
-//   cg_apply_csr     the product on the assembled operator, halo exchange included
 //   cg_report_reset  what zzz_cg_info says about a solve, at its "nothing special" values
 // Not part of the ABI.
 #pragma once
@@ -155,9 +154,6 @@ struct CgSolve
 };
 
 // zzz_cg.hip
-// y = A x on the assembled operator, ghost values of x fetched first (overlapped with the interior tiles where the
-// partition allows); parts / np: the partials of <x,y> and, with dot_r, of <dot_r,x> and the test norm behind them
-int cg_apply_csr(zzz_ctx* ctx, double* x, double* y, double* parts, int* np, const double* dot_r = nullptr, int nn_is_rr = 0);
 void cg_report_reset(zzz_ctx* ctx); // last_pc_bound, last_solve_red_overlapped, last_solve_xdefer_k, last_solve_dinv_codes
 int dinv_codes_build(zzz_ctx* ctx, int64_t n, DinvCodes& dzc); // ctx->dinv as 16-bit codes (dzc.codes stays null: too many values)
 bool loop_exceeds_cache(zzz_ctx* ctx, int nvec);               // operator + nvec vectors against the Infinity Cache

@@ -1013,19 +1013,6 @@ void cg_report_reset(zzz_ctx* ctx)
   ctx->last_solve_dinv_codes = 0;
 }
 
-int cg_apply_csr(zzz_ctx* ctx, double* x, double* y, double* parts, int* np, const double* dot_r, int nn_is_rr)
-{
-  if (ctx->comm)
-  {
-    // partitioned operator: halo of x overlapped with the interior tiles
-    if (ctx->overlap && ctx->have_tile_split)
-      return launch_spmv_overlapped(ctx, x, y, parts, np, dot_r, nn_is_rr);
-    if (int rc = comm_halo_forward(ctx, x))
-      return rc;
-  }
-  return launch_spmv(ctx, x, y, parts, np, dot_r, nn_is_rr);
-}
-
 int CgSolve::begin(zzz_ctx* c, const zzz_solver_opts* opts, int prof_stride)
 {
   ctx = c;
@@ -1251,7 +1238,7 @@ int cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
 
   auto apply = [&](double* x, double* y, double* parts, int* np) -> int {
     if (o->op == ZZZ_OP_CSR)
-      return cg_apply_csr(ctx, x, y, parts, np);
+      return launch_product(ctx, x, y, parts, np);
     if (multi)
       if (int rc = comm_halo_forward(ctx, x))
         return rc;
@@ -1618,7 +1605,7 @@ struct ChebPlan
   int degree = 3;
   double hi = 0.0, theta = 0.0, delta = 0.0, sigma = 0.0;
   double *g = nullptr, *d = nullptr, *d2 = nullptr; // residual of the polynomial's recurrence; its direction, two buffers
-  bool fused = false, split = false;
+  bool fused = false;
 };
 
 // Spectrum bound (Gershgorin, tightened by the Lanczos estimate), constants, buffers.  Runs the estimate's short Jacobi
@@ -1678,8 +1665,8 @@ static int chebyshev_setup(zzz_ctx* ctx, const zzz_solver_opts* o, ChebPlan& C)
   C.fused = sellp_active(ctx);
   if (const char* e = getenv("ZZZ_CHEB_FUSED"))
     C.fused = C.fused && atoi(e) != 0;
-  C.split = multi && ctx->overlap && ctx->have_tile_split;
-  if (C.split && !ctx->have_group_split)
+  // (the overlapped product of a partition without a group split is the tile kernel's, launch_product: no epilogue there)
+  if (multi && ctx->overlap && ctx->have_tile_split && !ctx->have_group_split)
     C.fused = false;
   ZZZ_HIP(ctx, ctx->cheb_d.alloc((size_t)ctx->nloc())); // ghost entries: the product gathers it
   ZZZ_HIP(ctx, ctx->cheb_d2.alloc((size_t)ctx->nloc()));
@@ -1698,7 +1685,6 @@ static int chebyshev_setup(zzz_ctx* ctx, const zzz_solver_opts* o, ChebPlan& C)
 static int chebyshev_terms(zzz_ctx* ctx, const ChebPlan& C, int norm, bool dots, double* pa, double* pb, int* np_last)
 {
   const int64_t n = ctx->n_owned * ctx->bs;
-  const bool multi = ctx->comm != nullptr;
   const int g = vgrid(n);
   hipStream_t s = ctx->stream;
   const int* stop_flag = reinterpret_cast<const int*>(ctx->state.p);
@@ -1720,35 +1706,14 @@ static int chebyshev_terms(zzz_ctx* ctx, const ChebPlan& C, int norm, bool dots,
       E.r = ctx->r.p;
       E.c1 = c1;
       E.c2 = c2;
-      double* parts = last ? ctx->part_a.p : nullptr;
-      int rc;
-      if (C.split)
-        rc = launch_sellp_overlapped(ctx, dcur, dalt, parts, last ? np_last : nullptr, nullptr, nn_is_rr, &E);
-      else
-      {
-        if (multi)
-          if (int rh = comm_halo_forward(ctx, dcur))
-            return rh;
-        rc = launch_sellp(ctx, dcur, dalt, parts, last ? np_last : nullptr, nullptr, nn_is_rr, &E);
-      }
-      if (rc)
+      if (int rc = launch_product(ctx, dcur, dalt, last ? ctx->part_a.p : nullptr, last ? np_last : nullptr, nullptr, nn_is_rr, &E))
         return rc;
       std::swap(dcur, dalt);
       continue;
     }
     // terms as launches of their own: the product's output goes to the second direction buffer (free in this form; the
     // CG vector w is the single-reduction form's A p and must survive)
-    int rc;
-    if (C.split)
-      rc = launch_spmv_overlapped(ctx, dcur, C.d2, nullptr, nullptr);
-    else
-    {
-      if (multi)
-        if (int rh = comm_halo_forward(ctx, dcur))
-          return rh;
-      rc = launch_spmv(ctx, dcur, C.d2, nullptr, nullptr);
-    }
-    if (rc)
+    if (int rc = launch_product(ctx, dcur, C.d2, nullptr, nullptr))
       return rc;
     hipLaunchKernelGGL(k_cheb_step, dim3(g), dim3(VB), 0, s, stop_flag, C.d2, ctx->dinv.p, c1, c2, last ? 1 : 0, C.g, dcur,
                        ctx->z.p, ctx->r.p, norm, pa, pb, n);
@@ -1829,7 +1794,7 @@ static int cg_solve_chebyshev(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters
                        it, P, rz_src, nn_src, n_rz, ctx->z.p, ctx->p.p, ctx->u.p, n, 1);
     int np = 0;
     S.product_begin(it);
-    if (int rc = S.product_end(cg_apply_csr(ctx, ctx->p.p, ctx->w.p, ctx->part_a.p, &np)))
+    if (int rc = S.product_end(launch_product(ctx, ctx->p.p, ctx->w.p, ctx->part_a.p, &np)))
       return rc;
     if (multi)
     {
@@ -1991,7 +1956,7 @@ static int cg_solve_single_reduction(zzz_ctx* ctx, const zzz_solver_opts* o, int
   int np = 0;
   // s = A z with the three partial dot products; then (multi) one all-reduce of three doubles
   auto apply = [&]() -> int {
-    if (int rc = cg_apply_csr(ctx, ctx->z.p, ctx->sr_s.p, parts, &np, ctx->r.p, nn_is_rr))
+    if (int rc = launch_product(ctx, ctx->z.p, ctx->sr_s.p, parts, &np, ctx->r.p, nn_is_rr))
       return rc;
     if (multi)
     {

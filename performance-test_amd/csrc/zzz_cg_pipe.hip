@@ -13,7 +13,7 @@
 //     x += alpha p;  r -= alpha s;  w -= alpha z                            (u -= alpha q = D^-1 r: recomputed)
 //
 // One iteration is TWO launches on the main stream: k_pipe_update (everything but the product, one pass over the
-// vectors) and the product n = A m on whatever form the matrix took (launch_spmv / launch_spmv_overlapped; the partials
+// vectors) and the product n = A m on whatever form the matrix took (launch_product; the partials
 // the product leaves are not used).  k_pipe_update(i) takes the reduced (gamma, delta, norm^2) of iteration i, tests,
 // forms alpha and beta, updates z, p, s, x, r, w, writes m = D^-1 w for the product to gather and leaves the block
 // partials of gamma, delta and norm^2 of iteration i + 1.
@@ -312,7 +312,7 @@ int cg_solve_pipe(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rn
   // them makes the launches behind a converged solve return at once, as in the other forms)
   auto apply = [&](double* v, double* y) -> int {
     int np = 0;
-    return cg_apply_csr(ctx, v, y, ctx->part_a.p, &np);
+    return launch_product(ctx, v, y, ctx->part_a.p, &np);
   };
   // the two sets of partials, and where the kernel of iteration `it` finds its sums
   auto parts = [&](int it) { return ctx->pipe_parts.p + (size_t)(it & 1) * 3 * VGRID_MAX; };

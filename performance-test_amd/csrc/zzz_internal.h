@@ -531,9 +531,64 @@ void to_caller(const zzz_ctx* ctx, const double* in, double* out, bool owned_onl
 int csr_to_caller(zzz_ctx* ctx, std::vector<zzz::rp_t>& rowptr_c, int32_t* cols_c, double* vals_c, bool need_cols);
 int csr_values_to_internal(zzz_ctx* ctx, const double* vals_c, std::vector<double>& vals_i);
 // kernels_spmv
-// y = A x (x has ncols entries), optionally per-block partials of <x_owned, y>
+// The five forms of a product y = A x: with the per-workgroup partial sums of <x, y> (DOT), with those of <r, x> and of the
+// test norm beside them (SR, single-reduction CG), as a term of the Chebyshev-Jacobi polynomial (ChebEpi), the last term
+// with its sums.  Every product kernel's table of instantiations (tile_kernels, sp_kernels, ...) is indexed by this and
+// by the load policy of the matrix stream, the non-temporal loads first.
+enum ProductMode { PM_DOT_SR, PM_DOT, PM_PLAIN, PM_CHEB_DOT, PM_CHEB, PM_COUNT };
+enum ProductLoad { LOAD_NT, LOAD_PLAIN };
+// One product as its launchers see it: what the caller asked for and the selection made from it, once per product
+struct ProductCall
+{
+  const double* x = nullptr;
+  double* y = nullptr;
+  double* partials = nullptr;    // != null: the product also leaves partial sums (the DOT forms)
+  const int* stop = nullptr;     // CgState::converged: a product with sums is skipped once it is set
+  const int32_t* list = nullptr; // != null: only the nlist listed items (interior or boundary part of a partitioned matrix)
+  int64_t nlist = 0;
+  const double* rvec = nullptr;
+  int nn_is_rr = 0;
+  const ChebEpi* epi = nullptr;
+  ProductMode mode = PM_PLAIN;
+  ProductLoad load = LOAD_PLAIN; // set by the driver of the kernel family: each has its own size rule
+  int special = 0;               // operator stream: 1 the block-row kernel serves the call, 2 the block-window kernel
+};
+inline ProductCall product_call(const zzz_ctx* ctx, const double* x, double* y, double* partials, const double* rvec, int nn_is_rr,
+                                const ChebEpi* epi)
+{
+  ProductCall c;
+  c.x = x;
+  c.y = y;
+  c.epi = epi;
+  if (partials)
+  {
+    c.partials = partials;
+    c.stop = reinterpret_cast<const int*>(ctx->state.p);
+    c.rvec = rvec;
+    c.nn_is_rr = nn_is_rr;
+  }
+  c.mode = epi ? (partials ? PM_CHEB_DOT : PM_CHEB) : partials ? (rvec ? PM_DOT_SR : PM_DOT) : PM_PLAIN;
+  return c;
+}
+typedef void (*ProductLauncher)(zzz_ctx* ctx, int grid, const ProductCall& c);
+// the interior or the boundary part of a partitioned product: its items, their list and its workgroups (0 where n is 0)
+struct ProductPart
+{
+  int64_t n;
+  const int32_t* list;
+  int grid;
+};
+// y = A x on this rank's matrix as it stands (x has ncols entries, ghosts in place), optionally per-block partials of
+// <x_owned, y>; epi (operator stream only): the product carries a Chebyshev term
 int launch_spmv(zzz_ctx* ctx, const double* x, double* y, double* partials, int* npartials, const double* rvec = nullptr,
-                int nn_is_rr = 0);
+                int nn_is_rr = 0, const ChebEpi* epi = nullptr);
+// ... on a possibly partitioned operator: the forward halo of x first, overlapped with the interior part where the
+// partition is split (ZZZ_OVERLAP), blocking otherwise
+int launch_product(zzz_ctx* ctx, double* x, double* y, double* partials, int* npartials, const double* rvec = nullptr,
+                   int nn_is_rr = 0, const ChebEpi* epi = nullptr);
+// halo begin / interior launch / halo end / boundary launch (its partials behind the interior's) / number of partials
+int launch_overlapped(zzz_ctx* ctx, double* x, ProductCall c, const ProductPart& in, const ProductPart& bd, ProductLauncher launch,
+                      int* npartials);
 // operator stream (zzz_sellp.hip)
 int sell_update(zzz_ctx* ctx, bool structure);
 bool sellp_active(zzz_ctx* ctx);
@@ -542,10 +597,8 @@ int sellp_pattern_bounds(zzz_ctx* ctx);
 int sellp_capacity_rows(zzz_ctx* ctx); // sp_crow := capacity-based row starts of the compacted copy (+ its allocation)
 int64_t sellp_stream_bytes(const zzz_ctx* ctx);
 constexpr int SP_DICT_LDS_ENTRIES = 2048; // a value dictionary of at most this many entries is copied into LDS by every workgroup (16 KiB: eight per CU)
-int launch_sellp(zzz_ctx* ctx, const double* x, double* y, double* partials, int* npartials, const double* rvec, int nn_is_rr,
-                 const ChebEpi* epi = nullptr);
-int launch_sellp_overlapped(zzz_ctx* ctx, double* x, double* y, double* partials, int* npartials, const double* rvec,
-                            int nn_is_rr, const ChebEpi* epi = nullptr);
+int launch_sellp(zzz_ctx* ctx, ProductCall c, int* npartials);
+int launch_sellp_overlapped(zzz_ctx* ctx, double* x, ProductCall c, int* npartials);
 
 // kernels_assemble
 int launch_assemble_matrix(zzz_ctx* ctx, int form);
@@ -605,7 +658,5 @@ int comm_halo_forward(zzz_ctx* ctx, double* vec);
 int comm_halo_begin(zzz_ctx* ctx, double* vec); // on the comm stream, after the work enqueued so far
 int comm_halo_end(zzz_ctx* ctx);                // main stream waits for the halo
 int build_tile_split(zzz_ctx* ctx);
-int launch_spmv_overlapped(zzz_ctx* ctx, double* x, double* y, double* partials, int* npartials,
-                           const double* rvec = nullptr, int nn_is_rr = 0);
 void comm_destroy(zzz_ctx* ctx);
 } // namespace zzz

@@ -61,6 +61,17 @@ inline int grid_cap(int64_t items, int per, int cap)
   return (int)g;
 }
 
+// the fields the kernel-argument structs of the specialised products (PipeArgs, BlkArgs, WinArgs) have in common
+template <typename Args>
+inline void product_args_tail(Args& a, const ProductCall& c)
+{
+  a.partials = c.partials;
+  a.stop_flag = c.stop;
+  a.nlist = c.nlist;
+  a.pstride = SPMV_PSTRIDE;
+  a.nn_is_rr = c.nn_is_rr;
+}
+
 // the stream's value dictionaries (zzz_sellp_dict.hip), built at the stream's first use after an assembly
 int sp_dict_build(zzz_ctx* ctx);
 int sp_sd_build(zzz_ctx* ctx);
@@ -71,8 +82,7 @@ constexpr int SP_ONE_WGS = 4; // (five fit its 89 registers: 73.4 us against 70-
 constexpr int SP_ONE_WGS_SR = 4; // ... with the single-reduction form's extra sums
 int sellp_pipe_wgs(const zzz_ctx* ctx, bool sr); // workgroups per CU if spmv_one_kernel serves the context's stream; 0: it does not
 int sellp_pairs_build(zzz_ctx* ctx); // marks the affine slice pairs of a stream of one-chunk slices (spmv_one_kernel)
-bool launch_sellp_pipe(zzz_ctx* ctx, bool dot, bool nt, int grid, const double* x, double* y, double* partials, const int* stop,
-                       const int32_t* group_list, int64_t nlist, const double* rvec, int nn_is_rr);
+bool launch_sellp_pipe(zzz_ctx* ctx, int grid, const ProductCall& c);
 // special forms (block rows, block windows): build what applies; true if one of them serves the products of this matrix
 bool sellp_special_build(zzz_ctx* ctx);
 int sell_pack_generic(zzz_ctx* ctx); // the generic operator stream of the current values (zzz_sellp_pack.hip)
@@ -81,12 +91,10 @@ int sellp_need_generic(zzz_ctx* ctx); // ... packed now if a launch needs it and
 int sellp_win_build(zzz_ctx* ctx);
 bool sellp_win_serves(const zzz_ctx* ctx);
 int sellp_win_grid(const zzz_ctx* ctx, int64_t items);
-bool launch_sellp_win(zzz_ctx* ctx, bool dot, bool nt, int grid, const double* x, double* y, double* partials, const int* stop,
-                      const int32_t* list, int64_t nlist, const double* rvec, int nn_is_rr, const ChebEpi* epi = nullptr);
+bool launch_sellp_win(zzz_ctx* ctx, int grid, const ProductCall& c);
 // block-row form for block size 3 (zzz_sellp_blk.hip)
 int sellp_blk_build(zzz_ctx* ctx);
 bool sellp_blk_serves(const zzz_ctx* ctx);
 int sellp_blk_grid(const zzz_ctx* ctx, int64_t items);
-bool launch_sellp_blk(zzz_ctx* ctx, bool dot, bool nt, int grid, const double* x, double* y, double* partials, const int* stop,
-                      const int32_t* list, int64_t nlist, const double* rvec, int nn_is_rr, const ChebEpi* epi = nullptr);
+bool launch_sellp_blk(zzz_ctx* ctx, int grid, const ProductCall& c);
 } // namespace zzz

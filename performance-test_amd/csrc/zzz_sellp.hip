@@ -531,156 +531,118 @@ static int sp_grid(const zzz_ctx* ctx, int64_t ngroups, bool sr, bool plain)
   return (int)gs;
 }
 
-template <bool DOT>
-static void launch_one(zzz_ctx* ctx, int grid, const double* x, double* y, double* partials, const int* stop,
-                       const int32_t* group_list, int64_t nlist, const double* rvec, int nn_is_rr,
-                       const ChebEpi* epi = nullptr, int special = 0)
+// The generic kernel's instantiations: [mode][load], then by the stream's layout and the form of its values.  The kernel
+// takes rvec at run time, so the single-reduction form is the DOT instantiation.
+enum SpLayout { SP_PLAIN, SP_SORTED, SP_WINDOWED, SP_LAYOUTS };
+using SpKernel = decltype(&spmv_sellp_kernel<false, false, false>);
+struct SpVariants
 {
+  SpKernel k[SP_LAYOUTS][4]; // [layout][DICT]
+};
+template <bool DOT, bool CHEB, bool NT>
+constexpr SpVariants sp_variants()
+{
+  return {{{spmv_sellp_kernel<DOT, NT, false, CHEB, false, 0>, spmv_sellp_kernel<DOT, NT, false, CHEB, false, 1>,
+            spmv_sellp_kernel<DOT, NT, false, CHEB, false, 2>, spmv_sellp_kernel<DOT, NT, false, CHEB, false, 3>},
+           {spmv_sellp_kernel<DOT, NT, true, CHEB, false, 0>, spmv_sellp_kernel<DOT, NT, true, CHEB, false, 1>,
+            spmv_sellp_kernel<DOT, NT, true, CHEB, false, 2>, spmv_sellp_kernel<DOT, NT, true, CHEB, false, 3>},
+           // (windowed groups never read the slices' own dictionaries)
+           {spmv_sellp_kernel<DOT, NT, false, CHEB, true, 0>, spmv_sellp_kernel<DOT, NT, false, CHEB, true, 1>,
+            spmv_sellp_kernel<DOT, NT, false, CHEB, true, 2>, nullptr}}};
+}
+static const SpVariants sp_kernels[PM_COUNT][2] = {{sp_variants<true, false, true>(), sp_variants<true, false, false>()},
+                                                   {sp_variants<true, false, true>(), sp_variants<true, false, false>()},
+                                                   {sp_variants<false, false, true>(), sp_variants<false, false, false>()},
+                                                   {sp_variants<true, true, true>(), sp_variants<true, true, false>()},
+                                                   {sp_variants<false, true, true>(), sp_variants<false, true, false>()}};
+
+static void launch_one(zzz_ctx* ctx, int grid, const ProductCall& c)
+{
+  // special: the caller sized the grid and chose the list for the block-row kernel (1: block size 3) or the block-window kernel
+  // (2: long scalar rows)
+  if (c.special == 1 && launch_sellp_blk(ctx, grid, c))
+    return;
+  if (c.special == 2 && launch_sellp_win(ctx, grid, c))
+    return;
+  if (launch_sellp_pipe(ctx, grid, c))
+    return;
+  // windowed groups: their codes index the LDS window the kernel loads per group
+  const SpLayout layout = ctx->sp_sorted ? SP_SORTED : ctx->sp_win_max > 0 ? SP_WINDOWED : SP_PLAIN;
+  size_t lds = layout == SP_WINDOWED ? (size_t)ctx->sp_win_max * sizeof(double) : 0;
+  // the values: 3 the slices' own dictionaries, 2 the stream's dictionary in LDS, 1 the same in memory, 0 doubles
+  int dict = 0;
+  if (ctx->sp_sd_on && layout != SP_WINDOWED)
+  {
+    dict = 3;
+    lds = (size_t)4 * SD_MAX * sizeof(double);
+  }
+  else if (ctx->sp_dict_on && ctx->sp_dict_n <= SP_DICT_LDS_ENTRIES)
+  {
+    dict = 2;
+    lds += (size_t)((ctx->sp_dict_n + 1) & ~1) * sizeof(double);
+  }
+  else if (ctx->sp_dict_on)
+    dict = 1;
+  hipLaunchKernelGGL(sp_kernels[c.mode][c.load].k[layout][dict], dim3(grid), dim3(SP_BLOCK), lds, ctx->stream,
+                     reinterpret_cast<const int2*>(ctx->sp_desc.p), ctx->sp_vals.p, ctx->sp_codes16.p, ctx->sp_codes32.p,
+                     ctx->sp_meta.p, ctx->sp_perm.p, c.x, c.y, (int)ctx->nrows, ctx->nslices, c.partials, c.stop, c.list, c.nlist,
+                     c.rvec, SPMV_PSTRIDE, c.nn_is_rr, c.epi ? *c.epi : ChebEpi(), reinterpret_cast<const int2*>(ctx->sp_win_info.p),
+                     reinterpret_cast<const int2*>(ctx->sp_win_seg.p), dict == 3 ? ctx->sp_vcode8.p : ctx->sp_vcode.p,
+                     dict == 3 ? ctx->sp_sd_vals.p : ctx->sp_dset.dict.p, ctx->sp_dict_n, ctx->sp_sd_info.p, ctx->sp_sd_off.p);
+}
+
+// what both drivers decide once per product: the special form that serves it (the special forms carry the Chebyshev
+// epilogue; a partitioned product needs the form's own interior / boundary lists) and the load policy
+static int sp_prepare(zzz_ctx* ctx, ProductCall& c, bool split)
+{
+  c.special = (sellp_blk_serves(ctx) && (!split || ctx->bk_have_split)) ? 1
+              : (sellp_win_serves(ctx) && (!split || ctx->bw_have_split)) ? 2 : 0;
   // load policy by stream size, as for the tile kernel: a stream that stays in the 256 MiB Infinity Cache from
   // one CG iteration to the next is read with plain loads, a larger one with non-temporal loads
   bool nt = sp_stream_nt(ctx);
   if (!ctx->spmv_auto)
     nt = (ctx->spmv_variant & 1) != 0;
-  // special: the caller sized the grid and chose the list for the block-row kernel (1: block size 3) or the block-window kernel
-  // (2: long scalar rows)
-  if (special == 1 && launch_sellp_blk(ctx, DOT, nt, grid, x, y, partials, stop, group_list, nlist, rvec, nn_is_rr, epi))
-    return;
-  if (special == 2 && launch_sellp_win(ctx, DOT, nt, grid, x, y, partials, stop, group_list, nlist, rvec, nn_is_rr, epi))
-    return;
-  if (!epi && launch_sellp_pipe(ctx, DOT, nt, grid, x, y, partials, stop, group_list, nlist, rvec, nn_is_rr))
-    return;
-  const int2* off = reinterpret_cast<const int2*>(ctx->sp_desc.p);
-  const int2* winfo = reinterpret_cast<const int2*>(ctx->sp_win_info.p);
-  const int2* wseg = reinterpret_cast<const int2*>(ctx->sp_win_seg.p);
-#define ZZZ_SP_GO6(NT, PERM, WIN, LDSB, DICT)                                                                          \
-  do                                                                                                                   \
-  {                                                                                                                    \
-    const uint16_t* VC_ = (DICT) == 3 ? ctx->sp_vcode8.p : ctx->sp_vcode.p;         \
-    const double* DG_ = (DICT) == 3 ? ctx->sp_sd_vals.p : ctx->sp_dset.dict.p;                                         \
-    if (epi)                                                                                                           \
-      hipLaunchKernelGGL((spmv_sellp_kernel<DOT, NT, PERM, true, WIN, DICT>), dim3(grid), dim3(SP_BLOCK), LDSB,         \
-                         ctx->stream, off, ctx->sp_vals.p, ctx->sp_codes16.p, ctx->sp_codes32.p, ctx->sp_meta.p,           \
-                         ctx->sp_perm.p, x, y, (int)ctx->nrows, ctx->nslices, partials, stop, group_list, nlist, rvec,     \
-                         SPMV_PSTRIDE, nn_is_rr, *epi, winfo, wseg, VC_, DG_, ctx->sp_dict_n,                              \
-                         ctx->sp_sd_info.p, ctx->sp_sd_off.p);                                                         \
-    else                                                                                                               \
-      hipLaunchKernelGGL((spmv_sellp_kernel<DOT, NT, PERM, false, WIN, DICT>), dim3(grid), dim3(SP_BLOCK), LDSB,        \
-                         ctx->stream, off, ctx->sp_vals.p, ctx->sp_codes16.p, ctx->sp_codes32.p, ctx->sp_meta.p,           \
-                         ctx->sp_perm.p, x, y, (int)ctx->nrows, ctx->nslices, partials, stop, group_list, nlist, rvec,     \
-                         SPMV_PSTRIDE, nn_is_rr, ChebEpi(), winfo, wseg, VC_, DG_, ctx->sp_dict_n,                         \
-                         ctx->sp_sd_info.p, ctx->sp_sd_off.p);                                                         \
-  } while (0)
-#define ZZZ_SP_GO5(NT, PERM, WIN, LDSB)                                                                                \
-  do                                                                                                                   \
-  {                                                                                                                    \
-    if (ctx->sp_sd_on && !(WIN))                                                                                       \
-      ZZZ_SP_GO6(NT, PERM, false, (size_t)4 * SD_MAX * sizeof(double), 3);                                             \
-    else if (ctx->sp_dict_on && ctx->sp_dict_n <= SP_DICT_LDS_ENTRIES)                                                     \
-      ZZZ_SP_GO6(NT, PERM, WIN, (LDSB) + (size_t)((ctx->sp_dict_n + 1) & ~1) * sizeof(double), 2);                     \
-    else if (ctx->sp_dict_on)                                                                                          \
-      ZZZ_SP_GO6(NT, PERM, WIN, LDSB, 1);                                                                              \
-    else                                                                                                               \
-      ZZZ_SP_GO6(NT, PERM, WIN, LDSB, 0);                                                                              \
-  } while (0)
-#define ZZZ_SP_GO(NT, PERM) ZZZ_SP_GO5(NT, PERM, false, 0)
-  if (ctx->sp_win_max > 0 && !ctx->sp_sorted)
-  {
-    // windowed groups: their codes index the LDS window the kernel loads per group
-    const size_t ldsb = (size_t)ctx->sp_win_max * sizeof(double);
-    if (nt)
-      ZZZ_SP_GO5(true, false, true, ldsb);
-    else
-      ZZZ_SP_GO5(false, false, true, ldsb);
-  }
-  else if (ctx->sp_sorted)
-  {
-    if (nt)
-      ZZZ_SP_GO(true, true);
-    else
-      ZZZ_SP_GO(false, true);
-  }
-  else
-  {
-    if (nt)
-      ZZZ_SP_GO(true, false);
-    else
-      ZZZ_SP_GO(false, false);
-  }
-#undef ZZZ_SP_GO
-#undef ZZZ_SP_GO5
-#undef ZZZ_SP_GO6
+  c.load = nt ? LOAD_NT : LOAD_PLAIN;
+  return c.special ? ZZZ_OK : sellp_need_generic(ctx);
 }
 
-int launch_sellp(zzz_ctx* ctx, const double* x, double* y, double* partials, int* npartials, const double* rvec, int nn_is_rr,
-                 const ChebEpi* epi)
+int launch_sellp(zzz_ctx* ctx, ProductCall c, int* npartials)
 {
-  const int* stop = partials ? reinterpret_cast<const int*>(ctx->state.p) : nullptr; // CgState::converged
-  const int blk = sellp_blk_serves(ctx) ? 1 : (sellp_win_serves(ctx) ? 2 : 0); // (the special forms carry the Chebyshev epilogue)
-  if (!blk)
-    if (int rc = sellp_need_generic(ctx))
-      return rc;
-  const int gs = blk == 1 ? sellp_blk_grid(ctx, ctx->bk_slices) : blk == 2 ? sellp_win_grid(ctx, ctx->bw_nblk)
-                          : sp_grid(ctx, (ctx->nslices + 3) / 4, (partials && rvec), !epi);
-  if (partials)
-  {
-    launch_one<true>(ctx, gs, x, y, partials, stop, nullptr, 0, rvec, nn_is_rr, epi, blk);
-    if (npartials)
-      *npartials = gs;
-  }
-  else
-    launch_one<false>(ctx, gs, x, y, nullptr, stop, nullptr, 0, nullptr, 0, epi, blk);
+  if (int rc = sp_prepare(ctx, c, false))
+    return rc;
+  const int gs = c.special == 1 ? sellp_blk_grid(ctx, ctx->bk_slices) : c.special == 2 ? sellp_win_grid(ctx, ctx->bw_nblk)
+                 : sp_grid(ctx, (ctx->nslices + 3) / 4, c.mode == PM_DOT_SR, !c.epi);
+  launch_one(ctx, gs, c);
+  if (c.partials && npartials)
+    *npartials = gs;
   ZZZ_HIP(ctx, hipGetLastError());
   return ZZZ_OK;
 }
 
 // Partitioned matrix: forward halo of x overlapped with the groups that reference no ghost column
-// (scheme and the 7-of-8 workgroup slots: launch_spmv_overlapped in zzz_spmv.hip)
-int launch_sellp_overlapped(zzz_ctx* ctx, double* x, double* y, double* partials, int* npartials, const double* rvec,
-                            int nn_is_rr, const ChebEpi* epi)
+// (scheme and the 7-of-8 workgroup slots: launch_overlapped in zzz_spmv.hip)
+int launch_sellp_overlapped(zzz_ctx* ctx, double* x, ProductCall c, int* npartials)
 {
-  const int* stop = partials ? reinterpret_cast<const int*>(ctx->state.p) : nullptr;
-  const bool plain = !epi;
-  const int blk = (sellp_blk_serves(ctx) && ctx->bk_have_split) ? 1 : (sellp_win_serves(ctx) && ctx->bw_have_split) ? 2 : 0;
-  if (!blk)
-    if (int rc = sellp_need_generic(ctx))
-      return rc;
+  if (int rc = sp_prepare(ctx, c, true))
+    return rc;
+  const int blk = c.special;
+  const bool plain = !c.epi, sr = c.mode == PM_DOT_SR;
   const int64_t gi = blk == 1 ? ctx->bk_n_interior : blk == 2 ? ctx->bw_n_interior : ctx->n_groups_interior;
   const int64_t gb = blk == 1 ? ctx->bk_n_boundary : blk == 2 ? ctx->bw_n_boundary : ctx->n_groups_boundary;
   const int32_t* list_in = blk == 1 ? ctx->bk_list_interior.p : blk == 2 ? ctx->bw_list_interior.p : ctx->groups_interior.p;
   const int32_t* list_bd = blk == 1 ? ctx->bk_list_boundary.p : blk == 2 ? ctx->bw_list_boundary.p : ctx->groups_boundary.p;
-  auto special_grid = [&](int64_t items) { return blk == 1 ? sellp_blk_grid(ctx, items) : sellp_win_grid(ctx, items); };
-  int g_in = gi ? (blk ? special_grid(gi) : sp_grid(ctx, gi, (partials && rvec), plain)) : 0;
-  const int pw = plain ? sellp_pipe_wgs(ctx, partials && rvec) : 0;
+  auto grid = [&](int64_t items) {
+    return !items ? 0 : blk == 1 ? sellp_blk_grid(ctx, items) : blk == 2 ? sellp_win_grid(ctx, items) : sp_grid(ctx, items, sr, plain);
+  };
+  int g_in = grid(gi);
+  const int pw = plain ? sellp_pipe_wgs(ctx, sr) : 0;
   const int room = 256 * ((pw ? pw : 8) - 1); // (one workgroup slot per CU left to the exchange's kernel; the block-row
   if (!blk && g_in > room && ctx->nneigh > 0) //  kernel's one workgroup per CU leaves half the CU's wavefront slots free)
     g_in = room;
-  const int g_bd = gb ? (blk ? special_grid(gb) : sp_grid(ctx, gb, (partials && rvec), plain)) : 0;
-  if (partials && (size_t)(g_in + g_bd) > (size_t)SPMV_PSTRIDE)
+  const int g_bd = grid(gb);
+  if (c.partials && (size_t)(g_in + g_bd) > (size_t)SPMV_PSTRIDE)
     return fail(ctx, ZZZ_ERR_ARG, "partials buffer too small");
-  int rc = comm_halo_begin(ctx, x);
-  if (rc)
-    return rc;
-  if (gi)
-  {
-    if (partials)
-      launch_one<true>(ctx, g_in, x, y, partials, stop, list_in, gi, rvec, nn_is_rr, epi, blk);
-    else
-      launch_one<false>(ctx, g_in, x, y, nullptr, stop, list_in, gi, nullptr, 0, epi, blk);
-  }
-  rc = comm_halo_end(ctx);
-  if (rc)
-    return rc;
-  if (gb)
-  {
-    if (partials)
-      launch_one<true>(ctx, g_bd, x, y, partials + g_in, stop, list_bd, gb, rvec, nn_is_rr, epi, blk);
-    else
-      launch_one<false>(ctx, g_bd, x, y, nullptr, stop, list_bd, gb, nullptr, 0, epi, blk);
-  }
-  if (npartials)
-    *npartials = g_in + g_bd;
-  ZZZ_HIP(ctx, hipGetLastError());
-  return ZZZ_OK;
+  return launch_overlapped(ctx, x, c, {gi, list_in, g_in}, {gb, list_bd, g_bd}, launch_one, npartials);
 }
 ZZZ_PRELOAD_TU(sellp)
 } // namespace zzz

@@ -729,6 +729,17 @@ __global__ __launch_bounds__(BK_THREADS) void spmv_blk3_kernel(const int2* __res
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
+// [mode][load] of either form: every instantiation there is.  FORM 1 keeps the whole block table in LDS and gets the
+// dynamic-LDS attribute (sellp_blk_build).
+using BlkKernel = decltype(&spmv_blk3_kernel<false, false, false, 1>);
+template <int FORM>
+static const BlkKernel blk_kernels[PM_COUNT][2] = {
+    {spmv_blk3_kernel<true, true, true, FORM>, spmv_blk3_kernel<true, true, false, FORM>},
+    {spmv_blk3_kernel<true, false, true, FORM>, spmv_blk3_kernel<true, false, false, FORM>},
+    {spmv_blk3_kernel<false, false, true, FORM>, spmv_blk3_kernel<false, false, false, FORM>},
+    {spmv_blk3_kernel<true, false, true, FORM, true>, spmv_blk3_kernel<true, false, false, FORM, true>},
+    {spmv_blk3_kernel<false, false, true, FORM, true>, spmv_blk3_kernel<false, false, false, FORM, true>}};
+
 // The block-row form of a freshly assembled matrix of block size 3 (called at the stream's first use, behind the dictionaries).
 // Declined (bk_on stays false, nothing else changes): another block size, sorted rows, more distinct blocks than the table
 // holds, columns beyond 16-bit codes, ZZZ_SELLP_BLK=0.
@@ -846,24 +857,9 @@ int sellp_blk_build(zzz_ctx* ctx)
   ctx->bk_bytes = (int64_t)bytes + (ctx->bk_form == 1 ? (int64_t)h[2] * 72 : (int64_t)h[2] * 32 + (int64_t)ctx->bk_ndict * 8);
   if (!ctx->bk_lds_attr)
   {
-#define ZZZ_BK_ATTR(DOT, SR, NT)                                                                                                   \
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&spmv_blk3_kernel<DOT, SR, NT, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                            BK_TAB_MAX * 72)
-    ZZZ_BK_ATTR(true, true, true);
-    ZZZ_BK_ATTR(true, true, false);
-    ZZZ_BK_ATTR(true, false, true);
-    ZZZ_BK_ATTR(true, false, false);
-    ZZZ_BK_ATTR(false, false, true);
-    ZZZ_BK_ATTR(false, false, false);
-#define ZZZ_BK_ATTRC(DOT, NT)                                                                                                      \
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&spmv_blk3_kernel<DOT, false, NT, 1, true>),                            \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, BK_TAB_MAX * 72)
-    ZZZ_BK_ATTRC(true, true);
-    ZZZ_BK_ATTRC(true, false);
-    ZZZ_BK_ATTRC(false, true);
-    ZZZ_BK_ATTRC(false, false);
-#undef ZZZ_BK_ATTRC
-#undef ZZZ_BK_ATTR
+    for (const auto& by_load : blk_kernels<1>)
+      for (BlkKernel k : by_load)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, BK_TAB_MAX * 72);
     ZZZ_HIP(ctx, hipGetLastError());
     ctx->bk_lds_attr = true;
   }
@@ -883,8 +879,7 @@ int sellp_blk_grid(const zzz_ctx* ctx, int64_t items)
   return (int)std::max<int64_t>(8, std::min<int64_t>(g, 256));
 }
 
-bool launch_sellp_blk(zzz_ctx* ctx, bool dot, bool nt, int grid, const double* x, double* y, double* partials, const int* stop,
-                      const int32_t* list, int64_t nlist, const double* rvec, int nn_is_rr, const ChebEpi* epi)
+bool launch_sellp_blk(zzz_ctx* ctx, int grid, const ProductCall& c)
 {
   if (!sellp_blk_serves(ctx))
     return false;
@@ -894,76 +889,12 @@ bool launch_sellp_blk(zzz_ctx* ctx, bool dot, bool nt, int grid, const double* x
   a.nnodes = (int)(ctx->nrows / 3);
   a.nslices = (int)ctx->bk_slices;
   a.nx8 = (int)((ctx->n_owned + ctx->n_ghost) * 24);
-  a.partials = partials;
-  a.stop_flag = stop;
-  a.nlist = nlist;
-  a.pstride = SPMV_PSTRIDE;
-  a.nn_is_rr = nn_is_rr;
+  product_args_tail(a, c);
   const size_t lds = f1 ? (size_t)ctx->bk_entries * 72 : (size_t)ctx->bk_ndict * 8;
   const double* tabp = f1 ? ctx->bk_tab.p : ctx->bk_vset.dict.p;
-#define ZZZ_BK_GO3(DOT, SR, NT, FORM, CHEB, EPI)                                                                                   \
-  hipLaunchKernelGGL((spmv_blk3_kernel<DOT, SR, NT, FORM, CHEB>), dim3(grid), dim3(BK_THREADS), lds, ctx->stream,                  \
-                     reinterpret_cast<const int2*>(ctx->bk_desc.p), ctx->bk_meta.p, ctx->bk_flags.p, ctx->bk_code.p, ctx->bk_ccode.p,  \
-                     tabp, ctx->bk_rows16.p, x, y, rvec, list, a, EPI)
-#define ZZZ_BK_GO2(DOT, SR, NT, FORM) ZZZ_BK_GO3(DOT, SR, NT, FORM, false, ChebEpi())
-#define ZZZ_BK_GO(DOT, SR, NT)                                                                                                     \
-  do                                                                                                                               \
-  {                                                                                                                                \
-    if (f1)                                                                                                                        \
-      ZZZ_BK_GO2(DOT, SR, NT, 1);                                                                                                  \
-    else                                                                                                                           \
-      ZZZ_BK_GO2(DOT, SR, NT, 2);                                                                                                  \
-  } while (0)
-#define ZZZ_BK_GOC(DOT, NT)                                                                                                        \
-  do                                                                                                                               \
-  {                                                                                                                                \
-    if (f1)                                                                                                                        \
-      ZZZ_BK_GO3(DOT, false, NT, 1, true, *epi);                                                                                   \
-    else                                                                                                                           \
-      ZZZ_BK_GO3(DOT, false, NT, 2, true, *epi);                                                                                   \
-  } while (0)
-  if (epi)
-  {
-    if (dot)
-    {
-      if (nt)
-        ZZZ_BK_GOC(true, true);
-      else
-        ZZZ_BK_GOC(true, false);
-    }
-    else
-    {
-      if (nt)
-        ZZZ_BK_GOC(false, true);
-      else
-        ZZZ_BK_GOC(false, false);
-    }
-  }
-  else if (dot && rvec)
-  {
-    if (nt)
-      ZZZ_BK_GO(true, true, true);
-    else
-      ZZZ_BK_GO(true, true, false);
-  }
-  else if (dot)
-  {
-    if (nt)
-      ZZZ_BK_GO(true, false, true);
-    else
-      ZZZ_BK_GO(true, false, false);
-  }
-  else
-  {
-    if (nt)
-      ZZZ_BK_GO(false, false, true);
-    else
-      ZZZ_BK_GO(false, false, false);
-  }
-#undef ZZZ_BK_GOC
-#undef ZZZ_BK_GO3
-#undef ZZZ_BK_GO2
-#undef ZZZ_BK_GO
+  hipLaunchKernelGGL((f1 ? blk_kernels<1> : blk_kernels<2>)[c.mode][c.load], dim3(grid), dim3(BK_THREADS), lds, ctx->stream,
+                     reinterpret_cast<const int2*>(ctx->bk_desc.p), ctx->bk_meta.p, ctx->bk_flags.p, ctx->bk_code.p, ctx->bk_ccode.p,
+                     tabp, ctx->bk_rows16.p, c.x, c.y, c.rvec, c.list, a, c.epi ? *c.epi : ChebEpi());
   return true;
 }
 ZZZ_PRELOAD_TU(sellp_blk)

@@ -509,47 +509,25 @@ int sellp_pipe_wgs(const zzz_ctx* ctx, bool sr)
   return sr ? SP_ONE_WGS_SR : SP_ONE_WGS;
 }
 
-bool launch_sellp_pipe(zzz_ctx* ctx, bool dot, bool nt, int grid, const double* x, double* y, double* partials, const int* stop,
-                       const int32_t* group_list, int64_t nlist, const double* rvec, int nn_is_rr)
+// [mode][load]; a product with a Chebyshev term takes the generic kernel
+using OneKernel = decltype(&spmv_one_kernel<false, false, false>);
+static const OneKernel one_kernels[PM_PLAIN + 1][2] = {{spmv_one_kernel<true, true, true>, spmv_one_kernel<true, true, false>},
+                                                       {spmv_one_kernel<true, false, true>, spmv_one_kernel<true, false, false>},
+                                                       {spmv_one_kernel<false, false, true>, spmv_one_kernel<false, false, false>}};
+
+bool launch_sellp_pipe(zzz_ctx* ctx, int grid, const ProductCall& c)
 {
-  if (!sellp_pipe_wgs(ctx, dot && rvec))
+  if (c.epi || !sellp_pipe_wgs(ctx, c.mode == PM_DOT_SR))
     return false;
   PipeArgs a;
   a.dict_n = ctx->sp_dict_n;
   a.nrows = (int)ctx->nrows;
   a.nslices = (int)ctx->nslices;
-  a.partials = partials;
-  a.stop_flag = stop;
-  a.nlist = nlist;
-  a.pstride = SPMV_PSTRIDE;
-  a.nn_is_rr = nn_is_rr;
+  product_args_tail(a, c);
   const size_t lds = (size_t)((ctx->sp_dict_n + 1) & ~1) * sizeof(double);
-#define ZZZ_ONE_GO(DOT, SR, NT)                                                                                                    \
-  hipLaunchKernelGGL((spmv_one_kernel<DOT, SR, NT>), dim3(grid), dim3(SP_BLOCK), lds, ctx->stream,                                 \
-                     reinterpret_cast<const int2*>(ctx->sp_desc.p), ctx->sp_smode.p, ctx->sp_pairs.p, ctx->sp_vals.p,               \
-                     ctx->sp_codes16.p, ctx->sp_meta.p, ctx->sp_vcode.p, ctx->sp_dset.dict.p, x, y, rvec, group_list, a)
-  if (dot && rvec)
-  {
-    if (nt)
-      ZZZ_ONE_GO(true, true, true);
-    else
-      ZZZ_ONE_GO(true, true, false);
-  }
-  else if (dot)
-  {
-    if (nt)
-      ZZZ_ONE_GO(true, false, true);
-    else
-      ZZZ_ONE_GO(true, false, false);
-  }
-  else
-  {
-    if (nt)
-      ZZZ_ONE_GO(false, false, true);
-    else
-      ZZZ_ONE_GO(false, false, false);
-  }
-#undef ZZZ_ONE_GO
+  hipLaunchKernelGGL(one_kernels[c.mode][c.load], dim3(grid), dim3(SP_BLOCK), lds, ctx->stream,
+                     reinterpret_cast<const int2*>(ctx->sp_desc.p), ctx->sp_smode.p, ctx->sp_pairs.p, ctx->sp_vals.p, ctx->sp_codes16.p,
+                     ctx->sp_meta.p, ctx->sp_vcode.p, ctx->sp_dset.dict.p, c.x, c.y, c.rvec, c.list, a);
   return true;
 }
 ZZZ_PRELOAD_TU(sellp_pipe)

@@ -1053,6 +1053,15 @@ static int bw_structure(zzz_ctx* ctx)
   return ZZZ_OK;
 }
 
+// [mode][load]: every instantiation there is; all of them get the dynamic-LDS attribute (sellp_win_build)
+using WinKernel = decltype(&spmv_win_kernel<false, false, false>);
+static const WinKernel win_kernels[PM_COUNT][2] = {
+    {spmv_win_kernel<true, true, true>, spmv_win_kernel<true, true, false>},
+    {spmv_win_kernel<true, false, true>, spmv_win_kernel<true, false, false>},
+    {spmv_win_kernel<false, false, true>, spmv_win_kernel<false, false, false>},
+    {spmv_win_kernel<true, false, true, true>, spmv_win_kernel<true, false, false, true>},
+    {spmv_win_kernel<false, false, true, true>, spmv_win_kernel<false, false, false, true>}};
+
 // Called when the matrix is assembled (sell_update) or at the stream's first use after an assembly (sellp_active).  Declined (bw_on stays false, nothing else changes): block
 // size 3, short rows, sorted stream, a block beyond the LDS budget, ZZZ_SELLP_BWIN=0.
 int sellp_win_build(zzz_ctx* ctx)
@@ -1100,24 +1109,9 @@ int sellp_win_build(zzz_ctx* ctx)
     return ZZZ_OK; // a block with more distinct values than the table holds (an irregular mesh): the stream serves the product
   if (!ctx->bw_lds_attr)
   {
-#define ZZZ_BW_ATTR(DOT, SR, NT)                                                                                                   \
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&spmv_win_kernel<DOT, SR, NT>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                            (BW_WCAP + BW_DCAP) * 8)
-    ZZZ_BW_ATTR(true, true, true);
-    ZZZ_BW_ATTR(true, true, false);
-    ZZZ_BW_ATTR(true, false, true);
-    ZZZ_BW_ATTR(true, false, false);
-    ZZZ_BW_ATTR(false, false, true);
-    ZZZ_BW_ATTR(false, false, false);
-#define ZZZ_BW_ATTRC(DOT, NT)                                                                                                      \
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&spmv_win_kernel<DOT, false, NT, true>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                            (BW_WCAP + BW_DCAP) * 8)
-    ZZZ_BW_ATTRC(true, true);
-    ZZZ_BW_ATTRC(true, false);
-    ZZZ_BW_ATTRC(false, true);
-    ZZZ_BW_ATTRC(false, false);
-#undef ZZZ_BW_ATTRC
-#undef ZZZ_BW_ATTR
+    for (const auto& by_load : win_kernels)
+      for (WinKernel k : by_load)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (BW_WCAP + BW_DCAP) * 8);
     ZZZ_HIP(ctx, hipGetLastError());
     ctx->bw_lds_attr = true;
   }
@@ -1155,65 +1149,19 @@ int sellp_win_grid(const zzz_ctx* ctx, int64_t items)
   return (int)std::max<int64_t>(8, std::min<int64_t>(g, 256));
 }
 
-bool launch_sellp_win(zzz_ctx* ctx, bool dot, bool nt, int grid, const double* x, double* y, double* partials, const int* stop,
-                      const int32_t* list, int64_t nlist, const double* rvec, int nn_is_rr, const ChebEpi* epi)
+bool launch_sellp_win(zzz_ctx* ctx, int grid, const ProductCall& c)
 {
   if (!sellp_win_serves(ctx))
     return false;
   WinArgs a;
   a.nblk = ctx->bw_nblk;
   a.nrows = (int)ctx->nrows;
-  a.partials = partials;
-  a.stop_flag = stop;
-  a.nlist = nlist;
-  a.pstride = SPMV_PSTRIDE;
-  a.nn_is_rr = nn_is_rr;
+  product_args_tail(a, c);
   const size_t lds = (size_t)(BW_WCAP + BW_DCAP) * 8;
-#define ZZZ_BW_GO4(DOT, SR, NT, CHEB, EPI)                                                                                         \
-  hipLaunchKernelGGL((spmv_win_kernel<DOT, SR, NT, CHEB>), dim3(grid), dim3(BW_THREADS), lds, ctx->stream, ctx->bw_perm.p,         \
-                     reinterpret_cast<const int2*>(ctx->bw_desc.p), ctx->bw_woff.p, ctx->bw_blk_wn.p, ctx->bw_wlist.p, ctx->bw_ccode.p, ctx->bw_vcode.p, \
-                     ctx->bw_cpack.p, ctx->bw_vpack.p, ctx->bw_cflag.p, ctx->bw_vflag.p, ctx->bw_dict.p, ctx->bw_dnum.p, x, y, rvec, list, a, EPI)
-#define ZZZ_BW_GO(DOT, SR, NT) ZZZ_BW_GO4(DOT, SR, NT, false, ChebEpi())
-  if (epi)
-  {
-    if (dot)
-    {
-      if (nt)
-        ZZZ_BW_GO4(true, false, true, true, *epi);
-      else
-        ZZZ_BW_GO4(true, false, false, true, *epi);
-    }
-    else
-    {
-      if (nt)
-        ZZZ_BW_GO4(false, false, true, true, *epi);
-      else
-        ZZZ_BW_GO4(false, false, false, true, *epi);
-    }
-  }
-  else if (dot && rvec)
-  {
-    if (nt)
-      ZZZ_BW_GO(true, true, true);
-    else
-      ZZZ_BW_GO(true, true, false);
-  }
-  else if (dot)
-  {
-    if (nt)
-      ZZZ_BW_GO(true, false, true);
-    else
-      ZZZ_BW_GO(true, false, false);
-  }
-  else
-  {
-    if (nt)
-      ZZZ_BW_GO(false, false, true);
-    else
-      ZZZ_BW_GO(false, false, false);
-  }
-#undef ZZZ_BW_GO4
-#undef ZZZ_BW_GO
+  hipLaunchKernelGGL(win_kernels[c.mode][c.load], dim3(grid), dim3(BW_THREADS), lds, ctx->stream, ctx->bw_perm.p,
+                     reinterpret_cast<const int2*>(ctx->bw_desc.p), ctx->bw_woff.p, ctx->bw_blk_wn.p, ctx->bw_wlist.p, ctx->bw_ccode.p,
+                     ctx->bw_vcode.p, ctx->bw_cpack.p, ctx->bw_vpack.p, ctx->bw_cflag.p, ctx->bw_vflag.p, ctx->bw_dict.p, ctx->bw_dnum.p,
+                     c.x, c.y, c.rvec, c.list, a, c.epi ? *c.epi : ChebEpi());
   return true;
 }
 ZZZ_PRELOAD_TU(sellp_win)

@@ -244,12 +244,12 @@ __global__ __launch_bounds__(SPMV_BLOCK, 8) void spmv_tile_kernel(const rp_t* __
   }
 }
 
-static int spmv_grid(const zzz_ctx* ctx)
+static int tile_grid(int64_t ntiles)
 {
   // 8 workgroups of 256 threads per CU; always a multiple of 8 so that every XCD residue
   // (blockIdx % 8) that owns tiles in xcd_tile() has at least one workgroup
   int64_t g = 256 * 8;
-  const int64_t need = (ctx->ntiles + 7) / 8 * 8;
+  const int64_t need = (ntiles + 7) / 8 * 8;
   if (g > need)
     g = need;
   if (g < 8)
@@ -257,119 +257,131 @@ static int spmv_grid(const zzz_ctx* ctx)
   return (int)g;
 }
 
-template <bool DOT>
-static void launch_variant(zzz_ctx* ctx, int grid, const double* x, double* y, double* partials, const int* stop,
-                           int nnz_even, const int32_t* tile_list = nullptr, int64_t nlist = 0, const double* rvec = nullptr,
-                           int nn_is_rr = 0)
+// [mode][load].  The kernel takes rvec at run time, so the single-reduction form is the DOT instantiation, and it has no
+// Chebyshev epilogue: those products need the operator stream.
+using TileKernel = decltype(&spmv_tile_kernel<false, false>);
+static const TileKernel tile_kernels[PM_PLAIN + 1][2] = {{spmv_tile_kernel<true, true>, spmv_tile_kernel<true, false>},
+                                                         {spmv_tile_kernel<true, true>, spmv_tile_kernel<true, false>},
+                                                         {spmv_tile_kernel<false, true>, spmv_tile_kernel<false, false>}};
+
+// bit 0 of the variant: non-temporal matrix loads.  Unless a variant was forced, the load
+// policy follows the matrix size: a matrix that fits the 256 MiB Infinity Cache is re-read from it
+// every CG iteration, and non-temporal loads would throw that away (measured, 1.25 M-dof P1 matrix,
+// 221 MB: 44 us plain vs 55 us nt; 2.5 M dofs and up: nt 2-8 % faster).
+static ProductLoad tile_load(const zzz_ctx* ctx)
 {
-  const int4* tiles = reinterpret_cast<const int4*>(ctx->tile_row.p);
-  const int64_t nt = tile_list ? nlist : ctx->ntiles;
-  // bit 4 of the variant: ignore the packed columns (A/B and parity of the two index streams)
-  const uint16_t* c16 = (ctx->have_cols16 && !(ctx->spmv_variant & 16)) ? ctx->cols16.p : nullptr;
-  const int col_max = (int)ctx->nloc() - 1; // nloc() counts scalar entries (a clamp bs times too far read past the end of x)
-#define ZZZ_SPMV_GO(NT)                                                                                               \
-  hipLaunchKernelGGL((spmv_tile_kernel<DOT, NT>), dim3(grid), dim3(SPMV_BLOCK), 0, ctx->stream,                       \
-                     ctx->rowptr.p, ctx->cols.p, ctx->vals.p, x, y, tiles, nt, nnz_even, partials, stop, tile_list,    \
-                     rvec, SPMV_PSTRIDE, nn_is_rr, c16, ctx->tile_base.p, ctx->cols16_offb, col_max, ctx->spmv_lpr_shift)
-  // bit 0: non-temporal matrix loads.  Unless a variant was forced, the load
-  // policy follows the matrix size: a matrix that fits the 256 MiB Infinity Cache is re-read from it
-  // every CG iteration, and non-temporal loads would throw that away (measured, 1.25 M-dof P1 matrix,
-  // 221 MB: 44 us plain vs 55 us nt; 2.5 M dofs and up: nt 2-8 % faster).
   int var = ctx->spmv_variant;
   if (ctx->spmv_auto)
     var = (var & ~1) | (12.0 * (double)ctx->nnz > 300.0e6 ? 1 : 0);
-  if (var & 1)
-    ZZZ_SPMV_GO(true);
-  else
-    ZZZ_SPMV_GO(false);
-#undef ZZZ_SPMV_GO
+  return (var & 1) ? LOAD_NT : LOAD_PLAIN;
 }
 
-int launch_spmv(zzz_ctx* ctx, const double* x, double* y, double* partials, int* npartials, const double* rvec,
-                int nn_is_rr)
+static void launch_variant(zzz_ctx* ctx, int grid, const ProductCall& c)
 {
-  const int grid = spmv_grid(ctx);
-  const int nnz_even = ctx->tiles_ok ? (int)((ctx->nnz + 1) & ~(int64_t)1) : 0; // last valid clamped index (arrays are padded by 8)
-  const int* stop = partials ? reinterpret_cast<const int*>(ctx->state.p) : nullptr; // CgState::converged
-  if (sellp_active(ctx))
-    return launch_sellp(ctx, x, y, partials, npartials, rvec, nn_is_rr);
+  const int4* tiles = reinterpret_cast<const int4*>(ctx->tile_row.p);
+  const int64_t nt = c.list ? c.nlist : ctx->ntiles;
+  const int nnz_even = (int)((ctx->nnz + 1) & ~(int64_t)1); // last valid clamped index (arrays are padded by 8)
+  // bit 4 of the variant: ignore the packed columns (A/B and parity of the two index streams)
+  const uint16_t* c16 = (ctx->have_cols16 && !(ctx->spmv_variant & 16)) ? ctx->cols16.p : nullptr;
+  const int col_max = (int)ctx->nloc() - 1; // nloc() counts scalar entries (a clamp bs times too far read past the end of x)
+  hipLaunchKernelGGL(tile_kernels[c.mode][c.load], dim3(grid), dim3(SPMV_BLOCK), 0, ctx->stream, ctx->rowptr.p, ctx->cols.p,
+                     ctx->vals.p, c.x, c.y, tiles, nt, nnz_even, c.partials, c.stop, c.list, c.rvec, SPMV_PSTRIDE, c.nn_is_rr, c16,
+                     ctx->tile_base.p, ctx->cols16_offb, col_max, ctx->spmv_lpr_shift);
+}
+
+// what a product on the tile kernel needs, whichever driver launches it
+static int tile_prepare(zzz_ctx* ctx, ProductCall& c)
+{
+  if (c.epi)
+    return fail(ctx, ZZZ_ERR_ARG, "a product with a Chebyshev term needs the operator stream (zzz_sellp.hip)");
   if (!ctx->tiles_ok)
     return fail(ctx, ZZZ_ERR_LIMIT, "%lld nonzeros: the product of a matrix of 2^31 nonzeros or more needs the operator stream "
                 "(zzz_sellp.hip), which this matrix / these settings do not use", (long long)ctx->nnz);
-  if (int rc = ensure_cols16(ctx))
+  c.load = tile_load(ctx);
+  return ensure_cols16(ctx);
+}
+
+int launch_spmv(zzz_ctx* ctx, const double* x, double* y, double* partials, int* npartials, const double* rvec, int nn_is_rr,
+                const ChebEpi* epi)
+{
+  ProductCall c = product_call(ctx, x, y, partials, rvec, nn_is_rr, epi);
+  if (sellp_active(ctx))
+    return launch_sellp(ctx, c, npartials);
+  if (int rc = tile_prepare(ctx, c))
     return rc;
-  if (partials)
-  {
-    if ((size_t)grid > ctx->part_a.n)
-      return fail(ctx, ZZZ_ERR_ARG, "partials buffer too small");
-    launch_variant<true>(ctx, grid, x, y, partials, stop, nnz_even, nullptr, 0, rvec, nn_is_rr);
-    if (npartials)
-      *npartials = grid;
-  }
-  else
-    launch_variant<false>(ctx, grid, x, y, nullptr, stop, nnz_even);
+  const int grid = tile_grid(ctx->ntiles);
+  if (partials && (size_t)grid > ctx->part_a.n)
+    return fail(ctx, ZZZ_ERR_ARG, "partials buffer too small");
+  launch_variant(ctx, grid, c);
+  if (partials && npartials)
+    *npartials = grid;
   ZZZ_HIP(ctx, hipGetLastError());
   return ZZZ_OK;
 }
-static int grid_for_tiles(int64_t nt)
+
+// Partitioned matrix: y = A x with the forward halo of x overlapped with the interior items (tiles, groups of slices).
+//   comm stream : (waits for x) pack + send/recv of the ghost entries        -- issued FIRST so that
+//   main stream : product over the items that reference no ghost column         its kernels get CUs
+//   main stream : (waits for the halo) product over the boundary items
+// Partials of <x,y>: interior workgroups first, then the boundary ones.
+int launch_overlapped(zzz_ctx* ctx, double* x, ProductCall c, const ProductPart& in, const ProductPart& bd, ProductLauncher launch,
+                      int* npartials)
 {
-  int64_t g = 256 * 8;
-  const int64_t need = (nt + 7) / 8 * 8;
-  if (g > need)
-    g = need;
-  if (g < 8)
-    g = 8;
-  return (int)g;
+  int rc = comm_halo_begin(ctx, x);
+  if (rc)
+    return rc;
+  c.list = in.list;
+  c.nlist = in.n;
+  if (in.n)
+    launch(ctx, in.grid, c);
+  rc = comm_halo_end(ctx);
+  if (rc)
+    return rc;
+  c.list = bd.list;
+  c.nlist = bd.n;
+  if (c.partials)
+    c.partials += in.grid;
+  if (bd.n)
+    launch(ctx, bd.grid, c);
+  if (npartials)
+    *npartials = in.grid + bd.grid;
+  ZZZ_HIP(ctx, hipGetLastError());
+  return ZZZ_OK;
 }
 
-// Partitioned matrix: y = A x with the forward halo of x overlapped with the interior tiles.
-//   comm stream : (waits for x) pack + send/recv of the ghost entries        -- issued FIRST so that
-//   main stream : SpMV over the tiles that reference no ghost column            its kernels get CUs
-//   main stream : (waits for the halo) SpMV over the boundary tiles
-// Partials of <x,y>: interior workgroups first, then the boundary ones.
-int launch_spmv_overlapped(zzz_ctx* ctx, double* x, double* y, double* partials, int* npartials, const double* rvec,
-                           int nn_is_rr)
+static int launch_spmv_overlapped(zzz_ctx* ctx, double* x, double* y, double* partials, int* npartials, const double* rvec,
+                                  int nn_is_rr, const ChebEpi* epi)
 {
-  const int nnz_even = (int)((ctx->nnz + 1) & ~(int64_t)1);
-  const int* stop = partials ? reinterpret_cast<const int*>(ctx->state.p) : nullptr;
+  ProductCall c = product_call(ctx, x, y, partials, rvec, nn_is_rr, epi);
   if (sellp_active(ctx) && ctx->have_group_split)
-    return launch_sellp_overlapped(ctx, x, y, partials, npartials, rvec, nn_is_rr);
-  if (int rc = ensure_cols16(ctx))
+    return launch_sellp_overlapped(ctx, x, c, npartials);
+  if (int rc = tile_prepare(ctx, c))
     return rc;
   const int64_t n_in = ctx->n_tiles_interior, n_bd = ctx->n_tiles_boundary;
   // The interior launch leaves one workgroup slot per CU free (7 of 8): at full occupancy the persistent
   // SpMV workgroups hold every wave slot until the launch ends and RCCL's send/recv kernel, although
   // enqueued first on a high-priority stream, could not start beside them -- no overlap at all.
-  int g_in = n_in ? grid_for_tiles(n_in) : 0;
+  int g_in = n_in ? tile_grid(n_in) : 0;
   if (g_in > 256 * 7 && ctx->nneigh > 0)
     g_in = 256 * 7;
-  const int g_bd = n_bd ? grid_for_tiles(n_bd) : 0;
+  const int g_bd = n_bd ? tile_grid(n_bd) : 0;
   if (partials && (size_t)(g_in + g_bd) > ctx->part_a.n)
     return fail(ctx, ZZZ_ERR_ARG, "partials buffer too small");
-  int rc = comm_halo_begin(ctx, x);
-  if (rc)
-    return rc;
-  if (n_in)
+  return launch_overlapped(ctx, x, c, {n_in, ctx->tiles_interior.p, g_in}, {n_bd, ctx->tiles_boundary.p, g_bd}, launch_variant,
+                           npartials);
+}
+
+int launch_product(zzz_ctx* ctx, double* x, double* y, double* partials, int* npartials, const double* rvec, int nn_is_rr,
+                   const ChebEpi* epi)
+{
+  if (ctx->comm)
   {
-    if (partials)
-      launch_variant<true>(ctx, g_in, x, y, partials, stop, nnz_even, ctx->tiles_interior.p, n_in, rvec, nn_is_rr);
-    else
-      launch_variant<false>(ctx, g_in, x, y, nullptr, stop, nnz_even, ctx->tiles_interior.p, n_in);
+    if (ctx->overlap && ctx->have_tile_split)
+      return launch_spmv_overlapped(ctx, x, y, partials, npartials, rvec, nn_is_rr, epi);
+    if (int rc = comm_halo_forward(ctx, x))
+      return rc;
   }
-  rc = comm_halo_end(ctx);
-  if (rc)
-    return rc;
-  if (n_bd)
-  {
-    if (partials)
-      launch_variant<true>(ctx, g_bd, x, y, partials + g_in, stop, nnz_even, ctx->tiles_boundary.p, n_bd, rvec, nn_is_rr);
-    else
-      launch_variant<false>(ctx, g_bd, x, y, nullptr, stop, nnz_even, ctx->tiles_boundary.p, n_bd);
-  }
-  if (npartials)
-    *npartials = g_in + g_bd;
-  ZZZ_HIP(ctx, hipGetLastError());
-  return ZZZ_OK;
+  return launch_spmv(ctx, x, y, partials, npartials, rvec, nn_is_rr, epi);
 }
 ZZZ_PRELOAD_TU(spmv)
 } // namespace zzz

@@ -147,6 +147,76 @@ def test_x_windows_in_a_partitioned_run():
     assert abs(res["2048"][0][1] - it0) <= 1 and np.linalg.norm(u - u0) <= 1e-9 * np.linalg.norm(u0)
 
 
+@pytest.mark.parametrize("sellp", [None, "0"], ids=["operator-stream", "tile-kernel"])
+@pytest.mark.parametrize("problem,order,dims", [("poisson", 1, (10, 9, 12)), ("poisson", 3, (3, 3, 6)),
+                                                ("elasticity", 1, (5, 5, 8))])
+def test_overlapped_product_equals_blocking_product(problem, order, dims, sellp):
+    """The two ways to a partitioned product, side by side: halo begun, interior launch, halo awaited, boundary launch
+    (ZZZ_OVERLAP=1) against halo, then one launch over everything (ZZZ_OVERLAP=0) -- two ranks (contexts of one process,
+    host-mediated communicator), on the default operator stream and on the CSR tile kernel (ZZZ_SELLP=0).  A row's
+    products are added in the stream's order whichever launch carries the row: y has the same bits.  The partial sums
+    of the solves regroup (interior workgroups, then boundary ones), so those agree as the partitioned solves agree with
+    the single-rank one: iterations +-1, solution 1e-8."""
+    import threading
+
+    nparts = 2
+    knobs = ("ZZZ_OVERLAP", "ZZZ_SELLP")
+    saved = {k: os.environ.get(k) for k in knobs}
+    res = {}
+    try:
+        if sellp is not None:
+            os.environ["ZZZ_SELLP"] = sellp   # (both knobs are read when a context is created)
+        for overlap in ("1", "0"):
+            os.environ["ZZZ_OVERLAP"] = overlap
+            grp = zzz.LocalGroup(nparts)
+            out, err = [None] * nparts, []
+
+            def run(rank):
+                try:
+                    P = zzz.Part(problem, order, *dims, nparts, rank)
+                    with zzz.Context(0) as c:
+                        c.comm_init_local(grp.h, rank)
+                        c.cube_generate(problem, order, *dims, nparts, rank)
+                        c.pattern_build()
+                        c.assemble_matrix(P.form)
+                        c.assemble_vector(P.form)
+                        lo, hi = P.own_offset * P.bs, (P.own_offset + P.n_owned) * P.bs
+                        y = c.spmv(np.sin(0.23 * np.arange(lo, hi)))
+                        it, _, _ = c.cg_solve(pc=zzz.PC_JACOBI, rtol=1e-9)
+                        u = c.vec_download(zzz.VEC_U)
+                        itc, _, _ = c.cg_solve(pc=zzz.PC_CHEBYSHEV_JACOBI, rtol=1e-9)
+                        out[rank] = (y, it, u, itc, c.vec_download(zzz.VEC_U), c.comm_info()["halo_overlapped"])
+                except Exception as e:  # noqa: BLE001
+                    err.append((rank, repr(e)))
+
+            try:
+                th = [threading.Thread(target=run, args=(r,)) for r in range(nparts)]
+                for t in th:
+                    t.start()
+                for t in th:
+                    t.join(timeout=300)
+            finally:
+                grp.close()
+            assert not err, err
+            assert all(o is not None for o in out)
+            res[overlap] = out
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+    assert all(o[5] == 1 for o in res["1"]) and all(o[5] == 0 for o in res["0"])  # both paths ran
+    for a, b in zip(res["1"], res["0"]):
+        assert np.array_equal(a[0], b[0])
+    for its, sol in ((1, 2), (3, 4)):  # Jacobi, Chebyshev-Jacobi
+        ia, ib = {o[its] for o in res["1"]}, {o[its] for o in res["0"]}
+        assert len(ia) == 1 and len(ib) == 1 and abs(ia.pop() - ib.pop()) <= 1
+        ua, ub = (np.concatenate([o[sol] for o in res[k]]) for k in ("1", "0"))
+        print(problem, order, sellp, "|u_overlapped - u_blocking| / |u| =", np.linalg.norm(ua - ub) / np.linalg.norm(ub))
+        assert np.linalg.norm(ua - ub) <= 1e-8 * np.linalg.norm(ub)
+
+
 @pytest.mark.parametrize("p2p", [False, True], ids=["allreduce-comm", "allreduce-peer-memory"])
 @pytest.mark.parametrize("problem,order,dims,nparts", [("poisson", 1, (10, 9, 12), 2), ("poisson", 1, (8, 8, 13), 4),
                                                        ("poisson", 3, (3, 3, 6), 3), ("elasticity", 1, (5, 5, 8), 2),
