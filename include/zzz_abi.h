@@ -319,7 +319,12 @@ int zzz_spmv_time(zzz_ctx* ctx, int reps, int variant, double* avg_ms);
 /* y = action(x): the matrix-free operator lambda of cgpoisson (src/cgpoisson_problem.cpp:193-230):
  * assemble_vector of form M = action(a, un) with un = x, rows of constrained dofs zeroed, ghosts
  * of x updated first.  Needs mesh, dofmap and Dirichlet dofs only: no pattern, no matrix (the reference's cgpoisson
- * creates neither, src/cgpoisson_problem.cpp:47-247).  Builds the operator's plan on first use (zzz_matfree_setup). */
+ * creates neither, src/cgpoisson_problem.cpp:47-247).  Builds the operator's plan on first use (zzz_matfree_setup).
+ * Non-finite input (zzz_action and zzz_action_f32 alike): an Inf or NaN in x[d] stays with the cells that hold d.  y[d] is
+ * non-finite (d unconstrained); rows of constrained dofs are 0 whatever their cells carry; the entries of the other dofs
+ * that share a cell with d are non-finite wherever the element arithmetic couples them to d -- all of them for P1, for
+ * P2/P3 all but those the factorised tables' exact zeros keep apart -- and every dof that shares no cell with d keeps the
+ * bits of the clean action.  Nothing lingers: the next action of a finite x gives the clean bits. */
 int zzz_action(zzz_ctx* ctx, const double* x, double* y);
 
 /* What cgpoisson sets up once before its solve: fem::create_form of M (src/cgpoisson_problem.cpp:133-145), the
@@ -347,8 +352,15 @@ int zzz_action_time(zzz_ctx* ctx, int reps, double* avg_ms);
  * instantiation on one rank, beside the double path, which they leave untouched: the operator's plan is shared, only its
  * value arrays (geometry factors, reference tables, P1 coordinates, partial sums) get float twins, built by the first
  * float action and dropped with the plan.  G = |detJ| K K^T is computed in double and rounded; P1 coordinates are stored
- * relative to an origin of their cell block (subtracted in double), so that the Jacobian's differences carry the block's
- * extent and not the domain's.  Declined with ZZZ_ERR_ARG and a reason: block size 3, an attached communicator. */
+ * relative to an origin of their cell block (subtracted in double): a rounded coordinate is then off by 2^-25 of its distance
+ * from that origin, not from the domain's.  The origin is checked against every cell of the block: the float Jacobian is
+ * compared with the double one entry by entry, against the cell's extent along that axis, and the float determinant must be
+ * safely non-zero.  The block's first listed dof stays the origin within 2^-16; past it the better of it and a second origin
+ * -- where the block's cells are finest -- is taken; and where neither keeps the Jacobian within 2^-12 the float action is
+ * REFUSED: ZZZ_ERR_LIMIT with a message that names the blocks and the worst distance / extent (a mesh graded towards both
+ * ends of a block by 10^5 and more).  A refusal builds no float twin and leaves the plan, the vectors and the double path as
+ * they were; zzz_cg_solve_f32 refuses before it touches u.  A float action never returns ZZZ_OK with entries that a cell's
+ * collapsed determinant made non-finite.  Declined with ZZZ_ERR_ARG and a reason: block size 3, an attached communicator. */
 
 /* y = action(x) in float (src/cgpoisson_problem.cpp:193-230 with T = float): host arrays of n_owned floats, as zzz_action
  * takes doubles.  Bit-reproducible from call to call. */

@@ -146,6 +146,9 @@ int cg_solve_f32(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rno
   const int g = vgrid(n);
   hipStream_t s = ctx->stream;
 
+  // a mesh the float action refuses is refused before the solve touches anything
+  if (int rc = mf_f32_prepare(ctx))
+    return rc;
   // grow-only: nothing is freed on the solve path
   ZZZ_HIP(ctx, ctx->f32_x.reserve(nl));
   ZZZ_HIP(ctx, ctx->f32_r.reserve(nl));

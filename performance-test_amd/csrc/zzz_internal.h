@@ -156,7 +156,8 @@ struct MfPlan
   bool f32_built = false;
   int64_t nu = 0;                   // entries of the block-local dof lists
   int64_t bytes_per_action_f32 = 0; // what one float action addresses
-  DevBuf<float> xyz32;              // P1: coordinates relative to the block's first listed dof (subtracted in double)
+  DevBuf<float> xyz32;              // P1: coordinates relative to the block's origin (subtracted in double): the block's first
+                                    // listed dof where that serves every cell of the block, else the second origin of zzz_mf_elem.h
   DevBuf<float> geom32, dtab32;     // P2/P3: geom and dtab rounded
   DevBuf<float> ypart32;            // partial sums of the shared dofs
 };
@@ -614,6 +615,7 @@ int mf_action(zzz_ctx* ctx, const double* x, double* y, double* partials, int* n
 int mf_diagonal(zzz_ctx* ctx, double* y);
 // the same action on the plan's float twins (built on first use; the plan itself as well); x, y: nloc floats on the device
 int mf_action_f32(zzz_ctx* ctx, const float* x, float* y, double* partials, int* npartials);
+int mf_f32_prepare(zzz_ctx* ctx); // plan + float twins, or ZZZ_ERR_LIMIT with the reason the float action is refused
 int mf_f32_info(zzz_ctx* ctx, int64_t info[4]); // zzz_matfree_info_f32
 // zzz_cg_f32.hip
 int cg_solve_f32(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm);

@@ -1193,16 +1193,134 @@ __global__ __launch_bounds__(256) void k_mf32_round(const double* __restrict__ i
   for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += gridDim.x * 256ll)
     out[i] = mf_round<float>(in[i]);
 }
-// P1 coordinates of every block's dof list, relative to the block's first listed dof
+// P1: the origin of every block's float coordinates.  status 0: the block's first listed dof (kept within MF_F32_JKEEP, or the better of
+// the two); 1: the second origin (MfF32Thin); 2: neither serves (mf_f32_choose, zzz_mf_elem.h) -- `ratio` is then the largest
+// (distance from the origin) / (cell extent) of the block under the origin that does better by it.  One workgroup per block; the
+// cells' vertices come from the block's own lists (16-bit local indices, double coordinates), as the action reads them.
+__device__ inline bool mf32_cell_points(const int32_t* __restrict__ mf_cell, const uint32_t* __restrict__ idxw,
+                                        const double* __restrict__ xyz, int64_t b, int nc, int e, int64_t off, double (&p)[4][3])
+{
+  if (mf_cell[b * nc + e] < 0)
+    return false;
+  const uint32_t w0 = idxw[(b * 2 + 0) * nc + e], w1 = idxw[(b * 2 + 1) * nc + e];
+  const int i[4] = {(int)(w0 & 0xffff), (int)(w0 >> 16), (int)(w1 & 0xffff), (int)(w1 >> 16)};
+  for (int k = 0; k < 4; ++k)
+    for (int a = 0; a < 3; ++a)
+      p[k][a] = xyz[3 * (off + i[k]) + a];
+  return true;
+}
+// doubles as unsigned keys of the same order (for LDS atomicMin / atomicMax)
+__device__ inline unsigned long long f64_key(double v)
+{
+  const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+__device__ inline double f64_unkey(unsigned long long k)
+{
+  return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
+}
+
+// the verdict of one origin on the block's cells, into LDS: cells whose determinant fails, largest jerr, largest ratio
+__device__ inline void mf32_origin_verdict(const int32_t* __restrict__ mf_cell, const uint32_t* __restrict__ idxw,
+                                           const double* __restrict__ xyz, int64_t b, int nc, int64_t off, double ox, double oy,
+                                           double oz, int* nbad, unsigned long long* jmax, unsigned long long* rmax)
+{
+  __syncthreads();
+  if (threadIdx.x == 0)
+  {
+    *nbad = 0;
+    *jmax = *rmax = f64_key(0.0);
+  }
+  __syncthreads();
+  const double o[3] = {ox, oy, oz};
+  for (int e = threadIdx.x; e < nc; e += 256)
+  {
+    double p[4][3];
+    if (!mf32_cell_points(mf_cell, idxw, xyz, b, nc, e, off, p))
+      continue;
+    const MfF32Verdict v = mf_f32_cell(p, o);
+    if (!v.ok)
+      atomicAdd(nbad, 1);
+    atomicMax(jmax, f64_key(v.jerr));
+    atomicMax(rmax, f64_key(v.ratio));
+  }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(256) void k_mf32_origin(const int32_t* __restrict__ hdr, int64_t nblocks, int nc,
+                                                     const int32_t* __restrict__ mf_cell, const uint32_t* __restrict__ idxw,
+                                                     const double* __restrict__ xyz, double jtol, double* __restrict__ origin,
+                                                     int32_t* __restrict__ status, double* __restrict__ ratio)
+{
+  __shared__ int nbad;
+  __shared__ unsigned long long jmax, rmax, thin_ext[3], thin_at[3];
+  for (int64_t b = blockIdx.x; b < nblocks; b += gridDim.x)
+  {
+    const int64_t off = hdr[MF_HDR * b + 0];
+    const double x0 = xyz[3 * off + 0], y0 = xyz[3 * off + 1], z0 = xyz[3 * off + 2];
+    mf32_origin_verdict(mf_cell, idxw, xyz, b, nc, off, x0, y0, z0, &nbad, &jmax, &rmax);
+    const bool ok0 = nbad == 0;
+    const double j0 = f64_unkey(jmax), far0 = f64_unkey(rmax);
+    int st = 0;
+    double x1 = x0, y1 = y0, z1 = z0, far1 = far0;
+    if (!mf_f32_keep_first(ok0, j0, jtol)) // (uniform: every thread reads the same verdict)
+    {
+      // the second origin: two passes of minima over the block's cells
+      if (threadIdx.x < 3)
+        thin_ext[threadIdx.x] = thin_at[threadIdx.x] = f64_key(DBL_MAX);
+      __syncthreads();
+      MfF32Thin t;
+      for (int e = threadIdx.x; e < nc; e += 256)
+      {
+        double p[4][3];
+        if (mf32_cell_points(mf_cell, idxw, xyz, b, nc, e, off, p))
+          mf_f32_thin_ext(t, p);
+      }
+      atomicMin(&thin_ext[0], f64_key(t.ext[0]));
+      atomicMin(&thin_ext[1], f64_key(t.ext[1]));
+      atomicMin(&thin_ext[2], f64_key(t.ext[2]));
+      __syncthreads();
+      t.ext[0] = f64_unkey(thin_ext[0]);
+      t.ext[1] = f64_unkey(thin_ext[1]);
+      t.ext[2] = f64_unkey(thin_ext[2]);
+      for (int e = threadIdx.x; e < nc; e += 256)
+      {
+        double p[4][3];
+        if (mf32_cell_points(mf_cell, idxw, xyz, b, nc, e, off, p))
+          mf_f32_thin_at(t, p);
+      }
+      atomicMin(&thin_at[0], f64_key(t.at[0]));
+      atomicMin(&thin_at[1], f64_key(t.at[1]));
+      atomicMin(&thin_at[2], f64_key(t.at[2]));
+      __syncthreads();
+      x1 = f64_unkey(thin_at[0]);
+      y1 = f64_unkey(thin_at[1]);
+      z1 = f64_unkey(thin_at[2]);
+      mf32_origin_verdict(mf_cell, idxw, xyz, b, nc, off, x1, y1, z1, &nbad, &jmax, &rmax);
+      far1 = f64_unkey(rmax);
+      st = mf_f32_choose(ok0, j0, nbad == 0, f64_unkey(jmax), jtol);
+    }
+    if (threadIdx.x == 0)
+    {
+      origin[3 * b + 0] = st == 1 ? x1 : x0;
+      origin[3 * b + 1] = st == 1 ? y1 : y0;
+      origin[3 * b + 2] = st == 1 ? z1 : z0;
+      status[b] = st;
+      ratio[b] = st == 2 ? fmin(far0, far1) : 0.0;
+    }
+  }
+}
+
+// P1 coordinates of every block's dof list, relative to the block's origin
 __global__ __launch_bounds__(256) void k_mf32_xyz(const int32_t* __restrict__ hdr, int64_t nblocks, const double* __restrict__ xyz,
-                                                  float* __restrict__ out)
+                                                  const double* __restrict__ origin, float* __restrict__ out)
 {
   for (int64_t b = blockIdx.x; b < nblocks; b += gridDim.x)
   {
     const int64_t off = hdr[MF_HDR * b + 0];
     const int nloc = hdr[MF_HDR * b + 1];
     for (int k = threadIdx.x; k < 3 * nloc; k += 256)
-      out[3 * off + k] = mf_rel_coord<float>(xyz[3 * off + k], xyz[3 * off + k % 3]);
+      out[3 * off + k] = mf_rel_coord<float>(xyz[3 * off + k], origin[3 * b + k % 3]);
   }
 }
 } // namespace
@@ -1213,9 +1331,47 @@ static int mf_f32_build(zzz_ctx* ctx)
   hipStream_t s = ctx->stream;
   if (M.nd == 4)
   {
+    // every block's origin: checked cell by cell, a second one tried, the plan refused where neither serves (zzz_mf_elem.h)
+    const unsigned g = (unsigned)std::min<int64_t>(M.nblocks, 8192);
+    DevBuf<double> origin, ratio;
+    DevBuf<int32_t> status;
+    ZZZ_HIP(ctx, origin.alloc((size_t)M.nblocks * 3));
+    ZZZ_HIP(ctx, ratio.alloc((size_t)M.nblocks));
+    ZZZ_HIP(ctx, status.alloc((size_t)M.nblocks));
+    // ZZZ_MF_F32_JTOL: a TIGHTER bar on the float Jacobian, in units of 2^-24 (0 .. 4096; the driver's test uses it to meet
+    // a refusal on a cube); a looser one is not offered
+    double jtol = MF_F32_JTOL;
+    if (const char* e = getenv("ZZZ_MF_F32_JTOL"))
+    {
+      const double v = atof(e);
+      if (v >= 0.0 && v <= 4096.0)
+        jtol = v * 0x1p-24;
+    }
+    hipLaunchKernelGGL(k_mf32_origin, dim3(g), dim3(256), 0, s, M.hdr.p, M.nblocks, M.nc, M.mf_cell.p, M.idxw.p, M.xyz.p, jtol,
+                       origin.p, status.p, ratio.p);
+    std::vector<int32_t> h_status((size_t)M.nblocks);
+    std::vector<double> h_ratio((size_t)M.nblocks);
+    ZZZ_HIP(ctx, hipMemcpyAsync(h_status.data(), status.p, h_status.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    ZZZ_HIP(ctx, hipMemcpyAsync(h_ratio.data(), ratio.p, h_ratio.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    ZZZ_HIP(ctx, hipStreamSynchronize(s));
+    int64_t refused = 0;
+    double worst = 0.0;
+    for (int64_t b = 0; b < M.nblocks; ++b)
+    {
+      if (h_status[(size_t)b] == 2)
+      {
+        ++refused;
+        worst = std::max(worst, h_ratio[(size_t)b]);
+      }
+    }
+    if (refused)
+      return fail(ctx, ZZZ_ERR_LIMIT,
+                  "float32 action refused: %lld of %lld cell blocks hold P1 cells that float coordinates relative to one origin per block "
+                  "cannot resolve (a cell lies %.3g times its own extent from the best origin tried; its Jacobian would miss %.3g x 2^-24): "
+                  "this mesh is graded too steeply for blocks of %d cells, solve it in double",
+                  (long long)refused, (long long)M.nblocks, worst, jtol * 0x1p24, M.nc);
     ZZZ_HIP(ctx, M.xyz32.alloc((size_t)M.nu * 3));
-    hipLaunchKernelGGL(k_mf32_xyz, dim3((unsigned)std::min<int64_t>(M.nblocks, 8192)), dim3(256), 0, s, M.hdr.p, M.nblocks, M.xyz.p,
-                       M.xyz32.p);
+    hipLaunchKernelGGL(k_mf32_xyz, dim3(g), dim3(256), 0, s, M.hdr.p, M.nblocks, M.xyz.p, origin.p, M.xyz32.p);
   }
   else
   {
@@ -1232,7 +1388,8 @@ static int mf_f32_build(zzz_ctx* ctx)
   return ZZZ_OK;
 }
 
-int mf_action_f32(zzz_ctx* ctx, const float* u, float* y, double* partials, int* npartials)
+// the plan and its float twins, or the reason there are none (a refusal leaves the plan and the double path as they were)
+int mf_f32_prepare(zzz_ctx* ctx)
 {
   MfPlan& M = ctx->mf;
   if (!M.valid)
@@ -1245,6 +1402,13 @@ int mf_action_f32(zzz_ctx* ctx, const float* u, float* y, double* partials, int*
   if (!M.f32_built)
     if (int rc = mf_f32_build(ctx))
       return rc;
+  return ZZZ_OK;
+}
+
+int mf_action_f32(zzz_ctx* ctx, const float* u, float* y, double* partials, int* npartials)
+{
+  if (int rc = mf_f32_prepare(ctx))
+    return rc;
   return mf_run<float>(ctx, false, u, y, partials, npartials);
 }
 

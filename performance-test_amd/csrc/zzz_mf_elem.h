@@ -4,8 +4,15 @@
 //   * geometry factors, reference tables: computed in double, then rounded once (mf_round);
 //   * P1 coordinates: NOT absolute.  The Jacobian is a difference of coordinates; formed from rounded absolute values its
 //     relative error is eps32 / h and grows with the mesh.  The float copy holds every coordinate relative to an origin of
-//     its cell block, subtracted in double (mf_rel_coord): the float differences carry the block's extent, not the domain's.
+//     its cell block, subtracted in double (mf_rel_coord).  A rounded relative coordinate is off by 2^-25 of its DISTANCE
+//     FROM THE ORIGIN, so an entry of a cell's Jacobian is off by up to 2^-24 x (distance from the origin) / (the cell's
+//     extent along that axis): harmless where a block spans a few dozen of its cells, ruinous on a graded mesh whose block
+//     holds cells 10^5 times smaller than itself far from its origin (the far cells collapse to det J == 0 in float).  So
+//     the origin is CHECKED, cell by cell (mf_f32_cell), a second origin is tried (MfF32Thin) and a block neither origin
+//     serves makes the float action refuse the plan (mf_f32_build in zzz_matfree.hip; tools/mf_f32_host.cpp runs the same
+//     decision on the CPU).
 #pragma once
+#include <cfloat>
 #include <cmath>
 #include <cstdint>
 
@@ -190,5 +197,118 @@ ZZZ_HD inline void mf_element_p1(const MfPoint<R>& p0, const MfPoint<R>& p1, con
     ye[3] = C20 * t0 + C21 * t1 + C22 * t2;
     ye[0] = -(ye[1] + ye[2] + ye[3]);
   }
+}
+
+// ---- P1 in float: how well an origin serves a cell, which origin a block takes, or none ----------------------------------
+// Column by column (column al = edge p_(al+1) - p_0), every entry of the Jacobian formed in float from the rounded relative
+// coordinates is compared with the double Jacobian's, against the cell's extent along that entry's axis (per axis: an
+// anisotropic or sheared cell is judged by what each coordinate has to resolve, as tests/_hp_ref.py judges the result against
+// what its terms weigh): jerr, at most 2^-24 x (distance from the origin) / extent.  What real plans cost, any origin: a
+// uniform mesh up to 32 units of 2^-24 (a Morton run of 2048 cells spans up to ~32 cell widths), the unstructured spoke mesh
+// with its cells of aspect 31 65 .. 340 units; a mesh graded to a corner with the origin at the wrong end 10^4 .. 10^6.
+//   * MF_F32_JKEEP (256 units): the block's first listed dof stays the origin while every cell is within it -- the plans
+//     served before keep their bits;
+//   * beyond it the better of the first and the second origin (MfF32Thin) is taken;
+//   * MF_F32_JTOL (4096 units: the geometry keeps 12 of float's 24 bits) is where the float action refuses the block -- a
+//     factor 10 beyond any mesh seen served, a factor 10 short of the meshes that came back wrong.
+// The float determinant must also be safely away from zero (2^-18 of the sum of its terms' magnitudes: the float evaluation
+// of that sum is off by at most ~2^-22 of it), have the double determinant's sign, and leave 1 / (6 |det|) and the cofactors
+// inside float's range: `ok`.
+constexpr double MF_F32_JKEEP = 0x1p-16, MF_F32_JTOL = 0x1p-12;
+constexpr double MF_F32_DET_MARGIN = 0x1p-18, MF_F32_DET_MIN = 0x1p-100, MF_F32_DET_MAX = 0x1p100;
+
+struct MfF32Verdict
+{
+  bool ok;      // the determinant's conditions
+  double jerr;  // largest |J_float - J_double| / (extent of the cell along that axis)
+  double ratio; // largest (distance of the cell from the origin) / (extent of the cell) over the three axes
+};
+// what a block does with the verdicts of its two origins (ok: every cell's; jerr: the largest): 0 first, 1 second, 2 refuse
+ZZZ_HD inline bool mf_f32_keep_first(bool ok0, double j0, double jtol) { return ok0 && j0 <= (MF_F32_JKEEP < jtol ? MF_F32_JKEEP : jtol); }
+ZZZ_HD inline int mf_f32_choose(bool ok0, double j0, bool ok1, double j1, double jtol)
+{
+  const bool c0 = ok0 && j0 <= jtol, c1 = ok1 && j1 <= jtol;
+  return c1 && (!c0 || j1 < j0) ? 1 : (c0 ? 0 : 2);
+}
+
+// lowest coordinate and extent of a cell along every axis
+ZZZ_HD inline void mf_f32_extent(const double (&p)[4][3], double (&lo)[3], double (&ext)[3])
+{
+  for (int a = 0; a < 3; ++a)
+  {
+    double l = p[0][a], h = p[0][a];
+    for (int k = 1; k < 4; ++k)
+    {
+      l = p[k][a] < l ? p[k][a] : l;
+      h = p[k][a] > h ? p[k][a] : h;
+    }
+    lo[a] = l;
+    ext[a] = h - l;
+  }
+}
+
+ZZZ_HD inline MfF32Verdict mf_f32_cell(const double (&p)[4][3], const double (&o)[3])
+{
+  double lo[3], ext[3], Jf[3][3], Jd[3][3];
+  mf_f32_extent(p, lo, ext);
+  MfF32Verdict v = {true, 0.0, 0.0};
+  for (int a = 0; a < 3; ++a)
+  {
+    const float r0 = mf_rel_coord<float>(p[0][a], o[a]);
+    double far = std::fabs(p[0][a] - o[a]);
+    for (int al = 0; al < 3; ++al)
+    {
+      const float r = mf_rel_coord<float>(p[al + 1][a], o[a]);
+      Jf[a][al] = (double)(r - r0); // (the float subtraction of mf_element_p1)
+      Jd[a][al] = p[al + 1][a] - p[0][a];
+      far = std::fmax(far, std::fabs(p[al + 1][a] - o[a]));
+      if (ext[a] > 0.0)
+        v.jerr = std::fmax(v.jerr, std::fabs(Jf[a][al] - Jd[a][al]) / ext[a]);
+    }
+    if (!(ext[a] > 0.0))
+    {
+      v.ok = false;
+      v.jerr = HUGE_VAL;
+    }
+    v.ratio = std::fmax(v.ratio, ext[a] > 0.0 ? far / ext[a] : HUGE_VAL);
+  }
+  // the determinant of the FLOAT Jacobian, its terms as mf_element_p1 groups them
+  double det = 0.0, mag = 0.0, detd = 0.0;
+  for (int al = 0; al < 3; ++al)
+  {
+    const int b = (al + 1) % 3, c = (al + 2) % 3;
+    det += Jf[0][al] * (Jf[1][b] * Jf[2][c] - Jf[1][c] * Jf[2][b]);
+    mag += std::fabs(Jf[0][al]) * (std::fabs(Jf[1][b] * Jf[2][c]) + std::fabs(Jf[1][c] * Jf[2][b]));
+    detd += Jd[0][al] * (Jd[1][b] * Jd[2][c] - Jd[1][c] * Jd[2][b]);
+  }
+  if (!(std::fabs(det) >= MF_F32_DET_MARGIN * mag) || !(std::fabs(det) >= MF_F32_DET_MIN) || !(std::fabs(det) <= MF_F32_DET_MAX)
+      || (det > 0.0) != (detd > 0.0))
+    v.ok = false;
+  return v;
+}
+
+// The second origin, tried where the block's first listed dof is past MF_F32_JKEEP: axis by axis, stand where the block is
+// finest -- the lowest coordinate among the cells whose extent along that axis is within a factor 2 of the block's least.
+// Two passes over the block's cells (least extent, then lowest coordinate), both plain minima: the result does not depend
+// on the order of the cells.  (The block's min corner serves a mesh graded towards low coordinates only; a mesh graded
+// towards the far corner needs the origin there.)
+struct MfF32Thin
+{
+  double ext[3] = {DBL_MAX, DBL_MAX, DBL_MAX}, at[3] = {DBL_MAX, DBL_MAX, DBL_MAX};
+};
+ZZZ_HD inline void mf_f32_thin_ext(MfF32Thin& t, const double (&p)[4][3])
+{
+  double lo[3], ext[3];
+  mf_f32_extent(p, lo, ext);
+  for (int a = 0; a < 3; ++a)
+    t.ext[a] = ext[a] < t.ext[a] ? ext[a] : t.ext[a];
+}
+ZZZ_HD inline void mf_f32_thin_at(MfF32Thin& t, const double (&p)[4][3])
+{
+  double lo[3], ext[3];
+  mf_f32_extent(p, lo, ext);
+  for (int a = 0; a < 3; ++a)
+    if (ext[a] <= 2.0 * t.ext[a] && lo[a] < t.at[a])
+      t.at[a] = lo[a];
 }
 } // namespace zzz

@@ -5,7 +5,9 @@ Action.  y_e = float32(A_e) . float32(u_e) in float32, A_e from the oracle's `ta
 scattered in double and the constrained rows zeroed.  For P1 there is a second form, `action32_p1_geometry`, that builds
 the element geometry in float32 as a float kernel must: the vertex coordinates are first taken relative to an origin of
 their chunk of cells (subtracted in double) and rounded; Jacobian, cofactors, determinant and the element vector are then
-float32 arithmetic.  `absolute=True` rounds the absolute coordinates instead -- what the library must NOT do.
+float32 arithmetic.  `absolute=True` rounds the absolute coordinates instead -- what the library must NOT do.  The chunks and
+their origins can be given (`block`, `origin`), and the library's rule for the origin -- check every cell's float Jacobian
+against the double one, take the better of it and a second origin past a bar, refuse the block past another -- is restated next to it (p1_block_origins).
 
 CG.  src/cg.h:38-86 on vectors of `dtype`; the sums behind <p,y> and <r,r> are accumulated in double and rounded to `dtype`
 once (the library's stated difference from the reference, which accumulates in U); alpha and beta are `dtype`.
@@ -59,12 +61,18 @@ def action(Ae, cell_dofs, bc, u, dtype):
     return scatter(cell_dofs, ye, bc, u.shape[0])
 
 
-def action32_p1_geometry(x, cells, cell_dofs, bc, u, chunk=2048, absolute=False):
-    """P1 with the geometry formed in float32 from chunk-relative coordinates"""
+def action32_p1_geometry(x, cells, cell_dofs, bc, u, chunk=2048, absolute=False, block=None, origin=None):
+    """P1 with the geometry formed in float32 from block-relative coordinates.  block[c] = the block of cell c and
+    origin[b] = the origin of block b; without them: chunks of `chunk` consecutive cells, each relative to the first vertex
+    of its first cell.  A cell whose float determinant is 0 gives non-finite entries, as it does in a kernel."""
     f = np.float32
     nc = len(cells)
-    origin = x[cells[(np.arange(nc) // chunk) * chunk, 0]]  # first vertex of the chunk's first cell
-    p = (x[cells].astype(f) if absolute else (x[cells] - origin[:, None, :]).astype(f))  # [nc, 4, 3]
+    if block is None:
+        first = (np.arange(nc) // chunk) * chunk
+        o = x[cells[first, 0]]  # first vertex of the chunk's first cell
+    else:
+        o = np.asarray(origin, np.float64)[np.asarray(block)]
+    p = (x[cells].astype(f) if absolute else (x[cells] - o[:, None, :]).astype(f))  # [nc, 4, 3]
     J = (p[:, 1:, :] - p[:, :1, :]).transpose(0, 2, 1)  # J[a][al] = p_(al+1)[a] - p_0[a]
     C = np.empty_like(J)
     for i in range(3):
@@ -76,9 +84,108 @@ def action32_p1_geometry(x, cells, cell_dofs, bc, u, chunk=2048, absolute=False)
     # grad phi_(al+1) = C[al][:] / det, grad phi_0 = -(their sum); A_ij = grad phi_i . grad phi_j |det| / 6
     Gr = np.concatenate([-(C.sum(axis=1, keepdims=True)), C], axis=1)  # [nc, 4, 3], times det
     ue = u.astype(f)[cell_dofs]
-    t = np.einsum("cja,cj->ca", Gr, ue).astype(f) / (f(6.0) * np.abs(det))[:, None]
-    ye = np.einsum("cia,ca->ci", Gr, t).astype(f)
+    with np.errstate(all="ignore"):
+        t = np.einsum("cja,cj->ca", Gr, ue).astype(f) / (f(6.0) * np.abs(det))[:, None]
+        ye = np.einsum("cia,ca->ci", Gr, t).astype(f)
     return scatter(cell_dofs, ye, bc, u.shape[0])
+
+
+U32 = 2.0 ** -24
+
+
+def figure32(y, y_ref, t_ref):
+    """the per-entry figure of tests/_hp_ref.py (metric: max |y - y_ref| / scale, exact where the scale is 0) in units of
+    2^-24; inf when an entry is not finite"""
+    y, y_ref, t_ref = np.asarray(y, np.float64), np.asarray(y_ref), np.asarray(t_ref)
+    if not np.isfinite(y).all():
+        return float("inf")
+    z = t_ref == 0
+    assert np.array_equal(y[z], y_ref[z]), "an entry of scale 0 is not exact"
+    return float((np.abs(y[~z] - y_ref[~z]) / t_ref[~z]).max() / U32) if not z.all() else 0.0
+
+
+# ---- the rule that picks a block's origin, or refuses the block (csrc/zzz_mf_elem.h: mf_f32_cell_ok, MfF32Thin), restated --
+JKEEP, JTOL, DET_MARGIN, DET_MIN, DET_MAX = 2.0 ** -16, 2.0 ** -12, 2.0 ** -18, 2.0 ** -100, 2.0 ** 100
+
+
+def p1_cells(xc, o):
+    """xc [n, 4, 3] vertex coordinates, o [3] origin -> (ok [n], jerr [n], ratio [n]).  jerr: the largest |J_float - J_double|
+    over the entries of the Jacobian (float: differences of the rounded relative coordinates), each against the cell's extent
+    along that axis.  ok: the float determinant DET_MARGIN of its terms' magnitudes away from zero, of the double one's sign
+    and inside [DET_MIN, DET_MAX].  ratio: largest distance from the origin / extent over the axes."""
+    f = np.float32
+    o = np.broadcast_to(np.asarray(o, np.float64), (len(xc), 3))
+    ext = xc.max(1) - xc.min(1)  # [n, 3]
+    r = (xc - o[:, None, :]).astype(f)
+    Jf = (r[:, 1:, :] - r[:, :1, :]).astype(np.float64)  # [n, al, a]
+    Jd = xc[:, 1:, :] - xc[:, :1, :]
+    with np.errstate(all="ignore"):
+        jerr = np.where(ext > 0, np.abs(Jf - Jd).max(1) / ext, np.inf).max(1)
+        ok = (ext > 0).all(1)
+        ratio = np.where(ext > 0, np.abs(xc - o[:, None, :]).max(1) / ext, np.inf).max(1)
+
+    def terms(J):  # J[n, al, a]: the three terms of det and of its magnitude
+        d, m = 0.0, 0.0
+        for al in range(3):
+            b, c = (al + 1) % 3, (al + 2) % 3
+            d = d + J[:, al, 0] * (J[:, b, 1] * J[:, c, 2] - J[:, c, 1] * J[:, b, 2])
+            m = m + np.abs(J[:, al, 0]) * (np.abs(J[:, b, 1] * J[:, c, 2]) + np.abs(J[:, c, 1] * J[:, b, 2]))
+        return d, m
+
+    det, mag = terms(Jf)
+    detd, _ = terms(Jd)
+    ok &= (np.abs(det) >= DET_MARGIN * mag) & (np.abs(det) >= DET_MIN) & (np.abs(det) <= DET_MAX) & ((det > 0) == (detd > 0))
+    return ok, jerr, ratio
+
+
+def p1_second_origin(xc):
+    """the second origin of a block with cells xc [n, 4, 3]: along every axis the lowest coordinate among the cells whose
+    extent along that axis is within a factor 2 of the block's least"""
+    lo, ext = xc.min(1), xc.max(1) - xc.min(1)
+    return np.array([lo[ext[:, a] <= 2.0 * ext[:, a].min(), a].min() for a in range(3)])
+
+
+def p1_block_origins(x, cells, block, first):
+    """(origin [nb, 3], status [nb], jerr [nb]) of the rule.  first[b] stays the origin of block b while every cell is ok and
+    within JKEEP; past it the better of first[b] and the second origin is taken (status 1: the second); status 2 -- neither
+    is ok and within JTOL: the float action is refused.  jerr: the chosen origin's largest Jacobian error"""
+    xc = x[cells]
+    nb = int(block.max()) + 1
+    origin, status, jerr = np.array(first, np.float64).copy(), np.zeros(nb, np.int64), np.zeros(nb)
+    for b in range(nb):
+        xb = xc[block == b]
+        ok0, j0, _ = p1_cells(xb, origin[b])
+        ok0, j0 = ok0.all(), j0.max()
+        jerr[b] = j0
+        if ok0 and j0 <= JKEEP:
+            continue
+        o1 = p1_second_origin(xb)
+        ok1, j1, _ = p1_cells(xb, o1)
+        ok1, j1 = ok1.all(), j1.max()
+        c0, c1 = ok0 and j0 <= JTOL, ok1 and j1 <= JTOL
+        if c1 and (not c0 or j1 < j0):
+            origin[b], status[b], jerr[b] = o1, 1, j1
+        elif not c0:
+            status[b], jerr[b] = 2, min(j0, j1)
+    return origin, status, jerr
+
+
+def first_listed_dof(cell_dofs, block, rank=None):
+    """the dof a block lists first (csrc/zzz_matfree.hip: dofs interior to the block, then those shared with other blocks,
+    each ascending in the library's internal numbering): [nb] caller dof ids.  rank[d] = internal number of caller dof d
+    (identity when the library kept the caller's order)"""
+    nb = int(block.max()) + 1
+    n = int(cell_dofs.max()) + 1
+    rank = np.arange(n) if rank is None else np.asarray(rank)
+    touch = np.zeros((nb, n), bool)
+    touch[np.repeat(block, cell_dofs.shape[1]), cell_dofs.reshape(-1)] = True
+    shared = touch.sum(0) > 1
+    out = np.empty(nb, np.int64)
+    for b in range(nb):
+        d = np.nonzero(touch[b])[0]
+        key = shared[d].astype(np.int64) * n + rank[d]
+        out[b] = d[np.argmin(key)]
+    return out
 
 
 def cg_h(apply, b, dtype, kmax=100, rtol=1e-6):

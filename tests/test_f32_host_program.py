@@ -2,7 +2,11 @@
 the rounding of the geometry factors and reference tables, the block-relative P1 coordinates and the element arithmetic the
 kernel's lanes run -- is host-compilable, and tools/mf_f32_host.cpp (a stand-alone program with its own main) runs it over
 a P1, a P2 and a P3 cube.  The element vectors it writes, scattered in double, must give the action the numpy restatement
-(tests/_f32_ref.py) gives: the same bound as on the GPU, 4 x the restatement's own error against the double action."""
+(tests/_f32_ref.py) gives: the same bound as on the GPU, 4 x the restatement's own error against the double action.
+
+The P1 path of the program also runs the library's decision about a block's origin (mf_f32_cell_ok, MfF32Thin: check the first
+origin cell by cell, try the second, refuse) over hostile meshes cut into Morton blocks of 128 cells as the plan cuts them;
+the build adds -fsanitize=float-divide-by-zero, so a cell that collapses to det J == 0 in a block called served ends the run."""
 import os
 import shutil
 import subprocess
@@ -11,6 +15,7 @@ import numpy as np
 import pytest
 
 import _f32_ref as fr
+import _hostile as H
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
@@ -23,7 +28,7 @@ def program(tmp_path_factory):
         pytest.skip("ROCm's clang++ not available")
     exe = str(tmp_path_factory.mktemp("mf_f32_host") / "mf_f32_host")
     src = os.path.join(ROOT, "performance-test_amd", "tools", "mf_f32_host.cpp")
-    cmd = [CLANG, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+    cmd = [CLANG, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined,float-divide-by-zero", "-fno-sanitize-recover=all",
            "-I" + os.path.join(ROOT, "performance-test_amd", "csrc"), src, "-o", exe]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -54,3 +59,52 @@ def test_host_program_under_sanitizers_matches_the_restatement(program, tmp_path
     ref = np.abs(ry - y64).max() / np.abs(y64).max()
     print(f"P{order} {dims}: host program {err:.3e}, restatement {ref:.3e}")
     assert 0 < err <= 4 * ref
+
+
+def _run_p1(program, tmp_path, C, o, block, u):
+    """the program on the cells of C in the order o, blocks of `block`: (y, status per block)"""
+    fin, fout = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
+    with open(fin, "wb") as f:
+        np.array([1, len(o), C.n, block], np.int32).tofile(f)
+        np.ascontiguousarray(C.x[C.cells[o]], np.float64).tofile(f)
+        np.ascontiguousarray(C.cell_dofs[o], np.int32).tofile(f)
+        u.tofile(f)
+    fst = str(tmp_path / "status.bin")
+    r = subprocess.run([program, fin, fout, fst], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and r.stderr == "", r.stderr[-3000:]
+    ye = np.fromfile(fout, np.float32).reshape(len(o), 4)
+    status = np.fromfile(fst, np.int32)
+    return fr.scatter(C.cell_dofs[o], ye, C.bc, C.n), status
+
+
+@pytest.mark.parametrize("name", ["offset", "shear50_b", "graded_corner"] + H.F32_P1_EXTRA)
+def test_host_program_decides_the_origin_as_the_restatement_does(program, tmp_path, name):
+    """Morton blocks of 128 cells, first origin the first vertex of a block's first cell: the program's status per block is
+    the restated rule's, no block is refused, and the action stays within the bar of the GPU test --
+    max(8 x the restatement's figure, 32) units of 2^-24 against the 50-digit reference."""
+    C = H.case(name, 1)
+    u = np.random.default_rng(1).standard_normal(C.n).astype(np.float32).astype(np.float64)
+    y_ref, t_ref, _ = H.action_reference(C, u)
+    o, blk = H.plan_cell_order(C), H.plan_cell_blocks(C, 128)
+    origin, status, jerr = fr.p1_block_origins(C.x, C.cells, blk, C.x[C.cells[o[::128], 0]])
+    y, st = _run_p1(program, tmp_path, C, o, 128, u)
+    fig = fr.figure32(y, y_ref, t_ref)
+    ref = fr.figure32(fr.action32_p1_geometry(C.x, C.cells, C.cell_dofs, C.bc, u, block=blk, origin=origin), y_ref, t_ref)
+    print(f"{name}: {len(st)} blocks, {np.count_nonzero(st == 1)} on the second origin; host program {fig:.2f}, restatement {ref:.2f}")
+    np.testing.assert_array_equal(st, status)
+    assert np.all(st < 2) and np.all(y[C.bc.astype(bool)] == 0)
+    assert (name == "offset" or name == "shear50_b") == (not np.any(st == 1))  # the graded ones need the second origin
+    assert fig <= max(8.0 * ref, 32.0)
+
+
+def test_host_program_refuses_a_block_no_origin_serves(program, tmp_path):
+    C = H.case(H.F32_P1_REFUSED, 1)
+    u = np.random.default_rng(1).standard_normal(C.n).astype(np.float32).astype(np.float64)
+    o = H.plan_cell_order(C)
+    for block in (128, len(o)):
+        blk = H.plan_cell_blocks(C, block)
+        _, status, _ = fr.p1_block_origins(C.x, C.cells, blk, C.x[C.cells[o[::block], 0]])
+        y, st = _run_p1(program, tmp_path, C, o, block, u)
+        print(f"{H.F32_P1_REFUSED} blocks of {block}: status {st.tolist()}")
+        np.testing.assert_array_equal(st, status)
+        assert np.any(st == 2) and np.isfinite(y).all()
