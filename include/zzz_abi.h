@@ -476,12 +476,15 @@ int zzz_spmv_info(zzz_ctx* ctx, int64_t info[8]);
  * one of one-chunk slices and the product runs on the kernel for those (csrc/zzz_sellp_pipe.hip: two rows per lane), else 0;
  * info[5] = workgroups per CU of the product's persistent grid.  0s when the product does not run on the stream.
  * zzz_spmv_values_info writes info[0..3] only (its signature of round 4: a caller built against that header passes four
- * entries); everything from info[4] on comes through zzz_spmv_values_info2, which writes the first min(n, 10) entries:
+ * entries); everything from info[4] on comes through zzz_spmv_values_info2, which writes the first min(n, 14) entries:
  * info[6] = 1 when the product of a block-size-3 matrix runs in block-row form (csrc/zzz_sellp_blk.hip: one lane per node,
  * 16-bit codes into a table of the matrix's distinct 3 x 3 blocks in LDS), info[7] = entries of that table (zero block
  * included), info[8] = chunks of 16 block slots per node, info[9] = 1 when the table's rows (nine doubles each) sit in LDS, 2 when
  * they are rows of nine 16-bit value offsets in memory and the VALUES sit in LDS (more than 2 200 distinct blocks; then
- * info[7] still counts the blocks); info[2] is then the bytes of THAT form. */
+ * info[7] still counts the blocks); info[2] is then the bytes of THAT form.  Where info[4] = 1: info[10] = slices whose value
+ * codes the kernel reads PACKED (4-bit indices into per-slot palettes of 16 codes: 512 B per slice for 1 024; ZZZ_SELLP_PAL=0:
+ * none), info[11] = slices read as 16-bit codes, info[12] = pairs of slices of one of either, info[13] = the most distinct
+ * codes met in one slot of one slice (a slice is packed when no slot holds more than 16). */
 int zzz_spmv_values_info(zzz_ctx* ctx, int64_t info[4]);
 int zzz_spmv_values_info2(zzz_ctx* ctx, int n, int64_t* info);
 /* ---- geometric multigrid (ZZZ_PC_MG, ZZZ_PC_PMG) ----------------------------------------------

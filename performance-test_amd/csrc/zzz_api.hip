@@ -187,6 +187,8 @@ int zzz_ctx_create(int device, zzz_ctx** out)
     ctx->sellp_blk = atoi(e);
   if (const char* e = getenv("ZZZ_SELLP_PIPE")) // 0: the generic product kernel always (A/B against the pipelined one)
     ctx->sellp_pipe = atoi(e);
+  if (const char* e = getenv("ZZZ_SELLP_PAL")) // 0: the one-chunk product reads 16-bit value codes everywhere (A/B against the packed form)
+    ctx->sellp_pal = atoi(e) != 0;
   if (const char* e = getenv("ZZZ_CG_DINV_CODES"))
     ctx->cg_dinv_codes = atoi(e);
   if (const char* e = getenv("ZZZ_CG_XDEFER")) // the classical CG's solution update once per K iterations: 0 never, 1 by size, 2 always
@@ -1171,7 +1173,7 @@ int zzz_spmv_values_info2(zzz_ctx* ctx, int n, int64_t* out)
   ZZZ_ENTER(ctx);
   if (!out || n < 0 || !ctx->have_pattern)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_spmv_values_info: no pattern");
-  int64_t info[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  int64_t info[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   if (sellp_active(ctx))
   {
     const bool blk = zzz::sellp_blk_serves(ctx);
@@ -1188,8 +1190,22 @@ int zzz_spmv_values_info2(zzz_ctx* ctx, int n, int64_t* out)
     info[9] = blk ? ctx->bk_form : (win ? ctx->bw_nblk : 0);
     if (win)
       info[4] = 0, info[5] = 1;
+    // the packed form of the one-chunk kernel's value codes (k_sp_pal_build): slices packed / read as 16-bit codes, pairs of
+    // one of either, the largest number of distinct codes met in a (slice, slot)
+    if (info[4] && ctx->sp_pal_on)
+    {
+      info[10] = ctx->sp_pal_packed;
+      info[11] = ctx->nslices - ctx->sp_pal_packed;
+      info[12] = ctx->sp_pal_mixed;
+      info[13] = ctx->sp_pal_maxcount;
+    }
+    else if (info[4])
+    {
+      info[11] = ctx->nslices;
+      info[13] = ctx->sellp_pal ? ctx->sp_pal_maxcount : 0;
+    }
   }
-  for (int i = 0; i < std::min(n, 10); ++i)
+  for (int i = 0; i < std::min(n, 14); ++i)
     out[i] = info[i];
   return ZZZ_OK;
 }

@@ -923,7 +923,7 @@ int dinv_codes_build(zzz_ctx* ctx, int64_t n, DinvCodes& dzc)
 // bytes one CG iteration touches (operator + `nvec` vectors) against the Infinity Cache
 bool loop_exceeds_cache(zzz_ctx* ctx, int nvec)
 {
-  const double op = sellp_active(ctx) ? (double)sellp_stream_bytes(ctx) : 10.0 * (double)ctx->nnz;
+  const double op = sellp_active(ctx) ? (double)sellp_stream_bytes(ctx, true) : 10.0 * (double)ctx->nnz;
   return op + 8.0 * nvec * (double)ctx->nloc() > 200.0e6;
 }
 

@@ -301,6 +301,17 @@ struct zzz_ctx
   zzz::DevBuf<uint8_t> sp_pairs;            // one-chunk streams: slices 2 p and 2 p + 1 form an affine pair (zzz_sellp_pipe.hip)
   bool sp_pairs_ok = false;
   int sellp_pipe = 1;                       // ZZZ_SELLP_PIPE=0: the generic product always
+  // one-chunk streams on the stream dictionary in LDS: a slice none of whose eight slots holds more than 16 distinct value
+  // codes in its 64 rows is also kept PACKED (k_sp_pal_build, zzz_sellp_dict.hip): 512 B per chunk in sp_pal, entry l (8 B) =
+  // {row l's eight 4-bit palette indices, slot e at bits 4 e; palette codes 2 l and 2 l + 1 of the slice's 8 x 16, ascending
+  // per slot}.  sp_palok[slice] = 1: packed.  sp_vcode stays whole beside it (generic kernel, unpacked slices).
+  zzz::DevBuf<uint2> sp_pal;
+  zzz::DevBuf<uint8_t> sp_palok;
+  zzz::DevBuf<int32_t> sp_pal_info;         // [0] packed slices, [1] largest count of distinct codes in a (slice, slot), [2] mixed pairs
+  bool sp_pal_on = false;                   // the packed form serves the one-chunk kernel's launches (at least one slice is packed)
+  int64_t sp_pal_packed = 0, sp_pal_mixed = 0;
+  int sp_pal_maxcount = 0;
+  int sellp_pal = 1;                        // ZZZ_SELLP_PAL=0: never
   int64_t nslices = 0, sp_chunks = 0, sp_kept = 0, sp_bytes = 0; // slices, chunks of the stream, matrix entries kept in it,
                                                                  // bytes a product reads from it
   zzz::DevBuf<uint8_t> sp_wlast; // per slice: entries of the longest row in its last chunk (1..8)
@@ -596,7 +607,7 @@ bool sellp_active(zzz_ctx* ctx);
 int sellp_resolve(zzz_ctx* ctx);
 int sellp_pattern_bounds(zzz_ctx* ctx);
 int sellp_capacity_rows(zzz_ctx* ctx); // sp_crow := capacity-based row starts of the compacted copy (+ its allocation)
-int64_t sellp_stream_bytes(const zzz_ctx* ctx);
+int64_t sellp_stream_bytes(const zzz_ctx* ctx, bool as_codes = false);
 constexpr int SP_DICT_LDS_ENTRIES = 2048; // a value dictionary of at most this many entries is copied into LDS by every workgroup (16 KiB: eight per CU)
 int launch_sellp(zzz_ctx* ctx, ProductCall c, int* npartials);
 int launch_sellp_overlapped(zzz_ctx* ctx, double* x, ProductCall c, int* npartials);

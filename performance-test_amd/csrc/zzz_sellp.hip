@@ -464,7 +464,7 @@ bool sellp_active(zzz_ctx* ctx)
     // that still take the generic kernel read its values as doubles.  7.6 ms per assembly at 6.2 M rows of P3, 3 ms at C4.
     // A failed build leaves the stream as it is.
     ctx->sp_dict_done = true;
-    ctx->sp_dict_on = ctx->sp_sd_on = ctx->sp_sd_all = false;
+    ctx->sp_dict_on = ctx->sp_sd_on = ctx->sp_sd_all = ctx->sp_pal_on = false;
     ctx->sp_dict_n = 0;
     if (!ctx->sp_special_tried)
     {
@@ -475,7 +475,7 @@ bool sellp_active(zzz_ctx* ctx)
     {
       if (sp_dict_build(ctx) != ZZZ_OK)
       {
-        ctx->sp_dict_on = false;
+        ctx->sp_dict_on = ctx->sp_pal_on = false;
         (void)hipGetLastError();
         ctx->sp_vcode.release();
       }
@@ -498,13 +498,18 @@ bool sellp_active(zzz_ctx* ctx)
 
 // bytes one product reads from the stream (values or value codes + dictionary, column codes, bases; int32 chunks are not
 // counted separately)
-int64_t sellp_stream_bytes(const zzz_ctx* ctx)
+// as_codes: a packed slice counted as its 16-bit codes -- what the 200-MB size rules go by (below, cg_loop_exceeds_cache): they
+// were set on that form's bytes, and the sizes either side of them keep the load policy, the coded diagonal and the deferred
+// solution update they had before the packed form
+int64_t sellp_stream_bytes(const zzz_ctx* ctx, bool as_codes)
 {
   if (sellp_blk_serves(ctx))
     return ctx->bk_bytes; // (descriptors and table included)
   if (sellp_win_serves(ctx))
     return ctx->bw_bytes;
-  return (ctx->sp_sd_on ? ctx->sp_sd_bytes : (ctx->sp_dict_on ? ctx->sp_dict_bytes : ctx->sp_bytes)) + ctx->nslices * 8; // (x windows: sp_win_bytes, reported apart)
+  // (a packed slice of the one-chunk kernel: 512 B of indices and palettes for its 1 024 B of codes)
+  const int64_t packed = !as_codes && ctx->sp_pal_on && sellp_pipe_wgs(ctx, false) ? 512 * ctx->sp_pal_packed : 0;
+  return (ctx->sp_sd_on ? ctx->sp_sd_bytes : (ctx->sp_dict_on ? ctx->sp_dict_bytes : ctx->sp_bytes)) + ctx->nslices * 8 - packed; // (x windows: sp_win_bytes, reported apart)
 }
 
 // Load policy of the product: non-temporal stream loads when one CG iteration (the stream and six vectors) cannot stay in
@@ -513,7 +518,7 @@ int64_t sellp_stream_bytes(const zzz_ctx* ctx)
 // vectors reads 4 % faster non-temporally: 0.091 -> 0.087 ms at C2.)
 static bool sp_stream_nt(const zzz_ctx* ctx)
 {
-  return (double)sellp_stream_bytes(ctx) + 48.0 * (double)(ctx->n_owned + ctx->n_ghost) * ctx->bs > 200.0e6;
+  return (double)sellp_stream_bytes(ctx, true) + 48.0 * (double)(ctx->n_owned + ctx->n_ghost) * ctx->bs > 200.0e6;
 }
 
 // plain: the launch carries no Chebyshev epilogue, so the specialised kernels (one-chunk slices, block rows) may serve it;

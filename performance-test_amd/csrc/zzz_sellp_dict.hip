@@ -127,6 +127,112 @@ __global__ __launch_bounds__(256) void k_sp_dict_encode(const int2* __restrict__
     atomicAdd(bytes_out, bytes);
 }
 
+// ---- the packed form of one-chunk slices: 4-bit palette indices --------------------------------------------------------
+// The 1 200 values of a regular mesh's matrix are rounding variants of a handful of stencil entries: the 64 rows of a slice
+// hold three or four distinct codes in a slot, seldom more than a dozen.  One wavefront per slice, lane = row, ONE walk over
+// the codes just written: per slot the distinct codes are collected (the first lane still without a palette entry names the
+// next one: as many rounds as there are values), ranked, and stored ascending -- the result depends on the codes alone.  Every
+// slot at most 16: the slice is PACKED -- pal[chunk][lane] = {the row's eight 4-bit indices, slot e at bits 4 e; palette codes
+// 2 l and 2 l + 1 of the slice's 8 x 16} (512 B; unused palette entries: code 0), palok[slice] = 1.  Otherwise its block is
+// zeros and palok[slice] = 0: the product reads its 16-bit codes.  A slot beyond the width and a lane without a row hold code 0
+// like any +0.0 and count as that value.  info: [0] packed slices, [1] the largest count met, [2] mixed pairs (k_sp_pal_mixed).
+__global__ __launch_bounds__(256) void k_sp_pal_build(const int2* __restrict__ desc, const uint16_t* __restrict__ vcode, int64_t nslices,
+                                                       const int* __restrict__ dict_info, uint2* __restrict__ pal,
+                                                       uint8_t* __restrict__ palok, int32_t* __restrict__ info)
+{
+  __shared__ uint16_t pal_s[4][128];
+  if (dict_info[1])
+    return;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  uint16_t* const ps = pal_s[wv];
+  int npacked = 0, maxc = 0;
+  for (int64_t s = blockIdx.x * 4ll + wv; s < nslices; s += gridDim.x * 4ll)
+  {
+    const int2 ds = desc[s];
+    const int nch = ds.y & 0xffffff;
+    if (nch != 1) // (no chunk: nothing to read, packed or not; one-chunk streams have no longer slices)
+    {
+      if (lane == 0)
+        palok[s] = 0;
+      continue;
+    }
+    const uint4v q = reinterpret_cast<const uint4v*>(vcode + (size_t)ds.x * 512)[lane];
+    const unsigned code[8] = {q.x & 0xffffu, q.x >> 16, q.y & 0xffffu, q.y >> 16, q.z & 0xffffu, q.z >> 16, q.w & 0xffffu, q.w >> 16};
+    ps[2 * lane] = 0;
+    ps[2 * lane + 1] = 0;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    unsigned idx = 0;
+    bool ok = true;
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+    {
+      const unsigned cur = code[e];
+      bool rem = true;
+      unsigned myval = 0, mine = 0; // lane k: the k-th value found; the lane's own value is the mine-th
+      int k = 0;
+      for (;;)
+      {
+        const unsigned long long m = __ballot(rem);
+        if (!m)
+          break;
+        const unsigned v = (unsigned)__builtin_amdgcn_readlane((int)cur, __builtin_amdgcn_readfirstlane(__builtin_ctzll(m)));
+        if (cur == v)
+        {
+          mine = (unsigned)k;
+          rem = false;
+        }
+        if (lane == k)
+          myval = v;
+        ++k;
+      }
+      maxc = k > maxc ? k : maxc;
+      if (k > 16)
+      {
+        ok = false;
+        continue;
+      }
+      unsigned rank = 0;
+      for (int j = 0; j < k; ++j)
+        rank += (unsigned)__builtin_amdgcn_readlane((int)myval, j) < myval ? 1u : 0u;
+      if (lane < k)
+        ps[e * 16 + rank] = (uint16_t)myval;
+      idx |= (unsigned)__shfl((int)rank, (int)mine) << (4 * e);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    uint2 out = make_uint2(0u, 0u);
+    if (ok)
+      out = make_uint2(idx, (unsigned)ps[2 * lane] | ((unsigned)ps[2 * lane + 1] << 16));
+    pal[(size_t)ds.x * 64 + lane] = out;
+    if (lane == 0)
+      palok[s] = ok ? 1 : 0;
+    npacked += ok ? 1 : 0;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
+  if (lane == 0)
+  {
+    if (npacked)
+      atomicAdd(&info[0], npacked);
+    if (maxc)
+      atomicMax(&info[1], maxc);
+  }
+}
+
+// pairs of slices 2 p, 2 p + 1 of which one is packed and one is not (the product takes them a lane per row)
+__global__ __launch_bounds__(256) void k_sp_pal_mixed(const uint8_t* __restrict__ palok, int64_t nslices, const int* __restrict__ dict_info,
+                                                       int32_t* __restrict__ info)
+{
+  if (dict_info[1])
+    return;
+  int n = 0;
+  for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; 2 * p + 1 < nslices; p += (int64_t)gridDim.x * blockDim.x)
+    n += palok[2 * p] != palok[2 * p + 1] ? 1 : 0;
+  if (n)
+    atomicAdd(&info[2], n);
+}
+
 // ---- per-slice value dictionaries (long rows: P3) ----------------------------------------------------------------
 // A slice of 64 rows of one entity type holds a few hundred distinct values even where the whole matrix holds thousands
 // (P3 at 30^3 sub-cubes: median 296 per slice, all slices below 1 024; 7 400 in the matrix; 8 270 at 61^3).  One wavefront
@@ -305,7 +411,7 @@ __global__ __launch_bounds__(128) void k_sp_sd_build(const int2* __restrict__ de
 int sp_dict_build(zzz_ctx* ctx)
 {
   ctx->sp_dict_done = true;
-  ctx->sp_dict_on = false;
+  ctx->sp_dict_on = ctx->sp_pal_on = false;
   ctx->sp_dict_n = 0;
   // ZZZ_SELLP_DICT: 0 never, 2 always (tests at small sizes), 1: for streams of more than 48 MB of values -- below that the
   // whole loop sits in the Infinity Cache, bytes are not what the product waits for, and building the dictionary (three
@@ -342,6 +448,22 @@ int sp_dict_build(zzz_ctx* ctx)
                        ctx->sp_meta.p, (int)ctx->nrows, nsl, vs.table.p, vs.slot.p, vs.info.p, ctx->sp_vcode.p, bytes);
   unsigned long long hb = 0;
   ZZZ_HIP(ctx, hipMemcpyAsync(&hb, bytes, sizeof(hb), hipMemcpyDeviceToHost, s));
+  // the packed form of the codes (ZZZ_SELLP_PAL: 0 never, 1 default) for the streams spmv_one_kernel serves (sellp_pipe_wgs:
+  // one-chunk slices, natural order, the dictionary in LDS): built behind the encoding, read back with the same synchronisation
+  const bool pal = ctx->sellp_pal && ctx->sp_one_chunk && !ctx->sp_sorted && ctx->bs == 1 && ctx->sp_win_max == 0;
+  int32_t hp[4] = {0, 0, 0, 0};
+  if (pal)
+  {
+    ZZZ_HIP(ctx, ctx->sp_pal.alloc((size_t)ctx->sp_chunks * 64));
+    ZZZ_HIP(ctx, ctx->sp_palok.alloc((size_t)nsl + 1));
+    ZZZ_HIP(ctx, ctx->sp_pal_info.reserve(4));
+    ZZZ_HIP(ctx, hipMemsetAsync(ctx->sp_pal_info.p, 0, 4 * sizeof(int32_t), s));
+    hipLaunchKernelGGL(k_sp_pal_build, dim3(grid), dim3(256), 0, s, desc, ctx->sp_vcode.p, nsl, vs.info.p, ctx->sp_pal.p, ctx->sp_palok.p,
+                       ctx->sp_pal_info.p);
+    hipLaunchKernelGGL(k_sp_pal_mixed, dim3((unsigned)std::min<int64_t>((nsl / 2 + 255) / 256 + 1, 1024)), dim3(256), 0, s, ctx->sp_palok.p,
+                       nsl, vs.info.p, ctx->sp_pal_info.p);
+    ZZZ_HIP(ctx, hipMemcpyAsync(hp, ctx->sp_pal_info.p, sizeof(hp), hipMemcpyDeviceToHost, s));
+  }
   int n = 0;
   ZZZ_HIP(ctx, vs.finish(s, n));
   if (!n)
@@ -349,6 +471,10 @@ int sp_dict_build(zzz_ctx* ctx)
   ctx->sp_dict_n = n;
   ctx->sp_dict_bytes = (int64_t)hb + (int64_t)n * 8;
   ctx->sp_dict_on = true;
+  ctx->sp_pal_packed = hp[0];
+  ctx->sp_pal_maxcount = hp[1];
+  ctx->sp_pal_mixed = hp[2];
+  ctx->sp_pal_on = pal && n <= SP_DICT_LDS_ENTRIES && hp[0] > 0;
   return ZZZ_OK;
 }
 

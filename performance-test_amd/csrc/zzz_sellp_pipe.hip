@@ -18,6 +18,7 @@
 // longer explained by that count -- deeper look-ahead, a touch of the farthest run a step ahead and staggered wavefronts
 // were measured and changed nothing: see DESIGN.md section 4b.
 #include <algorithm>
+#include <array>
 #include <cstdlib>
 #include <type_traits>
 
@@ -88,15 +89,28 @@ __global__ __launch_bounds__(256) void k_sp_pairs(const int2* __restrict__ desc,
   }
 }
 
-template <bool DOT, bool SR, bool NT>
+// PAL: the PACKED form of the value codes (k_sp_pal_build, zzz_sellp_dict.hip; the layout: zzz_internal.h, sp_pal).  A slice
+// whose every slot holds at most 16 distinct codes is read as 512 B instead of 1 024: per row eight 4-bit indices into the
+// slice's palettes (8 slots x 16 codes).  An affine pair of two packed slices takes its stream in ONE 16-B load per lane (lanes
+// 0..31 the first slice's block, 32..63 the second's): the lane's two rows' indices and four palette codes -- its share of the
+// two palettes.  At consumption the lane looks its four codes up in the dictionary and stores the doubles into the wavefront's
+// own LDS area (2 x 128 doubles: [slice of the pair][slot][index]); the sixteen values of its two rows are then read from
+// there.  Nobody but the wavefront touches the area: the order is program order (LDS serves a wavefront's accesses in order),
+// kept for the compiler by wavefront-scope fences; no workgroup barrier in the loop.  The doubles that meet x are the
+// dictionary's, in the same order: the same bits.  A slice that is not packed is served by its own mark, in the pair form (the
+// lanes of its half) and in the lane-per-row form alike: its 16-bit codes are loaded where the slice is worked on (rare: the
+// stage holds four dwords, not eight); a packed slice in the lane-per-row form: 8 B of stream per lane, its half of the area.
+template <bool DOT, bool SR, bool NT, bool PAL>
 __global__ __launch_bounds__(SP_BLOCK, SR ? SP_ONE_WGS_SR : SP_ONE_WGS) void spmv_one_kernel(
     const int2* __restrict__ p_desc, const unsigned long long* __restrict__ p_smode, const uint8_t* __restrict__ p_pairs,
     const double* __restrict__ p_svals, const uint16_t* __restrict__ p_c16, const int32_t* __restrict__ p_meta,
-    const uint16_t* __restrict__ p_vcode, const double* __restrict__ p_dict, const double* __restrict__ p_x, double* __restrict__ p_y,
+    const uint16_t* __restrict__ p_vcode, const uint2* __restrict__ p_pal, const uint8_t* __restrict__ p_palok,
+    const double* __restrict__ p_dict, const double* __restrict__ p_x, double* __restrict__ p_y,
     const double* __restrict__ p_rvec, const int32_t* __restrict__ p_list, PipeArgs a)
 {
   extern __shared__ __attribute__((aligned(16))) double pp_lds[]; // the value dictionary
   __shared__ double red[SP_BLOCK / 64];
+  __shared__ __attribute__((aligned(16))) double pal_area[PAL ? (SP_BLOCK / 64) * 256 : 2]; // per wavefront 2 x [8 slots][16]
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const double* dict = pp_lds;
@@ -112,7 +126,7 @@ __global__ __launch_bounds__(SP_BLOCK, SR ? SP_ONE_WGS_SR : SP_ONE_WGS) void spm
   const int n_steps = first_item < hi ? (int)((hi - first_item + n_in_xcd - 1) / n_in_xcd) : 0;
 
   // look-ahead registers, lane l <-> step regs_base + l: per slice chunk | width << 25 | class << 29 | exists << 31;
-  // the first slice's index, bit 30: an affine pair
+  // the first slice's index, bit 30: an affine pair, bits 28, 29: the first, the second slice is packed
   int r_ia = 0, r_ib = 0, r_s = 0;
   auto load_regs = [&](int base) {
     const int i = base + lane;
@@ -132,8 +146,10 @@ __global__ __launch_bounds__(SP_BLOCK, SR ? SP_ONE_WGS_SR : SP_ONE_WGS) void spm
     };
     r_ia = slice_info(sa);
     r_ib = slice_info(sa + 1);
-    const bool pr = have && sa + 1 < a.nslices && p_pairs[sa >> 1] != 0;
-    r_s = have ? ((int)sa | (pr ? 0x40000000 : 0)) : 0;
+    bool pr = have && sa + 1 < a.nslices && p_pairs[sa >> 1] != 0;
+    const bool pka = PAL && have && sa < a.nslices && p_palok[sa] != 0;
+    const bool pkb = PAL && have && sa + 1 < a.nslices && p_palok[sa + 1] != 0;
+    r_s = have ? ((int)sa | (pr ? 0x40000000 : 0) | (pka ? 0x10000000 : 0) | (pkb ? 0x20000000 : 0)) : 0;
   };
   load_regs(0);
   if (a.stop_flag && *a.stop_flag)
@@ -160,6 +176,7 @@ __global__ __launch_bounds__(SP_BLOCK, SR ? SP_ONE_WGS_SR : SP_ONE_WGS) void spm
   // descriptors: the codes, x, y (and r) -- offsets below 4 GB (the launcher sees to it)
   const int nb8 = a.nrows * 8;
   const __amdgpu_buffer_rsrc_t rs_vq = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p_vcode), 0, a.nslices * 1024, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_pq = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint2*>(p_pal), 0, PAL ? a.nslices * 512 : 0, 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(p_x), 0, nb8, 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(p_y, 0, nb8, 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_r = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(SR ? p_rvec : p_x), 0, nb8, 0x00020000);
@@ -170,7 +187,9 @@ __global__ __launch_bounds__(SP_BLOCK, SR ? SP_ONE_WGS_SR : SP_ONE_WGS) void spm
   {
     int ba[8];          // slot bases of the first slice (scalars; word 0 with the mode bits; a pair's second: 64 on)
     uint4v c0, c1;      // value codes: pair form, the lane's rows 2 l and 2 l + 1; else the lane's row of either slice
+                        // (PAL: c0 alone -- pair form, the lane's 16 B of the packed blocks; else .xy, .zw its 8 B of either slice's)
   };
+  double* const area = pal_area + (PAL ? wv * 256 : 0);
   // requested behind the gathers of the step before: bases (scalar loads), value codes
   auto prefetch = [&](Two& S, int ia, int ib, int sw) {
     const int ca = ia & 0x1ffffff, cb = ib & 0x1ffffff;
@@ -178,6 +197,22 @@ __global__ __launch_bounds__(SP_BLOCK, SR ? SP_ONE_WGS_SR : SP_ONE_WGS) void spm
 #pragma unroll
     for (int e = 0; e < 8; ++e)
       S.ba[e] = ma[e];
+    if (PAL)
+    {
+      if (sw & 0x40000000)
+      {
+        const auto q = __builtin_amdgcn_raw_buffer_load_b128(rs_pq, ((lane < 32 ? ca : cb) << 9) + ((lane & 31) << 4), 0, aux);
+        S.c0.x = q[0], S.c0.y = q[1], S.c0.z = q[2], S.c0.w = q[3];
+      }
+      else
+      {
+        // (an unpacked slice's block holds zeros, a missing slice reads chunk 0's: loaded, not used)
+        const auto t0 = __builtin_amdgcn_raw_buffer_load_b64(rs_pq, (ca << 9) + lane8, 0, aux);
+        const auto t1 = __builtin_amdgcn_raw_buffer_load_b64(rs_pq, (cb << 9) + lane8, 0, aux);
+        S.c0.x = t0[0], S.c0.y = t0[1], S.c0.z = t1[0], S.c0.w = t1[1];
+      }
+      return;
+    }
     int off0, off1;
     if (sw & 0x40000000)
     {
@@ -232,10 +267,17 @@ __global__ __launch_bounds__(SP_BLOCK, SR ? SP_ONE_WGS_SR : SP_ONE_WGS) void spm
   };
 
   // one slice in the lane-per-row form: W gathers, W dictionary look-ups, W products; `between`: what is requested behind the gathers
-  auto slice = [&](auto wtag, const int (&b)[8], const uint4v vq, int info, int s, auto&& between) {
+  // (PAL: vq.xy = the lane's 8 B of a packed slice, half = which half of the wavefront's area the slice's palettes take;
+  // an unpacked slice's codes are loaded here)
+  auto slice = [&](auto wtag, const int (&b)[8], uint4v vq, int info, int s, bool packed, int half, auto&& between) {
     constexpr int W = decltype(wtag)::value;
     const int w = (info >> 25) & 15, cls = (info >> 29) & 3;
     const uint4v cq = load_codes(info);
+    if (PAL && !packed)
+    {
+      const auto q = __builtin_amdgcn_raw_buffer_load_b128(rs_vq, ((info & 0x1ffffff) << 10) + lane16, 0, aux);
+      vq.x = q[0], vq.y = q[1], vq.z = q[2], vq.w = q[3];
+    }
     unsigned cc[8];
     if (cls == SP_CLS_C16)
     {
@@ -273,9 +315,25 @@ __global__ __launch_bounds__(SP_BLOCK, SR ? SP_ONE_WGS_SR : SP_ONE_WGS) void spm
         rr = __hiloint2double((int)t[1], (int)t[0]);
       }
     }
+    if (PAL && packed)
+    {
+      double* const ah = area + half * 128;
+      dbl2 t;
+      t.x = dict[vq.y & 0xffffu], t.y = dict[vq.y >> 16];
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      *reinterpret_cast<dbl2*>(ah + 2 * lane) = t;
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();
 #pragma unroll
-    for (int e = 0; e < W; ++e)
-      v[e] = dict[vc[e]];
+      for (int e = 0; e < W; ++e)
+        v[e] = ah[e * 16 + ((vq.x >> (4 * e)) & 15u)];
+    }
+    else
+    {
+#pragma unroll
+      for (int e = 0; e < W; ++e)
+        v[e] = dict[vc[e]];
+    }
     between();
     double sum = 0.0;
 #pragma unroll
@@ -293,7 +351,7 @@ __global__ __launch_bounds__(SP_BLOCK, SR ? SP_ONE_WGS_SR : SP_ONE_WGS) void spm
       }
     }
   };
-  auto slice_w = [&](const int (&b)[8], const uint4v vq, int info, int s, auto&& between) {
+  auto slice_w = [&](const int (&b)[8], const uint4v vq, int info, int s, bool packed, int half, auto&& between) {
     if (info >= 0) // no such slice
     {
       between();
@@ -301,14 +359,14 @@ __global__ __launch_bounds__(SP_BLOCK, SR ? SP_ONE_WGS_SR : SP_ONE_WGS) void spm
     }
     const int w = (info >> 25) & 15;
     if (w == 7)
-      slice(std::integral_constant<int, 7>(), b, vq, info, s, between);
+      slice(std::integral_constant<int, 7>(), b, vq, info, s, packed, half, between);
     else
-      slice(std::integral_constant<int, 8>(), b, vq, info, s, between);
+      slice(std::integral_constant<int, 8>(), b, vq, info, s, packed, half, between);
   };
 
   // one step: consume stage S (scalars ia, ib, sw), request the next step's stream into stage N
   auto body = [&](Two& S, int ia, int ib, int sw, Two& N, int ia_n, int ib_n, int sw_n) {
-    const int sa = sw & 0x3fffffff;
+    const int sa = sw & 0x0fffffff;
     auto request_next = [&]() {
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_waitcnt(0xC07F); // lgkmcnt(0): the look-ups are back before scalar loads are in flight (they return out of order)
@@ -319,8 +377,12 @@ __global__ __launch_bounds__(SP_BLOCK, SR ? SP_ONE_WGS_SR : SP_ONE_WGS) void spm
     {
       // an affine pair: the lane's rows are 2 l and 2 l + 1 of the 128; slot e is the run of 128 doubles from ba[e]
       const int w = (ia >> 25) & 15;
-      auto pair = [&](auto wtag, auto dtag) {
+      auto pair = [&](auto wtag, auto dtag, auto mtag) {
         constexpr int W = decltype(wtag)::value;
+        // MIX (PAL only): one of the pair's slices, or both, are not packed -- the lanes of such a half load their rows' 16-bit
+        // codes here and look the values up in the dictionary.  The pair keeps the pair form, so that a lane sums the same rows'
+        // <p, A p> terms whether the stream is packed or not: solves agree bit for bit with ZZZ_SELLP_PAL=0.
+        constexpr bool MIX = decltype(mtag)::value;
         // D >= 1: slot D is the DIAGONAL's (its run starts at the pair's first row) and slots D - 1, D, D + 1 start at
         // consecutive columns (c - 1, c, c + 1: the mesh line's own neighbours) -- the caller has checked both on the slots'
         // bases (scalars).  Two loads are saved per pair then: the middle run is the outer two's inner halves,
@@ -374,13 +436,53 @@ __global__ __launch_bounds__(SP_BLOCK, SR ? SP_ONE_WGS_SR : SP_ONE_WGS) void spm
           return (e & 1) ? wd >> 16 : wd & 0xffffu;
         };
         double s0 = 0.0, s1 = 0.0;
-#pragma unroll
-        for (int e = 0; e < W; ++e)
-          if (W < 8 || e < w) // (W = 8 also serves the narrow pairs: a slot beyond the width has read run 0, a valid one)
+        if (PAL)
+        {
+          // the lane's four palette entries into the wavefront's area (entries 4 l .. 4 l + 3 of the 256: lanes 32.. fill the
+          // second slice's half), then the rows' values from the lane's half by their 4-bit indices
+          dbl2 t0, t1;
+          t0.x = dict[c0.y & 0xffffu], t0.y = dict[c0.y >> 16];
+          t1.x = dict[c0.w & 0xffffu], t1.y = dict[c0.w >> 16];
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+          *reinterpret_cast<dbl2*>(area + 4 * lane) = t0;
+          *reinterpret_cast<dbl2*>(area + 4 * lane + 2) = t1;
+          __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+          __builtin_amdgcn_wave_barrier();
+          const double* const ah = area + (lane >> 5) * 128;
+          // (an unpacked slice's block is zeros: its lanes have stored dictionary entry 0 and read it here, for nothing)
+          uint4v u0 = {0u, 0u, 0u, 0u}, u1 = {0u, 0u, 0u, 0u};
+          bool coded = false;
+          if (MIX)
           {
-            s0 += dict[code(c0, e)] * xq[e].x;
-            s1 += dict[code(c1, e)] * xq[e].y;
+            coded = ((lane < 32 ? sw & 0x10000000 : sw & 0x20000000)) == 0;
+            if (coded)
+            {
+              const int off = (((lane < 32 ? ia : ib) & 0x1ffffff) << 10) + ((lane & 31) << 5);
+              const auto q0 = __builtin_amdgcn_raw_buffer_load_b128(rs_vq, off, 0, aux);
+              const auto q1 = __builtin_amdgcn_raw_buffer_load_b128(rs_vq, off + 16, 0, aux);
+              u0.x = q0[0], u0.y = q0[1], u0.z = q0[2], u0.w = q0[3];
+              u1.x = q1[0], u1.y = q1[1], u1.z = q1[2], u1.w = q1[3];
+            }
           }
+#pragma unroll
+          for (int e = 0; e < W; ++e)
+            if (W < 8 || e < w)
+            {
+              const double v0 = ah[e * 16 + ((c0.x >> (4 * e)) & 15u)], v1 = ah[e * 16 + ((c0.z >> (4 * e)) & 15u)];
+              s0 += (MIX && coded ? dict[code(u0, e)] : v0) * xq[e].x;
+              s1 += (MIX && coded ? dict[code(u1, e)] : v1) * xq[e].y;
+            }
+        }
+        else
+        {
+#pragma unroll
+          for (int e = 0; e < W; ++e)
+            if (W < 8 || e < w) // (W = 8 also serves the narrow pairs: a slot beyond the width has read run 0, a valid one)
+            {
+              s0 += dict[code(c0, e)] * xq[e].x;
+              s1 += dict[code(c1, e)] * xq[e].y;
+            }
+        }
         uint4v out;
         out.x = (unsigned)__double2loint(s0), out.y = (unsigned)__double2hiint(s0);
         out.z = (unsigned)__double2loint(s1), out.w = (unsigned)__double2hiint(s1);
@@ -416,35 +518,47 @@ __global__ __launch_bounds__(SP_BLOCK, SR ? SP_ONE_WGS_SR : SP_ONE_WGS) void spm
         return d + 1 < w && (unsigned)S.ba[d] == rb && bl + 1u == rb && (unsigned)S.ba[d + 1] == rb + 1u;
       };
       const int dsel = tri(3) ? 3 : (tri(4) ? 4 : -1);
-      if (w == 7)
+      constexpr std::false_type all_packed;
+      constexpr std::integral_constant<bool, PAL> not_all_packed; // (never taken without PAL: the body of all_packed again)
+      if (PAL && (sw & 0x30000000) != 0x30000000) // (rare: the general body, every slot loaded)
+      {
+        if (w == 7)
+          pair(std::integral_constant<int, 7>(), std::integral_constant<int, -1>(), not_all_packed);
+        else
+          pair(std::integral_constant<int, 8>(), std::integral_constant<int, -1>(), not_all_packed);
+      }
+      else if (w == 7)
       {
         if (dsel == 3)
-          pair(std::integral_constant<int, 7>(), std::integral_constant<int, 3>());
+          pair(std::integral_constant<int, 7>(), std::integral_constant<int, 3>(), all_packed);
         else if (dsel == 4)
-          pair(std::integral_constant<int, 7>(), std::integral_constant<int, 4>());
+          pair(std::integral_constant<int, 7>(), std::integral_constant<int, 4>(), all_packed);
         else
-          pair(std::integral_constant<int, 7>(), std::integral_constant<int, -1>());
+          pair(std::integral_constant<int, 7>(), std::integral_constant<int, -1>(), all_packed);
       }
       else
       {
         if (dsel == 3)
-          pair(std::integral_constant<int, 8>(), std::integral_constant<int, 3>());
+          pair(std::integral_constant<int, 8>(), std::integral_constant<int, 3>(), all_packed);
         else if (dsel == 4)
-          pair(std::integral_constant<int, 8>(), std::integral_constant<int, 4>());
+          pair(std::integral_constant<int, 8>(), std::integral_constant<int, 4>(), all_packed);
         else
-          pair(std::integral_constant<int, 8>(), std::integral_constant<int, -1>());
+          pair(std::integral_constant<int, 8>(), std::integral_constant<int, -1>(), all_packed);
       }
     }
     else
     {
       // the two slices one after the other, a lane per row; the next step's stream goes out behind the first one's gathers
-      slice_w(S.ba, S.c0, ia, sa, request_next);
+      uint4v qb = S.c1;
+      if (PAL)
+        qb.x = S.c0.z, qb.y = S.c0.w; // (before request_next: the stage it fills may be read no later than that)
+      slice_w(S.ba, S.c0, ia, sa, (sw & 0x10000000) != 0, 0, request_next);
       int bb[8]; // (the second slice's bases: loaded here, this path is the rare one)
       const int32_t* __restrict__ mb = p_meta + (int64_t)(ib & 0x1ffffff) * 8;
 #pragma unroll
       for (int e = 0; e < 8; ++e)
         bb[e] = mb[e];
-      slice_w(bb, S.c1, ib, sa + 1, []() {});
+      slice_w(bb, qb, ib, sa + 1, (sw & 0x20000000) != 0, 1, []() {});
     }
   };
 
@@ -510,10 +624,15 @@ int sellp_pipe_wgs(const zzz_ctx* ctx, bool sr)
 }
 
 // [mode][load]; a product with a Chebyshev term takes the generic kernel
-using OneKernel = decltype(&spmv_one_kernel<false, false, false>);
-static const OneKernel one_kernels[PM_PLAIN + 1][2] = {{spmv_one_kernel<true, true, true>, spmv_one_kernel<true, true, false>},
-                                                       {spmv_one_kernel<true, false, true>, spmv_one_kernel<true, false, false>},
-                                                       {spmv_one_kernel<false, false, true>, spmv_one_kernel<false, false, false>}};
+using OneKernel = decltype(&spmv_one_kernel<false, false, false, false>);
+template <bool PAL>
+constexpr std::array<std::array<OneKernel, 2>, PM_PLAIN + 1> one_variants()
+{
+  return {{{spmv_one_kernel<true, true, true, PAL>, spmv_one_kernel<true, true, false, PAL>},
+           {spmv_one_kernel<true, false, true, PAL>, spmv_one_kernel<true, false, false, PAL>},
+           {spmv_one_kernel<false, false, true, PAL>, spmv_one_kernel<false, false, false, PAL>}}};
+}
+static const std::array<std::array<OneKernel, 2>, PM_PLAIN + 1> one_kernels[2] = {one_variants<false>(), one_variants<true>()}; // [packed form]
 
 bool launch_sellp_pipe(zzz_ctx* ctx, int grid, const ProductCall& c)
 {
@@ -525,9 +644,9 @@ bool launch_sellp_pipe(zzz_ctx* ctx, int grid, const ProductCall& c)
   a.nslices = (int)ctx->nslices;
   product_args_tail(a, c);
   const size_t lds = (size_t)((ctx->sp_dict_n + 1) & ~1) * sizeof(double);
-  hipLaunchKernelGGL(one_kernels[c.mode][c.load], dim3(grid), dim3(SP_BLOCK), lds, ctx->stream,
+  hipLaunchKernelGGL(one_kernels[ctx->sp_pal_on ? 1 : 0][c.mode][c.load], dim3(grid), dim3(SP_BLOCK), lds, ctx->stream,
                      reinterpret_cast<const int2*>(ctx->sp_desc.p), ctx->sp_smode.p, ctx->sp_pairs.p, ctx->sp_vals.p, ctx->sp_codes16.p,
-                     ctx->sp_meta.p, ctx->sp_vcode.p, ctx->sp_dset.dict.p, c.x, c.y, c.rvec, c.list, a);
+                     ctx->sp_meta.p, ctx->sp_vcode.p, ctx->sp_pal.p, ctx->sp_palok.p, ctx->sp_dset.dict.p, c.x, c.y, c.rvec, c.list, a);
   return true;
 }
 ZZZ_PRELOAD_TU(sellp_pipe)

@@ -662,13 +662,17 @@ class Context:
     def spmv_values_info(self):
         """how the operator stream holds its values: dict(form = 'doubles' | 'dictionary in memory' | 'dictionary in LDS',
         distinct values, bytes per product in that form, bytes per product as doubles)"""
-        info = (C.c_int64 * 10)()
-        self._ck(self.L.zzz_spmv_values_info2(self.h, 10, info))
+        info = (C.c_int64 * 14)()
+        self._ck(self.L.zzz_spmv_values_info2(self.h, 14, info))
         return dict(form=("doubles", "dictionary in memory", "dictionary in LDS", "slice dictionaries")[int(info[0])], distinct_values=int(info[1]),
                     bytes_per_product=int(info[2]), bytes_per_product_as_doubles=int(info[3]),
                     one_chunk_kernel=bool(info[4]), workgroups_per_cu=int(info[5]), block_rows=int(info[6]) == 1, row_windows=int(info[6]) == 2,
                     special_form=("", "block rows", "block windows")[int(info[6])],
-                    block_table_entries=int(info[7]), block_chunks=int(info[8]), block_form=int(info[9]))
+                    block_table_entries=int(info[7]), block_chunks=int(info[8]), block_form=int(info[9]),
+                    # the one-chunk kernel's packed value codes (4-bit palette indices, ZZZ_SELLP_PAL): slices read in that form /
+                    # as 16-bit codes, pairs of one of either, the most distinct codes met in one slot of one slice
+                    packed_slices=int(info[10]), unpacked_slices=int(info[11]), mixed_pairs=int(info[12]),
+                    max_codes_per_slot=int(info[13]))
 
     def spmv_x_windows(self):
         """(LDS doubles per workgroup, bytes of x loaded into LDS per product) when the operator stream carries x windows,
