@@ -5,8 +5,8 @@ and cells are shuffled with a fixed seed, so that the library's internal orders 
 the vertex coordinates and leaves everything else alone (Dirichlet set, facets and coefficients are inputs).  Every case
 is a valid mesh: the maps are injective and no cell degenerates.
 
-reference(case) is the one mp pass per (case, order) that the matrix, vector, action and diagonal tests share
-(tests/_hp_ref.py), with the oracle's values on the same input next to it.
+reference(case) is the one mp pass per (case, order, problem) that the matrix, vector, action, diagonal and lifting tests
+share (tests/_hp_ref.py), with the oracle's values on the same input next to it.
 """
 import numpy as np
 
@@ -14,6 +14,9 @@ import _hp_ref as hp
 import zzz_oracle as zo
 
 BASE = {1: (6, 5, 5), 2: (4, 4, 5), 3: (3, 3, 4)}
+# elasticity costs nine times the mp work per pair of nodes: smaller P2 / P3 bases (88 911 and 164 574 nonzeros -- still dozens
+# of assembly tiles, a padded window block, interior vertices and both constrained faces)
+ELASTICITY_BASE = {1: (6, 5, 5), 2: (3, 3, 4), 3: (2, 2, 3)}
 SEED = 20240611
 
 
@@ -78,7 +81,16 @@ F32_P1_REFUSED = "graded_ends12"
 P2_CASES = ["aniso", "graded", "mirror", "shear50_a", "noise10"]
 P3_CASES = ["offset", "graded", "mirror", "shear50_a"]
 POISSON_CASES = [(n, 1) for n in P1_CASES] + [(n, 2) for n in P2_CASES] + [(n, 3) for n in P3_CASES]
-ELASTICITY_CASES = ["offset", "aniso", "mirror", "shear50_a", "noise10"]
+ELASTICITY_P1_ORACLE_CASES = ["offset", "aniso", "mirror", "shear50_a", "noise10"]  # (judged against the oracle alone)
+# elasticity against the 50-digit reference, per order (tests/test_gpu_hostile_elasticity.py)
+ELASTICITY_CASES = {1: ["identity", "offset", "aniso", "needle", "graded", "mirror", "noise10", "noise7", "rotated", "shear50_a",
+                        "shear50_b"],
+                    2: ["aniso", "graded", "mirror", "rotated", "shear50_a", "noise10"],
+                    3: ["offset", "graded", "rotated", "shear50_a"]}
+ELASTICITY_SOLVE_CASES = ("identity", "offset", "graded", "mirror", "noise10", "noise7", "rotated")
+# the lifting pass (Dirichlet values): (name, order) per problem
+LIFTING_CASES = {"poisson": [("offset", 1), ("aniso", 1), ("graded", 1), ("rotated", 1), ("shear50_a", 1), ("graded", 2), ("offset", 3)],
+                 "elasticity": [("aniso", 1), ("rotated", 1), ("shear50_a", 1), ("aniso", 2), ("graded", 3)]}
 SOLVE_CASES = ("identity", "offset", "graded", "mirror", "mirror_axes", "noise13", "noise10", "noise7", "rotated")
 # the kind of internal order the code fixes for a case (1: lattice, 0: the caller's, or 2 when the bins are asked for)
 KIND_LATTICE = ("identity", "offset", "aniso", "needle", "needle_line", "graded", "graded_corner", "graded_corner_16", "noise13")
@@ -97,7 +109,7 @@ def case(name, order, problem="poisson"):
     if key in _CASES:
         return _CASES[key]
     fmap, dims = MAPS[name] if name in MAPS else F32_MAPS[name]
-    dims = dims if (dims is not None and order == 1) else BASE[order]
+    dims = dims if (dims is not None and order == 1) else (ELASTICITY_BASE if problem == "elasticity" else BASE)[order]
     zo.set_num_threads(1)
     O = zo.Problem(problem, order, *dims)
     rng = np.random.default_rng(SEED + 97 * order)
@@ -142,26 +154,68 @@ def oracle(C):
 
 
 def reference(C):
-    """dict of the mp pass of a Poisson case: R, S (unconstrained), Rc, Sc (Dirichlet rows and columns applied), r, s
-    (b, constrained entries exactly zero), the oracle's unconstrained matrix ou and its figures against the reference"""
-    key = (C.name, C.order)
+    """dict of the mp pass of a case: R, S (unconstrained), Rc, Sc (Dirichlet rows and columns applied), r, s (b,
+    constrained entries exactly zero), r_unc, s_unc (b with nothing constrained), the oracle's unconstrained matrix ou and
+    vector ob_unc, and the oracle's figures against the reference"""
+    key = (C.name, C.order, C.problem)
     if key in hp.CACHE:
         return hp.CACHE[key]
-    assert C.problem == "poisson"
-    R, S = hp.matrix(C.order, C.x, C.cells, C.cell_dofs, C.rowptr, C.cols)
-    r, s = hp.vector(C.order, C.x, C.cells, C.cell_dofs, C.f, C.g, C.facets, C.n)
+    if C.problem == "poisson":
+        R, S = hp.matrix(C.order, C.x, C.cells, C.cell_dofs, C.rowptr, C.cols)
+        r, s = hp.vector(C.order, C.x, C.cells, C.cell_dofs, C.f, C.g, C.facets, C.n)
+    else:
+        R, S = hp.elasticity_matrix(C.order, C.x, C.cells, C.cell_dofs, C.rowptr, C.cols)
+        r, s = hp.elasticity_vector(C.order, C.x, C.cells, C.cell_dofs, C.f, C.n)
+    r_unc, s_unc = r.copy(), s.copy()
     bcb = C.bc.astype(bool)
     r[bcb] = 0.0
     s[bcb] = 0.0
     Rc, Sc = hp.dirichlet(R, S, C.rowptr, C.cols, C.bc)
     zo.set_num_threads(1)
     ou = zo.assemble_matrix(C.form, C.order, C.x, C.cells, C.cell_dofs, np.zeros_like(C.bc), C.rowptr, C.cols)
+    ob_unc = zo.assemble_vector(C.form, C.order, C.x, C.cells, C.cell_dofs, C.f, C.g, C.facets, np.zeros_like(C.bc))
     ov, ob = oracle(C)
-    ref = dict(R=R, S=S, Rc=Rc, Sc=Sc, r=r, s=s, ou=ou,
+    ref = dict(R=R, S=S, Rc=Rc, Sc=Sc, r=r, s=s, r_unc=r_unc, s_unc=s_unc, ou=ou, ob_unc=ob_unc,
                oracle_A_free=hp.metric(ou, R, S) / hp.U, oracle_A=hp.metric(ov, Rc, Sc) / hp.U,
-               oracle_b=hp.metric(ob, r, s) / hp.U)
+               oracle_b=hp.metric(ob, r, s) / hp.U, oracle_b_free=hp.metric(ob_unc, r_unc, s_unc) / hp.U)
+    for v in ref.values():
+        if isinstance(v, np.ndarray):
+            v.setflags(write=False)
     hp.CACHE[key] = ref
     return ref
+
+
+def lifted_reference(C, g):
+    """(r, s, the oracle's figure) of the vector with the Dirichlet values g lifted (g is read on the Dirichlet set alone):
+        free rows          r_i = r_unc_i - sum_(j in bc) R_ij g_j   (products and sums in long double, rounded once)
+                           s_i = s_unc_i + sum_(j in bc) S_ij |g_j|
+        constrained rows   r_i = g_i exactly, s_i = 0
+    and the oracle's unconstrained A and b lifted the same way in doubles"""
+    ref = reference(C)
+    bcb = C.bc.astype(bool)
+    gm = np.where(bcb, g, 0.0)  # (g may hold NaN off the Dirichlet set: never multiplied)
+    rows = C.rowptr[:-1]
+    assert np.all(np.diff(C.rowptr) > 0)
+    lift = np.add.reduceat(ref["R"].astype(np.longdouble) * gm[C.cols].astype(np.longdouble), rows)
+    r = (ref["r_unc"].astype(np.longdouble) - lift).astype(np.float64)
+    s = ref["s_unc"] + np.add.reduceat(ref["S"] * np.abs(gm[C.cols]), rows)
+    r[bcb] = g[bcb]
+    s[bcb] = 0.0
+    ro = ref["ob_unc"] - np.add.reduceat(ref["ou"] * gm[C.cols], rows)
+    ro[bcb] = g[bcb]
+    return r, s, hp.metric(ro, r, s) / hp.U
+
+
+def dof_coords(C):
+    """The coordinates of the block dofs of a mapped case: the affine image of the reference nodes in each MAPPED cell (what
+    a Pk space on the mapped mesh has), not the map applied to the base dof coordinates -- on a graded mesh the two differ"""
+    X = zo.ref_nodes(C.order)
+    xs = C.x[C.cells]  # [cell][vertex][a]
+    e = xs[:, 1:, :] - xs[:, :1, :]
+    pts = xs[:, :1, :] + np.einsum("ia,cab->cib", X, e)
+    out = np.zeros((C.nblock, 3))
+    out[C.cell_dofs] = pts
+    return out
 
 
 def action_reference(C, u):

@@ -1,4 +1,4 @@
-"""High-precision restatement of the Poisson forms on any tetrahedral mesh: TEST INFRASTRUCTURE ONLY.
+"""High-precision restatement of the Poisson and elasticity forms on any tetrahedral mesh: TEST INFRASTRUCTURE ONLY.
 
 Pure Python, numpy and mpmath at 50 digits.  The reference tensors are those of performance-test_amd/tools/
 gen_element_tables.py (exact monomial integration in mpmath); nothing of the oracle and nothing of the library is used.
@@ -14,6 +14,20 @@ Every value comes with a SCALE, the magnitude a computation of it in doubles has
 ||K||_F^2 = tr(K K^T) is invariant under rotations, and S_ij > 0 wherever a cell couples i and j: no entry escapes through
 an exact zero of a lattice, and a zero that is one only up to rounding (a rotated lattice) is judged against what its terms
 weigh.  metric() is the largest |value - reference| / scale; its unit in the tests is 2^-53.
+
+Elasticity (dofs 3 node + component, E = 1e6, nu = 0.3; mu and lambda are the exact values of the doubles that the code's
+own expressions give) from the same tables and the same geometry():
+
+    D^ij_cd = |det J| sum_(al,be) K[al][c] K[be][d] S^(al be)_ij                      ( = int d_c phi_i d_d phi_j )
+    A[(i,c),(j,d)] = mu (delta_cd tr D^ij + D^ij_dc) + lambda D^ij_cd
+    b[(i,c)]       = |det J| sum_j M_ij f[(j,c)]
+    scale of A     = sum_cells |det J| T_ij (mu delta_cd ||K||_F^2 + (mu + lambda) k_c k_d),    T_ij = sum_ab |S^ab_ij|
+    scale of b     = sum_cells |det J| sum_j |M_ij| |f[(j,c)]|
+
+with k_c the 2-norm of column c of K: the scale follows the COMPONENTS.  On a mesh stretched by 2^20 and 2^-20 the nine
+entries of one 3 x 3 block span 2^80, and the rotation-invariant ||K||_F^2 (mu (delta_cd + 1) + lambda) would judge every one
+of them against the largest -- the small couplings could then be wrong by any factor.  k_c > 0 on every valid cell, so no
+entry of a block has scale 0.
 """
 import importlib.util
 import os
@@ -28,7 +42,7 @@ FACE_V = [(1, 2, 3), (0, 2, 3), (0, 1, 3), (0, 1, 2)]
 PAIRS = [(0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2)]
 _GEN = None
 _TAB = {}
-CACHE = {}  # (case, order) -> whatever the tests keep of one mp pass
+CACHE = {}  # (case, order, problem) -> whatever the tests keep of one mp pass
 
 
 def _gen():
@@ -93,6 +107,103 @@ def element_matrix(order, xc):
     for (i, j), s in zip(t["upper"], t["sym"]):
         A[i][j] = A[j][i] = w[0] * s[0] + w[1] * s[1] + w[2] * s[2] + w[3] * s[3] + w[4] * s[4] + w[5] * s[5]
     return A, float(adet * fro) * t["T"]
+
+
+EL_E, EL_NU = 1.0e6, 0.3
+MU = mp.mpf(EL_E / (2.0 * (1.0 + EL_NU)))  # the doubles of the code's own expressions, taken exactly
+LAMBDA = mp.mpf(EL_E * EL_NU / ((1.0 + EL_NU) * (1.0 - 2.0 * EL_NU)))
+
+
+def _elasticity_pair(K, adet, Sab, i, j):
+    """D[c][d] = |det J| sum_(al,be) K[al][c] K[be][d] S^(al be)_ij of one pair of nodes, in mp"""
+    tmp = [[Sab[al][0][i][j] * K[0][d] + Sab[al][1][i][j] * K[1][d] + Sab[al][2][i][j] * K[2][d] for d in range(3)]
+           for al in range(3)]
+    return [[adet * (K[0][c] * tmp[0][d] + K[1][c] * tmp[1][d] + K[2][c] * tmp[2][d]) for d in range(3)] for c in range(3)]
+
+
+def _elasticity_block(D):
+    """the 3 x 3 block A[c][d] = mu (delta_cd tr D + D_dc) + lambda D_cd of one pair of nodes"""
+    tr = D[0][0] + D[1][1] + D[2][2]
+    return [[MU * ((tr if c == d else 0) + D[d][c]) + LAMBDA * D[c][d] for d in range(3)] for c in range(3)]
+
+
+def _elasticity_weight(K, adet, fro):
+    """w[c][d] = |det J| (mu delta_cd ||K||_F^2 + (mu + lambda) k_c k_d) as floats: the scale of a block is T_ij w"""
+    k = [mp.sqrt(K[0][c] * K[0][c] + K[1][c] * K[1][c] + K[2][c] * K[2][c]) for c in range(3)]
+    return np.array([[float(adet * ((MU * fro if c == d else 0) + (MU + LAMBDA) * k[c] * k[d])) for d in range(3)]
+                     for c in range(3)])
+
+
+def elasticity_element_matrix(order, xc):
+    """(Ae, scale) of one cell, 3 nd x 3 nd (dof 3 i + c): lists of mp numbers / a float array"""
+    t = tables(order)
+    nd = t["nd"]
+    adet, K, _, fro = geometry(xc)
+    A = [[None] * (3 * nd) for _ in range(3 * nd)]
+    for i in range(nd):
+        for j in range(nd):
+            B = _elasticity_block(_elasticity_pair(K, adet, t["S"], i, j))
+            for c in range(3):
+                for d in range(3):
+                    A[3 * i + c][3 * j + d] = B[c][d]
+    return A, np.kron(t["T"], _elasticity_weight(K, adet, fro))
+
+
+def elasticity_element_vector(order, xc, fc):
+    """(be, scale) of one cell for the coefficient fc[3 j + c] at its nodes"""
+    t = tables(order)
+    nd = t["nd"]
+    adet = geometry(xc)[0]
+    fm = [mp.mpf(float(v)) for v in fc]
+    b = [adet * mp.fdot(t["M"][i], fm[c::3]) for i in range(nd) for c in range(3)]
+    s = float(adet) * (t["Mabs"] @ np.abs(np.asarray(fc, np.float64).reshape(nd, 3))).reshape(-1)
+    return b, s
+
+
+def elasticity_matrix(order, x, cells, cell_dofs, rowptr, cols):
+    """(R, S) on the scalar pattern (rowptr, cols) of block size 3: the unconstrained elasticity matrix rounded once, and
+    its scale.  A[(j,d),(i,c)] = A[(i,c),(j,d)] (S^ab_ij = S^ba_ji): the pairs i <= j are enough."""
+    t = tables(order)
+    Sab, T, nd = t["S"], t["T"], t["nd"]
+    pos = _positions(rowptr, cols)
+    acc = [mp.mpf(0)] * len(cols)
+    S = np.zeros(len(cols))
+    for cell in range(cells.shape[0]):
+        adet, K, _, fro = geometry(x[cells[cell]])
+        w = _elasticity_weight(K, adet, fro)
+        dofs = [int(v) for v in cell_dofs[cell]]
+        for i in range(nd):
+            for j in range(i, nd):
+                B = _elasticity_block(_elasticity_pair(K, adet, Sab, i, j))
+                for c in range(3):
+                    pr = pos[3 * dofs[i] + c]
+                    for d in range(3):
+                        acc[pr[3 * dofs[j] + d]] += B[c][d]
+                        S[pr[3 * dofs[j] + d]] += T[i, j] * w[c, d]
+                        if i != j:
+                            q = pos[3 * dofs[j] + d][3 * dofs[i] + c]
+                            acc[q] += B[c][d]
+                            S[q] += T[i, j] * w[c, d]
+    return np.array([float(v) for v in acc]), S
+
+
+def elasticity_vector(order, x, cells, cell_dofs, f, n):
+    """(r, s) of b[(i,c)] = sum_cells |det J| sum_j M_ij f[(j,c)], unconstrained"""
+    t = tables(order)
+    nd, M, Mabs = t["nd"], t["M"], t["Mabs"]
+    acc = [mp.mpf(0)] * n
+    s = np.zeros(n)
+    fm = [mp.mpf(float(v)) for v in f]
+    fa = np.abs(np.asarray(f, np.float64)).reshape(-1, 3)
+    for cell in range(cells.shape[0]):
+        adet = geometry(x[cells[cell]])[0]
+        dofs = [int(v) for v in cell_dofs[cell]]
+        for c in range(3):
+            fc = [fm[3 * k + c] for k in dofs]
+            for i in range(nd):
+                acc[3 * dofs[i] + c] += adet * mp.fdot(M[i], fc)
+        s.reshape(-1, 3)[dofs] += float(adet) * (Mabs @ fa[dofs])  # (the dofs of one cell are distinct)
+    return np.array([float(v) for v in acc]), s
 
 
 def facet_scale(xc, lf):

@@ -67,7 +67,7 @@ from _gpu_helpers import *  # noqa: F401,F403 -- helpers, np / os / zzz / zo / p
 import _f32_ref as fr
 import _hostile as H
 import _hp_ref as hp  # noqa: F401 -- (H.action_reference keeps its passes in hp.CACHE, shared with the double file)
-from test_gpu_hostile_geometry import MF_SMALL, _env, _upload
+from _hostile_gpu import MF_SMALL, _env, _upload
 
 pytestmark = pytest.mark.gpu  # noqa: F405
 

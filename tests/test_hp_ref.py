@@ -12,6 +12,21 @@ with the scale of _hp_ref.py.  Measured when the reference was written (P1 6x5x5
 The oracle sits within a few units of the truth and loses digits only where cond(J) grows.  Each figure must stay within
 twice the measured one (for the P1 group: twice the group's worst, 1.8): a change of the oracle that loses digits fails
 here, on the CPU, before any kernel is judged against it.
+
+Elasticity, with the component-aware scale of _hp_ref.py, for the unconstrained matrix (the unconstrained vector in brackets;
+P1 6x5x5 -- shear50_b 6x9x5 --, P2 3x3x4, P3 2x2x3 cubes; one thread):
+
+    P1   identity 1.55 (4.52)   offset 2.20 (4.80)   aniso 2.34 (4.52)   needle 2.00 (4.52)   graded 2.93 (5.09)
+         mirror 1.55 (4.77)   noise10 2.17 (4.57)   noise7 2.93 (4.69)   rotated 2.33 (3.96)
+         shear50_a 26.15 (38.71)   shear50_b 22.83 (30.06)
+    P2   aniso 3.61 (5.09)   graded 3.66 (4.75)   mirror 3.25 (4.28)   rotated 3.46 (4.28)   noise10 3.80 (4.15)
+         shear50_a 25.91 (34.98)
+    P3   offset 5.46 (9.52)   graded 6.37 (7.74)   rotated 5.48 (11.66)   shear50_a 33.70 (65.45)
+
+Every scale of every case is > 0 (the smallest, on aniso, is 8.8e-20 of max|A| at P1 and 1.0e-20 at P2) and no figure comes
+near 100, beyond which the GPU bar of 8 x the oracle's figure would mean nothing.  A handful are pinned below at twice the
+measured figure; tests/test_gpu_hostile_elasticity.py takes every case.  (A rotated cube stretched by 2^10 and 2^-10 gives
+4.6e7: a property of cond(J), not of any code, and not a case.)
 """
 import os
 
@@ -132,6 +147,104 @@ def test_assembled_reference_is_the_sum_of_its_cells():
 ORACLE_FIGURES = [("identity", 1, 1.8), ("offset", 1, 1.8), ("aniso", 1, 1.8), ("graded", 1, 1.8), ("rotated", 1, 1.8),
                   ("needle", 1, 1.8), ("noise13", 1, 1.8), ("aniso", 2, 2.2), ("graded", 3, 5.9),
                   ("shear50_a", 1, 23.6), ("shear50_a", 2, 26.3), ("shear50_a", 3, 24.9)]
+
+
+@pytest.mark.parametrize("order", [1, 2, 3])
+def test_elasticity_element_against_the_oracle(order):
+    """Elasticity matrix and load of one cell (dofs 3 i + c) at the bar of the Poisson element test, every entry against its
+    own component-aware scale; no entry of the full 3 nd x 3 nd block has scale 0"""
+    nd = hp.tables(order)["nd"]
+    rng = np.random.default_rng(200 + order)
+    for xc in _tets(order):
+        A, sc = hp.elasticity_element_matrix(order, xc)
+        A = np.array([[float(v) for v in row] for row in A])
+        assert np.all(sc > 0) and np.array_equal(A, A.T)
+        assert hp.metric(zo.tabulate("elasticity_a", order, xc), A, sc) <= 64 * hp.U
+        f = rng.standard_normal(3 * nd)
+        b, s = hp.elasticity_element_vector(order, xc, f)
+        assert np.all(s > 0)
+        assert hp.metric(zo.tabulate("elasticity_L", order, xc, w=f), np.array([float(v) for v in b]), s) <= 64 * hp.U
+
+
+def test_assembled_elasticity_reference_is_the_sum_of_its_cells():
+    """elasticity_matrix() and elasticity_vector() on a mesh of a few cells against the dense sums of their cells"""
+    C = _hostile.case("rotated", 2, "elasticity")
+    cells, cd = C.cells[:6], C.cell_dofs[:6]
+    n = C.n
+    D = [[hp.mp.mpf(0)] * n for _ in range(n)]
+    Ds = np.zeros((n, n))
+    db, dbs = [hp.mp.mpf(0)] * n, np.zeros(n)
+    for c in range(6):
+        sd = (3 * cd[c][:, None] + np.arange(3)).reshape(-1)
+        A, sc = hp.elasticity_element_matrix(2, C.x[cells[c]])
+        be, bs = hp.elasticity_element_vector(2, C.x[cells[c]], C.f[sd])
+        for i in range(30):
+            db[sd[i]] += be[i]
+            dbs[sd[i]] += bs[i]
+            for j in range(30):
+                D[sd[i]][sd[j]] += A[i][j]
+                Ds[sd[i], sd[j]] += sc[i, j]
+    rp, cl = zo.pattern(C.nblock, cd, 3)
+    R, S = hp.elasticity_matrix(2, C.x, cells, cd, rp, cl)
+    rows = np.repeat(np.arange(n), np.diff(rp))
+    assert len(cl) == np.count_nonzero(Ds)
+    np.testing.assert_array_equal(R, np.array([float(D[i][j]) for i, j in zip(rows, cl)]))
+    np.testing.assert_allclose(S, Ds[rows, cl], rtol=1e-14, atol=0)
+    assert np.all(S > 0)
+    r, s = hp.elasticity_vector(2, C.x, cells, cd, C.f, n)
+    np.testing.assert_array_equal(r, np.array([float(v) for v in db]))
+    np.testing.assert_allclose(s, dbs, rtol=1e-14, atol=0)
+
+
+def test_dof_coordinates_of_a_mapped_case():
+    """_hostile.dof_coords: on the unmapped cube it gives the oracle's dof coordinates, on a graded mesh the vertices sit at
+    the mapped vertices and the other dofs do NOT sit at the map of their base coordinates"""
+    for order in (2, 3):
+        C = _hostile.case("identity", order, "elasticity")
+        assert np.abs(_hostile.dof_coords(C) - C.dof_x_base).max() <= 4 * hp.U
+        C = _hostile.case("graded", order, "elasticity")
+        X = _hostile.dof_coords(C)
+        np.testing.assert_array_equal(X[C.cell_dofs[:, :4]], C.x[C.cells])
+        edge = np.setdiff1d(C.cell_dofs[:, 4:], C.cell_dofs[:, :4])
+        assert np.abs(X[edge] - C.dof_x_base[edge] ** 3).max() > 1e-3
+
+
+def test_elasticity_reference_annihilates_the_rigid_body_modes():
+    """A pin that owes nothing to the oracle: the unconstrained reference matrix of `rotated` P2 applied to the three
+    translations and the three rotations of the mapped dof coordinates.  Exactly, every row sums to zero against them; here
+    the entries are rounded once (half a unit of their scale each: 0.5 of t) and the rotations carry the rounding of the dof
+    coordinates (the affine image of a P2 node: a difference and a sum rounded, the product by 1/2 exact -- one unit of the
+    coordinates, so 1 of t = sum_j S_ij |u_j|).  That is 1.5 units of apply()'s t at the worst; the bar is 2, and 0.05 to
+    0.10 was measured.  A reference that lost a few digits in its own assembly, or swapped D_cd and D_dc, misses it."""
+    C = _hostile.case("rotated", 2, "elasticity")
+    ref = _hostile.reference(C)
+    X = _hostile.dof_coords(C)
+    one, zero = np.ones(C.nblock), np.zeros(C.nblock)
+    modes = [(one, zero, zero), (zero, one, zero), (zero, zero, one),
+             (-X[:, 1], X[:, 0], zero), (zero, -X[:, 2], X[:, 1]), (X[:, 2], zero, -X[:, 0])]
+    for k, m in enumerate(modes):
+        u = np.stack(m, axis=1).reshape(-1)
+        y, t = hp.apply(ref["R"], ref["S"], C.rowptr, C.cols, u)
+        fig = float((np.abs(y) / t).max()) / hp.U
+        print(f"rigid-body mode {k}: |R u| / t = {fig:.2f} x 2^-53, |R u| / (|R| |u|) = {np.abs(y).max() / np.abs(ref['R']).max() / np.abs(u).max():.2e}")
+        assert np.all(t > 0) and fig <= 2.0
+
+
+ELASTICITY_ORACLE_FIGURES = [("identity", 1, 1.55), ("aniso", 1, 2.34), ("shear50_a", 1, 26.2), ("aniso", 2, 3.61),
+                             ("rotated", 2, 3.46), ("offset", 3, 5.46)]
+
+
+@pytest.mark.parametrize("name,order,measured", ELASTICITY_ORACLE_FIGURES, ids=[f"{n}-P{o}" for n, o, _ in ELASTICITY_ORACLE_FIGURES])
+def test_oracle_figures_of_elasticity_on_the_hostile_meshes(name, order, measured):
+    C = _hostile.case(name, order, "elasticity")
+    assert C.dims == _hostile.ELASTICITY_BASE[order]
+    ref = _hostile.reference(C)
+    fig = ref["oracle_A_free"]
+    print(f"oracle against the 50-digit reference, elasticity {name} P{order}: A {fig:.2f} x 2^-53 (measured {measured}),"
+          f" b {ref['oracle_b_free']:.2f}")
+    assert np.all(ref["S"] > 0) and np.all(ref["s_unc"] > 0)
+    assert fig <= 2 * measured
+    assert fig <= 100 and ref["oracle_b_free"] <= 100  # beyond that the GPU bar (8 x the oracle's figure) means nothing
 
 
 @pytest.mark.parametrize("name,order,measured", ORACLE_FIGURES, ids=[f"{n}-P{o}" for n, o, _ in ORACLE_FIGURES])
