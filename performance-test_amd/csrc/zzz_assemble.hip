@@ -16,226 +16,19 @@
 #include <algorithm>
 #include <climits>
 #include <cstring>
+#include <type_traits>
 
-#include "zzz_device.h"
-#include "zzz_internal.h"
+#include "zzz_asm_elem.h"
 
 #include <rocprim/rocprim.hpp>
 
 namespace zzz
 {
-constexpr int ASM_BLOCK = 256;
 constexpr int ASM_NNZ = 4096; // LDS: 32 KiB values + 16 KiB columns per workgroup ...
 constexpr int ASM_NNZ_P1 = 1920;    // scalar P1: ~126 rows per tile for a 128-thread workgroup (one thread per row)
 constexpr int ASM_NNZ_SMALL = 2048; // ... or half of that for scalar P1/P2 (short rows): twice the workgroups per CU
                                     // (measured: Poisson P1 6.6 -> 5.6 ms, P2 6.4 -> 4.5 ms; elasticity and P3 lose)
-constexpr int ASM_ORD_CAP = 512; // block dofs of a tile that the high-order kernel sorts by cell count
 constexpr int ASM_RP_CAP = 255;  // scalar rows of a tile whose offsets the position-based kernel keeps in LDS
-
-struct Geom
-{
-  double adet;    // |det J|
-  double K[3][3]; // J^-1: K[al][a] = dX_al/dx_a
-};
-
-__device__ inline void load_cell(const double* __restrict__ x, const int4 v, double p[4][3])
-{
-  const int vv[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-  {
-    const double* q = x + 3 * (int64_t)vv[k];
-    p[k][0] = q[0];
-    p[k][1] = q[1];
-    p[k][2] = q[2];
-  }
-}
-
-// P1 through the dof-addressed coordinates (zzz_ctx::xq): dd = the cell's four block dofs
-__device__ inline void load_cell_q(const double* __restrict__ xq, const int4 dd, double p[4][3]) { load_cell(xq, dd, p); }
-// the same for a row that knows its own vertex (local index li, coordinates own[]): three gathers instead of four.  The
-// loads are predicated per lane; where the lanes of a wavefront agree on li (structured feeds) the fourth is not issued.
-__device__ inline void load_cell_q3(const double* __restrict__ xq, const int4 dd, int li, const double own[3], double p[4][3])
-{
-  const int vv[4] = {dd.x, dd.y, dd.z, dd.w};
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-  {
-    if (k != li)
-    {
-      const double* q = xq + 3 * (int64_t)vv[k];
-      p[k][0] = q[0];
-      p[k][1] = q[1];
-      p[k][2] = q[2];
-    }
-    else
-    {
-      p[k][0] = own[0];
-      p[k][1] = own[1];
-      p[k][2] = own[2];
-    }
-  }
-}
-
-__device__ inline void geometry(const double p[4][3], Geom& G)
-{
-  double J[3][3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a)
-#pragma unroll
-    for (int al = 0; al < 3; ++al)
-      J[a][al] = p[al + 1][a] - p[0][a];
-  const double c00 = J[1][1] * J[2][2] - J[1][2] * J[2][1];
-  const double c01 = J[1][0] * J[2][2] - J[1][2] * J[2][0];
-  const double c02 = J[1][0] * J[2][1] - J[1][1] * J[2][0];
-  const double det = J[0][0] * c00 - J[0][1] * c01 + J[0][2] * c02;
-  const double id = 1.0 / det;
-  G.adet = fabs(det);
-  G.K[0][0] = c00 * id;
-  G.K[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) * id;
-  G.K[0][2] = (J[0][1] * J[1][2] - J[0][2] * J[1][1]) * id;
-  G.K[1][0] = -c01 * id;
-  G.K[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) * id;
-  G.K[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) * id;
-  G.K[2][0] = c02 * id;
-  G.K[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) * id;
-  G.K[2][2] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) * id;
-}
-
-// physical gradients of the four P1 hat functions: g[i][a] = sum_al K[al][a] * dphi_i/dX_al
-__device__ inline void p1_grads(const Geom& G, double g[4][3])
-{
-#pragma unroll
-  for (int a = 0; a < 3; ++a)
-  {
-    g[1][a] = G.K[0][a];
-    g[2][a] = G.K[1][a];
-    g[3][a] = G.K[2][a];
-    g[0][a] = -(G.K[0][a] + G.K[1][a] + G.K[2][a]);
-  }
-}
-
-__device__ inline double sel3(double a0, double a1, double a2, int c) { return c == 0 ? a0 : (c == 1 ? a1 : a2); }
-
-// ---- entries of the element matrices of form a, shared by the matrix kernels and the lifting pass (k_lift), so that
-// the two cannot drift apart.  Every helper is the expression the matrix kernels held inline: same operations, same order.
-constexpr double EL_E = 1.0e6, EL_NU = 0.3; // src/Elasticity.py:12-15
-constexpr double EL_MU = EL_E / (2.0 * (1.0 + EL_NU));
-constexpr double EL_LAMBDA = EL_E * EL_NU / ((1.0 + EL_NU) * (1.0 - 2.0 * EL_NU));
-
-// P1 elasticity, entry (row node i, component c; column node j, component d) of a cell of reference volume weight w:
-// mu (delta_cd g_i.g_j + d_d phi_i d_c phi_j) + lambda d_c phi_i d_d phi_j, with gg = g_i.g_j, gid = d_d phi_i,
-// gjc = d_c phi_j, gic = d_c phi_i, gjd = d_d phi_j
-__device__ inline double p1_elasticity_entry(double w, double gg, bool c_is_d, double gid, double gjc, double gic, double gjd)
-{
-  return w * (EL_MU * ((c_is_d ? gg : 0.0) + gid * gjc) + EL_LAMBDA * gic * gjd);
-}
-
-// Pk Poisson: |detJ| (K K^T) (six numbers: 00 11 22 01 02 12) contracted with the symmetrised reference tensors of the
-// pair (li, j); Tlj points at piece 0 of the pair, the pieces are NN apart
-template <int NN>
-__device__ inline double pk_poisson_entry(const double* GG, const double* Tlj)
-{
-  double val = 0.0;
-#pragma unroll
-  for (int t = 0; t < 6; ++t)
-    val += GG[t] * Tlj[t * NN];
-  return val;
-}
-
-// Pk elasticity: D[cc][d] = |detJ| sum_{al,be} K[al][cc] K[be][d] S^[al][be]_{li,j} = int d_cc phi_i d_d phi_j
-// (Kf: K[al][d] at Kf[3 al + d]; Tlj points at piece (0, 0) of the pair (li, j), the nine pieces are NN apart)
-template <int NN>
-__device__ inline void pk_grad_products(double adet, const double* Kf, const double* Tlj, double (&D)[3][3])
-{
-  double tmp[3][3];
-#pragma unroll
-  for (int al = 0; al < 3; ++al)
-#pragma unroll
-    for (int d = 0; d < 3; ++d)
-      tmp[al][d] = Tlj[(al * 3 + 0) * NN] * Kf[0 + d] + Tlj[(al * 3 + 1) * NN] * Kf[3 + d] + Tlj[(al * 3 + 2) * NN] * Kf[6 + d];
-#pragma unroll
-  for (int cc = 0; cc < 3; ++cc)
-#pragma unroll
-    for (int d = 0; d < 3; ++d)
-      D[cc][d] = adet * (Kf[0 + cc] * tmp[0][d] + Kf[3 + cc] * tmp[1][d] + Kf[6 + cc] * tmp[2][d]);
-}
-// ... and the entry (component c of the row, d of the column) of the pair from D and its trace
-__device__ inline double pk_elasticity_entry(const double (&D)[3][3], double tr, int c, int d)
-{
-  const double Dcd = sel3(D[0][d], D[1][d], D[2][d], c), Ddc = sel3(D[d][0], D[d][1], D[d][2], c);
-  return EL_MU * ((c == d ? tr : 0.0) + Ddc) + EL_LAMBDA * Dcd;
-}
-// |detJ| (K K^T): 00 11 22 01 02 12
-__device__ inline void pk_poisson_geom(const Geom& G, double (&GG)[6])
-{
-  GG[0] = G.adet * (G.K[0][0] * G.K[0][0] + G.K[0][1] * G.K[0][1] + G.K[0][2] * G.K[0][2]);
-  GG[1] = G.adet * (G.K[1][0] * G.K[1][0] + G.K[1][1] * G.K[1][1] + G.K[1][2] * G.K[1][2]);
-  GG[2] = G.adet * (G.K[2][0] * G.K[2][0] + G.K[2][1] * G.K[2][1] + G.K[2][2] * G.K[2][2]);
-  GG[3] = G.adet * (G.K[0][0] * G.K[1][0] + G.K[0][1] * G.K[1][1] + G.K[0][2] * G.K[1][2]);
-  GG[4] = G.adet * (G.K[0][0] * G.K[2][0] + G.K[0][1] * G.K[2][1] + G.K[0][2] * G.K[2][2]);
-  GG[5] = G.adet * (G.K[1][0] * G.K[2][0] + G.K[1][1] * G.K[2][1] + G.K[1][2] * G.K[2][2]);
-}
-
-__device__ inline int find_pos(const int32_t* __restrict__ c, int len, int32_t col)
-{
-  int lo = 0, hi = len - 1;
-  while (lo < hi)
-  {
-    const int mid = (lo + hi) >> 1;
-    if (c[mid] < col)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
-  return lo;
-}
-
-// The positions of four columns in a row's sorted columns c[0 .. len): four lower-bound searches side by side, without
-// branches -- pos = number of entries below the column, found bit by bit from the top.  (One after the other, as loops
-// around find_pos, the four searches of a P1 cell were twenty dependent LDS round trips per (row, cell) pair, half of
-// asm_matrix_p1's time; side by side they are five.)
-__device__ inline void find_pos4(const int32_t* __restrict__ c, int len, const int (&col)[4], int (&pos)[4])
-{
-  // byte offsets from c: q = 4 pos; an entry is read at q + 4 step - 4 whether or not it lies in the row (the arrays this is
-  // called on are 32 entries longer than the rows they hold) and counts only if it does
-  const char* __restrict__ cb = reinterpret_cast<const char*>(c);
-  const int end = 4 * len;
-  int q[4] = {0, 0, 0, 0};
-  int top = 16;
-  while (top * 2 <= len) // (not taken on a P1 lattice: 27 columns at most)
-    top *= 2;
-  for (; top > 16; top >>= 1)
-  {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-    {
-      const int t = q[j] + 4 * top;
-      const int v = t <= end ? *reinterpret_cast<const int32_t*>(cb + t - 4) : INT_MAX;
-      q[j] = v < col[j] ? t : q[j];
-    }
-  }
-  const bool short_rows = __all(len < 16); // (a P1 lattice of Kuhn simplices: 15 columns per row)
-#pragma unroll
-  for (int step = 64; step >= 4; step >>= 1) // 16 entries, 8, ... 1
-  {
-    if (step == 64 && short_rows)
-      continue;
-    int v[4], t[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-    {
-      t[j] = q[j] + step;
-      v[j] = *reinterpret_cast<const int32_t*>(cb + q[j] + (step - 4));
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      q[j] = ((int)(t[j] <= end) & (int)(v[j] < col[j])) ? t[j] : q[j];
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    pos[j] = q[j] >> 2;
-}
 
 // Adjacency transposed in slices of 64 rows: entry a of row (64 s + lane) sits at off[s] + 64 a + lane
 // (cell index, -1 = padding) with the dof's local index in that cell beside it.  A wavefront owns a
@@ -286,24 +79,6 @@ __global__ __launch_bounds__(256) void k_adjT_fill(const int32_t* __restrict__ a
   }
 }
 
-// iteration over the cells of block dof i through the transposed adjacency
-struct AdjIter
-{
-  const int32_t* cp;
-  const uint8_t* lp;
-  int len;
-  __device__ AdjIter(const int32_t* __restrict__ off, const int32_t* __restrict__ cellT, const uint8_t* __restrict__ liT, int i)
-  {
-    const int sl = i >> 6, ln = i & 63;
-    const int o = off[sl];
-    len = (off[sl + 1] - o) >> 6;
-    cp = cellT + o + ln;
-    lp = liT + o + ln;
-  }
-  __device__ int cell(int a) const { return cp[a * 64]; } // -1 once the list of this row is exhausted
-  __device__ int li(int a) const { return lp[a * 64]; }
-};
-
 // ---- matrix, P1, BS = 1 (Poisson a1, src/Poisson.py:31) or 3 (Elasticity a1, src/Elasticity.py:39)
 template <int BS, int NNZ, int BLK>
 __global__ __launch_bounds__(BLK) void asm_matrix_p1(const double* __restrict__ xq,
@@ -325,10 +100,9 @@ __global__ __launch_bounds__(BLK) void asm_matrix_p1(const double* __restrict__ 
   const int64_t tile = xcd_item(ntiles);
   if (tile < 0)
     return;
-  const int d0 = tiles[tile], d1 = tiles[tile + 1];
-  const int row0 = d0 * BS, row1 = d1 * BS;
-  const int64_t s = rowptr[row0];
-  const int e = (int)(rowptr[row1] - s); // entries of the tile's CSR segment (fits LDS)
+  const TileSpan ts = tile_span<BS>(tiles, rowptr, tile);
+  const int row0 = ts.row0, row1 = ts.row1, e = ts.e;
+  const int64_t s = ts.s;
   for (int k = threadIdx.x; k < e; k += BLK)
   {
     cols_s[k] = cols[s + k];
@@ -341,58 +115,8 @@ __global__ __launch_bounds__(BLK) void asm_matrix_p1(const double* __restrict__ 
     const int a0 = (int)(rowptr[r] - s), len = (int)(rowptr[r + 1] - rowptr[r]);
     const bool bcr = bc[r] != 0;
     const AdjIter adj(adjT_off, adjT_cells, adj_li, i);
-    // Three-stage software pipeline over the row's cells.  A cell needs a chain of three dependent loads (adjacency
-    // -> connectivity -> coordinates and BC flags); each link is issued one iteration ahead of the next: while cell a
-    // is evaluated the coordinates of a+1, the connectivity of a+2 and the adjacency entry a+3 are in flight, so an
-    // iteration waits for one memory round trip, not three (the workgroup's CSR segment in LDS leaves 3-4 wavefronts
-    // per SIMD: occupancy alone does not hide the chain).
-    // (profiles/r05_pmc_asm_c2.json, 10 M dofs: 296 VALU + 44 SALU + 26 LDS + 17 VMEM instructions per (row, cell) pair,
-    // VALU busy 78 % of the kernel's cycles, L2 hit rate 80 %: the kernel is bound by the instructions it issues -- with
-    // every gather, the search and the geometry removed (a timing probe, since removed from the code) it still takes 1.55 of its
-    // 2.65 ms: three wavefronts per SIMD, 24 dependent round trips per row.)
-    // The walk has no branches: every lane runs the slice's `alen` iterations (the transposed adjacency pads shorter
-    // rows with -1), a padding entry loads and evaluates cell 0 and only its update of the row is masked; the
-    // coordinate stages alternate between two register sets (DA, DB: no copies of 25 registers per cell).
-    struct Conn
-    {
-      int cell, li;
-      int4 dd;
-    };
-    struct Data
-    {
-      double p[4][3];
-      uint8_t bcj[4 * BS];
-    };
-    const int alen = adj.len;
-    auto adj_at = [&](int a, int& cell, int& li) {
-      const int ac = min(a, alen - 1);
-      const int cc = adj.cell(ac);
-      cell = a < alen ? cc : -1;
-      li = adj.li(ac);
-    };
-    auto conn_at = [&](int cell, int li, Conn& K) {
-      K.cell = cell;
-      K.li = li;
-      K.dd = *reinterpret_cast<const int4*>(cell_dofs + 4 * (int64_t)max(cell, 0));
-    };
-    auto data_at = [&](const Conn& K, Data& D) {
-      load_cell_q(xq, K.dd, D.p); // (skipping the row's own vertex, as asm_vector_p1 does, made this kernel 3 % slower)
-      const int dj[4] = {K.dd.x, K.dd.y, K.dd.z, K.dd.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int d = 0; d < BS; ++d)
-          D.bcj[j * BS + d] = bc[dj[j] * BS + d];
-    };
-    Conn K0, K1;
-    Data DA, DB;
-    int c2, l2;
-    auto iter = [&](int a, const Data& D0, Data& D1) {
-      Conn K2;
-      int c3, l3;
-      data_at(K1, D1);
-      conn_at(c2, l2, K2);
-      adj_at(a + 3, c3, l3);
+    // the three-stage pipeline over the row's cells (p1_walk_cells); a padding entry (K0.cell < 0) is evaluated, not added
+    p1_walk_cells<BS>(adj, xq, cell_dofs, bc, [&](const P1Conn& K0, const P1Data<BS>& D0) {
       const int li = K0.li;
       const int dofs[4] = {K0.dd.x, K0.dd.y, K0.dd.z, K0.dd.w};
       double g[4][3];
@@ -447,31 +171,7 @@ __global__ __launch_bounds__(BLK) void asm_matrix_p1(const double* __restrict__ 
           for (int d = 0; d < BS; ++d)
             vals_s[a0 + pos4[j] + d] = acc[j][d] + val[j][d];
       }
-      K0 = K1;
-      K1 = K2;
-      c2 = c3;
-      l2 = l3;
-    };
-    if (alen > 0)
-    {
-      {
-        int ca, la;
-        adj_at(0, ca, la);
-        conn_at(ca, la, K0);
-        data_at(K0, DA);
-        adj_at(1, ca, la);
-        conn_at(ca, la, K1);
-        adj_at(2, c2, l2);
-      }
-      int a = 0;
-      for (; a + 1 < alen; a += 2)
-      {
-        iter(a, DA, DB);
-        iter(a + 1, DB, DA);
-      }
-      if (a < alen)
-        iter(a, DA, DB);
-    }
+    });
     if (bcr) // fem::set_diagonal: 1.0 on constrained rows
       vals_s[a0 + find_pos(cols_s + a0, len, r)] = 1.0;
   }
@@ -503,9 +203,9 @@ __global__ __launch_bounds__(64) void asm_matrix_p1_node3(const double* __restri
   const int64_t tile = xcd_item(ntiles);
   if (tile < 0)
     return;
-  const int d0 = tiles[tile], d1 = tiles[tile + 1];
-  const int64_t s = rowptr[(int64_t)d0 * BS];
-  const int e = (int)(rowptr[(int64_t)d1 * BS] - s); // entries of the tile's CSR segment (fits LDS)
+  const TileSpan ts = tile_span<BS>(tiles, rowptr, tile);
+  const int d0 = ts.d0, d1 = ts.d1, e = ts.e;
+  const int64_t s = ts.s;
   for (int k = threadIdx.x; k < e; k += BLK)
     vals_s[k] = 0.0;
   // block columns: entry q of the tile's block rows = column / 3 of the first scalar row's entry 3 q'
@@ -528,46 +228,8 @@ __global__ __launch_bounds__(64) void asm_matrix_p1_node3(const double* __restri
     for (int c = 0; c < BS; ++c)
       bcr[c] = bc[(int64_t)i * BS + c] != 0;
     const AdjIter adj(adjT_off, adjT_cells, adj_li, i);
-    struct Conn
-    {
-      int cell, li;
-      int4 dd;
-    };
-    struct Data
-    {
-      double p[4][3];
-      uint8_t bcj[4 * BS];
-    };
-    const int alen = adj.len;
-    auto adj_at = [&](int a, int& cell, int& li) {
-      const int ac = min(a, alen - 1);
-      const int cc = adj.cell(ac);
-      cell = a < alen ? cc : -1;
-      li = adj.li(ac);
-    };
-    auto conn_at = [&](int cell, int li, Conn& K) {
-      K.cell = cell;
-      K.li = li;
-      K.dd = *reinterpret_cast<const int4*>(cell_dofs + 4 * (int64_t)max(cell, 0));
-    };
-    auto data_at = [&](const Conn& K, Data& D) {
-      load_cell_q(xq, K.dd, D.p);
-      const int dj[4] = {K.dd.x, K.dd.y, K.dd.z, K.dd.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int d = 0; d < BS; ++d)
-          D.bcj[j * BS + d] = bc[dj[j] * BS + d];
-    };
-    Conn K0, K1;
-    Data DA, DB;
-    int c2, l2;
-    auto iter = [&](int a, const Data& D0, Data& D1) {
-      Conn K2;
-      int c3, l3;
-      data_at(K1, D1);
-      conn_at(c2, l2, K2);
-      adj_at(a + 3, c3, l3);
+    // the three-stage pipeline over the node's cells (p1_walk_cells); a padding entry (K0.cell < 0) is evaluated, not added
+    p1_walk_cells<BS>(adj, xq, cell_dofs, bc, [&](const P1Conn& K0, const P1Data<BS>& D0) {
       const int li = K0.li;
       const int dofs[4] = {K0.dd.x, K0.dd.y, K0.dd.z, K0.dd.w};
       double g[4][3];
@@ -620,31 +282,7 @@ __global__ __launch_bounds__(64) void asm_matrix_p1_node3(const double* __restri
             for (int d = 0; d < BS; ++d)
               vals_s[a0 + c * len + BS * pos4[j] + d] = acc[j][c][d];
       }
-      K0 = K1;
-      K1 = K2;
-      c2 = c3;
-      l2 = l3;
-    };
-    if (alen > 0)
-    {
-      {
-        int ca, la;
-        adj_at(0, ca, la);
-        conn_at(ca, la, K0);
-        data_at(K0, DA);
-        adj_at(1, ca, la);
-        conn_at(ca, la, K1);
-        adj_at(2, c2, l2);
-      }
-      int a = 0;
-      for (; a + 1 < alen; a += 2)
-      {
-        iter(a, DA, DB);
-        iter(a + 1, DB, DA);
-      }
-      if (a < alen)
-        iter(a, DA, DB);
-    }
+    });
 #pragma unroll
     for (int c = 0; c < BS; ++c)
       if (bcr[c]) // fem::set_diagonal: 1.0 on constrained rows
@@ -822,18 +460,9 @@ __global__ __launch_bounds__(ASM_BLOCK) void asm_vector_p1(const double* __restr
           for (int lf = 0; lf < 4; ++lf)
             if (((m >> lf) & 1u) && lf != li)
             {
-              // facet lf = the three vertices other than lf
-              const int q0 = lf == 0 ? 1 : 0, q1 = lf <= 1 ? 2 : 1, q2 = lf == 3 ? 2 : 3;
-              double e1[3], e2[3];
-#pragma unroll
-              for (int k = 0; k < 3; ++k)
-              {
-                e1[k] = p[q1][k] - p[q0][k];
-                e2[k] = p[q2][k] - p[q0][k];
-              }
-              const double cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2],
-                           cz = e1[0] * e2[1] - e1[1] * e2[0];
-              const double scale = sqrt(cx * cx + cy * cy + cz * cz); // 2 * area
+              int q0, q1, q2;
+              facet_vertices(lf, q0, q1, q2);
+              const double scale = facet_scale(p, lf); // 2 * area
               const double gs = gl[q0] + gl[q1] + gl[q2];
               sum += scale * ((gs + gi) / 24.0); // 2 area * sum_j (1+delta_ij)/24 g_j
             }
@@ -874,59 +503,22 @@ __global__ __launch_bounds__(ASM_BLOCK) void asm_matrix_pk(const double* __restr
   double* vals_s = reinterpret_cast<double*>(lds_raw);
   double* T_s = vals_s + cap; // cap = nonzeros a tile may hold (asm_tile_nnz)
   int32_t* cols_s = reinterpret_cast<int32_t*>(T_s + NT * NN);
-  for (int k = threadIdx.x; k < NT * NN; k += ASM_BLOCK)
-  {
-    if (BS == 1)
-    {
-      // symmetrised pieces: G is symmetric, so S^{ab} + S^{ba} is all a < b needs
-      const int t = k / NN, ij = k % NN;
-      const int a = t < 3 ? t : (t == 3 ? 0 : (t == 4 ? 0 : 1)), b = t < 3 ? t : (t == 3 ? 1 : 2);
-      T_s[k] = (t < 3) ? tab[(a * 3 + a) * NN + ij] : tab[(a * 3 + b) * NN + ij] + tab[(b * 3 + a) * NN + ij];
-    }
-    else
-      T_s[k] = tab[k];
-  }
+  stage_reference_tensors<ND, BS>(tab, T_s);
   const int64_t tile = xcd_item(ntiles);
   if (tile < 0)
     return;
-  const int d0 = tiles[tile], d1 = tiles[tile + 1];
-  const int row0 = d0 * BS, row1 = d1 * BS;
-  const int64_t s = rowptr[row0];
-  const int e = (int)(rowptr[row1] - s); // entries of the tile's CSR segment (fits LDS)
+  const TileSpan ts = tile_span<BS>(tiles, rowptr, tile);
+  const int d0 = ts.d0, d1 = ts.d1, e = ts.e;
+  const int64_t s = ts.s;
   for (int k = threadIdx.x; k < e; k += ASM_BLOCK)
   {
     cols_s[k] = cols[s + k];
     vals_s[k] = 0.0;
   }
-  // Block dofs of the tile in order of descending cell count (counting sort in LDS): with the point-major
-  // numbering a tile mixes vertex rows (24 cells) with face rows (2 cells), and a wavefront takes as long as
-  // its heaviest row.  Which lane group computes a row changes nothing in the result.
   __shared__ int ord_s[ASM_ORD_CAP];
   __shared__ int hist_s[34];
   const int nt = d1 - d0;
-  const bool sorted = nt <= ASM_ORD_CAP;
-  if (sorted)
-  {
-    if (threadIdx.x < 34)
-      hist_s[threadIdx.x] = 0;
-    __syncthreads();
-    for (int k = threadIdx.x; k < nt; k += ASM_BLOCK)
-      atomicAdd(&hist_s[32 - min(adj_off[d0 + k + 1] - adj_off[d0 + k], 32)], 1);
-    __syncthreads();
-    if (threadIdx.x == 0)
-    {
-      int acc = 0;
-      for (int b = 0; b < 33; ++b)
-      {
-        const int h = hist_s[b];
-        hist_s[b] = acc;
-        acc += h;
-      }
-    }
-    __syncthreads();
-    for (int k = threadIdx.x; k < nt; k += ASM_BLOCK)
-      ord_s[atomicAdd(&hist_s[32 - min(adj_off[d0 + k + 1] - adj_off[d0 + k], 32)], 1)] = k;
-  }
+  const bool sorted = tile_order_by_cell_count(adj_off, d0, nt, ord_s, hist_s); // descending cell count, where the tile fits ord_s
   __syncthreads();
   const int lane = (int)threadIdx.x % LPR;
   for (int q = (int)threadIdx.x / LPR; q < nt * BS; q += ASM_BLOCK / LPR)
@@ -1120,17 +712,7 @@ __global__ __launch_bounds__(ASM_BLOCK) void asm_vector_pk(const double* __restr
         for (int lf = 0; lf < 4; ++lf)
           if ((m >> lf) & 1u)
           {
-            const int q0 = lf == 0 ? 1 : 0, q1 = lf <= 1 ? 2 : 1, q2 = lf == 3 ? 2 : 3;
-            double e1[3], e2[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-            {
-              e1[k] = p[q1][k] - p[q0][k];
-              e2[k] = p[q2][k] - p[q0][k];
-            }
-            const double cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2],
-                         cz = e1[0] * e2[1] - e1[1] * e2[0];
-            const double scale = sqrt(cx * cx + cy * cy + cz * cz);
+            const double scale = facet_scale(p, lf);
             double fa = 0.0;
             for (int j = 0; j < ND; ++j)
               fa += F_s[(lf * ND + li) * ND + j] * gc[cdv[j]]; // rows of dofs off the facet are zero
@@ -1246,12 +828,11 @@ __global__ void k_cell_geom(const double* __restrict__ x, const int32_t* __restr
     double* o = out + c * NG;
     if (BS == 1)
     {
-      o[0] = G.adet * (G.K[0][0] * G.K[0][0] + G.K[0][1] * G.K[0][1] + G.K[0][2] * G.K[0][2]);
-      o[1] = G.adet * (G.K[1][0] * G.K[1][0] + G.K[1][1] * G.K[1][1] + G.K[1][2] * G.K[1][2]);
-      o[2] = G.adet * (G.K[2][0] * G.K[2][0] + G.K[2][1] * G.K[2][1] + G.K[2][2] * G.K[2][2]);
-      o[3] = G.adet * (G.K[0][0] * G.K[1][0] + G.K[0][1] * G.K[1][1] + G.K[0][2] * G.K[1][2]);
-      o[4] = G.adet * (G.K[0][0] * G.K[2][0] + G.K[0][1] * G.K[2][1] + G.K[0][2] * G.K[2][2]);
-      o[5] = G.adet * (G.K[1][0] * G.K[2][0] + G.K[1][1] * G.K[2][1] + G.K[1][2] * G.K[2][2]);
+      double GG[6];
+      pk_poisson_geom(G, GG);
+#pragma unroll
+      for (int t = 0; t < 6; ++t)
+        o[t] = GG[t];
     }
     else
     {
@@ -1289,24 +870,12 @@ __global__ __launch_bounds__(ASM_BLOCK) void asm_matrix_pk_pos(const double* __r
                                                                int32_t* __restrict__ rownnz, const int64_t* __restrict__ crow,
                                                                double* __restrict__ cvals, int32_t* __restrict__ ccols)
 {
-  constexpr int NT = (BS == 1) ? 6 : 9;
   constexpr int NN = ND * ND;
   constexpr int NG = BS == 1 ? 6 : 10;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   double* vals_s = reinterpret_cast<double*>(lds_raw);
   double* T_s = vals_s + cap; // cap = nonzeros a tile may hold (asm_tile_nnz)
-  for (int k = threadIdx.x; k < NT * NN; k += ASM_BLOCK)
-  {
-    if (BS == 1)
-    {
-      // symmetrised pieces: G is symmetric, so S^{ab} + S^{ba} is all a < b needs
-      const int t = k / NN, ij = k % NN;
-      const int a = t < 3 ? t : (t == 3 ? 0 : (t == 4 ? 0 : 1)), b = t < 3 ? t : (t == 3 ? 1 : 2);
-      T_s[k] = (t < 3) ? tab[(a * 3 + a) * NN + ij] : tab[(a * 3 + b) * NN + ij] + tab[(b * 3 + a) * NN + ij];
-    }
-    else
-      T_s[k] = tab[k];
-  }
+  stage_reference_tensors<ND, BS>(tab, T_s);
   // persistent workgroups: the reference tensors above are staged once per workgroup, not once per tile (at 2048
   // nonzeros per tile the 6.2 M-dof P3 matrix has 146 k tiles: 2.8 GB of table reads otherwise); XCD x walks the x-th
   // eighth of the tiles
@@ -1314,13 +883,11 @@ __global__ __launch_bounds__(ASM_BLOCK) void asm_matrix_pk_pos(const double* __r
   const int64_t t_lo = ntiles * xcd / 8, t_hi = ntiles * (xcd + 1) / 8;
   for (int64_t tile = t_lo + wg_in_xcd; tile < t_hi; tile += n_in_xcd)
   {
-  const int d0 = tiles[tile], d1 = tiles[tile + 1];
-  const int row0 = d0 * BS, row1 = d1 * BS;
-  const int64_t s = rowptr[row0];
-  const int e = (int)(rowptr[row1] - s); // entries of the tile's CSR segment (fits LDS)
+  const TileSpan ts = tile_span<BS>(tiles, rowptr, tile);
+  const int d0 = ts.d0, d1 = ts.d1, row0 = ts.row0, e = ts.e;
+  const int64_t s = ts.s;
   for (int k = threadIdx.x; k < e; k += ASM_BLOCK)
     vals_s[k] = 0.0;
-  // block dofs of the tile in order of descending cell count, as in asm_matrix_pk
   __shared__ int ord_s[ASM_ORD_CAP];
   __shared__ int hist_s[34];
   __shared__ int rp_s[ASM_RP_CAP + 1]; // the tile's row offsets relative to s: every later phase reads them here
@@ -1330,29 +897,7 @@ __global__ __launch_bounds__(ASM_BLOCK) void asm_matrix_pk_pos(const double* __r
     for (int k = threadIdx.x; k <= nt * BS; k += ASM_BLOCK)
       rp_s[k] = (int)(rowptr[row0 + k] - s);
   auto row_begin = [&](int q) { return rp_in_lds ? rp_s[q] : (int)(rowptr[row0 + q] - s); }; // q = scalar row - row0
-  const bool sorted = nt <= ASM_ORD_CAP;
-  if (sorted)
-  {
-    if (threadIdx.x < 34)
-      hist_s[threadIdx.x] = 0;
-    __syncthreads();
-    for (int k = threadIdx.x; k < nt; k += ASM_BLOCK)
-      atomicAdd(&hist_s[32 - min(adj_off[d0 + k + 1] - adj_off[d0 + k], 32)], 1);
-    __syncthreads();
-    if (threadIdx.x == 0)
-    {
-      int acc = 0;
-      for (int b = 0; b < 33; ++b)
-      {
-        const int h = hist_s[b];
-        hist_s[b] = acc;
-        acc += h;
-      }
-    }
-    __syncthreads();
-    for (int k = threadIdx.x; k < nt; k += ASM_BLOCK)
-      ord_s[atomicAdd(&hist_s[32 - min(adj_off[d0 + k + 1] - adj_off[d0 + k], 32)], 1)] = k;
-  }
+  const bool sorted = tile_order_by_cell_count(adj_off, d0, nt, ord_s, hist_s); // descending cell count, where the tile fits ord_s
   __syncthreads();
   const int lane = (int)threadIdx.x % LPR;
   constexpr int JM = (ND + LPR - 1) / LPR; // columns of a cell this lane handles
@@ -1506,6 +1051,24 @@ __global__ __launch_bounds__(ASM_BLOCK) void asm_matrix_pk_pos(const double* __r
   }
 }
 
+// Raises a kernel's limit of dynamic LDS to `bytes`.  The attribute belongs to (kernel, device): it is set once per context
+// and kernel, outside the hot path, and again only if a launch asks for more than the context has set before.
+static int raise_dynamic_lds(zzz_ctx* ctx, const void* kern, size_t bytes)
+{
+  size_t* set = nullptr;
+  for (auto& [k, b] : ctx->lds_raised)
+    if (k == kern)
+      set = &b;
+  if (set && *set >= bytes)
+    return ZZZ_OK;
+  ZZZ_HIP(ctx, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  if (set)
+    *set = bytes;
+  else
+    ctx->lds_raised.emplace_back(kern, bytes);
+  return ZZZ_OK;
+}
+
 template <int ND, int BS, int LPR>
 static int launch_matrix_pk_pos(zzz_ctx* ctx)
 {
@@ -1514,12 +1077,8 @@ static int launch_matrix_pk_pos(zzz_ctx* ctx)
   const int cap = asm_tile_nnz(ctx);
   const size_t lds = (size_t)cap * 8 + (size_t)NT * ND * ND * 8;
   auto kern = asm_matrix_pk_pos<ND, BS, LPR>;
-  const unsigned bit = (16u << ((ND == 10 ? 0 : 2) + (BS == 1 ? 0 : 1))) << (LPR == 8 ? 0 : (LPR == 4 ? 4 : 8));
-  if (!(ctx->lds_attr_set & bit))
-  {
-    ZZZ_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    ctx->lds_attr_set |= bit;
-  }
+  if (int rc = raise_dynamic_lds(ctx, reinterpret_cast<const void*>(kern), lds))
+    return rc;
   ZZZ_HIP(ctx, ctx->cell_geom.alloc((size_t)(ctx->ncells * NG)));
   hipLaunchKernelGGL(k_cell_geom<BS>, dim3((unsigned)std::min<int64_t>((ctx->ncells + 255) / 256, 16384)), dim3(256), 0, ctx->stream,
                      ctx->x.p, ctx->cell_verts.p, ctx->ncells, ctx->cell_geom.p);
@@ -1555,13 +1114,8 @@ static int launch_matrix_pk(zzz_ctx* ctx)
   const int cap = asm_tile_nnz(ctx);
   const size_t lds = (size_t)cap * 8 + (size_t)NT * ND * ND * 8 + (size_t)cap * 4;
   auto kern = asm_matrix_pk<ND, BS, LPR>;
-  // the attribute belongs to (kernel, device): set it once per context, outside the hot path
-  const unsigned bit = 1u << ((ND == 10 ? 0 : 2) + (BS == 1 ? 0 : 1));
-  if (!(ctx->lds_attr_set & bit))
-  {
-    ZZZ_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    ctx->lds_attr_set |= bit;
-  }
+  if (int rc = raise_dynamic_lds(ctx, reinterpret_cast<const void*>(kern), lds))
+    return rc;
   hipLaunchKernelGGL(kern, dim3((unsigned)xcd_grid(ctx->n_asm_tiles)), dim3(ASM_BLOCK), lds, ctx->stream, ctx->x.p,
                      ctx->cell_verts.p, ctx->cell_dofs.p, ctx->adjT_off.p, ctx->adjT_cells.p, ctx->adj_li.p, ctx->adj_off.p, ctx->bc.p,
                      ctx->rowptr.p, ctx->cols.p, ctx->vals.p, ctx->asm_tile.p, ctx->n_asm_tiles, ctx->tables.p, cap);
@@ -1577,6 +1131,35 @@ static void launch_vector_pk(zzz_ctx* ctx, int64_t nrows)
                      BS == 1 ? ctx->coeff[1].p : (const double*)nullptr, ctx->b.p, nrows, ctx->tables.p);
 }
 
+// ---- host dispatch: (order, block size) of the context -> the compile-time <ND, BS> of the kernels, in one place.
+// f is called with two std::integral_constant<int, .> values and returns an error code.
+template <class F>
+static int dispatch_nd_bs(const zzz_ctx* ctx, F&& f)
+{
+  auto with_nd = [&](auto nd) -> int {
+    return ctx->bs == 1 ? f(nd, std::integral_constant<int, 1>()) : f(nd, std::integral_constant<int, 3>());
+  };
+  if (ctx->order == 1)
+    return with_nd(std::integral_constant<int, 4>());
+  if (ctx->order == 2)
+    return with_nd(std::integral_constant<int, 10>());
+  return with_nd(std::integral_constant<int, 20>());
+}
+
+// Lanes per matrix row (listed row of the lifting pass) by kernel, order and block size.
+//   asm_matrix_pk_pos: Poisson four (P3: five columns each, no idle lane: 2.80 against 2.92 ms), elasticity P3 eight;
+//   k_lift: one at P1 (four columns); otherwise as many as leave each lane five (Poisson) or three (elasticity: nine
+//   entries each) columns of a cell -- the P3 matrix kernels' split, for the same reason: a P3 vertex row walks 24 cells
+//   of 20 dofs.
+enum AsmKernel { ASM_PK_POS, ASM_PK, ASM_LIFT };
+constexpr int ASM_LPR[3][3][2] = {
+    // [kernel][order - 1][BS == 3]; the P2 / P3 matrix kernels do not serve P1
+    {{0, 0}, {4, 4}, {4, 8}}, // asm_matrix_pk_pos
+    {{0, 0}, {4, 4}, {8, 8}}, // asm_matrix_pk
+    {{1, 1}, {2, 4}, {4, 8}}, // k_lift
+};
+constexpr int asm_lpr(AsmKernel k, int nd, int bs) { return ASM_LPR[k][nd == 4 ? 0 : (nd == 10 ? 1 : 2)][bs == 3]; }
+
 int launch_assemble_matrix(zzz_ctx* ctx, int form)
 {
   ctx->sp_rownnz_fresh = ctx->sp_compact_fresh = false;
@@ -1584,47 +1167,35 @@ int launch_assemble_matrix(zzz_ctx* ctx, int form)
   const int bs = form == ZZZ_FORM_ELASTICITY ? 3 : 1;
   if (bs != ctx->bs)
     return fail(ctx, ZZZ_ERR_ARG, "form %d needs block size %d, dofmap has %d", form, bs, ctx->bs);
-  const dim3 grid((unsigned)xcd_grid(ctx->n_asm_tiles)), block(ASM_BLOCK);
   if (int rc = ensure_p1_coords(ctx))
     return rc;
-  if (ctx->order == 1)
-  {
-    if (bs == 1)
-    {
-      // one thread per row: a 1920-nonzero tile holds ~126 rows of 15, so 128 threads leave no lane idle
-      hipLaunchKernelGGL((asm_matrix_p1<1, ASM_NNZ_P1, 128>), grid, dim3(128), 0, ctx->stream, ctx->xq, ctx->cell_dofs.p,
-                         ctx->adjT_off.p, ctx->adjT_cells.p, ctx->adj_li.p, ctx->bc.p, ctx->rowptr.p, ctx->cols.p, ctx->vals.p,
-                         ctx->asm_tile.p, ctx->n_asm_tiles);
-    }
-    else if (ctx->asm_node3)
-      hipLaunchKernelGGL((asm_matrix_p1_node3<ASM_NNZ_NODE3>), grid, dim3(64), 0, ctx->stream, ctx->xq, ctx->cell_dofs.p,
-                         ctx->adjT_off.p, ctx->adjT_cells.p, ctx->adj_li.p, ctx->bc.p, ctx->rowptr.p, ctx->cols.p, ctx->vals.p,
-                         ctx->asm_tile.p, ctx->n_asm_tiles);
-    else
-      hipLaunchKernelGGL((asm_matrix_p1<3, ASM_NNZ, ASM_BLOCK>), grid, block, 0, ctx->stream, ctx->xq, ctx->cell_dofs.p,
-                         ctx->adjT_off.p, ctx->adjT_cells.p, ctx->adj_li.p, ctx->bc.p, ctx->rowptr.p, ctx->cols.p, ctx->vals.p,
-                         ctx->asm_tile.p, ctx->n_asm_tiles);
-  }
-  else
-  {
-    int rc = ensure_tables(ctx);
-    if (rc)
+  if (ctx->order != 1)
+    if (int rc = ensure_tables(ctx))
       return rc;
-    if (ctx->have_asm_pos) // positions from the pattern build: no column search (asm_matrix_pk_pos)
+  const int rc = dispatch_nd_bs(ctx, [&](auto nd, auto bs_) -> int {
+    constexpr int ND = decltype(nd)::value, BS = decltype(bs_)::value;
+    if constexpr (ND == 4)
     {
-      // lanes per row: Poisson four (P3: five columns each, no idle lane: 2.80 against 2.92 ms), elasticity P3 eight
-      if (ctx->order == 2)
-        rc = bs == 1 ? launch_matrix_pk_pos<10, 1, 4>(ctx) : launch_matrix_pk_pos<10, 3, 4>(ctx);
+      const dim3 grid((unsigned)xcd_grid(ctx->n_asm_tiles));
+      auto launch = [&](auto kern, int blk) {
+        hipLaunchKernelGGL(kern, grid, dim3(blk), 0, ctx->stream, ctx->xq, ctx->cell_dofs.p, ctx->adjT_off.p, ctx->adjT_cells.p,
+                           ctx->adj_li.p, ctx->bc.p, ctx->rowptr.p, ctx->cols.p, ctx->vals.p, ctx->asm_tile.p, ctx->n_asm_tiles);
+      };
+      if (BS == 1) // one thread per row: a 1920-nonzero tile holds ~126 rows of 15, so 128 threads leave no lane idle
+        launch(asm_matrix_p1<1, ASM_NNZ_P1, 128>, 128);
+      else if (ctx->asm_node3)
+        launch(asm_matrix_p1_node3<ASM_NNZ_NODE3>, 64);
       else
-        rc = bs == 1 ? launch_matrix_pk_pos<20, 1, 4>(ctx) : launch_matrix_pk_pos<20, 3, 8>(ctx);
+        launch(asm_matrix_p1<3, ASM_NNZ, ASM_BLOCK>, ASM_BLOCK);
+      return ZZZ_OK;
     }
-    else if (ctx->order == 2)
-      rc = bs == 1 ? launch_matrix_pk<10, 1, 4>(ctx) : launch_matrix_pk<10, 3, 4>(ctx);
+    else if (ctx->have_asm_pos) // positions from the pattern build: no column search (asm_matrix_pk_pos)
+      return launch_matrix_pk_pos<ND, BS, asm_lpr(ASM_PK_POS, ND, BS)>(ctx);
     else
-      rc = bs == 1 ? launch_matrix_pk<20, 1, 8>(ctx) : launch_matrix_pk<20, 3, 8>(ctx);
-    if (rc)
-      return rc;
-  }
+      return launch_matrix_pk<ND, BS, asm_lpr(ASM_PK, ND, BS)>(ctx);
+  });
+  if (rc)
+    return rc;
   ZZZ_HIP(ctx, hipGetLastError());
   return ZZZ_OK;
 }
@@ -1635,46 +1206,35 @@ int launch_assemble_vector(zzz_ctx* ctx, int form)
   if (bs != ctx->bs)
     return fail(ctx, ZZZ_ERR_ARG, "form %d needs block size %d, dofmap has %d", form, bs, ctx->bs);
   const int64_t nrows = ctx->n_owned * bs;
-  const dim3 grid((unsigned)xcd_grid((nrows + ASM_BLOCK - 1) / ASM_BLOCK)), block(ASM_BLOCK);
   if (int rc = ensure_p1_coords(ctx))
     return rc;
-  if (ctx->order == 1)
-  {
-    // the cells' records first (|det J| and the coefficient's vertex sum: k_cell_load_p1), then the row walk
-    ZZZ_HIP(ctx, ctx->cell_geom.alloc((size_t)(ctx->ncells * (bs == 1 ? 2 : 4))));
-    const int cper = bs == 1 ? 1024 : 256; // cells per workgroup and round (k_cell_load_p1: U)
-    // (a partition without cells: no cell pass -- a grid of 0 workgroups is an invalid configuration and the kernel clamps
-    // cell numbers to ncells - 1; the row walk below then meets empty adjacency lists only)
-    const dim3 cgrid((unsigned)std::max<int64_t>(1, std::min<int64_t>((ctx->ncells + cper - 1) / cper, 16384)));
-    if (bs == 1)
+  if (ctx->order != 1)
+    if (int rc = ensure_tables(ctx))
+      return rc;
+  const int rc = dispatch_nd_bs(ctx, [&](auto nd, auto bs_) -> int {
+    constexpr int ND = decltype(nd)::value, BS = decltype(bs_)::value;
+    if constexpr (ND == 4)
     {
+      // the cells' records first (|det J| and the coefficient's vertex sum: k_cell_load_p1), then the row walk
+      ZZZ_HIP(ctx, ctx->cell_geom.alloc((size_t)(ctx->ncells * (BS == 1 ? 2 : 4))));
+      constexpr int cper = BS == 1 ? 1024 : 256; // cells per workgroup and round (k_cell_load_p1: U)
+      // (a partition without cells: no cell pass -- a grid of 0 workgroups is an invalid configuration and the kernel clamps
+      // cell numbers to ncells - 1; the row walk below then meets empty adjacency lists only)
       if (ctx->ncells > 0)
-        hipLaunchKernelGGL(k_cell_load_p1<1>, cgrid, dim3(256), 0, ctx->stream, ctx->xq, ctx->cell_dofs.p, ctx->coeff[0].p,
-                           ctx->facet_mask.p, ctx->ncells, ctx->cell_geom.p);
-      hipLaunchKernelGGL(asm_vector_p1<1>, grid, block, 0, ctx->stream, ctx->xq, ctx->cell_dofs.p, ctx->adjT_off.p, ctx->adjT_cells.p,
-                         ctx->adj_li.p, ctx->bc.p, ctx->facet_mask.p, ctx->coeff[0].p, ctx->coeff[1].p, ctx->cell_geom.p, ctx->b.p,
-                         nrows);
-    }
-    else
-    {
-      if (ctx->ncells > 0)
-        hipLaunchKernelGGL(k_cell_load_p1<3>, cgrid, dim3(256), 0, ctx->stream, ctx->xq, ctx->cell_dofs.p, ctx->coeff[0].p,
-                           (const uint8_t*)nullptr, ctx->ncells, ctx->cell_geom.p);
-      hipLaunchKernelGGL(asm_vector_p1<3>, grid, block, 0, ctx->stream, ctx->xq, ctx->cell_dofs.p, ctx->adjT_off.p, ctx->adjT_cells.p,
-                         ctx->adj_li.p, ctx->bc.p, ctx->facet_mask.p, ctx->coeff[0].p, (const double*)nullptr, ctx->cell_geom.p,
+        hipLaunchKernelGGL(k_cell_load_p1<BS>, dim3((unsigned)std::min<int64_t>((ctx->ncells + cper - 1) / cper, 16384)), dim3(256), 0,
+                           ctx->stream, ctx->xq, ctx->cell_dofs.p, ctx->coeff[0].p,
+                           BS == 1 ? ctx->facet_mask.p : (const uint8_t*)nullptr, ctx->ncells, ctx->cell_geom.p);
+      hipLaunchKernelGGL(asm_vector_p1<BS>, dim3((unsigned)xcd_grid((nrows + ASM_BLOCK - 1) / ASM_BLOCK)), dim3(ASM_BLOCK), 0,
+                         ctx->stream, ctx->xq, ctx->cell_dofs.p, ctx->adjT_off.p, ctx->adjT_cells.p, ctx->adj_li.p, ctx->bc.p,
+                         ctx->facet_mask.p, ctx->coeff[0].p, BS == 1 ? ctx->coeff[1].p : (const double*)nullptr, ctx->cell_geom.p,
                          ctx->b.p, nrows);
     }
-  }
-  else
-  {
-    int rc = ensure_tables(ctx);
-    if (rc)
-      return rc;
-    if (ctx->order == 2)
-      bs == 1 ? launch_vector_pk<10, 1>(ctx, nrows) : launch_vector_pk<10, 3>(ctx, nrows);
     else
-      bs == 1 ? launch_vector_pk<20, 1>(ctx, nrows) : launch_vector_pk<20, 3>(ctx, nrows);
-  }
+      launch_vector_pk<ND, BS>(ctx, nrows);
+    return ZZZ_OK;
+  });
+  if (rc)
+    return rc;
   ZZZ_HIP(ctx, hipGetLastError());
   return ZZZ_OK;
 }
@@ -1727,18 +1287,7 @@ __global__ __launch_bounds__(ASM_BLOCK) void k_lift(const double* __restrict__ x
   __shared__ double T_s[ND == 4 ? 1 : NT * NN];
   if (ND != 4)
   {
-    for (int k = threadIdx.x; k < NT * NN; k += ASM_BLOCK)
-    {
-      if (BS == 1)
-      {
-        // symmetrised pieces, as the matrix kernels stage them
-        const int t = k / NN, ij = k % NN;
-        const int a = t < 3 ? t : (t == 3 ? 0 : (t == 4 ? 0 : 1)), bb = t < 3 ? t : (t == 3 ? 1 : 2);
-        T_s[k] = (t < 3) ? tab[(a * 3 + a) * NN + ij] : tab[(a * 3 + bb) * NN + ij] + tab[(bb * 3 + a) * NN + ij];
-      }
-      else
-        T_s[k] = tab[k];
-    }
+    stage_reference_tensors<ND, BS>(tab, T_s); // as the matrix kernels stage them
     __syncthreads();
   }
   const int lane = (int)threadIdx.x % LPR;
@@ -1931,14 +1480,11 @@ int launch_lift(zzz_ctx* ctx)
       return rc;
   if (ctx->n_lift_rows > 0)
   {
-    // lanes per row: one at P1 (four columns); otherwise as many as leave each lane five (Poisson) or three (elasticity: nine
-    // entries each) columns of a cell -- the P3 matrix kernels' split, for the same reason: a P3 vertex row walks 24 cells of 20 dofs
-    if (ctx->order == 1)
-      ctx->bs == 1 ? launch_k_lift<4, 1, 1>(ctx) : launch_k_lift<4, 3, 1>(ctx);
-    else if (ctx->order == 2)
-      ctx->bs == 1 ? launch_k_lift<10, 1, 2>(ctx) : launch_k_lift<10, 3, 4>(ctx);
-    else
-      ctx->bs == 1 ? launch_k_lift<20, 1, 4>(ctx) : launch_k_lift<20, 3, 8>(ctx);
+    dispatch_nd_bs(ctx, [&](auto nd, auto bs) -> int {
+      constexpr int ND = decltype(nd)::value, BS = decltype(bs)::value;
+      launch_k_lift<ND, BS, asm_lpr(ASM_LIFT, ND, BS)>(ctx);
+      return ZZZ_OK;
+    });
   }
   const int64_t nrows = ctx->n_owned * ctx->bs;
   hipLaunchKernelGGL(k_bc_set_values, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((nrows + 255) / 256, 2048))), dim3(256), 0,
@@ -1974,12 +1520,7 @@ __global__ __launch_bounds__(ASM_BLOCK) void matfree_cell(const double* __restri
   __shared__ double T_s[ND == 4 ? 1 : 6 * NN];
   if (ND != 4)
   {
-    for (int k = threadIdx.x; k < 6 * NN; k += ASM_BLOCK)
-    {
-      const int t = k / NN, ij = k % NN;
-      const int a = t < 3 ? t : (t == 3 ? 0 : (t == 4 ? 0 : 1)), b = t < 3 ? t : (t == 3 ? 1 : 2);
-      T_s[k] = (t < 3) ? tab[(a * 3 + a) * NN + ij] : tab[(a * 3 + b) * NN + ij] + tab[(b * 3 + a) * NN + ij];
-    }
+    stage_reference_tensors<ND, 1>(tab, T_s);
     __syncthreads();
   }
   for (int64_t c = blockIdx.x * (int64_t)ASM_BLOCK + threadIdx.x; c < ncells; c += (int64_t)gridDim.x * ASM_BLOCK)
@@ -2012,12 +1553,7 @@ __global__ __launch_bounds__(ASM_BLOCK) void matfree_cell(const double* __restri
     else
     {
       double GG[6];
-      GG[0] = G.adet * (G.K[0][0] * G.K[0][0] + G.K[0][1] * G.K[0][1] + G.K[0][2] * G.K[0][2]);
-      GG[1] = G.adet * (G.K[1][0] * G.K[1][0] + G.K[1][1] * G.K[1][1] + G.K[1][2] * G.K[1][2]);
-      GG[2] = G.adet * (G.K[2][0] * G.K[2][0] + G.K[2][1] * G.K[2][1] + G.K[2][2] * G.K[2][2]);
-      GG[3] = G.adet * (G.K[0][0] * G.K[1][0] + G.K[0][1] * G.K[1][1] + G.K[0][2] * G.K[1][2]);
-      GG[4] = G.adet * (G.K[0][0] * G.K[2][0] + G.K[0][1] * G.K[2][1] + G.K[0][2] * G.K[2][2]);
-      GG[5] = G.adet * (G.K[1][0] * G.K[2][0] + G.K[1][1] * G.K[2][1] + G.K[1][2] * G.K[2][2]);
+      pk_poisson_geom(G, GG);
       double ul[ND];
 #pragma unroll
       for (int j = 0; j < ND; ++j)

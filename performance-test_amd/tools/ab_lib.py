@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """A/B of two BUILDS of libzzz_hip.so on the assembly phases: child processes alternate between the two libraries
 (ZZZ_HIP_LIB), each times pattern build, matrix assembly and vector assembly on one device-generated system.
-Usage: ab_lib.py <other libzzz_hip.so> [case ...]   (cases as in ab_sellp.py; the in-tree build is "new")"""
+Usage: ab_lib.py <other libzzz_hip.so> [case ...] [--rounds N] [--json FILE]   (cases as in ab_sellp.py; the in-tree build is
+"new"; per phase the median, minimum and maximum over the rounds of each build; --json keeps the per-round numbers)"""
 import os
 import subprocess
 import sys
@@ -36,11 +37,24 @@ def child(case):
 
 
 def main():
-    other = os.path.abspath(sys.argv[1])
-    cases = sys.argv[2:] or ["c2"]
+    args = sys.argv[1:]
+    rounds, json_path = 3, None
+    for flag in ("--rounds", "--json"):
+        if flag in args:
+            k = args.index(flag)
+            if flag == "--rounds":
+                rounds = int(args[k + 1])
+            else:
+                json_path = args[k + 1]
+            del args[k:k + 2]
+    other = os.path.abspath(args[0])
+    cases = args[1:] or ["c2"]
+    phases = ("pattern", "matrix", "vector")
+    record = {"tool": "ab_lib.py", "old": other, "rounds": rounds, "unit": "ms (per child: median of its last five of six repetitions)",
+              "cases": {}}
     for case in cases:
         res = {"old": [], "new": []}
-        for rnd in range(3):
+        for rnd in range(rounds):
             for tag in ("old", "new"):
                 env = dict(os.environ)
                 if tag == "old":
@@ -49,15 +63,32 @@ def main():
                     env.pop("ZZZ_HIP_LIB", None)
                 out = subprocess.run([sys.executable, __file__, "--child", case], env=env, capture_output=True, text=True, timeout=900)
                 line = [ln for ln in out.stdout.splitlines() if ln.startswith("RES")]
-                if not line:
+                if out.returncode != 0 or not line:
                     print(out.stdout[-2000:], out.stderr[-2000:])
                     sys.exit(1)
                 res[tag].append(line[0].split()[1:])
+        t = {tag: np.array([[float(x) for x in r[:3]] for r in res[tag]]) for tag in res}
         for tag in ("old", "new"):
-            a = np.array([[float(x) for x in r[:3]] for r in res[tag]])
-            print(f"[{case}] {tag}: pattern {np.median(a[:, 0]):.3f} ms  matrix (+ stream packing) {np.median(a[:, 1]):.3f} ms  "
-                  f"vector {np.median(a[:, 2]):.3f} ms   |b| {res[tag][0][3]}  sum|A| {res[tag][0][4]}")
-        print(f"[{case}] identical |b| and sum|A|:", res["old"][0][3:] == res["new"][0][3:])
+            a = t[tag]
+            print(f"[{case}] {tag}: " + "  ".join(f"{ph} {np.median(a[:, k]):.3f} [{a[:, k].min():.3f}, {a[:, k].max():.3f}] ms"
+                                                   for k, ph in enumerate(phases))
+                  + f"   (median [min, max] of {rounds} rounds; matrix with stream packing)   |b| {res[tag][0][3]}  sum|A| {res[tag][0][4]}")
+        same = all(r[3:] == res["old"][0][3:] for tag in res for r in res[tag])
+        print(f"[{case}] identical |b| and sum|A|:", same)
+        # the new build's median against the old one's, with the old build's own spread over its rounds as the margin
+        within = {ph: bool(np.median(t["new"][:, k]) - np.median(t["old"][:, k]) <= t["old"][:, k].max() - t["old"][:, k].min())
+                  for k, ph in enumerate(phases)}
+        print(f"[{case}] new median within old median + old (max - min):", within)
+        record["cases"][case] = {"old": {ph: t["old"][:, k].tolist() for k, ph in enumerate(phases)},
+                                 "new": {ph: t["new"][:, k].tolist() for k, ph in enumerate(phases)},
+                                 "norm_b": res["old"][0][3], "sum_abs_A": res["old"][0][4], "identical_norms": same,
+                                 "new_median_within_old_spread": within}
+    if json_path:
+        import json
+
+        with open(json_path, "w") as f:
+            json.dump(record, f, indent=1)
+            f.write("\n")
 
 
 if __name__ == "__main__":
