@@ -134,7 +134,10 @@ enum
 enum
 {
   ZZZ_OP_CSR = 0,    /* assembled operator (poisson, elasticity) */
-  ZZZ_OP_MATFREE = 1 /* cgpoisson's action(a, un) (src/cgpoisson_problem.cpp:193-230) */
+  ZZZ_OP_MATFREE = 1 /* cgpoisson's action(a, un) (src/cgpoisson_problem.cpp:193-230); on a context of block size 3 the same
+                        for form a of src/Elasticity.py (the driver's cgelasticity).  At either block size: ZZZ_CG_CGH with
+                        ZZZ_PC_NONE, ZZZ_CG_PETSC with ZZZ_PC_NONE or ZZZ_PC_JACOBI and any norm type, with or without a
+                        communicator; declined: Chebyshev-Jacobi, mg, pmg, single_reduction, ZZZ_CG_PIPE */
 };
 
 typedef struct
@@ -320,6 +323,12 @@ int zzz_spmv_time(zzz_ctx* ctx, int reps, int variant, double* avg_ms);
  * assemble_vector of form M = action(a, un) with un = x, rows of constrained dofs zeroed, ghosts
  * of x updated first.  Needs mesh, dofmap and Dirichlet dofs only: no pattern, no matrix (the reference's cgpoisson
  * creates neither, src/cgpoisson_problem.cpp:47-247).  Builds the operator's plan on first use (zzz_matfree_setup).
+ * Block size 3 (a dofmap uploaded or generated for elasticity): y = A x for form a of src/Elasticity.py, inner(sigma(u),
+ * eps(v)) dx with E = 1e6, nu = 0.3, applied cell by cell and never stored; x and y hold 3 n_owned doubles, the three
+ * components of a node side by side, and the rows of constrained SCALAR dofs are exactly 0 (a Dirichlet set may constrain
+ * one component of a node).  zzz_matfree_setup, _info, _diagonal and zzz_action_time serve both block sizes; a mesh whose
+ * smallest cell block touches more nodes than LDS holds is refused with ZZZ_ERR_LIMIT and the context stays usable (the
+ * two-pass fallback exists for block size 1 only).  The float entry points keep declining block size 3.
  * Non-finite input (zzz_action and zzz_action_f32 alike): an Inf or NaN in x[d] stays with the cells that hold d.  y[d] is
  * non-finite (d unconstrained); rows of constrained dofs are 0 whatever their cells carry; the entries of the other dofs
  * that share a cell with d are non-finite wherever the element arithmetic couples them to d -- all of them for P1, for
@@ -336,7 +345,7 @@ int zzz_matfree_setup(zzz_ctx* ctx);
 /* info[0] plan valid, [1] cell blocks, [2] cells per block, [3] threads per workgroup, [4] most dofs a block touches,
  * [5] dofs shared between blocks, [6] their partial sums per action, [7] bytes one action addresses (plan + vectors). */
 int zzz_matfree_info(zzz_ctx* ctx, int64_t info[8]);
-/* diag[n_owned] = the diagonal of the operator zzz_action applies, as the assembled matrix holds it (MatGetDiagonal after
+/* diag[n_owned * block size] = the diagonal of the operator zzz_action applies, as the assembled matrix holds it (MatGetDiagonal after
  * fem::set_diagonal: 1.0 on constrained rows, src/poisson_problem.cpp:146-157) -- computed from the element matrices in
  * the matrix-free kernel's pass, nothing assembled.  It is what PCJACOBI uses when zzz_cg_solve runs KSPCG on
  * op = ZZZ_OP_MATFREE (an extension: the reference's KSP path always multiplies with the assembled AIJ matrix,

@@ -1706,7 +1706,7 @@ int launch_matfree_action(zzz_ctx* ctx, const double* u, double* y, double* part
   if (!ctx->mf.valid && !ctx->mf.failed)
   {
     const int rc = mf_plan_build(ctx);
-    if (rc == ZZZ_ERR_LIMIT && ctx->have_pattern && ctx->have_adj_li)
+    if (rc == ZZZ_ERR_LIMIT && ctx->bs == 1 && ctx->have_pattern && ctx->have_adj_li)
       ctx->mf.failed = true; // a mesh the plan cannot hold (a dof in more than 254 cells of one step): the two-pass form serves it
     else if (rc)
       return rc;

@@ -133,6 +133,7 @@ struct CgParams
 struct MfPlan
 {
   bool valid = false, failed = false;
+  int bs = 1;                               // values per block dof: 1 (Poisson form M) or 3 (elasticity form a)
   int nd = 0, nc = 0, threads = 0, nsb = 0; // dofs per cell; cells per block; workgroup size; steps per block (nc / threads)
   int ndw = 0, nrw = 0;                     // 32-bit words of indices / of ranks per cell
   int64_t nblocks = 0, nshared = 0, nslots = 0;

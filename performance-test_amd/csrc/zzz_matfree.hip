@@ -346,10 +346,16 @@ __global__ __launch_bounds__(256) void k_mf_headers(const int32_t* __restrict__ 
     atomicMax(nloc_max, m);
 }
 
+// block size 3: the Dirichlet markers of a node's three scalar dofs, bit c = component c
+__device__ inline uint8_t mf_flag3(const uint8_t* __restrict__ bc, uint32_t g)
+{
+  return (uint8_t)((bc[3ll * g] ? 1 : 0) | (bc[3ll * g + 1] ? 2 : 0) | (bc[3ll * g + 2] ? 4 : 0));
+}
+
 // the block-local lists in their final order (sorted key2): global dof, Dirichlet flag, coordinates; local index of every
 // unique; (dof, slot) of the shared ones
 __global__ __launch_bounds__(256) void k_mf_lists(const uint64_t* __restrict__ key2s, const int32_t* __restrict__ val2s, int64_t nu,
-                                                  const int32_t* __restrict__ hdr, const uint8_t* __restrict__ bc,
+                                                  const int32_t* __restrict__ hdr, const uint8_t* __restrict__ bc, int bs,
                                                   const double* __restrict__ xq, int32_t* __restrict__ dof_ids,
                                                   uint8_t* __restrict__ dof_flag, double* __restrict__ xyz,
                                                   int32_t* __restrict__ loc_of, uint32_t* __restrict__ sh_key,
@@ -364,7 +370,7 @@ __global__ __launch_bounds__(256) void k_mf_lists(const uint64_t* __restrict__ k
     const int32_t* h = hdr + MF_HDR * b;
     const int loc = (int)(q - h[0]);
     dof_ids[q] = (int32_t)g;
-    dof_flag[q] = bc[g];
+    dof_flag[q] = bs == 1 ? bc[g] : mf_flag3(bc, g);
     if (xyz)
     {
       xyz[3 * q + 0] = xq[3ll * g + 0];
@@ -469,7 +475,7 @@ __global__ __launch_bounds__(256) void k_mf_sh_heads(const uint32_t* __restrict_
 // where the block that owns old slot `val[p]` stores that sum
 __global__ __launch_bounds__(256) void k_mf_sh_fill(const uint32_t* __restrict__ key, const int32_t* __restrict__ val,
                                                     const int32_t* __restrict__ flag, const int32_t* __restrict__ uidx, int64_t n,
-                                                    const uint8_t* __restrict__ bc, int32_t* __restrict__ sh_dof,
+                                                    const uint8_t* __restrict__ bc, int bs, int32_t* __restrict__ sh_dof,
                                                     int32_t* __restrict__ sh_off, uint8_t* __restrict__ sh_flag,
                                                     int32_t* __restrict__ pslot, int64_t nshared)
 {
@@ -485,7 +491,7 @@ __global__ __launch_bounds__(256) void k_mf_sh_fill(const uint32_t* __restrict__
     {
       sh_dof[uidx[i]] = (int32_t)key[i];
       sh_off[uidx[i]] = (int32_t)i;
-      sh_flag[uidx[i]] = bc[key[i]];
+      sh_flag[uidx[i]] = bs == 1 ? bc[key[i]] : mf_flag3(bc, key[i]);
     }
   }
 }
@@ -528,6 +534,32 @@ __global__ __launch_bounds__(256) void k_mf_geom(const double* __restrict__ x, c
     }
     for (int t = 0; t < 6; ++t)
       geom[(b * 6 + t) * nc + e] = G[t];
+  }
+}
+
+// block size 3, P2/P3: K = J^-1 (nine values) and |detJ| of every cell, same layout with ten values per cell
+__global__ __launch_bounds__(256) void k_mf_geom_el(const double* __restrict__ x, const int32_t* __restrict__ cell_verts,
+                                                    const int32_t* __restrict__ mf_cell, int nc, int64_t total,
+                                                    double* __restrict__ geom)
+{
+  for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < total; i += gridDim.x * 256ll)
+  {
+    const int64_t b = i / nc;
+    const int e = (int)(i - b * nc);
+    const int32_t c = mf_cell[i];
+    double Kd[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    if (c >= 0)
+    {
+      const int4 v = *reinterpret_cast<const int4*>(cell_verts + 4ll * c);
+      const int vv[4] = {v.x, v.y, v.z, v.w};
+      double p[4][3];
+      for (int k = 0; k < 4; ++k)
+        for (int a = 0; a < 3; ++a)
+          p[k][a] = x[3ll * vv[k] + a];
+      mf_cell_geom_el(p, Kd);
+    }
+    for (int t = 0; t < 10; ++t)
+      geom[(b * 10 + t) * nc + e] = Kd[t];
   }
 }
 
@@ -803,6 +835,248 @@ __global__ __launch_bounds__(256) void k_mf_finish(const int32_t* __restrict__ s
   }
 }
 
+// ---- block size 3: form a of src/Elasticity.py (zzz_mf_elem.h: mf_el_*) on the same plan ------------------------------------
+// The plan is per NODE (block dof) and unchanged; a node carries three values.  LDS per node: P1 coordinates + 3 u + 3 y
+// (72 B), P2 3 u + 3 y (48 B), P3 3 y (24 B: u gathered from memory through gid).  A round adds the three values of every
+// incidence of its rank with the same return-free LDS adds (two lanes of a round never hold the same node, so never the same
+// address); dof_flag carries one bit per component.  P2/P3 run the element in three phases (zzz_mf_elem.h) so that u_e and
+// y_e of the three components are never live together: g for all modes component by component, sigma in place, then y_e.
+// Two wavefronts per SIMD at P3 (256 registers: g is 90 doubles, y_e 60).
+template <int ND, int T, bool DIAG>
+__global__ __launch_bounds__(T, (ND == 20 ? 2 : 1)) void k_mf_action3(const MfArgs<double> A)
+{
+  if (A.stop && *A.stop)
+    return;
+  constexpr int NDW = ND / 2, NRW = (ND + 3) / 4;
+  extern __shared__ __align__(32) unsigned char mf_lds[];
+  constexpr bool GU = ND == 20;
+  // P1: xs[3 cap] us[3 cap] ys[3 cap]; P2: us ys; P3: ys
+  double* const base = reinterpret_cast<double*>(mf_lds);
+  double* const xs = base;
+  double* const us = base + (size_t)(ND == 4 ? 3 : 0) * A.nloc_cap;
+  double* const ys = base + (size_t)(ND == 4 ? 6 : (GU ? 0 : 3)) * A.nloc_cap;
+  __shared__ double red[T / 64];
+  constexpr int NTAB = ND == 4 ? 1 : 3 * ND * (ND == 10 ? 4 : 10);
+  __shared__ double tab_s[NTAB], tabT_s[NTAB];
+  const int tid = threadIdx.x;
+  if (ND != 4)
+    for (int k = tid; k < NTAB; k += T) // (the first block's barrier below orders this)
+    {
+      constexpr int NQ = ND == 10 ? 4 : 10;
+      const double v = A.dtab[k]; // [a][q][j]
+      const int a = k / (NQ * ND), q = (k / ND) % NQ, j = k % ND;
+      tab_s[k] = v;
+      tabT_s[(q * ND + j) * 3 + a] = v;
+    }
+  double dot = 0.0;
+  for (int step = 0;; ++step)
+  {
+    const int64_t b = xcd_stride_item(A.nblocks, step);
+    if (b < 0)
+      break;
+    const int32_t* __restrict__ h = A.hdr + MF_HDR * b;
+    const int dof_off = h[0], nloc = h[1], n_int = h[2], n_sh = h[3], part_off = h[4];
+    for (int d = tid; d < nloc; d += T)
+    {
+      if constexpr (ND == 4)
+      {
+        const double* __restrict__ q = A.xyz + 3ll * (dof_off + d);
+        xs[3 * d + 0] = q[0];
+        xs[3 * d + 1] = q[1];
+        xs[3 * d + 2] = q[2];
+      }
+      if constexpr (!GU && !DIAG)
+      {
+        const double* __restrict__ q = A.u + 3ll * A.dof_ids[dof_off + d];
+        us[3 * d + 0] = q[0];
+        us[3 * d + 1] = q[1];
+        us[3 * d + 2] = q[2];
+      }
+      ys[3 * d + 0] = 0.0;
+      ys[3 * d + 1] = 0.0;
+      ys[3 * d + 2] = 0.0;
+    }
+    for (int s = 0; s < A.nsb; ++s)
+    {
+      const int e = s * T + tid;
+      uint32_t iw[NDW], rw[NRW];
+#pragma unroll
+      for (int w = 0; w < NDW; ++w)
+        iw[w] = A.idxw[(b * NDW + w) * A.nc + e];
+#pragma unroll
+      for (int w = 0; w < NRW; ++w)
+        rw[w] = A.rnkw[(b * NRW + w) * A.nc + e];
+      double ye[3][ND]; // [component][local node]
+      if (s == 0)
+      {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __syncthreads(); // the staged values are in LDS
+      }
+      // rounds, as in k_mf_action: the incidences of rank r of this step are added in round r
+      const uint32_t* __restrict__ rm = reinterpret_cast<const uint32_t*>(A.rmax) + (b * A.nsb + s) * NRW;
+      int Rc[3] = {0, 0, 0};
+      constexpr int NE = ND == 20 ? 16 : ND;
+#pragma unroll
+      for (int w = 0; w < NRW; ++w)
+      {
+        const uint32_t m = __builtin_amdgcn_readfirstlane(rm[w]);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (4 * w + k < ND)
+          {
+            const int c = 4 * w + k < 4 ? 0 : (4 * w + k < NE ? 1 : 2);
+            Rc[c] = max(Rc[c], (int)((m >> (8 * k)) & 255u));
+          }
+      }
+      const int R2 = Rc[2], R1 = max(R2, Rc[1]), R0 = max(R1, Rc[0]);
+      auto rounds = [&](auto add) {
+        for (int r = 0; r < R0; ++r)
+        {
+          // (the wait is spelled out: see k_mf_action)
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          __syncthreads();
+          const int jend = r < R2 ? ND : (r < R1 ? NE : 4); // uniform
+#pragma unroll
+          for (int j = 0; j < ND; ++j)
+          {
+            if (j < 4 || (j < NE ? jend > 4 : jend > NE))
+              if ((int)((rw[j >> 2] >> (8 * (j & 3))) & 255u) == r)
+                add((int)((iw[j >> 1] >> (16 * (j & 1))) & 0xffff), j);
+          }
+        }
+      };
+      // the three values of an incidence (two lanes of a round never hold the same node, so never the same address)
+      auto add3 = [&](int i, int j) {
+        __hip_atomic_fetch_add(&ys[3 * i + 0], ye[0][j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __hip_atomic_fetch_add(&ys[3 * i + 1], ye[1][j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __hip_atomic_fetch_add(&ys[3 * i + 2], ye[2][j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      };
+      if constexpr (ND == 4)
+      {
+        double px[4][3], pu[4][3], pe[4][3];
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+        {
+          const int i = (iw[k >> 1] >> (16 * (k & 1))) & 0xffff;
+#pragma unroll
+          for (int a = 0; a < 3; ++a)
+          {
+            px[k][a] = xs[3 * i + a];
+            pu[k][a] = DIAG ? 0.0 : us[3 * i + a];
+          }
+        }
+        mf_el_element_p1<DIAG>(px, pu, pe);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+          for (int a = 0; a < 3; ++a)
+            ye[a][k] = pe[k][a];
+        rounds(add3);
+      }
+      else
+      {
+        constexpr int NQ = MfTab<ND>::NQ;
+        double Kd[10];
+#pragma unroll
+        for (int t = 0; t < 10; ++t)
+          Kd[t] = A.geom[(b * 10 + t) * A.nc + e];
+        if constexpr (DIAG)
+        {
+          mf_el_diag_pk<ND>(tabT_s, Kd, ye);
+          rounds(add3);
+        }
+        else
+        {
+          double g[3][NQ][3];
+#pragma unroll
+          for (int c = 0; c < 3; ++c)
+          {
+            double ue[ND];
+#pragma unroll
+            for (int j = 0; j < ND; ++j)
+            {
+              if constexpr (GU)
+                ue[j] = A.u[3ll * A.gid[(b * ND + j) * A.nc + e] + c];
+              else
+                ue[j] = us[3 * (int)((iw[j >> 1] >> (16 * (j & 1))) & 0xffff) + c];
+            }
+            mf_el_modes<ND>(tab_s, ue, g[c]);
+          }
+          mf_el_stress<NQ>(Kd, g);
+#pragma unroll
+          for (int c = 0; c < 3; ++c)
+            mf_el_accumulate<ND>(tabT_s, g[c], ye[c]);
+          rounds(add3);
+        }
+      }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __syncthreads();
+    // nodes interior to the block: final values (a constrained scalar dof: 0, the diagonal 1); shared ones: partial sums
+    for (int d = tid; d < n_int; d += T)
+    {
+      const int32_t g = A.dof_ids[dof_off + d];
+      const int fl = A.dof_flag[dof_off + d];
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+      {
+        const double v = ((fl >> c) & 1) ? (DIAG ? 1.0 : 0.0) : ys[3 * d + c];
+        A.y[3ll * g + c] = v;
+        if constexpr (!DIAG)
+          dot += v * (GU ? A.u[3ll * g + c] : us[3 * d + c]);
+      }
+    }
+    for (int d = tid; d < n_sh; d += T)
+    {
+      const int64_t p = A.pslot[part_off + d];
+      A.ypart[3 * p + 0] = ys[3 * (n_int + d) + 0];
+      A.ypart[3 * p + 1] = ys[3 * (n_int + d) + 1];
+      A.ypart[3 * p + 2] = ys[3 * (n_int + d) + 2];
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __syncthreads();
+  }
+  if (A.partials)
+  {
+    const double t = block_reduce_sum(dot, red);
+    if (tid == 0)
+      A.partials[blockIdx.x] = t;
+  }
+}
+
+// the nodes shared between blocks, three scalar dofs each: partial sums added in ascending block order
+__global__ __launch_bounds__(256) void k_mf_finish3(const int32_t* __restrict__ sh_dof, const int32_t* __restrict__ sh_off,
+                                                    const uint8_t* __restrict__ sh_flag, int64_t nshared,
+                                                    const double* __restrict__ ypart, const double* __restrict__ u,
+                                                    double* __restrict__ y, double* __restrict__ partials,
+                                                    const int* __restrict__ stop, double fixed_value)
+{
+  if (stop && *stop)
+    return;
+  __shared__ double red[4];
+  double dot = 0.0;
+  for (int64_t kk = blockIdx.x * 256ll + threadIdx.x; kk < 3 * nshared; kk += gridDim.x * 256ll)
+  {
+    const int64_t k = kk / 3;
+    const int c = (int)(kk - 3 * k);
+    const int64_t row = 3ll * sh_dof[k] + c;
+    const int p0 = sh_off[k], p1 = sh_off[k + 1];
+    double s = ypart[3ll * p0 + c];
+    for (int p = p0 + 1; p < p1; ++p)
+      s += ypart[3ll * p + c];
+    if ((sh_flag[k] >> c) & 1)
+      s = fixed_value;
+    y[row] = s;
+    dot += s * (u ? u[row] : 0.0);
+  }
+  if (partials)
+  {
+    const double t = block_reduce_sum(dot, red);
+    if (threadIdx.x == 0)
+      partials[blockIdx.x] = t;
+  }
+}
+
 struct SegOffset
 {
   unsigned seg;
@@ -846,18 +1120,21 @@ unsigned bits_for(uint64_t v)
   return b;
 }
 
-int lds_bytes(int nd, int nloc_cap) { return (nd == 4 ? 40 : (nd == 20 ? 8 : 16)) * nloc_cap; }
+int lds_per_dof(int nd, int bs) { return bs == 3 ? (nd == 4 ? 72 : (nd == 20 ? 24 : 48)) : (nd == 4 ? 40 : (nd == 20 ? 8 : 16)); }
+int lds_bytes(int nd, int nloc_cap, int bs = 1) { return lds_per_dof(nd, bs) * nloc_cap; }
 int lds_bytes_f32(int nd, int nloc_cap) { return (nd == 4 ? 20 : (nd == 20 ? 4 : 8)) * nloc_cap; }
 
 // what one action addresses with values of vb bytes: the per-cell streams, the block lists (ids, flags, coordinates), u
 // gathered and y written per list entry, the partial sums out and back, the shared dofs' finish
+// (block size 3: ten geometry values per cell where Poisson reads six, three values of u and y per list entry)
 int64_t action_bytes(const MfPlan& M, int64_t vb)
 {
   const int nd = M.nd;
   const int64_t total = M.nblocks * M.nc, nu = M.nu;
-  return total * (4ll * M.ndw + 4ll * M.nrw + (nd == 4 ? 0 : 6 * vb) + (nd == 20 ? 4 * nd + vb * nd : 0))
-         + nu * (nd == 20 ? 0 : 4 + 1 + vb + (nd == 4 ? 3 * vb : 0)) + (nd == 20 ? (nu - M.nslots) * (4 + 1 + vb) : 0)
-         + (nu - M.nslots) * vb + M.nslots * (vb + vb + 4) + M.nshared * (4 + 4 + 1 + vb + vb)
+  const int64_t uv = vb * M.bs, ng = M.bs == 3 ? 10 : 6;
+  return total * (4ll * M.ndw + 4ll * M.nrw + (nd == 4 ? 0 : ng * vb) + (nd == 20 ? 4 * nd + uv * nd : 0))
+         + nu * (nd == 20 ? 0 : 4 + 1 + uv + (nd == 4 ? 3 * vb : 0)) + (nd == 20 ? (nu - M.nslots) * (4 + 1 + uv) : 0)
+         + (nu - M.nslots) * uv + M.nslots * (uv + uv + 4) + M.nshared * (4 + 4 + 1 + uv + uv)
          + M.nblocks * (MF_HDR * 4 + M.nsb * M.nrw * 4);
 }
 
@@ -874,6 +1151,7 @@ int plan_attempt(zzz_ctx* ctx, int nc, int T, int nloc_limit, bool* retry)
   if (total * nd > (int64_t)INT32_MAX - 1024 || nb >= (1ll << 27))
     return fail(ctx, ZZZ_ERR_LIMIT, "matrix-free plan: %lld incidences exceed int32: use more parts", (long long)(total * nd));
   M.nd = nd;
+  M.bs = ctx->bs;
   M.nc = nc;
   M.threads = T;
   M.nsb = nsb;
@@ -1029,7 +1307,7 @@ int plan_attempt(zzz_ctx* ctx, int nc, int T, int nloc_limit, bool* retry)
   ZZZ_HIP(ctx, sh_key_s.alloc((size_t)nu));
   ZZZ_HIP(ctx, sh_val.alloc((size_t)nu));
   ZZZ_HIP(ctx, sh_val_s.alloc((size_t)nu));
-  hipLaunchKernelGGL(k_mf_lists, dim3(grid_for(nu)), dim3(256), 0, s, key2s.p, val2s.p, nu, M.hdr.p, ctx->bc.p,
+  hipLaunchKernelGGL(k_mf_lists, dim3(grid_for(nu)), dim3(256), 0, s, key2s.p, val2s.p, nu, M.hdr.p, ctx->bc.p, ctx->bs,
                      nd == 4 ? ctx->xq : (const double*)nullptr, M.dof_ids.p, M.dof_flag.p, nd == 4 ? M.xyz.p : (double*)nullptr,
                      loc_of.p, sh_key.p, sh_val.p);
 
@@ -1074,10 +1352,10 @@ int plan_attempt(zzz_ctx* ctx, int nc, int T, int nloc_limit, bool* retry)
     ZZZ_HIP(ctx, M.sh_slot.alloc((size_t)M.nslots));
     ZZZ_HIP(ctx, M.sh_flag.alloc((size_t)ns));
     hipLaunchKernelGGL(k_mf_sh_fill, dim3(grid_for(M.nslots + 1)), dim3(256), 0, s, sh_key_s.p, sh_val_s.p, f2.p, u2.p, M.nslots,
-                       ctx->bc.p, M.sh_dof.p, M.sh_off.p, M.sh_flag.p, M.sh_slot.p, (int64_t)ns);
+                       ctx->bc.p, ctx->bs, M.sh_dof.p, M.sh_off.p, M.sh_flag.p, M.sh_slot.p, (int64_t)ns);
     ZZZ_HIP(ctx, hipStreamSynchronize(s));
   }
-  ZZZ_HIP(ctx, M.ypart.alloc((size_t)std::max<int64_t>(M.nslots, 1)));
+  ZZZ_HIP(ctx, M.ypart.alloc((size_t)std::max<int64_t>(M.nslots, 1) * (size_t)ctx->bs));
 
   // 6. P2/P3: geometry factors per cell, the factorised reference tables
   if (nd != 4)
@@ -1091,8 +1369,11 @@ int plan_attempt(zzz_ctx* ctx, int nc, int T, int nloc_limit, bool* retry)
       ZZZ_HIP(ctx, M.gid.alloc((size_t)(total * nd)));
       hipLaunchKernelGGL(k_mf_gid, dim3(grid_for(total * nd)), dim3(256), 0, s, M.mf_cell.p, ctx->cell_dofs.p, nd, nc, total, M.gid.p);
     }
-    ZZZ_HIP(ctx, M.geom.alloc((size_t)(nb * 6 * nc)));
-    hipLaunchKernelGGL(k_mf_geom, dim3(grid_for(total)), dim3(256), 0, s, ctx->x.p, ctx->cell_verts.p, M.mf_cell.p, nc, total, M.geom.p);
+    ZZZ_HIP(ctx, M.geom.alloc((size_t)(nb * (ctx->bs == 3 ? 10 : 6) * nc)));
+    if (ctx->bs == 3)
+      hipLaunchKernelGGL(k_mf_geom_el, dim3(grid_for(total)), dim3(256), 0, s, ctx->x.p, ctx->cell_verts.p, M.mf_cell.p, nc, total, M.geom.p);
+    else
+      hipLaunchKernelGGL(k_mf_geom, dim3(grid_for(total)), dim3(256), 0, s, ctx->x.p, ctx->cell_verts.p, M.mf_cell.p, nc, total, M.geom.p);
   }
   ZZZ_HIP(ctx, hipGetLastError());
   ZZZ_HIP(ctx, hipStreamSynchronize(s));
@@ -1108,8 +1389,8 @@ int mf_plan_build(zzz_ctx* ctx)
   MfPlan& M = ctx->mf;
   M.valid = M.failed = false;
   M.f32_built = false; // (the twins follow the plan)
-  if (ctx->bs != 1)
-    return fail(ctx, ZZZ_ERR_ARG, "the matrix-free operator exists for the Poisson form M only (src/Poisson.py:33)");
+  if (ctx->bs != 1 && ctx->bs != 3)
+    return fail(ctx, ZZZ_ERR_ARG, "the matrix-free operator exists for block sizes 1 (src/Poisson.py:33, form M) and 3 (src/Elasticity.py, form a)");
   if (ctx->order == 0 || ctx->ncells == 0)
     return fail(ctx, ZZZ_ERR_ARG, "matrix-free operator before zzz_dofmap_upload");
   if (int rc = ensure_p1_coords(ctx))
@@ -1118,12 +1399,17 @@ int mf_plan_build(zzz_ctx* ctx)
   // defaults (measured): workgroup size and cells per block; ZZZ_MF_T / ZZZ_MF_NC override them
   // (tools/mf_sweep.sh, MI355X: P1 10 M dofs 0.70 ms at 2048 x 256 against 0.84 at 4096 x 512 and 1.30 at 8192 x 512 --
   // small blocks share more dofs but keep five workgroups on a CU; P3 6.2 M dofs 0.30 ms at 768 x 256, 0.32 at 512, 0.38 at 1024)
+  // block size 3: sized from the LDS a node costs there -- 72 / 48 / 24 B -- so that a block stays within the 64 KiB budget
+  // below and two to four workgroups share a CU (tools/mf_el_sweep.sh, MI355X, DESIGN.md 4f: P1 4 M dofs 0.247 ms at 1024 x 256,
+  // 0.241 at 2048 x 256; P2 2 M dofs 0.068 at 512 x 256; P3 1 M dofs 0.155 at 256 x 256, 0.138 at 128 x 128 in one session)
+  const bool el = ctx->bs == 3;
   int T = 256;
-  int nc = nd == 4 ? 2048 : (nd == 10 ? 1024 : 768);
+  int nc = el ? (nd == 4 ? 1024 : (nd == 10 ? 512 : 256)) : (nd == 4 ? 2048 : (nd == 10 ? 1024 : 768));
   if (const char* e = getenv("ZZZ_MF_T"))
   {
     const int v = atoi(e);
-    if (v == 128 || v == 256 || v == 512 || v == 1024)
+    // (block size 3 has no instantiation for 1024 threads: 128 registers per lane do not hold a P2 element without scratch)
+    if (v == 128 || v == 256 || v == 512 || (v == 1024 && !el))
       T = v;
   }
   if (const char* e = getenv("ZZZ_MF_NC"))
@@ -1137,8 +1423,8 @@ int mf_plan_build(zzz_ctx* ctx)
   while (nc / 2 >= T && (nc / 2) % T == 0 && (nd / 2 + (nd + 3) / 4) * 4 * nc > 150 * 1024)
     nc /= 2;
   // LDS budget per workgroup (160 KiB per CU)
-  const int lds_kb = nd == 4 ? 40 : 64;
-  const int nloc_limit = std::min(65535, lds_kb * 1024 / (nd == 4 ? 40 : (nd == 20 ? 8 : 16)));
+  const int lds_kb = nd == 4 && !el ? 40 : 64;
+  const int nloc_limit = std::min(65535, lds_kb * 1024 / lds_per_dof(nd, ctx->bs));
   for (;;)
   {
     bool retry = false;
@@ -1147,7 +1433,8 @@ int mf_plan_build(zzz_ctx* ctx)
     if (!retry)
       break;
     if (nc / 2 < T || (nc / 2) % T)
-      return fail(ctx, ZZZ_ERR_LIMIT, "matrix-free plan: a block of %d cells touches more dofs than LDS holds", nc);
+      return fail(ctx, ZZZ_ERR_LIMIT, "matrix-free plan: a block of %d cells touches more dofs than LDS holds (%d B per dof, %d KiB)", nc,
+                  lds_per_dof(nd, ctx->bs), lds_kb);
     nc /= 2;
   }
   M.valid = true;
@@ -1164,6 +1451,19 @@ static int mf_launch(zzz_ctx* ctx, const MfArgs<R>& A, int grid, int lds)
     attr_lds[ctx->device & 15] = lds;
   }
   hipLaunchKernelGGL((k_mf_action<ND, T, DIAG, R>), dim3(grid), dim3(T), lds, ctx->stream, A);
+  return ZZZ_OK;
+}
+
+template <int ND, int T, bool DIAG>
+static int mf_launch3(zzz_ctx* ctx, const MfArgs<double>& A, int grid, int lds)
+{
+  static int attr_lds[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  if (lds > 48 * 1024 && lds > attr_lds[ctx->device & 15])
+  {
+    ZZZ_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_mf_action3<ND, T, DIAG>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    attr_lds[ctx->device & 15] = lds;
+  }
+  hipLaunchKernelGGL((k_mf_action3<ND, T, DIAG>), dim3(grid), dim3(T), lds, ctx->stream, A);
   return ZZZ_OK;
 }
 
@@ -1430,7 +1730,9 @@ static int mf_run(zzz_ctx* ctx, bool diag, const R* u, R* y, double* partials, i
   MfPlan& M = ctx->mf;
   if (!M.valid)
     return fail(ctx, ZZZ_ERR_ARG, "matrix-free plan missing");
-  const int lds = F32 ? lds_bytes_f32(M.nd, M.nloc_max) : lds_bytes(M.nd, M.nloc_max);
+  if (M.bs != ctx->bs || (F32 && M.bs != 1))
+    return fail(ctx, ZZZ_ERR_ARG, "matrix-free plan of another block size");
+  const int lds = F32 ? lds_bytes_f32(M.nd, M.nloc_max) : lds_bytes(M.nd, M.nloc_max, M.bs);
   // persistent workgroups: as many as fit a CU by LDS and threads, XCD-aware walk over the blocks
   const int per_cu = mf_per_cu(M, lds);
   int grid = (int)std::min<int64_t>(256ll * per_cu, (M.nblocks + 7) / 8 * 8);
@@ -1473,6 +1775,31 @@ static int mf_run(zzz_ctx* ctx, bool diag, const R* u, R* y, double* partials, i
                     : M.threads == 256 ? mf_launch<ND_, 256, DG_, R>(ctx, A, grid, lds)                                   \
                                        : M.threads == 512 ? mf_launch<ND_, 512, DG_, R>(ctx, A, grid, lds)                \
                                                           : mf_launch<ND_, 1024, DG_, R>(ctx, A, grid, lds))
+  if constexpr (!F32)
+    if (M.bs == 3)
+    {
+#define ZZZ_MF_T3(ND_, DG_)                                                                                             \
+  (M.threads == 128 ? mf_launch3<ND_, 128, DG_>(ctx, A, grid, lds)                                                        \
+                    : M.threads == 256 ? mf_launch3<ND_, 256, DG_>(ctx, A, grid, lds)                                     \
+                                       : mf_launch3<ND_, 512, DG_>(ctx, A, grid, lds))
+      if (M.nd == 4)
+        rc = diag ? ZZZ_MF_T3(4, true) : ZZZ_MF_T3(4, false);
+      else if (M.nd == 10)
+        rc = diag ? ZZZ_MF_T3(10, true) : ZZZ_MF_T3(10, false);
+      else
+        rc = diag ? ZZZ_MF_T3(20, true) : ZZZ_MF_T3(20, false);
+#undef ZZZ_MF_T3
+      if (rc)
+        return rc;
+      const int gf3 = (int)std::min<int64_t>(std::max<int64_t>((3 * M.nshared + 255) / 256, 1), 2048);
+      if (M.nshared > 0)
+        hipLaunchKernelGGL(k_mf_finish3, dim3(gf3), dim3(256), 0, ctx->stream, M.sh_dof.p, M.sh_off.p, M.sh_flag.p, M.nshared, A.ypart, u,
+                           y, partials ? partials + grid : nullptr, A.stop, diag ? 1.0 : 0.0);
+      if (npartials)
+        *npartials = grid + (M.nshared > 0 ? gf3 : 0);
+      ZZZ_HIP(ctx, hipGetLastError());
+      return ZZZ_OK;
+    }
   if constexpr (F32)
   {
     // (the diagonal stays double)

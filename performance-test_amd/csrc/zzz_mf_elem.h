@@ -199,6 +199,197 @@ ZZZ_HD inline void mf_element_p1(const MfPoint<R>& p0, const MfPoint<R>& p1, con
   }
 }
 
+// ---- block size 3: form a of src/Elasticity.py, inner(sigma(u), eps(v)) dx, per cell, never stored -------------------------
+// sigma = mu (H + H^T) + lambda tr(H) I with H the physical gradient of u; since sigma is symmetric, inner(sigma, eps(v)) =
+// inner(sigma, grad v).  Double only (the float path keeps its block-size-3 refusal).
+constexpr double MF_EL_E = 1.0e6, MF_EL_NU = 0.3; // src/Elasticity.py:12-15
+constexpr double MF_EL_MU = MF_EL_E / (2.0 * (1.0 + MF_EL_NU));
+constexpr double MF_EL_LAMBDA = MF_EL_E * MF_EL_NU / ((1.0 + MF_EL_NU) * (1.0 - 2.0 * MF_EL_NU));
+
+// sg = mu (H + H^T) + lambda tr(H) I
+ZZZ_HD inline void mf_el_sigma(const double (&H)[3][3], double (&sg)[3][3])
+{
+#pragma clang fp contract(fast)
+  const double lt = MF_EL_LAMBDA * (H[0][0] + H[1][1] + H[2][2]);
+  for (int c = 0; c < 3; ++c)
+    for (int d = 0; d < 3; ++d)
+      sg[c][d] = MF_EL_MU * (H[c][d] + H[d][c]) + (c == d ? lt : 0.0);
+}
+
+// P2/P3 geometry record: K = J^-1 (K[al][d] = dX_al / dx_d at Kd[3 al + d]) and |det J| at Kd[9], in double as mf_cell_geom
+ZZZ_HD inline void mf_cell_geom_el(const double (&p)[4][3], double (&Kd)[10])
+{
+  double J[3][3];
+  for (int a = 0; a < 3; ++a)
+    for (int al = 0; al < 3; ++al)
+      J[a][al] = p[al + 1][a] - p[0][a];
+  double C[3][3];
+  C[0][0] = J[1][1] * J[2][2] - J[1][2] * J[2][1];
+  C[0][1] = J[0][2] * J[2][1] - J[0][1] * J[2][2];
+  C[0][2] = J[0][1] * J[1][2] - J[0][2] * J[1][1];
+  C[1][0] = J[1][2] * J[2][0] - J[1][0] * J[2][2];
+  C[1][1] = J[0][0] * J[2][2] - J[0][2] * J[2][0];
+  C[1][2] = J[0][2] * J[1][0] - J[0][0] * J[1][2];
+  C[2][0] = J[1][0] * J[2][1] - J[1][1] * J[2][0];
+  C[2][1] = J[0][1] * J[2][0] - J[0][0] * J[2][1];
+  C[2][2] = J[0][0] * J[1][1] - J[0][1] * J[1][0];
+  const double det = J[0][0] * C[0][0] + J[0][1] * C[1][0] + J[0][2] * C[2][0];
+  const double inv = 1.0 / det;
+  for (int al = 0; al < 3; ++al)
+    for (int d = 0; d < 3; ++d)
+      Kd[3 * al + d] = C[al][d] * inv;
+  Kd[9] = std::fabs(det);
+}
+
+// The factorised element of block size 3 in three phases, so that the caller never holds u_e and y_e of the three components
+// at once (2 x 60 doubles at P3): with S^ab_ij = sum_q D_a[q][i] D_b[q][j], for every mode q
+//   1. g[q][a] = D_a[q][:] . u_e^c                      (mf_el_modes, one component c at a time: u_e^c alone is live)
+//   2. H[c][d] = sum_a g[c][q][a] K[a][d];  sigma(H);  T[c][q][a] = |det J| sum_d sigma[c][d] K[a][d]   (mf_el_stress, in place)
+//   3. y_e^c[j] = sum_q sum_a D_a[q][j] T[c][q][a]      (mf_el_accumulate, one component at a time)
+template <int ND>
+ZZZ_HD inline void mf_el_modes(const double* __restrict__ tab, const double (&ue)[ND], double (&g)[MfTab<ND>::NQ][3])
+{
+#pragma clang fp contract(fast)
+  constexpr int NQ = MfTab<ND>::NQ;
+#pragma unroll
+  for (int q = 0; q < NQ; ++q)
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+    {
+      double acc = 0.0;
+#pragma unroll
+      for (int j = 0; j < ND; ++j)
+        if (MfTab<ND>::nz(a, q, j))
+          acc += tab[(a * NQ + q) * ND + j] * ue[j];
+      g[q][a] = acc;
+    }
+}
+template <int NQ>
+ZZZ_HD inline void mf_el_stress(const double (&Kd)[10], double (&g)[3][NQ][3])
+{
+#pragma clang fp contract(fast)
+#pragma unroll
+  for (int q = 0; q < NQ; ++q)
+  {
+    double H[3][3], sg[3][3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+      for (int d = 0; d < 3; ++d)
+        H[c][d] = g[c][q][0] * Kd[d] + g[c][q][1] * Kd[3 + d] + g[c][q][2] * Kd[6 + d];
+    mf_el_sigma(H, sg);
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+      for (int a = 0; a < 3; ++a)
+        g[c][q][a] = Kd[9] * (sg[c][0] * Kd[3 * a] + sg[c][1] * Kd[3 * a + 1] + sg[c][2] * Kd[3 * a + 2]);
+  }
+}
+template <int ND>
+ZZZ_HD inline void mf_el_accumulate(const double* __restrict__ tabT, const double (&t)[MfTab<ND>::NQ][3], double (&ye)[ND])
+{
+#pragma clang fp contract(fast)
+  constexpr int NQ = MfTab<ND>::NQ;
+#pragma unroll
+  for (int j = 0; j < ND; ++j)
+    ye[j] = 0.0;
+#pragma unroll
+  for (int q = 0; q < NQ; ++q)
+#pragma unroll
+    for (int j = 0; j < ND; ++j)
+    {
+      if (MfTab<ND>::nz(0, q, j))
+        ye[j] += tabT[(q * ND + j) * 3 + 0] * t[q][0];
+      if (MfTab<ND>::nz(1, q, j))
+        ye[j] += tabT[(q * ND + j) * 3 + 1] * t[q][1];
+      if (MfTab<ND>::nz(2, q, j))
+        ye[j] += tabT[(q * ND + j) * 3 + 2] * t[q][2];
+    }
+}
+// the element matrix's diagonal: for (j, c) sum_q d^T M^cc d, d_a = D_a[q][j],
+// M^cc_ab = |det J| (mu (K K^T)_ab + (mu + lambda) K[a][c] K[b][c]):  with v = K^T d,  |det J| (mu |v|^2 + (mu + lambda) v_c^2)
+template <int ND>
+ZZZ_HD inline void mf_el_diag_pk(const double* __restrict__ tabT, const double (&Kd)[10], double (&ye)[3][ND])
+{
+#pragma clang fp contract(fast)
+  constexpr int NQ = MfTab<ND>::NQ;
+#pragma unroll
+  for (int j = 0; j < ND; ++j)
+  {
+    double vv = 0.0, v2[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+    for (int q = 0; q < NQ; ++q)
+    {
+      if (!(MfTab<ND>::nz(0, q, j) || MfTab<ND>::nz(1, q, j) || MfTab<ND>::nz(2, q, j)))
+        continue;
+      const double d0 = tabT[(q * ND + j) * 3 + 0], d1 = tabT[(q * ND + j) * 3 + 1], d2 = tabT[(q * ND + j) * 3 + 2];
+#pragma unroll
+      for (int x = 0; x < 3; ++x)
+      {
+        const double v = d0 * Kd[x] + d1 * Kd[3 + x] + d2 * Kd[6 + x];
+        vv += v * v;
+        v2[x] += v * v;
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      ye[c][j] = Kd[9] * (MF_EL_MU * vv + (MF_EL_MU + MF_EL_LAMBDA) * v2[c]);
+  }
+}
+
+// P1 from the vertex coordinates x[k][:] and values u[k][c]: cofactors and one division; H is constant on the cell.
+// With H' = (u_(al+1) - u_0) C (the gradient times det J) and sigma linear:  y^c_(al+1) = sum_d sigma(H')[c][d] C[al][d] / (6 |det J|),
+// y^c_0 = -(their sum).  DIAG: (j, c) -> (mu |C_j|^2 + (mu + lambda) C_j[c]^2) / (6 |det J|), C_0 = -(C_1 + C_2 + C_3).
+template <bool DIAG>
+ZZZ_HD inline void mf_el_element_p1(const double (&x)[4][3], const double (&u)[4][3], double (&ye)[4][3])
+{
+#pragma clang fp contract(fast)
+  const double J00 = x[1][0] - x[0][0], J01 = x[2][0] - x[0][0], J02 = x[3][0] - x[0][0];
+  const double J10 = x[1][1] - x[0][1], J11 = x[2][1] - x[0][1], J12 = x[3][1] - x[0][1];
+  const double J20 = x[1][2] - x[0][2], J21 = x[2][2] - x[0][2], J22 = x[3][2] - x[0][2];
+  double C[4][3];
+  C[1][0] = J11 * J22 - J12 * J21, C[1][1] = J02 * J21 - J01 * J22, C[1][2] = J01 * J12 - J02 * J11;
+  C[2][0] = J12 * J20 - J10 * J22, C[2][1] = J00 * J22 - J02 * J20, C[2][2] = J02 * J10 - J00 * J12;
+  C[3][0] = J10 * J21 - J11 * J20, C[3][1] = J01 * J20 - J00 * J21, C[3][2] = J00 * J11 - J01 * J10;
+  const double det = J00 * C[1][0] + J01 * C[2][0] + J02 * C[3][0];
+  const double sc = 1.0 / (6.0 * std::fabs(det));
+  if constexpr (DIAG)
+  {
+#pragma unroll
+    for (int d = 0; d < 3; ++d)
+      C[0][d] = -(C[1][d] + C[2][d] + C[3][d]);
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+    {
+      const double cc = C[k][0] * C[k][0] + C[k][1] * C[k][1] + C[k][2] * C[k][2];
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        ye[k][c] = (MF_EL_MU * cc + (MF_EL_MU + MF_EL_LAMBDA) * C[k][c] * C[k][c]) * sc;
+    }
+  }
+  else
+  {
+    double H[3][3], sg[3][3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+    {
+      const double d1 = u[1][c] - u[0][c], d2 = u[2][c] - u[0][c], d3 = u[3][c] - u[0][c];
+#pragma unroll
+      for (int d = 0; d < 3; ++d)
+        H[c][d] = d1 * C[1][d] + d2 * C[2][d] + d3 * C[3][d];
+    }
+    mf_el_sigma(H, sg);
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+    {
+#pragma unroll
+      for (int k = 1; k < 4; ++k)
+        ye[k][c] = (sg[c][0] * C[k][0] + sg[c][1] * C[k][1] + sg[c][2] * C[k][2]) * sc;
+      ye[0][c] = -(ye[1][c] + ye[2][c] + ye[3][c]);
+    }
+  }
+}
+
 // ---- P1 in float: how well an origin serves a cell, which origin a block takes, or none ----------------------------------
 // Column by column (column al = edge p_(al+1) - p_0), every entry of the Jacobian formed in float from the rounded relative
 // coordinates is compared with the double Jacobian's, against the cell's extent along that entry's axis (per axis: an

@@ -114,6 +114,10 @@ struct Options
   // cgpoisson only: the reference's scalar is PetscScalar (src/cgpoisson_problem.cpp:28); "float32" runs the action and
   // linalg::cg as a single-precision PETSc build would (zzz_cg_solve_f32), one GPU
   std::string scalar_type = "float64";
+  // cgelasticity only: "linalg" = linalg::cg(u, b, action, 100, 1e-6) as cgpoisson runs it; "ksp" = KSPCG on the matrix-free
+  // operator with the options database (-pc_type jacobi | none, -ksp_rtol, -ksp_max_it, the norm options)
+  std::string cg_solver = "linalg";
+  bool have_cg_solver = false;
   // u0 == bc_value at every constrained dof (all components for elasticity); absent = 0 = the reference's u0: no upload
   bool have_bc_value = false;
   double bc_value = 0.0;
@@ -138,7 +142,8 @@ void usage()
   // boost::program_options layout of the reference's help (src/main.cpp:84-89)
   std::cout << "Allowed options:\n"
                "  -h [ --help ]                   print usage message\n"
-               "  --problem_type arg (=poisson)   problem (poisson, cgpoisson, or elasticity)\n"
+               "  --problem_type arg (=poisson)   problem (poisson, cgpoisson, elasticity, or cgelasticity: elasticity on the\n"
+               "                                  matrix-free operator, what cgpoisson is to poisson -- no matrix)\n"
                "  --mesh_type arg (=cube)         mesh (cube or unstructured)\n"
                "  --memory_profiling              turn on memory logging\n"
                "  --subcomm_partition             Use sub-communicator for partitioning\n"
@@ -154,6 +159,9 @@ void usage()
                "                                  operator, Jacobi from the element matrices' diagonals; no matrix)\n"
                "  --scalar_type arg (=float64)    float64 | float32 (cgpoisson on one GPU: action and linalg::cg in single\n"
                "                                  precision, as the reference built on a single-precision PETSc)\n"
+               "  --cg_solver arg (=linalg)       cgelasticity only: linalg (linalg::cg, 100 iterations, rtol 1e-6, as cgpoisson) |\n"
+               "                                  ksp (KSPCG on the matrix-free operator: -pc_type jacobi | none, -ksp_rtol,\n"
+               "                                  -ksp_max_it, -ksp_norm_type)\n"
                "  --bc_value arg (=0)             value of u0 at every Dirichlet dof (the reference's u0 is 0); non-zero: the\n"
                "                                  vector assembly lifts it (apply_lifting, bc->set)\n"
                "PETSc-style solver options honoured: -ksp_type {cg,pipecg} -pc_type {jacobi,none,chebyshev_jacobi,mg,pmg} -ksp_rtol -ksp_atol\n"
@@ -212,6 +220,11 @@ Options parse(int argc, char** argv)
         o.op = value(i, arg, key);
       else if (key == "scalar_type")
         o.scalar_type = value(i, arg, key);
+      else if (key == "cg_solver")
+      {
+        o.cg_solver = value(i, arg, key);
+        o.have_cg_solver = true;
+      }
       else if (key == "bc_value")
       {
         o.bc_value = std::stod(value(i, arg, key));
@@ -382,9 +395,14 @@ void run_rank(Shared& S, std::barrier<>& bar, int rank)
     bar.arrive_and_wait();
   };
 
-  const int problem = o.problem_type == "elasticity" ? ZZZH_ELASTICITY : ZZZH_POISSON;
+  // cgelasticity: the mesh, space, Dirichlet set and right-hand side of elasticity (src/elasticity_problem.cpp:101-176), the
+  // solve of cgpoisson (or, --cg_solver ksp, KSPCG) on the matrix-free operator of form a: no matrix
+  const bool cgelasticity = o.problem_type == "cgelasticity";
+  const int problem = o.problem_type == "elasticity" || cgelasticity ? ZZZH_ELASTICITY : ZZZH_POISSON;
   const int form = problem == ZZZH_ELASTICITY ? ZZZ_FORM_ELASTICITY : ZZZ_FORM_POISSON;
   const bool cgpoisson = o.problem_type == "cgpoisson";
+  const bool cg_problem = cgpoisson || cgelasticity;                           // no matrix, the plan inside ZZZ Solve
+  const bool linalg_cg = cgpoisson || (cgelasticity && o.cg_solver == "linalg"); // linalg::cg, the Gdof/s line
   const bool matfree_op = o.op == "matfree";
 
   // The structured feed (mesh, function space, Dirichlet set, coefficients, halo plan) is generated
@@ -465,10 +483,10 @@ void run_rank(Shared& S, std::barrier<>& bar, int rank)
   if (matfree_op)
     // no matrix: what takes its place is the plan of the matrix-free kernel (the diagonal is PCSetUp's, in ZZZ Solve)
     phase("ZZZ Assemble matrix", [&] { ZCK(ctx, zzz_matfree_setup(ctx)); });
-  else if (!cgpoisson)
+  else if (!cg_problem)
     phase("ZZZ Assemble matrix", [&] { ZCK(ctx, zzz_assemble_matrix(ctx, form)); });
   phase("ZZZ Assemble vector", [&] { ZCK(ctx, zzz_assemble_vector(ctx, form)); });
-  if (problem == ZZZH_ELASTICITY)
+  if (problem == ZZZH_ELASTICITY && !cgelasticity)
     // build_near_nullspace (src/elasticity_problem.cpp:233-244): six orthonormalised rigid-body modes; GAMG would consume
     // them (MatSetNearNullSpace), Jacobi-CG does not
     phase("ZZZ Create near-nullspace", [&] {
@@ -505,7 +523,7 @@ void run_rank(Shared& S, std::barrier<>& bar, int rank)
 
   zzz_solver_opts so;
   std::memset(&so, 0, sizeof(so));
-  if (cgpoisson)
+  if (linalg_cg)
   {
     // linalg::cg(*u.x(), b, action, 100, 1e-6), src/cgpoisson_problem.cpp:233
     so.variant = ZZZ_CG_CGH;
@@ -528,7 +546,7 @@ void run_rank(Shared& S, std::barrier<>& bar, int rank)
     so.norm = o.ksp_norm_type == "unpreconditioned" ? ZZZ_NORM_UNPRECONDITIONED
               : o.ksp_norm_type == "natural"        ? ZZZ_NORM_NATURAL
                                                     : ZZZ_NORM_PRECONDITIONED;
-    so.op = matfree_op ? ZZZ_OP_MATFREE : ZZZ_OP_CSR;
+    so.op = matfree_op || cgelasticity ? ZZZ_OP_MATFREE : ZZZ_OP_CSR;
     so.max_it = o.ksp_max_it;
     so.rtol = o.ksp_rtol;
     so.atol = o.ksp_atol;
@@ -539,21 +557,34 @@ void run_rank(Shared& S, std::barrier<>& bar, int rank)
   double solve_s = 0, cg_s = 0;
   {
     Timer ts("ZZZ Solve");
-    if (!failed)
+    // cgpoisson: what solver_function sets up before it calls linalg::cg -- coefficient storage of `un`, the
+    // Scatterer and its buffers (src/cgpoisson_problem.cpp:181-190) -- is inside ZZZ Solve and outside the
+    // timer of the Gdof/s line (:232-235); here that is the plan of the matrix-free kernel.  Every rank finishes its plan
+    // before any rank starts to iterate: the plan build frees scratch buffers, hipFree waits for every kernel on the device,
+    // and with several ranks on one GPU a rank already polling its all-reduce mailbox would wait for this one in turn
+    if (cg_problem)
     {
-      try
+      if (!failed)
       {
-        double rn[2] = {0, 0};
-        // cgpoisson: what solver_function sets up before it calls linalg::cg -- coefficient storage of `un`, the
-        // Scatterer and its buffers (src/cgpoisson_problem.cpp:181-190) -- is inside ZZZ Solve and outside the
-        // timer of the Gdof/s line (:232-235); here that is the plan of the matrix-free kernel
-        if (cgpoisson)
+        try
         {
           Timer tplan("plan");
           ZCK(ctx, zzz_matfree_setup(ctx));
           ZCK(ctx, zzz_sync(ctx));
           S.tplan[rank] = tplan.stop();
         }
+        catch (const std::exception& e)
+        {
+          rank_failed(e);
+        }
+      }
+      bar.arrive_and_wait();
+    }
+    if (!failed)
+    {
+      try
+      {
+        double rn[2] = {0, 0};
         Timer tcg("cg");
         if (o.scalar_type == "float32")
           ZCK(ctx, zzz_cg_solve_f32(ctx, &so, &S.iters[rank], rn));
@@ -588,11 +619,12 @@ void run_rank(Shared& S, std::barrier<>& bar, int rank)
       g_timers.add("ZZZ Solve", solve_s);
     bar.arrive_and_wait();
   }
-  if (root && cgpoisson && !failed)
+  if (root && cg_problem && !failed)
   {
     // src/cgpoisson_problem.cpp:236-241
     const double gdofs = (S.iters[0] * (double)S.num_dofs) / cg_s / 1e9;
-    std::cout << "CG matrix-free action processed: " << gdofs << " Gdof/s\n";
+    if (linalg_cg)
+      std::cout << "CG matrix-free action processed: " << gdofs << " Gdof/s\n";
     // no line of the reference: what the Gdof/s figure leaves out here (the plan is built once per dofmap; ~40 actions' worth)
     std::cout << "CG matrix-free plan set-up (once per dofmap, not in the Gdof/s figure): "
               << *std::max_element(S.tplan.begin(), S.tplan.end()) * 1e3 << " ms\n";
@@ -698,13 +730,31 @@ void solve(int argc, char** argv)
     strong = false;
   else
     throw std::runtime_error("Scaling type '" + o.scaling_type + "` unknown"); // src/main.cpp:115
-  if (o.problem_type != "poisson" && o.problem_type != "cgpoisson" && o.problem_type != "elasticity")
-    throw std::runtime_error("Unknown problem type: " + o.problem_type); // src/main.cpp:170
+  const bool cgel = o.problem_type == "cgelasticity";
+  if (o.problem_type != "poisson" && o.problem_type != "cgpoisson" && o.problem_type != "elasticity" && !cgel)
+    throw std::runtime_error("Unknown problem type: " + o.problem_type + " (poisson, cgpoisson, elasticity or cgelasticity)"); // src/main.cpp:170
+  if (o.cg_solver != "linalg" && o.cg_solver != "ksp")
+    throw std::runtime_error("--cg_solver " + o.cg_solver + ": linalg or ksp");
+  if (o.have_cg_solver && !cgel)
+    throw std::runtime_error("--cg_solver applies to --problem_type cgelasticity only (cgpoisson runs linalg::cg, the other "
+                             "problems a KSP)");
+  if (cgel)
+  {
+    // what the matrix-free operator declines at block size 3 as at 1 (include/zzz_abi.h), said here before any GPU work
+    const char* why = o.op == "matfree" ? "not with --operator matfree (the operator is already matrix-free)"
+                      : o.pc_type == "chebyshev_jacobi" || o.pc_type == "mg" || o.pc_type == "pmg"
+                          ? "-pc_type jacobi or none only (Chebyshev-Jacobi and the multigrid preconditioners need the assembled operator)"
+                      : o.ksp_type == "pipecg"    ? "-ksp_type pipecg needs the assembled operator (--cg_solver ksp runs the classical KSPCG)"
+                      : o.ksp_cg_single_reduction ? "-ksp_cg_single_reduction needs the assembled operator"
+                                                  : nullptr;
+    if (why)
+      throw std::runtime_error("--problem_type cgelasticity: " + std::string(why));
+  }
   if (o.scalar_type != "float64" && o.scalar_type != "float32")
     throw std::runtime_error("--scalar_type " + o.scalar_type + ": float64 or float32");
   if (o.scalar_type == "float32" && o.problem_type != "cgpoisson")
-    throw std::runtime_error("--scalar_type float32 applies to --problem_type cgpoisson only (the assembled path, KSPCG and "
-                             "elasticity run in float64)");
+    throw std::runtime_error("--scalar_type float32 applies to --problem_type cgpoisson only (the assembled path, KSPCG, "
+                             "elasticity and cgelasticity run in float64)");
   if (o.scalar_type == "float32" && o.ngpus != 1)
     throw std::runtime_error("--scalar_type float32: --ngpus 1 only (the float32 halo exchange and all-reduce are not built)");
   if (o.scalar_type == "float32" && o.have_bc_value)
@@ -728,8 +778,8 @@ void solve(int argc, char** argv)
   if (o.op != "assembled" && o.op != "matfree")
     throw std::runtime_error("--operator " + o.op + ": assembled or matfree");
   if (o.op == "matfree" && o.problem_type != "poisson")
-    throw std::runtime_error("--operator matfree applies to --problem_type poisson (cgpoisson is matrix-free already; the "
-                             "matrix-free kernel holds the Poisson form only)");
+    throw std::runtime_error("--operator matfree applies to --problem_type poisson (cgpoisson and cgelasticity are matrix-free "
+                             "already; for elasticity without a matrix use --problem_type cgelasticity)");
   if (o.op == "matfree" && (o.pc_type == "chebyshev_jacobi" || o.ksp_cg_single_reduction))
     throw std::runtime_error("--operator matfree: -pc_type jacobi or none, classical CG");
   if (o.ksp_type == "pipecg" && o.problem_type == "cgpoisson")
@@ -759,7 +809,7 @@ void solve(int argc, char** argv)
   Shared S;
   S.opt = o;
   S.nranks = o.ngpus;
-  const int ndofs_per_node = (o.problem_type == "elasticity") ? 3 : 1; // src/main.cpp:128
+  const int ndofs_per_node = (o.problem_type == "elasticity" || cgel) ? 3 : 1; // src/main.cpp:128
   if (o.mesh_type == "cube")
   {
     zzzh_mesh_size((std::int64_t)o.ndofs, strong ? 1 : 0, S.nranks, ndofs_per_node, (int)o.order, S.dims);
@@ -852,7 +902,7 @@ void solve(int argc, char** argv)
               << o.ksp_rtol << ", absolute=" << o.ksp_atol << "\n  using " << o.ksp_norm_type
               << " norm type for convergence test\n"
               << (o.ksp_cg_single_reduction ? "  using single-reduction variant\n" : "") << "PC Object: type: " << o.pc_type
-              << (o.op == "matfree" ? "\n  linear system matrix: type=shell (matrix-free action, diagonal from the element matrices) on "
+              << (o.op == "matfree" || cgel ? "\n  linear system matrix: type=shell (matrix-free action, diagonal from the element matrices) on "
                                     : "\n  linear system matrix: type=csr (fp64 values, int32 indices) on ")
               << S.nranks << " MI355X\n"
               << (S.nranks > 1 ? (S.p2p_enabled[0] ? "  scalar all-reduces: peer-memory mailboxes; halo: peer-memory window where the plan fits\n"
