@@ -328,7 +328,8 @@ int zzz_spmv_time(zzz_ctx* ctx, int reps, int variant, double* avg_ms);
  * components of a node side by side, and the rows of constrained SCALAR dofs are exactly 0 (a Dirichlet set may constrain
  * one component of a node).  zzz_matfree_setup, _info, _diagonal and zzz_action_time serve both block sizes; a mesh whose
  * smallest cell block touches more nodes than LDS holds is refused with ZZZ_ERR_LIMIT and the context stays usable (the
- * two-pass fallback exists for block size 1 only).  The float entry points keep declining block size 3.
+ * two-pass fallback exists for block size 1 only); zzz_cg_solve(op = ZZZ_OP_MATFREE) returns the same refusal before it
+ * writes u or any other vector of the solve.  The float entry points keep declining block size 3.
  * Non-finite input (zzz_action and zzz_action_f32 alike): an Inf or NaN in x[d] stays with the cells that hold d.  y[d] is
  * non-finite (d unconstrained); rows of constrained dofs are 0 whatever their cells carry; the entries of the other dofs
  * that share a cell with d are non-finite wherever the element arithmetic couples them to d -- all of them for P1, for

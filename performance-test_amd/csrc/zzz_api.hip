@@ -1018,6 +1018,11 @@ int zzz_cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rno
     return fail(ctx, ZZZ_ERR_ARG, "-ksp_cg_single_reduction applies to KSPCG on the assembled operator only");
   if (o->max_it < 0 || o->max_it > (1 << 24))
     return fail(ctx, ZZZ_ERR_ARG, "max_it %d out of range", o->max_it);
+  // block size 3 has no two-pass form behind the plan: a plan that is refused (ZZZ_ERR_LIMIT) ends the solve here, before the
+  // zero initial guess or anything else of the solve is written (with pc = none the refusal used to come after u was cleared)
+  if (o->op == ZZZ_OP_MATFREE && ctx->bs == 3 && !ctx->mf.valid)
+    if (int rc = zzz::mf_plan_build(ctx))
+      return rc;
   return cg_solve(ctx, o, iters, rnorm);
 }
 

@@ -104,12 +104,16 @@ class Case:
 _CASES = {}
 
 
-def case(name, order, problem="poisson"):
-    key = (name, order, problem)
+def case(name, order, problem="poisson", dims=None):
+    """dims: a base of the caller's own instead of the map's or the table's (it enters the keys of _CASES and of the mp pass)"""
+    key = (name, order, problem) if dims is None else (name, order, problem, tuple(dims))
     if key in _CASES:
         return _CASES[key]
-    fmap, dims = MAPS[name] if name in MAPS else F32_MAPS[name]
-    dims = dims if (dims is not None and order == 1) else (ELASTICITY_BASE if problem == "elasticity" else BASE)[order]
+    fmap, own = MAPS[name] if name in MAPS else F32_MAPS[name]
+    if dims is not None:
+        dims = tuple(dims)
+    else:
+        dims = own if (own is not None and order == 1) else (ELASTICITY_BASE if problem == "elasticity" else BASE)[order]
     zo.set_num_threads(1)
     O = zo.Problem(problem, order, *dims)
     rng = np.random.default_rng(SEED + 97 * order)
@@ -119,6 +123,7 @@ def case(name, order, problem="poisson"):
     C = Case()
     C.name, C.order, C.problem, C.dims, C.bs, C.form, C.nblock = name, order, problem, dims, O.bs, O.form, nb
     C.n = nb * O.bs
+    C.key = key
     x0 = np.zeros_like(O.x)
     x0[pv] = O.x  # vertex v is now called pv[v]
     C.x_base = x0
@@ -157,7 +162,7 @@ def reference(C):
     """dict of the mp pass of a case: R, S (unconstrained), Rc, Sc (Dirichlet rows and columns applied), r, s (b,
     constrained entries exactly zero), r_unc, s_unc (b with nothing constrained), the oracle's unconstrained matrix ou and
     vector ob_unc, and the oracle's figures against the reference"""
-    key = (C.name, C.order, C.problem)
+    key = getattr(C, "key", (C.name, C.order, C.problem))  # ((name, order, problem), and the dims where the caller chose them)
     if key in hp.CACHE:
         return hp.CACHE[key]
     if C.problem == "poisson":

@@ -3,8 +3,11 @@
 Nothing is assembled by the code under test: action, diagonal and the solves on ZZZ_OP_MATFREE are compared with the oracle's
 ASSEMBLED matrix (unconstrained, bc = 0, rows of constrained scalar dofs zeroed), with the library's own assembled solve, and
 on the hostile meshes with the 50-digit reference.  "many blocks" = ZZZ_MF_NC = ZZZ_MF_T = 128 (_hostile_gpu.MF_SMALL): 8, 2
-and 2 cell blocks at the dims below, so nodes are shared between blocks and k_mf_finish3 runs.
+and 2 cell blocks at the dims below, so nodes are shared between blocks and k_mf_finish3 runs.  The other thread counts, several
+steps per block, the LDS retry and the refusal: tests/test_gpu_mf_elasticity_plans.py.
 
+  1. action and diagonal per ROW, in units of 2^-53 of the row's own scale (HE.oracle_figures), within max(8 o, 32) + o of the
+     oracle's matrix, o = HE.O_ACTION / HE.O_DIAGONAL being the oracle's own distance from the 50-digit reference.
   5. linalg::cg: the numpy restatement of src/cg.h (tests/_cgh_ref.py) on the P1 cube 4 x 3 x 3 (240 scalar dofs, 60 of them
      constrained) meets the strict test rnorm / rnorm0 < 1e-12 after 90 of its 100 iterations (counted on a CPU, numpy).
   8. hostile meshes: figures in units of 2^-53 of the per-row scale, printed by the test.
@@ -47,26 +50,25 @@ def _system(order, dims, bc=None):
 def _check_action_and_diagonal(c, S, seed, many):
     P, bcb = S["P"], S["bc"].astype(bool)
     v = np.random.default_rng(seed).standard_normal(3 * P.n_owned)
-    oy = np.where(bcb, 0.0, zo.spmv(S["rp"], S["cl"], S["Au"], v))
-    od = np.where(bcb, 1.0, S["diag"])
     c.matfree_setup()
     info = c.matfree_info()
     assert info["valid"] == 1
     if many:
         assert info["blocks"] > 1 and info["shared_dofs"] > 0, info
     y = c.action(v)
-    ey = np.abs(y - oy).max() / np.abs(oy).max()
     d = c.matfree_diagonal()
-    ed = np.abs(d - od).max() / np.abs(od).max()
+    # per row, against the row's own scale (HE.oracle_figures; a constrained row must hold the bits 0.0 / 1.0): the bar is what
+    # a kernel is granted against the truth plus what the oracle is away from it (HE.O_ACTION, HE.O_DIAGONAL)
+    ey, ed = HE.oracle_figures(S["rp"], S["cl"], S["Au"], S["diag"], S["bc"], v, y, d)
     print(f"\nMF elasticity P{P.order} {P.dims}: {info['blocks']} blocks of {info['cells_per_block']} cells, {info['shared_dofs']} shared "
-          f"nodes, {info['bytes_per_action']} B per action; action {ey:.2e}, diagonal {ed:.2e} of the largest reference value")
-    assert ey <= 1e-12
+          f"nodes, {info['bytes_per_action']} B per action; action {ey:.2f}, diagonal {ed:.2f} units of 2^-53 of the row's scale")
+    assert ey <= _bar(HE.O_ACTION[P.order]) + HE.O_ACTION[P.order]
     assert np.all(y[bcb] == 0.0)
     for _ in range(4):
         np.testing.assert_array_equal(c.action(v), y)
     c.matfree_setup()  # a rebuilt plan is the same plan
     np.testing.assert_array_equal(c.action(v), y)
-    assert ed <= 1e-12
+    assert ed <= _bar(HE.O_DIAGONAL[P.order]) + HE.O_DIAGONAL[P.order]
     assert np.all(d[bcb] == 1.0)
     np.testing.assert_array_equal(c.matfree_diagonal(), d)
     return y
@@ -81,9 +83,12 @@ def test_action_and_diagonal_against_the_oracle(order, many):
         _check_action_and_diagonal(c, S, 10 + order, many)
 
 
-@pytest.mark.parametrize("order", [1, 2])
+@pytest.mark.parametrize("order", [1, 2, 3])
 def test_dirichlet_set_per_component(order):
-    """2. component 1 alone of the nodes on x = 0, all three components on x = 1: a per-node flag gets the first face wrong"""
+    """2. component 1 alone of the nodes on x = 0, all three components on x = 1: a per-node flag gets the first face wrong.
+    P3 (u gathered through gid, the dot product read from A.u) keeps the caller's cell order (ZZZ_RENUMBER=0), so that the host
+    restates the blocks (H.plan_cell_blocks): half-constrained nodes lie in cells of BOTH blocks, i.e. their component bits are
+    read from sh_flag in k_mf_finish3 and not from dof_flag alone."""
     P = _system(order, DIMS[order])["P"]
     x = P.dof_x[:P.n_owned, 0]
     m = np.zeros(3 * P.n_owned, np.uint8)
@@ -91,9 +96,17 @@ def test_dirichlet_set_per_component(order):
     for k in range(3):
         m[3 * np.nonzero(x == 1.0)[0] + k] = 1
     assert 0 < m.sum() and np.any(m.reshape(-1, 3).sum(axis=1) == 1) and np.any(m.reshape(-1, 3).sum(axis=1) == 3)
+    if order == 3:
+        blk = H.plan_cell_blocks(P, int(MF_SMALL["ZZZ_MF_NC"]))
+        in_blocks = np.zeros((P.n_owned, int(blk.max()) + 1), bool)
+        in_blocks[P.cell_dofs.reshape(-1), np.repeat(blk, P.cell_dofs.shape[1])] = True
+        half_shared = (m.reshape(-1, 3).sum(axis=1) == 1) & (in_blocks.sum(axis=1) > 1)
+        print(f"\nMF elasticity P3 {P.dims}: {int(half_shared.sum())} half-constrained nodes shared between blocks")
+        assert half_shared.sum() >= 4
     S = _system(order, DIMS[order], m)
     with _env(**MF_SMALL), zzz.Context(0) as c:
-        c.upload_part(P)
+        with _env(ZZZ_RENUMBER="0" if order == 3 else None):
+            c.upload_part(P)
         c.upload_bc(np.nonzero(m)[0].astype(np.int32))
         y = _check_action_and_diagonal(c, S, 20 + order, True)
     free_on_face = np.zeros_like(m, bool)
@@ -252,23 +265,30 @@ def test_dirichlet_values():
 
 @pytest.mark.parametrize("name,order", HE.CASES, ids=[f"{n}-P{o}" for n, o in HE.CASES])
 def test_hostile_geometry_against_the_50_digit_reference(name, order):
-    """8. many blocks; the bar of the other hostile tests: figure(gpu) <= max(8 x figure(oracle), 32) units of 2^-53"""
-    C = H.case(name, order, "elasticity")
+    """8. many blocks (P3 on HE.DIMS: two); the bar of the other hostile tests, for the action and for the diagonal that Jacobi
+    divides by entry by entry: figure(gpu) <= max(8 x figure(oracle), 32) units of 2^-53"""
+    C = HE.case(name, order)
     u = np.random.default_rng(40 + order).standard_normal(C.n)
     y_ref, t_ref, ofig = HE.action_reference(C, u)
+    d_ref, ds_ref, odfig = HE.diagonal_reference(C)
     bcb = C.bc.astype(bool)
-    assert np.all(t_ref[~bcb] > 0)
+    assert np.all(t_ref[~bcb] > 0) and np.all(ds_ref[~bcb] > 0)
     with _env(**MF_SMALL), zzz.Context(0) as c:
         _upload(c, C, None)
         c.matfree_setup()
         info = c.matfree_info()
         y = c.action(u)
+        d = c.matfree_diagonal()
         np.testing.assert_array_equal(c.action(u), y)
+        np.testing.assert_array_equal(c.matfree_diagonal(), d)
     fig = hp.metric(y, y_ref, t_ref) / hp.U  # (asks the constrained rows, scale 0, for the bits: 0.0)
-    print(f"\nHOSTILE MF elasticity {name:8s} P{order}: {info['blocks']} blocks, gpu {fig:7.2f} oracle {ofig:7.2f}")
-    # (the P3 base of the elasticity cases, 72 cells, is one block even at 128 cells per block)
-    assert info["blocks"] == -(-len(C.cells) // 128) and (info["blocks"] == 1 or info["shared_dofs"] > 0)
+    dfig = hp.metric(d, d_ref, ds_ref) / hp.U  # (... and for 1.0)
+    print(f"\nHOSTILE MF elasticity {name:8s} P{order}: {info['blocks']} blocks, action gpu {fig:7.2f} oracle {ofig:7.2f}, "
+          f"diagonal gpu {dfig:7.2f} oracle {odfig:7.2f}")
+    assert info["blocks"] == -(-len(C.cells) // 128) and info["blocks"] >= 2 and info["shared_dofs"] > 0
+    assert np.all(y[bcb] == 0.0) and np.all(d[bcb] == 1.0)
     assert fig <= _bar(ofig), (fig, ofig)
+    assert dfig <= _bar(odfig), (dfig, odfig)
 
 
 def test_what_stays_declined():
