@@ -352,6 +352,19 @@ int zzz_matfree_info(zzz_ctx* ctx, int64_t info[8]);
  * op = ZZZ_OP_MATFREE (an extension: the reference's KSP path always multiplies with the assembled AIJ matrix,
  * src/poisson_problem.cpp:159-181; same mathematics, the operator recomputed per product instead of streamed). */
 int zzz_matfree_diagonal(zzz_ctx* ctx, double* diag);
+/* The `ZZZ Assemble vector` block of the matrix-free problem types (src/cgpoisson_problem.cpp:147-170 and its elasticity
+ * twin) WITHOUT a sparsity pattern: fills b as zzz_assemble_vector does -- same forms, coefficients, Dirichlet set, lifting
+ * once zzz_bc_values_upload has given values, the same ZZZ_ERR_ARG for an unknown form or a missing coefficient -- on the
+ * cell-block plan of zzz_matfree_setup (built on first use) instead of the dof -> cell adjacency of the pattern build.
+ * Needs mesh, dofmap, Dirichlet dofs, coefficients and, for Poisson, the facets; never calls or needs zzz_csr_pattern_build
+ * and creates no pattern (zzz_csr_sizes keeps answering "no sparsity pattern yet").  b is in the caller's numbering, owned
+ * rows are complete without communication (u0 at ghost dofs comes from the upload); rows of constrained scalar dofs are
+ * exactly 0.0, or u0 with values.  Entries of the uploaded values off the Dirichlet set reach no result.  Every call, and a
+ * rebuilt plan, gives the same bits; they are not zzz_assemble_vector's bits (the cells are summed in another order), the
+ * two agree to rounding and coexist on one context in either order.  Where the plan cannot be built (the refusal described
+ * at zzz_action, either block size) the call returns ZZZ_ERR_LIMIT naming zzz_csr_pattern_build + zzz_assemble_vector as
+ * the way out, writes nothing and leaves the context usable.  (A new entry point: ZZZ_ABI_VERSION is unchanged.) */
+int zzz_matfree_assemble_vector(zzz_ctx* ctx, int form);
 /* Measurement aid, as zzz_spmv_time: HIP-event time of `reps` back-to-back actions w = action(p) with the <p,w>
  * partials (what one iteration of linalg::cg launches at src/cg.h:62,65). */
 int zzz_action_time(zzz_ctx* ctx, int reps, double* avg_ms);

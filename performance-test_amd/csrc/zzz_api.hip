@@ -947,6 +947,41 @@ int zzz_matfree_diagonal(zzz_ctx* ctx, double* diag)
   return ZZZ_OK;
 }
 
+int zzz_matfree_assemble_vector(zzz_ctx* ctx, int form)
+{
+  ZZZ_ENTER(ctx);
+  if (ctx->order == 0)
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_matfree_assemble_vector before zzz_dofmap_upload");
+  if (form != ZZZ_FORM_POISSON && form != ZZZ_FORM_ELASTICITY)
+    return fail(ctx, ZZZ_ERR_ARG, "unknown form %d", form);
+  if (!ctx->have_coeff[ZZZ_COEFF_F] || (form == ZZZ_FORM_POISSON && !ctx->have_coeff[ZZZ_COEFF_G]))
+    return fail(ctx, ZZZ_ERR_ARG, "coefficient(s) of L not uploaded");
+  const int bs = form == ZZZ_FORM_ELASTICITY ? 3 : 1;
+  if (bs != ctx->bs)
+    return fail(ctx, ZZZ_ERR_ARG, "form %d needs block size %d, dofmap has %d", form, bs, ctx->bs);
+  // the plan first: a refusal comes before anything is written.  (mf.failed: zzz_action has met the refusal on this context
+  // already and runs its two-pass form behind the pattern; nothing has changed since, so the plan is not tried again)
+  if (!ctx->mf.valid)
+  {
+    const int rc = ctx->mf.failed ? fail(ctx, ZZZ_ERR_LIMIT, "this mesh does not fit the cell-block plan") : mf_plan_build(ctx);
+    if (rc == ZZZ_ERR_LIMIT)
+    {
+      const std::string why = ctx->err;
+      return fail(ctx, ZZZ_ERR_LIMIT, "zzz_matfree_assemble_vector needs the cell-block plan (%s): assemble this right-hand side with "
+                                      "zzz_csr_pattern_build + zzz_assemble_vector",
+                  why.c_str());
+    }
+    if (rc)
+      return rc;
+  }
+  // what rides on the pattern build elsewhere: the reference tables, the P1 coordinates by dof
+  if (int rc = ensure_tables(ctx))
+    return rc;
+  if (int rc = ensure_p1_coords(ctx))
+    return rc;
+  return mf_assemble_vector(ctx);
+}
+
 int zzz_matfree_info(zzz_ctx* ctx, int64_t info[8])
 {
   if (!ctx || !info)

@@ -4,6 +4,7 @@
 
 #include <climits>
 
+#include "zzz_cell_geom.h"
 #include "zzz_device.h"
 #include "zzz_internal.h"
 
@@ -11,12 +12,6 @@ namespace zzz
 {
 constexpr int ASM_BLOCK = 256;
 constexpr int ASM_ORD_CAP = 512; // block dofs of a tile that the high-order kernels sort by cell count
-
-struct Geom
-{
-  double adet;    // |det J|
-  double K[3][3]; // J^-1: K[al][a] = dX_al/dx_a
-};
 
 __device__ inline void load_cell(const double* __restrict__ x, const int4 v, double p[4][3])
 {
@@ -55,31 +50,6 @@ __device__ inline void load_cell_q3(const double* __restrict__ xq, const int4 dd
       p[k][2] = own[2];
     }
   }
-}
-
-__device__ inline void geometry(const double p[4][3], Geom& G)
-{
-  double J[3][3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a)
-#pragma unroll
-    for (int al = 0; al < 3; ++al)
-      J[a][al] = p[al + 1][a] - p[0][a];
-  const double c00 = J[1][1] * J[2][2] - J[1][2] * J[2][1];
-  const double c01 = J[1][0] * J[2][2] - J[1][2] * J[2][0];
-  const double c02 = J[1][0] * J[2][1] - J[1][1] * J[2][0];
-  const double det = J[0][0] * c00 - J[0][1] * c01 + J[0][2] * c02;
-  const double id = 1.0 / det;
-  G.adet = fabs(det);
-  G.K[0][0] = c00 * id;
-  G.K[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) * id;
-  G.K[0][2] = (J[0][1] * J[1][2] - J[0][2] * J[1][1]) * id;
-  G.K[1][0] = -c01 * id;
-  G.K[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) * id;
-  G.K[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) * id;
-  G.K[2][0] = c02 * id;
-  G.K[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) * id;
-  G.K[2][2] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) * id;
 }
 
 // physical gradients of the four P1 hat functions: g[i][a] = sum_al K[al][a] * dphi_i/dX_al
@@ -155,29 +125,6 @@ __device__ inline void pk_poisson_geom(const Geom& G, double (&GG)[6])
   GG[3] = G.adet * (G.K[0][0] * G.K[1][0] + G.K[0][1] * G.K[1][1] + G.K[0][2] * G.K[1][2]);
   GG[4] = G.adet * (G.K[0][0] * G.K[2][0] + G.K[0][1] * G.K[2][1] + G.K[0][2] * G.K[2][2]);
   GG[5] = G.adet * (G.K[1][0] * G.K[2][0] + G.K[1][1] * G.K[2][1] + G.K[1][2] * G.K[2][2]);
-}
-
-// facet lf of a cell = the three vertices other than lf
-__device__ inline void facet_vertices(int lf, int& q0, int& q1, int& q2)
-{
-  q0 = lf == 0 ? 1 : 0;
-  q1 = lf <= 1 ? 2 : 1;
-  q2 = lf == 3 ? 2 : 3;
-}
-// ... and twice its area, the scale of the exterior-facet terms
-__device__ inline double facet_scale(const double p[4][3], int lf)
-{
-  int q0, q1, q2;
-  facet_vertices(lf, q0, q1, q2);
-  double e1[3], e2[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k)
-  {
-    e1[k] = p[q1][k] - p[q0][k];
-    e2[k] = p[q2][k] - p[q0][k];
-  }
-  const double cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
-  return sqrt(cx * cx + cy * cy + cz * cz);
 }
 
 __device__ inline int find_pos(const int32_t* __restrict__ c, int len, int32_t col)

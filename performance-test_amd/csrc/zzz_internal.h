@@ -625,6 +625,7 @@ int launch_matfree_diagonal(zzz_ctx* ctx, double* d);
 int mf_plan_build(zzz_ctx* ctx);
 int mf_action(zzz_ctx* ctx, const double* x, double* y, double* partials, int* npartials);
 int mf_diagonal(zzz_ctx* ctx, double* y);
+int mf_assemble_vector(zzz_ctx* ctx); // b = L on the plan (zzz_matfree_assemble_vector), lifting included
 // the same action on the plan's float twins (built on first use; the plan itself as well); x, y: nloc floats on the device
 int mf_action_f32(zzz_ctx* ctx, const float* x, float* y, double* partials, int* npartials);
 int mf_f32_prepare(zzz_ctx* ctx); // plan + float twins, or ZZZ_ERR_LIMIT with the reason the float action is refused

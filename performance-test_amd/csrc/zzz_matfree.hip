@@ -33,6 +33,7 @@
 
 #include <type_traits>
 
+#include "zzz_asm_elem.h"
 #include "zzz_mf_elem.h"
 
 namespace zzz
@@ -1077,6 +1078,271 @@ __global__ __launch_bounds__(256) void k_mf_finish3(const int32_t* __restrict__ 
   }
 }
 
+// ---- the right-hand side on the plan: b = L, then b[bc] = 0 (zzz_matfree_assemble_vector) --------------------------------------
+// The action's pass with a mass element in place of the stiffness element (zzz_mf_elem.h: mf_rhs_*): the coefficient f is
+// staged where the action stages u (P3: gathered through gid), the element vector |det J| M f_e goes into the block's
+// accumulators in the plan's rank rounds, interior dofs leave directly and shared ones through ypart and k_mf_finish /
+// k_mf_finish3.  LDS per dof is the action's (lds_per_dof): the plan's nloc_max serves.  |det J| and the facet scale come from
+// the mesh coordinates through the row-gather kernels' helpers (zzz_cell_geom.h) -- P1 from the staged xyz, P2/P3 through
+// mf_cell and cell_verts; the plan's G = |det J| K K^T is no source for |det J| on a stretched mesh.  Poisson's ds term: a
+// cell with a facet mask (a surface's worth of them) reads g, its dofs and the facet table from memory, nothing of it is staged.
+struct MfRhsArgs
+{
+  const int32_t* hdr;
+  const int32_t* dof_ids;
+  const uint8_t* dof_flag;
+  const double* xyz;
+  const uint32_t* idxw;
+  const uint32_t* rnkw;
+  const uint8_t* rmax;
+  const int32_t* pslot;
+  const int32_t* gid;
+  const int32_t* mf_cell;
+  const double* x;
+  const int32_t* cell_verts;
+  const int32_t* cell_dofs;
+  const uint8_t* facet_mask;
+  const double* tab; // ensure_tables: [14][ND][ND], mass at 9, the four facet tables from 10
+  const double* f;
+  const double* g;
+  double* ypart;
+  double* b;
+  int64_t nblocks;
+  int nc, nsb, nloc_cap;
+};
+
+template <int ND, int T, int BS>
+__global__ __launch_bounds__(T, (ND == 20 ? (BS == 3 ? 2 : 3) : 1)) void k_mf_rhs(const MfRhsArgs A)
+{
+  constexpr int NDW = ND / 2, NRW = (ND + 3) / 4, NN = ND * ND;
+  constexpr bool GU = ND == 20;
+  extern __shared__ __align__(32) unsigned char mf_lds[];
+  // P1: xs[3 cap] fs[BS cap] ys[BS cap]; P2: fs ys; P3: ys (f gathered from memory through gid) -- lds_per_dof
+  double* const xs = reinterpret_cast<double*>(mf_lds);
+  double* const fs = xs + (size_t)(ND == 4 ? 3 : 0) * A.nloc_cap;
+  double* const ys = xs + (size_t)(ND == 4 ? 3 + BS : (GU ? 0 : BS)) * A.nloc_cap;
+  __shared__ double M_s[NN];
+  const int tid = threadIdx.x;
+  for (int k = tid; k < NN; k += T) // (the first block's barrier below orders this)
+    M_s[k] = A.tab[9 * NN + k];
+  for (int step = 0;; ++step)
+  {
+    const int64_t b = xcd_stride_item(A.nblocks, step);
+    if (b < 0)
+      break;
+    const int32_t* __restrict__ h = A.hdr + MF_HDR * b;
+    const int dof_off = h[0], nloc = h[1], n_int = h[2], n_sh = h[3], part_off = h[4];
+    for (int d = tid; d < nloc; d += T)
+    {
+      if constexpr (ND == 4)
+      {
+        const double* __restrict__ q = A.xyz + 3ll * (dof_off + d);
+        xs[3 * d + 0] = q[0];
+        xs[3 * d + 1] = q[1];
+        xs[3 * d + 2] = q[2];
+      }
+      if constexpr (!GU)
+      {
+        const double* __restrict__ q = A.f + (int64_t)BS * A.dof_ids[dof_off + d];
+#pragma unroll
+        for (int c = 0; c < BS; ++c)
+          fs[BS * d + c] = q[c];
+      }
+#pragma unroll
+      for (int c = 0; c < BS; ++c)
+        ys[BS * d + c] = 0.0;
+    }
+    for (int s = 0; s < A.nsb; ++s)
+    {
+      const int e = s * T + tid;
+      // the cell's index and rank words: in flight during the element, except at P3 with 1024 threads, where the element
+      // reads f through gid and 128 registers do not hold the fifteen words beside it
+      constexpr bool WORDS_LATE = GU && T == 1024;
+      // (there the block's number is also made opaque per step: hoisted out of this loop, the 35 row bases of idxw, rnkw and gid
+      // are 70 scalar registers that live through it, and five of them spilled)
+      int64_t bq = b;
+      if constexpr (WORDS_LATE)
+        asm volatile("" : "+s"(bq));
+      uint32_t iw[NDW], rw[NRW];
+      if constexpr (!WORDS_LATE)
+      {
+#pragma unroll
+        for (int w = 0; w < NDW; ++w)
+          iw[w] = A.idxw[(bq * NDW + w) * A.nc + e];
+#pragma unroll
+        for (int w = 0; w < NRW; ++w)
+          rw[w] = A.rnkw[(bq * NRW + w) * A.nc + e];
+      }
+      const int32_t cell = A.mf_cell[bq * A.nc + e]; // -1: no cell (the last block's tail: rank bytes 0xff, nothing is added)
+      // the cell's vertices: P1 from the staged coordinates, P2/P3 from the mesh
+      auto vertices = [&](double(&p)[4][3]) {
+        if constexpr (ND == 4)
+        {
+#pragma unroll
+          for (int k = 0; k < 4; ++k)
+          {
+            const int i = (iw[k >> 1] >> (16 * (k & 1))) & 0xffff;
+#pragma unroll
+            for (int a = 0; a < 3; ++a)
+              p[k][a] = xs[3 * i + a];
+          }
+        }
+        else
+          load_cell(A.x, *reinterpret_cast<const int4*>(A.cell_verts + 4ll * max(cell, 0)), p);
+      };
+      double adet;
+      if constexpr (ND != 4)
+      {
+        double p[4][3];
+        Geom Gm;
+        vertices(p);
+        geometry(p, Gm); // (|det J| alone is used: the inverse goes away at compile time)
+        adet = Gm.adet;
+      }
+      if (s == 0)
+      {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __syncthreads(); // the staged values are in LDS (the loads above are in flight meanwhile)
+      }
+      [[maybe_unused]] int off = 0; // (always 0)
+      if constexpr (ND == 4)
+      {
+        double p[4][3];
+        Geom Gm;
+        vertices(p);
+        geometry(p, Gm);
+        adet = Gm.adet;
+        // (the reads of f wait for |det J|: hoisted above the geometry they cost the registers of an eighth wavefront per SIMD)
+        asm volatile("" : "+v"(off), "+v"(adet));
+      }
+      double ye[BS][ND]; // [component][local node]
+      // (o: the element's chain offset, always 0 -- with 1024 threads the P3 gathers of a pass wait for the pass before)
+      auto f_at = [&](int j, int c, [[maybe_unused]] int o) -> double {
+        if constexpr (GU)
+          return A.f[(int64_t)BS * A.gid[(bq * ND + j) * A.nc + e + (T == 1024 ? o : 0)] + c];
+        else
+          return fs[off + BS * (int)((iw[j >> 1] >> (16 * (j & 1))) & 0xffff) + c];
+      };
+      if constexpr (BS == 3)
+        mf_rhs_mass3<ND>(M_s, adet, f_at, ye);
+      else
+      {
+        mf_rhs_mass<ND, (ND == 20 ? (T == 1024 ? 5 : 10) : ND)>(M_s, adet, [&](int j, int o) -> double { return f_at(j, 0, o); }, ye[0]);
+        const unsigned m = cell >= 0 ? A.facet_mask[cell] : 0u;
+        if (m)
+        {
+          // few cells: the facet's three vertices are fetched again, facet by facet, rather than kept across the mass element
+          // (facet_scale_of, zzz_cell_geom.h)
+          const int32_t* __restrict__ cd = A.cell_dofs + (int64_t)ND * cell;
+          const double* __restrict__ F = A.tab + 10 * NN;
+#pragma unroll 1
+          for (int lf = 0; lf < 4; ++lf)
+            if ((m >> lf) & 1u)
+            {
+              int q[3];
+              facet_vertices(lf, q[0], q[1], q[2]);
+              double v[3][3];
+#pragma unroll
+              for (int t = 0; t < 3; ++t)
+              {
+                const double* __restrict__ xv;
+                if constexpr (ND == 4)
+                  xv = xs + 3 * (int)(((q[t] < 2 ? iw[0] : iw[1]) >> (16 * (q[t] & 1))) & 0xffff);
+                else
+                  xv = A.x + 3ll * A.cell_verts[4ll * cell + q[t]];
+#pragma unroll
+                for (int a = 0; a < 3; ++a)
+                  v[t][a] = xv[a];
+              }
+              mf_rhs_facet<ND>(F, lf, facet_scale_of(v), [&](int j) -> double { return A.g[cd[j]]; }, ye[0]);
+            }
+        }
+      }
+      if constexpr (WORDS_LATE)
+      {
+#pragma unroll
+        for (int w = 0; w < NDW; ++w)
+          iw[w] = A.idxw[(bq * NDW + w) * A.nc + e];
+#pragma unroll
+        for (int w = 0; w < NRW; ++w)
+          rw[w] = A.rnkw[(bq * NRW + w) * A.nc + e];
+      }
+      // rounds, as in k_mf_action: the incidences of rank r of this step are added in round r
+      const uint32_t* __restrict__ rm = reinterpret_cast<const uint32_t*>(A.rmax) + (b * A.nsb + s) * NRW;
+      int Rc[3] = {0, 0, 0};
+      constexpr int NE = ND == 20 ? 16 : ND;
+#pragma unroll
+      for (int w = 0; w < NRW; ++w)
+      {
+        const uint32_t mm = __builtin_amdgcn_readfirstlane(rm[w]);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (4 * w + k < ND)
+          {
+            const int c = 4 * w + k < 4 ? 0 : (4 * w + k < NE ? 1 : 2);
+            Rc[c] = max(Rc[c], (int)((mm >> (8 * k)) & 255u));
+          }
+      }
+      const int R2 = Rc[2], R1 = max(R2, Rc[1]), R0 = max(R1, Rc[0]);
+      for (int r = 0; r < R0; ++r)
+      {
+        // (the wait is spelled out: see k_mf_action)
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __syncthreads();
+        const int jend = r < R2 ? ND : (r < R1 ? NE : 4); // uniform
+#pragma unroll
+        for (int j = 0; j < ND; ++j)
+        {
+          if (j < 4 || (j < NE ? jend > 4 : jend > NE))
+            if ((int)((rw[j >> 2] >> (8 * (j & 3))) & 255u) == r)
+            {
+              const int i = (iw[j >> 1] >> (16 * (j & 1))) & 0xffff;
+#pragma unroll
+              for (int c = 0; c < BS; ++c)
+                __hip_atomic_fetch_add(&ys[BS * i + c], ye[c][j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+        }
+      }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __syncthreads();
+    // dofs interior to the block: final values, a constrained scalar dof exactly 0.0 (bc->set(b), u0 == 0); shared: partial sums
+    for (int d = tid; d < n_int; d += T)
+    {
+      const int64_t g = A.dof_ids[dof_off + d];
+      const int fl = A.dof_flag[dof_off + d];
+#pragma unroll
+      for (int c = 0; c < BS; ++c)
+        A.b[BS * g + c] = ((fl >> c) & 1) ? 0.0 : ys[BS * d + c];
+    }
+    for (int d = tid; d < n_sh; d += T)
+    {
+      const int64_t q = A.pslot[part_off + d];
+#pragma unroll
+      for (int c = 0; c < BS; ++c)
+        A.ypart[BS * q + c] = ys[BS * (n_int + d) + c];
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __syncthreads();
+  }
+}
+
+// lifting (zzz_bc_values_upload): v = u0 on the constrained scalar dofs and 0 elsewhere -- whatever else the uploaded array
+// holds, NaN included, goes no further; then, with y = action(v) (which leaves 0 on constrained rows),
+// b_i = u0_i on constrained rows and b_i - y_i on free ones
+__global__ __launch_bounds__(256) void k_mf_lift_src(const uint8_t* __restrict__ bc, const double* __restrict__ gval, int64_t n,
+                                                     double* __restrict__ v)
+{
+  for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += gridDim.x * 256ll)
+    v[i] = bc[i] ? gval[i] : 0.0;
+}
+__global__ __launch_bounds__(256) void k_mf_lift_apply(const uint8_t* __restrict__ bc, const double* __restrict__ gval,
+                                                       const double* __restrict__ y, int64_t n, double* __restrict__ b)
+{
+  for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += gridDim.x * 256ll)
+    b[i] = bc[i] ? gval[i] : b[i] - y[i];
+}
+
 struct SegOffset
 {
   unsigned seg;
@@ -1823,6 +2089,91 @@ static int mf_run(zzz_ctx* ctx, bool diag, const R* u, R* y, double* partials, i
   if (npartials)
     *npartials = grid + (M.nshared > 0 ? gf : 0);
   ZZZ_HIP(ctx, hipGetLastError());
+  return ZZZ_OK;
+}
+template <int ND, int T, int BS>
+static int mf_rhs_launch(zzz_ctx* ctx, const MfRhsArgs& A, int grid, int lds)
+{
+  static int attr_lds[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  if (lds > 48 * 1024 && lds > attr_lds[ctx->device & 15])
+  {
+    ZZZ_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_mf_rhs<ND, T, BS>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    attr_lds[ctx->device & 15] = lds;
+  }
+  hipLaunchKernelGGL((k_mf_rhs<ND, T, BS>), dim3(grid), dim3(T), lds, ctx->stream, A);
+  return ZZZ_OK;
+}
+
+// b = L on the plan (zzz_matfree_assemble_vector; the caller has checked the form, the coefficients and the plan): the
+// cell-block pass, the shared dofs' finish, and with Dirichlet values the lifting through the plan's own action -- no halo
+// exchange, u0 at ghost dofs comes from the upload.  Reproducible: the rounds and the finish fix every order of addition.
+int mf_assemble_vector(zzz_ctx* ctx)
+{
+  MfPlan& M = ctx->mf;
+  if (!M.valid || M.bs != ctx->bs)
+    return fail(ctx, ZZZ_ERR_ARG, "matrix-free plan missing");
+  const int lds = lds_bytes(M.nd, M.nloc_max, M.bs);
+  const int per_cu = mf_per_cu(M, lds);
+  int grid = (int)std::min<int64_t>(256ll * per_cu, (M.nblocks + 7) / 8 * 8);
+  grid = std::max(8, grid / 8 * 8);
+  MfRhsArgs A;
+  A.hdr = M.hdr.p;
+  A.dof_ids = M.dof_ids.p;
+  A.dof_flag = M.dof_flag.p;
+  A.xyz = M.xyz.p;
+  A.idxw = M.idxw.p;
+  A.rnkw = M.rnkw.p;
+  A.rmax = M.rmax.p;
+  A.pslot = M.sh_slot.p;
+  A.gid = M.gid.p;
+  A.mf_cell = M.mf_cell.p;
+  A.x = ctx->x.p;
+  A.cell_verts = ctx->cell_verts.p;
+  A.cell_dofs = ctx->cell_dofs.p;
+  A.facet_mask = ctx->facet_mask.p;
+  A.tab = ctx->tables.p;
+  A.f = ctx->coeff[0].p;
+  A.g = ctx->coeff[1].p;
+  A.ypart = M.ypart.p;
+  A.b = ctx->b.p;
+  A.nblocks = M.nblocks;
+  A.nc = M.nc;
+  A.nsb = M.nsb;
+  A.nloc_cap = M.nloc_max;
+  int rc = ZZZ_OK;
+#define ZZZ_MF_RHS(ND_)                                                                                                 \
+  (M.bs == 3 ? (M.threads == 128 ? mf_rhs_launch<ND_, 128, 3>(ctx, A, grid, lds)                                          \
+                                 : M.threads == 256 ? mf_rhs_launch<ND_, 256, 3>(ctx, A, grid, lds)                       \
+                                                    : mf_rhs_launch<ND_, 512, 3>(ctx, A, grid, lds))                      \
+             : (M.threads == 128 ? mf_rhs_launch<ND_, 128, 1>(ctx, A, grid, lds)                                          \
+                                 : M.threads == 256 ? mf_rhs_launch<ND_, 256, 1>(ctx, A, grid, lds)                       \
+                                                    : M.threads == 512 ? mf_rhs_launch<ND_, 512, 1>(ctx, A, grid, lds)    \
+                                                                       : mf_rhs_launch<ND_, 1024, 1>(ctx, A, grid, lds)))
+  rc = M.nd == 4 ? ZZZ_MF_RHS(4) : (M.nd == 10 ? ZZZ_MF_RHS(10) : ZZZ_MF_RHS(20));
+#undef ZZZ_MF_RHS
+  if (rc)
+    return rc;
+  if (M.nshared > 0)
+  {
+    const int gf = (int)std::min<int64_t>(std::max<int64_t>((M.bs * M.nshared + 255) / 256, 1), 2048);
+    if (M.bs == 3)
+      hipLaunchKernelGGL(k_mf_finish3, dim3(gf), dim3(256), 0, ctx->stream, M.sh_dof.p, M.sh_off.p, M.sh_flag.p, M.nshared, M.ypart.p,
+                         (const double*)nullptr, ctx->b.p, (double*)nullptr, (const int*)nullptr, 0.0);
+    else
+      hipLaunchKernelGGL(k_mf_finish<double>, dim3(gf), dim3(256), 0, ctx->stream, M.sh_dof.p, M.sh_off.p, M.sh_flag.p, M.nshared,
+                         M.ypart.p, (const double*)nullptr, ctx->b.p, (double*)nullptr, (const int*)nullptr, 0.0);
+  }
+  ZZZ_HIP(ctx, hipGetLastError());
+  if (ctx->have_bc_val)
+  {
+    const int64_t nall = ctx->nloc(), nrows = ctx->n_owned * ctx->bs;
+    hipLaunchKernelGGL(k_mf_lift_src, dim3(grid_for(nall)), dim3(256), 0, ctx->stream, ctx->bc.p, ctx->bc_val.p, nall, ctx->p.p);
+    if (int rc2 = mf_action(ctx, ctx->p.p, ctx->w.p, nullptr, nullptr))
+      return rc2;
+    hipLaunchKernelGGL(k_mf_lift_apply, dim3(grid_for(nrows)), dim3(256), 0, ctx->stream, ctx->bc.p, ctx->bc_val.p, ctx->w.p, nrows,
+                       ctx->b.p);
+    ZZZ_HIP(ctx, hipGetLastError());
+  }
   return ZZZ_OK;
 }
 ZZZ_PRELOAD_TU(matfree)

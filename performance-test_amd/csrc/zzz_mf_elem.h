@@ -390,6 +390,78 @@ ZZZ_HD inline void mf_el_element_p1(const double (&x)[4][3], const double (&u)[4
   }
 }
 
+// ---- the right-hand side on the same plan: form L of src/Poisson.py (inner(f, v) dx + inner(g, v) ds) and of
+// src/Elasticity.py (inner(f, v) dx), per cell (k_mf_rhs of zzz_matfree.hip; tools/mf_rhs_host.cpp runs the same code on the
+// CPU).  M is the reference mass table the row-gather kernels read (tab[9 ND^2 ...] of element_tables.inc, [i][j]), F the four
+// reference facet tables behind it (tab[10 ND^2 ...], [lf][i][j], rows of dofs off the facet are zero).  The products are
+// formed in asm_vector_pk's order -- sum over j first, then the geometry factor -- with the library's two roundings per
+// multiply-add: a cell contributes the same bits here and there, only the order of the cells differs.
+// f_at(j, o) = the coefficient at local dof j; o is the chain's offset (always 0), which a caller short of registers adds to the
+// address it reads so that a pass's reads wait for the pass before.  The columns are taken ten at a time at P3, so that half of f_e and half a row of
+// the table are in flight beside the twenty sums, not all of both (128 registers hold the element then); a row's sum is still
+// formed column by column from the left.  On the device the rows are chained through an empty asm statement, as
+// ZZZ_MF_FENCE_G chains the action's modes: without it the scheduler hoists the ND^2 table reads to the top -- 256 registers
+// and scratch at P2 already.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define ZZZ_MF_RHS_FENCE(v) asm volatile("" : "+v"(off), "+v"(v))
+#define ZZZ_MF_RHS_OPAQUE(o) asm volatile("" : "+v"(o))
+#else
+#define ZZZ_MF_RHS_FENCE(v) ((void)0)
+#define ZZZ_MF_RHS_OPAQUE(o) ((void)0)
+#endif
+template <int ND, int NH = (ND == 20 ? 10 : ND), class FAt> // NH: columns per pass (k_mf_rhs: five at P3 with 1024 threads)
+ZZZ_HD inline void mf_rhs_mass(const double* __restrict__ M, double adet, FAt&& f_at, double (&ye)[ND])
+{
+  static_assert(ND % NH == 0, "whole passes");
+  [[maybe_unused]] int off = 0;          // (always 0)
+#pragma unroll
+  for (int j0 = 0; j0 < ND; j0 += NH)
+  {
+    double fe[NH];
+#pragma unroll
+    for (int j = 0; j < NH; ++j)
+      fe[j] = f_at(j0 + j, off);
+#pragma unroll
+    for (int i = 0; i < ND; ++i)
+    {
+      double acc = j0 == 0 ? 0.0 : ye[i];
+#pragma unroll
+      for (int j = 0; j < NH; ++j)
+        acc += M[off + i * ND + j0 + j] * fe[j];
+      ye[i] = j0 + NH == ND ? adet * acc : acc;
+      ZZZ_MF_RHS_FENCE(ye[i]);
+    }
+  }
+}
+// block size 3: the same table per component, three values per node; f_at(j, c) = component c of the coefficient at local
+// node j (and the chain's offset), one component at a time
+template <int ND, class FAt>
+ZZZ_HD inline void mf_rhs_mass3(const double* __restrict__ M, double adet, FAt&& f_at, double (&ye)[3][ND])
+{
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+    mf_rhs_mass<ND>(M, adet, [&](int j, int o) -> double { return f_at(j, c, o); }, ye[c]);
+}
+// exterior facet lf of a cell: y_e += scale * F[lf] g_e, scale = twice the facet's area; g_at(j) = the boundary coefficient
+// at local dof j, fetched where it is used (the cells that have such a facet are a surface's worth)
+template <int ND, class GAt>
+ZZZ_HD inline void mf_rhs_facet(const double* __restrict__ F, int lf, double scale, GAt&& g_at, double (&ye)[ND])
+{
+  // (a loop over j per row, not unrolled, the row's offset formed where it is used: a handful of registers beside y_e)
+#pragma unroll
+  for (int i = 0; i < ND; ++i)
+  {
+    int o = (lf * ND + i) * ND;
+    if constexpr (ND > 4) // (as a compile-time offset from a uniform base the ND row pointers are hoisted: 49 spilled SGPRs at P3)
+      ZZZ_MF_RHS_OPAQUE(o);
+    double fa = 0.0;
+#pragma unroll 1
+    for (int j = 0; j < ND; ++j)
+      fa += F[o + j] * g_at(j);
+    ye[i] += scale * fa;
+  }
+}
+
 // ---- P1 in float: how well an origin serves a cell, which origin a block takes, or none ----------------------------------
 // Column by column (column al = edge p_(al+1) - p_0), every entry of the Jacobian formed in float from the rounded relative
 // coordinates is compared with the double Jacobian's, against the cell's extent along that entry's axis (per axis: an

@@ -114,6 +114,9 @@ struct Options
   // cgpoisson only: the reference's scalar is PetscScalar (src/cgpoisson_problem.cpp:28); "float32" runs the action and
   // linalg::cg as a single-precision PETSc build would (zzz_cg_solve_f32), one GPU
   std::string scalar_type = "float64";
+  // the right-hand side: rowgather (zzz_assemble_vector, behind zzz_csr_pattern_build) | cellblock (zzz_matfree_assemble_vector
+  // on the matrix-free plan: no sparsity pattern at all)
+  std::string vector_assembly = "rowgather";
   // cgelasticity only: "linalg" = linalg::cg(u, b, action, 100, 1e-6) as cgpoisson runs it; "ksp" = KSPCG on the matrix-free
   // operator with the options database (-pc_type jacobi | none, -ksp_rtol, -ksp_max_it, the norm options)
   std::string cg_solver = "linalg";
@@ -159,6 +162,8 @@ void usage()
                "                                  operator, Jacobi from the element matrices' diagonals; no matrix)\n"
                "  --scalar_type arg (=float64)    float64 | float32 (cgpoisson on one GPU: action and linalg::cg in single\n"
                "                                  precision, as the reference built on a single-precision PETSc)\n"
+               "  --vector_assembly arg (=rowgather)  rowgather | cellblock (cgpoisson, cgelasticity, poisson --operator matfree:\n"
+               "                                  the right-hand side on the matrix-free plan, no sparsity pattern is built)\n"
                "  --cg_solver arg (=linalg)       cgelasticity only: linalg (linalg::cg, 100 iterations, rtol 1e-6, as cgpoisson) |\n"
                "                                  ksp (KSPCG on the matrix-free operator: -pc_type jacobi | none, -ksp_rtol,\n"
                "                                  -ksp_max_it, -ksp_norm_type)\n"
@@ -220,6 +225,8 @@ Options parse(int argc, char** argv)
         o.op = value(i, arg, key);
       else if (key == "scalar_type")
         o.scalar_type = value(i, arg, key);
+      else if (key == "vector_assembly")
+        o.vector_assembly = value(i, arg, key);
       else if (key == "cg_solver")
       {
         o.cg_solver = value(i, arg, key);
@@ -479,13 +486,18 @@ void run_rank(Shared& S, std::barrier<>& bar, int rank)
   if (problem == ZZZH_ELASTICITY)
     phase("ZZZ Create forms", [&] {});
   // fem::petsc::create_matrix: untimed in the reference, inside the ZZZ Assemble umbrella
-  phase(nullptr, [&] { ZCK(ctx, zzz_csr_pattern_build(ctx)); });
+  const bool cellblock = o.vector_assembly == "cellblock";
+  if (!cellblock)
+    phase(nullptr, [&] { ZCK(ctx, zzz_csr_pattern_build(ctx)); });
+  else if (!matfree_op)
+    // no pattern: the plan of the matrix-free kernels stands where create_matrix stood (--operator matfree builds it below)
+    phase(nullptr, [&] { ZCK(ctx, zzz_matfree_setup(ctx)); });
   if (matfree_op)
     // no matrix: what takes its place is the plan of the matrix-free kernel (the diagonal is PCSetUp's, in ZZZ Solve)
     phase("ZZZ Assemble matrix", [&] { ZCK(ctx, zzz_matfree_setup(ctx)); });
   else if (!cg_problem)
     phase("ZZZ Assemble matrix", [&] { ZCK(ctx, zzz_assemble_matrix(ctx, form)); });
-  phase("ZZZ Assemble vector", [&] { ZCK(ctx, zzz_assemble_vector(ctx, form)); });
+  phase("ZZZ Assemble vector", [&] { ZCK(ctx, cellblock ? zzz_matfree_assemble_vector(ctx, form) : zzz_assemble_vector(ctx, form)); });
   if (problem == ZZZH_ELASTICITY && !cgelasticity)
     // build_near_nullspace (src/elasticity_problem.cpp:233-244): six orthonormalised rigid-body modes; GAMG would consume
     // them (MatSetNearNullSpace), Jacobi-CG does not
@@ -514,6 +526,8 @@ void run_rank(Shared& S, std::barrier<>& bar, int rank)
     std::cout << "  Scaling type:    " << o.scaling_type << std::endl;
     if (o.scalar_type == "float32")
       std::cout << "  Scalar type:     float32" << std::endl;
+    if (o.vector_assembly == "cellblock")
+      std::cout << "  Vector assembly: cellblock (no sparsity pattern)" << std::endl;
     std::cout << "  Num processes:   " << S.nranks << std::endl;
     std::cout << "  Num cells:       " << S.num_cells << count_suffix(S.num_cells) << std::endl;
     std::cout << "  Total degrees of freedom:               " << S.num_dofs << count_suffix(S.num_dofs) << std::endl;
@@ -750,6 +764,12 @@ void solve(int argc, char** argv)
     if (why)
       throw std::runtime_error("--problem_type cgelasticity: " + std::string(why));
   }
+  if (o.vector_assembly != "rowgather" && o.vector_assembly != "cellblock")
+    throw std::runtime_error("--vector_assembly " + o.vector_assembly + ": rowgather or cellblock");
+  if (o.vector_assembly == "cellblock" && !(o.problem_type == "cgpoisson" || cgel || (o.problem_type == "poisson" && o.op == "matfree")))
+    throw std::runtime_error("--vector_assembly cellblock applies to the matrix-free problem types (cgpoisson, cgelasticity, poisson "
+                             "--operator matfree): --problem_type " + o.problem_type + " with the assembled operator needs the sparsity "
+                             "pattern anyway");
   if (o.scalar_type != "float64" && o.scalar_type != "float32")
     throw std::runtime_error("--scalar_type " + o.scalar_type + ": float64 or float32");
   if (o.scalar_type == "float32" && o.problem_type != "cgpoisson")
