@@ -465,8 +465,8 @@ int zzz_cg_history(zzz_ctx* ctx, int n, double* out);
 
 /* About the last zzz_cg_solve: info[0] bit 0 is reserved and always 0; bit 1 (value 2)
  * when Jacobi's inverse diagonal was read as 16-bit codes into a table of its distinct values and z = D^-1 r recomputed
- * instead of stored (68 instead of 80 B per row and iteration in the two vector kernels; the same bits), info[0] >> 8 = those
- * distinct values; bit 2 (value 4) when the solve was ZZZ_CG_PIPE with a communicator and its all-reduces ran on a stream of
+ * instead of stored (68 instead of 80 B per row and iteration in the two vector kernels; the same bits), bits 8-31 = those
+ * distinct values, bit 32 set when there were at most 256 of them and the codes were 8 bits wide (66 B); bit 2 (value 4) when the solve was ZZZ_CG_PIPE with a communicator and its all-reduces ran on a stream of
  * their own beside the halo exchange and the product (not with the host-mediated local backend, nor with mailboxes
  * between contexts of one process);
  * info[1] = its iteration count (same iterates, bit for bit, either way); info[2] = how it ended, in

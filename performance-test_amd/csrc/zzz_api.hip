@@ -1270,9 +1270,11 @@ int zzz_cg_info(zzz_ctx* ctx, int64_t info[4])
 {
   if (!ctx || !info)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_cg_info: bad arguments");
-  // bit 3: the solution update was deferred; bits 4-7: over how many iterations (K; 1 when it was not)
+  // bit 3: the solution update was deferred; bits 4-7: over how many iterations (K; 1 when it was not); bits 8-31: the
+  // coded inverse diagonal's distinct values; bit 32: its codes were 8 bits wide
   info[0] = (ctx->last_solve_dinv_codes > 0 ? 2 : 0) | (ctx->last_solve_red_overlapped ? 4 : 0) | (ctx->last_solve_xdefer_k > 1 ? 8 : 0) |
-            ((int64_t)(ctx->last_solve_xdefer_k & 15) << 4) | ((int64_t)ctx->last_solve_dinv_codes << 8);
+            ((int64_t)(ctx->last_solve_xdefer_k & 15) << 4) | ((int64_t)ctx->last_solve_dinv_codes << 8) |
+            ((int64_t)(ctx->last_solve_dinv_bits == 8 ? 1 : 0) << 32);
   info[1] = ctx->last_iters;
   info[2] = ctx->last_reason;
   info[3] = (int64_t)(ctx->last_pc_bound * 1.0e6); // Chebyshev-Jacobi: spectrum bound x 1e6

@@ -95,12 +95,38 @@ __device__ inline int block_flag(int f)
 
 struct DinvCodes
 {
-  const uint32_t* codes; // two 16-bit codes per word, entry pairs as the dbl2 accesses take them
+  const uint32_t* codes; // two 16-bit codes per word, entry pairs as the dbl2 accesses take them; bits == 8: one byte per entry
   const double* dict;
   const double* r;
   int ndict;
+  int bits; // 16, or 8 when ndict <= DZ8_MAX (dinv_codes_build)
 };
 constexpr int DZ_MAX = 2048;
+constexpr int DZ8_MAX = 256;
+
+// The kernels that take DinvCodes are compiled per form of the inverse diagonal, DZ: 0 doubles, 1 16-bit codes, 2 8-bit
+// codes (the LDS table then holds DZ8_MAX entries).  A dbl2 access' two codes are one load either way.
+constexpr int dz_table(int DZ) { return DZ == 2 ? DZ8_MAX : DZ == 1 ? DZ_MAX : 1; }
+template <int DZ>
+__device__ inline uint32_t dz_load2(const DinvCodes& dz, int64_t i2) // the codes of entries 2 i2 and 2 i2 + 1
+{
+  return DZ == 2 ? (uint32_t)reinterpret_cast<const uint16_t*>(dz.codes)[i2] : dz.codes[i2];
+}
+template <int DZ>
+__device__ inline uint32_t dz_lo(uint32_t dc)
+{
+  return DZ == 2 ? dc & 0xffu : dc & 0xffffu;
+}
+template <int DZ>
+__device__ inline uint32_t dz_hi(uint32_t dc)
+{
+  return DZ == 2 ? dc >> 8 : dc >> 16;
+}
+template <int DZ>
+__device__ inline uint32_t dz_load1(const DinvCodes& dz, int64_t i) // the code of entry i
+{
+  return DZ == 2 ? (uint32_t)reinterpret_cast<const uint8_t*>(dz.codes)[i] : (uint32_t)reinterpret_cast<const uint16_t*>(dz.codes)[i];
+}
 
 // the polling events of one solve: destroyed on every exit path
 template <int N>
@@ -155,7 +181,8 @@ struct CgSolve
 
 // zzz_cg.hip
 void cg_report_reset(zzz_ctx* ctx); // last_pc_bound, last_solve_red_overlapped, last_solve_xdefer_k, last_solve_dinv_codes
-int dinv_codes_build(zzz_ctx* ctx, int64_t n, DinvCodes& dzc); // ctx->dinv as 16-bit codes (dzc.codes stays null: too many values)
+// ctx->dinv as 8- or 16-bit codes (dzc.codes stays null: too many values)
+int dinv_codes_build(zzz_ctx* ctx, int64_t n, DinvCodes& dzc);
 bool loop_exceeds_cache(zzz_ctx* ctx, int nvec);               // operator + nvec vectors against the Infinity Cache
 int vgrid(int64_t n);                                          // workgroups of a vector kernel over n entries
 int cg_solve_pipe(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm); // zzz_cg_pipe.hip

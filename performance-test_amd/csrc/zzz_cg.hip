@@ -203,12 +203,22 @@ __global__ __launch_bounds__(256) void k_dd_insert(const double* __restrict__ d,
 }
 __global__ __launch_bounds__(256) void k_dd_encode(const double* __restrict__ d, int64_t n, int64_t npad,
                                                    const unsigned long long* __restrict__ table, const int32_t* __restrict__ slot_code,
-                                                   uint16_t* __restrict__ codes, const int* __restrict__ info)
+                                                   uint16_t* __restrict__ codes, const int* __restrict__ info, int allow8)
 {
   if (info[1])
     return;
+  // one byte per entry when every code fits one (info[2]: the values numbered; dinv_codes_build applies the same rule to
+  // the count it reads back)
+  const bool b8 = allow8 && info[2] <= DZ8_MAX;
+  uint8_t* __restrict__ codes8 = reinterpret_cast<uint8_t*>(codes);
   for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < npad; i += gridDim.x * 256ll)
-    codes[i] = i < n ? (uint16_t)valset_find<DD_BITS>(table, slot_code, (unsigned long long)__double_as_longlong(d[i])) : 0;
+  {
+    const int c = i < n ? valset_find<DD_BITS>(table, slot_code, (unsigned long long)__double_as_longlong(d[i])) : 0;
+    if (b8)
+      codes8[i] = (uint8_t)c;
+    else
+      codes[i] = (uint16_t)c;
+  }
 }
 
 // r = b - w (w = A x0, or nothing when x0 == 0); z = dinv r; partials: pa = <r,z>, pb = test norm^2
@@ -246,17 +256,20 @@ __global__ __launch_bounds__(VB) void k_init_residual(const double* __restrict__
 // matrix's: section 3 of DESIGN.md); as 16-bit codes into a table in LDS it costs 2 B per row instead of 8, and with it
 // z = D^-1 r is cheaper to RECOMPUTE here from r (the same product of the same two doubles: the same bits) than to
 // write in k_update_xr and read back: 80 -> 68 B per row and iteration for the two kernels.  dz.codes = nullptr: off.
+// With at most 256 distinct values the codes are bytes (DZ = 2 of zzz_cg.h): 1 B per row, 66 B for the two kernels.  The
+// table entry a code selects is the same double, so nothing downstream changes.  Each kernel below is a body compiled per
+// DZ and two __global__ entry points: the one it always had (doubles | 16-bit codes) and a `_c8` one for the 8-bit codes.
 
-template <bool NT, bool DZ = false>
-__global__ __launch_bounds__(VB) void k_update_p(CgState* __restrict__ st, double* __restrict__ beta_hist,
-                                                 double* __restrict__ dp_hist, const double* __restrict__ alpha_hist,
-                                                 int it, CgParams P, const double* __restrict__ pa,
-                                                 const double* __restrict__ pb, int np, const double* __restrict__ z,
-                                                 double* __restrict__ p, double* __restrict__ x, int64_t n,
-                                                 int update_dir, DinvCodes dz = DinvCodes())
+template <bool NT, int DZ>
+__device__ __forceinline__ void update_p_body(CgState* __restrict__ st, double* __restrict__ beta_hist,
+                                              double* __restrict__ dp_hist, const double* __restrict__ alpha_hist,
+                                              int it, const CgParams& P, const double* __restrict__ pa,
+                                              const double* __restrict__ pb, int np, const double* __restrict__ z,
+                                              double* __restrict__ p, double* __restrict__ x, int64_t n,
+                                              int update_dir, const DinvCodes& dz)
 {
   __shared__ double sh[VB / 64];
-  __shared__ double dtab[DZ ? DZ_MAX : 1];
+  __shared__ double dtab[dz_table(DZ)];
   if (DZ)
   {
     for (int k = threadIdx.x; k < dz.ndict; k += VB)
@@ -281,7 +294,7 @@ __global__ __launch_bounds__(VB) void k_update_p(CgState* __restrict__ st, doubl
     xi0 = vload<NT>(x2 + c0);
     zi0 = vload<NT>(z2 + c0); // DZ: r
     if (DZ)
-      dc0 = dz.codes[c0];
+      dc0 = dz_load2<DZ>(dz, c0);
   }
   const double alpha_h = it > 0 ? alpha_hist[it - 1] : 0.0; // requested with the rest of the prologue's inputs
   DirScalars S;
@@ -294,7 +307,7 @@ __global__ __launch_bounds__(VB) void k_update_p(CgState* __restrict__ st, doubl
   {
     if (dir)
       for (int64_t i = blockIdx.x * (int64_t)VB + threadIdx.x; i < n; i += (int64_t)gridDim.x * VB)
-        p[i] = DZ ? dtab[reinterpret_cast<const uint16_t*>(dz.codes)[i]] * dz.r[i] : z[i];
+        p[i] = DZ ? dtab[dz_load1<DZ>(dz, i)] * dz.r[i] : z[i];
     return;
   }
   const double alpha = alpha_h;
@@ -317,9 +330,9 @@ __global__ __launch_bounds__(VB) void k_update_p(CgState* __restrict__ st, doubl
     }
     if (DZ)
     {
-      const uint32_t dc = i == i0 ? dc0 : dz.codes[i];
-      zi.x = dtab[dc & 0xffffu] * zi.x; // z = D^-1 r, as k_update_xr formed it for its sums
-      zi.y = dtab[dc >> 16] * zi.y;
+      const uint32_t dc = i == i0 ? dc0 : dz_load2<DZ>(dz, i);
+      zi.x = dtab[dz_lo<DZ>(dc)] * zi.x; // z = D^-1 r, as k_update_xr formed it for its sums
+      zi.y = dtab[dz_hi<DZ>(dc)] * zi.y;
     }
     xi.x = alpha * pi.x + xi.x; // src/cg.h:68, one kernel late
     xi.y = alpha * pi.y + xi.y;
@@ -338,8 +351,28 @@ __global__ __launch_bounds__(VB) void k_update_p(CgState* __restrict__ st, doubl
     const double pi = p[i];
     x[i] = alpha * pi + x[i];
     if (dir)
-      p[i] = bcoef * pi + (DZ ? dtab[reinterpret_cast<const uint16_t*>(dz.codes)[i]] * dz.r[i] : z[i]);
+      p[i] = bcoef * pi + (DZ ? dtab[dz_load1<DZ>(dz, i)] * dz.r[i] : z[i]);
   }
+}
+template <bool NT, bool DZ = false>
+__global__ __launch_bounds__(VB) void k_update_p(CgState* __restrict__ st, double* __restrict__ beta_hist,
+                                                 double* __restrict__ dp_hist, const double* __restrict__ alpha_hist,
+                                                 int it, CgParams P, const double* __restrict__ pa,
+                                                 const double* __restrict__ pb, int np, const double* __restrict__ z,
+                                                 double* __restrict__ p, double* __restrict__ x, int64_t n,
+                                                 int update_dir, DinvCodes dz = DinvCodes())
+{
+  update_p_body<NT, DZ ? 1 : 0>(st, beta_hist, dp_hist, alpha_hist, it, P, pa, pb, np, z, p, x, n, update_dir, dz);
+}
+template <bool NT>
+__global__ __launch_bounds__(VB) void k_update_p_c8(CgState* __restrict__ st, double* __restrict__ beta_hist,
+                                                    double* __restrict__ dp_hist, const double* __restrict__ alpha_hist,
+                                                    int it, CgParams P, const double* __restrict__ pa,
+                                                    const double* __restrict__ pb, int np, const double* __restrict__ z,
+                                                    double* __restrict__ p, double* __restrict__ x, int64_t n,
+                                                    int update_dir, DinvCodes dz)
+{
+  update_p_body<NT, 2>(st, beta_hist, dp_hist, alpha_hist, it, P, pa, pb, np, z, p, x, n, update_dir, dz);
 }
 
 // ---- the solution update deferred (ZZZ_CG_XDEFER): a ring of K direction vectors, x touched once per K iterations ----
@@ -362,7 +395,7 @@ struct PRing
   double* slot[XD_KMAX];
 };
 
-template <bool NT, bool DZ, int NF> // NF: updates applied by this launch (0: the light form; K: the flush form)
+template <bool NT, int DZ, int NF> // NF: updates applied by this launch (0: the light form; K: the flush form)
 __device__ __forceinline__ void update_p_deferred(CgState* __restrict__ st, double* __restrict__ beta_hist, double* __restrict__ dp_hist,
                                                   const double* __restrict__ alpha_hist, int it, const CgParams& P,
                                                   const double* __restrict__ pa, const double* __restrict__ pb, int np,
@@ -370,7 +403,7 @@ __device__ __forceinline__ void update_p_deferred(CgState* __restrict__ st, doub
                                                   double* __restrict__ x, int64_t n, int update_dir, const DinvCodes& dz)
 {
   __shared__ double sh[VB / 64];
-  __shared__ double dtab[DZ ? DZ_MAX : 1];
+  __shared__ double dtab[dz_table(DZ)];
   if (DZ)
   {
     for (int k = threadIdx.x; k < dz.ndict; k += VB)
@@ -395,7 +428,7 @@ __device__ __forceinline__ void update_p_deferred(CgState* __restrict__ st, doub
       xi0 = vload<NT>(x2 + c0);
     zi0 = vload<NT>(z2 + c0); // DZ: r
     if (DZ)
-      dc0 = dz.codes[c0];
+      dc0 = dz_load2<DZ>(dz, c0);
   }
   double al[NF ? NF : 1]; // alpha_{it-K} .. alpha_{it-1}, requested with the rest of the prologue's inputs
   if (NF)
@@ -415,7 +448,7 @@ __device__ __forceinline__ void update_p_deferred(CgState* __restrict__ st, doub
     if (it == 0)
     {
       for (int64_t i = blockIdx.x * (int64_t)VB + threadIdx.x; i < n; i += (int64_t)gridDim.x * VB)
-        pnew[i] = DZ ? dtab[reinterpret_cast<const uint16_t*>(dz.codes)[i]] * dz.r[i] : z[i];
+        pnew[i] = DZ ? dtab[dz_load1<DZ>(dz, i)] * dz.r[i] : z[i];
       return;
     }
   }
@@ -438,9 +471,9 @@ __device__ __forceinline__ void update_p_deferred(CgState* __restrict__ st, doub
     }
     if (DZ)
     {
-      const uint32_t dc = i == i0 ? dc0 : dz.codes[i];
-      zi.x = dtab[dc & 0xffffu] * zi.x; // z = D^-1 r, as k_update_xr formed it for its sums
-      zi.y = dtab[dc >> 16] * zi.y;
+      const uint32_t dc = i == i0 ? dc0 : dz_load2<DZ>(dz, i);
+      zi.x = dtab[dz_lo<DZ>(dc)] * zi.x; // z = D^-1 r, as k_update_xr formed it for its sums
+      zi.y = dtab[dz_hi<DZ>(dc)] * zi.y;
     }
     if (NF)
     {
@@ -479,7 +512,7 @@ __device__ __forceinline__ void update_p_deferred(CgState* __restrict__ st, doub
       x[i] = al[NF - 1] * pi + xi;
     }
     if (dir)
-      pnew[i] = bcoef * pi + (DZ ? dtab[reinterpret_cast<const uint16_t*>(dz.codes)[i]] * dz.r[i] : z[i]);
+      pnew[i] = bcoef * pi + (DZ ? dtab[dz_load1<DZ>(dz, i)] * dz.r[i] : z[i]);
   }
 }
 
@@ -491,7 +524,16 @@ __global__ __launch_bounds__(VB) void k_update_p_light(CgState* __restrict__ st,
                                                        const double* __restrict__ z, const double* pprev, double* pnew, PRing ring,
                                                        double* __restrict__ x, int64_t n, int update_dir, DinvCodes dz)
 {
-  update_p_deferred<NT, DZ, 0>(st, beta_hist, dp_hist, alpha_hist, it, P, pa, pb, np, z, pprev, pnew, ring, x, n, update_dir, dz);
+  update_p_deferred<NT, DZ ? 1 : 0, 0>(st, beta_hist, dp_hist, alpha_hist, it, P, pa, pb, np, z, pprev, pnew, ring, x, n, update_dir, dz);
+}
+template <bool NT>
+__global__ __launch_bounds__(VB) void k_update_p_light_c8(CgState* __restrict__ st, double* __restrict__ beta_hist, double* __restrict__ dp_hist,
+                                                          const double* __restrict__ alpha_hist, int it, CgParams P,
+                                                          const double* __restrict__ pa, const double* __restrict__ pb, int np,
+                                                          const double* __restrict__ z, const double* pprev, double* pnew, PRing ring,
+                                                          double* __restrict__ x, int64_t n, int update_dir, DinvCodes dz)
+{
+  update_p_deferred<NT, 2, 0>(st, beta_hist, dp_hist, alpha_hist, it, P, pa, pb, np, z, pprev, pnew, ring, x, n, update_dir, dz);
 }
 template <bool NT, bool DZ, int K>
 __global__ __launch_bounds__(VB) void k_update_p_flush(CgState* __restrict__ st, double* __restrict__ beta_hist, double* __restrict__ dp_hist,
@@ -500,8 +542,18 @@ __global__ __launch_bounds__(VB) void k_update_p_flush(CgState* __restrict__ st,
                                                        const double* __restrict__ z, const double*, double*, PRing ring,
                                                        double* __restrict__ x, int64_t n, int update_dir, DinvCodes dz)
 {
-  update_p_deferred<NT, DZ, K>(st, beta_hist, dp_hist, alpha_hist, it, P, pa, pb, np, z, ring.slot[K - 1], ring.slot[0], ring, x, n,
-                               update_dir, dz);
+  update_p_deferred<NT, DZ ? 1 : 0, K>(st, beta_hist, dp_hist, alpha_hist, it, P, pa, pb, np, z, ring.slot[K - 1], ring.slot[0], ring, x, n,
+                                       update_dir, dz);
+}
+template <bool NT, int K>
+__global__ __launch_bounds__(VB) void k_update_p_flush_c8(CgState* __restrict__ st, double* __restrict__ beta_hist, double* __restrict__ dp_hist,
+                                                          const double* __restrict__ alpha_hist, int it, CgParams P,
+                                                          const double* __restrict__ pa, const double* __restrict__ pb, int np,
+                                                          const double* __restrict__ z, const double*, double*, PRing ring,
+                                                          double* __restrict__ x, int64_t n, int update_dir, DinvCodes dz)
+{
+  update_p_deferred<NT, 2, K>(st, beta_hist, dp_hist, alpha_hist, it, P, pa, pb, np, z, ring.slot[K - 1], ring.slot[0], ring, x, n,
+                              update_dir, dz);
 }
 
 // The updates still pending when the solve has ended: j in [K floor(c / K), c), c = the iteration the solve stopped at
@@ -552,17 +604,22 @@ static update_p_ring_fn pick_update_p_flush(int K)
 {
   return K == 2 ? k_update_p_flush<NT, DZ, 2> : K == 4 ? k_update_p_flush<NT, DZ, 4> : k_update_p_flush<NT, DZ, 8>;
 }
-
-template <bool NT, bool DZ = false>
-__global__ __launch_bounds__(VB) void k_update_xr(CgState* __restrict__ st, const double* __restrict__ beta_hist,
-                                                  double* __restrict__ alpha_hist, int it,
-                                                  const double* __restrict__ pw_parts, int npw,
-                                                  const double* __restrict__ w, const double* __restrict__ dinv,
-                                                  double* __restrict__ r, double* __restrict__ z, int64_t n, int norm,
-                                                  double* __restrict__ pa, double* __restrict__ pb, int variant,
-                                                  DinvCodes dz = DinvCodes())
+template <bool NT>
+static update_p_ring_fn pick_update_p_flush_c8(int K)
 {
-  __shared__ double dtab[DZ ? DZ_MAX : 1];
+  return K == 2 ? k_update_p_flush_c8<NT, 2> : K == 4 ? k_update_p_flush_c8<NT, 4> : k_update_p_flush_c8<NT, 8>;
+}
+
+template <bool NT, int DZ>
+__device__ __forceinline__ void update_xr_body(CgState* __restrict__ st, const double* __restrict__ beta_hist,
+                                               double* __restrict__ alpha_hist, int it,
+                                               const double* __restrict__ pw_parts, int npw,
+                                               const double* __restrict__ w, const double* __restrict__ dinv,
+                                               double* __restrict__ r, double* __restrict__ z, int64_t n, int norm,
+                                               double* __restrict__ pa, double* __restrict__ pb, int variant,
+                                               const DinvCodes& dz)
+{
+  __shared__ double dtab[dz_table(DZ)];
   if (DZ)
   {
     for (int k = threadIdx.x; k < dz.ndict; k += VB)
@@ -584,7 +641,7 @@ __global__ __launch_bounds__(VB) void k_update_xr(CgState* __restrict__ st, cons
   {
     wi0 = vload<NT>(w2 + c0); // last use of w
     if (DZ)
-      dc0 = dz.codes[c0];
+      dc0 = dz_load2<DZ>(dz, c0);
     else
       di0 = vload<NT>(d2 + c0);
     ri0 = vload<NT>(r2 + c0); // r and D^-1 are touched once per iteration
@@ -630,9 +687,9 @@ __global__ __launch_bounds__(VB) void k_update_xr(CgState* __restrict__ st, cons
     }
     if (DZ)
     {
-      const uint32_t dc = i == i0 ? dc0 : dz.codes[i];
-      di.x = dtab[dc & 0xffffu];
-      di.y = dtab[dc >> 16];
+      const uint32_t dc = i == i0 ? dc0 : dz_load2<DZ>(dz, i);
+      di.x = dtab[dz_lo<DZ>(dc)];
+      di.y = dtab[dz_hi<DZ>(dc)];
     }
     ri.x = -alpha * wi.x + ri.x; // src/cg.h:71
     ri.y = -alpha * wi.y + ri.y;
@@ -662,7 +719,7 @@ __global__ __launch_bounds__(VB) void k_update_xr(CgState* __restrict__ st, cons
   {
     const int64_t i = n - 1;
     const double ri = -alpha * w[i] + r[i];
-    const double zi = (DZ ? dtab[reinterpret_cast<const uint16_t*>(dz.codes)[i]] : dinv[i]) * ri;
+    const double zi = (DZ ? dtab[dz_load1<DZ>(dz, i)] : dinv[i]) * ri;
     r[i] = ri;
     if (!DZ)
       z[i] = zi;
@@ -677,6 +734,27 @@ __global__ __launch_bounds__(VB) void k_update_xr(CgState* __restrict__ st, cons
     pb[blockIdx.x] = tb;
   }
 }
+template <bool NT, bool DZ = false>
+__global__ __launch_bounds__(VB) void k_update_xr(CgState* __restrict__ st, const double* __restrict__ beta_hist,
+                                                  double* __restrict__ alpha_hist, int it,
+                                                  const double* __restrict__ pw_parts, int npw,
+                                                  const double* __restrict__ w, const double* __restrict__ dinv,
+                                                  double* __restrict__ r, double* __restrict__ z, int64_t n, int norm,
+                                                  double* __restrict__ pa, double* __restrict__ pb, int variant,
+                                                  DinvCodes dz = DinvCodes())
+{
+  update_xr_body<NT, DZ ? 1 : 0>(st, beta_hist, alpha_hist, it, pw_parts, npw, w, dinv, r, z, n, norm, pa, pb, variant, dz);
+}
+template <bool NT>
+__global__ __launch_bounds__(VB) void k_update_xr_c8(CgState* __restrict__ st, const double* __restrict__ beta_hist,
+                                                     double* __restrict__ alpha_hist, int it,
+                                                     const double* __restrict__ pw_parts, int npw,
+                                                     const double* __restrict__ w, const double* __restrict__ dinv,
+                                                     double* __restrict__ r, double* __restrict__ z, int64_t n, int norm,
+                                                     double* __restrict__ pa, double* __restrict__ pb, int variant, DinvCodes dz)
+{
+  update_xr_body<NT, 2>(st, beta_hist, alpha_hist, it, pw_parts, npw, w, dinv, r, z, n, norm, pa, pb, variant, dz);
+}
 
 // ---- PETSc's -ksp_cg_single_reduction (KSPCGUseSingleReduction; Chronopoulos/Gear form) ----------
 // One iteration = this kernel + one SpMV (s = A z with the partials of <z,s>, <r,z> and the norm):
@@ -689,18 +767,18 @@ __global__ __launch_bounds__(VB) void k_update_xr(CgState* __restrict__ st, cons
 // DZ (round 5): as in k_update_p -- Jacobi's inverse diagonal as 16-bit codes into a table in LDS, and z = D^-1 r of the
 // LAST iteration recomputed from the r this kernel reads anyway (the same product of the same two doubles: the same bits)
 // instead of read back: 96 -> 82 B per row and iteration.  z is still written: the product gathers it.
-template <bool NT, bool CHEB = false, bool DZ = false>
-__global__ __launch_bounds__(VB) void k_sr_update(CgState* __restrict__ st, double* __restrict__ beta_hist,
-                                                  double* __restrict__ dpi_hist, double* __restrict__ dp_hist, int it,
-                                                  CgParams P, const double* __restrict__ pa, const double* __restrict__ pb,
-                                                  const double* __restrict__ pc, int np, const double* __restrict__ dinv,
-                                                  const double* __restrict__ s, double* __restrict__ z, double* __restrict__ p,
-                                                  double* __restrict__ w, double* __restrict__ x, double* __restrict__ r,
-                                                  int64_t n, int scalars_only, double theta = 0.0, double* __restrict__ chg = nullptr,
-                                                  double* __restrict__ chd = nullptr, DinvCodes dz = DinvCodes())
+template <bool NT, bool CHEB, int DZ>
+__device__ __forceinline__ void sr_update_body(CgState* __restrict__ st, double* __restrict__ beta_hist,
+                                               double* __restrict__ dpi_hist, double* __restrict__ dp_hist, int it,
+                                               const CgParams& P, const double* __restrict__ pa, const double* __restrict__ pb,
+                                               const double* __restrict__ pc, int np, const double* __restrict__ dinv,
+                                               const double* __restrict__ s, double* __restrict__ z, double* __restrict__ p,
+                                               double* __restrict__ w, double* __restrict__ x, double* __restrict__ r,
+                                               int64_t n, int scalars_only, double theta, double* __restrict__ chg,
+                                               double* __restrict__ chd, const DinvCodes& dz)
 {
   static_assert(!(CHEB && DZ), "the polynomial's first term is not D^-1 r alone");
-  __shared__ double dtab[DZ ? DZ_MAX : 1];
+  __shared__ double dtab[dz_table(DZ)];
   if (DZ)
   {
     for (int k = threadIdx.x; k < dz.ndict; k += VB)
@@ -722,7 +800,7 @@ __global__ __launch_bounds__(VB) void k_sr_update(CgState* __restrict__ st, doub
   if (n2 > 0 && !scalars_only)
   {
     if (DZ)
-      dc0 = dz.codes[c0];
+      dc0 = dz_load2<DZ>(dz, c0);
     else
     {
       zi0 = z2[c0];
@@ -794,7 +872,7 @@ __global__ __launch_bounds__(VB) void k_sr_update(CgState* __restrict__ st, doub
   if (conv || scalars_only)
     return;
   auto one = [&](int64_t i) {
-    const double dv = DZ ? dtab[reinterpret_cast<const uint16_t*>(dz.codes)[i]] : dinv[i];
+    const double dv = DZ ? dtab[dz_load1<DZ>(dz, i)] : dinv[i];
     const double zo = DZ ? dv * r[i] : z[i];
     const double pn = (it == 0) ? zo : b * p[i] + zo;
     const double wn = (it == 0) ? s[i] : b * w[i] + s[i];
@@ -826,7 +904,7 @@ __global__ __launch_bounds__(VB) void k_sr_update(CgState* __restrict__ st, doub
     else
     {
       if (DZ)
-        dc = dz.codes[i];
+        dc = dz_load2<DZ>(dz, i);
       else
         zi = z2[i], di = vload<NT>(d2 + i);
       si = vload<NT>(s2 + i), xi = vload<NT>(x2 + i), ri = vload<NT>(r2 + i);
@@ -835,8 +913,8 @@ __global__ __launch_bounds__(VB) void k_sr_update(CgState* __restrict__ st, doub
     }
     if (DZ)
     {
-      di.x = dtab[dc & 0xffffu];
-      di.y = dtab[dc >> 16];
+      di.x = dtab[dz_lo<DZ>(dc)];
+      di.y = dtab[dz_hi<DZ>(dc)];
       zi.x = di.x * ri.x; // z = D^-1 r as the last iteration (or k_init_residual) formed it
       zi.y = di.y * ri.y;
     }
@@ -872,6 +950,32 @@ __global__ __launch_bounds__(VB) void k_sr_update(CgState* __restrict__ st, doub
   }
   if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0)
     one(n - 1);
+}
+template <bool NT, bool CHEB = false, bool DZ = false>
+__global__ __launch_bounds__(VB) void k_sr_update(CgState* __restrict__ st, double* __restrict__ beta_hist,
+                                                  double* __restrict__ dpi_hist, double* __restrict__ dp_hist, int it,
+                                                  CgParams P, const double* __restrict__ pa, const double* __restrict__ pb,
+                                                  const double* __restrict__ pc, int np, const double* __restrict__ dinv,
+                                                  const double* __restrict__ s, double* __restrict__ z, double* __restrict__ p,
+                                                  double* __restrict__ w, double* __restrict__ x, double* __restrict__ r,
+                                                  int64_t n, int scalars_only, double theta = 0.0, double* __restrict__ chg = nullptr,
+                                                  double* __restrict__ chd = nullptr, DinvCodes dz = DinvCodes())
+{
+  sr_update_body<NT, CHEB, DZ ? 1 : 0>(st, beta_hist, dpi_hist, dp_hist, it, P, pa, pb, pc, np, dinv, s, z, p, w, x, r, n, scalars_only,
+                                       theta, chg, chd, dz);
+}
+template <bool NT>
+__global__ __launch_bounds__(VB) void k_sr_update_c8(CgState* __restrict__ st, double* __restrict__ beta_hist,
+                                                     double* __restrict__ dpi_hist, double* __restrict__ dp_hist, int it,
+                                                     CgParams P, const double* __restrict__ pa, const double* __restrict__ pb,
+                                                     const double* __restrict__ pc, int np, const double* __restrict__ dinv,
+                                                     const double* __restrict__ s, double* __restrict__ z, double* __restrict__ p,
+                                                     double* __restrict__ w, double* __restrict__ x, double* __restrict__ r,
+                                                     int64_t n, int scalars_only, double theta, double* __restrict__ chg,
+                                                     double* __restrict__ chd, DinvCodes dz)
+{
+  sr_update_body<NT, false, 2>(st, beta_hist, dpi_hist, dp_hist, it, P, pa, pb, pc, np, dinv, s, z, p, w, x, r, n, scalars_only, theta,
+                               chg, chd, dz);
 }
 
 __device__ inline double reduce_parts(const double* __restrict__ parts, int np, double* sh)
@@ -912,11 +1016,14 @@ int dinv_codes_build(zzz_ctx* ctx, int64_t n, DinvCodes& dzc)
   const unsigned gd = (unsigned)std::min<int64_t>((n + 255) / 256, 4096);
   hipLaunchKernelGGL(k_dd_insert, dim3(gd), dim3(256), 0, s, ctx->dinv.p, n, vs.table.p, vs.info.p, DZ_MAX);
   vs.number(s);
-  hipLaunchKernelGGL(k_dd_encode, dim3(gd), dim3(256), 0, s, ctx->dinv.p, n, npad, vs.table.p, vs.slot.p, ctx->dd_codes.p, vs.info.p);
+  // ZZZ_CG_DINV_CODES=3: 16-bit codes even where 8 would do (the A/B reference of the 8-bit form)
+  const int allow8 = ctx->cg_dinv_codes != 3;
+  hipLaunchKernelGGL(k_dd_encode, dim3(gd), dim3(256), 0, s, ctx->dinv.p, n, npad, vs.table.p, vs.slot.p, ctx->dd_codes.p, vs.info.p,
+                     allow8);
   int nd = 0;
   ZZZ_HIP(ctx, vs.finish(s, nd));
   if (nd)
-    dzc = DinvCodes{reinterpret_cast<const uint32_t*>(ctx->dd_codes.p), vs.dict.p, ctx->r.p, nd};
+    dzc = DinvCodes{reinterpret_cast<const uint32_t*>(ctx->dd_codes.p), vs.dict.p, ctx->r.p, nd, (allow8 && nd <= DZ8_MAX) ? 8 : 16};
   return ZZZ_OK;
 }
 
@@ -1011,6 +1118,7 @@ void cg_report_reset(zzz_ctx* ctx)
   ctx->last_solve_red_overlapped = false;
   ctx->last_solve_xdefer_k = 1;
   ctx->last_solve_dinv_codes = 0;
+  ctx->last_solve_dinv_bits = 0;
 }
 
 int CgSolve::begin(zzz_ctx* c, const zzz_solver_opts* opts, int prof_stride)
@@ -1151,8 +1259,17 @@ int cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
   hipStream_t s = ctx->stream;
   const bool nt = loop_exceeds_cache(ctx, 6);
   // (kernels by load policy and by whether z is recomputed from the coded inverse diagonal: chosen where dz is known)
-  auto pick_update_p = [&](bool dzf) { return dzf ? (nt ? k_update_p<true, true> : k_update_p<false, true>) : (nt ? k_update_p<true, false> : k_update_p<false, false>); };
-  auto pick_update_xr = [&](bool dzf) { return dzf ? (nt ? k_update_xr<true, true> : k_update_xr<false, true>) : (nt ? k_update_xr<true, false> : k_update_xr<false, false>); };
+  // (dzb: the codes' width, 0 without codes)
+  auto pick_update_p = [&](int dzb) {
+    return dzb == 8 ? (nt ? k_update_p_c8<true> : k_update_p_c8<false>)
+           : dzb    ? (nt ? k_update_p<true, true> : k_update_p<false, true>)
+                    : (nt ? k_update_p<true, false> : k_update_p<false, false>);
+  };
+  auto pick_update_xr = [&](int dzb) {
+    return dzb == 8 ? (nt ? k_update_xr_c8<true> : k_update_xr_c8<false>)
+           : dzb    ? (nt ? k_update_xr<true, true> : k_update_xr<false, true>)
+                    : (nt ? k_update_xr<true, false> : k_update_xr<false, false>);
+  };
 
   CgSolve S;
   if (int rc = S.begin(ctx, o))
@@ -1178,14 +1295,16 @@ int cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
   // Jacobi's inverse diagonal as 16-bit codes and no z vector (DinvCodes, k_update_p): KSPCG + PCJACOBI, a loop too large for
   // the Infinity Cache (where bytes are what the vector kernels wait for: the criterion of their load policy;
   // ZZZ_CG_DINV_CODES: 0 never, 2 at any size), at most 2 048 values
-  DinvCodes dzc{nullptr, nullptr, nullptr, 0};
-  if (o->variant == ZZZ_CG_PETSC && o->pc == ZZZ_PC_JACOBI && ctx->cg_dinv_codes != 0 && (ctx->cg_dinv_codes == 2 || nt))
+  DinvCodes dzc{nullptr, nullptr, nullptr, 0, 0};
+  if (o->variant == ZZZ_CG_PETSC && o->pc == ZZZ_PC_JACOBI && ctx->cg_dinv_codes != 0 && (ctx->cg_dinv_codes >= 2 || nt))
     if (int rc = dinv_codes_build(ctx, n, dzc))
       return rc;
   ctx->last_solve_dinv_codes = dzc.codes ? dzc.ndict : 0;
+  ctx->last_solve_dinv_bits = dzc.codes ? dzc.bits : 0;
   const bool dz = dzc.codes != nullptr;
-  auto kern_update_p = pick_update_p(dz);
-  auto kern_update_xr = pick_update_xr(dz);
+  const bool dz8 = dz && dzc.bits == 8;
+  auto kern_update_p = pick_update_p(dz ? dzc.bits : 0);
+  auto kern_update_xr = pick_update_xr(dz ? dzc.bits : 0);
 
   // The solution update deferred (k_update_p_light / _flush): where x comes from HBM, i.e. under the same rule as the
   // load policy (ZZZ_CG_XDEFER: 0 never, 2 at any size; ZZZ_CG_XDEFER_K: the ring's length).  Slot 0 is ctx->p, the other
@@ -1219,10 +1338,12 @@ int cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
   update_p_ring_fn kern_light = nullptr, kern_flush = nullptr;
   if (K > 1)
   {
-    kern_light = dz ? (nt ? k_update_p_light<true, true> : k_update_p_light<false, true>)
-                    : (nt ? k_update_p_light<true, false> : k_update_p_light<false, false>);
-    kern_flush = dz ? (nt ? pick_update_p_flush<true, true>(K) : pick_update_p_flush<false, true>(K))
-                    : (nt ? pick_update_p_flush<true, false>(K) : pick_update_p_flush<false, false>(K));
+    kern_light = dz8  ? (nt ? k_update_p_light_c8<true> : k_update_p_light_c8<false>)
+                 : dz ? (nt ? k_update_p_light<true, true> : k_update_p_light<false, true>)
+                      : (nt ? k_update_p_light<true, false> : k_update_p_light<false, false>);
+    kern_flush = dz8  ? (nt ? pick_update_p_flush_c8<true>(K) : pick_update_p_flush_c8<false>(K))
+                 : dz ? (nt ? pick_update_p_flush<true, true>(K) : pick_update_p_flush<false, true>(K))
+                      : (nt ? pick_update_p_flush<true, false>(K) : pick_update_p_flush<false, false>(K));
   }
   // the test of iteration k and (update_dir) the direction p_k; where p_k lives
   auto dir_of = [&](int k) { return ring.slot[k % K]; };
@@ -1921,15 +2042,17 @@ static int cg_solve_single_reduction(zzz_ctx* ctx, const zzz_solver_opts* o, int
                      o->pc != ZZZ_PC_NONE ? 1 : 0);
   // Jacobi's inverse diagonal as 16-bit codes, z of the last iteration recomputed from r (k_sr_update<.., DZ>): under the
   // rule of the classical form (a loop too large for the Infinity Cache; ZZZ_CG_DINV_CODES: 0 never, 2 at any size)
-  DinvCodes dzc{nullptr, nullptr, nullptr, 0};
-  if (!cheb && o->pc == ZZZ_PC_JACOBI && ctx->cg_dinv_codes != 0 && (ctx->cg_dinv_codes == 2 || ntv))
+  DinvCodes dzc{nullptr, nullptr, nullptr, 0, 0};
+  if (!cheb && o->pc == ZZZ_PC_JACOBI && ctx->cg_dinv_codes != 0 && (ctx->cg_dinv_codes >= 2 || ntv))
     if (int rc = dinv_codes_build(ctx, n, dzc))
       return rc;
   ctx->last_solve_dinv_codes = dzc.codes ? dzc.ndict : 0;
+  ctx->last_solve_dinv_bits = dzc.codes ? dzc.bits : 0;
   const bool dz = dzc.codes != nullptr;
   auto kern_sr_update = cheb ? (ntv ? k_sr_update<true, true> : k_sr_update<false, true>)
-                             : (dz ? (ntv ? k_sr_update<true, false, true> : k_sr_update<false, false, true>)
-                                   : (ntv ? k_sr_update<true> : k_sr_update<false>));
+                        : (dz && dzc.bits == 8) ? (ntv ? k_sr_update_c8<true> : k_sr_update_c8<false>)
+                        : dz                    ? (ntv ? k_sr_update<true, false, true> : k_sr_update<false, false, true>)
+                                                : (ntv ? k_sr_update<true> : k_sr_update<false>);
   // r = b, z = D^-1 r (the partials of this kernel are not used: the SpMV below leaves all three)
   hipLaunchKernelGGL(k_init_residual, dim3(g), dim3(VB), 0, s, ctx->b.p, (const double*)nullptr, ctx->dinv.p, ctx->r.p,
                      ctx->z.p, n, P.norm, ctx->part_b.p, ctx->part_b.p + VGRID_MAX);

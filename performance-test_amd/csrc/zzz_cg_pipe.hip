@@ -65,19 +65,20 @@ __global__ __launch_bounds__(VB) void k_pipe_start(const double* __restrict__ di
 // gamma = <r,u>, delta = <w,u> and the test norm^2 of iteration `it`; qa/qb/qc: where this launch leaves the partials of
 // iteration it + 1 (another set than pa/pb/pc: workgroups of one launch read the one while others already write the
 // other).  nv = A m of this iteration.  scalars_only: the test of the last completed iteration (one workgroup).
-// DZ: D^-1 as 16-bit codes into a table in LDS (DinvCodes), 2 B per row instead of 8.
-template <bool NT, bool DZ>
-__global__ __launch_bounds__(VB) void k_pipe_update(CgState* __restrict__ st, double* __restrict__ gamma_hist,
-                                                    double* __restrict__ alpha_hist, double* __restrict__ dp_hist, int it,
-                                                    CgParams P, const double* __restrict__ pa, const double* __restrict__ pb,
-                                                    const double* __restrict__ pc, int np, const double* __restrict__ dinv,
-                                                    const double* __restrict__ nv, double* __restrict__ z,
-                                                    double* __restrict__ s, double* __restrict__ p, double* __restrict__ x,
-                                                    double* __restrict__ r, double* __restrict__ w, double* __restrict__ m,
-                                                    int64_t n, int scalars_only, double* __restrict__ qa,
-                                                    double* __restrict__ qb, double* __restrict__ qc, DinvCodes dz)
+// DZ: D^-1 as codes into a table in LDS (DinvCodes), 2 B per row instead of 8 (DZ = 1, 16-bit codes) or 1 B (DZ = 2, 8-bit
+// codes: k_pipe_update_c8).
+template <bool NT, int DZ>
+__device__ __forceinline__ void pipe_update_body(CgState* __restrict__ st, double* __restrict__ gamma_hist,
+                                                 double* __restrict__ alpha_hist, double* __restrict__ dp_hist, int it,
+                                                 const CgParams& P, const double* __restrict__ pa, const double* __restrict__ pb,
+                                                 const double* __restrict__ pc, int np, const double* __restrict__ dinv,
+                                                 const double* __restrict__ nv, double* __restrict__ z,
+                                                 double* __restrict__ s, double* __restrict__ p, double* __restrict__ x,
+                                                 double* __restrict__ r, double* __restrict__ w, double* __restrict__ m,
+                                                 int64_t n, int scalars_only, double* __restrict__ qa,
+                                                 double* __restrict__ qb, double* __restrict__ qc, const DinvCodes& dz)
 {
-  __shared__ double dtab[DZ ? DZ_MAX : 1];
+  __shared__ double dtab[dz_table(DZ)];
   if (DZ)
   {
     for (int k = threadIdx.x; k < dz.ndict; k += VB)
@@ -100,7 +101,7 @@ __global__ __launch_bounds__(VB) void k_pipe_update(CgState* __restrict__ st, do
   if (n2 > 0 && !scalars_only)
   {
     if (DZ)
-      dc0 = dz.codes[c0];
+      dc0 = dz_load2<DZ>(dz, c0);
     else
       di0 = vload<NT>(d2 + c0);
     ni0 = vload<NT>(n2v + c0);
@@ -183,7 +184,7 @@ __global__ __launch_bounds__(VB) void k_pipe_update(CgState* __restrict__ st, do
     else
     {
       if (DZ)
-        dc = dz.codes[i];
+        dc = dz_load2<DZ>(dz, i);
       else
         di = vload<NT>(d2 + i);
       ni = vload<NT>(n2v + i), ri = vload<NT>(r2 + i), wi = vload<NT>(w2 + i), xi = vload<NT>(x2 + i);
@@ -192,8 +193,8 @@ __global__ __launch_bounds__(VB) void k_pipe_update(CgState* __restrict__ st, do
     }
     if (DZ)
     {
-      di.x = dtab[dc & 0xffffu];
-      di.y = dtab[dc >> 16];
+      di.x = dtab[dz_lo<DZ>(dc)];
+      di.y = dtab[dz_hi<DZ>(dc)];
     }
     dbl2 ui, zn = ni, sn = wi, pn, un, mn;
     ui.x = di.x * ri.x; // u = D^-1 r as the last launch formed it for its sums
@@ -243,7 +244,7 @@ __global__ __launch_bounds__(VB) void k_pipe_update(CgState* __restrict__ st, do
   if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0)
   {
     const int64_t i = n - 1;
-    const double dv = DZ ? dtab[reinterpret_cast<const uint16_t*>(dz.codes)[i]] : dinv[i];
+    const double dv = DZ ? dtab[dz_load1<DZ>(dz, i)] : dinv[i];
     const double ui = dv * r[i];
     const double zn = (it == 0) ? nv[i] : beta * z[i] + nv[i];
     const double sn = (it == 0) ? w[i] : beta * s[i] + w[i];
@@ -272,6 +273,34 @@ __global__ __launch_bounds__(VB) void k_pipe_update(CgState* __restrict__ st, do
     qc[blockIdx.x] = tc;
   }
 }
+template <bool NT, bool DZ>
+__global__ __launch_bounds__(VB) void k_pipe_update(CgState* __restrict__ st, double* __restrict__ gamma_hist,
+                                                    double* __restrict__ alpha_hist, double* __restrict__ dp_hist, int it,
+                                                    CgParams P, const double* __restrict__ pa, const double* __restrict__ pb,
+                                                    const double* __restrict__ pc, int np, const double* __restrict__ dinv,
+                                                    const double* __restrict__ nv, double* __restrict__ z,
+                                                    double* __restrict__ s, double* __restrict__ p, double* __restrict__ x,
+                                                    double* __restrict__ r, double* __restrict__ w, double* __restrict__ m,
+                                                    int64_t n, int scalars_only, double* __restrict__ qa,
+                                                    double* __restrict__ qb, double* __restrict__ qc, DinvCodes dz)
+{
+  pipe_update_body<NT, DZ ? 1 : 0>(st, gamma_hist, alpha_hist, dp_hist, it, P, pa, pb, pc, np, dinv, nv, z, s, p, x, r, w, m, n,
+                                   scalars_only, qa, qb, qc, dz);
+}
+template <bool NT>
+__global__ __launch_bounds__(VB) void k_pipe_update_c8(CgState* __restrict__ st, double* __restrict__ gamma_hist,
+                                                       double* __restrict__ alpha_hist, double* __restrict__ dp_hist, int it,
+                                                       CgParams P, const double* __restrict__ pa, const double* __restrict__ pb,
+                                                       const double* __restrict__ pc, int np, const double* __restrict__ dinv,
+                                                       const double* __restrict__ nv, double* __restrict__ z,
+                                                       double* __restrict__ s, double* __restrict__ p, double* __restrict__ x,
+                                                       double* __restrict__ r, double* __restrict__ w, double* __restrict__ m,
+                                                       int64_t n, int scalars_only, double* __restrict__ qa,
+                                                       double* __restrict__ qb, double* __restrict__ qc, DinvCodes dz)
+{
+  pipe_update_body<NT, 2>(st, gamma_hist, alpha_hist, dp_hist, it, P, pa, pb, pc, np, dinv, nv, z, s, p, x, r, w, m, n, scalars_only, qa,
+                          qb, qc, dz);
+}
 
 int cg_solve_pipe(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
 {
@@ -299,13 +328,15 @@ int cg_solve_pipe(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rn
   cg_launch_extract_dinv(ctx, n, o->pc == ZZZ_PC_JACOBI ? 1 : 0);
   // Jacobi's inverse diagonal as 16-bit codes: under the rule of the other forms (a loop too large for the Infinity
   // Cache; ZZZ_CG_DINV_CODES: 0 never, 2 at any size)
-  DinvCodes dzc{nullptr, nullptr, nullptr, 0};
-  if (o->pc == ZZZ_PC_JACOBI && ctx->cg_dinv_codes != 0 && (ctx->cg_dinv_codes == 2 || ntv))
+  DinvCodes dzc{nullptr, nullptr, nullptr, 0, 0};
+  if (o->pc == ZZZ_PC_JACOBI && ctx->cg_dinv_codes != 0 && (ctx->cg_dinv_codes >= 2 || ntv))
     if (int rc = dinv_codes_build(ctx, n, dzc))
       return rc;
   ctx->last_solve_dinv_codes = dzc.codes ? dzc.ndict : 0;
-  auto kern = dzc.codes ? (ntv ? k_pipe_update<true, true> : k_pipe_update<false, true>)
-                        : (ntv ? k_pipe_update<true, false> : k_pipe_update<false, false>);
+  ctx->last_solve_dinv_bits = dzc.codes ? dzc.bits : 0;
+  auto kern = (dzc.codes && dzc.bits == 8) ? (ntv ? k_pipe_update_c8<true> : k_pipe_update_c8<false>)
+              : dzc.codes                  ? (ntv ? k_pipe_update<true, true> : k_pipe_update<false, true>)
+                                           : (ntv ? k_pipe_update<true, false> : k_pipe_update<false, false>);
 
   double *x = ctx->u.p, *r = ctx->r.p, *w = ctx->w.p, *m = ctx->pipe_m.p, *nvec = ctx->pipe_n.p;
   // y = A v on the form the matrix took; the partials of <v,y> the product leaves in part_a are not used (asking for

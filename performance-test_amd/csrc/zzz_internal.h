@@ -337,11 +337,13 @@ struct zzz_ctx
   bool sp_special_tried = false; // the special forms were built or declined for the current values
   bool sellp_early = true;       // ZZZ_SELLP_EARLY=0: pack the generic stream at every assembly, special forms at the first product (A/B)
   int sellp_dict = 1;       // ZZZ_SELLP_DICT=0: no value dictionary
-  // Jacobi's inverse diagonal as 16-bit codes (zzz_cg.hip, DinvCodes)
+  // Jacobi's inverse diagonal as 8- or 16-bit codes (zzz_cg.hip, DinvCodes)
   zzz::ValSet<14, 0> dd_set;
-  zzz::DevBuf<uint16_t> dd_codes;
-  int cg_dinv_codes = 1;          // ZZZ_CG_DINV_CODES: 0 never, 1 when the CG loop exceeds the Infinity Cache, 2 always
+  zzz::DevBuf<uint16_t> dd_codes; // (8-bit codes: the first half of it, one byte per entry)
+  int cg_dinv_codes = 1;          // ZZZ_CG_DINV_CODES: 0 never, 1 when the CG loop exceeds the Infinity Cache, 2 always,
+                                  // 3 always and 16-bit codes even where 8 bits would do (A/B)
   int last_solve_dinv_codes = 0;  // distinct values of the inverse diagonal when the last solve ran on codes, else 0
+  int last_solve_dinv_bits = 0;   // ... and the width of a code, 8 or 16 (0 without codes)
   // the classical loop's solution update applied once per K iterations from a ring of K direction vectors (zzz_cg.hip,
   // k_update_p_light / _flush): slot 0 of the ring is `p`, these are slots 1 .. K-1
   zzz::DevBuf<double> p_ring[7];

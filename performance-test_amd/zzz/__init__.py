@@ -712,7 +712,8 @@ class Context:
     def cg_info(self):
         info = (C.c_int64 * 4)()
         self._ck(self.L.zzz_cg_info(self.h, info))
-        return {"fused": bool(info[0] & 1), "dinv_codes": int(info[0] >> 8) if info[0] & 2 else 0,
+        return {"fused": bool(info[0] & 1), "dinv_codes": int((info[0] >> 8) & 0xffffff) if info[0] & 2 else 0,
+                "dinv_code_bits": (8 if (info[0] >> 32) & 1 else 16) if info[0] & 2 else 0,
                 "allreduce_overlapped": bool(info[0] & 4), "xdefer_k": int((info[0] >> 4) & 15) if info[0] & 8 else 1,
                 "reason": int(info[2]),
                 "pc_spectrum_bound": info[3] * 1.0e-6}
