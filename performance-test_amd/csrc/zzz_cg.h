@@ -10,6 +10,8 @@
 #include "zzz_device.h"
 #include "zzz_internal.h"
 
+#include <type_traits>
+
 namespace zzz
 {
 typedef double dbl2 __attribute__((ext_vector_type(2)));
@@ -104,9 +106,34 @@ struct DinvCodes
 constexpr int DZ_MAX = 2048;
 constexpr int DZ8_MAX = 256;
 
-// The kernels that take DinvCodes are compiled per form of the inverse diagonal, DZ: 0 doubles, 1 16-bit codes, 2 8-bit
-// codes (the LDS table then holds DZ8_MAX entries).  A dbl2 access' two codes are one load either way.
+// The kernels that take DinvCodes are compiled per form of the inverse diagonal, their template parameter DZ: 0 doubles,
+// 1 16-bit codes, 2 8-bit codes (the LDS table then holds DZ8_MAX entries).  One __global__ entry point per kernel; the
+// host turns the load policy and dz_form() into its template arguments with dz_dispatch.  A dbl2 access' two codes are
+// one load either way.
 constexpr int dz_table(int DZ) { return DZ == 2 ? DZ8_MAX : DZ == 1 ? DZ_MAX : 1; }
+inline int dz_form(const DinvCodes& dz) { return !dz.codes ? 0 : dz.bits == 8 ? 2 : 1; }
+// f(std::integral_constant<bool, NT>, std::integral_constant<int, DZ>) for the pair that (nt, form) name
+template <typename F>
+auto dz_dispatch(bool nt, int form, F f)
+{
+  auto by_form = [&](auto NT) {
+    return form == 2   ? f(NT, std::integral_constant<int, 2>{})
+           : form == 1 ? f(NT, std::integral_constant<int, 1>{})
+                       : f(NT, std::integral_constant<int, 0>{});
+  };
+  return nt ? by_form(std::true_type{}) : by_form(std::false_type{});
+}
+// the dictionary into the kernel's LDS table (dtab[dz_table(DZ)]), by the whole workgroup
+template <int DZ>
+__device__ __forceinline__ void dz_stage(double (&dtab)[dz_table(DZ)], const DinvCodes& dz)
+{
+  if (DZ)
+  {
+    for (int k = threadIdx.x; k < dz.ndict; k += VB)
+      dtab[k] = dz.dict[k];
+    __syncthreads();
+  }
+}
 template <int DZ>
 __device__ inline uint32_t dz_load2(const DinvCodes& dz, int64_t i2) // the codes of entries 2 i2 and 2 i2 + 1
 {

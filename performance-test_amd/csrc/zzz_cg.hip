@@ -257,25 +257,20 @@ __global__ __launch_bounds__(VB) void k_init_residual(const double* __restrict__
 // z = D^-1 r is cheaper to RECOMPUTE here from r (the same product of the same two doubles: the same bits) than to
 // write in k_update_xr and read back: 80 -> 68 B per row and iteration for the two kernels.  dz.codes = nullptr: off.
 // With at most 256 distinct values the codes are bytes (DZ = 2 of zzz_cg.h): 1 B per row, 66 B for the two kernels.  The
-// table entry a code selects is the same double, so nothing downstream changes.  Each kernel below is a body compiled per
-// DZ and two __global__ entry points: the one it always had (doubles | 16-bit codes) and a `_c8` one for the 8-bit codes.
+// table entry a code selects is the same double, so nothing downstream changes.  Each kernel below is one __global__
+// template compiled per DZ (0 doubles, 1 16-bit codes, 2 8-bit codes); the drivers pick the instantiation with dz_dispatch.
 
-template <bool NT, int DZ>
-__device__ __forceinline__ void update_p_body(CgState* __restrict__ st, double* __restrict__ beta_hist,
-                                              double* __restrict__ dp_hist, const double* __restrict__ alpha_hist,
-                                              int it, const CgParams& P, const double* __restrict__ pa,
-                                              const double* __restrict__ pb, int np, const double* __restrict__ z,
-                                              double* __restrict__ p, double* __restrict__ x, int64_t n,
-                                              int update_dir, const DinvCodes& dz)
+template <bool NT, int DZ = 0>
+__global__ __launch_bounds__(VB) void k_update_p(CgState* __restrict__ st, double* __restrict__ beta_hist,
+                                                 double* __restrict__ dp_hist, const double* __restrict__ alpha_hist,
+                                                 int it, CgParams P, const double* __restrict__ pa,
+                                                 const double* __restrict__ pb, int np, const double* __restrict__ z,
+                                                 double* __restrict__ p, double* __restrict__ x, int64_t n,
+                                                 int update_dir, DinvCodes dz = DinvCodes())
 {
   __shared__ double sh[VB / 64];
   __shared__ double dtab[dz_table(DZ)];
-  if (DZ)
-  {
-    for (int k = threadIdx.x; k < dz.ndict; k += VB)
-      dtab[k] = dz.dict[k];
-    __syncthreads();
-  }
+  dz_stage<DZ>(dtab, dz);
   // The first entries of this thread are requested BEFORE the scalar prologue (flag, partial sums, convergence logic: a
   // chain of dependent loads and barriers of 3-5 us that every workgroup walks): at the 8-GPU per-rank size a thread
   // has one or two entries in all, so the kernel was prologue + one memory round trip in sequence (11-12 us for 50 MB
@@ -354,26 +349,6 @@ __device__ __forceinline__ void update_p_body(CgState* __restrict__ st, double* 
       p[i] = bcoef * pi + (DZ ? dtab[dz_load1<DZ>(dz, i)] * dz.r[i] : z[i]);
   }
 }
-template <bool NT, bool DZ = false>
-__global__ __launch_bounds__(VB) void k_update_p(CgState* __restrict__ st, double* __restrict__ beta_hist,
-                                                 double* __restrict__ dp_hist, const double* __restrict__ alpha_hist,
-                                                 int it, CgParams P, const double* __restrict__ pa,
-                                                 const double* __restrict__ pb, int np, const double* __restrict__ z,
-                                                 double* __restrict__ p, double* __restrict__ x, int64_t n,
-                                                 int update_dir, DinvCodes dz = DinvCodes())
-{
-  update_p_body<NT, DZ ? 1 : 0>(st, beta_hist, dp_hist, alpha_hist, it, P, pa, pb, np, z, p, x, n, update_dir, dz);
-}
-template <bool NT>
-__global__ __launch_bounds__(VB) void k_update_p_c8(CgState* __restrict__ st, double* __restrict__ beta_hist,
-                                                    double* __restrict__ dp_hist, const double* __restrict__ alpha_hist,
-                                                    int it, CgParams P, const double* __restrict__ pa,
-                                                    const double* __restrict__ pb, int np, const double* __restrict__ z,
-                                                    double* __restrict__ p, double* __restrict__ x, int64_t n,
-                                                    int update_dir, DinvCodes dz)
-{
-  update_p_body<NT, 2>(st, beta_hist, dp_hist, alpha_hist, it, P, pa, pb, np, z, p, x, n, update_dir, dz);
-}
 
 // ---- the solution update deferred (ZZZ_CG_XDEFER): a ring of K direction vectors, x touched once per K iterations ----
 // Nothing in the loop reads x, yet k_update_p above reads and writes it in every iteration: 16 of its 42 B per row.
@@ -404,12 +379,7 @@ __device__ __forceinline__ void update_p_deferred(CgState* __restrict__ st, doub
 {
   __shared__ double sh[VB / 64];
   __shared__ double dtab[dz_table(DZ)];
-  if (DZ)
-  {
-    for (int k = threadIdx.x; k < dz.ndict; k += VB)
-      dtab[k] = dz.dict[k];
-    __syncthreads();
-  }
+  dz_stage<DZ>(dtab, dz);
   // first entries requested before the scalar prologue, as in k_update_p (the older directions of a flush are not: they
   // would be K - 1 more 16-B requests per lane for a form that runs once in K iterations)
   const int64_t n2 = n >> 1, stride = (int64_t)gridDim.x * VB;
@@ -517,43 +487,24 @@ __device__ __forceinline__ void update_p_deferred(CgState* __restrict__ st, doub
 }
 
 // (two kernels, not one with a flag: a kernel trace tells them apart by name)
-template <bool NT, bool DZ>
+template <bool NT, int DZ>
 __global__ __launch_bounds__(VB) void k_update_p_light(CgState* __restrict__ st, double* __restrict__ beta_hist, double* __restrict__ dp_hist,
                                                        const double* __restrict__ alpha_hist, int it, CgParams P,
                                                        const double* __restrict__ pa, const double* __restrict__ pb, int np,
                                                        const double* __restrict__ z, const double* pprev, double* pnew, PRing ring,
                                                        double* __restrict__ x, int64_t n, int update_dir, DinvCodes dz)
 {
-  update_p_deferred<NT, DZ ? 1 : 0, 0>(st, beta_hist, dp_hist, alpha_hist, it, P, pa, pb, np, z, pprev, pnew, ring, x, n, update_dir, dz);
+  update_p_deferred<NT, DZ, 0>(st, beta_hist, dp_hist, alpha_hist, it, P, pa, pb, np, z, pprev, pnew, ring, x, n, update_dir, dz);
 }
-template <bool NT>
-__global__ __launch_bounds__(VB) void k_update_p_light_c8(CgState* __restrict__ st, double* __restrict__ beta_hist, double* __restrict__ dp_hist,
-                                                          const double* __restrict__ alpha_hist, int it, CgParams P,
-                                                          const double* __restrict__ pa, const double* __restrict__ pb, int np,
-                                                          const double* __restrict__ z, const double* pprev, double* pnew, PRing ring,
-                                                          double* __restrict__ x, int64_t n, int update_dir, DinvCodes dz)
-{
-  update_p_deferred<NT, 2, 0>(st, beta_hist, dp_hist, alpha_hist, it, P, pa, pb, np, z, pprev, pnew, ring, x, n, update_dir, dz);
-}
-template <bool NT, bool DZ, int K>
+template <bool NT, int DZ, int K>
 __global__ __launch_bounds__(VB) void k_update_p_flush(CgState* __restrict__ st, double* __restrict__ beta_hist, double* __restrict__ dp_hist,
                                                        const double* __restrict__ alpha_hist, int it, CgParams P,
                                                        const double* __restrict__ pa, const double* __restrict__ pb, int np,
                                                        const double* __restrict__ z, const double*, double*, PRing ring,
                                                        double* __restrict__ x, int64_t n, int update_dir, DinvCodes dz)
 {
-  update_p_deferred<NT, DZ ? 1 : 0, K>(st, beta_hist, dp_hist, alpha_hist, it, P, pa, pb, np, z, ring.slot[K - 1], ring.slot[0], ring, x, n,
-                                       update_dir, dz);
-}
-template <bool NT, int K>
-__global__ __launch_bounds__(VB) void k_update_p_flush_c8(CgState* __restrict__ st, double* __restrict__ beta_hist, double* __restrict__ dp_hist,
-                                                          const double* __restrict__ alpha_hist, int it, CgParams P,
-                                                          const double* __restrict__ pa, const double* __restrict__ pb, int np,
-                                                          const double* __restrict__ z, const double*, double*, PRing ring,
-                                                          double* __restrict__ x, int64_t n, int update_dir, DinvCodes dz)
-{
-  update_p_deferred<NT, 2, K>(st, beta_hist, dp_hist, alpha_hist, it, P, pa, pb, np, z, ring.slot[K - 1], ring.slot[0], ring, x, n,
-                              update_dir, dz);
+  update_p_deferred<NT, DZ, K>(st, beta_hist, dp_hist, alpha_hist, it, P, pa, pb, np, z, ring.slot[K - 1], ring.slot[0], ring, x, n,
+                               update_dir, dz);
 }
 
 // The updates still pending when the solve has ended: j in [K floor(c / K), c), c = the iteration the solve stopped at
@@ -599,33 +550,23 @@ __global__ __launch_bounds__(VB) void k_x_apply_pending(const CgState* __restric
 
 typedef void (*update_p_ring_fn)(CgState*, double*, double*, const double*, int, CgParams, const double*, const double*, int,
                                  const double*, const double*, double*, PRing, double*, int64_t, int, DinvCodes);
-template <bool NT, bool DZ>
+template <bool NT, int DZ>
 static update_p_ring_fn pick_update_p_flush(int K)
 {
   return K == 2 ? k_update_p_flush<NT, DZ, 2> : K == 4 ? k_update_p_flush<NT, DZ, 4> : k_update_p_flush<NT, DZ, 8>;
 }
-template <bool NT>
-static update_p_ring_fn pick_update_p_flush_c8(int K)
-{
-  return K == 2 ? k_update_p_flush_c8<NT, 2> : K == 4 ? k_update_p_flush_c8<NT, 4> : k_update_p_flush_c8<NT, 8>;
-}
 
-template <bool NT, int DZ>
-__device__ __forceinline__ void update_xr_body(CgState* __restrict__ st, const double* __restrict__ beta_hist,
-                                               double* __restrict__ alpha_hist, int it,
-                                               const double* __restrict__ pw_parts, int npw,
-                                               const double* __restrict__ w, const double* __restrict__ dinv,
-                                               double* __restrict__ r, double* __restrict__ z, int64_t n, int norm,
-                                               double* __restrict__ pa, double* __restrict__ pb, int variant,
-                                               const DinvCodes& dz)
+template <bool NT, int DZ = 0>
+__global__ __launch_bounds__(VB) void k_update_xr(CgState* __restrict__ st, const double* __restrict__ beta_hist,
+                                                  double* __restrict__ alpha_hist, int it,
+                                                  const double* __restrict__ pw_parts, int npw,
+                                                  const double* __restrict__ w, const double* __restrict__ dinv,
+                                                  double* __restrict__ r, double* __restrict__ z, int64_t n, int norm,
+                                                  double* __restrict__ pa, double* __restrict__ pb, int variant,
+                                                  DinvCodes dz = DinvCodes())
 {
   __shared__ double dtab[dz_table(DZ)];
-  if (DZ)
-  {
-    for (int k = threadIdx.x; k < dz.ndict; k += VB)
-      dtab[k] = dz.dict[k];
-    __syncthreads();
-  }
+  dz_stage<DZ>(dtab, dz);
   // first entries requested before the scalar prologue (see k_update_p)
   const int64_t n2 = n >> 1, stride = (int64_t)gridDim.x * VB;
   const int64_t i0 = blockIdx.x * (int64_t)VB + threadIdx.x;
@@ -734,27 +675,6 @@ __device__ __forceinline__ void update_xr_body(CgState* __restrict__ st, const d
     pb[blockIdx.x] = tb;
   }
 }
-template <bool NT, bool DZ = false>
-__global__ __launch_bounds__(VB) void k_update_xr(CgState* __restrict__ st, const double* __restrict__ beta_hist,
-                                                  double* __restrict__ alpha_hist, int it,
-                                                  const double* __restrict__ pw_parts, int npw,
-                                                  const double* __restrict__ w, const double* __restrict__ dinv,
-                                                  double* __restrict__ r, double* __restrict__ z, int64_t n, int norm,
-                                                  double* __restrict__ pa, double* __restrict__ pb, int variant,
-                                                  DinvCodes dz = DinvCodes())
-{
-  update_xr_body<NT, DZ ? 1 : 0>(st, beta_hist, alpha_hist, it, pw_parts, npw, w, dinv, r, z, n, norm, pa, pb, variant, dz);
-}
-template <bool NT>
-__global__ __launch_bounds__(VB) void k_update_xr_c8(CgState* __restrict__ st, const double* __restrict__ beta_hist,
-                                                     double* __restrict__ alpha_hist, int it,
-                                                     const double* __restrict__ pw_parts, int npw,
-                                                     const double* __restrict__ w, const double* __restrict__ dinv,
-                                                     double* __restrict__ r, double* __restrict__ z, int64_t n, int norm,
-                                                     double* __restrict__ pa, double* __restrict__ pb, int variant, DinvCodes dz)
-{
-  update_xr_body<NT, 2>(st, beta_hist, alpha_hist, it, pw_parts, npw, w, dinv, r, z, n, norm, pa, pb, variant, dz);
-}
 
 // ---- PETSc's -ksp_cg_single_reduction (KSPCGUseSingleReduction; Chronopoulos/Gear form) ----------
 // One iteration = this kernel + one SpMV (s = A z with the partials of <z,s>, <r,z> and the norm):
@@ -767,24 +687,19 @@ __global__ __launch_bounds__(VB) void k_update_xr_c8(CgState* __restrict__ st, c
 // DZ (round 5): as in k_update_p -- Jacobi's inverse diagonal as 16-bit codes into a table in LDS, and z = D^-1 r of the
 // LAST iteration recomputed from the r this kernel reads anyway (the same product of the same two doubles: the same bits)
 // instead of read back: 96 -> 82 B per row and iteration.  z is still written: the product gathers it.
-template <bool NT, bool CHEB, int DZ>
-__device__ __forceinline__ void sr_update_body(CgState* __restrict__ st, double* __restrict__ beta_hist,
-                                               double* __restrict__ dpi_hist, double* __restrict__ dp_hist, int it,
-                                               const CgParams& P, const double* __restrict__ pa, const double* __restrict__ pb,
-                                               const double* __restrict__ pc, int np, const double* __restrict__ dinv,
-                                               const double* __restrict__ s, double* __restrict__ z, double* __restrict__ p,
-                                               double* __restrict__ w, double* __restrict__ x, double* __restrict__ r,
-                                               int64_t n, int scalars_only, double theta, double* __restrict__ chg,
-                                               double* __restrict__ chd, const DinvCodes& dz)
+template <bool NT, bool CHEB = false, int DZ = 0>
+__global__ __launch_bounds__(VB) void k_sr_update(CgState* __restrict__ st, double* __restrict__ beta_hist,
+                                                  double* __restrict__ dpi_hist, double* __restrict__ dp_hist, int it,
+                                                  CgParams P, const double* __restrict__ pa, const double* __restrict__ pb,
+                                                  const double* __restrict__ pc, int np, const double* __restrict__ dinv,
+                                                  const double* __restrict__ s, double* __restrict__ z, double* __restrict__ p,
+                                                  double* __restrict__ w, double* __restrict__ x, double* __restrict__ r,
+                                                  int64_t n, int scalars_only, double theta = 0.0, double* __restrict__ chg = nullptr,
+                                                  double* __restrict__ chd = nullptr, DinvCodes dz = DinvCodes())
 {
   static_assert(!(CHEB && DZ), "the polynomial's first term is not D^-1 r alone");
   __shared__ double dtab[dz_table(DZ)];
-  if (DZ)
-  {
-    for (int k = threadIdx.x; k < dz.ndict; k += VB)
-      dtab[k] = dz.dict[k];
-    __syncthreads();
-  }
+  dz_stage<DZ>(dtab, dz);
   // first entries requested before the scalar prologue (see k_update_p): seven 16-B loads in flight per thread while
   // the workgroup walks the flag, the three partial sums and the convergence logic
   const int64_t n2 = n >> 1, stride = (int64_t)gridDim.x * VB;
@@ -950,32 +865,6 @@ __device__ __forceinline__ void sr_update_body(CgState* __restrict__ st, double*
   }
   if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0)
     one(n - 1);
-}
-template <bool NT, bool CHEB = false, bool DZ = false>
-__global__ __launch_bounds__(VB) void k_sr_update(CgState* __restrict__ st, double* __restrict__ beta_hist,
-                                                  double* __restrict__ dpi_hist, double* __restrict__ dp_hist, int it,
-                                                  CgParams P, const double* __restrict__ pa, const double* __restrict__ pb,
-                                                  const double* __restrict__ pc, int np, const double* __restrict__ dinv,
-                                                  const double* __restrict__ s, double* __restrict__ z, double* __restrict__ p,
-                                                  double* __restrict__ w, double* __restrict__ x, double* __restrict__ r,
-                                                  int64_t n, int scalars_only, double theta = 0.0, double* __restrict__ chg = nullptr,
-                                                  double* __restrict__ chd = nullptr, DinvCodes dz = DinvCodes())
-{
-  sr_update_body<NT, CHEB, DZ ? 1 : 0>(st, beta_hist, dpi_hist, dp_hist, it, P, pa, pb, pc, np, dinv, s, z, p, w, x, r, n, scalars_only,
-                                       theta, chg, chd, dz);
-}
-template <bool NT>
-__global__ __launch_bounds__(VB) void k_sr_update_c8(CgState* __restrict__ st, double* __restrict__ beta_hist,
-                                                     double* __restrict__ dpi_hist, double* __restrict__ dp_hist, int it,
-                                                     CgParams P, const double* __restrict__ pa, const double* __restrict__ pb,
-                                                     const double* __restrict__ pc, int np, const double* __restrict__ dinv,
-                                                     const double* __restrict__ s, double* __restrict__ z, double* __restrict__ p,
-                                                     double* __restrict__ w, double* __restrict__ x, double* __restrict__ r,
-                                                     int64_t n, int scalars_only, double theta, double* __restrict__ chg,
-                                                     double* __restrict__ chd, DinvCodes dz)
-{
-  sr_update_body<NT, false, 2>(st, beta_hist, dpi_hist, dp_hist, it, P, pa, pb, pc, np, dinv, s, z, p, w, x, r, n, scalars_only, theta,
-                               chg, chd, dz);
 }
 
 __device__ inline double reduce_parts(const double* __restrict__ parts, int np, double* sh)
@@ -1258,18 +1147,7 @@ int cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
   const int g = vgrid(n);
   hipStream_t s = ctx->stream;
   const bool nt = loop_exceeds_cache(ctx, 6);
-  // (kernels by load policy and by whether z is recomputed from the coded inverse diagonal: chosen where dz is known)
-  // (dzb: the codes' width, 0 without codes)
-  auto pick_update_p = [&](int dzb) {
-    return dzb == 8 ? (nt ? k_update_p_c8<true> : k_update_p_c8<false>)
-           : dzb    ? (nt ? k_update_p<true, true> : k_update_p<false, true>)
-                    : (nt ? k_update_p<true, false> : k_update_p<false, false>);
-  };
-  auto pick_update_xr = [&](int dzb) {
-    return dzb == 8 ? (nt ? k_update_xr_c8<true> : k_update_xr_c8<false>)
-           : dzb    ? (nt ? k_update_xr<true, true> : k_update_xr<false, true>)
-                    : (nt ? k_update_xr<true, false> : k_update_xr<false, false>);
-  };
+  // (kernels by load policy and by the form of the inverse diagonal: chosen below, where dzc is known)
 
   CgSolve S;
   if (int rc = S.begin(ctx, o))
@@ -1301,10 +1179,9 @@ int cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
       return rc;
   ctx->last_solve_dinv_codes = dzc.codes ? dzc.ndict : 0;
   ctx->last_solve_dinv_bits = dzc.codes ? dzc.bits : 0;
-  const bool dz = dzc.codes != nullptr;
-  const bool dz8 = dz && dzc.bits == 8;
-  auto kern_update_p = pick_update_p(dz ? dzc.bits : 0);
-  auto kern_update_xr = pick_update_xr(dz ? dzc.bits : 0);
+  const int form = dz_form(dzc);
+  auto kern_update_p = dz_dispatch(nt, form, [](auto NT, auto DZ) { return k_update_p<decltype(NT)::value, decltype(DZ)::value>; });
+  auto kern_update_xr = dz_dispatch(nt, form, [](auto NT, auto DZ) { return k_update_xr<decltype(NT)::value, decltype(DZ)::value>; });
 
   // The solution update deferred (k_update_p_light / _flush): where x comes from HBM, i.e. under the same rule as the
   // load policy (ZZZ_CG_XDEFER: 0 never, 2 at any size; ZZZ_CG_XDEFER_K: the ring's length).  Slot 0 is ctx->p, the other
@@ -1338,12 +1215,8 @@ int cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
   update_p_ring_fn kern_light = nullptr, kern_flush = nullptr;
   if (K > 1)
   {
-    kern_light = dz8  ? (nt ? k_update_p_light_c8<true> : k_update_p_light_c8<false>)
-                 : dz ? (nt ? k_update_p_light<true, true> : k_update_p_light<false, true>)
-                      : (nt ? k_update_p_light<true, false> : k_update_p_light<false, false>);
-    kern_flush = dz8  ? (nt ? pick_update_p_flush_c8<true>(K) : pick_update_p_flush_c8<false>(K))
-                 : dz ? (nt ? pick_update_p_flush<true, true>(K) : pick_update_p_flush<false, true>(K))
-                      : (nt ? pick_update_p_flush<true, false>(K) : pick_update_p_flush<false, false>(K));
+    kern_light = dz_dispatch(nt, form, [](auto NT, auto DZ) { return k_update_p_light<decltype(NT)::value, decltype(DZ)::value>; });
+    kern_flush = dz_dispatch(nt, form, [K](auto NT, auto DZ) { return pick_update_p_flush<decltype(NT)::value, decltype(DZ)::value>(K); });
   }
   // the test of iteration k and (update_dir) the direction p_k; where p_k lives
   auto dir_of = [&](int k) { return ring.slot[k % K]; };
@@ -2048,11 +1921,10 @@ static int cg_solve_single_reduction(zzz_ctx* ctx, const zzz_solver_opts* o, int
       return rc;
   ctx->last_solve_dinv_codes = dzc.codes ? dzc.ndict : 0;
   ctx->last_solve_dinv_bits = dzc.codes ? dzc.bits : 0;
-  const bool dz = dzc.codes != nullptr;
   auto kern_sr_update = cheb ? (ntv ? k_sr_update<true, true> : k_sr_update<false, true>)
-                        : (dz && dzc.bits == 8) ? (ntv ? k_sr_update_c8<true> : k_sr_update_c8<false>)
-                        : dz                    ? (ntv ? k_sr_update<true, false, true> : k_sr_update<false, false, true>)
-                                                : (ntv ? k_sr_update<true> : k_sr_update<false>);
+                             : dz_dispatch(ntv, dz_form(dzc), [](auto NT, auto DZ) {
+                                 return k_sr_update<decltype(NT)::value, false, decltype(DZ)::value>;
+                               });
   // r = b, z = D^-1 r (the partials of this kernel are not used: the SpMV below leaves all three)
   hipLaunchKernelGGL(k_init_residual, dim3(g), dim3(VB), 0, s, ctx->b.p, (const double*)nullptr, ctx->dinv.p, ctx->r.p,
                      ctx->z.p, n, P.norm, ctx->part_b.p, ctx->part_b.p + VGRID_MAX);

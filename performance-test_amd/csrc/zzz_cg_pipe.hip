@@ -66,25 +66,20 @@ __global__ __launch_bounds__(VB) void k_pipe_start(const double* __restrict__ di
 // iteration it + 1 (another set than pa/pb/pc: workgroups of one launch read the one while others already write the
 // other).  nv = A m of this iteration.  scalars_only: the test of the last completed iteration (one workgroup).
 // DZ: D^-1 as codes into a table in LDS (DinvCodes), 2 B per row instead of 8 (DZ = 1, 16-bit codes) or 1 B (DZ = 2, 8-bit
-// codes: k_pipe_update_c8).
+// codes); DZ = 0: doubles.
 template <bool NT, int DZ>
-__device__ __forceinline__ void pipe_update_body(CgState* __restrict__ st, double* __restrict__ gamma_hist,
-                                                 double* __restrict__ alpha_hist, double* __restrict__ dp_hist, int it,
-                                                 const CgParams& P, const double* __restrict__ pa, const double* __restrict__ pb,
-                                                 const double* __restrict__ pc, int np, const double* __restrict__ dinv,
-                                                 const double* __restrict__ nv, double* __restrict__ z,
-                                                 double* __restrict__ s, double* __restrict__ p, double* __restrict__ x,
-                                                 double* __restrict__ r, double* __restrict__ w, double* __restrict__ m,
-                                                 int64_t n, int scalars_only, double* __restrict__ qa,
-                                                 double* __restrict__ qb, double* __restrict__ qc, const DinvCodes& dz)
+__global__ __launch_bounds__(VB) void k_pipe_update(CgState* __restrict__ st, double* __restrict__ gamma_hist,
+                                                    double* __restrict__ alpha_hist, double* __restrict__ dp_hist, int it,
+                                                    CgParams P, const double* __restrict__ pa, const double* __restrict__ pb,
+                                                    const double* __restrict__ pc, int np, const double* __restrict__ dinv,
+                                                    const double* __restrict__ nv, double* __restrict__ z,
+                                                    double* __restrict__ s, double* __restrict__ p, double* __restrict__ x,
+                                                    double* __restrict__ r, double* __restrict__ w, double* __restrict__ m,
+                                                    int64_t n, int scalars_only, double* __restrict__ qa,
+                                                    double* __restrict__ qb, double* __restrict__ qc, DinvCodes dz)
 {
   __shared__ double dtab[dz_table(DZ)];
-  if (DZ)
-  {
-    for (int k = threadIdx.x; k < dz.ndict; k += VB)
-      dtab[k] = dz.dict[k];
-    __syncthreads();
-  }
+  dz_stage<DZ>(dtab, dz);
   // first entries requested before the scalar prologue (see k_update_p of zzz_cg.hip): up to eight 16-B loads in flight
   // per thread while the workgroup walks the flag, the three sums and the convergence logic
   const int64_t n2 = n >> 1, stride = (int64_t)gridDim.x * VB;
@@ -273,34 +268,6 @@ __device__ __forceinline__ void pipe_update_body(CgState* __restrict__ st, doubl
     qc[blockIdx.x] = tc;
   }
 }
-template <bool NT, bool DZ>
-__global__ __launch_bounds__(VB) void k_pipe_update(CgState* __restrict__ st, double* __restrict__ gamma_hist,
-                                                    double* __restrict__ alpha_hist, double* __restrict__ dp_hist, int it,
-                                                    CgParams P, const double* __restrict__ pa, const double* __restrict__ pb,
-                                                    const double* __restrict__ pc, int np, const double* __restrict__ dinv,
-                                                    const double* __restrict__ nv, double* __restrict__ z,
-                                                    double* __restrict__ s, double* __restrict__ p, double* __restrict__ x,
-                                                    double* __restrict__ r, double* __restrict__ w, double* __restrict__ m,
-                                                    int64_t n, int scalars_only, double* __restrict__ qa,
-                                                    double* __restrict__ qb, double* __restrict__ qc, DinvCodes dz)
-{
-  pipe_update_body<NT, DZ ? 1 : 0>(st, gamma_hist, alpha_hist, dp_hist, it, P, pa, pb, pc, np, dinv, nv, z, s, p, x, r, w, m, n,
-                                   scalars_only, qa, qb, qc, dz);
-}
-template <bool NT>
-__global__ __launch_bounds__(VB) void k_pipe_update_c8(CgState* __restrict__ st, double* __restrict__ gamma_hist,
-                                                       double* __restrict__ alpha_hist, double* __restrict__ dp_hist, int it,
-                                                       CgParams P, const double* __restrict__ pa, const double* __restrict__ pb,
-                                                       const double* __restrict__ pc, int np, const double* __restrict__ dinv,
-                                                       const double* __restrict__ nv, double* __restrict__ z,
-                                                       double* __restrict__ s, double* __restrict__ p, double* __restrict__ x,
-                                                       double* __restrict__ r, double* __restrict__ w, double* __restrict__ m,
-                                                       int64_t n, int scalars_only, double* __restrict__ qa,
-                                                       double* __restrict__ qb, double* __restrict__ qc, DinvCodes dz)
-{
-  pipe_update_body<NT, 2>(st, gamma_hist, alpha_hist, dp_hist, it, P, pa, pb, pc, np, dinv, nv, z, s, p, x, r, w, m, n, scalars_only, qa,
-                          qb, qc, dz);
-}
 
 int cg_solve_pipe(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
 {
@@ -334,9 +301,7 @@ int cg_solve_pipe(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rn
       return rc;
   ctx->last_solve_dinv_codes = dzc.codes ? dzc.ndict : 0;
   ctx->last_solve_dinv_bits = dzc.codes ? dzc.bits : 0;
-  auto kern = (dzc.codes && dzc.bits == 8) ? (ntv ? k_pipe_update_c8<true> : k_pipe_update_c8<false>)
-              : dzc.codes                  ? (ntv ? k_pipe_update<true, true> : k_pipe_update<false, true>)
-                                           : (ntv ? k_pipe_update<true, false> : k_pipe_update<false, false>);
+  auto kern = dz_dispatch(ntv, dz_form(dzc), [](auto NT, auto DZ) { return k_pipe_update<decltype(NT)::value, decltype(DZ)::value>; });
 
   double *x = ctx->u.p, *r = ctx->r.p, *w = ctx->w.p, *m = ctx->pipe_m.p, *nvec = ctx->pipe_n.p;
   // y = A v on the form the matrix took; the partials of <v,y> the product leaves in part_a are not used (asking for

@@ -6,13 +6,10 @@ the legacy matfree_cell<10> / <20>, which may not use more scratch than they did
 kernel instantiations is the table's.  VGPR counts are printed, not asserted: within an occupancy step they may move."""
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+from _kernel_resources import HIPCC, kernel_resources
 
 # kernel<template arguments>: (waves/SIMD, scratch bytes/lane, static LDS bytes) before the sharing
 PARENT = {
@@ -33,31 +30,22 @@ MAY_SPILL = ("matfree_cell<10>", "matfree_cell<20>")  # legacy: a thread holds a
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
-def test_assembly_kernels_keep_their_occupancy_and_stay_out_of_scratch(tmp_path):
-    src = os.path.join(ROOT, "performance-test_amd", "csrc", "zzz_assemble.hip")
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-fopenmp", "-I" + os.path.dirname(src),
-           "-I" + os.path.join(ROOT, "include"), "-c", src, "-o", str(tmp_path / "k.o"), "-Rpass-analysis=kernel-resource-usage"]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
+def test_assembly_kernels_keep_their_occupancy_and_stay_out_of_scratch():
     seen = set()
-    for b in re.split(r"remark: Function Name: ", r.stderr)[1:]:
-        name = b.split()[0]
+    for name, num in kernel_resources("zzz_assemble.hip").items():
         # _ZN3zzz13asm_matrix_p1ILi1ELi1920ELi128EEEv...: the kernel and its integer template arguments
         m = re.match(r"_ZN3zzz\d+((?:asm_|k_cell_|k_lift(?!_)|matfree_cell)\w*?)I((?:Li\d+E)+)E", name)
         if not m:
             assert not re.match(r"_ZN3zzz\d+(asm_|k_cell_|k_liftI|matfree_cell)", name), name
             continue
         key = m.group(1) + "<" + ",".join(re.findall(r"Li(\d+)E", m.group(2))) + ">"
-        num = {k: int(re.search(re.escape(k) + r": (\d+)", b).group(1))
-               for k in ("VGPRs", "AGPRs", "Occupancy [waves/SIMD]", "ScratchSize [bytes/lane]", "VGPRs Spill", "SGPRs Spill",
-                         "LDS Size [bytes/block]")}
         print(key, num)
         assert key in PARENT, key
         occ, scratch, lds = PARENT[key]
-        assert num["Occupancy [waves/SIMD]"] >= occ, (key, num)
-        assert num["ScratchSize [bytes/lane]"] <= scratch, (key, num)
+        assert num["occ"] >= occ, (key, num)
+        assert num["scratch"] <= scratch, (key, num)
         if key not in MAY_SPILL:
-            assert num["VGPRs Spill"] == 0 and num["SGPRs Spill"] == 0, (key, num)
-        assert num["LDS Size [bytes/block]"] == lds, (key, num)
+            assert num["vspill"] == 0 and num["sspill"] == 0, (key, num)
+        assert num["lds"] == lds, (key, num)
         seen.add(key)
     assert seen == set(PARENT), (sorted(seen - set(PARENT)), sorted(set(PARENT) - seen))

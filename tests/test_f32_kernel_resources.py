@@ -6,34 +6,15 @@ wavefronts per SIMD in the same compile; the three vector kernels of the float C
 occupancy."""
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-
-
-def _resources(src_name, tmp_path):
-    src = os.path.join(ROOT, "performance-test_amd", "csrc", src_name)
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-fopenmp", "-I" + os.path.dirname(src),
-           "-I" + os.path.join(ROOT, "include"), "-c", src, "-o", str(tmp_path / "k.o"), "-Rpass-analysis=kernel-resource-usage"]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    out = {}
-    for b in re.split(r"remark: Function Name: ", r.stderr)[1:]:
-        out[b.split()[0]] = dict(vgprs=int(re.search(r"VGPRs: (\d+)", b).group(1)),
-                                 occ=int(re.search(r"Occupancy \[waves/SIMD\]: (\d+)", b).group(1)),
-                                 scratch=int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", b).group(1)),
-                                 vspill=int(re.search(r"VGPRs Spill: (\d+)", b).group(1)),
-                                 sspill=int(re.search(r"SGPRs Spill: (\d+)", b).group(1)))
-    return out
+from _kernel_resources import HIPCC, kernel_resources
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
-def test_float_action_has_no_scratch_and_p3_keeps_the_double_kernels_occupancy(tmp_path):
-    res = _resources("zzz_matfree.hip", tmp_path)
+def test_float_action_has_no_scratch_and_p3_keeps_the_double_kernels_occupancy():
+    res = kernel_resources("zzz_matfree.hip")
     seen, nfloat = {}, 0
     for name, k in res.items():
         # k_mf_action<ND, T, DIAG, R>: R is the last template argument, d or f
@@ -59,8 +40,8 @@ def test_float_action_has_no_scratch_and_p3_keeps_the_double_kernels_occupancy(t
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
-def test_float_cg_vector_kernels_keep_full_occupancy(tmp_path):
-    res = _resources("zzz_cg_f32.hip", tmp_path)
+def test_float_cg_vector_kernels_keep_full_occupancy():
+    res = kernel_resources("zzz_cg_f32.hip")
     seen = set()
     for name, k in res.items():
         m = re.search(r"\d+(k32_[a-z_]+?)E[iPK]", name)

@@ -1,5 +1,5 @@
-"""GPU parity tests: Jacobi's inverse diagonal as 8-bit codes (at most 256 distinct values: one byte per row, the `_c8` entry
-points of csrc/zzz_cg.hip and csrc/zzz_cg_pipe.hip) against the same solve on 16-bit codes (ZZZ_CG_DINV_CODES=3) and on the
+"""GPU parity tests: Jacobi's inverse diagonal as 8-bit codes (at most 256 distinct values: one byte per row, the DZ = 2
+instantiations of the vector kernels of csrc/zzz_cg.hip and csrc/zzz_cg_pipe.hip) against the same solve on 16-bit codes (ZZZ_CG_DINV_CODES=3) and on the
 doubles (=0), each on a fresh context.  A code selects the same double from the table whatever its width, and the kernels
 multiply the same doubles in the same order, so everything is compared BIT FOR BIT: solution, iteration count, both norms,
 the residual history and the reason.
@@ -123,10 +123,10 @@ def _same(a, b, what=""):
     np.testing.assert_array_equal(a["u"], b["u"], err_msg=str(what))
 
 
-def _run(name, values, knob, solves, xdefer):
-    """fresh context under ZZZ_CG_DINV_CODES=knob; the classical loop in place (xdefer False) or over a ring of K directions"""
+def _run(name, values, knob, solves, xdefer, k=K):
+    """fresh context under ZZZ_CG_DINV_CODES=knob; the classical loop in place (xdefer False) or over a ring of k directions"""
     P = _system(name)[0]
-    xd = dict(ZZZ_CG_XDEFER=2, ZZZ_CG_XDEFER_K=K) if xdefer else dict(ZZZ_CG_XDEFER=0)
+    xd = dict(ZZZ_CG_XDEFER=2, ZZZ_CG_XDEFER_K=k) if xdefer else dict(ZZZ_CG_XDEFER=0)
     with _env(ZZZ_CG_DINV_CODES=knob, **xd):
         with zzz.Context(0) as c:
             c.upload_part(P)
@@ -137,15 +137,15 @@ def _run(name, values, knob, solves, xdefer):
             return [_solve(c, **kw) for kw in solves]
 
 
-def _three_ways(name, values, solves, xdefer, codes, bits):
+def _three_ways(name, values, solves, xdefer, codes, bits, k=K):
     """knob 2 (the width the count allows) against 3 (16 bits) and 0 (doubles); the forms each run must report"""
-    new, wide, dbl = (_run(name, values, knob, solves, xdefer) for knob in (2, 3, 0))
+    new, wide, dbl = (_run(name, values, knob, solves, xdefer, k) for knob in (2, 3, 0))
     for kw, a, w, d in zip(solves, new, wide, dbl):
         classical = not kw.get("single_reduction") and kw.get("variant") != zzz.CG_PIPE
         assert (a["codes"], a["bits"]) == (codes, bits), (kw, a["codes"], a["bits"])
         assert (w["codes"], w["bits"]) == (codes, 16), (kw, w["codes"], w["bits"])
         assert (d["codes"], d["bits"]) == (0, 0), (kw, d["codes"], d["bits"])
-        assert a["k"] == w["k"] == d["k"] == (K if xdefer and classical else 1), (kw, a["k"], w["k"], d["k"])
+        assert a["k"] == w["k"] == d["k"] == (k if xdefer and classical else 1), (kw, a["k"], w["k"], d["k"])
         _same(w, a, (name, "against 16-bit codes", kw))
         _same(d, a, (name, "against doubles", kw))
     return new
@@ -186,6 +186,18 @@ def test_every_way_a_deferred_solve_can_end(name):
     assert [r["it"] for r in new[:ncap]] == list(range(ncap)) and all(r["reason"] == -3 for r in new[:ncap])
     assert all(r["reason"] == 2 for r in new[ncap:])
     assert {r["it"] % K for r in new[ncap:]} == set(range(K)), sorted({r["it"] for r in new[ncap:]})
+
+
+@pytest.mark.parametrize("k", [2, 8], ids=["K2", "K8"])
+@pytest.mark.parametrize("name", ["even", "odd"])
+def test_ring_lengths_2_and_8_read_the_8bit_codes(name, k):
+    """The ring lengths the other tests leave out: the flush form is compiled per ring length and chosen per form of the
+    diagonal, so a mis-wired choice shows only here.  The classical form, max_it = 2 k + 1 under a tolerance never met: the
+    light form, two flushes and one pending update, three ways bit for bit."""
+    v = _scaled_values(name, 256)
+    new = _three_ways(name, v, [dict(pc=zzz.PC_JACOBI, rtol=1e-30, max_it=2 * k + 1)], True, 256, 8, k)
+    assert new[0]["bits"] == 8 and new[0]["k"] == k, (new[0]["bits"], new[0]["k"])
+    assert new[0]["it"] == 2 * k + 1 and new[0]["reason"] == -3, (new[0]["it"], new[0]["reason"])
 
 
 @pytest.mark.parametrize("xdefer", [False, True], ids=["K1", "K4"])

@@ -4,67 +4,37 @@ it sits exactly at the 64-VGPR limit of that occupancy.  hipcc cross-compiles wi
 count of the shipped variants is checked here, where a regression is cheap to see."""
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+from _kernel_resources import HIPCC, kernel_resources
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
-def test_spmv_tile_kernel_keeps_full_occupancy(tmp_path):
-    src = os.path.join(ROOT, "performance-test_amd", "csrc", "zzz_spmv.hip")
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-I" + os.path.dirname(src),
-           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "performance-test_amd", "host"), "-c", src, "-o",
-           str(tmp_path / "spmv.o"), "-Rpass-analysis=kernel-resource-usage"]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    # remarks come in blocks: "Function Name: <mangled>" followed by the resource lines of that kernel
-    blocks = re.split(r"remark: Function Name: ", r.stderr)[1:]
+def test_spmv_tile_kernel_keeps_full_occupancy():
     seen = 0
-    for b in blocks:
-        name = b.split()[0]
+    for name, k in kernel_resources("zzz_spmv.hip").items():
         # spmv_tile_kernel<DOT, NT>: the four variants the solver launches
-        m = re.match(r"_ZN3zzz16spmv_tile_kernelILb([01])ELb([01])EEE", name)
-        if not m:
+        if not re.match(r"_ZN3zzz16spmv_tile_kernelILb([01])ELb([01])EEE", name):
             continue
-        vgprs = int(re.search(r"VGPRs: (\d+)", b).group(1))
-        occ = int(re.search(r"Occupancy \[waves/SIMD\]: (\d+)", b).group(1))
-        spill = int(re.search(r"VGPRs Spill: (\d+)", b).group(1))
-        lds = int(re.search(r"LDS Size \[bytes/block\]: (\d+)", b).group(1))
-        assert vgprs <= 64 and occ == 8 and spill == 0, (name, vgprs, occ, spill)
-        assert lds * 8 <= 160 * 1024, (name, lds)  # eight workgroups per CU must fit the 160 KB of LDS
+        assert k["vgprs"] <= 64 and k["occ"] == 8 and k["vspill"] == 0, (name, k)
+        assert k["lds"] * 8 <= 160 * 1024, (name, k)  # eight workgroups per CU must fit the 160 KB of LDS
         seen += 1
     assert seen == 4
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
-def test_operator_stream_kernel_keeps_full_occupancy(tmp_path):
+def test_operator_stream_kernel_keeps_full_occupancy():
     """The product on the operator stream (zzz_sellp.hip) has no LDS and must stay at 8 wavefronts per SIMD (<= 64 VGPRs:
     its launch bound); without spills it would need 74 registers = 6 wavefronts, measured exactly as fast, so the few
     spilled dwords are tolerated -- but not growth beyond that."""
-    src = os.path.join(ROOT, "performance-test_amd", "csrc", "zzz_sellp.hip")
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-I" + os.path.dirname(src),
-           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "performance-test_amd", "host"), "-c", src, "-o",
-           str(tmp_path / "sellp.o"), "-Rpass-analysis=kernel-resource-usage"]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    blocks = re.split(r"remark: Function Name: ", r.stderr)[1:]
     seen = 0
-    for b in blocks:
-        name = b.split()[0]
+    for name, k in kernel_resources("zzz_sellp.hip").items():
         if not re.match(r"_ZN3zzz17spmv_sellp_kernelILb[01]ELb[01]ELb[01]ELb[01]ELb[01]ELi[0123]EEE", name):
             continue
-        vgprs = int(re.search(r"VGPRs: (\d+)", b).group(1))
-        occ = int(re.search(r"Occupancy \[waves/SIMD\]: (\d+)", b).group(1))
-        scratch = int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", b).group(1))
-        lds = int(re.search(r"LDS Size \[bytes/block\]: (\d+)", b).group(1))
-        sgprs = int(re.search(r"TotalSGPRs: (\d+)", b).group(1))
         # LDS: the cross-wavefront sums, a few hundred bytes per workgroup;
         # SGPRs <= 80 keeps eight 256-thread workgroups per CU admissible (MI355X_MICROARCH.md, Residency)
-        assert vgprs <= 64 and occ == 8 and scratch <= 64 and lds <= 512 and sgprs <= 80, (name, vgprs, occ, scratch, lds, sgprs)
+        assert k["vgprs"] <= 64 and k["occ"] == 8 and k["scratch"] <= 64 and k["lds"] <= 512 and k["sgprs"] <= 80, (name, k)
         seen += 1
     # (dot products, load policy, row permutation, Chebyshev-term epilogue) + x windows (natural order), each with the
     # values as doubles, as codes into a dictionary in memory, as codes into a dictionary in LDS, as 8-bit codes into
@@ -76,27 +46,15 @@ def test_operator_stream_kernel_keeps_full_occupancy(tmp_path):
 @pytest.mark.parametrize("src_name,kernel_re,lds_budget,variants", [
     ("zzz_sellp_blk.hip", r"_ZN3zzz16spmv_blk3_kernelILb[01]ELb[01]ELb[01]ELi[12]ELb[01]EEE", 2200 * 72, 20),
     ("zzz_sellp_win.hip", r"_ZN3zzz15spmv_win_kernelILb[01]ELb[01]ELb[01]ELb[01]EEE", (11264 + 8192) * 8, 10)])
-def test_special_product_kernels_fit_one_workgroup_of_1024_lanes_per_cu(tmp_path, src_name, kernel_re, lds_budget, variants):
+def test_special_product_kernels_fit_one_workgroup_of_1024_lanes_per_cu(src_name, kernel_re, lds_budget, variants):
     """The block-row and block-window products (round 6) run ONE workgroup of 1 024 lanes per CU: sixteen wavefronts, four per SIMD,
     i.e. at most 128 VGPRs per lane, with (nearly) no scratch; their dynamic LDS (block table / window + dictionary) plus the static
     part must fit the CU's 160 KB."""
-    src = os.path.join(ROOT, "performance-test_amd", "csrc", src_name)
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-I" + os.path.dirname(src),
-           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "performance-test_amd", "host"), "-c", src, "-o",
-           str(tmp_path / "k.o"), "-Rpass-analysis=kernel-resource-usage"]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    blocks = re.split(r"remark: Function Name: ", r.stderr)[1:]
     seen = 0
-    for b in blocks:
-        name = b.split()[0]
+    for name, k in kernel_resources(src_name).items():
         if not re.match(kernel_re, name):
             continue
-        vgprs = int(re.search(r"VGPRs: (\d+)", b).group(1))
-        occ = int(re.search(r"Occupancy \[waves/SIMD\]: (\d+)", b).group(1))
-        scratch = int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", b).group(1))
-        lds = int(re.search(r"LDS Size \[bytes/block\]: (\d+)", b).group(1))
-        assert vgprs <= 128 and occ >= 4 and scratch <= 64, (name, vgprs, occ, scratch)
-        assert lds + lds_budget <= 160 * 1024, (name, lds)
+        assert k["vgprs"] <= 128 and k["occ"] >= 4 and k["scratch"] <= 64, (name, k)
+        assert k["lds"] + lds_budget <= 160 * 1024, (name, k)
         seen += 1
     assert seen == variants, seen  # (dot / single reduction / load policy [/ table form], and the Chebyshev-epilogue variants)

@@ -14,34 +14,15 @@ resource report is read.
 """
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-
-
-def _resources(src_name, tmp_path):
-    src = os.path.join(ROOT, "performance-test_amd", "csrc", src_name)
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-fopenmp", "-I" + os.path.dirname(src),
-           "-I" + os.path.join(ROOT, "include"), "--cuda-device-only", "-c", src, "-o", str(tmp_path / "k.o"),
-           "-Rpass-analysis=kernel-resource-usage"]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    out = {}
-    for b in re.split(r"remark: Function Name: ", r.stderr)[1:]:
-        g = lambda p: int(re.search(p, b).group(1))  # noqa: E731
-        out[b.split()[0]] = dict(vgprs=g(r"VGPRs: (\d+)"), agprs=g(r"AGPRs: (\d+)"), occ=g(r"Occupancy \[waves/SIMD\]: (\d+)"),
-                                 scratch=g(r"ScratchSize \[bytes/lane\]: (\d+)"), vspill=g(r"VGPRs Spill: (\d+)"),
-                                 sspill=g(r"SGPRs Spill: (\d+)"), lds=g(r"LDS Size \[bytes/block\]: (\d+)"))
-    return out
+from _kernel_resources import HIPCC, kernel_resources
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
-def test_block_size_3_action_resources(tmp_path):
-    res = _resources("zzz_matfree.hip", tmp_path)
+def test_block_size_3_action_resources():
+    res = kernel_resources("zzz_matfree.hip")
     seen = {}
     for name, k in res.items():
         m = re.search(r"k_mf_action3ILi(\d+)ELi(\d+)ELb([01])E", name)
