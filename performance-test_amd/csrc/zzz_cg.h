@@ -14,8 +14,6 @@
 
 namespace zzz
 {
-typedef double dbl2 __attribute__((ext_vector_type(2)));
-
 // One workgroup-wide sum of up to three partial arrays in ONE pass and one barrier pair (same tree per array as
 // reduce_parts_bcast of zzz_cg.hip:
 // strided per-thread sums, shuffles inside a wavefront, the per-wavefront sums added in order -- here by every thread
@@ -65,23 +63,6 @@ constexpr int VGRID_MAX = 2048; // 8 workgroups per CU
 // of the product against 0.5-0.8 us elsewhere), i.e. 7 us per timed iteration -- 13 % of a 52-us iteration when every
 // launch was timed.
 constexpr int PROF_STRIDE = 8;
-
-// Non-temporal access for data touched once per iteration pays only when the working set of the loop exceeds the
-// 256 MiB Infinity Cache; a loop that fits (the 8-GPU per-rank size: ~100 MB of operator stream + 60 MB of vectors)
-// keeps everything on-die with plain accesses.
-template <bool NT, typename T>
-__device__ inline T vload(const T* p)
-{
-  return NT ? __builtin_nontemporal_load(p) : *p;
-}
-template <bool NT, typename T>
-__device__ inline void vstore(T v, T* p)
-{
-  if (NT)
-    __builtin_nontemporal_store(v, p);
-  else
-    *p = v;
-}
 
 // The convergence flag can be set by workgroup 0 of the SAME launch while other workgroups start: one value per
 // workgroup (thread 0's, loaded by the caller ahead of its other requests), so all threads of a workgroup take the same

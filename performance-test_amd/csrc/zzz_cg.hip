@@ -1423,8 +1423,8 @@ __global__ __launch_bounds__(VB) void k_cheb_step(const int* __restrict__ stop, 
   double sa = 0, sb = 0;
   for (int64_t i = blockIdx.x * (int64_t)VB + threadIdx.x; i < n; i += (int64_t)gridDim.x * VB)
   {
-    const double gi = -1.0 * (dinv[i] * w[i]) + gv[i];
-    const double dn = c1 * d[i] + c2 * gi; // (built with -ffp-contract=off: rounded as written, here, in the product's epilogue and in the oracle)
+    double gi, dn;
+    cheb_term(dinv[i], w[i], gv[i], d[i], c1, c2, gi, dn);
     const double zi = z[i] + dn;
     z[i] = zi;
     if (!last)

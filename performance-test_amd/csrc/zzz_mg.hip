@@ -199,7 +199,7 @@ __global__ __launch_bounds__(VB) void k_mg_first(const int* __restrict__ stop, c
     x[i] = t ? x[i] + di : di;
   }
 }
-// A further term, t = A d given (k_cheb_step's arithmetic): g -= D^-1 t; d = c1 d + c2 g; x += d
+// A further term, t = A d given (cheb_term): g -= D^-1 t; d = c1 d + c2 g; x += d
 __global__ __launch_bounds__(VB) void k_mg_term(const int* __restrict__ stop, const double* __restrict__ t,
                                                 const double* __restrict__ dinv, double c1, double c2, double* __restrict__ gv,
                                                 double* __restrict__ d, double* __restrict__ x, int64_t n)
@@ -208,8 +208,8 @@ __global__ __launch_bounds__(VB) void k_mg_term(const int* __restrict__ stop, co
     return;
   for (int64_t i = blockIdx.x * (int64_t)VB + threadIdx.x; i < n; i += (int64_t)gridDim.x * VB)
   {
-    const double gi = -1.0 * (dinv[i] * t[i]) + gv[i];
-    const double dn = c1 * d[i] + c2 * gi;
+    double gi, dn;
+    cheb_term(dinv[i], t[i], gv[i], d[i], c1, c2, gi, dn);
     gv[i] = gi;
     d[i] = dn;
     x[i] = x[i] + dn;

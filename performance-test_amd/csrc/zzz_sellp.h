@@ -9,10 +9,6 @@
 
 namespace zzz
 {
-typedef double dbl2 __attribute__((ext_vector_type(2)));
-typedef unsigned uint4v __attribute__((ext_vector_type(4)));
-typedef int int4v __attribute__((ext_vector_type(4)));
-typedef unsigned uint2v __attribute__((ext_vector_type(2)));
 constexpr int SP_BLOCK = 256;
 constexpr int SP_SIGMA = 512; // sorting window (rows) of the sorted form: one workgroup
 
@@ -32,16 +28,6 @@ constexpr int SP_CLS_C8 = 1;    // 8-bit codes, first half of the chunk's code b
 constexpr int SP_CLS_C16 = 2;   // 16-bit codes, the chunk's code block
 constexpr int SP_CLS_C8T = 3;   // 8-bit codes in the free tail of the chunk's value block
 constexpr int SP_SMODE_CHUNKS = 32; // chunks per slice the mode word describes (longer slices: the generic product)
-
-// tile index for (workgroup b, step i): XCD x = b % 8 owns items [x*T/8, (x+1)*T/8)   (as in zzz_spmv.hip)
-__device__ inline int64_t sp_xcd_item(int64_t n, int b, int nb, int i)
-{
-  const int xcd = b & 7;
-  const int64_t lo = n * xcd / 8, hi = n * (xcd + 1) / 8;
-  const int wg_in_xcd = b >> 3, n_in_xcd = (nb + 7 - xcd) >> 3;
-  const int64_t t = lo + wg_in_xcd + (int64_t)i * n_in_xcd;
-  return t < hi ? t : -1;
-}
 
 // x[col] with a 32-bit byte offset: one shift per gather instead of a 64-bit address computation
 // (the launcher guarantees 8 * ncols < 2^32)

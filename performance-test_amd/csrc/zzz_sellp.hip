@@ -11,12 +11,6 @@
 namespace zzz
 {
 // ---- the product --------------------------------------------------------------------------------------
-template <bool NT, typename T>
-__device__ inline T sp_load(const T* p)
-{
-  return NT ? __builtin_nontemporal_load(p) : *p;
-}
-
 // Values and columns of chunk c for this lane.  FULL: all eight slots (every chunk but the last of a slice);
 // otherwise only the first w: unused value blocks are not loaded (an odd w loads its last entry with one 8-B load).
 // Columns by the chunk's mode (meta[c][0]: bit 31 int32, bit 30 8-bit codes, else 16-bit codes on the slot bases).
@@ -35,7 +29,7 @@ __device__ inline void read_chunk(int c, int w, int lane, const double* __restri
   const double* __restrict__ sp = svals + (size_t)c * 512;
   if (DICT == 1 || DICT == 2 || (DICT == 3 && dict != nullptr))
   {
-    const uint4v q = sp_load<NT>(reinterpret_cast<const uint4v*>(vcode + (size_t)c * 512) + lane);
+    const uint4v q = vload<NT>(reinterpret_cast<const uint4v*>(vcode + (size_t)c * 512) + lane);
     // DICT == 2: `dict` is the workgroup's copy in LDS (a small dictionary: the lanes of a slice mostly hold the same
     // code in a slot -- broadcast reads); DICT == 1: gathers from memory; DICT == 3: the slice's own table in the
     // wavefront's LDS (dict == nullptr: this slice stays doubles, below)
@@ -54,10 +48,10 @@ __device__ inline void read_chunk(int c, int w, int lane, const double* __restri
   for (int j = 0; j < 4; ++j)
   {
     if (FULL || 2 * j + 1 < w)
-      v[j] = sp_load<NT>(reinterpret_cast<const dbl2*>(sp + 128 * j) + lane);
+      v[j] = vload<NT>(reinterpret_cast<const dbl2*>(sp + 128 * j) + lane);
     else if (2 * j < w)
     {
-      v[j].x = sp_load<NT>(sp + 128 * j + lane);
+      v[j].x = vload<NT>(sp + 128 * j + lane);
       v[j].y = 0.0;
     }
     else
@@ -108,7 +102,7 @@ __device__ inline void read_chunk(int c, int w, int lane, const double* __restri
   else if (m0 < 0)
   {
     const int4v* __restrict__ cp = reinterpret_cast<const int4v*>(c32 + (size_t)c * 512) + 2 * lane;
-    const int4v q0 = sp_load<NT>(cp), q1 = sp_load<NT>(cp + 1);
+    const int4v q0 = vload<NT>(cp), q1 = vload<NT>(cp + 1);
     cl[0] = q0.x, cl[1] = q0.y, cl[2] = q0.z, cl[3] = q0.w;
     cl[4] = q1.x, cl[5] = q1.y, cl[6] = q1.z, cl[7] = q1.w;
   }
@@ -122,8 +116,8 @@ __device__ inline void read_chunk(int c, int w, int lane, const double* __restri
   }
   else if (m0 & 0x40000000)
   {
-    const uint2v q = (m0 & 0x20000000) ? sp_load<NT>(reinterpret_cast<const uint2v*>(sp + 448) + lane)
-                                       : sp_load<NT>(reinterpret_cast<const uint2v*>(c16 + (size_t)c * 512) + lane);
+    const uint2v q = (m0 & 0x20000000) ? vload<NT>(reinterpret_cast<const uint2v*>(sp + 448) + lane)
+                                       : vload<NT>(reinterpret_cast<const uint2v*>(c16 + (size_t)c * 512) + lane);
     cl[0] = (m0 & 0x1fffffff) + (int)(q.x & 0xffu);
     cl[1] = mp[1] + (int)((q.x >> 8) & 0xffu);
     cl[2] = mp[2] + (int)((q.x >> 16) & 0xffu);
@@ -135,7 +129,7 @@ __device__ inline void read_chunk(int c, int w, int lane, const double* __restri
   }
   else
   {
-    const uint4v q = sp_load<NT>(reinterpret_cast<const uint4v*>(c16 + (size_t)c * 512) + lane);
+    const uint4v q = vload<NT>(reinterpret_cast<const uint4v*>(c16 + (size_t)c * 512) + lane);
     cl[0] = m0 + (int)(q.x & 0xffffu);
     cl[1] = mp[1] + (int)(q.x >> 16);
     cl[2] = mp[2] + (int)(q.y & 0xffffu);
@@ -200,13 +194,13 @@ __global__ __launch_bounds__(SP_BLOCK, 8) void spmv_sellp_kernel(const int2* __r
   __shared__ double red[SP_BLOCK / 64];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int64_t ngroups = group_list ? nlist : (nslices + 3) / 4; // a workgroup takes 4 consecutive slices
-  double dot = 0.0, dot_rx = 0.0, dot_nn = 0.0;
+  RowSums S;
   // A slice is a chain of dependent round trips: (group list ->) descriptor -> values / codes / bases -> gathers.  At the
   // 8-GPU per-rank size a wavefront has two or three slices in all, so the kernel's length is that chain times three;
   // the slice number and descriptor of the NEXT slice are therefore requested (scalar loads) before the current slice's
   // chunks, and those of the first slice before the stop word is looked at.
   auto next_slice = [&](int i, int& s_out, int2& ds_out) -> int { // 1 valid, 0 no slice for this wavefront, -1 done
-    const int64_t gi = sp_xcd_item(ngroups, blockIdx.x, gridDim.x, i);
+    const int64_t gi = xcd_stride_item(ngroups, i);
     if (gi < 0)
       return -1;
     const int64_t g = group_list ? group_list[gi] : gi;
@@ -368,49 +362,26 @@ __global__ __launch_bounds__(SP_BLOCK, 8) void spmv_sellp_kernel(const int2* __r
     }
     if (CHEB)
     {
-      // a term of the Chebyshev-Jacobi polynomial (ChebEpi): x is d, y the next d; DOT marks the last term
       if (r >= 0)
-      {
-        const double gi = -1.0 * (epi.dinv[r] * sum) + epi.g[r];
-        const double dn = epi.c1 * xr + epi.c2 * gi;
-        const double zi = epi.z[r] + dn;
-        epi.z[r] = zi;
-        if (DOT)
-        {
-          const double ri = epi.r[r];
-          dot_rx += ri * zi;
-          dot_nn += nn_is_rr ? ri * ri : zi * zi;
-        }
-        else
-        {
-          epi.g[r] = gi;
-          y[r] = dn;
-        }
-      }
+        cheb_row<DOT>(S, epi, nn_is_rr, r, sum, xr, y);
     }
     else if (r >= 0)
     {
       y[r] = sum;
       if (DOT)
-      {
-        dot += sum * xr;
-        if (rvec)
-        {
-          const double rr_ = rvec[r];
-          dot_rx += rr_ * xr;
-          dot_nn += nn_is_rr ? rr_ * rr_ : xr * xr;
-        }
-      }
+        row_sums(S, rvec != nullptr, nn_is_rr, sum, xr, [&] { return rvec[r]; });
     }
   }
+  // row_sums_store's text, kept here by hand: behind the helper this kernel's scalar registers are allocated differently and
+  // the instantiations on dictionaries spill up to ten more of them
   if (DOT)
   {
-    const double sres = CHEB ? 0.0 : block_reduce_sum(dot, red);
+    const double sres = CHEB ? 0.0 : block_reduce_sum(S.dot, red);
     double s1 = 0.0, s2 = 0.0;
     if (rvec || CHEB)
     {
-      s1 = block_reduce_sum(dot_rx, red);
-      s2 = block_reduce_sum(dot_nn, red);
+      s1 = block_reduce_sum(S.dot_rx, red);
+      s2 = block_reduce_sum(S.dot_nn, red);
     }
     if (threadIdx.x == 0)
     {
@@ -424,7 +395,6 @@ __global__ __launch_bounds__(SP_BLOCK, 8) void spmv_sellp_kernel(const int2* __r
     }
   }
 }
-
 
 // ---- host side ------------------------------------------------------------------------------------------
 // A failed build leaves its form off (and the stream, where there is one, as it is).

@@ -395,12 +395,6 @@ struct BlkArgs
   int pstride, nn_is_rr;
 };
 
-template <bool NT, typename T>
-__device__ inline T bk_ld(const T* p)
-{
-  return NT ? __builtin_nontemporal_load(p) : *p;
-}
-
 __device__ inline unsigned bk_code16(const uint4v& a, const uint4v& b, int e)
 {
   const uint4v& q = e < 8 ? a : b;
@@ -461,7 +455,7 @@ __global__ __launch_bounds__(BK_THREADS) void spmv_blk3_kernel(const int2* __res
   const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(p_y, 0, a.nnodes * 24, 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_r = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(SR ? p_rvec : p_x), 0, a.nnodes * 24, 0x00020000);
 
-  double dot = 0.0, dot_rx = 0.0, dot_nn = 0.0;
+  RowSums Q;
   // One slice of look-ahead: while a slice is summed, the descriptor, the first chunk's flags and codes of the wavefront's next
   // slice are in flight (a slice is a chain list -> descriptor -> flags / bases -> codes -> x; without the look-ahead a
   // wavefront's five slices at C4 are five such chains end to end).  Two named stages, the body exists twice: no register that
@@ -486,8 +480,8 @@ __global__ __launch_bounds__(BK_THREADS) void spmv_blk3_kernel(const int2* __res
       {
         S.fl = __builtin_amdgcn_readfirstlane(p_flags[S.c0]);
         const uint4v* __restrict__ bp = reinterpret_cast<const uint4v*>(p_bcode + (int64_t)S.c0 * 1024) + 2 * lane;
-        S.b0 = bk_ld<NT>(bp);
-        S.b1 = bk_ld<NT>(bp + 1);
+        S.b0 = vload<NT>(bp);
+        S.b1 = vload<NT>(bp + 1);
       }
     }
   };
@@ -521,14 +515,14 @@ __global__ __launch_bounds__(BK_THREADS) void spmv_blk3_kernel(const int2* __res
       {
         fl = __builtin_amdgcn_readfirstlane(p_flags[c]);
         const uint4v* __restrict__ bp = reinterpret_cast<const uint4v*>(p_bcode + (int64_t)c * 1024) + 2 * lane;
-        b0 = bk_ld<NT>(bp);
-        b1 = bk_ld<NT>(bp + 1);
+        b0 = vload<NT>(bp);
+        b1 = vload<NT>(bp + 1);
       }
       if (!(fl & 0x100))
       {
         const uint4v* __restrict__ cp = reinterpret_cast<const uint4v*>(p_ccode + (int64_t)c * 1024) + 2 * lane;
-        q0 = bk_ld<NT>(cp);
-        q1 = bk_ld<NT>(cp + 1);
+        q0 = vload<NT>(cp);
+        q1 = vload<NT>(cp + 1);
       }
       const int width = fl & 31;
       const bool affine = (fl & 0x100) != 0;
@@ -635,32 +629,13 @@ __global__ __launch_bounds__(BK_THREADS) void spmv_blk3_kernel(const int2* __res
       fetch(it_next, N);
     if (CHEB)
     {
-      // a term of the Chebyshev-Jacobi polynomial as the epilogue (ChebEpi, zzz_internal.h; the generic kernel's arithmetic
-      // row by row): x is d, y the next d; DOT marks the last term (sums of <r,z> and the norm, nothing else stored but z)
+      // a term of the Chebyshev-Jacobi polynomial as the epilogue (cheb_row, row by row)
       if (s * 64 + lane < a.nnodes)
       {
         const int r0 = (s * 64 + lane) * 3;
-        const double sum[3] = {a0, a1, a2}, xr[3] = {xr0, xr1, xr2};
-        double dn[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-        {
-          const double gi = -1.0 * (epi.dinv[r0 + c] * sum[c]) + epi.g[r0 + c];
-          dn[c] = epi.c1 * xr[c] + epi.c2 * gi;
-          const double zi = epi.z[r0 + c] + dn[c];
-          epi.z[r0 + c] = zi;
-          if (DOT)
-          {
-            const double ri = epi.r[r0 + c];
-            dot_rx += ri * zi;
-            dot_nn += a.nn_is_rr ? ri * ri : zi * zi;
-          }
-          else
-          {
-            epi.g[r0 + c] = gi;
-            p_y[r0 + c] = dn[c];
-          }
-        }
+        cheb_row<DOT>(Q, epi, a.nn_is_rr, r0, a0, xr0, p_y);
+        cheb_row<DOT>(Q, epi, a.nn_is_rr, r0 + 1, a1, xr1, p_y);
+        cheb_row<DOT>(Q, epi, a.nn_is_rr, r0 + 2, a2, xr2, p_y);
       }
     }
     else
@@ -675,18 +650,9 @@ __global__ __launch_bounds__(BK_THREADS) void spmv_blk3_kernel(const int2* __res
     }
     if (!CHEB && DOT && s * 64 + lane < a.nnodes)
     {
-      dot += a0 * xr0;
-      dot += a1 * xr1;
-      dot += a2 * xr2;
-      if (SR)
-      {
-        dot_rx += rr0 * xr0;
-        dot_rx += rr1 * xr1;
-        dot_rx += rr2 * xr2;
-        dot_nn += a.nn_is_rr ? rr0 * rr0 : xr0 * xr0;
-        dot_nn += a.nn_is_rr ? rr1 * rr1 : xr1 * xr1;
-        dot_nn += a.nn_is_rr ? rr2 * rr2 : xr2 * xr2;
-      }
+      row_sums(Q, SR, a.nn_is_rr, a0, xr0, rr0);
+      row_sums(Q, SR, a.nn_is_rr, a1, xr1, rr1);
+      row_sums(Q, SR, a.nn_is_rr, a2, xr2, rr2);
     }
   };
   {
@@ -707,25 +673,7 @@ __global__ __launch_bounds__(BK_THREADS) void spmv_blk3_kernel(const int2* __res
     }
   }
   if (DOT)
-  {
-    const double sres = CHEB ? 0.0 : block_reduce_sum(dot, red);
-    double s1 = 0.0, s2 = 0.0;
-    if (SR || CHEB)
-    {
-      s1 = block_reduce_sum(dot_rx, red);
-      s2 = block_reduce_sum(dot_nn, red);
-    }
-    if (threadIdx.x == 0)
-    {
-      if (!CHEB)
-        a.partials[blockIdx.x] = sres;
-      if (SR || CHEB)
-      {
-        a.partials[a.pstride + blockIdx.x] = s1;
-        a.partials[2 * a.pstride + blockIdx.x] = s2;
-      }
-    }
-  }
+    row_sums_store(Q, SR, CHEB, a.partials, a.pstride, red);
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------

@@ -858,8 +858,8 @@ __global__ __launch_bounds__(256) void k_sp_pack(const rp_t* __restrict__ rowptr
       {
         const int64_t k = g0 + 64 * u + lane;
         const bool in = k < b;
-        vv[u] = in ? __builtin_nontemporal_load(vals + k) : 0.0;
-        cc[u] = in ? __builtin_nontemporal_load(cols + k) : 0;
+        vv[u] = in ? vload<true>(vals + k) : 0.0;
+        cc[u] = in ? vload<true>(cols + k) : 0;
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u)

@@ -39,12 +39,6 @@ struct PipeArgs
   int pstride, nn_is_rr;
 };
 
-template <bool NT, typename T>
-__device__ inline T pipe_load(const T* p)
-{
-  return NT ? __builtin_nontemporal_load(p) : *p;
-}
-
 // TWO slices per wavefront and step, a lane owning rows 2 l and 2 l + 1 of the 128: where both slices are affine with the same
 // slot layout (slot e of the second starts 64 columns behind slot e of the first: an interior slice pair of a regular mesh --
 // 99.4 % of the pairs at C2; found once per packing, k_sp_pairs) slot e of the pair is ONE run of 128 doubles, i.e. one 16-B
@@ -236,18 +230,18 @@ __global__ __launch_bounds__(SP_BLOCK, SR ? SP_ONE_WGS_SR : SP_ONE_WGS) void spm
     const int c = info & 0x1ffffff, cls = (info >> 29) & 3;
     uint4v q = {0u, 0u, 0u, 0u};
     if (cls == SP_CLS_C16)
-      q = pipe_load<NT>(reinterpret_cast<const uint4v*>(p_c16 + (int64_t)c * 512) + lane);
+      q = vload<NT>(reinterpret_cast<const uint4v*>(p_c16 + (int64_t)c * 512) + lane);
     else if (cls != SP_CLS_NONE)
     {
       const char* cbase = cls == SP_CLS_C8T ? reinterpret_cast<const char*>(p_svals) + ((int64_t)c * 4096 + 3584)
                                             : reinterpret_cast<const char*>(p_c16) + (int64_t)c * 1024;
-      const uint2v t = pipe_load<NT>(reinterpret_cast<const uint2v*>(cbase) + lane);
+      const uint2v t = vload<NT>(reinterpret_cast<const uint2v*>(cbase) + lane);
       q.x = t.x, q.y = t.y;
     }
     return q;
   };
 
-  double dot = 0.0, dot_rx = 0.0, dot_nn = 0.0;
+  RowSums Q;
   int regs_base = 0;
   auto step_scalars = [&](int i, int& ia, int& ib, int& sw) {
     if (i >= n_steps)
@@ -342,14 +336,7 @@ __global__ __launch_bounds__(SP_BLOCK, SR ? SP_ONE_WGS_SR : SP_ONE_WGS) void spm
         sum += v[e] * xv[e];
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(uint2v, sum), rs_y, lane8, s << 9, 0);
     if (DOT && (s << 6) + lane < a.nrows) // (no row, no term: a lane without a row may hold 0 * inf)
-    {
-      dot += sum * xr;
-      if (SR)
-      {
-        dot_rx += rr * xr;
-        dot_nn += a.nn_is_rr ? rr * rr : xr * xr;
-      }
-    }
+      row_sums(Q, SR, a.nn_is_rr, sum, xr, rr);
   };
   auto slice_w = [&](const int (&b)[8], const uint4v vq, int info, int s, bool packed, int half, auto&& between) {
     if (info >= 0) // no such slice
@@ -489,23 +476,25 @@ __global__ __launch_bounds__(SP_BLOCK, SR ? SP_ONE_WGS_SR : SP_ONE_WGS) void spm
         __builtin_amdgcn_raw_buffer_store_b128(out, rs_y, lane16, sa << 9, 0); // (rows beyond the last: the range check)
         if (DOT)
         {
+          // row 2 l before row 2 l + 1.  row_sums' text, kept here by hand: through the helper the eight pair bodies' last sums
+          // are merged behind their branches and the single-reduction form needs 100 registers instead of 89
           const int r0 = (sa << 6) + 2 * lane;
           if (r0 < a.nrows)
           {
-            dot += s0 * xr0;
+            Q.dot += s0 * xr0;
             if (SR)
             {
-              dot_rx += rr0 * xr0;
-              dot_nn += a.nn_is_rr ? rr0 * rr0 : xr0 * xr0;
+              Q.dot_rx += rr0 * xr0;
+              Q.dot_nn += a.nn_is_rr ? rr0 * rr0 : xr0 * xr0;
             }
           }
           if (r0 + 1 < a.nrows)
           {
-            dot += s1 * xr1;
+            Q.dot += s1 * xr1;
             if (SR)
             {
-              dot_rx += rr1 * xr1;
-              dot_nn += a.nn_is_rr ? rr1 * rr1 : xr1 * xr1;
+              Q.dot_rx += rr1 * xr1;
+              Q.dot_nn += a.nn_is_rr ? rr1 * rr1 : xr1 * xr1;
             }
           }
         }
@@ -578,24 +567,7 @@ __global__ __launch_bounds__(SP_BLOCK, SR ? SP_ONE_WGS_SR : SP_ONE_WGS) void spm
   }
 
   if (DOT)
-  {
-    const double sres = block_reduce_sum(dot, red);
-    double s1 = 0.0, s2 = 0.0;
-    if (SR)
-    {
-      s1 = block_reduce_sum(dot_rx, red);
-      s2 = block_reduce_sum(dot_nn, red);
-    }
-    if (threadIdx.x == 0)
-    {
-      a.partials[blockIdx.x] = sres;
-      if (SR)
-      {
-        a.partials[a.pstride + blockIdx.x] = s1;
-        a.partials[2 * a.pstride + blockIdx.x] = s2;
-      }
-    }
-  }
+    row_sums_store(Q, SR, false, a.partials, a.pstride, red);
 }
 
 // the pairs of a freshly packed stream of one-chunk slices (called by the stream's first use, behind the dictionary build)

@@ -726,7 +726,7 @@ __global__ __launch_bounds__(BW_THREADS) void spmv_win_kernel(const int32_t* __r
   if (a.stop_flag && *a.stop_flag) // CG already converged: the host is a few iterations ahead
     return;
   const int64_t nitems = p_list ? a.nlist : (int64_t)a.nblk;
-  double dot = 0.0, dot_rx = 0.0, dot_nn = 0.0;
+  RowSums S;
   for (int i = 0;; ++i)
   {
     const int64_t t = xcd_stride_item(nitems, i);
@@ -796,23 +796,21 @@ __global__ __launch_bounds__(BW_THREADS) void spmv_win_kernel(const int32_t* __r
         if (vpk)
         {
           const uint32_t* __restrict__ vp = p_vpack + ((c0 + jj) * 64 + lane) * 3;
-          R.v.x = NT ? __builtin_nontemporal_load(vp) : vp[0];
-          R.v.y = NT ? __builtin_nontemporal_load(vp + 1) : vp[1];
-          R.v.z = NT ? __builtin_nontemporal_load(vp + 2) : vp[2];
+          R.v.x = vload<NT>(vp);
+          R.v.y = vload<NT>(vp + 1);
+          R.v.z = vload<NT>(vp + 2);
         }
         else
-          R.v = NT ? __builtin_nontemporal_load(reinterpret_cast<const uint4v*>(p_vcode + (c0 + jj) * 512) + lane)
-                   : reinterpret_cast<const uint4v*>(p_vcode + (c0 + jj) * 512)[lane];
+          R.v = vload<NT>(reinterpret_cast<const uint4v*>(p_vcode + (c0 + jj) * 512) + lane);
         if (cpk)
         {
           const uint32_t* __restrict__ cp = p_cpack + ((c0 + jj) * 64 + lane) * 3;
-          R.c.x = NT ? __builtin_nontemporal_load(cp) : cp[0];
-          R.c.y = NT ? __builtin_nontemporal_load(cp + 1) : cp[1];
-          R.c.z = NT ? __builtin_nontemporal_load(cp + 2) : cp[2];
+          R.c.x = vload<NT>(cp);
+          R.c.y = vload<NT>(cp + 1);
+          R.c.z = vload<NT>(cp + 2);
         }
         else
-          R.c = NT ? __builtin_nontemporal_load(reinterpret_cast<const uint4v*>(p_ccode + (c0 + jj) * 512) + lane)
-                   : reinterpret_cast<const uint4v*>(p_ccode + (c0 + jj) * 512)[lane];
+          R.c = vload<NT>(reinterpret_cast<const uint4v*>(p_ccode + (c0 + jj) * 512) + lane);
       };
       auto consume = [&](const Raw& R) {
         unsigned vc[8], cc[8];
@@ -882,61 +880,19 @@ __global__ __launch_bounds__(BW_THREADS) void spmv_win_kernel(const int32_t* __r
       }
       if (CHEB)
       {
-        // a term of the Chebyshev-Jacobi polynomial as the epilogue (ChebEpi; the generic kernel's arithmetic): x is d, y the next d
         if (r >= 0)
-        {
-          const double gi = -1.0 * (epi.dinv[r] * sum) + epi.g[r];
-          const double dn = epi.c1 * xr + epi.c2 * gi;
-          const double zi = epi.z[r] + dn;
-          epi.z[r] = zi;
-          if (DOT)
-          {
-            const double ri = epi.r[r];
-            dot_rx += ri * zi;
-            dot_nn += a.nn_is_rr ? ri * ri : zi * zi;
-          }
-          else
-          {
-            epi.g[r] = gi;
-            p_y[r] = dn;
-          }
-        }
+          cheb_row<DOT>(S, epi, a.nn_is_rr, r, sum, xr, p_y);
       }
       else if (r >= 0)
       {
         p_y[r] = sum;
         if (DOT)
-        {
-          dot += sum * xr;
-          if (SR)
-          {
-            dot_rx += rr * xr;
-            dot_nn += a.nn_is_rr ? rr * rr : xr * xr;
-          }
-        }
+          row_sums(S, SR, a.nn_is_rr, sum, xr, rr);
       }
     }
   }
   if (DOT)
-  {
-    const double sres = CHEB ? 0.0 : block_reduce_sum(dot, red);
-    double s1 = 0.0, s2 = 0.0;
-    if (SR || CHEB)
-    {
-      s1 = block_reduce_sum(dot_rx, red);
-      s2 = block_reduce_sum(dot_nn, red);
-    }
-    if (threadIdx.x == 0)
-    {
-      if (!CHEB)
-        a.partials[blockIdx.x] = sres;
-      if (SR || CHEB)
-      {
-        a.partials[a.pstride + blockIdx.x] = s1;
-        a.partials[2 * a.pstride + blockIdx.x] = s2;
-      }
-    }
-  }
+    row_sums_store(S, SR, CHEB, a.partials, a.pstride, red);
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------

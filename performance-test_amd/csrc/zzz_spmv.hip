@@ -21,24 +21,6 @@
 namespace zzz
 {
 constexpr int SPMV_BLOCK = 256;
-typedef double dbl2 __attribute__((ext_vector_type(2)));
-typedef int int2v __attribute__((ext_vector_type(2)));
-
-// tile index for (workgroup b, step i): XCD x = b % 8 owns tiles [x*T/8, (x+1)*T/8)
-__device__ inline int64_t xcd_tile(int64_t ntiles, int b, int nb, int i)
-{
-  const int xcd = b & 7;
-  const int64_t lo = ntiles * xcd / 8, hi = ntiles * (xcd + 1) / 8;
-  const int wg_in_xcd = b >> 3, n_in_xcd = (nb + 7 - xcd) >> 3;
-  const int64_t t = lo + wg_in_xcd + (int64_t)i * n_in_xcd;
-  return t < hi ? t : -1;
-}
-
-template <bool NT, typename T>
-__device__ inline T stream_load(const T* p)
-{
-  return NT ? __builtin_nontemporal_load(p) : *p;
-}
 
 // One tile descriptor = {first row, end row, first nonzero, end nonzero}: one 16-B load per tile.
 template <bool DOT, bool NT>
@@ -72,13 +54,13 @@ __global__ __launch_bounds__(SPMV_BLOCK, 8) void spmv_tile_kernel(const rp_t* __
   __shared__ __attribute__((aligned(16))) double prod[TILE + 16];
   __shared__ double red[SPMV_BLOCK / 64];
   constexpr int NPASS = TILE / (2 * SPMV_BLOCK);
-  double dot = 0.0, dot_rx = 0.0, dot_nn = 0.0;
+  RowSums S;
   dbl2 v[NPASS];
   int2v c[NPASS];
   int4 td = make_int4(0, 0, 0, 0);
   int bands = 0;
   const int nbands = 1 << (16 - offb);
-  int64_t t = xcd_tile(ntiles, blockIdx.x, gridDim.x, 0);
+  int64_t t = xcd_stride_item(ntiles, 0);
   // every matrix load is unconditional (indices clamped into the padded arrays), so all 2*NPASS
   // loads of a tile are in flight together, ahead of the 2*NPASS gathers that depend on them
   auto issue = [&](const int4 d, const int64_t tt) {
@@ -87,11 +69,11 @@ __global__ __launch_bounds__(SPMV_BLOCK, 8) void spmv_tile_kernel(const rp_t* __
     for (int j = 0; j < NPASS; ++j)
     {
       const int kc = min(s_al + 2 * (int)threadIdx.x + j * 2 * SPMV_BLOCK, nnz_even);
-      v[j] = stream_load<NT>(reinterpret_cast<const dbl2*>(vals + kc));
+      v[j] = vload<NT>(reinterpret_cast<const dbl2*>(vals + kc));
       if (cols16 && d.y >= 0) // packed columns: 4 B per pair instead of 8
-        c[j].x = (int)stream_load<NT>(reinterpret_cast<const unsigned*>(cols16 + kc));
+        c[j].x = (int)vload<NT>(reinterpret_cast<const unsigned*>(cols16 + kc));
       else
-        c[j] = stream_load<NT>(reinterpret_cast<const int2v*>(cols + kc));
+        c[j] = vload<NT>(reinterpret_cast<const int2v*>(cols + kc));
     }
     if (cols16 && d.y >= 0)
       bands = tile_base[tt * nbands + (threadIdx.x & (nbands - 1))];
@@ -143,7 +125,7 @@ __global__ __launch_bounds__(SPMV_BLOCK, 8) void spmv_tile_kernel(const rp_t* __
         *reinterpret_cast<dbl2*>(prod + (kk - s_al)) = pr;
       }
     }
-    const int64_t tn = xcd_tile(ntiles, blockIdx.x, gridDim.x, i + 1);
+    const int64_t tn = xcd_stride_item(ntiles, i + 1);
     __syncthreads();
     if (lpr_shift == 0)
     {
@@ -167,15 +149,7 @@ __global__ __launch_bounds__(SPMV_BLOCK, 8) void spmv_tile_kernel(const rp_t* __
         }
         y[rr] = sum;
         if (DOT)
-        {
-          dot += sum * xr_;
-          if (rvec)
-          {
-            const double rr_ = (rr == r) ? rv : rvec[rr];
-            dot_rx += rr_ * xr_;
-            dot_nn += nn_is_rr ? rr_ * rr_ : xr_ * xr_;
-          }
-        }
+          row_sums(S, rvec != nullptr, nn_is_rr, sum, xr_, [&] { return (rr == r) ? rv : rvec[rr]; });
       }
     }
     else
@@ -204,16 +178,7 @@ __global__ __launch_bounds__(SPMV_BLOCK, 8) void spmv_tile_kernel(const rp_t* __
         {
           y[rr] = sum;
           if (DOT)
-          {
-            const double xr_ = x[rr];
-            dot += sum * xr_;
-            if (rvec)
-            {
-              const double rr_ = rvec[rr];
-              dot_rx += rr_ * xr_;
-              dot_nn += nn_is_rr ? rr_ * rr_ : xr_ * xr_;
-            }
-          }
+            row_sums(S, rvec != nullptr, nn_is_rr, sum, x[rr], [&] { return rvec[rr]; });
         }
       }
     }
@@ -227,27 +192,13 @@ __global__ __launch_bounds__(SPMV_BLOCK, 8) void spmv_tile_kernel(const rp_t* __
     }
   }
   if (DOT)
-  {
-    const double sres = block_reduce_sum(dot, red);
-    if (threadIdx.x == 0)
-      partials[blockIdx.x] = sres;
-    if (rvec)
-    {
-      const double s1 = block_reduce_sum(dot_rx, red);
-      const double s2 = block_reduce_sum(dot_nn, red);
-      if (threadIdx.x == 0)
-      {
-        partials[pstride + blockIdx.x] = s1;
-        partials[2 * pstride + blockIdx.x] = s2;
-      }
-    }
-  }
+    row_sums_store(S, rvec != nullptr, false, partials, pstride, red);
 }
 
 static int tile_grid(int64_t ntiles)
 {
   // 8 workgroups of 256 threads per CU; always a multiple of 8 so that every XCD residue
-  // (blockIdx % 8) that owns tiles in xcd_tile() has at least one workgroup
+  // (blockIdx % 8) that owns tiles in xcd_stride_item() has at least one workgroup
   int64_t g = 256 * 8;
   const int64_t need = (ntiles + 7) / 8 * 8;
   if (g > need)
