@@ -111,7 +111,23 @@ enum
    * (1 term at a vertex, 2 on an edge with the weights of the Pk nodes, 3 x 1/3 at a face centroid), closed form, no P
    * stored, fixed summation order, constrained dofs zeroed on both sides.  At order 1 it builds exactly ZZZ_PC_MG's
    * hierarchy.  ZZZ_PC_MG itself keeps declining orders 2 and 3. */
-  ZZZ_PC_PMG = 4
+  ZZZ_PC_PMG = 4,
+  /* Unsmoothed (plain) aggregation multigrid from the assembled matrix alone (PETSc: -pc_type gamg
+   * -pc_gamg_agg_nsmooths 0).  Served: any context with a sparsity pattern and matrix values -- generated, uploaded,
+   * unstructured or zzz_csr_upload_values feeds, block size 1 and 3, orders 1 to 3 -- with ZZZ_OP_CSR, ZZZ_CG_PETSC in its
+   * classical form, all three norm types, one rank.  Declined with ZZZ_ERR_ARG and the reason (the context stays usable):
+   * a communicator attached, ZZZ_OP_MATFREE, single_reduction, ZZZ_CG_PIPE, ZZZ_CG_CGH.  Per level: the block dofs with an
+   * unconstrained component are the nodes of a graph (adjacent: a nonzero scalar entry in their coupling); the roots
+   * are a distance-2 maximal independent set chosen in synchronous rounds by a fixed integer priority (csrc/zzz_agg.hip
+   * gives the formula), two joining rounds attach the rest, what is left becomes singletons.  P is 1 from each
+   * unconstrained scalar dof to the same component of its aggregate (piecewise constant, never stored; no rigid-body
+   * modes), the coarse matrix is P^T A P summed in one fixed order, built on the device; coarse levels have no Dirichlet
+   * rows.  Levels are added until one has at most pc_mg_coarse_eq_limit scalar dofs (0: 1000), pc_mg_levels is reached,
+   * there are 12, or an aggregation reduces the dofs by less than a factor of 2; the last one is solved with the dense
+   * inverse (at most 4 096 dofs, else declined).  Smoother, cycle and options (pc_degree, pc_ratio, pc_esteig_its) are
+   * ZZZ_PC_MG's.  The hierarchy is kept while pattern and Dirichlet set are kept; new matrix values refresh the coarse
+   * VALUES on the kept aggregates. */
+  ZZZ_PC_AGG = 5
 };
 enum
 {
@@ -514,7 +530,9 @@ int zzz_spmv_values_info2(zzz_ctx* ctx, int n, int64_t* info);
  * PCSetUp(PCMG) behind solver.set_from_options() (src/poisson_problem.cpp:169; README.md:59-146): builds the hierarchy
  * for these options, or refreshes its values after an assembly.  Optional: zzz_cg_solve(pc = ZZZ_PC_MG) does it on first
  * use, inside the solve, where PETSc's PCSetUp runs.  Overwrites the context's Krylov work vectors (not b, not u).
- * opts->pc == ZZZ_PC_PMG builds the p-multigrid hierarchy; any other value is read as ZZZ_PC_MG. */
+ * opts->pc == ZZZ_PC_PMG builds the p-multigrid hierarchy, ZZZ_PC_AGG the aggregation hierarchy (zzz_mg_info then reports
+ * nx = ny = nz = 0 for every level); any other value is read as ZZZ_PC_MG.  One context holds one hierarchy: a set-up
+ * of another kind replaces it. */
 int zzz_mg_setup(zzz_ctx* ctx, const zzz_solver_opts* opts);
 /* PCView of that hierarchy.  level < 0: out = {levels, scalar dofs of the coarsest, set-ups done so far (builds and
  * refreshes), products per V-cycle on level 0, device bytes of the coarse levels, HIP-event ms per V-cycle in the last solve
@@ -528,12 +546,15 @@ int zzz_mg_apply(zzz_ctx* ctx, const double* r, double* z);
  * out = P~ in (in: level + 1, out: level), dir 1 gives out = P~^T in.  P~ = F_f P F_c with F zeroing the constrained
  * dofs.  The restriction sums in a fixed order: two calls give the same bits. */
 int zzz_mg_transfer(zzz_ctx* ctx, int level, int dir, const double* in, double* out);
+/* The matrix of a coarse level (1 <= level < levels) as the hierarchy holds it, for parity checks: 64-bit row pointers
+ * (scalar dofs + 1), columns and values (zzz_mg_info(level) gives the sizes); any of the three may be NULL. */
+int zzz_mg_level_csr(zzz_ctx* ctx, int level, int64_t* rowptr, int32_t* cols, double* vals);
 
 /* Version of this header's ABI: bumped whenever an existing entry point changes what it reads or writes (7: zzz_cg_solve
  * reads the two pc_mg_* fields behind pc_ratio).  ZZZ_PC_PMG did not bump it: a new enumerator changes no struct, no
  * entry point and nothing that a caller built against the earlier header passes or receives -- such a caller never
  * sends the value 4, and a library without it answers that value with ZZZ_ERR_ARG.  Nor did zzz_bc_values_upload: a new
- * entry point, no struct and no existing entry changed. */
+ * entry point, no struct and no existing entry changed.  ZZZ_PC_AGG (5) and zzz_mg_level_csr: the same two arguments. */
 #define ZZZ_ABI_VERSION 7
 int zzz_abi_version(void);
 

@@ -64,6 +64,41 @@ int alloc_problem_vectors(zzz_ctx* ctx)
   ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return ZZZ_OK;
 }
+int ctx_adopt_values(zzz_ctx* ctx)
+{
+  ++ctx->mat_version;
+  ctx->sp_rownnz_fresh = ctx->sp_compact_fresh = false;
+  if (int rc = sell_update(ctx, false))
+    return rc;
+  ctx->have_matrix = true;
+  return ZZZ_OK;
+}
+int ctx_adopt_csr(zzz_ctx* ctx, int bs, int64_t nnodes, int64_t nnz, int max_row_nnz)
+{
+  ctx->order = 0; // (no element: zzz_csr_pattern_build and the assemblies decline such a context)
+  ctx->nd = 0;
+  ctx->bs = bs;
+  ctx->n_owned = nnodes;
+  ctx->n_ghost = 0;
+  ctx->nverts = ctx->ncells = 0;
+  ctx->nrows = ctx->ncols = nnodes * bs;
+  ctx->nnz = nnz;
+  ctx->have_pattern = ctx->have_matrix = false;
+  ctx->have_bc = false;
+  ++ctx->pattern_version;
+  ++ctx->feed_version;
+  if (int rc = alloc_problem_vectors(ctx))
+    return rc;
+  if (int rc = build_tiles_device(ctx, (max_row_nnz + bs - 1) / bs))
+    return rc;
+  ctx->have_sell = ctx->sell_current = ctx->sp_pending = false;
+  ctx->sp_bounds_ok = false;
+  if (ctx->sellp_mode != 0)
+    if (int rc = sellp_pattern_bounds(ctx))
+      return rc;
+  ctx->have_pattern = true;
+  return ctx_adopt_values(ctx);
+}
 // A new dof layout or Dirichlet set: the values of u0 uploaded for the old one mean nothing, and the lifting rows change
 void bc_values_clear(zzz_ctx* ctx)
 {
@@ -154,6 +189,7 @@ int zzz_ctx_create(int device, zzz_ctx** out)
       zzz::preload_comm();
       zzz::preload_matfree();
       zzz::preload_mg();
+      zzz::preload_agg();
       zzz::preload_pmg();
       zzz::preload_nullspace();
       (void)hipGetLastError();
@@ -1038,9 +1074,10 @@ int zzz_cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rno
                                   "-ksp_cg_single_reduction");
   if (o->variant == ZZZ_CG_CGH && o->pc != ZZZ_PC_NONE)
     return fail(ctx, ZZZ_ERR_ARG, "src/cg.h has no preconditioner: use pc = ZZZ_PC_NONE");
-  if (o->pc != ZZZ_PC_NONE && o->pc != ZZZ_PC_JACOBI && o->pc != ZZZ_PC_CHEBYSHEV_JACOBI && o->pc != ZZZ_PC_MG && o->pc != ZZZ_PC_PMG)
-    return fail(ctx, ZZZ_ERR_ARG, "unsupported preconditioner %d (none, jacobi, chebyshev-jacobi, mg, pmg)", o->pc);
-  if (o->pc == ZZZ_PC_MG || o->pc == ZZZ_PC_PMG)
+  if (o->pc != ZZZ_PC_NONE && o->pc != ZZZ_PC_JACOBI && o->pc != ZZZ_PC_CHEBYSHEV_JACOBI && o->pc != ZZZ_PC_MG && o->pc != ZZZ_PC_PMG
+      && o->pc != ZZZ_PC_AGG)
+    return fail(ctx, ZZZ_ERR_ARG, "unsupported preconditioner %d (none, jacobi, chebyshev-jacobi, mg, pmg, agg)", o->pc);
+  if (o->pc == ZZZ_PC_MG || o->pc == ZZZ_PC_PMG || o->pc == ZZZ_PC_AGG)
     if (int rc = mg_check(ctx, o))
       return rc;
   if (o->pc == ZZZ_PC_CHEBYSHEV_JACOBI && o->op != ZZZ_OP_CSR)

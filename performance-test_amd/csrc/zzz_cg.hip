@@ -1136,7 +1136,7 @@ int cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
     return cg_solve_pipe(ctx, o, iters, rnorm); // zzz_cg_pipe.hip
   if (o->pc == ZZZ_PC_CHEBYSHEV_JACOBI && !o->single_reduction)
     return cg_solve_chebyshev(ctx, o, iters, rnorm);
-  if (o->pc == ZZZ_PC_MG || o->pc == ZZZ_PC_PMG)
+  if (o->pc == ZZZ_PC_MG || o->pc == ZZZ_PC_PMG || o->pc == ZZZ_PC_AGG)
     return cg_solve_mg(ctx, o, iters, rnorm);
   if (o->single_reduction)
     return cg_solve_single_reduction(ctx, o, iters, rnorm);

@@ -100,7 +100,8 @@ struct DevBuf
 };
 
 struct Comm; // zzz_comm.cpp
-struct MgHier; // zzz_mg.hip: the level hierarchy of ZZZ_PC_MG and ZZZ_PC_PMG
+struct MgHier; // zzz_mg.hip: the level hierarchy of ZZZ_PC_MG, ZZZ_PC_PMG and ZZZ_PC_AGG
+struct AggLevel; // zzz_agg.hip: the aggregates of one level of ZZZ_PC_AGG and the Galerkin sum to the next
 
 typedef int64_t rp_t; // row pointers of the CSR matrix of record
 
@@ -505,6 +506,7 @@ void set_global_error(const char* msg);
     hipFuncAttributes a;                                                                                              \
     (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_preload_##name));                                 \
   }
+void preload_agg();
 void preload_assemble();
 void preload_cg();
 void preload_cg_pipe();
@@ -527,6 +529,11 @@ void preload_spmv();
 
 // api
 int alloc_problem_vectors(zzz_ctx* ctx);
+// A context without mesh or dofmap takes the CSR that its rowptr / cols / vals already hold (zzz_agg.hip's coarse levels):
+// nnodes block dofs of bs components in identity order, no ghosts, no Dirichlet rows; tiles, vectors and product stream
+// as zzz_csr_pattern_build and an assembly leave them.  ctx_adopt_values: the values alone were rewritten.
+int ctx_adopt_csr(zzz_ctx* ctx, int bs, int64_t nnodes, int64_t nnz, int max_row_nnz);
+int ctx_adopt_values(zzz_ctx* ctx);
 // pattern (zzz_pattern.hip)
 int pattern_build_device(zzz_ctx* ctx, bool* fallback);
 void pattern_reserve(zzz_ctx* ctx); // scratch sized by the dofmap, reserved at upload time
@@ -654,6 +661,16 @@ int pmg_prolong(zzz_ctx* ctx, const int* stop, int order, int bs, const int64_t 
                 const double* ec, double* xf, int accumulate);
 int pmg_restrict(zzz_ctx* ctx, const int* stop, int order, int bs, const int64_t n[3], const uint8_t* bcf, const uint8_t* bcc,
                  const double* rf, const double* sub, double* rc);
+// zzz_agg.hip (ZZZ_PC_AGG): the aggregates of f's matrix; A_c = P^T A P adopted by the child context c; its values again on
+// the kept aggregates; the two transfers enqueued on ctx->stream (bcf: the fine level's Dirichlet bytes)
+AggLevel* agg_new();
+void agg_free(AggLevel* A);
+int64_t agg_count(const AggLevel* A);
+int agg_aggregate(zzz_ctx* ctx, zzz_ctx* f, AggLevel* A);
+int agg_galerkin(zzz_ctx* ctx, zzz_ctx* f, AggLevel* A, zzz_ctx* c);
+int agg_refresh(zzz_ctx* ctx, zzz_ctx* f, AggLevel* A, zzz_ctx* c);
+int agg_restrict(zzz_ctx* ctx, const int* stop, const AggLevel* A, const uint8_t* bcf, const double* rf, const double* sub, double* rc);
+int agg_prolong(zzz_ctx* ctx, const int* stop, const AggLevel* A, const uint8_t* bcf, const double* ec, double* xf, int accumulate);
 // zzz_cg.hip: the spectrum bound of D^-1 A as ZZZ_PC_CHEBYSHEV_JACOBI takes it (cached per mat_version); leaves ctx->dinv = 1 / diag(A)
 int chebyshev_bound(zzz_ctx* ctx, const zzz_solver_opts* o, double* hi);
 int cg_solve_mg(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm);

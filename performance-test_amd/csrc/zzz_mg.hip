@@ -22,6 +22,9 @@
 // (a child context like the others), levels 2.. the hierarchy above of that P1 problem.  The pair (0, 1) is transferred by
 // zzz_pmg.hip; smoother, cycle, set-up caching, refresh, stop flag and profiling are the ones here.  At order 1
 // ZZZ_PC_PMG is ZZZ_PC_MG.
+//
+// ZZZ_PC_AGG builds its levels from the matrix instead (zzz_agg.hip: aggregates, P^T A P into child contexts that adopt the
+// CSR, the two transfers); everything else -- smoother, cycle, dense solve, caching, refresh, profiling -- is the one here.
 #include "zzz_cg.h"
 
 #include <algorithm>
@@ -29,6 +32,7 @@
 #include <chrono>
 #include <cmath>
 #include <memory>
+#include <vector>
 
 namespace zzz
 {
@@ -247,6 +251,8 @@ struct MgLevel
   MgGeom G{};
   DevBuf<int32_t> tc, rng;
   DevBuf<double> tf;
+  AggLevel* agg = nullptr; // ZZZ_PC_AGG: the aggregates of this level (zzz_agg.hip); the transfer is theirs, without tables
+  ~MgLevel() { agg_free(agg); }
 };
 
 struct MgHier
@@ -256,6 +262,8 @@ struct MgHier
   int degree = 2, est_its = 0, opt_levels = 0, opt_limit = 0;
   double ratio = 10.0;
   uint64_t feed_version = 0, mat_version = ~0ull;
+  bool agg = false; // built by ZZZ_PC_AGG: kept while pattern and Dirichlet set are (the aggregates depend on both)
+  uint64_t pattern_version = 0, bc_version = 0;
   int setups = 0;
   double coarse_bytes = 0.0;
   double setup_ms = 0.0; // host time of the last set-up that did work (it ends synchronised)
@@ -291,8 +299,8 @@ double mg_level0_bound(const zzz_ctx* ctx) { return ctx->mg && ctx->mg->ready ? 
 
 int mg_check(zzz_ctx* ctx, const zzz_solver_opts* o)
 {
-  const bool pmg = o->pc == ZZZ_PC_PMG;
-  const char* tag = pmg ? "-pc_type pmg" : "-pc_type mg";
+  const bool pmg = o->pc == ZZZ_PC_PMG, agg = o->pc == ZZZ_PC_AGG;
+  const char* tag = agg ? "-pc_type agg" : pmg ? "-pc_type pmg" : "-pc_type mg";
   if (o->variant == ZZZ_CG_PIPE)
     return fail(ctx, ZZZ_ERR_ARG, "%s: not with -ksp_type pipecg (ZZZ_CG_PIPE takes jacobi or none)", tag);
   if (o->variant != ZZZ_CG_PETSC)
@@ -303,6 +311,21 @@ int mg_check(zzz_ctx* ctx, const zzz_solver_opts* o)
     return fail(ctx, ZZZ_ERR_ARG, "%s: needs the assembled operator, not ZZZ_OP_MATFREE", tag);
   if (ctx->comm)
     return fail(ctx, ZZZ_ERR_ARG, "%s: a communicator is attached; multi-rank multigrid is not built", tag);
+  if (agg)
+  {
+    // the matrix alone: whatever feed, order, numbering or source of the values
+    if (!ctx->have_pattern || !ctx->have_matrix)
+      return fail(ctx, ZZZ_ERR_ARG, "%s: needs a sparsity pattern and matrix values", tag);
+    if (ctx->n_ghost != 0)
+      return fail(ctx, ZZZ_ERR_ARG, "%s: the context has %lld ghost dofs: one rank only", tag, (long long)ctx->n_ghost);
+    if (ctx->bs != 1 && ctx->bs != 3)
+      return fail(ctx, ZZZ_ERR_ARG, "%s: block size %d", tag, ctx->bs);
+    if (o->pc_degree < 0 || o->pc_degree > 64 || o->pc_esteig_its > 64)
+      return fail(ctx, ZZZ_ERR_ARG, "%s: smoother degree 1..64, estimate <= 64 steps", tag);
+    if (o->pc_mg_levels < 0 || o->pc_mg_coarse_eq_limit < 0)
+      return fail(ctx, ZZZ_ERR_ARG, "%s: negative pc_mg_levels or pc_mg_coarse_eq_limit", tag);
+    return ZZZ_OK;
+  }
   if (!ctx->cube_feed)
     return fail(ctx, ZZZ_ERR_ARG, "%s: the feed was uploaded (unstructured or host-built), not generated by "
                                   "zzz_cube_generate: the library does not know the cube to coarsen", tag);
@@ -329,7 +352,7 @@ int mg_check(zzz_ctx* ctx, const zzz_solver_opts* o)
 // the error of a child context becomes the caller's
 static int child_fail(zzz_ctx* ctx, zzz_ctx* c, int rc, int level, const char* what)
 {
-  return fail(ctx, rc, "-pc_type mg / pmg, level %d, %s: %s", level, what, c ? c->err.c_str() : zzz_last_error(nullptr));
+  return fail(ctx, rc, "-pc_type mg / pmg / agg, level %d, %s: %s", level, what, c ? c->err.c_str() : zzz_last_error(nullptr));
 }
 
 static int mg_build_tables(zzz_ctx* ctx, MgLevel& F, const MgLevel& C)
@@ -465,10 +488,66 @@ static int mg_dense_inverse(zzz_ctx* ctx, MgHier& H)
   return ZZZ_OK;
 }
 
+// a child context on the caller's stream: the cycle needs no event between levels
+static int mg_child_create(zzz_ctx* ctx, int level, zzz_ctx** out)
+{
+  zzz_ctx* c = nullptr;
+  if (int rc = zzz_ctx_create(ctx->device, &c))
+    return child_fail(ctx, nullptr, rc, level, "context");
+  (void)hipStreamDestroy(c->stream);
+  c->stream = ctx->stream;
+  c->stream_borrowed = true;
+  *out = c;
+  return ZZZ_OK;
+}
+
+// ZZZ_PC_AGG: level l + 1 from the aggregates of level l's matrix (zzz_agg.hip), until a level is small enough, the level
+// limit is reached, or an aggregation reduces the dofs by less than a factor of 2 (that level is then the last)
+static int mg_build_agg(zzz_ctx* ctx, MgHier* H, int limit, int max_levels)
+{
+  H->lv.emplace_back(new MgLevel());
+  H->lv[0]->ctx = ctx;
+  H->lv[0]->order = 1; // (the order of the element says nothing here: every transfer is the aggregates')
+  H->lv[0]->ndof = ctx->n_owned * ctx->bs;
+  for (;;)
+  {
+    MgLevel& L = *H->lv.back();
+    if (L.ndof <= limit || (int)H->lv.size() >= max_levels)
+      break;
+    L.agg = agg_new();
+    if (int rc = agg_aggregate(ctx, L.ctx, L.agg))
+      return rc;
+    const int64_t ncdof = agg_count(L.agg) * ctx->bs;
+    if (ncdof == 0 || 2 * ncdof > L.ndof)
+    {
+      agg_free(L.agg);
+      L.agg = nullptr;
+      break;
+    }
+    const int l = (int)H->lv.size();
+    H->lv.emplace_back(new MgLevel());
+    MgLevel& C = *H->lv.back();
+    C.ndof = ncdof;
+    if (int rc = mg_child_create(ctx, l, &C.ctx))
+      return rc;
+    // (no block-window product on a level without coordinates; the other forms are packed from the CSR alone)
+    C.ctx->sellp_bwin = 0;
+    if (int rc = agg_galerkin(ctx, L.ctx, L.agg, C.ctx))
+      return rc;
+  }
+  const int64_t dofs = H->lv.back()->ndof;
+  if (dofs > MG_DENSE_MAX)
+    return fail(ctx, ZZZ_ERR_ARG, "-pc_type agg: the coarsest of %d levels has %lld dofs, the dense solve takes at most %lld: "
+                                  "allow more levels (pc_mg_levels) or a lower pc_mg_coarse_eq_limit",
+                (int)H->lv.size(), (long long)dofs, (long long)MG_DENSE_MAX);
+  return ZZZ_OK;
+}
+
 int mg_setup(zzz_ctx* ctx, const zzz_solver_opts* o)
 {
   if (int rc = mg_check(ctx, o))
     return rc;
+  const bool agg = o->pc == ZZZ_PC_AGG;
   const int form = ctx->cube_problem;
   const int limit = o->pc_mg_coarse_eq_limit > 0 ? o->pc_mg_coarse_eq_limit : 1000;
   int max_levels = o->pc_mg_levels > 0 ? std::min<int>(o->pc_mg_levels, MG_MAX_LEVELS) : MG_MAX_LEVELS;
@@ -478,77 +557,99 @@ int mg_setup(zzz_ctx* ctx, const zzz_solver_opts* o)
   MgHier* H = ctx->mg;
   bool built = false;
   const auto t_begin = std::chrono::steady_clock::now();
-  if (!H || !H->ready || H->feed_version != ctx->feed_version || H->opt_levels != o->pc_mg_levels || H->opt_limit != limit)
+  if (!H || !H->ready || H->feed_version != ctx->feed_version || H->opt_levels != o->pc_mg_levels || H->opt_limit != limit || H->agg != agg
+      || (agg && (H->pattern_version != ctx->pattern_version || H->bc_version != ctx->bc_version)))
   {
     // ---- the levels --------------------------------------------------------------------------
     mg_destroy(ctx);
-    // ZZZ_PC_PMG at order > 1: the Pk level first, then the P1 levels from the same cube on; pc_mg_levels counts all
-    const size_t high = ctx->order > 1 ? 1 : 0;
-    std::vector<std::array<int64_t, 3>> dims;
-    if (high)
-      dims.push_back({ctx->cube_n[0], ctx->cube_n[1], ctx->cube_n[2]});
-    dims.push_back({ctx->cube_n[0], ctx->cube_n[1], ctx->cube_n[2]});
-    for (;;)
+    if (agg)
     {
-      const auto& d = dims.back();
-      const int64_t dofs = (d[0] + 1) * (d[1] + 1) * (d[2] + 1) * ctx->bs;
-      if (dofs <= limit || (d[0] <= 2 && d[1] <= 2 && d[2] <= 2) || (int)dims.size() >= max_levels)
-        break;
-      dims.push_back({std::max<int64_t>(2, (d[0] + 1) / 2), std::max<int64_t>(2, (d[1] + 1) / 2), std::max<int64_t>(2, (d[2] + 1) / 2)});
-    }
-    {
-      const auto& d = dims.back();
-      const int64_t dofs = (d[0] + 1) * (d[1] + 1) * (d[2] + 1) * ctx->bs;
-      if (dofs > MG_DENSE_MAX)
-        return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg: the coarsest of %d levels has %lld dofs, the dense solve takes at most %lld: "
-                                      "allow more levels (pc_mg_levels) or a lower pc_mg_coarse_eq_limit",
-                    (int)dims.size(), (long long)dofs, (long long)MG_DENSE_MAX);
-    }
-    size_t free0 = 0, free1 = 0, total = 0;
-    ZZZ_HIP(ctx, hipMemGetInfo(&free0, &total));
-    H = ctx->mg = new MgHier();
-    for (size_t l = 0; l < dims.size(); ++l)
-    {
-      H->lv.emplace_back(new MgLevel());
-      MgLevel& L = *H->lv.back();
-      for (int a = 0; a < 3; ++a)
-        L.n[a] = dims[l][(size_t)a];
-      L.ndof = (L.n[0] + 1) * (L.n[1] + 1) * (L.n[2] + 1) * ctx->bs;
-      if (l == 0)
+      size_t free0 = 0, free1 = 0, total = 0;
+      ZZZ_HIP(ctx, hipMemGetInfo(&free0, &total));
+      H = ctx->mg = new MgHier();
+      H->agg = true;
+      if (int rc = mg_build_agg(ctx, H, limit, max_levels))
       {
-        L.ctx = ctx;
-        L.order = ctx->order;
-        L.ndof = ctx->n_owned * ctx->bs;
-        continue;
-      }
-      zzz_ctx* c = nullptr;
-      if (int rc = zzz_ctx_create(ctx->device, &c))
-        return child_fail(ctx, nullptr, rc, (int)l, "context");
-      // every level enqueues on the caller's stream: the cycle needs no event between levels
-      (void)hipStreamDestroy(c->stream);
-      c->stream = ctx->stream;
-      c->stream_borrowed = true;
-      L.ctx = c;
-      if (int rc = zzz_cube_generate(c, form, 1, L.n[0], L.n[1], L.n[2], 1, 0, nullptr))
-        return child_fail(ctx, c, rc, (int)l, "generate");
-      if (int rc = zzz_csr_pattern_build(c))
-        return child_fail(ctx, c, rc, (int)l, "pattern");
-      if (c->renumbered || c->n_owned * c->bs != L.ndof)
-        return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg / pmg, level %d: the generated level is not in lexicographic order", (int)l);
-    }
-    for (size_t l = high; l + 1 < H->lv.size(); ++l)
-      if (int rc = mg_build_tables(ctx, *H->lv[l], *H->lv[l + 1]))
+        mg_destroy(ctx);
         return rc;
-    // smoother work vectors of every level that smooths (level 0's as ZZZ_PC_CHEBYSHEV_JACOBI allocates them)
-    for (size_t l = 0; l + 1 < H->lv.size(); ++l)
-    {
-      zzz_ctx* c = H->lv[l]->ctx;
-      ZZZ_HIP(ctx, c->cheb_d.alloc((size_t)c->nloc()));
-      ZZZ_HIP(ctx, c->cheb_d2.alloc((size_t)c->nloc()));
-      ZZZ_HIP(ctx, c->cheb_g.alloc((size_t)c->nloc()));
+      }
+      for (size_t l = 0; l + 1 < H->lv.size(); ++l)
+      {
+        zzz_ctx* c = H->lv[l]->ctx;
+        ZZZ_HIP(ctx, c->cheb_d.alloc((size_t)c->nloc()));
+        ZZZ_HIP(ctx, c->cheb_d2.alloc((size_t)c->nloc()));
+        ZZZ_HIP(ctx, c->cheb_g.alloc((size_t)c->nloc()));
+      }
+      ZZZ_HIP(ctx, hipMemGetInfo(&free1, &total));
+      H->coarse_bytes = free0 > free1 ? (double)(free0 - free1) : 0.0;
+      H->pattern_version = ctx->pattern_version;
+      H->bc_version = ctx->bc_version;
     }
-    ZZZ_HIP(ctx, hipMemGetInfo(&free1, &total));
-    H->coarse_bytes = free0 > free1 ? (double)(free0 - free1) : 0.0; // (set-up scratch of the levels included; level 0's smoother vectors too)
+    else
+    {
+      // ZZZ_PC_PMG at order > 1: the Pk level first, then the P1 levels from the same cube on; pc_mg_levels counts all
+      const size_t high = ctx->order > 1 ? 1 : 0;
+      std::vector<std::array<int64_t, 3>> dims;
+      if (high)
+        dims.push_back({ctx->cube_n[0], ctx->cube_n[1], ctx->cube_n[2]});
+      dims.push_back({ctx->cube_n[0], ctx->cube_n[1], ctx->cube_n[2]});
+      for (;;)
+      {
+        const auto& d = dims.back();
+        const int64_t dofs = (d[0] + 1) * (d[1] + 1) * (d[2] + 1) * ctx->bs;
+        if (dofs <= limit || (d[0] <= 2 && d[1] <= 2 && d[2] <= 2) || (int)dims.size() >= max_levels)
+          break;
+        dims.push_back({std::max<int64_t>(2, (d[0] + 1) / 2), std::max<int64_t>(2, (d[1] + 1) / 2), std::max<int64_t>(2, (d[2] + 1) / 2)});
+      }
+      {
+        const auto& d = dims.back();
+        const int64_t dofs = (d[0] + 1) * (d[1] + 1) * (d[2] + 1) * ctx->bs;
+        if (dofs > MG_DENSE_MAX)
+          return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg: the coarsest of %d levels has %lld dofs, the dense solve takes at most %lld: "
+                                        "allow more levels (pc_mg_levels) or a lower pc_mg_coarse_eq_limit",
+                      (int)dims.size(), (long long)dofs, (long long)MG_DENSE_MAX);
+      }
+      size_t free0 = 0, free1 = 0, total = 0;
+      ZZZ_HIP(ctx, hipMemGetInfo(&free0, &total));
+      H = ctx->mg = new MgHier();
+      for (size_t l = 0; l < dims.size(); ++l)
+      {
+        H->lv.emplace_back(new MgLevel());
+        MgLevel& L = *H->lv.back();
+        for (int a = 0; a < 3; ++a)
+          L.n[a] = dims[l][(size_t)a];
+        L.ndof = (L.n[0] + 1) * (L.n[1] + 1) * (L.n[2] + 1) * ctx->bs;
+        if (l == 0)
+        {
+          L.ctx = ctx;
+          L.order = ctx->order;
+          L.ndof = ctx->n_owned * ctx->bs;
+          continue;
+        }
+        if (int rc = mg_child_create(ctx, (int)l, &L.ctx))
+          return rc;
+        zzz_ctx* c = L.ctx;
+        if (int rc = zzz_cube_generate(c, form, 1, L.n[0], L.n[1], L.n[2], 1, 0, nullptr))
+          return child_fail(ctx, c, rc, (int)l, "generate");
+        if (int rc = zzz_csr_pattern_build(c))
+          return child_fail(ctx, c, rc, (int)l, "pattern");
+        if (c->renumbered || c->n_owned * c->bs != L.ndof)
+          return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg / pmg, level %d: the generated level is not in lexicographic order", (int)l);
+      }
+      for (size_t l = high; l + 1 < H->lv.size(); ++l)
+        if (int rc = mg_build_tables(ctx, *H->lv[l], *H->lv[l + 1]))
+          return rc;
+      // smoother work vectors of every level that smooths (level 0's as ZZZ_PC_CHEBYSHEV_JACOBI allocates them)
+      for (size_t l = 0; l + 1 < H->lv.size(); ++l)
+      {
+        zzz_ctx* c = H->lv[l]->ctx;
+        ZZZ_HIP(ctx, c->cheb_d.alloc((size_t)c->nloc()));
+        ZZZ_HIP(ctx, c->cheb_d2.alloc((size_t)c->nloc()));
+        ZZZ_HIP(ctx, c->cheb_g.alloc((size_t)c->nloc()));
+      }
+      ZZZ_HIP(ctx, hipMemGetInfo(&free1, &total));
+      H->coarse_bytes = free0 > free1 ? (double)(free0 - free1) : 0.0; // (set-up scratch of the levels included; level 0's smoother vectors too)
+    }
     H->feed_version = ctx->feed_version;
     H->opt_levels = o->pc_mg_levels;
     H->opt_limit = limit;
@@ -569,7 +670,14 @@ int mg_setup(zzz_ctx* ctx, const zzz_solver_opts* o)
     {
       MgLevel& L = *H->lv[l];
       zzz_ctx* c = L.ctx;
-      if (l > 0 && values)
+      if (l > 0 && values && agg)
+      {
+        // (a build has just summed them; a refresh sums the new values on the kept aggregates, level by level)
+        if (!built)
+          if (int rc = agg_refresh(ctx, H->lv[l - 1]->ctx, H->lv[l - 1]->agg, c))
+            return child_fail(ctx, c, rc, (int)l, "coarse values");
+      }
+      else if (l > 0 && values)
         if (int rc = zzz_assemble_matrix(c, form))
           return child_fail(ctx, c, rc, (int)l, "assembly");
       L.hi = L.lo = 0.0;
@@ -603,6 +711,8 @@ int mg_setup(zzz_ctx* ctx, const zzz_solver_opts* o)
 
 static int mg_restrict(zzz_ctx* ctx, const int* stop, MgLevel& F, MgLevel& C, const double* rf, const double* sub, double* rc)
 {
+  if (F.agg)
+    return agg_restrict(ctx, stop, F.agg, F.ctx->bc.p, rf, sub, rc);
   if (F.order > 1)
     return pmg_restrict(ctx, stop, F.order, ctx->bs, F.n, F.ctx->bc.p, C.ctx->bc.p, rf, sub, rc);
   const int g = vgrid(F.G.ncv * 8); // (a thread walks up to 64 fine vertices: one coarse vertex per thread, no striding)
@@ -616,6 +726,8 @@ static int mg_restrict(zzz_ctx* ctx, const int* stop, MgLevel& F, MgLevel& C, co
 }
 static int mg_prolong(zzz_ctx* ctx, const int* stop, MgLevel& F, MgLevel& C, const double* ec, double* xf, int accumulate)
 {
+  if (F.agg)
+    return agg_prolong(ctx, stop, F.agg, F.ctx->bc.p, ec, xf, accumulate);
   if (F.order > 1)
     return pmg_prolong(ctx, stop, F.order, ctx->bs, F.n, F.ctx->bc.p, C.ctx->bc.p, ec, xf, accumulate);
   hipLaunchKernelGGL(k_mg_prolong, dim3(vgrid(F.G.nfv * 4)), dim3(VB), 0, ctx->stream, stop, F.G, F.tc.p, F.tf.p, F.ctx->bc.p, C.ctx->bc.p,
@@ -744,7 +856,7 @@ int zzz_mg_setup(zzz_ctx* ctx, const zzz_solver_opts* opts)
   if (!opts)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_mg_setup: NULL options");
   zzz_solver_opts o = *opts;
-  o.pc = opts->pc == ZZZ_PC_PMG ? ZZZ_PC_PMG : ZZZ_PC_MG;
+  o.pc = opts->pc == ZZZ_PC_PMG ? ZZZ_PC_PMG : opts->pc == ZZZ_PC_AGG ? ZZZ_PC_AGG : ZZZ_PC_MG;
   if (int rc = mg_setup(ctx, &o))
     return rc;
   ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -801,11 +913,21 @@ int zzz_mg_apply(zzz_ctx* ctx, const double* r, double* z)
   const size_t n = (size_t)(ctx->n_owned * ctx->bs);
   hipStream_t s = ctx->stream;
   ZZZ_HIP(ctx, hipMemsetAsync(ctx->state.p, 0, sizeof(CgState), s)); // (a finished solve leaves its stop flag set)
-  ZZZ_HIP(ctx, hipMemcpyAsync(ctx->r.p, r, n * sizeof(double), hipMemcpyHostToDevice, s));
+  // (a context in an internal dof order -- ZZZ_PC_AGG alone serves one -- translates at the boundary, as zzz_spmv does)
+  std::vector<double> ri, zi;
+  if (ctx->renumbered)
+  {
+    ri.resize(n);
+    zi.resize(n);
+    to_internal(ctx, r, ri.data(), true);
+  }
+  ZZZ_HIP(ctx, hipMemcpyAsync(ctx->r.p, ctx->renumbered ? ri.data() : r, n * sizeof(double), hipMemcpyHostToDevice, s));
   if (int rc = mg_vcycle(ctx, ctx->r.p, ctx->z.p, false))
     return rc;
-  ZZZ_HIP(ctx, hipMemcpyAsync(z, ctx->z.p, n * sizeof(double), hipMemcpyDeviceToHost, s));
+  ZZZ_HIP(ctx, hipMemcpyAsync(ctx->renumbered ? zi.data() : z, ctx->z.p, n * sizeof(double), hipMemcpyDeviceToHost, s));
   ZZZ_HIP(ctx, hipStreamSynchronize(s));
+  if (ctx->renumbered)
+    to_caller(ctx, zi.data(), z, true);
   return ZZZ_OK;
 }
 
@@ -825,6 +947,15 @@ int zzz_mg_transfer(zzz_ctx* ctx, int level, int dir, const double* in, double* 
   hipStream_t s = ctx->stream;
   ZZZ_HIP(ctx, H->tx_in.reserve(nin));
   ZZZ_HIP(ctx, H->tx_out.reserve(nout));
+  // (level 0 of a context in an internal dof order: its side of the pair is translated)
+  const bool tr = level == 0 && ctx->renumbered;
+  std::vector<double> vi;
+  if (tr && dir == 1)
+  {
+    vi.resize(nin);
+    to_internal(ctx, in, vi.data(), true);
+    in = vi.data();
+  }
   ZZZ_HIP(ctx, hipMemcpyAsync(H->tx_in.p, in, nin * sizeof(double), hipMemcpyHostToDevice, s));
   if (dir == 0)
   {
@@ -834,8 +965,36 @@ int zzz_mg_transfer(zzz_ctx* ctx, int level, int dir, const double* in, double* 
   else if (int rc = mg_restrict(ctx, nullptr, F, C, H->tx_in.p, nullptr, H->tx_out.p))
     return rc;
   ZZZ_HIP(ctx, hipGetLastError());
-  ZZZ_HIP(ctx, hipMemcpyAsync(out, H->tx_out.p, nout * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (tr && dir == 0)
+    vi.resize(nout);
+  ZZZ_HIP(ctx, hipMemcpyAsync(tr && dir == 0 ? vi.data() : out, H->tx_out.p, nout * sizeof(double), hipMemcpyDeviceToHost, s));
   ZZZ_HIP(ctx, hipStreamSynchronize(s));
+  if (tr && dir == 0)
+    to_caller(ctx, vi.data(), out, true);
+  return ZZZ_OK;
+}
+
+int zzz_mg_level_csr(zzz_ctx* ctx, int level, int64_t* rowptr, int32_t* cols, double* vals)
+{
+  if (!ctx)
+    return fail(nullptr, ZZZ_ERR_ARG, "NULL context");
+  ZZZ_HIP(ctx, hipSetDevice(ctx->device));
+  MgHier* H = ctx->mg;
+  if (!H || !H->ready)
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_mg_level_csr: no hierarchy (zzz_mg_setup, or a solve with a multigrid preconditioner)");
+  if (level < 1 || (size_t)level >= H->lv.size())
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_mg_level_csr: level %d; the coarse levels are 1 .. %d (level 0 is zzz_csr_download's)", level,
+                (int)H->lv.size() - 1);
+  const zzz_ctx* c = H->lv[(size_t)level]->ctx;
+  if (c->renumbered)
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_mg_level_csr: level %d keeps an internal dof order", level);
+  ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (rowptr)
+    ZZZ_HIP(ctx, hipMemcpy(rowptr, c->rowptr.p, ((size_t)c->nrows + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+  if (cols)
+    ZZZ_HIP(ctx, hipMemcpy(cols, c->cols.p, (size_t)c->nnz * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (vals)
+    ZZZ_HIP(ctx, hipMemcpy(vals, c->vals.p, (size_t)c->nnz * sizeof(double), hipMemcpyDeviceToHost));
   return ZZZ_OK;
 }
 }

@@ -169,7 +169,7 @@ void usage()
                "                                  -ksp_max_it, -ksp_norm_type)\n"
                "  --bc_value arg (=0)             value of u0 at every Dirichlet dof (the reference's u0 is 0); non-zero: the\n"
                "                                  vector assembly lifts it (apply_lifting, bc->set)\n"
-               "PETSc-style solver options honoured: -ksp_type {cg,pipecg} -pc_type {jacobi,none,chebyshev_jacobi,mg,pmg} -ksp_rtol -ksp_atol\n"
+               "PETSc-style solver options honoured: -ksp_type {cg,pipecg} -pc_type {jacobi,none,chebyshev_jacobi,mg,pmg,agg} -ksp_rtol -ksp_atol\n"
                "  -ksp_divtol -pc_chebyshev_jacobi_degree (=3) -pc_chebyshev_jacobi_ratio (=60) -pc_chebyshev_jacobi_esteig (=10)\n"
                "  -ksp_max_it -ksp_norm_type {preconditioned,unpreconditioned,natural} -ksp_view -ksp_monitor\n"
                "  -ksp_cg_single_reduction -ksp_converged_reason -ksp_error_if_not_converged\n"
@@ -178,6 +178,9 @@ void usage()
                "  -pc_mg_coarse_eq_limit (=1000) -mg_levels_ksp_max_it (=2, Chebyshev degree) -mg_levels_ksp_chebyshev_ratio (=10)\n"
                "  -pc_type pmg: p-multigrid, the same with --order 1..3: the Pk matrix is level 0, the P1 problem on the same cube\n"
                "  level 1, -pc_type mg's hierarchy below it; the same -pc_mg_* / -mg_levels_* options (-pc_mg_levels counts all levels)\n"
+               "  -pc_type agg: plain aggregation multigrid from the assembled matrix alone (poisson or elasticity, any --order, both\n"
+               "  mesh types, --ngpus 1, --operator assembled, -ksp_type cg without -ksp_cg_single_reduction); the same -pc_mg_* /\n"
+               "  -mg_levels_* options\n"
                "  -log_view -options_left\n"
             << std::endl;
 }
@@ -550,8 +553,8 @@ void run_rank(Shared& S, std::barrier<>& bar, int rank)
   {
     so.variant = o.ksp_type == "pipecg" ? ZZZ_CG_PIPE : ZZZ_CG_PETSC;
     so.pc = o.pc_type == "none" ? ZZZ_PC_NONE : o.pc_type == "chebyshev_jacobi" ? ZZZ_PC_CHEBYSHEV_JACOBI
-            : o.pc_type == "mg" ? ZZZ_PC_MG : o.pc_type == "pmg" ? ZZZ_PC_PMG : ZZZ_PC_JACOBI;
-    const bool multigrid = o.pc_type == "mg" || o.pc_type == "pmg";
+            : o.pc_type == "mg" ? ZZZ_PC_MG : o.pc_type == "pmg" ? ZZZ_PC_PMG : o.pc_type == "agg" ? ZZZ_PC_AGG : ZZZ_PC_JACOBI;
+    const bool multigrid = o.pc_type == "mg" || o.pc_type == "pmg" || o.pc_type == "agg";
     so.pc_degree = multigrid ? o.mg_degree : o.pc_degree;
     so.pc_ratio = multigrid ? o.mg_ratio : o.pc_ratio;
     so.pc_esteig_its = o.pc_esteig;
@@ -608,7 +611,7 @@ void run_rank(Shared& S, std::barrier<>& bar, int rank)
         S.tcg[rank] = tcg.stop();
         S.rnorm[rank] = rn[0];
         S.rnorm0[rank] = rn[1];
-        if (root && (so.pc == ZZZ_PC_MG || so.pc == ZZZ_PC_PMG)) // PCView: the hierarchy zzz_cg_solve set up above (PCSetUp runs inside ZZZ Solve, as in PETSc)
+        if (root && (so.pc == ZZZ_PC_MG || so.pc == ZZZ_PC_PMG || so.pc == ZZZ_PC_AGG)) // PCView: the hierarchy zzz_cg_solve set up above (PCSetUp runs inside ZZZ Solve, as in PETSc)
         {
           std::array<double, 8> v{};
           ZCK(ctx, zzz_mg_info(ctx, -1, v.data()));
@@ -756,7 +759,7 @@ void solve(int argc, char** argv)
   {
     // what the matrix-free operator declines at block size 3 as at 1 (include/zzz_abi.h), said here before any GPU work
     const char* why = o.op == "matfree" ? "not with --operator matfree (the operator is already matrix-free)"
-                      : o.pc_type == "chebyshev_jacobi" || o.pc_type == "mg" || o.pc_type == "pmg"
+                      : o.pc_type == "chebyshev_jacobi" || o.pc_type == "mg" || o.pc_type == "pmg" || o.pc_type == "agg"
                           ? "-pc_type jacobi or none only (Chebyshev-Jacobi and the multigrid preconditioners need the assembled operator)"
                       : o.ksp_type == "pipecg"    ? "-ksp_type pipecg needs the assembled operator (--cg_solver ksp runs the classical KSPCG)"
                       : o.ksp_cg_single_reduction ? "-ksp_cg_single_reduction needs the assembled operator"
@@ -782,7 +785,8 @@ void solve(int argc, char** argv)
   // src/main.cpp:131-141: "cube", anything else is the unstructured (spoke) mesh
   if (o.ksp_type != "cg" && o.ksp_type != "pipecg")
     throw std::runtime_error("-ksp_type " + o.ksp_type + ": only cg and pipecg are built");
-  if (o.pc_type != "jacobi" && o.pc_type != "none" && o.pc_type != "chebyshev_jacobi" && o.pc_type != "mg" && o.pc_type != "pmg")
+  if (o.pc_type != "jacobi" && o.pc_type != "none" && o.pc_type != "chebyshev_jacobi" && o.pc_type != "mg" && o.pc_type != "pmg"
+      && o.pc_type != "agg")
     throw std::runtime_error("-pc_type " + o.pc_type +
                              ": only jacobi, none, chebyshev_jacobi, mg and pmg are built (hypre/gamg are out of scope: the "
                              "multigrid preconditioner here is the geometric one, -pc_type mg, or -pc_type pmg for --order 2 / 3)");
@@ -822,6 +826,19 @@ void solve(int argc, char** argv)
                                                             : nullptr;
     if (why)
       throw std::runtime_error("-pc_type " + o.pc_type + ": " + why);
+  }
+  if (o.pc_type == "agg")
+  {
+    // what ZZZ_PC_AGG declines (include/zzz_abi.h), said here before any GPU work
+    const char* why = o.ngpus != 1                                       ? "--ngpus 1 only (multi-rank multigrid is not built)"
+                      : o.problem_type != "poisson" && o.problem_type != "elasticity" ? "poisson or elasticity (the assembled matrix is what it coarsens)"
+                      : o.op == "matfree"                                ? "--operator assembled only"
+                      : o.ksp_type != "cg"                               ? "-ksp_type cg only"
+                      : o.ksp_cg_single_reduction                        ? "not with -ksp_cg_single_reduction"
+                      : o.pc_mg_levels < 0 || o.pc_mg_coarse_eq_limit < 0 || o.mg_degree < 0 ? "negative -pc_mg_* / -mg_levels_* value"
+                                                                         : nullptr;
+    if (why)
+      throw std::runtime_error("-pc_type agg: " + std::string(why));
   }
   if (o.ngpus < 1 || (o.comm == "rccl" && o.ngpus > ndev))
     throw std::runtime_error("--ngpus " + std::to_string(o.ngpus) + " but " + std::to_string(ndev) + " GPU(s) visible");
@@ -936,9 +953,12 @@ void solve(int argc, char** argv)
     for (size_t l = 1; l < S.mg_view.size(); ++l)
     {
       const auto& v = S.mg_view[l];
-      std::cout << "  level " << l - 1 << ": cells " << (long long)v[0] << "x" << (long long)v[1] << "x" << (long long)v[2] << ", order "
-                << (l - 1 < (size_t)m[7] ? o.order : 1) << ", dofs "
-                << (long long)v[3] << ", nonzeros " << (long long)v[4];
+      if (o.pc_type == "agg")
+        std::cout << "  level " << l - 1 << ": " << (l == 1 ? "the assembled matrix" : "aggregates of the level above") << ", dofs "
+                  << (long long)v[3] << ", nonzeros " << (long long)v[4];
+      else
+        std::cout << "  level " << l - 1 << ": cells " << (long long)v[0] << "x" << (long long)v[1] << "x" << (long long)v[2] << ", order "
+                  << (l - 1 < (size_t)m[7] ? o.order : 1) << ", dofs " << (long long)v[3] << ", nonzeros " << (long long)v[4];
       if (v[7] > 0)
         std::cout << ", smoother chebyshev-jacobi degree " << (int)v[7] << " on [" << v[6] << ", " << v[5] << "]\n";
       else
