@@ -27,9 +27,7 @@
 // thread then sums each run front to back -- two set-ups give the same bits, and a refresh is that sum alone.
 #include "zzz_cg.h"
 
-#include <cstring> // (rocPRIM's texture_cache_iterator.hpp calls memset without including it)
-
-#include <rocprim/rocprim.hpp>
+#include "zzz_prim.h"
 
 #include <algorithm>
 #include <vector>
@@ -62,8 +60,6 @@ __device__ inline long long agg_priority(long long idx)
   x ^= x >> 31;
   return (long long)(((x >> 33) << 32) | (unsigned long long)(unsigned)idx);
 }
-
-static int agg_grid(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + VB - 1) / VB, 1 << 16)); }
 
 #define AGG_FOR(i, n) for (int64_t i = blockIdx.x * (int64_t)VB + threadIdx.x; i < (n); i += (int64_t)gridDim.x * VB)
 
@@ -417,30 +413,17 @@ AggLevel* agg_new() { return new AggLevel(); }
 void agg_free(AggLevel* A) { delete A; }
 int64_t agg_count(const AggLevel* A) { return A->nagg; }
 
-template <typename F>
-static int agg_with_temp(zzz_ctx* ctx, DevBuf<unsigned char>& tmp, F call)
-{
-  size_t tb = 0;
-  ZZZ_HIP(ctx, call(nullptr, tb));
-  ZZZ_HIP(ctx, tmp.reserve(tb + 16));
-  ZZZ_HIP(ctx, call((void*)tmp.p, tb));
-  return ZZZ_OK;
-}
-
 // flags (caller order) -> numbers base + rank for the flagged nodes; *count = how many
 static int agg_number(zzz_ctx* ctx, AggLevel& A, int what, int32_t base, const int32_t* perm, const int32_t* state,
                       DevBuf<int32_t>& flag, DevBuf<int32_t>& scan, DevBuf<unsigned char>& tmp, int32_t* count)
 {
   hipStream_t s = ctx->stream;
   const int64_t n = A.nf;
-  const int g = agg_grid(n);
+  const int g = grid_cap(n, VB, 1 << 16);
   hipLaunchKernelGGL(k_agg_flags, dim3(g), dim3(VB), 0, s, n, what, perm, state, A.agg.p, flag.p);
-  if (int rc = agg_with_temp(ctx, tmp, [&](void* t, size_t& tb) {
-        return rocprim::exclusive_scan(t, tb, flag.p, scan.p, (int32_t)0, (size_t)n + 1, rocprim::plus<int32_t>(), s);
-      }))
+  if (int rc = with_scratch(ctx, tmp, scan_excl(flag.p, scan.p, (size_t)n + 1, s)))
     return rc;
-  ZZZ_HIP(ctx, hipMemcpyAsync(count, scan.p + n, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  ZZZ_HIP(ctx, hipStreamSynchronize(s));
+  ZZZ_HIP(ctx, dev_fetch(ctx, scan.p + n, count));
   hipLaunchKernelGGL(k_agg_number, dim3(g), dim3(VB), 0, s, n, what, base, perm, flag.p, scan.p, A.agg.p);
   ZZZ_HIP(ctx, hipGetLastError());
   return ZZZ_OK;
@@ -452,7 +435,7 @@ static int agg_aggregate_bs(zzz_ctx* ctx, zzz_ctx* f, AggLevel& A)
 {
   hipStream_t s = ctx->stream;
   const int64_t n = f->n_owned;
-  const int g = agg_grid(n);
+  const int g = grid_cap(n, VB, 1 << 16);
   const int32_t* perm = f->renumbered ? f->perm.p : nullptr;
   A.bs = BS;
   A.nf = n;
@@ -483,8 +466,7 @@ static int agg_aggregate_bs(zzz_ctx* ctx, zzz_ctx* f, AggLevel& A)
     hipLaunchKernelGGL(k_agg_max2<BS>, dim3(g), dim3(VB), 0, s, n, rp, cl, vl, key.p, m1.p, state.p);
     hipLaunchKernelGGL(k_agg_near1<BS>, dim3(g), dim3(VB), 0, s, n, rp, cl, vl, state.p, near.p);
     hipLaunchKernelGGL(k_agg_near2<BS>, dim3(g), dim3(VB), 0, s, n, rp, cl, vl, near.p, state.p, counter.p);
-    ZZZ_HIP(ctx, hipMemcpyAsync(&left, counter.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    ZZZ_HIP(ctx, hipStreamSynchronize(s));
+    ZZZ_HIP(ctx, dev_fetch(ctx, counter.p, &left));
     ++A.rounds;
     if (left == 0)
       break;
@@ -509,9 +491,7 @@ static int agg_aggregate_bs(zzz_ctx* ctx, zzz_ctx* f, AggLevel& A)
   ZZZ_HIP(ctx, A.mem.alloc((size_t)n));
   ZZZ_HIP(ctx, A.moff.alloc((size_t)A.nagg + 1));
   hipLaunchKernelGGL(k_agg_member_keys, dim3(g), dim3(VB), 0, s, n, perm, A.agg.p, mk.p, mv.p);
-  if (int rc = agg_with_temp(ctx, tmp, [&](void* t, size_t& tb) {
-        return rocprim::radix_sort_pairs(t, tb, mk.p, mk2.p, mv.p, A.mem.p, (size_t)n, 0, 32, s);
-      }))
+  if (int rc = with_scratch(ctx, tmp, sort_pairs(mk.p, mk2.p, mv.p, A.mem.p, (size_t)n, 0, 32, s)))
     return rc;
   hipLaunchKernelGGL((k_agg_offsets<uint32_t, int32_t>), dim3(g), dim3(VB), 0, s, mk2.p, n, A.nagg, A.moff.p);
   ZZZ_HIP(ctx, hipGetLastError());
@@ -531,7 +511,7 @@ int agg_aggregate(zzz_ctx* ctx, zzz_ctx* f, AggLevel* A)
 int agg_refresh(zzz_ctx* ctx, zzz_ctx* f, AggLevel* A, zzz_ctx* c)
 {
   if (A->nnzc > 0)
-    hipLaunchKernelGGL(k_agg_values, dim3(agg_grid(A->nnzc)), dim3(VB), 0, ctx->stream, A->nnzc, A->seg.p, A->src.p, f->vals.p, c->vals.p);
+    hipLaunchKernelGGL(k_agg_values, dim3(grid_cap(A->nnzc, VB, 1 << 16)), dim3(VB), 0, ctx->stream, A->nnzc, A->seg.p, A->src.p, f->vals.p, c->vals.p);
   ZZZ_HIP(ctx, hipGetLastError());
   return ctx_adopt_values(c);
 }
@@ -542,7 +522,7 @@ static int agg_galerkin_bs(zzz_ctx* ctx, zzz_ctx* f, AggLevel& A, zzz_ctx* c)
 {
   hipStream_t s = ctx->stream;
   const int64_t N = f->nnz, nrows = f->n_owned * BS, ncdof = A.nagg * BS;
-  const int g = agg_grid(N);
+  const int g = grid_cap(N, VB, 1 << 16);
   DevBuf<int32_t> rowidx, v0, v1, head, pos, crow, stats;
   DevBuf<unsigned long long> k0, k1;
   DevBuf<unsigned char> tmp;
@@ -555,31 +535,24 @@ static int agg_galerkin_bs(zzz_ctx* ctx, zzz_ctx* f, AggLevel& A, zzz_ctx* c)
   ZZZ_HIP(ctx, pos.alloc((size_t)N + 1));
   ZZZ_HIP(ctx, stats.alloc(2));
   ZZZ_HIP(ctx, A.src.alloc((size_t)N));
-  hipLaunchKernelGGL(k_agg_rowidx, dim3(agg_grid(nrows)), dim3(VB), 0, s, nrows, f->rowptr.p, rowidx.p);
+  hipLaunchKernelGGL(k_agg_rowidx, dim3(grid_cap(nrows, VB, 1 << 16)), dim3(VB), 0, s, nrows, f->rowptr.p, rowidx.p);
   const int32_t* order = nullptr;
   if (f->renumbered)
   {
     hipLaunchKernelGGL(k_agg_caller_keys<BS>, dim3(g), dim3(VB), 0, s, N, rowidx.p, f->cols.p, f->perm.p, k0.p, v0.p);
-    if (int rc = agg_with_temp(ctx, tmp, [&](void* t, size_t& tb) {
-          return rocprim::radix_sort_pairs(t, tb, k0.p, k1.p, v0.p, v1.p, (size_t)N, 0, 64, s);
-        }))
+    if (int rc = with_scratch(ctx, tmp, sort_pairs(k0.p, k1.p, v0.p, v1.p, (size_t)N, 0, 64, s)))
       return rc;
     order = v1.p;
   }
   // (v0 may be written while v1 is read: different buffers)
   hipLaunchKernelGGL(k_agg_coarse_keys<BS>, dim3(g), dim3(VB), 0, s, N, order, rowidx.p, f->cols.p, f->bc.p, A.agg.p, k0.p, v0.p);
-  if (int rc = agg_with_temp(ctx, tmp, [&](void* t, size_t& tb) {
-        return rocprim::radix_sort_pairs(t, tb, k0.p, k1.p, v0.p, A.src.p, (size_t)N, 0, 64, s);
-      }))
+  if (int rc = with_scratch(ctx, tmp, sort_pairs(k0.p, k1.p, v0.p, A.src.p, (size_t)N, 0, 64, s)))
     return rc;
   hipLaunchKernelGGL(k_agg_heads, dim3(g), dim3(VB), 0, s, N, k1.p, head.p);
-  if (int rc = agg_with_temp(ctx, tmp, [&](void* t, size_t& tb) {
-        return rocprim::exclusive_scan(t, tb, head.p, pos.p, (int32_t)0, (size_t)N + 1, rocprim::plus<int32_t>(), s);
-      }))
+  if (int rc = with_scratch(ctx, tmp, scan_excl(head.p, pos.p, (size_t)N + 1, s)))
     return rc;
   int32_t nnzc = 0;
-  ZZZ_HIP(ctx, hipMemcpyAsync(&nnzc, pos.p + N, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  ZZZ_HIP(ctx, hipStreamSynchronize(s));
+  ZZZ_HIP(ctx, dev_fetch(ctx, pos.p + N, &nnzc));
   if (nnzc <= 0)
     return fail(ctx, ZZZ_ERR_ARG, "-pc_type agg: the coarse matrix of %lld aggregates is empty", (long long)A.nagg);
   A.nfine = N;
@@ -593,12 +566,11 @@ static int agg_galerkin_bs(zzz_ctx* ctx, zzz_ctx* f, AggLevel& A, zzz_ctx* c)
   ZZZ_HIP(ctx, hipMemsetAsync(c->vals.p + nnzc, 0, 8 * sizeof(double), s));
   ZZZ_HIP(ctx, hipMemsetAsync(stats.p, 0, 2 * sizeof(int32_t), s));
   hipLaunchKernelGGL(k_agg_entries, dim3(g), dim3(VB), 0, s, N, (int64_t)nnzc, k1.p, head.p, pos.p, A.seg.p, c->cols.p, crow.p);
-  hipLaunchKernelGGL((k_agg_offsets<int32_t, rp_t>), dim3(agg_grid(nnzc)), dim3(VB), 0, s, crow.p, (int64_t)nnzc, ncdof, c->rowptr.p);
-  hipLaunchKernelGGL(k_agg_values, dim3(agg_grid(nnzc)), dim3(VB), 0, s, (int64_t)nnzc, A.seg.p, A.src.p, f->vals.p, c->vals.p);
-  hipLaunchKernelGGL(k_agg_rowstats, dim3(agg_grid(ncdof)), dim3(VB), 0, s, ncdof, c->rowptr.p, stats.p);
+  hipLaunchKernelGGL((k_agg_offsets<int32_t, rp_t>), dim3(grid_cap(nnzc, VB, 1 << 16)), dim3(VB), 0, s, crow.p, (int64_t)nnzc, ncdof, c->rowptr.p);
+  hipLaunchKernelGGL(k_agg_values, dim3(grid_cap(nnzc, VB, 1 << 16)), dim3(VB), 0, s, (int64_t)nnzc, A.seg.p, A.src.p, f->vals.p, c->vals.p);
+  hipLaunchKernelGGL(k_agg_rowstats, dim3(grid_cap(ncdof, VB, 1 << 16)), dim3(VB), 0, s, ncdof, c->rowptr.p, stats.p);
   int32_t hs[2] = {0, 0};
-  ZZZ_HIP(ctx, hipMemcpyAsync(hs, stats.p, sizeof(hs), hipMemcpyDeviceToHost, s));
-  ZZZ_HIP(ctx, hipStreamSynchronize(s));
+  ZZZ_HIP(ctx, dev_fetch(ctx, stats.p, hs, 2));
   ZZZ_HIP(ctx, hipGetLastError());
   if (hs[1] > 0)
     return fail(ctx, ZZZ_ERR_ARG, "-pc_type agg: %d coarse dofs have no unconstrained member (aggregates of partly constrained "
@@ -615,7 +587,7 @@ int agg_galerkin(zzz_ctx* ctx, zzz_ctx* f, AggLevel* A, zzz_ctx* c)
 
 int agg_restrict(zzz_ctx* ctx, const int* stop, const AggLevel* A, const uint8_t* bcf, const double* rf, const double* sub, double* rc)
 {
-  const int g = agg_grid(A->nagg);
+  const int g = grid_cap(A->nagg, VB, 1 << 16);
   if (A->bs == 3)
     hipLaunchKernelGGL(k_agg_restrict<3>, dim3(g), dim3(VB), 0, ctx->stream, stop, A->nagg, A->moff.p, A->mem.p, bcf, rf, sub, rc);
   else
@@ -626,7 +598,7 @@ int agg_restrict(zzz_ctx* ctx, const int* stop, const AggLevel* A, const uint8_t
 int agg_prolong(zzz_ctx* ctx, const int* stop, const AggLevel* A, const uint8_t* bcf, const double* ec, double* xf, int accumulate)
 {
   const int64_t n = A->nf * A->bs;
-  const int g = agg_grid(n);
+  const int g = grid_cap(n, VB, 1 << 16);
   if (A->bs == 3)
     hipLaunchKernelGGL(k_agg_prolong<3>, dim3(g), dim3(VB), 0, ctx->stream, stop, n, A->agg.p, bcf, ec, xf, accumulate);
   else

@@ -20,7 +20,7 @@
 
 #include "zzz_asm_elem.h"
 
-#include <rocprim/rocprim.hpp>
+#include "zzz_prim.h"
 
 namespace zzz
 {
@@ -762,8 +762,7 @@ int ensure_p1_coords(zzz_ctx* ctx)
   ZZZ_HIP(ctx, hipMemsetAsync(flag.p, 0, sizeof(int), ctx->stream));
   hipLaunchKernelGGL(k_conn_differs, dim3(g), dim3(256), 0, ctx->stream, ctx->cell_verts.p, ctx->cell_dofs.p, n, flag.p);
   int differs = 0;
-  ZZZ_HIP(ctx, hipMemcpyAsync(&differs, flag.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  ZZZ_HIP(ctx, dev_fetch(ctx, flag.p, &differs));
   if (!differs && ctx->nverts >= nblock)
     ctx->xq = ctx->x.p;
   else
@@ -1439,13 +1438,12 @@ static int lift_rows_build(zzz_ctx* ctx)
                      ctx->rowptr.p, ctx->cols.p, ctx->bc.p, nrows, ctx->lift_flag.p);
   rocprim::counting_iterator<int32_t> ids(0);
   int32_t* count = ctx->lift_rows.p + nrows;
-  size_t tb = 0;
-  ZZZ_HIP(ctx, rocprim::select(nullptr, tb, ids, ctx->lift_flag.p, ctx->lift_rows.p, count, (size_t)nrows, ctx->stream));
-  ZZZ_HIP(ctx, ctx->scr_tmp.grow_keep(tb, ctx->retired));
-  ZZZ_HIP(ctx, rocprim::select(ctx->scr_tmp.p, tb, ids, ctx->lift_flag.p, ctx->lift_rows.p, count, (size_t)nrows, ctx->stream));
+  if (int rc = with_scratch(ctx, [&](void* tmp, size_t& bytes) {
+        return rocprim::select(tmp, bytes, ids, ctx->lift_flag.p, ctx->lift_rows.p, count, (size_t)nrows, ctx->stream);
+      }))
+    return rc;
   int32_t n = 0;
-  ZZZ_HIP(ctx, hipMemcpyAsync(&n, count, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  ZZZ_HIP(ctx, dev_fetch(ctx, count, &n));
   ctx->n_lift_rows = n;
   if (timed)
   {
@@ -1653,19 +1651,13 @@ int build_adjT_offsets(zzz_ctx* ctx)
     ZZZ_HIP(ctx, hipMemsetAsync(tot64.p, 0, sizeof(unsigned long long), ctx->stream));
     hipLaunchKernelGGL(k_adjT_slice_len, dim3(g0), dim3(256), 0, ctx->stream, ctx->adj_off.p, nrows, nsl, slen.p, tot64.p);
     unsigned long long h64 = 0;
-    ZZZ_HIP(ctx, hipMemcpyAsync(&h64, tot64.p, sizeof(h64), hipMemcpyDeviceToHost, ctx->stream));
-    ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ZZZ_HIP(ctx, dev_fetch(ctx, tot64.p, &h64));
     if (h64 > (unsigned long long)(INT32_MAX - 4096))
       return fail(ctx, ZZZ_ERR_LIMIT, "transposed adjacency (%llu entries) exceeds int32: use more parts", h64);
-    size_t tb = 0;
-    ZZZ_HIP(ctx, rocprim::exclusive_scan(nullptr, tb, slen.p, ctx->adjT_off.p, 0, (size_t)nsl + 1, rocprim::plus<int32_t>(),
-                                         ctx->stream));
-    ZZZ_HIP(ctx, tmp.alloc(tb));
-    ZZZ_HIP(ctx, rocprim::exclusive_scan(tmp.p, tb, slen.p, ctx->adjT_off.p, 0, (size_t)nsl + 1, rocprim::plus<int32_t>(),
-                                         ctx->stream));
+    if (int rc = with_scratch(ctx, tmp, scan_excl(slen.p, ctx->adjT_off.p, (size_t)nsl + 1, ctx->stream)))
+      return rc;
     int32_t total = 0;
-    ZZZ_HIP(ctx, hipMemcpyAsync(&total, ctx->adjT_off.p + nsl, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ZZZ_HIP(ctx, dev_fetch(ctx, ctx->adjT_off.p + nsl, &total)); // (waits for the scan: tmp goes with this scope)
     if (total < 0)
       return fail(ctx, ZZZ_ERR_LIMIT, "transposed adjacency exceeds int32");
     ZZZ_HIP(ctx, ctx->adjT_cells.alloc((size_t)total + 64));

@@ -6,7 +6,7 @@
 // host and copied over PCIe.  The closed forms live in host/cube_layout.h and are shared with the
 // host generator (host/mesh_part.cpp), so both feeds are identical integer for integer and the
 // coordinates bit for bit; only exp()/sin() of the coefficients may differ in the last ulp.
-#include "zzz_internal.h"
+#include "zzz_prim.h"
 
 #include "../host/cube_layout.h"
 
@@ -77,15 +77,6 @@ __global__ void k_cube_dofs(int problem, int bs, int64_t nloc, const double* __r
   }
 }
 
-static int gridfor(int64_t n)
-{
-  int64_t g = (n + 255) / 256;
-  if (g > 8192)
-    g = 8192;
-  if (g < 1)
-    g = 1;
-  return (int)g;
-}
 ZZZ_PRELOAD_TU(cubegen)
 } // namespace zzz
 
@@ -131,10 +122,10 @@ extern "C" int zzz_cube_generate(zzz_ctx* ctx, int problem, int order, int64_t n
     return rc;
   DevBuf<double> dof_x;
   ZZZ_HIP(ctx, dof_x.alloc((size_t)(3 * S.nloc)));
-  hipLaunchKernelGGL(k_cube_vertices, dim3(gridfor(S.nverts)), dim3(256), 0, s, S, ctx->x.p);
-  hipLaunchKernelGGL(k_cube_cells, dim3(gridfor(S.ncells)), dim3(256), 0, s, S, ctx->cell_verts.p, ctx->cell_dofs.p,
+  hipLaunchKernelGGL(k_cube_vertices, dim3(grid_cap(S.nverts, 256, 8192)), dim3(256), 0, s, S, ctx->x.p);
+  hipLaunchKernelGGL(k_cube_cells, dim3(grid_cap(S.ncells, 256, 8192)), dim3(256), 0, s, S, ctx->cell_verts.p, ctx->cell_dofs.p,
                      ctx->facet_mask.p, dof_x.p);
-  hipLaunchKernelGGL(k_cube_dofs, dim3(gridfor(S.nloc)), dim3(256), 0, s, problem, bs, S.nloc, dof_x.p, ctx->bc.p,
+  hipLaunchKernelGGL(k_cube_dofs, dim3(grid_cap(S.nloc, 256, 8192)), dim3(256), 0, s, problem, bs, S.nloc, dof_x.p, ctx->bc.p,
                      ctx->coeff[0].p, ctx->coeff[1].p);
   ZZZ_HIP(ctx, hipGetLastError());
   ZZZ_HIP(ctx, hipStreamSynchronize(s));

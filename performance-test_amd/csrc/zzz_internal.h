@@ -62,8 +62,7 @@ struct DevBuf
   // Scratch that may be asked for while ANOTHER context's kernel is waiting for this one (two ranks on one GPU: the other rank
   // polls its all-reduce mailbox inside a kernel while this one still builds its product form): grows only, and a buffer that
   // is too small is RETIRED -- handed to `retired`, freed with the context -- not freed: hipFree waits for every kernel on the
-  // device, i.e. for the poll's time-out (a soak run of elasticity P2 on two ranks: found in round 5 at the
-  // dictionaries' buffers, again in round 6 at the scans' scratch behind a pattern build's larger one).
+  // device, i.e. for the poll's time-out.  The primitives' shared scratch is only ever sized through this (zzz_prim.h).
   hipError_t grow_keep(size_t count, std::vector<void*>& retired)
   {
     if (count == 0)
@@ -249,7 +248,7 @@ struct zzz_ctx
   zzz::DevBuf<int32_t> adj_runs, adj_run_lo, adj_win_base;
   int adj_runs_n = -1;
   int32_t* adj_flag_host = nullptr; // pinned: "a window did not fit" travels here behind the build's kernels
-  zzz::DevBuf<unsigned char> scr_tmp;
+  zzz::DevBuf<unsigned char> scr_tmp; // the device primitives' shared scratch: zzz_prim.h alone touches it
   std::vector<void*> retired; // device buffers replaced by larger ones while another context's kernel may be waiting (DevBuf::grow_keep)
   zzz::DevBuf<int32_t> adj_off, adj_cells; // owned block dof -> incident cells (ascending)
   zzz::DevBuf<int32_t> adjT_off, adjT_cells; // the same lists transposed in 64-row slices (dense wave reads)

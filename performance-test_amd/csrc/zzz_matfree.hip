@@ -27,9 +27,7 @@
 #include <cstring>
 
 #include "zzz_device.h"
-#include "zzz_internal.h"
-
-#include <rocprim/rocprim.hpp>
+#include "zzz_prim.h"
 
 #include <type_traits>
 
@@ -1349,35 +1347,6 @@ struct SegOffset
   __host__ __device__ unsigned operator()(unsigned k) const { return k * seg; }
 };
 
-int grid_for(int64_t n)
-{
-  int64_t g = (n + 255) / 256;
-  return (int)std::min<int64_t>(std::max<int64_t>(g, 1), 8192);
-}
-
-template <typename K, typename V>
-int sort_pairs(zzz_ctx* ctx, DevBuf<K>& kin, DevBuf<K>& kout, DevBuf<V>& vin, DevBuf<V>& vout, size_t n, unsigned end_bit)
-{
-  size_t tb = 0;
-  ZZZ_HIP(ctx, rocprim::radix_sort_pairs(nullptr, tb, kin.p, kout.p, vin.p, vout.p, n, 0u, end_bit, ctx->stream));
-  DevBuf<unsigned char> tmp;
-  ZZZ_HIP(ctx, tmp.alloc(tb));
-  ZZZ_HIP(ctx, rocprim::radix_sort_pairs(tmp.p, tb, kin.p, kout.p, vin.p, vout.p, n, 0u, end_bit, ctx->stream));
-  ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return ZZZ_OK;
-}
-
-int scan_excl(zzz_ctx* ctx, const int32_t* in, int32_t* out, size_t n)
-{
-  size_t tb = 0;
-  ZZZ_HIP(ctx, rocprim::exclusive_scan(nullptr, tb, in, out, 0, n, rocprim::plus<int32_t>(), ctx->stream));
-  DevBuf<unsigned char> tmp;
-  ZZZ_HIP(ctx, tmp.alloc(tb));
-  ZZZ_HIP(ctx, rocprim::exclusive_scan(tmp.p, tb, in, out, 0, n, rocprim::plus<int32_t>(), ctx->stream));
-  ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return ZZZ_OK;
-}
-
 unsigned bits_for(uint64_t v)
 {
   unsigned b = 1;
@@ -1424,6 +1393,9 @@ int plan_attempt(zzz_ctx* ctx, int nc, int T, int nloc_limit, bool* retry)
   M.ndw = nd / 2;
   M.nrw = (nd + 3) / 4;
   M.nblocks = nb;
+  // scratch of the sorts and scans below (the segmented sort has its own): each is waited for where it is called, so that
+  // what it read and wrote may be freed behind it
+  DevBuf<unsigned char> tmp;
 
   // 1. cells in the Morton order of their centroids, dealt into execution order
   DevBuf<int32_t> sorted_cells;
@@ -1458,9 +1430,10 @@ int plan_attempt(zzz_ctx* ctx, int nc, int T, int nloc_limit, bool* retry)
     ZZZ_HIP(ctx, k1.alloc((size_t)ncells));
     ZZZ_HIP(ctx, v0.alloc((size_t)ncells));
     ZZZ_HIP(ctx, sorted_cells.alloc((size_t)ncells));
-    hipLaunchKernelGGL(k_mf_cell_keys, dim3(grid_for(ncells)), dim3(256), 0, s, ctx->x.p, ctx->cell_verts.p, ncells, B, k0.p, v0.p);
-    if (int rc = sort_pairs(ctx, k0, k1, v0, sorted_cells, (size_t)ncells, 30))
+    hipLaunchKernelGGL(k_mf_cell_keys, dim3(grid_cap(ncells, 256, 8192)), dim3(256), 0, s, ctx->x.p, ctx->cell_verts.p, ncells, B, k0.p, v0.p);
+    if (int rc = with_scratch(ctx, tmp, sort_pairs(k0.p, k1.p, v0.p, sorted_cells.p, (size_t)ncells, 0u, 30u, s)))
       return rc;
+    ZZZ_HIP(ctx, hipStreamSynchronize(s));
   }
   ZZZ_HIP(ctx, M.mf_cell.alloc((size_t)total));
   {
@@ -1493,29 +1466,29 @@ int plan_attempt(zzz_ctx* ctx, int nc, int T, int nloc_limit, bool* retry)
     ZZZ_HIP(ctx, val0.alloc((size_t)np));
     ZZZ_HIP(ctx, key.alloc((size_t)np));
     ZZZ_HIP(ctx, val.alloc((size_t)np));
-    hipLaunchKernelGGL(k_mf_pairs, dim3(grid_for(np)), dim3(256), 0, s, M.mf_cell.p, ctx->cell_dofs.p, nd, nc, total, key0.p, val0.p);
+    hipLaunchKernelGGL(k_mf_pairs, dim3(grid_cap(np, 256, 8192)), dim3(256), 0, s, M.mf_cell.p, ctx->cell_dofs.p, nd, nc, total, key0.p, val0.p);
     auto begin = rocprim::make_transform_iterator(rocprim::counting_iterator<unsigned>(0), SegOffset{(unsigned)seg});
     auto end = rocprim::make_transform_iterator(rocprim::counting_iterator<unsigned>(1), SegOffset{(unsigned)seg});
     // (one bit above the dofs': the key of a missing cell stays behind every dof)
     const unsigned end_bit = std::min(32u, bits_for((uint64_t)(ctx->n_owned + ctx->n_ghost)) + 1u);
-    size_t tb = 0;
-    ZZZ_HIP(ctx, rocprim::segmented_radix_sort_pairs(nullptr, tb, key0.p, key.p, val0.p, val.p, (unsigned)np, (unsigned)nb, begin, end,
-                                                     0u, end_bit, s));
-    DevBuf<unsigned char> tmp;
-    ZZZ_HIP(ctx, tmp.alloc(tb));
-    ZZZ_HIP(ctx, rocprim::segmented_radix_sort_pairs(tmp.p, tb, key0.p, key.p, val0.p, val.p, (unsigned)np, (unsigned)nb, begin, end,
-                                                     0u, end_bit, s));
+    DevBuf<unsigned char> seg_tmp;
+    if (int rc = with_scratch(ctx, seg_tmp, [&](void* t, size_t& bytes) {
+          return rocprim::segmented_radix_sort_pairs(t, bytes, key0.p, key.p, val0.p, val.p, (unsigned)np, (unsigned)nb, begin, end, 0u,
+                                                     end_bit, s);
+        }))
+      return rc;
     ZZZ_HIP(ctx, hipStreamSynchronize(s));
   }
   DevBuf<int32_t> flag, uidx;
   ZZZ_HIP(ctx, flag.alloc((size_t)np + 1));
   ZZZ_HIP(ctx, uidx.alloc((size_t)np + 1));
-  hipLaunchKernelGGL(k_mf_heads, dim3(grid_for(np)), dim3(256), 0, s, key.p, np, seg, flag.p);
+  hipLaunchKernelGGL(k_mf_heads, dim3(grid_cap(np, 256, 8192)), dim3(256), 0, s, key.p, np, seg, flag.p);
   ZZZ_HIP(ctx, hipMemsetAsync(flag.p + np, 0, sizeof(int32_t), s));
-  if (int rc = scan_excl(ctx, flag.p, uidx.p, (size_t)np + 1))
+  // (the scans of this plan read through pointers to const: the instantiation they have always had)
+  if (int rc = with_scratch(ctx, tmp, scan_excl((const int32_t*)flag.p, uidx.p, (size_t)np + 1, s)))
     return rc;
   int32_t nu32 = 0;
-  ZZZ_HIP(ctx, hipMemcpy(&nu32, uidx.p + np, sizeof(int32_t), hipMemcpyDeviceToHost));
+  ZZZ_HIP(ctx, dev_fetch(ctx, uidx.p + np, &nu32));
   const int64_t nu = nu32;
   const int64_t nloc_all = ctx->n_owned + ctx->n_ghost;
   DevBuf<uint64_t> ukey;
@@ -1524,7 +1497,7 @@ int plan_attempt(zzz_ctx* ctx, int nc, int T, int nloc_limit, bool* retry)
   ZZZ_HIP(ctx, run_start.alloc((size_t)nu + 1));
   ZZZ_HIP(ctx, nblk_of.alloc((size_t)nloc_all));
   ZZZ_HIP(ctx, hipMemsetAsync(nblk_of.p, 0, (size_t)nloc_all * sizeof(int32_t), s));
-  hipLaunchKernelGGL(k_mf_uniques, dim3(grid_for(np)), dim3(256), 0, s, key.p, flag.p, uidx.p, np, seg, ukey.p, run_start.p, nblk_of.p);
+  hipLaunchKernelGGL(k_mf_uniques, dim3(grid_cap(np, 256, 8192)), dim3(256), 0, s, key.p, flag.p, uidx.p, np, seg, ukey.p, run_start.p, nblk_of.p);
 
   // 3. classes, block-local order, headers
   DevBuf<uint64_t> key2, key2s;
@@ -1541,14 +1514,16 @@ int plan_attempt(zzz_ctx* ctx, int nc, int T, int nloc_limit, bool* retry)
   ZZZ_HIP(ctx, nlmax.alloc(2));
   ZZZ_HIP(ctx, hipMemsetAsync(cnt3.p, 0, (size_t)nb * 3 * sizeof(int32_t), s));
   ZZZ_HIP(ctx, hipMemsetAsync(nlmax.p, 0, 2 * sizeof(int32_t), s));
-  hipLaunchKernelGGL(k_mf_classify, dim3(grid_for(nu)), dim3(256), 0, s, ukey.p, nu, nblk_of.p, ctx->n_owned, key2.p, val2.p, cnt3.p);
-  hipLaunchKernelGGL(k_mf_block_sizes, dim3(grid_for(nb + 1)), dim3(256), 0, s, cnt3.p, nb, nloc_b.p, nsh_b.p);
-  if (int rc = scan_excl(ctx, nloc_b.p, dof_off.p, (size_t)nb + 1))
+  hipLaunchKernelGGL(k_mf_classify, dim3(grid_cap(nu, 256, 8192)), dim3(256), 0, s, ukey.p, nu, nblk_of.p, ctx->n_owned, key2.p, val2.p, cnt3.p);
+  hipLaunchKernelGGL(k_mf_block_sizes, dim3(grid_cap(nb + 1, 256, 8192)), dim3(256), 0, s, cnt3.p, nb, nloc_b.p, nsh_b.p);
+  if (int rc = with_scratch(ctx, tmp, scan_excl((const int32_t*)nloc_b.p, dof_off.p, (size_t)nb + 1, s)))
     return rc;
-  if (int rc = scan_excl(ctx, nsh_b.p, part_off.p, (size_t)nb + 1))
+  ZZZ_HIP(ctx, hipStreamSynchronize(s));
+  if (int rc = with_scratch(ctx, tmp, scan_excl((const int32_t*)nsh_b.p, part_off.p, (size_t)nb + 1, s)))
     return rc;
+  ZZZ_HIP(ctx, hipStreamSynchronize(s));
   ZZZ_HIP(ctx, M.hdr.alloc((size_t)nb * MF_HDR));
-  hipLaunchKernelGGL(k_mf_headers, dim3(grid_for(nb)), dim3(256), 0, s, cnt3.p, dof_off.p, part_off.p, nb, M.hdr.p, nlmax.p);
+  hipLaunchKernelGGL(k_mf_headers, dim3(grid_cap(nb, 256, 8192)), dim3(256), 0, s, cnt3.p, dof_off.p, part_off.p, nb, M.hdr.p, nlmax.p);
   int32_t h_nlmax = 0, h_nslots = 0;
   ZZZ_HIP(ctx, hipMemcpyAsync(&h_nlmax, nlmax.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
   ZZZ_HIP(ctx, hipMemcpyAsync(&h_nslots, part_off.p + nb, sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -1560,8 +1535,9 @@ int plan_attempt(zzz_ctx* ctx, int nc, int T, int nloc_limit, bool* retry)
   }
   M.nloc_max = h_nlmax;
   M.nslots = h_nslots;
-  if (int rc = sort_pairs(ctx, key2, key2s, val2, val2s, (size_t)nu, 34 + bits_for((uint64_t)nb)))
+  if (int rc = with_scratch(ctx, tmp, sort_pairs(key2.p, key2s.p, val2.p, val2s.p, (size_t)nu, 0u, 34 + bits_for((uint64_t)nb), s)))
     return rc;
+  ZZZ_HIP(ctx, hipStreamSynchronize(s));
   DevBuf<int32_t> loc_of, sh_val, sh_val_s;
   DevBuf<uint32_t> sh_key, sh_key_s;
   ZZZ_HIP(ctx, M.dof_ids.alloc((size_t)nu));
@@ -1573,7 +1549,7 @@ int plan_attempt(zzz_ctx* ctx, int nc, int T, int nloc_limit, bool* retry)
   ZZZ_HIP(ctx, sh_key_s.alloc((size_t)nu));
   ZZZ_HIP(ctx, sh_val.alloc((size_t)nu));
   ZZZ_HIP(ctx, sh_val_s.alloc((size_t)nu));
-  hipLaunchKernelGGL(k_mf_lists, dim3(grid_for(nu)), dim3(256), 0, s, key2s.p, val2s.p, nu, M.hdr.p, ctx->bc.p, ctx->bs,
+  hipLaunchKernelGGL(k_mf_lists, dim3(grid_cap(nu, 256, 8192)), dim3(256), 0, s, key2s.p, val2s.p, nu, M.hdr.p, ctx->bc.p, ctx->bs,
                      nd == 4 ? ctx->xq : (const double*)nullptr, M.dof_ids.p, M.dof_flag.p, nd == 4 ? M.xyz.p : (double*)nullptr,
                      loc_of.p, sh_key.p, sh_val.p);
 
@@ -1592,32 +1568,32 @@ int plan_attempt(zzz_ctx* ctx, int nc, int T, int nloc_limit, bool* retry)
   hipLaunchKernelGGL(k_mf_rmax, dim3((unsigned)std::min<int64_t>((nb * nsb * M.nrw + 3) / 4, 8192)), dim3(256), 0, s, M.rnkw.p, nb, nc,
                      T, nsb, M.nrw, M.rmax.p);
   int32_t h_err = 0;
-  ZZZ_HIP(ctx, hipMemcpyAsync(&h_err, nlmax.p + 1, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  ZZZ_HIP(ctx, hipStreamSynchronize(s));
+  ZZZ_HIP(ctx, dev_fetch(ctx, nlmax.p + 1, &h_err));
   if (h_err)
     return fail(ctx, ZZZ_ERR_LIMIT, "matrix-free plan: a dof meets more than 254 cells of one step");
 
   // 5. the shared dofs and their slots
-  if (int rc = sort_pairs(ctx, sh_key, sh_key_s, sh_val, sh_val_s, (size_t)nu, 32))
+  if (int rc = with_scratch(ctx, tmp, sort_pairs(sh_key.p, sh_key_s.p, sh_val.p, sh_val_s.p, (size_t)nu, 0u, 32u, s)))
     return rc;
+  ZZZ_HIP(ctx, hipStreamSynchronize(s));
   M.nshared = 0;
   if (M.nslots > 0)
   {
     DevBuf<int32_t> f2, u2;
     ZZZ_HIP(ctx, f2.alloc((size_t)M.nslots + 1));
     ZZZ_HIP(ctx, u2.alloc((size_t)M.nslots + 1));
-    hipLaunchKernelGGL(k_mf_sh_heads, dim3(grid_for(M.nslots)), dim3(256), 0, s, sh_key_s.p, M.nslots, f2.p);
+    hipLaunchKernelGGL(k_mf_sh_heads, dim3(grid_cap(M.nslots, 256, 8192)), dim3(256), 0, s, sh_key_s.p, M.nslots, f2.p);
     ZZZ_HIP(ctx, hipMemsetAsync(f2.p + M.nslots, 0, sizeof(int32_t), s));
-    if (int rc = scan_excl(ctx, f2.p, u2.p, (size_t)M.nslots + 1))
+    if (int rc = with_scratch(ctx, tmp, scan_excl((const int32_t*)f2.p, u2.p, (size_t)M.nslots + 1, s)))
       return rc;
     int32_t ns = 0;
-    ZZZ_HIP(ctx, hipMemcpy(&ns, u2.p + M.nslots, sizeof(int32_t), hipMemcpyDeviceToHost));
+    ZZZ_HIP(ctx, dev_fetch(ctx, u2.p + M.nslots, &ns));
     M.nshared = ns;
     ZZZ_HIP(ctx, M.sh_dof.alloc((size_t)ns));
     ZZZ_HIP(ctx, M.sh_off.alloc((size_t)ns + 1));
     ZZZ_HIP(ctx, M.sh_slot.alloc((size_t)M.nslots));
     ZZZ_HIP(ctx, M.sh_flag.alloc((size_t)ns));
-    hipLaunchKernelGGL(k_mf_sh_fill, dim3(grid_for(M.nslots + 1)), dim3(256), 0, s, sh_key_s.p, sh_val_s.p, f2.p, u2.p, M.nslots,
+    hipLaunchKernelGGL(k_mf_sh_fill, dim3(grid_cap(M.nslots + 1, 256, 8192)), dim3(256), 0, s, sh_key_s.p, sh_val_s.p, f2.p, u2.p, M.nslots,
                        ctx->bc.p, ctx->bs, M.sh_dof.p, M.sh_off.p, M.sh_flag.p, M.sh_slot.p, (int64_t)ns);
     ZZZ_HIP(ctx, hipStreamSynchronize(s));
   }
@@ -1633,13 +1609,13 @@ int plan_attempt(zzz_ctx* ctx, int nc, int T, int nloc_limit, bool* retry)
     if (nd == 20)
     {
       ZZZ_HIP(ctx, M.gid.alloc((size_t)(total * nd)));
-      hipLaunchKernelGGL(k_mf_gid, dim3(grid_for(total * nd)), dim3(256), 0, s, M.mf_cell.p, ctx->cell_dofs.p, nd, nc, total, M.gid.p);
+      hipLaunchKernelGGL(k_mf_gid, dim3(grid_cap(total * nd, 256, 8192)), dim3(256), 0, s, M.mf_cell.p, ctx->cell_dofs.p, nd, nc, total, M.gid.p);
     }
     ZZZ_HIP(ctx, M.geom.alloc((size_t)(nb * (ctx->bs == 3 ? 10 : 6) * nc)));
     if (ctx->bs == 3)
-      hipLaunchKernelGGL(k_mf_geom_el, dim3(grid_for(total)), dim3(256), 0, s, ctx->x.p, ctx->cell_verts.p, M.mf_cell.p, nc, total, M.geom.p);
+      hipLaunchKernelGGL(k_mf_geom_el, dim3(grid_cap(total, 256, 8192)), dim3(256), 0, s, ctx->x.p, ctx->cell_verts.p, M.mf_cell.p, nc, total, M.geom.p);
     else
-      hipLaunchKernelGGL(k_mf_geom, dim3(grid_for(total)), dim3(256), 0, s, ctx->x.p, ctx->cell_verts.p, M.mf_cell.p, nc, total, M.geom.p);
+      hipLaunchKernelGGL(k_mf_geom, dim3(grid_cap(total, 256, 8192)), dim3(256), 0, s, ctx->x.p, ctx->cell_verts.p, M.mf_cell.p, nc, total, M.geom.p);
   }
   ZZZ_HIP(ctx, hipGetLastError());
   ZZZ_HIP(ctx, hipStreamSynchronize(s));
@@ -1944,7 +1920,7 @@ static int mf_f32_build(zzz_ctx* ctx)
     const int64_t ng = M.nblocks * 6 * M.nc, nt = M.nd == 10 ? 120 : 600;
     ZZZ_HIP(ctx, M.geom32.alloc((size_t)ng));
     ZZZ_HIP(ctx, M.dtab32.alloc((size_t)nt));
-    hipLaunchKernelGGL(k_mf32_round, dim3(grid_for(ng)), dim3(256), 0, s, M.geom.p, ng, M.geom32.p);
+    hipLaunchKernelGGL(k_mf32_round, dim3(grid_cap(ng, 256, 8192)), dim3(256), 0, s, M.geom.p, ng, M.geom32.p);
     hipLaunchKernelGGL(k_mf32_round, dim3(1), dim3(256), 0, s, M.dtab.p, nt, M.dtab32.p);
   }
   ZZZ_HIP(ctx, M.ypart32.alloc((size_t)std::max<int64_t>(M.nslots, 1)));
@@ -2167,10 +2143,10 @@ int mf_assemble_vector(zzz_ctx* ctx)
   if (ctx->have_bc_val)
   {
     const int64_t nall = ctx->nloc(), nrows = ctx->n_owned * ctx->bs;
-    hipLaunchKernelGGL(k_mf_lift_src, dim3(grid_for(nall)), dim3(256), 0, ctx->stream, ctx->bc.p, ctx->bc_val.p, nall, ctx->p.p);
+    hipLaunchKernelGGL(k_mf_lift_src, dim3(grid_cap(nall, 256, 8192)), dim3(256), 0, ctx->stream, ctx->bc.p, ctx->bc_val.p, nall, ctx->p.p);
     if (int rc2 = mf_action(ctx, ctx->p.p, ctx->w.p, nullptr, nullptr))
       return rc2;
-    hipLaunchKernelGGL(k_mf_lift_apply, dim3(grid_for(nrows)), dim3(256), 0, ctx->stream, ctx->bc.p, ctx->bc_val.p, ctx->w.p, nrows,
+    hipLaunchKernelGGL(k_mf_lift_apply, dim3(grid_cap(nrows, 256, 8192)), dim3(256), 0, ctx->stream, ctx->bc.p, ctx->bc_val.p, ctx->w.p, nrows,
                        ctx->b.p);
     ZZZ_HIP(ctx, hipGetLastError());
   }

@@ -15,9 +15,7 @@
 #include <cstring>
 
 #include "zzz_device.h"
-#include "zzz_internal.h"
-
-#include <rocprim/rocprim.hpp>
+#include "zzz_prim.h"
 
 #include <climits>
 #include <cstdlib>
@@ -695,16 +693,6 @@ __global__ void k_asm_tiles(const rp_t* __restrict__ rowptr, int nb, int bs, int
     tiles[t] = (t == ntiles) ? nb : lower_bound_rows(rowptr, bs, nb, t * W);
 }
 
-static int grid_for(int64_t n, int block = 256, int cap = 4096)
-{
-  int64_t g = (n + block - 1) / block;
-  if (g > cap)
-    g = cap;
-  if (g < 1)
-    g = 1;
-  return (int)g;
-}
-
 // packed column stream of the SpMV tiles; the offset width is the first of four candidates (10..13 bits)
 // that leaves no tile on int32 columns, else the one that leaves the fewest.  Encoded when the CSR tile kernel is
 // first used on this pattern (matrices that run on the operator stream of zzz_sellp.hip never need it).
@@ -731,12 +719,11 @@ int ensure_cols16(zzz_ctx* ctx)
   int32_t best_fb = INT32_MAX;
   auto run = [&](int offb, int32_t* nfb) -> int {
     ZZZ_HIP(ctx, hipMemsetAsync(ctx->scr_c16.p, 0, sizeof(int32_t), s));
-    const int g = grid_for(ctx->ntiles, 1, 256 * 8);
+    const int g = grid_cap(ctx->ntiles, 1, 256 * 8);
     hipLaunchKernelGGL(k_tile_encode_cols, dim3(g), dim3(256), 0, s, reinterpret_cast<int4*>(ctx->tile_row.p), ctx->ntiles,
                        ctx->cols.p, offb, ctx->cols16.p, ctx->tile_base.p, ctx->scr_c16.p);
     ZZZ_HIP(ctx, hipGetLastError());
-    ZZZ_HIP(ctx, hipMemcpyAsync(nfb, ctx->scr_c16.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    ZZZ_HIP(ctx, hipStreamSynchronize(s));
+    ZZZ_HIP(ctx, dev_fetch(ctx, ctx->scr_c16.p, nfb));
     return ZZZ_OK;
   };
   int last = -1;
@@ -797,9 +784,9 @@ int build_tiles_device(zzz_ctx* ctx, int max_block_cols)
   ZZZ_HIP(ctx, ctx->tile_row.alloc((size_t)ctx->ntiles * 4 + 4));
   ZZZ_HIP(ctx, ctx->asm_tile.alloc((size_t)ctx->n_asm_tiles + 1));
   if (ctx->ntiles)
-    hipLaunchKernelGGL(k_spmv_tiles, dim3(grid_for(ctx->ntiles)), dim3(256), 0, s, ctx->rowptr.p, (int)ctx->nrows, Ws,
+    hipLaunchKernelGGL(k_spmv_tiles, dim3(grid_cap(ctx->ntiles, 256, 4096)), dim3(256), 0, s, ctx->rowptr.p, (int)ctx->nrows, Ws,
                        ctx->ntiles, reinterpret_cast<int4*>(ctx->tile_row.p));
-  hipLaunchKernelGGL(k_asm_tiles, dim3(grid_for(ctx->n_asm_tiles + 1)), dim3(256), 0, s, ctx->rowptr.p,
+  hipLaunchKernelGGL(k_asm_tiles, dim3(grid_cap(ctx->n_asm_tiles + 1, 256, 4096)), dim3(256), 0, s, ctx->rowptr.p,
                      (int)ctx->n_owned, bs, Wa, ctx->n_asm_tiles, ctx->asm_tile.p);
   ZZZ_HIP(ctx, hipGetLastError());
   int rc = build_tile_split(ctx);
@@ -1047,7 +1034,7 @@ static void adjacency_find_runs(zzz_ctx* ctx)
     return;
   }
   if (nc > 1)
-    hipLaunchKernelGGL(k_run_breaks, dim3(grid_for((nc - 1) * nd)), dim3(256), 0, s, ctx->cell_dofs.p, nc, nd, ADJ_BREAK_CAP,
+    hipLaunchKernelGGL(k_run_breaks, dim3(grid_cap((nc - 1) * nd, 256, 4096)), dim3(256), 0, s, ctx->cell_dofs.p, nc, nd, ADJ_BREAK_CAP,
                        nbr.p, brk.p);
   int32_t n = 0;
   if (hipMemcpyAsync(&n, nbr.p, sizeof(n), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
@@ -1099,9 +1086,9 @@ static int adjacency_by_runs(zzz_ctx* ctx)
     ZZZ_HIP(ctx, hipHostMalloc((void**)&ctx->adj_flag_host, sizeof(int32_t), hipHostMallocDefault));
   int32_t* flag = ctx->adj_win_base.p + nwin + 1;
   ZZZ_HIP(ctx, hipMemsetAsync(flag, 0, sizeof(int32_t), s));
-  hipLaunchKernelGGL(k_run_window_bounds, dim3(grid_for((int64_t)nruns * (nwin + 1), 256, 16384)), dim3(256), 0, s,
+  hipLaunchKernelGGL(k_run_window_bounds, dim3(grid_cap((int64_t)nruns * (nwin + 1), 256, 16384)), dim3(256), 0, s,
                      ctx->cell_dofs.p, nd, ctx->adj_runs.p, nruns, nwin, ctx->adj_run_lo.p);
-  hipLaunchKernelGGL(k_window_tot, dim3(grid_for(nwin)), dim3(256), 0, s, ctx->adj_run_lo.p, nruns, nwin, ctx->adj_win_base.p);
+  hipLaunchKernelGGL(k_window_tot, dim3(grid_cap(nwin, 256, 4096)), dim3(256), 0, s, ctx->adj_run_lo.p, nruns, nwin, ctx->adj_win_base.p);
   hipLaunchKernelGGL(k_window_base, dim3(1), dim3(1024), 0, s, nwin, ctx->adj_win_base.p, flag);
   hipLaunchKernelGGL(k_adj_window, dim3(nwin), dim3(ADJ_W), 0, s, ctx->cell_dofs.p, nd, ctx->adj_runs.p, nruns, ctx->adj_run_lo.p,
                      nwin, ctx->adj_win_base.p, nb, ctx->adj_off.p, ctx->adj_cells.p);
@@ -1123,6 +1110,16 @@ static bool stage_fits(const zzz_ctx* ctx, int64_t nstage)
     return nstage < ((int64_t)3 << 30);
   }
   return nstage < ((int64_t)3 << 30) || (double)nstage * 4.0 < 0.25 * (double)fr;
+}
+
+// The build's sort of the (dof, cell) incidences by dof, on the buffers pattern_reserve and pattern_build_device share: a
+// primitive for with_scratch (zzz_prim.h)
+static auto adjacency_sort(zzz_ctx* ctx, int64_t N, int end_bit)
+{
+  return [=](void* tmp, size_t& bytes) {
+    return rocprim::radix_sort_pairs<AdjSortConfig>(tmp, bytes, ctx->cell_dofs.p, ctx->scr_keys_out.p, ctx->scr_vals_in.p,
+                                                    ctx->adj_cells.p, (size_t)N, 0, (unsigned)end_bit, ctx->stream);
+  };
 }
 
 // Scratch of the pattern build whose size follows from the dofmap alone (sort buffers, the entry -> cell map, the
@@ -1147,21 +1144,18 @@ void pattern_reserve(zzz_ctx* ctx)
   }
   if (ctx->scr_cell_of_n != N || ctx->scr_cell_of_nd != nd)
   {
-    hipLaunchKernelGGL(k_cell_of, dim3(grid_for(N)), dim3(256), 0, s, N, nd, ctx->scr_vals_in.p);
+    hipLaunchKernelGGL(k_cell_of, dim3(grid_cap(N, 256, 4096)), dim3(256), 0, s, N, nd, ctx->scr_vals_in.p);
     ctx->scr_cell_of_n = N;
     ctx->scr_cell_of_nd = nd;
   }
   int end_bit = 1;
   while ((1ll << end_bit) <= (long long)(ctx->n_owned + ctx->n_ghost))
     ++end_bit;
+  // the shared scratch at the larger of the build's sort and scan, which then find it there
   size_t tb = 0, tb2 = 0;
-  if (rocprim::radix_sort_pairs<AdjSortConfig>(nullptr, tb, ctx->cell_dofs.p, ctx->scr_keys_out.p, ctx->scr_vals_in.p,
-                                               ctx->adj_cells.p, (size_t)N, 0, (unsigned)end_bit, s)
-          == hipSuccess
-      && rocprim::exclusive_scan(nullptr, tb2, ctx->scr_cnt.p, ctx->scr_bptr.p, (int64_t)0, (size_t)nb + 1,
-                                 rocprim::plus<int64_t>(), s)
-             == hipSuccess)
-    (void)ctx->scr_tmp.alloc(tb > tb2 ? tb : tb2);
+  if (scratch_bytes(adjacency_sort(ctx, N, end_bit), &tb) == hipSuccess
+      && scratch_bytes(scan_excl(ctx->scr_cnt.p, ctx->scr_bptr.p, (size_t)nb + 1, s), &tb2) == hipSuccess)
+    (void)scratch_reserve(ctx, tb > tb2 ? tb : tb2);
   const int64_t nstage = N * nd;
   if (stage_fits(ctx, nstage))
     (void)ctx->scr_stage.alloc((size_t)nstage);
@@ -1185,7 +1179,6 @@ int pattern_build_device(zzz_ctx* ctx, bool* fallback)
 
   DevBuf<int32_t>&keys_out = ctx->scr_keys_out, &cnt = ctx->scr_cnt;
   DevBuf<int64_t>& bptr = ctx->scr_bptr;
-  DevBuf<unsigned char>& tmp = ctx->scr_tmp;
   DevBuf<int32_t> scal;
   ZZZ_HIP(ctx, keys_out.alloc((size_t)N));
   ZZZ_HIP(ctx, ctx->adj_cells.alloc((size_t)N));
@@ -1206,15 +1199,10 @@ int pattern_build_device(zzz_ctx* ctx, bool* fallback)
   if (ctx->scr_cell_of_n != N || ctx->scr_cell_of_nd != nd)
   {
     ZZZ_HIP(ctx, cell_of.alloc((size_t)N));
-    hipLaunchKernelGGL(k_cell_of, dim3(grid_for(N)), dim3(256), 0, s, N, nd, cell_of.p);
+    hipLaunchKernelGGL(k_cell_of, dim3(grid_cap(N, 256, 4096)), dim3(256), 0, s, N, nd, cell_of.p);
     ctx->scr_cell_of_n = N;
     ctx->scr_cell_of_nd = nd;
   }
-  size_t tb = 0, tb2 = 0;
-  ZZZ_HIP(ctx, rocprim::radix_sort_pairs<AdjSortConfig>(nullptr, tb, ctx->cell_dofs.p, keys_out.p, cell_of.p, ctx->adj_cells.p, (size_t)N, 0,
-                                         (unsigned)end_bit, s));
-  ZZZ_HIP(ctx, rocprim::exclusive_scan(nullptr, tb2, cnt.p, bptr.p, (int64_t)0, (size_t)nb + 1, rocprim::plus<int64_t>(), s));
-  ZZZ_HIP(ctx, tmp.alloc(tb > tb2 ? tb : tb2));
   if (ctx->adj_runs_n < 0)
     adjacency_find_runs(ctx);
   const bool by_runs = ctx->adj_runs_n > 0;
@@ -1225,13 +1213,13 @@ int pattern_build_device(zzz_ctx* ctx, bool* fallback)
   }
   else
   {
-    ZZZ_HIP(ctx, rocprim::radix_sort_pairs<AdjSortConfig>(tmp.p, tb, ctx->cell_dofs.p, keys_out.p, cell_of.p, ctx->adj_cells.p, (size_t)N,
-                                           0, (unsigned)end_bit, s));
-    hipLaunchKernelGGL(k_adj_bounds, dim3(grid_for((N + 4) / 4)), dim3(256), 0, s, keys_out.p, N, nb, ctx->adj_off.p);
+    if (int rc = with_scratch(ctx, adjacency_sort(ctx, N, end_bit))) // (into keys_out, from cell_of)
+      return rc;
+    hipLaunchKernelGGL(k_adj_bounds, dim3(grid_cap((N + 4) / 4, 256, 4096)), dim3(256), 0, s, keys_out.p, N, nb, ctx->adj_off.p);
   }
 
   // 2. pattern: count, scan, fill
-  const int rgrid = grid_for((int64_t)nb, 4, 256 * 16);
+  const int rgrid = grid_cap((int64_t)nb, 4, 256 * 16);
   // staging area for the sorted unique columns (upper bound: every candidate distinct); skipped when
   // it would not fit comfortably -- then the fill pass sorts again
   const int64_t nstage = N * nd;
@@ -1250,7 +1238,7 @@ int pattern_build_device(zzz_ctx* ctx, bool* fallback)
       return rc;
     // 8 workgroups per CU = 4 wavefronts per SIMD, what the kernel's 108 registers allow (a cap of 4 left half of that
     // occupancy unused: 2.98 -> ~2.0 ms)
-    const dim3 tg((grid_for((int64_t)nb, ROW_T_BLOCK, 256 * 8) + 7) / 8 * 8);
+    const dim3 tg((grid_cap((int64_t)nb, ROW_T_BLOCK, 256 * 8) + 7) / 8 * 8);
     // rows of up to 16 unique columns first (the sorted list in 16 registers), then up to 32
     for (int cap = 16; cap <= 32; cap *= 2)
     {
@@ -1301,10 +1289,10 @@ int pattern_build_device(zzz_ctx* ctx, bool* fallback)
     *fallback = true;
     return fail(ctx, ZZZ_ERR_LIMIT, "a row gathers %d candidate columns (device limit %d)", h[1], PAT_CAP);
   }
-  ZZZ_HIP(ctx, rocprim::exclusive_scan(tmp.p, tb2, cnt.p, bptr.p, (int64_t)0, (size_t)nb + 1, rocprim::plus<int64_t>(), s));
+  if (int rc = with_scratch(ctx, scan_excl(cnt.p, bptr.p, (size_t)nb + 1, s)))
+    return rc;
   int64_t nblk = 0;
-  ZZZ_HIP(ctx, hipMemcpyAsync(&nblk, bptr.p + nb, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  ZZZ_HIP(ctx, hipStreamSynchronize(s));
+  ZZZ_HIP(ctx, dev_fetch(ctx, bptr.p + nb, &nblk));
   const int64_t nnz = nblk * bs * bs;
   if (nblk < 0 || nnz > ((int64_t)1 << 40))
     return fail(ctx, ZZZ_ERR_LIMIT, "%lld nonzeros: use more parts", (long long)nnz);
@@ -1316,10 +1304,10 @@ int pattern_build_device(zzz_ctx* ctx, bool* fallback)
   ZZZ_HIP(ctx, ctx->vals.alloc((size_t)nnz + 8));
   ZZZ_HIP(ctx, hipMemsetAsync(ctx->cols.p + nnz, 0, 8 * sizeof(int32_t), s));
   ZZZ_HIP(ctx, hipMemsetAsync(ctx->vals.p + nnz, 0, 8 * sizeof(double), s)); // the assembly writes every entry itself
-  hipLaunchKernelGGL(k_scalar_rowptr, dim3(grid_for((int64_t)nb + 1)), dim3(256), 0, s, bptr.p, cnt.p, nb, bs,
+  hipLaunchKernelGGL(k_scalar_rowptr, dim3(grid_cap((int64_t)nb + 1, 256, 4096)), dim3(256), 0, s, bptr.p, cnt.p, nb, bs,
                      ctx->rowptr.p);
   if (stage)
-    hipLaunchKernelGGL(k_row_copy, dim3(grid_for((int64_t)nb * 16, 256, 8192)), dim3(256), 0, s, stage, ctx->adj_off.p, nd, bs,
+    hipLaunchKernelGGL(k_row_copy, dim3(grid_cap((int64_t)nb * 16, 256, 8192)), dim3(256), 0, s, stage, ctx->adj_off.p, nd, bs,
                        nb, cnt.p, bptr.p, ctx->cols.p);
   else
     hipLaunchKernelGGL(k_row_pattern<true>, dim3(rgrid), dim3(256), 0, s, ctx->cell_dofs.p, nd, bs, ctx->adj_off.p,
@@ -1360,7 +1348,7 @@ int build_tile_split(zzz_ctx* ctx)
     return ZZZ_OK;
   DevBuf<uint8_t> flag;
   ZZZ_HIP(ctx, flag.alloc((size_t)ctx->ntiles));
-  hipLaunchKernelGGL(k_tile_ghost_flag, dim3(grid_for(ctx->ntiles, 4, 4096)), dim3(256), 0, ctx->stream,
+  hipLaunchKernelGGL(k_tile_ghost_flag, dim3(grid_cap(ctx->ntiles, 4, 4096)), dim3(256), 0, ctx->stream,
                      reinterpret_cast<const int4*>(ctx->tile_row.p), ctx->ntiles, ctx->cols.p, (int32_t)ctx->nrows, flag.p);
   std::vector<uint8_t> h((size_t)ctx->ntiles);
   ZZZ_HIP(ctx, hipMemcpyAsync(h.data(), flag.p, h.size(), hipMemcpyDeviceToHost, ctx->stream));

@@ -22,9 +22,7 @@
 // the coordinate-bin order.  Set-up work ("ZZZ FunctionSpace" of the reference), not part of any ZZZ Assemble/Solve timer.
 #include <cstring>
 
-#include "zzz_internal.h"
-
-#include <rocprim/rocprim.hpp>
+#include "zzz_prim.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -293,7 +291,6 @@ __global__ void k_translate(int32_t* __restrict__ cell_dofs, int64_t n, const in
   }
 }
 
-int grid_of(int64_t n) { return (int)std::min<int64_t>((n + 255) / 256, 16384); }
 } // namespace
 
 static int renumber_cells(zzz_ctx* ctx, const Lattice& L);
@@ -347,23 +344,23 @@ int renumber_build(zzz_ctx* ctx)
   ZZZ_HIP(ctx, sorted.alloc((size_t)nv));
   ZZZ_HIP(ctx, head.alloc((size_t)nv));
   ZZZ_HIP(ctx, pos.alloc((size_t)nv));
-  size_t tb_sort = 0, tb_scan = 0;
-  ZZZ_HIP(ctx, rocprim::radix_sort_keys(nullptr, tb_sort, col.p, sorted.p, (size_t)nv, 0, 64, s));
-  ZZZ_HIP(ctx, rocprim::exclusive_scan(nullptr, tb_scan, head.p, pos.p, (int32_t)0, (size_t)nv, rocprim::plus<int32_t>(), s));
-  ZZZ_HIP(ctx, tmp.alloc(std::max(tb_sort, tb_scan)));
   Lattice L{};
   bool lattice = true;
   double lo[3], hi[3];
   for (int a = 0; a < 3; ++a)
   {
-    hipLaunchKernelGGL(k_axis, dim3(grid_of(nv)), dim3(256), 0, s, ctx->x.p, nv, a, col.p);
-    ZZZ_HIP(ctx, rocprim::radix_sort_keys(tmp.p, tb_sort, col.p, sorted.p, (size_t)nv, 0, 64, s));
+    hipLaunchKernelGGL(k_axis, dim3(grid_cap(nv, 256, 16384)), dim3(256), 0, s, ctx->x.p, nv, a, col.p);
+    if (int rc = with_scratch(ctx, tmp, [&](void* t, size_t& bytes) {
+          return rocprim::radix_sort_keys(t, bytes, col.p, sorted.p, (size_t)nv, 0, 64, s);
+        }))
+      return rc;
     ZZZ_HIP(ctx, hipMemcpyAsync(&lo[a], sorted.p, sizeof(double), hipMemcpyDeviceToHost, s));
     ZZZ_HIP(ctx, hipMemcpyAsync(&hi[a], sorted.p + nv - 1, sizeof(double), hipMemcpyDeviceToHost, s));
     ZZZ_HIP(ctx, hipStreamSynchronize(s));
     const double tol = 1e-9 * std::max(hi[a] - lo[a], 1e-300);
-    hipLaunchKernelGGL(k_heads, dim3(grid_of(nv)), dim3(256), 0, s, sorted.p, nv, tol, head.p);
-    ZZZ_HIP(ctx, rocprim::exclusive_scan(tmp.p, tb_scan, head.p, pos.p, (int32_t)0, (size_t)nv, rocprim::plus<int32_t>(), s));
+    hipLaunchKernelGGL(k_heads, dim3(grid_cap(nv, 256, 16384)), dim3(256), 0, s, sorted.p, nv, tol, head.p);
+    if (int rc = with_scratch(ctx, tmp, scan_excl(head.p, pos.p, (size_t)nv, s))) // (tmp keeps the larger of the two sizes)
+      return rc;
     int32_t last_pos = 0, last_head = 0;
     ZZZ_HIP(ctx, hipMemcpyAsync(&last_pos, pos.p + nv - 1, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     ZZZ_HIP(ctx, hipMemcpyAsync(&last_head, head.p + nv - 1, sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -374,7 +371,7 @@ int renumber_build(zzz_ctx* ctx)
     if (m > LATTICE_MAX)
       lattice = false;
     ZZZ_HIP(ctx, lat[a].alloc((size_t)L.m[a]));
-    hipLaunchKernelGGL(k_take_heads, dim3(grid_of(nv)), dim3(256), 0, s, sorted.p, head.p, pos.p, nv, L.m[a], lat[a].p);
+    hipLaunchKernelGGL(k_take_heads, dim3(grid_cap(nv, 256, 16384)), dim3(256), 0, s, sorted.p, head.p, pos.p, nv, L.m[a], lat[a].p);
     L.v[a] = lat[a].p;
   }
   // a lattice holds (nearly) all of its points: an unstructured cloud has as many distinct values per axis as points
@@ -413,17 +410,14 @@ int renumber_build(zzz_ctx* ctx)
   ZZZ_HIP(ctx, hipMemsetAsync(keys.p, 0xff, (size_t)nb * sizeof(unsigned long long), s)); // a dof no cell touches sorts last
   ZZZ_HIP(ctx, hipMemsetAsync(flag.p, 0, 2 * sizeof(int32_t), s));
   const int64_t N = ctx->ncells * ctx->nd;
-  hipLaunchKernelGGL(k_dof_keys, dim3(grid_of(N)), dim3(256), 0, s, ctx->x.p, ctx->cell_verts.p, ctx->cell_dofs.p, ctx->ncells,
+  hipLaunchKernelGGL(k_dof_keys, dim3(grid_cap(N, 256, 16384)), dim3(256), 0, s, ctx->x.p, ctx->cell_verts.p, ctx->cell_dofs.p, ctx->ncells,
                      ctx->nd, ctx->order, (int32_t)nb, L, keys.p);
-  hipLaunchKernelGGL(k_iota, dim3(grid_of(nb)), dim3(256), 0, s, ident.p, nb);
-  size_t tb_pairs = 0;
-  ZZZ_HIP(ctx, rocprim::radix_sort_pairs(nullptr, tb_pairs, keys.p, skeys.p, ident.p, ctx->perm.p, (size_t)nb, 0, 64, s));
-  ZZZ_HIP(ctx, tmp.alloc(tb_pairs));
-  ZZZ_HIP(ctx, rocprim::radix_sort_pairs(tmp.p, tb_pairs, keys.p, skeys.p, ident.p, ctx->perm.p, (size_t)nb, 0, 64, s)); // stable
-  hipLaunchKernelGGL(k_invert, dim3(grid_of(nb)), dim3(256), 0, s, ctx->perm.p, skeys.p, nb, ctx->iperm.p, flag.p);
+  hipLaunchKernelGGL(k_iota, dim3(grid_cap(nb, 256, 16384)), dim3(256), 0, s, ident.p, nb);
+  if (int rc = with_scratch(ctx, tmp, sort_pairs(keys.p, skeys.p, ident.p, ctx->perm.p, (size_t)nb, 0, 64, s))) // stable
+    return rc;
+  hipLaunchKernelGGL(k_invert, dim3(grid_cap(nb, 256, 16384)), dim3(256), 0, s, ctx->perm.p, skeys.p, nb, ctx->iperm.p, flag.p);
   int32_t hflag[2] = {0, 0};
-  ZZZ_HIP(ctx, hipMemcpyAsync(hflag, flag.p, sizeof(hflag), hipMemcpyDeviceToHost, s));
-  ZZZ_HIP(ctx, hipStreamSynchronize(s));
+  ZZZ_HIP(ctx, dev_fetch(ctx, flag.p, hflag, 2));
   ZZZ_HIP(ctx, hipGetLastError());
   // two dofs with one key on a lattice: the mesh is not of the family the key describes (e.g. another splitting of
   // the sub-cubes, a curved geometry): leave the caller's order alone rather than guess
@@ -438,7 +432,7 @@ int renumber_build(zzz_ctx* ctx)
     ctx->renumber_kind = lattice ? 1 : 2;
     return ZZZ_OK;
   }
-  hipLaunchKernelGGL(k_translate, dim3(grid_of(N)), dim3(256), 0, s, ctx->cell_dofs.p, N, ctx->iperm.p, (int32_t)nb);
+  hipLaunchKernelGGL(k_translate, dim3(grid_cap(N, 256, 16384)), dim3(256), 0, s, ctx->cell_dofs.p, N, ctx->iperm.p, (int32_t)nb);
   ctx->h_perm.resize((size_t)nb);
   ctx->h_iperm.resize((size_t)nb);
   ZZZ_HIP(ctx, hipMemcpyAsync(ctx->h_perm.data(), ctx->perm.p, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -469,24 +463,21 @@ static int renumber_cells(zzz_ctx* ctx, const Lattice& L)
   ZZZ_HIP(ctx, cperm.alloc((size_t)nc));
   ZZZ_HIP(ctx, flag.alloc(2));
   ZZZ_HIP(ctx, hipMemsetAsync(flag.p, 0, 2 * sizeof(int32_t), s));
-  hipLaunchKernelGGL(k_cell_keys, dim3(grid_of(nc)), dim3(256), 0, s, ctx->x.p, ctx->cell_verts.p, nc, L, keys.p, flag.p);
-  hipLaunchKernelGGL(k_iota, dim3(grid_of(nc)), dim3(256), 0, s, ident.p, nc);
-  size_t tb = 0;
-  ZZZ_HIP(ctx, rocprim::radix_sort_pairs(nullptr, tb, keys.p, skeys.p, ident.p, cperm.p, (size_t)nc, 0, 64, s));
-  ZZZ_HIP(ctx, tmp.alloc(tb));
-  ZZZ_HIP(ctx, rocprim::radix_sort_pairs(tmp.p, tb, keys.p, skeys.p, ident.p, cperm.p, (size_t)nc, 0, 64, s)); // stable
-  hipLaunchKernelGGL(k_not_identity, dim3(grid_of(nc)), dim3(256), 0, s, cperm.p, nc, flag.p + 1);
+  hipLaunchKernelGGL(k_cell_keys, dim3(grid_cap(nc, 256, 16384)), dim3(256), 0, s, ctx->x.p, ctx->cell_verts.p, nc, L, keys.p, flag.p);
+  hipLaunchKernelGGL(k_iota, dim3(grid_cap(nc, 256, 16384)), dim3(256), 0, s, ident.p, nc);
+  if (int rc = with_scratch(ctx, tmp, sort_pairs(keys.p, skeys.p, ident.p, cperm.p, (size_t)nc, 0, 64, s))) // stable
+    return rc;
+  hipLaunchKernelGGL(k_not_identity, dim3(grid_cap(nc, 256, 16384)), dim3(256), 0, s, cperm.p, nc, flag.p + 1);
   int32_t hf[2] = {0, 0};
-  ZZZ_HIP(ctx, hipMemcpyAsync(hf, flag.p, sizeof(hf), hipMemcpyDeviceToHost, s));
-  ZZZ_HIP(ctx, hipStreamSynchronize(s));
+  ZZZ_HIP(ctx, dev_fetch(ctx, flag.p, hf, 2));
   ZZZ_HIP(ctx, hipGetLastError());
   if (hf[0] || !hf[1])
     return ZZZ_OK; // a cell that is no lattice simplex (keep the caller's order), or the order is already this one
   const int nd = ctx->nd;
   ZZZ_HIP(ctx, tmpi.alloc((size_t)(nc * std::max(nd, 4))));
-  hipLaunchKernelGGL(k_gather_rows, dim3(grid_of(nc * 4)), dim3(256), 0, s, ctx->cell_verts.p, cperm.p, nc, 4, tmpi.p);
+  hipLaunchKernelGGL(k_gather_rows, dim3(grid_cap(nc * 4, 256, 16384)), dim3(256), 0, s, ctx->cell_verts.p, cperm.p, nc, 4, tmpi.p);
   ZZZ_HIP(ctx, hipMemcpyAsync(ctx->cell_verts.p, tmpi.p, (size_t)(4 * nc) * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-  hipLaunchKernelGGL(k_gather_rows, dim3(grid_of(nc * nd)), dim3(256), 0, s, ctx->cell_dofs.p, cperm.p, nc, nd, tmpi.p);
+  hipLaunchKernelGGL(k_gather_rows, dim3(grid_cap(nc * nd, 256, 16384)), dim3(256), 0, s, ctx->cell_dofs.p, cperm.p, nc, nd, tmpi.p);
   ZZZ_HIP(ctx, hipMemcpyAsync(ctx->cell_dofs.p, tmpi.p, (size_t)(nd * nc) * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
   ctx->h_cperm.resize((size_t)nc);
   ZZZ_HIP(ctx, hipMemcpyAsync(ctx->h_cperm.data(), cperm.p, (size_t)nc * sizeof(int32_t), hipMemcpyDeviceToHost, s));

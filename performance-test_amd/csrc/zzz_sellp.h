@@ -36,17 +36,6 @@ __device__ inline double gather(const double* __restrict__ x, int col)
   return *reinterpret_cast<const double*>(reinterpret_cast<const char*>(x) + ((unsigned)col << 3));
 }
 
-// a grid of at most `cap` workgroups for `items` items at `per` each
-inline int grid_cap(int64_t items, int per, int cap)
-{
-  int64_t g = (items + per - 1) / per;
-  if (g > cap)
-    g = cap;
-  if (g < 1)
-    g = 1;
-  return (int)g;
-}
-
 // the fields the kernel-argument structs of the specialised products (PipeArgs, BlkArgs, WinArgs) have in common
 template <typename Args>
 inline void product_args_tail(Args& a, const ProductCall& c)

@@ -32,7 +32,7 @@
 
 #include "zzz_sellp.h"
 
-#include <rocprim/rocprim.hpp>
+#include "zzz_prim.h"
 
 namespace zzz
 {
@@ -729,12 +729,8 @@ int sellp_blk_build(zzz_ctx* ctx)
                      ctx->bk_hash_tag2.p, ctx->bk_hash_owner.p, ctx->bk_park.p, ctx->bk_nch.p, info.p, BK_CODE_MAX);
   hipLaunchKernelGGL(k_bk_number, dim3(1), dim3(1024), 0, s, ctx->bk_hash_tag.p, ctx->bk_hash_owner.p, ctx->rowptr.p, vals,
                      ctx->bk_slot_code.p, reinterpret_cast<unsigned long long*>(ctx->bk_tab.p), info.p);
-  {
-    size_t tb = 0;
-    ZZZ_HIP(ctx, rocprim::exclusive_scan(nullptr, tb, ctx->bk_nch.p, ctx->bk_c0.p, (int32_t)0, (size_t)nsl + 1, rocprim::plus<int32_t>(), s));
-    ZZZ_HIP(ctx, ctx->scr_tmp.grow_keep(tb, ctx->retired));
-    ZZZ_HIP(ctx, rocprim::exclusive_scan(ctx->scr_tmp.p, tb, ctx->bk_nch.p, ctx->bk_c0.p, (int32_t)0, (size_t)nsl + 1, rocprim::plus<int32_t>(), s));
-  }
+  if (int rc = with_scratch(ctx, scan_excl(ctx->bk_nch.p, ctx->bk_c0.p, (size_t)nsl + 1, s)))
+    return rc;
   ZZZ_HIP(ctx, hipGetLastError());
   int32_t h[8];
   int32_t total = 0;

@@ -6,7 +6,7 @@
 
 #include "zzz_sellp.h"
 
-#include <rocprim/rocprim.hpp>
+#include "zzz_prim.h"
 
 namespace zzz
 {
@@ -506,16 +506,11 @@ int sp_sd_build(zzz_ctx* ctx)
     hipLaunchKernelGGL((k_sp_sd_build<false, true>), dim3(grid), dim3(128), 0, s, desc, (const int32_t*)nullptr, ctx->sp_vals.p,
                        ctx->sp_meta.p, (int)ctx->nrows, nsl, (uint16_t*)nullptr, (double*)nullptr, (const int64_t*)nullptr,
                        ctx->sp_sd_info.p, bytes);
-  {
-    const auto even = rocprim::make_transform_iterator(ctx->sp_sd_info.p, Even2{}); // (tables start at even entries: 16-B aligned)
-    size_t tb = 0;
-    ZZZ_HIP(ctx, rocprim::exclusive_scan(nullptr, tb, even, ctx->sp_sd_off.p, (int64_t)0, (size_t)nsl + 1, rocprim::plus<int64_t>(), s));
-    ZZZ_HIP(ctx, ctx->scr_tmp.grow_keep(tb, ctx->retired));
-    ZZZ_HIP(ctx, rocprim::exclusive_scan(ctx->scr_tmp.p, tb, even, ctx->sp_sd_off.p, (int64_t)0, (size_t)nsl + 1, rocprim::plus<int64_t>(), s));
-  }
+  const auto even = rocprim::make_transform_iterator(ctx->sp_sd_info.p, Even2{}); // (tables start at even entries: 16-B aligned)
+  if (int rc = with_scratch(ctx, scan_excl(even, ctx->sp_sd_off.p, (size_t)nsl + 1, s)))
+    return rc;
   int64_t total = 0;
-  ZZZ_HIP(ctx, hipMemcpyAsync(&total, ctx->sp_sd_off.p + nsl, sizeof(total), hipMemcpyDeviceToHost, s));
-  ZZZ_HIP(ctx, hipStreamSynchronize(s));
+  ZZZ_HIP(ctx, dev_fetch(ctx, ctx->sp_sd_off.p + nsl, &total));
   ZZZ_HIP(ctx, ctx->sp_sd_vals.alloc((size_t)total + 2));
   if (ctx->sp_sorted)
     hipLaunchKernelGGL((k_sp_sd_build<true, false>), dim3(grid), dim3(128), 0, s, desc, ctx->sp_perm.p, ctx->sp_vals.p, ctx->sp_meta.p,

@@ -31,7 +31,7 @@
 
 #include "zzz_sellp.h"
 
-#include <rocprim/rocprim.hpp>
+#include "zzz_prim.h"
 
 namespace zzz
 {
@@ -1063,15 +1063,10 @@ static int sp_build_sorted(zzz_ctx* ctx, int64_t* total_out, bool sorted = true)
   else // natural row order, rows too long for the LDS staging of k_sp_pack
     hipLaunchKernelGGL(k_sp_slice_len, dim3(grid_cap(nsl + 1, 4, 8192)), dim3(256), 0, s, ctx->sp_rownnz.p, nrows, nsl,
                        ctx->sp_nch.p, ctx->sp_wlast.p);
-  size_t tb = 0;
-  ZZZ_HIP(ctx, rocprim::exclusive_scan(nullptr, tb, ctx->sp_nch.p, ctx->sp_chunk_off.p, 0, (size_t)nsl + 1,
-                                       rocprim::plus<int32_t>(), s));
-  ZZZ_HIP(ctx, ctx->scr_tmp.grow_keep(tb, ctx->retired));
-  ZZZ_HIP(ctx, rocprim::exclusive_scan(ctx->scr_tmp.p, tb, ctx->sp_nch.p, ctx->sp_chunk_off.p, 0, (size_t)nsl + 1,
-                                       rocprim::plus<int32_t>(), s));
+  if (int rc = with_scratch(ctx, scan_excl(ctx->sp_nch.p, ctx->sp_chunk_off.p, (size_t)nsl + 1, s)))
+    return rc;
   int32_t* tot = reinterpret_cast<int32_t*>(ctx->h_state + 4); // pinned scratch
-  ZZZ_HIP(ctx, hipMemcpyAsync(&tot[0], ctx->sp_chunk_off.p + nsl, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  ZZZ_HIP(ctx, hipStreamSynchronize(s));
+  ZZZ_HIP(ctx, dev_fetch(ctx, ctx->sp_chunk_off.p + nsl, tot));
   *total_out = tot[0];
   return ZZZ_OK;
 }
@@ -1111,12 +1106,8 @@ static int sp_fill_sorted(zzz_ctx* ctx, int64_t total, bool sorted = true)
       ZZZ_HIP(ctx, ctx->sp_ccols.alloc((size_t)cap));
       ctx->sp_crow_is_cap = false;
       const auto padded = rocprim::make_transform_iterator(ctx->sp_rownnz.p, Pad8{});
-      size_t tb = 0;
-      ZZZ_HIP(ctx, rocprim::exclusive_scan(nullptr, tb, padded, ctx->sp_crow.p, (int64_t)0, (size_t)nrows + 1,
-                                           rocprim::plus<int64_t>(), s));
-      ZZZ_HIP(ctx, ctx->scr_tmp.grow_keep(tb, ctx->retired));
-      ZZZ_HIP(ctx, rocprim::exclusive_scan(ctx->scr_tmp.p, tb, padded, ctx->sp_crow.p, (int64_t)0, (size_t)nrows + 1,
-                                           rocprim::plus<int64_t>(), s));
+      if (int rc = with_scratch(ctx, scan_excl(padded, ctx->sp_crow.p, (size_t)nrows + 1, s)))
+        return rc;
       hipLaunchKernelGGL(k_sp_compact, dim3(grid_cap(nsl, 4, 8192)), dim3(256), 0, s, ctx->rowptr.p, ctx->cols.p, ctx->vals.p, nrows,
                          nsl, ctx->sellp_drop ? 1 : 0, ctx->sp_crow.p, ctx->sp_cvals.p, ctx->sp_ccols.p);
     }
@@ -1172,12 +1163,8 @@ int sellp_capacity_rows(zzz_ctx* ctx)
   ZZZ_HIP(ctx, ctx->sp_cvals.alloc((size_t)cap));
   ZZZ_HIP(ctx, ctx->sp_ccols.alloc((size_t)cap));
   hipLaunchKernelGGL(k_sp_cap_len, dim3(grid_cap((int64_t)nrows + 1, 256, 4096)), dim3(256), 0, s, ctx->rowptr.p, nrows, ctx->sp_crow.p);
-  size_t tb = 0;
-  ZZZ_HIP(ctx, rocprim::exclusive_scan(nullptr, tb, ctx->sp_crow.p, ctx->sp_crow.p, (int64_t)0, (size_t)nrows + 1,
-                                       rocprim::plus<int64_t>(), s));
-  ZZZ_HIP(ctx, ctx->scr_tmp.grow_keep(tb, ctx->retired));
-  ZZZ_HIP(ctx, rocprim::exclusive_scan(ctx->scr_tmp.p, tb, ctx->sp_crow.p, ctx->sp_crow.p, (int64_t)0, (size_t)nrows + 1,
-                                       rocprim::plus<int64_t>(), s));
+  if (int rc = with_scratch(ctx, scan_excl(ctx->sp_crow.p, ctx->sp_crow.p, (size_t)nrows + 1, s))) // (in place)
+    return rc;
   ZZZ_HIP(ctx, hipGetLastError());
   ctx->sp_crow_is_cap = true;
   return ZZZ_OK;

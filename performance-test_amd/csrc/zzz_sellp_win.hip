@@ -34,7 +34,7 @@
 
 #include "zzz_sellp.h"
 
-#include <rocprim/rocprim.hpp>
+#include "zzz_prim.h"
 
 namespace zzz
 {
@@ -922,12 +922,8 @@ static int bw_structure(zzz_ctx* ctx)
   hipLaunchKernelGGL(k_bw_cellsum, dim3(1), dim3(64), 0, s, bbox.p + 16, (int)cs_grid, bbox.p);
   hipLaunchKernelGGL(k_bw_keys, dim3((unsigned)std::min<int64_t>(((int64_t)nrows + 255) / 256, 4096)), dim3(256), 0, s, dofx.p, bbox.p,
                      ctx->ncells, nrows, ctx->bs, key.p, val.p);
-  {
-    size_t tb = 0;
-    ZZZ_HIP(ctx, rocprim::radix_sort_pairs(nullptr, tb, key.p, key2.p, val.p, ctx->bw_order.p, (size_t)nrows, 0, 30, s));
-    ZZZ_HIP(ctx, ctx->scr_tmp.grow_keep(tb, ctx->retired));
-    ZZZ_HIP(ctx, rocprim::radix_sort_pairs(ctx->scr_tmp.p, tb, key.p, key2.p, val.p, ctx->bw_order.p, (size_t)nrows, 0, 30, s));
-  }
+  if (int rc = with_scratch(ctx, sort_pairs(key.p, key2.p, val.p, ctx->bw_order.p, (size_t)nrows, 0, 30, s)))
+    return rc;
   DevBuf<int32_t>& info = ctx->bw_info;
   ZZZ_HIP(ctx, info.reserve(8));
   ZZZ_HIP(ctx, hipMemsetAsync(info.p, 0, 8 * sizeof(int32_t), s));
@@ -942,12 +938,8 @@ static int bw_structure(zzz_ctx* ctx)
   const unsigned grid = (unsigned)std::min<int32_t>(nblk, 256 * 2);
   hipLaunchKernelGGL(k_bw_sort, dim3(grid), dim3(BW_THREADS), 0, s, ctx->bw_order.p, nrows, nblk, ctx->rowptr.p, ctx->bw_skey.p,
                      ctx->bw_blk_chunks.p, ctx->bw_woff.p, info.p);
-  {
-    size_t tb = 0;
-    ZZZ_HIP(ctx, rocprim::exclusive_scan(nullptr, tb, ctx->bw_blk_chunks.p, ctx->bw_chunk0.p, (int64_t)0, (size_t)nblk + 1, rocprim::plus<int64_t>(), s));
-    ZZZ_HIP(ctx, ctx->scr_tmp.grow_keep(tb, ctx->retired));
-    ZZZ_HIP(ctx, rocprim::exclusive_scan(ctx->scr_tmp.p, tb, ctx->bw_blk_chunks.p, ctx->bw_chunk0.p, (int64_t)0, (size_t)nblk + 1, rocprim::plus<int64_t>(), s));
-  }
+  if (int rc = with_scratch(ctx, scan_excl(ctx->bw_blk_chunks.p, ctx->bw_chunk0.p, (size_t)nblk + 1, s))) // (32-bit counts, 64-bit sums)
+    return rc;
   ZZZ_HIP(ctx, hipGetLastError());
   int32_t h[8];
   int64_t tot[2] = {0, 0};
