@@ -214,7 +214,17 @@ int zzz_sync(zzz_ctx* ctx);
 
 /* mesh::Geometry::x() and the geometry dofmap of the mesh handed to problem()
  * (src/poisson_problem.h:19-23; created at src/mesh.cpp:184-186).
- * x: nverts*3 row-major; cell_verts: ncells*4 local vertex indices. */
+ * x: nverts*3 row-major; cell_verts: ncells*4 local vertex indices.
+ * A successful call FORGETS the dofmap and everything behind it -- the Dirichlet set and its values, the exterior facets,
+ * the coefficients, the internal dof and cell orders, pattern, matrix, matrix-free plan and near-nullspace: all of them
+ * were indexed by the cells or dofs of the mesh just replaced.  Until the next zzz_dofmap_upload every entry point that
+ * needs a dofmap answers ZZZ_ERR_ARG ("... before zzz_dofmap_upload", or the missing pattern / matrix it would have
+ * built from one): a host-side test in front of every launch, nothing is enqueued.  A multigrid hierarchy of the old
+ * problem is no longer served either (zzz_mg_info, _apply, _transfer, _level_csr: "no hierarchy").  A refused call (a bad array) leaves
+ * the context as it was.  zzz_dofmap_upload may be called again on the same mesh (another order or block size): the
+ * context is then what a fresh one is after the same mesh and that dofmap -- the Dirichlet set, facets and coefficients
+ * are uploaded again after it, as after the first.
+ * (No ABI version bump: nothing an entry point reads or writes has changed.) */
 int zzz_mesh_upload(zzz_ctx* ctx, int64_t nverts, const double* x, int64_t ncells, const int32_t* cell_verts);
 
 /* fem::create_functionspace's DofMap + IndexMap (src/poisson_problem.cpp:43-44,

@@ -321,8 +321,6 @@ int zzz_sync(zzz_ctx* ctx)
 int zzz_mesh_upload(zzz_ctx* ctx, int64_t nverts, const double* x, int64_t ncells, const int32_t* cell_verts)
 {
   ZZZ_ENTER(ctx);
-  ctx->cube_feed = false; // (ZZZ_PC_MG needs a generated cube)
-  ++ctx->feed_version;
   if (nverts <= 0 || ncells <= 0 || !x || !cell_verts)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_mesh_upload: empty mesh or NULL array");
   if (nverts > INT32_MAX / 4 || ncells > (INT32_MAX - 8) / 20)
@@ -331,24 +329,71 @@ int zzz_mesh_upload(zzz_ctx* ctx, int64_t nverts, const double* x, int64_t ncell
   for (int64_t i = 0; i < 4 * ncells; ++i)
     if (cell_verts[i] < 0 || cell_verts[i] >= nverts)
       return fail(ctx, ZZZ_ERR_ARG, "cell_verts[%lld] = %d out of range", (long long)i, cell_verts[i]);
+  ctx->cube_feed = false; // (ZZZ_PC_MG needs a generated cube; a refused call above has not changed the feed)
+  ++ctx->feed_version;
   ctx->nverts = nverts;
   ctx->ncells = ncells;
   ctx->h_cell_verts.assign(cell_verts, cell_verts + 4 * ncells);
-  int rc = upload(ctx, ctx->x, x, (size_t)(3 * nverts));
-  if (rc)
-    return rc;
-  rc = upload(ctx, ctx->cell_verts, cell_verts, (size_t)(4 * ncells));
+  // A new mesh forgets the dofmap and everything behind it: cell_dofs, the internal dof and cell orders, the facet mask, the
+  // Dirichlet set and its values, the coefficients were all laid out cell by cell or dof by dof of the OLD mesh (another cell
+  // count would even be walked past its end).  order == 0 is what every entry point that needs a dofmap tests before it
+  // launches anything; the next zzz_dofmap_upload sets all of this up again.
+  ctx->order = ctx->nd = 0;
+  ctx->h_cell_dofs.clear();
+  renumber_clear(ctx);
+  mg_invalidate(ctx); // (zzz_mg_apply, _transfer, _info and _level_csr serve a ready hierarchy only)
+  ctx->have_bc = false;
+  bc_values_clear(ctx);
+  ctx->have_coeff[0] = ctx->have_coeff[1] = false;
+  ctx->nfacets = 0;
+  ctx->near_null_ld = 0;
+  ctx->adj_runs_n = -1;
   ctx->have_pattern = ctx->have_matrix = false;
   ctx->xq_valid = false;
   ctx->mf.valid = ctx->mf.failed = false;
-  return rc;
+  int rc = upload(ctx, ctx->x, x, (size_t)(3 * nverts));
+  if (rc)
+    return rc;
+  return upload(ctx, ctx->cell_verts, cell_verts, (size_t)(4 * ncells));
+}
+
+// The device's cell_verts back in the caller's cell order (renumber_cells permutes it in place): from the host copy of an
+// uploaded mesh, else -- a generated mesh has none -- by undoing h_cperm.
+static int restore_cell_verts(zzz_ctx* ctx)
+{
+  if (!ctx->cells_renumbered)
+    return ZZZ_OK;
+  const size_t n = (size_t)(4 * ctx->ncells);
+  int rc;
+  if (ctx->h_cell_verts.size() == n)
+    rc = upload(ctx, ctx->cell_verts, ctx->h_cell_verts.data(), n);
+  else
+  {
+    if (ctx->h_cperm.size() != (size_t)ctx->ncells)
+      return fail(ctx, ZZZ_ERR_ARG, "zzz_dofmap_upload: the internal cell order of the mesh is lost: upload or generate the mesh again");
+    std::vector<int32_t> cur(n), orig(n);
+    ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ZZZ_HIP(ctx, hipMemcpy(cur.data(), ctx->cell_verts.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < (size_t)ctx->ncells; ++i)
+      for (int k = 0; k < 4; ++k)
+        orig[4 * (size_t)ctx->h_cperm[i] + k] = cur[4 * i + k];
+    rc = upload(ctx, ctx->cell_verts, orig.data(), n);
+  }
+  if (rc)
+    return rc;
+  // the device's cell order is the caller's again.  The old cell_dofs and facet mask are not in it: the dofmap behind them is
+  // void from here on, whether or not the rest of this upload succeeds
+  ctx->cells_renumbered = false;
+  ctx->h_cperm.clear();
+  ctx->order = ctx->nd = 0;
+  ctx->have_pattern = ctx->have_matrix = false;
+  ctx->mf.valid = ctx->mf.failed = false;
+  return ZZZ_OK;
 }
 
 int zzz_dofmap_upload(zzz_ctx* ctx, int order, int bs, const int32_t* cell_dofs, int64_t n_owned, int64_t n_ghost)
 {
   ZZZ_ENTER(ctx);
-  ctx->cube_feed = false; // (ZZZ_PC_MG needs a generated cube)
-  ++ctx->feed_version;
   const int nd = ndofs_cell(order);
   if (nd < 0) // form_poisson_a.at(order - 1) throws std::out_of_range in the reference
     return fail(ctx, ZZZ_ERR_ARG, "order %d not supported (1..3)", order);
@@ -364,6 +409,12 @@ int zzz_dofmap_upload(zzz_ctx* ctx, int order, int bs, const int32_t* cell_dofs,
   for (int64_t i = 0; i < ctx->ncells * nd; ++i)
     if (cell_dofs[i] < 0 || cell_dofs[i] >= nloc)
       return fail(ctx, ZZZ_ERR_ARG, "cell_dofs[%lld] = %d out of range", (long long)i, cell_dofs[i]);
+  // a second dofmap on the same mesh: an earlier one may have left cell_verts in the library's cell order, and the new
+  // cell_dofs arrive in the caller's -- renumber_build below must see both in the caller's order, as on a fresh context
+  if (int rc = restore_cell_verts(ctx))
+    return rc;
+  ctx->cube_feed = false; // (ZZZ_PC_MG needs a generated cube; a refused call above has not changed the feed)
+  ++ctx->feed_version;
   ctx->order = order;
   ctx->bs = bs;
   ctx->nd = nd;
@@ -400,8 +451,6 @@ int zzz_dofmap_upload(zzz_ctx* ctx, int order, int bs, const int32_t* cell_dofs,
 int zzz_bc_upload(zzz_ctx* ctx, int64_t nbc, const int32_t* bc_dofs)
 {
   ZZZ_ENTER(ctx);
-  ctx->cube_feed = false; // (ZZZ_PC_MG needs a generated cube)
-  ++ctx->feed_version;
   bc_values_clear(ctx); // (a new Dirichlet set, or a failed attempt at one: u0 == 0 until values are uploaded for it)
   if (ctx->order == 0)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_bc_upload before zzz_dofmap_upload");
@@ -417,6 +466,8 @@ int zzz_bc_upload(zzz_ctx* ctx, int64_t nbc, const int32_t* bc_dofs)
       d = (int64_t)ctx->h_iperm[(size_t)(d / ctx->bs)] * ctx->bs + d % ctx->bs;
     m[(size_t)d] = 1;
   }
+  ctx->cube_feed = false; // (ZZZ_PC_MG needs a generated cube; a refused call above has not changed the feed)
+  ++ctx->feed_version;
   ZZZ_HIP(ctx, hipMemcpyAsync(ctx->bc.p, m.data(), m.size(), hipMemcpyHostToDevice, ctx->stream));
   ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
   ctx->have_bc = true;
@@ -457,8 +508,6 @@ int zzz_bc_values_upload(zzz_ctx* ctx, const double* values)
 int zzz_facets_upload(zzz_ctx* ctx, int64_t nfacets, const int32_t* pairs)
 {
   ZZZ_ENTER(ctx);
-  ctx->cube_feed = false; // (ZZZ_PC_MG needs a generated cube)
-  ++ctx->feed_version;
   if (ctx->order == 0)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_facets_upload before zzz_dofmap_upload");
   if (nfacets < 0 || (nfacets > 0 && !pairs))
@@ -471,6 +520,8 @@ int zzz_facets_upload(zzz_ctx* ctx, int64_t nfacets, const int32_t* pairs)
       return fail(ctx, ZZZ_ERR_ARG, "facet %lld = (%d, %d) out of range", (long long)i, c, f);
     m[c] |= (uint8_t)(1u << f);
   }
+  ctx->cube_feed = false; // (ZZZ_PC_MG needs a generated cube; a refused call above has not changed the feed)
+  ++ctx->feed_version;
   if (ctx->cells_renumbered) // the device holds the cells in the library's order: mask of internal cell i = caller's cperm[i]
   {
     std::vector<uint8_t> mi(m.size());
@@ -782,6 +833,8 @@ int zzz_csr_upload_values(zzz_ctx* ctx, const double* vals)
 int zzz_assemble_matrix(zzz_ctx* ctx, int form)
 {
   ZZZ_ENTER(ctx);
+  if (ctx->order == 0)
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_assemble_matrix before zzz_dofmap_upload");
   if (!ctx->have_pattern)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_assemble_matrix before zzz_csr_pattern_build");
   if (form != ZZZ_FORM_POISSON && form != ZZZ_FORM_ELASTICITY)
@@ -798,6 +851,8 @@ int zzz_assemble_matrix(zzz_ctx* ctx, int form)
 int zzz_assemble_vector(zzz_ctx* ctx, int form)
 {
   ZZZ_ENTER(ctx);
+  if (ctx->order == 0)
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_assemble_vector before zzz_dofmap_upload");
   if (!ctx->have_pattern)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_assemble_vector before zzz_csr_pattern_build");
   if (form != ZZZ_FORM_POISSON && form != ZZZ_FORM_ELASTICITY)
@@ -1067,6 +1122,8 @@ int zzz_cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rno
     return fail(ctx, ZZZ_ERR_ARG, "zzz_cg_solve: matrix not assembled");
   if (o->op != ZZZ_OP_CSR && o->op != ZZZ_OP_MATFREE)
     return fail(ctx, ZZZ_ERR_ARG, "unknown operator kind %d", o->op);
+  if (o->op == ZZZ_OP_MATFREE && ctx->order == 0) // (before the solve writes its initial guess)
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_cg_solve: the matrix-free operator before zzz_dofmap_upload");
   if (o->variant != ZZZ_CG_PETSC && o->variant != ZZZ_CG_CGH && o->variant != ZZZ_CG_PIPE)
     return fail(ctx, ZZZ_ERR_ARG, "unknown CG variant %d", o->variant);
   if (o->variant == ZZZ_CG_PIPE && (o->op != ZZZ_OP_CSR || o->single_reduction || (o->pc != ZZZ_PC_NONE && o->pc != ZZZ_PC_JACOBI)))

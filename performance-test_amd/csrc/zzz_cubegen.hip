@@ -137,6 +137,7 @@ extern "C" int zzz_cube_generate(zzz_ctx* ctx, int problem, int order, int64_t n
   ctx->have_pattern = ctx->have_matrix = false;
   ctx->xq_valid = false;
   ctx->mf.valid = ctx->mf.failed = false;
+  ctx->near_null_ld = 0; // (as zzz_dofmap_upload: a basis built for the earlier dofs is not this problem's)
   ctx->adj_runs_n = -1;
   pattern_reserve(ctx);
   rc = ensure_p1_coords(ctx);

@@ -654,6 +654,7 @@ void mg_profile_end(zzz_ctx* ctx, int cycles); // ... and their mean over the cy
 int mg_level0_products(const zzz_ctx* ctx);
 double mg_level0_bound(const zzz_ctx* ctx);
 void mg_destroy(zzz_ctx* ctx);
+void mg_invalidate(zzz_ctx* ctx); // the hierarchy is of a problem that is gone: declined by zzz_mg_*, rebuilt by the next set-up
 // zzz_pmg.hip: the transfer between the Pk (order 2, 3) and the P1 dofs of one generated n[0] x n[1] x n[2] cube, enqueued on
 // ctx->stream; bcf / bcc are the Dirichlet bytes of the two contexts, sub (may be null) is subtracted from rf on the way in
 int pmg_prolong(zzz_ctx* ctx, const int* stop, int order, int bs, const int64_t n[3], const uint8_t* bcf, const uint8_t* bcc,

@@ -297,6 +297,14 @@ int mg_level0_products(const zzz_ctx* ctx)
 }
 double mg_level0_bound(const zzz_ctx* ctx) { return ctx->mg && ctx->mg->ready ? ctx->mg->lv[0]->hi : 0.0; }
 
+// The hierarchy belongs to a problem that is gone (zzz_mesh_upload): not ready, so that the zzz_mg_* entry points decline it and
+// the next set-up builds anew.  Nothing is freed here (hipFree waits for the whole device); the rebuild or the context frees it.
+void mg_invalidate(zzz_ctx* ctx)
+{
+  if (ctx->mg)
+    ctx->mg->ready = false;
+}
+
 int mg_check(zzz_ctx* ctx, const zzz_solver_opts* o)
 {
   const bool pmg = o->pc == ZZZ_PC_PMG, agg = o->pc == ZZZ_PC_AGG;

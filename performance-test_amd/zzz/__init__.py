@@ -688,6 +688,12 @@ class Context:
                     packed_slices=int(info[10]), unpacked_slices=int(info[11]), mixed_pairs=int(info[12]),
                     max_codes_per_slot=int(info[13]))
 
+    def spmv_values_info_raw(self):
+        """the 14 entries of zzz_spmv_values_info2 as they come"""
+        info = (C.c_int64 * 14)()
+        self._ck(self.L.zzz_spmv_values_info2(self.h, 14, info))
+        return [int(v) for v in info]
+
     def spmv_x_windows(self):
         """(LDS doubles per workgroup, bytes of x loaded into LDS per product) when the operator stream carries x windows,
         else (0, 0)"""
