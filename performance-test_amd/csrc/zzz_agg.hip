@@ -436,7 +436,7 @@ static int agg_aggregate_bs(zzz_ctx* ctx, zzz_ctx* f, AggLevel& A)
   hipStream_t s = ctx->stream;
   const int64_t n = f->n_owned;
   const int g = grid_cap(n, VB, 1 << 16);
-  const int32_t* perm = f->renumbered ? f->perm.p : nullptr;
+  const int32_t* perm = f->dofmap.renumbered ? f->perm.p : nullptr;
   A.bs = BS;
   A.nf = n;
   A.nagg = 0;
@@ -537,7 +537,7 @@ static int agg_galerkin_bs(zzz_ctx* ctx, zzz_ctx* f, AggLevel& A, zzz_ctx* c)
   ZZZ_HIP(ctx, A.src.alloc((size_t)N));
   hipLaunchKernelGGL(k_agg_rowidx, dim3(grid_cap(nrows, VB, 1 << 16)), dim3(VB), 0, s, nrows, f->rowptr.p, rowidx.p);
   const int32_t* order = nullptr;
-  if (f->renumbered)
+  if (f->dofmap.renumbered)
   {
     hipLaunchKernelGGL(k_agg_caller_keys<BS>, dim3(g), dim3(VB), 0, s, N, rowidx.p, f->cols.p, f->perm.p, k0.p, v0.p);
     if (int rc = with_scratch(ctx, tmp, sort_pairs(k0.p, k1.p, v0.p, v1.p, (size_t)N, 0, 64, s)))

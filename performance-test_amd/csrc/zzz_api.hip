@@ -64,46 +64,147 @@ int alloc_problem_vectors(zzz_ctx* ctx)
   ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return ZZZ_OK;
 }
-int ctx_adopt_values(zzz_ctx* ctx)
+// ---- the forget path (zzz_internal.h): each function resets its tier to what a fresh context holds, then the tiers behind it
+void forget_values(zzz_ctx* ctx) { ctx->values = {}; }
+void forget_pattern(zzz_ctx* ctx)
+{
+  ctx->pattern = {};
+  forget_values(ctx);
+}
+// A new dof layout or Dirichlet set: the values of u0 uploaded for the old one mean nothing, and the lifting rows change
+void forget_bc_values(zzz_ctx* ctx)
+{
+  ctx->dirichlet.have_bc_val = false;
+  ++ctx->bc_version;
+}
+void forget_bc(zzz_ctx* ctx)
+{
+  ctx->dirichlet = {};
+  ctx->mf.valid = ctx->mf.failed = false; // the plan of the matrix-free action carries the Dirichlet markers of its dof lists
+  forget_bc_values(ctx);
+}
+// cell_dofs, the internal dof and cell orders, the facet mask, the Dirichlet set and its values, the coefficients are all laid
+// out cell by cell or dof by dof of the OLD dofmap (another cell count would even be walked past its end)
+void forget_dofmap(zzz_ctx* ctx)
+{
+  ctx->dofmap = {};
+  ctx->h_cell_dofs.clear();
+  ctx->perm.release();
+  ctx->iperm.release();
+  ctx->h_perm.clear();
+  ctx->h_iperm.clear();
+  std::vector<int32_t>().swap(ctx->h_cperm);
+  std::vector<uint16_t>().swap(ctx->csr_slot);
+  forget_bc(ctx);
+  forget_pattern(ctx);
+}
+void forget_mesh(zzz_ctx* ctx)
+{
+  ctx->h_cell_verts.clear();
+  mg_invalidate(ctx); // (zzz_mg_apply, _transfer, _info and _level_csr serve a ready hierarchy only)
+  forget_dofmap(ctx);
+}
+// The values in ctx->vals were rewritten (an assembly, an upload, a coarse level's Galerkin sum)
+int ctx_adopt_values(zzz_ctx* ctx, bool assembled)
 {
   ++ctx->mat_version;
-  ctx->sp_rownnz_fresh = ctx->sp_compact_fresh = false;
-  if (int rc = sell_update(ctx, false))
-    return rc;
-  ctx->have_matrix = true;
-  return ZZZ_OK;
+  // what the assembly that has just run left for the packer (launch_matrix_pk_pos) belongs to the NEW values: it alone passes
+  // the forget, and sell_update spends it
+  const bool rownnz = assembled && ctx->values.sp_rownnz_fresh, compact = assembled && ctx->values.sp_compact_fresh;
+  forget_values(ctx);
+  ctx->values.sp_rownnz_fresh = rownnz;
+  ctx->values.sp_compact_fresh = compact;
+  const int rc = sell_update(ctx); // MatAssemblyEnd-like finalisation: refresh the SpMV copy
+  ctx->values.sp_rownnz_fresh = ctx->values.sp_compact_fresh = false; // (whether or not this packing path had a use for them)
+  ctx->values.have_matrix = rc == ZZZ_OK;
+  return rc;
 }
 int ctx_adopt_csr(zzz_ctx* ctx, int bs, int64_t nnodes, int64_t nnz, int max_row_nnz)
 {
-  ctx->order = 0; // (no element: zzz_csr_pattern_build and the assemblies decline such a context)
-  ctx->nd = 0;
+  forget_dofmap(ctx); // (order == 0, no element: zzz_csr_pattern_build and the assemblies decline such a context)
   ctx->bs = bs;
   ctx->n_owned = nnodes;
   ctx->n_ghost = 0;
   ctx->nverts = ctx->ncells = 0;
   ctx->nrows = ctx->ncols = nnodes * bs;
   ctx->nnz = nnz;
-  ctx->have_pattern = ctx->have_matrix = false;
-  ctx->have_bc = false;
   ++ctx->pattern_version;
   ++ctx->feed_version;
   if (int rc = alloc_problem_vectors(ctx))
     return rc;
   if (int rc = build_tiles_device(ctx, (max_row_nnz + bs - 1) / bs))
     return rc;
-  ctx->have_sell = ctx->sell_current = ctx->sp_pending = false;
-  ctx->sp_bounds_ok = false;
-  if (ctx->sellp_mode != 0)
+  if (ctx->knob.sellp_mode != 0)
     if (int rc = sellp_pattern_bounds(ctx))
       return rc;
-  ctx->have_pattern = true;
+  ctx->pattern.have_pattern = true;
   return ctx_adopt_values(ctx);
 }
-// A new dof layout or Dirichlet set: the values of u0 uploaded for the old one mean nothing, and the lifting rows change
-void bc_values_clear(zzz_ctx* ctx)
+// tuning knobs for A/B measurements (defaults are the measured best)
+static void read_knobs(Knobs& k)
 {
-  ctx->have_bc_val = false;
-  ++ctx->bc_version;
+  if (const char* e = getenv("ZZZ_SPMV_VARIANT"))
+    k.spmv_variant = atoi(e) & 27;
+  if (const char* e = getenv("ZZZ_SELLP")) // operator stream: 0 off, 1 automatic, 2 natural row order, 3 sorted rows
+  {
+    const int v = atoi(e);
+    k.sellp_mode = v >= 0 && v <= 4 ? v : 1; // (4: natural row order through the long-row packer whatever the row lengths: tests)
+    k.sellp_long_rows = v == 4;
+    if (v == 4)
+      k.sellp_mode = 2;
+  }
+  if (const char* e = getenv("ZZZ_SELLP_DROP"))
+    k.sellp_drop = atoi(e) != 0;
+  if (const char* e = getenv("ZZZ_SELLP_DICT"))
+    k.sellp_dict = atoi(e);
+  if (const char* e = getenv("ZZZ_SELLP_BWIN")) // long scalar rows, x from LDS windows: 0 never, 1 by size, 2 always
+    k.sellp_bwin = atoi(e);
+  if (const char* e = getenv("ZZZ_SELLP_EARLY")) // 0: generic stream at every assembly, special forms at the first product (A/B)
+    k.sellp_early = atoi(e) != 0;
+  if (const char* e = getenv("ZZZ_ASM_NODE3")) // 0: elasticity P1 matrix assembly with a thread per scalar row (A/B)
+    k.asm_node3 = atoi(e) != 0;
+  if (const char* e = getenv("ZZZ_SELLP_BLK")) // 0: block size 3 stays on the generic product (A/B against the block-row form)
+    k.sellp_blk = atoi(e);
+  if (const char* e = getenv("ZZZ_SELLP_PIPE")) // 0: the generic product kernel always (A/B against the pipelined one)
+    k.sellp_pipe = atoi(e);
+  if (const char* e = getenv("ZZZ_SELLP_PAL")) // 0: the one-chunk product reads 16-bit value codes everywhere (A/B against the packed form)
+    k.sellp_pal = atoi(e) != 0;
+  if (const char* e = getenv("ZZZ_CG_DINV_CODES"))
+    k.cg_dinv_codes = atoi(e);
+  if (const char* e = getenv("ZZZ_CG_XDEFER")) // the classical CG's solution update once per K iterations: 0 never, 1 by size, 2 always
+    k.cg_xdefer = atoi(e);
+  if (const char* e = getenv("ZZZ_CG_XDEFER_K"))
+  {
+    const int v = atoi(e);
+    if (v == 2 || v == 4 || v == 8)
+      k.cg_xdefer_k = v;
+  }
+  if (const char* e = getenv("ZZZ_SELLP_FORMS")) // A/B knob, a mask of the code-free chunk forms (default 7): 1 affine chunks
+  {                                              // (column = slot base + lane), 2 one-chunk slices placed by column so that
+    const int v = atoi(e);                       // short boundary rows fit the affine form, 4 periodic chunks (block size 3)
+    if (!(v & 1))
+      k.sellp_tail |= 2;
+    k.sellp_align = (v & 2) != 0;
+    k.sellp_periodic = (v & 4) != 0;
+  }
+  if (const char* e = getenv("ZZZ_SPMV_LPR")) // lanes per row of the SpMV row phase: 1, 2, 4, 8, 16
+  {
+    const int v = atoi(e);
+    for (int sft = 0; sft <= 4; ++sft)
+      if (v == (1 << sft))
+        k.spmv_lpr_forced = sft;
+  }
+  if (const char* e = getenv("ZZZ_COLS16")) // 0: keep the SpMV on the int32 columns; 10..13: force the offset width
+  {
+    const int v = atoi(e);
+    k.cols16_enabled = v != 0;
+    if (v >= 10 && v <= 13)
+      k.cols16_offb_forced = v;
+  }
+  if (const char* e = getenv("ZZZ_OVERLAP"))
+    k.overlap = atoi(e) != 0;
+  if (const char* e = getenv("ZZZ_CG_PIPE_STREAM")) // 0: the all-reduce of the pipelined CG stays on the main stream (A/B against its own stream)
+    k.pipe_stream = atoi(e) != 0;
 }
 } // namespace zzz
 
@@ -195,72 +296,10 @@ int zzz_ctx_create(int device, zzz_ctx** out)
       (void)hipGetLastError();
     }
   }
-  // tuning knobs for A/B measurements (defaults are the measured best)
-  if (const char* e = getenv("ZZZ_SPMV_VARIANT"))
-  {
-    ctx->spmv_variant = atoi(e) & 27;
-    ctx->spmv_auto = false;
-  }
-  if (const char* e = getenv("ZZZ_SELLP")) // operator stream: 0 off, 1 automatic, 2 natural row order, 3 sorted rows
-  {
-    const int v = atoi(e);
-    ctx->sellp_mode = v >= 0 && v <= 4 ? v : 1; // (4: natural row order through the long-row packer whatever the row lengths: tests)
-    ctx->sellp_long_rows = v == 4;
-    if (v == 4)
-      ctx->sellp_mode = 2;
-  }
-  if (const char* e = getenv("ZZZ_SELLP_DROP"))
-    ctx->sellp_drop = atoi(e) != 0;
-  if (const char* e = getenv("ZZZ_SELLP_DICT"))
-    ctx->sellp_dict = atoi(e);
-  if (const char* e = getenv("ZZZ_SELLP_BWIN")) // long scalar rows, x from LDS windows: 0 never, 1 by size, 2 always
-    ctx->sellp_bwin = atoi(e);
-  if (const char* e = getenv("ZZZ_SELLP_EARLY")) // 0: generic stream at every assembly, special forms at the first product (A/B)
-    ctx->sellp_early = atoi(e) != 0;
-  if (const char* e = getenv("ZZZ_ASM_NODE3")) // 0: elasticity P1 matrix assembly with a thread per scalar row (A/B)
-    ctx->asm_node3 = atoi(e) != 0;
-  if (const char* e = getenv("ZZZ_SELLP_BLK")) // 0: block size 3 stays on the generic product (A/B against the block-row form)
-    ctx->sellp_blk = atoi(e);
-  if (const char* e = getenv("ZZZ_SELLP_PIPE")) // 0: the generic product kernel always (A/B against the pipelined one)
-    ctx->sellp_pipe = atoi(e);
-  if (const char* e = getenv("ZZZ_SELLP_PAL")) // 0: the one-chunk product reads 16-bit value codes everywhere (A/B against the packed form)
-    ctx->sellp_pal = atoi(e) != 0;
-  if (const char* e = getenv("ZZZ_CG_DINV_CODES"))
-    ctx->cg_dinv_codes = atoi(e);
-  if (const char* e = getenv("ZZZ_CG_XDEFER")) // the classical CG's solution update once per K iterations: 0 never, 1 by size, 2 always
-    ctx->cg_xdefer = atoi(e);
-  if (const char* e = getenv("ZZZ_CG_XDEFER_K"))
-  {
-    const int v = atoi(e);
-    if (v == 2 || v == 4 || v == 8)
-      ctx->cg_xdefer_k = v;
-  }
-  if (const char* e = getenv("ZZZ_SELLP_FORMS")) // A/B knob, a mask of the code-free chunk forms (default 7): 1 affine chunks
-  {                                              // (column = slot base + lane), 2 one-chunk slices placed by column so that
-    const int v = atoi(e);                       // short boundary rows fit the affine form, 4 periodic chunks (block size 3)
-    if (!(v & 1))
-      ctx->sellp_tail |= 2;
-    ctx->sellp_align = (v & 2) != 0;
-    ctx->sellp_periodic = (v & 4) != 0;
-  }
-  if (const char* e = getenv("ZZZ_SPMV_LPR")) // lanes per row of the SpMV row phase: 1, 2, 4, 8, 16
-  {
-    const int v = atoi(e);
-    for (int sft = 0; sft <= 4; ++sft)
-      if (v == (1 << sft))
-        ctx->spmv_lpr_forced = sft;
-  }
-  if (const char* e = getenv("ZZZ_COLS16")) // 0: keep the SpMV on the int32 columns; 10..13: force the offset width
-  {
-    const int v = atoi(e);
-    ctx->cols16_enabled = v != 0;
-    if (v >= 10 && v <= 13)
-      ctx->cols16_offb_forced = v;
-  }
-  if (const char* e = getenv("ZZZ_OVERLAP"))
-    ctx->overlap = atoi(e) != 0;
-  if (const char* e = getenv("ZZZ_CG_PIPE_STREAM")) // 0: the all-reduce of the pipelined CG stays on the main stream (A/B against its own stream)
-    ctx->pipe_stream = atoi(e) != 0;
+  read_knobs(ctx->knob);
+  ctx->spmv_auto = ctx->knob.spmv_variant < 0;
+  if (!ctx->spmv_auto)
+    ctx->spmv_variant = ctx->knob.spmv_variant;
   *out = ctx;
   return ZZZ_OK;
 }
@@ -329,28 +368,12 @@ int zzz_mesh_upload(zzz_ctx* ctx, int64_t nverts, const double* x, int64_t ncell
   for (int64_t i = 0; i < 4 * ncells; ++i)
     if (cell_verts[i] < 0 || cell_verts[i] >= nverts)
       return fail(ctx, ZZZ_ERR_ARG, "cell_verts[%lld] = %d out of range", (long long)i, cell_verts[i]);
+  forget_mesh(ctx); // the next zzz_dofmap_upload sets the dofmap and everything behind it up again
   ctx->cube_feed = false; // (ZZZ_PC_MG needs a generated cube; a refused call above has not changed the feed)
   ++ctx->feed_version;
   ctx->nverts = nverts;
   ctx->ncells = ncells;
   ctx->h_cell_verts.assign(cell_verts, cell_verts + 4 * ncells);
-  // A new mesh forgets the dofmap and everything behind it: cell_dofs, the internal dof and cell orders, the facet mask, the
-  // Dirichlet set and its values, the coefficients were all laid out cell by cell or dof by dof of the OLD mesh (another cell
-  // count would even be walked past its end).  order == 0 is what every entry point that needs a dofmap tests before it
-  // launches anything; the next zzz_dofmap_upload sets all of this up again.
-  ctx->order = ctx->nd = 0;
-  ctx->h_cell_dofs.clear();
-  renumber_clear(ctx);
-  mg_invalidate(ctx); // (zzz_mg_apply, _transfer, _info and _level_csr serve a ready hierarchy only)
-  ctx->have_bc = false;
-  bc_values_clear(ctx);
-  ctx->have_coeff[0] = ctx->have_coeff[1] = false;
-  ctx->nfacets = 0;
-  ctx->near_null_ld = 0;
-  ctx->adj_runs_n = -1;
-  ctx->have_pattern = ctx->have_matrix = false;
-  ctx->xq_valid = false;
-  ctx->mf.valid = ctx->mf.failed = false;
   int rc = upload(ctx, ctx->x, x, (size_t)(3 * nverts));
   if (rc)
     return rc;
@@ -361,34 +384,20 @@ int zzz_mesh_upload(zzz_ctx* ctx, int64_t nverts, const double* x, int64_t ncell
 // uploaded mesh, else -- a generated mesh has none -- by undoing h_cperm.
 static int restore_cell_verts(zzz_ctx* ctx)
 {
-  if (!ctx->cells_renumbered)
+  if (!ctx->dofmap.cells_renumbered)
     return ZZZ_OK;
   const size_t n = (size_t)(4 * ctx->ncells);
-  int rc;
   if (ctx->h_cell_verts.size() == n)
-    rc = upload(ctx, ctx->cell_verts, ctx->h_cell_verts.data(), n);
-  else
-  {
-    if (ctx->h_cperm.size() != (size_t)ctx->ncells)
-      return fail(ctx, ZZZ_ERR_ARG, "zzz_dofmap_upload: the internal cell order of the mesh is lost: upload or generate the mesh again");
-    std::vector<int32_t> cur(n), orig(n);
-    ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ZZZ_HIP(ctx, hipMemcpy(cur.data(), ctx->cell_verts.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < (size_t)ctx->ncells; ++i)
-      for (int k = 0; k < 4; ++k)
-        orig[4 * (size_t)ctx->h_cperm[i] + k] = cur[4 * i + k];
-    rc = upload(ctx, ctx->cell_verts, orig.data(), n);
-  }
-  if (rc)
-    return rc;
-  // the device's cell order is the caller's again.  The old cell_dofs and facet mask are not in it: the dofmap behind them is
-  // void from here on, whether or not the rest of this upload succeeds
-  ctx->cells_renumbered = false;
-  ctx->h_cperm.clear();
-  ctx->order = ctx->nd = 0;
-  ctx->have_pattern = ctx->have_matrix = false;
-  ctx->mf.valid = ctx->mf.failed = false;
-  return ZZZ_OK;
+    return upload(ctx, ctx->cell_verts, ctx->h_cell_verts.data(), n);
+  if (ctx->h_cperm.size() != (size_t)ctx->ncells)
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_dofmap_upload: the internal cell order of the mesh is lost: upload or generate the mesh again");
+  std::vector<int32_t> cur(n), orig(n);
+  ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  ZZZ_HIP(ctx, hipMemcpy(cur.data(), ctx->cell_verts.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < (size_t)ctx->ncells; ++i)
+    for (int k = 0; k < 4; ++k)
+      orig[4 * (size_t)ctx->h_cperm[i] + k] = cur[4 * i + k];
+  return upload(ctx, ctx->cell_verts, orig.data(), n);
 }
 
 int zzz_dofmap_upload(zzz_ctx* ctx, int order, int bs, const int32_t* cell_dofs, int64_t n_owned, int64_t n_ghost)
@@ -413,11 +422,12 @@ int zzz_dofmap_upload(zzz_ctx* ctx, int order, int bs, const int32_t* cell_dofs,
   // cell_dofs arrive in the caller's -- renumber_build below must see both in the caller's order, as on a fresh context
   if (int rc = restore_cell_verts(ctx))
     return rc;
+  forget_dofmap(ctx); // (the old cell_dofs and facet mask are not in that order: void, whether or not the rest succeeds)
   ctx->cube_feed = false; // (ZZZ_PC_MG needs a generated cube; a refused call above has not changed the feed)
   ++ctx->feed_version;
-  ctx->order = order;
+  ctx->dofmap.order = order;
   ctx->bs = bs;
-  ctx->nd = nd;
+  ctx->dofmap.nd = nd;
   ctx->n_owned = n_owned;
   ctx->n_ghost = n_ghost;
   ctx->h_cell_dofs.assign(cell_dofs, cell_dofs + ctx->ncells * nd);
@@ -427,70 +437,74 @@ int zzz_dofmap_upload(zzz_ctx* ctx, int order, int bs, const int32_t* cell_dofs,
   // facet mask: no exterior facets until uploaded
   ZZZ_HIP(ctx, ctx->facet_mask.alloc((size_t)ctx->ncells));
   ZZZ_HIP(ctx, hipMemsetAsync(ctx->facet_mask.p, 0, (size_t)ctx->ncells, ctx->stream));
-  ctx->nfacets = 0;
   rc = alloc_problem_vectors(ctx);
   if (rc)
     return rc;
-  ctx->have_bc = false;
-  bc_values_clear(ctx);
-  ctx->have_coeff[0] = ctx->have_coeff[1] = false;
-  ctx->have_pattern = ctx->have_matrix = false;
-  ctx->xq_valid = false;
-  ctx->mf.valid = ctx->mf.failed = false;
-  ctx->near_null_ld = 0;
   // the library's own locality order of the owned dofs (zzz_renumber.hip): from here on the device connectivity is in
   // internal numbering and every entry point below translates at the boundary
   rc = renumber_build(ctx);
   if (rc)
     return rc;
-  ctx->adj_runs_n = -1;
   pattern_reserve(ctx);
   return ensure_p1_coords(ctx); // function-space data (dof coordinates), not assembly work
 }
 
-int zzz_bc_upload(zzz_ctx* ctx, int64_t nbc, const int32_t* bc_dofs)
+// the marker bytes of a Dirichlet set in the device's numbering, or why the set is refused
+static int bc_markers(zzz_ctx* ctx, int64_t nbc, const int32_t* bc_dofs, std::vector<uint8_t>& m)
 {
-  ZZZ_ENTER(ctx);
-  bc_values_clear(ctx); // (a new Dirichlet set, or a failed attempt at one: u0 == 0 until values are uploaded for it)
-  if (ctx->order == 0)
+  if (ctx->dofmap.order == 0)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_bc_upload before zzz_dofmap_upload");
   if (nbc < 0 || (nbc > 0 && !bc_dofs))
     return fail(ctx, ZZZ_ERR_ARG, "zzz_bc_upload: bad arguments");
-  std::vector<uint8_t> m((size_t)ctx->nloc(), 0);
+  m.assign((size_t)ctx->nloc(), 0);
   for (int64_t i = 0; i < nbc; ++i)
   {
     if (bc_dofs[i] < 0 || bc_dofs[i] >= ctx->nloc())
       return fail(ctx, ZZZ_ERR_ARG, "bc_dofs[%lld] = %d out of range", (long long)i, bc_dofs[i]);
     int64_t d = bc_dofs[i];
-    if (ctx->renumbered && d / ctx->bs < ctx->n_owned)
+    if (ctx->dofmap.renumbered && d / ctx->bs < ctx->n_owned)
       d = (int64_t)ctx->h_iperm[(size_t)(d / ctx->bs)] * ctx->bs + d % ctx->bs;
     m[(size_t)d] = 1;
   }
+  return ZZZ_OK;
+}
+
+int zzz_bc_upload(zzz_ctx* ctx, int64_t nbc, const int32_t* bc_dofs)
+{
+  ZZZ_ENTER(ctx);
+  std::vector<uint8_t> m;
+  if (int rc = bc_markers(ctx, nbc, bc_dofs, m))
+  {
+    forget_bc_values(ctx); // (the one refused call that changes something: u0 == 0 until values are uploaded again, zzz_abi.h)
+    return rc;
+  }
+  forget_bc(ctx);
   ctx->cube_feed = false; // (ZZZ_PC_MG needs a generated cube; a refused call above has not changed the feed)
   ++ctx->feed_version;
   ZZZ_HIP(ctx, hipMemcpyAsync(ctx->bc.p, m.data(), m.size(), hipMemcpyHostToDevice, ctx->stream));
   ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->have_bc = true;
-  ctx->mf.valid = ctx->mf.failed = false; // the plan of the matrix-free action carries the Dirichlet markers of its dof lists
+  ctx->dirichlet.have_bc = true;
   return ZZZ_OK;
 }
 
 int zzz_bc_values_upload(zzz_ctx* ctx, const double* values)
 {
   ZZZ_ENTER(ctx);
+  // The builder of have_bc_val, which nothing is cached behind: it sets its own flag either way and calls no forget function
+  // (forget_bc_values would count a Dirichlet set in bc_version and have the lifting rows rebuilt; this entry point bumps nothing)
   if (!values) // u0 == 0 again: the vector assembly enqueues what it did before any upload
   {
-    ctx->have_bc_val = false;
+    ctx->dirichlet.have_bc_val = false;
     return ZZZ_OK;
   }
-  if (ctx->order == 0)
+  if (ctx->dofmap.order == 0)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_bc_values_upload before zzz_dofmap_upload / zzz_cube_generate: the values are indexed by local dof");
-  if (!ctx->have_bc)
+  if (!ctx->dirichlet.have_bc)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_bc_values_upload before a Dirichlet set exists (zzz_bc_upload / zzz_cube_generate): the values "
                                   "belong to its dofs");
   const size_t nv = (size_t)ctx->nloc();
   std::vector<double> tmp;
-  if (ctx->renumbered)
+  if (ctx->dofmap.renumbered)
   {
     tmp.resize(nv);
     to_internal(ctx, values, tmp.data(), false);
@@ -501,14 +515,14 @@ int zzz_bc_values_upload(zzz_ctx* ctx, const double* values)
   ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
   // (no feed_version, cube_feed or mat_version here: the matrix does not depend on u0, so a multigrid hierarchy, the
   // Chebyshev bound and the product's special forms stay what they are)
-  ctx->have_bc_val = true;
+  ctx->dirichlet.have_bc_val = true;
   return ZZZ_OK;
 }
 
 int zzz_facets_upload(zzz_ctx* ctx, int64_t nfacets, const int32_t* pairs)
 {
   ZZZ_ENTER(ctx);
-  if (ctx->order == 0)
+  if (ctx->dofmap.order == 0)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_facets_upload before zzz_dofmap_upload");
   if (nfacets < 0 || (nfacets > 0 && !pairs))
     return fail(ctx, ZZZ_ERR_ARG, "zzz_facets_upload: bad arguments");
@@ -522,7 +536,7 @@ int zzz_facets_upload(zzz_ctx* ctx, int64_t nfacets, const int32_t* pairs)
   }
   ctx->cube_feed = false; // (ZZZ_PC_MG needs a generated cube; a refused call above has not changed the feed)
   ++ctx->feed_version;
-  if (ctx->cells_renumbered) // the device holds the cells in the library's order: mask of internal cell i = caller's cperm[i]
+  if (ctx->dofmap.cells_renumbered) // the device holds the cells in the library's order: mask of internal cell i = caller's cperm[i]
   {
     std::vector<uint8_t> mi(m.size());
     for (size_t i = 0; i < m.size(); ++i)
@@ -531,19 +545,19 @@ int zzz_facets_upload(zzz_ctx* ctx, int64_t nfacets, const int32_t* pairs)
   }
   ZZZ_HIP(ctx, hipMemcpyAsync(ctx->facet_mask.p, m.data(), m.size(), hipMemcpyHostToDevice, ctx->stream));
   ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->nfacets = nfacets;
+  ctx->dofmap.nfacets = nfacets;
   return ZZZ_OK;
 }
 
 int zzz_coeff_upload(zzz_ctx* ctx, int which, const double* values)
 {
   ZZZ_ENTER(ctx);
-  if (ctx->order == 0)
+  if (ctx->dofmap.order == 0)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_coeff_upload before zzz_dofmap_upload");
   if ((which != ZZZ_COEFF_F && which != ZZZ_COEFF_G) || !values)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_coeff_upload: bad arguments");
   std::vector<double> tmp;
-  if (ctx->renumbered)
+  if (ctx->dofmap.renumbered)
   {
     // coefficient G is scalar-valued whatever the block size of the space (src/poisson_problem.cpp:96-106): both are
     // stored with nloc * bs entries and Poisson has bs = 1, so one layout serves
@@ -554,7 +568,7 @@ int zzz_coeff_upload(zzz_ctx* ctx, int which, const double* values)
   ZZZ_HIP(ctx, hipMemcpyAsync(ctx->coeff[which].p, values, (size_t)ctx->nloc() * sizeof(double), hipMemcpyHostToDevice,
                               ctx->stream));
   ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->have_coeff[which] = true;
+  ctx->dofmap.have_coeff[which] = true;
   return ZZZ_OK;
 }
 
@@ -563,13 +577,10 @@ static int pattern_build_host(zzz_ctx* ctx);
 int zzz_csr_pattern_build(zzz_ctx* ctx)
 {
   ZZZ_ENTER(ctx);
-  if (ctx->order == 0)
+  if (ctx->dofmap.order == 0)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_csr_pattern_build before zzz_dofmap_upload");
-  ctx->have_pattern = ctx->have_matrix = false;
+  forget_pattern(ctx); // (the operator stream with it: it is packed from the values, after the assembly)
   ++ctx->pattern_version;
-  ctx->bw_on = false;
-  ctx->have_adj_li = false;
-  ctx->have_asm_pos = false;
   ++ctx->mat_version;
   const char* mode = getenv("ZZZ_PATTERN"); // "host": the C++ host builder (kept for meshes whose
                                             // vertex valence exceeds the device kernel's LDS budget)
@@ -590,15 +601,13 @@ int zzz_csr_pattern_build(zzz_ctx* ctx)
     rc = ensure_tables(ctx); // reference tensors of the element: resident before the assembly timers start
   if (rc)
     return rc;
-  ctx->have_sell = ctx->sell_current = ctx->sp_pending = false; // the operator stream is packed from the values: after assembly
-  ctx->sp_bounds_ok = false;
-  if (ctx->sellp_mode != 0)
+  if (ctx->knob.sellp_mode != 0)
   {
     rc = sellp_pattern_bounds(ctx);
     if (rc)
       return rc;
   }
-  ctx->have_pattern = true;
+  ctx->pattern.have_pattern = true;
   return ZZZ_OK;
 }
 
@@ -607,14 +616,14 @@ static int pattern_build_host(zzz_ctx* ctx)
 {
   if (ctx->h_cell_dofs.empty()) // feed was generated on the device
   {
-    ctx->h_cell_dofs.resize((size_t)(ctx->ncells * ctx->nd));
+    ctx->h_cell_dofs.resize((size_t)(ctx->ncells * ctx->dofmap.nd));
     ZZZ_HIP(ctx, hipMemcpy(ctx->h_cell_dofs.data(), ctx->cell_dofs.p, ctx->h_cell_dofs.size() * sizeof(int32_t),
                            hipMemcpyDeviceToHost));
   }
-  const int nd = ctx->nd, bs = ctx->bs;
+  const int nd = ctx->dofmap.nd, bs = ctx->bs;
   const int64_t nb = ctx->n_owned, nc = ctx->ncells;
   std::vector<int32_t> cd_internal;
-  const bool internal = ctx->renumbered || ctx->cells_renumbered;
+  const bool internal = ctx->dofmap.renumbered || ctx->dofmap.cells_renumbered;
   if (internal) // the host copy keeps the caller's dof numbering and cell order (zzz_ghost_layer_build reads it)
   {
     cd_internal.resize((size_t)(nc * nd));
@@ -733,7 +742,7 @@ int zzz_csr_sizes(const zzz_ctx* ctx, int64_t* nrows, int64_t* ncols, int64_t* n
 {
   if (!ctx)
     return fail(nullptr, ZZZ_ERR_ARG, "NULL context");
-  if (!ctx->have_pattern)
+  if (!ctx->pattern.have_pattern)
     return fail(const_cast<zzz_ctx*>(ctx), ZZZ_ERR_ARG, "no sparsity pattern yet");
   if (nrows)
     *nrows = ctx->nrows;
@@ -747,10 +756,10 @@ int zzz_csr_sizes(const zzz_ctx* ctx, int64_t* nrows, int64_t* ncols, int64_t* n
 int zzz_csr_download(zzz_ctx* ctx, int32_t* rowptr, int32_t* cols, double* vals)
 {
   ZZZ_ENTER(ctx);
-  if (!ctx->have_pattern)
+  if (!ctx->pattern.have_pattern)
     return fail(ctx, ZZZ_ERR_ARG, "no sparsity pattern yet");
   ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (ctx->renumbered)
+  if (ctx->dofmap.renumbered)
   {
     if (rowptr && ctx->nnz > INT32_MAX)
       return fail(ctx, ZZZ_ERR_LIMIT, "%lld nonzeros do not fit 32-bit row pointers: use zzz_csr_rowptr64_download",
@@ -779,7 +788,7 @@ int zzz_csr_download(zzz_ctx* ctx, int32_t* rowptr, int32_t* cols, double* vals)
     ZZZ_HIP(ctx, hipMemcpy(cols, ctx->cols.p, (size_t)ctx->nnz * sizeof(int32_t), hipMemcpyDeviceToHost));
   if (vals)
   {
-    if (ctx->have_matrix)
+    if (ctx->values.have_matrix)
       ZZZ_HIP(ctx, hipMemcpy(vals, ctx->vals.p, (size_t)ctx->nnz * sizeof(double), hipMemcpyDeviceToHost));
     else // a created, not yet assembled matrix is zero (the device array is written whole by the first assembly)
       memset(vals, 0, (size_t)ctx->nnz * sizeof(double));
@@ -790,10 +799,10 @@ int zzz_csr_download(zzz_ctx* ctx, int32_t* rowptr, int32_t* cols, double* vals)
 int zzz_csr_rowptr64_download(zzz_ctx* ctx, int64_t* rowptr)
 {
   ZZZ_ENTER(ctx);
-  if (!ctx->have_pattern || !rowptr)
+  if (!ctx->pattern.have_pattern || !rowptr)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_csr_rowptr64_download: no sparsity pattern yet / NULL array");
   ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (ctx->renumbered)
+  if (ctx->dofmap.renumbered)
   {
     std::vector<rp_t> rpc;
     if (int rc = csr_to_caller(ctx, rpc, nullptr, nullptr, false))
@@ -808,11 +817,10 @@ int zzz_csr_rowptr64_download(zzz_ctx* ctx, int64_t* rowptr)
 int zzz_csr_upload_values(zzz_ctx* ctx, const double* vals)
 {
   ZZZ_ENTER(ctx);
-  if (!ctx->have_pattern || !vals)
+  if (!ctx->pattern.have_pattern || !vals)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_csr_upload_values: no pattern or NULL values");
-  ++ctx->mat_version;
   std::vector<double> vi;
-  if (ctx->renumbered)
+  if (ctx->dofmap.renumbered)
   {
     ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (int rc = csr_values_to_internal(ctx, vals, vi))
@@ -821,47 +829,40 @@ int zzz_csr_upload_values(zzz_ctx* ctx, const double* vals)
   }
   ZZZ_HIP(ctx, hipMemcpyAsync(ctx->vals.p, vals, (size_t)ctx->nnz * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the staging copy above may be a local
-  ctx->sp_rownnz_fresh = ctx->sp_compact_fresh = false; // what an assembly left belongs to the values just replaced
-  int rc = sell_update(ctx, false);
-  if (rc)
+  if (int rc = ctx_adopt_values(ctx))
     return rc;
   ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->have_matrix = true;
   return ZZZ_OK;
 }
 
 int zzz_assemble_matrix(zzz_ctx* ctx, int form)
 {
   ZZZ_ENTER(ctx);
-  if (ctx->order == 0)
+  if (ctx->dofmap.order == 0)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_assemble_matrix before zzz_dofmap_upload");
-  if (!ctx->have_pattern)
+  if (!ctx->pattern.have_pattern)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_assemble_matrix before zzz_csr_pattern_build");
   if (form != ZZZ_FORM_POISSON && form != ZZZ_FORM_ELASTICITY)
     return fail(ctx, ZZZ_ERR_ARG, "unknown form %d", form);
-  int rc = launch_assemble_matrix(ctx, form);
-  if (!rc)
-    rc = sell_update(ctx, false); // MatAssemblyEnd-like finalisation: refresh the SpMV copy
-  ctx->sp_rownnz_fresh = ctx->sp_compact_fresh = false; // (whether or not this packing path had a use for them)
-  if (!rc)
-    ctx->have_matrix = true;
-  return rc;
+  if (int rc = launch_assemble_matrix(ctx, form))
+    return rc;
+  return ctx_adopt_values(ctx, true);
 }
 
 int zzz_assemble_vector(zzz_ctx* ctx, int form)
 {
   ZZZ_ENTER(ctx);
-  if (ctx->order == 0)
+  if (ctx->dofmap.order == 0)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_assemble_vector before zzz_dofmap_upload");
-  if (!ctx->have_pattern)
+  if (!ctx->pattern.have_pattern)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_assemble_vector before zzz_csr_pattern_build");
   if (form != ZZZ_FORM_POISSON && form != ZZZ_FORM_ELASTICITY)
     return fail(ctx, ZZZ_ERR_ARG, "unknown form %d", form);
-  if (!ctx->have_coeff[ZZZ_COEFF_F] || (form == ZZZ_FORM_POISSON && !ctx->have_coeff[ZZZ_COEFF_G]))
+  if (!ctx->dofmap.have_coeff[ZZZ_COEFF_F] || (form == ZZZ_FORM_POISSON && !ctx->dofmap.have_coeff[ZZZ_COEFF_G]))
     return fail(ctx, ZZZ_ERR_ARG, "coefficient(s) of L not uploaded");
   if (int rc = launch_assemble_vector(ctx, form))
     return rc;
-  return ctx->have_bc_val ? launch_lift(ctx) : ZZZ_OK; // apply_lifting and bc->set with u0 != 0: a pass of its own
+  return ctx->dirichlet.have_bc_val ? launch_lift(ctx) : ZZZ_OK; // apply_lifting and bc->set with u0 != 0: a pass of its own
 }
 
 static zzz::DevBuf<double>* pick_vec(zzz_ctx* ctx, int which)
@@ -876,7 +877,7 @@ int zzz_vec_download(zzz_ctx* ctx, int which, double* out)
   if (!v || !v->p || !out)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_vec_download: bad vector / not allocated");
   ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (ctx->renumbered)
+  if (ctx->dofmap.renumbered)
   {
     std::vector<double> tmp((size_t)(ctx->n_owned * ctx->bs));
     ZZZ_HIP(ctx, hipMemcpy(tmp.data(), v->p, tmp.size() * sizeof(double), hipMemcpyDeviceToHost));
@@ -894,7 +895,7 @@ int zzz_vec_upload(zzz_ctx* ctx, int which, const double* in)
   if (!v || !v->p || !in)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_vec_upload: bad vector / not allocated");
   std::vector<double> tmp;
-  if (ctx->renumbered)
+  if (ctx->dofmap.renumbered)
   {
     tmp.resize((size_t)(ctx->n_owned * ctx->bs));
     to_internal(ctx, in, tmp.data(), true);
@@ -918,11 +919,11 @@ int zzz_vec_norm(zzz_ctx* ctx, int which, double* out)
 int zzz_spmv(zzz_ctx* ctx, const double* x, double* y)
 {
   ZZZ_ENTER(ctx);
-  if (!ctx->have_matrix || !x || !y)
+  if (!ctx->values.have_matrix || !x || !y)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_spmv: no matrix or NULL vector");
   const size_t n = (size_t)(ctx->n_owned * ctx->bs);
   std::vector<double> xin;
-  if (ctx->renumbered)
+  if (ctx->dofmap.renumbered)
   {
     xin.resize(n);
     to_internal(ctx, x, xin.data(), true);
@@ -933,7 +934,7 @@ int zzz_spmv(zzz_ctx* ctx, const double* x, double* y)
   ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (int rc = launch_product(ctx, ctx->p.p, ctx->w.p, nullptr, nullptr))
     return rc;
-  if (ctx->renumbered)
+  if (ctx->dofmap.renumbered)
   {
     ZZZ_HIP(ctx, hipMemcpyAsync(xin.data(), ctx->w.p, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -948,7 +949,7 @@ int zzz_spmv(zzz_ctx* ctx, const double* x, double* y)
 int zzz_spmv_time(zzz_ctx* ctx, int reps, int variant, double* avg_ms)
 {
   ZZZ_ENTER(ctx);
-  if (!ctx->have_matrix || reps < 1 || !avg_ms)
+  if (!ctx->values.have_matrix || reps < 1 || !avg_ms)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_spmv_time: no matrix or bad arguments");
   const int saved = ctx->spmv_variant;
   const bool saved_auto = ctx->spmv_auto;
@@ -981,11 +982,11 @@ int zzz_spmv_time(zzz_ctx* ctx, int reps, int variant, double* avg_ms)
 int zzz_action(zzz_ctx* ctx, const double* x, double* y)
 {
   ZZZ_ENTER(ctx);
-  if (ctx->order == 0 || !x || !y)
+  if (ctx->dofmap.order == 0 || !x || !y)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_action: no dofmap or NULL vector");
   const size_t n = (size_t)(ctx->n_owned * ctx->bs);
   std::vector<double> xin;
-  if (ctx->renumbered)
+  if (ctx->dofmap.renumbered)
   {
     xin.resize(n);
     to_internal(ctx, x, xin.data(), true);
@@ -1003,7 +1004,7 @@ int zzz_action(zzz_ctx* ctx, const double* x, double* y)
   int rc = launch_matfree_action(ctx, ctx->p.p, ctx->w.p, nullptr, nullptr);
   if (rc)
     return rc;
-  if (ctx->renumbered)
+  if (ctx->dofmap.renumbered)
   {
     ZZZ_HIP(ctx, hipMemcpyAsync(xin.data(), ctx->w.p, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1024,16 +1025,16 @@ int zzz_matfree_setup(zzz_ctx* ctx)
 int zzz_matfree_diagonal(zzz_ctx* ctx, double* diag)
 {
   ZZZ_ENTER(ctx);
-  if (ctx->order == 0 || !diag)
+  if (ctx->dofmap.order == 0 || !diag)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_matfree_diagonal: no dofmap or NULL vector");
   if (int rc = launch_matfree_diagonal(ctx, ctx->w.p))
     return rc;
   const size_t n = (size_t)(ctx->n_owned * ctx->bs);
-  std::vector<double> tmp(ctx->renumbered ? n : 0);
-  double* dst = ctx->renumbered ? tmp.data() : diag;
+  std::vector<double> tmp(ctx->dofmap.renumbered ? n : 0);
+  double* dst = ctx->dofmap.renumbered ? tmp.data() : diag;
   ZZZ_HIP(ctx, hipMemcpyAsync(dst, ctx->w.p, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (ctx->renumbered)
+  if (ctx->dofmap.renumbered)
     to_caller(ctx, tmp.data(), diag, true);
   return ZZZ_OK;
 }
@@ -1041,11 +1042,11 @@ int zzz_matfree_diagonal(zzz_ctx* ctx, double* diag)
 int zzz_matfree_assemble_vector(zzz_ctx* ctx, int form)
 {
   ZZZ_ENTER(ctx);
-  if (ctx->order == 0)
+  if (ctx->dofmap.order == 0)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_matfree_assemble_vector before zzz_dofmap_upload");
   if (form != ZZZ_FORM_POISSON && form != ZZZ_FORM_ELASTICITY)
     return fail(ctx, ZZZ_ERR_ARG, "unknown form %d", form);
-  if (!ctx->have_coeff[ZZZ_COEFF_F] || (form == ZZZ_FORM_POISSON && !ctx->have_coeff[ZZZ_COEFF_G]))
+  if (!ctx->dofmap.have_coeff[ZZZ_COEFF_F] || (form == ZZZ_FORM_POISSON && !ctx->dofmap.have_coeff[ZZZ_COEFF_G]))
     return fail(ctx, ZZZ_ERR_ARG, "coefficient(s) of L not uploaded");
   const int bs = form == ZZZ_FORM_ELASTICITY ? 3 : 1;
   if (bs != ctx->bs)
@@ -1092,7 +1093,7 @@ int zzz_matfree_info(zzz_ctx* ctx, int64_t info[8])
 int zzz_action_time(zzz_ctx* ctx, int reps, double* avg_ms)
 {
   ZZZ_ENTER(ctx);
-  if (reps <= 0 || !avg_ms || ctx->order == 0)
+  if (reps <= 0 || !avg_ms || ctx->dofmap.order == 0)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_action_time: bad arguments");
   hipEvent_t e0, e1;
   ZZZ_HIP(ctx, hipEventCreate(&e0));
@@ -1118,11 +1119,11 @@ int zzz_cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rno
   ZZZ_ENTER(ctx);
   if (!o)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_cg_solve: NULL options");
-  if (o->op == ZZZ_OP_CSR && !ctx->have_matrix)
+  if (o->op == ZZZ_OP_CSR && !ctx->values.have_matrix)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_cg_solve: matrix not assembled");
   if (o->op != ZZZ_OP_CSR && o->op != ZZZ_OP_MATFREE)
     return fail(ctx, ZZZ_ERR_ARG, "unknown operator kind %d", o->op);
-  if (o->op == ZZZ_OP_MATFREE && ctx->order == 0) // (before the solve writes its initial guess)
+  if (o->op == ZZZ_OP_MATFREE && ctx->dofmap.order == 0) // (before the solve writes its initial guess)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_cg_solve: the matrix-free operator before zzz_dofmap_upload");
   if (o->variant != ZZZ_CG_PETSC && o->variant != ZZZ_CG_CGH && o->variant != ZZZ_CG_PIPE)
     return fail(ctx, ZZZ_ERR_ARG, "unknown CG variant %d", o->variant);
@@ -1159,7 +1160,7 @@ int zzz_cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rno
 // what the float path does not serve, said once for its entry points (null: it applies)
 static const char* f32_declined(const zzz_ctx* ctx)
 {
-  if (ctx->order == 0)
+  if (ctx->dofmap.order == 0)
     return "no dofmap";
   if (ctx->bs != 1)
     return "block size 3: the float32 path exists for the Poisson form M only (src/Poisson.py:33), not for elasticity";
@@ -1177,7 +1178,7 @@ int zzz_action_f32(zzz_ctx* ctx, const float* x, float* y)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_action_f32: %s", why);
   const size_t n = (size_t)ctx->n_owned, nl = (size_t)ctx->nloc();
   std::vector<float> tmp;
-  if (ctx->renumbered)
+  if (ctx->dofmap.renumbered)
   {
     tmp.resize(n);
     for (size_t i = 0; i < n; ++i)
@@ -1191,10 +1192,10 @@ int zzz_action_f32(zzz_ctx* ctx, const float* x, float* y)
   ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (int rc = mf_action_f32(ctx, ctx->f32_p.p, ctx->f32_y.p, nullptr, nullptr))
     return rc;
-  float* dst = ctx->renumbered ? tmp.data() : y;
+  float* dst = ctx->dofmap.renumbered ? tmp.data() : y;
   ZZZ_HIP(ctx, hipMemcpyAsync(dst, ctx->f32_y.p, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
   ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (ctx->renumbered)
+  if (ctx->dofmap.renumbered)
     for (size_t i = 0; i < n; ++i)
       y[ctx->h_perm[i]] = tmp[i];
   return ZZZ_OK;
@@ -1254,7 +1255,7 @@ int zzz_cg_solve_f32(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double*
     return fail(ctx, ZZZ_ERR_ARG, "zzz_cg_solve_f32: -ksp_cg_single_reduction (single_reduction) applies to KSPCG on the assembled operator only");
   if (const char* why = f32_declined(ctx))
     return fail(ctx, ZZZ_ERR_ARG, "zzz_cg_solve_f32: %s", why);
-  if (ctx->have_bc_val)
+  if (ctx->dirichlet.have_bc_val)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_cg_solve_f32: Dirichlet values were uploaded (zzz_bc_values_upload): the lifted right-hand side is "
                                   "not formed in float32 yet");
   if (o->max_it < 0 || o->max_it > (1 << 24))
@@ -1276,7 +1277,7 @@ int zzz_cg_history(zzz_ctx* ctx, int n, double* out)
 int zzz_spmv_info(zzz_ctx* ctx, int64_t info[8])
 {
   ZZZ_ENTER(ctx);
-  if (!info || !ctx->have_pattern)
+  if (!info || !ctx->pattern.have_pattern)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_spmv_info: no pattern");
   // the packed column stream of the tile kernel is encoded on first use OF THAT KERNEL: a matrix whose product runs on
   // the operator stream never pays for it (several hundred MB at the c4 / c5_rank sizes); info[0..2] then describe a
@@ -1284,28 +1285,28 @@ int zzz_spmv_info(zzz_ctx* ctx, int64_t info[8])
   if (!sellp_active(ctx))
     if (int rc = ensure_cols16(ctx))
       return rc;
-  info[0] = ctx->have_cols16 ? 1 : 0;
+  info[0] = ctx->pattern.have_cols16 ? 1 : 0;
   info[1] = ctx->cols16_offb;
-  info[2] = ctx->have_cols16 ? ctx->cols16_fallback_tiles : ctx->ntiles;
+  info[2] = ctx->pattern.have_cols16 ? ctx->cols16_fallback_tiles : ctx->ntiles;
   info[3] = ctx->ntiles;
-  if (sellp_active(ctx) && ctx->sp_win_max > 0)
+  if (sellp_active(ctx) && ctx->values.sp_win_max > 0)
   {
     // x windows of the operator stream (no tile kernel in use then): bytes of x the product loads into LDS per launch
     // in place of per-entry gathers, and the LDS doubles a workgroup holds
-    info[2] = ctx->sp_win_bytes;
-    info[3] = -(int64_t)ctx->sp_win_max;
+    info[2] = ctx->values.sp_win_bytes;
+    info[3] = -(int64_t)ctx->values.sp_win_max;
   }
   info[4] = sellp_active(ctx) ? 1 : (int64_t)1 << ctx->spmv_lpr_shift; // the stream sums a row serially
   info[5] = sellp_active(ctx) ? (ctx->sp_sorted ? 2 : 1) : 0;
   info[6] = sellp_active(ctx) ? sellp_stream_bytes(ctx) : 0; // bytes of the operator stream read per product
-  info[7] = sellp_active(ctx) ? ctx->sp_chunks * 512 : 0;     // its entries, padding included
+  info[7] = sellp_active(ctx) ? ctx->values.sp_chunks * 512 : 0;     // its entries, padding included
   return ZZZ_OK;
 }
 
 int zzz_spmv_values_info2(zzz_ctx* ctx, int n, int64_t* out)
 {
   ZZZ_ENTER(ctx);
-  if (!out || n < 0 || !ctx->have_pattern)
+  if (!out || n < 0 || !ctx->pattern.have_pattern)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_spmv_values_info: no pattern");
   int64_t info[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   if (sellp_active(ctx))
@@ -1313,10 +1314,10 @@ int zzz_spmv_values_info2(zzz_ctx* ctx, int n, int64_t* out)
     const bool blk = zzz::sellp_blk_serves(ctx);
     info[4] = !blk && zzz::sellp_pipe_wgs(ctx, false) ? 1 : 0;
     info[5] = blk ? 1 : (info[4] ? zzz::sellp_pipe_wgs(ctx, false) : 8);
-    info[0] = ctx->sp_sd_on ? 3 : (ctx->sp_dict_on ? (ctx->sp_dict_n <= zzz::SP_DICT_LDS_ENTRIES ? 2 : 1) : 0);
-    info[1] = ctx->sp_dict_on ? ctx->sp_dict_n : 0;
+    info[0] = ctx->values.sp_sd_on ? 3 : (ctx->values.sp_dict_on ? (ctx->sp_dict_n <= zzz::SP_DICT_LDS_ENTRIES ? 2 : 1) : 0);
+    info[1] = ctx->values.sp_dict_on ? ctx->sp_dict_n : 0;
     info[2] = sellp_stream_bytes(ctx);
-    info[3] = ctx->sp_bytes + ctx->nslices * 8;
+    info[3] = ctx->values.sp_bytes + ctx->nslices * 8;
     const bool win = zzz::sellp_win_serves(ctx);
     info[6] = blk ? 1 : (win ? 2 : 0);
     info[7] = blk ? ctx->bk_entries : (win ? ctx->bw_window_entries : 0);
@@ -1326,7 +1327,7 @@ int zzz_spmv_values_info2(zzz_ctx* ctx, int n, int64_t* out)
       info[4] = 0, info[5] = 1;
     // the packed form of the one-chunk kernel's value codes (k_sp_pal_build): slices packed / read as 16-bit codes, pairs of
     // one of either, the largest number of distinct codes met in a (slice, slot)
-    if (info[4] && ctx->sp_pal_on)
+    if (info[4] && ctx->values.sp_pal_on)
     {
       info[10] = ctx->sp_pal_packed;
       info[11] = ctx->nslices - ctx->sp_pal_packed;
@@ -1336,7 +1337,7 @@ int zzz_spmv_values_info2(zzz_ctx* ctx, int n, int64_t* out)
     else if (info[4])
     {
       info[11] = ctx->nslices;
-      info[13] = ctx->sellp_pal ? ctx->sp_pal_maxcount : 0;
+      info[13] = ctx->knob.sellp_pal ? ctx->sp_pal_maxcount : 0;
     }
   }
   for (int i = 0; i < std::min(n, 14); ++i)
@@ -1350,13 +1351,13 @@ int zzz_abi_version(void) { return ZZZ_ABI_VERSION; }
 
 int zzz_internal_order_download(zzz_ctx* ctx, int32_t* perm, int32_t* kind)
 {
-  if (!ctx || ctx->order == 0)
+  if (!ctx || ctx->dofmap.order == 0)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_internal_order_download: no dofmap yet");
   if (perm)
     for (int64_t i = 0; i < ctx->n_owned; ++i)
-      perm[i] = ctx->renumbered ? ctx->h_perm[(size_t)i] : (int32_t)i;
+      perm[i] = ctx->dofmap.renumbered ? ctx->h_perm[(size_t)i] : (int32_t)i;
   if (kind)
-    *kind = (ctx->renumbered ? ctx->renumber_kind : 0) | (ctx->cells_renumbered ? 16 : 0);
+    *kind = (ctx->dofmap.renumbered ? ctx->dofmap.renumber_kind : 0) | (ctx->dofmap.cells_renumbered ? 16 : 0);
   return ZZZ_OK;
 }
 

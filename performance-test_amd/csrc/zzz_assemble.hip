@@ -753,7 +753,7 @@ __global__ void k_dof_coords(const double* __restrict__ x, const int32_t* __rest
 
 int ensure_p1_coords(zzz_ctx* ctx)
 {
-  if (ctx->xq_valid || ctx->order != 1 || ctx->ncells == 0 || !ctx->cell_dofs.p || !ctx->cell_verts.p)
+  if (ctx->dofmap.xq_valid || ctx->dofmap.order != 1 || ctx->ncells == 0 || !ctx->cell_dofs.p || !ctx->cell_verts.p)
     return ZZZ_OK;
   const int64_t n = 4 * ctx->ncells, nblock = ctx->n_owned + ctx->n_ghost;
   const int g = (int)std::min<int64_t>((n + 255) / 256, 8192);
@@ -774,29 +774,29 @@ int ensure_p1_coords(zzz_ctx* ctx)
     ZZZ_HIP(ctx, hipGetLastError());
     ctx->xq = ctx->xdof.p;
   }
-  ctx->xq_valid = true;
+  ctx->dofmap.xq_valid = true;
   return ZZZ_OK;
 }
 
 int ensure_tables(zzz_ctx* ctx)
 {
-  if (ctx->tables_order == ctx->order)
+  if (ctx->tables_order == ctx->dofmap.order)
     return ZZZ_OK;
-  const double* src = ctx->order == 1 ? ZZZ_TAB_P1 : (ctx->order == 2 ? ZZZ_TAB_P2 : ZZZ_TAB_P3);
-  const size_t n = (size_t)14 * ctx->nd * ctx->nd;
+  const double* src = ctx->dofmap.order == 1 ? ZZZ_TAB_P1 : (ctx->dofmap.order == 2 ? ZZZ_TAB_P2 : ZZZ_TAB_P3);
+  const size_t n = (size_t)14 * ctx->dofmap.nd * ctx->dofmap.nd;
   ZZZ_HIP(ctx, ctx->tables.alloc(n));
   ZZZ_HIP(ctx, hipMemcpy(ctx->tables.p, src, n * sizeof(double), hipMemcpyHostToDevice));
-  ctx->tables_order = ctx->order;
+  ctx->tables_order = ctx->dofmap.order;
   return ZZZ_OK;
 }
 
 int asm_tile_nnz(const zzz_ctx* ctx)
 {
-  if (ctx->bs == 1 && ctx->order == 1)
+  if (ctx->bs == 1 && ctx->dofmap.order == 1)
     return ASM_NNZ_P1;
-  if (ctx->bs == 3 && ctx->order == 1 && ctx->asm_node3)
+  if (ctx->bs == 3 && ctx->dofmap.order == 1 && ctx->knob.asm_node3)
     return ASM_NNZ_NODE3; // (one thread per node: asm_matrix_p1_node3)
-  if (ctx->have_asm_pos)
+  if (ctx->pattern.have_asm_pos)
   {
     // position-based kernel (asm_matrix_pk_pos: no columns in LDS, persistent workgroups): smaller tiles = more
     // workgroups per CU.  Measured (tools/ab_asm.sh): Poisson P3 6.2 M dofs 2.80 ms at 2048 against 4.79 at 4096 and 3.30
@@ -804,9 +804,9 @@ int asm_tile_nnz(const zzz_ctx* ctx)
     // vertex has ~2000 entries)
     if (ctx->bs == 1)
       return ASM_NNZ_SMALL;
-    return ctx->order == 2 ? 3072 : ASM_NNZ;
+    return ctx->dofmap.order == 2 ? 3072 : ASM_NNZ;
   }
-  return (ctx->bs == 1 && ctx->order == 2) ? ASM_NNZ_SMALL : ASM_NNZ;
+  return (ctx->bs == 1 && ctx->dofmap.order == 2) ? ASM_NNZ_SMALL : ASM_NNZ;
 }
 
 // Geometry factors of every cell, once per assembly (one thread per cell, dense): BS = 1: |detJ| (K K^T), the six
@@ -1086,7 +1086,7 @@ static int launch_matrix_pk_pos(zzz_ctx* ctx)
   const int64_t grid = std::min<int64_t>(xcd_grid(ctx->n_asm_tiles), 256 * (int64_t)per_cu);
   // the non-zero count per row, for the packer of the operator stream (zzz_sellp.hip: sp_build_sorted)
   int32_t* rownnz = nullptr;
-  if (ctx->sellp_mode != 0 && ctx->sellp_drop && ctx->sp_rownnz.alloc((size_t)ctx->nrows + 1) == hipSuccess)
+  if (ctx->knob.sellp_mode != 0 && ctx->knob.sellp_drop && ctx->sp_rownnz.alloc((size_t)ctx->nrows + 1) == hipSuccess)
     rownnz = ctx->sp_rownnz.p;
   (void)hipGetLastError();
   // long rows (the packer's synchronous path): the compacted copy of the kept entries is written from here as well
@@ -1101,8 +1101,8 @@ static int launch_matrix_pk_pos(zzz_ctx* ctx)
                      ctx->adjT_off.p, ctx->adjT_cells.p, ctx->adj_li.p, ctx->adj_off.p, ctx->asm_pos.p, ctx->bc.p,
                      ctx->rowptr.p, ctx->cols.p, ctx->vals.p, ctx->asm_tile.p, ctx->n_asm_tiles, ctx->tables.p, cap, rownnz, crow,
                      ctx->sp_cvals.p, ctx->sp_ccols.p);
-  ctx->sp_rownnz_fresh = rownnz != nullptr;
-  ctx->sp_compact_fresh = crow != nullptr;
+  ctx->values.sp_rownnz_fresh = rownnz != nullptr;
+  ctx->values.sp_compact_fresh = crow != nullptr;
   return ZZZ_OK;
 }
 
@@ -1138,9 +1138,9 @@ static int dispatch_nd_bs(const zzz_ctx* ctx, F&& f)
   auto with_nd = [&](auto nd) -> int {
     return ctx->bs == 1 ? f(nd, std::integral_constant<int, 1>()) : f(nd, std::integral_constant<int, 3>());
   };
-  if (ctx->order == 1)
+  if (ctx->dofmap.order == 1)
     return with_nd(std::integral_constant<int, 4>());
-  if (ctx->order == 2)
+  if (ctx->dofmap.order == 2)
     return with_nd(std::integral_constant<int, 10>());
   return with_nd(std::integral_constant<int, 20>());
 }
@@ -1161,14 +1161,13 @@ constexpr int asm_lpr(AsmKernel k, int nd, int bs) { return ASM_LPR[k][nd == 4 ?
 
 int launch_assemble_matrix(zzz_ctx* ctx, int form)
 {
-  ctx->sp_rownnz_fresh = ctx->sp_compact_fresh = false;
-  ++ctx->mat_version;
   const int bs = form == ZZZ_FORM_ELASTICITY ? 3 : 1;
   if (bs != ctx->bs)
     return fail(ctx, ZZZ_ERR_ARG, "form %d needs block size %d, dofmap has %d", form, bs, ctx->bs);
+  forget_values(ctx); // the old values go from here on: a failure below leaves no matrix (ctx_adopt_values follows a success)
   if (int rc = ensure_p1_coords(ctx))
     return rc;
-  if (ctx->order != 1)
+  if (ctx->dofmap.order != 1)
     if (int rc = ensure_tables(ctx))
       return rc;
   const int rc = dispatch_nd_bs(ctx, [&](auto nd, auto bs_) -> int {
@@ -1182,13 +1181,13 @@ int launch_assemble_matrix(zzz_ctx* ctx, int form)
       };
       if (BS == 1) // one thread per row: a 1920-nonzero tile holds ~126 rows of 15, so 128 threads leave no lane idle
         launch(asm_matrix_p1<1, ASM_NNZ_P1, 128>, 128);
-      else if (ctx->asm_node3)
+      else if (ctx->knob.asm_node3)
         launch(asm_matrix_p1_node3<ASM_NNZ_NODE3>, 64);
       else
         launch(asm_matrix_p1<3, ASM_NNZ, ASM_BLOCK>, ASM_BLOCK);
       return ZZZ_OK;
     }
-    else if (ctx->have_asm_pos) // positions from the pattern build: no column search (asm_matrix_pk_pos)
+    else if (ctx->pattern.have_asm_pos) // positions from the pattern build: no column search (asm_matrix_pk_pos)
       return launch_matrix_pk_pos<ND, BS, asm_lpr(ASM_PK_POS, ND, BS)>(ctx);
     else
       return launch_matrix_pk<ND, BS, asm_lpr(ASM_PK, ND, BS)>(ctx);
@@ -1207,7 +1206,7 @@ int launch_assemble_vector(zzz_ctx* ctx, int form)
   const int64_t nrows = ctx->n_owned * bs;
   if (int rc = ensure_p1_coords(ctx))
     return rc;
-  if (ctx->order != 1)
+  if (ctx->dofmap.order != 1)
     if (int rc = ensure_tables(ctx))
       return rc;
   const int rc = dispatch_nd_bs(ctx, [&](auto nd, auto bs_) -> int {
@@ -1637,7 +1636,7 @@ int build_adjT_offsets(zzz_ctx* ctx)
 {
   const int64_t nrows = ctx->n_owned;
   const int64_t nsl = (nrows + 63) / 64;
-  ctx->have_adj_li = false;
+  ctx->pattern.have_adj_li = false;
   {
     DevBuf<int32_t> slen;
     DevBuf<unsigned char> tmp;
@@ -1668,7 +1667,7 @@ int build_adjT_offsets(zzz_ctx* ctx)
 
 int build_adjT(zzz_ctx* ctx)
 {
-  if (ctx->have_adj_li) // the P1 pattern kernel has written it already
+  if (ctx->pattern.have_adj_li) // the P1 pattern kernel has written it already
     return ZZZ_OK;
   int rc = build_adjT_offsets(ctx);
   if (rc)
@@ -1680,10 +1679,10 @@ int build_adjT(zzz_ctx* ctx)
     if (g1 > 8192)
       g1 = 8192;
     hipLaunchKernelGGL(k_adjT_fill, dim3(g1), dim3(256), 0, ctx->stream, ctx->adj_off.p, ctx->adj_cells.p, ctx->cell_dofs.p,
-                       ctx->nd, nrows, nsl, ctx->adjT_off.p, ctx->adjT_cells.p, ctx->adj_li.p);
+                       ctx->dofmap.nd, nrows, nsl, ctx->adjT_off.p, ctx->adjT_cells.p, ctx->adj_li.p);
     ZZZ_HIP(ctx, hipGetLastError());
     ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->have_adj_li = true;
+    ctx->pattern.have_adj_li = true;
   }
   return ZZZ_OK;
 }
@@ -1698,7 +1697,7 @@ int launch_matfree_action(zzz_ctx* ctx, const double* u, double* y, double* part
   if (!ctx->mf.valid && !ctx->mf.failed)
   {
     const int rc = mf_plan_build(ctx);
-    if (rc == ZZZ_ERR_LIMIT && ctx->bs == 1 && ctx->have_pattern && ctx->have_adj_li)
+    if (rc == ZZZ_ERR_LIMIT && ctx->bs == 1 && ctx->pattern.have_pattern && ctx->pattern.have_adj_li)
       ctx->mf.failed = true; // a mesh the plan cannot hold (a dof in more than 254 cells of one step): the two-pass form serves it
     else if (rc)
       return rc;
@@ -1726,17 +1725,17 @@ int launch_matfree_legacy(zzz_ctx* ctx, const double* u, double* y, double* part
 {
   if (ctx->bs != 1)
     return fail(ctx, ZZZ_ERR_ARG, "the matrix-free operator exists for the Poisson form M only (src/Poisson.py:33)");
-  if (!ctx->have_pattern)
+  if (!ctx->pattern.have_pattern)
     return fail(ctx, ZZZ_ERR_ARG, "matrix-free operator needs zzz_csr_pattern_build (dof->cell adjacency)");
   int rc = ensure_tables(ctx);
   if (rc)
     return rc;
   const int64_t nrows = ctx->n_owned, nc = ctx->ncells;
   const int64_t nsl = (nrows + 63) / 64;
-  if (!ctx->have_adj_li)
+  if (!ctx->pattern.have_adj_li)
     return fail(ctx, ZZZ_ERR_ARG, "transposed adjacency missing (zzz_csr_pattern_build not run)");
-  if (ctx->cell_w.n < (size_t)(nc * ctx->nd))
-    ZZZ_HIP(ctx, ctx->cell_w.alloc((size_t)(nc * ctx->nd)));
+  if (ctx->cell_w.n < (size_t)(nc * ctx->dofmap.nd))
+    ZZZ_HIP(ctx, ctx->cell_w.alloc((size_t)(nc * ctx->dofmap.nd)));
   const int* stop = partials ? reinterpret_cast<const int*>(ctx->state.p) : nullptr;
   int64_t gc = (nc + ASM_BLOCK - 1) / ASM_BLOCK;
   if (gc > 4096)
@@ -1744,9 +1743,9 @@ int launch_matfree_legacy(zzz_ctx* ctx, const double* u, double* y, double* part
 #define ZZZ_MFC(ND_)                                                                                                    \
   hipLaunchKernelGGL(matfree_cell<ND_>, dim3((unsigned)gc), dim3(ASM_BLOCK), 0, ctx->stream, ctx->x.p, ctx->cell_verts.p,  \
                      ctx->cell_dofs.p, nc, u, ctx->cell_w.p, ctx->tables.p, stop)
-  if (ctx->order == 1)
+  if (ctx->dofmap.order == 1)
     ZZZ_MFC(4);
-  else if (ctx->order == 2)
+  else if (ctx->dofmap.order == 2)
     ZZZ_MFC(10);
   else
     ZZZ_MFC(20);

@@ -906,7 +906,7 @@ int dinv_codes_build(zzz_ctx* ctx, int64_t n, DinvCodes& dzc)
   hipLaunchKernelGGL(k_dd_insert, dim3(gd), dim3(256), 0, s, ctx->dinv.p, n, vs.table.p, vs.info.p, DZ_MAX);
   vs.number(s);
   // ZZZ_CG_DINV_CODES=3: 16-bit codes even where 8 would do (the A/B reference of the 8-bit form)
-  const int allow8 = ctx->cg_dinv_codes != 3;
+  const int allow8 = ctx->knob.cg_dinv_codes != 3;
   hipLaunchKernelGGL(k_dd_encode, dim3(gd), dim3(256), 0, s, ctx->dinv.p, n, npad, vs.table.p, vs.slot.p, ctx->dd_codes.p, vs.info.p,
                      allow8);
   int nd = 0;
@@ -1174,7 +1174,7 @@ int cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
   // the Infinity Cache (where bytes are what the vector kernels wait for: the criterion of their load policy;
   // ZZZ_CG_DINV_CODES: 0 never, 2 at any size), at most 2 048 values
   DinvCodes dzc{nullptr, nullptr, nullptr, 0, 0};
-  if (o->variant == ZZZ_CG_PETSC && o->pc == ZZZ_PC_JACOBI && ctx->cg_dinv_codes != 0 && (ctx->cg_dinv_codes >= 2 || nt))
+  if (o->variant == ZZZ_CG_PETSC && o->pc == ZZZ_PC_JACOBI && ctx->knob.cg_dinv_codes != 0 && (ctx->knob.cg_dinv_codes >= 2 || nt))
     if (int rc = dinv_codes_build(ctx, n, dzc))
       return rc;
   ctx->last_solve_dinv_codes = dzc.codes ? dzc.ndict : 0;
@@ -1188,7 +1188,7 @@ int cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
   // slots are allocated at the first solve that uses them and kept.  Owned entries of a slot are written in full by the
   // k_update_p that forms its direction before anything reads them; ghost tail and padding are cleared here, once per solve,
   // as the memset above does for ctx->p.
-  int K = (ctx->cg_xdefer != 0 && (ctx->cg_xdefer == 2 || nt)) ? ctx->cg_xdefer_k : 1;
+  int K = (ctx->knob.cg_xdefer != 0 && (ctx->knob.cg_xdefer == 2 || nt)) ? ctx->knob.cg_xdefer_k : 1;
   PRing ring{};
   ring.slot[0] = ctx->p.p;
   for (int j = 1; j < K; ++j)
@@ -1253,7 +1253,7 @@ int cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
   double* pa = ctx->part_b.p;
   double* pb = ctx->part_b.p + VGRID_MAX;
   // (the matrix-free operator is served by this loop alone: every other form asks for the assembled one)
-  const bool lifted_mf = o->op == ZZZ_OP_MATFREE && ctx->have_bc_val;
+  const bool lifted_mf = o->op == ZZZ_OP_MATFREE && ctx->dirichlet.have_bc_val;
   const double* rhs = ctx->b.p;
   if (lifted_mf)
   {
@@ -1546,7 +1546,7 @@ static int chebyshev_esteig(zzz_ctx* ctx, const zzz_solver_opts* o, int its, dou
     offset += (int64_t)sizes[(size_t)r];
   ZZZ_HIP(ctx, ctx->cheb_noise.alloc(ctx->b.n));
   ZZZ_HIP(ctx, hipMemsetAsync(ctx->cheb_noise.p, 0, sizeof(double) * ctx->cheb_noise.n, ctx->stream));
-  hipLaunchKernelGGL(k_noise, dim3(vgrid(n)), dim3(VB), 0, ctx->stream, ctx->renumbered ? ctx->perm.p : (const int32_t*)nullptr,
+  hipLaunchKernelGGL(k_noise, dim3(vgrid(n)), dim3(VB), 0, ctx->stream, ctx->dofmap.renumbered ? ctx->perm.p : (const int32_t*)nullptr,
                      ctx->bs, offset, n, ctx->cheb_noise.p);
   zzz_solver_opts o2 = *o;
   o2.pc = ZZZ_PC_JACOBI;
@@ -1660,7 +1660,7 @@ static int chebyshev_setup(zzz_ctx* ctx, const zzz_solver_opts* o, ChebPlan& C)
   if (const char* e = getenv("ZZZ_CHEB_FUSED"))
     C.fused = C.fused && atoi(e) != 0;
   // (the overlapped product of a partition without a group split is the tile kernel's, launch_product: no epilogue there)
-  if (multi && ctx->overlap && ctx->have_tile_split && !ctx->have_group_split)
+  if (multi && ctx->knob.overlap && ctx->pattern.have_tile_split && !ctx->pattern.have_group_split)
     C.fused = false;
   ZZZ_HIP(ctx, ctx->cheb_d.alloc((size_t)ctx->nloc())); // ghost entries: the product gathers it
   ZZZ_HIP(ctx, ctx->cheb_d2.alloc((size_t)ctx->nloc()));
@@ -1916,7 +1916,7 @@ static int cg_solve_single_reduction(zzz_ctx* ctx, const zzz_solver_opts* o, int
   // Jacobi's inverse diagonal as 16-bit codes, z of the last iteration recomputed from r (k_sr_update<.., DZ>): under the
   // rule of the classical form (a loop too large for the Infinity Cache; ZZZ_CG_DINV_CODES: 0 never, 2 at any size)
   DinvCodes dzc{nullptr, nullptr, nullptr, 0, 0};
-  if (!cheb && o->pc == ZZZ_PC_JACOBI && ctx->cg_dinv_codes != 0 && (ctx->cg_dinv_codes >= 2 || ntv))
+  if (!cheb && o->pc == ZZZ_PC_JACOBI && ctx->knob.cg_dinv_codes != 0 && (ctx->knob.cg_dinv_codes >= 2 || ntv))
     if (int rc = dinv_codes_build(ctx, n, dzc))
       return rc;
   ctx->last_solve_dinv_codes = dzc.codes ? dzc.ndict : 0;

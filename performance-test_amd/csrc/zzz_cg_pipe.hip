@@ -296,7 +296,7 @@ int cg_solve_pipe(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rn
   // Jacobi's inverse diagonal as 16-bit codes: under the rule of the other forms (a loop too large for the Infinity
   // Cache; ZZZ_CG_DINV_CODES: 0 never, 2 at any size)
   DinvCodes dzc{nullptr, nullptr, nullptr, 0, 0};
-  if (o->pc == ZZZ_PC_JACOBI && ctx->cg_dinv_codes != 0 && (ctx->cg_dinv_codes >= 2 || ntv))
+  if (o->pc == ZZZ_PC_JACOBI && ctx->knob.cg_dinv_codes != 0 && (ctx->knob.cg_dinv_codes >= 2 || ntv))
     if (int rc = dinv_codes_build(ctx, n, dzc))
       return rc;
   ctx->last_solve_dinv_codes = dzc.codes ? dzc.ndict : 0;

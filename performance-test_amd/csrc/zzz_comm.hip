@@ -486,7 +486,7 @@ int comm_reduce_begin(zzz_ctx* ctx, const int* stop, const double* pa, const dou
   if (!ctx->comm)
     return ZZZ_OK;
   const bool second = comm_p2p_enabled(ctx) ? !ctx->comm->p2p->inproc : (!ctx->comm->local && ctx->comm->comm != nullptr);
-  if (!second || !ctx->pipe_stream)
+  if (!second || !ctx->knob.pipe_stream)
     return comm_reduce_allreduce(ctx, stop, pa, pb, pc, np, nv, out);
   if (!ctx->red_stream)
   {
@@ -1027,8 +1027,8 @@ int zzz_comm_info(zzz_ctx* ctx, int64_t info[12])
   if (halo_peer_usable(ctx))
     info[5] = 2; // the halo travels through peer memory (device stores into the neighbour's window), no communicator
   info[6] = comm_p2p_enabled(ctx) ? 1 : 0;                // CG scalars through the peer-memory mailboxes
-  const bool stream_split = sellp_active(ctx) && ctx->have_group_split;
-  info[7] = (ctx->comm && ctx->overlap && (stream_split || ctx->have_tile_split)) ? 1 : 0; // halo overlapped with interior rows
+  const bool stream_split = sellp_active(ctx) && ctx->pattern.have_group_split;
+  info[7] = (ctx->comm && ctx->knob.overlap && (stream_split || ctx->pattern.have_tile_split)) ? 1 : 0; // halo overlapped with interior rows
   info[8] = stream_split ? ctx->n_groups_interior : ctx->n_tiles_interior;
   info[9] = stream_split ? ctx->n_groups_boundary : ctx->n_tiles_boundary;
   info[10] = ctx->comm && ctx->comm->local ? 1 : 0;
@@ -1445,7 +1445,7 @@ int zzz_halo_upload(zzz_ctx* ctx, int nneigh, const int32_t* neigh_rank, const i
   if (!ctx)
     return fail(nullptr, ZZZ_ERR_ARG, "NULL context");
   ZZZ_HIP(ctx, hipSetDevice(ctx->device));
-  if (ctx->order == 0)
+  if (ctx->dofmap.order == 0)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_halo_upload before zzz_dofmap_upload");
   if (nneigh < 0 || (nneigh > 0 && (!neigh_rank || !send_off || !recv_cnt)))
     return fail(ctx, ZZZ_ERR_ARG, "zzz_halo_upload: bad arguments");
@@ -1464,7 +1464,7 @@ int zzz_halo_upload(zzz_ctx* ctx, int nneigh, const int32_t* neigh_rank, const i
     if (send_idx[i] < 0 || send_idx[i] >= ctx->n_owned)
       return fail(ctx, ZZZ_ERR_ARG, "send_idx[%lld] = %d is not an owned block dof", (long long)i, send_idx[i]);
   std::vector<int32_t> send_internal;
-  if (ctx->renumbered && nsend)
+  if (ctx->dofmap.renumbered && nsend)
   {
     send_internal.assign(send_idx, send_idx + nsend);
     for (int32_t& d : send_internal)

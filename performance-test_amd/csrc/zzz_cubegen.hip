@@ -103,16 +103,14 @@ extern "C" int zzz_cube_generate(zzz_ctx* ctx, int problem, int order, int64_t n
     return fail(ctx, ZZZ_ERR_LIMIT, "partition too large for int32 local indexing (%lld scalar dofs, %lld cells): use more parts",
                 (long long)(S.nloc * bs), (long long)S.ncells);
   hipStream_t s = ctx->stream;
+  forget_mesh(ctx); // (no internal order either: this feed is generated in it, host/cube_layout.h)
   ctx->nverts = S.nverts;
   ctx->ncells = S.ncells;
-  ctx->order = order;
+  ctx->dofmap.order = order;
   ctx->bs = bs;
-  ctx->nd = S.nd;
+  ctx->dofmap.nd = S.nd;
   ctx->n_owned = S.n_owned;
   ctx->n_ghost = S.n_lower + S.n_upper;
-  ctx->h_cell_verts.clear();
-  ctx->h_cell_dofs.clear();
-  renumber_clear(ctx); // this feed is generated in the internal order (host/cube_layout.h)
   ZZZ_HIP(ctx, ctx->x.alloc((size_t)(3 * S.nverts)));
   ZZZ_HIP(ctx, ctx->cell_verts.alloc((size_t)(4 * S.ncells)));
   ZZZ_HIP(ctx, ctx->cell_dofs.alloc((size_t)(S.nd * S.ncells)));
@@ -129,16 +127,10 @@ extern "C" int zzz_cube_generate(zzz_ctx* ctx, int problem, int order, int64_t n
                      ctx->coeff[0].p, ctx->coeff[1].p);
   ZZZ_HIP(ctx, hipGetLastError());
   ZZZ_HIP(ctx, hipStreamSynchronize(s));
-  ctx->nfacets = -1; // not counted: the mask is what the kernels read
-  ctx->have_bc = true;
-  bc_values_clear(ctx);
-  ctx->have_coeff[0] = true;
-  ctx->have_coeff[1] = problem == ZZZ_FORM_POISSON;
-  ctx->have_pattern = ctx->have_matrix = false;
-  ctx->xq_valid = false;
-  ctx->mf.valid = ctx->mf.failed = false;
-  ctx->near_null_ld = 0; // (as zzz_dofmap_upload: a basis built for the earlier dofs is not this problem's)
-  ctx->adj_runs_n = -1;
+  ctx->dofmap.nfacets = -1; // not counted: the mask is what the kernels read
+  ctx->dirichlet.have_bc = true;
+  ctx->dofmap.have_coeff[0] = true;
+  ctx->dofmap.have_coeff[1] = problem == ZZZ_FORM_POISSON;
   pattern_reserve(ctx);
   rc = ensure_p1_coords(ctx);
   if (rc)

@@ -90,7 +90,7 @@ int zzz_global_ids_upload(zzz_ctx* ctx, const int64_t* dof_global, const int64_t
 {
   if (!ctx)
     return fail(nullptr, ZZZ_ERR_ARG, "NULL context");
-  if (ctx->order == 0 || !dof_global || !vert_global)
+  if (ctx->dofmap.order == 0 || !dof_global || !vert_global)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_global_ids_upload: upload mesh and dofmap first; NULL array");
   ctx->h_dof_global.assign(dof_global, dof_global + (ctx->n_owned + ctx->n_ghost));
   ctx->h_vert_global.assign(vert_global, vert_global + ctx->nverts);
@@ -118,12 +118,12 @@ int zzz_ghost_layer_build(zzz_ctx* ctx)
   // together, none is left waiting in a send/recv for a peer that has already given up.
   const int64_t n_owned = ctx->n_owned, n_ghost = ctx->n_ghost, nloc = n_owned + n_ghost;
   const int64_t ncells = ctx->ncells, nverts = ctx->nverts;
-  const int nd = ctx->nd, bs = ctx->bs, order = ctx->order;
+  const int nd = ctx->dofmap.nd, bs = ctx->bs, order = ctx->dofmap.order;
   const int nr = comm_size(ctx), me = comm_rank(ctx);
   std::vector<double> x, cf, cg;
   std::vector<int32_t> cverts, cdofs, send_idx;
   std::vector<uint8_t> bc, fmask;
-  const bool haveF = ctx->have_coeff[ZZZ_COEFF_F], haveG = ctx->have_coeff[ZZZ_COEFF_G];
+  const bool haveF = ctx->dofmap.have_coeff[ZZZ_COEFF_F], haveG = ctx->dofmap.have_coeff[ZZZ_COEFF_G];
   const int64_t nsend_old = ctx->nneigh ? ctx->send_off[(size_t)ctx->nneigh] : 0;
   int rc = [&]() -> int {
   if (order == 0 || (int64_t)ctx->h_dof_global.size() != nloc || (int64_t)ctx->h_vert_global.size() != nverts)
@@ -154,14 +154,14 @@ int zzz_ghost_layer_build(zzz_ctx* ctx)
     rc = download(ctx, ctx->coeff[ZZZ_COEFF_G], cg, (size_t)nloc);
   if (!rc)
     rc = download(ctx, ctx->send_idx, send_idx, (size_t)nsend_old);
-  if (!rc && ctx->cells_renumbered)
+  if (!rc && ctx->dofmap.cells_renumbered)
   {
     std::vector<uint8_t> fm2(fmask.size());
     for (int64_t i = 0; i < ncells; ++i)
       fm2[(size_t)ctx->h_cperm[(size_t)i]] = fmask[(size_t)i];
     fmask.swap(fm2);
   }
-  if (!rc && ctx->renumbered)
+  if (!rc && ctx->dofmap.renumbered)
   {
     // the device holds the library's internal numbering of the owned dofs; this function works in the caller's
     // (h_cell_dofs, h_dof_global) and re-uploads through the translating entry points
@@ -194,7 +194,7 @@ int zzz_ghost_layer_build(zzz_ctx* ctx)
   }();
   if ((rc = agree(ctx, rc)))
     return rc;
-  const bool had_bc = ctx->have_bc;
+  const bool had_bc = ctx->dirichlet.have_bc;
   std::vector<int64_t> dof_g = ctx->h_dof_global, vert_g = ctx->h_vert_global;
   std::vector<int32_t> old_neigh = ctx->neigh_rank;
   std::vector<int64_t> old_send_off = ctx->send_off, old_recv = ctx->recv_cnt;

@@ -165,75 +165,66 @@ struct MfPlan
 } // namespace zzz
 
 #include "zzz_valset.h" // (after DevBuf: a set owns four of them)
+#include "zzz_tiers.h"  // the flags of the context's cached state, tier by tier, and its knobs
 
 struct zzz_ctx
 {
   int device = 0;
   hipStream_t stream = nullptr;
   std::string err;
+  zzz::Knobs knob;
+  zzz::DofmapTier dofmap; // the cached state's flags, tier by tier (zzz_tiers.h); each tier's buffers follow under its heading
+  zzz::DirichletTier dirichlet;
+  zzz::PatternTier pattern;
+  zzz::ValuesTier values;
 
-  // mesh
+  // ---- mesh
   int64_t nverts = 0, ncells = 0;
-  zzz::DevBuf<double> x;         // nverts*3
-  // P1: vertex coordinates addressed by BLOCK DOF (ensure_p1_coords): the assembly kernels then read one connectivity
-  // table, not two.  Points at x when the dofmap numbers dofs as the mesh numbers vertices, else at xdof.
-  zzz::DevBuf<double> xdof;
-  const double* xq = nullptr;
-  bool xq_valid = false;
+  zzz::DevBuf<double> x;           // nverts*3
   zzz::DevBuf<int32_t> cell_verts; // ncells*4
   std::vector<int32_t> h_cell_verts;
 
-  // dofmap
-  int order = 0, bs = 0, nd = 0;
+  // ---- dofmap
+  int bs = 0;
   int64_t n_owned = 0, n_ghost = 0; // block dofs
   zzz::DevBuf<int32_t> cell_dofs;   // ncells*nd
   std::vector<int32_t> h_cell_dofs;
   // global indices of the local block dofs / vertices (zzz_global_ids_upload): only the ghost-layer build needs them
   std::vector<int64_t> h_dof_global, h_vert_global;
   int64_t owned_cells = 0; // cells the caller uploaded, when zzz_ghost_layer_build has appended ghost cells
-  // Internal locality numbering of the owned block dofs (zzz_renumber.hip): perm[internal] = caller index,
-  // iperm[caller] = internal index; ghosts keep their places.  Everything on the device (cell_dofs, pattern, CSR,
-  // vectors) is in internal order when `renumbered`; h_cell_dofs, h_dof_global stay in the caller's.
-  bool renumbered = false;
-  int renumber_kind = 0; // 0: not examined / left alone, 1: lattice key, 2: coordinate bins
-  zzz::DevBuf<int32_t> perm, iperm;
-  std::vector<int32_t> h_perm, h_iperm;
+  zzz::DevBuf<int32_t> perm, iperm; // the internal numbering (dofmap.renumbered, dofmap.cells_renumbered)
+  std::vector<int32_t> h_perm, h_iperm, h_cperm;
   std::vector<uint16_t> csr_slot; // caller CSR entry -> position inside its internal row (built on first CSR download)
-  // ... and of the cells (simplex type by simplex type, lattice cube by lattice cube): h_cperm[internal] = caller cell.
-  // cell_verts, cell_dofs and facet_mask on the device are in internal cell order when cells_renumbered.
-  bool cells_renumbered = false;
-  std::vector<int32_t> h_cperm;
-
-  // bc marker per local scalar dof (owned + ghost)
-  zzz::DevBuf<uint8_t> bc;
-  bool have_bc = false;
-  // values of u0 at the constrained dofs (zzz_bc_values_upload): nloc * bs doubles in the device's numbering; only the
-  // entries whose marker is set are ever read.  Cleared by everything that changes the dof layout or the Dirichlet set.
-  zzz::DevBuf<double> bc_val;
-  bool have_bc_val = false;
-  uint64_t bc_version = 0; // counts Dirichlet sets (zzz_dofmap_upload, zzz_bc_upload, zzz_cube_generate)
-  // lifting pass (zzz_assemble.hip: k_lift): the owned unconstrained scalar rows whose pattern row holds a constrained
-  // column, ascending; built by the first lifted assembly of a (pattern, Dirichlet set) pair and kept until either changes
-  zzz::DevBuf<int32_t> lift_rows;
-  zzz::DevBuf<uint8_t> lift_flag; // scratch of the build (kept: a rebuild asks for the same size)
-  int64_t n_lift_rows = 0;
-  uint64_t lift_pattern_version = ~0ull, lift_bc_version = ~0ull;
-  zzz::DevBuf<double> b_masked; // the matrix-free solve's right-hand side with its constrained entries zeroed (zzz_cg.hip)
-
-  // exterior-facet mask per cell (bit f = local facet f is exterior)
-  zzz::DevBuf<uint8_t> facet_mask;
-  int64_t nfacets = 0;
-
-  // reference tensors of the element (element_tables.inc), for orders 2 and 3
+  // P1: vertex coordinates addressed by BLOCK DOF (ensure_p1_coords): the assembly kernels then read one connectivity
+  // table, not two.  Points at x when the dofmap numbers dofs as the mesh numbers vertices, else at xdof.
+  zzz::DevBuf<double> xdof;
+  const double* xq = nullptr;
+  zzz::DevBuf<uint8_t> facet_mask; // exterior-facet mask per cell (bit f = local facet f is exterior)
+  zzz::DevBuf<double> coeff[2];
+  zzz::DevBuf<double> near_null; // the six orthonormalised rigid-body modes (zzz_nullspace.hip), [6][dofmap.near_null_ld]
+  // reference tensors of the element (element_tables.inc), for orders 2 and 3; keyed on their own content
   zzz::DevBuf<double> tables;
   int tables_order = 0;
   std::vector<std::pair<const void*, size_t>> lds_raised; // kernels whose dynamic-LDS limit this context raised, and to what
 
-  // coefficients
-  zzz::DevBuf<double> coeff[2];
-  bool have_coeff[2] = {false, false};
+  // ---- Dirichlet set (bc: marker per local scalar dof, owned + ghost) and its values
+  zzz::DevBuf<uint8_t> bc;
+  // values of u0 at the constrained dofs (zzz_bc_values_upload): nloc * bs doubles in the device's numbering; only the
+  // entries whose marker is set are ever read.  Forgotten by everything that changes the dof layout or the Dirichlet set.
+  zzz::DevBuf<double> bc_val;
+  uint64_t bc_version = 0; // counts Dirichlet sets (zzz_dofmap_upload, zzz_bc_upload, zzz_cube_generate)
+  zzz::DevBuf<double> b_masked; // the matrix-free solve's right-hand side with its constrained entries zeroed (zzz_cg.hip)
+  // ---- dofmap AND Dirichlet set: the plan of the matrix-free action (forgotten by forget_bc, and through it by forget_dofmap)
+  zzz::MfPlan mf;
+  // ---- pattern AND Dirichlet set, keyed on the versions of both: the lifting pass (zzz_assemble.hip: k_lift): the owned
+  // unconstrained scalar rows whose pattern row holds a constrained column, ascending; built by the first lifted assembly of
+  // a (pattern, Dirichlet set) pair and kept until either changes
+  zzz::DevBuf<int32_t> lift_rows;
+  zzz::DevBuf<uint8_t> lift_flag; // scratch of the build (kept: a rebuild asks for the same size)
+  int64_t n_lift_rows = 0;
+  uint64_t lift_pattern_version = ~0ull, lift_bc_version = ~0ull;
 
-  // pattern (owned rows) + adjacency
+  // ---- pattern (owned rows) + adjacency
   int64_t nrows = 0, ncols = 0, nnz = 0;
   zzz::DevBuf<zzz::rp_t> rowptr; // 64-bit: 50 M P3 dofs carry 2.4 G nonzeros on one GPU
   zzz::DevBuf<int32_t> cols;
@@ -244,9 +235,8 @@ struct zzz_ctx
   int scr_cell_of_nd = 0;     // ... of nd dofs per cell
   zzz::DevBuf<int64_t> scr_bptr;
   // monotone runs of the connectivity (zzz_pattern.hip, adjacency without a sort): per run {local dof index k, first
-  // cell, end cell}; found once per dofmap (adj_runs_n: -1 not examined, 0 none usable / too many, else the count)
+  // cell, end cell}; found once per dofmap (dofmap.adj_runs_n)
   zzz::DevBuf<int32_t> adj_runs, adj_run_lo, adj_win_base;
-  int adj_runs_n = -1;
   int32_t* adj_flag_host = nullptr; // pinned: "a window did not fit" travels here behind the build's kernels
   zzz::DevBuf<unsigned char> scr_tmp; // the device primitives' shared scratch: zzz_prim.h alone touches it
   std::vector<void*> retired; // device buffers replaced by larger ones while another context's kernel may be waiting (DevBuf::grow_keep)
@@ -254,11 +244,9 @@ struct zzz_ctx
   zzz::DevBuf<int32_t> adjT_off, adjT_cells; // the same lists transposed in 64-row slices (dense wave reads)
   zzz::DevBuf<uint8_t> adj_li;             // local index of the dof in each of those cells, same layout
   zzz::DevBuf<double> cell_w;              // matrix-free: Ae_c u_c per cell, component-major
-  bool have_adj_li = false;
   // P2/P3: position inside its CSR row of every (adjacency entry, local column) pair -- a by-product of the pattern
   // build's sort (the candidates carry their origin through it), so that the matrix assembly adds without searching
   zzz::DevBuf<uint16_t> asm_pos;
-  bool have_asm_pos = false;
   zzz::DevBuf<double> cell_geom; // P2/P3 matrix assembly: per cell |detJ| K K^T (6 doubles) or |detJ|, K (10), evaluated once per assembly
   int max_row_nnz = 0;
   // SpMV tiling (row-aligned tiles of the nonzero stream)
@@ -267,15 +255,13 @@ struct zzz_ctx
   zzz::DevBuf<uint16_t> cols16;   // 16-bit column codes for the SpMV (k_tile_encode_cols); cols stays the matrix of record
   zzz::DevBuf<int32_t> tile_base; // band bases: 2^(16-cols16_offb) per tile
   zzz::DevBuf<int32_t> scr_c16;   // fallback-tile counter
-  bool have_cols16 = false, cols16_enabled = true, cols16_pending = false;
-  int cols16_offb = 12, cols16_offb_forced = 0;
+  int cols16_offb = 12;
   int64_t cols16_fallback_tiles = 0;
   int64_t ntiles = 0;
   // tiles of a partitioned matrix split by "references a ghost column" (halo/compute overlap)
   zzz::DevBuf<int32_t> tiles_interior, tiles_boundary;
   int64_t n_tiles_interior = 0, n_tiles_boundary = 0;
-  bool have_tile_split = false;
-  int spmv_lpr_shift = 0, spmv_lpr_forced = -1; // log2(lanes per row) of the SpMV row phase
+  int spmv_lpr_shift = 0; // log2(lanes per row) of the SpMV row phase
   bool spmv_auto = true; // choose bit 0 from the matrix size (off when ZZZ_SPMV_VARIANT / zzz_spmv_time force one)
   int spmv_variant = 1;  // bit 0: non-temporal matrix loads, bit 1: unused,
                          // bit 3: the sliced-ELL operator stream (zzz_sellp.hip) instead of the CSR tile kernel
@@ -288,20 +274,13 @@ struct zzz_ctx
   zzz::DevBuf<int32_t> sp_ccols;
   zzz::DevBuf<uint8_t> sp_gflag;
   hipEvent_t sp_event = nullptr;
-  bool sp_pending = false, sp_forced = false, sp_bounds_ok = false, sp_lds_attr = false;
-  bool sp_rownnz_fresh = false; // sp_rownnz holds the non-zero counts of the CURRENT values (left by the matrix assembly)
-  bool sp_compact_fresh = false; // ... and sp_cvals / sp_ccols the kept entries, rows at sp_crow (capacity-based starts)
-  bool sp_crow_is_cap = false;   // sp_crow = scan of the FULL row lengths padded to 8 (pattern-only; valid until the pattern changes)
+  bool sp_forced = false, sp_lds_attr = false;
   int sp_max_range = 0;       // longest CSR range of a 64-row slice
   int64_t sp_chunk_bound = 0; // chunks of the natural-order stream if no entry were zero
   zzz::DevBuf<uint16_t> sp_codes16;
   zzz::DevBuf<double> sp_vals;
   zzz::DevBuf<unsigned long long> sp_smode; // per slice: two bits per chunk, what a product loads for its columns (zzz_sellp.h)
-  bool sp_pipe_ok = false;                  // every chunk is described by its slice's mode word: the pipelined product may run
-  bool sp_one_chunk = false;                // ... and no slice has more than one chunk (scalar P1 on a regular mesh)
   zzz::DevBuf<uint8_t> sp_pairs;            // one-chunk streams: slices 2 p and 2 p + 1 form an affine pair (zzz_sellp_pipe.hip)
-  bool sp_pairs_ok = false;
-  int sellp_pipe = 1;                       // ZZZ_SELLP_PIPE=0: the generic product always
   // one-chunk streams on the stream dictionary in LDS: a slice none of whose eight slots holds more than 16 distinct value
   // codes in its 64 rows is also kept PACKED (k_sp_pal_build, zzz_sellp_dict.hip): 512 B per chunk in sp_pal, entry l (8 B) =
   // {row l's eight 4-bit palette indices, slot e at bits 4 e; palette codes 2 l and 2 l + 1 of the slice's 8 x 16, ascending
@@ -309,12 +288,9 @@ struct zzz_ctx
   zzz::DevBuf<uint2> sp_pal;
   zzz::DevBuf<uint8_t> sp_palok;
   zzz::DevBuf<int32_t> sp_pal_info;         // [0] packed slices, [1] largest count of distinct codes in a (slice, slot), [2] mixed pairs
-  bool sp_pal_on = false;                   // the packed form serves the one-chunk kernel's launches (at least one slice is packed)
   int64_t sp_pal_packed = 0, sp_pal_mixed = 0;
   int sp_pal_maxcount = 0;
-  int sellp_pal = 1;                        // ZZZ_SELLP_PAL=0: never
-  int64_t nslices = 0, sp_chunks = 0, sp_kept = 0, sp_bytes = 0; // slices, chunks of the stream, matrix entries kept in it,
-                                                                 // bytes a product reads from it
+  int64_t nslices = 0;
   zzz::DevBuf<uint8_t> sp_wlast; // per slice: entries of the longest row in its last chunk (1..8)
   // value dictionary of the stream (zzz_sellp.hip, sp_dict_build): the matrices of a regular mesh hold a few hundred to a few
   // ten thousand DISTINCT values (10 M-dof P1 Poisson: ~1 300); where there are at most 65 535 the product reads a 16-bit
@@ -328,39 +304,19 @@ struct zzz_ctx
   zzz::DevBuf<double> sp_sd_vals;
   zzz::DevBuf<int32_t> sp_sd_info;
   zzz::DevBuf<int64_t> sp_sd_off; // where slice s's table starts in sp_sd_vals (the tables back to back, at even entries)
-  bool sp_sd_on = false;
-  bool sp_sd_all = false; // every slice has its table (none stays doubles)
   int64_t sp_sd_bytes = 0;
-  bool sp_dict_done = false, sp_dict_on = false;
-  bool sp_generic = false;       // the generic operator stream is packed for the current values (not when a special form was chosen at
-                                 // assembly time: sell_update; packed late by sellp_need_generic if a launch asks for it)
-  bool sp_special_tried = false; // the special forms were built or declined for the current values
-  bool sellp_early = true;       // ZZZ_SELLP_EARLY=0: pack the generic stream at every assembly, special forms at the first product (A/B)
-  int sellp_dict = 1;       // ZZZ_SELLP_DICT=0: no value dictionary
   // Jacobi's inverse diagonal as 8- or 16-bit codes (zzz_cg.hip, DinvCodes)
   zzz::ValSet<14, 0> dd_set;
   zzz::DevBuf<uint16_t> dd_codes; // (8-bit codes: the first half of it, one byte per entry)
-  int cg_dinv_codes = 1;          // ZZZ_CG_DINV_CODES: 0 never, 1 when the CG loop exceeds the Infinity Cache, 2 always,
-                                  // 3 always and 16-bit codes even where 8 bits would do (A/B)
   int last_solve_dinv_codes = 0;  // distinct values of the inverse diagonal when the last solve ran on codes, else 0
   int last_solve_dinv_bits = 0;   // ... and the width of a code, 8 or 16 (0 without codes)
   // the classical loop's solution update applied once per K iterations from a ring of K direction vectors (zzz_cg.hip,
   // k_update_p_light / _flush): slot 0 of the ring is `p`, these are slots 1 .. K-1
   zzz::DevBuf<double> p_ring[7];
-  int cg_xdefer = 1;              // ZZZ_CG_XDEFER: 0 never, 1 when the CG loop exceeds the Infinity Cache, 2 always
-  int cg_xdefer_k = 4;            // ZZZ_CG_XDEFER_K: 2, 4 or 8
   int last_solve_xdefer_k = 1;    // the ring's length in the last solve (1: x updated in place in every iteration)
   int sp_dict_n = 0;        // distinct values (with +0.0)
   int64_t sp_dict_bytes = 0; // bytes a product reads from the stream in dictionary form
   bool sp_sorted = false;    // rows ordered by length inside windows (SELL-C-sigma)
-  int sellp_mode = 1;        // ZZZ_SELLP: 0 off, 1 automatic, 2 natural row order always, 3 sorted rows always
-  bool sellp_long_rows = false; // ZZZ_SELLP=4: natural order, always through the long-row packer (count / compact / fill)
-  bool sellp_align = true; // scalar rows, one-chunk slices: entries placed by column so that short boundary rows fit the affine form
-  bool sellp_periodic = true; // block size 3: chunks whose columns are T[slot][row mod 3] + 3 (row div 3) carry no codes
-  int sellp_tail = 1;        // bit 0: 8-bit codes of a narrow chunk go into the free tail of its value block; bit 1: no affine chunks
-  bool sellp_drop = true;    // ZZZ_SELLP_DROP=0: keep the exact zeros of the pattern in the stream
-  bool have_sell = false;    // stream built
-  bool sell_current = false; // ... from the current CSR values
   zzz::DevBuf<int32_t> groups_interior, groups_boundary; // groups of 4 slices without / with ghost columns
   // block-window form of the product for long scalar rows (zzz_sellp_win.hip): rows in the Morton order of their nodes, blocks of
   // 4 096 with the columns they reach as a window in LDS and a dictionary of their values
@@ -375,9 +331,7 @@ struct zzz_ctx
   zzz::DevBuf<double> bw_dofx, bw_bbox;
   zzz::DevBuf<double> bw_dict;
   zzz::DevBuf<uint8_t> bw_gflag;
-  bool bw_on = false, bw_struct_ok = false, bw_have_split = false, bw_lds_attr = false;
-  int sellp_bwin = 1; // ZZZ_SELLP_BWIN: 0 never, 1 by size (zzz_sellp_win.hip), 2 always
-  bool asm_node3 = true; // ZZZ_ASM_NODE3=0: elasticity P1 matrix by the thread-per-scalar-row kernel (A/B against asm_matrix_p1_node3)
+  bool bw_lds_attr = false;
   int32_t bw_nblk = 0;
   int64_t bw_chunks = 0, bw_window_entries = 0, bw_dict_entries = 0, bw_bytes = 0, bw_n_interior = 0, bw_n_boundary = 0;
   uint64_t pattern_version = 0, bw_struct_version = ~0ull; // pattern_version counts zzz_csr_pattern_build calls
@@ -391,16 +345,13 @@ struct zzz_ctx
   zzz::DevBuf<unsigned long long> bk_hash_tag, bk_hash_tag2, bk_hash_owner;
   zzz::DevBuf<int32_t> bk_park; // per block of the matrix: its slot in the set (-1: a zero block), k_bk_insert to k_bk_fill
   zzz::DevBuf<uint8_t> bk_gflag;
-  bool bk_on = false, bk_have_split = false, bk_lds_attr = false;
-  int sellp_blk = 1;       // ZZZ_SELLP_BLK=0: block size 3 stays on the generic product
+  bool bk_lds_attr = false;
   int bk_entries = 0;      // entries of the block table (the zero block included)
   int64_t bk_chunks = 0, bk_slices = 0, bk_bytes = 0, bk_n_interior = 0, bk_n_boundary = 0;
   int64_t n_groups_interior = 0, n_groups_boundary = 0;
-  bool have_group_split = false;
   // assembly tiling: contiguous owned block-dof ranges whose CSR segment fits LDS
   zzz::DevBuf<int32_t> asm_tile;
   int64_t n_asm_tiles = 0;
-  bool have_pattern = false, have_matrix = false;
   bool tiles_ok = true; // false: 2^31 nonzeros or more -- the CSR tile kernel (32-bit tile windows) is not available,
                         // the product must run on the operator stream
 
@@ -425,14 +376,9 @@ struct zzz_ctx
   // as a few contiguous segments that fit LDS; the stream's column codes of such a group are LDS indices
   zzz::DevBuf<int32_t> sp_win_info; // [group] = {segments (0: the group gathers from memory), window length in doubles}
   zzz::DevBuf<int32_t> sp_win_seg;  // [group][SP_WIN_NSEG] = {first column, length}
-  int sp_win_max = 0;               // doubles of LDS per workgroup the product launches with (0: no windowed group)
-  int64_t sp_win_bytes = 0;         // window bytes a product loads (all windowed groups)
   bool halo_pending = false; // comm_halo_begin put an exchange on the comm stream: comm_halo_end waits for it
-  zzz::MfPlan mf; // matrix-free action
   // linalg::cg in float (zzz_cg_f32.hip): x, r, p, y of src/cg.h:38-86 with U = float; grow-only, never freed by a solve
   zzz::DevBuf<float> f32_x, f32_r, f32_p, f32_y;
-  zzz::DevBuf<double> near_null; // the six orthonormalised rigid-body modes (zzz_nullspace.hip), [6][near_null_ld]
-  int64_t near_null_ld = 0;
   // ZZZ_PC_CHEBYSHEV_JACOBI: the spectrum bound of the matrix as it stands (Gershgorin and Lanczos estimate cost ~10 products
   // and ~20 all-reduces: taken once per set of matrix values, not once per solve); mat_version counts assemblies / uploads
   uint64_t mat_version = 0, cheb_version = ~0ull;
@@ -465,9 +411,7 @@ struct zzz_ctx
   hipStream_t red_stream = nullptr;
   hipEvent_t ev_parts_ready = nullptr, ev_red_done = nullptr;
   bool red_pending = false;
-  bool pipe_stream = true; // ZZZ_CG_PIPE_STREAM=0: the all-reduce of the pipelined CG stays on the main stream (A/B)
   bool last_solve_red_overlapped = false; // the last solve's all-reduces went to red_stream (zzz_cg_info)
-  bool overlap = true; // ZZZ_OVERLAP=0 disables the halo/compute overlap
 
   // ZZZ_PC_MG (zzz_mg.hip): the cube this context's feed was generated from by zzz_cube_generate (cleared by every
   // upload of mesh, dofmap, Dirichlet set or facets; feed_version counts all of them), and the hierarchy built on it
@@ -530,9 +474,19 @@ void preload_spmv();
 int alloc_problem_vectors(zzz_ctx* ctx);
 // A context without mesh or dofmap takes the CSR that its rowptr / cols / vals already hold (zzz_agg.hip's coarse levels):
 // nnodes block dofs of bs components in identity order, no ghosts, no Dirichlet rows; tiles, vectors and product stream
-// as zzz_csr_pattern_build and an assembly leave them.  ctx_adopt_values: the values alone were rewritten.
+// as zzz_csr_pattern_build and an assembly leave them.  ctx_adopt_values: the values alone were rewritten -- the one
+// sequence behind every assembly and upload: mat_version, forget_values, the operator stream, have_matrix.
 int ctx_adopt_csr(zzz_ctx* ctx, int bs, int64_t nnodes, int64_t nnz, int max_row_nnz);
-int ctx_adopt_values(zzz_ctx* ctx);
+int ctx_adopt_values(zzz_ctx* ctx, bool assembled = false); // assembled: launch_assemble_matrix wrote them, and its by-products
+// The one forget path, nested along the ladder of the tiers: an entry point that replaces an input calls the function of
+// that input's tier, after its argument checks and before it writes, and everything behind the input is what a fresh
+// context holds.  forget_mesh > forget_dofmap > { forget_bc > forget_bc_values ; forget_pattern > forget_values }.
+void forget_mesh(zzz_ctx* ctx);
+void forget_dofmap(zzz_ctx* ctx);
+void forget_bc(zzz_ctx* ctx);
+void forget_bc_values(zzz_ctx* ctx); // (counts in bc_version: the lifting rows are rebuilt)
+void forget_pattern(zzz_ctx* ctx);
+void forget_values(zzz_ctx* ctx);
 // pattern (zzz_pattern.hip)
 int pattern_build_device(zzz_ctx* ctx, bool* fallback);
 void pattern_reserve(zzz_ctx* ctx); // scratch sized by the dofmap, reserved at upload time
@@ -546,7 +500,6 @@ int ensure_tables(zzz_ctx* ctx);
 int ensure_p1_coords(zzz_ctx* ctx); // P1 only; a no-op for P2/P3
 // internal numbering (zzz_renumber.hip)
 int renumber_build(zzz_ctx* ctx);
-void renumber_clear(zzz_ctx* ctx);
 void to_internal(const zzz_ctx* ctx, const double* in, double* out, bool owned_only);
 void to_caller(const zzz_ctx* ctx, const double* in, double* out, bool owned_only);
 int csr_to_caller(zzz_ctx* ctx, std::vector<zzz::rp_t>& rowptr_c, int32_t* cols_c, double* vals_c, bool need_cols);
@@ -611,7 +564,7 @@ int launch_product(zzz_ctx* ctx, double* x, double* y, double* partials, int* np
 int launch_overlapped(zzz_ctx* ctx, double* x, ProductCall c, const ProductPart& in, const ProductPart& bd, ProductLauncher launch,
                       int* npartials);
 // operator stream (zzz_sellp.hip)
-int sell_update(zzz_ctx* ctx, bool structure);
+int sell_update(zzz_ctx* ctx); // (ctx_adopt_values alone calls it, behind forget_values)
 bool sellp_active(zzz_ctx* ctx);
 int sellp_resolve(zzz_ctx* ctx);
 int sellp_pattern_bounds(zzz_ctx* ctx);
@@ -625,7 +578,6 @@ int launch_sellp_overlapped(zzz_ctx* ctx, double* x, ProductCall c, int* npartia
 int launch_assemble_matrix(zzz_ctx* ctx, int form);
 int launch_assemble_vector(zzz_ctx* ctx, int form);
 int launch_lift(zzz_ctx* ctx); // b -= A_e g over the lifting rows, then b[bc] = g (apply_lifting + bc->set with values)
-void bc_values_clear(zzz_ctx* ctx);
 int launch_matfree_action(zzz_ctx* ctx, const double* x, double* y, double* partials, int* npartials);
 int launch_matfree_legacy(zzz_ctx* ctx, const double* x, double* y, double* partials, int* npartials);
 int launch_matfree_diagonal(zzz_ctx* ctx, double* d);

@@ -1378,7 +1378,7 @@ int plan_attempt(zzz_ctx* ctx, int nc, int T, int nloc_limit, bool* retry)
 {
   MfPlan& M = ctx->mf;
   hipStream_t s = ctx->stream;
-  const int nd = ctx->nd;
+  const int nd = ctx->dofmap.nd;
   const int64_t ncells = ctx->ncells;
   const int nsb = nc / T;
   const int64_t nb = (ncells + nc - 1) / nc, total = nb * nc;
@@ -1633,11 +1633,11 @@ int mf_plan_build(zzz_ctx* ctx)
   M.f32_built = false; // (the twins follow the plan)
   if (ctx->bs != 1 && ctx->bs != 3)
     return fail(ctx, ZZZ_ERR_ARG, "the matrix-free operator exists for block sizes 1 (src/Poisson.py:33, form M) and 3 (src/Elasticity.py, form a)");
-  if (ctx->order == 0 || ctx->ncells == 0)
+  if (ctx->dofmap.order == 0 || ctx->ncells == 0)
     return fail(ctx, ZZZ_ERR_ARG, "matrix-free operator before zzz_dofmap_upload");
   if (int rc = ensure_p1_coords(ctx))
     return rc;
-  const int nd = ctx->nd;
+  const int nd = ctx->dofmap.nd;
   // defaults (measured): workgroup size and cells per block; ZZZ_MF_T / ZZZ_MF_NC override them
   // (tools/mf_sweep.sh, MI355X: P1 10 M dofs 0.70 ms at 2048 x 256 against 0.84 at 4096 x 512 and 1.30 at 8192 x 512 --
   // small blocks share more dofs but keep five workgroups on a CU; P3 6.2 M dofs 0.30 ms at 768 x 256, 0.32 at 512, 0.38 at 1024)
@@ -2140,7 +2140,7 @@ int mf_assemble_vector(zzz_ctx* ctx)
                          M.ypart.p, (const double*)nullptr, ctx->b.p, (double*)nullptr, (const int*)nullptr, 0.0);
   }
   ZZZ_HIP(ctx, hipGetLastError());
-  if (ctx->have_bc_val)
+  if (ctx->dirichlet.have_bc_val)
   {
     const int64_t nall = ctx->nloc(), nrows = ctx->n_owned * ctx->bs;
     hipLaunchKernelGGL(k_mf_lift_src, dim3(grid_cap(nall, 256, 8192)), dim3(256), 0, ctx->stream, ctx->bc.p, ctx->bc_val.p, nall, ctx->p.p);

@@ -322,7 +322,7 @@ int mg_check(zzz_ctx* ctx, const zzz_solver_opts* o)
   if (agg)
   {
     // the matrix alone: whatever feed, order, numbering or source of the values
-    if (!ctx->have_pattern || !ctx->have_matrix)
+    if (!ctx->pattern.have_pattern || !ctx->values.have_matrix)
       return fail(ctx, ZZZ_ERR_ARG, "%s: needs a sparsity pattern and matrix values", tag);
     if (ctx->n_ghost != 0)
       return fail(ctx, ZZZ_ERR_ARG, "%s: the context has %lld ghost dofs: one rank only", tag, (long long)ctx->n_ghost);
@@ -339,16 +339,16 @@ int mg_check(zzz_ctx* ctx, const zzz_solver_opts* o)
                                   "zzz_cube_generate: the library does not know the cube to coarsen", tag);
   if (ctx->cube_nparts != 1 || ctx->n_ghost != 0)
     return fail(ctx, ZZZ_ERR_ARG, "%s: the cube was generated as part of %d: one part only", tag, ctx->cube_nparts);
-  if (ctx->order != 1 && !pmg)
-    return fail(ctx, ZZZ_ERR_ARG, "%s: order %d; P1 only (p-coarsening for P2 / P3 is -pc_type pmg, ZZZ_PC_PMG)", tag, ctx->order);
-  if (ctx->order < 1 || ctx->order > 3)
-    return fail(ctx, ZZZ_ERR_ARG, "%s: order %d", tag, ctx->order);
-  if (ctx->order > 1 && o->pc_mg_levels == 1)
+  if (ctx->dofmap.order != 1 && !pmg)
+    return fail(ctx, ZZZ_ERR_ARG, "%s: order %d; P1 only (p-coarsening for P2 / P3 is -pc_type pmg, ZZZ_PC_PMG)", tag, ctx->dofmap.order);
+  if (ctx->dofmap.order < 1 || ctx->dofmap.order > 3)
+    return fail(ctx, ZZZ_ERR_ARG, "%s: order %d", tag, ctx->dofmap.order);
+  if (ctx->dofmap.order > 1 && o->pc_mg_levels == 1)
     return fail(ctx, ZZZ_ERR_ARG, "%s: pc_mg_levels = 1 at order %d: the P%d level and the P1 level of the same cube make two at least",
-                tag, ctx->order, ctx->order);
-  if (ctx->renumbered)
+                tag, ctx->dofmap.order, ctx->dofmap.order);
+  if (ctx->dofmap.renumbered)
     return fail(ctx, ZZZ_ERR_ARG, "%s: the context keeps an internal dof order; the transfer needs the lexicographic one", tag);
-  if (!ctx->have_matrix)
+  if (!ctx->values.have_matrix)
     return fail(ctx, ZZZ_ERR_ARG, "%s: matrix not assembled", tag);
   if (o->pc_degree < 0 || o->pc_degree > 64 || o->pc_esteig_its > 64)
     return fail(ctx, ZZZ_ERR_ARG, "%s: smoother degree 1..64, estimate <= 64 steps", tag);
@@ -539,7 +539,7 @@ static int mg_build_agg(zzz_ctx* ctx, MgHier* H, int limit, int max_levels)
     if (int rc = mg_child_create(ctx, l, &C.ctx))
       return rc;
     // (no block-window product on a level without coordinates; the other forms are packed from the CSR alone)
-    C.ctx->sellp_bwin = 0;
+    C.ctx->knob.sellp_bwin = 0;
     if (int rc = agg_galerkin(ctx, L.ctx, L.agg, C.ctx))
       return rc;
   }
@@ -596,7 +596,7 @@ int mg_setup(zzz_ctx* ctx, const zzz_solver_opts* o)
     else
     {
       // ZZZ_PC_PMG at order > 1: the Pk level first, then the P1 levels from the same cube on; pc_mg_levels counts all
-      const size_t high = ctx->order > 1 ? 1 : 0;
+      const size_t high = ctx->dofmap.order > 1 ? 1 : 0;
       std::vector<std::array<int64_t, 3>> dims;
       if (high)
         dims.push_back({ctx->cube_n[0], ctx->cube_n[1], ctx->cube_n[2]});
@@ -630,7 +630,7 @@ int mg_setup(zzz_ctx* ctx, const zzz_solver_opts* o)
         if (l == 0)
         {
           L.ctx = ctx;
-          L.order = ctx->order;
+          L.order = ctx->dofmap.order;
           L.ndof = ctx->n_owned * ctx->bs;
           continue;
         }
@@ -641,7 +641,7 @@ int mg_setup(zzz_ctx* ctx, const zzz_solver_opts* o)
           return child_fail(ctx, c, rc, (int)l, "generate");
         if (int rc = zzz_csr_pattern_build(c))
           return child_fail(ctx, c, rc, (int)l, "pattern");
-        if (c->renumbered || c->n_owned * c->bs != L.ndof)
+        if (c->dofmap.renumbered || c->n_owned * c->bs != L.ndof)
           return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg / pmg, level %d: the generated level is not in lexicographic order", (int)l);
       }
       for (size_t l = high; l + 1 < H->lv.size(); ++l)
@@ -923,18 +923,18 @@ int zzz_mg_apply(zzz_ctx* ctx, const double* r, double* z)
   ZZZ_HIP(ctx, hipMemsetAsync(ctx->state.p, 0, sizeof(CgState), s)); // (a finished solve leaves its stop flag set)
   // (a context in an internal dof order -- ZZZ_PC_AGG alone serves one -- translates at the boundary, as zzz_spmv does)
   std::vector<double> ri, zi;
-  if (ctx->renumbered)
+  if (ctx->dofmap.renumbered)
   {
     ri.resize(n);
     zi.resize(n);
     to_internal(ctx, r, ri.data(), true);
   }
-  ZZZ_HIP(ctx, hipMemcpyAsync(ctx->r.p, ctx->renumbered ? ri.data() : r, n * sizeof(double), hipMemcpyHostToDevice, s));
+  ZZZ_HIP(ctx, hipMemcpyAsync(ctx->r.p, ctx->dofmap.renumbered ? ri.data() : r, n * sizeof(double), hipMemcpyHostToDevice, s));
   if (int rc = mg_vcycle(ctx, ctx->r.p, ctx->z.p, false))
     return rc;
-  ZZZ_HIP(ctx, hipMemcpyAsync(ctx->renumbered ? zi.data() : z, ctx->z.p, n * sizeof(double), hipMemcpyDeviceToHost, s));
+  ZZZ_HIP(ctx, hipMemcpyAsync(ctx->dofmap.renumbered ? zi.data() : z, ctx->z.p, n * sizeof(double), hipMemcpyDeviceToHost, s));
   ZZZ_HIP(ctx, hipStreamSynchronize(s));
-  if (ctx->renumbered)
+  if (ctx->dofmap.renumbered)
     to_caller(ctx, zi.data(), z, true);
   return ZZZ_OK;
 }
@@ -956,7 +956,7 @@ int zzz_mg_transfer(zzz_ctx* ctx, int level, int dir, const double* in, double* 
   ZZZ_HIP(ctx, H->tx_in.reserve(nin));
   ZZZ_HIP(ctx, H->tx_out.reserve(nout));
   // (level 0 of a context in an internal dof order: its side of the pair is translated)
-  const bool tr = level == 0 && ctx->renumbered;
+  const bool tr = level == 0 && ctx->dofmap.renumbered;
   std::vector<double> vi;
   if (tr && dir == 1)
   {
@@ -994,7 +994,7 @@ int zzz_mg_level_csr(zzz_ctx* ctx, int level, int64_t* rowptr, int32_t* cols, do
     return fail(ctx, ZZZ_ERR_ARG, "zzz_mg_level_csr: level %d; the coarse levels are 1 .. %d (level 0 is zzz_csr_download's)", level,
                 (int)H->lv.size() - 1);
   const zzz_ctx* c = H->lv[(size_t)level]->ctx;
-  if (c->renumbered)
+  if (c->dofmap.renumbered)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_mg_level_csr: level %d keeps an internal dof order", level);
   ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (rowptr)

@@ -151,13 +151,13 @@ int dof_coords_device(zzz_ctx* ctx, DevBuf<double>& dofx, DevBuf<int32_t>& first
 {
   hipStream_t s = ctx->stream;
   const int64_t nblock = ctx->n_owned + ctx->n_ghost, nc = ctx->ncells;
-  const int g = (int)std::max<int64_t>(1, std::min<int64_t>((nc * ctx->nd + 255) / 256, 8192));
+  const int g = (int)std::max<int64_t>(1, std::min<int64_t>((nc * ctx->dofmap.nd + 255) / 256, 8192));
   ZZZ_HIP(ctx, first.alloc((size_t)nblock));
   ZZZ_HIP(ctx, dofx.alloc((size_t)(3 * nblock)));
   ZZZ_HIP(ctx, hipMemsetAsync(first.p, 0x7f, (size_t)nblock * sizeof(int32_t), s));
   ZZZ_HIP(ctx, hipMemsetAsync(dofx.p, 0, (size_t)(3 * nblock) * sizeof(double), s));
-  hipLaunchKernelGGL(k_nn_first_cell, dim3(g), dim3(256), 0, s, ctx->cell_dofs.p, ctx->nd, nc, first.p);
-  hipLaunchKernelGGL(k_nn_dof_coords, dim3(g), dim3(256), 0, s, ctx->x.p, ctx->cell_verts.p, ctx->cell_dofs.p, ctx->order, ctx->nd, nc,
+  hipLaunchKernelGGL(k_nn_first_cell, dim3(g), dim3(256), 0, s, ctx->cell_dofs.p, ctx->dofmap.nd, nc, first.p);
+  hipLaunchKernelGGL(k_nn_dof_coords, dim3(g), dim3(256), 0, s, ctx->x.p, ctx->cell_verts.p, ctx->cell_dofs.p, ctx->dofmap.order, ctx->dofmap.nd, nc,
                      first.p, dofx.p);
   ZZZ_HIP(ctx, hipGetLastError());
   return ZZZ_OK;
@@ -173,12 +173,12 @@ int zzz_near_nullspace_build(zzz_ctx* ctx, double* max_deviation)
   if (!ctx)
     return fail(nullptr, ZZZ_ERR_ARG, "NULL context");
   ZZZ_HIP(ctx, hipSetDevice(ctx->device));
-  if (ctx->order == 0 || ctx->bs != 3)
+  if (ctx->dofmap.order == 0 || ctx->bs != 3)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_near_nullspace_build: needs the vector-valued space of the elasticity problem (block size 3)");
   hipStream_t s = ctx->stream;
   const int64_t nblock = ctx->n_owned + ctx->n_ghost, ld = 3 * nblock, nown = 3 * ctx->n_owned;
   const int64_t nc = ctx->ncells;
-  const int g = (int)std::min<int64_t>((nc * ctx->nd + 255) / 256, 8192);
+  const int g = (int)std::min<int64_t>((nc * ctx->dofmap.nd + 255) / 256, 8192);
   DevBuf<int32_t> first;
   DevBuf<double> dofx, parts;
   ZZZ_HIP(ctx, first.alloc((size_t)nblock));
@@ -187,8 +187,8 @@ int zzz_near_nullspace_build(zzz_ctx* ctx, double* max_deviation)
   ZZZ_HIP(ctx, ctx->near_null.alloc((size_t)(6 * ld)));
   ZZZ_HIP(ctx, hipMemsetAsync(first.p, 0x7f, (size_t)nblock * sizeof(int32_t), s));
   ZZZ_HIP(ctx, hipMemsetAsync(dofx.p, 0, (size_t)(3 * nblock) * sizeof(double), s));
-  hipLaunchKernelGGL(k_nn_first_cell, dim3(g), dim3(256), 0, s, ctx->cell_dofs.p, ctx->nd, nc, first.p);
-  hipLaunchKernelGGL(k_nn_dof_coords, dim3(g), dim3(256), 0, s, ctx->x.p, ctx->cell_verts.p, ctx->cell_dofs.p, ctx->order, ctx->nd, nc,
+  hipLaunchKernelGGL(k_nn_first_cell, dim3(g), dim3(256), 0, s, ctx->cell_dofs.p, ctx->dofmap.nd, nc, first.p);
+  hipLaunchKernelGGL(k_nn_dof_coords, dim3(g), dim3(256), 0, s, ctx->x.p, ctx->cell_verts.p, ctx->cell_dofs.p, ctx->dofmap.order, ctx->dofmap.nd, nc,
                      first.p, dofx.p);
   double* B = ctx->near_null.p;
   const int gb = (int)std::min<int64_t>((nblock + 255) / 256, 4096), gv = (int)std::min<int64_t>((ld + 255) / 256, 4096);
@@ -242,7 +242,7 @@ int zzz_near_nullspace_build(zzz_ctx* ctx, double* max_deviation)
     }
   if (max_deviation)
     *max_deviation = dev;
-  ctx->near_null_ld = ld;
+  ctx->dofmap.near_null_ld = ld;
   if (!(dev <= 1.0e-10)) // [EXT] dolfinx::la::is_orthonormal's default tolerance is the scalar type's epsilon scaled; 1e-10 here
     return fail(ctx, ZZZ_ERR_ARG, "Space not orthonormal (largest deviation %g)", dev);
   return ZZZ_OK;
@@ -250,13 +250,13 @@ int zzz_near_nullspace_build(zzz_ctx* ctx, double* max_deviation)
 
 int zzz_near_nullspace_download(zzz_ctx* ctx, int k, double* out)
 {
-  if (!ctx || !out || k < 0 || k > 5 || ctx->near_null_ld == 0)
+  if (!ctx || !out || k < 0 || k > 5 || ctx->dofmap.near_null_ld == 0)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_near_nullspace_download: no basis built, or bad arguments");
   ZZZ_HIP(ctx, hipSetDevice(ctx->device));
   const size_t n = (size_t)(3 * ctx->n_owned);
   std::vector<double> tmp(n);
-  ZZZ_HIP(ctx, hipMemcpy(tmp.data(), ctx->near_null.p + (size_t)k * ctx->near_null_ld, n * sizeof(double), hipMemcpyDeviceToHost));
-  if (ctx->renumbered)
+  ZZZ_HIP(ctx, hipMemcpy(tmp.data(), ctx->near_null.p + (size_t)k * ctx->dofmap.near_null_ld, n * sizeof(double), hipMemcpyDeviceToHost));
+  if (ctx->dofmap.renumbered)
     to_caller(ctx, tmp.data(), out, true);
   else
     std::copy(tmp.begin(), tmp.end(), out);

@@ -698,12 +698,12 @@ __global__ void k_asm_tiles(const rp_t* __restrict__ rowptr, int nb, int bs, int
 // first used on this pattern (matrices that run on the operator stream of zzz_sellp.hip never need it).
 int ensure_cols16(zzz_ctx* ctx)
 {
-  if (!ctx->cols16_pending)
+  if (!ctx->pattern.cols16_pending)
     return ZZZ_OK;
-  ctx->cols16_pending = false;
-  ctx->have_cols16 = false;
+  ctx->pattern.cols16_pending = false;
+  ctx->pattern.have_cols16 = false;
   ctx->cols16_fallback_tiles = 0;
-  if (!ctx->cols16_enabled || ctx->ntiles == 0)
+  if (!ctx->knob.cols16_enabled || ctx->ntiles == 0)
     return ZZZ_OK;
   hipStream_t s = ctx->stream;
   ZZZ_HIP(ctx, ctx->cols16.alloc((size_t)ctx->nnz + 16));
@@ -714,7 +714,7 @@ int ensure_cols16(zzz_ctx* ctx)
   // long rows (high order, vector-valued) spread a tile over more, narrower clusters: start narrower
   const bool long_rows = ctx->max_row_nnz > 64;
   const int order[4] = {long_rows ? 11 : 12, long_rows ? 12 : 11, long_rows ? 10 : 13, long_rows ? 13 : 10};
-  const int ntry = ctx->cols16_offb_forced ? 1 : 4;
+  const int ntry = ctx->knob.cols16_offb_forced ? 1 : 4;
   int best = -1;
   int32_t best_fb = INT32_MAX;
   auto run = [&](int offb, int32_t* nfb) -> int {
@@ -729,7 +729,7 @@ int ensure_cols16(zzz_ctx* ctx)
   int last = -1;
   for (int i = 0; i < ntry; ++i)
   {
-    const int offb = ctx->cols16_offb_forced ? ctx->cols16_offb_forced : order[i];
+    const int offb = ctx->knob.cols16_offb_forced ? ctx->knob.cols16_offb_forced : order[i];
     int32_t nfb = 0;
     int rc = run(offb, &nfb);
     if (rc)
@@ -752,7 +752,7 @@ int ensure_cols16(zzz_ctx* ctx)
   }
   ctx->cols16_offb = best;
   ctx->cols16_fallback_tiles = best_fb;
-  ctx->have_cols16 = true;
+  ctx->pattern.have_cols16 = true;
   return ZZZ_OK;
 }
 
@@ -768,7 +768,7 @@ int build_tiles_device(zzz_ctx* ctx, int max_block_cols)
   // measured: 8 lanes pay from ~128 nonzeros per row on average (P3 elasticity 0.47 -> 0.40 ms), cost below
   {
     const double avg = ctx->nrows > 0 ? (double)ctx->nnz / (double)ctx->nrows : 0.0;
-    ctx->spmv_lpr_shift = ctx->spmv_lpr_forced >= 0 ? ctx->spmv_lpr_forced : (avg >= 128.0 ? 3 : 0);
+    ctx->spmv_lpr_shift = ctx->knob.spmv_lpr_forced >= 0 ? ctx->knob.spmv_lpr_forced : (avg >= 128.0 ? 3 : 0);
   }
   const int64_t Ws = (int64_t)SPMV_TILE_NNZ - maxrow - 2;
   const int64_t Wa = (int64_t)asm_tile_nnz(ctx) - maxblock;
@@ -792,8 +792,8 @@ int build_tiles_device(zzz_ctx* ctx, int max_block_cols)
   int rc = build_tile_split(ctx);
   if (rc)
     return rc;
-  ctx->have_cols16 = false;
-  ctx->cols16_pending = true;
+  ctx->pattern.have_cols16 = false;
+  ctx->pattern.cols16_pending = true;
   return ZZZ_OK;
 }
 
@@ -1020,8 +1020,8 @@ __global__ __launch_bounds__(ADJ_W) void k_adj_window(const int32_t* __restrict_
 // path applies
 static void adjacency_find_runs(zzz_ctx* ctx)
 {
-  ctx->adj_runs_n = 0;
-  const int nd = ctx->nd;
+  ctx->dofmap.adj_runs_n = 0;
+  const int nd = ctx->dofmap.nd;
   const int64_t nc = ctx->ncells;
   if (nc >= INT32_MAX)
     return;
@@ -1071,14 +1071,14 @@ static void adjacency_find_runs(zzz_ctx* ctx)
     (void)hipGetLastError();
     return;
   }
-  ctx->adj_runs_n = nruns;
+  ctx->dofmap.adj_runs_n = nruns;
 }
 
 // adjacency through the runs, enqueued without a host wait: whether every window fitted arrives in
 // ctx->adj_flag_host behind these kernels and is looked at the next time the build waits for the device anyway
 static int adjacency_by_runs(zzz_ctx* ctx)
 {
-  const int nruns = ctx->adj_runs_n, nd = ctx->nd;
+  const int nruns = ctx->dofmap.adj_runs_n, nd = ctx->dofmap.nd;
   const int32_t nb = (int32_t)ctx->n_owned;
   const int nwin = (nb + ADJ_W - 1) / ADJ_W;
   hipStream_t s = ctx->stream;
@@ -1128,9 +1128,9 @@ static auto adjacency_sort(zzz_ctx* ctx, int64_t N, int end_bit)
 // build allocates what it needs.
 void pattern_reserve(zzz_ctx* ctx)
 {
-  if (ctx->ncells <= 0 || ctx->nd <= 0 || ctx->n_owned <= 0)
+  if (ctx->ncells <= 0 || ctx->dofmap.nd <= 0 || ctx->n_owned <= 0)
     return;
-  const int nd = ctx->nd;
+  const int nd = ctx->dofmap.nd;
   const int64_t N = ctx->ncells * nd, nb = ctx->n_owned;
   if (N > INT32_MAX - 8)
     return;
@@ -1170,7 +1170,7 @@ void pattern_reserve(zzz_ctx* ctx)
 int pattern_build_device(zzz_ctx* ctx, bool* fallback)
 {
   *fallback = false;
-  const int nd = ctx->nd, bs = ctx->bs;
+  const int nd = ctx->dofmap.nd, bs = ctx->bs;
   const int32_t nb = (int32_t)ctx->n_owned;
   const int64_t N = ctx->ncells * nd;
   hipStream_t s = ctx->stream;
@@ -1203,9 +1203,9 @@ int pattern_build_device(zzz_ctx* ctx, bool* fallback)
     ctx->scr_cell_of_n = N;
     ctx->scr_cell_of_nd = nd;
   }
-  if (ctx->adj_runs_n < 0)
+  if (ctx->dofmap.adj_runs_n < 0)
     adjacency_find_runs(ctx);
-  const bool by_runs = ctx->adj_runs_n > 0;
+  const bool by_runs = ctx->dofmap.adj_runs_n > 0;
   if (by_runs)
   {
     if (int rc = adjacency_by_runs(ctx))
@@ -1252,7 +1252,7 @@ int pattern_build_device(zzz_ctx* ctx, bool* fallback)
       ZZZ_HIP(ctx, hipStreamSynchronize(s));
       if (adjacency_overflowed())
       {
-        ctx->adj_runs_n = 0;
+        ctx->dofmap.adj_runs_n = 0;
         return pattern_build_device(ctx, fallback);
       }
       if (h[2] == 0 || cap == 32)
@@ -1260,7 +1260,7 @@ int pattern_build_device(zzz_ctx* ctx, bool* fallback)
       ZZZ_HIP(ctx, hipMemsetAsync(scal.p, 0, 4 * sizeof(int32_t), s));
     }
     counted = h[2] == 0;
-    ctx->have_adj_li = counted; // complete only if no row overflowed
+    ctx->pattern.have_adj_li = counted; // complete only if no row overflowed
     if (!counted)
       ZZZ_HIP(ctx, hipMemsetAsync(scal.p, 0, 4 * sizeof(int32_t), s));
   }
@@ -1268,7 +1268,7 @@ int pattern_build_device(zzz_ctx* ctx, bool* fallback)
   {
     // P2/P3: the positions of the element-matrix entries inside their rows, for the assembly (row_unique_regs)
     uint16_t* pos_out = nullptr;
-    ctx->have_asm_pos = false;
+    ctx->pattern.have_asm_pos = false;
     if (nd > 4 && !getenv("ZZZ_ASM_SEARCH") && ctx->asm_pos.alloc((size_t)nstage) == hipSuccess)
       pos_out = ctx->asm_pos.p;
     (void)hipGetLastError();
@@ -1277,10 +1277,10 @@ int pattern_build_device(zzz_ctx* ctx, bool* fallback)
                        scal.p + 3);
     ZZZ_HIP(ctx, hipMemcpyAsync(h, scal.p, sizeof(h), hipMemcpyDeviceToHost, s));
     ZZZ_HIP(ctx, hipStreamSynchronize(s));
-    ctx->have_asm_pos = pos_out != nullptr && h[3] == 0;
+    ctx->pattern.have_asm_pos = pos_out != nullptr && h[3] == 0;
     if (adjacency_overflowed())
     {
-      ctx->adj_runs_n = 0;
+      ctx->dofmap.adj_runs_n = 0;
       return pattern_build_device(ctx, fallback);
     }
   }
@@ -1342,7 +1342,7 @@ __global__ __launch_bounds__(256) void k_tile_ghost_flag(const int4* __restrict_
 // interior / boundary tile lists for the halo-compute overlap of a partitioned matrix
 int build_tile_split(zzz_ctx* ctx)
 {
-  ctx->have_tile_split = false;
+  ctx->pattern.have_tile_split = false;
   ctx->n_tiles_interior = ctx->n_tiles_boundary = 0;
   if (ctx->n_ghost == 0 || ctx->ntiles == 0)
     return ZZZ_OK;
@@ -1364,7 +1364,7 @@ int build_tile_split(zzz_ctx* ctx)
     ZZZ_HIP(ctx, hipMemcpy(ctx->tiles_boundary.p, bd.data(), bd.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   ctx->n_tiles_interior = (int64_t)in.size();
   ctx->n_tiles_boundary = (int64_t)bd.size();
-  ctx->have_tile_split = true;
+  ctx->pattern.have_tile_split = true;
   return ZZZ_OK;
 }
 ZZZ_PRELOAD_TU(pattern)

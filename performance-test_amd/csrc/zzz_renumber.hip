@@ -295,39 +295,11 @@ __global__ void k_translate(int32_t* __restrict__ cell_dofs, int64_t n, const in
 
 static int renumber_cells(zzz_ctx* ctx, const Lattice& L);
 
-// forgets the dof order only (the cells may already have been put into theirs)
-static void renumber_clear_dofs(zzz_ctx* ctx)
-{
-  ctx->renumbered = false;
-  ctx->perm.release();
-  ctx->iperm.release();
-  ctx->h_perm.clear();
-  ctx->h_iperm.clear();
-  ctx->csr_slot.clear();
-  ctx->csr_slot.shrink_to_fit();
-}
-
-void renumber_clear(zzz_ctx* ctx)
-{
-  ctx->renumbered = false;
-  ctx->perm.release();
-  ctx->iperm.release();
-  ctx->h_perm.clear();
-  ctx->h_iperm.clear();
-  ctx->csr_slot.clear();
-  ctx->csr_slot.shrink_to_fit();
-  ctx->renumber_kind = 0;
-  ctx->cells_renumbered = false;
-  ctx->h_cperm.clear();
-  ctx->h_cperm.shrink_to_fit();
-}
-
-// Called by zzz_dofmap_upload with the caller's connectivity on the device: decides on the internal order, and when
+// Called by zzz_dofmap_upload, behind its forget_dofmap, with the caller's connectivity on the device: decides on the internal order, and when
 // it is not the caller's, translates the device connectivity (owned dofs only; ghosts keep their places, which the
 // forward scatter defines).
 int renumber_build(zzz_ctx* ctx)
 {
-  renumber_clear(ctx);
   int mode = 1;
   if (const char* e = getenv("ZZZ_RENUMBER")) // 0: keep the caller's order; 1: lattice meshes (default); 2: any mesh
     mode = atoi(e);
@@ -409,9 +381,9 @@ int renumber_build(zzz_ctx* ctx)
   ZZZ_HIP(ctx, ctx->iperm.alloc((size_t)nb));
   ZZZ_HIP(ctx, hipMemsetAsync(keys.p, 0xff, (size_t)nb * sizeof(unsigned long long), s)); // a dof no cell touches sorts last
   ZZZ_HIP(ctx, hipMemsetAsync(flag.p, 0, 2 * sizeof(int32_t), s));
-  const int64_t N = ctx->ncells * ctx->nd;
+  const int64_t N = ctx->ncells * ctx->dofmap.nd;
   hipLaunchKernelGGL(k_dof_keys, dim3(grid_cap(N, 256, 16384)), dim3(256), 0, s, ctx->x.p, ctx->cell_verts.p, ctx->cell_dofs.p, ctx->ncells,
-                     ctx->nd, ctx->order, (int32_t)nb, L, keys.p);
+                     ctx->dofmap.nd, ctx->dofmap.order, (int32_t)nb, L, keys.p);
   hipLaunchKernelGGL(k_iota, dim3(grid_cap(nb, 256, 16384)), dim3(256), 0, s, ident.p, nb);
   if (int rc = with_scratch(ctx, tmp, sort_pairs(keys.p, skeys.p, ident.p, ctx->perm.p, (size_t)nb, 0, 64, s))) // stable
     return rc;
@@ -421,15 +393,13 @@ int renumber_build(zzz_ctx* ctx)
   ZZZ_HIP(ctx, hipGetLastError());
   // two dofs with one key on a lattice: the mesh is not of the family the key describes (e.g. another splitting of
   // the sub-cubes, a curved geometry): leave the caller's order alone rather than guess
-  if (lattice && hflag[1] && mode < 2)
+  const bool unkeyed = lattice && hflag[1] && mode < 2;
+  if (unkeyed || !hflag[0]) // ... or the caller's numbering IS the internal order: no dof order (the cells may be in theirs)
   {
-    renumber_clear_dofs(ctx);
-    return ZZZ_OK;
-  }
-  if (!hflag[0])
-  {
-    renumber_clear_dofs(ctx); // the caller's numbering IS the internal order
-    ctx->renumber_kind = lattice ? 1 : 2;
+    ctx->perm.release();
+    ctx->iperm.release();
+    if (!unkeyed)
+      ctx->dofmap.renumber_kind = lattice ? 1 : 2;
     return ZZZ_OK;
   }
   hipLaunchKernelGGL(k_translate, dim3(grid_cap(N, 256, 16384)), dim3(256), 0, s, ctx->cell_dofs.p, N, ctx->iperm.p, (int32_t)nb);
@@ -438,8 +408,8 @@ int renumber_build(zzz_ctx* ctx)
   ZZZ_HIP(ctx, hipMemcpyAsync(ctx->h_perm.data(), ctx->perm.p, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, s));
   ZZZ_HIP(ctx, hipMemcpyAsync(ctx->h_iperm.data(), ctx->iperm.p, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, s));
   ZZZ_HIP(ctx, hipStreamSynchronize(s));
-  ctx->renumbered = true;
-  ctx->renumber_kind = lattice ? 1 : 2;
+  ctx->dofmap.renumbered = true;
+  ctx->dofmap.renumber_kind = lattice ? 1 : 2;
   return ZZZ_OK;
 }
 
@@ -473,7 +443,7 @@ static int renumber_cells(zzz_ctx* ctx, const Lattice& L)
   ZZZ_HIP(ctx, hipGetLastError());
   if (hf[0] || !hf[1])
     return ZZZ_OK; // a cell that is no lattice simplex (keep the caller's order), or the order is already this one
-  const int nd = ctx->nd;
+  const int nd = ctx->dofmap.nd;
   ZZZ_HIP(ctx, tmpi.alloc((size_t)(nc * std::max(nd, 4))));
   hipLaunchKernelGGL(k_gather_rows, dim3(grid_cap(nc * 4, 256, 16384)), dim3(256), 0, s, ctx->cell_verts.p, cperm.p, nc, 4, tmpi.p);
   ZZZ_HIP(ctx, hipMemcpyAsync(ctx->cell_verts.p, tmpi.p, (size_t)(4 * nc) * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
@@ -483,7 +453,7 @@ static int renumber_cells(zzz_ctx* ctx, const Lattice& L)
   ZZZ_HIP(ctx, hipMemcpyAsync(ctx->h_cperm.data(), cperm.p, (size_t)nc * sizeof(int32_t), hipMemcpyDeviceToHost, s));
   ZZZ_HIP(ctx, hipStreamSynchronize(s));
   ZZZ_HIP(ctx, hipGetLastError());
-  ctx->cells_renumbered = true;
+  ctx->dofmap.cells_renumbered = true;
   return ZZZ_OK;
 }
 
@@ -545,7 +515,7 @@ int csr_to_caller(zzz_ctx* ctx, std::vector<rp_t>& rowptr_c, int32_t* cols_c, do
   if (vals_c)
   {
     vi.resize((size_t)nnz);
-    if (ctx->have_matrix)
+    if (ctx->values.have_matrix)
       ZZZ_HIP(ctx, hipMemcpy(vi.data(), ctx->vals.p, (size_t)nnz * sizeof(double), hipMemcpyDeviceToHost));
     else
       std::fill(vi.begin(), vi.end(), 0.0);

@@ -402,12 +402,12 @@ bool sellp_special_build(zzz_ctx* ctx)
 {
   if (sellp_blk_build(ctx) != ZZZ_OK)
   {
-    ctx->bk_on = false;
+    ctx->values.bk_on = false;
     (void)hipGetLastError();
   }
   if (sellp_win_build(ctx) != ZZZ_OK)
   {
-    ctx->bw_on = false;
+    ctx->values.bw_on = false;
     (void)hipGetLastError();
   }
   return sellp_blk_serves(ctx) || sellp_win_serves(ctx);
@@ -415,13 +415,13 @@ bool sellp_special_build(zzz_ctx* ctx)
 
 bool sellp_active(zzz_ctx* ctx)
 {
-  if (ctx->sp_pending)
+  if (ctx->values.sp_pending)
     (void)sellp_resolve(ctx);
-  if (!ctx->have_sell || !ctx->sell_current)
+  if (!ctx->values.have_sell)
     return false;
   if (!(ctx->spmv_auto || (ctx->spmv_variant & 8) != 0))
     return false;
-  if (!ctx->sp_dict_done)
+  if (!ctx->values.sp_dict_done)
   {
     // a FAILED build (a hipMalloc that did not fit) leaves the stream on doubles -- valid -- but must not leave its partial
     // allocations or HIP's sticky last error behind (the next hipGetLastError after a product launch would report it).
@@ -433,25 +433,25 @@ bool sellp_active(zzz_ctx* ctx)
     // zzz_sellp_win.hip): where one of them serves the product, the stream's value dictionaries are not built -- the launches
     // that still take the generic kernel read its values as doubles.  7.6 ms per assembly at 6.2 M rows of P3, 3 ms at C4.
     // A failed build leaves the stream as it is.
-    ctx->sp_dict_done = true;
-    ctx->sp_dict_on = ctx->sp_sd_on = ctx->sp_sd_all = ctx->sp_pal_on = false;
+    ctx->values.sp_dict_done = true;
+    ctx->values.sp_dict_on = ctx->values.sp_sd_on = ctx->values.sp_sd_all = ctx->values.sp_pal_on = false;
     ctx->sp_dict_n = 0;
-    if (!ctx->sp_special_tried)
+    if (!ctx->values.sp_special_tried)
     {
       (void)sellp_special_build(ctx);
-      ctx->sp_special_tried = true;
+      ctx->values.sp_special_tried = true;
     }
     if (!sellp_blk_serves(ctx) && !sellp_win_serves(ctx))
     {
       if (sp_dict_build(ctx) != ZZZ_OK)
       {
-        ctx->sp_dict_on = ctx->sp_pal_on = false;
+        ctx->values.sp_dict_on = ctx->values.sp_pal_on = false;
         (void)hipGetLastError();
         ctx->sp_vcode.release();
       }
       if (sp_sd_build(ctx) != ZZZ_OK)
       {
-        ctx->sp_sd_on = ctx->sp_sd_all = false;
+        ctx->values.sp_sd_on = ctx->values.sp_sd_all = false;
         (void)hipGetLastError();
         ctx->sp_vcode8.release();
         ctx->sp_sd_vals.release();
@@ -459,9 +459,9 @@ bool sellp_active(zzz_ctx* ctx)
         ctx->sp_sd_off.release();
       }
     }
-    ctx->sp_pairs_ok = false;
-    if (ctx->sp_one_chunk && ctx->sp_dict_on && ctx->bs == 1 && !ctx->sp_sorted)
-      ctx->sp_pairs_ok = sellp_pairs_build(ctx) == ZZZ_OK;
+    ctx->values.sp_pairs_ok = false;
+    if (ctx->values.sp_one_chunk && ctx->values.sp_dict_on && ctx->bs == 1 && !ctx->sp_sorted)
+      ctx->values.sp_pairs_ok = sellp_pairs_build(ctx) == ZZZ_OK;
   }
   return true;
 }
@@ -478,8 +478,8 @@ int64_t sellp_stream_bytes(const zzz_ctx* ctx, bool as_codes)
   if (sellp_win_serves(ctx))
     return ctx->bw_bytes;
   // (a packed slice of the one-chunk kernel: 512 B of indices and palettes for its 1 024 B of codes)
-  const int64_t packed = !as_codes && ctx->sp_pal_on && sellp_pipe_wgs(ctx, false) ? 512 * ctx->sp_pal_packed : 0;
-  return (ctx->sp_sd_on ? ctx->sp_sd_bytes : (ctx->sp_dict_on ? ctx->sp_dict_bytes : ctx->sp_bytes)) + ctx->nslices * 8 - packed; // (x windows: sp_win_bytes, reported apart)
+  const int64_t packed = !as_codes && ctx->values.sp_pal_on && sellp_pipe_wgs(ctx, false) ? 512 * ctx->sp_pal_packed : 0;
+  return (ctx->values.sp_sd_on ? ctx->sp_sd_bytes : (ctx->values.sp_dict_on ? ctx->sp_dict_bytes : ctx->values.sp_bytes)) + ctx->nslices * 8 - packed; // (x windows: sp_win_bytes, reported apart)
 }
 
 // Load policy of the product: non-temporal stream loads when one CG iteration (the stream and six vectors) cannot stay in
@@ -542,21 +542,21 @@ static void launch_one(zzz_ctx* ctx, int grid, const ProductCall& c)
   if (launch_sellp_pipe(ctx, grid, c))
     return;
   // windowed groups: their codes index the LDS window the kernel loads per group
-  const SpLayout layout = ctx->sp_sorted ? SP_SORTED : ctx->sp_win_max > 0 ? SP_WINDOWED : SP_PLAIN;
-  size_t lds = layout == SP_WINDOWED ? (size_t)ctx->sp_win_max * sizeof(double) : 0;
+  const SpLayout layout = ctx->sp_sorted ? SP_SORTED : ctx->values.sp_win_max > 0 ? SP_WINDOWED : SP_PLAIN;
+  size_t lds = layout == SP_WINDOWED ? (size_t)ctx->values.sp_win_max * sizeof(double) : 0;
   // the values: 3 the slices' own dictionaries, 2 the stream's dictionary in LDS, 1 the same in memory, 0 doubles
   int dict = 0;
-  if (ctx->sp_sd_on && layout != SP_WINDOWED)
+  if (ctx->values.sp_sd_on && layout != SP_WINDOWED)
   {
     dict = 3;
     lds = (size_t)4 * SD_MAX * sizeof(double);
   }
-  else if (ctx->sp_dict_on && ctx->sp_dict_n <= SP_DICT_LDS_ENTRIES)
+  else if (ctx->values.sp_dict_on && ctx->sp_dict_n <= SP_DICT_LDS_ENTRIES)
   {
     dict = 2;
     lds += (size_t)((ctx->sp_dict_n + 1) & ~1) * sizeof(double);
   }
-  else if (ctx->sp_dict_on)
+  else if (ctx->values.sp_dict_on)
     dict = 1;
   hipLaunchKernelGGL(sp_kernels[c.mode][c.load].k[layout][dict], dim3(grid), dim3(SP_BLOCK), lds, ctx->stream,
                      reinterpret_cast<const int2*>(ctx->sp_desc.p), ctx->sp_vals.p, ctx->sp_codes16.p, ctx->sp_codes32.p,
@@ -570,8 +570,8 @@ static void launch_one(zzz_ctx* ctx, int grid, const ProductCall& c)
 // epilogue; a partitioned product needs the form's own interior / boundary lists) and the load policy
 static int sp_prepare(zzz_ctx* ctx, ProductCall& c, bool split)
 {
-  c.special = (sellp_blk_serves(ctx) && (!split || ctx->bk_have_split)) ? 1
-              : (sellp_win_serves(ctx) && (!split || ctx->bw_have_split)) ? 2 : 0;
+  c.special = (sellp_blk_serves(ctx) && (!split || ctx->pattern.bk_have_split)) ? 1
+              : (sellp_win_serves(ctx) && (!split || ctx->pattern.bw_have_split)) ? 2 : 0;
   // load policy by stream size, as for the tile kernel: a stream that stays in the 256 MiB Infinity Cache from
   // one CG iteration to the next is read with plain loads, a larger one with non-temporal loads
   bool nt = sp_stream_nt(ctx);

@@ -695,14 +695,14 @@ static const BlkKernel blk_kernels[PM_COUNT][2] = {
 // 0.29 ms (0.37 when each thread read a run of consecutive slots), k_bk_fill 0.50 ms.
 int sellp_blk_build(zzz_ctx* ctx)
 {
-  ctx->bk_on = false;
-  if (!ctx->sellp_blk || ctx->bs != 3 || ctx->sp_sorted || ctx->nrows <= 0 || ctx->nrows % 3 != 0)
+  ctx->values.bk_on = false;
+  if (!ctx->knob.sellp_blk || ctx->bs != 3 || ctx->sp_sorted || ctx->nrows <= 0 || ctx->nrows % 3 != 0)
     return ZZZ_OK;
   if ((double)(ctx->n_owned + ctx->n_ghost) * 24.0 >= 2147483647.0)
     return ZZZ_OK; // (32-bit byte offsets into x)
   // ZZZ_SELLP_BLK: 0 never, 1 (default) from 100 000 nodes on -- below that the generic product is as fast or faster (a few
   // slices per wavefront, the table copy per workgroup: 30^3 sub-cubes 13.7 against 8.9 us, 50^3 15.6 against 16.6), 2 always
-  if (ctx->sellp_blk == 1 && ctx->nrows / 3 < 100000)
+  if (ctx->knob.sellp_blk == 1 && ctx->nrows / 3 < 100000)
     return ZZZ_OK;
   hipStream_t s = ctx->stream;
   const int nnodes = (int)(ctx->nrows / 3);
@@ -773,8 +773,8 @@ int sellp_blk_build(zzz_ctx* ctx)
     return ZZZ_OK;
   // interior / boundary slices for the halo-compute overlap of a partitioned matrix (its own lists: a slice here is 64 NODES)
   ctx->bk_n_interior = ctx->bk_n_boundary = 0;
-  ctx->bk_have_split = false;
-  if (ctx->n_ghost > 0 || ctx->have_group_split)
+  ctx->pattern.bk_have_split = false;
+  if (ctx->n_ghost > 0 || ctx->pattern.have_group_split)
   {
     std::vector<uint8_t> gf((size_t)nsl);
     ZZZ_HIP(ctx, hipMemcpyAsync(gf.data(), ctx->bk_gflag.p, gf.size(), hipMemcpyDeviceToHost, s));
@@ -791,7 +791,7 @@ int sellp_blk_build(zzz_ctx* ctx)
     ZZZ_HIP(ctx, hipStreamSynchronize(s));
     ctx->bk_n_interior = (int64_t)in.size();
     ctx->bk_n_boundary = (int64_t)bd.size();
-    ctx->bk_have_split = true;
+    ctx->pattern.bk_have_split = true;
   }
   unsigned long long bytes = 0;
   memcpy(&bytes, h + 4, sizeof(bytes));
@@ -807,12 +807,12 @@ int sellp_blk_build(zzz_ctx* ctx)
     ZZZ_HIP(ctx, hipGetLastError());
     ctx->bk_lds_attr = true;
   }
-  ctx->bk_on = true;
+  ctx->values.bk_on = true;
   return ZZZ_OK;
 }
 
 // Does the block-row kernel serve the products on this context?
-bool sellp_blk_serves(const zzz_ctx* ctx) { return ctx->bk_on && ctx->sellp_blk && ctx->bs == 3 && !ctx->sp_sorted; }
+bool sellp_blk_serves(const zzz_ctx* ctx) { return ctx->values.bk_on && ctx->knob.sellp_blk && ctx->bs == 3 && !ctx->sp_sorted; }
 
 // workgroups of a launch over `items` slices: one per CU, persistent
 int sellp_blk_grid(const zzz_ctx* ctx, int64_t items)

@@ -410,19 +410,19 @@ __global__ __launch_bounds__(128) void k_sp_sd_build(const int2* __restrict__ de
 // 10 M rows.  More than 65 535 distinct values, or ZZZ_SELLP_DICT=0: the stream keeps being read as values.
 int sp_dict_build(zzz_ctx* ctx)
 {
-  ctx->sp_dict_done = true;
-  ctx->sp_dict_on = ctx->sp_pal_on = false;
+  ctx->values.sp_dict_done = true;
+  ctx->values.sp_dict_on = ctx->values.sp_pal_on = false;
   ctx->sp_dict_n = 0;
   // ZZZ_SELLP_DICT: 0 never, 2 always (tests at small sizes), 1: for streams of more than 48 MB of values -- below that the
   // whole loop sits in the Infinity Cache, bytes are not what the product waits for, and building the dictionary (three
   // passes over the stream and a synchronisation, ~0.4 ms at 500 k rows) costs more than a solve gains
-  if (!ctx->sellp_dict || ctx->sp_chunks <= 0 || (ctx->sellp_dict == 1 && ctx->sp_bytes < 48ll << 20))
+  if (!ctx->knob.sellp_dict || ctx->values.sp_chunks <= 0 || (ctx->knob.sellp_dict == 1 && ctx->values.sp_bytes < 48ll << 20))
     return ZZZ_OK;
   hipStream_t s = ctx->stream;
   const int64_t nsl = ctx->nslices;
   ValSet<SP_DICT_BITS, 1>& vs = ctx->sp_dset;
   ZZZ_HIP(ctx, vs.begin(SP_DICT_MAX + 1, s, ctx->retired));
-  ZZZ_HIP(ctx, ctx->sp_vcode.alloc((size_t)ctx->sp_chunks * 512));
+  ZZZ_HIP(ctx, ctx->sp_vcode.alloc((size_t)ctx->values.sp_chunks * 512));
   ZZZ_HIP(ctx, ctx->sp_dict_info.reserve(4));
   ZZZ_HIP(ctx, hipMemsetAsync(ctx->sp_dict_info.p, 0, 4 * sizeof(int32_t), s));
   unsigned long long* bytes = reinterpret_cast<unsigned long long*>(ctx->sp_dict_info.p);
@@ -432,7 +432,7 @@ int sp_dict_build(zzz_ctx* ctx)
   // A dictionary too large for the LDS copy is gathered from memory: 2.3x fewer bytes at P3 6.2 M dofs (8 270 values) and the
   // same 0.61-0.63 ms per product -- the gathers, not the bytes, are what the kernel waits for -- so that form is not used
   // unless ZZZ_SELLP_DICT=2 asks for it (tests)
-  const int limit = ctx->sellp_dict == 2 ? SP_DICT_MAX - 1 : SP_DICT_LDS_ENTRIES - 2;
+  const int limit = ctx->knob.sellp_dict == 2 ? SP_DICT_MAX - 1 : SP_DICT_LDS_ENTRIES - 2;
   if (ctx->sp_sorted)
     hipLaunchKernelGGL(k_sp_dict_insert<true>, dim3(grid), dim3(256), 0, s, desc, ctx->sp_perm.p, ctx->sp_vals.p, (int)ctx->nrows, nsl,
                        vs.table.p, vs.info.p, limit);
@@ -450,11 +450,11 @@ int sp_dict_build(zzz_ctx* ctx)
   ZZZ_HIP(ctx, hipMemcpyAsync(&hb, bytes, sizeof(hb), hipMemcpyDeviceToHost, s));
   // the packed form of the codes (ZZZ_SELLP_PAL: 0 never, 1 default) for the streams spmv_one_kernel serves (sellp_pipe_wgs:
   // one-chunk slices, natural order, the dictionary in LDS): built behind the encoding, read back with the same synchronisation
-  const bool pal = ctx->sellp_pal && ctx->sp_one_chunk && !ctx->sp_sorted && ctx->bs == 1 && ctx->sp_win_max == 0;
+  const bool pal = ctx->knob.sellp_pal && ctx->values.sp_one_chunk && !ctx->sp_sorted && ctx->bs == 1 && ctx->values.sp_win_max == 0;
   int32_t hp[4] = {0, 0, 0, 0};
   if (pal)
   {
-    ZZZ_HIP(ctx, ctx->sp_pal.alloc((size_t)ctx->sp_chunks * 64));
+    ZZZ_HIP(ctx, ctx->sp_pal.alloc((size_t)ctx->values.sp_chunks * 64));
     ZZZ_HIP(ctx, ctx->sp_palok.alloc((size_t)nsl + 1));
     ZZZ_HIP(ctx, ctx->sp_pal_info.reserve(4));
     ZZZ_HIP(ctx, hipMemsetAsync(ctx->sp_pal_info.p, 0, 4 * sizeof(int32_t), s));
@@ -470,11 +470,11 @@ int sp_dict_build(zzz_ctx* ctx)
     return ZZZ_OK;
   ctx->sp_dict_n = n;
   ctx->sp_dict_bytes = (int64_t)hb + (int64_t)n * 8;
-  ctx->sp_dict_on = true;
+  ctx->values.sp_dict_on = true;
   ctx->sp_pal_packed = hp[0];
   ctx->sp_pal_maxcount = hp[1];
   ctx->sp_pal_mixed = hp[2];
-  ctx->sp_pal_on = pal && n <= SP_DICT_LDS_ENTRIES && hp[0] > 0;
+  ctx->values.sp_pal_on = pal && n <= SP_DICT_LDS_ENTRIES && hp[0] > 0;
   return ZZZ_OK;
 }
 
@@ -482,14 +482,14 @@ int sp_dict_build(zzz_ctx* ctx)
 // they take the stream below 60 % of its bytes.  ZZZ_SELLP_DICT: 0 none of this, 3 slice dictionaries whenever they apply.
 int sp_sd_build(zzz_ctx* ctx)
 {
-  ctx->sp_sd_on = ctx->sp_sd_all = false;
-  if (!ctx->sellp_dict || ctx->sp_dict_on || ctx->sp_chunks <= 0 || ctx->sp_win_max > 0)
+  ctx->values.sp_sd_on = ctx->values.sp_sd_all = false;
+  if (!ctx->knob.sellp_dict || ctx->values.sp_dict_on || ctx->values.sp_chunks <= 0 || ctx->values.sp_win_max > 0)
     return ZZZ_OK;
-  if (ctx->sellp_dict != 3 && (ctx->sp_bytes < 48ll << 20 || ctx->sp_chunks < 4 * ctx->nslices))
+  if (ctx->knob.sellp_dict != 3 && (ctx->values.sp_bytes < 48ll << 20 || ctx->values.sp_chunks < 4 * ctx->nslices))
     return ZZZ_OK; // (small streams: bytes do not matter; short rows -- P1: the table would cost as much as it saves)
   hipStream_t s = ctx->stream;
   const int64_t nsl = ctx->nslices;
-  ZZZ_HIP(ctx, ctx->sp_vcode8.alloc((size_t)ctx->sp_chunks * 512));
+  ZZZ_HIP(ctx, ctx->sp_vcode8.alloc((size_t)ctx->values.sp_chunks * 512));
   ZZZ_HIP(ctx, ctx->sp_sd_info.alloc((size_t)nsl + 1));
   ZZZ_HIP(ctx, ctx->sp_sd_off.alloc((size_t)nsl + 1));
   ZZZ_HIP(ctx, ctx->sp_dict_info.reserve(4));
@@ -525,13 +525,13 @@ int sp_sd_build(zzz_ctx* ctx)
   ZZZ_HIP(ctx, hipStreamSynchronize(s));
   unsigned long long b = 0;
   memcpy(&b, h, sizeof(b));
-  if (ctx->sellp_dict != 3 && (double)b > 0.6 * (double)ctx->sp_bytes)
+  if (ctx->knob.sellp_dict != 3 && (double)b > 0.6 * (double)ctx->values.sp_bytes)
     return ZZZ_OK;
   if ((int64_t)h[2] >= nsl)
     return ZZZ_OK; // (no slice got a dictionary: the stream is read as doubles and says so)
   ctx->sp_sd_bytes = (int64_t)b;
-  ctx->sp_sd_on = true;
-  ctx->sp_sd_all = h[2] == 0;
+  ctx->values.sp_sd_on = true;
+  ctx->values.sp_sd_all = h[2] == 0;
   return ZZZ_OK;
 }
 ZZZ_PRELOAD_TU(sellp_dict)

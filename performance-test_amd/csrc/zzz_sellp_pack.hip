@@ -1004,7 +1004,7 @@ static int sp_group_split(zzz_ctx* ctx, const uint8_t* gflag)
   hipStream_t s = ctx->stream;
   const int64_t nsl = ctx->nslices;
   ctx->n_groups_interior = ctx->n_groups_boundary = 0;
-  ctx->have_group_split = false;
+  ctx->pattern.have_group_split = false;
   if (!gflag)
     return ZZZ_OK;
   std::vector<uint8_t> h((size_t)nsl);
@@ -1028,7 +1028,7 @@ static int sp_group_split(zzz_ctx* ctx, const uint8_t* gflag)
   ZZZ_HIP(ctx, hipStreamSynchronize(s));
   ctx->n_groups_interior = (int64_t)in.size();
   ctx->n_groups_boundary = (int64_t)bd.size();
-  ctx->have_group_split = true;
+  ctx->pattern.have_group_split = true;
   return ZZZ_OK;
 }
 
@@ -1039,15 +1039,15 @@ static int sp_build_sorted(zzz_ctx* ctx, int64_t* total_out, bool sorted = true)
   hipStream_t s = ctx->stream;
   const int nrows = (int)ctx->nrows;
   const int64_t nsl = ctx->nslices;
-  const int drop = ctx->sellp_drop ? 1 : 0;
+  const int drop = ctx->knob.sellp_drop ? 1 : 0;
   ZZZ_HIP(ctx, ctx->sp_rownnz.alloc((size_t)nrows + 1));
   ZZZ_HIP(ctx, hipMemsetAsync(ctx->sp_rownnz.p + nrows, 0, sizeof(int32_t), s)); // closes the scans over nrows + 1 entries
   ZZZ_HIP(ctx, ctx->sp_nch.alloc((size_t)nsl + 1));
   ZZZ_HIP(ctx, ctx->sp_chunk_off.alloc((size_t)nsl + 1));
   ZZZ_HIP(ctx, ctx->sp_perm.alloc((size_t)nsl * 64));
   ZZZ_HIP(ctx, ctx->sp_wlast.alloc((size_t)nsl + 1));
-  const bool counted = drop && ctx->sp_rownnz_fresh; // the matrix assembly has left the counts (asm_matrix_pk_pos)
-  ctx->sp_rownnz_fresh = false;
+  const bool counted = drop && ctx->values.sp_rownnz_fresh; // the matrix assembly has left the counts (asm_matrix_pk_pos)
+  ctx->values.sp_rownnz_fresh = false;
   if (counted)
     ;
   else if (drop && ctx->nnz >= 16 * ctx->nrows) // long rows: dense sweep (short rows: a lane's row is one or two cache lines)
@@ -1097,48 +1097,48 @@ static int sp_fill_sorted(zzz_ctx* ctx, int64_t total, bool sorted = true)
   {
     // long rows: through the compacted copy (crow = scan of the kept counts padded to 8)
     const int64_t cap = ctx->nnz + 8 * ctx->nrows;
-    const bool compacted = ctx->sp_compact_fresh && ctx->sp_crow_is_cap; // the matrix assembly has written the copy already
-    ctx->sp_compact_fresh = false;
+    const bool compacted = ctx->values.sp_compact_fresh && ctx->pattern.sp_crow_is_cap; // the matrix assembly has written the copy already
+    ctx->values.sp_compact_fresh = false;
     if (!compacted)
     {
       ZZZ_HIP(ctx, ctx->sp_crow.alloc((size_t)nrows + 1));
       ZZZ_HIP(ctx, ctx->sp_cvals.alloc((size_t)cap));
       ZZZ_HIP(ctx, ctx->sp_ccols.alloc((size_t)cap));
-      ctx->sp_crow_is_cap = false;
+      ctx->pattern.sp_crow_is_cap = false;
       const auto padded = rocprim::make_transform_iterator(ctx->sp_rownnz.p, Pad8{});
       if (int rc = with_scratch(ctx, scan_excl(padded, ctx->sp_crow.p, (size_t)nrows + 1, s)))
         return rc;
       hipLaunchKernelGGL(k_sp_compact, dim3(grid_cap(nsl, 4, 8192)), dim3(256), 0, s, ctx->rowptr.p, ctx->cols.p, ctx->vals.p, nrows,
-                         nsl, ctx->sellp_drop ? 1 : 0, ctx->sp_crow.p, ctx->sp_cvals.p, ctx->sp_ccols.p);
+                         nsl, ctx->knob.sellp_drop ? 1 : 0, ctx->sp_crow.p, ctx->sp_cvals.p, ctx->sp_ccols.p);
     }
     if (sorted)
       hipLaunchKernelGGL(k_sp_fill_c<true>, dim3(grid_cap(nsl, 4, 8192)), dim3(256), 0, s, ctx->sp_crow.p, ctx->sp_rownnz.p,
                          ctx->sp_cvals.p, ctx->sp_ccols.p, nrows, nsl, ctx->sp_perm.p, desc, ctx->sp_vals.p, ctx->sp_codes16.p,
-                         ctx->sp_codes32.p, ctx->sp_meta.p, gflag, bytes, ctx->sellp_tail | ((ctx->bs == 3 && ctx->sellp_periodic) ? 4 : 0) | ((ctx->bs == 1 && ctx->sellp_align) ? 16 : 0), ctx->sp_smode.p, nopipe);
+                         ctx->sp_codes32.p, ctx->sp_meta.p, gflag, bytes, ctx->knob.sellp_tail | ((ctx->bs == 3 && ctx->knob.sellp_periodic) ? 4 : 0) | ((ctx->bs == 1 && ctx->knob.sellp_align) ? 16 : 0), ctx->sp_smode.p, nopipe);
     else
       hipLaunchKernelGGL(k_sp_fill_c<false>, dim3(grid_cap(nsl, 4, 8192)), dim3(256), 0, s, ctx->sp_crow.p, ctx->sp_rownnz.p,
                          ctx->sp_cvals.p, ctx->sp_ccols.p, nrows, nsl, (const int32_t*)nullptr, desc, ctx->sp_vals.p,
-                         ctx->sp_codes16.p, ctx->sp_codes32.p, ctx->sp_meta.p, gflag, bytes, ctx->sellp_tail | ((ctx->bs == 3 && ctx->sellp_periodic) ? 4 : 0) | ((ctx->bs == 1 && ctx->sellp_align) ? 16 : 0), ctx->sp_smode.p, nopipe);
+                         ctx->sp_codes16.p, ctx->sp_codes32.p, ctx->sp_meta.p, gflag, bytes, ctx->knob.sellp_tail | ((ctx->bs == 3 && ctx->knob.sellp_periodic) ? 4 : 0) | ((ctx->bs == 1 && ctx->knob.sellp_align) ? 16 : 0), ctx->sp_smode.p, nopipe);
   }
   else if (sorted)
     hipLaunchKernelGGL(k_sp_fill<true>, dim3(grid_cap(nsl, 4, 16384)), dim3(256), 0, s, ctx->rowptr.p, ctx->cols.p, ctx->vals.p,
-                       nrows, nsl, ctx->sellp_drop ? 1 : 0, ctx->sp_perm.p, desc, ctx->sp_vals.p, ctx->sp_codes16.p,
-                       ctx->sp_codes32.p, ctx->sp_meta.p, gflag, bytes, ctx->sellp_tail | ((ctx->bs == 3 && ctx->sellp_periodic) ? 4 : 0) | ((ctx->bs == 1 && ctx->sellp_align) ? 16 : 0), ctx->sp_smode.p, nopipe);
+                       nrows, nsl, ctx->knob.sellp_drop ? 1 : 0, ctx->sp_perm.p, desc, ctx->sp_vals.p, ctx->sp_codes16.p,
+                       ctx->sp_codes32.p, ctx->sp_meta.p, gflag, bytes, ctx->knob.sellp_tail | ((ctx->bs == 3 && ctx->knob.sellp_periodic) ? 4 : 0) | ((ctx->bs == 1 && ctx->knob.sellp_align) ? 16 : 0), ctx->sp_smode.p, nopipe);
   else
     hipLaunchKernelGGL(k_sp_fill<false>, dim3(grid_cap(nsl, 4, 16384)), dim3(256), 0, s, ctx->rowptr.p, ctx->cols.p, ctx->vals.p,
-                       nrows, nsl, ctx->sellp_drop ? 1 : 0, (const int32_t*)nullptr, desc, ctx->sp_vals.p, ctx->sp_codes16.p,
-                       ctx->sp_codes32.p, ctx->sp_meta.p, gflag, bytes, ctx->sellp_tail | ((ctx->bs == 3 && ctx->sellp_periodic) ? 4 : 0) | ((ctx->bs == 1 && ctx->sellp_align) ? 16 : 0), ctx->sp_smode.p, nopipe);
+                       nrows, nsl, ctx->knob.sellp_drop ? 1 : 0, (const int32_t*)nullptr, desc, ctx->sp_vals.p, ctx->sp_codes16.p,
+                       ctx->sp_codes32.p, ctx->sp_meta.p, gflag, bytes, ctx->knob.sellp_tail | ((ctx->bs == 3 && ctx->knob.sellp_periodic) ? 4 : 0) | ((ctx->bs == 1 && ctx->knob.sellp_align) ? 16 : 0), ctx->sp_smode.p, nopipe);
   ZZZ_HIP(ctx, hipGetLastError());
   unsigned long long hb = 0;
   int hnp = 0;
   ZZZ_HIP(ctx, hipMemcpyAsync(&hb, bytes, sizeof(hb), hipMemcpyDeviceToHost, s));
   ZZZ_HIP(ctx, hipMemcpyAsync(&hnp, nopipe, sizeof(hnp), hipMemcpyDeviceToHost, s));
   ZZZ_HIP(ctx, hipStreamSynchronize(s));
-  ctx->sp_bytes = (int64_t)hb;
-  ctx->sp_pipe_ok = hnp == 0;
-  ctx->sp_one_chunk = false; // (the synchronous builds serve long rows)
+  ctx->values.sp_bytes = (int64_t)hb;
+  ctx->values.sp_pipe_ok = hnp == 0;
+  ctx->values.sp_one_chunk = false; // (the synchronous builds serve long rows)
   ctx->sp_sorted = sorted;
-  ctx->sp_chunks = total;
+  ctx->values.sp_chunks = total;
   return sp_group_split(ctx, gflag);
 }
 
@@ -1154,7 +1154,7 @@ __global__ void k_sp_cap_len(const rp_t* __restrict__ rowptr, int nrows, int64_t
 // crow[r] and rownnz[r] only).
 int sellp_capacity_rows(zzz_ctx* ctx)
 {
-  if (ctx->sp_crow_is_cap)
+  if (ctx->pattern.sp_crow_is_cap)
     return ZZZ_OK;
   hipStream_t s = ctx->stream;
   const int nrows = (int)ctx->nrows;
@@ -1166,17 +1166,13 @@ int sellp_capacity_rows(zzz_ctx* ctx)
   if (int rc = with_scratch(ctx, scan_excl(ctx->sp_crow.p, ctx->sp_crow.p, (size_t)nrows + 1, s))) // (in place)
     return rc;
   ZZZ_HIP(ctx, hipGetLastError());
-  ctx->sp_crow_is_cap = true;
+  ctx->pattern.sp_crow_is_cap = true;
   return ZZZ_OK;
 }
 
-// Pattern-only bounds of the natural-order stream (once per pattern; one small read-back).
+// Pattern-only bounds of the natural-order stream (once per pattern, behind its forget_pattern; one small read-back).
 int sellp_pattern_bounds(zzz_ctx* ctx)
 {
-  ctx->sp_bounds_ok = false;
-  ctx->sp_crow_is_cap = false;
-  ctx->sp_compact_fresh = ctx->sp_rownnz_fresh = false;
-  ctx->have_sell = ctx->sell_current = ctx->sp_pending = false;
   if (ctx->nrows <= 0)
     return ZZZ_OK;
   hipStream_t s = ctx->stream;
@@ -1194,31 +1190,24 @@ int sellp_pattern_bounds(zzz_ctx* ctx)
   unsigned long long ch = 0;
   memcpy(&ch, &h[2], sizeof(ch));
   ctx->sp_chunk_bound = (int64_t)ch;
-  ctx->sp_bounds_ok = true;
+  ctx->pattern.sp_bounds_ok = true;
   return ZZZ_OK;
 }
 
 // (Re)build the operator stream from the CSR values (MatAssemblyEnd).  The natural-order stream is packed by ONE
 // kernel without waiting for the host; how many chunks it took (the allocator's counter) travels to pinned memory
-// behind it and is looked at when the first product is launched (sellp_resolve).
-int sell_update(zzz_ctx* ctx, bool structure)
+// behind it and is looked at when the first product is launched (sellp_resolve).  Called by ctx_adopt_values alone, behind its
+// forget_values: no stream, no special form, no dictionary, no window is on when this starts.
+int sell_update(zzz_ctx* ctx)
 {
-  (void)structure;
-  ctx->have_sell = ctx->sell_current = ctx->sp_pending = false;
-  ctx->sp_dict_done = ctx->sp_dict_on = ctx->sp_sd_on = false; // (the values changed: the dictionaries are rebuilt at the stream's first use)
-  ctx->bk_on = false;
-  ctx->bw_on = false;
-  ctx->sp_generic = ctx->sp_special_tried = false;
-  ctx->sp_win_max = 0; // (set again by the long-row packer when most groups get an x window)
-  ctx->sp_win_bytes = 0;
   const bool forced = (ctx->spmv_variant & 8) != 0 && !ctx->spmv_auto;
-  if (ctx->sellp_mode == 0 || (!ctx->spmv_auto && !forced) || !ctx->vals.p)
+  if (ctx->knob.sellp_mode == 0 || (!ctx->spmv_auto && !forced) || !ctx->vals.p)
     return ZZZ_OK;
-  if (ctx->spmv_lpr_forced >= 0) // ZZZ_SPMV_LPR: an A/B knob of the CSR tile kernel's row phase
+  if (ctx->knob.spmv_lpr_forced >= 0) // ZZZ_SPMV_LPR: an A/B knob of the CSR tile kernel's row phase
     return ZZZ_OK;
   if (ctx->nloc() >= ((int64_t)1 << 29)) // 32-bit byte offsets of the x gather
     return ZZZ_OK;
-  if (!ctx->sp_bounds_ok)
+  if (!ctx->pattern.sp_bounds_ok)
   {
     int rc = sellp_pattern_bounds(ctx);
     if (rc)
@@ -1229,18 +1218,16 @@ int sell_update(zzz_ctx* ctx, bool structure)
   // where no launch can need the generic kernel: automatic mode, no partition (the overlapped launches of a partitioned matrix
   // take their group split from the generic stream).  A launch that asks for the generic kernel after all packs it then:
   // sellp_need_generic.
-  if (ctx->sellp_mode == 1 && !forced && ctx->sellp_early && ctx->n_ghost == 0 && !ctx->comm)
+  if (ctx->knob.sellp_mode == 1 && !forced && ctx->knob.sellp_early && ctx->n_ghost == 0 && !ctx->comm)
   {
     ctx->sp_sorted = false;
     const bool serves = sellp_special_build(ctx);
-    ctx->sp_special_tried = true;
+    ctx->values.sp_special_tried = true;
     if (serves)
     {
-      ctx->sp_dict_done = true;
+      ctx->values.sp_dict_done = true;
       ctx->sp_dict_n = 0;
-      ctx->sp_pairs_ok = ctx->sp_one_chunk = ctx->sp_pipe_ok = false;
-      ctx->sp_bytes = ctx->sp_chunks = ctx->sp_kept = 0;
-      ctx->have_sell = ctx->sell_current = true;
+      ctx->values.have_sell = true; // (a special form in the stream's place: its flags and sizes stay what forget_values left)
       return ZZZ_OK;
     }
   }
@@ -1249,28 +1236,28 @@ int sell_update(zzz_ctx* ctx, bool structure)
 
 int sellp_need_generic(zzz_ctx* ctx)
 {
-  if (ctx->sp_generic)
+  if (ctx->values.sp_generic)
     return ZZZ_OK;
   int rc = sell_pack_generic(ctx);
   if (!rc)
     rc = sellp_resolve(ctx);
-  if (!rc && !(ctx->sp_generic && ctx->have_sell && ctx->sell_current))
+  if (!rc && !(ctx->values.sp_generic && ctx->values.have_sell))
     return fail(ctx, ZZZ_ERR_LIMIT, "this launch needs the generic operator stream, which this matrix does not get");
-  ctx->have_sell = ctx->sell_current = true;
+  ctx->values.have_sell = true;
   return rc;
 }
 
 int sell_pack_generic(zzz_ctx* ctx)
 {
   const bool forced = (ctx->spmv_variant & 8) != 0 && !ctx->spmv_auto;
-  ctx->sp_generic = true;
-  ctx->have_sell = ctx->sell_current = false; // (until a stream is packed below)
+  ctx->values.sp_generic = true;
+  ctx->values.have_sell = false; // (until a stream is packed below)
   hipStream_t s = ctx->stream;
   const int nrows = (int)ctx->nrows;
   const int64_t nsl = ctx->nslices;
   ZZZ_HIP(ctx, ctx->sp_desc.alloc(2 * (size_t)ctx->nslices + 2));
   ctx->sp_forced = forced;
-  if (ctx->sellp_mode == 3)
+  if (ctx->knob.sellp_mode == 3)
   {
     int64_t t1 = 0;
     int rc = sp_build_sorted(ctx, &t1);
@@ -1278,13 +1265,13 @@ int sell_pack_generic(zzz_ctx* ctx)
       rc = sp_fill_sorted(ctx, t1);
     if (rc)
       return rc;
-    ctx->have_sell = ctx->sell_current = true;
+    ctx->values.have_sell = true;
     return ZZZ_OK;
   }
   // natural order.  Not worth packing when even the pattern bound is hopeless (rows of very different lengths)
   const double full = (double)ctx->nnz + 64.0 * 512.0;
   const bool long_rows = (double)ctx->nnz >= 100.0 * (double)ctx->nrows;
-  const bool always = ctx->sellp_mode == 2 || forced;
+  const bool always = ctx->knob.sellp_mode == 2 || forced;
   if (ctx->sp_chunk_bound >= INT32_MAX)
     return ZZZ_OK;
   size_t lds = (size_t)((ctx->sp_max_range + 63) & ~63) * 12;
@@ -1294,7 +1281,7 @@ int sell_pack_generic(zzz_ctx* ctx)
   // (one wavefront per CU with up to 160 KB of staging was tried for the long rows of P3: the packing got 3 ms
   // faster, but its allocation order made the product 1.3 % slower: a net loss)
   // ZZZ_SELLP=4: take the long-row path (count / compact / pack, synchronous) whatever the row lengths (tests)
-  const bool lds_fits = lds * waves <= 160 * 1024 - 64 && (waves >= 2 || lds <= 64 * 1024) && !ctx->sellp_long_rows;
+  const bool lds_fits = lds * waves <= 160 * 1024 - 64 && (waves >= 2 || lds <= 64 * 1024) && !ctx->knob.sellp_long_rows;
   if (!lds_fits || (!always && (double)ctx->sp_chunk_bound * 512.0 > 2.2 * full))
   {
     // Synchronous builds (count, scan, read-back, fill): rows too long for the LDS staging of the one-pass packer
@@ -1310,7 +1297,7 @@ int sell_pack_generic(zzz_ctx* ctx)
       {
         rc = sp_fill_sorted(ctx, t0, false);
         if (!rc)
-          ctx->have_sell = ctx->sell_current = true;
+          ctx->values.have_sell = true;
         return rc;
       }
     }
@@ -1324,7 +1311,7 @@ int sell_pack_generic(zzz_ctx* ctx)
     rc = sp_fill_sorted(ctx, t1);
     if (rc)
       return rc;
-    ctx->have_sell = ctx->sell_current = true;
+    ctx->values.have_sell = true;
     return ZZZ_OK;
   }
   int rc = sp_alloc_stream(ctx, ctx->sp_chunk_bound);
@@ -1360,7 +1347,7 @@ int sell_pack_generic(zzz_ctx* ctx)
   ZZZ_HIP(ctx, hipMemsetAsync(ctx->sp_counter.p, 0, 4 * sizeof(int), s));
   ZZZ_HIP(ctx, hipMemsetAsync(ctx->sp_counter.p + 8, 0, 8 * sizeof(int), s)); // ([14]: "not for the pipelined product")
   const int cap = (ctx->sp_max_range + 63) & ~63;
-  const int tcodes = ctx->sellp_tail | ((ctx->bs == 3 && ctx->sellp_periodic) ? 4 : 0) | ((ctx->bs == 1 && ctx->sellp_align) ? 16 : 0);
+  const int tcodes = ctx->knob.sellp_tail | ((ctx->bs == 3 && ctx->knob.sellp_periodic) ? 4 : 0) | ((ctx->bs == 1 && ctx->knob.sellp_align) ? 16 : 0);
   // workgroups of the packer take slices in fours only when they have four wavefronts: the group of a slice is s >> 2
   // either way, and a workgroup of one or two wavefronts starts at a multiple of its size inside the group
   if (winb)
@@ -1369,18 +1356,18 @@ int sell_pack_generic(zzz_ctx* ctx)
     ZZZ_HIP(ctx, ctx->sp_win_info.alloc(2 * (size_t)ngroups));
     ZZZ_HIP(ctx, ctx->sp_win_seg.alloc(2 * (size_t)ngroups * SP_WIN_NSEG));
     hipLaunchKernelGGL(k_sp_windows, dim3((unsigned)std::min<int64_t>(ngroups, 256 * 8)), dim3(256), 0, s, ctx->rowptr.p, ctx->cols.p,
-                       ctx->vals.p, nrows, ngroups, ctx->sellp_drop ? 1 : 0, win_knob, reinterpret_cast<int2*>(ctx->sp_win_info.p),
+                       ctx->vals.p, nrows, ngroups, ctx->knob.sellp_drop ? 1 : 0, win_knob, reinterpret_cast<int2*>(ctx->sp_win_info.p),
                        reinterpret_cast<int2*>(ctx->sp_win_seg.p), reinterpret_cast<unsigned long long*>(ctx->sp_counter.p + 10));
     hipLaunchKernelGGL(k_sp_pack<true>, dim3(grid_cap(nsl, waves, 256 * 12)), dim3(64 * waves), lds * waves, s, ctx->rowptr.p,
-                       ctx->cols.p, ctx->vals.p, nrows, nsl, ctx->sellp_drop ? 1 : 0, cap, ctx->sp_counter.p,
+                       ctx->cols.p, ctx->vals.p, nrows, nsl, ctx->knob.sellp_drop ? 1 : 0, cap, ctx->sp_counter.p,
                        reinterpret_cast<int2*>(ctx->sp_desc.p), ctx->sp_vals.p, ctx->sp_codes16.p, ctx->sp_codes32.p, ctx->sp_meta.p,
                        gflag, tcodes, reinterpret_cast<const int2*>(ctx->sp_win_info.p), reinterpret_cast<const int2*>(ctx->sp_win_seg.p),
                        ctx->sp_smode.p);
-    ctx->sp_win_max = win_knob; // the product reads win_info per group; a group without a window gathers from memory
+    ctx->values.sp_win_max = win_knob; // the product reads win_info per group; a group without a window gathers from memory
   }
   else
     hipLaunchKernelGGL(k_sp_pack<false>, dim3(grid_cap(nsl, waves, 256 * 12)), dim3(64 * waves), lds * waves, s, ctx->rowptr.p,
-                       ctx->cols.p, ctx->vals.p, nrows, nsl, ctx->sellp_drop ? 1 : 0, cap, ctx->sp_counter.p,
+                       ctx->cols.p, ctx->vals.p, nrows, nsl, ctx->knob.sellp_drop ? 1 : 0, cap, ctx->sp_counter.p,
                        reinterpret_cast<int2*>(ctx->sp_desc.p), ctx->sp_vals.p, ctx->sp_codes16.p, ctx->sp_codes32.p, ctx->sp_meta.p,
                        gflag, tcodes, (const int2*)nullptr, (const int2*)nullptr, ctx->sp_smode.p);
   ZZZ_HIP(ctx, hipGetLastError());
@@ -1390,8 +1377,8 @@ int sell_pack_generic(zzz_ctx* ctx)
   ZZZ_HIP(ctx, hipMemcpyAsync(tot, ctx->sp_counter.p, 16 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
   ZZZ_HIP(ctx, hipEventRecord(ctx->sp_event, s));
   ctx->sp_sorted = false;
-  ctx->sp_pending = true;
-  ctx->have_sell = ctx->sell_current = true; // provisional until sellp_resolve has seen the size
+  ctx->values.sp_pending = true;
+  ctx->values.have_sell = true; // provisional until sellp_resolve has seen the size
   if (gflag)
     return sellp_resolve(ctx);
   return ZZZ_OK;
@@ -1400,30 +1387,30 @@ int sell_pack_generic(zzz_ctx* ctx)
 // The packed stream's size is known: keep it, or fall back (sorted form for long rows, else the CSR tile kernel).
 int sellp_resolve(zzz_ctx* ctx)
 {
-  if (!ctx->sp_pending)
+  if (!ctx->values.sp_pending)
     return ZZZ_OK;
-  ctx->sp_pending = false;
+  ctx->values.sp_pending = false;
   ZZZ_HIP(ctx, hipEventSynchronize(ctx->sp_event));
   const int32_t* hc = reinterpret_cast<int32_t*>(ctx->h_state + 5);
   const int64_t t0 = hc[0];
   unsigned long long kept = 0;
   memcpy(&kept, hc + 2, sizeof(kept));
-  ctx->sp_kept = (int64_t)kept;
+  ctx->values.sp_kept = (int64_t)kept;
   unsigned long long hb = 0;
   memcpy(&hb, hc + 8, sizeof(hb));
-  ctx->sp_bytes = (int64_t)hb;
-  ctx->sp_chunks = t0;
+  ctx->values.sp_bytes = (int64_t)hb;
+  ctx->values.sp_chunks = t0;
   unsigned long long hw = 0;
   memcpy(&hw, hc + 10, sizeof(hw));
-  ctx->sp_win_bytes = ctx->sp_win_max > 0 ? (int64_t)hw * 8 : 0;
-  ctx->sp_pipe_ok = hc[14] == 0;
-  ctx->sp_one_chunk = hc[14] == 0 && hc[15] == 0;
+  ctx->values.sp_win_bytes = ctx->values.sp_win_max > 0 ? (int64_t)hw * 8 : 0;
+  ctx->values.sp_pipe_ok = hc[14] == 0;
+  ctx->values.sp_one_chunk = hc[14] == 0 && hc[15] == 0;
   const double full = (double)ctx->nnz + 64.0 * 512.0;
-  const bool always = ctx->sellp_mode == 2 || ctx->sp_forced;
+  const bool always = ctx->knob.sellp_mode == 2 || ctx->sp_forced;
   // Natural row order unless its padding makes it slower than the alternatives: the length-sorted form (priced only
   // when the natural stream is padded by more than a third: it costs a synchronous build) or the CSR tile kernel.
-  const double c_nat = (double)(ctx->sp_bytes + ctx->nslices * 8) / 5.0, c_tile = cost_tile(ctx);
-  const bool padded = (double)t0 * 512.0 > 1.33 * (double)ctx->sp_kept + 64.0 * 512.0;
+  const double c_nat = (double)(ctx->values.sp_bytes + ctx->nslices * 8) / 5.0, c_tile = cost_tile(ctx);
+  const bool padded = (double)t0 * 512.0 > 1.33 * (double)ctx->values.sp_kept + 64.0 * 512.0;
   (void)full;
   if (always || (c_nat <= c_tile && !padded))
     return ctx->n_ghost > 0 ? sp_group_split(ctx, ctx->sp_gflag.p) : ZZZ_OK;
@@ -1434,13 +1421,13 @@ int sellp_resolve(zzz_ctx* ctx)
   const double c_srt = cost_stream(t1, true);
   if (c_nat <= c_tile && c_nat <= c_srt)
     return ctx->n_ghost > 0 ? sp_group_split(ctx, ctx->sp_gflag.p) : ZZZ_OK;
-  ctx->have_sell = ctx->sell_current = false;
+  ctx->values.have_sell = false;
   if (c_srt > c_tile)
     return ZZZ_OK;
   rc = sp_fill_sorted(ctx, t1);
   if (rc)
     return rc;
-  ctx->have_sell = ctx->sell_current = true;
+  ctx->values.have_sell = true;
   return ZZZ_OK;
 }
 ZZZ_PRELOAD_TU(sellp_pack)

@@ -586,11 +586,11 @@ int sellp_pairs_build(zzz_ctx* ctx)
 // adds: no Chebyshev epilogue.)
 int sellp_pipe_wgs(const zzz_ctx* ctx, bool sr)
 {
-  if (!ctx->sellp_pipe || !ctx->sp_pipe_ok || ctx->sp_sorted || ctx->sp_chunks <= 0)
+  if (!ctx->knob.sellp_pipe || !ctx->values.sp_pipe_ok || ctx->sp_sorted || ctx->values.sp_chunks <= 0)
     return 0;
-  if (!(ctx->sp_dict_on && ctx->sp_dict_n <= SP_DICT_LDS_ENTRIES && !ctx->sp_sd_on))
+  if (!(ctx->values.sp_dict_on && ctx->sp_dict_n <= SP_DICT_LDS_ENTRIES && !ctx->values.sp_sd_on))
     return 0;
-  if (!(ctx->sp_one_chunk && ctx->sp_pairs_ok && ctx->bs == 1 && ctx->sp_win_max == 0 && ctx->nslices < (1 << 21)))
+  if (!(ctx->values.sp_one_chunk && ctx->values.sp_pairs_ok && ctx->bs == 1 && ctx->values.sp_win_max == 0 && ctx->nslices < (1 << 21)))
     return 0;
   return sr ? SP_ONE_WGS_SR : SP_ONE_WGS;
 }
@@ -616,7 +616,7 @@ bool launch_sellp_pipe(zzz_ctx* ctx, int grid, const ProductCall& c)
   a.nslices = (int)ctx->nslices;
   product_args_tail(a, c);
   const size_t lds = (size_t)((ctx->sp_dict_n + 1) & ~1) * sizeof(double);
-  hipLaunchKernelGGL(one_kernels[ctx->sp_pal_on ? 1 : 0][c.mode][c.load], dim3(grid), dim3(SP_BLOCK), lds, ctx->stream,
+  hipLaunchKernelGGL(one_kernels[ctx->values.sp_pal_on ? 1 : 0][c.mode][c.load], dim3(grid), dim3(SP_BLOCK), lds, ctx->stream,
                      reinterpret_cast<const int2*>(ctx->sp_desc.p), ctx->sp_smode.p, ctx->sp_pairs.p, ctx->sp_vals.p, ctx->sp_codes16.p,
                      ctx->sp_meta.p, ctx->sp_vcode.p, ctx->sp_pal.p, ctx->sp_palok.p, ctx->sp_dset.dict.p, c.x, c.y, c.rvec, c.list, a);
   return true;

@@ -901,7 +901,7 @@ static int bw_structure(zzz_ctx* ctx)
   hipStream_t s = ctx->stream;
   const int32_t nrows = (int32_t)ctx->nrows;
   const int32_t nblk = (nrows + BW_R - 1) / BW_R;
-  ctx->bw_struct_ok = false;
+  ctx->pattern.bw_struct_ok = false;
   // Morton order of the rows' nodes
   // (scratch kept in the context: hipFree waits for the whole device -- other ranks' kernels on a shared GPU included)
   DevBuf<double>&dofx = ctx->bw_dofx, &bbox = ctx->bw_bbox;
@@ -974,8 +974,8 @@ static int bw_structure(zzz_ctx* ctx)
     return ZZZ_OK; // declined: a block beyond the LDS budget
   // interior / boundary blocks for the halo-compute overlap of a partitioned matrix
   ctx->bw_n_interior = ctx->bw_n_boundary = 0;
-  ctx->bw_have_split = false;
-  if (ctx->n_ghost > 0 || ctx->have_group_split)
+  ctx->pattern.bw_have_split = false;
+  if (ctx->n_ghost > 0 || ctx->pattern.have_group_split)
   {
     std::vector<uint8_t> gf((size_t)nblk);
     ZZZ_HIP(ctx, hipMemcpyAsync(gf.data(), ctx->bw_gflag.p, gf.size(), hipMemcpyDeviceToHost, s));
@@ -992,12 +992,12 @@ static int bw_structure(zzz_ctx* ctx)
     ZZZ_HIP(ctx, hipStreamSynchronize(s));
     ctx->bw_n_interior = (int64_t)in.size();
     ctx->bw_n_boundary = (int64_t)bd.size();
-    ctx->bw_have_split = true;
+    ctx->pattern.bw_have_split = true;
   }
   ctx->bw_nblk = nblk;
   ctx->bw_chunks = tot[0];
   ctx->bw_window_entries = tot[1];
-  ctx->bw_struct_ok = true;
+  ctx->pattern.bw_struct_ok = true;
   return ZZZ_OK;
 }
 
@@ -1014,28 +1014,28 @@ static const WinKernel win_kernels[PM_COUNT][2] = {
 // size 3, short rows, sorted stream, a block beyond the LDS budget, ZZZ_SELLP_BWIN=0.
 int sellp_win_build(zzz_ctx* ctx)
 {
-  ctx->bw_on = false;
+  ctx->values.bw_on = false;
   // (ZZZ_SELLP_BWIN=2 also takes P2's rows of ~27 -- the tests of the form at small sizes -- but never P1's 15)
   // (block size 3 and rows of ~44: elasticity P1 where the block-row form declined -- the generic product with its x windows is
   // faster there, 324 against 427 ms per C4 solve; its P2 / P3, rows of 80-170, take the form)
-  const int64_t min_avg = ctx->sellp_bwin == 2 ? 20 : (ctx->bs == 3 ? 64 : BW_MIN_AVG);
+  const int64_t min_avg = ctx->knob.sellp_bwin == 2 ? 20 : (ctx->bs == 3 ? 64 : BW_MIN_AVG);
   // (block size 3: the block-row form first -- elasticity P1, 2.4 x; where it declines, P2 / P3, the scalar rows are long rows like any)
-  if (!ctx->sellp_bwin || ctx->bk_on || ctx->sp_sorted || ctx->nrows <= 0 || ctx->nnz < min_avg * ctx->nrows)
+  if (!ctx->knob.sellp_bwin || ctx->values.bk_on || ctx->sp_sorted || ctx->nrows <= 0 || ctx->nnz < min_avg * ctx->nrows)
     return ZZZ_OK;
   // size rule (one MI355X, P3 / P2 cubes): rows of ~48 win from 390 k rows on (0.028 against 0.046 ms; 0.033 against 0.072 at 0.9 M;
   // about equal at 118 k), rows of ~27 from 0.9 M on (0.027 against 0.031; 0.022 against 0.016 at 275 k)
-  if (ctx->sellp_bwin == 1 && ctx->nrows < (ctx->nnz >= 40 * ctx->nrows ? 300000 : 800000))
+  if (ctx->knob.sellp_bwin == 1 && ctx->nrows < (ctx->nnz >= 40 * ctx->nrows ? 300000 : 800000))
     return ZZZ_OK;
-  if (ctx->nrows >= (int64_t)1 << 31 || ctx->order == 0 || ctx->ncells <= 0)
+  if (ctx->nrows >= (int64_t)1 << 31 || ctx->dofmap.order == 0 || ctx->ncells <= 0)
     return ZZZ_OK;
   hipStream_t s = ctx->stream;
-  if (ctx->bw_struct_version != ctx->pattern_version || !ctx->bw_struct_ok)
+  if (ctx->bw_struct_version != ctx->pattern_version || !ctx->pattern.bw_struct_ok)
   {
     ctx->bw_struct_version = ctx->pattern_version;
     if (int rc = bw_structure(ctx))
       return rc;
   }
-  if (!ctx->bw_struct_ok)
+  if (!ctx->pattern.bw_struct_ok)
     return ZZZ_OK;
   const int32_t nblk = ctx->bw_nblk;
   ZZZ_HIP(ctx, ctx->bw_dict.alloc((size_t)nblk * BW_DCAP));
@@ -1084,11 +1084,11 @@ int sellp_win_build(zzz_ctx* ctx)
     ctx->bw_dict_entries = t;
     ctx->bw_packed_planes = packed; // of 2 nblk
   }
-  ctx->bw_on = true;
+  ctx->values.bw_on = true;
   return ZZZ_OK;
 }
 
-bool sellp_win_serves(const zzz_ctx* ctx) { return ctx->bw_on && ctx->sellp_bwin && !ctx->sp_sorted; }
+bool sellp_win_serves(const zzz_ctx* ctx) { return ctx->values.bw_on && ctx->knob.sellp_bwin && !ctx->sp_sorted; }
 
 int sellp_win_grid(const zzz_ctx* ctx, int64_t items)
 {

@@ -233,7 +233,7 @@ static void launch_variant(zzz_ctx* ctx, int grid, const ProductCall& c)
   const int64_t nt = c.list ? c.nlist : ctx->ntiles;
   const int nnz_even = (int)((ctx->nnz + 1) & ~(int64_t)1); // last valid clamped index (arrays are padded by 8)
   // bit 4 of the variant: ignore the packed columns (A/B and parity of the two index streams)
-  const uint16_t* c16 = (ctx->have_cols16 && !(ctx->spmv_variant & 16)) ? ctx->cols16.p : nullptr;
+  const uint16_t* c16 = (ctx->pattern.have_cols16 && !(ctx->spmv_variant & 16)) ? ctx->cols16.p : nullptr;
   const int col_max = (int)ctx->nloc() - 1; // nloc() counts scalar entries (a clamp bs times too far read past the end of x)
   hipLaunchKernelGGL(tile_kernels[c.mode][c.load], dim3(grid), dim3(SPMV_BLOCK), 0, ctx->stream, ctx->rowptr.p, ctx->cols.p,
                      ctx->vals.p, c.x, c.y, tiles, nt, nnz_even, c.partials, c.stop, c.list, c.rvec, SPMV_PSTRIDE, c.nn_is_rr, c16,
@@ -304,7 +304,7 @@ static int launch_spmv_overlapped(zzz_ctx* ctx, double* x, double* y, double* pa
                                   int nn_is_rr, const ChebEpi* epi)
 {
   ProductCall c = product_call(ctx, x, y, partials, rvec, nn_is_rr, epi);
-  if (sellp_active(ctx) && ctx->have_group_split)
+  if (sellp_active(ctx) && ctx->pattern.have_group_split)
     return launch_sellp_overlapped(ctx, x, c, npartials);
   if (int rc = tile_prepare(ctx, c))
     return rc;
@@ -327,7 +327,7 @@ int launch_product(zzz_ctx* ctx, double* x, double* y, double* partials, int* np
 {
   if (ctx->comm)
   {
-    if (ctx->overlap && ctx->have_tile_split)
+    if (ctx->knob.overlap && ctx->pattern.have_tile_split)
       return launch_spmv_overlapped(ctx, x, y, partials, npartials, rvec, nn_is_rr, epi);
     if (int rc = comm_halo_forward(ctx, x))
       return rc;

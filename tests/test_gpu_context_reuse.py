@@ -219,8 +219,10 @@ def test_uploaded_values_and_the_assembly_after_them(name):
         same(R.observe(c, S, matrix="reassembled"), S)  # zzz_assemble_matrix alone, on the kept pattern
 
 
-@pytest.mark.parametrize("name", ["U1r", "G2"])
+@pytest.mark.parametrize("name", ["U1r", "G2", "E1r", "U3"])
 def test_pattern_build_a_second_time(name):
+    """zzz_csr_pattern_build forgets the whole pattern tier and the values behind it: also the block-row form's split (E1r) and
+    the block-window form's structure (U3), which the first build's assembly has left"""
     S = R.state(name)
     with zzz.Context(0) as c:
         S.feed(c)
@@ -304,6 +306,21 @@ def test_a_new_mesh_forgets_the_dofmap(then):
         same(R.observe(c, T), T)
 
 
+def test_a_generated_cube_forgets_the_hierarchy():
+    """zzz_cube_generate replaces the mesh as zzz_mesh_upload does: the agg hierarchy of the problem before it is declined, as
+    on a fresh context, until a set-up builds this problem's"""
+    S, T = R.state("U1r"), R.state("G1")
+    with zzz.Context(0) as c:
+        S.feed(c)
+        same(R.observe(c, S), S)
+        T.feed(c)
+        for call in (c.mg_info, lambda: c.mg_apply(np.ones(T.n)), lambda: c.mg_level_csr(1), lambda: c.mg_transfer(0, 1, np.ones(T.n))):
+            with pytest.raises(zzz.ZzzError) as e:
+                call()
+            assert e.value.code == 1, str(e.value)
+        same(R.observe(c, T), T)
+
+
 # ---- 4. refusals change nothing ------------------------------------------------------------------------------------------
 def _order_4(c, S):
     c.upload_dofmap(4, S.bs, S.P.cell_dofs, S.P.n_owned)
@@ -334,6 +351,10 @@ def _unknown_form(c, S):
     c.assemble_matrix(7)
 
 
+def _form_of_the_other_block_size(c, S):
+    c.assemble_matrix(zzz.FORM_ELASTICITY if S.bs == 1 else zzz.FORM_POISSON)
+
+
 def _mg_on_an_uploaded_feed(c, S):
     c.cg_solve(pc=zzz.PC_MG)
 
@@ -344,6 +365,7 @@ def _float_solve_at_block_size_3(c, S):
 
 REFUSED = [("U1r", _order_4), ("E1r", _order_4), ("U1r", _block_size_2), ("E1r", _block_size_2), ("U1r", _bad_facet), ("E1r", _bad_facet),
            ("U1r", _bad_coefficient), ("E1r", _bad_coefficient), ("U1r", _unknown_form), ("E1r", _unknown_form),
+           ("U1r", _form_of_the_other_block_size), ("E1r", _form_of_the_other_block_size),
            ("U1r", _mg_on_an_uploaded_feed), ("E1r", _mg_on_an_uploaded_feed), ("E1r", _float_solve_at_block_size_3),
            # a generated cube stays one (ZZZ_PC_MG keeps serving it) after an upload that was refused
            ("U1r", _bad_mesh), ("G1", _bad_mesh), ("G1", _order_4), ("G1", _bad_facet)]
