@@ -5,6 +5,7 @@
 //                    the host's poll of the device state, and the epilogue (state read-back, iteration count, norms,
 //                    history, profile averages, KSPConvergedReason)
 //   cg_report_reset  what zzz_cg_info says about a solve, at its "nothing special" values
+//   ChebPlan, cheb_first, cheb_terms   the Chebyshev-Jacobi polynomial: preconditioner and multigrid smoother
 // Not part of the ABI.
 #pragma once
 #include "zzz_device.h"
@@ -186,6 +187,42 @@ struct CgSolve
   // last_reason.  ZZZ_ERR_DIVERGED only under error_if_not_converged.
   int finish(int* iters, double* rnorm);
 };
+
+// The Chebyshev-Jacobi polynomial x = p_k(D^-1 A) D^-1 b for D^-1 A on [lo, hi] = [hi / ratio, hi]: the preconditioner
+// of ZZZ_PC_CHEBYSHEV_JACOBI and the smoother of every multigrid level.  Its constants, its work vectors (nloc doubles
+// each, of the context whose operator it applies) and the form of its terms.
+struct ChebPlan
+{
+  int degree = 0;
+  double hi = 0.0, lo = 0.0, theta = 0.0, delta = 0.0, sigma = 0.0;
+  double *g = nullptr, *d = nullptr, *d2 = nullptr; // residual of the polynomial's recurrence; its direction, two buffers
+  // terms as epilogues of their products (ChebEpi) instead of launches of their own: chebyshev_setup says where the
+  // product allows it; ZZZ_PC_CHEBYSHEV_JACOBI on the caller's context takes that, a multigrid level declines
+  bool fused = false;
+  ChebPlan() = default;
+  ChebPlan(double hi_, double ratio, int degree_)
+      : degree(degree_), hi(hi_), lo(hi_ / ratio), theta(0.5 * (hi + lo)), delta(0.5 * (hi - lo)), sigma(theta / delta)
+  {
+  }
+  // the coefficients of the next term, d_j = c1 d_(j-1) + c2 g; rho starts at 1 / sigma (the first term's) and is advanced
+  void next_term(double& rho, double& c1, double& c2) const
+  {
+    const double rhon = 1.0 / (2.0 * sigma - rho);
+    c1 = rhon * rho;
+    c2 = 2.0 * rhon / delta;
+    rho = rhon;
+  }
+};
+// The polynomial on context c (operator, inverse diagonal, n_owned * bs entries), enqueued on owner's stream and skipped
+// once owner's CgState says stop (owner is c or the context whose hierarchy c is a level of).
+//   cheb_first: g = D^-1 (b - t) or, t == null, D^-1 b (the start from zero: no product);  d = g / theta;  x (+)= d
+//   cheb_terms: terms 2 .. degree, a product of c each.  pa != null: the last one leaves g and d alone and sums the
+//               partials of <b,x> and of the test norm -- into pa / pb (vgrid of them) when it is a launch of its own,
+//               into the product's partial arrays at strides 1 and 2 (*np of them) when it is an epilogue
+int chebyshev_setup(zzz_ctx* ctx, const zzz_solver_opts* o, ChebPlan& C); // the plan of o's degree and ratio for ctx's matrix
+void cheb_first(zzz_ctx* c, zzz_ctx* owner, const ChebPlan& C, const double* b, const double* t, double* x);
+int cheb_terms(zzz_ctx* c, zzz_ctx* owner, const ChebPlan& C, const double* b, double* x, int norm = 0, double* pa = nullptr,
+               double* pb = nullptr, int* np = nullptr);
 
 // zzz_cg.hip
 void cg_report_reset(zzz_ctx* ctx); // last_pc_bound, last_solve_red_overlapped, last_solve_xdefer_k, last_solve_dinv_codes

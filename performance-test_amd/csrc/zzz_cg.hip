@@ -1127,17 +1127,15 @@ int CgSolve::finish(int* iters, double* rnorm)
   return finish_reason(ctx, o, fin, its);
 }
 
-static int cg_solve_chebyshev(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm);
+static int cg_solve_pc(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm);
 
 int cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
 {
   cg_report_reset(ctx);
   if (o->variant == ZZZ_CG_PIPE)
     return cg_solve_pipe(ctx, o, iters, rnorm); // zzz_cg_pipe.hip
-  if (o->pc == ZZZ_PC_CHEBYSHEV_JACOBI && !o->single_reduction)
-    return cg_solve_chebyshev(ctx, o, iters, rnorm);
-  if (o->pc == ZZZ_PC_MG || o->pc == ZZZ_PC_PMG || o->pc == ZZZ_PC_AGG)
-    return cg_solve_mg(ctx, o, iters, rnorm);
+  if ((o->pc == ZZZ_PC_CHEBYSHEV_JACOBI && !o->single_reduction) || o->pc == ZZZ_PC_MG || o->pc == ZZZ_PC_PMG || o->pc == ZZZ_PC_AGG)
+    return cg_solve_pc(ctx, o, iters, rnorm);
   if (o->single_reduction)
     return cg_solve_single_reduction(ctx, o, iters, rnorm);
   const int64_t n = ctx->n_owned * ctx->bs; // owned scalar rows
@@ -1330,6 +1328,9 @@ int cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
 // all-reduces.  The rest of the iteration is the classical loop's: k_update_p (test, x and p), the product, then k_cheb_xr
 // (k_update_xr's r -= alpha w with the polynomial's first term) and one product + k_cheb_step per further term; the last
 // k_cheb_step sums <r,z> and the norm.
+// The polynomial itself (ChebPlan, cheb_first, cheb_terms: zzz_cg.h) is also the smoother of every multigrid level
+// (zzz_mg.hip): one first-term kernel, one further-term kernel, one host recurrence.  The driver cg_solve_pc further down
+// is KSPCG around a preconditioner object and serves this preconditioner and the multigrid ones.
 __global__ __launch_bounds__(VB) void k_row_abs_max(const rp_t* __restrict__ rowptr, const double* __restrict__ vals,
                                                     const double* __restrict__ dinv, int64_t n, double* __restrict__ parts)
 {
@@ -1355,23 +1356,25 @@ __global__ __launch_bounds__(VB) void k_row_abs_max(const rp_t* __restrict__ row
     parts[blockIdx.x] = m;
   }
 }
-// g = D^-1 r; d = g / theta; z = d (the polynomial's first term: z_1 = 0 + d_0)
-__global__ __launch_bounds__(VB) void k_cheb_init(const int* __restrict__ stop, const double* __restrict__ r,
-                                                  const double* __restrict__ dinv, double theta, double* __restrict__ gv,
-                                                  double* __restrict__ d, double* __restrict__ z, int64_t n)
+// The polynomial's first term: g = D^-1 (b - t), d = g / theta, x = (x +) d.  t == null: the start from zero, whose
+// residual is b and costs no product (the preconditioner; a level's pre-smoother); t = A x: the start from x (the
+// post-smoother).
+__global__ __launch_bounds__(VB) void k_cheb_first(const int* __restrict__ stop, const double* __restrict__ b,
+                                                   const double* __restrict__ t, const double* __restrict__ dinv, double theta,
+                                                   double* __restrict__ gv, double* __restrict__ d, double* __restrict__ x, int64_t n)
 {
-  if (*stop)
+  if (stop && *stop)
     return;
   for (int64_t i = blockIdx.x * (int64_t)VB + threadIdx.x; i < n; i += (int64_t)gridDim.x * VB)
   {
-    const double gi = dinv[i] * r[i];
+    const double gi = t ? dinv[i] * (b[i] - t[i]) : dinv[i] * b[i];
     const double di = gi / theta;
     gv[i] = gi;
     d[i] = di;
-    z[i] = di;
+    x[i] = t ? x[i] + di : di;
   }
 }
-// k_update_xr and k_cheb_init in one pass: alpha = beta / <p,w>; r -= alpha w; g = D^-1 r; d = g / theta; z = d
+// k_update_xr and k_cheb_first from zero in one pass: alpha = beta / <p,w>; r -= alpha w; g = D^-1 r; d = g / theta; z = d
 __global__ __launch_bounds__(VB) void k_cheb_xr(CgState* __restrict__ st, const double* __restrict__ beta_hist,
                                                 double* __restrict__ alpha_hist, int it, const double* __restrict__ pw_parts,
                                                 int npw, const double* __restrict__ w, const double* __restrict__ dinv,
@@ -1417,7 +1420,7 @@ __global__ __launch_bounds__(VB) void k_cheb_step(const int* __restrict__ stop, 
                                                   const double* __restrict__ r, int norm, double* __restrict__ pa,
                                                   double* __restrict__ pb, int64_t n)
 {
-  if (*stop)
+  if (stop && *stop)
     return;
   __shared__ double sh[VB / 64];
   double sa = 0, sb = 0;
@@ -1592,33 +1595,21 @@ static int chebyshev_esteig(zzz_ctx* ctx, const zzz_solver_opts* o, int its, dou
   return ZZZ_OK;
 }
 
-// What both forms of the Chebyshev-Jacobi solve share: the polynomial's constants, its work vectors, the choice between
-// terms as product epilogues and terms as launches of their own.
-struct ChebPlan
-{
-  int degree = 3;
-  double hi = 0.0, theta = 0.0, delta = 0.0, sigma = 0.0;
-  double *g = nullptr, *d = nullptr, *d2 = nullptr; // residual of the polynomial's recurrence; its direction, two buffers
-  bool fused = false;
-};
-
-// Spectrum bound (Gershgorin, tightened by the Lanczos estimate), constants, buffers.  Runs the estimate's short Jacobi
-// solve through the classical loop: call it BEFORE the caller initialises its own solve.
-static int chebyshev_setup(zzz_ctx* ctx, const zzz_solver_opts* o, ChebPlan& C)
+// Spectrum bound (Gershgorin, tightened by the Lanczos estimate; cached per set of matrix values), constants, buffers.
+// Runs the estimate's short Jacobi solve through the classical loop: call it BEFORE the caller initialises its own solve.
+// Leaves ctx->dinv = 1 / diag(A).
+int chebyshev_setup(zzz_ctx* ctx, const zzz_solver_opts* o, ChebPlan& C)
 {
   const int64_t n = ctx->n_owned * ctx->bs;
   const bool multi = ctx->comm != nullptr;
   const int g = vgrid(n);
   hipStream_t s = ctx->stream;
-  C.degree = o->pc_degree > 0 ? o->pc_degree : 3;
-  const double ratio = o->pc_ratio > 1.0 ? o->pc_ratio : 60.0;
   hipLaunchKernelGGL(k_extract_dinv, dim3(g), dim3(VB), 0, s, ctx->rowptr.p, ctx->cols.p, ctx->vals.p, ctx->dinv.p, n, 1);
-  const int est_its = o->pc_esteig_its == 0 ? 10 : o->pc_esteig_its;
+  const zzz_ctx::ChebKey key{ctx->mat_version, o->pc_esteig_its == 0 ? 10 : o->pc_esteig_its};
   double hi = 0.0;
   // the bound belongs to the matrix, not to the solve: kept until the values change (every rank sees the same sequence of
   // assemblies and uploads, so all of them take or skip the estimate's collectives together)
-  const bool cached = ctx->cheb_version == ctx->mat_version && ctx->cheb_est_its == est_its && ctx->cheb_hi > 0.0;
-  if (cached)
+  if (ctx->cheb_key == key)
     hi = ctx->cheb_hi;
   else
   {
@@ -1636,23 +1627,18 @@ static int chebyshev_setup(zzz_ctx* ctx, const zzz_solver_opts* o, ChebPlan& C)
     hi = 1.0;
   // ... tightened by the Lanczos estimate where that is lower (Gershgorin's bound is exact for P1 Laplacians, 2, and up to
   // 2.7 x too high for P2 / P3 / elasticity, which costs 1.6 x the products); safety factor 1.1 as in PETSc
-  if (est_its > 0)
+  if (key.est_its > 0)
   {
     double ritz = 0.0;
-    if (int rc = chebyshev_esteig(ctx, o, est_its, &ritz))
+    if (int rc = chebyshev_esteig(ctx, o, key.est_its, &ritz))
       return rc;
     if (ritz > 0.0 && std::isfinite(ritz) && 1.1 * ritz < hi)
       hi = 1.1 * ritz;
   }
   ctx->cheb_hi = hi;
-  ctx->cheb_version = ctx->mat_version;
-  ctx->cheb_est_its = est_its;
+  ctx->cheb_key = key;
   }
-  const double lo = hi / ratio;
-  C.hi = hi;
-  C.theta = 0.5 * (hi + lo);
-  C.delta = 0.5 * (hi - lo);
-  C.sigma = C.theta / C.delta;
+  C = ChebPlan(hi, o->pc_ratio > 1.0 ? o->pc_ratio : 60.0, o->pc_degree > 0 ? o->pc_degree : 3);
   // On the operator stream a term is the EPILOGUE of its product (ChebEpi, zzz_sellp.hip): w = A d never travels through
   // memory and the term costs no launch of its own; d then alternates between two buffers (other lanes still gather the
   // old one).  A/B knob ZZZ_CHEB_FUSED=0: product and k_cheb_step as two launches (the tile kernel's form) -- same bits.
@@ -1673,107 +1659,173 @@ static int chebyshev_setup(zzz_ctx* ctx, const zzz_solver_opts* o, ChebPlan& C)
   return ZZZ_OK;
 }
 
-// The terms after the first of z = p_k(D^-1 A) D^-1 r (g, d and z hold the first).  dots: the LAST term also sums the
-// partials of <r,z> and of the test norm -- into the product's partial arrays at strides 1 and 2 (*np_last of them)
-// when the term is an epilogue, into pa / pb (vgrid of them) otherwise.
-static int chebyshev_terms(zzz_ctx* ctx, const ChebPlan& C, int norm, bool dots, double* pa, double* pb, int* np_last)
+void cheb_first(zzz_ctx* c, zzz_ctx* owner, const ChebPlan& C, const double* b, const double* t, double* x)
 {
-  const int64_t n = ctx->n_owned * ctx->bs;
-  const int g = vgrid(n);
-  hipStream_t s = ctx->stream;
-  const int* stop_flag = reinterpret_cast<const int*>(ctx->state.p);
-  const int nn_is_rr = norm == ZZZ_NORM_UNPRECONDITIONED ? 1 : 0;
+  const int64_t n = c->n_owned * c->bs;
+  hipLaunchKernelGGL(k_cheb_first, dim3(vgrid(n)), dim3(VB), 0, owner->stream, reinterpret_cast<const int*>(owner->state.p), b, t,
+                     c->dinv.p, C.theta, C.g, C.d, x, n);
+}
+
+int cheb_terms(zzz_ctx* c, zzz_ctx* owner, const ChebPlan& C, const double* b, double* x, int norm, double* pa, double* pb, int* np)
+{
+  const int64_t n = c->n_owned * c->bs;
+  const int* stop_flag = reinterpret_cast<const int*>(owner->state.p);
   double rho = 1.0 / C.sigma;
   double *dcur = C.d, *dalt = C.d2;
   for (int st = 1; st < C.degree; ++st)
   {
-    const bool last = dots && st + 1 == C.degree;
-    const double rhon = 1.0 / (2.0 * C.sigma - rho);
-    const double c1 = rhon * rho, c2 = 2.0 * rhon / C.delta;
-    rho = rhon;
+    const bool last = pa && st + 1 == C.degree;
+    double c1, c2;
+    C.next_term(rho, c1, c2);
     if (C.fused)
     {
       ChebEpi E;
-      E.dinv = ctx->dinv.p;
+      E.dinv = c->dinv.p;
       E.g = C.g;
-      E.z = ctx->z.p;
-      E.r = ctx->r.p;
+      E.z = x;
+      E.r = b;
       E.c1 = c1;
       E.c2 = c2;
-      if (int rc = launch_product(ctx, dcur, dalt, last ? ctx->part_a.p : nullptr, last ? np_last : nullptr, nullptr, nn_is_rr, &E))
+      if (int rc = launch_product(c, dcur, dalt, last ? c->part_a.p : nullptr, last ? np : nullptr, nullptr,
+                                  norm == ZZZ_NORM_UNPRECONDITIONED ? 1 : 0, &E))
         return rc;
       std::swap(dcur, dalt);
       continue;
     }
     // terms as launches of their own: the product's output goes to the second direction buffer (free in this form; the
-    // CG vector w is the single-reduction form's A p and must survive)
-    if (int rc = launch_product(ctx, dcur, C.d2, nullptr, nullptr))
+    // CG vector w is the single-reduction form's A p and must survive).  (Without a communicator -- every multigrid
+    // level -- launch_product is launch_spmv.)
+    if (int rc = launch_product(c, dcur, C.d2, nullptr, nullptr))
       return rc;
-    hipLaunchKernelGGL(k_cheb_step, dim3(g), dim3(VB), 0, s, stop_flag, C.d2, ctx->dinv.p, c1, c2, last ? 1 : 0, C.g, dcur,
-                       ctx->z.p, ctx->r.p, norm, pa, pb, n);
+    hipLaunchKernelGGL(k_cheb_step, dim3(vgrid(n)), dim3(VB), 0, owner->stream, stop_flag, C.d2, c->dinv.p, c1, c2, last ? 1 : 0, C.g,
+                       dcur, x, b, norm, pa, pb, n);
   }
   return ZZZ_OK;
 }
 
-static int cg_solve_chebyshev(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
+// ---- KSPCG around a preconditioner object (ZZZ_PC_CHEBYSHEV_JACOBI; ZZZ_PC_MG / _PMG / _AGG, zzz_mg.hip) -----------------
+// The scalar logic, history and reasons are the classical loop's (k_update_p with Jacobi's semantics for alpha and beta).
+// What a preconditioner brings:
+struct CgPc
 {
-  const int64_t n = ctx->n_owned * ctx->bs;
-  const int max_it = o->max_it;
-  // the scalar logic is KSPCG's with a preconditioner: k_update_p / k_update_xr take pc = Jacobi semantics for alpha, beta
+  zzz_ctx* ctx;
+  const zzz_solver_opts* o;
+  int64_t n;
+  int g;
+  double *pa, *pb; // where k_init_residual, k_update_xr and k_dots_rz leave the partials of <r,z> and of the test norm
+  const double *rz, *nn; // where apply left them: pa / pb unless it says otherwise
+  int n_rz;
+  double bound = 0.0; // zzz_cg_info's spectrum bound
+  int prof_stride = PROF_STRIDE;
+  // the host reads the state back in EVERY iteration, behind k_update_p and ahead of the product and the application it
+  // enqueues before it waits for the copy (one iteration of lag), instead of CgSolve::poll: for an iteration of a few
+  // milliseconds of device work, about ten of which make a solve
+  bool poll_each = false;
+  CgPc(zzz_ctx* c, const zzz_solver_opts* opts)
+      : ctx(c), o(opts), n(c->n_owned * c->bs), g(vgrid(n)), pa(c->part_b.p), pb(c->part_b.p + VGRID_MAX), rz(pa), nn(pb), n_rz(g)
+  {
+  }
+  virtual ~CgPc() = default;
+  // PCSetUp; sets bound, and prof_stride / poll_each where they differ.  Runs BEFORE CgSolve::begin: it may run solves of
+  // its own through the context's CG vectors.
+  virtual int setup() = 0;
+  // it < 0: z = M r behind k_init_residual (r = b);  else the residual update of iteration `it` (alpha from the npw
+  // partials of <p,w> at pw), then z = M r.  Either leaves the n_rz partials of <r,z> and of the norm at rz / nn
+  // (all-reduced into ctx->red with a communicator).
+  virtual int apply(int it, const double* pw, int npw) = 0;
+  virtual void end() {} // behind CgSolve::finish
+};
+
+struct ChebPc : CgPc
+{
+  using CgPc::CgPc;
+  ChebPlan C;
+  int setup() override
+  {
+    const int rc = chebyshev_setup(ctx, o, C);
+    bound = C.hi;
+    if (C.fused && C.degree > 1)
+    {
+      // the last term's partials sit behind the product's own (strides 1 and 2 of its partial array)
+      rz = ctx->part_a.p + SPMV_PSTRIDE;
+      nn = ctx->part_a.p + 2 * SPMV_PSTRIDE;
+    }
+    return rc;
+  }
+  int apply(int it, const double* pw, int npw) override
+  {
+    hipStream_t s = ctx->stream;
+    const int* stop_flag = reinterpret_cast<const int*>(ctx->state.p);
+    if (it < 0)
+      cheb_first(ctx, ctx, C, ctx->r.p, nullptr, ctx->z.p);
+    else
+      hipLaunchKernelGGL(k_cheb_xr, dim3(g), dim3(VB), 0, s, ctx->state.p, ctx->beta_hist.p, ctx->alpha_hist.p, it, pw, npw, ctx->w.p,
+                         ctx->dinv.p, C.theta, ctx->r.p, C.g, C.d, ctx->z.p, n);
+    if (int rc = cheb_terms(ctx, ctx, C, ctx->r.p, ctx->z.p, o->norm, pa, pb, &n_rz))
+      return rc;
+    if (C.degree == 1)
+      hipLaunchKernelGGL(k_dots_rz, dim3(g), dim3(VB), 0, s, stop_flag, ctx->r.p, ctx->z.p, n, o->norm, pa, pb);
+    return ctx->comm ? comm_reduce_allreduce(ctx, stop_flag, rz, nn, nullptr, n_rz, 2, ctx->red.p) : ZZZ_OK;
+  }
+};
+
+// "V-cycle, then k_dots_rz" in the polynomial's place; the cycle's own kernels return at once on the device's stop flag
+struct MgPc : CgPc
+{
+  using CgPc::CgPc;
+  int setup() override
+  {
+    prof_stride = 1; // (every product timed: about ten iterations of a few milliseconds each)
+    poll_each = true;
+    if (int rc = mg_setup(ctx, o)) // runs the levels' spectrum estimates through this context's CG vectors
+      return rc;
+    bound = mg_level0_bound(ctx);
+    mg_profile_begin(ctx);
+    return ZZZ_OK;
+  }
+  int apply(int it, const double* pw, int npw) override
+  {
+    hipStream_t s = ctx->stream;
+    if (it >= 0)
+      hipLaunchKernelGGL(k_update_xr<false>, dim3(g), dim3(VB), 0, s, ctx->state.p, ctx->beta_hist.p, ctx->alpha_hist.p, it, pw, npw,
+                         ctx->w.p, ctx->dinv.p, ctx->r.p, ctx->z.p, n, o->norm, pa, pb, o->variant, DinvCodes());
+    if (int rc = mg_vcycle(ctx, ctx->r.p, ctx->z.p, o->profile != 0))
+      return rc;
+    hipLaunchKernelGGL(k_dots_rz, dim3(g), dim3(VB), 0, s, reinterpret_cast<const int*>(ctx->state.p), ctx->r.p, ctx->z.p, n, o->norm, pa,
+                       pb);
+    return ZZZ_OK;
+  }
+  // the cycle of the start-up and one per iteration that ran.  Behind a finish that failed (a HIP error) last_iters is the
+  // solve's before and the mean says nothing; the call still runs, to hand the cycle's events back for the next solve.
+  void end() override { mg_profile_end(ctx, o->profile ? ctx->last_iters + 1 : 0); }
+};
+
+static int cg_solve_pc(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
+{
+  ChebPc cheb(ctx, o);
+  MgPc mg(ctx, o);
+  CgPc& M = o->pc == ZZZ_PC_CHEBYSHEV_JACOBI ? static_cast<CgPc&>(cheb) : mg;
+  const int64_t n = M.n;
+  const int max_it = o->max_it, g = M.g;
   CgParams P{o->variant, ZZZ_PC_JACOBI, o->norm, o->rtol, o->atol, o->dtol > 0.0 ? o->dtol : 1.0e4};
   const bool multi = ctx->comm != nullptr;
-  const int g = vgrid(n);
   hipStream_t s = ctx->stream;
-  ChebPlan C;
-  if (int rc = chebyshev_setup(ctx, o, C))
+  if (int rc = M.setup())
     return rc;
-  const int degree = C.degree;
-  const double hi = C.hi, theta = C.theta;
-  const bool fused = C.fused;
-  double *chd = C.d, *chg = C.g;
   CgSolve S;
-  if (int rc = S.begin(ctx, o))
+  if (int rc = S.begin(ctx, o, M.prof_stride))
     return rc;
   ZZZ_HIP(ctx, ctx->alpha_hist.reserve((size_t)max_it + 2));
   ZZZ_HIP(ctx, hipMemsetAsync(ctx->p.p, 0, sizeof(double) * ctx->p.n, s));
   ZZZ_HIP(ctx, hipMemsetAsync(ctx->u.p, 0, sizeof(double) * ctx->u.n, s)); // KSP zero initial guess
   hipLaunchKernelGGL(k_extract_dinv, dim3(g), dim3(VB), 0, s, ctx->rowptr.p, ctx->cols.p, ctx->vals.p, ctx->dinv.p, n, 1);
-
-  const int* stop_flag = reinterpret_cast<const int*>(ctx->state.p);
-  double* pa = ctx->part_b.p;
-  double* pb = ctx->part_b.p + VGRID_MAX;
-  int np_last = g;
-  // the polynomial's terms after the first, then the partials of <r,z> and the norm (all-reduced when a communicator
-  // is attached)
-  auto polynomial = [&]() -> int {
-    if (int rc = chebyshev_terms(ctx, C, P.norm, true, pa, pb, &np_last))
-      return rc;
-    if (degree == 1)
-      hipLaunchKernelGGL(k_dots_rz, dim3(g), dim3(VB), 0, s, stop_flag, ctx->r.p, ctx->z.p, n, P.norm, pa, pb);
-    if (multi)
-    {
-      if (fused && degree > 1)
-        return comm_reduce_allreduce(ctx, stop_flag, ctx->part_a.p + SPMV_PSTRIDE, ctx->part_a.p + 2 * SPMV_PSTRIDE, nullptr,
-                                     np_last, 2, ctx->red.p);
-      return comm_reduce_allreduce(ctx, stop_flag, pa, pb, nullptr, g, 2, ctx->red.p);
-    }
-    return ZZZ_OK;
-  };
   // r = b
   hipLaunchKernelGGL(k_init_residual, dim3(g), dim3(VB), 0, s, ctx->b.p, (const double*)nullptr, ctx->dinv.p, ctx->r.p, ctx->z.p, n,
-                     P.norm, pa, pb);
-  hipLaunchKernelGGL(k_cheb_init, dim3(g), dim3(VB), 0, s, stop_flag, ctx->r.p, ctx->dinv.p, theta, chg, chd, ctx->z.p, n);
-  if (int rc = polynomial())
+                     P.norm, M.pa, M.pb);
+  if (int rc = M.apply(-1, nullptr, 0))
     return rc;
-  const double *rz_src = pa, *nn_src = pb, *pw_src = ctx->part_a.p;
-  int n_rz = g;
-  if (fused && degree > 1)
-  {
-    // the last term's partials sit behind the product's own (strides 1 and 2 of its partial array)
-    rz_src = ctx->part_a.p + SPMV_PSTRIDE;
-    nn_src = ctx->part_a.p + 2 * SPMV_PSTRIDE;
-    n_rz = np_last;
-  }
+  const double *rz_src = M.rz, *nn_src = M.nn, *pw_src = ctx->part_a.p;
+  int n_rz = M.n_rz;
   if (multi)
   {
     rz_src = ctx->red.p;
@@ -1786,101 +1838,39 @@ static int cg_solve_chebyshev(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters
   {
     hipLaunchKernelGGL(k_update_p<false>, dim3(g), dim3(VB), 0, s, ctx->state.p, ctx->beta_hist.p, ctx->dp_hist.p, ctx->alpha_hist.p,
                        it, P, rz_src, nn_src, n_rz, ctx->z.p, ctx->p.p, ctx->u.p, n, 1);
+    const int slot = it % 2; // (poll_each: two of the skeleton's polling events; it waits for the copy it has just asked for)
+    if (M.poll_each)
+    {
+      ZZZ_HIP(ctx, hipMemcpyAsync(&ctx->h_state[slot], ctx->state.p, sizeof(CgState), hipMemcpyDeviceToHost, s));
+      ZZZ_HIP(ctx, hipEventRecord(S.chk_ev[slot], s));
+    }
     int np = 0;
     S.product_begin(it);
     if (int rc = S.product_end(launch_product(ctx, ctx->p.p, ctx->w.p, ctx->part_a.p, &np)))
       return rc;
     if (multi)
     {
-      if (int rc = comm_reduce_allreduce(ctx, stop_flag, ctx->part_a.p, nullptr, nullptr, np, 1, ctx->red.p + 2))
+      if (int rc = comm_reduce_allreduce(ctx, reinterpret_cast<const int*>(ctx->state.p), ctx->part_a.p, nullptr, nullptr, np, 1,
+                                         ctx->red.p + 2))
         return rc;
       np = 1;
     }
-    hipLaunchKernelGGL(k_cheb_xr, dim3(g), dim3(VB), 0, s, ctx->state.p, ctx->beta_hist.p, ctx->alpha_hist.p, it, pw_src, np,
-                       ctx->w.p, ctx->dinv.p, theta, ctx->r.p, chg, chd, ctx->z.p, n);
-    if (int rc = polynomial())
+    if (int rc = M.apply(it, pw_src, np))
       return rc;
-    if (int rc = S.poll(it + 1))
+    if (M.poll_each)
+    {
+      ZZZ_HIP(ctx, hipEventSynchronize(S.chk_ev[slot]));
+      if (ctx->h_state[slot].converged)
+        S.stop = true;
+    }
+    else if (int rc = S.poll(it + 1))
       return rc;
   }
   hipLaunchKernelGGL(k_update_p<false>, dim3(g), dim3(VB), 0, s, ctx->state.p, ctx->beta_hist.p, ctx->dp_hist.p, ctx->alpha_hist.p, it,
                      P, rz_src, nn_src, n_rz, ctx->z.p, ctx->p.p, ctx->u.p, n, 0);
-  ctx->last_pc_bound = hi;
-  return S.finish(iters, rnorm);
-}
-
-int chebyshev_bound(zzz_ctx* ctx, const zzz_solver_opts* o, double* hi)
-{
-  ChebPlan C;
-  if (int rc = chebyshev_setup(ctx, o, C))
-    return rc;
-  *hi = C.hi;
-  return ZZZ_OK;
-}
-
-// ---- KSPCG with the multigrid preconditioner (ZZZ_PC_MG / ZZZ_PC_PMG, zzz_mg.hip) -------------------------------------------------
-// cg_solve_chebyshev with "V-cycle, then k_dots_rz" in the polynomial's place: the scalar logic, history and reasons are
-// the classical loop's (k_update_p, k_update_xr).  An iteration is a few milliseconds of device work at the sizes that
-// matter and there are about ten of them, so the state is read back in EVERY iteration, behind k_update_p and ahead of
-// the product and the cycle the host enqueues before it waits for it: one iteration of lag, and the cycle's own
-// kernels return at once on the device's stop flag.
-int cg_solve_mg(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
-{
-  const int64_t n = ctx->n_owned * ctx->bs;
-  const int max_it = o->max_it;
-  CgParams P{o->variant, ZZZ_PC_JACOBI, o->norm, o->rtol, o->atol, o->dtol > 0.0 ? o->dtol : 1.0e4};
-  const int g = vgrid(n);
-  hipStream_t s = ctx->stream;
-  if (int rc = mg_setup(ctx, o)) // PCSetUp: runs the levels' spectrum estimates through this context's CG vectors
-    return rc;
-  CgSolve S;
-  if (int rc = S.begin(ctx, o, 1)) // (every product timed: about ten iterations of a few milliseconds each)
-    return rc;
-  ZZZ_HIP(ctx, ctx->alpha_hist.reserve((size_t)max_it + 2));
-  ZZZ_HIP(ctx, hipMemsetAsync(ctx->p.p, 0, sizeof(double) * ctx->p.n, s));
-  ZZZ_HIP(ctx, hipMemsetAsync(ctx->u.p, 0, sizeof(double) * ctx->u.n, s)); // KSP zero initial guess
-  hipLaunchKernelGGL(k_extract_dinv, dim3(g), dim3(VB), 0, s, ctx->rowptr.p, ctx->cols.p, ctx->vals.p, ctx->dinv.p, n, 1);
-  const int* stop_flag = reinterpret_cast<const int*>(ctx->state.p);
-  double* pa = ctx->part_b.p;
-  double* pb = ctx->part_b.p + VGRID_MAX;
-  mg_profile_begin(ctx);
-  auto precondition = [&]() -> int {
-    if (int rc = mg_vcycle(ctx, ctx->r.p, ctx->z.p, o->profile != 0))
-      return rc;
-    hipLaunchKernelGGL(k_dots_rz, dim3(g), dim3(VB), 0, s, stop_flag, ctx->r.p, ctx->z.p, n, P.norm, pa, pb);
-    return ZZZ_OK;
-  };
-  hipLaunchKernelGGL(k_init_residual, dim3(g), dim3(VB), 0, s, ctx->b.p, (const double*)nullptr, ctx->dinv.p, ctx->r.p, ctx->z.p, n,
-                     P.norm, pa, pb);
-  if (int rc = precondition())
-    return rc;
-  int it = 0;
-  for (; it < max_it && !S.stop; ++it)
-  {
-    hipLaunchKernelGGL(k_update_p<false>, dim3(g), dim3(VB), 0, s, ctx->state.p, ctx->beta_hist.p, ctx->dp_hist.p, ctx->alpha_hist.p,
-                       it, P, pa, pb, g, ctx->z.p, ctx->p.p, ctx->u.p, n, 1);
-    const int slot = it % 2; // (two of the skeleton's polling events: this form waits for the copy it has just asked for)
-    ZZZ_HIP(ctx, hipMemcpyAsync(&ctx->h_state[slot], ctx->state.p, sizeof(CgState), hipMemcpyDeviceToHost, s));
-    ZZZ_HIP(ctx, hipEventRecord(S.chk_ev[slot], s));
-    int np = 0;
-    S.product_begin(it);
-    if (int rc = S.product_end(launch_spmv(ctx, ctx->p.p, ctx->w.p, ctx->part_a.p, &np)))
-      return rc;
-    hipLaunchKernelGGL(k_update_xr<false>, dim3(g), dim3(VB), 0, s, ctx->state.p, ctx->beta_hist.p, ctx->alpha_hist.p, it,
-                       ctx->part_a.p, np, ctx->w.p, ctx->dinv.p, ctx->r.p, ctx->z.p, n, P.norm, pa, pb, P.variant, DinvCodes());
-    if (int rc = precondition())
-      return rc;
-    ZZZ_HIP(ctx, hipEventSynchronize(S.chk_ev[slot]));
-    if (ctx->h_state[slot].converged)
-      S.stop = true;
-  }
-  hipLaunchKernelGGL(k_update_p<false>, dim3(g), dim3(VB), 0, s, ctx->state.p, ctx->beta_hist.p, ctx->dp_hist.p, ctx->alpha_hist.p, it,
-                     P, pa, pb, g, ctx->z.p, ctx->p.p, ctx->u.p, n, 0);
-  ctx->last_pc_bound = mg_level0_bound(ctx);
+  ctx->last_pc_bound = M.bound;
   const int rc = S.finish(iters, rnorm);
-  // the cycle of the start-up and one per iteration that ran.  Behind a finish that failed (a HIP error) last_iters is the
-  // solve's before and the mean says nothing; the call still runs, to hand the cycle's events back for the next solve.
-  mg_profile_end(ctx, o->profile ? ctx->last_iters + 1 : 0);
+  M.end();
   return rc;
 }
 
@@ -1933,9 +1923,8 @@ static int cg_solve_single_reduction(zzz_ctx* ctx, const zzz_solver_opts* o, int
     if (!cheb)
       return ZZZ_OK;
     if (first)
-      hipLaunchKernelGGL(k_cheb_init, dim3(g), dim3(VB), 0, s, reinterpret_cast<const int*>(ctx->state.p), ctx->r.p, ctx->dinv.p,
-                         C.theta, C.g, C.d, ctx->z.p, n);
-    return chebyshev_terms(ctx, C, P.norm, false, ctx->part_b.p, ctx->part_b.p + VGRID_MAX, nullptr);
+      cheb_first(ctx, ctx, C, ctx->r.p, nullptr, ctx->z.p);
+    return cheb_terms(ctx, ctx, C, ctx->r.p, ctx->z.p);
   };
   if (int rc = polynomial(true))
     return rc;

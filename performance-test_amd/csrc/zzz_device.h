@@ -122,8 +122,8 @@ __device__ __forceinline__ void row_sums(RowSums& S, bool sr, const int& nn_is_r
 }
 
 // One term of the Chebyshev-Jacobi polynomial, w = (A d)_i given: g_i - D^-1_ii w_i and the next d_i.  The only copy of this
-// arithmetic: the products' epilogues (cheb_row), k_cheb_step (zzz_cg.hip) and k_mg_term (zzz_mg.hip) call it, so the fused
-// and unfused forms of a solver round alike, and like the oracle.
+// arithmetic: the products' epilogues (cheb_row) and k_cheb_step (zzz_cg.hip: the preconditioner's terms and the multigrid
+// smoother's) call it, so the fused and unfused forms of a solver round alike, and like the oracle.
 __device__ __forceinline__ void cheb_term(double dinv, double w, double g, double d, double c1, double c2, double& gi, double& dn)
 {
   gi = -1.0 * (dinv * w) + g;

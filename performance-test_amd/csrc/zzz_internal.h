@@ -11,7 +11,7 @@
 
 #include "../../include/zzz_abi.h"
 
-// One term of the Chebyshev-Jacobi polynomial (cg_solve_chebyshev) as the epilogue of the product of d: with
+// One term of the Chebyshev-Jacobi polynomial (cheb_terms, zzz_cg.hip) as the epilogue of the product of d: with
 // w_i = (A d)_i in the lane that owns row i,  g_i -= D^-1_ii w_i;  d'_i = c1 d_i + c2 g_i (written to the product's
 // output vector);  z_i += d'_i.  The last term leaves g and d alone and sums <r,z> and the test norm into the
 // partial arrays at strides 1 and 2.  dinv == null: the plain product.
@@ -381,8 +381,13 @@ struct zzz_ctx
   zzz::DevBuf<float> f32_x, f32_r, f32_p, f32_y;
   // ZZZ_PC_CHEBYSHEV_JACOBI: the spectrum bound of the matrix as it stands (Gershgorin and Lanczos estimate cost ~10 products
   // and ~20 all-reduces: taken once per set of matrix values, not once per solve); mat_version counts assemblies / uploads
-  uint64_t mat_version = 0, cheb_version = ~0ull;
-  int cheb_est_its = 0;
+  uint64_t mat_version = 0;
+  struct ChebKey // what cheb_hi was computed from
+  {
+    uint64_t mat_version = ~0ull;
+    int est_its = 0;
+    bool operator==(const ChebKey& k) const { return mat_version == k.mat_version && est_its == k.est_its; }
+  } cheb_key;
   double cheb_hi = 0.0;
   double last_pc_bound = 0.0; // ZZZ_PC_CHEBYSHEV_JACOBI: the spectrum bound the last solve used
 
@@ -623,9 +628,6 @@ int agg_galerkin(zzz_ctx* ctx, zzz_ctx* f, AggLevel* A, zzz_ctx* c);
 int agg_refresh(zzz_ctx* ctx, zzz_ctx* f, AggLevel* A, zzz_ctx* c);
 int agg_restrict(zzz_ctx* ctx, const int* stop, const AggLevel* A, const uint8_t* bcf, const double* rf, const double* sub, double* rc);
 int agg_prolong(zzz_ctx* ctx, const int* stop, const AggLevel* A, const uint8_t* bcf, const double* ec, double* xf, int accumulate);
-// zzz_cg.hip: the spectrum bound of D^-1 A as ZZZ_PC_CHEBYSHEV_JACOBI takes it (cached per mat_version); leaves ctx->dinv = 1 / diag(A)
-int chebyshev_bound(zzz_ctx* ctx, const zzz_solver_opts* o, double* hi);
-int cg_solve_mg(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm);
 
 // comm
 int comm_allreduce_sum(zzz_ctx* ctx, double* dev, int n);

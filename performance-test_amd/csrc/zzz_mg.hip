@@ -5,9 +5,10 @@
 // Level 0 is the caller's context.  Level l+1 is the SAME problem re-discretised on max(2, (n+1)/2) cells per axis -- a
 // child context fed by zzz_cube_generate, patterned by zzz_csr_pattern_build and assembled by zzz_assemble_matrix, on
 // the caller's stream; its product is launch_spmv in whatever stream form its matrix gets.  The levels are not nested
-// when n is odd.  What is new here: the grid transfer (closed form, no P stored), the Chebyshev-Jacobi smoother from a
-// nonzero start, the dense coarsest solve, the V-cycle.  Nothing in the cycle synchronises with the host, and every kernel
-// of it returns at once when the solve's stop flag is set.
+// when n is odd.  What is here: the grid transfer (closed form, no P stored), the dense coarsest solve, the V-cycle.  The
+// smoother is the Chebyshev-Jacobi polynomial of zzz_cg.hip (ChebPlan, cheb_first, cheb_terms: zzz_cg.h) on the level's
+// context, product and term as separate launches; the post-smoother starts from x.  Nothing in the cycle synchronises
+// with the host, and every kernel of it returns at once when the solve's stop flag is set.
 //
 // Transfer, for fine vertex (i_x, i_y, i_z) and axis a (nf / nc: fine / coarse cells of that axis):
 //   c_a = min(i_a nc_a / nf_a, nc_a - 1) in 64-bit integers;  f_a = double(i_a nc_a - c_a nf_a) / double(nf_a);
@@ -25,10 +26,12 @@
 //
 // ZZZ_PC_AGG builds its levels from the matrix instead (zzz_agg.hip: aggregates, P^T A P into child contexts that adopt the
 // CSR, the two transfers); everything else -- smoother, cycle, dense solve, caching, refresh, profiling -- is the one here.
+//
+// The three differ in MgKind alone (a level's transfer, the next level, that level's values); the set-up keeps a
+// hierarchy while its MgStructKey holds and the levels' values while its MgValuesKey holds.
 #include "zzz_cg.h"
 
 #include <algorithm>
-#include <array>
 #include <chrono>
 #include <cmath>
 #include <memory>
@@ -186,39 +189,6 @@ __global__ __launch_bounds__(VB) void k_mg_restrict(const int* __restrict__ stop
   }
 }
 
-// First term of the Chebyshev-Jacobi smoother: g = D^-1 (b - t), d = g / theta, x = (x +) d.  t == null: the start from
-// zero, whose residual is b and costs no product (k_cheb_init's form); t = A x: the start from x (the post-smoother).
-__global__ __launch_bounds__(VB) void k_mg_first(const int* __restrict__ stop, const double* __restrict__ b,
-                                                 const double* __restrict__ t, const double* __restrict__ dinv, double theta,
-                                                 double* __restrict__ gv, double* __restrict__ d, double* __restrict__ x, int64_t n)
-{
-  if (stop && *stop)
-    return;
-  for (int64_t i = blockIdx.x * (int64_t)VB + threadIdx.x; i < n; i += (int64_t)gridDim.x * VB)
-  {
-    const double gi = t ? dinv[i] * (b[i] - t[i]) : dinv[i] * b[i];
-    const double di = gi / theta;
-    gv[i] = gi;
-    d[i] = di;
-    x[i] = t ? x[i] + di : di;
-  }
-}
-// A further term, t = A d given (cheb_term): g -= D^-1 t; d = c1 d + c2 g; x += d
-__global__ __launch_bounds__(VB) void k_mg_term(const int* __restrict__ stop, const double* __restrict__ t,
-                                                const double* __restrict__ dinv, double c1, double c2, double* __restrict__ gv,
-                                                double* __restrict__ d, double* __restrict__ x, int64_t n)
-{
-  if (stop && *stop)
-    return;
-  for (int64_t i = blockIdx.x * (int64_t)VB + threadIdx.x; i < n; i += (int64_t)gridDim.x * VB)
-  {
-    double gi, dn;
-    cheb_term(dinv[i], t[i], gv[i], d[i], c1, c2, gi, dn);
-    gv[i] = gi;
-    d[i] = dn;
-    x[i] = x[i] + dn;
-  }
-}
 // The coarsest level: x = A^-1 b with the dense inverse, a wavefront per row; lane l sums columns l, l + 64, ... in
 // ascending order and the 64 sums meet in the shuffle tree -- one fixed order.
 __global__ __launch_bounds__(VB) void k_mg_dense(const int* __restrict__ stop, const double* __restrict__ ainv,
@@ -240,30 +210,62 @@ __global__ __launch_bounds__(VB) void k_mg_dense(const int* __restrict__ stop, c
     x[row] = s;
 }
 
+// How a level reaches the next coarser one -- its transfer, and where that level and its matrix values come from: the
+// same cube on half the cells (tables above), the same cube at order 1 (zzz_pmg.hip), the aggregates of its matrix
+// (zzz_agg.hip).  mg_coarsen, mg_level_values, mg_restrict and mg_prolong are the four places that tell them apart.
+enum class MgKind
+{
+  GEOM,
+  PLEVEL,
+  AGG
+};
+
 struct MgLevel
 {
   zzz_ctx* ctx = nullptr; // level 0: the caller's; else owned
-  int64_t n[3] = {0, 0, 0};
+  MgKind kind = MgKind::GEOM;
+  int64_t n[3] = {0, 0, 0}; // cells of the cube (AGG: none)
   int64_t ndof = 0;
-  int order = 1; // > 1: the Pk level of ZZZ_PC_PMG; the transfer to the next level is zzz_pmg.hip's, without tables
-  double hi = 0.0, lo = 0.0;
-  // transfer between this level and the next coarser one
+  int order = 1; // PLEVEL: the order of this level's element
+  ChebPlan cheb; // the smoother (its vectors: the level context's cheb_g, cheb_d, cheb_d2); the coarsest level has none
+  // GEOM: the transfer's tables
   MgGeom G{};
   DevBuf<int32_t> tc, rng;
   DevBuf<double> tf;
-  AggLevel* agg = nullptr; // ZZZ_PC_AGG: the aggregates of this level (zzz_agg.hip); the transfer is theirs, without tables
+  AggLevel* agg = nullptr; // AGG: the aggregates of this level
   ~MgLevel() { agg_free(agg); }
+};
+
+// what the levels were built from, and what their values were computed from: a set-up compares these
+struct MgStructKey
+{
+  uint64_t feed_version = 0, pattern_version = 0, bc_version = 0; // (pattern and Dirichlet set: the aggregates depend on both)
+  int opt_levels = 0, limit = 0;
+  bool agg = false;
+  bool operator==(const MgStructKey& k) const
+  {
+    return feed_version == k.feed_version && pattern_version == k.pattern_version && bc_version == k.bc_version
+           && opt_levels == k.opt_levels && limit == k.limit && agg == k.agg;
+  }
+};
+struct MgValuesKey
+{
+  uint64_t mat_version = ~0ull;
+  int degree = 2;
+  double ratio = 10.0;
+  int est_its = 0;
+  bool operator==(const MgValuesKey& k) const
+  {
+    return mat_version == k.mat_version && degree == k.degree && ratio == k.ratio && est_its == k.est_its;
+  }
 };
 
 struct MgHier
 {
   std::vector<std::unique_ptr<MgLevel>> lv;
   DevBuf<double> ainv, tx_in, tx_out;
-  int degree = 2, est_its = 0, opt_levels = 0, opt_limit = 0;
-  double ratio = 10.0;
-  uint64_t feed_version = 0, mat_version = ~0ull;
-  bool agg = false; // built by ZZZ_PC_AGG: kept while pattern and Dirichlet set are (the aggregates depend on both)
-  uint64_t pattern_version = 0, bc_version = 0;
+  MgStructKey skey;
+  MgValuesKey vkey;
   int setups = 0;
   double coarse_bytes = 0.0;
   double setup_ms = 0.0; // host time of the last set-up that did work (it ends synchronised)
@@ -293,9 +295,9 @@ int mg_level0_products(const zzz_ctx* ctx)
 {
   if (!ctx->mg || !ctx->mg->ready)
     return 0;
-  return ctx->mg->lv.size() > 1 ? 2 * ctx->mg->degree : 0; // degree - 1 terms, the residual, A x of the post-smoother, degree - 1 terms
+  return ctx->mg->lv.size() > 1 ? 2 * ctx->mg->vkey.degree : 0; // degree - 1 terms, the residual, A x of the post-smoother, degree - 1 terms
 }
-double mg_level0_bound(const zzz_ctx* ctx) { return ctx->mg && ctx->mg->ready ? ctx->mg->lv[0]->hi : 0.0; }
+double mg_level0_bound(const zzz_ctx* ctx) { return ctx->mg && ctx->mg->ready ? ctx->mg->lv[0]->cheb.hi : 0.0; }
 
 // The hierarchy belongs to a problem that is gone (zzz_mesh_upload): not ready, so that the zzz_mg_* entry points decline it and
 // the next set-up builds anew.  Nothing is freed here (hipFree waits for the whole device); the rebuild or the context frees it.
@@ -328,28 +330,26 @@ int mg_check(zzz_ctx* ctx, const zzz_solver_opts* o)
       return fail(ctx, ZZZ_ERR_ARG, "%s: the context has %lld ghost dofs: one rank only", tag, (long long)ctx->n_ghost);
     if (ctx->bs != 1 && ctx->bs != 3)
       return fail(ctx, ZZZ_ERR_ARG, "%s: block size %d", tag, ctx->bs);
-    if (o->pc_degree < 0 || o->pc_degree > 64 || o->pc_esteig_its > 64)
-      return fail(ctx, ZZZ_ERR_ARG, "%s: smoother degree 1..64, estimate <= 64 steps", tag);
-    if (o->pc_mg_levels < 0 || o->pc_mg_coarse_eq_limit < 0)
-      return fail(ctx, ZZZ_ERR_ARG, "%s: negative pc_mg_levels or pc_mg_coarse_eq_limit", tag);
-    return ZZZ_OK;
   }
-  if (!ctx->cube_feed)
-    return fail(ctx, ZZZ_ERR_ARG, "%s: the feed was uploaded (unstructured or host-built), not generated by "
-                                  "zzz_cube_generate: the library does not know the cube to coarsen", tag);
-  if (ctx->cube_nparts != 1 || ctx->n_ghost != 0)
-    return fail(ctx, ZZZ_ERR_ARG, "%s: the cube was generated as part of %d: one part only", tag, ctx->cube_nparts);
-  if (ctx->dofmap.order != 1 && !pmg)
-    return fail(ctx, ZZZ_ERR_ARG, "%s: order %d; P1 only (p-coarsening for P2 / P3 is -pc_type pmg, ZZZ_PC_PMG)", tag, ctx->dofmap.order);
-  if (ctx->dofmap.order < 1 || ctx->dofmap.order > 3)
-    return fail(ctx, ZZZ_ERR_ARG, "%s: order %d", tag, ctx->dofmap.order);
-  if (ctx->dofmap.order > 1 && o->pc_mg_levels == 1)
-    return fail(ctx, ZZZ_ERR_ARG, "%s: pc_mg_levels = 1 at order %d: the P%d level and the P1 level of the same cube make two at least",
-                tag, ctx->dofmap.order, ctx->dofmap.order);
-  if (ctx->dofmap.renumbered)
-    return fail(ctx, ZZZ_ERR_ARG, "%s: the context keeps an internal dof order; the transfer needs the lexicographic one", tag);
-  if (!ctx->values.have_matrix)
-    return fail(ctx, ZZZ_ERR_ARG, "%s: matrix not assembled", tag);
+  else
+  {
+    if (!ctx->cube_feed)
+      return fail(ctx, ZZZ_ERR_ARG, "%s: the feed was uploaded (unstructured or host-built), not generated by "
+                                    "zzz_cube_generate: the library does not know the cube to coarsen", tag);
+    if (ctx->cube_nparts != 1 || ctx->n_ghost != 0)
+      return fail(ctx, ZZZ_ERR_ARG, "%s: the cube was generated as part of %d: one part only", tag, ctx->cube_nparts);
+    if (ctx->dofmap.order != 1 && !pmg)
+      return fail(ctx, ZZZ_ERR_ARG, "%s: order %d; P1 only (p-coarsening for P2 / P3 is -pc_type pmg, ZZZ_PC_PMG)", tag, ctx->dofmap.order);
+    if (ctx->dofmap.order < 1 || ctx->dofmap.order > 3)
+      return fail(ctx, ZZZ_ERR_ARG, "%s: order %d", tag, ctx->dofmap.order);
+    if (ctx->dofmap.order > 1 && o->pc_mg_levels == 1)
+      return fail(ctx, ZZZ_ERR_ARG, "%s: pc_mg_levels = 1 at order %d: the P%d level and the P1 level of the same cube make two at least",
+                  tag, ctx->dofmap.order, ctx->dofmap.order);
+    if (ctx->dofmap.renumbered)
+      return fail(ctx, ZZZ_ERR_ARG, "%s: the context keeps an internal dof order; the transfer needs the lexicographic one", tag);
+    if (!ctx->values.have_matrix)
+      return fail(ctx, ZZZ_ERR_ARG, "%s: matrix not assembled", tag);
+  }
   if (o->pc_degree < 0 || o->pc_degree > 64 || o->pc_esteig_its > 64)
     return fail(ctx, ZZZ_ERR_ARG, "%s: smoother degree 1..64, estimate <= 64 steps", tag);
   if (o->pc_mg_levels < 0 || o->pc_mg_coarse_eq_limit < 0)
@@ -509,45 +509,102 @@ static int mg_child_create(zzz_ctx* ctx, int level, zzz_ctx** out)
   return ZZZ_OK;
 }
 
-// ZZZ_PC_AGG: level l + 1 from the aggregates of level l's matrix (zzz_agg.hip), until a level is small enough, the level
-// limit is reached, or an aggregation reduces the dofs by less than a factor of 2 (that level is then the last)
-static int mg_build_agg(zzz_ctx* ctx, MgHier* H, int limit, int max_levels)
+// The next coarser level below the last one, by that level's kind: its context with a pattern (AGG: with its values too,
+// the Galerkin sum makes both) and the transfer between the two.  *more stays false when the kind has none to give: a
+// cube of two cells per axis, or an aggregation that reduces the dofs by less than a factor of 2.
+static int mg_coarsen(zzz_ctx* ctx, MgHier& H, bool* more)
 {
-  H->lv.emplace_back(new MgLevel());
-  H->lv[0]->ctx = ctx;
-  H->lv[0]->order = 1; // (the order of the element says nothing here: every transfer is the aggregates')
-  H->lv[0]->ndof = ctx->n_owned * ctx->bs;
-  for (;;)
+  MgLevel& F = *H.lv.back();
+  const int l = (int)H.lv.size();
+  int64_t ncdof = 0;
+  if (F.kind == MgKind::AGG)
   {
-    MgLevel& L = *H->lv.back();
-    if (L.ndof <= limit || (int)H->lv.size() >= max_levels)
-      break;
-    L.agg = agg_new();
-    if (int rc = agg_aggregate(ctx, L.ctx, L.agg))
+    F.agg = agg_new();
+    if (int rc = agg_aggregate(ctx, F.ctx, F.agg))
       return rc;
-    const int64_t ncdof = agg_count(L.agg) * ctx->bs;
-    if (ncdof == 0 || 2 * ncdof > L.ndof)
+    ncdof = agg_count(F.agg) * ctx->bs;
+    if (ncdof == 0 || 2 * ncdof > F.ndof)
     {
-      agg_free(L.agg);
-      L.agg = nullptr;
-      break;
+      agg_free(F.agg);
+      F.agg = nullptr;
+      return ZZZ_OK;
     }
-    const int l = (int)H->lv.size();
-    H->lv.emplace_back(new MgLevel());
-    MgLevel& C = *H->lv.back();
+  }
+  else if (F.kind == MgKind::GEOM && F.n[0] <= 2 && F.n[1] <= 2 && F.n[2] <= 2)
+    return ZZZ_OK;
+  H.lv.emplace_back(new MgLevel()); // (in the hierarchy before it owns a context: every exit path destroys it)
+  MgLevel& C = *H.lv.back();
+  C.kind = F.kind == MgKind::AGG ? MgKind::AGG : MgKind::GEOM;
+  if (int rc = mg_child_create(ctx, l, &C.ctx))
+    return rc;
+  zzz_ctx* c = C.ctx;
+  *more = true;
+  if (F.kind == MgKind::AGG)
+  {
     C.ndof = ncdof;
-    if (int rc = mg_child_create(ctx, l, &C.ctx))
-      return rc;
     // (no block-window product on a level without coordinates; the other forms are packed from the CSR alone)
-    C.ctx->knob.sellp_bwin = 0;
-    if (int rc = agg_galerkin(ctx, L.ctx, L.agg, C.ctx))
+    c->knob.sellp_bwin = 0;
+    return agg_galerkin(ctx, F.ctx, F.agg, c);
+  }
+  // the same problem re-discretised at order 1: on the same cells below the Pk level, on half of them below a P1 level
+  for (int a = 0; a < 3; ++a)
+    C.n[a] = F.kind == MgKind::PLEVEL ? F.n[a] : std::max<int64_t>(2, (F.n[a] + 1) / 2);
+  C.ndof = (C.n[0] + 1) * (C.n[1] + 1) * (C.n[2] + 1) * ctx->bs;
+  if (int rc = zzz_cube_generate(c, ctx->cube_problem, 1, C.n[0], C.n[1], C.n[2], 1, 0, nullptr))
+    return child_fail(ctx, c, rc, l, "generate");
+  if (int rc = zzz_csr_pattern_build(c))
+    return child_fail(ctx, c, rc, l, "pattern");
+  if (c->dofmap.renumbered || c->n_owned * c->bs != C.ndof)
+    return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg / pmg, level %d: the generated level is not in lexicographic order", l);
+  return F.kind == MgKind::GEOM ? mg_build_tables(ctx, F, C) : ZZZ_OK;
+}
+
+// level C's matrix values (F: the level above it; built: the levels are new)
+static int mg_level_values(zzz_ctx* ctx, MgLevel& F, MgLevel& C, int l, bool built)
+{
+  if (F.kind == MgKind::AGG)
+  {
+    // (a build has just summed them; a refresh sums the new values on the kept aggregates, level by level)
+    if (!built)
+      if (int rc = agg_refresh(ctx, F.ctx, F.agg, C.ctx))
+        return child_fail(ctx, C.ctx, rc, l, "coarse values");
+    return ZZZ_OK;
+  }
+  if (int rc = zzz_assemble_matrix(C.ctx, ctx->cube_problem))
+    return child_fail(ctx, C.ctx, rc, l, "assembly");
+  return ZZZ_OK;
+}
+
+// Level 0 is the caller's context; then coarser levels until one is small enough, the level limit is reached or the kind
+// has none to give.  ZZZ_PC_PMG at order > 1: the Pk level first, then the P1 levels from the same cube on; pc_mg_levels
+// counts all, and the Pk level is never the coarsest (mg_check refuses pc_mg_levels = 1 there).
+static int mg_build(zzz_ctx* ctx, MgHier& H, bool agg, int limit, int max_levels)
+{
+  H.lv.emplace_back(new MgLevel());
+  MgLevel& L0 = *H.lv[0];
+  L0.ctx = ctx;
+  L0.ndof = ctx->n_owned * ctx->bs;
+  L0.kind = agg ? MgKind::AGG : ctx->dofmap.order > 1 ? MgKind::PLEVEL : MgKind::GEOM;
+  if (!agg) // (to the aggregates the element's order and the cube say nothing)
+  {
+    L0.order = ctx->dofmap.order;
+    for (int a = 0; a < 3; ++a)
+      L0.n[a] = ctx->cube_n[a];
+  }
+  for (bool more = true; more;)
+  {
+    const MgLevel& L = *H.lv.back();
+    if (L.kind != MgKind::PLEVEL && (L.ndof <= limit || (int)H.lv.size() >= max_levels))
+      break;
+    more = false;
+    if (int rc = mg_coarsen(ctx, H, &more))
       return rc;
   }
-  const int64_t dofs = H->lv.back()->ndof;
+  const int64_t dofs = H.lv.back()->ndof;
   if (dofs > MG_DENSE_MAX)
-    return fail(ctx, ZZZ_ERR_ARG, "-pc_type agg: the coarsest of %d levels has %lld dofs, the dense solve takes at most %lld: "
+    return fail(ctx, ZZZ_ERR_ARG, "-pc_type %s: the coarsest of %d levels has %lld dofs, the dense solve takes at most %lld: "
                                   "allow more levels (pc_mg_levels) or a lower pc_mg_coarse_eq_limit",
-                (int)H->lv.size(), (long long)dofs, (long long)MG_DENSE_MAX);
+                agg ? "agg" : "mg", (int)H.lv.size(), (long long)dofs, (long long)MG_DENSE_MAX);
   return ZZZ_OK;
 }
 
@@ -556,152 +613,68 @@ int mg_setup(zzz_ctx* ctx, const zzz_solver_opts* o)
   if (int rc = mg_check(ctx, o))
     return rc;
   const bool agg = o->pc == ZZZ_PC_AGG;
-  const int form = ctx->cube_problem;
   const int limit = o->pc_mg_coarse_eq_limit > 0 ? o->pc_mg_coarse_eq_limit : 1000;
-  int max_levels = o->pc_mg_levels > 0 ? std::min<int>(o->pc_mg_levels, MG_MAX_LEVELS) : MG_MAX_LEVELS;
-  const int degree = o->pc_degree > 0 ? o->pc_degree : 2;
-  const double ratio = o->pc_ratio > 1.0 ? o->pc_ratio : 10.0;
-  const int est_its = o->pc_esteig_its == 0 ? 10 : o->pc_esteig_its;
+  const int max_levels = o->pc_mg_levels > 0 ? std::min<int>(o->pc_mg_levels, MG_MAX_LEVELS) : MG_MAX_LEVELS;
+  const MgStructKey skey{ctx->feed_version, agg ? ctx->pattern_version : 0, agg ? ctx->bc_version : 0, o->pc_mg_levels, limit, agg};
+  const MgValuesKey vkey{ctx->mat_version, o->pc_degree > 0 ? o->pc_degree : 2, o->pc_ratio > 1.0 ? o->pc_ratio : 10.0,
+                         o->pc_esteig_its == 0 ? 10 : o->pc_esteig_its};
   MgHier* H = ctx->mg;
   bool built = false;
   const auto t_begin = std::chrono::steady_clock::now();
-  if (!H || !H->ready || H->feed_version != ctx->feed_version || H->opt_levels != o->pc_mg_levels || H->opt_limit != limit || H->agg != agg
-      || (agg && (H->pattern_version != ctx->pattern_version || H->bc_version != ctx->bc_version)))
+  if (!H || !H->ready || !(H->skey == skey))
   {
     // ---- the levels --------------------------------------------------------------------------
     mg_destroy(ctx);
-    if (agg)
+    size_t free0 = 0, free1 = 0, total = 0;
+    ZZZ_HIP(ctx, hipMemGetInfo(&free0, &total));
+    H = ctx->mg = new MgHier();
+    if (int rc = mg_build(ctx, *H, agg, limit, max_levels))
     {
-      size_t free0 = 0, free1 = 0, total = 0;
-      ZZZ_HIP(ctx, hipMemGetInfo(&free0, &total));
-      H = ctx->mg = new MgHier();
-      H->agg = true;
-      if (int rc = mg_build_agg(ctx, H, limit, max_levels))
-      {
-        mg_destroy(ctx);
-        return rc;
-      }
-      for (size_t l = 0; l + 1 < H->lv.size(); ++l)
-      {
-        zzz_ctx* c = H->lv[l]->ctx;
-        ZZZ_HIP(ctx, c->cheb_d.alloc((size_t)c->nloc()));
-        ZZZ_HIP(ctx, c->cheb_d2.alloc((size_t)c->nloc()));
-        ZZZ_HIP(ctx, c->cheb_g.alloc((size_t)c->nloc()));
-      }
-      ZZZ_HIP(ctx, hipMemGetInfo(&free1, &total));
-      H->coarse_bytes = free0 > free1 ? (double)(free0 - free1) : 0.0;
-      H->pattern_version = ctx->pattern_version;
-      H->bc_version = ctx->bc_version;
+      mg_destroy(ctx);
+      return rc;
     }
-    else
+    // smoother work vectors of every level that smooths (level 0's as ZZZ_PC_CHEBYSHEV_JACOBI allocates them)
+    for (size_t l = 0; l + 1 < H->lv.size(); ++l)
     {
-      // ZZZ_PC_PMG at order > 1: the Pk level first, then the P1 levels from the same cube on; pc_mg_levels counts all
-      const size_t high = ctx->dofmap.order > 1 ? 1 : 0;
-      std::vector<std::array<int64_t, 3>> dims;
-      if (high)
-        dims.push_back({ctx->cube_n[0], ctx->cube_n[1], ctx->cube_n[2]});
-      dims.push_back({ctx->cube_n[0], ctx->cube_n[1], ctx->cube_n[2]});
-      for (;;)
-      {
-        const auto& d = dims.back();
-        const int64_t dofs = (d[0] + 1) * (d[1] + 1) * (d[2] + 1) * ctx->bs;
-        if (dofs <= limit || (d[0] <= 2 && d[1] <= 2 && d[2] <= 2) || (int)dims.size() >= max_levels)
-          break;
-        dims.push_back({std::max<int64_t>(2, (d[0] + 1) / 2), std::max<int64_t>(2, (d[1] + 1) / 2), std::max<int64_t>(2, (d[2] + 1) / 2)});
-      }
-      {
-        const auto& d = dims.back();
-        const int64_t dofs = (d[0] + 1) * (d[1] + 1) * (d[2] + 1) * ctx->bs;
-        if (dofs > MG_DENSE_MAX)
-          return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg: the coarsest of %d levels has %lld dofs, the dense solve takes at most %lld: "
-                                        "allow more levels (pc_mg_levels) or a lower pc_mg_coarse_eq_limit",
-                      (int)dims.size(), (long long)dofs, (long long)MG_DENSE_MAX);
-      }
-      size_t free0 = 0, free1 = 0, total = 0;
-      ZZZ_HIP(ctx, hipMemGetInfo(&free0, &total));
-      H = ctx->mg = new MgHier();
-      for (size_t l = 0; l < dims.size(); ++l)
-      {
-        H->lv.emplace_back(new MgLevel());
-        MgLevel& L = *H->lv.back();
-        for (int a = 0; a < 3; ++a)
-          L.n[a] = dims[l][(size_t)a];
-        L.ndof = (L.n[0] + 1) * (L.n[1] + 1) * (L.n[2] + 1) * ctx->bs;
-        if (l == 0)
-        {
-          L.ctx = ctx;
-          L.order = ctx->dofmap.order;
-          L.ndof = ctx->n_owned * ctx->bs;
-          continue;
-        }
-        if (int rc = mg_child_create(ctx, (int)l, &L.ctx))
-          return rc;
-        zzz_ctx* c = L.ctx;
-        if (int rc = zzz_cube_generate(c, form, 1, L.n[0], L.n[1], L.n[2], 1, 0, nullptr))
-          return child_fail(ctx, c, rc, (int)l, "generate");
-        if (int rc = zzz_csr_pattern_build(c))
-          return child_fail(ctx, c, rc, (int)l, "pattern");
-        if (c->dofmap.renumbered || c->n_owned * c->bs != L.ndof)
-          return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg / pmg, level %d: the generated level is not in lexicographic order", (int)l);
-      }
-      for (size_t l = high; l + 1 < H->lv.size(); ++l)
-        if (int rc = mg_build_tables(ctx, *H->lv[l], *H->lv[l + 1]))
-          return rc;
-      // smoother work vectors of every level that smooths (level 0's as ZZZ_PC_CHEBYSHEV_JACOBI allocates them)
-      for (size_t l = 0; l + 1 < H->lv.size(); ++l)
-      {
-        zzz_ctx* c = H->lv[l]->ctx;
-        ZZZ_HIP(ctx, c->cheb_d.alloc((size_t)c->nloc()));
-        ZZZ_HIP(ctx, c->cheb_d2.alloc((size_t)c->nloc()));
-        ZZZ_HIP(ctx, c->cheb_g.alloc((size_t)c->nloc()));
-      }
-      ZZZ_HIP(ctx, hipMemGetInfo(&free1, &total));
-      H->coarse_bytes = free0 > free1 ? (double)(free0 - free1) : 0.0; // (set-up scratch of the levels included; level 0's smoother vectors too)
+      zzz_ctx* c = H->lv[l]->ctx;
+      ZZZ_HIP(ctx, c->cheb_d.alloc((size_t)c->nloc()));
+      ZZZ_HIP(ctx, c->cheb_d2.alloc((size_t)c->nloc()));
+      ZZZ_HIP(ctx, c->cheb_g.alloc((size_t)c->nloc()));
     }
-    H->feed_version = ctx->feed_version;
-    H->opt_levels = o->pc_mg_levels;
-    H->opt_limit = limit;
-    H->mat_version = ~0ull;
+    ZZZ_HIP(ctx, hipMemGetInfo(&free1, &total));
+    H->coarse_bytes = free0 > free1 ? (double)(free0 - free1) : 0.0; // (set-up scratch of the levels included; level 0's smoother vectors too)
+    H->skey = skey; // (H->vkey: of no matrix yet)
     built = true;
   }
-  const bool values = built || H->mat_version != ctx->mat_version;
-  if (values || H->degree != degree || H->ratio != ratio || H->est_its != est_its)
+  if (!(H->vkey == vkey))
   {
+    const bool values = H->vkey.mat_version != vkey.mat_version;
     H->ready = false;
     // ---- the levels' values: matrices, inverse diagonals, spectrum bounds, the coarsest inverse ----
     zzz_solver_opts os = *o;
     os.variant = ZZZ_CG_PETSC;
     os.op = ZZZ_OP_CSR;
     os.single_reduction = 0;
-    os.pc_esteig_its = o->pc_esteig_its;
+    os.pc_degree = vkey.degree;
+    os.pc_ratio = vkey.ratio;
     for (size_t l = 0; l < H->lv.size(); ++l)
     {
       MgLevel& L = *H->lv[l];
       zzz_ctx* c = L.ctx;
-      if (l > 0 && values && agg)
-      {
-        // (a build has just summed them; a refresh sums the new values on the kept aggregates, level by level)
-        if (!built)
-          if (int rc = agg_refresh(ctx, H->lv[l - 1]->ctx, H->lv[l - 1]->agg, c))
-            return child_fail(ctx, c, rc, (int)l, "coarse values");
-      }
-      else if (l > 0 && values)
-        if (int rc = zzz_assemble_matrix(c, form))
-          return child_fail(ctx, c, rc, (int)l, "assembly");
-      L.hi = L.lo = 0.0;
+      if (l > 0 && values)
+        if (int rc = mg_level_values(ctx, *H->lv[l - 1], L, (int)l, built))
+          return rc;
+      L.cheb = ChebPlan();
       if (l + 1 == H->lv.size())
         break;
-      if (int rc = chebyshev_bound(c, &os, &L.hi)) // (leaves c->dinv = 1 / diag(A))
+      if (int rc = chebyshev_setup(c, &os, L.cheb)) // (the level's own bound; leaves c->dinv = 1 / diag(A))
         return l > 0 ? child_fail(ctx, c, rc, (int)l, "spectrum bound") : rc;
-      L.lo = L.hi / ratio;
+      L.cheb.fused = false; // (a level's product and term stay two launches)
     }
     if (values)
       if (int rc = mg_dense_inverse(ctx, *H))
         return rc;
-    H->degree = degree;
-    H->ratio = ratio;
-    H->est_its = est_its;
-    H->mat_version = ctx->mat_version;
+    H->vkey = vkey;
     ++H->setups;
     H->ready = true;
     ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -719,10 +692,15 @@ int mg_setup(zzz_ctx* ctx, const zzz_solver_opts* o)
 
 static int mg_restrict(zzz_ctx* ctx, const int* stop, MgLevel& F, MgLevel& C, const double* rf, const double* sub, double* rc)
 {
-  if (F.agg)
+  switch (F.kind)
+  {
+  case MgKind::AGG:
     return agg_restrict(ctx, stop, F.agg, F.ctx->bc.p, rf, sub, rc);
-  if (F.order > 1)
+  case MgKind::PLEVEL:
     return pmg_restrict(ctx, stop, F.order, ctx->bs, F.n, F.ctx->bc.p, C.ctx->bc.p, rf, sub, rc);
+  case MgKind::GEOM:
+    break;
+  }
   const int g = vgrid(F.G.ncv * 8); // (a thread walks up to 64 fine vertices: one coarse vertex per thread, no striding)
   if (ctx->bs == 3)
     hipLaunchKernelGGL(k_mg_restrict<3>, dim3(g), dim3(VB), 0, ctx->stream, stop, F.G, F.tc.p, F.tf.p, F.rng.p, F.ctx->bc.p, C.ctx->bc.p,
@@ -734,53 +712,36 @@ static int mg_restrict(zzz_ctx* ctx, const int* stop, MgLevel& F, MgLevel& C, co
 }
 static int mg_prolong(zzz_ctx* ctx, const int* stop, MgLevel& F, MgLevel& C, const double* ec, double* xf, int accumulate)
 {
-  if (F.agg)
+  switch (F.kind)
+  {
+  case MgKind::AGG:
     return agg_prolong(ctx, stop, F.agg, F.ctx->bc.p, ec, xf, accumulate);
-  if (F.order > 1)
+  case MgKind::PLEVEL:
     return pmg_prolong(ctx, stop, F.order, ctx->bs, F.n, F.ctx->bc.p, C.ctx->bc.p, ec, xf, accumulate);
+  case MgKind::GEOM:
+    break;
+  }
   hipLaunchKernelGGL(k_mg_prolong, dim3(vgrid(F.G.nfv * 4)), dim3(VB), 0, ctx->stream, stop, F.G, F.tc.p, F.tf.p, F.ctx->bc.p, C.ctx->bc.p,
                      ec, xf, accumulate);
   return ZZZ_OK;
 }
 
-// terms 2 .. degree of the smoother on level L (g, d and x hold the first)
-static int mg_terms(zzz_ctx* ctx, const int* stop, const MgHier& H, MgLevel& L, double* x)
-{
-  zzz_ctx* c = L.ctx;
-  const int64_t n = c->n_owned * c->bs;
-  const double theta = 0.5 * (L.hi + L.lo), delta = 0.5 * (L.hi - L.lo), sigma = theta / delta;
-  double rho = 1.0 / sigma;
-  for (int st = 1; st < H.degree; ++st)
-  {
-    const double rhon = 1.0 / (2.0 * sigma - rho);
-    const double c1 = rhon * rho, c2 = 2.0 * rhon / delta;
-    rho = rhon;
-    if (int rc = launch_spmv(c, c->cheb_d.p, c->cheb_d2.p, nullptr, nullptr))
-      return rc;
-    hipLaunchKernelGGL(k_mg_term, dim3(vgrid(n)), dim3(VB), 0, ctx->stream, stop, c->cheb_d2.p, c->dinv.p, c1, c2, c->cheb_g.p,
-                       c->cheb_d.p, x, n);
-  }
-  return ZZZ_OK;
-}
-
+// (the smoother is the polynomial of zzz_cg.hip on the level's context: product and term as separate launches)
 static int mg_cycle_level(zzz_ctx* ctx, const int* stop, MgHier& H, size_t l, const double* b, double* x)
 {
   MgLevel& L = *H.lv[l];
   zzz_ctx* c = L.ctx;
-  const int64_t n = c->n_owned * c->bs;
-  hipStream_t s = ctx->stream;
   if (l + 1 == H.lv.size())
   {
-    hipLaunchKernelGGL(k_mg_dense, dim3((unsigned)((n + VB / 64 - 1) / (VB / 64))), dim3(VB), 0, s, stop, H.ainv.p, b, x, (int)n);
+    const int64_t n = c->n_owned * c->bs;
+    hipLaunchKernelGGL(k_mg_dense, dim3((unsigned)((n + VB / 64 - 1) / (VB / 64))), dim3(VB), 0, ctx->stream, stop, H.ainv.p, b, x, (int)n);
     return ZZZ_OK;
   }
   MgLevel& C = *H.lv[l + 1];
-  const double theta = 0.5 * (L.hi + L.lo);
-  const int g = vgrid(n);
-  double* t = c->cheb_d2.p;
+  double* t = L.cheb.d2;
   // pre-smoother from zero
-  hipLaunchKernelGGL(k_mg_first, dim3(g), dim3(VB), 0, s, stop, b, (const double*)nullptr, c->dinv.p, theta, c->cheb_g.p, c->cheb_d.p, x, n);
-  if (int rc = mg_terms(ctx, stop, H, L, x))
+  cheb_first(c, ctx, L.cheb, b, nullptr, x);
+  if (int rc = cheb_terms(c, ctx, L.cheb, b, x))
     return rc;
   // coarse correction: r_c = P~^T (b - A x), e_c = M_c r_c, x += P~ e_c
   if (int rc = launch_spmv(c, x, t, nullptr, nullptr))
@@ -794,8 +755,8 @@ static int mg_cycle_level(zzz_ctx* ctx, const int* stop, MgHier& H, size_t l, co
   // post-smoother from x: the same polynomial
   if (int rc = launch_spmv(c, x, t, nullptr, nullptr))
     return rc;
-  hipLaunchKernelGGL(k_mg_first, dim3(g), dim3(VB), 0, s, stop, b, (const double*)t, c->dinv.p, theta, c->cheb_g.p, c->cheb_d.p, x, n);
-  return mg_terms(ctx, stop, H, L, x);
+  cheb_first(c, ctx, L.cheb, b, t, x);
+  return cheb_terms(c, ctx, L.cheb, b, x);
 }
 
 int mg_vcycle(zzz_ctx* ctx, const double* r, double* z, bool timed)
@@ -891,7 +852,7 @@ int zzz_mg_info(zzz_ctx* ctx, int level, double out[8])
     out[4] = H->coarse_bytes;
     out[5] = H->cycle_ms;
     out[6] = H->setup_ms;
-    out[7] = H->lv[0]->order > 1 ? 1.0 : 0.0;
+    out[7] = H->lv[0]->kind == MgKind::PLEVEL ? 1.0 : 0.0;
     return ZZZ_OK;
   }
   if ((size_t)level >= H->lv.size())
@@ -903,9 +864,9 @@ int zzz_mg_info(zzz_ctx* ctx, int level, double out[8])
   out[3] = (double)L.ndof;
   out[4] = (double)L.ctx->nnz;
   const bool smooths = (size_t)level + 1 < H->lv.size();
-  out[5] = smooths ? L.hi : 0.0;
-  out[6] = smooths ? L.lo : 0.0;
-  out[7] = smooths ? (double)H->degree : 0.0;
+  out[5] = smooths ? L.cheb.hi : 0.0;
+  out[6] = smooths ? L.cheb.lo : 0.0;
+  out[7] = smooths ? (double)L.cheb.degree : 0.0;
   return ZZZ_OK;
 }
 

@@ -29,7 +29,7 @@ def cycles(rows):
     """lists of dispatch indices [first smoother kernel of level 0 .. last kernel before the next k_dots_rz]"""
     out, cur = [], None
     for i, (_, _, name) in enumerate(rows):
-        if "k_mg_" not in name and cur is None:
+        if "k_mg_" not in name and "k_cheb_first" not in name and cur is None:  # (the smoother's kernels are zzz_cg.hip's)
             continue
         if cur is None:
             cur = [i]

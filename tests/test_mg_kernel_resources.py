@@ -13,8 +13,9 @@ from _kernel_resources import HIPCC, kernel_resources
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
 def test_mg_kernels_have_no_scratch_and_the_transfer_keeps_four_waves():
     seen = {}
-    for name, k in kernel_resources("zzz_mg.hip").items():
-        m = re.match(r"_ZN3zzz\d+(k_mg_[a-z]+)", name)
+    # (the smoother's two kernels are the Chebyshev-Jacobi polynomial's, csrc/zzz_cg.hip)
+    for name, k in list(kernel_resources("zzz_mg.hip").items()) + list(kernel_resources("zzz_cg.hip").items()):
+        m = re.match(r"_ZN3zzz\d+(k_mg_[a-z]+|k_cheb_first|k_cheb_step)", name)
         if not m:
             continue
         print(name, k)
@@ -23,4 +24,4 @@ def test_mg_kernels_have_no_scratch_and_the_transfer_keeps_four_waves():
             assert k["occ"] >= 4 and k["vgprs"] <= 128, (name, k)
         seen[m.group(1)] = seen.get(m.group(1), 0) + 1
     # prolongation, restriction for block size 1 and 3, the smoother's two terms, the dense coarsest solve
-    assert seen == {"k_mg_prolong": 1, "k_mg_restrict": 2, "k_mg_first": 1, "k_mg_term": 1, "k_mg_dense": 1}
+    assert seen == {"k_mg_prolong": 1, "k_mg_restrict": 2, "k_cheb_first": 1, "k_cheb_step": 1, "k_mg_dense": 1}
