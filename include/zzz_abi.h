@@ -536,6 +536,17 @@ int zzz_spmv_info(zzz_ctx* ctx, int64_t info[8]);
  * codes met in one slot of one slice (a slice is packed when no slot holds more than 16). */
 int zzz_spmv_values_info(zzz_ctx* ctx, int64_t info[4]);
 int zzz_spmv_values_info2(zzz_ctx* ctx, int n, int64_t* info);
+/* The path the last zzz_csr_pattern_build took through its kernels and fallbacks (csrc/zzz_pattern.hip), for
+ * tests that pin a connectivity to a path: info[0] = how the dof -> cell adjacency was built: 1 without a sort, from the
+ * monotone runs of the connectivity, 2 by the radix sort from the start, 3 by the sort after a window of the sort-free build
+ * overflowed (the next build of the same dofmap answers 2: it remembers), 0 on the host; info[1] = the runs it was built
+ * from (0 unless info[0] = 1); info[2] = P1: 16 or 32, the column cap of the thread-per-row kernel that sufficed, 0 when a
+ * wavefront per row built the rows (always at P2 / P3), -1 on the host; info[3] = the builder: 0 device, 1 host after the
+ * device refused (a row of more candidate columns than it holds), 2 host by ZZZ_PATTERN=host; info[4] = unique block columns
+ * of the longest block row; info[5] = 1 when the transposed adjacency came from the P1 pattern kernel, 0 from its own pass;
+ * info[6] = 1 when the build left the positions of the element-matrix entries for the P2 / P3 assembly (else it searches the
+ * columns); info[7] = 0.  ZZZ_ERR_ARG without a pattern.  (A new entry point: ZZZ_ABI_VERSION is unchanged.) */
+int zzz_pattern_info(zzz_ctx* ctx, int64_t info[8]);
 /* ---- geometric multigrid (ZZZ_PC_MG, ZZZ_PC_PMG) ----------------------------------------------
  * PCSetUp(PCMG) behind solver.set_from_options() (src/poisson_problem.cpp:169; README.md:59-146): builds the hierarchy
  * for these options, or refreshes its values after an assembly.  Optional: zzz_cg_solve(pc = ZZZ_PC_MG) does it on first

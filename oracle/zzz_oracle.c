@@ -909,9 +909,11 @@ i64 zo_pattern(i64 nblock, i64 nc, int nd, int bs, const i32* cell_dofs, i64* ro
 {
   /* dof -> cells adjacency */
   i64* off = calloc((size_t)(nblock + 1), sizeof(i64));
+  /* (dofs >= nblock are a partition's ghosts: columns, never rows) */
   for (i64 c = 0; c < nc; ++c)
     for (int i = 0; i < nd; ++i)
-      off[cell_dofs[(size_t)c * nd + i] + 1]++;
+      if (cell_dofs[(size_t)c * nd + i] < nblock)
+        off[cell_dofs[(size_t)c * nd + i] + 1]++;
   for (i64 i = 0; i < nblock; ++i)
     off[i + 1] += off[i];
   i32* adj = malloc(sizeof(i32) * (size_t)off[nblock]);
@@ -919,7 +921,8 @@ i64 zo_pattern(i64 nblock, i64 nc, int nd, int bs, const i32* cell_dofs, i64* ro
   memcpy(pos, off, sizeof(i64) * (size_t)nblock);
   for (i64 c = 0; c < nc; ++c)
     for (int i = 0; i < nd; ++i)
-      adj[pos[cell_dofs[(size_t)c * nd + i]]++] = (i32)c;
+      if (cell_dofs[(size_t)c * nd + i] < nblock)
+        adj[pos[cell_dofs[(size_t)c * nd + i]]++] = (i32)c;
   free(pos);
   if (!cols)
     rowptr[0] = 0;

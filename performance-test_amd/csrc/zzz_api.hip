@@ -585,17 +585,26 @@ int zzz_csr_pattern_build(zzz_ctx* ctx)
   const char* mode = getenv("ZZZ_PATTERN"); // "host": the C++ host builder (kept for meshes whose
                                             // vertex valence exceeds the device kernel's LDS budget)
   int rc;
+  int builder = 0;
   if (mode && strcmp(mode, "host") == 0)
+  {
+    builder = 2;
     rc = pattern_build_host(ctx);
+  }
   else
   {
     bool fallback = false;
     rc = pattern_build_device(ctx, &fallback);
     if (rc && fallback)
+    {
+      builder = 1;
       rc = pattern_build_host(ctx);
+    }
   }
   if (rc)
     return rc;
+  ctx->pattern.path_builder = builder;
+  ctx->pattern.path_adj_source = ctx->pattern.have_adj_li ? 1 : 0;
   rc = build_adjT(ctx);
   if (!rc)
     rc = ensure_tables(ctx); // reference tensors of the element: resident before the assembly timers start
@@ -622,6 +631,12 @@ static int pattern_build_host(zzz_ctx* ctx)
   }
   const int nd = ctx->dofmap.nd, bs = ctx->bs;
   const int64_t nb = ctx->n_owned, nc = ctx->ncells;
+  // Nothing a device build left half-way serves this pattern.  The device refuses a row of more than PAT_CAP candidates
+  // AFTER its row kernel has run: that kernel skips such a row without raising pos_missed, so have_asm_pos stood at true
+  // with no positions for the row, and the P2/P3 matrix assembly scattered through whatever asm_pos held there.
+  ctx->pattern.have_asm_pos = ctx->pattern.have_adj_li = false;
+  ctx->pattern.path_adjacency = ctx->pattern.path_runs = 0;
+  ctx->pattern.path_row_kernel = -1;
   std::vector<int32_t> cd_internal;
   const bool internal = ctx->dofmap.renumbered || ctx->dofmap.cells_renumbered;
   if (internal) // the host copy keeps the caller's dof numbering and cell order (zzz_ghost_layer_build reads it)
@@ -735,6 +750,24 @@ static int pattern_build_host(zzz_ctx* ctx)
   if (rc)
     return rc;
   ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return ZZZ_OK;
+}
+
+int zzz_pattern_info(zzz_ctx* ctx, int64_t info[8])
+{
+  if (!ctx || !info)
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_pattern_info: bad arguments");
+  if (!ctx->pattern.have_pattern)
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_pattern_info: no sparsity pattern yet");
+  const zzz::PatternTier& P = ctx->pattern;
+  info[0] = P.path_adjacency;
+  info[1] = P.path_runs;
+  info[2] = P.path_row_kernel;
+  info[3] = P.path_builder;
+  info[4] = P.path_max_cols;
+  info[5] = P.path_adj_source;
+  info[6] = P.have_asm_pos ? 1 : 0;
+  info[7] = 0;
   return ZZZ_OK;
 }
 

@@ -764,6 +764,7 @@ int build_tiles_device(zzz_ctx* ctx, int max_block_cols)
   const int maxrow = max_block_cols * bs;           // longest scalar row
   const int maxblock = max_block_cols * bs * bs;    // nonzeros of the bs rows of one block dof
   ctx->max_row_nnz = maxrow;
+  ctx->pattern.path_max_cols = max_block_cols;
   // lanes per row of the SpMV row phase: one (the serial CPU order) unless the rows are very long --
   // measured: 8 lanes pay from ~128 nonzeros per row on average (P3 elasticity 0.47 -> 0.40 ms), cost below
   {
@@ -1253,6 +1254,7 @@ int pattern_build_device(zzz_ctx* ctx, bool* fallback)
       if (adjacency_overflowed())
       {
         ctx->dofmap.adj_runs_n = 0;
+        ctx->pattern.adj_retry = true;
         return pattern_build_device(ctx, fallback);
       }
       if (h[2] == 0 || cap == 32)
@@ -1261,6 +1263,7 @@ int pattern_build_device(zzz_ctx* ctx, bool* fallback)
     }
     counted = h[2] == 0;
     ctx->pattern.have_adj_li = counted; // complete only if no row overflowed
+    ctx->pattern.path_row_kernel = counted ? (h[0] > 16 ? 32 : 16) : 0;
     if (!counted)
       ZZZ_HIP(ctx, hipMemsetAsync(scal.p, 0, 4 * sizeof(int32_t), s));
   }
@@ -1281,9 +1284,12 @@ int pattern_build_device(zzz_ctx* ctx, bool* fallback)
     if (adjacency_overflowed())
     {
       ctx->dofmap.adj_runs_n = 0;
+      ctx->pattern.adj_retry = true;
       return pattern_build_device(ctx, fallback);
     }
   }
+  ctx->pattern.path_adjacency = by_runs ? 1 : (ctx->pattern.adj_retry ? 3 : 2);
+  ctx->pattern.path_runs = by_runs ? ctx->dofmap.adj_runs_n : 0;
   if (h[1] > 0)
   {
     *fallback = true;

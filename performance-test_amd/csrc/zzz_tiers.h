@@ -42,6 +42,14 @@ struct PatternTier
   bool sp_bounds_ok = false;
   bool sp_crow_is_cap = false; // sp_crow = scan of the FULL row lengths padded to 8 (pattern-only)
   bool bw_struct_ok = false;
+  // the path the build took (zzz_pattern_info): a report, read by nothing else
+  bool adj_retry = false; // a window of the sort-free adjacency overflowed and this build started again with the sort
+  int path_adjacency = 0; // 1 sort-free (monotone runs), 2 sorted from the start, 3 sorted after a window overflowed; 0: host
+  int path_runs = 0;      // runs the adjacency was built from (0 unless path_adjacency == 1)
+  int path_row_kernel = 0; // P1: 16 / 32, the cap of the thread-per-row kernel that sufficed; 0: a wavefront per row; -1: host
+  int path_builder = 0;    // 0 device, 1 host after the device refused, 2 host by ZZZ_PATTERN=host
+  int path_max_cols = 0;   // unique block columns of the longest block row
+  int path_adj_source = 0; // adj_li / adjT written by 1 the P1 pattern kernel, 0 k_adjT_fill
 };
 struct ValuesTier
 {

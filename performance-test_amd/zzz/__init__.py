@@ -26,7 +26,7 @@ ERR_NO_GPU = 4
 ABI_SYMBOLS = [
     "zzz_device_count", "zzz_device_memory", "zzz_ctx_create", "zzz_ctx_destroy", "zzz_last_error", "zzz_sync", "zzz_mesh_upload",
     "zzz_dofmap_upload", "zzz_bc_upload", "zzz_bc_values_upload", "zzz_facets_upload", "zzz_coeff_upload", "zzz_cube_generate",
-    "zzz_csr_pattern_build",
+    "zzz_csr_pattern_build", "zzz_pattern_info",
     "zzz_csr_sizes", "zzz_csr_download", "zzz_csr_rowptr64_download", "zzz_csr_upload_values", "zzz_assemble_matrix", "zzz_assemble_vector",
     "zzz_vec_download", "zzz_vec_upload", "zzz_vec_norm", "zzz_spmv", "zzz_spmv_time", "zzz_spmv_values_info", "zzz_spmv_values_info2", "zzz_abi_version", "zzz_action", "zzz_matfree_setup", "zzz_matfree_info", "zzz_matfree_diagonal", "zzz_matfree_assemble_vector", "zzz_action_time", "zzz_near_nullspace_build", "zzz_near_nullspace_download", "zzz_cg_solve", "zzz_cg_history",
     "zzz_profile_get", "zzz_cg_info", "zzz_internal_order_download", "zzz_global_ids_upload", "zzz_global_ids_download", "zzz_ghost_layer_build", "zzz_local_sizes", "zzz_spmv_info", "zzz_comm_load", "zzz_comm_library_path", "zzz_comm_info", "zzz_comm_unique_id", "zzz_comm_init", "zzz_halo_upload", "zzz_local_group_create",
@@ -106,6 +106,8 @@ def hip():
         L.zzz_cube_generate.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int,
                                         _i64p]
         L.zzz_csr_pattern_build.argtypes = [C.c_void_p]
+        if hasattr(L, "zzz_pattern_info"):  # (ZZZ_HIP_LIB may name a build from before the entry point: the A/B tools)
+            L.zzz_pattern_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
         L.zzz_csr_sizes.argtypes = [C.c_void_p] + [C.POINTER(C.c_int64)] * 3
         L.zzz_csr_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.zzz_csr_upload_values.argtypes = [C.c_void_p, _f64p]
@@ -478,6 +480,16 @@ class Context:
 
     def pattern_build(self):
         self._ck(self.L.zzz_csr_pattern_build(self.h))
+
+    def pattern_info(self):
+        """the path the last pattern_build took (zzz_pattern_info): adjacency 1 sort-free / 2 sorted / 3 sorted after an
+        overflow / 0 host; runs; row_kernel 16 / 32 / 0 wavefront / -1 host; builder 0 device / 1 host after the device
+        refused / 2 host by ZZZ_PATTERN=host; max_cols of the longest block row; adj_source 1 pattern kernel / 0 own pass;
+        have_asm_pos"""
+        a = (C.c_int64 * 8)()
+        self._ck(self.L.zzz_pattern_info(self.h, a))
+        return dict(zip(("adjacency", "runs", "row_kernel", "builder", "max_cols", "adj_source", "have_asm_pos"),
+                        [int(v) for v in a]))
 
     def csr_sizes(self):
         a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
