@@ -127,7 +127,24 @@ enum
    * inverse (at most 4 096 dofs, else declined).  Smoother, cycle and options (pc_degree, pc_ratio, pc_esteig_its) are
    * ZZZ_PC_MG's.  The hierarchy is kept while pattern and Dirichlet set are kept; new matrix values refresh the coarse
    * VALUES on the kept aggregates. */
-  ZZZ_PC_AGG = 5
+  ZZZ_PC_AGG = 5,
+  /* Smoothed-aggregation multigrid: ZZZ_PC_AGG with one prolongator-smoothing step (PETSc: -pc_type gamg
+   * -pc_gamg_agg_nsmooths 1, no near-nullspace).  Scope, refusals, options, level rule, smoother, cycle and dense coarsest
+   * solve are ZZZ_PC_AGG's, word for word.  Per level (csrc/zzz_sagg.hip; every sum a chain of plain double additions of
+   * individually rounded products, in ascending index -- of the caller's numbering on level 0, of the level's own below):
+   * the aggregates are ZZZ_PC_AGG's rule on the graph of that level's matrix (the coarse matrices are denser here, so the
+   * coarse aggregates differ from ZZZ_PC_AGG's; level 0's are the same); P_t is ZZZ_PC_AGG's P; omega = 4 / (3 hi) with hi
+   * the bound of D^-1 A that the level's smoother uses (pc_esteig_its), so a level's bound comes before the next level's
+   * values; P = (I - omega D^-1 A) P_t is STORED as CSR with ascending coarse columns -- pattern: (i, J) wherever row i is
+   * unconstrained and has a structural entry a_ik, zero or not, with k unconstrained and mapped to J by P_t; value:
+   * s = sum_k a_ik over those k, P(i, J) = delta - (omega s) / a_ii with delta = 1 when P_t(i, J) = 1, else 0; rows of
+   * constrained dofs are empty -- and so is R = P^T, coarse rows with ascending fine index, so the restriction is a gather
+   * summed in one fixed order (64 interleaved partial sums front to back, then a shuffle tree); T = A P, T(i, J) = sum_k a_ik P(k, J); A_c = P^T T, A_c(I, J) = sum_i P(i, I) T(i, J), its
+   * pattern every (I, J) that receives a structural term, adopted by the coarse level as ZZZ_PC_AGG's (block size kept, no
+   * Dirichlet rows).  A level whose products have more terms than 32-bit positions take is declined with ZZZ_ERR_LIMIT.
+   * The hierarchy is kept while pattern and Dirichlet set are kept; new matrix values (or another pc_esteig_its) refresh
+   * the bounds and the values of P and of the coarse matrices level by level, to the bits of a fresh set-up. */
+  ZZZ_PC_SAGG = 6
 };
 enum
 {
@@ -551,8 +568,8 @@ int zzz_pattern_info(zzz_ctx* ctx, int64_t info[8]);
  * PCSetUp(PCMG) behind solver.set_from_options() (src/poisson_problem.cpp:169; README.md:59-146): builds the hierarchy
  * for these options, or refreshes its values after an assembly.  Optional: zzz_cg_solve(pc = ZZZ_PC_MG) does it on first
  * use, inside the solve, where PETSc's PCSetUp runs.  Overwrites the context's Krylov work vectors (not b, not u).
- * opts->pc == ZZZ_PC_PMG builds the p-multigrid hierarchy, ZZZ_PC_AGG the aggregation hierarchy (zzz_mg_info then reports
- * nx = ny = nz = 0 for every level); any other value is read as ZZZ_PC_MG.  One context holds one hierarchy: a set-up
+ * opts->pc == ZZZ_PC_PMG builds the p-multigrid hierarchy, ZZZ_PC_AGG / ZZZ_PC_SAGG the (smoothed) aggregation hierarchy
+ * (zzz_mg_info then reports nx = ny = nz = 0 for every level); any other value is read as ZZZ_PC_MG.  One context holds one hierarchy: a set-up
  * of another kind replaces it. */
 int zzz_mg_setup(zzz_ctx* ctx, const zzz_solver_opts* opts);
 /* PCView of that hierarchy.  level < 0: out = {levels, scalar dofs of the coarsest, set-ups done so far (builds and
@@ -570,12 +587,17 @@ int zzz_mg_transfer(zzz_ctx* ctx, int level, int dir, const double* in, double* 
 /* The matrix of a coarse level (1 <= level < levels) as the hierarchy holds it, for parity checks: 64-bit row pointers
  * (scalar dofs + 1), columns and values (zzz_mg_info(level) gives the sizes); any of the three may be NULL. */
 int zzz_mg_level_csr(zzz_ctx* ctx, int level, int64_t* rowptr, int32_t* cols, double* vals);
+/* The stored prolongator between level and level + 1 of a ZZZ_PC_SAGG hierarchy: 64-bit row pointers (fine scalar dofs + 1),
+ * coarse columns, values, fine rows in the caller's numbering on level 0; any of the three may be NULL; out_nnz optional.
+ * ZZZ_ERR_ARG for another kind of hierarchy.  (A new entry point: ZZZ_ABI_VERSION is unchanged.) */
+int zzz_mg_level_p(zzz_ctx* ctx, int level, int64_t* rowptr, int32_t* cols, double* vals, int64_t* out_nnz);
 
 /* Version of this header's ABI: bumped whenever an existing entry point changes what it reads or writes (7: zzz_cg_solve
  * reads the two pc_mg_* fields behind pc_ratio).  ZZZ_PC_PMG did not bump it: a new enumerator changes no struct, no
  * entry point and nothing that a caller built against the earlier header passes or receives -- such a caller never
  * sends the value 4, and a library without it answers that value with ZZZ_ERR_ARG.  Nor did zzz_bc_values_upload: a new
- * entry point, no struct and no existing entry changed.  ZZZ_PC_AGG (5) and zzz_mg_level_csr: the same two arguments. */
+ * entry point, no struct and no existing entry changed.  ZZZ_PC_AGG (5) and zzz_mg_level_csr: the same two arguments;
+ * ZZZ_PC_SAGG (6) and zzz_mg_level_p: the same two again. */
 #define ZZZ_ABI_VERSION 7
 int zzz_abi_version(void);
 

@@ -412,6 +412,7 @@ __global__ __launch_bounds__(VB) void k_agg_prolong(const int* __restrict__ stop
 AggLevel* agg_new() { return new AggLevel(); }
 void agg_free(AggLevel* A) { delete A; }
 int64_t agg_count(const AggLevel* A) { return A->nagg; }
+const int32_t* agg_map(const AggLevel* A) { return A->agg.p; }
 
 // flags (caller order) -> numbers base + rank for the flagged nodes; *count = how many
 static int agg_number(zzz_ctx* ctx, AggLevel& A, int what, int32_t base, const int32_t* perm, const int32_t* state,

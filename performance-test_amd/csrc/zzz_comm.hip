@@ -515,6 +515,18 @@ int comm_reduce_end(zzz_ctx* ctx)
   return ZZZ_OK;
 }
 
+// Ranks that are contexts of ONE process on one GPU (validation) meet on the host before a solve enqueues its first mailbox
+// round.  Without it a rank that is through its set-up polls its mailbox while the other is still in a call that waits for
+// every kernel on the device (hipFree, hipMalloc): that call waits for the poll, the poll for that rank's contribution,
+// until the poll times out -- and the rank that failed frees the mailbox its peer stores into next.  halo_peer meets for
+// the same reason.  Collective where it does anything; ranks in processes of their own never wait for each other's calls.
+int comm_inproc_meet(zzz_ctx* ctx)
+{
+  if (comm_p2p_enabled(ctx) && ctx->comm->p2p->inproc && ctx->comm->local)
+    ZZZ_LOCAL_WAIT(ctx, ctx->comm->local);
+  return ZZZ_OK;
+}
+
 // did a peer all-reduce time out since the last call?  (checked at the end of a solve)
 int comm_p2p_check(zzz_ctx* ctx)
 {

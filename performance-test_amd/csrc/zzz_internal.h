@@ -101,6 +101,7 @@ struct DevBuf
 struct Comm; // zzz_comm.cpp
 struct MgHier; // zzz_mg.hip: the level hierarchy of ZZZ_PC_MG, ZZZ_PC_PMG and ZZZ_PC_AGG
 struct AggLevel; // zzz_agg.hip: the aggregates of one level of ZZZ_PC_AGG and the Galerkin sum to the next
+struct SaggLevel; // zzz_sagg.hip: the smoothed prolongator of one level of ZZZ_PC_SAGG and the two products to the next
 
 typedef int64_t rp_t; // row pointers of the CSR matrix of record
 
@@ -467,6 +468,7 @@ void preload_nullspace();
 void preload_pmg();
 void preload_pattern();
 void preload_renumber();
+void preload_sagg();
 void preload_sellp();
 void preload_sellp_dict();
 void preload_sellp_pack();
@@ -628,6 +630,20 @@ int agg_galerkin(zzz_ctx* ctx, zzz_ctx* f, AggLevel* A, zzz_ctx* c);
 int agg_refresh(zzz_ctx* ctx, zzz_ctx* f, AggLevel* A, zzz_ctx* c);
 int agg_restrict(zzz_ctx* ctx, const int* stop, const AggLevel* A, const uint8_t* bcf, const double* rf, const double* sub, double* rc);
 int agg_prolong(zzz_ctx* ctx, const int* stop, const AggLevel* A, const uint8_t* bcf, const double* ec, double* xf, int accumulate);
+const int32_t* agg_map(const AggLevel* A); // device: the aggregate of every fine block dof, -1: none
+// zzz_sagg.hip (ZZZ_PC_SAGG): the same aggregates; P = (I - omega D^-1 A) P_t stored with its transpose, A_c = P^T (A P)
+// adopted by the child context c (level: of f, for the messages); the values again on the kept patterns; the two transfers
+// enqueued on ctx->stream; P on the host, level 0's rows in the caller's numbering
+SaggLevel* sagg_new();
+void sagg_free(SaggLevel* S);
+int64_t sagg_count(const SaggLevel* S);
+int64_t sagg_p_nnz(const SaggLevel* S);
+int sagg_aggregate(zzz_ctx* ctx, zzz_ctx* f, SaggLevel* S);
+int sagg_galerkin(zzz_ctx* ctx, zzz_ctx* f, SaggLevel* S, double omega, zzz_ctx* c, int level);
+int sagg_refresh(zzz_ctx* ctx, zzz_ctx* f, SaggLevel* S, double omega, zzz_ctx* c);
+int sagg_restrict(zzz_ctx* ctx, const int* stop, const SaggLevel* S, const double* rf, const double* sub, double* rc);
+int sagg_prolong(zzz_ctx* ctx, const int* stop, const SaggLevel* S, const double* ec, double* xf, int accumulate);
+int sagg_download_p(zzz_ctx* ctx, zzz_ctx* f, const SaggLevel* S, int64_t* rowptr, int32_t* cols, double* vals);
 
 // comm
 int comm_allreduce_sum(zzz_ctx* ctx, double* dev, int n);
@@ -642,6 +658,7 @@ int comm_reduce_begin(zzz_ctx* ctx, const int* stop, const double* pa, const dou
 int comm_reduce_end(zzz_ctx* ctx);
 bool comm_p2p_enabled(const zzz_ctx* ctx);
 int comm_p2p_check(zzz_ctx* ctx);
+int comm_inproc_meet(zzz_ctx* ctx); // mailbox ranks inside one process: a host rendezvous before a solve's first round
 int comm_halo_forward(zzz_ctx* ctx, double* vec);
 int comm_halo_begin(zzz_ctx* ctx, double* vec); // on the comm stream, after the work enqueued so far
 int comm_halo_end(zzz_ctx* ctx);                // main stream waits for the halo

@@ -26,8 +26,10 @@
 //
 // ZZZ_PC_AGG builds its levels from the matrix instead (zzz_agg.hip: aggregates, P^T A P into child contexts that adopt the
 // CSR, the two transfers); everything else -- smoother, cycle, dense solve, caching, refresh, profiling -- is the one here.
+// ZZZ_PC_SAGG is ZZZ_PC_AGG with a smoothed prolongator (zzz_sagg.hip), whose damping needs the level's spectrum bound: there
+// a level's bound comes before the next level's values, in a build and in a refresh.
 //
-// The three differ in MgKind alone (a level's transfer, the next level, that level's values); the set-up keeps a
+// The four differ in MgKind alone (a level's transfer, the next level, that level's values); the set-up keeps a
 // hierarchy while its MgStructKey holds and the levels' values while its MgValuesKey holds.
 #include "zzz_cg.h"
 
@@ -212,13 +214,16 @@ __global__ __launch_bounds__(VB) void k_mg_dense(const int* __restrict__ stop, c
 
 // How a level reaches the next coarser one -- its transfer, and where that level and its matrix values come from: the
 // same cube on half the cells (tables above), the same cube at order 1 (zzz_pmg.hip), the aggregates of its matrix
-// (zzz_agg.hip).  mg_coarsen, mg_level_values, mg_restrict and mg_prolong are the four places that tell them apart.
+// (zzz_agg.hip), the same aggregates under a smoothed prolongator (zzz_sagg.hip).  mg_coarsen, mg_level_values, mg_restrict
+// and mg_prolong are the four places that tell them apart.
 enum class MgKind
 {
   GEOM,
   PLEVEL,
-  AGG
+  AGG,
+  SAGG
 };
+static bool mg_algebraic(MgKind k) { return k == MgKind::AGG || k == MgKind::SAGG; }
 
 struct MgLevel
 {
@@ -232,8 +237,13 @@ struct MgLevel
   MgGeom G{};
   DevBuf<int32_t> tc, rng;
   DevBuf<double> tf;
-  AggLevel* agg = nullptr; // AGG: the aggregates of this level
-  ~MgLevel() { agg_free(agg); }
+  AggLevel* agg = nullptr;   // AGG: the aggregates of this level
+  SaggLevel* sagg = nullptr; // SAGG: the aggregates of this level and the prolongator on them
+  ~MgLevel()
+  {
+    agg_free(agg);
+    sagg_free(sagg);
+  }
 };
 
 // what the levels were built from, and what their values were computed from: a set-up compares these
@@ -241,11 +251,11 @@ struct MgStructKey
 {
   uint64_t feed_version = 0, pattern_version = 0, bc_version = 0; // (pattern and Dirichlet set: the aggregates depend on both)
   int opt_levels = 0, limit = 0;
-  bool agg = false;
+  MgKind kind = MgKind::GEOM; // of level 0
   bool operator==(const MgStructKey& k) const
   {
     return feed_version == k.feed_version && pattern_version == k.pattern_version && bc_version == k.bc_version
-           && opt_levels == k.opt_levels && limit == k.limit && agg == k.agg;
+           && opt_levels == k.opt_levels && limit == k.limit && kind == k.kind;
   }
 };
 struct MgValuesKey
@@ -309,8 +319,8 @@ void mg_invalidate(zzz_ctx* ctx)
 
 int mg_check(zzz_ctx* ctx, const zzz_solver_opts* o)
 {
-  const bool pmg = o->pc == ZZZ_PC_PMG, agg = o->pc == ZZZ_PC_AGG;
-  const char* tag = agg ? "-pc_type agg" : pmg ? "-pc_type pmg" : "-pc_type mg";
+  const bool pmg = o->pc == ZZZ_PC_PMG, sagg = o->pc == ZZZ_PC_SAGG, agg = o->pc == ZZZ_PC_AGG || sagg;
+  const char* tag = sagg ? "-pc_type sagg" : agg ? "-pc_type agg" : pmg ? "-pc_type pmg" : "-pc_type mg";
   if (o->variant == ZZZ_CG_PIPE)
     return fail(ctx, ZZZ_ERR_ARG, "%s: not with -ksp_type pipecg (ZZZ_CG_PIPE takes jacobi or none)", tag);
   if (o->variant != ZZZ_CG_PETSC)
@@ -360,7 +370,7 @@ int mg_check(zzz_ctx* ctx, const zzz_solver_opts* o)
 // the error of a child context becomes the caller's
 static int child_fail(zzz_ctx* ctx, zzz_ctx* c, int rc, int level, const char* what)
 {
-  return fail(ctx, rc, "-pc_type mg / pmg / agg, level %d, %s: %s", level, what, c ? c->err.c_str() : zzz_last_error(nullptr));
+  return fail(ctx, rc, "-pc_type mg / pmg / agg / sagg, level %d, %s: %s", level, what, c ? c->err.c_str() : zzz_last_error(nullptr));
 }
 
 static int mg_build_tables(zzz_ctx* ctx, MgLevel& F, const MgLevel& C)
@@ -509,24 +519,33 @@ static int mg_child_create(zzz_ctx* ctx, int level, zzz_ctx** out)
   return ZZZ_OK;
 }
 
-// The next coarser level below the last one, by that level's kind: its context with a pattern (AGG: with its values too,
-// the Galerkin sum makes both) and the transfer between the two.  *more stays false when the kind has none to give: a
-// cube of two cells per axis, or an aggregation that reduces the dofs by less than a factor of 2.
-static int mg_coarsen(zzz_ctx* ctx, MgHier& H, bool* more)
+// omega of ZZZ_PC_SAGG's prolongator from the bound of the level's smoother
+static double mg_omega(const MgLevel& L) { return 4.0 / (3.0 * L.cheb.hi); }
+
+// The next coarser level below the last one, by that level's kind: its context with a pattern (AGG, SAGG: with its values
+// too, the Galerkin sums make both; SAGG takes the level's spectrum bound first, by the options os) and the transfer between
+// the two.  *more stays false when the kind has none to give: a cube of two cells per axis, or an aggregation that reduces
+// the dofs by less than a factor of 2.
+static int mg_coarsen(zzz_ctx* ctx, MgHier& H, const zzz_solver_opts* os, bool* more)
 {
   MgLevel& F = *H.lv.back();
   const int l = (int)H.lv.size();
   int64_t ncdof = 0;
-  if (F.kind == MgKind::AGG)
+  if (mg_algebraic(F.kind))
   {
-    F.agg = agg_new();
-    if (int rc = agg_aggregate(ctx, F.ctx, F.agg))
+    if (F.kind == MgKind::AGG)
+      F.agg = agg_new();
+    else
+      F.sagg = sagg_new();
+    if (int rc = F.agg ? agg_aggregate(ctx, F.ctx, F.agg) : sagg_aggregate(ctx, F.ctx, F.sagg))
       return rc;
-    ncdof = agg_count(F.agg) * ctx->bs;
+    ncdof = (F.agg ? agg_count(F.agg) : sagg_count(F.sagg)) * ctx->bs;
     if (ncdof == 0 || 2 * ncdof > F.ndof)
     {
       agg_free(F.agg);
+      sagg_free(F.sagg);
       F.agg = nullptr;
+      F.sagg = nullptr;
       return ZZZ_OK;
     }
   }
@@ -534,17 +553,21 @@ static int mg_coarsen(zzz_ctx* ctx, MgHier& H, bool* more)
     return ZZZ_OK;
   H.lv.emplace_back(new MgLevel()); // (in the hierarchy before it owns a context: every exit path destroys it)
   MgLevel& C = *H.lv.back();
-  C.kind = F.kind == MgKind::AGG ? MgKind::AGG : MgKind::GEOM;
+  C.kind = mg_algebraic(F.kind) ? F.kind : MgKind::GEOM;
   if (int rc = mg_child_create(ctx, l, &C.ctx))
     return rc;
   zzz_ctx* c = C.ctx;
   *more = true;
-  if (F.kind == MgKind::AGG)
+  if (mg_algebraic(F.kind))
   {
     C.ndof = ncdof;
     // (no block-window product on a level without coordinates; the other forms are packed from the CSR alone)
     c->knob.sellp_bwin = 0;
-    return agg_galerkin(ctx, F.ctx, F.agg, c);
+    if (F.kind == MgKind::AGG)
+      return agg_galerkin(ctx, F.ctx, F.agg, c);
+    if (int rc = chebyshev_setup(F.ctx, os, F.cheb)) // (kept per set of matrix values: the set-up below finds it again)
+      return l > 1 ? child_fail(ctx, F.ctx, rc, l - 1, "spectrum bound") : rc;
+    return sagg_galerkin(ctx, F.ctx, F.sagg, mg_omega(F), c, l - 1);
   }
   // the same problem re-discretised at order 1: on the same cells below the Pk level, on half of them below a P1 level
   for (int a = 0; a < 3; ++a)
@@ -562,11 +585,12 @@ static int mg_coarsen(zzz_ctx* ctx, MgHier& H, bool* more)
 // level C's matrix values (F: the level above it; built: the levels are new)
 static int mg_level_values(zzz_ctx* ctx, MgLevel& F, MgLevel& C, int l, bool built)
 {
-  if (F.kind == MgKind::AGG)
+  if (mg_algebraic(F.kind))
   {
-    // (a build has just summed them; a refresh sums the new values on the kept aggregates, level by level)
+    // (a build has just summed them; a refresh sums the new values on the kept aggregates, level by level -- SAGG with the
+    // bound that the level above has just been given)
     if (!built)
-      if (int rc = agg_refresh(ctx, F.ctx, F.agg, C.ctx))
+      if (int rc = F.agg ? agg_refresh(ctx, F.ctx, F.agg, C.ctx) : sagg_refresh(ctx, F.ctx, F.sagg, mg_omega(F), C.ctx))
         return child_fail(ctx, C.ctx, rc, l, "coarse values");
     return ZZZ_OK;
   }
@@ -578,13 +602,14 @@ static int mg_level_values(zzz_ctx* ctx, MgLevel& F, MgLevel& C, int l, bool bui
 // Level 0 is the caller's context; then coarser levels until one is small enough, the level limit is reached or the kind
 // has none to give.  ZZZ_PC_PMG at order > 1: the Pk level first, then the P1 levels from the same cube on; pc_mg_levels
 // counts all, and the Pk level is never the coarsest (mg_check refuses pc_mg_levels = 1 there).
-static int mg_build(zzz_ctx* ctx, MgHier& H, bool agg, int limit, int max_levels)
+static int mg_build(zzz_ctx* ctx, MgHier& H, MgKind kind, const zzz_solver_opts* os, int limit, int max_levels)
 {
+  const bool agg = mg_algebraic(kind);
   H.lv.emplace_back(new MgLevel());
   MgLevel& L0 = *H.lv[0];
   L0.ctx = ctx;
   L0.ndof = ctx->n_owned * ctx->bs;
-  L0.kind = agg ? MgKind::AGG : ctx->dofmap.order > 1 ? MgKind::PLEVEL : MgKind::GEOM;
+  L0.kind = kind;
   if (!agg) // (to the aggregates the element's order and the cube say nothing)
   {
     L0.order = ctx->dofmap.order;
@@ -597,14 +622,14 @@ static int mg_build(zzz_ctx* ctx, MgHier& H, bool agg, int limit, int max_levels
     if (L.kind != MgKind::PLEVEL && (L.ndof <= limit || (int)H.lv.size() >= max_levels))
       break;
     more = false;
-    if (int rc = mg_coarsen(ctx, H, &more))
+    if (int rc = mg_coarsen(ctx, H, os, &more))
       return rc;
   }
   const int64_t dofs = H.lv.back()->ndof;
   if (dofs > MG_DENSE_MAX)
     return fail(ctx, ZZZ_ERR_ARG, "-pc_type %s: the coarsest of %d levels has %lld dofs, the dense solve takes at most %lld: "
                                   "allow more levels (pc_mg_levels) or a lower pc_mg_coarse_eq_limit",
-                agg ? "agg" : "mg", (int)H.lv.size(), (long long)dofs, (long long)MG_DENSE_MAX);
+                kind == MgKind::SAGG ? "sagg" : agg ? "agg" : "mg", (int)H.lv.size(), (long long)dofs, (long long)MG_DENSE_MAX);
   return ZZZ_OK;
 }
 
@@ -612,12 +637,21 @@ int mg_setup(zzz_ctx* ctx, const zzz_solver_opts* o)
 {
   if (int rc = mg_check(ctx, o))
     return rc;
-  const bool agg = o->pc == ZZZ_PC_AGG;
+  const MgKind kind = o->pc == ZZZ_PC_SAGG ? MgKind::SAGG : o->pc == ZZZ_PC_AGG ? MgKind::AGG
+                      : ctx->dofmap.order > 1 ? MgKind::PLEVEL : MgKind::GEOM;
+  const bool agg = mg_algebraic(kind);
   const int limit = o->pc_mg_coarse_eq_limit > 0 ? o->pc_mg_coarse_eq_limit : 1000;
   const int max_levels = o->pc_mg_levels > 0 ? std::min<int>(o->pc_mg_levels, MG_MAX_LEVELS) : MG_MAX_LEVELS;
-  const MgStructKey skey{ctx->feed_version, agg ? ctx->pattern_version : 0, agg ? ctx->bc_version : 0, o->pc_mg_levels, limit, agg};
+  const MgStructKey skey{ctx->feed_version, agg ? ctx->pattern_version : 0, agg ? ctx->bc_version : 0, o->pc_mg_levels, limit, kind};
   const MgValuesKey vkey{ctx->mat_version, o->pc_degree > 0 ? o->pc_degree : 2, o->pc_ratio > 1.0 ? o->pc_ratio : 10.0,
                          o->pc_esteig_its == 0 ? 10 : o->pc_esteig_its};
+  // the options of the levels' spectrum estimates and smoothers
+  zzz_solver_opts os = *o;
+  os.variant = ZZZ_CG_PETSC;
+  os.op = ZZZ_OP_CSR;
+  os.single_reduction = 0;
+  os.pc_degree = vkey.degree;
+  os.pc_ratio = vkey.ratio;
   MgHier* H = ctx->mg;
   bool built = false;
   const auto t_begin = std::chrono::steady_clock::now();
@@ -628,7 +662,7 @@ int mg_setup(zzz_ctx* ctx, const zzz_solver_opts* o)
     size_t free0 = 0, free1 = 0, total = 0;
     ZZZ_HIP(ctx, hipMemGetInfo(&free0, &total));
     H = ctx->mg = new MgHier();
-    if (int rc = mg_build(ctx, *H, agg, limit, max_levels))
+    if (int rc = mg_build(ctx, *H, kind, &os, limit, max_levels))
     {
       mg_destroy(ctx);
       return rc;
@@ -648,15 +682,10 @@ int mg_setup(zzz_ctx* ctx, const zzz_solver_opts* o)
   }
   if (!(H->vkey == vkey))
   {
-    const bool values = H->vkey.mat_version != vkey.mat_version;
+    // (SAGG: the bounds are part of the prolongator, so another estimate is other values)
+    const bool values = H->vkey.mat_version != vkey.mat_version || (kind == MgKind::SAGG && H->vkey.est_its != vkey.est_its);
     H->ready = false;
     // ---- the levels' values: matrices, inverse diagonals, spectrum bounds, the coarsest inverse ----
-    zzz_solver_opts os = *o;
-    os.variant = ZZZ_CG_PETSC;
-    os.op = ZZZ_OP_CSR;
-    os.single_reduction = 0;
-    os.pc_degree = vkey.degree;
-    os.pc_ratio = vkey.ratio;
     for (size_t l = 0; l < H->lv.size(); ++l)
     {
       MgLevel& L = *H->lv[l];
@@ -696,6 +725,8 @@ static int mg_restrict(zzz_ctx* ctx, const int* stop, MgLevel& F, MgLevel& C, co
   {
   case MgKind::AGG:
     return agg_restrict(ctx, stop, F.agg, F.ctx->bc.p, rf, sub, rc);
+  case MgKind::SAGG:
+    return sagg_restrict(ctx, stop, F.sagg, rf, sub, rc);
   case MgKind::PLEVEL:
     return pmg_restrict(ctx, stop, F.order, ctx->bs, F.n, F.ctx->bc.p, C.ctx->bc.p, rf, sub, rc);
   case MgKind::GEOM:
@@ -716,6 +747,8 @@ static int mg_prolong(zzz_ctx* ctx, const int* stop, MgLevel& F, MgLevel& C, con
   {
   case MgKind::AGG:
     return agg_prolong(ctx, stop, F.agg, F.ctx->bc.p, ec, xf, accumulate);
+  case MgKind::SAGG:
+    return sagg_prolong(ctx, stop, F.sagg, ec, xf, accumulate);
   case MgKind::PLEVEL:
     return pmg_prolong(ctx, stop, F.order, ctx->bs, F.n, F.ctx->bc.p, C.ctx->bc.p, ec, xf, accumulate);
   case MgKind::GEOM:
@@ -825,7 +858,7 @@ int zzz_mg_setup(zzz_ctx* ctx, const zzz_solver_opts* opts)
   if (!opts)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_mg_setup: NULL options");
   zzz_solver_opts o = *opts;
-  o.pc = opts->pc == ZZZ_PC_PMG ? ZZZ_PC_PMG : opts->pc == ZZZ_PC_AGG ? ZZZ_PC_AGG : ZZZ_PC_MG;
+  o.pc = opts->pc == ZZZ_PC_PMG || opts->pc == ZZZ_PC_AGG || opts->pc == ZZZ_PC_SAGG ? opts->pc : ZZZ_PC_MG;
   if (int rc = mg_setup(ctx, &o))
     return rc;
   ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -882,7 +915,7 @@ int zzz_mg_apply(zzz_ctx* ctx, const double* r, double* z)
   const size_t n = (size_t)(ctx->n_owned * ctx->bs);
   hipStream_t s = ctx->stream;
   ZZZ_HIP(ctx, hipMemsetAsync(ctx->state.p, 0, sizeof(CgState), s)); // (a finished solve leaves its stop flag set)
-  // (a context in an internal dof order -- ZZZ_PC_AGG alone serves one -- translates at the boundary, as zzz_spmv does)
+  // (a context in an internal dof order -- ZZZ_PC_AGG and ZZZ_PC_SAGG alone serve one -- translates at the boundary, as zzz_spmv does)
   std::vector<double> ri, zi;
   if (ctx->dofmap.renumbered)
   {
@@ -965,5 +998,23 @@ int zzz_mg_level_csr(zzz_ctx* ctx, int level, int64_t* rowptr, int32_t* cols, do
   if (vals)
     ZZZ_HIP(ctx, hipMemcpy(vals, c->vals.p, (size_t)c->nnz * sizeof(double), hipMemcpyDeviceToHost));
   return ZZZ_OK;
+}
+
+int zzz_mg_level_p(zzz_ctx* ctx, int level, int64_t* rowptr, int32_t* cols, double* vals, int64_t* out_nnz)
+{
+  if (!ctx)
+    return fail(nullptr, ZZZ_ERR_ARG, "NULL context");
+  ZZZ_HIP(ctx, hipSetDevice(ctx->device));
+  MgHier* H = ctx->mg;
+  if (!H || !H->ready)
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_mg_level_p: no hierarchy (zzz_mg_setup, or a solve with ZZZ_PC_SAGG)");
+  if (H->lv[0]->kind != MgKind::SAGG)
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_mg_level_p: the hierarchy is not ZZZ_PC_SAGG's: no prolongator is stored");
+  if (level < 0 || (size_t)level + 1 >= H->lv.size())
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_mg_level_p: level %d of %d (the coarsest has no prolongator below it)", level, (int)H->lv.size());
+  const MgLevel& F = *H->lv[(size_t)level];
+  if (out_nnz)
+    *out_nnz = sagg_p_nnz(F.sagg);
+  return sagg_download_p(ctx, F.ctx, F.sagg, rowptr, cols, vals);
 }
 }

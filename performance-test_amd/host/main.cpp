@@ -169,7 +169,7 @@ void usage()
                "                                  -ksp_max_it, -ksp_norm_type)\n"
                "  --bc_value arg (=0)             value of u0 at every Dirichlet dof (the reference's u0 is 0); non-zero: the\n"
                "                                  vector assembly lifts it (apply_lifting, bc->set)\n"
-               "PETSc-style solver options honoured: -ksp_type {cg,pipecg} -pc_type {jacobi,none,chebyshev_jacobi,mg,pmg,agg} -ksp_rtol -ksp_atol\n"
+               "PETSc-style solver options honoured: -ksp_type {cg,pipecg} -pc_type {jacobi,none,chebyshev_jacobi,mg,pmg,agg,sagg} -ksp_rtol -ksp_atol\n"
                "  -ksp_divtol -pc_chebyshev_jacobi_degree (=3) -pc_chebyshev_jacobi_ratio (=60) -pc_chebyshev_jacobi_esteig (=10)\n"
                "  -ksp_max_it -ksp_norm_type {preconditioned,unpreconditioned,natural} -ksp_view -ksp_monitor\n"
                "  -ksp_cg_single_reduction -ksp_converged_reason -ksp_error_if_not_converged\n"
@@ -181,6 +181,8 @@ void usage()
                "  -pc_type agg: plain aggregation multigrid from the assembled matrix alone (poisson or elasticity, any --order, both\n"
                "  mesh types, --ngpus 1, --operator assembled, -ksp_type cg without -ksp_cg_single_reduction); the same -pc_mg_* /\n"
                "  -mg_levels_* options\n"
+               "  -pc_type sagg: smoothed aggregation, -pc_type agg with one prolongator-smoothing step (omega = 4 / (3 hi) of the\n"
+               "  level's smoother bound); the same scope and the same options\n"
                "  -log_view -options_left\n"
             << std::endl;
 }
@@ -349,6 +351,7 @@ struct Shared
   std::vector<double> tplan;  // cgpoisson: set-up of the matrix-free plan (inside ZZZ Solve, outside the Gdof/s timer)
   std::vector<int> iters;
   std::vector<std::array<double, 8>> mg_view; // -pc_type mg: the summary of zzz_mg_info, then one entry per level (rank 0)
+  std::vector<long long> mg_pnnz; // -pc_type sagg: entries of the stored prolongator below each level but the coarsest
   std::vector<double> norm, rnorm0, rnorm;
   std::vector<std::string> error;
   std::int64_t num_dofs = 0, num_cells = 0;
@@ -553,8 +556,9 @@ void run_rank(Shared& S, std::barrier<>& bar, int rank)
   {
     so.variant = o.ksp_type == "pipecg" ? ZZZ_CG_PIPE : ZZZ_CG_PETSC;
     so.pc = o.pc_type == "none" ? ZZZ_PC_NONE : o.pc_type == "chebyshev_jacobi" ? ZZZ_PC_CHEBYSHEV_JACOBI
-            : o.pc_type == "mg" ? ZZZ_PC_MG : o.pc_type == "pmg" ? ZZZ_PC_PMG : o.pc_type == "agg" ? ZZZ_PC_AGG : ZZZ_PC_JACOBI;
-    const bool multigrid = o.pc_type == "mg" || o.pc_type == "pmg" || o.pc_type == "agg";
+            : o.pc_type == "mg" ? ZZZ_PC_MG : o.pc_type == "pmg" ? ZZZ_PC_PMG : o.pc_type == "agg" ? ZZZ_PC_AGG
+            : o.pc_type == "sagg" ? ZZZ_PC_SAGG : ZZZ_PC_JACOBI;
+    const bool multigrid = o.pc_type == "mg" || o.pc_type == "pmg" || o.pc_type == "agg" || o.pc_type == "sagg";
     so.pc_degree = multigrid ? o.mg_degree : o.pc_degree;
     so.pc_ratio = multigrid ? o.mg_ratio : o.pc_ratio;
     so.pc_esteig_its = o.pc_esteig;
@@ -611,7 +615,7 @@ void run_rank(Shared& S, std::barrier<>& bar, int rank)
         S.tcg[rank] = tcg.stop();
         S.rnorm[rank] = rn[0];
         S.rnorm0[rank] = rn[1];
-        if (root && (so.pc == ZZZ_PC_MG || so.pc == ZZZ_PC_PMG || so.pc == ZZZ_PC_AGG)) // PCView: the hierarchy zzz_cg_solve set up above (PCSetUp runs inside ZZZ Solve, as in PETSc)
+        if (root && (so.pc == ZZZ_PC_MG || so.pc == ZZZ_PC_PMG || so.pc == ZZZ_PC_AGG || so.pc == ZZZ_PC_SAGG)) // PCView: the hierarchy zzz_cg_solve set up above (PCSetUp runs inside ZZZ Solve, as in PETSc)
         {
           std::array<double, 8> v{};
           ZCK(ctx, zzz_mg_info(ctx, -1, v.data()));
@@ -620,6 +624,12 @@ void run_rank(Shared& S, std::barrier<>& bar, int rank)
           {
             ZCK(ctx, zzz_mg_info(ctx, l, v.data()));
             S.mg_view.push_back(v);
+          }
+          for (int l = 0; so.pc == ZZZ_PC_SAGG && l + 1 < (int)S.mg_view[0][0]; ++l)
+          {
+            int64_t pnnz = 0;
+            ZCK(ctx, zzz_mg_level_p(ctx, l, nullptr, nullptr, nullptr, &pnnz));
+            S.mg_pnnz.push_back((long long)pnnz);
           }
         }
       }
@@ -759,7 +769,7 @@ void solve(int argc, char** argv)
   {
     // what the matrix-free operator declines at block size 3 as at 1 (include/zzz_abi.h), said here before any GPU work
     const char* why = o.op == "matfree" ? "not with --operator matfree (the operator is already matrix-free)"
-                      : o.pc_type == "chebyshev_jacobi" || o.pc_type == "mg" || o.pc_type == "pmg" || o.pc_type == "agg"
+                      : o.pc_type == "chebyshev_jacobi" || o.pc_type == "mg" || o.pc_type == "pmg" || o.pc_type == "agg" || o.pc_type == "sagg"
                           ? "-pc_type jacobi or none only (Chebyshev-Jacobi and the multigrid preconditioners need the assembled operator)"
                       : o.ksp_type == "pipecg"    ? "-ksp_type pipecg needs the assembled operator (--cg_solver ksp runs the classical KSPCG)"
                       : o.ksp_cg_single_reduction ? "-ksp_cg_single_reduction needs the assembled operator"
@@ -786,7 +796,7 @@ void solve(int argc, char** argv)
   if (o.ksp_type != "cg" && o.ksp_type != "pipecg")
     throw std::runtime_error("-ksp_type " + o.ksp_type + ": only cg and pipecg are built");
   if (o.pc_type != "jacobi" && o.pc_type != "none" && o.pc_type != "chebyshev_jacobi" && o.pc_type != "mg" && o.pc_type != "pmg"
-      && o.pc_type != "agg")
+      && o.pc_type != "agg" && o.pc_type != "sagg")
     throw std::runtime_error("-pc_type " + o.pc_type +
                              ": only jacobi, none, chebyshev_jacobi, mg and pmg are built (hypre/gamg are out of scope: the "
                              "multigrid preconditioner here is the geometric one, -pc_type mg, or -pc_type pmg for --order 2 / 3)");
@@ -827,9 +837,9 @@ void solve(int argc, char** argv)
     if (why)
       throw std::runtime_error("-pc_type " + o.pc_type + ": " + why);
   }
-  if (o.pc_type == "agg")
+  if (o.pc_type == "agg" || o.pc_type == "sagg")
   {
-    // what ZZZ_PC_AGG declines (include/zzz_abi.h), said here before any GPU work
+    // what ZZZ_PC_AGG and ZZZ_PC_SAGG decline (include/zzz_abi.h), said here before any GPU work
     const char* why = o.ngpus != 1                                       ? "--ngpus 1 only (multi-rank multigrid is not built)"
                       : o.problem_type != "poisson" && o.problem_type != "elasticity" ? "poisson or elasticity (the assembled matrix is what it coarsens)"
                       : o.op == "matfree"                                ? "--operator assembled only"
@@ -838,7 +848,7 @@ void solve(int argc, char** argv)
                       : o.pc_mg_levels < 0 || o.pc_mg_coarse_eq_limit < 0 || o.mg_degree < 0 ? "negative -pc_mg_* / -mg_levels_* value"
                                                                          : nullptr;
     if (why)
-      throw std::runtime_error("-pc_type agg: " + std::string(why));
+      throw std::runtime_error("-pc_type " + o.pc_type + ": " + why);
   }
   if (o.ngpus < 1 || (o.comm == "rccl" && o.ngpus > ndev))
     throw std::runtime_error("--ngpus " + std::to_string(o.ngpus) + " but " + std::to_string(ndev) + " GPU(s) visible");
@@ -953,14 +963,19 @@ void solve(int argc, char** argv)
     for (size_t l = 1; l < S.mg_view.size(); ++l)
     {
       const auto& v = S.mg_view[l];
-      if (o.pc_type == "agg")
+      if (o.pc_type == "agg" || o.pc_type == "sagg")
         std::cout << "  level " << l - 1 << ": " << (l == 1 ? "the assembled matrix" : "aggregates of the level above") << ", dofs "
                   << (long long)v[3] << ", nonzeros " << (long long)v[4];
       else
         std::cout << "  level " << l - 1 << ": cells " << (long long)v[0] << "x" << (long long)v[1] << "x" << (long long)v[2] << ", order "
                   << (l - 1 < (size_t)m[7] ? o.order : 1) << ", dofs " << (long long)v[3] << ", nonzeros " << (long long)v[4];
       if (v[7] > 0)
-        std::cout << ", smoother chebyshev-jacobi degree " << (int)v[7] << " on [" << v[6] << ", " << v[5] << "]\n";
+      {
+        std::cout << ", smoother chebyshev-jacobi degree " << (int)v[7] << " on [" << v[6] << ", " << v[5] << "]";
+        if (l - 1 < S.mg_pnnz.size())
+          std::cout << ", prolongator entries " << S.mg_pnnz[l - 1] << ", omega " << 4.0 / (3.0 * v[5]);
+        std::cout << "\n";
+      }
       else
         std::cout << ", dense direct solve\n";
     }
