@@ -144,7 +144,40 @@ enum
    * Dirichlet rows).  A level whose products have more terms than 32-bit positions take is declined with ZZZ_ERR_LIMIT.
    * The hierarchy is kept while pattern and Dirichlet set are kept; new matrix values (or another pc_esteig_its) refresh
    * the bounds and the values of P and of the coarse matrices level by level, to the bits of a fresh set-up. */
-  ZZZ_PC_SAGG = 6
+  ZZZ_PC_SAGG = 6,
+  /* ZZZ_PC_SAGG with a tentative prolongator that carries the near-nullspace -- the six rigid-body modes of
+   * zzz_near_nullspace_build -- through every level (PETSc: -pc_type gamg with MatSetNearNullSpace, what the reference builds
+   * the modes for).  Declined with ZZZ_ERR_ARG: everything ZZZ_PC_AGG declines; block size != 3 (for scalar problems use
+   * -pc_type sagg); a context with no near-nullspace built (zzz_near_nullspace_build, after the last dofmap upload).
+   * ZZZ_PC_SAGG itself never reads the modes.  The rule, per level (csrc/zzz_sagg_rbm.hip).  Scope, options, level rule,
+   * smoother, cycle, spectrum bound and omega = 4 / (3 hi) are ZZZ_PC_SAGG's.  Every sum is a chain of plain double additions
+   * of individually rounded products, with no fused multiply-add.
+   *   node size   3 on level 0, 6 on every coarse level.
+   *   B           level 0: the library's six vectors as zzz_near_nullspace_build left them, in the caller's numbering, entries
+   *               of constrained scalar dofs taken as 0.  Level l + 1: the B_c below, 6 columns by 6 rows per aggregate.
+   *   aggregates  ZZZ_PC_AGG's rule on the node graph of the level's matrix: nodes are blocks of 3 scalar dofs on level 0 and
+   *               blocks of 6 below.
+   *   P_t, B_c    per aggregate J, its m member nodes in ascending index (the caller's numbering on level 0): take the rows of
+   *               B of its member dofs, node-major then component ascending; modified Gram-Schmidt over the six columns in
+   *               column order q = 0..5: for j < q, R(j, q) = <Q_j, b_q>, then b_q -= R(j, q) Q_j; then R(q, q) = |b_q| and
+   *               Q_q = b_q / R(q, q).  A column is DROPPED when |b_q| after the projections is at most 2^-30 of its norm
+   *               before them, or when it is zero: then Q_q = 0 and row q of R is 0.  P_t(row, (J, q)) = Q_q(row); rows of
+   *               constrained dofs and dropped columns carry no entries.  B_c's rows (J, 0..5) are R.
+   *   one sum     every inner product and norm: partial sum l (l = 0..63) adds the products of the rows l, l + 64, ... front
+   *               to back, then the 64 partial sums meet in the tree s[i] += s[i + o] for i < o, o = 32, 16, 8, 4, 2, 1; the
+   *               result is s[0].  A norm is the square root of that sum of squares.
+   *   P           P_t - omega D^-1 (A P_t): P(i, (J, q)) = P_t(i, (J, q)) - (omega s) / a_ii, s = sum_k a_ik P_t(k, (J, q))
+   *               over the unconstrained k in ascending k.  Pattern: (i, (J, q)) wherever row i is unconstrained and has a
+   *               structural a_ik with k unconstrained, k in aggregate J and column q kept.  Rows of constrained dofs are empty.
+   *   R, T, A_c   R = P^T, T = A P and A_c = P^T T exactly as ZZZ_PC_SAGG forms them: sorted term lists, ascending summation
+   *               index, one thread per run.
+   *   dropped     a dropped coarse dof (J, q) has no entry in P; its row of A_c is the single entry 1 on the diagonal.  On the
+   *               next level it is an ordinary dof with a zero row in B.
+   * The coarse levels are scalar matrices (the node size belongs to the level).  The aggregates, Q, B_c and the drops depend
+   * on B, the Dirichlet bytes and the kept aggregates only: new matrix values (or another pc_esteig_its) re-form the values of
+   * P, T and A_c on the kept lists, to the bits of a fresh set-up.  P has six columns per aggregate: the ZZZ_ERR_LIMIT of
+   * 32-bit term positions comes much earlier than ZZZ_PC_SAGG's, near 1.7 M dofs on generated P1 elasticity cubes. */
+  ZZZ_PC_SAGG_RBM = 7
 };
 enum
 {
@@ -568,7 +601,7 @@ int zzz_pattern_info(zzz_ctx* ctx, int64_t info[8]);
  * PCSetUp(PCMG) behind solver.set_from_options() (src/poisson_problem.cpp:169; README.md:59-146): builds the hierarchy
  * for these options, or refreshes its values after an assembly.  Optional: zzz_cg_solve(pc = ZZZ_PC_MG) does it on first
  * use, inside the solve, where PETSc's PCSetUp runs.  Overwrites the context's Krylov work vectors (not b, not u).
- * opts->pc == ZZZ_PC_PMG builds the p-multigrid hierarchy, ZZZ_PC_AGG / ZZZ_PC_SAGG the (smoothed) aggregation hierarchy
+ * opts->pc == ZZZ_PC_PMG builds the p-multigrid hierarchy, ZZZ_PC_AGG / ZZZ_PC_SAGG / ZZZ_PC_SAGG_RBM the (smoothed) aggregation hierarchy
  * (zzz_mg_info then reports nx = ny = nz = 0 for every level); any other value is read as ZZZ_PC_MG.  One context holds one hierarchy: a set-up
  * of another kind replaces it. */
 int zzz_mg_setup(zzz_ctx* ctx, const zzz_solver_opts* opts);
@@ -587,17 +620,22 @@ int zzz_mg_transfer(zzz_ctx* ctx, int level, int dir, const double* in, double* 
 /* The matrix of a coarse level (1 <= level < levels) as the hierarchy holds it, for parity checks: 64-bit row pointers
  * (scalar dofs + 1), columns and values (zzz_mg_info(level) gives the sizes); any of the three may be NULL. */
 int zzz_mg_level_csr(zzz_ctx* ctx, int level, int64_t* rowptr, int32_t* cols, double* vals);
-/* The stored prolongator between level and level + 1 of a ZZZ_PC_SAGG hierarchy: 64-bit row pointers (fine scalar dofs + 1),
+/* The stored prolongator between level and level + 1 of a ZZZ_PC_SAGG or ZZZ_PC_SAGG_RBM hierarchy: 64-bit row pointers (fine scalar dofs + 1),
  * coarse columns, values, fine rows in the caller's numbering on level 0; any of the three may be NULL; out_nnz optional.
  * ZZZ_ERR_ARG for another kind of hierarchy.  (A new entry point: ZZZ_ABI_VERSION is unchanged.) */
 int zzz_mg_level_p(zzz_ctx* ctx, int level, int64_t* rowptr, int32_t* cols, double* vals, int64_t* out_nnz);
+/* The near-nullspace B that level's orthogonalisation read in a ZZZ_PC_SAGG_RBM hierarchy (the coarsest level: the B_c the
+ * level above it wrote), out[6][scalar dofs of the level]: level 0 in the caller's numbering with the entries of constrained
+ * dofs 0.  ZZZ_ERR_ARG for another kind of hierarchy.  zzz_mg_info(level) of such a hierarchy reports, in ny's slot (nx = nz = 0:
+ * there is no cube), how many of that level's dofs are dropped coarse dofs.  (A new entry point: ZZZ_ABI_VERSION is unchanged.) */
+int zzz_mg_level_nns(zzz_ctx* ctx, int level, double* out);
 
 /* Version of this header's ABI: bumped whenever an existing entry point changes what it reads or writes (7: zzz_cg_solve
  * reads the two pc_mg_* fields behind pc_ratio).  ZZZ_PC_PMG did not bump it: a new enumerator changes no struct, no
  * entry point and nothing that a caller built against the earlier header passes or receives -- such a caller never
  * sends the value 4, and a library without it answers that value with ZZZ_ERR_ARG.  Nor did zzz_bc_values_upload: a new
  * entry point, no struct and no existing entry changed.  ZZZ_PC_AGG (5) and zzz_mg_level_csr: the same two arguments;
- * ZZZ_PC_SAGG (6) and zzz_mg_level_p: the same two again. */
+ * ZZZ_PC_SAGG (6) and zzz_mg_level_p: the same two again; ZZZ_PC_SAGG_RBM (7) and zzz_mg_level_nns: and again. */
 #define ZZZ_ABI_VERSION 7
 int zzz_abi_version(void);
 

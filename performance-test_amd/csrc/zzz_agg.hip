@@ -25,6 +25,10 @@
 // A_c = P^T A P: coarse entry (I, J) is the sum of the fine entries a_ij with i in I, j in J, summed in ascending fine
 // (row, column) order of the caller's numbering: the entries' coarse keys go through a STABLE radix sort (rocPRIM), one
 // thread then sums each run front to back -- two set-ups give the same bits, and a refresh is that sum alone.
+//
+// The aggregation reads its graph through AggGraph: a context's matrix with its block size (1 or 3), or -- for the coarse levels
+// of ZZZ_PC_SAGG_RBM, whose nodes are blocks of six rows of a scalar matrix -- node rows written out by the caller
+// (agg_aggregate_graph).
 #include "zzz_cg.h"
 
 #include "zzz_prim.h"
@@ -413,6 +417,8 @@ AggLevel* agg_new() { return new AggLevel(); }
 void agg_free(AggLevel* A) { delete A; }
 int64_t agg_count(const AggLevel* A) { return A->nagg; }
 const int32_t* agg_map(const AggLevel* A) { return A->agg.p; }
+const int32_t* agg_member_offsets(const AggLevel* A) { return A->moff.p; }
+const int32_t* agg_members(const AggLevel* A) { return A->mem.p; }
 
 // flags (caller order) -> numbers base + rank for the flagged nodes; *count = how many
 static int agg_number(zzz_ctx* ctx, AggLevel& A, int what, int32_t base, const int32_t* perm, const int32_t* state,
@@ -430,14 +436,26 @@ static int agg_number(zzz_ctx* ctx, AggLevel& A, int what, int32_t base, const i
   return ZZZ_OK;
 }
 
-// The aggregates of the matrix of `f` as it stands (pattern, zero structure of the values, Dirichlet bytes), on ctx->stream.
+// The graph the aggregates are chosen on: n nodes of BS scalar rows each of a CSR matrix as it stands (pattern, zero structure
+// of the values), the Dirichlet bytes of its scalar rows, and the nodes' numbers in the caller's numbering (null: their own).
+struct AggGraph
+{
+  int64_t n;
+  const rp_t* rowptr;
+  const int32_t* cols;
+  const double* vals;
+  const uint8_t* bc;
+  const int32_t* perm;
+};
+
+// The aggregates of that graph, on ctx->stream.
 template <int BS>
-static int agg_aggregate_bs(zzz_ctx* ctx, zzz_ctx* f, AggLevel& A)
+static int agg_aggregate_bs(zzz_ctx* ctx, const AggGraph& G, AggLevel& A)
 {
   hipStream_t s = ctx->stream;
-  const int64_t n = f->n_owned;
+  const int64_t n = G.n;
   const int g = grid_cap(n, VB, 1 << 16);
-  const int32_t* perm = f->dofmap.renumbered ? f->perm.p : nullptr;
+  const int32_t* perm = G.perm;
   A.bs = BS;
   A.nf = n;
   A.nagg = 0;
@@ -454,10 +472,10 @@ static int agg_aggregate_bs(zzz_ctx* ctx, zzz_ctx* f, AggLevel& A)
   ZZZ_HIP(ctx, m1.alloc((size_t)n));
   ZZZ_HIP(ctx, near.alloc((size_t)n));
   ZZZ_HIP(ctx, A.agg.alloc((size_t)n));
-  hipLaunchKernelGGL(k_agg_init<BS>, dim3(g), dim3(VB), 0, s, n, f->bc.p, perm, state.p, key.p);
-  const rp_t* rp = f->rowptr.p;
-  const int32_t* cl = f->cols.p;
-  const double* vl = f->vals.p;
+  hipLaunchKernelGGL(k_agg_init<BS>, dim3(g), dim3(VB), 0, s, n, G.bc, perm, state.p, key.p);
+  const rp_t* rp = G.rowptr;
+  const int32_t* cl = G.cols;
+  const double* vl = G.vals;
   A.rounds = 0;
   for (;;)
   {
@@ -505,7 +523,19 @@ int agg_aggregate(zzz_ctx* ctx, zzz_ctx* f, AggLevel* A)
   if (f->n_owned >= ((int64_t)1 << 31) / 4 || f->nnz >= (int64_t)INT32_MAX - 16)
     return fail(ctx, ZZZ_ERR_LIMIT, "-pc_type agg: %lld block dofs / %lld nonzeros on a level: 32-bit entry indices",
                 (long long)f->n_owned, (long long)f->nnz);
-  return f->bs == 3 ? agg_aggregate_bs<3>(ctx, f, *A) : agg_aggregate_bs<1>(ctx, f, *A);
+  const AggGraph G{f->n_owned, f->rowptr.p, f->cols.p, f->vals.p, f->bc.p, f->dofmap.renumbered ? f->perm.p : nullptr};
+  return f->bs == 3 ? agg_aggregate_bs<3>(ctx, G, *A) : agg_aggregate_bs<1>(ctx, G, *A);
+}
+
+// ... of a graph given as it is: one row per node (ZZZ_PC_SAGG_RBM's coarse levels: the nodes are blocks of six scalar rows of
+// a matrix adopted as scalar, zzz_sagg.hip writes the node rows out)
+int agg_aggregate_graph(zzz_ctx* ctx, int64_t n, int64_t nnz, const rp_t* rowptr, const int32_t* cols, const double* vals,
+                        const uint8_t* bc, AggLevel* A)
+{
+  if (n >= ((int64_t)1 << 31) / 4 || nnz >= (int64_t)INT32_MAX - 16)
+    return fail(ctx, ZZZ_ERR_LIMIT, "-pc_type agg: %lld nodes / %lld nonzeros on a level: 32-bit entry indices", (long long)n,
+                (long long)nnz);
+  return agg_aggregate_bs<1>(ctx, AggGraph{n, rowptr, cols, vals, bc, nullptr}, *A);
 }
 
 // The coarse values on the kept aggregates, and the product stream of the coarse context packed from them

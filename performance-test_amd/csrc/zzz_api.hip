@@ -292,6 +292,7 @@ int zzz_ctx_create(int device, zzz_ctx** out)
       zzz::preload_mg();
       zzz::preload_agg();
       zzz::preload_sagg();
+      zzz::preload_sagg_rbm();
       zzz::preload_pmg();
       zzz::preload_nullspace();
       (void)hipGetLastError();
@@ -1167,9 +1168,9 @@ int zzz_cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rno
   if (o->variant == ZZZ_CG_CGH && o->pc != ZZZ_PC_NONE)
     return fail(ctx, ZZZ_ERR_ARG, "src/cg.h has no preconditioner: use pc = ZZZ_PC_NONE");
   if (o->pc != ZZZ_PC_NONE && o->pc != ZZZ_PC_JACOBI && o->pc != ZZZ_PC_CHEBYSHEV_JACOBI && o->pc != ZZZ_PC_MG && o->pc != ZZZ_PC_PMG
-      && o->pc != ZZZ_PC_AGG && o->pc != ZZZ_PC_SAGG)
-    return fail(ctx, ZZZ_ERR_ARG, "unsupported preconditioner %d (none, jacobi, chebyshev-jacobi, mg, pmg, agg, sagg)", o->pc);
-  if (o->pc == ZZZ_PC_MG || o->pc == ZZZ_PC_PMG || o->pc == ZZZ_PC_AGG || o->pc == ZZZ_PC_SAGG)
+      && o->pc != ZZZ_PC_AGG && o->pc != ZZZ_PC_SAGG && o->pc != ZZZ_PC_SAGG_RBM)
+    return fail(ctx, ZZZ_ERR_ARG, "unsupported preconditioner %d (none, jacobi, chebyshev-jacobi, mg, pmg, agg, sagg, sagg_rbm)", o->pc);
+  if (o->pc == ZZZ_PC_MG || o->pc == ZZZ_PC_PMG || o->pc == ZZZ_PC_AGG || o->pc == ZZZ_PC_SAGG || o->pc == ZZZ_PC_SAGG_RBM)
     if (int rc = mg_check(ctx, o))
       return rc;
   if (o->pc == ZZZ_PC_CHEBYSHEV_JACOBI && o->op != ZZZ_OP_CSR)

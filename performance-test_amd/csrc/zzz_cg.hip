@@ -1137,7 +1137,7 @@ int cg_solve(zzz_ctx* ctx, const zzz_solver_opts* o, int* iters, double* rnorm)
   if (o->variant == ZZZ_CG_PIPE)
     return cg_solve_pipe(ctx, o, iters, rnorm); // zzz_cg_pipe.hip
   if ((o->pc == ZZZ_PC_CHEBYSHEV_JACOBI && !o->single_reduction) || o->pc == ZZZ_PC_MG || o->pc == ZZZ_PC_PMG || o->pc == ZZZ_PC_AGG
-      || o->pc == ZZZ_PC_SAGG)
+      || o->pc == ZZZ_PC_SAGG || o->pc == ZZZ_PC_SAGG_RBM)
     return cg_solve_pc(ctx, o, iters, rnorm);
   if (o->single_reduction)
     return cg_solve_single_reduction(ctx, o, iters, rnorm);
@@ -1706,7 +1706,7 @@ int cheb_terms(zzz_ctx* c, zzz_ctx* owner, const ChebPlan& C, const double* b, d
   return ZZZ_OK;
 }
 
-// ---- KSPCG around a preconditioner object (ZZZ_PC_CHEBYSHEV_JACOBI; ZZZ_PC_MG / _PMG / _AGG / _SAGG, zzz_mg.hip) ---------
+// ---- KSPCG around a preconditioner object (ZZZ_PC_CHEBYSHEV_JACOBI; ZZZ_PC_MG / _PMG / _AGG / _SAGG / _SAGG_RBM, zzz_mg.hip) ----
 // The scalar logic, history and reasons are the classical loop's (k_update_p with Jacobi's semantics for alpha and beta).
 // What a preconditioner brings:
 struct CgPc

@@ -469,6 +469,7 @@ void preload_pmg();
 void preload_pattern();
 void preload_renumber();
 void preload_sagg();
+void preload_sagg_rbm();
 void preload_sellp();
 void preload_sellp_dict();
 void preload_sellp_pack();
@@ -631,6 +632,11 @@ int agg_refresh(zzz_ctx* ctx, zzz_ctx* f, AggLevel* A, zzz_ctx* c);
 int agg_restrict(zzz_ctx* ctx, const int* stop, const AggLevel* A, const uint8_t* bcf, const double* rf, const double* sub, double* rc);
 int agg_prolong(zzz_ctx* ctx, const int* stop, const AggLevel* A, const uint8_t* bcf, const double* ec, double* xf, int accumulate);
 const int32_t* agg_map(const AggLevel* A); // device: the aggregate of every fine block dof, -1: none
+const int32_t* agg_member_offsets(const AggLevel* A); // device: the map inverted -- the members of aggregate a are
+const int32_t* agg_members(const AggLevel* A);        // members[offsets[a] .. offsets[a + 1]), ascending in the caller's numbering
+// ... the aggregates of a graph given as it is: n nodes of one CSR row each (values: zero or not), bc: a byte per node
+int agg_aggregate_graph(zzz_ctx* ctx, int64_t n, int64_t nnz, const rp_t* rowptr, const int32_t* cols, const double* vals,
+                        const uint8_t* bc, AggLevel* A);
 // zzz_sagg.hip (ZZZ_PC_SAGG): the same aggregates; P = (I - omega D^-1 A) P_t stored with its transpose, A_c = P^T (A P)
 // adopted by the child context c (level: of f, for the messages); the values again on the kept patterns; the two transfers
 // enqueued on ctx->stream; P on the host, level 0's rows in the caller's numbering
@@ -644,6 +650,15 @@ int sagg_refresh(zzz_ctx* ctx, zzz_ctx* f, SaggLevel* S, double omega, zzz_ctx* 
 int sagg_restrict(zzz_ctx* ctx, const int* stop, const SaggLevel* S, const double* rf, const double* sub, double* rc);
 int sagg_prolong(zzz_ctx* ctx, const int* stop, const SaggLevel* S, const double* ec, double* xf, int accumulate);
 int sagg_download_p(zzz_ctx* ctx, zzz_ctx* f, const SaggLevel* S, int64_t* rowptr, int32_t* cols, double* vals);
+// zzz_sagg_rbm.hip (ZZZ_PC_SAGG_RBM): ZZZ_PC_SAGG's level with the near-nullspace in its tentative prolongator.  The aggregates
+// of f's node graph (nodes of 3 scalar dofs on level 0, of 6 below); P, R, T and A_c adopted by c as a scalar matrix (above:
+// the level above f, whose B_c the orthogonalisation reads; null on level 0: the context's near-nullspace); the values again.
+// Transfers, count, P's size and download are sagg_*'s.  srbm_nns: device, the B the level read (coarse: the B_c it wrote).
+int srbm_aggregate(zzz_ctx* ctx, zzz_ctx* f, SaggLevel* S, int level);
+int srbm_galerkin(zzz_ctx* ctx, zzz_ctx* f, SaggLevel* S, const SaggLevel* above, double omega, zzz_ctx* c, int level);
+int srbm_refresh(zzz_ctx* ctx, zzz_ctx* f, SaggLevel* S, double omega, zzz_ctx* c);
+int64_t srbm_dropped(const SaggLevel* S); // coarse dofs below S that carry no column of P
+const double* srbm_nns(const SaggLevel* S, bool coarse);
 
 // comm
 int comm_allreduce_sum(zzz_ctx* ctx, double* dev, int n);

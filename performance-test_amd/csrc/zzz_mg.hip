@@ -27,9 +27,11 @@
 // ZZZ_PC_AGG builds its levels from the matrix instead (zzz_agg.hip: aggregates, P^T A P into child contexts that adopt the
 // CSR, the two transfers); everything else -- smoother, cycle, dense solve, caching, refresh, profiling -- is the one here.
 // ZZZ_PC_SAGG is ZZZ_PC_AGG with a smoothed prolongator (zzz_sagg.hip), whose damping needs the level's spectrum bound: there
-// a level's bound comes before the next level's values, in a build and in a refresh.
+// a level's bound comes before the next level's values, in a build and in a refresh.  ZZZ_PC_SAGG_RBM is ZZZ_PC_SAGG with the
+// context's near-nullspace in the tentative prolongator (zzz_sagg_rbm.hip): nodes of 6 dofs on its coarse levels, whose
+// contexts are scalar.
 //
-// The four differ in MgKind alone (a level's transfer, the next level, that level's values); the set-up keeps a
+// The five differ in MgKind alone (a level's transfer, the next level, that level's values); the set-up keeps a
 // hierarchy while its MgStructKey holds and the levels' values while its MgValuesKey holds.
 #include "zzz_cg.h"
 
@@ -214,16 +216,20 @@ __global__ __launch_bounds__(VB) void k_mg_dense(const int* __restrict__ stop, c
 
 // How a level reaches the next coarser one -- its transfer, and where that level and its matrix values come from: the
 // same cube on half the cells (tables above), the same cube at order 1 (zzz_pmg.hip), the aggregates of its matrix
-// (zzz_agg.hip), the same aggregates under a smoothed prolongator (zzz_sagg.hip).  mg_coarsen, mg_level_values, mg_restrict
-// and mg_prolong are the four places that tell them apart.
+// (zzz_agg.hip), the same aggregates under a smoothed prolongator (zzz_sagg.hip), aggregates of the node graph under a
+// smoothed prolongator that carries the near-nullspace (zzz_sagg_rbm.hip).  mg_coarsen, mg_level_values, mg_restrict and
+// mg_prolong are the four places that tell them apart.
 enum class MgKind
 {
   GEOM,
   PLEVEL,
   AGG,
-  SAGG
+  SAGG,
+  SAGG_RBM
 };
-static bool mg_algebraic(MgKind k) { return k == MgKind::AGG || k == MgKind::SAGG; }
+static bool mg_smoothed(MgKind k) { return k == MgKind::SAGG || k == MgKind::SAGG_RBM; } // (a stored P whose damping needs the bound)
+static bool mg_algebraic(MgKind k) { return k == MgKind::AGG || mg_smoothed(k); }
+constexpr int MG_RBM_NODE = 6; // scalar dofs per coarse node of ZZZ_PC_SAGG_RBM: one per rigid-body mode
 
 struct MgLevel
 {
@@ -238,7 +244,7 @@ struct MgLevel
   DevBuf<int32_t> tc, rng;
   DevBuf<double> tf;
   AggLevel* agg = nullptr;   // AGG: the aggregates of this level
-  SaggLevel* sagg = nullptr; // SAGG: the aggregates of this level and the prolongator on them
+  SaggLevel* sagg = nullptr; // SAGG, SAGG_RBM: the aggregates of this level and the prolongator on them
   ~MgLevel()
   {
     agg_free(agg);
@@ -319,8 +325,9 @@ void mg_invalidate(zzz_ctx* ctx)
 
 int mg_check(zzz_ctx* ctx, const zzz_solver_opts* o)
 {
-  const bool pmg = o->pc == ZZZ_PC_PMG, sagg = o->pc == ZZZ_PC_SAGG, agg = o->pc == ZZZ_PC_AGG || sagg;
-  const char* tag = sagg ? "-pc_type sagg" : agg ? "-pc_type agg" : pmg ? "-pc_type pmg" : "-pc_type mg";
+  const bool pmg = o->pc == ZZZ_PC_PMG, rbm = o->pc == ZZZ_PC_SAGG_RBM, sagg = o->pc == ZZZ_PC_SAGG;
+  const bool agg = o->pc == ZZZ_PC_AGG || sagg || rbm;
+  const char* tag = rbm ? "-pc_type sagg_rbm" : sagg ? "-pc_type sagg" : agg ? "-pc_type agg" : pmg ? "-pc_type pmg" : "-pc_type mg";
   if (o->variant == ZZZ_CG_PIPE)
     return fail(ctx, ZZZ_ERR_ARG, "%s: not with -ksp_type pipecg (ZZZ_CG_PIPE takes jacobi or none)", tag);
   if (o->variant != ZZZ_CG_PETSC)
@@ -340,6 +347,12 @@ int mg_check(zzz_ctx* ctx, const zzz_solver_opts* o)
       return fail(ctx, ZZZ_ERR_ARG, "%s: the context has %lld ghost dofs: one rank only", tag, (long long)ctx->n_ghost);
     if (ctx->bs != 1 && ctx->bs != 3)
       return fail(ctx, ZZZ_ERR_ARG, "%s: block size %d", tag, ctx->bs);
+    if (rbm && ctx->bs != 3)
+      return fail(ctx, ZZZ_ERR_ARG, "%s: block size %d; the rigid-body modes belong to block size 3 -- for scalar problems use "
+                                    "-pc_type sagg", tag, ctx->bs);
+    if (rbm && ctx->dofmap.near_null_ld == 0)
+      return fail(ctx, ZZZ_ERR_ARG, "%s: the context has no near-nullspace: build it with zzz_near_nullspace_build (after the "
+                                    "last dofmap upload)", tag);
   }
   else
   {
@@ -370,7 +383,7 @@ int mg_check(zzz_ctx* ctx, const zzz_solver_opts* o)
 // the error of a child context becomes the caller's
 static int child_fail(zzz_ctx* ctx, zzz_ctx* c, int rc, int level, const char* what)
 {
-  return fail(ctx, rc, "-pc_type mg / pmg / agg / sagg, level %d, %s: %s", level, what, c ? c->err.c_str() : zzz_last_error(nullptr));
+  return fail(ctx, rc, "-pc_type mg / pmg / agg / sagg / sagg_rbm, level %d, %s: %s", level, what, c ? c->err.c_str() : zzz_last_error(nullptr));
 }
 
 static int mg_build_tables(zzz_ctx* ctx, MgLevel& F, const MgLevel& C)
@@ -537,9 +550,11 @@ static int mg_coarsen(zzz_ctx* ctx, MgHier& H, const zzz_solver_opts* os, bool* 
       F.agg = agg_new();
     else
       F.sagg = sagg_new();
-    if (int rc = F.agg ? agg_aggregate(ctx, F.ctx, F.agg) : sagg_aggregate(ctx, F.ctx, F.sagg))
+    if (int rc = F.agg                         ? agg_aggregate(ctx, F.ctx, F.agg)
+                 : F.kind == MgKind::SAGG_RBM ? srbm_aggregate(ctx, F.ctx, F.sagg, l - 1)
+                                              : sagg_aggregate(ctx, F.ctx, F.sagg))
       return rc;
-    ncdof = (F.agg ? agg_count(F.agg) : sagg_count(F.sagg)) * ctx->bs;
+    ncdof = F.agg ? agg_count(F.agg) * ctx->bs : sagg_count(F.sagg) * (F.kind == MgKind::SAGG_RBM ? MG_RBM_NODE : ctx->bs);
     if (ncdof == 0 || 2 * ncdof > F.ndof)
     {
       agg_free(F.agg);
@@ -567,6 +582,8 @@ static int mg_coarsen(zzz_ctx* ctx, MgHier& H, const zzz_solver_opts* os, bool* 
       return agg_galerkin(ctx, F.ctx, F.agg, c);
     if (int rc = chebyshev_setup(F.ctx, os, F.cheb)) // (kept per set of matrix values: the set-up below finds it again)
       return l > 1 ? child_fail(ctx, F.ctx, rc, l - 1, "spectrum bound") : rc;
+    if (F.kind == MgKind::SAGG_RBM)
+      return srbm_galerkin(ctx, F.ctx, F.sagg, l > 1 ? H.lv[(size_t)l - 2]->sagg : nullptr, mg_omega(F), c, l - 1);
     return sagg_galerkin(ctx, F.ctx, F.sagg, mg_omega(F), c, l - 1);
   }
   // the same problem re-discretised at order 1: on the same cells below the Pk level, on half of them below a P1 level
@@ -590,7 +607,9 @@ static int mg_level_values(zzz_ctx* ctx, MgLevel& F, MgLevel& C, int l, bool bui
     // (a build has just summed them; a refresh sums the new values on the kept aggregates, level by level -- SAGG with the
     // bound that the level above has just been given)
     if (!built)
-      if (int rc = F.agg ? agg_refresh(ctx, F.ctx, F.agg, C.ctx) : sagg_refresh(ctx, F.ctx, F.sagg, mg_omega(F), C.ctx))
+      if (int rc = F.agg                         ? agg_refresh(ctx, F.ctx, F.agg, C.ctx)
+                   : F.kind == MgKind::SAGG_RBM ? srbm_refresh(ctx, F.ctx, F.sagg, mg_omega(F), C.ctx)
+                                                : sagg_refresh(ctx, F.ctx, F.sagg, mg_omega(F), C.ctx))
         return child_fail(ctx, C.ctx, rc, l, "coarse values");
     return ZZZ_OK;
   }
@@ -629,7 +648,7 @@ static int mg_build(zzz_ctx* ctx, MgHier& H, MgKind kind, const zzz_solver_opts*
   if (dofs > MG_DENSE_MAX)
     return fail(ctx, ZZZ_ERR_ARG, "-pc_type %s: the coarsest of %d levels has %lld dofs, the dense solve takes at most %lld: "
                                   "allow more levels (pc_mg_levels) or a lower pc_mg_coarse_eq_limit",
-                kind == MgKind::SAGG ? "sagg" : agg ? "agg" : "mg", (int)H.lv.size(), (long long)dofs, (long long)MG_DENSE_MAX);
+                kind == MgKind::SAGG_RBM ? "sagg_rbm" : kind == MgKind::SAGG ? "sagg" : agg ? "agg" : "mg", (int)H.lv.size(), (long long)dofs, (long long)MG_DENSE_MAX);
   return ZZZ_OK;
 }
 
@@ -637,7 +656,7 @@ int mg_setup(zzz_ctx* ctx, const zzz_solver_opts* o)
 {
   if (int rc = mg_check(ctx, o))
     return rc;
-  const MgKind kind = o->pc == ZZZ_PC_SAGG ? MgKind::SAGG : o->pc == ZZZ_PC_AGG ? MgKind::AGG
+  const MgKind kind = o->pc == ZZZ_PC_SAGG_RBM ? MgKind::SAGG_RBM : o->pc == ZZZ_PC_SAGG ? MgKind::SAGG : o->pc == ZZZ_PC_AGG ? MgKind::AGG
                       : ctx->dofmap.order > 1 ? MgKind::PLEVEL : MgKind::GEOM;
   const bool agg = mg_algebraic(kind);
   const int limit = o->pc_mg_coarse_eq_limit > 0 ? o->pc_mg_coarse_eq_limit : 1000;
@@ -683,7 +702,7 @@ int mg_setup(zzz_ctx* ctx, const zzz_solver_opts* o)
   if (!(H->vkey == vkey))
   {
     // (SAGG: the bounds are part of the prolongator, so another estimate is other values)
-    const bool values = H->vkey.mat_version != vkey.mat_version || (kind == MgKind::SAGG && H->vkey.est_its != vkey.est_its);
+    const bool values = H->vkey.mat_version != vkey.mat_version || (mg_smoothed(kind) && H->vkey.est_its != vkey.est_its);
     H->ready = false;
     // ---- the levels' values: matrices, inverse diagonals, spectrum bounds, the coarsest inverse ----
     for (size_t l = 0; l < H->lv.size(); ++l)
@@ -726,6 +745,7 @@ static int mg_restrict(zzz_ctx* ctx, const int* stop, MgLevel& F, MgLevel& C, co
   case MgKind::AGG:
     return agg_restrict(ctx, stop, F.agg, F.ctx->bc.p, rf, sub, rc);
   case MgKind::SAGG:
+  case MgKind::SAGG_RBM:
     return sagg_restrict(ctx, stop, F.sagg, rf, sub, rc);
   case MgKind::PLEVEL:
     return pmg_restrict(ctx, stop, F.order, ctx->bs, F.n, F.ctx->bc.p, C.ctx->bc.p, rf, sub, rc);
@@ -748,6 +768,7 @@ static int mg_prolong(zzz_ctx* ctx, const int* stop, MgLevel& F, MgLevel& C, con
   case MgKind::AGG:
     return agg_prolong(ctx, stop, F.agg, F.ctx->bc.p, ec, xf, accumulate);
   case MgKind::SAGG:
+  case MgKind::SAGG_RBM:
     return sagg_prolong(ctx, stop, F.sagg, ec, xf, accumulate);
   case MgKind::PLEVEL:
     return pmg_prolong(ctx, stop, F.order, ctx->bs, F.n, F.ctx->bc.p, C.ctx->bc.p, ec, xf, accumulate);
@@ -858,7 +879,7 @@ int zzz_mg_setup(zzz_ctx* ctx, const zzz_solver_opts* opts)
   if (!opts)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_mg_setup: NULL options");
   zzz_solver_opts o = *opts;
-  o.pc = opts->pc == ZZZ_PC_PMG || opts->pc == ZZZ_PC_AGG || opts->pc == ZZZ_PC_SAGG ? opts->pc : ZZZ_PC_MG;
+  o.pc = opts->pc == ZZZ_PC_PMG || opts->pc == ZZZ_PC_AGG || opts->pc == ZZZ_PC_SAGG || opts->pc == ZZZ_PC_SAGG_RBM ? opts->pc : ZZZ_PC_MG;
   if (int rc = mg_setup(ctx, &o))
     return rc;
   ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -894,6 +915,8 @@ int zzz_mg_info(zzz_ctx* ctx, int level, double out[8])
   out[0] = (double)L.n[0];
   out[1] = (double)L.n[1];
   out[2] = (double)L.n[2];
+  if (L.kind == MgKind::SAGG_RBM && level > 0) // (no cube: ny's slot holds the dropped coarse dofs among this level's)
+    out[1] = (double)srbm_dropped(H->lv[(size_t)level - 1]->sagg);
   out[3] = (double)L.ndof;
   out[4] = (double)L.ctx->nnz;
   const bool smooths = (size_t)level + 1 < H->lv.size();
@@ -1008,13 +1031,33 @@ int zzz_mg_level_p(zzz_ctx* ctx, int level, int64_t* rowptr, int32_t* cols, doub
   MgHier* H = ctx->mg;
   if (!H || !H->ready)
     return fail(ctx, ZZZ_ERR_ARG, "zzz_mg_level_p: no hierarchy (zzz_mg_setup, or a solve with ZZZ_PC_SAGG)");
-  if (H->lv[0]->kind != MgKind::SAGG)
-    return fail(ctx, ZZZ_ERR_ARG, "zzz_mg_level_p: the hierarchy is not ZZZ_PC_SAGG's: no prolongator is stored");
+  if (!mg_smoothed(H->lv[0]->kind))
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_mg_level_p: the hierarchy is not ZZZ_PC_SAGG's or ZZZ_PC_SAGG_RBM's: no prolongator is stored");
   if (level < 0 || (size_t)level + 1 >= H->lv.size())
     return fail(ctx, ZZZ_ERR_ARG, "zzz_mg_level_p: level %d of %d (the coarsest has no prolongator below it)", level, (int)H->lv.size());
   const MgLevel& F = *H->lv[(size_t)level];
   if (out_nnz)
     *out_nnz = sagg_p_nnz(F.sagg);
   return sagg_download_p(ctx, F.ctx, F.sagg, rowptr, cols, vals);
+}
+
+int zzz_mg_level_nns(zzz_ctx* ctx, int level, double* out)
+{
+  if (!ctx)
+    return fail(nullptr, ZZZ_ERR_ARG, "NULL context");
+  ZZZ_HIP(ctx, hipSetDevice(ctx->device));
+  MgHier* H = ctx->mg;
+  if (!H || !H->ready)
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_mg_level_nns: no hierarchy (zzz_mg_setup, or a solve with ZZZ_PC_SAGG_RBM)");
+  if (H->lv[0]->kind != MgKind::SAGG_RBM)
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_mg_level_nns: the hierarchy is not ZZZ_PC_SAGG_RBM's: no near-nullspace is carried");
+  if (level < 0 || (size_t)level >= H->lv.size() || H->lv.size() < 2 || !out)
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_mg_level_nns: level %d of %d (a hierarchy of one level orthogonalises nothing), or NULL output",
+                level, (int)H->lv.size());
+  // level 0's is kept in the caller's numbering; a coarse level reads what the level above wrote
+  const double* B = level == 0 ? srbm_nns(H->lv[0]->sagg, false) : srbm_nns(H->lv[(size_t)level - 1]->sagg, true);
+  ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  ZZZ_HIP(ctx, hipMemcpy(out, B, (size_t)(MG_RBM_NODE * H->lv[(size_t)level]->ndof) * sizeof(double), hipMemcpyDeviceToHost));
+  return ZZZ_OK;
 }
 }

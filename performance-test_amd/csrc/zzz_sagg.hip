@@ -24,50 +24,18 @@
 // summation index with a 64-bit (row, column) key, a STABLE radix sort (rocPRIM) brings equal keys together in that order,
 // and one thread sums each run front to back.  The sorted term lists are kept: a refresh is the sums alone, and gives the
 // bits of a fresh set-up.  Term positions are 32-bit: a level with more terms is refused (ZZZ_ERR_LIMIT), never wrapped.
-#include "zzz_cg.h"
-
-#include "zzz_prim.h"
+//
+// ZZZ_PC_SAGG_RBM (zzz_sagg_rbm.hip) differs in P's terms and P's value kernel alone: the level (SaggLevel) and the host steps
+// from P's terms on -- sagg_p_from_terms, sagg_products, sagg_product_values, the transfers -- are declared in zzz_sagg.h and
+// serve both.  Its dropped coarse dofs reach A_c as one more term each (SaggUnitTerms).
+#include "zzz_sagg.h"
 
 #include <cstdlib>
 #include <vector>
 
 namespace zzz
 {
-typedef unsigned long long u64;
-constexpr u64 SAGG_NOKEY = ~0ull;
 constexpr int64_t SAGG_MAX_TERMS = (int64_t)INT32_MAX - 16;
-
-struct SaggLevel
-{
-  int bs = 1;
-  int64_t nf = 0, nc = 0; // scalar dofs, fine and coarse
-  AggLevel* agg = nullptr;
-  // P: rows are the fine scalar dofs in the level's stored order; entry e sums the matrix entries psrc[t] >> 32 of its run
-  int64_t pnnz = 0;
-  DevBuf<rp_t> prow;
-  DevBuf<int32_t> pcol, pfrow, pseg;
-  DevBuf<u64> psrc;
-  DevBuf<double> pval, diag;
-  // R = P^T: entry t of coarse row J is P's entry rsrc[t], of fine row rfine[t]
-  DevBuf<rp_t> rrow;
-  DevBuf<int32_t> rfine, rsrc;
-  DevBuf<double> rval;
-  // T = A P: entry e sums a[tsrc >> 32] * P[tsrc & 0xffffffff] over its run;  A_c: entry E sums T[csrc >> 32] * P[csrc & ...]
-  int64_t tnnz = 0, cnnz = 0, tterms = 0, cterms = 0;
-  DevBuf<int32_t> tseg, cseg;
-  DevBuf<u64> tsrc, csrc;
-  DevBuf<double> tval;
-  ~SaggLevel() { agg_free(agg); }
-};
-
-#define SAGG_FOR(i, n) for (int64_t i = blockIdx.x * (int64_t)VB + threadIdx.x; i < (n); i += (int64_t)gridDim.x * VB)
-
-// scalar dof d in the caller's numbering (perm: internal -> caller block index; null: the same)
-template <int BS>
-__device__ inline u64 sagg_caller(const int32_t* __restrict__ perm, int32_t d)
-{
-  return perm ? (u64)perm[d / BS] * BS + (unsigned)(d % BS) : (u64)d;
-}
 
 // the scalar row of every matrix entry
 __global__ __launch_bounds__(VB) void k_sagg_rowidx(int64_t nrows, const rp_t* __restrict__ rowptr, int32_t* __restrict__ rowidx)
@@ -395,15 +363,6 @@ static int64_t sagg_term_limit()
   return v > 0 && v < SAGG_MAX_TERMS ? (int64_t)v : SAGG_MAX_TERMS;
 }
 
-// the work buffers of the three sorts of one level, freed together
-struct SaggWork
-{
-  DevBuf<u64> k0, k1, v0;
-  DevBuf<int32_t> head, pos, cnt;
-  DevBuf<int64_t> off;
-  DevBuf<unsigned char> tmp;
-};
-
 // n terms in W.k0 / W.v0 -> the keys sorted into W.k1, the values beside them into src, heads and positions of the runs of
 // equal keys (SAGG_NOKEY belongs to none); *nruns = how many
 static int sagg_sort_runs(zzz_ctx* ctx, SaggWork& W, int64_t n, DevBuf<u64>& src, int64_t* nruns)
@@ -424,69 +383,87 @@ static int sagg_sort_runs(zzz_ctx* ctx, SaggWork& W, int64_t n, DevBuf<u64>& src
   return ZZZ_OK;
 }
 
-// W.cnt[0 .. n] -> W.off (64-bit: the total may not fit 32), *total; refused above the limit
-static int sagg_term_offsets(zzz_ctx* ctx, SaggWork& W, int64_t n, int level, const char* what, int64_t* total)
+int sagg_term_offsets(zzz_ctx* ctx, const SaggLevel& S, SaggWork& W, int64_t n, int level, const char* what, int64_t extra,
+                      int64_t* total)
 {
   ZZZ_HIP(ctx, W.off.alloc((size_t)n + 1));
   if (int rc = with_scratch(ctx, W.tmp, scan_excl(W.cnt.p, W.off.p, (size_t)n + 1, ctx->stream)))
     return rc;
   ZZZ_HIP(ctx, dev_fetch(ctx, W.off.p + n, total));
   const int64_t limit = sagg_term_limit();
-  if (*total > limit)
-    return fail(ctx, ZZZ_ERR_LIMIT, "-pc_type sagg: level %d: %lld terms of %s, 32-bit term positions take %lld", level,
-                (long long)*total, what, (long long)limit);
-  ZZZ_HIP(ctx, W.k0.alloc((size_t)*total));
-  ZZZ_HIP(ctx, W.v0.alloc((size_t)*total));
+  if (*total + extra > limit)
+    return fail(ctx, ZZZ_ERR_LIMIT, "%s: level %d: %lld terms of %s, 32-bit term positions take %lld", S.tag, level,
+                (long long)(*total + extra), what, (long long)limit);
+  ZZZ_HIP(ctx, W.k0.alloc((size_t)(*total + extra)));
+  ZZZ_HIP(ctx, W.v0.alloc((size_t)(*total + extra)));
   return ZZZ_OK;
 }
 
-// The patterns of P, R, T and A_c from f's pattern, Dirichlet bytes and aggregates, and the sorted term lists behind their
-// values; c's rowptr / cols / vals are allocated here (values: sagg_values).  *max_row = the longest row of A_c.
 template <int BS>
-static int sagg_structure_bs(zzz_ctx* ctx, zzz_ctx* f, SaggLevel& S, zzz_ctx* c, int level, int* max_row)
+static int sagg_frame_bs(zzz_ctx* ctx, zzz_ctx* f, SaggFrame& Fr)
 {
   hipStream_t s = ctx->stream;
-  const int64_t N = f->nnz, nf = f->n_owned * BS, nc = agg_count(S.agg) * BS;
-  const int32_t* perm = f->dofmap.renumbered ? f->perm.p : nullptr;
-  const int32_t* agg = agg_map(S.agg);
-  const int g = grid_cap(N, VB, 1 << 16);
-  S.bs = BS;
-  S.nf = nf;
-  S.nc = nc;
-  SaggWork W;
-  DevBuf<int32_t> rowidx, erow, tcol, tfrow, stats;
-  DevBuf<u64> ordbuf, rtmp;
-  ZZZ_HIP(ctx, rowidx.alloc((size_t)N));
+  const int64_t N = f->nnz, nf = f->n_owned * BS;
+  SaggWork& W = Fr.W;
+  Fr.perm = f->dofmap.renumbered ? f->perm.p : nullptr;
+  ZZZ_HIP(ctx, Fr.rowidx.alloc((size_t)N));
   ZZZ_HIP(ctx, W.k0.alloc((size_t)N));
   ZZZ_HIP(ctx, W.v0.alloc((size_t)N));
   ZZZ_HIP(ctx, W.cnt.alloc((size_t)N + 1));
-  ZZZ_HIP(ctx, stats.alloc(2));
-  hipLaunchKernelGGL(k_sagg_rowidx, dim3(grid_cap(nf, VB, 1 << 16)), dim3(VB), 0, s, nf, f->rowptr.p, rowidx.p);
-  const u64* order = nullptr;
-  if (perm)
+  hipLaunchKernelGGL(k_sagg_rowidx, dim3(grid_cap(nf, VB, 1 << 16)), dim3(VB), 0, s, nf, f->rowptr.p, Fr.rowidx.p);
+  Fr.order = nullptr;
+  if (Fr.perm)
   {
     ZZZ_HIP(ctx, W.k1.alloc((size_t)N));
-    ZZZ_HIP(ctx, ordbuf.alloc((size_t)N));
-    hipLaunchKernelGGL(k_sagg_caller_keys<BS>, dim3(g), dim3(VB), 0, s, N, rowidx.p, f->cols.p, perm, W.k0.p, W.v0.p);
-    if (int rc = with_scratch(ctx, W.tmp, sort_pairs(W.k0.p, W.k1.p, W.v0.p, ordbuf.p, (size_t)N, 0, 64, s)))
+    ZZZ_HIP(ctx, Fr.ordbuf.alloc((size_t)N));
+    hipLaunchKernelGGL(k_sagg_caller_keys<BS>, dim3(grid_cap(N, VB, 1 << 16)), dim3(VB), 0, s, N, Fr.rowidx.p, f->cols.p, Fr.perm, W.k0.p, W.v0.p);
+    if (int rc = with_scratch(ctx, W.tmp, sort_pairs(W.k0.p, W.k1.p, W.v0.p, Fr.ordbuf.p, (size_t)N, 0, 64, s)))
       return rc;
-    order = ordbuf.p;
+    Fr.order = Fr.ordbuf.p;
   }
-  // ---- P -------------------------------------------------------------------------------------
-  hipLaunchKernelGGL(k_sagg_p_keys<BS>, dim3(g), dim3(VB), 0, s, N, order, rowidx.p, f->cols.p, f->bc.p, agg, W.k0.p, W.v0.p);
-  if (int rc = sagg_sort_runs(ctx, W, N, S.psrc, &S.pnnz))
+  return ZZZ_OK;
+}
+int sagg_frame(zzz_ctx* ctx, zzz_ctx* f, SaggFrame& Fr)
+{
+  return f->bs == 3 ? sagg_frame_bs<3>(ctx, f, Fr) : sagg_frame_bs<1>(ctx, f, Fr);
+}
+
+int sagg_p_from_terms(zzz_ctx* ctx, SaggLevel& S, SaggFrame& Fr, int64_t n, int level)
+{
+  hipStream_t s = ctx->stream;
+  SaggWork& W = Fr.W;
+  S.pterms = n;
+  if (int rc = sagg_sort_runs(ctx, W, n, S.psrc, &S.pnnz))
     return rc;
   if (S.pnnz <= 0)
-    return fail(ctx, ZZZ_ERR_ARG, "-pc_type sagg: level %d: the prolongator to %lld coarse dofs is empty", level, (long long)nc);
+    return fail(ctx, ZZZ_ERR_ARG, "%s: level %d: the prolongator to %lld coarse dofs is empty", S.tag, level, (long long)S.nc);
   const int gp = grid_cap(S.pnnz, VB, 1 << 16);
   ZZZ_HIP(ctx, S.pseg.alloc((size_t)S.pnnz + 1));
   ZZZ_HIP(ctx, S.pcol.alloc((size_t)S.pnnz));
   ZZZ_HIP(ctx, S.pfrow.alloc((size_t)S.pnnz));
-  ZZZ_HIP(ctx, S.pval.alloc((size_t)S.pnnz));
-  ZZZ_HIP(ctx, S.diag.alloc((size_t)nf));
-  ZZZ_HIP(ctx, S.prow.alloc((size_t)nf + 1));
-  hipLaunchKernelGGL(k_sagg_entries, dim3(g), dim3(VB), 0, s, N, S.pnnz, W.k1.p, W.head.p, W.pos.p, S.pseg.p, S.pcol.p, S.pfrow.p);
-  hipLaunchKernelGGL(k_sagg_offsets, dim3(gp), dim3(VB), 0, s, S.pfrow.p, S.pnnz, nf, S.prow.p);
+  ZZZ_HIP(ctx, S.pval.alloc((size_t)S.pnnz + 1));
+  ZZZ_HIP(ctx, S.diag.alloc((size_t)S.nf));
+  ZZZ_HIP(ctx, S.prow.alloc((size_t)S.nf + 1));
+  hipLaunchKernelGGL(k_sagg_entries, dim3(grid_cap(n, VB, 1 << 16)), dim3(VB), 0, s, n, S.pnnz, W.k1.p, W.head.p, W.pos.p, S.pseg.p, S.pcol.p,
+                     S.pfrow.p);
+  hipLaunchKernelGGL(k_sagg_offsets, dim3(gp), dim3(VB), 0, s, S.pfrow.p, S.pnnz, S.nf, S.prow.p);
+  return ZZZ_OK;
+}
+
+template <int BS>
+static int sagg_products_bs(zzz_ctx* ctx, zzz_ctx* f, SaggLevel& S, zzz_ctx* c, int level, SaggFrame& Fr, const SaggUnitTerms& unit,
+                            int* max_row)
+{
+  hipStream_t s = ctx->stream;
+  const int64_t N = f->nnz, nc = S.nc;
+  const int32_t* perm = Fr.perm;
+  const u64* order = Fr.order;
+  const int32_t* rowidx = Fr.rowidx.p;
+  const int g = grid_cap(N, VB, 1 << 16), gp = grid_cap(S.pnnz, VB, 1 << 16);
+  SaggWork& W = Fr.W;
+  DevBuf<int32_t> erow, tcol, tfrow, stats;
+  DevBuf<u64> rtmp;
+  ZZZ_HIP(ctx, stats.alloc(2));
   // ---- R: P's entries under (coarse column, fine row in the caller's numbering); the keys are distinct ----------
   ZZZ_HIP(ctx, S.rrow.alloc((size_t)nc + 1));
   ZZZ_HIP(ctx, S.rfine.alloc((size_t)S.pnnz));
@@ -494,37 +471,51 @@ static int sagg_structure_bs(zzz_ctx* ctx, zzz_ctx* f, SaggLevel& S, zzz_ctx* c,
   ZZZ_HIP(ctx, S.rval.alloc((size_t)S.pnnz));
   ZZZ_HIP(ctx, erow.alloc((size_t)S.pnnz));
   ZZZ_HIP(ctx, rtmp.alloc((size_t)S.pnnz));
+  ZZZ_HIP(ctx, W.k0.reserve((size_t)S.pnnz)); // (they hold P's terms, which are at least as many)
+  ZZZ_HIP(ctx, W.v0.reserve((size_t)S.pnnz));
+  ZZZ_HIP(ctx, W.k1.reserve((size_t)S.pnnz));
   hipLaunchKernelGGL(k_sagg_r_keys<BS>, dim3(gp), dim3(VB), 0, s, S.pnnz, S.pfrow.p, S.pcol.p, perm, W.k0.p, W.v0.p);
   if (int rc = with_scratch(ctx, W.tmp, sort_pairs(W.k0.p, W.k1.p, W.v0.p, rtmp.p, (size_t)S.pnnz, 0, 64, s)))
     return rc;
   hipLaunchKernelGGL(k_sagg_r_entries, dim3(gp), dim3(VB), 0, s, S.pnnz, W.k1.p, rtmp.p, S.pfrow.p, S.rsrc.p, S.rfine.p, erow.p);
   hipLaunchKernelGGL(k_sagg_offsets, dim3(gp), dim3(VB), 0, s, erow.p, S.pnnz, nc, S.rrow.p);
   // ---- T = A P -------------------------------------------------------------------------------
-  hipLaunchKernelGGL(k_sagg_t_count, dim3(g), dim3(VB), 0, s, N, order, rowidx.p, f->cols.p, f->bc.p, S.prow.p, W.cnt.p);
-  if (int rc = sagg_term_offsets(ctx, W, N, level, "A P", &S.tterms))
+  ZZZ_HIP(ctx, W.cnt.alloc((size_t)N + 1));
+  hipLaunchKernelGGL(k_sagg_t_count, dim3(g), dim3(VB), 0, s, N, order, rowidx, f->cols.p, f->bc.p, S.prow.p, W.cnt.p);
+  if (int rc = sagg_term_offsets(ctx, S, W, N, level, "A P", 0, &S.tterms))
     return rc;
-  hipLaunchKernelGGL(k_sagg_t_terms<BS>, dim3(g), dim3(VB), 0, s, N, order, rowidx.p, f->cols.p, f->bc.p, perm, S.prow.p, S.pcol.p,
+  hipLaunchKernelGGL(k_sagg_t_terms<BS>, dim3(g), dim3(VB), 0, s, N, order, rowidx, f->cols.p, f->bc.p, perm, S.prow.p, S.pcol.p,
                      W.off.p, W.k0.p, W.v0.p);
   if (int rc = sagg_sort_runs(ctx, W, S.tterms, S.tsrc, &S.tnnz))
     return rc;
   const int gtt = grid_cap(S.tterms, VB, 1 << 16), gt = grid_cap(S.tnnz, VB, 1 << 16);
   ZZZ_HIP(ctx, S.tseg.alloc((size_t)S.tnnz + 1));
-  ZZZ_HIP(ctx, S.tval.alloc((size_t)S.tnnz));
+  ZZZ_HIP(ctx, S.tval.alloc((size_t)S.tnnz + 1));
   ZZZ_HIP(ctx, tcol.alloc((size_t)S.tnnz));
   ZZZ_HIP(ctx, tfrow.alloc((size_t)S.tnnz));
   ZZZ_HIP(ctx, erow.alloc((size_t)S.tnnz));
   hipLaunchKernelGGL(k_sagg_entries, dim3(gtt), dim3(VB), 0, s, S.tterms, S.tnnz, W.k1.p, W.head.p, W.pos.p, S.tseg.p, tcol.p, erow.p);
-  hipLaunchKernelGGL(k_sagg_t_rows, dim3(gt), dim3(VB), 0, s, S.tnnz, S.tseg.p, S.tsrc.p, rowidx.p, tfrow.p);
+  hipLaunchKernelGGL(k_sagg_t_rows, dim3(gt), dim3(VB), 0, s, S.tnnz, S.tseg.p, S.tsrc.p, rowidx, tfrow.p);
   // ---- A_c = P^T T -----------------------------------------------------------------------------
   ZZZ_HIP(ctx, W.cnt.alloc((size_t)S.tnnz + 1));
   hipLaunchKernelGGL(k_sagg_c_count, dim3(gt), dim3(VB), 0, s, S.tnnz, tfrow.p, S.prow.p, W.cnt.p);
-  if (int rc = sagg_term_offsets(ctx, W, S.tnnz, level, "P^T (A P)", &S.cterms))
+  if (int rc = sagg_term_offsets(ctx, S, W, S.tnnz, level, "P^T (A P)", unit.n, &S.cterms))
     return rc;
   hipLaunchKernelGGL(k_sagg_c_terms, dim3(gt), dim3(VB), 0, s, S.tnnz, tfrow.p, tcol.p, S.prow.p, S.pcol.p, W.off.p, W.k0.p, W.v0.p);
+  if (unit.n > 0)
+  {
+    // the unit diagonal of a dropped coarse dof: one term of its own, the product of the two slots behind T's and P's values
+    const double one = 1.0;
+    ZZZ_HIP(ctx, hipMemcpyAsync(S.tval.p + S.tnnz, &one, sizeof(double), hipMemcpyHostToDevice, s));
+    ZZZ_HIP(ctx, hipMemcpyAsync(S.pval.p + S.pnnz, &one, sizeof(double), hipMemcpyHostToDevice, s));
+    ZZZ_HIP(ctx, hipStreamSynchronize(s)); // (`one` is a local)
+    unit.write(s, unit.n, unit.dofs, ((u64)S.tnnz << 32) | (u64)S.pnnz, W.k0.p + S.cterms, W.v0.p + S.cterms);
+    S.cterms += unit.n;
+  }
   if (int rc = sagg_sort_runs(ctx, W, S.cterms, S.csrc, &S.cnnz))
     return rc;
   if (S.cnnz <= 0)
-    return fail(ctx, ZZZ_ERR_ARG, "-pc_type sagg: level %d: the coarse matrix of %lld dofs is empty", level, (long long)nc);
+    return fail(ctx, ZZZ_ERR_ARG, "%s: level %d: the coarse matrix of %lld dofs is empty", S.tag, level, (long long)nc);
   const int gc = grid_cap(S.cnnz, VB, 1 << 16);
   ZZZ_HIP(ctx, S.cseg.alloc((size_t)S.cnnz + 1));
   ZZZ_HIP(ctx, erow.alloc((size_t)S.cnnz));
@@ -542,9 +533,52 @@ static int sagg_structure_bs(zzz_ctx* ctx, zzz_ctx* f, SaggLevel& S, zzz_ctx* c,
   ZZZ_HIP(ctx, dev_fetch(ctx, stats.p, hs, 2)); // (waits for the stream: the work buffers go out of scope below)
   ZZZ_HIP(ctx, hipGetLastError());
   if (hs[1] > 0)
-    return fail(ctx, ZZZ_ERR_ARG, "-pc_type sagg: level %d: %d coarse dofs have no unconstrained member (aggregates of partly "
-                                  "constrained block dofs): the coarse matrix would be singular", level, hs[1]);
+    return fail(ctx, ZZZ_ERR_ARG, "%s: level %d: %d coarse dofs have no unconstrained member (aggregates of partly "
+                                  "constrained block dofs): the coarse matrix would be singular", S.tag, level, hs[1]);
   *max_row = hs[0];
+  return ZZZ_OK;
+}
+int sagg_products(zzz_ctx* ctx, zzz_ctx* f, SaggLevel& S, zzz_ctx* c, int level, SaggFrame& Fr, const SaggUnitTerms& unit, int* max_row)
+{
+  return f->bs == 3 ? sagg_products_bs<3>(ctx, f, S, c, level, Fr, unit, max_row)
+                    : sagg_products_bs<1>(ctx, f, S, c, level, Fr, unit, max_row);
+}
+
+// The patterns of P, R, T and A_c from f's pattern, Dirichlet bytes and aggregates, and the sorted term lists behind their
+// values; c's rowptr / cols / vals are allocated here (values: sagg_values).  *max_row = the longest row of A_c.
+template <int BS>
+static int sagg_structure_bs(zzz_ctx* ctx, zzz_ctx* f, SaggLevel& S, zzz_ctx* c, int level, int* max_row)
+{
+  const int64_t N = f->nnz;
+  S.bs = BS;
+  S.nf = f->n_owned * BS;
+  S.nc = agg_count(S.agg) * BS;
+  SaggFrame Fr;
+  if (int rc = sagg_frame(ctx, f, Fr))
+    return rc;
+  hipLaunchKernelGGL(k_sagg_p_keys<BS>, dim3(grid_cap(N, VB, 1 << 16)), dim3(VB), 0, ctx->stream, N, Fr.order, Fr.rowidx.p, f->cols.p,
+                     f->bc.p, agg_map(S.agg), Fr.W.k0.p, Fr.W.v0.p);
+  if (int rc = sagg_p_from_terms(ctx, S, Fr, N, level))
+    return rc;
+  return sagg_products(ctx, f, S, c, level, Fr, SaggUnitTerms(), max_row);
+}
+
+int sagg_diagonal(zzz_ctx* ctx, zzz_ctx* f, SaggLevel& S)
+{
+  hipLaunchKernelGGL(k_sagg_diag, dim3(grid_cap(S.nf, VB, 1 << 16)), dim3(VB), 0, ctx->stream, S.nf, f->rowptr.p, f->cols.p, f->vals.p,
+                     S.diag.p);
+  return ZZZ_OK;
+}
+
+int sagg_product_values(zzz_ctx* ctx, zzz_ctx* f, SaggLevel& S, zzz_ctx* c)
+{
+  hipStream_t s = ctx->stream;
+  hipLaunchKernelGGL(k_sagg_gather, dim3(grid_cap(S.pnnz, VB, 1 << 16)), dim3(VB), 0, s, S.pnnz, S.rsrc.p, S.pval.p, S.rval.p);
+  hipLaunchKernelGGL(k_sagg_sum_products, dim3(grid_cap(S.tnnz, VB, 1 << 16)), dim3(VB), 0, s, S.tnnz, S.tseg.p, S.tsrc.p, f->vals.p,
+                     S.pval.p, S.tval.p);
+  hipLaunchKernelGGL(k_sagg_sum_products, dim3(grid_cap(S.cnnz, VB, 1 << 16)), dim3(VB), 0, s, S.cnnz, S.cseg.p, S.csrc.p, S.tval.p,
+                     S.pval.p, c->vals.p);
+  ZZZ_HIP(ctx, hipGetLastError());
   return ZZZ_OK;
 }
 
@@ -554,20 +588,14 @@ static int sagg_values(zzz_ctx* ctx, zzz_ctx* f, SaggLevel& S, double omega, zzz
   hipStream_t s = ctx->stream;
   const int gp = grid_cap(S.pnnz, VB, 1 << 16);
   const int32_t* agg = agg_map(S.agg);
-  hipLaunchKernelGGL(k_sagg_diag, dim3(grid_cap(S.nf, VB, 1 << 16)), dim3(VB), 0, s, S.nf, f->rowptr.p, f->cols.p, f->vals.p, S.diag.p);
+  sagg_diagonal(ctx, f, S);
   if (S.bs == 3)
     hipLaunchKernelGGL(k_sagg_p_values<3>, dim3(gp), dim3(VB), 0, s, S.pnnz, S.pseg.p, S.psrc.p, f->vals.p, S.pfrow.p, S.pcol.p, agg,
                        S.diag.p, omega, S.pval.p);
   else
     hipLaunchKernelGGL(k_sagg_p_values<1>, dim3(gp), dim3(VB), 0, s, S.pnnz, S.pseg.p, S.psrc.p, f->vals.p, S.pfrow.p, S.pcol.p, agg,
                        S.diag.p, omega, S.pval.p);
-  hipLaunchKernelGGL(k_sagg_gather, dim3(gp), dim3(VB), 0, s, S.pnnz, S.rsrc.p, S.pval.p, S.rval.p);
-  hipLaunchKernelGGL(k_sagg_sum_products, dim3(grid_cap(S.tnnz, VB, 1 << 16)), dim3(VB), 0, s, S.tnnz, S.tseg.p, S.tsrc.p, f->vals.p,
-                     S.pval.p, S.tval.p);
-  hipLaunchKernelGGL(k_sagg_sum_products, dim3(grid_cap(S.cnnz, VB, 1 << 16)), dim3(VB), 0, s, S.cnnz, S.cseg.p, S.csrc.p, S.tval.p,
-                     S.pval.p, c->vals.p);
-  ZZZ_HIP(ctx, hipGetLastError());
-  return ZZZ_OK;
+  return sagg_product_values(ctx, f, S, c);
 }
 
 int sagg_galerkin(zzz_ctx* ctx, zzz_ctx* f, SaggLevel* S, double omega, zzz_ctx* c, int level)

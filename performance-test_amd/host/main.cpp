@@ -169,7 +169,7 @@ void usage()
                "                                  -ksp_max_it, -ksp_norm_type)\n"
                "  --bc_value arg (=0)             value of u0 at every Dirichlet dof (the reference's u0 is 0); non-zero: the\n"
                "                                  vector assembly lifts it (apply_lifting, bc->set)\n"
-               "PETSc-style solver options honoured: -ksp_type {cg,pipecg} -pc_type {jacobi,none,chebyshev_jacobi,mg,pmg,agg,sagg} -ksp_rtol -ksp_atol\n"
+               "PETSc-style solver options honoured: -ksp_type {cg,pipecg} -pc_type {jacobi,none,chebyshev_jacobi,mg,pmg,agg,sagg,sagg_rbm} -ksp_rtol -ksp_atol\n"
                "  -ksp_divtol -pc_chebyshev_jacobi_degree (=3) -pc_chebyshev_jacobi_ratio (=60) -pc_chebyshev_jacobi_esteig (=10)\n"
                "  -ksp_max_it -ksp_norm_type {preconditioned,unpreconditioned,natural} -ksp_view -ksp_monitor\n"
                "  -ksp_cg_single_reduction -ksp_converged_reason -ksp_error_if_not_converged\n"
@@ -183,6 +183,9 @@ void usage()
                "  -mg_levels_* options\n"
                "  -pc_type sagg: smoothed aggregation, -pc_type agg with one prolongator-smoothing step (omega = 4 / (3 hi) of the\n"
                "  level's smoother bound); the same scope and the same options\n"
+               "  -pc_type sagg_rbm: -pc_type sagg whose prolongator carries the six rigid-body modes of `ZZZ Create near-nullspace`\n"
+               "  through every level (coarse nodes of 6 dofs); --problem_type elasticity only (for scalar problems use -pc_type\n"
+               "  sagg), otherwise -pc_type sagg's scope and options\n"
                "  -log_view -options_left\n"
             << std::endl;
 }
@@ -557,8 +560,8 @@ void run_rank(Shared& S, std::barrier<>& bar, int rank)
     so.variant = o.ksp_type == "pipecg" ? ZZZ_CG_PIPE : ZZZ_CG_PETSC;
     so.pc = o.pc_type == "none" ? ZZZ_PC_NONE : o.pc_type == "chebyshev_jacobi" ? ZZZ_PC_CHEBYSHEV_JACOBI
             : o.pc_type == "mg" ? ZZZ_PC_MG : o.pc_type == "pmg" ? ZZZ_PC_PMG : o.pc_type == "agg" ? ZZZ_PC_AGG
-            : o.pc_type == "sagg" ? ZZZ_PC_SAGG : ZZZ_PC_JACOBI;
-    const bool multigrid = o.pc_type == "mg" || o.pc_type == "pmg" || o.pc_type == "agg" || o.pc_type == "sagg";
+            : o.pc_type == "sagg" ? ZZZ_PC_SAGG : o.pc_type == "sagg_rbm" ? ZZZ_PC_SAGG_RBM : ZZZ_PC_JACOBI;
+    const bool multigrid = o.pc_type == "mg" || o.pc_type == "pmg" || o.pc_type == "agg" || o.pc_type == "sagg" || o.pc_type == "sagg_rbm";
     so.pc_degree = multigrid ? o.mg_degree : o.pc_degree;
     so.pc_ratio = multigrid ? o.mg_ratio : o.pc_ratio;
     so.pc_esteig_its = o.pc_esteig;
@@ -615,7 +618,7 @@ void run_rank(Shared& S, std::barrier<>& bar, int rank)
         S.tcg[rank] = tcg.stop();
         S.rnorm[rank] = rn[0];
         S.rnorm0[rank] = rn[1];
-        if (root && (so.pc == ZZZ_PC_MG || so.pc == ZZZ_PC_PMG || so.pc == ZZZ_PC_AGG || so.pc == ZZZ_PC_SAGG)) // PCView: the hierarchy zzz_cg_solve set up above (PCSetUp runs inside ZZZ Solve, as in PETSc)
+        if (root && (so.pc == ZZZ_PC_MG || so.pc == ZZZ_PC_PMG || so.pc == ZZZ_PC_AGG || so.pc == ZZZ_PC_SAGG || so.pc == ZZZ_PC_SAGG_RBM)) // PCView: the hierarchy zzz_cg_solve set up above (PCSetUp runs inside ZZZ Solve, as in PETSc)
         {
           std::array<double, 8> v{};
           ZCK(ctx, zzz_mg_info(ctx, -1, v.data()));
@@ -625,7 +628,7 @@ void run_rank(Shared& S, std::barrier<>& bar, int rank)
             ZCK(ctx, zzz_mg_info(ctx, l, v.data()));
             S.mg_view.push_back(v);
           }
-          for (int l = 0; so.pc == ZZZ_PC_SAGG && l + 1 < (int)S.mg_view[0][0]; ++l)
+          for (int l = 0; (so.pc == ZZZ_PC_SAGG || so.pc == ZZZ_PC_SAGG_RBM) && l + 1 < (int)S.mg_view[0][0]; ++l)
           {
             int64_t pnnz = 0;
             ZCK(ctx, zzz_mg_level_p(ctx, l, nullptr, nullptr, nullptr, &pnnz));
@@ -770,6 +773,7 @@ void solve(int argc, char** argv)
     // what the matrix-free operator declines at block size 3 as at 1 (include/zzz_abi.h), said here before any GPU work
     const char* why = o.op == "matfree" ? "not with --operator matfree (the operator is already matrix-free)"
                       : o.pc_type == "chebyshev_jacobi" || o.pc_type == "mg" || o.pc_type == "pmg" || o.pc_type == "agg" || o.pc_type == "sagg"
+                              || o.pc_type == "sagg_rbm"
                           ? "-pc_type jacobi or none only (Chebyshev-Jacobi and the multigrid preconditioners need the assembled operator)"
                       : o.ksp_type == "pipecg"    ? "-ksp_type pipecg needs the assembled operator (--cg_solver ksp runs the classical KSPCG)"
                       : o.ksp_cg_single_reduction ? "-ksp_cg_single_reduction needs the assembled operator"
@@ -796,7 +800,7 @@ void solve(int argc, char** argv)
   if (o.ksp_type != "cg" && o.ksp_type != "pipecg")
     throw std::runtime_error("-ksp_type " + o.ksp_type + ": only cg and pipecg are built");
   if (o.pc_type != "jacobi" && o.pc_type != "none" && o.pc_type != "chebyshev_jacobi" && o.pc_type != "mg" && o.pc_type != "pmg"
-      && o.pc_type != "agg" && o.pc_type != "sagg")
+      && o.pc_type != "agg" && o.pc_type != "sagg" && o.pc_type != "sagg_rbm")
     throw std::runtime_error("-pc_type " + o.pc_type +
                              ": only jacobi, none, chebyshev_jacobi, mg and pmg are built (hypre/gamg are out of scope: the "
                              "multigrid preconditioner here is the geometric one, -pc_type mg, or -pc_type pmg for --order 2 / 3)");
@@ -837,10 +841,12 @@ void solve(int argc, char** argv)
     if (why)
       throw std::runtime_error("-pc_type " + o.pc_type + ": " + why);
   }
-  if (o.pc_type == "agg" || o.pc_type == "sagg")
+  if (o.pc_type == "agg" || o.pc_type == "sagg" || o.pc_type == "sagg_rbm")
   {
-    // what ZZZ_PC_AGG and ZZZ_PC_SAGG decline (include/zzz_abi.h), said here before any GPU work
+    // what ZZZ_PC_AGG, ZZZ_PC_SAGG and ZZZ_PC_SAGG_RBM decline (include/zzz_abi.h), said here before any GPU work
     const char* why = o.ngpus != 1                                       ? "--ngpus 1 only (multi-rank multigrid is not built)"
+                      : o.pc_type == "sagg_rbm" && o.problem_type != "elasticity"
+                          ? "--problem_type elasticity only (the rigid-body modes belong to block size 3): for scalar problems use -pc_type sagg"
                       : o.problem_type != "poisson" && o.problem_type != "elasticity" ? "poisson or elasticity (the assembled matrix is what it coarsens)"
                       : o.op == "matfree"                                ? "--operator assembled only"
                       : o.ksp_type != "cg"                               ? "-ksp_type cg only"
@@ -963,9 +969,13 @@ void solve(int argc, char** argv)
     for (size_t l = 1; l < S.mg_view.size(); ++l)
     {
       const auto& v = S.mg_view[l];
-      if (o.pc_type == "agg" || o.pc_type == "sagg")
+      if (o.pc_type == "agg" || o.pc_type == "sagg" || o.pc_type == "sagg_rbm")
+      {
         std::cout << "  level " << l - 1 << ": " << (l == 1 ? "the assembled matrix" : "aggregates of the level above") << ", dofs "
                   << (long long)v[3] << ", nonzeros " << (long long)v[4];
+        if (o.pc_type == "sagg_rbm" && l > 1)
+          std::cout << ", dropped dofs " << (long long)v[1];
+      }
       else
         std::cout << "  level " << l - 1 << ": cells " << (long long)v[0] << "x" << (long long)v[1] << "x" << (long long)v[2] << ", order "
                   << (l - 1 < (size_t)m[7] ? o.order : 1) << ", dofs " << (long long)v[3] << ", nonzeros " << (long long)v[4];

@@ -17,7 +17,7 @@ ROOT = os.path.dirname(PKG)
 FORM_POISSON, FORM_ELASTICITY = 0, 1
 COEFF_F, COEFF_G = 0, 1
 VEC_B, VEC_U = 0, 1
-PC_NONE, PC_JACOBI, PC_CHEBYSHEV_JACOBI, PC_MG, PC_PMG, PC_AGG, PC_SAGG = 0, 1, 2, 3, 4, 5, 6
+PC_NONE, PC_JACOBI, PC_CHEBYSHEV_JACOBI, PC_MG, PC_PMG, PC_AGG, PC_SAGG, PC_SAGG_RBM = 0, 1, 2, 3, 4, 5, 6, 7
 NORM_PRECONDITIONED, NORM_UNPRECONDITIONED, NORM_NATURAL = 0, 1, 2
 CG_PETSC, CG_CGH, CG_PIPE = 0, 1, 2
 OP_CSR, OP_MATFREE = 0, 1
@@ -31,7 +31,7 @@ ABI_SYMBOLS = [
     "zzz_vec_download", "zzz_vec_upload", "zzz_vec_norm", "zzz_spmv", "zzz_spmv_time", "zzz_spmv_values_info", "zzz_spmv_values_info2", "zzz_abi_version", "zzz_action", "zzz_matfree_setup", "zzz_matfree_info", "zzz_matfree_diagonal", "zzz_matfree_assemble_vector", "zzz_action_time", "zzz_near_nullspace_build", "zzz_near_nullspace_download", "zzz_cg_solve", "zzz_cg_history",
     "zzz_profile_get", "zzz_cg_info", "zzz_internal_order_download", "zzz_global_ids_upload", "zzz_global_ids_download", "zzz_ghost_layer_build", "zzz_local_sizes", "zzz_spmv_info", "zzz_comm_load", "zzz_comm_library_path", "zzz_comm_info", "zzz_comm_unique_id", "zzz_comm_init", "zzz_halo_upload", "zzz_local_group_create",
     "zzz_local_group_destroy", "zzz_local_group_abort", "zzz_comm_init_local", "zzz_comm_init_peer_only", "zzz_comm_p2p_export", "zzz_comm_p2p_attach", "zzz_comm_p2p_disable", "zzz_comm_p2p_enable", "zzz_comm_p2p_halo",
-    "zzz_mg_setup", "zzz_mg_info", "zzz_mg_apply", "zzz_mg_transfer", "zzz_mg_level_csr", "zzz_mg_level_p",
+    "zzz_mg_setup", "zzz_mg_info", "zzz_mg_apply", "zzz_mg_transfer", "zzz_mg_level_csr", "zzz_mg_level_p", "zzz_mg_level_nns",
     "zzz_action_f32", "zzz_action_time_f32", "zzz_matfree_info_f32", "zzz_cg_solve_f32",
 ]
 HOST_SYMBOLS = [
@@ -136,6 +136,8 @@ def hip():
             L.zzz_mg_level_csr.argtypes = [C.c_void_p, C.c_int, _i64p, _i32p, _f64p]
         if hasattr(L, "zzz_mg_level_p"):  # (... or from before ZZZ_PC_SAGG)
             L.zzz_mg_level_p.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+        if hasattr(L, "zzz_mg_level_nns"):  # (... or from before ZZZ_PC_SAGG_RBM)
+            L.zzz_mg_level_nns.argtypes = [C.c_void_p, C.c_int, _f64p]
         L.zzz_profile_get.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
         L.zzz_spmv_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
         L.zzz_spmv_values_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
@@ -627,7 +629,8 @@ class Context:
         return it.value, rn[0], rn[1]
 
     def mg_setup(self, pc_degree=0, pc_ratio=0.0, pc_esteig_its=0, pc_mg_levels=0, pc_mg_coarse_eq_limit=0, pc=PC_MG):
-        """PCSetUp of ZZZ_PC_MG, ZZZ_PC_PMG, ZZZ_PC_AGG or ZZZ_PC_SAGG (optional: the first solve with that pc does it)"""
+        """PCSetUp of ZZZ_PC_MG, ZZZ_PC_PMG, ZZZ_PC_AGG, ZZZ_PC_SAGG or ZZZ_PC_SAGG_RBM (optional: the first solve with that pc does
+        it)"""
         o = SolverOpts(CG_PETSC, pc, NORM_PRECONDITIONED, OP_CSR, 10000, 0, 0, 0, 1e-8, 1e-50, 0.0, pc_degree, pc_esteig_its,
                        pc_ratio, pc_mg_levels, pc_mg_coarse_eq_limit)
         self._ck(self.L.zzz_mg_setup(self.h, C.byref(o)))
@@ -635,14 +638,15 @@ class Context:
     def mg_info(self, level=-1):
         """level < 0: dict(levels, coarse_dofs, setups, products_per_cycle, coarse_bytes, cycle_ms, setup_ms, high_order_levels);
         else that level's
-        dict(cells=(nx, ny, nz), dofs, nnz, hi, lo, degree)"""
+        dict(cells=(nx, ny, nz), dofs, nnz, hi, lo, degree, dropped); dropped: of a ZZZ_PC_SAGG_RBM hierarchy, how many of the
+        level's dofs are dropped coarse dofs (reported in ny's slot where there is no cube: nx = nz = 0)"""
         out = np.zeros(8)
         self._ck(self.L.zzz_mg_info(self.h, level, out))
         if level < 0:
             return dict(levels=int(out[0]), coarse_dofs=int(out[1]), setups=int(out[2]), products_per_cycle=int(out[3]),
                         coarse_bytes=int(out[4]), cycle_ms=float(out[5]), setup_ms=float(out[6]), high_order_levels=int(out[7]))
         return dict(cells=(int(out[0]), int(out[1]), int(out[2])), dofs=int(out[3]), nnz=int(out[4]), hi=float(out[5]),
-                    lo=float(out[6]), degree=int(out[7]))
+                    lo=float(out[6]), degree=int(out[7]), dropped=int(out[1]) if out[0] == 0 and out[2] == 0 else 0)
 
     def mg_apply(self, r):
         """z = M r: one V-cycle (zzz_mg_apply)"""
@@ -675,6 +679,13 @@ class Context:
         rp, cl, v = np.zeros(self.mg_info(level)["dofs"] + 1, np.int64), np.zeros(nnz.value, np.int32), np.zeros(nnz.value)
         self._ck(self.L.zzz_mg_level_p(self.h, level, rp.ctypes.data, cl.ctypes.data, v.ctypes.data, None))
         return rp, cl, v
+
+    def mg_level_nns(self, level):
+        """B [6][dofs of the level]: the near-nullspace that level's orthogonalisation read in a ZZZ_PC_SAGG_RBM hierarchy, level 0
+        in the caller's numbering with constrained entries 0 (zzz_mg_level_nns)"""
+        B = np.zeros((6, self.mg_info(level)["dofs"]))
+        self._ck(self.L.zzz_mg_level_nns(self.h, level, B))
+        return B
 
     def cg_history(self, n):
         out = np.zeros(n)
