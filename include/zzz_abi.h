@@ -629,13 +629,39 @@ int zzz_mg_level_p(zzz_ctx* ctx, int level, int64_t* rowptr, int32_t* cols, doub
  * dofs 0.  ZZZ_ERR_ARG for another kind of hierarchy.  zzz_mg_info(level) of such a hierarchy reports, in ny's slot (nx = nz = 0:
  * there is no cube), how many of that level's dofs are dropped coarse dofs.  (A new entry point: ZZZ_ABI_VERSION is unchanged.) */
 int zzz_mg_level_nns(zzz_ctx* ctx, int level, double* out);
+/* How the next ZZZ_PC_SAGG / ZZZ_PC_SAGG_RBM hierarchy of this context forms P, T = A P and A_c = P^T T (csrc/zzz_sagg_rows.hip).
+ * ZZZ_MG_PRODUCTS_LISTS (the default): every term written out with a 64-bit key, sorted, the sorted lists kept for the refresh;
+ * a level with more terms than 32-bit positions take is declined with ZZZ_ERR_LIMIT.  ZZZ_MG_PRODUCTS_ROWS: row by row -- the
+ * patterns from sorted and uniqued (row, column) candidates of a bounded chunk of rows at a time, the values with one
+ * accumulator per entry and the summation index ascending -- the SAME sums in the same order, so the same P, R, T, A_c, coarse
+ * near-nullspace and drops bit for bit, with no term list kept and no limit on the terms; a level whose A, T or A_c has 2^31
+ * or more entries is declined with ZZZ_ERR_LIMIT.  (ZZZ_SAGG_ROWS_BUDGET lowers the candidates per chunk and ZZZ_SAGG_ROWS_LDS the
+ * row length, 1024, up to which a row's accumulators sit in LDS: both for tests; ZZZ_SAGG_MAX_TERMS is not read in this mode.)  The mode belongs to the context and survives every upload; it is part of what a smoothed
+ * hierarchy was built from: the next set-up or solve after a change rebuilds, a hierarchy built in the current mode is kept
+ * and refreshed.  ZZZ_PC_MG, ZZZ_PC_PMG and ZZZ_PC_AGG never read it.  Any other mode: ZZZ_ERR_ARG, nothing changed.
+ * (A new entry point: ZZZ_ABI_VERSION is unchanged.) */
+enum zzz_mg_products_mode
+{
+  ZZZ_MG_PRODUCTS_LISTS = 0,
+  ZZZ_MG_PRODUCTS_ROWS = 1
+};
+int zzz_mg_products(zzz_ctx* ctx, int mode);
+/* The products of the standing ZZZ_PC_SAGG / ZZZ_PC_SAGG_RBM hierarchy: info[0] = the mode it was built in; info[1] = device
+ * bytes its levels keep for P, R, T and the term lists (lists) or the level-0 entry permutation (rows), the coarse matrices
+ * excluded; then, of the last build in the rows mode (0 in the lists mode): info[2] = chunks of the symbolic passes, summed
+ * over levels and products; info[3] = the most candidates one row had; info[4] = the budget, candidates per chunk;
+ * info[5] = rows that formed a chunk alone because they exceeded it; info[6] = the peak of the transient device bytes of the
+ * products' set-up; info[7] = 0.  ZZZ_ERR_ARG without a hierarchy or for another kind.  (A new entry point: ZZZ_ABI_VERSION
+ * is unchanged.) */
+int zzz_mg_products_info(zzz_ctx* ctx, int64_t info[8]);
 
 /* Version of this header's ABI: bumped whenever an existing entry point changes what it reads or writes (7: zzz_cg_solve
  * reads the two pc_mg_* fields behind pc_ratio).  ZZZ_PC_PMG did not bump it: a new enumerator changes no struct, no
  * entry point and nothing that a caller built against the earlier header passes or receives -- such a caller never
  * sends the value 4, and a library without it answers that value with ZZZ_ERR_ARG.  Nor did zzz_bc_values_upload: a new
  * entry point, no struct and no existing entry changed.  ZZZ_PC_AGG (5) and zzz_mg_level_csr: the same two arguments;
- * ZZZ_PC_SAGG (6) and zzz_mg_level_p: the same two again; ZZZ_PC_SAGG_RBM (7) and zzz_mg_level_nns: and again. */
+ * ZZZ_PC_SAGG (6) and zzz_mg_level_p: the same two again; ZZZ_PC_SAGG_RBM (7) and zzz_mg_level_nns: and again.  zzz_mg_products and zzz_mg_products_info: new
+ * entry points, version unchanged. */
 #define ZZZ_ABI_VERSION 7
 int zzz_abi_version(void);
 

@@ -293,6 +293,7 @@ int zzz_ctx_create(int device, zzz_ctx** out)
       zzz::preload_agg();
       zzz::preload_sagg();
       zzz::preload_sagg_rbm();
+      zzz::preload_sagg_rows();
       zzz::preload_pmg();
       zzz::preload_nullspace();
       (void)hipGetLastError();

@@ -426,6 +426,7 @@ struct zzz_ctx
   int64_t cube_n[3] = {0, 0, 0};
   uint64_t feed_version = 0;
   zzz::MgHier* mg = nullptr;
+  int mg_products = ZZZ_MG_PRODUCTS_LISTS; // zzz_mg_products: how ZZZ_PC_SAGG / ZZZ_PC_SAGG_RBM form their products; survives every upload
   bool stream_borrowed = false; // a coarse level of another context's hierarchy: `stream` is that context's
 
   int64_t nloc() const { return (n_owned + n_ghost) * bs; }
@@ -470,6 +471,7 @@ void preload_pattern();
 void preload_renumber();
 void preload_sagg();
 void preload_sagg_rbm();
+void preload_sagg_rows();
 void preload_sellp();
 void preload_sellp_dict();
 void preload_sellp_pack();
@@ -659,6 +661,9 @@ int srbm_galerkin(zzz_ctx* ctx, zzz_ctx* f, SaggLevel* S, const SaggLevel* above
 int srbm_refresh(zzz_ctx* ctx, zzz_ctx* f, SaggLevel* S, double omega, zzz_ctx* c);
 int64_t srbm_dropped(const SaggLevel* S); // coarse dofs below S that carry no column of P
 const double* srbm_nns(const SaggLevel* S, bool coarse);
+// what a level's products keep (zzz_sagg.hip; the rows mode itself: zzz_sagg_rows.hip).  out[0] = 1 when the level was built row by row, out[1] =
+// device bytes it keeps for P, R, T and the term lists or the entry permutation, out[2..6] as zzz_mg_products_info's, of this level
+void sagg_products_info(const SaggLevel* S, int64_t out[8]);
 
 // comm
 int comm_allreduce_sum(zzz_ctx* ctx, double* dev, int n);

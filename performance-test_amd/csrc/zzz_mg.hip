@@ -258,10 +258,11 @@ struct MgStructKey
   uint64_t feed_version = 0, pattern_version = 0, bc_version = 0; // (pattern and Dirichlet set: the aggregates depend on both)
   int opt_levels = 0, limit = 0;
   MgKind kind = MgKind::GEOM; // of level 0
+  int products = 0;           // SAGG, SAGG_RBM: zzz_mg_products' mode; else 0
   bool operator==(const MgStructKey& k) const
   {
     return feed_version == k.feed_version && pattern_version == k.pattern_version && bc_version == k.bc_version
-           && opt_levels == k.opt_levels && limit == k.limit && kind == k.kind;
+           && opt_levels == k.opt_levels && limit == k.limit && kind == k.kind && products == k.products;
   }
 };
 struct MgValuesKey
@@ -661,7 +662,8 @@ int mg_setup(zzz_ctx* ctx, const zzz_solver_opts* o)
   const bool agg = mg_algebraic(kind);
   const int limit = o->pc_mg_coarse_eq_limit > 0 ? o->pc_mg_coarse_eq_limit : 1000;
   const int max_levels = o->pc_mg_levels > 0 ? std::min<int>(o->pc_mg_levels, MG_MAX_LEVELS) : MG_MAX_LEVELS;
-  const MgStructKey skey{ctx->feed_version, agg ? ctx->pattern_version : 0, agg ? ctx->bc_version : 0, o->pc_mg_levels, limit, kind};
+  const MgStructKey skey{ctx->feed_version, agg ? ctx->pattern_version : 0, agg ? ctx->bc_version : 0, o->pc_mg_levels, limit, kind,
+                         mg_smoothed(kind) ? ctx->mg_products : 0};
   const MgValuesKey vkey{ctx->mat_version, o->pc_degree > 0 ? o->pc_degree : 2, o->pc_ratio > 1.0 ? o->pc_ratio : 10.0,
                          o->pc_esteig_its == 0 ? 10 : o->pc_esteig_its};
   // the options of the levels' spectrum estimates and smoothers
@@ -923,6 +925,46 @@ int zzz_mg_info(zzz_ctx* ctx, int level, double out[8])
   out[5] = smooths ? L.cheb.hi : 0.0;
   out[6] = smooths ? L.cheb.lo : 0.0;
   out[7] = smooths ? (double)L.cheb.degree : 0.0;
+  return ZZZ_OK;
+}
+
+int zzz_mg_products(zzz_ctx* ctx, int mode)
+{
+  if (!ctx)
+    return fail(nullptr, ZZZ_ERR_ARG, "NULL context");
+  if (mode != ZZZ_MG_PRODUCTS_LISTS && mode != ZZZ_MG_PRODUCTS_ROWS)
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_mg_products: mode %d (ZZZ_MG_PRODUCTS_LISTS = 0, ZZZ_MG_PRODUCTS_ROWS = 1)", mode);
+  ctx->mg_products = mode; // (part of MgStructKey: the next set-up of a smoothed hierarchy compares it)
+  return ZZZ_OK;
+}
+
+int zzz_mg_products_info(zzz_ctx* ctx, int64_t info[8])
+{
+  if (!ctx)
+    return fail(nullptr, ZZZ_ERR_ARG, "NULL context");
+  if (!info)
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_mg_products_info: NULL output");
+  for (int i = 0; i < 8; ++i)
+    info[i] = 0;
+  const MgHier* H = ctx->mg;
+  if (!H || !H->ready)
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_mg_products_info: no hierarchy (zzz_mg_setup, or a solve with ZZZ_PC_SAGG)");
+  if (!mg_smoothed(H->lv[0]->kind))
+    return fail(ctx, ZZZ_ERR_ARG, "zzz_mg_products_info: the hierarchy is not ZZZ_PC_SAGG's or ZZZ_PC_SAGG_RBM's: it forms no products");
+  info[0] = H->skey.products;
+  for (size_t l = 0; l + 1 < H->lv.size(); ++l)
+  {
+    int64_t li[8];
+    if (!H->lv[l]->sagg)
+      continue;
+    sagg_products_info(H->lv[l]->sagg, li);
+    info[1] += li[1];
+    info[2] += li[2];
+    info[3] = std::max(info[3], li[3]);
+    info[4] = std::max(info[4], li[4]);
+    info[5] += li[5];
+    info[6] = std::max(info[6], li[6]);
+  }
   return ZZZ_OK;
 }
 

@@ -83,4 +83,11 @@ inline auto sort_pairs(K* kin, K* kout, V* vin, V* vout, size_t n, unsigned begi
     return rocprim::radix_sort_pairs(tmp, bytes, kin, kout, vin, vout, n, begin_bit, end_bit, s);
   };
 }
+
+// ... and of n keys alone
+template <typename K>
+inline auto sort_keys(K* kin, K* kout, size_t n, unsigned begin_bit, unsigned end_bit, hipStream_t s)
+{
+  return [=](void* tmp, size_t& bytes) { return rocprim::radix_sort_keys(tmp, bytes, kin, kout, n, begin_bit, end_bit, s); };
+}
 } // namespace zzz

@@ -12,6 +12,7 @@ namespace zzz
 {
 typedef unsigned long long u64;
 constexpr u64 SAGG_NOKEY = ~0ull;
+constexpr int RBM_NCOL = 6; // ZZZ_PC_SAGG_RBM: columns of P per aggregate, one per rigid-body mode
 
 struct SaggLevel
 {
@@ -45,6 +46,16 @@ struct SaggLevel
   int64_t ndrop = 0;
   DevBuf<double> qt, B, Bc;
   DevBuf<int32_t> pos, drop, droplist;
+  // ZZZ_MG_PRODUCTS_ROWS (zzz_sagg_rows.hip): no term list.  P and R are the CSR above (pfrow, pseg, psrc, tseg, tsrc, cseg,
+  // csrc stay empty); T is a CSR of its own, rows in the level's stored order; ord (level 0 in an internal order alone): the
+  // matrix entries of every stored row in ascending caller column.  ri: what the last build's symbolic passes did.
+  bool rows = false;
+  DevBuf<rp_t> trow;
+  DevBuf<int32_t> tcol, ord;
+  struct RowsInfo
+  {
+    int64_t chunks = 0, max_cand = 0, budget = 0, lone = 0, peak = 0;
+  } ri;
   ~SaggLevel() { agg_free(agg); }
 };
 
@@ -97,4 +108,26 @@ int sagg_products(zzz_ctx* ctx, zzz_ctx* f, SaggLevel& S, zzz_ctx* c, int level,
 // a_ii of f's rows into S.diag;  then, with P's values in S.pval: R's, T's and A_c's (into c->vals) on the kept term lists
 int sagg_diagonal(zzz_ctx* ctx, zzz_ctx* f, SaggLevel& S);
 int sagg_product_values(zzz_ctx* ctx, zzz_ctx* f, SaggLevel& S, zzz_ctx* c);
+// R = P^T from P's pattern (S.prow / S.pcol; pfrow: the stored fine row of every entry of P): S.rrow, S.rfine, S.rsrc are
+// filled and S.rval allocated; perm as SaggFrame's.  Both modes build R here.
+int sagg_transpose_p(zzz_ctx* ctx, SaggLevel& S, const int32_t* perm, const int32_t* pfrow, SaggWork& W);
+// pieces of the lists mode that the rows mode launches as they are: the row of every entry of a CSR; R's values from P's;
+// out[0] = the longest row, out[1] = the empty rows of a CSR (out: two zeroed device words)
+void sagg_row_index(zzz_ctx* ctx, int64_t nrows, const rp_t* rowptr, int32_t* rowidx);
+void sagg_r_values(zzz_ctx* ctx, SaggLevel& S);
+void sagg_row_stats(zzz_ctx* ctx, int64_t nrows, const rp_t* rowptr, int32_t* out);
+
+// ---- ZZZ_MG_PRODUCTS_ROWS (zzz_sagg_rows.hip) ----------------------------------------------------------------------
+// P_t as the row-by-row engine reads it: ZZZ_PC_SAGG's (one entry 1 per unconstrained dof of an aggregate) or
+// ZZZ_PC_SAGG_RBM's (the kept columns of Q in S.qt)
+enum class SaggPt
+{
+  UNIT,
+  RBM
+};
+// P, R, T and A_c of level f in the rows mode, patterns and values; c's rowptr / cols / vals are allocated here.  The
+// aggregates (and for RBM: S.qt, S.pos, S.drop, S.droplist, S.ndrop) stand.  *max_row = the longest row of A_c.
+int sagg_rows_build(zzz_ctx* ctx, zzz_ctx* f, SaggLevel& S, SaggPt pt, double omega, zzz_ctx* c, int level, int* max_row);
+// the values again on the kept patterns: no sort, no allocation
+int sagg_rows_values(zzz_ctx* ctx, zzz_ctx* f, SaggLevel& S, SaggPt pt, double omega, zzz_ctx* c);
 } // namespace zzz

@@ -28,6 +28,9 @@
 // ZZZ_PC_SAGG_RBM (zzz_sagg_rbm.hip) differs in P's terms and P's value kernel alone: the level (SaggLevel) and the host steps
 // from P's terms on -- sagg_p_from_terms, sagg_products, sagg_product_values, the transfers -- are declared in zzz_sagg.h and
 // serve both.  Its dropped coarse dofs reach A_c as one more term each (SaggUnitTerms).
+//
+// zzz_mg_products(ZZZ_MG_PRODUCTS_ROWS) forms the same products row by row, with no term list (zzz_sagg_rows.hip): sagg_galerkin
+// and sagg_refresh branch on it here, R is built by sagg_transpose_p in both modes, and the transfers read the same arrays.
 #include "zzz_sagg.h"
 
 #include <cstdlib>
@@ -450,6 +453,48 @@ int sagg_p_from_terms(zzz_ctx* ctx, SaggLevel& S, SaggFrame& Fr, int64_t n, int 
   return ZZZ_OK;
 }
 
+// ---- R: P's entries under (coarse column, fine row in the caller's numbering); the keys are distinct ----------
+template <int BS>
+static int sagg_transpose_p_bs(zzz_ctx* ctx, SaggLevel& S, const int32_t* perm, const int32_t* pfrow, SaggWork& W)
+{
+  hipStream_t s = ctx->stream;
+  const int gp = grid_cap(S.pnnz, VB, 1 << 16);
+  DevBuf<int32_t> erow;
+  DevBuf<u64> rtmp;
+  ZZZ_HIP(ctx, S.rrow.alloc((size_t)S.nc + 1));
+  ZZZ_HIP(ctx, S.rfine.alloc((size_t)S.pnnz));
+  ZZZ_HIP(ctx, S.rsrc.alloc((size_t)S.pnnz));
+  ZZZ_HIP(ctx, S.rval.alloc((size_t)S.pnnz));
+  ZZZ_HIP(ctx, erow.alloc((size_t)S.pnnz));
+  ZZZ_HIP(ctx, rtmp.alloc((size_t)S.pnnz));
+  ZZZ_HIP(ctx, W.k0.reserve((size_t)S.pnnz)); // (the lists mode: they hold P's terms, which are at least as many)
+  ZZZ_HIP(ctx, W.v0.reserve((size_t)S.pnnz));
+  ZZZ_HIP(ctx, W.k1.reserve((size_t)S.pnnz));
+  hipLaunchKernelGGL(k_sagg_r_keys<BS>, dim3(gp), dim3(VB), 0, s, S.pnnz, pfrow, S.pcol.p, perm, W.k0.p, W.v0.p);
+  if (int rc = with_scratch(ctx, W.tmp, sort_pairs(W.k0.p, W.k1.p, W.v0.p, rtmp.p, (size_t)S.pnnz, 0, 64, s)))
+    return rc;
+  hipLaunchKernelGGL(k_sagg_r_entries, dim3(gp), dim3(VB), 0, s, S.pnnz, W.k1.p, rtmp.p, pfrow, S.rsrc.p, S.rfine.p, erow.p);
+  hipLaunchKernelGGL(k_sagg_offsets, dim3(gp), dim3(VB), 0, s, erow.p, S.pnnz, S.nc, S.rrow.p);
+  ZZZ_HIP(ctx, hipStreamSynchronize(s)); // (erow and rtmp are locals)
+  return ZZZ_OK;
+}
+int sagg_transpose_p(zzz_ctx* ctx, SaggLevel& S, const int32_t* perm, const int32_t* pfrow, SaggWork& W)
+{
+  return S.bs == 3 ? sagg_transpose_p_bs<3>(ctx, S, perm, pfrow, W) : sagg_transpose_p_bs<1>(ctx, S, perm, pfrow, W);
+}
+void sagg_row_index(zzz_ctx* ctx, int64_t nrows, const rp_t* rowptr, int32_t* rowidx)
+{
+  hipLaunchKernelGGL(k_sagg_rowidx, dim3(grid_cap(nrows, VB, 1 << 16)), dim3(VB), 0, ctx->stream, nrows, rowptr, rowidx);
+}
+void sagg_r_values(zzz_ctx* ctx, SaggLevel& S)
+{
+  hipLaunchKernelGGL(k_sagg_gather, dim3(grid_cap(S.pnnz, VB, 1 << 16)), dim3(VB), 0, ctx->stream, S.pnnz, S.rsrc.p, S.pval.p, S.rval.p);
+}
+void sagg_row_stats(zzz_ctx* ctx, int64_t nrows, const rp_t* rowptr, int32_t* out)
+{
+  hipLaunchKernelGGL(k_sagg_rowstats, dim3(grid_cap(nrows, VB, 1 << 16)), dim3(VB), 0, ctx->stream, nrows, rowptr, out);
+}
+
 template <int BS>
 static int sagg_products_bs(zzz_ctx* ctx, zzz_ctx* f, SaggLevel& S, zzz_ctx* c, int level, SaggFrame& Fr, const SaggUnitTerms& unit,
                             int* max_row)
@@ -459,26 +504,12 @@ static int sagg_products_bs(zzz_ctx* ctx, zzz_ctx* f, SaggLevel& S, zzz_ctx* c, 
   const int32_t* perm = Fr.perm;
   const u64* order = Fr.order;
   const int32_t* rowidx = Fr.rowidx.p;
-  const int g = grid_cap(N, VB, 1 << 16), gp = grid_cap(S.pnnz, VB, 1 << 16);
+  const int g = grid_cap(N, VB, 1 << 16);
   SaggWork& W = Fr.W;
   DevBuf<int32_t> erow, tcol, tfrow, stats;
-  DevBuf<u64> rtmp;
   ZZZ_HIP(ctx, stats.alloc(2));
-  // ---- R: P's entries under (coarse column, fine row in the caller's numbering); the keys are distinct ----------
-  ZZZ_HIP(ctx, S.rrow.alloc((size_t)nc + 1));
-  ZZZ_HIP(ctx, S.rfine.alloc((size_t)S.pnnz));
-  ZZZ_HIP(ctx, S.rsrc.alloc((size_t)S.pnnz));
-  ZZZ_HIP(ctx, S.rval.alloc((size_t)S.pnnz));
-  ZZZ_HIP(ctx, erow.alloc((size_t)S.pnnz));
-  ZZZ_HIP(ctx, rtmp.alloc((size_t)S.pnnz));
-  ZZZ_HIP(ctx, W.k0.reserve((size_t)S.pnnz)); // (they hold P's terms, which are at least as many)
-  ZZZ_HIP(ctx, W.v0.reserve((size_t)S.pnnz));
-  ZZZ_HIP(ctx, W.k1.reserve((size_t)S.pnnz));
-  hipLaunchKernelGGL(k_sagg_r_keys<BS>, dim3(gp), dim3(VB), 0, s, S.pnnz, S.pfrow.p, S.pcol.p, perm, W.k0.p, W.v0.p);
-  if (int rc = with_scratch(ctx, W.tmp, sort_pairs(W.k0.p, W.k1.p, W.v0.p, rtmp.p, (size_t)S.pnnz, 0, 64, s)))
+  if (int rc = sagg_transpose_p(ctx, S, perm, S.pfrow.p, W))
     return rc;
-  hipLaunchKernelGGL(k_sagg_r_entries, dim3(gp), dim3(VB), 0, s, S.pnnz, W.k1.p, rtmp.p, S.pfrow.p, S.rsrc.p, S.rfine.p, erow.p);
-  hipLaunchKernelGGL(k_sagg_offsets, dim3(gp), dim3(VB), 0, s, erow.p, S.pnnz, nc, S.rrow.p);
   // ---- T = A P -------------------------------------------------------------------------------
   ZZZ_HIP(ctx, W.cnt.alloc((size_t)N + 1));
   hipLaunchKernelGGL(k_sagg_t_count, dim3(g), dim3(VB), 0, s, N, order, rowidx, f->cols.p, f->bc.p, S.prow.p, W.cnt.p);
@@ -601,10 +632,21 @@ static int sagg_values(zzz_ctx* ctx, zzz_ctx* f, SaggLevel& S, double omega, zzz
 int sagg_galerkin(zzz_ctx* ctx, zzz_ctx* f, SaggLevel* S, double omega, zzz_ctx* c, int level)
 {
   int max_row = 0;
-  if (int rc = f->bs == 3 ? sagg_structure_bs<3>(ctx, f, *S, c, level, &max_row) : sagg_structure_bs<1>(ctx, f, *S, c, level, &max_row))
-    return rc;
-  if (int rc = sagg_values(ctx, f, *S, omega, c))
-    return rc;
+  if (ctx->mg_products == ZZZ_MG_PRODUCTS_ROWS)
+  {
+    S->bs = f->bs;
+    S->nf = f->n_owned * f->bs;
+    S->nc = agg_count(S->agg) * f->bs;
+    if (int rc = sagg_rows_build(ctx, f, *S, SaggPt::UNIT, omega, c, level, &max_row))
+      return rc;
+  }
+  else
+  {
+    if (int rc = f->bs == 3 ? sagg_structure_bs<3>(ctx, f, *S, c, level, &max_row) : sagg_structure_bs<1>(ctx, f, *S, c, level, &max_row))
+      return rc;
+    if (int rc = sagg_values(ctx, f, *S, omega, c))
+      return rc;
+  }
   if (int rc = ctx_adopt_csr(c, S->bs, S->nc / S->bs, S->cnnz, max_row))
     return fail(ctx, rc, "-pc_type sagg: the coarse level of %lld dofs: %s", (long long)S->nc, c->err.c_str());
   return ZZZ_OK;
@@ -612,9 +654,27 @@ int sagg_galerkin(zzz_ctx* ctx, zzz_ctx* f, SaggLevel* S, double omega, zzz_ctx*
 
 int sagg_refresh(zzz_ctx* ctx, zzz_ctx* f, SaggLevel* S, double omega, zzz_ctx* c)
 {
-  if (int rc = sagg_values(ctx, f, *S, omega, c))
+  if (int rc = S->rows ? sagg_rows_values(ctx, f, *S, SaggPt::UNIT, omega, c) : sagg_values(ctx, f, *S, omega, c))
     return rc;
   return ctx_adopt_values(c);
+}
+
+template <typename T>
+static int64_t sagg_bytes(const DevBuf<T>& b) { return b.p ? (int64_t)(b.cap * sizeof(T)) : 0; }
+void sagg_products_info(const SaggLevel* S, int64_t out[8])
+{
+  for (int i = 0; i < 8; ++i)
+    out[i] = 0;
+  out[0] = S->rows ? 1 : 0;
+  out[1] = sagg_bytes(S->prow) + sagg_bytes(S->pcol) + sagg_bytes(S->pfrow) + sagg_bytes(S->pseg) + sagg_bytes(S->psrc) + sagg_bytes(S->pval)
+           + sagg_bytes(S->diag) + sagg_bytes(S->rrow) + sagg_bytes(S->rfine) + sagg_bytes(S->rsrc) + sagg_bytes(S->rval)
+           + sagg_bytes(S->tseg) + sagg_bytes(S->cseg) + sagg_bytes(S->tsrc) + sagg_bytes(S->csrc) + sagg_bytes(S->tval)
+           + sagg_bytes(S->trow) + sagg_bytes(S->tcol) + sagg_bytes(S->ord);
+  out[2] = S->ri.chunks;
+  out[3] = S->ri.max_cand;
+  out[4] = S->ri.budget;
+  out[5] = S->ri.lone;
+  out[6] = S->ri.peak;
 }
 
 int sagg_restrict(zzz_ctx* ctx, const int* stop, const SaggLevel* S, const double* rf, const double* sub, double* rc)

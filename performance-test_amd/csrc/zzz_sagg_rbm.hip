@@ -42,8 +42,6 @@
 
 namespace zzz
 {
-constexpr int RBM_NCOL = 6;
-
 // level 0: B[q][caller's index of d] = the library's vector q at the stored dof d, 0 where d is constrained
 __global__ __launch_bounds__(VB) void k_srbm_b0(int64_t nf, int64_t ld, const double* __restrict__ nn, const uint8_t* __restrict__ bc,
                                                 const int32_t* __restrict__ perm, double* __restrict__ B)
@@ -311,17 +309,21 @@ int srbm_aggregate(zzz_ctx* ctx, zzz_ctx* f, SaggLevel* S, int level)
 
 // B of the level, the orthogonalisation, and P's pattern and term list
 template <int NS>
-static int srbm_structure_ns(zzz_ctx* ctx, zzz_ctx* f, SaggLevel& S, const SaggLevel* above, zzz_ctx* c, int level, int* max_row)
+static int srbm_structure_ns(zzz_ctx* ctx, zzz_ctx* f, SaggLevel& S, const SaggLevel* above, double omega, zzz_ctx* c, int level,
+                             int* max_row)
 {
+  const bool rows = ctx->mg_products == ZZZ_MG_PRODUCTS_ROWS; // (zzz_sagg_rows.hip: no term positions, so no limit on them)
   hipStream_t s = ctx->stream;
   const int64_t N = f->nnz, nf = f->n_owned * f->bs, nn = nf / NS, nagg = agg_count(S.agg), nc = nagg * RBM_NCOL;
   S.bs = f->bs;
   S.nf = nf;
   S.nc = nc;
-  if ((uint64_t)nf * RBM_NCOL >= (1ull << 32))
+  if (!rows && (uint64_t)nf * RBM_NCOL >= (1ull << 32))
     return fail(ctx, ZZZ_ERR_LIMIT, "%s: level %d: %lld dofs: 32-bit term positions take six values per dof", S.tag, level, (long long)nf);
   SaggFrame Fr;
-  if (int rc = sagg_frame(ctx, f, Fr))
+  if (rows)
+    Fr.perm = f->dofmap.renumbered ? f->perm.p : nullptr;
+  else if (int rc = sagg_frame(ctx, f, Fr))
     return rc;
   const int32_t* agg = agg_map(S.agg);
   const int g = grid_cap(N, VB, 1 << 16), gf = grid_cap(nf, VB, 1 << 16);
@@ -352,6 +354,11 @@ static int srbm_structure_ns(zzz_ctx* ctx, zzz_ctx* f, SaggLevel& S, const SaggL
   ZZZ_HIP(ctx, S.droplist.alloc((size_t)nd));
   if (nd > 0)
     hipLaunchKernelGGL(k_srbm_drop_list, dim3(grid_cap(nc, VB, 1 << 16)), dim3(VB), 0, s, nc, S.drop.p, dscan.p, S.droplist.p);
+  if (rows)
+  {
+    ZZZ_HIP(ctx, hipStreamSynchronize(s)); // (dscan is a local)
+    return sagg_rows_build(ctx, f, S, SaggPt::RBM, omega, c, level, max_row); // (P, R, T and A_c with their values)
+  }
   // ---- P ------------------------------------------------------------------------------------
   hipLaunchKernelGGL(k_srbm_p_count<NS>, dim3(g), dim3(VB), 0, s, N, Fr.order, Fr.rowidx.p, f->cols.p, f->bc.p, agg, S.drop.p, Fr.W.cnt.p);
   int64_t pterms = 0;
@@ -391,11 +398,12 @@ static int srbm_values(zzz_ctx* ctx, zzz_ctx* f, SaggLevel& S, double omega, zzz
 int srbm_galerkin(zzz_ctx* ctx, zzz_ctx* f, SaggLevel* S, const SaggLevel* above, double omega, zzz_ctx* c, int level)
 {
   int max_row = 0;
-  if (int rc = S->ns == 3 ? srbm_structure_ns<3>(ctx, f, *S, above, c, level, &max_row)
-                          : srbm_structure_ns<RBM_NCOL>(ctx, f, *S, above, c, level, &max_row))
+  if (int rc = S->ns == 3 ? srbm_structure_ns<3>(ctx, f, *S, above, omega, c, level, &max_row)
+                          : srbm_structure_ns<RBM_NCOL>(ctx, f, *S, above, omega, c, level, &max_row))
     return rc;
-  if (int rc = srbm_values(ctx, f, *S, omega, c))
-    return rc;
+  if (!S->rows)
+    if (int rc = srbm_values(ctx, f, *S, omega, c))
+      return rc;
   if (int rc = ctx_adopt_csr(c, 1, S->nc, S->cnnz, max_row)) // (scalar: the node size is the level's)
     return fail(ctx, rc, "%s: the coarse level of %lld dofs: %s", S->tag, (long long)S->nc, c->err.c_str());
   return ZZZ_OK;
@@ -403,7 +411,7 @@ int srbm_galerkin(zzz_ctx* ctx, zzz_ctx* f, SaggLevel* S, const SaggLevel* above
 
 int srbm_refresh(zzz_ctx* ctx, zzz_ctx* f, SaggLevel* S, double omega, zzz_ctx* c)
 {
-  if (int rc = srbm_values(ctx, f, *S, omega, c))
+  if (int rc = S->rows ? sagg_rows_values(ctx, f, *S, SaggPt::RBM, omega, c) : srbm_values(ctx, f, *S, omega, c))
     return rc;
   return ctx_adopt_values(c);
 }

@@ -135,6 +135,7 @@ struct Options
   int pc_mg_coarse_eq_limit = 0; // -pc_mg_coarse_eq_limit (0: the library's default, 1000)
   int mg_degree = 0;      // -mg_levels_ksp_max_it: the smoother's Chebyshev degree (0: the library's default, 2)
   double mg_ratio = 0.0;  // -mg_levels_ksp_chebyshev_ratio: upper / lower bound of the smoothed spectrum (0: 10)
+  std::string pc_sagg_products; // -pc_sagg_products lists | rows (empty: the library's default, lists)
   bool ksp_view = false, log_view = false, options_left = false, ksp_monitor = false, ksp_cg_single_reduction = false;
   bool ksp_error_if_not_converged = false, ksp_converged_reason = false;
   std::vector<std::string> unused;
@@ -186,6 +187,8 @@ void usage()
                "  -pc_type sagg_rbm: -pc_type sagg whose prolongator carries the six rigid-body modes of `ZZZ Create near-nullspace`\n"
                "  through every level (coarse nodes of 6 dofs); --problem_type elasticity only (for scalar problems use -pc_type\n"
                "  sagg), otherwise -pc_type sagg's scope and options\n"
+               "  -pc_sagg_products arg (=lists)  -pc_type sagg / sagg_rbm: how P, A P and P^T (A P) are formed: lists (sorted term\n"
+               "  lists, kept for the refresh) | rows (row by row: the same bits, no term list, no limit on the terms)\n"
                "  -log_view -options_left\n"
             << std::endl;
 }
@@ -265,6 +268,8 @@ Options parse(int argc, char** argv)
         o.ksp_type = next();
       else if (key == "pc_type")
         o.pc_type = next();
+      else if (key == "pc_sagg_products")
+        o.pc_sagg_products = next();
       else if (key == "pc_mg_levels")
         o.pc_mg_levels = std::stoi(next());
       else if (key == "pc_mg_coarse_eq_limit")
@@ -354,6 +359,7 @@ struct Shared
   std::vector<double> tplan;  // cgpoisson: set-up of the matrix-free plan (inside ZZZ Solve, outside the Gdof/s timer)
   std::vector<int> iters;
   std::vector<std::array<double, 8>> mg_view; // -pc_type mg: the summary of zzz_mg_info, then one entry per level (rank 0)
+  std::array<std::int64_t, 8> mg_products{}; // -pc_type sagg / sagg_rbm: zzz_mg_products_info
   std::vector<long long> mg_pnnz; // -pc_type sagg: entries of the stored prolongator below each level but the coarsest
   std::vector<double> norm, rnorm0, rnorm;
   std::vector<std::string> error;
@@ -609,6 +615,8 @@ void run_rank(Shared& S, std::barrier<>& bar, int rank)
       try
       {
         double rn[2] = {0, 0};
+        if (!o.pc_sagg_products.empty())
+          ZCK(ctx, zzz_mg_products(ctx, o.pc_sagg_products == "rows" ? ZZZ_MG_PRODUCTS_ROWS : ZZZ_MG_PRODUCTS_LISTS));
         Timer tcg("cg");
         if (o.scalar_type == "float32")
           ZCK(ctx, zzz_cg_solve_f32(ctx, &so, &S.iters[rank], rn));
@@ -634,6 +642,8 @@ void run_rank(Shared& S, std::barrier<>& bar, int rank)
             ZCK(ctx, zzz_mg_level_p(ctx, l, nullptr, nullptr, nullptr, &pnnz));
             S.mg_pnnz.push_back((long long)pnnz);
           }
+          if (so.pc == ZZZ_PC_SAGG || so.pc == ZZZ_PC_SAGG_RBM)
+            ZCK(ctx, zzz_mg_products_info(ctx, S.mg_products.data()));
         }
       }
       catch (const std::exception& e)
@@ -856,6 +866,14 @@ void solve(int argc, char** argv)
     if (why)
       throw std::runtime_error("-pc_type " + o.pc_type + ": " + why);
   }
+  if (!o.pc_sagg_products.empty())
+  {
+    if (o.pc_type != "sagg" && o.pc_type != "sagg_rbm")
+      throw std::runtime_error("-pc_sagg_products " + o.pc_sagg_products + ": only -pc_type sagg and -pc_type sagg_rbm form the products it "
+                               "chooses between (-pc_type " + o.pc_type + " does not)");
+    if (o.pc_sagg_products != "lists" && o.pc_sagg_products != "rows")
+      throw std::runtime_error("-pc_sagg_products " + o.pc_sagg_products + ": lists or rows");
+  }
   if (o.ngpus < 1 || (o.comm == "rccl" && o.ngpus > ndev))
     throw std::runtime_error("--ngpus " + std::to_string(o.ngpus) + " but " + std::to_string(ndev) + " GPU(s) visible");
 
@@ -988,6 +1006,16 @@ void solve(int argc, char** argv)
       }
       else
         std::cout << ", dense direct solve\n";
+    }
+    if (o.pc_type == "sagg" || o.pc_type == "sagg_rbm")
+    {
+      const auto& p = S.mg_products;
+      std::cout << "  products: " << (p[0] == ZZZ_MG_PRODUCTS_ROWS ? "rows" : "lists") << ", P, R, T and their "
+                << (p[0] == ZZZ_MG_PRODUCTS_ROWS ? "permutation" : "term lists") << " hold " << (long long)p[1] << " bytes";
+      if (p[0] == ZZZ_MG_PRODUCTS_ROWS)
+        std::cout << ", " << (long long)p[2] << " chunks of at most " << (long long)p[4] << " candidates (" << (long long)p[5]
+                  << " rows alone), the longest row " << (long long)p[3] << ", transient peak " << (long long)p[6] << " bytes";
+      std::cout << "\n";
     }
   }
   g_timers.list(); // dolfinx::list_timings, src/main.cpp:226

@@ -21,6 +21,7 @@ PC_NONE, PC_JACOBI, PC_CHEBYSHEV_JACOBI, PC_MG, PC_PMG, PC_AGG, PC_SAGG, PC_SAGG
 NORM_PRECONDITIONED, NORM_UNPRECONDITIONED, NORM_NATURAL = 0, 1, 2
 CG_PETSC, CG_CGH, CG_PIPE = 0, 1, 2
 OP_CSR, OP_MATFREE = 0, 1
+MG_PRODUCTS_LISTS, MG_PRODUCTS_ROWS = 0, 1
 ERR_NO_GPU = 4
 
 ABI_SYMBOLS = [
@@ -32,6 +33,7 @@ ABI_SYMBOLS = [
     "zzz_profile_get", "zzz_cg_info", "zzz_internal_order_download", "zzz_global_ids_upload", "zzz_global_ids_download", "zzz_ghost_layer_build", "zzz_local_sizes", "zzz_spmv_info", "zzz_comm_load", "zzz_comm_library_path", "zzz_comm_info", "zzz_comm_unique_id", "zzz_comm_init", "zzz_halo_upload", "zzz_local_group_create",
     "zzz_local_group_destroy", "zzz_local_group_abort", "zzz_comm_init_local", "zzz_comm_init_peer_only", "zzz_comm_p2p_export", "zzz_comm_p2p_attach", "zzz_comm_p2p_disable", "zzz_comm_p2p_enable", "zzz_comm_p2p_halo",
     "zzz_mg_setup", "zzz_mg_info", "zzz_mg_apply", "zzz_mg_transfer", "zzz_mg_level_csr", "zzz_mg_level_p", "zzz_mg_level_nns",
+    "zzz_mg_products", "zzz_mg_products_info",
     "zzz_action_f32", "zzz_action_time_f32", "zzz_matfree_info_f32", "zzz_cg_solve_f32",
 ]
 HOST_SYMBOLS = [
@@ -138,6 +140,9 @@ def hip():
             L.zzz_mg_level_p.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
         if hasattr(L, "zzz_mg_level_nns"):  # (... or from before ZZZ_PC_SAGG_RBM)
             L.zzz_mg_level_nns.argtypes = [C.c_void_p, C.c_int, _f64p]
+        if hasattr(L, "zzz_mg_products"):  # (... or from before ZZZ_MG_PRODUCTS_ROWS)
+            L.zzz_mg_products.argtypes = [C.c_void_p, C.c_int]
+            L.zzz_mg_products_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
         L.zzz_profile_get.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
         L.zzz_spmv_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
         L.zzz_spmv_values_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
@@ -686,6 +691,19 @@ class Context:
         B = np.zeros((6, self.mg_info(level)["dofs"]))
         self._ck(self.L.zzz_mg_level_nns(self.h, level, B))
         return B
+
+    def mg_products(self, mode):
+        """how the next ZZZ_PC_SAGG / ZZZ_PC_SAGG_RBM hierarchy forms P, A P and P^T (A P): MG_PRODUCTS_LISTS (sorted term lists,
+        the default) or MG_PRODUCTS_ROWS (row by row, no term list; the same bits) (zzz_mg_products)"""
+        self._ck(self.L.zzz_mg_products(self.h, int(mode)))
+
+    def mg_products_info(self):
+        """dict(mode, kept_bytes, chunks, max_row_candidates, budget, lone_rows, peak_transient_bytes) of the standing smoothed
+        hierarchy (zzz_mg_products_info)"""
+        a = (C.c_int64 * 8)()
+        self._ck(self.L.zzz_mg_products_info(self.h, a))
+        return dict(zip(("mode", "kept_bytes", "chunks", "max_row_candidates", "budget", "lone_rows", "peak_transient_bytes"),
+                        [int(v) for v in a[:7]]))
 
     def cg_history(self, n):
         out = np.zeros(n)
