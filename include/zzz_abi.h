@@ -91,7 +91,8 @@ enum
    * cube meshes, not an algebraic one).  Scope: P1, Poisson and elasticity, a context whose feed came from
    * zzz_cube_generate with nparts == 1, the assembled operator, ZZZ_CG_PETSC in its classical form, all three norm
    * types.  Declined with ZZZ_ERR_ARG and a message that names the reason (the context stays usable): order 2 or 3,
-   * an uploaded / unstructured feed, a communicator attached, ZZZ_OP_MATFREE, single_reduction, ZZZ_CG_PIPE, ZZZ_CG_CGH.
+   * an uploaded / unstructured feed, a communicator attached (but see SEVERAL RANKS below), ZZZ_OP_MATFREE,
+   * single_reduction, ZZZ_CG_PIPE, ZZZ_CG_CGH.
    * Level l+1 is the same problem RE-DISCRETISED on max(2, (n+1)/2) cells per axis (not nested when n is odd), generated,
    * patterned and assembled by the library's own kernels; the coarsest level is the first with at most
    * pc_mg_coarse_eq_limit scalar dofs (or 2 x 2 x 2 cells, or level pc_mg_levels, 12 at most) and is solved with a dense
@@ -101,7 +102,23 @@ enum
    * symmetric; for mg pc_degree == 0 selects 2 and pc_ratio <= 1 selects 10; hi is each level's own bound, taken as
    * ZZZ_PC_CHEBYSHEV_JACOBI takes it (pc_esteig_its).  The hierarchy is built by the first solve (or zzz_mg_setup), kept
    * across solves, rebuilt when the feed changes, its values refreshed when the matrix values change.  After
-   * zzz_csr_upload_values on the context the coarse levels STAY the re-discretised ones of the generated problem. */
+   * zzz_csr_upload_values on the context the coarse levels STAY the re-discretised ones of the generated problem.
+   * SEVERAL RANKS: a communicator of two or more ranks with a transport (zzz_comm_init or zzz_comm_init_local) on a cube
+   * generated by zzz_cube_generate(..., nparts = nranks, part = rank) is served too.  Level 0 stays on the z-slabs (its
+   * products exchange the halo, its bound is the ranks' common one, as ZZZ_PC_CHEBYSHEV_JACOBI has them) and EVERY coarser
+   * level is held whole by every rank, built by the level rule from the global cube: the one-rank hierarchy and, up to the
+   * order of one sum, the one-rank preconditioner, whatever the number of ranks.  The prolongation reads the whole level-1
+   * vector and writes the owned fine dofs, with the one-rank kernel's bits; the restriction leaves each rank's partial sums
+   * over its own fine vertex planes in the whole level-1 vector, zero where it reaches nothing, and the communicator adds
+   * them (one all-reduce of the level-1 right-hand side per cycle, in the communicator's order).  From level 1 down every
+   * rank runs the same cycle on the same numbers.  zzz_mg_setup, zzz_mg_apply, zzz_mg_transfer at level 0 (both directions)
+   * and zzz_cg_solve with this preconditioner are then COLLECTIVE; before a set-up returns on any rank the ranks agree on
+   * its status, so none enters a cycle while another has failed.  Declined there, with ZZZ_ERR_ARG and the reason: a
+   * communicator of ONE rank (as before: "a communicator is attached"), a peer-only communicator (zzz_comm_init_peer_only:
+   * the all-reduce needs a transport), a cube generated as another part or of another number of parts than the
+   * communicator's rank and size, an uploaded feed (the native partition behind zzz_ghost_layer_build is one), a cube under
+   * the coarse limit (one level: a dense solve of a matrix no rank holds).  ZZZ_PC_PMG, ZZZ_PC_AGG, ZZZ_PC_SAGG and
+   * ZZZ_PC_SAGG_RBM keep declining any communicator. */
   ZZZ_PC_MG = 3,
   /* p-multigrid for orders 2 and 3 on the same cubes: ZZZ_PC_MG's scope with the order test dropped.  Level 0 is the
    * caller's Pk matrix, smoothed like every other level; level 1 is the SAME cube re-discretised at order 1 (generated,
@@ -524,7 +541,9 @@ int zzz_internal_order_download(zzz_ctx* ctx, int32_t* perm /* n_owned */, int32
 /* solver_function(u, b) (src/poisson_problem.cpp:164-179; src/cgpoisson_problem.cpp:178-244;
  * called under `ZZZ Solve` at src/main.cpp:208-211).  Solves A u = b with the vectors held by
  * the context; returns the Krylov iteration count like KSPGetIterationNumber / cg()'s k.
- * rnorm[0] = final norm, rnorm[1] = initial norm (variant CGH: <r,r> and <r0,r0>). */
+ * rnorm[0] = final norm, rnorm[1] = initial norm (variant CGH: <r,r> and <r0,r0>).  With a communicator the solve is
+ * collective; that holds for pc = ZZZ_PC_MG on several ranks too (set-up, every cycle's halo exchanges and its all-reduce
+ * of the level-1 right-hand side, the all-reduced scalars: all ranks stop together). */
 int zzz_cg_solve(zzz_ctx* ctx, const zzz_solver_opts* opts, int* iters, double* rnorm);
 /* linalg::cg<float> (src/cg.h:38-86 with U = float, called at src/cgpoisson_problem.cpp:233) on the float action: x, r,
  * p, y are float device vectors, alpha and beta floats as `const U alpha`, `const U beta` are (:65,75).  DIFFERENCE: the
@@ -603,19 +622,25 @@ int zzz_pattern_info(zzz_ctx* ctx, int64_t info[8]);
  * use, inside the solve, where PETSc's PCSetUp runs.  Overwrites the context's Krylov work vectors (not b, not u).
  * opts->pc == ZZZ_PC_PMG builds the p-multigrid hierarchy, ZZZ_PC_AGG / ZZZ_PC_SAGG / ZZZ_PC_SAGG_RBM the (smoothed) aggregation hierarchy
  * (zzz_mg_info then reports nx = ny = nz = 0 for every level); any other value is read as ZZZ_PC_MG.  One context holds one hierarchy: a set-up
- * of another kind replaces it. */
+ * of another kind replaces it.  ZZZ_PC_MG on several ranks (see ZZZ_PC_MG): COLLECTIVE; every rank returns the ranks' common
+ * status (a rank whose own set-up succeeded while another's failed gets ZZZ_ERR_RCCL and keeps no hierarchy). */
 int zzz_mg_setup(zzz_ctx* ctx, const zzz_solver_opts* opts);
 /* PCView of that hierarchy.  level < 0: out = {levels, scalar dofs of the coarsest, set-ups done so far (builds and
  * refreshes), products per V-cycle on level 0, device bytes of the coarse levels, HIP-event ms per V-cycle in the last solve
  * with opts.profile != 0 (else 0), host ms of the last set-up that did work (it ends synchronised), levels of order > 1
  * (ZZZ_PC_PMG at order 2 or 3: 1, they come first; else 0)}.  Otherwise that level's
- * {nx, ny, nz, scalar dofs, nonzeros, hi, lo, smoother degree} (hi = lo = degree = 0 on the coarsest: a dense solve). */
+ * {nx, ny, nz, scalar dofs, nonzeros, hi, lo, smoother degree} (hi = lo = degree = 0 on the coarsest: a dense solve).
+ * ZZZ_PC_MG on several ranks: level 0 reports the cells, dofs and nonzeros of the GLOBAL cube (the ranks' owned rows together),
+ * so the level table is the same on every rank, and the one-rank run's. */
 int zzz_mg_info(zzz_ctx* ctx, int level, double out[8]);
-/* PCApply: z = M r, one V-cycle on host vectors of the owned size -- zzz_spmv's counterpart, for parity checks. */
+/* PCApply: z = M r, one V-cycle on host vectors of the owned size -- zzz_spmv's counterpart, for parity checks.  ZZZ_PC_MG on
+ * several ranks: COLLECTIVE; takes and returns this rank's owned-length vectors. */
 int zzz_mg_apply(zzz_ctx* ctx, const double* r, double* z);
 /* The grid transfer between level and level + 1 alone (MatInterpolate / MatRestrict of PCMG): dir 0 gives
  * out = P~ in (in: level + 1, out: level), dir 1 gives out = P~^T in.  P~ = F_f P F_c with F zeroing the constrained
- * dofs.  The restriction sums in a fixed order: two calls give the same bits. */
+ * dofs.  The restriction sums in a fixed order: two calls give the same bits.  ZZZ_PC_MG on several ranks: level 0 moves between
+ * this rank's OWNED fine vector and the WHOLE level-1 vector and is COLLECTIVE in both directions (the restriction's result is
+ * the ranks' sum, the same on every rank); the levels below are every rank's own. */
 int zzz_mg_transfer(zzz_ctx* ctx, int level, int dir, const double* in, double* out);
 /* The matrix of a coarse level (1 <= level < levels) as the hierarchy holds it, for parity checks: 64-bit row pointers
  * (scalar dofs + 1), columns and values (zzz_mg_info(level) gives the sizes); any of the three may be NULL. */

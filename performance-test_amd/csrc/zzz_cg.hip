@@ -1480,10 +1480,6 @@ __global__ __launch_bounds__(VB) void k_dots_rz(const int* __restrict__ stop, co
   }
 }
 
-int comm_allgather_max(zzz_ctx* ctx, double* v); // zzz_comm.hip: maximum of one double over the ranks (set-up exchange)
-int comm_allgather_double(zzz_ctx* ctx, double v, double* all);
-int comm_rank_of(const zzz_ctx* ctx, int* nranks);
-
 // the noise vector of the spectrum estimate (oracle: zo_noise): a fixed hash of the GLOBAL row number in the caller's
 // numbering, so that neither the library's internal order nor the partition changes the estimate
 __global__ __launch_bounds__(VB) void k_noise(const int32_t* __restrict__ perm, int bs, int64_t offset, int64_t n,
@@ -1794,9 +1790,10 @@ struct MgPc : CgPc
                          ctx->w.p, ctx->dinv.p, ctx->r.p, ctx->z.p, n, o->norm, pa, pb, o->variant, DinvCodes());
     if (int rc = mg_vcycle(ctx, ctx->r.p, ctx->z.p, o->profile != 0))
       return rc;
-    hipLaunchKernelGGL(k_dots_rz, dim3(g), dim3(VB), 0, s, reinterpret_cast<const int*>(ctx->state.p), ctx->r.p, ctx->z.p, n, o->norm, pa,
-                       pb);
-    return ZZZ_OK;
+    const int* stop_flag = reinterpret_cast<const int*>(ctx->state.p);
+    hipLaunchKernelGGL(k_dots_rz, dim3(g), dim3(VB), 0, s, stop_flag, ctx->r.p, ctx->z.p, n, o->norm, pa, pb);
+    // (ZZZ_PC_MG on several ranks: the scalars of the owned entries, summed over the ranks as ChebPc's are)
+    return ctx->comm ? comm_reduce_allreduce(ctx, stop_flag, rz, nn, nullptr, n_rz, 2, ctx->red.p) : ZZZ_OK;
   }
   // the cycle of the start-up and one per iteration that ran.  Behind a finish that failed (a HIP error) last_iters is the
   // solve's before and the mean says nothing; the call still runs, to hand the cycle's events back for the next solve.

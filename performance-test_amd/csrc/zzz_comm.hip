@@ -556,6 +556,8 @@ static void p2p_destroy(P2P* P)
   delete P;
 }
 
+bool comm_has_transport(const zzz_ctx* ctx) { return ctx->comm && (ctx->comm->local || ctx->comm->comm); }
+
 int comm_allreduce_sum(zzz_ctx* ctx, double* dev, int n)
 {
   if (!ctx->comm)

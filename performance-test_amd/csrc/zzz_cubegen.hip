@@ -165,6 +165,7 @@ extern "C" int zzz_cube_generate(zzz_ctx* ctx, int problem, int order, int64_t n
   ctx->cube_feed = true;
   ctx->cube_problem = problem;
   ctx->cube_nparts = nparts;
+  ctx->cube_part = part;
   ctx->cube_n[0] = nx;
   ctx->cube_n[1] = ny;
   ctx->cube_n[2] = nz;

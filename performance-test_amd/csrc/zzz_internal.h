@@ -422,7 +422,7 @@ struct zzz_ctx
   // ZZZ_PC_MG (zzz_mg.hip): the cube this context's feed was generated from by zzz_cube_generate (cleared by every
   // upload of mesh, dofmap, Dirichlet set or facets; feed_version counts all of them), and the hierarchy built on it
   bool cube_feed = false;
-  int cube_problem = 0, cube_nparts = 0;
+  int cube_problem = 0, cube_nparts = 0, cube_part = 0;
   int64_t cube_n[3] = {0, 0, 0};
   uint64_t feed_version = 0;
   zzz::MgHier* mg = nullptr;
@@ -667,6 +667,10 @@ void sagg_products_info(const SaggLevel* S, int64_t out[8]);
 
 // comm
 int comm_allreduce_sum(zzz_ctx* ctx, double* dev, int n);
+bool comm_has_transport(const zzz_ctx* ctx); // comm_allreduce_sum has something to go through: the local group or RCCL (not peer-only)
+int comm_allgather_max(zzz_ctx* ctx, double* v); // maximum of one double over the ranks (set-up exchange)
+int comm_allgather_double(zzz_ctx* ctx, double v, double* all);
+int comm_rank_of(const zzz_ctx* ctx, int* nranks);
 // out[0..nv) = all-reduced sums of up to three partial arrays (one kernel with the peer-memory backend,
 // reduce kernel + ncclAllReduce otherwise); stop: device flag that makes the call a no-op, or null
 int comm_reduce_allreduce(zzz_ctx* ctx, const int* stop, const double* pa, const double* pb, const double* pc, int np, int nv,

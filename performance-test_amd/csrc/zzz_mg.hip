@@ -31,9 +31,17 @@
 // context's near-nullspace in the tentative prolongator (zzz_sagg_rbm.hip): nodes of 6 dofs on its coarse levels, whose
 // contexts are scalar.
 //
+// ZZZ_PC_MG on several ranks (a communicator of two or more, the cube generated as part `rank` of `nranks` z-slabs): level 0 is
+// the caller's slab -- its products exchange the halo, its bound is the ranks' common one (chebyshev_setup) -- and EVERY coarser
+// level is whole on every rank, the child contexts of the one-rank hierarchy, built from the global cube's dimensions.  The pair
+// (0, 1) moves between the owned fine vector and the whole level-1 vector: the prolongation reads the whole coarse vector, the
+// restriction leaves this rank's partial sums and the communicator adds them (comm_allreduce_sum, in its order).  From level 1
+// down every rank runs the same cycle on the same numbers, so the preconditioner is the one-rank operator.
+//
 // The five differ in MgKind alone (a level's transfer, the next level, that level's values); the set-up keeps a
 // hierarchy while its MgStructKey holds and the levels' values while its MgValuesKey holds.
 #include "zzz_cg.h"
+#include "zzz_mg_transfer.h"
 
 #include <algorithm>
 #include <chrono>
@@ -43,59 +51,8 @@
 
 namespace zzz
 {
-// one level pair: vertices per axis, table offsets of the axes (fine tables: c and f per fine index; coarse tables: the
-// range of fine indices whose simplex can touch a coarse index)
-struct MgGeom
-{
-  int32_t pf[3], pc[3]; // vertices per axis, fine / coarse
-  int32_t of[3], oc[3]; // where axis a starts in the fine / coarse tables
-  int32_t bs;
-  int64_t nfv, ncv; // vertices
-};
-
-struct MgSimplex
-{
-  int32_t j[4]; // coarse vertices
-  double w[4];
-};
-
-// (values and axes travel through the three compare-exchanges in registers: no indexed private array, no scratch)
-__device__ inline MgSimplex mg_simplex(const MgGeom& G, const int32_t* __restrict__ tc, const double* __restrict__ tf, int ix,
-                                       int iy, int iz)
-{
-  const int cx = tc[G.of[0] + ix], cy = tc[G.of[1] + iy], cz = tc[G.of[2] + iz];
-  double v0 = tf[G.of[0] + ix], v1 = tf[G.of[1] + iy], v2 = tf[G.of[2] + iz];
-  const int sx = 1, sy = G.pc[0], sz = G.pc[0] * G.pc[1];
-  int s0 = sx, s1 = sy, s2 = sz;
-  // descending, ties to the lower axis: strict comparisons of neighbours keep equal values in axis order
-  if (v1 > v0)
-  {
-    const double t = v0; v0 = v1; v1 = t;
-    const int u = s0; s0 = s1; s1 = u;
-  }
-  if (v2 > v1)
-  {
-    const double t = v1; v1 = v2; v2 = t;
-    const int u = s1; s1 = s2; s2 = u;
-  }
-  if (v1 > v0)
-  {
-    const double t = v0; v0 = v1; v1 = t;
-    const int u = s0; s0 = s1; s1 = u;
-  }
-  MgSimplex S;
-  S.j[0] = (cz * G.pc[1] + cy) * G.pc[0] + cx;
-  S.j[1] = S.j[0] + s0;
-  S.j[2] = S.j[1] + s1;
-  S.j[3] = S.j[2] + s2;
-  S.w[0] = 1.0 - v0;
-  S.w[1] = v0 - v1;
-  S.w[2] = v1 - v2;
-  S.w[3] = v2;
-  return S;
-}
-
-// x_f (+)= P~ e_c: a thread per fine vertex, four gathers per component, summed in the simplex's order
+// x_f (+)= P~ e_c: a thread per fine vertex of the window (zzz_mg_transfer.h), four gathers per component, summed in the
+// simplex's order
 __global__ __launch_bounds__(VB) void k_mg_prolong(const int* __restrict__ stop, MgGeom G, const int32_t* __restrict__ tc,
                                                    const double* __restrict__ tf, const uint8_t* __restrict__ bcf,
                                                    const uint8_t* __restrict__ bcc, const double* __restrict__ ec,
@@ -104,33 +61,12 @@ __global__ __launch_bounds__(VB) void k_mg_prolong(const int* __restrict__ stop,
   if (stop && *stop)
     return;
   for (int64_t v = blockIdx.x * (int64_t)VB + threadIdx.x; v < G.nfv; v += (int64_t)gridDim.x * VB)
-  {
-    const int ix = (int)(v % G.pf[0]), iy = (int)((v / G.pf[0]) % G.pf[1]), iz = (int)(v / ((int64_t)G.pf[0] * G.pf[1]));
-    const MgSimplex S = mg_simplex(G, tc, tf, ix, iy, iz);
-    for (int k = 0; k < G.bs; ++k)
-    {
-      const int64_t i = v * G.bs + k;
-      double e[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-      {
-        const int64_t j = (int64_t)S.j[q] * G.bs + k;
-        e[q] = bcc[j] ? 0.0 : ec[j];
-      }
-      double s = S.w[0] * e[0];
-      s += S.w[1] * e[1];
-      s += S.w[2] * e[2];
-      s += S.w[3] * e[3];
-      if (bcf[i])
-        s = 0.0;
-      xf[i] = accumulate ? xf[i] + s : s;
-    }
-  }
+    mg_prolong_vertex(G, tc, tf, bcf, bcc, ec, xf, accumulate, v);
 }
 
-// r_c = P~^T r_f in gather form: a thread per coarse vertex walks the fine vertices whose simplex can hold it, in
-// ascending (i_z, i_y, i_x) -- no atomics, the same bits in every run.  sub != null: r_f = b - sub, the residual formed
-// on the way in (b - A x with sub = A x), which saves the pass that would store it.
+// r_c = P~^T r_f in gather form: a thread per coarse vertex of the planes the window reaches walks the window's fine vertices
+// whose simplex can hold it, in ascending (i_z, i_y, i_x) -- no atomics, the same bits in every run.  sub != null:
+// r_f = b - sub, the residual formed on the way in (b - A x with sub = A x), which saves the pass that would store it.
 template <int BS>
 __global__ __launch_bounds__(VB) void k_mg_restrict(const int* __restrict__ stop, MgGeom G, const int32_t* __restrict__ tc,
                                                     const double* __restrict__ tf, const int32_t* __restrict__ rng,
@@ -140,57 +76,9 @@ __global__ __launch_bounds__(VB) void k_mg_restrict(const int* __restrict__ stop
 {
   if (stop && *stop)
     return;
+  const int64_t c0 = (int64_t)G.cz0 * G.pc[0] * G.pc[1];
   for (int64_t c = blockIdx.x * (int64_t)VB + threadIdx.x; c < G.ncv; c += (int64_t)gridDim.x * VB)
-  {
-    const int Cx = (int)(c % G.pc[0]), Cy = (int)((c / G.pc[0]) % G.pc[1]), Cz = (int)(c / ((int64_t)G.pc[0] * G.pc[1]));
-    const int x0 = rng[2 * (G.oc[0] + Cx)], x1 = rng[2 * (G.oc[0] + Cx) + 1];
-    const int y0 = rng[2 * (G.oc[1] + Cy)], y1 = rng[2 * (G.oc[1] + Cy) + 1];
-    const int z0 = rng[2 * (G.oc[2] + Cz)], z1 = rng[2 * (G.oc[2] + Cz) + 1];
-    double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0;
-    for (int iz = z0; iz <= z1; ++iz)
-      for (int iy = y0; iy <= y1; ++iy)
-        for (int ix = x0; ix <= x1; ++ix)
-        {
-          const MgSimplex S = mg_simplex(G, tc, tf, ix, iy, iz);
-          // the four vertices of a simplex are distinct: at most one of them is this thread's
-          double w;
-          if (S.j[0] == (int32_t)c)
-            w = S.w[0];
-          else if (S.j[1] == (int32_t)c)
-            w = S.w[1];
-          else if (S.j[2] == (int32_t)c)
-            w = S.w[2];
-          else if (S.j[3] == (int32_t)c)
-            w = S.w[3];
-          else
-            continue;
-          const int64_t i = (((int64_t)iz * G.pf[1] + iy) * G.pf[0] + ix) * BS;
-          {
-            double v = sub ? rf[i] - sub[i] : rf[i];
-            if (bcf[i])
-              v = 0.0;
-            acc0 += w * v;
-          }
-          if (BS == 3)
-          {
-            double v = sub ? rf[i + 1] - sub[i + 1] : rf[i + 1];
-            if (bcf[i + 1])
-              v = 0.0;
-            acc1 += w * v;
-            v = sub ? rf[i + 2] - sub[i + 2] : rf[i + 2];
-            if (bcf[i + 2])
-              v = 0.0;
-            acc2 += w * v;
-          }
-        }
-    const int64_t o = c * BS;
-    rc[o] = bcc[o] ? 0.0 : acc0;
-    if (BS == 3)
-    {
-      rc[o + 1] = bcc[o + 1] ? 0.0 : acc1;
-      rc[o + 2] = bcc[o + 2] ? 0.0 : acc2;
-    }
-  }
+    mg_restrict_vertex<BS>(G, tc, tf, rng, bcf, bcc, rf, sub, rc, c0 + c);
 }
 
 // The coarsest level: x = A^-1 b with the dense inverse, a wavefront per row; lane l sums columns l, l + 64, ... in
@@ -237,6 +125,8 @@ struct MgLevel
   MgKind kind = MgKind::GEOM;
   int64_t n[3] = {0, 0, 0}; // cells of the cube (AGG: none)
   int64_t ndof = 0;
+  bool slab = false; // level 0 of a hierarchy on several ranks: this rank's planes of the cube, G's window
+  int64_t nvec = 0; // entries of this rank's vectors on the level: ndof, but on level 0 of a slab the owned ones
   int order = 1; // PLEVEL: the order of this level's element
   ChebPlan cheb; // the smoother (its vectors: the level context's cheb_g, cheb_d, cheb_d2); the coarsest level has none
   // GEOM: the transfer's tables
@@ -259,10 +149,12 @@ struct MgStructKey
   int opt_levels = 0, limit = 0;
   MgKind kind = MgKind::GEOM; // of level 0
   int products = 0;           // SAGG, SAGG_RBM: zzz_mg_products' mode; else 0
+  int nparts = 1, part = 0;   // GEOM on several ranks: the slab that level 0 is
   bool operator==(const MgStructKey& k) const
   {
     return feed_version == k.feed_version && pattern_version == k.pattern_version && bc_version == k.bc_version
-           && opt_levels == k.opt_levels && limit == k.limit && kind == k.kind && products == k.products;
+           && opt_levels == k.opt_levels && limit == k.limit && kind == k.kind && products == k.products && nparts == k.nparts
+           && part == k.part;
   }
 };
 struct MgValuesKey
@@ -284,6 +176,8 @@ struct MgHier
   MgStructKey skey;
   MgValuesKey vkey;
   int setups = 0;
+  bool slab = false;      // level 0 is a z-slab of the cube, the coarser levels are whole on every rank
+  double nnz0 = 0.0;      // slab: the nonzeros of the whole cube's matrix (the ranks' owned rows together)
   double coarse_bytes = 0.0;
   double setup_ms = 0.0; // host time of the last set-up that did work (it ends synchronised)
   double cycle_ms = 0.0; // HIP-event time per V-cycle in the last solve with zzz_solver_opts.profile set
@@ -337,8 +231,15 @@ int mg_check(zzz_ctx* ctx, const zzz_solver_opts* o)
     return fail(ctx, ZZZ_ERR_ARG, "%s: not with -ksp_cg_single_reduction (the classical form of KSPCG only)", tag);
   if (o->op != ZZZ_OP_CSR)
     return fail(ctx, ZZZ_ERR_ARG, "%s: needs the assembled operator, not ZZZ_OP_MATFREE", tag);
-  if (ctx->comm)
+  // a communicator: ZZZ_PC_MG alone serves one, of two ranks or more (level 0 on the slabs, the coarser levels whole on every rank)
+  int nranks = 1;
+  const int rank = comm_rank_of(ctx, &nranks);
+  const bool slab = ctx->comm && o->pc == ZZZ_PC_MG && nranks >= 2;
+  if (ctx->comm && !slab)
     return fail(ctx, ZZZ_ERR_ARG, "%s: a communicator is attached; multi-rank multigrid is not built", tag);
+  if (slab && !comm_has_transport(ctx))
+    return fail(ctx, ZZZ_ERR_ARG, "%s: the communicator has no transport (peer-only): the all-reduce of the level-1 right-hand side "
+                                  "needs one (zzz_comm_init or zzz_comm_init_local)", tag);
   if (agg)
   {
     // the matrix alone: whatever feed, order, numbering or source of the values
@@ -360,7 +261,12 @@ int mg_check(zzz_ctx* ctx, const zzz_solver_opts* o)
     if (!ctx->cube_feed)
       return fail(ctx, ZZZ_ERR_ARG, "%s: the feed was uploaded (unstructured or host-built), not generated by "
                                     "zzz_cube_generate: the library does not know the cube to coarsen", tag);
-    if (ctx->cube_nparts != 1 || ctx->n_ghost != 0)
+    if (slab && (ctx->cube_nparts != nranks || ctx->cube_part != rank))
+      return fail(ctx, ZZZ_ERR_ARG, "%s: the cube was generated as part %d of %d, the communicator has rank %d of %d: a rank's level 0 "
+                                    "is its own slab of as many slabs as ranks", tag, ctx->cube_part, ctx->cube_nparts, rank, nranks);
+    if (slab && ctx->cube_n[2] < nranks) // (zzz_cube_generate refuses it already)
+      return fail(ctx, ZZZ_ERR_ARG, "%s: %lld cell layers for %d ranks: a rank would own none", tag, (long long)ctx->cube_n[2], nranks);
+    if (!slab && (ctx->cube_nparts != 1 || ctx->n_ghost != 0))
       return fail(ctx, ZZZ_ERR_ARG, "%s: the cube was generated as part of %d: one part only", tag, ctx->cube_nparts);
     if (ctx->dofmap.order != 1 && !pmg)
       return fail(ctx, ZZZ_ERR_ARG, "%s: order %d; P1 only (p-coarsening for P2 / P3 is -pc_type pmg, ZZZ_PC_PMG)", tag, ctx->dofmap.order);
@@ -387,46 +293,19 @@ static int child_fail(zzz_ctx* ctx, zzz_ctx* c, int rc, int level, const char* w
   return fail(ctx, rc, "-pc_type mg / pmg / agg / sagg / sagg_rbm, level %d, %s: %s", level, what, c ? c->err.c_str() : zzz_last_error(nullptr));
 }
 
-static int mg_build_tables(zzz_ctx* ctx, MgLevel& F, const MgLevel& C)
+// (slab: F is level 0 of a hierarchy on several ranks -- the window is the planes this rank owns)
+static int mg_build_tables(zzz_ctx* ctx, MgLevel& F, const MgLevel& C, bool slab)
 {
-  MgGeom& G = F.G;
-  G.bs = ctx->bs;
-  int32_t nf_tot = 0, nc_tot = 0;
-  for (int a = 0; a < 3; ++a)
-  {
-    G.pf[a] = (int32_t)F.n[a] + 1;
-    G.pc[a] = (int32_t)C.n[a] + 1;
-    G.of[a] = nf_tot;
-    G.oc[a] = nc_tot;
-    nf_tot += G.pf[a];
-    nc_tot += G.pc[a];
-  }
-  G.nfv = (int64_t)G.pf[0] * G.pf[1] * G.pf[2];
-  G.ncv = (int64_t)G.pc[0] * G.pc[1] * G.pc[2];
+  int64_t nf_tot = 0, nc_tot = 0, z0 = 0, z1 = F.n[2];
+  mg_table_sizes(F.n, C.n, &nf_tot, &nc_tot);
+  if ((F.slab = slab))
+    mg_slab_planes(F.n[2], ctx->cube_nparts, ctx->cube_part, &z0, &z1);
   std::vector<int32_t> tc((size_t)nf_tot), rng(2 * (size_t)nc_tot);
   std::vector<double> tf((size_t)nf_tot);
-  for (int a = 0; a < 3; ++a)
-  {
-    const int64_t nf = F.n[a], nc = C.n[a];
-    for (int64_t j = 0; j <= nc; ++j)
-    {
-      rng[2 * (size_t)(G.oc[a] + j)] = INT32_MAX;
-      rng[2 * (size_t)(G.oc[a] + j) + 1] = -1;
-    }
-    for (int64_t i = 0; i <= nf; ++i)
-    {
-      const int64_t c = std::min(i * nc / nf, nc - 1);
-      tc[(size_t)(G.of[a] + i)] = (int32_t)c;
-      tf[(size_t)(G.of[a] + i)] = (double)(i * nc - c * nf) / (double)nf;
-      // fine index i can reach coarse indices c and c + 1 of this axis
-      for (int64_t j = c; j <= c + 1; ++j)
-      {
-        int32_t* r = &rng[2 * (size_t)(G.oc[a] + j)];
-        r[0] = std::min(r[0], (int32_t)i);
-        r[1] = std::max(r[1], (int32_t)i);
-      }
-    }
-  }
+  mg_fill_tables(F.G, F.n, C.n, ctx->bs, z0, z1, tc.data(), tf.data(), rng.data());
+  if (F.G.nfv * ctx->bs != F.nvec)
+    return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg: the context owns %lld dofs, planes %lld..%lld of the cube hold %lld", (long long)F.nvec,
+                (long long)z0, (long long)z1, (long long)(F.G.nfv * ctx->bs));
   hipStream_t s = ctx->stream;
   ZZZ_HIP(ctx, F.tc.alloc(tc.size()));
   ZZZ_HIP(ctx, F.tf.alloc(tf.size()));
@@ -576,7 +455,7 @@ static int mg_coarsen(zzz_ctx* ctx, MgHier& H, const zzz_solver_opts* os, bool* 
   *more = true;
   if (mg_algebraic(F.kind))
   {
-    C.ndof = ncdof;
+    C.ndof = C.nvec = ncdof;
     // (no block-window product on a level without coordinates; the other forms are packed from the CSR alone)
     c->knob.sellp_bwin = 0;
     if (F.kind == MgKind::AGG)
@@ -590,14 +469,14 @@ static int mg_coarsen(zzz_ctx* ctx, MgHier& H, const zzz_solver_opts* os, bool* 
   // the same problem re-discretised at order 1: on the same cells below the Pk level, on half of them below a P1 level
   for (int a = 0; a < 3; ++a)
     C.n[a] = F.kind == MgKind::PLEVEL ? F.n[a] : std::max<int64_t>(2, (F.n[a] + 1) / 2);
-  C.ndof = (C.n[0] + 1) * (C.n[1] + 1) * (C.n[2] + 1) * ctx->bs;
+  C.ndof = C.nvec = (C.n[0] + 1) * (C.n[1] + 1) * (C.n[2] + 1) * ctx->bs;
   if (int rc = zzz_cube_generate(c, ctx->cube_problem, 1, C.n[0], C.n[1], C.n[2], 1, 0, nullptr))
     return child_fail(ctx, c, rc, l, "generate");
   if (int rc = zzz_csr_pattern_build(c))
     return child_fail(ctx, c, rc, l, "pattern");
   if (c->dofmap.renumbered || c->n_owned * c->bs != C.ndof)
     return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg / pmg, level %d: the generated level is not in lexicographic order", l);
-  return F.kind == MgKind::GEOM ? mg_build_tables(ctx, F, C) : ZZZ_OK;
+  return F.kind == MgKind::GEOM ? mg_build_tables(ctx, F, C, H.slab && l == 1) : ZZZ_OK;
 }
 
 // level C's matrix values (F: the level above it; built: the levels are new)
@@ -628,13 +507,16 @@ static int mg_build(zzz_ctx* ctx, MgHier& H, MgKind kind, const zzz_solver_opts*
   H.lv.emplace_back(new MgLevel());
   MgLevel& L0 = *H.lv[0];
   L0.ctx = ctx;
-  L0.ndof = ctx->n_owned * ctx->bs;
+  L0.ndof = L0.nvec = ctx->n_owned * ctx->bs;
   L0.kind = kind;
   if (!agg) // (to the aggregates the element's order and the cube say nothing)
   {
     L0.order = ctx->dofmap.order;
     for (int a = 0; a < 3; ++a)
       L0.n[a] = ctx->cube_n[a];
+    // (a slab: the level rule counts the dofs of the whole cube, so every rank builds the table the one-rank run builds)
+    if (H.slab)
+      L0.ndof = (L0.n[0] + 1) * (L0.n[1] + 1) * (L0.n[2] + 1) * ctx->bs;
   }
   for (bool more = true; more;)
   {
@@ -646,10 +528,40 @@ static int mg_build(zzz_ctx* ctx, MgHier& H, MgKind kind, const zzz_solver_opts*
       return rc;
   }
   const int64_t dofs = H.lv.back()->ndof;
+  if (H.slab && H.lv.size() == 1)
+    return fail(ctx, ZZZ_ERR_ARG, "-pc_type mg: the whole cube (%lld dofs) is a hierarchy of one level, a dense solve of a matrix that no "
+                                  "rank of a partition holds: use one rank, or a lower pc_mg_coarse_eq_limit", (long long)dofs);
   if (dofs > MG_DENSE_MAX)
     return fail(ctx, ZZZ_ERR_ARG, "-pc_type %s: the coarsest of %d levels has %lld dofs, the dense solve takes at most %lld: "
                                   "allow more levels (pc_mg_levels) or a lower pc_mg_coarse_eq_limit",
                 kind == MgKind::SAGG_RBM ? "sagg_rbm" : kind == MgKind::SAGG ? "sagg" : agg ? "agg" : "mg", (int)H.lv.size(), (long long)dofs, (long long)MG_DENSE_MAX);
+  return ZZZ_OK;
+}
+
+// Several ranks: no rank goes on while another has failed.  Every rank that passed mg_check (whose refusals depend on what
+// all ranks share) comes here with its status at the same places of the set-up -- behind the levels, which no collective
+// builds, and behind the values -- and leaves with the ranks' common one.  One double through the all-reduce of the CG scalars.
+static int mg_agree(zzz_ctx* ctx, int rc, const char* what)
+{
+  if (!ctx->comm)
+    return rc;
+  const std::string mine = ctx->err;
+  double st = rc ? 1.0 : 0.0;
+  int rc2 = comm_inproc_meet(ctx);
+  if (!rc2)
+    rc2 = comm_allgather_max(ctx, &st);
+  if (rc)
+  {
+    ctx->err = mine;
+    return rc;
+  }
+  if (rc2)
+    return rc2;
+  if (st != 0.0)
+  {
+    mg_invalidate(ctx);
+    return fail(ctx, ZZZ_ERR_RCCL, "-pc_type mg: another rank failed in the set-up (%s); this rank's hierarchy is dropped with it", what);
+  }
   return ZZZ_OK;
 }
 
@@ -663,7 +575,7 @@ int mg_setup(zzz_ctx* ctx, const zzz_solver_opts* o)
   const int limit = o->pc_mg_coarse_eq_limit > 0 ? o->pc_mg_coarse_eq_limit : 1000;
   const int max_levels = o->pc_mg_levels > 0 ? std::min<int>(o->pc_mg_levels, MG_MAX_LEVELS) : MG_MAX_LEVELS;
   const MgStructKey skey{ctx->feed_version, agg ? ctx->pattern_version : 0, agg ? ctx->bc_version : 0, o->pc_mg_levels, limit, kind,
-                         mg_smoothed(kind) ? ctx->mg_products : 0};
+                         mg_smoothed(kind) ? ctx->mg_products : 0, ctx->comm ? ctx->cube_nparts : 1, ctx->comm ? ctx->cube_part : 0};
   const MgValuesKey vkey{ctx->mat_version, o->pc_degree > 0 ? o->pc_degree : 2, o->pc_ratio > 1.0 ? o->pc_ratio : 10.0,
                          o->pc_esteig_its == 0 ? 10 : o->pc_esteig_its};
   // the options of the levels' spectrum estimates and smoothers
@@ -676,13 +588,16 @@ int mg_setup(zzz_ctx* ctx, const zzz_solver_opts* o)
   MgHier* H = ctx->mg;
   bool built = false;
   const auto t_begin = std::chrono::steady_clock::now();
-  if (!H || !H->ready || !(H->skey == skey))
-  {
+  // (the two halves of the set-up as functions of their own: with a communicator the ranks agree on the status of each, mg_agree)
+  auto levels = [&]() -> int {
+    if (H && H->ready && H->skey == skey)
+      return ZZZ_OK;
     // ---- the levels --------------------------------------------------------------------------
     mg_destroy(ctx);
     size_t free0 = 0, free1 = 0, total = 0;
     ZZZ_HIP(ctx, hipMemGetInfo(&free0, &total));
     H = ctx->mg = new MgHier();
+    H->slab = ctx->comm != nullptr; // (mg_check: ZZZ_PC_MG on two ranks or more)
     if (int rc = mg_build(ctx, *H, kind, &os, limit, max_levels))
     {
       mg_destroy(ctx);
@@ -700,9 +615,17 @@ int mg_setup(zzz_ctx* ctx, const zzz_solver_opts* o)
     H->coarse_bytes = free0 > free1 ? (double)(free0 - free1) : 0.0; // (set-up scratch of the levels included; level 0's smoother vectors too)
     H->skey = skey; // (H->vkey: of no matrix yet)
     built = true;
-  }
-  if (!(H->vkey == vkey))
+    return ZZZ_OK;
+  };
+  if (int rc = mg_agree(ctx, levels(), "the levels"))
   {
+    mg_destroy(ctx);
+    return rc;
+  }
+  H = ctx->mg;
+  auto values_of_levels = [&]() -> int {
+    if (H->vkey == vkey)
+      return ZZZ_OK;
     // (SAGG: the bounds are part of the prolongator, so another estimate is other values)
     const bool values = H->vkey.mat_version != vkey.mat_version || (mg_smoothed(kind) && H->vkey.est_its != vkey.est_its);
     H->ready = false;
@@ -729,6 +652,21 @@ int mg_setup(zzz_ctx* ctx, const zzz_solver_opts* o)
     H->ready = true;
     ZZZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
     H->setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    return ZZZ_OK;
+  };
+  if (int rc = mg_agree(ctx, values_of_levels(), "the levels' values"))
+    return rc;
+  // (a slab: the nonzeros of the whole cube's matrix for zzz_mg_info -- the owned rows of the ranks together; collective)
+  if (H->slab)
+  {
+    int nranks = 1;
+    comm_rank_of(ctx, &nranks);
+    std::vector<double> all((size_t)nranks, 0.0);
+    if (int rc = comm_allgather_double(ctx, (double)ctx->nnz, all.data()))
+      return rc;
+    H->nnz0 = 0.0;
+    for (double v : all)
+      H->nnz0 += v;
   }
   // the estimates above ran Jacobi solves through the levels' vectors: the inverse diagonals as the cycle reads them
   for (size_t l = 0; l + 1 < H->lv.size(); ++l)
@@ -761,7 +699,16 @@ static int mg_restrict(zzz_ctx* ctx, const int* stop, MgLevel& F, MgLevel& C, co
   else
     hipLaunchKernelGGL(k_mg_restrict<1>, dim3(g), dim3(VB), 0, ctx->stream, stop, F.G, F.tc.p, F.tf.p, F.rng.p, F.ctx->bc.p, C.ctx->bc.p,
                        rf, sub, rc);
-  return ZZZ_OK;
+  if (!F.slab)
+    return ZZZ_OK;
+  // a slab's window: the coarse planes it cannot reach are zero, and the ranks' partial sums are added by the communicator, in its
+  // order (issued whatever the stop flag says: the ranks stay in step)
+  const size_t plane = (size_t)F.G.pc[0] * F.G.pc[1] * ctx->bs, below = (size_t)F.G.cz0 * plane, upto = ((size_t)F.G.cz1 + 1) * plane;
+  if (below)
+    ZZZ_HIP(ctx, hipMemsetAsync(rc, 0, below * sizeof(double), ctx->stream));
+  if (upto < (size_t)C.ndof)
+    ZZZ_HIP(ctx, hipMemsetAsync(rc + upto, 0, ((size_t)C.ndof - upto) * sizeof(double), ctx->stream));
+  return comm_allreduce_sum(ctx, rc, (int)C.ndof);
 }
 static int mg_prolong(zzz_ctx* ctx, const int* stop, MgLevel& F, MgLevel& C, const double* ec, double* xf, int accumulate)
 {
@@ -800,7 +747,7 @@ static int mg_cycle_level(zzz_ctx* ctx, const int* stop, MgHier& H, size_t l, co
   if (int rc = cheb_terms(c, ctx, L.cheb, b, x))
     return rc;
   // coarse correction: r_c = P~^T (b - A x), e_c = M_c r_c, x += P~ e_c
-  if (int rc = launch_spmv(c, x, t, nullptr, nullptr))
+  if (int rc = launch_product(c, x, t, nullptr, nullptr)) // (level 0 of a slab exchanges the halo of x; else launch_spmv)
     return rc;
   if (int rc = mg_restrict(ctx, stop, L, C, b, t, C.ctx->b.p))
     return rc;
@@ -809,7 +756,7 @@ static int mg_cycle_level(zzz_ctx* ctx, const int* stop, MgHier& H, size_t l, co
   if (int rc = mg_prolong(ctx, stop, L, C, C.ctx->u.p, x, 1))
     return rc;
   // post-smoother from x: the same polynomial
-  if (int rc = launch_spmv(c, x, t, nullptr, nullptr))
+  if (int rc = launch_product(c, x, t, nullptr, nullptr))
     return rc;
   cheb_first(c, ctx, L.cheb, b, t, x);
   return cheb_terms(c, ctx, L.cheb, b, x);
@@ -920,7 +867,7 @@ int zzz_mg_info(zzz_ctx* ctx, int level, double out[8])
   if (L.kind == MgKind::SAGG_RBM && level > 0) // (no cube: ny's slot holds the dropped coarse dofs among this level's)
     out[1] = (double)srbm_dropped(H->lv[(size_t)level - 1]->sagg);
   out[3] = (double)L.ndof;
-  out[4] = (double)L.ctx->nnz;
+  out[4] = level == 0 && H->slab ? H->nnz0 : (double)L.ctx->nnz; // (a slab: the whole cube's, as its cells and dofs are)
   const bool smooths = (size_t)level + 1 < H->lv.size();
   out[5] = smooths ? L.cheb.hi : 0.0;
   out[6] = smooths ? L.cheb.lo : 0.0;
@@ -1010,7 +957,7 @@ int zzz_mg_transfer(zzz_ctx* ctx, int level, int dir, const double* in, double* 
     return fail(ctx, ZZZ_ERR_ARG, "zzz_mg_transfer: level %d of %d (the coarsest has no transfer below it), dir %d, or NULL vector",
                 level, (int)H->lv.size(), dir);
   MgLevel &F = *H->lv[(size_t)level], &C = *H->lv[(size_t)level + 1];
-  const size_t nin = (size_t)(dir == 0 ? C.ndof : F.ndof), nout = (size_t)(dir == 0 ? F.ndof : C.ndof);
+  const size_t nin = (size_t)(dir == 0 ? C.nvec : F.nvec), nout = (size_t)(dir == 0 ? F.nvec : C.nvec);
   hipStream_t s = ctx->stream;
   ZZZ_HIP(ctx, H->tx_in.reserve(nin));
   ZZZ_HIP(ctx, H->tx_out.reserve(nout));

@@ -840,6 +840,8 @@ void solve(int argc, char** argv)
     // what ZZZ_PC_MG / ZZZ_PC_PMG decline (include/zzz_abi.h), said here before any GPU work
     const char* why = o.order != 1 && o.pc_type == "mg"     ? "--order 1 only (p-coarsening for P2 / P3 is -pc_type pmg)"
                       : o.mesh_type != "cube"               ? "--mesh_type cube only (the levels are coarser cubes)"
+                      : o.ngpus != 1 && o.pc_type == "mg"   ? "--ngpus 1 only in this driver (the library serves ZZZ_PC_MG on the z-slabs of "
+                                                              "several ranks, include/zzz_abi.h; the driver does not pass it on yet)"
                       : o.ngpus != 1                        ? "--ngpus 1 only (multi-rank multigrid is not built)"
                       : o.problem_type == "cgpoisson"       ? "poisson or elasticity (cgpoisson runs linalg::cg, which has no preconditioner)"
                       : o.op == "matfree"                   ? "--operator assembled only"

@@ -661,9 +661,12 @@ class Context:
         return z
 
     def mg_transfer(self, level, direction, v):
-        """direction 0: P~ v (level + 1 -> level); 1: P~^T v"""
+        """direction 0: P~ v (level + 1 -> level); 1: P~^T v.  ZZZ_PC_MG on several ranks (collective at level 0): level 0's side is
+        this rank's owned vector, level 1's the whole coarse vector -- the restriction's result is the ranks' sum"""
         v = np.ascontiguousarray(v, np.float64)
         a, b = self.mg_info(level)["dofs"], self.mg_info(level + 1)["dofs"]
+        if level == 0 and self.n_owned:
+            a = self.n_owned * self.bs  # (mg_info(0) reports the whole cube on every rank)
         assert v.shape[0] == (b if direction == 0 else a)
         out = np.zeros(a if direction == 0 else b)
         self._ck(self.L.zzz_mg_transfer(self.h, level, direction, v, out))
